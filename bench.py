@@ -8,15 +8,20 @@ One "step" = one K-iteration propagation H <- (1-a) A_hat H + a H0 (K = 10; refe
 synthetic graph, through the C ABI of libgnx.so.  The workload is the SAME global graph for every N (strong scaling):
 BASELINE.json configs[4] -- RMAT 80M vertices / 1B stored entries, 128 float32 features -- on pv = N contiguous vertex blocks with
 a pairwise RCCL exchange of pulled rows / pushed partial sums per iteration (bench_sharded.py, gnntf.sharded).  N = 1 is that graph
-on one GPU (it fits: ~131 GB) and additionally times, in the same run, BASELINE.json configs[3] (the roofline run, RMAT 10M / 100M,
-C = 256), other widths, config 3's arxiv-shaped GCN forward and training steps (bench_secondary.py).  ``--workload config4`` makes
-the roofline run the primary line instead.
+on one GPU (it fits: ~131 GB).  ``--workload config4`` makes BASELINE.json configs[3] (the roofline run, RMAT 10M / 100M, C = 256)
+the primary line instead.
 
-Rank 0 prints ONE JSON line of at most 12 KB (bench_record.fit_line): the contract keys, ``config``, ``roofline`` (headline keys +
-flat config4_* / per-width / train_* scalars) and ``cpu_baseline``.  Everything else -- full records with their notes, the
-secondaries, yardsticks, the variant table -- goes to bench_detail_n<N>.json next to this script (``config.detail_file``).
-ms_per_step / value are the MEDIAN of the per-step event times; the wall clock of the bracketed region is
-reported beside them (wall_ms_per_step).
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs (``--dump-outputs DIR``) and prints the line.
+``--full`` adds everything else, each in the same run: the in-run counter passes (bench_pmc.py), the fixed-point self check, the
+bare exchange and kernels (N > 1), the second field (N > 1), the stream yardsticks and the roofline record, the CPU baselines
+(bench_cpu.py), the no-reuse gather yardstick, and at N = 1 the other widths, config 3's arxiv-shaped GCN forward and the training
+steps (bench_secondary.py).
+
+Rank 0 prints ONE JSON line of at most 12 KB (bench_record.fit_line): the contract keys, ``config``, and with ``--full``
+``roofline`` (headline keys + flat config4_* / per-width / train_* scalars) and ``cpu_baseline``.  Everything else of a ``--full``
+run -- full records with their notes, the secondaries, yardsticks, the variant table -- goes to bench_detail_n<N>.json next to this
+script (``config.detail_file``).  ms_per_step / value are the MEDIAN of the per-step event times; the wall clock
+of the bracketed region is reported beside them (wall_ms_per_step).
 
 Files: bench_record.py (byte models, roofline record, the line), bench_device.py (graph, timing), bench_pmc.py (in-run counter
 passes), bench_secondary.py, bench_sharded.py (N > 1), bench_cpu.py (cpu_baseline).
@@ -38,6 +43,7 @@ from bench_pmc import fabric_bytes_by_segment, fabric_bytes_per_launch, measure_
 
 PUSH_WEIGHTS_DEFAULT = "0.5"        # weighted covers the N > 1 selection times after "cover" and "pull" (under EMULATED
                                     # link time w = 0 wins at every rate; one intermediate weight is timed anyway, inside the selection's budget)
+DUMP_BYTES = 32 << 20               # --dump-outputs: the sampled rows of the last step's result (well inside the 64 MB an output set may take)
 
 
 def parse(argv=None):
@@ -79,7 +85,18 @@ def parse(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the cpu_baseline sample (0 = skip)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads of the N = 1 line")
     ap.add_argument("--no-alt-grid", action="store_true", help="N > 1: skip the second field (the same graph on feature slices, no exchange)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: counter passes, self check, yardsticks and roofline, CPU baselines, secondaries, the second "
+                         "field and the detail file (--pmc-in-run, --gather-yardstick, --cpu-seconds, --no-secondary and --no-alt-grid "
+                         "act only with it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned to DIR/*.npy (float32; a fixed, seeded sample of "
+                         "at most %d MB of its rows) -- one GPU only" % (DUMP_BYTES >> 20))
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.gpus > 1 or args.force_sharded):
+        ap.error("--dump-outputs: the single-GPU path only (--gpus 1, no --force-sharded)")
     kind, _, weight = args.cover.partition("@")
     if kind not in ("auto", "cover", "pull") or (weight and (kind != "cover" or float(weight) < 0)):
         ap.error("--cover: auto, cover, cover@W (W >= 0) or pull")
@@ -108,7 +125,7 @@ def relaunch_under_torchrun(args):
 
 def pmc_passes(args):
     """The in-run counter passes (N = 1, before this process touches the GPU; never from inside a profiler run)."""
-    if not (args.gpus == 1 and args.pmc_in_run == "on" and not args.pmc_child and not args.force_sharded and args.workload in WORKLOADS
+    if not (args.full and args.gpus == 1 and args.pmc_in_run == "on" and not args.pmc_child and not args.force_sharded and args.workload in WORKLOADS
             and os.environ.get("GNX_BENCH_PMC", "1") != "0" and not any(k.startswith("ROCPROF") for k in os.environ)
             and "rocprof" not in os.environ.get("LD_PRELOAD", "")):
         return None
@@ -183,6 +200,22 @@ def single_gpu_checks(args, device, s, step_ms):
     err = max_relative_deviation(s.iters[-1].value, E0)
     s.iters[-1].value, s.pre.value = None, s.H0
     return err
+
+
+def dump_outputs(directory, H):
+    """--dump-outputs: H, what the last timed step returned to its caller, as float32 -- every row when they fit in DUMP_BYTES, else
+    a sorted sample of rows drawn with a fixed seed -- and the numbers of those rows (float64, exact), so that two builds of the
+    project can be compared output for output."""
+    import numpy as np
+    import torch
+    n, C = H.shape
+    rows = min(n, max(1, DUMP_BYTES // (4 * C)))
+    idx = np.arange(n) if rows == n else np.sort(np.random.default_rng(0).choice(n, size=rows, replace=False))
+    sample = H.index_select(0, torch.from_numpy(idx).to(H.device)).to(torch.float32).cpu().numpy()
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "propagated.npy"), sample)
+    np.save(os.path.join(directory, "propagated_rows.npy"), idx.astype(np.float64))
+    note(f"outputs written to {directory}: {rows} of {n} rows x {C} features")
 
 
 def main():
@@ -262,7 +295,11 @@ def main():
         elapsed, step_ms = float(t[0].item()), [float(x) for x in t[1:].tolist()]
     stats = br.step_statistics(step_ms)
     note(f"steps done: median {stats['median']:.1f} ms per step (min {stats['min']:.1f}, max {stats['max']:.1f}; wall {elapsed / args.steps * 1e3:.1f})")
-    if sharded_path and world > 1:                   # measured, per iteration: the bare exchange and the bare kernels (collective calls)
+    if args.dump_outputs:                            # (parse(): one GPU only) before the checks below overwrite the layers' values
+        t_ph = time.time()
+        dump_outputs(args.dump_outputs, s.iters[-1].value)
+        phase("dump_outputs", t_ph)
+    if args.full and sharded_path and world > 1:     # measured, per iteration: the bare exchange and the bare kernels (collective calls)
         t_ph = time.time()
         t_x, t_c = s.sg.time_exchange(s.state), s.sg.time_compute(s.state, a)
         phase("exchange_and_kernels_alone", t_ph)
@@ -273,26 +310,28 @@ def main():
                     pull_only_bytes_per_rank_per_iteration=halo["max_pull_only_rows"] * C_local * 4)
         note(f"exchange alone {halo['exchange_ms_alone']:.2f} ms, kernels alone {halo['compute_ms_alone']:.2f} ms per iteration")
 
-    # in-run parity evidence: sqrt(degree) x s is a fixed point of the propagation on a symmetric graph -- more iterations through
-    # the very path that was timed (for N > 1: the plan, the kernels AND the RCCL exchange) must reproduce it.  Behind schedule
-    # (--max-seconds) the N > 1 check runs 2 iterations instead of K: every exchange direction and kernel is still exercised.
-    note("self check: fixed point of the propagation")
-    t_ph = time.time()
-    check_iterations = K
-    if sharded_path:
-        if not everyone(deadline.left() > 3.0 * stats["median"] * 1e-3 + 30.0):
-            check_iterations = min(K, 2)
-            deadline.dropped.append(f"self check shortened to {check_iterations} iterations")
-        check_err = s.sg.fixed_point_error(s.state, a, check_iterations)
-    else:
-        check_err = single_gpu_checks(args, device, s, step_ms)
-    self_check = {"what": "H0 = sqrt(degree) x s_c is a fixed point of H <- (1-a) A_hat H + a H0: max rel. deviation through the timed path",
-                  "iterations": check_iterations, "max_rel_err": check_err, "ok": bool(check_err < 1e-4)}
-    note(f"self check: {check_err:.2e}")
-    phase("self_check", t_ph)
+    self_check = None
+    if args.full:
+        # in-run parity evidence: sqrt(degree) x s is a fixed point of the propagation on a symmetric graph -- more iterations through
+        # the very path that was timed (for N > 1: the plan, the kernels AND the RCCL exchange) must reproduce it.  Behind schedule
+        # (--max-seconds) the N > 1 check runs 2 iterations instead of K: every exchange direction and kernel is still exercised.
+        note("self check: fixed point of the propagation")
+        t_ph = time.time()
+        check_iterations = K
+        if sharded_path:
+            if not everyone(deadline.left() > 3.0 * stats["median"] * 1e-3 + 30.0):
+                check_iterations = min(K, 2)
+                deadline.dropped.append(f"self check shortened to {check_iterations} iterations")
+            check_err = s.sg.fixed_point_error(s.state, a, check_iterations)
+        else:
+            check_err = single_gpu_checks(args, device, s, step_ms)
+        self_check = {"what": "H0 = sqrt(degree) x s_c is a fixed point of H <- (1-a) A_hat H + a H0: max rel. deviation through the timed path",
+                      "iterations": check_iterations, "max_rel_err": check_err, "ok": bool(check_err < 1e-4)}
+        note(f"self check: {check_err:.2e}")
+        phase("self_check", t_ph)
 
     alt, kernel_blocks = None, (s.sg.graph.last_kernel() if sharded_path else None)
-    if world > 1 and not args.no_alt_grid and not args.grid and C % world == 0:
+    if args.full and world > 1 and not args.no_alt_grid and not args.grid and C % world == 0:
         if everyone(deadline.room(4.0 * prep["gen_s"] + 3.0 * stats["median"] * 1e-3 + 20.0, "second field (feature slices)")):
             note("second field: the whole graph on every rank, C / N columns each")
             t_ph = time.time()
@@ -304,66 +343,66 @@ def main():
             phase("alt_grid_feature_slices", t_ph)
 
     if rank == 0:
-        t_ph = time.time()
-        measured_peak = stream_copy_GBs(device)
-        br.MEASURED_READ_PEAK[0] = stream_read_GBs(device)
-        phase("stream_yardsticks", t_ph)
         name = workload_name(args.nodes, args.entries, C)
-        if not sharded_path:
-            launch_s = stats["median"] / 1e3 / K                     # one fused SpMM+mix launch (+ its long-row tail)
-            roof = roofline_record(n_local, nnz_local, C, launch_s, K, name, measured_peak)
-        else:                                                       # this rank's block: kernels alone (no exchange beside them)
-            t_c = halo["compute_ms_alone"] * 1e-3 if world > 1 else s.sg.time_compute(s.state, a)
-            # (the block's committed PMC passes are per plan: tools/sim_blocks.py --pmc-iterations under rocprofv3, profiles/summarize_blocks.py)
-            block_name = name + f"_block_of_{pv}_{halo['plan']}_chunks{halo['chunks']}"
-            roof = roofline_record(n_local, nnz_local, C_local, t_c, K, block_name, measured_peak,
-                                   what="rank 0's vertex block, one iteration's kernels alone (pack + SpMM of every column chunk; no exchange beside them)")
-        detail = {"roofline": roof, "halo": halo, "pmc_in_run": pmc_notes, "alt_grid_feature_slices": alt, "step_ms": step_ms}
-
-        def optional(what, fn, default=None):
-            """What follows the timed region must never cost the headline its line: a part that fails is recorded and left out."""
-            try:
-                return fn()
-            except Exception as error:
-                deadline.dropped.append(f"{what} failed: {error!r}"[:200])
-                note(f"{what} failed and is left out: {error!r}")
-                torch.cuda.empty_cache()
-                return default
-        cpu = None
-        if not sharded_path and args.cpu_seconds > 0:
-            from bench_cpu import cpu_baseline
-            if deadline.left() < 4.0 * args.cpu_seconds + 120.0:    # behind schedule: a shorter sample rather than none (the contract asks for it)
-                args.cpu_seconds = max(3.0, min(args.cpu_seconds, (deadline.left() - 120.0) / 4.0))
-                deadline.dropped.append(f"cpu_baseline sample shortened to {args.cpu_seconds:.0f} s")
-            note("CPU baselines (C / OpenMP port, scipy on one thread, torch.sparse on all threads; bounded samples)")
+        roof, cpu, detail, flat = None, None, None, {}
+        if args.full:
             t_ph = time.time()
-            g_, adj_, H0_ = s.g, s.adj, s.H0
-            cpu = optional("cpu_baseline", lambda: cpu_baseline(g_, adj_, H0_, args))
-            del g_, adj_, H0_
-            phase("cpu_baseline", t_ph)
-        detail["cpu_baseline"] = cpu
-        flat = {}
+            measured_peak = stream_copy_GBs(device)
+            br.MEASURED_READ_PEAK[0] = stream_read_GBs(device)
+            phase("stream_yardsticks", t_ph)
+            if not sharded_path:
+                launch_s = stats["median"] / 1e3 / K                     # one fused SpMM+mix launch (+ its long-row tail)
+                roof = roofline_record(n_local, nnz_local, C, launch_s, K, name, measured_peak)
+            else:                                                       # this rank's block: kernels alone (no exchange beside them)
+                t_c = halo["compute_ms_alone"] * 1e-3 if world > 1 else s.sg.time_compute(s.state, a)
+                # (the block's committed PMC passes are per plan: tools/sim_blocks.py --pmc-iterations under rocprofv3, profiles/summarize_blocks.py)
+                block_name = name + f"_block_of_{pv}_{halo['plan']}_chunks{halo['chunks']}"
+                roof = roofline_record(n_local, nnz_local, C_local, t_c, K, block_name, measured_peak,
+                                       what="rank 0's vertex block, one iteration's kernels alone (pack + SpMM of every column chunk; no exchange beside them)")
+            detail = {"roofline": roof, "halo": halo, "pmc_in_run": pmc_notes, "alt_grid_feature_slices": alt, "step_ms": step_ms}
+
+            def optional(what, fn, default=None):
+                """What follows the timed region must never cost the headline its line: a part that fails is recorded and left out."""
+                try:
+                    return fn()
+                except Exception as error:
+                    deadline.dropped.append(f"{what} failed: {error!r}"[:200])
+                    note(f"{what} failed and is left out: {error!r}")
+                    torch.cuda.empty_cache()
+                    return default
+            if not sharded_path and args.cpu_seconds > 0:
+                from bench_cpu import cpu_baseline
+                if deadline.left() < 4.0 * args.cpu_seconds + 120.0:    # behind schedule: a shorter sample rather than none (the contract asks for it)
+                    args.cpu_seconds = max(3.0, min(args.cpu_seconds, (deadline.left() - 120.0) / 4.0))
+                    deadline.dropped.append(f"cpu_baseline sample shortened to {args.cpu_seconds:.0f} s")
+                note("CPU baselines (C / OpenMP port, scipy on one thread, torch.sparse on all threads; bounded samples)")
+                t_ph = time.time()
+                g_, adj_, H0_ = s.g, s.adj, s.H0
+                cpu = optional("cpu_baseline", lambda: cpu_baseline(g_, adj_, H0_, args))
+                del g_, adj_, H0_
+                phase("cpu_baseline", t_ph)
+            detail["cpu_baseline"] = cpu
         if not sharded_path:
-            kernel = s.g.last_kernel()
-            for layer in s.model.layers():
-                layer.value = None
-            api = s.api
-            s = None
-            torch.cuda.empty_cache()
-            if args.gather_yardstick == "on" and deadline.room(15.0, "no-reuse gather yardstick of the headline"):
-                from bench_secondary import gather_yardstick
-                note("no-reuse gather yardstick (d-regular random graph of the same N and C)")
-                t_ph = time.time()
-                yard = optional("gather yardstick", lambda: gather_yardstick(device, args.nodes, [C], a)[C])
-                br.add_gather_ceiling(roof, yard)
-                detail["no_reuse_gather_yardstick"] = yard
-                phase("gather_yardstick", t_ph)
-            if not args.no_secondary and deadline.room(40.0, "secondary workloads"):
-                from bench_secondary import secondary_workloads
-                t_ph = time.time()
-                detail["secondary"], flat = optional("secondary workloads", lambda: secondary_workloads(
-                    args, device, measured_peak, skip_config4=args.workload == "config4", deadline=deadline), default=({}, {}))
-                phase("secondary_workloads", t_ph)
+            kernel, api = s.g.last_kernel(), s.api
+            if args.full:
+                for layer in s.model.layers():
+                    layer.value = None
+                s = None
+                torch.cuda.empty_cache()
+                if args.gather_yardstick == "on" and deadline.room(15.0, "no-reuse gather yardstick of the headline"):
+                    from bench_secondary import gather_yardstick
+                    note("no-reuse gather yardstick (d-regular random graph of the same N and C)")
+                    t_ph = time.time()
+                    yard = optional("gather yardstick", lambda: gather_yardstick(device, args.nodes, [C], a)[C])
+                    br.add_gather_ceiling(roof, yard)
+                    detail["no_reuse_gather_yardstick"] = yard
+                    phase("gather_yardstick", t_ph)
+                if not args.no_secondary and deadline.room(40.0, "secondary workloads"):
+                    from bench_secondary import secondary_workloads
+                    t_ph = time.time()
+                    detail["secondary"], flat = optional("secondary workloads", lambda: secondary_workloads(
+                        args, device, measured_peak, skip_config4=args.workload == "config4", deadline=deadline), default=({}, {}))
+                    phase("secondary_workloads", t_ph)
         else:
             kernel, api = kernel_blocks, None
         br.PHASES["total"] = round(time.time() - br.T_START, 2)
@@ -383,16 +422,17 @@ def main():
                        "alt_grid_feature_slices": alt, "self_check": self_check, "phases_s": br.PHASES,
                        "pmc_in_run": ({k: ("in run" if v == "measured in this run" else v) for k, v in pmc_notes.items()} if pmc_notes else None),
                        "dropped": deadline.dropped, "detail_file": None},
-            "roofline": dict(br.line_roofline(roof), **flat),
+            "roofline": dict(br.line_roofline(roof), **flat) if roof else None,
             "cpu_baseline": br.line_cpu_baseline(cpu),
         }
-        detail["line"] = result
-        result["config"]["detail_file"] = br.write_detail(detail, world)
+        if detail is not None:
+            detail["line"] = result
+            result["config"]["detail_file"] = br.write_detail(detail, world)
         os.write(json_fd, (br.fit_line(result) + "\n").encode())
     if sharded_path:
         dist.barrier()
         dist.destroy_process_group()
-    if not self_check["ok"]:                       # (check_err is all-reduced: every rank leaves the same way)
+    if self_check and not self_check["ok"]:        # (check_err is all-reduced: every rank leaves the same way)
         raise SystemExit(3)
 
 

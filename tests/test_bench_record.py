@@ -386,3 +386,27 @@ def test_deadline_drops_optional_parts_and_says_so():
     now[0] = 70.0
     assert not d.room(40.0, "second field") and d.room(20.0, "b")
     assert len(d.dropped) == 1 and d.dropped[0].startswith("second field (needs ~40 s, 30 s left)")
+
+
+def test_plain_run_by_default_and_dumped_outputs(tmp_path, monkeypatch):
+    """A plain run does only the headline (--full adds the rest); --dump-outputs writes the last step's rows, a fixed seeded sample
+    of them once they exceed DUMP_BYTES, as float32 beside their row numbers; two dumps of the same result are identical."""
+    import numpy as np
+    import torch
+    assert not bench.parse([]).full and bench.parse(["--full"]).full and bench.parse([]).dump_outputs is None
+    for bad in (["--steps", "0"], ["--gpus", "2", "--dump-outputs", "d"], ["--force-sharded", "--dump-outputs", "d"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+    H = torch.randn(1000, 7, generator=torch.Generator().manual_seed(0)).double()
+    bench.dump_outputs(str(tmp_path / "all"), H)
+    assert np.array_equal(np.load(tmp_path / "all" / "propagated.npy"), H.float().numpy())
+    assert np.array_equal(np.load(tmp_path / "all" / "propagated_rows.npy"), np.arange(1000, dtype=np.float64))
+    monkeypatch.setattr(bench, "DUMP_BYTES", 100 * 7 * 4)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), H)
+    rows = np.load(tmp_path / "a" / "propagated_rows.npy")
+    sample = np.load(tmp_path / "a" / "propagated.npy")
+    assert sample.dtype == np.float32 and sample.shape == (100, 7) and rows.dtype == np.float64
+    assert len(np.unique(rows)) == 100 and (np.diff(rows) > 0).all()
+    assert np.array_equal(sample, H.float().numpy()[rows.astype(np.int64)])
+    assert all(np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)) for f in ("propagated.npy", "propagated_rows.npy"))

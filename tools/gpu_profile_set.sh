@@ -20,7 +20,7 @@ profile_one() {      # TAG [bench args]: the three passes of one bench command (
 profile_full() {     # TAG: kernel stats of the full default bench run (primary workload + yardsticks + secondary block)
   local OUT=gpurun_out/$1
   mkdir -p $OUT
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- python3 bench.py --steps 3 --warmup 1 --cpu-seconds 0 --pmc-in-run off \
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- python3 bench.py --steps 3 --warmup 1 --full --cpu-seconds 0 --pmc-in-run off \
       > $OUT/bench_under_rocprof.json 2> $OUT/stats.err || return 1
   rm -f $OUT/stats/run_kernel_trace.csv
 }
