@@ -41,7 +41,7 @@ class Structural(Layer):
 class GNN(Trainable):
     """gnn.py:29-50."""
 
-    def __init__(self, graph, features, preprocessor: Layer = None, reorder=None):
+    def __init__(self, graph, features, preprocessor: Layer = None, reorder=None, inference_dtype=torch.float32):
         """``reorder`` (opt-in, not in the reference): store the graph and the feature rows with the vertices relabelled; every
         [N, .] tensor inside the model then lives in that order, and the model's OUTPUT is put back into the caller's order, so
         tasks, labels and node ids are unaffected.  Results agree with the unordered model to float32 rounding.
@@ -53,8 +53,16 @@ class GNN(Trainable):
         vertices.  On a graph without communities (R-MAT) the order finds none (``locality_share`` fails
         ordering.found_communities) and the model keeps the default order (``reorder_used`` is then None); so do graphs of
         a few windows, which fit the caches in any order.
-        Measurements: profiles/NOTES.md round 5."""
+        Measurements: profiles/NOTES.md round 5.
+        ``inference_dtype=torch.bfloat16`` (opt-in, not in the reference): eval-mode forwards without autograd (``predict()``, the
+        validation forwards inside ``train()``) gather the propagated features as bf16 with f32 sums (sparse.appnp_propagate /
+        sparse.spmm ``storage``); every forward with grad enabled -- every training step -- runs the f32 path unchanged.  Error:
+        the APPNP loop is within (2^-8 / a) max_k ||H_k||_2 per column of the f32 result (first order), a GCN SpMM within
+        2^-8 |A| |X| elementwise."""
+        if inference_dtype not in (torch.float32, torch.bfloat16):
+            raise Exception("GNN: inference_dtype must be torch.float32 or torch.bfloat16")
         super().__init__(features)
+        self.inference_dtype = inference_dtype
         self._order = self._newid = None
         self.reorder_used, self.locality_share = None, None
         if isinstance(graph, sparse.DeviceGraph):
@@ -119,6 +127,13 @@ class GNN(Trainable):
         return self._adjacency_cache[key]
 
 
+def _eval_storage(architecture) -> torch.dtype:
+    """The feature storage of a propagation: GNN.inference_dtype in an eval-mode forward without autograd, else float32."""
+    if torch.is_grad_enabled() or not isinstance(architecture, GNN) or architecture.is_training():
+        return torch.float32
+    return architecture.inference_dtype
+
+
 def _propagation_run(architecture: "GNN", H0_value, a, iterations, graph_dropout, with_relu=False):
     """``iterations`` PPR steps from H0 through the fused loop (what PPRLoop and a run of plain PPRIteration layers execute).
     ``with_relu``: relu after every step (the reference's ``activation`` argument, filter.py:22,28,35), in the kernels' epilogue.
@@ -148,7 +163,8 @@ def _propagation_run(architecture: "GNN", H0_value, a, iterations, graph_dropout
         adj = architecture.get_adjacency(graph_dropout)
         make_adj = lambda k, bwd=False: adj
     if not torch.is_grad_enabled() and not training:
-        run = lambda k: sparse.appnp_propagate(make_adj(0, False), H0_value, a, k, relu=with_relu)
+        storage = _eval_storage(architecture)
+        run = lambda k: sparse.appnp_propagate(make_adj(0, False), H0_value, a, k, relu=with_relu, storage=storage)
     else:
         run = lambda k: sparse.ppr_loop(make_adj, H0_value, a, k, relu=with_relu)
     return run(iterations), run, (make_adj if cheap else None)
@@ -294,12 +310,13 @@ class GCNLayer(Layer):
         if self.transform_first:
             bias = self.b if isinstance(self.b, torch.Tensor) else None
             projected = affine(features, self.W, 0)
+            storage = _eval_storage(gcn)
             if self.activation is relu or self.activation is linear:
-                out = sparse.spmm_bias_act(adjacency, projected, bias, relu=self.activation is relu)
+                out = sparse.spmm_bias_act(adjacency, projected, bias, relu=self.activation is relu, storage=storage)
             else:
-                out = self.activation(sparse.spmm_bias_act(adjacency, projected, bias))
+                out = self.activation(sparse.spmm_bias_act(adjacency, projected, bias, storage=storage))
             return gcn.dropout(out, self.dropout)
-        aggregated_features = sparse.spmm(adjacency, features)
+        aggregated_features = sparse.spmm(adjacency, features, storage=_eval_storage(gcn))
         return gcn.dropout(affine(aggregated_features, self.W, self.b, self.activation), self.dropout)
 
 

@@ -424,9 +424,11 @@ PAD_WIDTHS = True      # tools flip this for A/B runs
 PAD_MIN_ROWS = 1 << 16      # smaller graphs are launch-bound: the pad / slice launches would cost more than the loads save
 
 
-def lines_per_row(C: int) -> float:
-    """Average number of 128-byte lines a row of C floats touches when rows are stored back to back (row r starts at byte 4 C r)."""
-    size, step = 4 * C, math.gcd(4 * C, 128)
+def lines_per_row(C: int, elem_bytes: int = 4) -> float:
+    """Average number of 128-byte lines a row of C floats (``elem_bytes`` = 2: bf16) touches when rows are stored back to back (row r
+    starts at byte elem_bytes C r)."""
+    size = elem_bytes * C
+    step = math.gcd(size, 128)
     offsets = range(0, 128, step)
     return sum((off + size + 127) // 128 for off in offsets) / len(offsets)
 
@@ -447,6 +449,23 @@ def friendly_width(C: int, n_rows: int = PAD_MIN_ROWS) -> int:
     best = Cp
     for wider in range(Cp + 4, (Cp + 31) // 32 * 32 + 1, 4):
         if lines_per_row(wider) < lines_per_row(best) - 1e-9:
+            best = wider
+    return best
+
+
+def friendly_width_bf16(C: int, n_rows: int = PAD_MIN_ROWS) -> int:
+    """friendly_width for bf16 rows (2-byte elements, 8 per 16-byte lane load): rows of 7 ... 63 elements are padded to the next
+    power of two (C = 40: 80-byte rows, half of which span two lines, become one 128-byte line), wider ones to the next multiple of
+    8 and on to the first multiple of 8 up to the next multiple of 64 at which a row touches no more lines than its size needs.
+    The pad columns are zero and stay zero."""
+    if not PAD_WIDTHS or C <= 6 or n_rows < PAD_MIN_ROWS:
+        return C
+    if C <= 64:
+        return 1 << (C - 1).bit_length()
+    Cp = (C + 7) // 8 * 8
+    best = Cp
+    for wider in range(Cp + 8, (Cp + 63) // 64 * 64 + 1, 8):
+        if lines_per_row(wider, 2) < lines_per_row(best, 2) - 1e-9:
             best = wider
     return best
 
@@ -580,13 +599,24 @@ class _SpMMBiasAct(torch.autograd.Function):
         return gY, gb, None, None
 
 
-def spmm_bias_act(adj: Adjacency, Y: torch.Tensor, bias=None, relu=False) -> torch.Tensor:
-    """act(A . Y + bias) fused; ``bias`` is [1, C] or None."""
+def spmm_bias_act(adj: Adjacency, Y: torch.Tensor, bias=None, relu=False, storage=torch.float32) -> torch.Tensor:
+    """act(A . Y + bias) fused; ``bias`` is [1, C] or None.  ``storage=torch.bfloat16``: Y gathered as bf16 (inference only; the
+    error bound of ``spmm``)."""
+    if _bf16(storage):
+        _no_grad_for_bf16("spmm_bias_act", Y, bias)
+        return _launch_bf16(adj, Y, bias, 1.0, 1.0, nat.ACT_RELU if relu else nat.ACT_NONE)
     return _SpMMBiasAct.apply(Y, bias, adj, bool(relu))
 
 
-def spmm(adj: Adjacency, X: torch.Tensor) -> torch.Tensor:
-    """Drop-in for tf.sparse.sparse_dense_matmul(adj, X); differentiable w.r.t. X."""
+def spmm(adj: Adjacency, X: torch.Tensor, storage=torch.float32) -> torch.Tensor:
+    """Drop-in for tf.sparse.sparse_dense_matmul(adj, X); differentiable w.r.t. X.
+    ``storage=torch.bfloat16`` (inference only: raises where autograd would need a gradient): X is gathered as bf16 -- a bf16 X as
+    it is, an f32 X rounded once (gnx_cast_bf16) -- and summed in f32 (gnx_spmm_bf16); the f32 result is the exact sum over the
+    rounded rows, i.e. |out - A.X| <= u |A| |X| elementwise (u = 2^-8) plus f32 rounding.  The default keeps the f32 path (a bf16
+    X is widened to f32 there)."""
+    if _bf16(storage):
+        _no_grad_for_bf16("spmm", X)
+        return _launch_bf16(adj, X, None, 1.0, 0.0, nat.ACT_NONE)
     return _SpMM.apply(X, adj)
 
 
@@ -598,16 +628,24 @@ def ppr_step(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a) -> torch.Tens
     return _PPRStep.apply(H, H0, adj, float(a))
 
 
-def appnp_propagate(adj: Adjacency, H0: torch.Tensor, a: float = 0.1, iterations: int = 10, relu: bool = False) -> torch.Tensor:
+def appnp_propagate(adj: Adjacency, H0: torch.Tensor, a: float = 0.1, iterations: int = 10, relu: bool = False,
+                    storage=torch.float32) -> torch.Tensor:
     """The eval-mode K-iteration loop as ONE library call with two ping-pong buffers
     (no autograd, no per-layer .value caching) -- the measured hot path.  ``relu``: the reference's per-iteration activation
-    (filter.py:22,28,35) in every iteration's epilogue (gnx_appnp_propagate_act)."""
+    (filter.py:22,28,35) in every iteration's epilogue (gnx_appnp_propagate_act).
+    ``storage=torch.bfloat16``: the iterate is kept as bf16 between iterations (gnx_appnp_propagate_bf16): every gather moves half
+    the bytes; sums, H0 and the mix stay f32 and the result is f32.  Error bound (u = 2^-8, symmetric normalisation of a
+    symmetric pattern, no diagonal): per column ||H_bf16 - H_f32||_2 <= (u / a) max_k ||H_k||_2 to first order.  bf16 is an
+    allowance: the library may keep f32 where bf16 does not pay (narrow widths on large graphs: BF16_MIN_WIDTH); the bound holds
+    either way."""
     g = adj.graph
     nat.require_cuda(H0)
     H0 = _as_f32_rows(H0).contiguous()
     if g.n_rows != g.n_cols or H0.shape[0] != g.n_rows:
         raise Exception("appnp_propagate: needs a square graph matching H0")
     C = H0.shape[1]
+    if _bf16(storage) and not (C < BF16_MIN_WIDTH and g.n_rows >= BF16_F32_ROWS):
+        return _appnp_propagate_bf16(adj, H0, a, iterations, relu)
     H0 = _padded(H0, friendly_width(C, H0.shape[0]))
     out = torch.empty_like(H0)
     work = torch.empty_like(H0) if iterations > 1 else None
@@ -615,6 +653,85 @@ def appnp_propagate(adj: Adjacency, H0: torch.Tensor, a: float = 0.1, iterations
         nat.check(nat.lib().gnx_appnp_propagate_act(g.handle, nat.ptr(adj.vals), nat.ptr(adj.diag), nat.ptr(H0), float(a),
                                                     int(iterations), H0.shape[1], nat.ACT_RELU if relu else nat.ACT_NONE,
                                                     nat.ptr(out), nat.ptr(work), nat.current_stream()))
+    return out if out.shape[1] == C else out[:, :C].contiguous()
+
+
+# ---- opt-in bf16 feature storage (inference only) ----------------------------------------------------------------------------
+# bf16 is an allowance: appnp_propagate keeps f32 below BF16_MIN_WIDTH on graphs of at least BF16_F32_ROWS vertices -- there every
+# gather is one 128-byte line whatever the element size and the f32 loop runs on the degree-relabelled copy (gnx_appnp_propagate),
+# which the bf16 loop does not have (profiles/NOTES.md, bf16 storage)
+BF16_MIN_WIDTH = 17
+BF16_F32_ROWS = 1 << 20
+
+
+def _bf16(storage) -> bool:
+    if storage is torch.bfloat16:
+        return True
+    if storage is torch.float32:
+        return False
+    raise Exception(f"storage must be torch.float32 or torch.bfloat16, not {storage}")
+
+
+def _no_grad_for_bf16(fn, *tensors):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise Exception(f"{fn}: bf16 storage is inference only (no backward); run it under torch.no_grad() or detach the inputs")
+
+
+def to_bf16(X: torch.Tensor) -> torch.Tensor:
+    """bf(X) on the device (gnx_cast_bf16: round to nearest even, NaN stays NaN), [n, C] contiguous bf16."""
+    nat.require_cuda(X)
+    X = _as_f32_rows(X)
+    out = torch.empty(X.shape, dtype=torch.bfloat16, device=X.device)
+    with nat.on_device(X.device):
+        nat.check(nat.lib().gnx_cast_bf16(nat.ptr(X), X.shape[0], X.shape[1], X.stride(0), nat.ptr(out), X.shape[1],
+                                          nat.current_stream()))
+    return out
+
+
+def _launch_bf16(adj: Adjacency, X, H0, beta, alpha, act, out_bf16=False):
+    """_launch with X gathered as bf16 (gnx_spmm_bf16): f32 result, or bf16 with ``out_bf16``."""
+    g = adj.graph
+    nat.require_cuda(X, H0)
+    _same_device(g, X, H0, adj.diag)
+    if X.dim() != 2:
+        raise Exception("propagation expects a 2-D feature matrix")
+    if X.dtype == torch.bfloat16:
+        Xb = X if X.stride(1) == 1 and X.stride(0) >= X.shape[1] else X.contiguous()
+    else:
+        Xb = to_bf16(X)
+    if Xb.shape[0] != g.n_cols:
+        raise Exception(f"spmm: features have {Xb.shape[0]} rows, adjacency expects {g.n_cols}")
+    if adj.vals is None and adj.vals_t is not None:
+        raise Exception("spmm: this adjacency only holds transposed-order values")
+    C = Xb.shape[1]
+    out = torch.empty((g.n_rows, C), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=Xb.device)
+    ldh0 = 0
+    if H0 is not None:
+        H0 = _as_f32_rows(H0)
+        if tuple(H0.shape) == (1, C) and g.n_rows != 1:
+            H0, ldh0 = H0.contiguous(), 0                       # one row for every output row (bias)
+        elif tuple(H0.shape) != (g.n_rows, C):
+            raise Exception("spmm: H0 shape mismatch")
+        else:
+            ldh0 = H0.stride(0)
+    with nat.on_device(Xb.device):
+        nat.check(nat.lib().gnx_spmm_bf16(g.handle, nat.ptr(adj.vals), nat.ptr(adj.diag), nat.ptr(Xb), Xb.stride(0), C, nat.ptr(H0),
+                                          ldh0, float(beta), float(alpha), int(act), nat.ptr(out), 1 if out_bf16 else 0, out.stride(0),
+                                          nat.current_stream()))
+    return out
+
+
+def _appnp_propagate_bf16(adj: Adjacency, H0: torch.Tensor, a, iterations, relu):
+    """appnp_propagate on gnx_appnp_propagate_bf16 (H0: f32 contiguous [n, C]), at the bf16 line-friendly width."""
+    g = adj.graph
+    C = H0.shape[1]
+    H0 = _padded(H0, friendly_width_bf16(C, H0.shape[0]))
+    out = torch.empty_like(H0)
+    work = torch.empty((2,) + tuple(H0.shape), dtype=torch.bfloat16, device=H0.device) if iterations > 0 else None
+    with nat.on_device(H0.device):
+        nat.check(nat.lib().gnx_appnp_propagate_bf16(g.handle, nat.ptr(adj.vals), nat.ptr(adj.diag), nat.ptr(H0), float(a),
+                                                     int(iterations), H0.shape[1], nat.ACT_RELU if relu else nat.ACT_NONE,
+                                                     nat.ptr(out), nat.ptr(work), nat.current_stream()))
     return out if out.shape[1] == C else out[:, :C].contiguous()
 
 

@@ -52,8 +52,8 @@ const char *gnx_last_error(void);
  * the same names between 0.2 and 0.3 (gnx_halo_plan_create / _layout / _pack / _exchange gained `part` and split pull / push
  * counts; gnx_gcnii_step's d_work became d_mixed), so a 0.2 client linked against a 0.3+ library passes shifted arguments.
  * 0.4 adds gnx_graph_reserve and changes no existing signature; 0.5 adds gnx_graph_set_row_window, 0.6 gnx_appnp_propagate_act,
- * likewise. */
-#define GNX_ABI_VERSION 600
+ * likewise; 0.6.1 adds the bf16 storage entries (gnx_cast_bf16, gnx_spmm_bf16, gnx_appnp_propagate_bf16) and changes nothing else. */
+#define GNX_ABI_VERSION 601
 int gnx_version(void);
 
 /* ---- graph construction ------------------------------------------------------------
@@ -284,6 +284,25 @@ int gnx_appnp_propagate(gnx_graph_t g, const float *d_vals, const float *d_diag,
 int gnx_appnp_propagate_act(gnx_graph_t g, const float *d_vals, const float *d_diag, const float *d_H0,
                             float a, int K, int64_t C, int act, float *d_out, float *d_work, void *stream);
 
+/* ---- opt-in bf16 feature storage (eval-mode propagation; no backward) -------------------------------------------------
+ * bf16 values are passed as uint16_t bit patterns.  bf(x) = x rounded to nearest even, NaN stays NaN; u = 2^-8.
+ * gnx_cast_bf16: dst = bf(src), [n_rows, C] with leading dimensions lds / ldd (elements); dst must not alias src.
+ * gnx_spmm_bf16: out[i,:] = act( beta * ( sum_j A[i,j] X~[j,:] + diag[i] X~[i,:] ) + alpha * H0[i,:] ) with X~ bf16 (widened
+ *   exactly), the sums, H0 and the epilogue in f32; out is f32 (out_bf16 = 0) or bf(.) (out_bf16 = 1).  The argument rules of
+ *   gnx_spmm: d_vals NULL = raw values, d_diag optional (square graph), ldh0 == 0 broadcasts one H0 row, act may carry
+ *   GNX_ACT_SKIP_EMPTY.  The per-row summation order follows the fixed rules of gnx_spmm (chunk order for long rows): two calls
+ *   give the same bits.
+ * gnx_appnp_propagate_bf16: the loop of gnx_appnp_propagate_act with the iterate stored as bf16 between iterations:
+ *   H~_0 = bf(H0); H_{k+1} = act((1-a) A_hat . H~_k + a H0) with H0 f32 in the mix; H~_{k+1} = bf(H_{k+1}) for k < K-1; d_out
+ *   receives f32 H_K for every row.  d_work holds TWO bf16 [n, C] buffers (the bytes of one f32 [n, C] buffer) and is needed for
+ *   every K >= 1; K = 0 copies H0.  Rows without entries follow the settled-row rule of gnx_appnp_propagate.  No relabelled copy. */
+int gnx_cast_bf16(const float *d_src, int64_t n_rows, int64_t C, int64_t lds, uint16_t *d_dst, int64_t ldd, void *stream);
+int gnx_spmm_bf16(gnx_graph_t g, const float *d_vals, const float *d_diag, const uint16_t *d_X, int64_t ldx, int64_t C,
+                  const float *d_H0, int64_t ldh0, float beta, float alpha, int act, void *d_out, int out_bf16, int64_t ldo,
+                  void *stream);
+int gnx_appnp_propagate_bf16(gnx_graph_t g, const float *d_vals, const float *d_diag, const float *d_H0, float a, int K, int64_t C,
+                             int act, float *d_out, uint16_t *d_work, void *stream);
+
 /* One GCNIILayer.__forward__ (gnntf/core/gnn/architectures/gcn.py:22-27) with a fixed adjacency:
  *   out = act( ((A_hat . H)*(1-a) + H0*a) . M ),   M = (1-b) I + b W  given by the caller as a [C, C] matrix (ldm).
  * For C in {16, 32, 64} (16-byte aligned buffers) this is ONE launch for all rows of at most 512 entries: the mixed rows
@@ -397,7 +416,8 @@ int gnx_probe_block_xcd(int64_t n_blocks, int32_t *d_xcd_out, void *stream);
 /* Name of the SpMM kernel the last gnx_spmm/_t call on this handle dispatched (static
  * string; for profiles and tests): "spmm_wave", "spmm_group8" ... "spmm_group32" (lanes per row; "spmm_group4+chunks": the merged small-graph launch), "..._drop" (weights made
  * in the kernel), "...+chunks" (structures below 2^20 rows: the chunks of the long rows share the launch of the short rows),
- * "spmm_gcnii_mfma", "spmm+dense_mfma". */
+ * "spmm_gcnii_mfma", "spmm+dense_mfma"; the bf16 entries report "spmm_wave_bf16", "spmm_group8_bf16" ... "spmm_group32_bf16",
+ * "...+long_bf16" (hub rows through the chunk kernels) and "...+chunks_bf16". */
 const char *gnx_graph_last_kernel(gnx_graph_t g);
 
 #ifdef __cplusplus
