@@ -608,6 +608,10 @@ int gnx_graph_destroy(gnx_graph_t g) {
     if (g->t_raw) (void)hipFree(g->t_raw);
     if (g->t_rowidx) (void)hipFree(g->t_rowidx);
     if (g->t_mask) (void)hipFree(g->t_mask);
+    if (g->ed_mult) (void)hipFree(g->ed_mult);
+    if (g->t_ed_mult) (void)hipFree(g->t_ed_mult);
+    if (g->ed_vals) (void)hipFree(g->ed_vals);
+    if (g->t_ed_vals) (void)hipFree(g->t_ed_vals);
     if (g->partial) (void)hipFree(g->partial);
     if (g->deg) (void)hipFree(g->deg);
     if (g->blk_col_gid) (void)hipFree(g->blk_col_gid);

@@ -102,6 +102,12 @@ struct gnx_graph {
     float *t_vals = nullptr;     // [a.nnz] scratch: values gathered into transposed order
     float *t_raw = nullptr;      // [a.nnz] raw values in transposed order (streaming column sums)
     int32_t *t_rowidx = nullptr; // [a.nnz] row of the transposed structure (= column of A) per transposed position
+    // entry dropout of a handle with duplicates (gnx_graph_enable_entry_dropout): per slot the multiplicity (ENTRY_GENERAL: walk the
+    // entry list) and the value its entries share, in CSR order and in transposed order (t_perm depends on the structure alone, so
+    // the transposed tables stay valid if the transposed structure is ever rebuilt)
+    bool entry_drop = false;
+    uint8_t *ed_mult = nullptr, *t_ed_mult = nullptr;
+    float *ed_vals = nullptr, *t_ed_vals = nullptr;
     uint16_t *t_mask = nullptr;  // [a.nnz] scratch: keep bits of up to 16 dropout streams per transposed position (gnx_graph_colsum_streams)
     // partial slab for long rows (grown on demand)
     float *partial = nullptr;
@@ -144,12 +150,37 @@ __device__ __forceinline__ uint64_t rng_fin(uint64_t z) {
     z ^= z >> 31;
     return z;
 }
-__device__ __forceinline__ uint32_t hash_u24(uint64_t seed, uint64_t stream, uint64_t row, uint64_t col, uint64_t dup) {
+// hash_u24 in two parts: the first two rounds depend on (seed, stream, row, col) only, the last one on the duplicate rank as well
+__device__ __forceinline__ uint64_t hash_key(uint64_t seed, uint64_t stream, uint64_t row, uint64_t col) {
     const uint64_t k = seed ^ (stream * 0xD1342543DE82EF95ull);
     uint64_t x = rng_fin(k + row * 0x9E3779B97F4A7C15ull);
-    x ^= col * 0xC2B2AE3D27D4EB4Full;
-    x = rng_fin(x + dup * 0x165667B19E3779F9ull);
-    return (uint32_t)(x >> 40);
+    return x ^ (col * 0xC2B2AE3D27D4EB4Full);
+}
+__device__ __forceinline__ uint32_t hash_rank(uint64_t key, uint64_t dup) {
+    return (uint32_t)(rng_fin(key + dup * 0x165667B19E3779F9ull) >> 40);
+}
+__device__ __forceinline__ uint32_t hash_u24(uint64_t seed, uint64_t stream, uint64_t row, uint64_t col, uint64_t dup) {
+    return hash_rank(hash_key(seed, stream, row, col), dup);
+}
+
+// Entry dropout on a handle with duplicate COO entries (gnx_graph_enable_entry_dropout): per coalesced slot a multiplicity byte;
+// ENTRY_GENERAL marks a slot whose entries are not all the same float (or more than 254 of them), whose value is then the walk
+// of its entry list.  Kept sum of a slot = its kept entries * 1/(1-p), added in input order exactly as slot_value (gnx_prep.hip)
+// writes it.  For a uniform slot every term is the same float, so the m-fold loop over one value is bit for bit the walk of the list.
+constexpr uint32_t ENTRY_GENERAL = 255;
+
+__device__ __forceinline__ float slot_kept_sum(uint64_t key, uint32_t thr, float scale, uint32_t m, float uval,
+                                               const float *__restrict__ e_vals, const int64_t *__restrict__ slot_ptr, int64_t slot) {
+    float acc = 0.f;
+    if (m != ENTRY_GENERAL) {
+        for (uint32_t i = 0; i < m; ++i)
+            if (hash_rank(key, i) >= thr) acc += uval * scale;
+    } else {
+        const int64_t b = slot_ptr[slot], e = slot_ptr[slot + 1];
+        for (int64_t i = b; i < e; ++i)
+            if (hash_rank(key, (uint64_t)(i - b)) >= thr) acc += e_vals[i] * scale;
+    }
+    return acc;
 }
 
 // gnx_spmm_dropped: the values of one training iteration's dropped + re-normalised adjacency are produced inside the
@@ -164,6 +195,12 @@ struct DropFuse {
     int col_prescaled;     // the gathered rows already carry their column's scale (written by the previous iteration's epilogue)
     int64_t row0_key, row0_D;   // vertex block: global id of row 0 / position of row 0's scale in D (0, 0 otherwise)
     const int32_t *gid;         // vertex block: global id of every column (null: the column index itself)
+    // entry dropout (the _entries kernels only): multiplicity of every slot of the structure walked, the handle's entry lists and,
+    // for the transposed structure, the coalesced slot of every position (t_perm); SpmmArgs::vals holds each uniform slot's value
+    const uint8_t *mult;
+    const float *e_vals;
+    const int64_t *slot_ptr;
+    const int32_t *perm;
 };
 
 __device__ __forceinline__ float dropped_weight(const DropFuse &f, float raw, int64_t r, int64_t c) {
@@ -175,6 +212,28 @@ __device__ __forceinline__ float dropped_weight(const DropFuse &f, float raw, in
         return (raw * f.scale) * f.D[ac];
     const float w = f.D[ar + f.row0_D] * (raw * f.scale);
     return f.col_prescaled ? w : w * f.D[ac];
+}
+
+// dropped_weight on a handle with duplicate entries: `uval` = the uniform value of the slot at position `pos` of the structure walked.
+// Weight (D[row] * kept sum) * D[col], as k_scale_values makes it; a slot whose kept sum is 0 weighs 0 and is skipped like a dropped one.
+__device__ __forceinline__ float dropped_weight_entries(const DropFuse &f, float uval, int64_t pos, int64_t r, int64_t c) {
+    const int64_t ar = f.transposed ? c : r, ac = f.transposed ? r : c;
+    const uint64_t stream = f.stream + (f.offset ? *f.offset : 0);
+    const uint64_t kc = f.gid ? (uint64_t)f.gid[ac] : (uint64_t)ac;
+    const uint32_t m = f.mult[pos];
+    const int64_t slot = (m == ENTRY_GENERAL && f.perm) ? (int64_t)f.perm[pos] : pos;
+    const float v = slot_kept_sum(hash_key(f.seed, stream, (uint64_t)(ar + f.row0_key), kc), f.thr, f.scale, m, uval, f.e_vals,
+                                  f.slot_ptr, slot);
+    if (v == 0.f) return 0.f;
+    if (f.col_prescaled && f.transposed) return v * f.D[ac];
+    const float w = f.D[ar + f.row0_D] * v;
+    return f.col_prescaled ? w : w * f.D[ac];
+}
+
+template <bool ENTRIES>
+__device__ __forceinline__ float dropped_weight_at(const DropFuse &f, float raw, int64_t pos, int64_t r, int64_t c) {
+    if constexpr (ENTRIES) return dropped_weight_entries(f, raw, pos, r, c);
+    else return dropped_weight(f, raw, r, c);
 }
 
 struct SpmmArgs {

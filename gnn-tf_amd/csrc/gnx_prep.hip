@@ -246,6 +246,102 @@ __global__ __launch_bounds__(256) void k_colsum_long_masked(const int64_t *__res
     }
 }
 
+// The column sums of NS streams on a handle with duplicate entries (gnx_graph_enable_entry_dropout): the walk and the reduction tree
+// of k_colsum_short<true> / k_colsum_long<true>, each position's kept slot sum made per stream from the entry tables in transposed
+// order (slot_kept_sum: a uniform slot reads its multiplicity and value, a general one walks its entries through t_perm) -- so every
+// stream's sums are bit for bit what gnx_graph_colsum gives, and the structure is read once for all of them.
+template <int NS>
+__device__ __forceinline__ void entry_sums(float (&acc)[NS], const Drop &d, int ns, uint64_t row, uint64_t kc, uint32_t m, float uval,
+                                           const int32_t *__restrict__ t_perm, int64_t p) {
+    const int64_t slot = m == ENTRY_GENERAL ? (int64_t)t_perm[p] : 0;
+    const uint64_t stream = stream_of(d);
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+        if (s < ns) acc[s] += slot_kept_sum(hash_key(d.seed, stream + s, row, kc), d.thr, d.scale, m, uval, d.e_vals, d.slot_ptr, slot);
+}
+
+template <int NS>
+__global__ void k_colsum_short_entries(const int64_t *__restrict__ t_rowptr, const int32_t *__restrict__ t_colidx,
+                                       const int32_t *__restrict__ t_perm, const uint8_t *__restrict__ t_mult,
+                                       const float *__restrict__ t_uval, Drop d, int ns, int64_t n_cols, int long_row,
+                                       float *__restrict__ out) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t j = gid >> 3;
+    const int sub = (int)(gid & 7);
+    float acc[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) acc[s] = 0.f;
+    bool is_long = false;
+    if (j < n_cols) {
+        const int64_t b = t_rowptr[j], e = t_rowptr[j + 1];
+        is_long = (e - b) > long_row;
+        if (!is_long) {
+            const uint64_t kc = key_col(d, j);
+            for (int64_t p = b + sub; p < e; p += 8)
+                entry_sums<NS>(acc, d, ns, key_row(d, t_colidx[p]), kc, t_mult[p], t_uval[p], t_perm, p);
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        float a = acc[s];
+        a += __shfl_xor(a, 4);
+        a += __shfl_xor(a, 2);
+        a += __shfl_xor(a, 1);
+        if (j < n_cols && sub == 0 && !is_long && s < ns) out[(int64_t)s * n_cols + j] = a;
+    }
+}
+
+template <int NS>
+__global__ __launch_bounds__(256) void k_colsum_long_entries(const int64_t *__restrict__ t_rowptr, const int32_t *__restrict__ t_colidx,
+                                                             const int32_t *__restrict__ t_perm, const uint8_t *__restrict__ t_mult,
+                                                             const float *__restrict__ t_uval, Drop d, int ns,
+                                                             const int32_t *__restrict__ long_rows, int64_t n_cols, float *__restrict__ out) {
+    __shared__ float red[256];
+    const int32_t j = long_rows[blockIdx.x];
+    const int64_t b = t_rowptr[j], e = t_rowptr[j + 1];
+    float acc[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) acc[s] = 0.f;
+    const uint64_t kc = key_col(d, j);
+    for (int64_t p = b + threadIdx.x; p < e; p += 256)
+        entry_sums<NS>(acc, d, ns, key_row(d, t_colidx[p]), kc, t_mult[p], t_uval[p], t_perm, p);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        if (s < ns) {                                                // (block-uniform)
+            __syncthreads();
+            red[threadIdx.x] = acc[s];
+            __syncthreads();
+            for (int w = 128; w > 0; w >>= 1) {
+                if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+                __syncthreads();
+            }
+            if (threadIdx.x == 0) out[(int64_t)s * n_cols + j] = red[0];
+        }
+    }
+}
+
+// gnx_graph_enable_entry_dropout: per coalesced slot its multiplicity and, when all its entries are the same float, that value
+__global__ void k_entry_tables(const float *__restrict__ e_vals, const int64_t *__restrict__ slot_ptr, int64_t nslots,
+                               uint8_t *__restrict__ mult, float *__restrict__ uval) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nslots) return;
+    const int64_t b = slot_ptr[k], e = slot_ptr[k + 1];
+    const uint32_t bits = __float_as_uint(e_vals[b]);
+    bool uniform = e - b < (int64_t)ENTRY_GENERAL;
+    for (int64_t i = b + 1; uniform && i < e; ++i) uniform = __float_as_uint(e_vals[i]) == bits;
+    mult[k] = uniform ? (uint8_t)(e - b) : (uint8_t)ENTRY_GENERAL;
+    uval[k] = uniform ? __uint_as_float(bits) : 0.f;
+}
+
+__global__ void k_permute_entry_tables(const int32_t *__restrict__ perm, int64_t n, const uint8_t *__restrict__ mult,
+                                       const float *__restrict__ uval, uint8_t *__restrict__ t_mult, float *__restrict__ t_uval) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const int32_t k = perm[p];
+    t_mult[p] = mult[k];
+    t_uval[p] = uval[k];
+}
+
 // gnn.py:41 / :44 with optional "+I before" folded in as +1 on every column sum
 __global__ void k_degree_scale(float *__restrict__ d, int64_t n, int normalized, float eye) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -335,6 +431,33 @@ int gnx_graph_set_block(gnx_graph_t g, int64_t row0_global, int64_t row0_buf, co
     return GNX_OK;
 }
 
+int gnx_graph_enable_entry_dropout(gnx_graph_t g, void *stream) {
+    GNX_CHECK_ARG(g != nullptr, "gnx_graph_enable_entry_dropout: NULL handle");
+    if (!g->has_dups || g->entry_drop) return GNX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    GNX_CHECK_ARG(!stream_is_capturing(s), "gnx_graph_enable_entry_dropout: the stream is being captured -- enable before the capture begins");
+    int rc = ensure_transpose(g, s);
+    if (rc != GNX_OK) return rc;
+    const int64_t nnz = g->a.nnz;
+    struct Tables {
+        uint8_t *m = nullptr, *tm = nullptr;
+        float *v = nullptr, *tv = nullptr;
+        ~Tables() { if (m) (void)hipFree(m); if (tm) (void)hipFree(tm); if (v) (void)hipFree(v); if (tv) (void)hipFree(tv); }
+    } tb;
+    GNX_HIP(hipMalloc((void **)&tb.m, nnz));
+    GNX_HIP(hipMalloc((void **)&tb.tm, nnz));
+    GNX_HIP(hipMalloc((void **)&tb.v, nnz * sizeof(float)));
+    GNX_HIP(hipMalloc((void **)&tb.tv, nnz * sizeof(float)));
+    hipLaunchKernelGGL(k_entry_tables, dim3(blocks_for(nnz)), dim3(256), 0, s, g->e_vals, g->slot_ptr, nnz, tb.m, tb.v);
+    hipLaunchKernelGGL(k_permute_entry_tables, dim3(blocks_for(nnz)), dim3(256), 0, s, g->t_perm, nnz, tb.m, tb.v, tb.tm, tb.tv);
+    GNX_HIP(hipGetLastError());
+    GNX_HIP(hipStreamSynchronize(s));
+    g->ed_mult = tb.m; g->t_ed_mult = tb.tm; g->ed_vals = tb.v; g->t_ed_vals = tb.tv;
+    tb.m = tb.tm = nullptr; tb.v = tb.tv = nullptr;
+    g->entry_drop = true;
+    return GNX_OK;
+}
+
 int gnx_graph_colsum(gnx_graph_t g, float dropout_p, uint64_t seed, uint64_t stream_id, float *d_colsum_out, void *stream) {
     GNX_CHECK_ARG(g != nullptr && d_colsum_out != nullptr, "gnx_graph_colsum: NULL argument");
     hipStream_t s = (hipStream_t)stream;
@@ -367,6 +490,36 @@ int gnx_graph_colsum_streams(gnx_graph_t g, float dropout_p, uint64_t seed, uint
     GNX_CHECK_ARG(n_streams >= 1 && n_streams <= 4096, "gnx_graph_colsum_streams: bad stream count %d", n_streams);
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = g->a.n_cols;
+    if (g->has_dups && g->entry_drop && dropout_p > 0.f) {   // entry tables (gnx_graph_enable_entry_dropout): one pass per 16 streams
+        int rc = ensure_transpose(g, s);
+        if (rc != GNX_OK) return rc;
+        const Csr &t = g->t;
+        if (t.n_rows == 0) return GNX_OK;
+        const unsigned nb = blocks_for(t.n_rows * 8);
+        for (int k0 = 0; k0 < n_streams; k0 += 16) {
+            const int ns = n_streams - k0 < 16 ? n_streams - k0 : 16;
+            Drop d;
+            rc = make_drop(g, dropout_p, seed, first_stream + k0, d);
+            if (rc != GNX_OK) return rc;
+            float *out = d_colsum_out + (int64_t)k0 * n;
+#define GNX_ENTRY_SUMS(NS)                                                                                                             \
+            do {                                                                                                                       \
+                hipLaunchKernelGGL(k_colsum_short_entries<NS>, dim3(nb), dim3(256), 0, s, t.rowptr, t.colidx, g->t_perm, g->t_ed_mult,  \
+                                   g->t_ed_vals, d, ns, t.n_rows, t.long_row, out);                                                    \
+                if (t.n_long > 0)                                                                                                      \
+                    hipLaunchKernelGGL(k_colsum_long_entries<NS>, dim3((unsigned)t.n_long), dim3(256), 0, s, t.rowptr, t.colidx,       \
+                                       g->t_perm, g->t_ed_mult, g->t_ed_vals, d, ns, t.long_rows, t.n_rows, out);                      \
+            } while (0)
+            if (ns > 8) GNX_ENTRY_SUMS(16);
+            else if (ns > 4) GNX_ENTRY_SUMS(8);
+            else if (ns > 2) GNX_ENTRY_SUMS(4);
+            else if (ns > 1) GNX_ENTRY_SUMS(2);
+            else GNX_ENTRY_SUMS(1);
+#undef GNX_ENTRY_SUMS
+        }
+        GNX_HIP(hipGetLastError());
+        return GNX_OK;
+    }
     if (g->has_dups || dropout_p <= 0.f) {              // entry lists / no dropout: one stream at a time through the general kernels
         for (int k = 0; k < n_streams; ++k) {
             int rc = gnx_graph_colsum(g, dropout_p, seed, first_stream + k, d_colsum_out + (int64_t)k * n, stream);

@@ -59,8 +59,9 @@ __device__ __forceinline__ float readlane_f(float v, int lane) {
 }
 
 // Sum of w_e * X[col_e, c .. c+VEC) over entries [beg, end) of one row; the whole wave works
-// on the same entries (beg/end wave-uniform), lane `lane` owns columns c .. c+VEC.
-template <int VEC, int U, bool FUSE = false>
+// on the same entries (beg/end wave-uniform), lane `lane` owns columns c .. c+VEC.  ENTRIES (with FUSE): the handle holds duplicate
+// entries and the weight of a slot is its kept sum (dropped_weight_entries).
+template <int VEC, int U, bool FUSE = false, bool ENTRIES = false>
 __device__ __forceinline__ void wave_accumulate(const int32_t *__restrict__ colidx, const float *__restrict__ vals,
                                                 const float *__restrict__ X, int64_t ldx, int64_t beg, int64_t end,
                                                 int c, int lane, float (&acc)[VEC], bool nt_index = false,
@@ -77,7 +78,7 @@ __device__ __forceinline__ void wave_accumulate(const int32_t *__restrict__ coli
                 mycol = colidx[base + lane];
                 myval = vals[base + lane];
             }
-            if (FUSE) myval = dropped_weight(*fuse, myval, row, mycol);      // one entry per lane: 64 weights per wave instruction
+            if (FUSE) myval = dropped_weight_at<ENTRIES>(*fuse, myval, base + lane, row, mycol);   // one entry per lane: 64 weights per wave instruction
         }
         int i = 0;
         if (FUSE) {

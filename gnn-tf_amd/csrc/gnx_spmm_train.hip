@@ -10,7 +10,10 @@ namespace {
 // Same row / lane mapping as the kernels above; what differs is where an entry's weight comes from: p.vals holds the RAW
 // values and every weight is (D[row] * drop(raw)) * D[col] (layered.py:47-50 + gnn.py:41-42), computed ONCE per entry by one
 // lane and handed to the lanes that need it (readlane / shuffles), so the hash costs one evaluation per stored entry.
-template <int VEC, int U, int WPB>
+// ENTRIES (the _entries instantiations, a handle with duplicate COO entries after gnx_graph_enable_entry_dropout): p.vals holds each
+// slot's uniform value and the lane that owns a slot makes its kept sum (dropped_weight_entries) -- one more hash round per further
+// duplicate; everything else, and the kernels without duplicates, as before.
+template <int VEC, int U, int WPB, bool ENTRIES = false>
 __global__ __launch_bounds__(64 * WPB) void k_spmm_wave_drop(const SpmmArgs p) {
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -26,14 +29,14 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_wave_drop(const SpmmArgs p) {
         float acc[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-        wave_accumulate<VEC, U, true>(p.colidx, p.vals, p.X, p.ldx, beg, end, active ? c : 0, lane, acc, false, &p.fuse, row);
+        wave_accumulate<VEC, U, true, ENTRIES>(p.colidx, p.vals, p.X, p.ldx, beg, end, active ? c : 0, lane, acc, false, &p.fuse, row);
         epilogue_store<VEC>(p, row, c, active, acc);
     }
 }
 
 // PIPE: the (col, raw value) pair a lane owns in the NEXT round is loaded before this round's kept entries are gathered, so a row
 // of more than G entries pays the index latency once instead of once per round.
-template <int VEC, int G, int U, bool PIPE>
+template <int VEC, int G, int U, bool PIPE, bool ENTRIES = false>
 __global__ __launch_bounds__(256) void k_spmm_group_drop(const SpmmArgs p) {
     constexpr int RPB = 256 / G;
     const int sub = threadIdx.x % G;
@@ -63,10 +66,10 @@ __global__ __launch_bounds__(256) void k_spmm_group_drop(const SpmmArgs p) {
                 const int ccol = ncol;
                 const float craw = nraw;
                 if (base + G + sub < end) { ncol = p.colidx[base + G + sub]; nraw = p.vals[base + G + sub]; }
-                if (sub < n) { mycol = ccol; myw = dropped_weight(p.fuse, craw, row, ccol); }
+                if (sub < n) { mycol = ccol; myw = dropped_weight_at<ENTRIES>(p.fuse, craw, base + sub, row, ccol); }
             } else if (sub < n) {
                 mycol = p.colidx[base + sub];
-                myw = dropped_weight(p.fuse, p.vals[base + sub], row, mycol);
+                myw = dropped_weight_at<ENTRIES>(p.fuse, p.vals[base + sub], base + sub, row, mycol);
             }
             // dropped entries (weight exactly 0) are not gathered: the group walks only the kept entries of its round, in order
             const uint64_t all = __ballot(myw != 0.f);
@@ -98,7 +101,7 @@ __global__ __launch_bounds__(256) void k_spmm_group_drop(const SpmmArgs p) {
     }
 }
 
-template <int VEC, int U>
+template <int VEC, int U, bool ENTRIES = false>
 __global__ __launch_bounds__(256) void k_spmm_long_partial_drop(const SpmmArgs p) {
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -116,14 +119,14 @@ __global__ __launch_bounds__(256) void k_spmm_long_partial_drop(const SpmmArgs p
         float acc[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-        wave_accumulate<VEC, U, true>(p.colidx, p.vals, p.X, p.ldx, beg, end, active ? c : 0, lane, acc, false, &p.fuse, row);
+        wave_accumulate<VEC, U, true, ENTRIES>(p.colidx, p.vals, p.X, p.ldx, beg, end, active ? c : 0, lane, acc, false, &p.fuse, row);
         if (active) vstore<VEC>(p.partial + chunk * (int64_t)p.C + c, acc);
     }
 }
 
 // narrow long rows: the wave computes 64 weights per round (one per lane); sub-group s then takes entries s, s + NS, ... of the
 // round, which is the entry -> sub-group dealing of k_spmm_long_partial_group (so the partial sums are bitwise the same)
-template <int VEC, int G, int U>
+template <int VEC, int G, int U, bool ENTRIES = false>
 __global__ __launch_bounds__(256) void k_spmm_long_partial_group_drop(const SpmmArgs p) {
     constexpr int NS = 64 / G;
     const int lane = threadIdx.x & 63;
@@ -151,7 +154,7 @@ __global__ __launch_bounds__(256) void k_spmm_long_partial_group_drop(const Spmm
         float myw = 0.f;
         if (lane < n) {
             mycol = p.colidx[base + lane];
-            myw = dropped_weight(p.fuse, p.vals[base + lane], row, mycol);
+            myw = dropped_weight_at<ENTRIES>(p.fuse, p.vals[base + lane], base + lane, row, mycol);
         }
 #pragma unroll 1
         for (int k = 0; k < G; k += U) {
@@ -185,7 +188,10 @@ __global__ __launch_bounds__(256) void k_spmm_long_partial_group_drop(const Spmm
 [[maybe_unused]] constexpr bool DROP_U8 = false, DROP_PIPE = false;     // product defaults of the training row kernels (see launch_rows_drop)
 constexpr int DROP_LONG_U = 4;
 
-template <int VEC>
+// the name gnx_graph_last_kernel reports: "_entries" appended for the instantiations over a handle with duplicate entries
+#define GNX_DROP_NAME(base) (E ? base "_entries" : base)
+
+template <int VEC, bool E>
 const char *launch_rows_drop(const SpmmArgs &p0, hipStream_t s) {
     SpmmArgs p = p0;
     const int lanes = (p.C + VEC - 1) / VEC;
@@ -193,11 +199,11 @@ const char *launch_rows_drop(const SpmmArgs &p0, hipStream_t s) {
         if (lanes <= 32 && p.row_order != nullptr) p.n_rows = p.n_nonempty;
         else if (lanes > 32 && p.nonempty_rows != nullptr) { p.row_list = p.nonempty_rows; p.n_rows = p.n_nonempty; }
     }
-    if (p.n_rows == 0) return "spmm_none_drop";
+    if (p.n_rows == 0) return GNX_DROP_NAME("spmm_none_drop");
     if (lanes > 32) {
-        if (p.C <= 64 * VEC) GNX_ROW_PIECES((k_spmm_wave_drop<VEC, 8, 8>), 8, 512);
-        else                 GNX_ROW_PIECES((k_spmm_wave_drop<VEC, 8, 4>), 4, 256);
-        return "spmm_wave_drop";
+        if (p.C <= 64 * VEC) GNX_ROW_PIECES((k_spmm_wave_drop<VEC, 8, 8, E>), 8, 512);
+        else                 GNX_ROW_PIECES((k_spmm_wave_drop<VEC, 8, 4, E>), 4, 256);
+        return GNX_DROP_NAME("spmm_wave_drop");
     }
     // U gathers in flight per lane and the index prefetch: round-4 A/B on the config-4 graph (tuning build bits 1 << 17 = U 8,
     // 1 << 19 = PIPE; profiles/NOTES.md)
@@ -208,40 +214,72 @@ const char *launch_rows_drop(const SpmmArgs &p0, hipStream_t s) {
 #endif
 #define GNX_DROP_ROWS(G, RPB)                                                                                         \
     do {                                                                                                              \
-        if (u8 && pipe)  GNX_ROW_PIECES((k_spmm_group_drop<VEC, G, 8, true>), RPB, 256);                              \
-        else if (u8)     GNX_ROW_PIECES((k_spmm_group_drop<VEC, G, 8, false>), RPB, 256);                             \
-        else if (pipe)   GNX_ROW_PIECES((k_spmm_group_drop<VEC, G, 4, true>), RPB, 256);                              \
-        else             GNX_ROW_PIECES((k_spmm_group_drop<VEC, G, 4, false>), RPB, 256);                             \
+        if (u8 && pipe)  GNX_ROW_PIECES((k_spmm_group_drop<VEC, G, 8, true, E>), RPB, 256);                           \
+        else if (u8)     GNX_ROW_PIECES((k_spmm_group_drop<VEC, G, 8, false, E>), RPB, 256);                          \
+        else if (pipe)   GNX_ROW_PIECES((k_spmm_group_drop<VEC, G, 4, true, E>), RPB, 256);                           \
+        else             GNX_ROW_PIECES((k_spmm_group_drop<VEC, G, 4, false, E>), RPB, 256);                          \
     } while (0)
     // A group of G lanes takes G entries per round (lane `sub` draws the weight of entry base + sub), so G is also how many index
     // loads and draws are in flight per row.  Round 6 (profiles/NOTES.md, config-4 graph, middle iteration): rows of up to 4 lanes
     // (C <= 16) on 8-lane groups instead of 4-lane ones -- half the lanes then only fetch and draw, their gather repeats a
     // neighbour's line -- C = 8: 1.94 -> 1.52 ms forward, 2.03 -> 1.61 backward; C = 16: 2.00 -> 1.56 / 2.08 -> 1.63; same bits.
     // 16 lanes: 1.83 / 1.85 ms, 32 lanes: 2.7 ms (fewer rows per wave than the gathers need in flight).
-    if (lanes > 16) { GNX_DROP_ROWS(32, 8); return "spmm_group32_drop"; }
-    if (lanes > 8)  { GNX_DROP_ROWS(16, 16); return "spmm_group16_drop"; }
+    if (lanes > 16) { GNX_DROP_ROWS(32, 8); return GNX_DROP_NAME("spmm_group32_drop"); }
+    if (lanes > 8)  { GNX_DROP_ROWS(16, 16); return GNX_DROP_NAME("spmm_group16_drop"); }
     GNX_DROP_ROWS(8, 32);
 #undef GNX_DROP_ROWS
-    return "spmm_group8_drop";
+    return GNX_DROP_NAME("spmm_group8_drop");
 }
+#undef GNX_DROP_NAME
 
-template <int VEC>
+template <int VEC, bool E>
 void launch_long_drop(const SpmmArgs &p, hipStream_t s) {
     const int lanes = (p.C + VEC - 1) / VEC;
-    if (lanes > 32)      GNX_LAUNCH((k_spmm_long_partial_drop<VEC, 8>), blocks_for(p.n_chunks, 4), p);
+    if (lanes > 32)      GNX_LAUNCH((k_spmm_long_partial_drop<VEC, 8, E>), blocks_for(p.n_chunks, 4), p);
 #ifdef GNX_TUNING
     else if (p.tune & (1 << 18)) {
-        if (lanes > 16)      GNX_LAUNCH((k_spmm_long_partial_group_drop<VEC, 32, 8>), blocks_for(p.n_chunks, 4), p);
-        else if (lanes > 8)  GNX_LAUNCH((k_spmm_long_partial_group_drop<VEC, 16, 8>), blocks_for(p.n_chunks, 4), p);
-        else if (lanes > 4)  GNX_LAUNCH((k_spmm_long_partial_group_drop<VEC, 8, 8>), blocks_for(p.n_chunks, 4), p);
-        else                 GNX_LAUNCH((k_spmm_long_partial_group_drop<VEC, 4, 4>), blocks_for(p.n_chunks, 4), p);
+        if (lanes > 16)      GNX_LAUNCH((k_spmm_long_partial_group_drop<VEC, 32, 8, E>), blocks_for(p.n_chunks, 4), p);
+        else if (lanes > 8)  GNX_LAUNCH((k_spmm_long_partial_group_drop<VEC, 16, 8, E>), blocks_for(p.n_chunks, 4), p);
+        else if (lanes > 4)  GNX_LAUNCH((k_spmm_long_partial_group_drop<VEC, 8, 8, E>), blocks_for(p.n_chunks, 4), p);
+        else                 GNX_LAUNCH((k_spmm_long_partial_group_drop<VEC, 4, 4, E>), blocks_for(p.n_chunks, 4), p);
     }
 #endif
-    else if (lanes > 16) GNX_LAUNCH((k_spmm_long_partial_group_drop<VEC, 32, DROP_LONG_U>), blocks_for(p.n_chunks, 4), p);
-    else if (lanes > 8)  GNX_LAUNCH((k_spmm_long_partial_group_drop<VEC, 16, DROP_LONG_U>), blocks_for(p.n_chunks, 4), p);
-    else if (lanes > 4)  GNX_LAUNCH((k_spmm_long_partial_group_drop<VEC, 8, DROP_LONG_U>), blocks_for(p.n_chunks, 4), p);
-    else                 GNX_LAUNCH((k_spmm_long_partial_group_drop<VEC, 4, 4>), blocks_for(p.n_chunks, 4), p);
+    else if (lanes > 16) GNX_LAUNCH((k_spmm_long_partial_group_drop<VEC, 32, DROP_LONG_U, E>), blocks_for(p.n_chunks, 4), p);
+    else if (lanes > 8)  GNX_LAUNCH((k_spmm_long_partial_group_drop<VEC, 16, DROP_LONG_U, E>), blocks_for(p.n_chunks, 4), p);
+    else if (lanes > 4)  GNX_LAUNCH((k_spmm_long_partial_group_drop<VEC, 8, DROP_LONG_U, E>), blocks_for(p.n_chunks, 4), p);
+    else                 GNX_LAUNCH((k_spmm_long_partial_group_drop<VEC, 4, 4, E>), blocks_for(p.n_chunks, 4), p);
     GNX_LAUNCH((k_spmm_long_reduce<VEC>), blocks_for(p.n_long, 4), p);
+}
+
+template <bool E>
+const char *launch_dropped(const SpmmArgs &p, int vec, bool has_long, hipStream_t s) {
+    const char *name;
+    if (vec == 4)      { name = launch_rows_drop<4, E>(p, s); if (has_long) launch_long_drop<4, E>(p, s); }
+    else if (vec == 2) { name = launch_rows_drop<2, E>(p, s); if (has_long) launch_long_drop<2, E>(p, s); }
+    else               { name = launch_rows_drop<1, E>(p, s); if (has_long) launch_long_drop<1, E>(p, s); }
+    return name;
+}
+
+// per-entry dropout of duplicated COO entries needs the tables gnx_graph_enable_entry_dropout builds
+int refuse_duplicates(const gnx_graph *g, const char *fn) {
+    if (!g->has_dups || g->entry_drop) return GNX_OK;
+    set_error("%s: the graph holds duplicate COO entries: call gnx_graph_enable_entry_dropout on the handle first (or use "
+              "gnx_graph_normalize + gnx_spmm)", fn);
+    return GNX_ERR_UNSUPPORTED;
+}
+
+// what a fused launch over handle g reads as its per-slot values (after ensure_transpose when `transposed`), and the entry tables
+// of a handle with duplicates
+void set_values(const gnx_graph *g, bool transposed, SpmmArgs &p) {
+    if (!g->has_dups) {
+        p.vals = transposed ? g->t_raw : g->raw_vals;
+        return;
+    }
+    p.vals = transposed ? g->t_ed_vals : g->ed_vals;
+    p.fuse.mult = transposed ? g->t_ed_mult : g->ed_mult;
+    p.fuse.e_vals = g->e_vals;
+    p.fuse.slot_ptr = g->slot_ptr;
+    p.fuse.perm = transposed ? g->t_perm : nullptr;
 }
 
 }  // namespace
@@ -249,11 +287,7 @@ void launch_long_drop(const SpmmArgs &p, hipStream_t s) {
 namespace gnx {
 
 const char *launch_spmm_dropped(const SpmmArgs &p, int vec, bool has_long, hipStream_t s) {
-    const char *name;
-    if (vec == 4)      { name = launch_rows_drop<4>(p, s); if (has_long) launch_long_drop<4>(p, s); }
-    else if (vec == 2) { name = launch_rows_drop<2>(p, s); if (has_long) launch_long_drop<2>(p, s); }
-    else               { name = launch_rows_drop<1>(p, s); if (has_long) launch_long_drop<1>(p, s); }
-    return name;
+    return p.fuse.mult ? launch_dropped<true>(p, vec, has_long, s) : launch_dropped<false>(p, vec, has_long, s);
 }
 
 }  // namespace gnx
@@ -269,17 +303,15 @@ int gnx_spmm_dropped(gnx_graph_t g, const float *d_D, float dropout_p, uint64_t 
     GNX_CHECK_ARG(d_D != nullptr, "gnx_spmm_dropped: NULL degree scales");
     GNX_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "dropout rate %g outside [0, 1)", (double)dropout_p);
     GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols || g->blk_col_gid != nullptr, "gnx_spmm_dropped: needs a square graph or a vertex block (gnx_graph_set_block)");
-    if (g->has_dups) {   // per-entry dropout of duplicated COO entries needs the entry lists: use gnx_graph_normalize + gnx_spmm
-        set_error("gnx_spmm_dropped: the graph holds duplicate COO entries");
-        return GNX_ERR_UNSUPPORTED;
-    }
+    rc = refuse_duplicates(g, "gnx_spmm_dropped");
+    if (rc != GNX_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (transposed) {
         rc = ensure_transpose(g, s);
         if (rc != GNX_OK) return rc;
     }
     SpmmArgs p{};
-    p.vals = transposed ? g->t_raw : g->raw_vals;
+    set_values(g, transposed, p);
     p.X = d_X; p.ldx = ldx; p.H0 = d_H0; p.ldh0 = ldh0; p.beta = beta; p.alpha = alpha; p.act = act;
     p.out = d_out; p.ldo = ldo; p.C = (int)C;
     p.fuse.D = d_D; p.fuse.seed = seed; p.fuse.stream = stream_id; p.fuse.offset = g->stream_offset;
@@ -301,12 +333,10 @@ int gnx_spmm_dropped_chained(gnx_graph_t g, const float *d_D, float dropout_p, u
     GNX_CHECK_ARG(d_D != nullptr, "gnx_spmm_dropped_chained: NULL degree scales");
     GNX_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "dropout rate %g outside [0, 1)", (double)dropout_p);
     GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols || g->blk_col_gid != nullptr, "gnx_spmm_dropped_chained: needs a square graph or a vertex block");
-    if (g->has_dups) {
-        set_error("gnx_spmm_dropped_chained: the graph holds duplicate COO entries");
-        return GNX_ERR_UNSUPPORTED;
-    }
+    rc = refuse_duplicates(g, "gnx_spmm_dropped_chained");
+    if (rc != GNX_OK) return rc;
     SpmmArgs p{};
-    p.vals = g->raw_vals;
+    set_values(g, false, p);
     p.X = d_X; p.ldx = ldx; p.H0 = d_H0; p.ldh0 = ldh0; p.beta = beta; p.alpha = alpha; p.act = act;
     p.out = d_out; p.ldo = ldo; p.C = (int)C;
     p.out_scale = d_D_next ? d_D_next + g->blk_row0_buf : nullptr;
@@ -335,16 +365,14 @@ int gnx_spmm_dropped_back(gnx_graph_t g, const float *d_D, float dropout_p, uint
                   "gnx_spmm_dropped_back: the pre-scaled output needs a buffer of its own");
     GNX_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "dropout rate %g outside [0, 1)", (double)dropout_p);
     GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols && g->blk_col_gid == nullptr, "gnx_spmm_dropped_back: needs a square stand-alone graph");
-    if (g->has_dups) {
-        set_error("gnx_spmm_dropped_back: the graph holds duplicate COO entries");
-        return GNX_ERR_UNSUPPORTED;
-    }
+    rc = refuse_duplicates(g, "gnx_spmm_dropped_back");
+    if (rc != GNX_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     rc = ensure_transpose(g, s);
     if (rc != GNX_OK) return rc;
     if (!g->t.empty_rows_unreferenced) act = GNX_ACT_NONE;               // honoured only when nobody gathers the rows it would leave untouched
     SpmmArgs p{};
-    p.vals = g->t_raw;
+    set_values(g, true, p);
     p.X = d_X; p.ldx = ldx; p.H0 = d_S_in; p.ldh0 = lds_in; p.beta = s_beta; p.alpha = s_alpha; p.act = act;
     p.out = d_S_out; p.ldo = lds_out; p.C = (int)C;
     p.out2 = d_Y_out; p.ldo2 = ldy; p.beta2 = y_beta; p.out2_scale = d_Y_out ? d_D_next : nullptr;

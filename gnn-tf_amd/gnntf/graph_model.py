@@ -41,6 +41,11 @@ class Structural(Layer):
 class GNN(Trainable):
     """gnn.py:29-50."""
 
+    # a graph whose COO holds duplicate entries (graph2adj of a both-direction graph) gets its entry tables the first time it
+    # propagates in training mode with edge dropout (DeviceGraph.enable_entry_dropout): the fused training kernels then run on it,
+    # same masks and values as the materialised form.  False: such graphs stay on the materialised form (A/B comparisons)
+    fuse_entry_dropout = True
+
     def __init__(self, graph, features, preprocessor: Layer = None, reorder=None, inference_dtype=torch.float32):
         """``reorder`` (opt-in, not in the reference): store the graph and the feature rows with the vertices relabelled; every
         [N, .] tensor inside the model then lives in that order, and the model's OUTPUT is put back into the caller's order, so
@@ -119,12 +124,19 @@ class GNN(Trainable):
         if graph_dropout != 0 and self.is_training():
             seed, stream = self._next_mask_stream()
             if normalized == "symmetric" and add_eye == "none":          # the values are produced inside the SpMM kernels
+                self._enable_entry_dropout()
                 return sparse.dropped_adjacency(self.graph, graph_dropout, seed, stream)
             return sparse.normalize(self.graph, normalized, add_eye, graph_dropout, seed, stream)
         key = (normalized, add_eye)
         if key not in self._adjacency_cache:
             self._adjacency_cache[key] = sparse.normalize(self.graph, normalized, add_eye)
         return self._adjacency_cache[key]
+
+    def _enable_entry_dropout(self):
+        """The entry tables of a graph with duplicate entries, once, before its first fused training propagation (fuse_entry_dropout)."""
+        g = self.graph
+        if self.fuse_entry_dropout and g.nnz_entries != g.nnz and g.n_rows == g.n_cols and not g.entry_dropout:
+            g.enable_entry_dropout()
 
 
 def _eval_storage(architecture) -> torch.dtype:
@@ -143,6 +155,8 @@ def _propagation_run(architecture: "GNN", H0_value, a, iterations, graph_dropout
     if training:
         seed, first = architecture._next_mask_stream(iterations)
         graph, p = architecture.graph, graph_dropout
+        if isinstance(architecture, GNN):
+            architecture._enable_entry_dropout()
         if sparse.can_fuse_dropout(graph, p):
             # the degree scales of all K iterations in one pass over the structure; kept (K x N floats) for the backward
             scales = sparse.dropped_degree_scales(graph, p, seed, first, iterations)

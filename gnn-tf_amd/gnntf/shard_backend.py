@@ -75,6 +75,10 @@ class NativeBackend:
             nat.check(nat.lib().gnx_graph_set_block(graph.handle, int(row0_global), int(row0_buf), nat.ptr(col_gid),
                                                     nat.current_stream()))
 
+    def enable_entry_dropout(self, graph):
+        """The entry tables of a block whose COO holds duplicate entries (gnx_graph_enable_entry_dropout)."""
+        graph.enable_entry_dropout()
+
     def colsum_streams(self, graph, p, seed, first_stream, n_streams):
         """[n_streams, n_cols]: this block's PARTIAL column sums of the dropped raw values, one row per dropout stream."""
         out = torch.empty((n_streams, graph.n_cols), dtype=torch.float32, device=graph.device)

@@ -190,7 +190,10 @@ class ShardedGraph:
         collective, capped in time, GNX_TUNE_OVERLAP=0 disables it as well).
         ``edge_dropout``: build the block for TRAINING with per-iteration edge dropout (layered.py:47-50 + gnn.py:41-42):
         raw values (``normalized`` is ignored -- every iteration re-normalises its own dropped entries), classic halo, whole
-        rows; use dropped_scales / propagate_dropped / propagate_dropped_backward instead of propagate()."""
+        rows; use dropped_scales / propagate_dropped / propagate_dropped_backward instead of propagate().  A COO with duplicate
+        entries is kept as given (every stored entry dropped on its own, the rank of a duplicate = its place among the duplicates
+        of its (row, col) in this rank's COO): each rank's COO must then list the duplicates of a (row, col) in the same relative
+        order as the whole graph's COO -- which any row filter of the whole COO does."""
         if cover not in ("cover", "pull"):
             raise Exception("ShardedGraph: cover must be 'cover' or 'pull'")
         self.edge_dropout = bool(edge_dropout)
@@ -240,8 +243,11 @@ class ShardedGraph:
         del g0, raw
         self.row_order = None
         self.nnz_local = int(colidx.numel())
-        if self.edge_dropout and self.nnz_local != int(idx_global.shape[0]):
-            raise Exception("ShardedGraph: edge dropout across blocks needs a COO without duplicate entries")
+        # duplicate entries with edge dropout: every stored entry is dropped on its own (layered.py:47-50), so the block keeps the
+        # entries as given -- the ranks of a (row, col)'s duplicates are their order in THIS rank's COO, which equals their order in
+        # the whole graph's COO whenever the rank's COO is a row filter of it (the contract of the caller) -- and the block's handle
+        # gets its entry tables (gnx_graph_enable_entry_dropout)
+        entry_dropout = self.edge_dropout and self.nnz_local != int(idx_global.shape[0])
         t = torch.tensor([self.nnz_local], dtype=torch.int64, device=dev)
         self.comm.all_reduce(t)
         self.nnz_global = int(t.item())
@@ -250,8 +256,13 @@ class ShardedGraph:
         if keep_entries:
             self.entries = [rowidx.to(torch.int64) + lo, colidx.to(torch.int64), nvals.clone(), None]
 
+        if entry_dropout:
+            rowidx, colidx, nvals = idx_global[:, 0] - lo, idx_global[:, 1], vals.to(torch.float32)
         if self.world == 1:
-            self._build_single_block(rowptr, colidx, nvals, relabel)
+            if entry_dropout:
+                self._build_single_block(None, None, None, False, coo=(torch.stack([rowidx, colidx], 1), nvals))
+            else:
+                self._build_single_block(rowptr, colidx, nvals, relabel)
         else:
             if tune_overlap and hasattr(self.comm, "tune_overlap"):
                 # (once per Comm) an exchange-lane stream whose transfers run beside the compute stream.  Every failure inside is agreed
@@ -262,11 +273,15 @@ class ShardedGraph:
                 if getattr(self.comm, "lane_stream", None) is not None:
                     self._lanes = _Lanes(dev, self.comm.lane_stream)
             self._build_block(rowidx.to(torch.int64), colidx.to(torch.int64), nvals, split_rows)
+        if entry_dropout:
+            be.enable_entry_dropout(self.graph)
 
     # ---- one vertex block: no exchange -----------------------------------------------------------------
-    def _build_single_block(self, rowptr, colidx, nvals, relabel):
+    def _build_single_block(self, rowptr, colidx, nvals, relabel, coo=None):
         be, dev = self.backend, self.device
-        if relabel and colidx.numel() > 0:
+        if coo is not None:                                  # the entries as given (edge dropout over duplicate entries)
+            g = be.graph_from_coo(coo[0], coo[1], (self.n_local, self.n_local))
+        elif relabel and colidx.numel() > 0:
             deg = rowptr[1:] - rowptr[:-1]
             order = torch.argsort(deg, descending=True, stable=True)                 # new id -> old id
             newid = torch.empty_like(order)

@@ -91,10 +91,26 @@ class DeviceGraph:
         nat.check(lib.gnx_graph_info(self._h, byref(n_rows), byref(n_cols), byref(nnz_e), byref(nnz_c)))
         self.n_rows, self.n_cols = n_rows.value, n_cols.value
         self.nnz_entries, self.nnz = nnz_e.value, nnz_c.value
+        self._entry_dropout = False
 
     @property
     def handle(self):
         return self._h
+
+    @property
+    def entry_dropout(self) -> bool:
+        """Whether enable_entry_dropout() has run on this graph: the fused training kernels then accept its duplicate entries."""
+        return getattr(self, "_entry_dropout", False)
+
+    def enable_entry_dropout(self):
+        """Builds NOW what the fused training kernels need on a graph whose COO holds duplicate entries (graph2adj of a graph that
+        stores both directions: every entry twice): per coalesced slot its multiplicity and shared value, in CSR and transposed
+        order (gnx_graph_enable_entry_dropout).  Edge dropout then stays per stored entry (layered.py:47-50), bit for bit what the
+        materialised form gives, without writing a value array per iteration.  Allocates and synchronises: call before capturing.
+        Does nothing on a graph without duplicates."""
+        with nat.on_device(self.device):
+            nat.check(nat.lib().gnx_graph_enable_entry_dropout(self._h, nat.current_stream()))
+        self._entry_dropout = True
 
     def csr_arrays(self, with_rows=False):
         """Copies of (rowptr int64, colidx int32, raw values float32[, rowidx int32])."""
@@ -214,12 +230,12 @@ def dropped_degree_scales(graph: DeviceGraph, p, seed, first_stream, n_streams) 
 
 
 def can_fuse_dropout(graph: DeviceGraph, p) -> bool:
-    return graph.nnz_entries == graph.nnz and graph.n_rows == graph.n_cols and p > 0
+    return graph.n_rows == graph.n_cols and p > 0 and (graph.nnz_entries == graph.nnz or graph.entry_dropout)
 
 
 def dropped_adjacency(graph: DeviceGraph, p, seed, stream_id, D=None) -> Adjacency:
-    """A training iteration's adjacency: the fused form when the graph allows it (no duplicate COO entries, square),
-    else the materialised one.  ``D``: its degree scales if already known (dropped_degree_scales)."""
+    """A training iteration's adjacency: the fused form when the graph allows it (square; no duplicate COO entries, or
+    enable_entry_dropout() called), else the materialised one.  ``D``: its degree scales if already known (dropped_degree_scales)."""
     if can_fuse_dropout(graph, p):
         return DroppedAdjacency(graph, p, seed, stream_id, D=D)
     return normalize(graph, "symmetric", "none", p, seed, stream_id)
@@ -498,9 +514,11 @@ class _PPRLoop(torch.autograd.Function):
         H = H0
         first = make_adj(0, False) if K > 0 else None
         kept = []
-        if K > 1 and isinstance(first, DroppedAdjacency) and not relu:
+        if K > 1 and isinstance(first, DroppedAdjacency) and not relu and first.graph.nnz_entries == first.graph.nnz:
             # weights made in the kernels (only the K degree-scale vectors exist): the next iteration's column scale rides out with
-            # the rows, so from k = 1 on no per-entry scale gather is left (gnx_spmm_dropped_chained)
+            # the rows, so from k = 1 on no per-entry scale gather is left (gnx_spmm_dropped_chained).  Not on graphs with duplicate
+            # entries: their fused form replaces the materialised one, whose results it keeps bit for bit (one gnx_spmm_dropped per
+            # iteration, below), where the chained loop would round differently
             adjs = [first] + [make_adj(k, False) for k in range(1, K)]
             chained = all(isinstance(adj, DroppedAdjacency) and adj.graph is first.graph for adj in adjs)
             ctx.chained = chained and first.graph.n_rows == first.graph.n_cols

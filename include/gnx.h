@@ -52,8 +52,9 @@ const char *gnx_last_error(void);
  * the same names between 0.2 and 0.3 (gnx_halo_plan_create / _layout / _pack / _exchange gained `part` and split pull / push
  * counts; gnx_gcnii_step's d_work became d_mixed), so a 0.2 client linked against a 0.3+ library passes shifted arguments.
  * 0.4 adds gnx_graph_reserve and changes no existing signature; 0.5 adds gnx_graph_set_row_window, 0.6 gnx_appnp_propagate_act,
- * likewise; 0.6.1 adds the bf16 storage entries (gnx_cast_bf16, gnx_spmm_bf16, gnx_appnp_propagate_bf16) and changes nothing else. */
-#define GNX_ABI_VERSION 601
+ * likewise; 0.6.1 adds the bf16 storage entries (gnx_cast_bf16, gnx_spmm_bf16, gnx_appnp_propagate_bf16) and changes nothing else;
+ * 0.7 adds gnx_graph_enable_entry_dropout (the fused training entries accept handles with duplicate entries once it was called). */
+#define GNX_ABI_VERSION 701
 int gnx_version(void);
 
 /* ---- graph construction ------------------------------------------------------------
@@ -111,6 +112,16 @@ int gnx_graph_normalize(gnx_graph_t g, int normalized, int add_eye, float dropou
  * caller decides when it is sized.)  Nothing in the reference corresponds: TensorFlow eager allocates per op. */
 enum { GNX_RESERVE_TRANSPOSED = 1, GNX_RESERVE_K_LOOP = 2 };
 int gnx_graph_reserve(gnx_graph_t g, int64_t C, int flags, void *stream);
+
+/* gnx_graph_enable_entry_dropout: builds, NOW, what the fused training entries (gnx_spmm_dropped, gnx_spmm_dropped_chained,
+ * gnx_spmm_dropped_back) and the one-pass column sums of gnx_graph_colsum_streams need on a handle whose COO held duplicate entries
+ * -- what graph2adj makes of a graph that stores both directions already (graph_manipulation.py:28-30): every (row, col) twice.
+ * Per coalesced slot a multiplicity byte and the value its entries share, in CSR and in transposed order (5 bytes per slot each,
+ * plus the transposed structure); slots whose entries differ walk the entry list.  The draws and sums stay those of
+ * gnx_graph_normalize: keep bit = hash(seed, stream, row, col, duplicate rank), slot value = its kept entries * 1/(1-p) added in
+ * input order.  Allocates and synchronises: call before capturing.  Until it has been called those entries return
+ * GNX_ERR_UNSUPPORTED on such a handle; on a handle without duplicates it does nothing.  Nothing in the reference corresponds. */
+int gnx_graph_enable_entry_dropout(gnx_graph_t g, void *stream);
 
 /* gnx_graph_set_row_window: the caller declares that ITS numbering of the vertices carries locality -- neighbours in the graph
  * are neighbours in the numbering (a community / breadth-first order of the dataset; gnntf's GNN(reorder="locality") computes one).
@@ -210,9 +221,9 @@ int gnx_spmm_scatter(gnx_graph_t g, const float *d_vals, const float *d_diag, co
  * gnx_degree_scale(d_D, n, GNX_NORM_SYMMETRIC, 0).  Saves the nnz-sized value array and the pass that writes it
  * (layered.py:47-50 + gnn.py:41-42 happen in the SpMM's value fetch).  PRECONDITION: finite d_X and d_D -- a dropped entry is
  * skipped (its row of d_X is not read), while the two-call form multiplies it by an explicit zero, so a non-finite row behind a
- * dropped entry, or a NaN scale, turns the two-call result into NaN and not this one.  Square graphs or vertex blocks (gnx_graph_set_block);
- * GNX_ERR_UNSUPPORTED when the COO held
- * duplicate entries (their per-entry dropout needs the entry lists: use gnx_graph_normalize). */
+ * dropped entry, or a NaN scale, turns the two-call result into NaN and not this one.  Square graphs or vertex blocks (gnx_graph_set_block).
+ * When the COO held duplicate entries (per-entry dropout: a slot's weight is made from its kept entries) the handle needs
+ * gnx_graph_enable_entry_dropout first; without it GNX_ERR_UNSUPPORTED (use gnx_graph_normalize), as for the two entries below. */
 int gnx_spmm_dropped(gnx_graph_t g, const float *d_D, float dropout_p, uint64_t seed, uint64_t stream_id, int transposed,
                      const float *d_X, int64_t ldx, int64_t C, const float *d_H0, int64_t ldh0, float beta, float alpha,
                      int act, float *d_out, int64_t ldo, void *stream);
@@ -238,7 +249,8 @@ int gnx_spmm_dropped_chained(gnx_graph_t g, const float *d_D, float dropout_p, u
  * column scale is left -- in the un-chained form (gnx_spmm_dropped, transposed) that gather fetches a 128-byte line per kept
  * entry (profiles/NOTES.md round 4: +4.5 GB per launch at config 4, C = 64).  The loop: X = upstream gradient, S_in = X,
  * s_alpha = a for the first call; afterwards X = the previous Y_out, S_in = S_out, s_alpha = 1; s_beta = a (1-a), y_beta = 1-a;
- * the last call (stream 0) adds g_0 whole: s_beta = 1-a, no Y_out.  Square stand-alone graphs without duplicate entries.
+ * the last call (stream 0) adds g_0 whole: s_beta = 1-a, no Y_out.  Square stand-alone graphs (with duplicate entries: after
+ * gnx_graph_enable_entry_dropout).
  * act: GNX_ACT_NONE, or GNX_ACT_SKIP_EMPTY (with S_in == S_out) for every call but the first of a loop: rows without entries
  * contribute g_k = 0, so their sum stays what the first call made it and their Y row is never gathered -- they are left untouched
  * (honoured only on graphs where no entry references a row without entries; gnx_spmm_dropped_chained takes the same flag for
