@@ -9,7 +9,7 @@
 
 #include "../../include/gnx.h"
 
-#define GNX_VERSION_NUM GNX_ABI_VERSION /* 0.6.0: the header's number */
+#define GNX_VERSION_NUM GNX_ABI_VERSION /* the header's number (include/gnx.h) */
 
 namespace gnx {
 
@@ -166,7 +166,20 @@ __device__ __forceinline__ uint32_t hash_u24(uint64_t seed, uint64_t stream, uin
 // Entry dropout on a handle with duplicate COO entries (gnx_graph_enable_entry_dropout): per coalesced slot a multiplicity byte;
 // ENTRY_GENERAL marks a slot whose entries are not all the same float (or more than 254 of them), whose value is then the walk
 // of its entry list.  Kept sum of a slot = its kept entries * 1/(1-p), added in input order exactly as slot_value (gnx_prep.hip)
-// writes it.  For a uniform slot every term is the same float, so the m-fold loop over one value is bit for bit the walk of the list.
+// writes it.  For a uniform slot every term is the same float, so the m-fold loop over one value is bit for bit the walk of the list
+// -- as long as both round alike.  kept_term spells the rounding out: the product is rounded on its own and then added, which is what
+// the reference does (tf.nn.dropout scales the values, layered.py:50; the entries of a slot are summed afterwards).  Written as
+// `sum += value * scale` the compiler contracts the walk of a list into fmaf(value, scale, sum) but hoists the product of a uniform
+// slot out of its loop: with three or more kept entries and a scale that is no power of two (p = 0.1, 0.9) the two sums differed in
+// the last bit, and a slot holding +v and -v, both kept, summed to the rounding residue of v * scale instead of 0 -- a negative
+// column sum, hence a NaN degree scale, when nothing else of the column is kept.
+// (the pragma and not __fmul_rn / __fadd_rn: HIP defines those as the plain operators, which are contracted all the same)
+__device__ __forceinline__ float kept_term(float acc, float value, float scale) {
+#pragma clang fp contract(off)
+    const float term = value * scale;
+    return acc + term;
+}
+
 constexpr uint32_t ENTRY_GENERAL = 255;
 
 __device__ __forceinline__ float slot_kept_sum(uint64_t key, uint32_t thr, float scale, uint32_t m, float uval,
@@ -174,11 +187,11 @@ __device__ __forceinline__ float slot_kept_sum(uint64_t key, uint32_t thr, float
     float acc = 0.f;
     if (m != ENTRY_GENERAL) {
         for (uint32_t i = 0; i < m; ++i)
-            if (hash_rank(key, i) >= thr) acc += uval * scale;
+            if (hash_rank(key, i) >= thr) acc = kept_term(acc, uval, scale);
     } else {
         const int64_t b = slot_ptr[slot], e = slot_ptr[slot + 1];
         for (int64_t i = b; i < e; ++i)
-            if (hash_rank(key, (uint64_t)(i - b)) >= thr) acc += e_vals[i] * scale;
+            if (hash_rank(key, (uint64_t)(i - b)) >= thr) acc = kept_term(acc, e_vals[i], scale);
     }
     return acc;
 }

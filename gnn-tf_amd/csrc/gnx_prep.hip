@@ -37,7 +37,7 @@ __device__ __forceinline__ float slot_value(const float *__restrict__ raw, const
     const int64_t b = d.slot_ptr[k], e = d.slot_ptr[k + 1];
     const uint64_t kr = key_row(d, row), kc = key_col(d, col);
     for (int64_t i = b; i < e; ++i)
-        if (hash_u24(d.seed, stream_of(d), kr, kc, (uint64_t)(i - b)) >= d.thr) acc += d.e_vals[i] * d.scale;
+        if (hash_u24(d.seed, stream_of(d), kr, kc, (uint64_t)(i - b)) >= d.thr) acc = kept_term(acc, d.e_vals[i], d.scale);   // (gnx_internal.h: slot_kept_sum rounds alike)
     return acc;
 }
 

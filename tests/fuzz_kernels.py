@@ -5,14 +5,17 @@
     python tests/fuzz_kernels.py --dump CASE SEED OUT.npz    write one case's drawn inputs as a fixture (no GPU needed)
 
 ``draw_case`` makes every random draw of a case on the host (numpy only: replaying a seed needs no GPU), ``check_case`` runs the
-kernels on it.  tests/test_gpu_fuzz.py runs a fixed 200-case slice under ``-m gpu`` and pins the one miss the long runs ever
-produced (seed 303, case 1081; tests/golden/fuzz_seed303_case1081.npz)."""
-import os, sys, time
+kernels on it.  ``draw_extra`` draws the inputs of the two riders ("entries": the training kernels on a COO with duplicates after
+enable_entry_dropout, on the kind-1 cases; "bf16": gnx_spmm_bf16 / gnx_appnp_propagate_bf16, on the kind-0 and kind-2 cases) from a
+child generator of (seed, case, tag), so the stream ``draw_case`` reads stays what it was (tests/test_fuzz_draws.py pins it).
+tests/test_gpu_fuzz.py runs a fixed 200-case slice under ``-m gpu`` and pins the one miss the long runs ever produced (seed 303,
+case 1081; tests/golden/fuzz_seed303_case1081.npz)."""
+import hashlib, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "gnn-tf_amd"), os.path.join(ROOT, "tests")]
 import numpy as np
 
-KINDS = ("spmm", "dropped", "kloop", "gcnii", "dense", "wgrad", "head", "edge")
+KINDS = ("spmm", "dropped", "kloop", "gcnii", "dense", "wgrad", "head", "edge", "entries", "bf16")
 DROP_SEED = 5                                    # seed of the counter RNG in the edge-dropout cases (streams = case number + k)
 
 
@@ -80,12 +83,103 @@ def draw_case(rng, case):
     return s
 
 
+ENTRY_MODES = ("twice", "share", "many", "plus_minus")
+MANY = (253, 254, 255, 256, 300)                 # entries of one slot around the multiplicity byte's limit (254: the last uniform slot)
+A_LOOP = 0.1                                     # teleport weight of the training loops
+
+
+def _kept_column_sums_negative(e_idx, e_vals, s):
+    """Whether some column's kept values sum to less than zero under one of the case's K dropout streams (the oracle's keep masks:
+    host arithmetic).  A negative column sum makes a NaN degree scale, which is outside what the fused form promises."""
+    from oracle import gnntf_oracle as orc
+    for k in range(s["K"]):
+        keep = orc.keep_mask(e_idx, s["p"], DROP_SEED, s["case"] + k)
+        sums = np.bincount(e_idx[keep, 1], weights=e_vals[keep].astype(np.float64), minlength=s["n"])
+        if (sums < -1e-9).any():
+            return True
+    return False
+
+
+def draw_extra(seed, case, s):
+    """The riders' draws of case ``case``, from a child generator of (seed, case, tag): nothing is taken from the stream draw_case
+    reads.  Keys carry the rider's prefix (``e_``: entries, ``b_``: bf16).  Returns {} for a case without a rider."""
+    kind, x = s["kind"], {}
+    if kind == 1 and s.get("nnz"):
+        rng = np.random.default_rng([seed, case, 1])
+        idx, vals, nnz = s["idx"], s["vals"], s["nnz"]
+        mode = int(rng.integers(len(ENTRY_MODES)))
+        for attempt in range(8):
+            if mode == 0:                        # graph2adj of a graph that holds both directions: every entry twice, equal values
+                e_idx, e_vals = np.concatenate([idx, idx]), np.concatenate([vals, vals])
+            elif mode == 1:                      # a share of the entries 2 ... 4 times, unequal values
+                pick = np.flatnonzero(rng.random(nnz) < rng.uniform(0.05, 0.6))
+                if len(pick) == 0:
+                    pick = np.array([int(rng.integers(nnz))])
+                rep = np.repeat(pick, rng.integers(1, 4, size=len(pick)))
+                e_idx = np.concatenate([idx, idx[rep]])
+                e_vals = np.concatenate([vals, (vals[rep] * rng.uniform(0.5, 1.5, len(rep))).astype(np.float32)])
+            elif mode == 2:                      # one or two slots of m equal entries, in half the draws one of them another value
+                e_idx, e_vals = [idx], [vals]
+                for slot in rng.choice(nnz, size=min(nnz, int(rng.integers(1, 3))), replace=False):
+                    m = int(rng.choice(MANY))
+                    more = np.full(m - 1, vals[slot], dtype=np.float32)
+                    if rng.random() < 0.5:
+                        more[int(rng.integers(m - 1))] *= np.float32(0.5)
+                    e_idx.append(np.repeat(idx[slot:slot + 1], m - 1, axis=0)); e_vals.append(more)
+                e_idx, e_vals = np.concatenate(e_idx), np.concatenate(e_vals)
+            else:                                # one slot holding +v and -v
+                slot = int(rng.integers(nnz))
+                e_idx = np.concatenate([idx, idx[slot:slot + 1]])
+                e_vals = np.concatenate([vals, -vals[slot:slot + 1]])
+            order = rng.permutation(len(e_idx))  # input order among duplicates is part of the semantics
+            e_idx, e_vals = e_idx[order], e_vals[order].astype(np.float32)
+            # the -v entry may be the only kept one of its column: sqrt of a negative column sum.  Such a draw is redrawn (another
+            # slot), and after 8 of them the case takes the graph2adj shape
+            if mode != 3 or not _kept_column_sums_negative(e_idx, e_vals, s):
+                break
+            if attempt == 6:
+                mode = 0
+        x.update(e_mode=mode, e_idx=e_idx, e_vals=e_vals)
+    elif kind == 0 or (kind == 2 and s.get("nnz")):
+        rng = np.random.default_rng([seed, case, 2])
+        x["b_out_bf16"] = bool(rng.random() < 0.5)
+        x["b_diag"] = bool(rng.random() < 0.4) and s["sq"]
+        x["b_bias"] = bool(rng.random() < 0.3)
+        x["b_skip_empty"] = bool(rng.random() < 0.4)
+        x["b_pad"] = int(rng.choice([0, 1, 8, 24]))                      # operand: columns b_off ... b_off + C of a buffer C + b_pad wide
+        x["b_off"] = int(rng.integers(0, x["b_pad"] + 1))
+        x["b_relu"] = bool(rng.random() < 0.5)                            # (the K loop; the single SpMM takes the case's own relu draw)
+        x["b_d"] = rng.uniform(0.5, 1.5, s["n"]).astype(np.float32)
+    return x
+
+
 def replay(seed, case):
-    """The inputs of (seed, case): the draws of every earlier case are made and thrown away."""
+    """The inputs of (seed, case), the riders' included: the draws of every earlier case are made and thrown away."""
     rng = np.random.default_rng(seed)
     for c in range(case):
         draw_case(rng, c)
-    return draw_case(rng, case)
+    s = draw_case(rng, case)
+    s.update(draw_extra(seed, case, s))
+    return s
+
+
+def case_digest(s):
+    """sha256 over what draw_case drew for one case (names, dtypes, shapes, bytes; scalars by value): the seed's contract as data
+    (tests/golden/fuzz_seed11_draw_digests.json, written before the riders existed)."""
+    h = hashlib.sha256()
+    for k in sorted(s):
+        v = s[k]
+        h.update(k.encode() + b"=")
+        if isinstance(v, np.ndarray):
+            h.update(f"{v.dtype.str}{v.shape}".encode() + np.ascontiguousarray(v).tobytes())
+        elif isinstance(v, (bool, np.bool_)):
+            h.update(b"T" if v else b"F")
+        elif isinstance(v, (int, np.integer)):
+            h.update(b"i%d" % int(v))
+        else:
+            h.update(b"f" + float(v).hex().encode())
+        h.update(b";")
+    return h.hexdigest()
 
 
 def dev(x):
@@ -104,22 +198,35 @@ def rel_rows(x, y, floor_share=1e-2):
 PASSED_ONLY_WITH_THE_FLOOR = [0]        # backward comparisons of this process that the 1 % floor let pass (run() reports the count)
 
 
-def training_loops(s):
+def training_loops(s, entries=False):
     """The dropped-edge training loops of one ``kind == 1`` case, every way they can be computed.  Returns a dict of device
-    tensors: forward chained / step by step, backward chained / step by step, plus the K adjacencies and degree scales."""
+    tensors: forward chained / step by step, backward chained / step by step, plus the K adjacencies and degree scales.
+    ``entries``: on the rider's COO with duplicates (``e_idx`` / ``e_vals``) after enable_entry_dropout().  ppr_loop never chains on
+    such a handle (it keeps the materialised form's bits), so the chained forward is launched here in the shape ppr_loop uses on
+    graphs without duplicates: prescaled from k = 1 on, the next iteration's scale riding out, skip_empty on all but the last."""
     import torch
     import gnntf
-    from gnntf.sparse import _launch
-    n, idx, vals, p, K, case = s["n"], s["idx"], s["vals"], s["p"], s["K"], s["case"]
-    a_ = 0.1
+    from gnntf.sparse import _launch, _launch_chained
+    n, p, K, case = s["n"], s["p"], s["K"], s["case"]
+    idx, vals = (s["e_idx"], s["e_vals"]) if entries else (s["idx"], s["vals"])
+    a_ = A_LOOP
     g = gnntf.DeviceGraph(gnntf.SparseCOO(idx, vals, (n, s["n_cols"])), device="cuda:0")
     if s.get("window"):
         g.set_row_window(s["window"])
+    if entries:
+        g.enable_entry_dropout()
     D = gnntf.sparse.dropped_degree_scales(g, p, DROP_SEED, case, K)
     adjs = [gnntf.sparse.dropped_adjacency(g, p, DROP_SEED, case + k, D=D[k]) for k in range(K)]
+    assert all(isinstance(adj, gnntf.sparse.DroppedAdjacency) for adj in adjs)
     H0, up = dev(s["H0"]), dev(s["X"])
     with torch.no_grad():
-        f_got = gnntf.sparse.ppr_loop(lambda k, bwd=False: adjs[k], H0, a_, K)
+        if entries:
+            f_got = H0
+            for k in range(K):
+                f_got = _launch_chained(adjs[k], f_got, H0, 1.0 - a_, a_, prescaled=k > 0, D_next=D[k + 1] if k + 1 < K else None,
+                                        skip_empty=k + 1 < K)
+        else:
+            f_got = gnntf.sparse.ppr_loop(lambda k, bwd=False: adjs[k], H0, a_, K)
         f_want = H0
         for k in range(K):
             f_want = _launch(adjs[k], f_want, H0, 1.0 - a_, a_, 0)
@@ -131,12 +238,14 @@ def training_loops(s):
     return dict(g=g, D=D, adjs=adjs, a=a_, f_got=f_got, f_want=f_want, b_got=b_got, b_want=b_want)
 
 
-def backward_float64(s, a_=0.1):
+def backward_float64(s, a_=A_LOOP, entries=False):
     """dH0 of the K dropped iterations in float64 through the oracle's materialised dropped adjacencies (A_k^T products with
-    scipy), and per row the sum of the absolute values of every term that enters it (the scale float32 rounding acts on)."""
+    scipy), and per row the sum of the absolute values of every term that enters it (the scale float32 rounding acts on).
+    ``entries``: of the rider's COO with duplicates."""
     import scipy.sparse as sp
     from oracle import gnntf_oracle as orc
-    n, idx, vals, p, K, case = s["n"], s["idx"], s["vals"], s["p"], s["K"], s["case"]
+    n, p, K, case = s["n"], s["p"], s["K"], s["case"]
+    idx, vals = (s["e_idx"], s["e_vals"]) if entries else (s["idx"], s["vals"])
     ref_g = s["X"].astype(np.float64)
     mag_g = np.abs(ref_g)
     ref, mag = a_ * ref_g, a_ * mag_g
@@ -150,8 +259,168 @@ def backward_float64(s, a_=0.1):
     return ref, mag
 
 
+EPS = 2.0 ** -24                                  # one float32 rounding (half an ulp, relative)
+BF16_BAND = 1e-4                                  # |value before the activation| below this share of mag: a cancelling sum
+BF16_BAND_CAP = 0.01                              # at most this share of a case's elements may lie in the band
+
+
+def check_entries(s):
+    """Rider "entries": the ENTRIES instantiations of the training kernels on the case's COO with duplicates."""
+    import torch
+    import gnntf
+    from gnntf.sparse import _launch
+    from oracle import gnntf_oracle as orc
+    case, n, C, p, K, X, H0 = (s[k] for k in ("case", "n", "C", "p", "K", "X", "H0"))
+    idx, vals = s["e_idx"], s["e_vals"]
+    r = training_loops(s, entries=True)
+    g = r["g"]
+    assert g.nnz_entries > g.nnz and g.entry_dropout, f"entries case {case}: no duplicates on the handle"
+    longest = int(np.bincount(idx[:, 0], minlength=n).max())
+    fused = r["adjs"][0]
+    two = gnntf.normalize(g, "symmetric", "none", dropout=p, seed=DROP_SEED, stream_id=case)
+    for tr in (False, True):
+        a_ = _launch(fused, dev(X), dev(H0), 0.9, 0.1, 0, transposed=tr)
+        name = g.last_kernel()
+        b_ = _launch(two, dev(X), dev(H0), 0.9, 0.1, 0, transposed=tr)
+        assert name.endswith("_entries"), f"entries case {case}: {name}"
+        assert torch.equal(a_, b_), f"entries case {case} mode {s['e_mode']} transposed={tr}: {float((a_ - b_).abs().max())}"
+    ai, av = orc.get_adjacency(idx, vals, (n, n), graph_dropout=p, training=True, seed=DROP_SEED, stream=case, dtype=np.float64)
+    want = orc.sparse_dense_matmul(ai, av, (n, n), X.astype(np.float64)) * 0.9 + 0.1 * H0
+    atol = 2e-4 + 1e-5 * np.sqrt(longest) + 1e-7 * longest
+    np.testing.assert_allclose(_launch(fused, dev(X), dev(H0), 0.9, 0.1, 0).cpu().numpy(), want, rtol=1e-4, atol=atol,
+                               err_msg=f"entries case {case} mode {s['e_mode']} against float64")
+    for k in range(K):
+        assert torch.equal(r["D"][k], gnntf.sparse.dropped_degree_scales(g, p, DROP_SEED, case + k, 1)[0]), f"entries scales case {case} stream {k}"
+    tol = 2e-5 * (1.0 + np.sqrt(longest) / 10.0)
+    e_f = float(rel_rows(r["f_got"], r["f_want"], floor_share=0.0).max())
+    assert e_f < tol, f"entries chained forward case {case} mode {s['e_mode']}: {e_f} (tol {tol})"
+    e_b = rel_rows(r["b_got"], r["b_want"])
+    if float(e_b.max()) >= tol:
+        # float64 through the materialised dropped adjacencies decides: the chained result must be as close to it as the step
+        # loop is, or within 8 roundings of the sum of the absolute values of a row's terms (the pinned case's rule)
+        ref, mag = backward_float64(s, r["a"], entries=True)
+        e_chained = np.abs(r["b_got"].double().cpu().numpy() - ref)
+        e_steps = np.abs(r["b_want"].double().cpu().numpy() - ref)
+        allowed = np.maximum(e_steps, 8 * EPS * np.maximum(mag, 1e-30))
+        assert (e_chained <= allowed).all(), (f"entries chained backward case {case} mode {s['e_mode']}: chained vs steps {float(e_b.max()):.3e} "
+                                              f"(tol {tol:.3e}); vs float64 {float((e_chained / np.maximum(mag, 1e-30)).max() / EPS):.1f} roundings of "
+                                              f"sum|terms|; n={n} C={C} p={p} K={K} longest={longest}")
+    return "entries"
+
+
+def bf16_operand(s):
+    """The bf16 operand of a kind-0 case: bf(X), as bit patterns and as the float64 values the kernel gathers."""
+    from bf16_ref import bf16_bits, bf16_decode
+    bits = bf16_bits(s["X"])
+    return bits, bf16_decode(bits).astype(np.float64)
+
+
+def bf16_spmm_reference(s, beta=0.8, alpha=0.2):
+    """Float64 value BEFORE the activation of the kind-0 bf16 rider, and mag = |beta| (|A| |x| + |d| |x|) + |alpha h0| (numpy and
+    scipy alone: tests/test_fuzz_draws.py bounds the share of cancelling elements with it, no GPU needed)."""
+    import scipy.sparse as sp
+    n, n_cols, idx, vals = s["n"], s["n_cols"], s["idx"], s["vals"]
+    x = bf16_operand(s)[1]
+    A = sp.coo_matrix((vals.astype(np.float64), (idx[:, 0], idx[:, 1])), shape=(n, n_cols)).tocsr()      # duplicates are summed
+    S, M = A @ x, abs(A) @ np.abs(x)
+    if s["b_diag"]:
+        d = s["b_d"].astype(np.float64)
+        S, M = S + d[:, None] * x, M + d[:, None] * np.abs(x)
+    h0 = (s["H0"][:1] if s["b_bias"] else s["H0"]).astype(np.float64)
+    b, a = float(np.float32(beta)), float(np.float32(alpha))
+    return b * S + a * h0, abs(b) * M + np.abs(a * h0)
+
+
+def check_bf16_spmm(s, g):
+    """Rider "bf16" on a kind-0 case: one gnx_spmm_bf16 launch against float64 on the bf16-decoded operand."""
+    import torch
+    import gnntf
+    from gnntf import sparse, _native as nat
+    from bf16_ref import bf16_bits
+    case, n, C, relu = s["case"], s["n"], s["C"], s["relu"]
+    bits, _ = bf16_operand(s)
+    wide = np.full((s["n_cols"], C + s["b_pad"]), 0x7FC0, dtype=np.uint16)         # NaN around the operand's columns
+    wide[:, s["b_off"]:s["b_off"] + C] = bits
+    Xb = dev(wide.view(np.int16)).view(torch.bfloat16)[:, s["b_off"]:s["b_off"] + C]
+    h0 = dev(s["H0"][:1] if s["b_bias"] else s["H0"])
+    adj = sparse.Adjacency(g, None, dev(s["b_d"]) if s["b_diag"] else None)
+    out_bf16 = s["b_out_bf16"]
+    skip = s["b_skip_empty"] and not s["b_diag"]                                    # (ignored by the library when a diagonal is given)
+    act = (nat.ACT_RELU if relu else nat.ACT_NONE) | (nat.ACT_SKIP_EMPTY if s["b_skip_empty"] else 0)
+    if skip:        # rows without entries keep what the buffer held: a buffer of sevens
+        got = torch.full((n, C), 7.0, dtype=torch.bfloat16 if out_bf16 else torch.float32, device="cuda:0")
+        ldh0 = 0 if (s["b_bias"] and n != 1) else C
+        nat.check(nat.lib().gnx_spmm_bf16(g.handle, None, None, nat.ptr(Xb), Xb.stride(0), C, nat.ptr(h0), ldh0, 0.8, 0.2, act, nat.ptr(got),
+                                          1 if out_bf16 else 0, C, nat.current_stream()))
+    else:
+        got = sparse._launch_bf16(adj, Xb, h0, 0.8, 0.2, act, out_bf16=out_bf16)
+    assert g.last_kernel().endswith("_bf16") and got.dtype == (torch.bfloat16 if out_bf16 else torch.float32), f"bf16 case {case}: {g.last_kernel()}"
+    pre, mag = bf16_spmm_reference(s)
+    ref = np.maximum(pre, 0) if relu else pre
+    rows = np.ones(n, dtype=bool)
+    if skip:
+        rows = np.bincount(s["idx"][:, 0], minlength=n) > 0
+        assert (got[dev(~rows)].float() == 7.0).all(), f"bf16 case {case}: GNX_ACT_SKIP_EMPTY wrote a row without entries"
+    what = f"bf16 case {case}: n={n} C={C} relu={relu} " + " ".join(f"{k[2:]}={s[k]}" for k in sorted(s) if k.startswith("b_") and k != "b_d")
+    if not out_bf16:
+        gv = got.double().cpu().numpy()
+        bad = (np.abs(gv - ref) > 1e-5 * np.abs(ref) + 1e-5 * mag) & rows[:, None]
+        assert not bad.any(), (what, np.argwhere(bad)[:5], float(np.abs(gv - ref)[rows].max()))
+        return
+    band = np.abs(pre) < BF16_BAND * mag
+    assert band.mean() <= BF16_BAND_CAP, (what, "cancelling share", float(band.mean()))
+    gb = got.view(torch.int16).cpu().numpy().view(np.uint16).astype(np.int64)
+    wb = bf16_bits(ref.astype(np.float32)).astype(np.int64)
+    signed = lambda b: np.where(b >= 0x8000, -(b - 0x8000), b)              # one bf16 ulp = 1 in the bit pattern; +0 / -0 the same number
+    diff = np.abs(signed(gb) - signed(wb))
+    judged = ~band & rows[:, None]
+    cut = judged & (pre < 0) & relu                                          # below the relu floor by more than the band: exactly zero
+    assert ((gb[cut] & 0x7FFF) == 0).all(), (what, "relu", np.argwhere(cut & ((gb & 0x7FFF) != 0))[:5])
+    assert (diff[judged & ~cut] <= 1).all(), (what, np.argwhere((diff > 1) & judged & ~cut)[:5])
+
+
+def check_bf16_loop(s, g):
+    """Rider "bf16" on a kind-2 case: gnx_appnp_propagate_bf16 is deterministic, is K single gnx_spmm_bf16 steps bit for bit (bf16
+    results but for the last; the loop runs at the row width C itself on graphs this small) and follows the float64 emulation."""
+    import torch
+    import gnntf
+    import scipy.sparse as sp
+    from gnntf import sparse, _native as nat
+    from bf16_ref import appnp_bf16
+    case, n, C, K, relu = s["case"], s["n"], s["C"], s["K"], s["b_relu"]
+    a = 0.15
+    adj = gnntf.normalize(g, "symmetric", "before" if s["b_diag"] else "none")
+    H0 = dev(s["H0"])
+    got = sparse._appnp_propagate_bf16(adj, H0, a, K, relu)
+    assert g.last_kernel().endswith("_bf16"), f"bf16 loop case {case}: {g.last_kernel()}"
+    assert torch.equal(got, sparse._appnp_propagate_bf16(adj, H0, a, K, relu)), f"bf16 loop case {case} not repeatable"
+    what = f"bf16 loop case {case}: n={n} C={C} K={K} relu={relu} diag={s['b_diag']}"
+    if sparse.friendly_width_bf16(C, n) == C:
+        beta = 1.0 - float(np.float32(a))                                    # the library's (float)(1.0 - (double)a)
+        H = sparse.to_bf16(H0)
+        for k in range(K):
+            H = sparse._launch_bf16(adj, H, H0, beta, a, nat.ACT_RELU if relu else nat.ACT_NONE, out_bf16=k < K - 1)
+        assert torch.equal(got, H), (what, "loop vs single steps", float((got - H).abs().max()))
+    rowptr, colidx, _ = g.csr_arrays()
+    A = sp.csr_matrix((adj.vals.double().cpu().numpy(), colidx.cpu().numpy(), rowptr.cpu().numpy()), shape=(n, n))
+    want = appnp_bf16(A, s["H0"], a, K, relu=relu, diag=adj.diag.cpu().numpy() if adj.diag is not None else None)
+    err = np.linalg.norm(got.double().cpu().numpy() - want) / max(np.linalg.norm(want), 1e-30)
+    assert err <= 1e-3, (what, "against the emulation", err)
+
+
 def check_case(s):
-    """Runs the kernels on one drawn case; returns the name of the statistic it counts for (None: an empty graph, nothing run)."""
+    """Runs the kernels on one drawn case; returns the names of the statistics it counts for (none: an empty graph, nothing run):
+    the case's own kind and, with the rider's draws present (draw_extra), its rider's."""
+    kind = _check_case(s)
+    kinds = [kind] if kind is not None else []
+    if "e_idx" in s:
+        kinds.append(check_entries(s))
+    if "b_pad" in s and kind is not None:            # (checked inside the case: it shares the case's device graph)
+        kinds.append("bf16")
+    return kinds
+
+
+def _check_case(s):
     import torch
     import gnntf
     from gnntf.sparse import _launch, _dense_wgrad
@@ -174,6 +443,8 @@ def check_case(s):
                 gt = _launch(gnntf.Adjacency(g, dev(g.csr_arrays()[2].cpu().numpy())), dev(H0), None, 1.0, 0.0, 0, transposed=True).cpu().numpy()
                 wt = orc.sparse_dense_matmul(idx[:, ::-1], vals.astype(np.float64), (n_cols, n), H0.astype(np.float64))
                 np.testing.assert_allclose(gt, wt, rtol=1e-4, atol=2e-4 + 1e-5 * np.sqrt(int(np.bincount(idx[:, 1], minlength=n_cols).max())), err_msg=f"spmm_t case {case}")
+            if "b_pad" in s:
+                check_bf16_spmm(s, g)
             return "spmm"
         if kind == 1 and nnz:
             p, K = s["p"], s["K"]
@@ -225,6 +496,8 @@ def check_case(s):
             else:
                 spread = float(np.sqrt(max(np.bincount(idx[:, 0]).max(), 1)))
                 assert torch.allclose(got, H, rtol=1e-5, atol=2e-6 * spread), f"relu kloop case {case}: {float((got - H).abs().max())}"
+            if "b_pad" in s:
+                check_bf16_loop(s, g)
             return "kloop"
         if kind == 3 and nnz:
             adj = gnntf.normalize(g, "symmetric")
@@ -290,8 +563,8 @@ def run(cases, seed, first=0, verbose=True):
         s = draw_case(rng, case)
         if case < first:
             continue
-        kind = check_case(s)
-        if kind is not None:
+        s.update(draw_extra(seed, case, s))
+        for kind in check_case(s):
             stats[kind] += 1
         if verbose and case % 50 == 49:
             print(f"{case + 1} cases, {time.time() - t0:.0f} s", stats, flush=True)

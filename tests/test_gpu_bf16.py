@@ -221,6 +221,60 @@ def test_k_loop_large_graph(gnntf, C):
         assert torch.equal(pub, sparse.appnp_propagate(adj, H0, 0.1, 10))
 
 
+def test_k_loop_between_the_size_regimes(gnntf):
+    """40000 vertices (2^15 <= n < 2^20: rows cut at 128 entries, chunks and short rows in one launch) with hub rows above 128 and
+    above 512 entries: deterministic, and within the first-order bound of the f32 loop."""
+    from gnntf import sparse
+    n = 40000
+    coo, _, shape = graphs.rmat_symmetric_coo(n, 200000, seed=6)
+    rng = np.random.default_rng(6)
+    extra = []
+    for hub, deg in ((3, 200), (5, 700), (11, 1500)):
+        other = rng.choice(np.arange(16, n), size=deg, replace=False)
+        extra += [np.stack([np.full(deg, hub), other], 1), np.stack([other, np.full(deg, hub)], 1)]
+    coo = np.unique(np.concatenate([coo] + extra), axis=0)
+    g = device_graph(gnntf, coo, np.ones(len(coo), dtype=np.float32), shape)
+    degrees = np.diff(g.csr_arrays()[0].cpu().numpy())
+    assert ((degrees > 128) & (degrees <= 512)).any() and (degrees > 512).any()
+    adj = gnntf.normalize(g, "symmetric")
+    names = set()
+    for C in (8, 40, 256):
+        H0 = dev(rng.uniform(-1, 1, (n, C)).astype(np.float32))
+        for relu in (False, True):
+            got = _loop_bf16(sparse, adj, H0, 0.1, 10, relu)
+            names.add(g.last_kernel())
+            assert torch.equal(got, _loop_bf16(sparse, adj, H0, 0.1, 10, relu))
+            _check_bound(sparse, adj, H0, 0.1, 10, relu, got)
+            A = scipy_of(g, adj.vals)
+            want = appnp_bf16(A, H0.cpu().numpy(), 0.1, 10, relu=relu)
+            err = np.linalg.norm(got.double().cpu().numpy() - want) / np.linalg.norm(want)
+            assert err <= 1e-3, (C, relu, err)
+    assert all(name.endswith("_bf16") for name in names) and any("+chunks_bf16" in name for name in names), names
+
+
+@pytest.mark.parametrize("window", [64, 1000])
+def test_row_window_keeps_the_bits(gnntf, window):
+    """gnx_graph_set_row_window: another launch order, the same sums -- a bf16 SpMM (f32 and bf16 result) and the bf16 K loop."""
+    from gnntf import sparse, _native as nat
+    coo, vals, shape = hub_graph(3000, 3000, seed=9, symmetric=True)
+    rng = np.random.default_rng(window)
+    for C in (8, 100):
+        X = dev(rng.uniform(-1, 1, (shape[1], C)).astype(np.float32))
+        H0 = dev(rng.uniform(-1, 1, (shape[0], C)).astype(np.float32))
+        results = []
+        for w in (0, window):
+            g = device_graph(gnntf, coo, vals, shape)
+            if w:
+                g.set_row_window(w)
+            adj = gnntf.normalize(g, "symmetric")
+            results.append([sparse._launch_bf16(adj, X, H0, 0.9, 0.35, nat.ACT_RELU, out_bf16=False),
+                            sparse._launch_bf16(adj, X, H0, 0.9, 0.35, nat.ACT_NONE, out_bf16=True).view(torch.int16),
+                            _loop_bf16(sparse, adj, H0, 0.1, 4, False)])
+            assert g.last_kernel().endswith("_bf16")
+        for x, y in zip(*results):
+            assert torch.equal(x, y), (C, window)
+
+
 def test_public_spmm_storage(gnntf):
     from gnntf import sparse
     coo, vals, shape = graphs.rmat_symmetric_coo(3000, 20000, seed=2)

@@ -57,3 +57,27 @@ def test_seed_303_case_1081_chained_backward_against_float64(golden_dir, capsys)
     # (6.07e-5 when recorded: float32 noise of terms ~1 on a row of 1.1e-3) -- bounded from BOTH sides: a fixture that stopped
     # hitting the cancelling row would show ~1e-7 here and no longer test what it was pinned for
     assert 1e-5 < float(own.max()) < 1e-3
+
+
+def test_seed_808_case_913_slot_of_plus_and_minus_v(golden_dir):
+    """The long run of seed 808 (profiles/notes/fuzz_seed808_1200.txt), case 913, rider "entries": one vertex whose single slot
+    holds -v and +v, p = 0.1.  In three of the five streams both entries are kept: the slot sums to 0 as the reference's does
+    (each kept value scaled and rounded, then added), the degree scale is divide_no_nan's 0 and every weight is 0.  Contracted into
+    fmaf(value, scale, sum) the slot summed to the rounding residue of v / (1 - p), -2.5e-8: a negative column sum, NaN."""
+    import gnntf
+    from oracle import gnntf_oracle as orc
+    s = fz.load(os.path.join(golden_dir, "fuzz_seed808_case913.npz"))
+    assert (s["seed"], s["case"], s["n"], s["p"], s["K"], s["e_mode"]) == (808, 913, 1, 0.1, 5, 3)
+    assert s["e_vals"][0] == -s["e_vals"][1] and (s["e_idx"] == 0).all()
+    both = [orc.keep_mask(s["e_idx"], s["p"], fz.DROP_SEED, s["case"] + k).all() for k in range(s["K"])]
+    assert both == [True, True, False, False, True]
+    g = gnntf.DeviceGraph(gnntf.SparseCOO(s["e_idx"], s["e_vals"], (1, 1)), device="cuda:0")
+    for prepared in (False, True):
+        if prepared:
+            g.enable_entry_dropout()
+        D = gnntf.sparse.dropped_degree_scales(g, s["p"], fz.DROP_SEED, s["case"], s["K"]).cpu().numpy()[:, 0]
+        assert np.isfinite(D).all() and ((D == 0) == np.array(both)).all(), D
+        for k in range(s["K"]):
+            vals = gnntf.normalize(g, "symmetric", "none", dropout=s["p"], seed=fz.DROP_SEED, stream_id=s["case"] + k).vals
+            assert torch.isfinite(vals).all() and (float(vals[0]) == 0.0) == both[k]
+    assert fz.check_entries(s) == "entries"
