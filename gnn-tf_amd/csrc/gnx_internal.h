@@ -307,6 +307,12 @@ struct PerDeviceOnce {
 int launch_spmm(gnx_graph *g, const Csr &m, SpmmArgs &p, hipStream_t s);                      // gnx_spmm.hip
 void launch_long_rows(const SpmmArgs &p, hipStream_t s);                                       // gnx_spmm.hip: long rows only
 const char *launch_spmm_dropped(const SpmmArgs &p, int vec, bool has_long, hipStream_t s);    // gnx_spmm_train.hip
+// gnx_spmm_train.hip, shared with gnx_spmm_train_bf16.hip: a handle with duplicate entries needs gnx_graph_enable_entry_dropout
+// (GNX_ERR_UNSUPPORTED otherwise); the per-slot values and entry tables a fused launch over the handle reads
+int refuse_duplicates(const gnx_graph *g, const char *fn);
+void set_values(const gnx_graph *g, bool transposed, SpmmArgs &p);
+void set_drop_fuse(const gnx_graph *g, float dropout_p, uint64_t seed, uint64_t stream_id, const float *d_D, int transposed,
+                   int x_prescaled, SpmmArgs &p);
 // out[out_rows[r]] = act(X[in_rows[r]] . W + bias) on the matrix cores (gnx_dense.hip); row maps optional
 int dense_rows(const float *X, int64_t ldx, int64_t n, int64_t F, const float *W, int64_t ldw, int64_t O, const float *bias, int act,
                const int32_t *in_rows, const int32_t *out_rows, float *out, int64_t ldo, hipStream_t s);

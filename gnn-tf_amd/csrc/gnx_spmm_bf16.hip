@@ -11,7 +11,7 @@
 // than 32 lanes, 32/16/8-lane groups below, long rows cut into chunks whose f32 partial sums a second kernel adds in chunk order
 // (no float atomics: two calls give the same bits) -- with up to 8 bf16 (16 bytes) per lane: C = 128 runs on 16-lane groups.
 // Every kernel here is its own (the f32 kernels and the helpers of gnx_spmm_device.h are not touched).
-#include "gnx_spmm_device.h"
+#include "gnx_bf16_device.h"   // bload / bstore / fload / fstore (shared with gnx_spmm_train_bf16.hip)
 
 namespace {
 
@@ -20,63 +20,6 @@ struct BfArgs : SpmmArgs {     // SpmmArgs::X / ::out stay null: the operand and
     void *outv;                // f32 or bf16 [n_rows, ldo]
     int out_bf16;
 };
-
-template <int VEC> struct BfRaw;
-template <> struct BfRaw<1> { using type = uint16_t; };
-template <> struct BfRaw<2> { using type = uint32_t; };
-template <> struct BfRaw<4> { using type = uint2; };
-template <> struct BfRaw<8> { using type = uint4; };
-
-// VEC bf16 values (2 * VEC bytes, one load) widened to f32: exact, a bf16 is the upper half of an f32
-template <int VEC>
-__device__ __forceinline__ void bload(float (&x)[VEC], const uint16_t *__restrict__ p) {
-    if constexpr (VEC == 1) {
-        x[0] = __uint_as_float((uint32_t)*p << 16);
-    } else {
-        using T = typename BfRaw<VEC>::type;
-        const T v = *reinterpret_cast<const T *>(p);
-        uint32_t w[VEC / 2];
-        __builtin_memcpy(w, &v, sizeof(T));
-#pragma unroll
-        for (int i = 0; i < VEC / 2; ++i) {
-            x[2 * i] = __uint_as_float(w[i] << 16);
-            x[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u);
-        }
-    }
-}
-
-__device__ __forceinline__ uint16_t to_bf16(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }   // RNE, NaN-preserving
-
-template <int VEC>
-__device__ __forceinline__ void bstore(uint16_t *__restrict__ p, const float (&x)[VEC]) {
-    uint16_t h[VEC];
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) h[v] = to_bf16(x[v]);
-    using T = typename BfRaw<VEC>::type;
-    T t;
-    __builtin_memcpy(&t, h, sizeof(T));
-    *reinterpret_cast<T *>(p) = t;
-}
-
-// f32 rows at up to 8 values per lane (two 16-byte accesses at 8)
-template <int VEC>
-__device__ __forceinline__ void fload(float (&x)[VEC], const float *__restrict__ p) {
-    if constexpr (VEC == 8) {
-        vload<4>(*reinterpret_cast<float(*)[4]>(&x[0]), p);
-        vload<4>(*reinterpret_cast<float(*)[4]>(&x[4]), p + 4);
-    } else {
-        vload<VEC>(x, p);
-    }
-}
-template <int VEC>
-__device__ __forceinline__ void fstore(float *__restrict__ p, const float (&x)[VEC]) {
-    if constexpr (VEC == 8) {
-        vstore<4>(p, *reinterpret_cast<const float(*)[4]>(&x[0]));
-        vstore<4>(p + 4, *reinterpret_cast<const float(*)[4]>(&x[4]));
-    } else {
-        vstore<VEC>(p, x);
-    }
-}
 
 // wave_accumulate (gnx_spmm_device.h) over bf16 rows: the same (col, val) fetch, v_readlane broadcast and entry order
 template <int VEC, int U>
@@ -393,25 +336,7 @@ __global__ __launch_bounds__(256) void k_cast_bf16(const float *__restrict__ src
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------
-// The row kernels in pieces of at most 2^31 work-items, the XCD block map padded as in GNX_ROW_PIECES (gnx_spmm_device.h)
-template <typename Kern>
-void row_pieces(Kern kern, const BfArgs &p, int rows_per_block, int threads, hipStream_t s) {
-    const int64_t per_launch = (((int64_t)1 << 31) / threads) * rows_per_block;
-    for (int64_t r0 = 0; r0 < p.n_rows; r0 += per_launch) {
-        BfArgs q = p;
-        q.slot0 = r0;
-        const int64_t rows = p.n_rows - r0 < per_launch ? p.n_rows - r0 : per_launch;
-        q.n_rows = r0 + rows;
-        unsigned grid = blocks_for(rows, rows_per_block);
-        if (q.xcd_rows > 0 && rows < 64 * q.xcd_rows) q.xcd_rows = 0;
-        if (q.xcd_rows > 0) {
-            q.xcd_chunk = (uint32_t)((q.xcd_rows + rows_per_block - 1) / rows_per_block);
-            const unsigned span = 8u * q.xcd_chunk;
-            grid = (grid + span - 1) / span * span;
-        }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, s, q);
-    }
-}
+// (the row kernels go out through launch_row_pieces of gnx_spmm_device.h: pieces of at most 2^31 work-items, the XCD map padded)
 
 // dispatch classes of the short rows (launch_rows of gnx_spmm.hip); the names gnx_graph_last_kernel reports, "+long" when hub rows
 // went through the chunk kernels
@@ -430,13 +355,13 @@ RowClass launch_rows_bf16(const BfArgs &p0, hipStream_t s) {
     if (lanes > 32 && p.skip_empty && p.nonempty_rows != nullptr && p.n_nonempty < p.n_rows) { p.row_list = p.nonempty_rows; p.n_rows = p.n_nonempty; }
     if (p.n_rows == 0) return ROWS_NONE;
     if (lanes > 32) {
-        if (p.C <= 64 * VEC) row_pieces(k_spmm_wave_bf16<VEC, 8, 8>, p, 8, 512, s);
-        else                 row_pieces(k_spmm_wave_bf16<VEC, 8, 4>, p, 4, 256, s);
+        if (p.C <= 64 * VEC) launch_row_pieces(k_spmm_wave_bf16<VEC, 8, 8>, p, 8, 512, s);
+        else                 launch_row_pieces(k_spmm_wave_bf16<VEC, 8, 4>, p, 4, 256, s);
         return ROWS_WAVE;
     }
-    if (lanes > 16) { row_pieces(k_spmm_group_bf16<VEC, 32>, p, 8, 256, s); return ROWS_G32; }
-    if (lanes > 8)  { row_pieces(k_spmm_group_bf16<VEC, 16>, p, 16, 256, s); return ROWS_G16; }
-    row_pieces(k_spmm_group_bf16<VEC, 8>, p, 32, 256, s);   // (up to 4 lanes as well: the extra lanes share the index fetch)
+    if (lanes > 16) { launch_row_pieces(k_spmm_group_bf16<VEC, 32>, p, 8, 256, s); return ROWS_G32; }
+    if (lanes > 8)  { launch_row_pieces(k_spmm_group_bf16<VEC, 16>, p, 16, 256, s); return ROWS_G16; }
+    launch_row_pieces(k_spmm_group_bf16<VEC, 8>, p, 32, 256, s);   // (up to 4 lanes as well: the extra lanes share the index fetch)
     return ROWS_G8;
 }
 

@@ -251,24 +251,27 @@ inline bool aligned(const void *p, size_t a) { return p == nullptr || ((uintptr_
 // One launch holds at most 2^32 work-items (the dispatch packet's grid size is 32 bits).  A wave per row reaches that at 67M rows,
 // 32 lanes per row at 134M -- sizes a 288 GB card holds -- so the row kernels are dealt in pieces of at most 2^31 work-items
 // (SpmmArgs::slot0 = first row slot of the piece; one piece for everything smaller).
-#define GNX_ROW_PIECES(kern, rows_per_block, threads)                                                                       \
-    do {                                                                                                                    \
-        const int64_t per_launch_ = (((int64_t)1 << 31) / (threads)) * (rows_per_block);                                     \
-        for (int64_t r0_ = 0; r0_ < p.n_rows; r0_ += per_launch_) {                                                          \
-            SpmmArgs q_ = p;                                                                                                \
-            q_.slot0 = r0_;                                                                                                 \
-            const int64_t rows_ = p.n_rows - r0_ < per_launch_ ? p.n_rows - r0_ : per_launch_;                               \
-            q_.n_rows = r0_ + rows_;    /* a piece ends where the next begins (padded blocks of the XCD map must not run on) */       \
-            unsigned grid_ = blocks_for(rows_, rows_per_block);                                                             \
-            if (q_.xcd_rows > 0 && rows_ < 64 * q_.xcd_rows) q_.xcd_rows = 0;   /* a few windows only: they would not fill 8 XCDs evenly */   \
-            if (q_.xcd_rows > 0) {     /* xcd_block: whole chunks, the grid padded to 8 of them */                           \
-                q_.xcd_chunk = (uint32_t)((q_.xcd_rows + (rows_per_block) - 1) / (rows_per_block));                          \
-                const unsigned span_ = 8u * q_.xcd_chunk;                                                                   \
-                grid_ = (grid_ + span_ - 1) / span_ * span_;                                                                \
-            }                                                                                                               \
-            hipLaunchKernelGGL(kern, dim3(grid_), dim3(threads), 0, s, q_);                                                  \
-        }                                                                                                                   \
-    } while (0)
+// (one function for every argument struct -- SpmmArgs and the bf16 translation units' extensions of it -- so the piece size and the
+// padding of the XCD block map exist once)
+template <typename Args, typename Kern>
+void launch_row_pieces(Kern kern, const Args &p, int rows_per_block, int threads, hipStream_t s) {
+    const int64_t per_launch = (((int64_t)1 << 31) / threads) * rows_per_block;
+    for (int64_t r0 = 0; r0 < p.n_rows; r0 += per_launch) {
+        Args q = p;
+        q.slot0 = r0;
+        const int64_t rows = p.n_rows - r0 < per_launch ? p.n_rows - r0 : per_launch;
+        q.n_rows = r0 + rows;    // a piece ends where the next begins (padded blocks of the XCD map must not run on)
+        unsigned grid = blocks_for(rows, rows_per_block);
+        if (q.xcd_rows > 0 && rows < 64 * q.xcd_rows) q.xcd_rows = 0;   // a few windows only: they would not fill 8 XCDs evenly
+        if (q.xcd_rows > 0) {     // xcd_block: whole chunks, the grid padded to 8 of them
+            q.xcd_chunk = (uint32_t)((q.xcd_rows + rows_per_block - 1) / rows_per_block);
+            const unsigned span = 8u * q.xcd_chunk;
+            grid = (grid + span - 1) / span * span;
+        }
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, s, q);
+    }
+}
+#define GNX_ROW_PIECES(kern, rows_per_block, threads) launch_row_pieces(kern, p, rows_per_block, threads, s)
 
 [[maybe_unused]] int check_common(const char *fn, gnx_graph *g, const float *X, int64_t ldx, int64_t C, const float *H0, int64_t ldh0,
                  float *out, int64_t ldo) {

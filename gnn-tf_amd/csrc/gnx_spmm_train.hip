@@ -260,6 +260,10 @@ const char *launch_dropped(const SpmmArgs &p, int vec, bool has_long, hipStream_
     return name;
 }
 
+}  // namespace
+
+namespace gnx {
+
 // per-entry dropout of duplicated COO entries needs the tables gnx_graph_enable_entry_dropout builds
 int refuse_duplicates(const gnx_graph *g, const char *fn) {
     if (!g->has_dups || g->entry_drop) return GNX_OK;
@@ -282,9 +286,16 @@ void set_values(const gnx_graph *g, bool transposed, SpmmArgs &p) {
     p.fuse.perm = transposed ? g->t_perm : nullptr;
 }
 
-}  // namespace
-
-namespace gnx {
+// the counter-RNG part of a fused launch over a stand-alone handle or a vertex block: keep threshold, kept-value scale, stream, block keys
+void set_drop_fuse(const gnx_graph *g, float dropout_p, uint64_t seed, uint64_t stream_id, const float *d_D, int transposed,
+                   int x_prescaled, SpmmArgs &p) {
+    p.fuse.D = d_D; p.fuse.seed = seed; p.fuse.stream = stream_id; p.fuse.offset = g->stream_offset;
+    p.fuse.thr = (uint32_t)((double)dropout_p * 16777216.0);
+    p.fuse.scale = 1.0f / (1.0f - dropout_p);
+    p.fuse.transposed = transposed;
+    p.fuse.col_prescaled = x_prescaled ? 1 : 0;
+    p.fuse.row0_key = g->blk_row0_global; p.fuse.row0_D = g->blk_row0_buf; p.fuse.gid = g->blk_col_gid;
+}
 
 const char *launch_spmm_dropped(const SpmmArgs &p, int vec, bool has_long, hipStream_t s) {
     return p.fuse.mult ? launch_dropped<true>(p, vec, has_long, s) : launch_dropped<false>(p, vec, has_long, s);
@@ -314,11 +325,7 @@ int gnx_spmm_dropped(gnx_graph_t g, const float *d_D, float dropout_p, uint64_t 
     set_values(g, transposed, p);
     p.X = d_X; p.ldx = ldx; p.H0 = d_H0; p.ldh0 = ldh0; p.beta = beta; p.alpha = alpha; p.act = act;
     p.out = d_out; p.ldo = ldo; p.C = (int)C;
-    p.fuse.D = d_D; p.fuse.seed = seed; p.fuse.stream = stream_id; p.fuse.offset = g->stream_offset;
-    p.fuse.thr = (uint32_t)((double)dropout_p * 16777216.0);
-    p.fuse.scale = 1.0f / (1.0f - dropout_p);
-    p.fuse.transposed = transposed ? 1 : 0;
-    p.fuse.row0_key = g->blk_row0_global; p.fuse.row0_D = g->blk_row0_buf; p.fuse.gid = g->blk_col_gid;
+    set_drop_fuse(g, dropout_p, seed, stream_id, d_D, transposed ? 1 : 0, 0, p);
     return launch_spmm(g, transposed ? g->t : g->a, p, s);
 }
 
@@ -340,12 +347,7 @@ int gnx_spmm_dropped_chained(gnx_graph_t g, const float *d_D, float dropout_p, u
     p.X = d_X; p.ldx = ldx; p.H0 = d_H0; p.ldh0 = ldh0; p.beta = beta; p.alpha = alpha; p.act = act;
     p.out = d_out; p.ldo = ldo; p.C = (int)C;
     p.out_scale = d_D_next ? d_D_next + g->blk_row0_buf : nullptr;
-    p.fuse.D = d_D; p.fuse.seed = seed; p.fuse.stream = stream_id; p.fuse.offset = g->stream_offset;
-    p.fuse.thr = (uint32_t)((double)dropout_p * 16777216.0);
-    p.fuse.scale = 1.0f / (1.0f - dropout_p);
-    p.fuse.transposed = 0;
-    p.fuse.col_prescaled = x_prescaled ? 1 : 0;
-    p.fuse.row0_key = g->blk_row0_global; p.fuse.row0_D = g->blk_row0_buf; p.fuse.gid = g->blk_col_gid;
+    set_drop_fuse(g, dropout_p, seed, stream_id, d_D, 0, x_prescaled, p);
     return launch_spmm(g, g->a, p, (hipStream_t)stream);
 }
 
@@ -376,11 +378,7 @@ int gnx_spmm_dropped_back(gnx_graph_t g, const float *d_D, float dropout_p, uint
     p.X = d_X; p.ldx = ldx; p.H0 = d_S_in; p.ldh0 = lds_in; p.beta = s_beta; p.alpha = s_alpha; p.act = act;
     p.out = d_S_out; p.ldo = lds_out; p.C = (int)C;
     p.out2 = d_Y_out; p.ldo2 = ldy; p.beta2 = y_beta; p.out2_scale = d_Y_out ? d_D_next : nullptr;
-    p.fuse.D = d_D; p.fuse.seed = seed; p.fuse.stream = stream_id; p.fuse.offset = g->stream_offset;
-    p.fuse.thr = (uint32_t)((double)dropout_p * 16777216.0);
-    p.fuse.scale = 1.0f / (1.0f - dropout_p);
-    p.fuse.transposed = 1;
-    p.fuse.col_prescaled = x_prescaled ? 1 : 0;
+    set_drop_fuse(g, dropout_p, seed, stream_id, d_D, 1, x_prescaled, p);   // (stand-alone handle: the block keys are 0 / null)
     return launch_spmm(g, g->t, p, s);
 }
 

@@ -46,7 +46,8 @@ class GNN(Trainable):
     # same masks and values as the materialised form.  False: such graphs stay on the materialised form (A/B comparisons)
     fuse_entry_dropout = True
 
-    def __init__(self, graph, features, preprocessor: Layer = None, reorder=None, inference_dtype=torch.float32):
+    def __init__(self, graph, features, preprocessor: Layer = None, reorder=None, inference_dtype=torch.float32,
+                 training_dtype=torch.float32):
         """``reorder`` (opt-in, not in the reference): store the graph and the feature rows with the vertices relabelled; every
         [N, .] tensor inside the model then lives in that order, and the model's OUTPUT is put back into the caller's order, so
         tasks, labels and node ids are unaffected.  Results agree with the unordered model to float32 rounding.
@@ -61,13 +62,25 @@ class GNN(Trainable):
         Measurements: profiles/NOTES.md round 5.
         ``inference_dtype=torch.bfloat16`` (opt-in, not in the reference): eval-mode forwards without autograd (``predict()``, the
         validation forwards inside ``train()``) gather the propagated features as bf16 with f32 sums (sparse.appnp_propagate /
-        sparse.spmm ``storage``); every forward with grad enabled -- every training step -- runs the f32 path unchanged.  Error:
+        sparse.spmm ``storage``); every forward with grad enabled -- every training step -- runs the f32 path unchanged (``training_dtype`` is the
+        separate switch for those).  Error:
         the APPNP loop is within (2^-8 / a) max_k ||H_k||_2 per column of the f32 result (first order), a GCN SpMM within
-        2^-8 |A| |X| elementwise."""
+        2^-8 |A| |X| elementwise.
+        ``training_dtype=torch.bfloat16`` (opt-in, not in the reference; separate from ``inference_dtype``, which keeps meaning eval
+        only): training-mode PPR propagation with edge dropout (PPRLoop, fused runs of PPRIteration layers) gathers its iterate and
+        its back-propagated gradient as bf16 (sparse.ppr_loop ``storage``): masks, degree scales, weights, sums, H0, the mix and
+        both results of the step stay f32, a row is rounded once as it is handed to the next iteration.  It is an allowance: the
+        loop keeps f32 -- today's bits -- where the fused chained form does not apply (relu, no edge dropout, a graph that cannot
+        fuse its dropout), below sparse.BF16_TRAIN_MIN_WIDTH columns and on graphs of fewer than sparse.BF16_TRAIN_MIN_ROWS vertices
+        (where it measured slower).  It is ignored by GCNLayer / GCNIILayer training and by the
+        vertex-partitioned path (sharded.py), which keep f32 whatever it says."""
         if inference_dtype not in (torch.float32, torch.bfloat16):
             raise Exception("GNN: inference_dtype must be torch.float32 or torch.bfloat16")
+        if training_dtype not in (torch.float32, torch.bfloat16):
+            raise Exception("GNN: training_dtype must be torch.float32 or torch.bfloat16")
         super().__init__(features)
         self.inference_dtype = inference_dtype
+        self.training_dtype = training_dtype
         self._order = self._newid = None
         self.reorder_used, self.locality_share = None, None
         if isinstance(graph, sparse.DeviceGraph):
@@ -180,7 +193,8 @@ def _propagation_run(architecture: "GNN", H0_value, a, iterations, graph_dropout
         storage = _eval_storage(architecture)
         run = lambda k: sparse.appnp_propagate(make_adj(0, False), H0_value, a, k, relu=with_relu, storage=storage)
     else:
-        run = lambda k: sparse.ppr_loop(make_adj, H0_value, a, k, relu=with_relu)
+        storage = getattr(architecture, "training_dtype", torch.float32) if training else torch.float32
+        run = lambda k: sparse.ppr_loop(make_adj, H0_value, a, k, relu=with_relu, storage=storage)
     return run(iterations), run, (make_adj if cheap else None)
 
 

@@ -377,6 +377,71 @@ def _backward_chained(adjs, g, a):
     return S
 
 
+def _launch_chained_bf16(adj: "DroppedAdjacency", X, H0, beta, alpha, prescaled, D_next, skip_empty=False, out_bf16=False):
+    """_launch_chained with the gathered rows X stored as bf16 (gnx_spmm_dropped_chained_bf16); f32 H0; the result is f32, or bf16
+    (rounded once, after the D_next scale) with ``out_bf16``."""
+    g = adj.graph
+    nat.require_cuda(X, H0)
+    _same_device(g, X, H0, adj.D, D_next)
+    if (X.dtype != torch.bfloat16 or H0.dtype != torch.float32 or X.shape[0] != g.n_cols or tuple(H0.shape) != (g.n_rows, X.shape[1])
+            or not X.is_contiguous() or not H0.is_contiguous()):
+        raise Exception("chained bf16 propagation: bad operands")
+    out = torch.empty((g.n_rows, X.shape[1]), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=X.device)
+    with nat.on_device(X.device):
+        nat.check(nat.lib().gnx_spmm_dropped_chained_bf16(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, 1 if prescaled else 0,
+                                                          nat.ptr(D_next), nat.ptr(X), X.stride(0), X.shape[1], nat.ptr(H0), H0.stride(0),
+                                                          float(beta), float(alpha),
+                                                          nat.ACT_NONE | (nat.ACT_SKIP_EMPTY if skip_empty else 0), nat.ptr(out),
+                                                          1 if out_bf16 else 0, out.stride(0), nat.current_stream()))
+    return out
+
+
+def _launch_back_bf16(adj: "DroppedAdjacency", X, prescaled, D_next, S_in, s_alpha, s_beta, S_out, y_beta, Y_out, skip_empty=False):
+    """_launch_back with the gathered rows X and the pre-scaled result Y_out stored as bf16 (gnx_spmm_dropped_back_bf16); the running
+    sum S_in / S_out is f32."""
+    g = adj.graph
+    nat.require_cuda(X, S_in, S_out)
+    _same_device(g, X, S_in, S_out, Y_out, adj.D, D_next)
+    C = X.shape[1]
+    if any(t is not None and (tuple(t.shape) != (g.n_rows, C) or not t.is_contiguous() or t.dtype != dt)
+           for t, dt in ((X, torch.bfloat16), (S_in, torch.float32), (S_out, torch.float32), (Y_out, torch.bfloat16))):
+        raise Exception("chained bf16 backward: bad operands")
+    with nat.on_device(X.device):
+        nat.check(nat.lib().gnx_spmm_dropped_back_bf16(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, 1 if prescaled else 0,
+                                                       nat.ptr(D_next), nat.ptr(X), C, C, nat.ptr(S_in), C, float(s_alpha), float(s_beta),
+                                                       nat.ptr(S_out), C, float(y_beta), nat.ptr(Y_out), C,
+                                                       nat.ACT_SKIP_EMPTY if skip_empty else nat.ACT_NONE, nat.current_stream()))
+
+
+def _forward_chained_bf16(adjs, H0, a):
+    """H_K of K >= 1 chained training iterations from f32 H0 ([n, C] contiguous) with the iterate stored as bf16 between launches:
+    X_0 = bf(H0); iteration k gathers X_k and writes bf(H_{k+1} * D_{k+1}), the last one f32 H_K."""
+    K = len(adjs)
+    X = to_bf16(H0)
+    for k, adj in enumerate(adjs):
+        last = k == K - 1
+        # (rows without entries are a * H0 in the result and gathered by nobody: only the last iteration writes them)
+        X = _launch_chained_bf16(adj, X, H0, 1.0 - a, a, prescaled=k > 0, D_next=None if last else adjs[k + 1].D, skip_empty=not last,
+                                 out_bf16=not last)
+    return X
+
+
+def _backward_chained_bf16(adjs, g, a):
+    """_backward_chained with the gathered gradient stored as bf16: the first call gathers bf(g), every later one the
+    bf((1-a) acc * D) its predecessor wrote; the running sum starts from f32 g and only ever adds f32 sums."""
+    K = len(adjs)
+    g = _as_f32_rows(g).contiguous()
+    S = torch.empty_like(g)
+    X = to_bf16(g)
+    for k in range(K - 1, -1, -1):
+        first, last = k == K - 1, k == 0
+        Y = None if last else torch.empty(g.shape, dtype=torch.bfloat16, device=g.device)
+        _launch_back_bf16(adjs[k], X, not first, None if last else adjs[k - 1].D, g if first else S, a if first else 1.0,
+                          (1.0 - a) if last else a * (1.0 - a), S, 1.0 - a, Y, skip_empty=not first)
+        X = Y
+    return S
+
+
 def launch_rows(adj: Adjacency, X, H0, beta, alpha, rows, out, act=nat.ACT_NONE):
     """The fused step over a graph that holds a SUBSET of the output rows (the interior or the boundary rows of
     a vertex block): result row r is written to out[rows[r]] and mixes in H0[rows[r]] (gnx_spmm_rows)."""
@@ -505,21 +570,31 @@ class _PPRLoop(torch.autograd.Function):
     masked by H_k > 0 before it goes through A_k^T: gz_k = g_k * (H_k > 0), g_{k-1} = (1-a) A_k^T gz_k, dH0 = g_0 + a sum_k gz_k."""
 
     @staticmethod
-    def forward(ctx, H0, make_adj, a, K, relu=False):
+    def forward(ctx, H0, make_adj, a, K, relu=False, storage=torch.float32):
         ctx.make_adj, ctx.a, ctx.K, ctx.relu = make_adj, a, K, relu
         act = nat.ACT_RELU if relu else nat.ACT_NONE
         H0 = _as_f32_rows(H0).contiguous()
         ctx.C = C = H0.shape[1]
+        first = make_adj(0, False) if K > 0 else None
+        ctx.bf16 = False
+        made = None                     # the K adjacencies if the bf16 branch asked for them: make_adj is called once per iteration
+        if _bf16(storage) and _bf16_training_applies(first, K, relu, C):
+            # opt-in bf16 storage of the gathered operand (gnx_spmm_dropped_chained_bf16 / _back_bf16): the chained loop, on graphs
+            # with duplicate entries too (there is no materialised bf16 form whose bits it would have to keep)
+            made = adjs = [first] + [make_adj(k, False) for k in range(1, K)]
+            if all(isinstance(adj, DroppedAdjacency) and adj.graph is first.graph for adj in adjs):
+                ctx.bf16 = True
+                H = _forward_chained_bf16(adjs, _padded(H0, friendly_width_bf16(C, H0.shape[0])), a)
+                return H if H.shape[1] == C else H[:, :C].contiguous()
         H0 = _padded(H0, friendly_width(C, H0.shape[0]))
         H = H0
-        first = make_adj(0, False) if K > 0 else None
         kept = []
         if K > 1 and isinstance(first, DroppedAdjacency) and not relu and first.graph.nnz_entries == first.graph.nnz:
             # weights made in the kernels (only the K degree-scale vectors exist): the next iteration's column scale rides out with
             # the rows, so from k = 1 on no per-entry scale gather is left (gnx_spmm_dropped_chained).  Not on graphs with duplicate
             # entries: their fused form replaces the materialised one, whose results it keeps bit for bit (one gnx_spmm_dropped per
             # iteration, below), where the chained loop would round differently
-            adjs = [first] + [make_adj(k, False) for k in range(1, K)]
+            adjs = made if made is not None else [first] + [make_adj(k, False) for k in range(1, K)]
             chained = all(isinstance(adj, DroppedAdjacency) and adj.graph is first.graph for adj in adjs)
             ctx.chained = chained and first.graph.n_rows == first.graph.n_cols
             for k, adj in enumerate(adjs):
@@ -531,7 +606,7 @@ class _PPRLoop(torch.autograd.Function):
                     H = _launch(adj, H, H0, 1.0 - a, a, nat.ACT_NONE)
         else:
             for k in range(K):           # one adjacency alive at a time (a materialised one is an nnz-sized array)
-                H = _launch(first if k == 0 else make_adj(k, False), H, H0, 1.0 - a, a, act)
+                H = _launch(first if k == 0 else made[k] if made is not None else make_adj(k, False), H, H0, 1.0 - a, a, act)
                 if relu:
                     kept.append(H)
         if relu:
@@ -542,12 +617,18 @@ class _PPRLoop(torch.autograd.Function):
     def backward(ctx, g):
         # dH0 = g_0 + a (g_1 + ... + g_K): the gradients of the iterations are KEPT (as many as a tenth of the card's memory
         # holds, at most 15) and added up by one pass (gnx_linear_combination) instead of a read-modify-write of dH0 per iteration
+        if ctx.bf16:
+            adjs = [ctx.make_adj(k, True) for k in range(ctx.K)]
+            if not all(isinstance(adj, DroppedAdjacency) for adj in adjs):
+                raise Exception("ppr_loop: the bf16 forward ran on fused adjacencies, the backward was handed others")
+            gH0 = _backward_chained_bf16(adjs, _padded(_as_f32_rows(g).contiguous(), friendly_width_bf16(ctx.C, g.shape[0])), ctx.a)
+            return (gH0 if gH0.shape[1] == ctx.C else gH0[:, :ctx.C].contiguous()), None, None, None, None, None
         g = _padded(g.contiguous(), friendly_width(ctx.C, g.shape[0]))
         if getattr(ctx, "chained", False):
             adjs = [ctx.make_adj(k, True) for k in range(ctx.K)]
             if all(isinstance(adj, DroppedAdjacency) for adj in adjs):
                 gH0 = _backward_chained(adjs, g, ctx.a)
-                return (gH0 if gH0.shape[1] == ctx.C else gH0[:, :ctx.C].contiguous()), None, None, None, None
+                return (gH0 if gH0.shape[1] == ctx.C else gH0[:, :ctx.C].contiguous()), None, None, None, None, None
         outs = ctx.saved_tensors if ctx.relu else None
         room = int(0.1 * torch.cuda.get_device_properties(g.device).total_memory) // max(g.numel() * 4, 1)
         limit = max(2, min(LINCOMB_TERMS - 1, room))
@@ -561,7 +642,7 @@ class _PPRLoop(torch.autograd.Function):
             g = _launch(ctx.make_adj(k, True), g, None, 1.0 - ctx.a, 0.0, nat.ACT_NONE, transposed=True)
         pending.append((g, 1.0))
         gH0 = linear_combination(([(total, 1.0)] if total is not None else []) + pending)
-        return (gH0 if gH0.shape[1] == ctx.C else gH0[:, :ctx.C].contiguous()), None, None, None, None
+        return (gH0 if gH0.shape[1] == ctx.C else gH0[:, :ctx.C].contiguous()), None, None, None, None, None
 
 
 LINCOMB_TERMS = 16
@@ -589,11 +670,20 @@ def linear_combination(terms) -> torch.Tensor:
     return out
 
 
-def ppr_loop(make_adj, H0: torch.Tensor, a: float, iterations: int, relu: bool = False) -> torch.Tensor:
+def ppr_loop(make_adj, H0: torch.Tensor, a: float, iterations: int, relu: bool = False, storage=torch.float32) -> torch.Tensor:
     """``iterations`` fused PPR steps starting from H0; ``make_adj(k, for_backward)`` returns the Adjacency
     of iteration k (called again, with the same k and for_backward=True, during the backward, where only the
-    transposed-order values are needed).  ``relu``: relu after every step (filter.py:22)."""
-    return _PPRLoop.apply(H0, make_adj, float(a), int(iterations), bool(relu))
+    transposed-order values are needed).  ``relu``: relu after every step (filter.py:22).
+    ``storage=torch.bfloat16`` (opt-in): where every iteration's adjacency is a DroppedAdjacency of one square graph (training with
+    edge dropout, weights made in the kernels) the rows the loop GATHERS are stored as bf16, forward and backward
+    (gnx_spmm_dropped_chained_bf16 / gnx_spmm_dropped_back_bf16): X_0 = bf(H0), every later iterate leaves its launch as
+    bf(H_{k+1} * D_{k+1}) -- one rounding, after the next iteration's column scale -- and the last iteration writes f32 H_K; the
+    backward gathers bf(g), then bf((1-a) acc * D_{k-1}), while dH0 is summed in f32 from unrounded addends.  Masks, degree scales,
+    weights, sums, H0 and the mix stay f32; two runs give the same bits.  bf16 is an allowance: the loop keeps f32 -- bit for bit
+    the default -- with ``relu``, with any other adjacency, at K = 0, below BF16_TRAIN_MIN_WIDTH columns and on graphs of fewer than
+    BF16_TRAIN_MIN_ROWS vertices (launch-bound steps, where bf16 measured slower)."""
+    _bf16(storage)
+    return _PPRLoop.apply(H0, make_adj, float(a), int(iterations), bool(relu), storage)
 
 
 class _SpMMBiasAct(torch.autograd.Function):
@@ -680,6 +770,23 @@ def appnp_propagate(adj: Adjacency, H0: torch.Tensor, a: float = 0.1, iterations
 # which the bf16 loop does not have (profiles/NOTES.md, bf16 storage)
 BF16_MIN_WIDTH = 17
 BF16_F32_ROWS = 1 << 20
+
+
+# Training (ppr_loop storage=bf16): the allowance, set from tools/bf16_train_bench.py (profiles/NOTES.md "bf16 training storage"): a
+# width / graph size gets bf16 only where its K = 10 step measured faster than the f32 step of the same run by more than the spread
+# of the two medians.  Width: on the config-4 graph C = 33 ... 128 gain 1.18 - 1.53 x, C <= 16 lose 2 - 4 %, C = 17 ... 32 are a wash
+# (up to 32 columns a gathered row is one 128-byte line in either format).  Rows: at 10^6 vertices C = 33 ... 128 gain 1.10 - 1.27 x,
+# at 40 000 and at 2 708 vertices (launch-bound steps of under 1.5 ms) bf16 LOSES 1.2 - 1.9 x; nothing between was measured, so
+# the smallest size that measured a gain is the threshold.  Outside the allowance the loop keeps f32
+BF16_TRAIN_MIN_WIDTH = 33
+BF16_TRAIN_MIN_ROWS = 1_000_000
+
+
+def _bf16_training_applies(first, K, relu, C) -> bool:
+    """Whether ppr_loop(storage=bf16) runs its bf16 loops: the chained fused form applies and width and graph size are inside the
+    allowance."""
+    return (K > 0 and not relu and isinstance(first, DroppedAdjacency) and first.graph.n_rows == first.graph.n_cols
+            and C >= BF16_TRAIN_MIN_WIDTH and first.graph.n_rows >= BF16_TRAIN_MIN_ROWS)
 
 
 def _bf16(storage) -> bool:

@@ -53,8 +53,10 @@ const char *gnx_last_error(void);
  * counts; gnx_gcnii_step's d_work became d_mixed), so a 0.2 client linked against a 0.3+ library passes shifted arguments.
  * 0.4 adds gnx_graph_reserve and changes no existing signature; 0.5 adds gnx_graph_set_row_window, 0.6 gnx_appnp_propagate_act,
  * likewise; 0.6.1 adds the bf16 storage entries (gnx_cast_bf16, gnx_spmm_bf16, gnx_appnp_propagate_bf16) and changes nothing else;
- * 0.7 adds gnx_graph_enable_entry_dropout (the fused training entries accept handles with duplicate entries once it was called). */
-#define GNX_ABI_VERSION 701
+ * 0.7 adds gnx_graph_enable_entry_dropout (the fused training entries accept handles with duplicate entries once it was called);
+ * 0.8 adds the bf16 storage entries of the fused training loops (gnx_spmm_dropped_chained_bf16, gnx_spmm_dropped_back_bf16) and
+ * changes nothing else. */
+#define GNX_ABI_VERSION 800
 int gnx_version(void);
 
 /* ---- graph construction ------------------------------------------------------------
@@ -296,7 +298,7 @@ int gnx_appnp_propagate(gnx_graph_t g, const float *d_vals, const float *d_diag,
 int gnx_appnp_propagate_act(gnx_graph_t g, const float *d_vals, const float *d_diag, const float *d_H0,
                             float a, int K, int64_t C, int act, float *d_out, float *d_work, void *stream);
 
-/* ---- opt-in bf16 feature storage (eval-mode propagation; no backward) -------------------------------------------------
+/* ---- opt-in bf16 feature storage: eval-mode propagation (no backward) -------------------------------------------------
  * bf16 values are passed as uint16_t bit patterns.  bf(x) = x rounded to nearest even, NaN stays NaN; u = 2^-8.
  * gnx_cast_bf16: dst = bf(src), [n_rows, C] with leading dimensions lds / ldd (elements); dst must not alias src.
  * gnx_spmm_bf16: out[i,:] = act( beta * ( sum_j A[i,j] X~[j,:] + diag[i] X~[i,:] ) + alpha * H0[i,:] ) with X~ bf16 (widened
@@ -314,6 +316,33 @@ int gnx_spmm_bf16(gnx_graph_t g, const float *d_vals, const float *d_diag, const
                   void *stream);
 int gnx_appnp_propagate_bf16(gnx_graph_t g, const float *d_vals, const float *d_diag, const float *d_H0, float a, int K, int64_t C,
                              int act, float *d_out, uint16_t *d_work, void *stream);
+
+/* ---- opt-in bf16 feature storage: the fused training loops -----------------------------------------------------------------
+ * gnx_spmm_dropped_chained and gnx_spmm_dropped_back, argument for argument, with the GATHERED operand d_X stored as bf16 (uint16_t
+ * bit patterns, widened exactly to f32 as they arrive).  The masks, the kept sums, the degree scales d_D / d_D_next and every
+ * weight are the f32 ones of the namesakes; every sum, H0, the mix, the running sum S and both results of a training step are f32.
+ * Rounding points (bf = the cast of gnx_cast_bf16), for K iterations with scale vectors D_0 .. D_{K-1}:
+ *   forward:  X_0 = bf(H0) gathered with x_prescaled = 0; H_{k+1} = beta * acc + alpha * H0 in f32; for k < K-1 the row leaves as
+ *             X_{k+1}[i] = bf(H_{k+1}[i] * D_{k+1}[i]) (out_bf16 = 1, d_D_next = D_{k+1}): ONE rounding, after the scale; the last
+ *             iteration writes f32 H_K (out_bf16 = 0, d_D_next = NULL).
+ *   backward: the first call gathers bf(g) unscaled and starts the sum from f32 g (d_S_in = g); every call updates
+ *             S = s_beta * acc + s_alpha * S_in in f32 and, unless d_Y_out is NULL, writes Y[r] = bf(y_beta * acc[r] * d_D_next[r]),
+ *             the next call's operand.  The sum never sees a rounded addend; only what is propagated further is rounded.
+ * With x_prescaled = 0 and d_D_next = NULL the first is a plain dropped SpMM over bf16 rows.  d_out of the first is f32
+ * (out_bf16 = 0) or bf16 (out_bf16 = 1), [n, ldo] elements of that type.  Rows without entries follow the GNX_ACT_SKIP_EMPTY rules of
+ * the namesakes.  The per-row summation order follows the fixed rules of the f32 training kernels (round order, chunk order for long
+ * rows, no float atomics): two calls give the same bits; bit-equality with the f32 entries is not a goal.
+ * Square stand-alone graphs only: a vertex block (gnx_graph_set_block) returns GNX_ERR_UNSUPPORTED; a handle with duplicate entries
+ * needs gnx_graph_enable_entry_dropout first.  Allocation-free once the handle is reserved (gnx_graph_reserve: the long-row slab,
+ * the transposed structure); under capture they return GNX_ERR_UNSUPPORTED naming gnx_graph_reserve where something would grow. */
+int gnx_spmm_dropped_chained_bf16(gnx_graph_t g, const float *d_D, float dropout_p, uint64_t seed, uint64_t stream_id,
+                                  int x_prescaled, const float *d_D_next, const uint16_t *d_X, int64_t ldx, int64_t C,
+                                  const float *d_H0, int64_t ldh0, float beta, float alpha, int act,
+                                  void *d_out, int out_bf16, int64_t ldo, void *stream);
+int gnx_spmm_dropped_back_bf16(gnx_graph_t g, const float *d_D, float dropout_p, uint64_t seed, uint64_t stream_id,
+                               int x_prescaled, const float *d_D_next, const uint16_t *d_X, int64_t ldx, int64_t C,
+                               const float *d_S_in, int64_t lds_in, float s_alpha, float s_beta, float *d_S_out, int64_t lds_out,
+                               float y_beta, uint16_t *d_Y_out, int64_t ldy, int act, void *stream);
 
 /* One GCNIILayer.__forward__ (gnntf/core/gnn/architectures/gcn.py:22-27) with a fixed adjacency:
  *   out = act( ((A_hat . H)*(1-a) + H0*a) . M ),   M = (1-b) I + b W  given by the caller as a [C, C] matrix (ldm).
@@ -429,7 +458,9 @@ int gnx_probe_block_xcd(int64_t n_blocks, int32_t *d_xcd_out, void *stream);
  * string; for profiles and tests): "spmm_wave", "spmm_group8" ... "spmm_group32" (lanes per row; "spmm_group4+chunks": the merged small-graph launch), "..._drop" (weights made
  * in the kernel), "...+chunks" (structures below 2^20 rows: the chunks of the long rows share the launch of the short rows),
  * "spmm_gcnii_mfma", "spmm+dense_mfma"; the bf16 entries report "spmm_wave_bf16", "spmm_group8_bf16" ... "spmm_group32_bf16",
- * "...+long_bf16" (hub rows through the chunk kernels) and "...+chunks_bf16". */
+ * "...+long_bf16" (hub rows through the chunk kernels) and "...+chunks_bf16"; the bf16 training entries report the f32 training
+ * names with "_bf16" appended ("spmm_group16_drop_bf16", "spmm_wave_drop_entries_bf16", ...), "+long" after the row class when hub
+ * rows went through the chunk kernels ("spmm_group8+long_drop_bf16"). */
 const char *gnx_graph_last_kernel(gnx_graph_t g);
 
 #ifdef __cplusplus
