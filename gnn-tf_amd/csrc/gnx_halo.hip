@@ -90,6 +90,71 @@ int pack_rows(const float *X, int64_t ldx, const int32_t *src, int64_t n_rows, i
     return GNX_OK;
 }
 
+// The same gather over bf16 rows (gnx_halo_pack_bf16): one unit of VEC bf16 per thread, grid-stride -- 16 bytes (8 bf16) where the
+// width, both leading dimensions and both base addresses allow, then 8 / 4 / 2 bytes.  A C = 64 chunk row is 128 bytes = one line
+// read by 8 consecutive lanes; a wave covers 8 gathered rows per pass and writes 1 KiB of consecutive send-buffer bytes.
+template <int VEC>
+__global__ __launch_bounds__(256) void k_pack_rows_bf16(const uint16_t *__restrict__ X, int64_t ldx, const int32_t *__restrict__ src,
+                                                        int64_t n_rows, int C, uint16_t *__restrict__ out, int64_t ldo) {
+    typedef uint16_t vec_t __attribute__((ext_vector_type(VEC)));
+    const int upr = C / VEC;
+    const int64_t total = n_rows * upr, stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const int64_t r = e / upr;
+        const int c = (int)(e - r * upr) * VEC;
+        const vec_t v = *reinterpret_cast<const vec_t *>(X + (int64_t)src[r] * ldx + c);
+        __builtin_nontemporal_store(v, reinterpret_cast<vec_t *>(out + r * ldo + c));     // next read by the copy engine / the link
+    }
+}
+
+int pack_rows_bf16(const uint16_t *X, int64_t ldx, const int32_t *src, int64_t n_rows, int64_t C, uint16_t *out, int64_t ldo, hipStream_t s) {
+    if (n_rows == 0) return GNX_OK;
+    int vec = 8;                               // widest unit every row start allows
+    while (vec > 1 && !(C % vec == 0 && ldx % vec == 0 && ldo % vec == 0 && (uintptr_t)X % (2 * vec) == 0 && (uintptr_t)out % (2 * vec) == 0)) vec >>= 1;
+    const int64_t units = n_rows * (C / vec);
+    const unsigned grid = (unsigned)std::min<int64_t>((units + 255) / 256, 256 * 64);
+#define GNX_PACK_BF16(V) hipLaunchKernelGGL(k_pack_rows_bf16<V>, dim3(grid), dim3(256), 0, s, X, ldx, src, n_rows, (int)C, out, ldo)
+    if (vec == 8)      GNX_PACK_BF16(8);
+    else if (vec == 4) GNX_PACK_BF16(4);
+    else if (vec == 2) GNX_PACK_BF16(2);
+    else               GNX_PACK_BF16(1);
+#undef GNX_PACK_BF16
+    GNX_HIP(hipGetLastError());
+    return GNX_OK;
+}
+
+// One RCCL group of gnx_halo_exchange / gnx_halo_exchange_bf16: rows of `elem` bytes per element, contiguous [rows, C] on both sides;
+// receives are posted before sends, peer by peer
+int exchange_rows(const char *fn, const gnx_halo_plan *p, int part, void *nccl_comm, const char *send, char *X, int64_t C, size_t elem,
+                  int nccl_type, hipStream_t s) {
+    Rccl rccl;
+    if (g_have_bound.load()) rccl = g_bound;
+    else if (!find_loaded_rccl(rccl)) {
+        gnx::set_error("%s: no RCCL entry points: hand them over with gnx_halo_bind_rccl (from the library that created the "
+                       "communicator), load librccl before the call, or move the rows yourself with the offsets of gnx_halo_plan_layout", fn);
+        return GNX_ERR_UNSUPPORTED;
+    }
+    const bool pull = part != GNX_HALO_PUSH, push = part != GNX_HALO_PULL;
+    const int64_t row = C * (int64_t)elem;     // bytes
+    int rc = rccl.start();
+    for (int q = 0; q < p->n_ranks && rc == 0; ++q) {
+        char *region = X + p->recv_row0[q] * row;
+        if (pull && p->recv_pull[q] > 0) rc = rccl.recv(region, (size_t)(p->recv_pull[q] * C), nccl_type, q, nccl_comm, s);
+        if (rc == 0 && push && p->recv_push[q] > 0)
+            rc = rccl.recv(region + p->recv_pull[q] * row, (size_t)(p->recv_push[q] * C), nccl_type, q, nccl_comm, s);
+        if (rc == 0 && pull && p->send_pull[q] > 0)
+            rc = rccl.send((void *)(send + p->send_pull_row0[q] * row), (size_t)(p->send_pull[q] * C), nccl_type, q, nccl_comm, s);
+        if (rc == 0 && push && p->send_push[q] > 0)
+            rc = rccl.send((void *)(send + p->send_push_row0[q] * row), (size_t)(p->send_push[q] * C), nccl_type, q, nccl_comm, s);
+    }
+    const int rc_end = rccl.end();
+    if (rc != 0 || rc_end != 0) {
+        gnx::set_error("%s: RCCL returned %d / %d", fn, rc, rc_end);
+        return GNX_ERR_HIP;
+    }
+    return GNX_OK;
+}
+
 }  // namespace
 
 using namespace gnx;
@@ -187,34 +252,33 @@ int gnx_halo_exchange(gnx_halo_plan_t p, int part, void *nccl_comm, const float 
     GNX_CHECK_ARG(p != nullptr && nccl_comm != nullptr, "gnx_halo_exchange: NULL plan / communicator");
     GNX_CHECK_ARG(part == GNX_HALO_ALL || part == GNX_HALO_PULL || part == GNX_HALO_PUSH, "gnx_halo_exchange: invalid part %d", part);
     GNX_CHECK_ARG(C >= 1 && (p->n_send == 0 || d_send) && d_X, "gnx_halo_exchange: NULL buffer");
-    Rccl rccl;
-    if (g_have_bound.load()) rccl = g_bound;
-    else if (!find_loaded_rccl(rccl)) {
-        set_error("gnx_halo_exchange: no RCCL entry points: hand them over with gnx_halo_bind_rccl (from the library that created the "
-                  "communicator), load librccl before the call, or move the rows yourself with the offsets of gnx_halo_plan_layout");
-        return GNX_ERR_UNSUPPORTED;
+    // ncclFloat32 of nccl.h's ncclDataType_t (ncclInt8 = 0 ... ncclFloat16 = 6, ncclFloat32 = 7)
+    return exchange_rows("gnx_halo_exchange", p, part, nccl_comm, (const char *)d_send, (char *)d_X, C, sizeof(float), 7, (hipStream_t)stream);
+}
+
+int gnx_halo_pack_bf16(gnx_halo_plan_t p, int part, const uint16_t *d_X, int64_t ldx, int64_t C, uint16_t *d_send, int64_t lds, void *stream) {
+    GNX_CHECK_ARG(p != nullptr, "gnx_halo_pack_bf16: NULL plan");
+    GNX_CHECK_ARG(part == GNX_HALO_ALL || part == GNX_HALO_PULL || part == GNX_HALO_PUSH, "gnx_halo_pack_bf16: invalid part %d", part);
+    if (p->n_send == 0) return GNX_OK;
+    GNX_CHECK_ARG(d_X && d_send && C >= 1 && ldx >= C && lds >= C, "gnx_halo_pack_bf16: NULL buffer or bad sizes");
+    const uint16_t *local = d_X + p->local_row0 * ldx;
+    if (part != GNX_HALO_PUSH && p->n_send_pull > 0) {
+        int rc = pack_rows_bf16(local, ldx, p->d_pull_src, p->n_send_pull, C, d_send, lds, (hipStream_t)stream);
+        if (rc != GNX_OK) return rc;
     }
-    const int nccl_float = 7;             // ncclFloat32 of nccl.h's ncclDataType_t (ncclInt8 = 0 ... ncclFloat16 = 6, ncclFloat32 = 7)
-    hipStream_t s = (hipStream_t)stream;
-    const bool pull = part != GNX_HALO_PUSH, push = part != GNX_HALO_PULL;
-    int rc = rccl.start();
-    // rows are contiguous [rows, C] on both sides; receives are posted before sends, peer by peer
-    for (int q = 0; q < p->n_ranks && rc == 0; ++q) {
-        float *region = d_X + p->recv_row0[q] * C;
-        if (pull && p->recv_pull[q] > 0) rc = rccl.recv(region, (size_t)(p->recv_pull[q] * C), nccl_float, q, nccl_comm, s);
-        if (rc == 0 && push && p->recv_push[q] > 0)
-            rc = rccl.recv(region + p->recv_pull[q] * C, (size_t)(p->recv_push[q] * C), nccl_float, q, nccl_comm, s);
-        if (rc == 0 && pull && p->send_pull[q] > 0)
-            rc = rccl.send((void *)(d_send + p->send_pull_row0[q] * C), (size_t)(p->send_pull[q] * C), nccl_float, q, nccl_comm, s);
-        if (rc == 0 && push && p->send_push[q] > 0)
-            rc = rccl.send((void *)(d_send + p->send_push_row0[q] * C), (size_t)(p->send_push[q] * C), nccl_float, q, nccl_comm, s);
-    }
-    const int rc_end = rccl.end();
-    if (rc != 0 || rc_end != 0) {
-        set_error("gnx_halo_exchange: RCCL returned %d / %d", rc, rc_end);
-        return GNX_ERR_HIP;
-    }
+    // a pushed partial sum: f32 sum over the sender's bf16 rows, ONE rounding on the way into the send buffer
+    if (part != GNX_HALO_PULL && p->n_send > p->n_send_pull)
+        return gnx_spmm_bf16(p->push_graph, nullptr, nullptr, local, ldx, C, nullptr, 0, 1.0f, 0.0f, GNX_ACT_NONE,
+                             d_send + p->n_send_pull * lds, 1, lds, stream);
     return GNX_OK;
+}
+
+int gnx_halo_exchange_bf16(gnx_halo_plan_t p, int part, void *nccl_comm, const uint16_t *d_send, uint16_t *d_X, int64_t C, void *stream) {
+    GNX_CHECK_ARG(p != nullptr && nccl_comm != nullptr, "gnx_halo_exchange_bf16: NULL plan / communicator");
+    GNX_CHECK_ARG(part == GNX_HALO_ALL || part == GNX_HALO_PULL || part == GNX_HALO_PUSH, "gnx_halo_exchange_bf16: invalid part %d", part);
+    GNX_CHECK_ARG(C >= 1 && (p->n_send == 0 || d_send) && d_X, "gnx_halo_exchange_bf16: NULL buffer");
+    // ncclBfloat16 = 9 (rccl.h: ... ncclFloat64 = 8, ncclBfloat16 = 9)
+    return exchange_rows("gnx_halo_exchange_bf16", p, part, nccl_comm, (const char *)d_send, (char *)d_X, C, sizeof(uint16_t), 9, (hipStream_t)stream);
 }
 
 int gnx_gather_rows32(const float *d_X, int64_t ldx, const int32_t *d_idx, int64_t n_idx, int64_t C, float *d_out, int64_t ldo,

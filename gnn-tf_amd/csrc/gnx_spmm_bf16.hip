@@ -11,6 +11,8 @@
 // than 32 lanes, 32/16/8-lane groups below, long rows cut into chunks whose f32 partial sums a second kernel adds in chunk order
 // (no float atomics: two calls give the same bits) -- with up to 8 bf16 (16 bytes) per lane: C = 128 runs on 16-lane groups.
 // Every kernel here is its own (the f32 kernels and the helpers of gnx_spmm_device.h are not touched).
+// gnx_spmm_rows_bf16 (the interior / boundary handles of a vertex block): SpmmArgs::out_rows / map_h0 send result row r to
+// out[rows[r]] and mix H0[rows[r]] in every row class; with a null map a row is its own destination, as before.
 #include "gnx_bf16_device.h"   // bload / bstore / fload / fstore (shared with gnx_spmm_train_bf16.hip)
 
 namespace {
@@ -75,9 +77,11 @@ __device__ __forceinline__ void epilogue_bf16(const BfArgs &p, int64_t row, int 
         for (int v = 0; v < VEC; ++v) acc[v] = fmaf(d, xr[v], acc[v]);
     }
     float o[VEC];
+    const int64_t orow = p.out_rows ? (int64_t)p.out_rows[row] : row;   // gnx_spmm_rows_bf16: the handle holds a subset of the output rows
     if (p.H0) {
+        const int64_t hrow = p.map_h0 ? orow : row;                     // ... and H0 is indexed like the output
         float h0[VEC];
-        fload<VEC>(h0, p.H0 + row * p.ldh0 + c);
+        fload<VEC>(h0, p.H0 + hrow * p.ldh0 + c);
 #pragma unroll
         for (int v = 0; v < VEC; ++v) o[v] = fmaf(acc[v], p.beta, h0[v] * p.alpha);
     } else {
@@ -88,8 +92,8 @@ __device__ __forceinline__ void epilogue_bf16(const BfArgs &p, int64_t row, int 
 #pragma unroll
         for (int v = 0; v < VEC; ++v) o[v] = fmaxf(o[v], 0.f);
     }
-    if (p.out_bf16) bstore<VEC>(static_cast<uint16_t *>(p.outv) + row * p.ldo + c, o);
-    else fstore<VEC>(static_cast<float *>(p.outv) + row * p.ldo + c, o);
+    if (p.out_bf16) bstore<VEC>(static_cast<uint16_t *>(p.outv) + orow * p.ldo + c, o);
+    else fstore<VEC>(static_cast<float *>(p.outv) + orow * p.ldo + c, o);
 }
 
 // ---- wide rows: one wave per row ----------------------------------------------------------------
@@ -480,6 +484,23 @@ int gnx_spmm_bf16(gnx_graph_t g, const float *d_vals, const float *d_diag, const
     p.vals = d_vals ? d_vals : g->raw_vals;
     p.diag = d_diag; p.Xb = d_X; p.ldx = ldx; p.H0 = d_H0; p.ldh0 = ldh0; p.beta = beta; p.alpha = alpha; p.act = act;
     p.outv = d_out; p.out_bf16 = out_bf16; p.ldo = ldo; p.C = (int)C;
+    return launch_spmm_bf16(g, g->a, p, (hipStream_t)stream);
+}
+
+int gnx_spmm_rows_bf16(gnx_graph_t g, const float *d_vals, const uint16_t *d_X, int64_t ldx, int64_t C, const float *d_H0, int64_t ldh0,
+                       float beta, float alpha, int act, const int32_t *d_rows, void *d_out, int out_bf16, int64_t ldo, void *stream) {
+    GNX_CHECK_ARG(g != nullptr, "gnx_spmm_rows_bf16: NULL handle");
+    GNX_CHECK_ARG(C >= 1 && C <= (1 << 20), "gnx_spmm_rows_bf16: feature width %lld not in [1, 2^20]", (long long)C);
+    GNX_CHECK_ARG(d_X != nullptr && d_out != nullptr, "gnx_spmm_rows_bf16: NULL X/out");
+    GNX_CHECK_ARG(ldx >= C && ldo >= C && (d_H0 == nullptr || ldh0 >= C || ldh0 == 0), "gnx_spmm_rows_bf16: leading dimension smaller than C");
+    GNX_CHECK_ARG((const void *)d_X != d_out, "gnx_spmm_rows_bf16: out must not alias X");
+    GNX_CHECK_ARG(out_bf16 == 0 || out_bf16 == 1, "gnx_spmm_rows_bf16: out_bf16 must be 0 or 1");
+    GNX_CHECK_ARG((act & ~GNX_ACT_SKIP_EMPTY) == GNX_ACT_NONE || (act & ~GNX_ACT_SKIP_EMPTY) == GNX_ACT_RELU, "gnx_spmm_rows_bf16: invalid activation %d", act);
+    GNX_CHECK_ARG(d_rows != nullptr || g->a.n_rows == 0, "gnx_spmm_rows_bf16: NULL row map");
+    BfArgs p{};
+    p.vals = d_vals ? d_vals : g->raw_vals;
+    p.Xb = d_X; p.ldx = ldx; p.H0 = d_H0; p.ldh0 = ldh0; p.beta = beta; p.alpha = alpha; p.act = act;
+    p.outv = d_out; p.out_bf16 = out_bf16; p.ldo = ldo; p.C = (int)C; p.out_rows = d_rows; p.map_h0 = true;
     return launch_spmm_bf16(g, g->a, p, (hipStream_t)stream);
 }
 

@@ -10,7 +10,7 @@ import os
 from ctypes import POINTER, c_char_p, c_float, c_int, c_int64, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 800         # include/gnx.h GNX_ABI_VERSION: the header this binding was written against
+ABI_VERSION = 900         # include/gnx.h GNX_ABI_VERSION: the header this binding was written against
 # GNX_LIBRARY: another build of the same library (the tuning build of tools/, `make TUNING=1` -> lib/tune/libgnx.so)
 LIB_PATH = os.environ.get("GNX_LIBRARY") or os.path.join(os.path.dirname(_HERE), "lib", "libgnx.so")
 
@@ -66,6 +66,10 @@ SIGNATURES = {
     "gnx_cast_bf16": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
     "gnx_spmm_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_float, c_float,
                               c_int, c_void_p, c_int, c_int64, c_void_p]),
+    "gnx_spmm_rows_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_float, c_float, c_int,
+                                   c_void_p, c_void_p, c_int, c_int64, c_void_p]),
+    "gnx_halo_pack_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    "gnx_halo_exchange_bf16": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "gnx_appnp_propagate_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int64, c_int, c_void_p, c_void_p,
                                          c_void_p]),
     "gnx_spmm_dropped_chained_bf16": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_int, c_void_p, c_void_p, c_int64, c_int64,

@@ -42,9 +42,21 @@ class NativeBackend:
     def spmm_mix(self, graph, vals, X, H0, beta, alpha, out, out_rows=None, rows=None, skip_empty=False):
         """out[i] = beta * (A X)[i] + alpha * H0[i];  ``rows``: the graph holds a subset of the output rows --
         result row r belongs to out[rows[r]] / H0[rows[r]];  ``out_rows``: scatter of the result only;
-        ``skip_empty``: rows without entries already hold alpha * H0 and are left alone (GNX_ACT_SKIP_EMPTY)."""
+        ``skip_empty``: rows without entries already hold alpha * H0 and are left alone (GNX_ACT_SKIP_EMPTY).
+        A bf16 ``X`` is gathered as bf16 (gnx_spmm_bf16 / gnx_spmm_rows_bf16; H0 stays f32) and ``out`` is f32 or bf16 (rounded once);
+        an f32 ``X`` with a bf16 ``out`` raises."""
         adj = sparse.Adjacency(graph, vals)
         act = nat.ACT_NONE | (nat.ACT_SKIP_EMPTY if skip_empty else 0)
+        if X.dtype == torch.bfloat16:                 # bf16 storage: the operand's dtype picks the kernels, the destination's the rounding
+            if out.dtype not in (torch.float32, torch.bfloat16) or out_rows is not None:
+                raise Exception("spmm_mix: a bf16 operand takes an f32 or bf16 destination and no scatter map")
+            if rows is not None:
+                sparse.launch_rows_bf16(adj, X, H0, beta, alpha, rows, out, act=act)
+            else:
+                sparse._launch_bf16(adj, X, H0, beta, alpha, act, out=out)
+            return
+        if X.dtype != torch.float32 or out.dtype != torch.float32:
+            raise Exception("spmm_mix: an f32 operand needs an f32 destination (%s into %s)" % (X.dtype, out.dtype))
         if rows is not None:
             sparse.launch_rows(adj, X, H0, beta, alpha, rows, out, act=act)
         else:
@@ -64,9 +76,20 @@ class NativeBackend:
         """The chosen half (or both) of the send buffer from the local rows of ``buf`` (gnx_halo_pack)."""
         if plan.n_send == 0:
             return
+        if buf.dtype != send.dtype or buf.dtype not in (torch.float32, torch.bfloat16):
+            raise Exception("halo_pack: the feature buffer and the send buffer must both be f32 or both bf16 (%s, %s)" % (buf.dtype, send.dtype))
+        if buf.dtype == torch.bfloat16:               # bf16 storage: pulled rows copied as they are, pushed sums rounded once
+            with nat.on_device(buf.device):
+                nat.check(nat.lib().gnx_halo_pack_bf16(plan.handle, PARTS[part], nat.ptr(buf), buf.stride(0), buf.shape[1], nat.ptr(send),
+                                                       send.stride(0), nat.current_stream()))
+            return
         with nat.on_device(buf.device):
             nat.check(nat.lib().gnx_halo_pack(plan.handle, PARTS[part], nat.ptr(buf), buf.stride(0), buf.shape[1], nat.ptr(send),
                                               send.stride(0), nat.current_stream()))
+
+    def cast_bf16(self, src, dst):
+        """dst = bf(src) (gnx_cast_bf16): the first iterate of a bf16 propagation, straight into the local rows of its buffer."""
+        sparse.cast_bf16_into(src, dst)
 
     # ---- training with edge dropout on a vertex block (raw values; weights made inside the kernels) ----------
     def set_block(self, graph, row0_global, row0_buf, col_gid):

@@ -154,11 +154,13 @@ class _Lanes:
 
 class ShardState:
     """Buffers of one propagation: per column chunk two ping-pong [regions | local | regions] buffers and a
-    send buffer; H0 and the result hold this rank's rows at full width."""
+    send buffer; H0 and the result hold this rank's rows at full width.  ``storage``: the dtype of the ping-pong and send
+    buffers (f32, or bf16 on request: make_state); H0 and the result are f32 either way."""
 
-    def __init__(self, H0):
+    def __init__(self, H0, storage=torch.float32):
         self.H0 = H0
         self.cur = 0
+        self.storage = storage
 
 
 class ShardedGraph:
@@ -471,24 +473,48 @@ class ShardedGraph:
     def local_view(self, buf):
         return buf[self.n_before:self.n_before + self.n_local]
 
-    def make_state(self, H0, chunks=None):
-        """Allocates the buffers for features of H0's width (this rank's rows)."""
+    def make_state(self, H0, chunks=None, storage=torch.float32):
+        """Allocates the buffers for features of H0's width (this rank's rows).
+        ``storage=torch.bfloat16`` (opt-in; eval-mode propagation only): the ping-pong buffers, the send buffer and every row on the
+        links are bf16 -- half the halo bytes per iteration and half the gather bytes of the block's own SpMM; H0, the sums, the mix
+        and the result stay f32.  Rounding points (include/gnx.h): X~_0 = bf(H0); a pulled row is a copy of the
+        owner's bf16 row; a pushed partial sum is summed in f32 by its sender and sent as bf(sum) (one extra rounding per pushed row
+        and iteration); H_{k+1} leaves its launch as bf(H_{k+1}) for k < K-1 and as f32 on the last iteration.  A ``cover="pull"``
+        plan therefore performs exactly the roundings of the one-GPU bf16 loop (sparse.appnp_propagate ``storage``).  There is NO
+        width allowance here: the one-GPU loop keeps f32 below BF16_MIN_WIDTH on large graphs because its f32 form runs on a
+        relabelled copy that the bf16 form lacks; blocks never use that copy, and the purpose here includes the bytes on the links
+        -- if the caller asks for bf16, bf16 runs.  Not available on a relabelled single block (``relabel=True``: an f32-only
+        device, as in gnx_appnp_propagate_bf16) nor on training blocks (``edge_dropout=True``): both raise."""
+        bf16 = sparse._bf16(storage)
+        if bf16 and self.row_order is not None:
+            raise Exception("make_state: bf16 storage is not available on a relabelled block (ShardedGraph(relabel=True) is f32 only)")
+        if bf16 and self.edge_dropout:
+            raise Exception("make_state: bf16 storage is not available on a training block (ShardedGraph(edge_dropout=True) is f32 only)")
         H0 = H0.to(torch.float32).contiguous()
         if H0.shape[0] != self.n_local:
             raise Exception("make_state: H0 must hold this rank's %d rows" % self.n_local)
-        state = ShardState(H0)
+        state = ShardState(H0, storage)
         C, dev = H0.shape[1], H0.device
         if self.world == 1:
-            state.bufs = [torch.zeros((self.n_local, C), dtype=torch.float32, device=dev) for _ in range(2)]
+            state.bufs = [torch.zeros((self.n_local, C), dtype=storage, device=dev) for _ in range(2)]
+            if bf16:
+                state.result = torch.empty_like(H0)
             if self.row_order is not None:                             # relabelled shard: H0 in the new order, result in the old
                 state.H0_user, state.H0 = H0, H0.index_select(0, self.row_order)
                 state.result = torch.empty_like(H0)
             return state
         state.cols = split_columns(C, self.chunks if chunks is None else chunks)
-        state.bufs = [[torch.zeros((self.n_buf, c1 - c0), dtype=torch.float32, device=dev) for _ in range(2)] for c0, c1 in state.cols]
-        state.send = [torch.zeros((max(self.n_send, 1), c1 - c0), dtype=torch.float32, device=dev) for c0, c1 in state.cols]
+        state.bufs = [[torch.zeros((self.n_buf, c1 - c0), dtype=storage, device=dev) for _ in range(2)] for c0, c1 in state.cols]
+        state.send = [torch.zeros((max(self.n_send, 1), c1 - c0), dtype=storage, device=dev) for c0, c1 in state.cols]
         state.result = torch.empty_like(H0)
         return state
+
+    def _first_iterate(self, state, first, dst):
+        """The first iterate into the local rows of its buffer: a copy, or bf(first) on a bf16 state (gnx_cast_bf16)."""
+        if state.storage is torch.bfloat16:
+            self.backend.cast_bf16(first, dst)
+        else:
+            dst.copy_(first)
 
     def _pack(self, state, c, buf, part="all"):
         """Outgoing rows of chunk c from the local part of ``buf``: the rows the peers pull ("pull": a gather), the partial sums
@@ -527,7 +553,8 @@ class ShardedGraph:
         """H <- H0 (or ``start``: this rank's rows of another initial H, e.g. the input of a GCNII layer whose mix term is
         H0), then K iterations of H <- (1-a) A_hat H + a H0; returns this rank's rows of the result (in the caller's vertex
         order).  ``early_pull`` (default: the graph's setting): the rows the peers pull go on the links as soon as they are
-        gathered, while the pushed partial sums are still being summed -- two messages per peer and iteration instead of one."""
+        gathered, while the pushed partial sums are still being summed -- two messages per peer and iteration instead of one.
+        A bf16 state (make_state ``storage``) runs the same schedule over bf16 buffers: every iteration but the last writes bf16."""
         if start is not None and tuple(start.shape) != tuple(state.H0_user.shape if self.row_order is not None else state.H0.shape):
             raise Exception("propagate: start must have the shape of H0")
         if self.world == 1:
@@ -548,7 +575,7 @@ class ShardedGraph:
             return half, lanes.mark()
 
         for c, (c0, c1) in enumerate(state.cols):
-            self.local_view(state.bufs[c][0]).copy_(first[:, c0:c1])
+            self._first_iterate(state, first[:, c0:c1], self.local_view(state.bufs[c][0]))
             packed.append(pack(c, state.bufs[c][0]))
         for k in range(iterations):
             last = k == iterations - 1
@@ -582,6 +609,15 @@ class ShardedGraph:
         # rows straight back into the caller's order
         if iterations == 0:
             return start if start is not None else (state.H0_user if self.row_order is not None else state.H0)
+        if state.storage is torch.bfloat16:
+            # the launches of a block among several, without the exchange: bf(first) into the first buffer, bf16 between the
+            # iterations, f32 into the result; rows without entries are written while each buffer is first a destination
+            self._first_iterate(state, state.H0 if start is None else start.to(torch.float32), state.bufs[0])
+            for k in range(iterations):
+                last = k == iterations - 1
+                self.backend.spmm_mix(self.graph, None, state.bufs[k % 2], state.H0, 1.0 - a, a, state.result if last else state.bufs[1 - k % 2],
+                                      skip_empty=k >= 2 and not last)
+            return state.result
         state.cur = 0
         src = state.H0
         if start is not None:
@@ -768,7 +804,8 @@ class ShardedGraph:
             self._sync()
             t0 = time.perf_counter()
             if self.world == 1:
-                self.backend.spmm_mix(self.graph, None, state.H0, state.H0, 1.0 - a, a, state.bufs[1])
+                self.backend.spmm_mix(self.graph, None, state.bufs[0] if state.storage is torch.bfloat16 else state.H0, state.H0, 1.0 - a, a,
+                                      state.bufs[1])
             else:
                 for c in range(len(state.cols)):
                     src, dst = state.bufs[c][0], state.bufs[c][1]
@@ -786,7 +823,9 @@ class ShardedGraph:
         """In-run check of the whole vertex-block path (plan, kernels, exchange): for a SYMMETRIC graph H0 = sqrt(column sums) x s
         (a different factor s_c per column) is a fixed point of H <- (1-a) A_hat H + a H0, so after any number of iterations every
         element must still equal H0.  Returns the largest relative deviation over all ranks (rows of isolated vertices must stay 0).
-        Overwrites state.H0.  Collective."""
+        Overwrites state.H0.  Collective.  On a bf16 state (make_state ``storage``) the iterate is rounded to bf16 between the
+        iterations, so the deviation is of bf16 size -- a few 2^-8, not 1e-5: callers that compare it with an f32 bar must hand over
+        an f32 state."""
         if self.sqrt_degree is None:
             raise Exception("fixed_point_error: needs a symmetrically normalised graph")
         C = state.H0.shape[1]

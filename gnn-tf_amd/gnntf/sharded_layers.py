@@ -61,10 +61,20 @@ class ShardedPPRLoop(Layer):
     ``graph_dropout`` > 0 (APPNP's default is 0.5, filter.py:8) needs ``dropout_graph``: the same rows built with
     ``ShardedGraph(..., edge_dropout=True)``.  In training mode every iteration then drops and re-normalises its edges exactly as
     the one-GPU PPRLoop does -- same masks, whatever the partition -- and the backward sends the halo rows of A_k^T g back to
-    their owners; directed graphs are fine on this path.  Every rank must have called gnntf.set_seed with the same seed."""
+    their owners; directed graphs are fine on this path.  Every rank must have called gnntf.set_seed with the same seed.
+
+    ``inference_dtype=torch.bfloat16`` (opt-in; the meaning of GNN.inference_dtype): the eval forward without autograd (``predict()``,
+    validation forwards) propagates over bf16 buffers and moves bf16 rows between the ranks (ShardedGraph.make_state ``storage``);
+    every forward that autograd records and every training-mode forward with edge dropout stays f32, bit for bit."""
 
     def __build__(self, architecture, H0: Layer, graph: "ShardedGraph", restart_probability: float = 0.1, iterations: int = 10,
-                  symmetric: bool = True, graph_dropout: float = 0.0, dropout_graph: "ShardedGraph" = None):
+                  symmetric: bool = True, graph_dropout: float = 0.0, dropout_graph: "ShardedGraph" = None,
+                  inference_dtype=torch.float32):
+        try:
+            sparse._bf16(inference_dtype)
+        except Exception:
+            raise Exception("ShardedPPRLoop: inference_dtype must be torch.float32 or torch.bfloat16") from None
+        self.inference_dtype = inference_dtype
         if architecture.top_shape()[0] != graph.n_local:
             raise Exception("ShardedPPRLoop: the architecture must hold this rank's %d rows" % graph.n_local)
         if graph_dropout != 0 and (dropout_graph is None or not dropout_graph.edge_dropout or dropout_graph.n_local != graph.n_local):
@@ -74,12 +84,15 @@ class ShardedPPRLoop(Layer):
         self._states = dict()
         return architecture.top_shape()
 
-    def _propagate(self, which, H0):
+    def _propagate(self, which, H0, storage=torch.float32):
         C = H0.shape[1]
-        H0 = sparse._padded(H0.to(torch.float32), sparse.friendly_width(C, self.graph.n_global))      # odd class counts run at a line-friendly row width
+        bf16 = storage is torch.bfloat16
+        width = sparse.friendly_width_bf16 if bf16 else sparse.friendly_width
+        H0 = sparse._padded(H0.to(torch.float32), width(C, self.graph.n_global))      # odd class counts run at a line-friendly row width
+        which = which + "_bf16" if bf16 else which
         state = self._states.get(which)
         if state is None or tuple(state.H0.shape) != tuple(H0.shape):
-            state = self._states[which] = self.graph.make_state(H0.clone())
+            state = self._states[which] = self.graph.make_state(H0.clone(), storage=storage)
         elif self.graph.row_order is not None:
             state.H0_user.copy_(H0)
             state.H0.copy_(H0.index_select(0, self.graph.row_order))
@@ -97,6 +110,8 @@ class ShardedPPRLoop(Layer):
             if not self.symmetric:
                 raise Exception("ShardedPPRLoop: gradients need a symmetric adjacency (the backward reuses the forward propagation)")
             return _BlockLoop.apply(H0, self)
+        if self.inference_dtype is torch.bfloat16 and not torch.is_grad_enabled() and not architecture.is_training():
+            return self._propagate("forward", H0.detach(), storage=torch.bfloat16)
         return self._propagate("forward", H0.detach())
 
 

@@ -813,8 +813,9 @@ def to_bf16(X: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def _launch_bf16(adj: Adjacency, X, H0, beta, alpha, act, out_bf16=False):
-    """_launch with X gathered as bf16 (gnx_spmm_bf16): f32 result, or bf16 with ``out_bf16``."""
+def _launch_bf16(adj: Adjacency, X, H0, beta, alpha, act, out_bf16=False, out=None):
+    """_launch with X gathered as bf16 (gnx_spmm_bf16): f32 result, or bf16 with ``out_bf16``.  ``out``: the destination (f32 or
+    bf16 rows, any leading dimension; its dtype decides the rounding)."""
     g = adj.graph
     nat.require_cuda(X, H0)
     _same_device(g, X, H0, adj.diag)
@@ -829,7 +830,14 @@ def _launch_bf16(adj: Adjacency, X, H0, beta, alpha, act, out_bf16=False):
     if adj.vals is None and adj.vals_t is not None:
         raise Exception("spmm: this adjacency only holds transposed-order values")
     C = Xb.shape[1]
-    out = torch.empty((g.n_rows, C), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=Xb.device)
+    if out is None:
+        out = torch.empty((g.n_rows, C), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=Xb.device)
+    else:
+        _same_device(g, out)
+        if (tuple(out.shape) != (g.n_rows, C) or out.dtype not in (torch.float32, torch.bfloat16) or out.stride(1) != 1
+                or out.stride(0) < C or not out.is_cuda):
+            raise Exception("spmm: bad output buffer")
+        out_bf16 = out.dtype == torch.bfloat16
     ldh0 = 0
     if H0 is not None:
         H0 = _as_f32_rows(H0)
@@ -843,6 +851,48 @@ def _launch_bf16(adj: Adjacency, X, H0, beta, alpha, act, out_bf16=False):
         nat.check(nat.lib().gnx_spmm_bf16(g.handle, nat.ptr(adj.vals), nat.ptr(adj.diag), nat.ptr(Xb), Xb.stride(0), C, nat.ptr(H0),
                                           ldh0, float(beta), float(alpha), int(act), nat.ptr(out), 1 if out_bf16 else 0, out.stride(0),
                                           nat.current_stream()))
+    return out
+
+
+def cast_bf16_into(X: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+    """dst = bf(X) (gnx_cast_bf16) for a destination that exists already: f32 rows and bf16 rows of the same shape, any leading
+    dimensions (a column range of a wider matrix into the local rows of a vertex block's buffer)."""
+    nat.require_cuda(X, dst)
+    X = _as_f32_rows(X)
+    if dst.dtype != torch.bfloat16 or tuple(dst.shape) != tuple(X.shape) or dst.stride(1) != 1 or dst.stride(0) < dst.shape[1] or dst.device != X.device:
+        raise Exception("cast_bf16_into: bad destination")
+    if X.shape[0] and X.shape[1]:
+        with nat.on_device(X.device):
+            nat.check(nat.lib().gnx_cast_bf16(nat.ptr(X), X.shape[0], X.shape[1], X.stride(0), nat.ptr(dst), dst.stride(0),
+                                              nat.current_stream()))
+    return dst
+
+
+def launch_rows_bf16(adj: Adjacency, X, H0, beta, alpha, rows, out, act=nat.ACT_NONE):
+    """launch_rows with the gathered rows X stored as bf16 (gnx_spmm_rows_bf16): result row r is written to out[rows[r]] -- f32, or
+    rounded once when ``out`` is bf16 -- and mixes in the f32 H0[rows[r]]."""
+    g = adj.graph
+    nat.require_cuda(X, H0, rows, out)
+    _same_device(g, X, H0, rows, out)
+    if X.dim() != 2 or X.dtype != torch.bfloat16 or X.stride(1) != 1 or X.stride(0) < X.shape[1]:
+        raise Exception("spmm: the bf16 row launch takes a bf16 feature matrix with unit column stride")
+    if X.shape[0] != g.n_cols:
+        raise Exception(f"spmm: features have {X.shape[0]} rows, adjacency expects {g.n_cols}")
+    C = X.shape[1]
+    if rows.dtype != torch.int32 or rows.numel() != g.n_rows or not rows.is_contiguous():
+        raise Exception("spmm: bad row map")
+    if out.dtype not in (torch.float32, torch.bfloat16) or out.dim() != 2 or out.shape[1] != C or out.stride(1) != 1 or out.stride(0) < C:
+        raise Exception("spmm: bad output buffer")
+    ldh0 = 0
+    if H0 is not None:
+        H0 = _as_f32_rows(H0)
+        if tuple(H0.shape) != tuple(out.shape):
+            raise Exception("spmm: H0 shape mismatch")
+        ldh0 = H0.stride(0)
+    with nat.on_device(X.device):
+        nat.check(nat.lib().gnx_spmm_rows_bf16(g.handle, nat.ptr(adj.vals), nat.ptr(X), X.stride(0), C, nat.ptr(H0), ldh0, float(beta),
+                                               float(alpha), int(act), nat.ptr(rows), nat.ptr(out),
+                                               1 if out.dtype == torch.bfloat16 else 0, out.stride(0), nat.current_stream()))
     return out
 
 

@@ -55,8 +55,9 @@ const char *gnx_last_error(void);
  * likewise; 0.6.1 adds the bf16 storage entries (gnx_cast_bf16, gnx_spmm_bf16, gnx_appnp_propagate_bf16) and changes nothing else;
  * 0.7 adds gnx_graph_enable_entry_dropout (the fused training entries accept handles with duplicate entries once it was called);
  * 0.8 adds the bf16 storage entries of the fused training loops (gnx_spmm_dropped_chained_bf16, gnx_spmm_dropped_back_bf16) and
- * changes nothing else. */
-#define GNX_ABI_VERSION 800
+ * changes nothing else; 0.9 adds the bf16 storage entries of the vertex-partitioned path (gnx_spmm_rows_bf16, gnx_halo_pack_bf16,
+ * gnx_halo_exchange_bf16), likewise. */
+#define GNX_ABI_VERSION 900
 int gnx_version(void);
 
 /* ---- graph construction ------------------------------------------------------------
@@ -316,6 +317,12 @@ int gnx_spmm_bf16(gnx_graph_t g, const float *d_vals, const float *d_diag, const
                   void *stream);
 int gnx_appnp_propagate_bf16(gnx_graph_t g, const float *d_vals, const float *d_diag, const float *d_H0, float a, int K, int64_t C,
                              int act, float *d_out, uint16_t *d_work, void *stream);
+/* gnx_spmm_rows_bf16: gnx_spmm_rows with the gathered operand stored as bf16 and the result f32 (out_bf16 = 0) or bf(.) (out_bf16 = 1):
+ *   for the interior / boundary handles of a vertex block.  Result row r lands in out[d_rows[r], :] and mixes in H0[d_rows[r], :]
+ *   (f32); per row the arithmetic and summation order of gnx_spmm_bf16 over the same handle; act may carry GNX_ACT_SKIP_EMPTY. */
+int gnx_spmm_rows_bf16(gnx_graph_t g, const float *d_vals, const uint16_t *d_X, int64_t ldx, int64_t C, const float *d_H0,
+                       int64_t ldh0, float beta, float alpha, int act, const int32_t *d_rows, void *d_out, int out_bf16, int64_t ldo,
+                       void *stream);
 
 /* ---- opt-in bf16 feature storage: the fused training loops -----------------------------------------------------------------
  * gnx_spmm_dropped_chained and gnx_spmm_dropped_back, argument for argument, with the GATHERED operand d_X stored as bf16 (uint16_t
@@ -421,6 +428,27 @@ int gnx_halo_plan_layout(gnx_halo_plan_t plan, int64_t *n_buf, int64_t *local_ro
 int gnx_halo_pack(gnx_halo_plan_t plan, int part, const float *d_X, int64_t ldx, int64_t C, float *d_send, int64_t lds, void *stream);
 int gnx_halo_exchange(gnx_halo_plan_t plan, int part, void *nccl_comm, const float *d_send, float *d_X, int64_t C, void *stream);
 int gnx_halo_bind_rccl(void *nccl_group_start, void *nccl_group_end, void *nccl_send, void *nccl_recv);
+/* ---- opt-in bf16 feature storage on a vertex block: the [regions | local rows | regions] buffers, the send buffer and every row
+ * on the links as bf16 (uint16_t bit patterns; bf = the cast of gnx_cast_bf16, u = 2^-8).  The plan and its layout are those of the
+ * f32 entries (rows, not bytes).  Rounding points of K >= 1 iterations on a block:
+ *   - X~_0 = bf(H0) (or bf(start)) for this rank's rows, cast into the local rows of the first buffer (gnx_cast_bf16, strided dst);
+ *   - a PULLED row is a copy of the owner's bf16 row: no rounding (gnx_halo_pack_bf16, pull half: a gather of 16 / 8 / 4 / 2-byte
+ *     units, whatever the width, the leading dimensions and the alignment allow);
+ *   - a PUSHED partial sum s_iq = sum_j A_hat[i,j] X~_k[j] (j over the sender q's columns) is summed in f32 by the sender and sent as
+ *     bf(s_iq) (gnx_halo_pack_bf16, push half = gnx_spmm_bf16 over the push graph with out_bf16 = 1): one extra rounding per pushed
+ *     row and iteration; the receiver adds the widened value with weight 1;
+ *   - H_{k+1} = (1-a) acc + a H0 in f32 with f32 H0 (gnx_spmm_bf16 / gnx_spmm_rows_bf16 over the block's handles); for k < K-1 it
+ *     leaves the launch as bf(H_{k+1}) into the local rows of the other buffer (out_bf16 = 1), the last iteration writes f32 H_K;
+ *   - rows without entries follow the settled-row rule of gnx_appnp_propagate (GNX_ACT_SKIP_EMPTY from k >= 2, or at once when nobody
+ *     references them; never on the last iteration).
+ * All sums, H0, the mix and the result are f32; no float atomics: two runs give the same bits.  A plan WITHOUT pushed rows performs
+ * exactly the roundings of gnx_appnp_propagate_bf16, row by row in the same summation order: bit for bit the one-GPU bf16 loop.
+ * gnx_halo_pack_bf16 / gnx_halo_exchange_bf16: gnx_halo_pack / gnx_halo_exchange argument for argument over bf16 buffers (the
+ * exchange uses ncclBfloat16; same grouping, receives before sends, same error paths); an empty plan packs as GNX_OK. */
+int gnx_halo_pack_bf16(gnx_halo_plan_t plan, int part, const uint16_t *d_X, int64_t ldx, int64_t C, uint16_t *d_send, int64_t lds,
+                       void *stream);
+int gnx_halo_exchange_bf16(gnx_halo_plan_t plan, int part, void *nccl_comm, const uint16_t *d_send, uint16_t *d_X, int64_t C,
+                           void *stream);
 /* out[r,:] = X[idx[r],:] for int32 row ids (the pulled half of gnx_halo_pack as a call of its own); any width, grid-stride. */
 int gnx_gather_rows32(const float *d_X, int64_t ldx, const int32_t *d_idx, int64_t n_idx, int64_t C, float *d_out, int64_t ldo,
                       void *stream);
@@ -458,7 +486,8 @@ int gnx_probe_block_xcd(int64_t n_blocks, int32_t *d_xcd_out, void *stream);
  * string; for profiles and tests): "spmm_wave", "spmm_group8" ... "spmm_group32" (lanes per row; "spmm_group4+chunks": the merged small-graph launch), "..._drop" (weights made
  * in the kernel), "...+chunks" (structures below 2^20 rows: the chunks of the long rows share the launch of the short rows),
  * "spmm_gcnii_mfma", "spmm+dense_mfma"; the bf16 entries report "spmm_wave_bf16", "spmm_group8_bf16" ... "spmm_group32_bf16",
- * "...+long_bf16" (hub rows through the chunk kernels) and "...+chunks_bf16"; the bf16 training entries report the f32 training
+ * "...+long_bf16" (hub rows through the chunk kernels) and "...+chunks_bf16" (gnx_spmm_rows_bf16 and the push half of
+ * gnx_halo_pack_bf16 -- on the push graph's handle -- report these same names: no new suffix); the bf16 training entries report the f32 training
  * names with "_bf16" appended ("spmm_group16_drop_bf16", "spmm_wave_drop_entries_bf16", ...), "+long" after the row class when hub
  * rows went through the chunk kernels ("spmm_group8+long_drop_bf16"). */
 const char *gnx_graph_last_kernel(gnx_graph_t g);
