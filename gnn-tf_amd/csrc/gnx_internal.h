@@ -306,7 +306,7 @@ struct PerDeviceOnce {
 
 int launch_spmm(gnx_graph *g, const Csr &m, SpmmArgs &p, hipStream_t s);                      // gnx_spmm.hip
 void launch_long_rows(const SpmmArgs &p, hipStream_t s);                                       // gnx_spmm.hip: long rows only
-const char *launch_spmm_dropped(const SpmmArgs &p, int vec, bool has_long, hipStream_t s);    // gnx_spmm_train.hip
+const char *launch_spmm_dropped(const SpmmArgs &p, int vec, hipStream_t s);              // gnx_spmm_train.hip
 // gnx_spmm_train.hip, shared with gnx_spmm_train_bf16.hip: a handle with duplicate entries needs gnx_graph_enable_entry_dropout
 // (GNX_ERR_UNSUPPORTED otherwise); the per-slot values and entry tables a fused launch over the handle reads
 int refuse_duplicates(const gnx_graph *g, const char *fn);

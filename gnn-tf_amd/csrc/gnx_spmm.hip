@@ -20,264 +20,12 @@
 //     across the chunk's entries + a fixed xor tree), then added in chunk order by a second kernel
 //     (fixed order: results are bitwise reproducible, no float atomics).  Chunks are processed in
 //     column-window order (Csr::chunk_order) so the hub rows they share stay in L2 / Infinity Cache.
-#include "gnx_spmm_device.h"
+//
+// Every dispatch class is written once, over how a feature row is stored (the row-storage policy of gnx_spmm_device.h), in
+// gnx_spmm_eval.h; this unit instantiates them for f32 rows and holds the f32 entry points, gnx_spmm_bf16.hip does the same for bf16.
+#include "gnx_spmm_eval.h"
 
 namespace {
-
-// ---- wide path: one wave per row -----------------------------------------------------------
-// tune bits (GNX_TUNE, experiments): 1 = degree-binned row order, 2 = non-temporal H0/out, 4 = non-temporal col/val
-template <int VEC, int U, int WPB>
-__global__ __launch_bounds__(64 * WPB) void k_spmm_wave(const SpmmArgs p) {
-    const int lane = threadIdx.x & 63;
-    const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t slot = p.slot0 + xcd_block(p) * WPB + wib;
-    if (slot >= p.n_rows) return;
-    const int64_t row = p.row_list ? (int64_t)__builtin_amdgcn_readfirstlane(p.row_list[slot])
-                                   : ((p.tune & 1) ? (int64_t)__builtin_amdgcn_readfirstlane(p.row_order[slot]) : slot);
-    const int64_t beg = p.rowptr[row], end = p.rowptr[row + 1];
-    if (end - beg > p.long_row) return;  // k_spmm_long_* take it
-    if (p.skip_empty && beg == end) return;   // GNX_ACT_SKIP_EMPTY: the row already holds alpha * H0 from an earlier iteration
-    for (int c0 = 0; c0 < p.C; c0 += 64 * VEC) {
-        const int c = c0 + lane * VEC;
-        const bool active = c < p.C;
-        float acc[VEC];
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-        wave_accumulate<VEC, U>(p.colidx, p.vals, p.X, p.ldx, beg, end, active ? c : 0, lane, acc, (p.tune & 4) != 0);
-        epilogue_store<VEC>(p, row, c, active, acc, (p.tune & 2) != 0);
-    }
-}
-
-// ---- narrow path: G lanes per row, 256/G rows per block ---------------------------------------
-// PIPE: the (col, val) pairs of batch b+1 are fetched while the gathers of batch b are in flight.
-template <int VEC, int G, int U, bool PIPE>
-__device__ __forceinline__ void group_rows(const SpmmArgs &p, int64_t block) {
-    constexpr int RPB = 256 / G;
-    const int sub = threadIdx.x % G;
-    const int64_t slot = p.slot0 + block * RPB + threadIdx.x / G;
-    if (slot >= p.n_rows) return;
-    const int64_t row = p.row_order ? (int64_t)p.row_order[slot] : slot;   // degree-binned: the rows of one wave have similar lengths
-    int64_t beg, end;
-    if (p.slot_beg) { beg = p.slot_beg[slot]; end = beg + p.slot_cnt[slot]; }      // (slot order: coalesced, independent of the row_order load)
-    else { beg = p.rowptr[row]; end = p.rowptr[row + 1]; }
-    if (end - beg > p.long_row) return;
-    if (p.skip_empty && beg == end) return;   // GNX_ACT_SKIP_EMPTY
-    for (int c0 = 0; c0 < p.C; c0 += G * VEC) {
-        const int c = c0 + sub * VEC;
-        const bool active = c < p.C;
-        const float *__restrict__ Xc = p.X + (active ? c : 0);
-        float acc[VEC];
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-        if (PIPE) {
-            int jn[U];
-            float wn[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const bool ok = beg + u < end;
-                jn[u] = ok ? p.colidx[beg + u] : -1;
-                wn[u] = ok ? p.vals[beg + u] : 0.f;
-            }
-            for (int64_t e = beg; e < end; e += U) {
-                float x[U][VEC];
-                float w[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {          // gathers of this batch
-                    w[u] = wn[u];
-                    if (jn[u] >= 0) vload<VEC>(x[u], Xc + (int64_t)jn[u] * p.ldx);
-                    else {
-#pragma unroll
-                        for (int v = 0; v < VEC; ++v) x[u][v] = 0.f;
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) {          // indices of the next batch, behind the gathers
-                    const bool ok = e + U + u < end;
-                    jn[u] = ok ? p.colidx[e + U + u] : -1;
-                    wn[u] = ok ? p.vals[e + U + u] : 0.f;
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
-            }
-        } else {
-            for (int64_t e = beg; e < end; e += U) {   // U entries in flight per lane, ragged tail predicated
-                float x[U][VEC];
-                float w[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    if (e + u < end) {
-                        const int j = p.colidx[e + u];
-                        w[u] = p.vals[e + u];
-                        vload<VEC>(x[u], Xc + (int64_t)j * p.ldx);
-                    } else {
-                        w[u] = 0.f;
-#pragma unroll
-                        for (int v = 0; v < VEC; ++v) x[u][v] = 0.f;
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
-            }
-        }
-        epilogue_store<VEC>(p, row, c, active, acc);
-    }
-}
-
-// The same rows with a COOPERATIVE index fetch, for the narrow groups (G <= 8 lanes per row, C <= 32).  In group_rows every lane of a
-// row's group loads the same (col, val) pair, so a step of four entries costs four index loads + four value loads + four gathers
-// per lane: twelve vector-memory instructions, each served line by line by the CU's L1 pipe (sixteen different lines per wave
-// instruction).  At narrow widths that pipe is what a launch waits for next to the fabric (SQ counters at C = 8: 60 % of the
-// wave cycles are issue stalls, the TCP is busy for the whole launch; with every gather made to hit, a launch still takes 57 %
-// of its time -- profiles/notes/r03_narrow_*).  Here lane `sub` of the group loads the pair of entry base + sub -- ONE index
-// load and one value load per four entries -- and the group reads them out of each other's registers (ds_bpermute, off the memory
-// pipe); the next batch's pairs are fetched behind the gathers.  Entries are added in ascending order as before: same bits.
-// Measured (RMAT 10M / 100M, K = 10): C = 8 17.2 -> 16.4 ms, C = 16 19.5 -> 19.0, C = 32 22.2 -> 21.9; the all-gathers-hit floor
-// 9.8 -> 7.6 ms at C = 8.  The wider groups LOSE 2-4 % with it (their gathers dominate the pipe, the shuffles only add latency).
-template <int VEC, int G, int B>
-__device__ __forceinline__ void group_rows_coop(const SpmmArgs &p, int64_t block) {
-    constexpr int RPB = 256 / G;
-    const int sub = threadIdx.x % G;
-    const int64_t slot = p.slot0 + block * RPB + threadIdx.x / G;
-    if (slot >= p.n_rows) return;
-    const int64_t row = p.row_order ? (int64_t)p.row_order[slot] : slot;
-    int64_t beg, end;
-    if (p.slot_beg) { beg = p.slot_beg[slot]; end = beg + p.slot_cnt[slot]; }
-    else { beg = p.rowptr[row]; end = p.rowptr[row + 1]; }
-    if (end - beg > p.long_row) return;
-    if (p.skip_empty && beg == end) return;   // GNX_ACT_SKIP_EMPTY
-    for (int c0 = 0; c0 < p.C; c0 += G * VEC) {
-        const int c = c0 + sub * VEC;
-        const bool active = c < p.C;
-        const float *__restrict__ Xc = p.X + (active ? c : 0);
-        float acc[VEC];
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-        int myj = -1;
-        float myw = 0.f;
-        if (sub < B && beg + sub < end) { myj = p.colidx[beg + sub]; myw = p.vals[beg + sub]; }
-        for (int64_t e = beg; e < end; e += B) {
-            float x[B][VEC];
-            float w[B];
-#pragma unroll
-            for (int u = 0; u < B; ++u) {                                   // gathers of this batch
-                const int j = __shfl(myj, u, G);
-                w[u] = __shfl(myw, u, G);
-                if (j >= 0) vload<VEC>(x[u], Xc + (int64_t)j * p.ldx);
-                else {
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) x[u][v] = 0.f;
-                }
-            }
-            myj = -1; myw = 0.f;                                            // pairs of the next batch, behind the gathers
-            if (sub < B && e + B + sub < end) { myj = p.colidx[e + B + sub]; myw = p.vals[e + B + sub]; }
-#pragma unroll
-            for (int u = 0; u < B; ++u)
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
-        }
-        epilogue_store<VEC>(p, row, c, active, acc);
-    }
-}
-
-template <int VEC, int G, int U, bool PIPE>
-__global__ __launch_bounds__(256) void k_spmm_group(const SpmmArgs p) {
-    if (G <= 8) group_rows_coop<VEC, G, 4>(p, xcd_block(p));
-    else group_rows<VEC, G, U, PIPE>(p, xcd_block(p));
-}
-
-// ---- long rows ---------------------------------------------------------------------------------
-template <int VEC, int U>
-__global__ __launch_bounds__(256) void k_spmm_long_partial(const SpmmArgs p) {
-    const int lane = threadIdx.x & 63;
-    const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t cslot = (int64_t)blockIdx.x * 4 + wib;
-    if (cslot >= p.n_chunks) return;
-    const int64_t chunk = p.chunk_order ? (int64_t)p.chunk_order[cslot] : cslot;   // column-window order
-    const int32_t li = p.chunk_long[chunk];
-    const int64_t row = p.long_rows[li];
-    const int64_t beg = p.rowptr[row] + (chunk - p.long_chunk_ptr[li]) * p.long_chunk;
-    const int64_t rend = p.rowptr[row + 1];
-    const int64_t end = beg + p.long_chunk < rend ? beg + p.long_chunk : rend;
-    for (int c0 = 0; c0 < p.C; c0 += 64 * VEC) {
-        const int c = c0 + lane * VEC;
-        const bool active = c < p.C;
-        float acc[VEC];
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-        wave_accumulate<VEC, U>(p.colidx, p.vals, p.X, p.ldx, beg, end, active ? c : 0, lane, acc);
-        if (active) vstore<VEC>(p.partial + chunk * (int64_t)p.C + c, acc);
-    }
-}
-
-// Narrow features: a chunk's entries are dealt round-robin to the wave's 64/G sub-groups of G lanes
-// (each sub-group gathers whole C-wide rows), then the sub-group sums are added with a fixed xor tree.
-template <int VEC, int G, int U>
-__device__ __forceinline__ void long_chunks_group(const SpmmArgs &p, int64_t block) {
-    constexpr int NS = 64 / G;
-    const int lane = threadIdx.x & 63;
-    const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t cslot = block * 4 + wib;
-    if (cslot >= p.n_chunks) return;
-    const int64_t chunk = p.chunk_order ? (int64_t)p.chunk_order[cslot] : cslot;   // column-window order
-    const int32_t li = p.chunk_long[chunk];
-    const int64_t row = p.long_rows[li];
-    const int64_t beg = p.rowptr[row] + (chunk - p.long_chunk_ptr[li]) * p.long_chunk;
-    const int64_t rend = p.rowptr[row + 1];
-    const int64_t end = beg + p.long_chunk < rend ? beg + p.long_chunk : rend;
-    const int sub = lane / G;
-    const int c = (lane % G) * VEC;
-    const bool active = c < p.C;
-    const float *__restrict__ Xc = p.X + (active ? c : 0);
-    float acc[VEC];
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-    for (int64_t e = beg + sub; e < end; e += (int64_t)NS * U) {
-        float x[U][VEC];
-        float w[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t eu = e + (int64_t)u * NS;
-            if (eu < end) {
-                const int j = p.colidx[eu];
-                w[u] = p.vals[eu];
-                vload<VEC>(x[u], Xc + (int64_t)j * p.ldx);
-            } else {
-                w[u] = 0.f;
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) x[u][v] = 0.f;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
-    }
-#pragma unroll
-    for (int off = G; off < 64; off <<= 1)
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) acc[v] += __shfl_xor(acc[v], off);
-    if (sub == 0 && active) vstore<VEC>(p.partial + chunk * (int64_t)p.C + c, acc);
-}
-
-template <int VEC, int G, int U>
-__global__ __launch_bounds__(256) void k_spmm_long_partial_group(const SpmmArgs p) {
-    long_chunks_group<VEC, G, U>(p, blockIdx.x);
-}
-
-// Short rows and the chunks of the long rows in ONE launch, for graphs with few chunks (a citation-graph-sized matrix has a few
-// hundred): a chunk is one wave walking 512 entries, so a launch of a few hundred waves is bound by the latency of that walk
-// (0.11 ms at C = 128) while most of the card idles; here the chunk blocks are dealt first and the short rows fill the rest of
-// the card under them.  Same per-row arithmetic as the two separate launches; k_spmm_long_reduce follows as before.
-template <int VEC, int G, bool PIPE>
-__global__ __launch_bounds__(256) void k_spmm_group_and_chunks(const SpmmArgs p, int chunk_blocks) {
-    if ((int)blockIdx.x < chunk_blocks) long_chunks_group<VEC, G, 4>(p, blockIdx.x);
-    else if (G <= 8) group_rows_coop<VEC, G, 4>(p, (int64_t)blockIdx.x - chunk_blocks);
-    else group_rows<VEC, G, 4, PIPE>(p, (int64_t)blockIdx.x - chunk_blocks);
-}
 
 // ---- small helpers --------------------------------------------------------------------------------
 __global__ void k_gather_vals(const float *__restrict__ vals, const int32_t *__restrict__ perm, int64_t n,
@@ -298,89 +46,6 @@ __global__ __launch_bounds__(256) void k_gather_rows32(const float *__restrict__
     }
 }
 
-template <int VEC>
-const char *launch_rows(const SpmmArgs &p0, hipStream_t s) {
-    SpmmArgs p = p0;
-    const int lanes = (p.C + VEC - 1) / VEC;  // lanes needed to cover one row
-    // GNX_ACT_SKIP_EMPTY on the sub-wave kernels: they walk the rows through row_order, whose trailing slots are exactly the rows
-    // without entries -- those slots are not launched at all (on the R-MAT workloads 60 % of the rows: no wave, no row-pointer read)
-    bool trim = lanes <= 32 && p.skip_empty && p.row_order != nullptr && p.n_nonempty < p.n_rows;
-#ifdef GNX_TUNING
-    if (p.tune & (1 << 21)) trim = false;                       // (A/B switch of the tuning build)
-#endif
-    if (trim) p.n_rows = p.n_nonempty;
-    // the one-wave-per-row kernels keep the rows in ascending order (their H0 / out rows stream): they walk the ascending list of
-    // the rows that have entries instead
-    bool list = lanes > 32 && p.skip_empty && p.nonempty_rows != nullptr && p.n_nonempty < p.n_rows && !(p.tune & 1);
-#ifdef GNX_TUNING
-    if (p.tune & (1 << 21)) list = false;
-#endif
-    if (list) { p.row_list = p.nonempty_rows; p.n_rows = p.n_nonempty; }
-    if (p.n_rows == 0) return "spmm_none";
-    if (lanes > 32) {
-        // measured: U = 8 rows in flight is the plateau (U=4 +0.7 %, U=16 +17 %, forcing 8 waves/SIMD +14 %,
-        // degree-ordered rows +9 %, non-temporal H0/out/index loads +-0 %)
-        // measured (tools/tune_spmm.py): 8 waves per block are 1.6 % faster than 4 when the row is one tile wide
-        // (C = 256), 0.6 % slower at two tiles (C = 512); 2 and 16 waves per block lose 3-11 %
-        if (p.C <= 64 * VEC) GNX_ROW_PIECES((k_spmm_wave<VEC, 8, 8>), 8, 512);
-        else                 GNX_ROW_PIECES((k_spmm_wave<VEC, 8, 4>), 4, 256);
-        return "spmm_wave";
-    }
-    // measured (tools/tune_spmm.py, RMAT 10M/100M): prefetching the next (col, val) batch behind the
-    // gathers pays for G <= 8 (C <= 32: -8..-12 %) and not for the wider groups
-    const int gsel = (p.tune >> 8) & 3;          // experiments: 1 = force plain, 2 = force pipelined
-#define GNX_GROUP(G, RPB_, PIPE_DEFAULT)                                                              \
-    do {                                                                                              \
-        const bool pipe = gsel == 2 || (gsel == 0 && PIPE_DEFAULT);                                   \
-        if (pipe) GNX_ROW_PIECES((k_spmm_group<VEC, G, 4, true>), RPB_, 256);                         \
-        else      GNX_ROW_PIECES((k_spmm_group<VEC, G, 4, false>), RPB_, 256);                        \
-    } while (0)
-    // (round 2, one-process A/B at C = 128 / 64: 8 entries in flight per lane 8.86 / 4.57 ms, pipelined 8.98 / 4.37, 2 entries 8.24 / 4.37
-    //  against 8.24 / 4.36 for the shipped 4 -- the sub-wave kernels sit on the bandwidth plateau, not on latency)
-    if (lanes > 16) { GNX_GROUP(32, 8, false); return "spmm_group32"; }
-    if (lanes > 8)  { GNX_GROUP(16, 16, false); return "spmm_group16"; }
-    // Rows of up to 4 lanes (C <= 16) run on 8-lane groups as well: the four lanes beyond the row's width only take part in the
-    // cooperative index fetch (round 6, config-4 graph: C = 8 1.543 -> 1.509 ms per iteration, C = 16 1.777 -> 1.741; same bits;
-    // 8 entries per batch: 1.515 / 1.755; 16-lane groups: 1.77 / 1.96).  (Round 2 tried the other direction, 2 lanes per row for
-    // C <= 8: 2.40 vs 2.28 ms -- every gather is one 128-byte line whatever the width, lane use is not the limit.)
-    GNX_GROUP(8, 32, true);
-    return "spmm_group8";
-#undef GNX_GROUP
-}
-
-// few chunks (see k_spmm_group_and_chunks): one launch for the short rows and the chunks, then the reduce
-
-template <int VEC>
-const char *launch_rows_and_chunks(const SpmmArgs &p, hipStream_t s) {
-    const int lanes = (p.C + VEC - 1) / VEC;
-    // (tune bit 65536: tuning builds' A/B of the merged launch on big graphs)
-    if (lanes > 32 || p.n_long == 0 || (p.n_rows >= SMALL_ROWS && !(p.tune & 65536)) || ((p.tune >> 8) & 3) != 0 || (p.tune & 4096)) return nullptr;
-    const unsigned cb = blocks_for(p.n_chunks, 4);
-    const char *name;
-#define GNX_BOTH(G, RPB_, PIPE_)                                                                                          \
-    hipLaunchKernelGGL((k_spmm_group_and_chunks<VEC, G, PIPE_>), dim3(cb + blocks_for(p.n_rows, RPB_)), dim3(256), 0, s, p, (int)cb)
-    if (lanes > 16)     { GNX_BOTH(32, 8, false); name = "spmm_group32+chunks"; }
-    else if (lanes > 8) { GNX_BOTH(16, 16, false); name = "spmm_group16+chunks"; }
-    else if (lanes > 4) { GNX_BOTH(8, 32, true); name = "spmm_group8+chunks"; }
-    // (rows of up to 4 lanes keep 4-lane groups HERE: the group width is also how a chunk's entries are dealt to sub-groups, i.e. the
-    //  long rows' summation order, which the training kernels of the same width reproduce bit for bit; these launches are latency-bound)
-    else                { GNX_BOTH(4, 64, true); name = "spmm_group4+chunks"; }
-#undef GNX_BOTH
-    GNX_LAUNCH((k_spmm_long_reduce<VEC>), blocks_for(p.n_long, 4), p);
-    return name;
-}
-
-template <int VEC>
-void launch_long(const SpmmArgs &p, hipStream_t s) {
-    const int lanes = (p.C + VEC - 1) / VEC;
-    if (lanes > 32)      GNX_LAUNCH((k_spmm_long_partial<VEC, 8>), blocks_for(p.n_chunks, 4), p);
-    else if (lanes > 16) GNX_LAUNCH((k_spmm_long_partial_group<VEC, 32, 4>), blocks_for(p.n_chunks, 4), p);
-    else if (lanes > 8)  GNX_LAUNCH((k_spmm_long_partial_group<VEC, 16, 4>), blocks_for(p.n_chunks, 4), p);
-    else if (lanes > 4)  GNX_LAUNCH((k_spmm_long_partial_group<VEC, 8, 4>), blocks_for(p.n_chunks, 4), p);
-    else                 GNX_LAUNCH((k_spmm_long_partial_group<VEC, 4, 4>), blocks_for(p.n_chunks, 4), p);
-    GNX_LAUNCH((k_spmm_long_reduce<VEC>), blocks_for(p.n_long, 4), p);
-}
-
 }  // namespace
 
 namespace gnx {
@@ -390,53 +55,26 @@ int tune_override = -1;   // set through gnx_debug_set_tune (tuning builds only:
 #endif
 
 int launch_spmm(gnx_graph *g, const Csr &m, SpmmArgs &p, hipStream_t s) {
-    p.rowptr = m.rowptr; p.colidx = m.colidx; p.n_rows = m.n_rows; p.n_nonempty = m.n_nonempty; p.nonempty_rows = m.nonempty_rows; p.row_list = nullptr;
-    p.slot_beg = m.slot_beg; p.slot_cnt = m.slot_cnt;
-    p.long_rows = m.long_rows; p.long_chunk_ptr = m.long_chunk_ptr; p.chunk_long = m.chunk_long;
-    p.row_order = m.row_order;
-    p.xcd_rows = m.order_window;
-    p.chunk_order = m.chunk_order;
+    int rc = bind_csr(g, m, p, s);
+    if (rc != GNX_OK) return rc;
 #ifdef GNX_TUNING   // kernel-variant switches exist only in tuning builds (tools/tune_spmm.py); the product library has none
     {
         static const int tune = [] { const char *e = getenv("GNX_TUNE"); return e ? atoi(e) : 0; }();
         p.tune = tune_override >= 0 ? tune_override : tune;
     }
-#else
-    p.tune = 0;
+    if (p.tune & 16384) p.ldx = 0;             // (every gather reads row 0 -- what a launch costs without its gather misses; wrong results)
 #endif
-    p.n_long = m.n_long; p.n_chunks = m.n_chunks; p.long_row = m.long_row; p.long_chunk = m.long_chunk;
-    p.partial = nullptr;
-    if (p.tune & 16384) p.ldx = 0;             // (tuning builds: every gather reads row 0 -- what a launch costs without its gather misses; wrong results)
-    p.skip_empty = (p.act & GNX_ACT_SKIP_EMPTY) != 0 && p.diag == nullptr;
-    p.act &= ~GNX_ACT_SKIP_EMPTY;
     if (m.n_rows == 0) return GNX_OK;
-    if (m.n_long > 0) {
-        int rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)p.C * sizeof(float), s);
-        if (rc != GNX_OK) return rc;
-        p.partial = g->partial;
-    }
-    const int vec = pick_vec(p);   // (tried for C = 128: one wave per row with float2 lanes instead of 32-lane groups of float4 -- 10.9 vs 8.2 ms)
-    const char *name;
-    if (p.fuse.D != nullptr) {                 // training iteration: the kernels of gnx_spmm_train.hip
-        name = launch_spmm_dropped(p, vec, m.n_long > 0, s);
-        g->last_kernel = name;
-        GNX_HIP(hipGetLastError());
-        return GNX_OK;
-    }
-    if (vec == 4)      { if (!(name = launch_rows_and_chunks<4>(p, s))) { name = launch_rows<4>(p, s); if (m.n_long) launch_long<4>(p, s); } }
-    else if (vec == 2) { if (!(name = launch_rows_and_chunks<2>(p, s))) { name = launch_rows<2>(p, s); if (m.n_long) launch_long<2>(p, s); } }
-    else               { if (!(name = launch_rows_and_chunks<1>(p, s))) { name = launch_rows<1>(p, s); if (m.n_long) launch_long<1>(p, s); } }
-    g->last_kernel = name;
+    // (tried for C = 128: one wave per row with float2 lanes instead of 32-lane groups of float4 -- 10.9 vs 8.2 ms)
+    // a training iteration (p.fuse.D) goes to the kernels of gnx_spmm_train.hip
+    g->last_kernel = p.fuse.D != nullptr ? launch_spmm_dropped(p, F32Rows::vec(p), s) : launch_eval<F32Rows>(p, s);
     GNX_HIP(hipGetLastError());
     return GNX_OK;
 }
 
 // the long rows of a launch whose short rows another translation unit's kernel took (gnx_gcnii.hip): partial sums + reduce
 void launch_long_rows(const SpmmArgs &p, hipStream_t s) {
-    const int vec = pick_vec(p);
-    if (vec == 4) launch_long<4>(p, s);
-    else if (vec == 2) launch_long<2>(p, s);
-    else launch_long<1>(p, s);
+    with_vec<F32Rows>(F32Rows::vec(p), [&](auto V) { launch_long<F32Rows, V()>(p, s); });
 }
 
 }  // namespace gnx

@@ -1,10 +1,13 @@
-// Device-side pieces every SpMM translation unit shares (gnx_spmm.hip: the eval kernels and their launchers; gnx_spmm_train.hip: the
-// training kernels; gnx_gcnii.hip: the GCNII layer): vector loads / stores, the wave-wide accumulate, the fused epilogue of
-// filter.py:20-22, the XCD block map, the long rows' second pass, and the launch plumbing.  Internal linkage throughout: every
-// translation unit gets its own copies (all of it is templates / forceinline device code / small host helpers).
+// Device-side pieces every SpMM translation unit shares: vector loads / stores, the row-storage policy (F32Rows / Bf16RowsT: how a
+// gathered feature row and a finished row are stored), the wave-wide accumulate, the fused epilogue of filter.py:20-22, the slot and
+// chunk prologues, the XCD block map, the long rows' second pass, and the launch plumbing.  The dispatch classes themselves are written
+// once over the policy in gnx_spmm_eval.h (eval) and gnx_spmm_drop.h (training) and instantiated by gnx_spmm.hip / gnx_spmm_train.hip
+// for f32 rows and by gnx_spmm_bf16.hip / gnx_spmm_train_bf16.hip for bf16 rows.  Internal linkage throughout: every translation unit
+// gets its own copies (all of it is templates / forceinline device code / small host helpers).
 #pragma once
 #include <stdlib.h>
 #include <algorithm>
+#include <type_traits>
 
 #include "gnx_internal.h"
 
@@ -17,18 +20,29 @@ template <> struct VecT<1> { using type = float; };
 template <> struct VecT<2> { using type = float2; };
 template <> struct VecT<4> { using type = float4; };
 
+// (VEC = 8, the f32 side of bf16 rows at 8 values per lane: two 16-byte accesses)
 template <int VEC>
 __device__ __forceinline__ void vload(float (&x)[VEC], const float *__restrict__ p) {
-    using T = typename VecT<VEC>::type;
-    const T v = *reinterpret_cast<const T *>(p);
-    __builtin_memcpy(x, &v, sizeof(T));
+    if constexpr (VEC == 8) {
+        vload<4>(*reinterpret_cast<float(*)[4]>(&x[0]), p);
+        vload<4>(*reinterpret_cast<float(*)[4]>(&x[4]), p + 4);
+    } else {
+        using T = typename VecT<VEC>::type;
+        const T v = *reinterpret_cast<const T *>(p);
+        __builtin_memcpy(x, &v, sizeof(T));
+    }
 }
 template <int VEC>
 __device__ __forceinline__ void vstore(float *__restrict__ p, const float (&x)[VEC]) {
-    using T = typename VecT<VEC>::type;
-    T v;
-    __builtin_memcpy(&v, x, sizeof(T));
-    *reinterpret_cast<T *>(p) = v;
+    if constexpr (VEC == 8) {
+        vstore<4>(p, *reinterpret_cast<const float(*)[4]>(&x[0]));
+        vstore<4>(p + 4, *reinterpret_cast<const float(*)[4]>(&x[4]));
+    } else {
+        using T = typename VecT<VEC>::type;
+        T v;
+        __builtin_memcpy(&v, x, sizeof(T));
+        *reinterpret_cast<T *>(p) = v;
+    }
 }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -41,17 +55,150 @@ template <> struct NatT<4> { using type = f32x4; };
 // streaming (touched once per launch) data: non-temporal so it does not evict gathered rows
 template <int VEC>
 __device__ __forceinline__ void vload_nt(float (&x)[VEC], const float *__restrict__ p) {
-    using T = typename NatT<VEC>::type;
-    const T v = __builtin_nontemporal_load(reinterpret_cast<const T *>(p));
-    __builtin_memcpy(x, &v, sizeof(T));
+    if constexpr (VEC == 8) {
+        vload_nt<4>(*reinterpret_cast<float(*)[4]>(&x[0]), p);
+        vload_nt<4>(*reinterpret_cast<float(*)[4]>(&x[4]), p + 4);
+    } else {
+        using T = typename NatT<VEC>::type;
+        const T v = __builtin_nontemporal_load(reinterpret_cast<const T *>(p));
+        __builtin_memcpy(x, &v, sizeof(T));
+    }
 }
 template <int VEC>
 __device__ __forceinline__ void vstore_nt(float *__restrict__ p, const float (&x)[VEC]) {
-    using T = typename NatT<VEC>::type;
-    T v;
-    __builtin_memcpy(&v, x, sizeof(T));
-    __builtin_nontemporal_store(v, reinterpret_cast<T *>(p));
+    if constexpr (VEC == 8) {
+        vstore_nt<4>(p, *reinterpret_cast<const float(*)[4]>(&x[0]));
+        vstore_nt<4>(p + 4, *reinterpret_cast<const float(*)[4]>(&x[4]));
+    } else {
+        using T = typename NatT<VEC>::type;
+        T v;
+        __builtin_memcpy(&v, x, sizeof(T));
+        __builtin_nontemporal_store(v, reinterpret_cast<T *>(p));
+    }
 }
+
+// ---- bf16 rows: one load of up to 8 bf16 (16 bytes) widened exactly to f32, and the rounding store ----
+template <int VEC> struct BfRaw;
+template <> struct BfRaw<1> { using type = uint16_t; };
+template <> struct BfRaw<2> { using type = uint32_t; };
+template <> struct BfRaw<4> { using type = uint2; };
+template <> struct BfRaw<8> { using type = uint4; };
+
+// VEC bf16 values (2 * VEC bytes, one load) widened to f32: exact, a bf16 is the upper half of an f32
+template <int VEC>
+__device__ __forceinline__ void bload(float (&x)[VEC], const uint16_t *__restrict__ p) {
+    if constexpr (VEC == 1) {
+        x[0] = __uint_as_float((uint32_t)*p << 16);
+    } else {
+        using T = typename BfRaw<VEC>::type;
+        const T v = *reinterpret_cast<const T *>(p);
+        uint32_t w[VEC / 2];
+        __builtin_memcpy(w, &v, sizeof(T));
+#pragma unroll
+        for (int i = 0; i < VEC / 2; ++i) {
+            x[2 * i] = __uint_as_float(w[i] << 16);
+            x[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u);
+        }
+    }
+}
+
+__device__ __forceinline__ uint16_t to_bf16(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }   // RNE, NaN-preserving
+
+template <int VEC>
+__device__ __forceinline__ void bstore(uint16_t *__restrict__ p, const float (&x)[VEC]) {
+    uint16_t h[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) h[v] = to_bf16(x[v]);
+    using T = typename BfRaw<VEC>::type;
+    T t;
+    __builtin_memcpy(&t, h, sizeof(T));
+    *reinterpret_cast<T *>(p) = t;
+}
+
+inline bool aligned(const void *p, size_t a) { return p == nullptr || ((uintptr_t)p % a) == 0; }
+
+// widest per-lane vector every row start allows (the policies' vec()): up to max_vec values per lane, X / out / out2 holding
+// elements of x_size / out_size / out2_size bytes, H0 f32; an access is at most 16 bytes
+[[maybe_unused]] int pick_vec(const SpmmArgs &p, int max_vec, const void *X, size_t x_size, const void *out, size_t out_size, const void *out2,
+             size_t out2_size) {
+    for (int vec = max_vec; vec > 1; vec >>= 1) {
+        if (p.C % vec == 0 && p.ldx % vec == 0 && p.ldo % vec == 0 && (p.H0 == nullptr || p.ldh0 % vec == 0) &&
+            (out2 == nullptr || p.ldo2 % vec == 0) && aligned(X, std::min<size_t>(x_size * vec, 16)) &&
+            aligned(out, std::min<size_t>(out_size * vec, 16)) && aligned(p.H0, std::min<size_t>(4 * vec, 16)) &&
+            aligned(out2, std::min<size_t>(out2_size * vec, 16)))
+            return vec;
+    }
+    return 1;
+}
+
+// ---- how a launch stores its feature rows: the policy every dispatch class is templated on -------------------------------------
+// Args = the argument struct of its kernels; MAX_VEC = the widest per-lane vector (16 bytes of a gathered row); X / load = the
+// gathered operand and VEC of its columns as float[VEC]; store / store2 = VEC finished columns of the main and of the second result
+// (`at` = element offset of the row, c = first column); diag / out_rows / out_scale / has_out2 = the optional pieces of the epilogue,
+// runtime-null pointers where an entry point of that storage can set them and a constant null where none can; EXPERIMENTS = the
+// kernels carry the A/B switches of the tuning build (SpmmArgs::tune, the PIPE / U variants), which exist for f32 rows only.
+// BF16 / NAMES_LONG only pick the reported name (kernel_name).
+struct F32Rows {
+    using Args = SpmmArgs;
+    using Elem = float;
+    static constexpr int MAX_VEC = 4;
+    static constexpr bool EXPERIMENTS = true;
+    static constexpr int BF16 = 0;
+    static constexpr bool NAMES_LONG = false;    // the reported name does not say whether hub rows went through the chunk kernels
+    __device__ static const float *X(const Args &p) { return p.X; }
+    template <int VEC>
+    __device__ static void load(float (&x)[VEC], const float *__restrict__ q) { vload<VEC>(x, q); }
+    __device__ static const float *diag(const Args &p) { return p.diag; }
+    __device__ static const int32_t *out_rows(const Args &p) { return p.out_rows; }
+    __device__ static bool has_out2(const Args &p) { return p.out2 != nullptr; }
+    __device__ static const float *out_scale(const Args &p) { return p.out_scale; }
+    template <int VEC>
+    __device__ static void store(const Args &p, int64_t at, int c, const float (&o)[VEC], bool nt) {
+        if (nt) vstore_nt<VEC>(p.out + at + c, o);
+        else vstore<VEC>(p.out + at + c, o);
+    }
+    template <int VEC>
+    __device__ static void store2(const Args &p, int64_t at, int c, const float (&o)[VEC]) { vstore<VEC>(p.out2 + at + c, o); }
+    // (the second result's row starts are not looked at: every caller so far keeps it laid out like the first)
+    static int vec(const Args &p) { return pick_vec(p, MAX_VEC, p.X, 4, p.out, 4, nullptr, 0); }
+};
+
+struct BfArgs : SpmmArgs {     // SpmmArgs::X / ::out / ::out2 stay null: the typed buffers are here
+    const uint16_t *Xb;        // bf16 [rows, ldx]: the gathered operand
+    void *outv;                // f32 or bf16 [n_rows, ldo]
+    int out_bf16;
+    uint16_t *out2b;           // bf16 [n_rows, ldo2] or null (gnx_spmm_dropped_back_bf16: the operand of the next call)
+};
+
+// X is bf16, widened exactly as it arrives; sums, H0, the partial slab and the epilogue stay f32; a row that leaves as bf16 is
+// rounded once (round to nearest even, NaN stays NaN: the plain cast, v_cvt_pk_bf16_f32).  TRAIN says which entry points launch:
+// the training ones set the second result and the next iteration's scale and never a diagonal or a row map, the eval ones the
+// reverse.  What a side cannot set is compiled out of its kernels: as runtime tests these pointers cost the eval group kernels 6
+// VGPRs (a wave per SIMD at 8 values per lane on 16/32-lane groups) and the training kernels up to 22 SGPRs (profiles/NOTES.md).
+template <bool TRAIN>
+struct Bf16RowsT {
+    using Args = BfArgs;
+    using Elem = uint16_t;
+    static constexpr int MAX_VEC = 8;
+    static constexpr bool EXPERIMENTS = false;
+    static constexpr int BF16 = 1;
+    static constexpr bool NAMES_LONG = true;
+    __device__ static const uint16_t *X(const Args &p) { return p.Xb; }
+    template <int VEC>
+    __device__ static void load(float (&x)[VEC], const uint16_t *__restrict__ q) { bload<VEC>(x, q); }
+    __device__ static const float *diag(const Args &p) { return TRAIN ? nullptr : p.diag; }
+    __device__ static const int32_t *out_rows(const Args &p) { return TRAIN ? nullptr : p.out_rows; }
+    __device__ static bool has_out2(const Args &p) { return TRAIN && p.out2b != nullptr; }
+    __device__ static const float *out_scale(const Args &p) { return TRAIN ? p.out_scale : nullptr; }
+    template <int VEC>
+    __device__ static void store(const Args &p, int64_t at, int c, const float (&o)[VEC], bool) {
+        if (p.out_bf16) bstore<VEC>(static_cast<uint16_t *>(p.outv) + at + c, o);
+        else vstore<VEC>(static_cast<float *>(p.outv) + at + c, o);
+    }
+    template <int VEC>
+    __device__ static void store2(const Args &p, int64_t at, int c, const float (&o)[VEC]) { bstore<VEC>(p.out2b + at + c, o); }
+    static int vec(const Args &p) { return pick_vec(p, MAX_VEC, p.Xb, 2, p.outv, p.out_bf16 ? 2 : 4, p.out2b, 2); }
+};
 
 __device__ __forceinline__ int readlane_i(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
 __device__ __forceinline__ float readlane_f(float v, int lane) {
@@ -61,9 +208,9 @@ __device__ __forceinline__ float readlane_f(float v, int lane) {
 // Sum of w_e * X[col_e, c .. c+VEC) over entries [beg, end) of one row; the whole wave works
 // on the same entries (beg/end wave-uniform), lane `lane` owns columns c .. c+VEC.  ENTRIES (with FUSE): the handle holds duplicate
 // entries and the weight of a slot is its kept sum (dropped_weight_entries).
-template <int VEC, int U, bool FUSE = false, bool ENTRIES = false>
+template <typename R, int VEC, int U, bool FUSE = false, bool ENTRIES = false>
 __device__ __forceinline__ void wave_accumulate(const int32_t *__restrict__ colidx, const float *__restrict__ vals,
-                                                const float *__restrict__ X, int64_t ldx, int64_t beg, int64_t end,
+                                                const typename R::Elem *__restrict__ X, int64_t ldx, int64_t beg, int64_t end,
                                                 int c, int lane, float (&acc)[VEC], bool nt_index = false,
                                                 const DropFuse *fuse = nullptr, int64_t row = 0) {
     for (int64_t base = beg; base < end; base += 64) {
@@ -94,7 +241,7 @@ __device__ __forceinline__ void wave_accumulate(const int32_t *__restrict__ coli
                     if (keep) keep &= keep - 1;
                     if (idx[u] >= 0) {
                         const int j = readlane_i(mycol, idx[u]);
-                        vload<VEC>(x[u], X + (int64_t)j * ldx + c);
+                        R::template load<VEC>(x[u], X + (int64_t)j * ldx + c);
                     }
                 }
 #pragma unroll
@@ -113,7 +260,7 @@ __device__ __forceinline__ void wave_accumulate(const int32_t *__restrict__ coli
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int j = readlane_i(mycol, i + u);
-                vload<VEC>(x[u], X + (int64_t)j * ldx + c);
+                R::template load<VEC>(x[u], X + (int64_t)j * ldx + c);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -128,7 +275,7 @@ __device__ __forceinline__ void wave_accumulate(const int32_t *__restrict__ coli
             for (int u = 0; u < U - 1; ++u) {
                 if (i + u < n) {
                     const int j = readlane_i(mycol, i + u);
-                    vload<VEC>(x[u], X + (int64_t)j * ldx + c);
+                    R::template load<VEC>(x[u], X + (int64_t)j * ldx + c);
                 }
             }
 #pragma unroll
@@ -144,26 +291,28 @@ __device__ __forceinline__ void wave_accumulate(const int32_t *__restrict__ coli
 }
 
 // filter.py:20-22: out = act(acc*beta + h0*alpha), with the add_eye diagonal folded in first.
-template <int VEC>
-__device__ __forceinline__ void epilogue_store(const SpmmArgs &p, int64_t row, int c, bool active, float (&acc)[VEC],
+// (every optional piece hangs on a wave-uniform null test of the policy's pointer: diag, the second result, the row map, the next
+// iteration's scale)
+template <typename R, int VEC>
+__device__ __forceinline__ void epilogue_store(const typename R::Args &p, int64_t row, int c, bool active, float (&acc)[VEC],
                                                bool nt = false) {
     if (!active) return;
-    if (p.diag) {
-        const float d = p.diag[row];
+    if (R::diag(p)) {
+        const float d = R::diag(p)[row];
         float xr[VEC];
-        vload<VEC>(xr, p.X + row * p.ldx + c);
+        R::template load<VEC>(xr, R::X(p) + row * p.ldx + c);
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[v] = fmaf(d, xr[v], acc[v]);
     }
-    if (p.out2) {                                  // second result of the same sums (see SpmmArgs::out2)
+    if (R::has_out2(p)) {                          // second result of the same sums (see SpmmArgs::out2)
         const float f2 = p.out2_scale ? p.out2_scale[row] : 1.f;
         float o2[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) o2[v] = (acc[v] * p.beta2) * f2;
-        vstore<VEC>(p.out2 + row * p.ldo2 + c, o2);
+        R::template store2<VEC>(p, row * p.ldo2, c, o2);
     }
     float o[VEC];
-    const int64_t orow = p.out_rows ? (int64_t)p.out_rows[row] : row;
+    const int64_t orow = R::out_rows(p) ? (int64_t)R::out_rows(p)[row] : row;
     if (p.H0) {
         const int64_t hrow = p.map_h0 ? orow : row;   // gnx_spmm_rows: H0 is indexed like the output
         float h0[VEC];
@@ -179,13 +328,12 @@ __device__ __forceinline__ void epilogue_store(const SpmmArgs &p, int64_t row, i
 #pragma unroll
         for (int v = 0; v < VEC; ++v) o[v] = fmaxf(o[v], 0.f);
     }
-    if (p.out_scale) {
-        const float os = p.out_scale[row];
+    if (R::out_scale(p)) {
+        const float os = R::out_scale(p)[row];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) o[v] *= os;
     }
-    if (nt) vstore_nt<VEC>(p.out + orow * p.ldo + c, o);
-    else vstore<VEC>(p.out + orow * p.ldo + c, o);
+    R::template store<VEC>(p, orow * p.ldo, c, o, nt);
 }
 
 // Which block of row slots this workgroup takes.  Default: its own index.  With a locality order (SpmmArgs::xcd_rows > 0) the index
@@ -204,9 +352,41 @@ __device__ __forceinline__ int64_t xcd_block(const SpmmArgs &p) {
     return ((int64_t)(i / ch) * 8 + x) * ch + i % ch;
 }
 
+// Row slot (below p.n_rows) -> (row, beg, end) of a row kernel.  WAVE (one wave per row, wave-uniform slot): the rows in ascending
+// order (their H0 / out rows stream), or the ascending list of the rows that have entries; `degree_order` is the f32 eval kernel's
+// experiment.  Otherwise (G lanes per row): degree-binned slots, so that the rows of one wave have similar lengths, with slot_beg /
+// slot_cnt read in slot order (coalesced, independent of the row_order load).
+// The kernel itself tests slot < p.n_rows before the call and leaves afterwards on a long row and, under GNX_ACT_SKIP_EMPTY, on a row
+// without entries.  Those three exits are not in here on purpose: with them inside (a bool result and reference outputs) the
+// compiler merges the exit branches and moves kernarg loads, and the f32 kernels no longer match the ones measured so far.
+struct RowSpan { int64_t row, beg, end; };
+template <bool WAVE>
+__device__ __forceinline__ RowSpan slot_row(const SpmmArgs &p, int64_t slot, bool degree_order = false) {
+    if (WAVE) {
+        const int64_t row = p.row_list ? (int64_t)__builtin_amdgcn_readfirstlane(p.row_list[slot])
+                                       : (degree_order ? (int64_t)__builtin_amdgcn_readfirstlane(p.row_order[slot]) : slot);
+        return {row, p.rowptr[row], p.rowptr[row + 1]};
+    }
+    const int64_t row = p.row_order ? (int64_t)p.row_order[slot] : slot;
+    if (p.slot_beg) { const int64_t beg = p.slot_beg[slot]; return {row, beg, beg + p.slot_cnt[slot]}; }
+    return {row, p.rowptr[row], p.rowptr[row + 1]};
+}
+
+// Chunk slot (below p.n_chunks) -> (chunk, row, beg, end) of a long-row kernel: chunks in column-window order (Csr::chunk_order),
+// chunk k of a long row = its entries [k * long_chunk, (k + 1) * long_chunk).
+struct ChunkSpan { int64_t chunk, row, beg, end; };
+__device__ __forceinline__ ChunkSpan slot_chunk(const SpmmArgs &p, int64_t cslot) {
+    const int64_t chunk = p.chunk_order ? (int64_t)p.chunk_order[cslot] : cslot;
+    const int32_t li = p.chunk_long[chunk];
+    const int64_t row = p.long_rows[li];
+    const int64_t beg = p.rowptr[row] + (chunk - p.long_chunk_ptr[li]) * p.long_chunk;
+    const int64_t rend = p.rowptr[row + 1];
+    return {chunk, row, beg, beg + p.long_chunk < rend ? beg + p.long_chunk : rend};
+}
+
 // ---- long rows, second pass: the chunks' partial sums added in chunk order + the epilogue (shared by the eval and training paths) ----
-template <int VEC>
-__global__ __launch_bounds__(256) void k_spmm_long_reduce(const SpmmArgs p) {
+template <typename R, int VEC>
+__global__ __launch_bounds__(256) void k_spmm_long_reduce(const typename R::Args p) {
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t li = (int64_t)blockIdx.x * 4 + wib;
@@ -227,32 +407,17 @@ __global__ __launch_bounds__(256) void k_spmm_long_reduce(const SpmmArgs p) {
                 for (int v = 0; v < VEC; ++v) acc[v] += x[v];
             }
         }
-        epilogue_store<VEC>(p, row, c, active, acc);
+        epilogue_store<R, VEC>(p, row, c, active, acc);
     }
 }
 
 inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
-
-inline bool aligned(const void *p, size_t a) { return p == nullptr || ((uintptr_t)p % a) == 0; }
-
-// widest vector width every row start allows
-[[maybe_unused]] int pick_vec(const SpmmArgs &p) {
-    for (int vec = 4; vec > 1; vec >>= 1) {
-        const size_t a = vec * sizeof(float);
-        if (p.C % vec == 0 && p.ldx % vec == 0 && p.ldo % vec == 0 && (p.H0 == nullptr || p.ldh0 % vec == 0) &&
-            aligned(p.X, a) && aligned(p.out, a) && aligned(p.H0, a))
-            return vec;
-    }
-    return 1;
-}
 
 #define GNX_LAUNCH(kern, grid, ...) hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, __VA_ARGS__)
 
 // One launch holds at most 2^32 work-items (the dispatch packet's grid size is 32 bits).  A wave per row reaches that at 67M rows,
 // 32 lanes per row at 134M -- sizes a 288 GB card holds -- so the row kernels are dealt in pieces of at most 2^31 work-items
 // (SpmmArgs::slot0 = first row slot of the piece; one piece for everything smaller).
-// (one function for every argument struct -- SpmmArgs and the bf16 translation units' extensions of it -- so the piece size and the
-// padding of the XCD block map exist once)
 template <typename Args, typename Kern>
 void launch_row_pieces(Kern kern, const Args &p, int rows_per_block, int threads, hipStream_t s) {
     const int64_t per_launch = (((int64_t)1 << 31) / threads) * rows_per_block;
@@ -273,14 +438,101 @@ void launch_row_pieces(Kern kern, const Args &p, int rows_per_block, int threads
 }
 #define GNX_ROW_PIECES(kern, rows_per_block, threads) launch_row_pieces(kern, p, rows_per_block, threads, s)
 
-[[maybe_unused]] int check_common(const char *fn, gnx_graph *g, const float *X, int64_t ldx, int64_t C, const float *H0, int64_t ldh0,
-                 float *out, int64_t ldo) {
-    GNX_CHECK_ARG(g != nullptr, "%s: NULL handle", fn);
+// A structure's arrays and long-row plan into the launch arguments, GNX_ACT_SKIP_EMPTY moved from p.act into p.skip_empty, and the
+// partial slab of its long rows (grown outside a capture only: GNX_ERR_UNSUPPORTED naming gnx_graph_reserve otherwise).
+[[maybe_unused]] int bind_csr(gnx_graph *g, const Csr &m, SpmmArgs &p, hipStream_t s) {
+    p.rowptr = m.rowptr; p.colidx = m.colidx; p.n_rows = m.n_rows; p.n_nonempty = m.n_nonempty; p.nonempty_rows = m.nonempty_rows; p.row_list = nullptr;
+    p.slot_beg = m.slot_beg; p.slot_cnt = m.slot_cnt;
+    p.long_rows = m.long_rows; p.long_chunk_ptr = m.long_chunk_ptr; p.chunk_long = m.chunk_long;
+    p.row_order = m.row_order;
+    p.xcd_rows = m.order_window;
+    p.chunk_order = m.chunk_order;
+    p.tune = 0;
+    p.n_long = m.n_long; p.n_chunks = m.n_chunks; p.long_row = m.long_row; p.long_chunk = m.long_chunk;
+    p.partial = nullptr;
+    p.skip_empty = (p.act & GNX_ACT_SKIP_EMPTY) != 0 && p.diag == nullptr;
+    p.act &= ~GNX_ACT_SKIP_EMPTY;
+    if (m.n_rows > 0 && m.n_long > 0) {
+        int rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)p.C * sizeof(float), s);
+        if (rc != GNX_OK) return rc;
+        p.partial = g->partial;
+    }
+    return GNX_OK;
+}
+
+// GNX_ACT_SKIP_EMPTY in the row launchers: the sub-wave kernels walk the rows through row_order, whose trailing slots are exactly the
+// rows without entries -- those slots are not launched at all (on the R-MAT workloads 60 % of the rows: no wave, no row-pointer
+// read); the one-wave-per-row kernels keep the rows in ascending order and walk the ascending list of the rows that have entries.
+[[maybe_unused]] void trim_empty_rows(SpmmArgs &p, int lanes) {
+    if (!p.skip_empty || p.n_nonempty >= p.n_rows) return;
+    if (lanes <= 32 && p.row_order != nullptr) p.n_rows = p.n_nonempty;
+    else if (lanes > 32 && p.nonempty_rows != nullptr) { p.row_list = p.nonempty_rows; p.n_rows = p.n_nonempty; }
+}
+
+// ---- dispatch: the per-lane vector and the lanes per row as template arguments, and the names gnx_graph_last_kernel reports ------
+template <int N> using IntC = std::integral_constant<int, N>;
+
+// f(IntC<VEC>) for the width pick_vec chose
+template <typename R, typename F>
+auto with_vec(int vec, F &&f) {
+    if constexpr (R::MAX_VEC == 8) {
+        if (vec == 8) return f(IntC<8>{});
+    }
+    if (vec == 4) return f(IntC<4>{});
+    if (vec == 2) return f(IntC<2>{});
+    return f(IntC<1>{});
+}
+
+enum RowClass { ROWS_NONE, ROWS_WAVE, ROWS_G32, ROWS_G16, ROWS_G8, ROWS_G4 };
+
+// The class ladder below one wave per row: f(IntC<G>) for the G lanes a row of `lanes` per-lane vectors runs on (256 / G rows per
+// block).  Rows of up to 4 lanes run on 8-lane groups as well (the lanes beyond the row's width share the index fetch / the draws)
+// unless G4: in the chunk kernels the group width is also how a chunk's entries are dealt to sub-groups, i.e. the long rows'
+// summation order, which the eval and the training kernels of the same width share bit for bit.
+template <bool G4, typename F>
+RowClass with_group(int lanes, F &&f) {
+    if (lanes > 16) { f(IntC<32>{}); return ROWS_G32; }
+    if (lanes > 8)  { f(IntC<16>{}); return ROWS_G16; }
+    if constexpr (G4) {
+        if (lanes <= 4) { f(IntC<4>{}); return ROWS_G4; }
+    }
+    f(IntC<8>{});
+    return ROWS_G8;
+}
+
+// "spmm_" class ["+long" | "+chunks"] ["_drop" ["_entries"]] ["_bf16"]: every name reported so far, byte for byte, from one scheme.
+// (The table spells out the whole product; most of its combinations -- "spmm_wave+chunks", "spmm_group4_drop" -- cannot be reported.)
+enum NameHubs { HUBS_NONE, HUBS_LONG, HUBS_CHUNKS };      // hub rows: none (or not named), separate chunk launches, chunks in the row launch
+enum NameMode { MODE_EVAL, MODE_DROP, MODE_DROP_ENTRIES };
+#define GNX_NAMES6(mid, tail) {"spmm_none" mid tail, "spmm_wave" mid tail, "spmm_group32" mid tail, "spmm_group16" mid tail, "spmm_group8" mid tail, "spmm_group4" mid tail}
+#define GNX_NAMES3(tail) {GNX_NAMES6("", tail), GNX_NAMES6("+long", tail), GNX_NAMES6("+chunks", tail)}
+#define GNX_NAMES(tail) {GNX_NAMES3(tail), GNX_NAMES3("_drop" tail), GNX_NAMES3("_drop_entries" tail)}
+[[maybe_unused]] const char *const kKernelNames[2][3][3][6] = {GNX_NAMES(""), GNX_NAMES("_bf16")};
+#undef GNX_NAMES
+#undef GNX_NAMES3
+#undef GNX_NAMES6
+
+template <typename R>
+const char *kernel_name(RowClass rows, NameMode mode, NameHubs hubs) {
+    if (hubs == HUBS_LONG && !R::NAMES_LONG) hubs = HUBS_NONE;
+    return kKernelNames[R::BF16][mode][hubs][rows];
+}
+
+// the operand checks every SpMM entry starts with (the bf16 training entries make them BEFORE they look at the handle, so that they
+// can be exercised without a device)
+[[maybe_unused]] int check_operands(const char *fn, const void *X, int64_t ldx, int64_t C, const float *H0, int64_t ldh0, const void *out,
+                                    int64_t ldo) {
     GNX_CHECK_ARG(C >= 1 && C <= (1 << 20), "%s: feature width %lld not in [1, 2^20]", fn, (long long)C);
     GNX_CHECK_ARG(X != nullptr && out != nullptr, "%s: NULL X/out", fn);
     GNX_CHECK_ARG(ldx >= C && ldo >= C && (H0 == nullptr || ldh0 >= C || ldh0 == 0), "%s: leading dimension smaller than C", fn);
-    GNX_CHECK_ARG((const void *)X != (const void *)out, "%s: out must not alias X", fn);
+    GNX_CHECK_ARG(X != out, "%s: out must not alias X", fn);
     return GNX_OK;
+}
+
+[[maybe_unused]] int check_common(const char *fn, gnx_graph *g, const void *X, int64_t ldx, int64_t C, const float *H0, int64_t ldh0,
+                                  const void *out, int64_t ldo) {
+    GNX_CHECK_ARG(g != nullptr, "%s: NULL handle", fn);
+    return check_operands(fn, X, ldx, C, H0, ldh0, out, ldo);
 }
 
 }  // namespace

@@ -1,0 +1,246 @@
+// The training-mode dispatch classes of the SpMM (fused edge dropout), each written once over the row-storage policy R
+// (gnx_spmm_device.h) and instantiated for f32 rows by gnx_spmm_train.hip and for bf16 rows by gnx_spmm_train_bf16.hip, and the
+// launcher layer that picks among them.
+#pragma once
+#include "gnx_spmm_device.h"
+
+namespace {
+
+// ---- training iterations: the dropped + re-normalised values are produced inside the SpMM (gnx_spmm_dropped) ------------
+// Same row / lane mapping as the eval kernels (gnx_spmm_eval.h); what differs is where an entry's weight comes from: p.vals holds the RAW
+// values and every weight is (D[row] * drop(raw)) * D[col] (layered.py:47-50 + gnn.py:41-42), computed ONCE per entry by one
+// lane and handed to the lanes that need it (readlane / shuffles), so the hash costs one evaluation per stored entry.
+// ENTRIES (the _entries instantiations, a handle with duplicate COO entries after gnx_graph_enable_entry_dropout): p.vals holds each
+// slot's uniform value and the lane that owns a slot makes its kept sum (dropped_weight_entries) -- one more hash round per further
+// duplicate; everything else, and the kernels without duplicates, as before.
+template <typename R, int VEC, int U, int WPB, bool ENTRIES = false>
+__global__ __launch_bounds__(64 * WPB) void k_spmm_wave_drop(const typename R::Args p) {
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t slot = p.slot0 + xcd_block(p) * WPB + wib;
+    if (slot >= p.n_rows) return;
+    const auto [row, beg, end] = slot_row<true>(p, slot);
+    if (end - beg > p.long_row) return;
+    if (p.skip_empty && beg == end) return;   // GNX_ACT_SKIP_EMPTY (chained training loops: nobody gathers this row, a later launch writes it)
+    for (int c0 = 0; c0 < p.C; c0 += 64 * VEC) {
+        const int c = c0 + lane * VEC;
+        const bool active = c < p.C;
+        float acc[VEC];
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
+        wave_accumulate<R, VEC, U, true, ENTRIES>(p.colidx, p.vals, R::X(p), p.ldx, beg, end, active ? c : 0, lane, acc, false, &p.fuse, row);
+        epilogue_store<R, VEC>(p, row, c, active, acc);
+    }
+}
+
+// PIPE: the (col, raw value) pair a lane owns in the NEXT round is loaded before this round's kept entries are gathered, so a row
+// of more than G entries pays the index latency once instead of once per round.
+template <typename R, int VEC, int G, int U, bool PIPE, bool ENTRIES = false>
+__global__ __launch_bounds__(256) void k_spmm_group_drop(const typename R::Args p) {
+    constexpr int RPB = 256 / G;
+    const int sub = threadIdx.x % G;
+    const int64_t slot = p.slot0 + xcd_block(p) * RPB + threadIdx.x / G;
+    if (slot >= p.n_rows) return;
+    const auto [row, beg, end] = slot_row<false>(p, slot);
+    if (end - beg > p.long_row) return;
+    if (p.skip_empty && beg == end) return;   // GNX_ACT_SKIP_EMPTY
+    for (int c0 = 0; c0 < p.C; c0 += G * VEC) {
+        const int c = c0 + sub * VEC;
+        const bool active = c < p.C;
+        const typename R::Elem *__restrict__ Xc = R::X(p) + (active ? c : 0);
+        float acc[VEC];
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
+        int ncol = 0;
+        float nraw = 0.f;
+        if (PIPE && beg + sub < end) { ncol = p.colidx[beg + sub]; nraw = p.vals[beg + sub]; }
+        for (int64_t base = beg; base < end; base += G) {          // G entries per round: lane `sub` owns entry base + sub
+            const int n = (int)((end - base) < G ? (end - base) : G);
+            int mycol = 0;
+            float myw = 0.f;
+            if (PIPE) {
+                const int ccol = ncol;
+                const float craw = nraw;
+                if (base + G + sub < end) { ncol = p.colidx[base + G + sub]; nraw = p.vals[base + G + sub]; }
+                if (sub < n) { mycol = ccol; myw = dropped_weight_at<ENTRIES>(p.fuse, craw, base + sub, row, ccol); }
+            } else if (sub < n) {
+                mycol = p.colidx[base + sub];
+                myw = dropped_weight_at<ENTRIES>(p.fuse, p.vals[base + sub], base + sub, row, mycol);
+            }
+            // dropped entries (weight exactly 0) are not gathered: the group walks only the kept entries of its round, in order
+            const uint64_t all = __ballot(myw != 0.f);
+            uint32_t keep = (uint32_t)(all >> ((threadIdx.x & 63) / G * G)) & (G == 32 ? 0xFFFFFFFFu : ((1u << G) - 1u));
+            while (keep) {
+                float x[U][VEC];
+                float w[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (keep) {
+                        const int idx = __builtin_ctz(keep);
+                        keep &= keep - 1;
+                        const int j = __shfl(mycol, idx, G);
+                        w[u] = __shfl(myw, idx, G);
+                        R::template load<VEC>(x[u], Xc + (int64_t)j * p.ldx);
+                    } else {
+                        w[u] = 0.f;
+#pragma unroll
+                        for (int v = 0; v < VEC; ++v) x[u][v] = 0.f;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
+            }
+        }
+        epilogue_store<R, VEC>(p, row, c, active, acc);
+    }
+}
+
+template <typename R, int VEC, int U, bool ENTRIES = false>
+__global__ __launch_bounds__(256) void k_spmm_long_partial_drop(const typename R::Args p) {
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t cslot = (int64_t)blockIdx.x * 4 + wib;
+    if (cslot >= p.n_chunks) return;
+    const auto [chunk, row, beg, end] = slot_chunk(p, cslot);
+    for (int c0 = 0; c0 < p.C; c0 += 64 * VEC) {
+        const int c = c0 + lane * VEC;
+        const bool active = c < p.C;
+        float acc[VEC];
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
+        wave_accumulate<R, VEC, U, true, ENTRIES>(p.colidx, p.vals, R::X(p), p.ldx, beg, end, active ? c : 0, lane, acc, false, &p.fuse, row);
+        if (active) vstore<VEC>(p.partial + chunk * (int64_t)p.C + c, acc);
+    }
+}
+
+// narrow long rows: the wave computes 64 weights per round (one per lane); sub-group s then takes entries s, s + NS, ... of the
+// round, which is the entry -> sub-group dealing of k_spmm_long_partial_group (so the partial sums are bitwise the same)
+template <typename R, int VEC, int G, int U, bool ENTRIES = false>
+__global__ __launch_bounds__(256) void k_spmm_long_partial_group_drop(const typename R::Args p) {
+    constexpr int NS = 64 / G;
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t cslot = (int64_t)blockIdx.x * 4 + wib;
+    if (cslot >= p.n_chunks) return;
+    const auto [chunk, row, beg, end] = slot_chunk(p, cslot);
+    const int sub = lane / G;
+    const int c = (lane % G) * VEC;
+    const bool active = c < p.C;
+    const typename R::Elem *__restrict__ Xc = R::X(p) + (active ? c : 0);
+    float acc[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
+    // the reference kernel walks e = beg + sub + k * NS (k = 0, 1, ...) in batches of U: entry index within the chunk = sub + k NS.
+    // A round of 64 entries covers k = 0 .. 64/NS - 1 = G - 1 for every sub-group.
+    for (int64_t base = beg; base < end; base += 64) {
+        const int n = (int)((end - base) < 64 ? (end - base) : 64);
+        int mycol = 0;
+        float myw = 0.f;
+        if (lane < n) {
+            mycol = p.colidx[base + lane];
+            myw = dropped_weight_at<ENTRIES>(p.fuse, p.vals[base + lane], base + lane, row, mycol);
+        }
+#pragma unroll 1
+        for (int k = 0; k < G; k += U) {
+            float x[U][VEC];
+            float w[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int src = sub + (k + u) * NS;                  // entry of the round this sub-group takes in slot k + u
+                const int j = __shfl(mycol, src);
+                w[u] = __shfl(myw, src);
+                if (k + u < G && src < n && w[u] != 0.f) R::template load<VEC>(x[u], Xc + (int64_t)j * p.ldx);   // dropped: not gathered
+                else {
+                    w[u] = 0.f;
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) x[u][v] = 0.f;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
+        }
+    }
+#pragma unroll
+    for (int off = G; off < 64; off <<= 1)
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc[v] += __shfl_xor(acc[v], off);
+    if (sub == 0 && active) vstore<VEC>(p.partial + chunk * (int64_t)p.C + c, acc);
+}
+
+[[maybe_unused]] constexpr bool DROP_U8 = false, DROP_PIPE = false;     // product defaults of the training row kernels (see launch_rows_drop)
+constexpr int DROP_LONG_U = 4;
+
+// ---- launchers ------------------------------------------------------------------------------------------------------------
+template <typename R, int VEC, bool E>
+RowClass launch_rows_drop(const typename R::Args &p0, hipStream_t s) {
+    typename R::Args p = p0;
+    const int lanes = (p.C + VEC - 1) / VEC;
+    trim_empty_rows(p, lanes);
+    if (p.n_rows == 0) return ROWS_NONE;
+    if (lanes > 32) {
+        if (p.C <= 64 * VEC) GNX_ROW_PIECES((k_spmm_wave_drop<R, VEC, 8, 8, E>), 8, 512);
+        else                 GNX_ROW_PIECES((k_spmm_wave_drop<R, VEC, 8, 4, E>), 4, 256);
+        return ROWS_WAVE;
+    }
+    // A group of G lanes takes G entries per round (lane `sub` draws the weight of entry base + sub), so G is also how many index
+    // loads and draws are in flight per row.  Round 6 (profiles/NOTES.md, config-4 graph, middle iteration): rows of up to 4 lanes
+    // (C <= 16) on 8-lane groups instead of 4-lane ones -- half the lanes then only fetch and draw, their gather repeats a
+    // neighbour's line -- C = 8: 1.94 -> 1.52 ms forward, 2.03 -> 1.61 backward; C = 16: 2.00 -> 1.56 / 2.08 -> 1.63; same bits.
+    // 16 lanes: 1.83 / 1.85 ms, 32 lanes: 2.7 ms (fewer rows per wave than the gathers need in flight).
+    return with_group<false>(lanes, [&](auto G) {
+        if constexpr (R::EXPERIMENTS) {
+            // U gathers in flight per lane and the index prefetch: round-4 A/B on the config-4 graph (tuning build bits 1 << 17 = U 8,
+            // 1 << 19 = PIPE; profiles/NOTES.md)
+#ifdef GNX_TUNING
+            const bool u8 = (p.tune & (1 << 17)) != 0, pipe = (p.tune & (1 << 19)) != 0;
+#else
+            const bool u8 = DROP_U8, pipe = DROP_PIPE;
+#endif
+            if (u8 && pipe)  GNX_ROW_PIECES((k_spmm_group_drop<R, VEC, G(), 8, true, E>), 256 / G(), 256);
+            else if (u8)     GNX_ROW_PIECES((k_spmm_group_drop<R, VEC, G(), 8, false, E>), 256 / G(), 256);
+            else if (pipe)   GNX_ROW_PIECES((k_spmm_group_drop<R, VEC, G(), 4, true, E>), 256 / G(), 256);
+            else             GNX_ROW_PIECES((k_spmm_group_drop<R, VEC, G(), 4, false, E>), 256 / G(), 256);
+        } else {
+            GNX_ROW_PIECES((k_spmm_group_drop<R, VEC, G(), 4, false, E>), 256 / G(), 256);
+        }
+    });
+}
+
+template <typename R, int VEC, bool E>
+void launch_long_drop(const typename R::Args &p, hipStream_t s) {
+    const int lanes = (p.C + VEC - 1) / VEC;
+    if (lanes > 32) GNX_LAUNCH((k_spmm_long_partial_drop<R, VEC, 8, E>), blocks_for(p.n_chunks, 4), p);
+    else with_group<true>(lanes, [&](auto G) {
+        constexpr int U = G() == 4 ? 4 : DROP_LONG_U;
+#ifdef GNX_TUNING
+        if constexpr (R::EXPERIMENTS) {
+            if (p.tune & (1 << 18)) {
+                GNX_LAUNCH((k_spmm_long_partial_group_drop<R, VEC, G(), (G() == 4 ? 4 : 8), E>), blocks_for(p.n_chunks, 4), p);
+                return;
+            }
+        }
+#endif
+        GNX_LAUNCH((k_spmm_long_partial_group_drop<R, VEC, G(), U, E>), blocks_for(p.n_chunks, 4), p);
+    });
+    GNX_LAUNCH((k_spmm_long_reduce<R, VEC>), blocks_for(p.n_long, 4), p);
+}
+
+// one training-mode SpMM over bound arguments (bind_csr), E = the handle holds duplicate entries (p.fuse.mult); the name
+// gnx_graph_last_kernel reports
+template <typename R>
+const char *launch_drop(const typename R::Args &p, int vec, hipStream_t s) {
+    return with_vec<R>(vec, [&](auto V) {
+        const RowClass rows = p.fuse.mult ? launch_rows_drop<R, V(), true>(p, s) : launch_rows_drop<R, V(), false>(p, s);
+        if (p.n_long > 0) {
+            if (p.fuse.mult) launch_long_drop<R, V(), true>(p, s);
+            else launch_long_drop<R, V(), false>(p, s);
+        }
+        return kernel_name<R>(rows, p.fuse.mult ? MODE_DROP_ENTRIES : MODE_DROP, p.n_long > 0 ? HUBS_LONG : HUBS_NONE);
+    });
+}
+
+}  // namespace
