@@ -1,5 +1,7 @@
 // The GCNII layer (gcn.py:7-27,54-74) in one launch on gfx950: SpMM + residual mix + the C x C transform on the matrix cores.
 // Shares the gathers' device code and the long-row path with gnx_spmm.hip (gnx_spmm_device.h, gnx::launch_long_rows).
+// gnx_gcnii_step_bf16 (inference, opt-in): the same kernel over bf16 feature rows (the row-storage policy of gnx_spmm_device.h), hub rows
+// and the other widths through the bf16 kernels of gnx_spmm_bf16.hip in the f32 launch's summation order; rounding points in gnx.h.
 #include "gnx_spmm_device.h"
 
 namespace {
@@ -14,8 +16,11 @@ namespace {
 // 135 KB of the CU's 160 KB of LDS -- but leaves one block of eight waves per CU: measured 19.2 ms against 11.8 ms for SpMM+mix
 // followed by the dense kernel, so wide layers keep the two launches.)  Rows longer than p.long_row are left to the long-row
 // kernels + the dense kernel.
-template <int NT, int U, int WPB>
-__global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const SpmmArgs p, const float *__restrict__ M, int64_t ldm, float *__restrict__ mixed) {
+// Written once over the row-storage policy R (gnx_spmm_device.h): F32Rows gathers float4 pieces of f32 rows, Bf16RowsT 8-byte pieces of
+// bf16 rows (four columns, widened exactly) and stores the finished row as f32 or rounded once to bf16; entry order, summation order,
+// the mix and the transform are the same code, so the bf16 instantiation over bf16-representable rows gives the bits of the f32 one.
+template <typename R, int NT, int U, int WPB>
+__global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args p, const float *__restrict__ M, int64_t ldm, float *__restrict__ mixed) {
     constexpr int C = 16 * NT, G = 4 * NT, RPP = 64 / G, PASSES = 16 / RPP, STRIDE = C + 4;
     __shared__ float Ms[C * STRIDE];
     __shared__ float Ts[WPB][16 * STRIDE];
@@ -43,7 +48,7 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const SpmmArgs p, const
         rows[ps] = row;
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
         if (live[ps]) {
-            const float *__restrict__ Xc = p.X + c;
+            const typename R::Elem *__restrict__ Xc = R::X(p) + c;
             for (int64_t e = beg; e < end; e += U) {
                 float x[U][4];
                 float w[U];
@@ -52,7 +57,7 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const SpmmArgs p, const
                     if (e + u < end) {
                         const int j = p.colidx[e + u];
                         w[u] = p.vals[e + u];
-                        vload<4>(x[u], Xc + (int64_t)j * p.ldx);
+                        R::template load<4>(x[u], Xc + (int64_t)j * p.ldx);
                     } else {
                         w[u] = 0.f;
 #pragma unroll
@@ -102,8 +107,38 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const SpmmArgs p, const
         const int rr = ps * RPP + lane / G;
         float o[4];
         vload<4>(o, T + rr * STRIDE + c);
-        vstore<4>(p.out + rows[ps] * p.ldo + c, o);
+        R::template store<4>(p, rows[ps] * p.ldo, c, o, false);
     }
+}
+
+using Bf16Rows = Bf16RowsT<false>;
+
+// dst[r, :] = bf(src[r, :]) for the rows listed (null: rows 0 .. n), both [., C] contiguous; VEC = 4: 16-byte loads, 8-byte stores
+template <int VEC>
+__global__ __launch_bounds__(256) void k_round_rows(const float *__restrict__ src, const int32_t *__restrict__ rows, int64_t n, int64_t C,
+                                                   uint16_t *__restrict__ dst) {
+    const int64_t per_row = C / VEC, total = n * per_row, stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const int64_t i = e / per_row, r = rows ? (int64_t)rows[i] : i, at = r * C + (e % per_row) * VEC;
+        float x[VEC];
+        vload<VEC>(x, src + at);
+        bstore<VEC>(dst + at, x);
+    }
+}
+
+void round_rows(const float *src, const int32_t *rows, int64_t n, int64_t C, uint16_t *dst, hipStream_t s) {
+    if (n == 0) return;
+    const bool v4 = C % 4 == 0 && aligned(src, 16) && aligned(dst, 8);
+    const unsigned grid = (unsigned)std::min<int64_t>(blocks_for(n * (v4 ? C / 4 : C), 256), 1 << 20);
+    if (v4) hipLaunchKernelGGL(k_round_rows<4>, dim3(grid), dim3(256), 0, s, src, rows, n, C, dst);
+    else    hipLaunchKernelGGL(k_round_rows<1>, dim3(grid), dim3(256), 0, s, src, rows, n, C, dst);
+}
+
+// the structure and the long-row plan of a fused launch (its short rows need nothing else of bind_csr)
+void bind_fused(const Csr &m, SpmmArgs &p) {
+    p.rowptr = m.rowptr; p.colidx = m.colidx; p.n_rows = m.n_rows; p.n_nonempty = m.n_nonempty; p.row_order = m.row_order;
+    p.long_rows = m.long_rows; p.long_chunk_ptr = m.long_chunk_ptr; p.chunk_long = m.chunk_long; p.chunk_order = m.chunk_order;
+    p.n_long = m.n_long; p.n_chunks = m.n_chunks; p.long_row = m.long_row; p.long_chunk = m.long_chunk;
 }
 
 }  // namespace
@@ -135,13 +170,11 @@ int gnx_gcnii_step(gnx_graph_t g, const float *d_vals, const float *d_H, const f
     SpmmArgs p{};
     p.vals = d_vals ? d_vals : g->raw_vals;
     p.X = d_H; p.ldx = C; p.H0 = d_H0; p.ldh0 = C; p.beta = beta; p.alpha = a; p.act = act; p.out = d_out; p.ldo = C; p.C = (int)C;
-    p.rowptr = m.rowptr; p.colidx = m.colidx; p.n_rows = m.n_rows; p.n_nonempty = m.n_nonempty; p.row_order = m.row_order;
-    p.long_rows = m.long_rows; p.long_chunk_ptr = m.long_chunk_ptr; p.chunk_long = m.chunk_long; p.chunk_order = m.chunk_order;
-    p.n_long = m.n_long; p.n_chunks = m.n_chunks; p.long_row = m.long_row; p.long_chunk = m.long_chunk;
+    bind_fused(m, p);
     const unsigned grid = blocks_for(blocks_for(m.n_rows, 16), 8);
-    if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii<4, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
-    else if (C == 32) hipLaunchKernelGGL((k_spmm_gcnii<2, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
-    else              hipLaunchKernelGGL((k_spmm_gcnii<1, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
+    if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii<F32Rows, 4, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
+    else if (C == 32) hipLaunchKernelGGL((k_spmm_gcnii<F32Rows, 2, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
+    else              hipLaunchKernelGGL((k_spmm_gcnii<F32Rows, 1, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
     g->last_kernel = "spmm_gcnii_mfma";
     if (m.n_long > 0) {   // hub rows: chunked partial sums -> mixed rows (into d_mixed when kept, else in place) -> transform of those rows alone
         rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)C * sizeof(float), s);
@@ -153,6 +186,74 @@ int gnx_gcnii_step(gnx_graph_t g, const float *d_vals, const float *d_H, const f
         launch_long_rows(p, s);
         rc = dense_rows(rows_at, C, m.n_long, C, d_M, ldm, C, nullptr, act, m.long_rows, m.long_rows, d_out, C, s);
         if (rc != GNX_OK) return rc;
+    }
+    GNX_HIP(hipGetLastError());
+    return GNX_OK;
+}
+
+int gnx_gcnii_step_bf16(gnx_graph_t g, const float *d_vals, const uint16_t *d_H, const float *d_H0, float a, int64_t C, const float *d_M,
+                        int64_t ldm, int act, void *d_out, int out_bf16, float *d_work, void *stream) {
+    int rc = check_common("gnx_gcnii_step_bf16", g, d_H, C, C, d_H0, C, d_out, C);
+    if (rc != GNX_OK) return rc;
+    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU, "gnx_gcnii_step_bf16: invalid activation %d", act);
+    GNX_CHECK_ARG(out_bf16 == 0 || out_bf16 == 1, "gnx_gcnii_step_bf16: out_bf16 must be 0 or 1");
+    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "gnx_gcnii_step_bf16: needs a square graph");
+    GNX_CHECK_ARG(d_H0 != nullptr && d_M != nullptr && ldm >= C, "gnx_gcnii_step_bf16: NULL H0 / M or ldm < C");
+    GNX_CHECK_ARG((const void *)d_out != (const void *)d_H0 && (const void *)d_out != (const void *)d_M, "gnx_gcnii_step_bf16: out must not alias H0 / M");
+    GNX_CHECK_ARG(d_work == nullptr || ((const void *)d_work != (const void *)d_out && (const void *)d_work != (const void *)d_H && d_work != d_H0 &&
+                                        d_work != d_M && d_work != d_vals),
+                  "gnx_gcnii_step_bf16: d_work must be a buffer of its own");
+    hipStream_t s = (hipStream_t)stream;
+    const Csr &m = g->a;
+    const float beta = (float)(1.0 - (double)a);
+    const bool fusable = (C == 16 || C == 32 || C == 64) && aligned(d_H, 8) && aligned(d_H0, 16) && aligned(d_out, out_bf16 ? 8 : 16) &&
+                         aligned(d_work, 16);
+    GNX_CHECK_ARG(d_work != nullptr || (fusable && m.n_long == 0),
+                  "gnx_gcnii_step_bf16: needs d_work [n, C] f32 (%s)", fusable ? "the graph has hub rows: their mixed rows go through memory"
+                                                                               : "this width / alignment runs the SpMM and the transform as two launches");
+    SpmmArgs p{};
+    p.vals = d_vals ? d_vals : g->raw_vals;
+    p.ldx = C; p.H0 = d_H0; p.ldh0 = C; p.beta = beta; p.alpha = a; p.ldo = C; p.C = (int)C;
+    if (!fusable) {   // other widths: the SpMM + mix over bf16 rows into d_work (f32), the transform on the matrix cores, the rounding last
+        p.act = GNX_ACT_NONE;
+        rc = launch_spmm_bf16_f32_order(g, m, p, d_H, d_work, s);
+        if (rc != GNX_OK) return rc;
+        g->last_kernel = "spmm+dense_mfma_bf16";
+        if (!out_bf16) return dense_rows(d_work, C, m.n_rows, C, d_M, ldm, C, nullptr, act, nullptr, nullptr, (float *)d_out, C, s);
+        // a bf16 result: the transform runs in place (every wave of the dense kernels reads whole rows of its own tile before it stores
+        // them -- what the hub rows of gnx_gcnii_step rely on -- as long as the result is ONE column panel), then the rows are rounded
+        if (C > 256) {
+            set_error("gnx_gcnii_step_bf16: a bf16 result needs C <= 256 (wider: out_bf16 = 0, then gnx_cast_bf16)");
+            return GNX_ERR_UNSUPPORTED;
+        }
+        rc = dense_rows(d_work, C, m.n_rows, C, d_M, ldm, C, nullptr, act, nullptr, nullptr, d_work, C, s);
+        if (rc != GNX_OK) return rc;
+        round_rows(d_work, nullptr, m.n_rows, C, (uint16_t *)d_out, s);
+        GNX_HIP(hipGetLastError());
+        return GNX_OK;
+    }
+    if (m.n_rows == 0) return GNX_OK;
+    bind_fused(m, p);
+    if (m.n_long > 0) {   // (before the first launch: under capture a slab that would have to grow refuses the whole call)
+        rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)C * sizeof(float), s);
+        if (rc != GNX_OK) return rc;
+    }
+    BfArgs q{};
+    static_cast<SpmmArgs &>(q) = p;
+    q.act = act; q.Xb = d_H; q.outv = d_out; q.out_bf16 = out_bf16;
+    const unsigned grid = blocks_for(blocks_for(m.n_rows, 16), 8);
+    if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii<Bf16Rows, 4, 4, 8>), dim3(grid), dim3(512), 0, s, q, d_M, ldm, (float *)nullptr);
+    else if (C == 32) hipLaunchKernelGGL((k_spmm_gcnii<Bf16Rows, 2, 4, 8>), dim3(grid), dim3(512), 0, s, q, d_M, ldm, (float *)nullptr);
+    else              hipLaunchKernelGGL((k_spmm_gcnii<Bf16Rows, 1, 4, 8>), dim3(grid), dim3(512), 0, s, q, d_M, ldm, (float *)nullptr);
+    g->last_kernel = "spmm_gcnii_mfma_bf16";
+    if (m.n_long > 0) {   // hub rows: chunked partial sums over the bf16 rows -> f32 mixed rows in d_work -> transform of those rows alone
+        p.partial = g->partial;
+        p.act = GNX_ACT_NONE;
+        launch_long_rows_bf16(p, d_H, d_work, s);
+        float *rows_to = out_bf16 ? d_work : (float *)d_out;      // (bf16: transformed in place, then rounded into d_out)
+        rc = dense_rows(d_work, C, m.n_long, C, d_M, ldm, C, nullptr, act, m.long_rows, m.long_rows, rows_to, C, s);
+        if (rc != GNX_OK) return rc;
+        if (out_bf16) round_rows(d_work, m.long_rows, m.n_long, C, (uint16_t *)d_out, s);
     }
     GNX_HIP(hipGetLastError());
     return GNX_OK;

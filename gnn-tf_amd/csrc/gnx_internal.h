@@ -306,6 +306,11 @@ struct PerDeviceOnce {
 
 int launch_spmm(gnx_graph *g, const Csr &m, SpmmArgs &p, hipStream_t s);                      // gnx_spmm.hip
 void launch_long_rows(const SpmmArgs &p, hipStream_t s);                                       // gnx_spmm.hip: long rows only
+// gnx_spmm_bf16.hip, for gnx_gcnii_step_bf16: p with its rows gathered from bf16 Xb (p.X unused) and finished as f32 into `out` (p.out
+// unused), per row in the summation order of the f32 launch over the same arguments: hub chunks are dealt to the lane groups of at most
+// 4 columns per lane, as F32Rows deals them (short rows add their entries in ascending order at any lane width).
+int launch_spmm_bf16_f32_order(gnx_graph *g, const Csr &m, const SpmmArgs &p, const uint16_t *Xb, float *out, hipStream_t s);
+void launch_long_rows_bf16(const SpmmArgs &p, const uint16_t *Xb, float *out, hipStream_t s);   // launch_long_rows, likewise
 const char *launch_spmm_dropped(const SpmmArgs &p, int vec, hipStream_t s);              // gnx_spmm_train.hip
 // gnx_spmm_train.hip, shared with gnx_spmm_train_bf16.hip: a handle with duplicate entries needs gnx_graph_enable_entry_dropout
 // (GNX_ERR_UNSUPPORTED otherwise); the per-slot values and entry tables a fused launch over the handle reads

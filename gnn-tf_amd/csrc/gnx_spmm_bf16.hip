@@ -53,7 +53,45 @@ int cast_bf16(const float *src, int64_t n_rows, int64_t C, int64_t lds, uint16_t
     return GNX_OK;
 }
 
+// the arguments of an f32 launch with its rows gathered from bf16 Xb and finished as f32 into `out`
+BfArgs bf_rows_of(const SpmmArgs &p, const uint16_t *Xb, float *out) {
+    BfArgs q{};
+    static_cast<SpmmArgs &>(q) = p;
+    q.X = nullptr; q.out = nullptr;
+    q.Xb = Xb; q.outv = out; q.out_bf16 = 0;
+    return q;
+}
+
 }  // namespace
+
+namespace gnx {
+
+// launch_eval<Bf16Rows> with the hub chunks on the lane groups of the f32 launch (at most 4 columns per lane): the group width deals a
+// chunk's entries to sub-groups, i.e. it IS the long rows' summation order.  The short rows keep 8 columns per lane wherever they have a
+// launch of their own (their entries are added in ascending order whatever the lane width).
+int launch_spmm_bf16_f32_order(gnx_graph *g, const Csr &m, const SpmmArgs &p, const uint16_t *Xb, float *out, hipStream_t s) {
+    BfArgs q = bf_rows_of(p, Xb, out);
+    int rc = bind_csr(g, m, q, s);
+    if (rc != GNX_OK) return rc;
+    if (m.n_rows == 0) return GNX_OK;
+    const int vec = Bf16Rows::vec(q);
+    g->last_kernel = with_vec<F32Rows>(std::min(vec, 4), [&](auto V4) {
+        RowClass rows = launch_rows_and_chunks<Bf16Rows, V4()>(q, s);
+        if (rows != ROWS_NONE) return kernel_name<Bf16Rows>(rows, MODE_EVAL, HUBS_CHUNKS);
+        rows = with_vec<Bf16Rows>(vec, [&](auto V) { return launch_rows<Bf16Rows, V()>(q, s); });
+        if (q.n_long > 0) launch_long<Bf16Rows, V4()>(q, s);
+        return kernel_name<Bf16Rows>(rows, MODE_EVAL, q.n_long > 0 ? HUBS_LONG : HUBS_NONE);
+    });
+    GNX_HIP(hipGetLastError());
+    return GNX_OK;
+}
+
+void launch_long_rows_bf16(const SpmmArgs &p, const uint16_t *Xb, float *out, hipStream_t s) {
+    const BfArgs q = bf_rows_of(p, Xb, out);
+    with_vec<F32Rows>(std::min(Bf16Rows::vec(q), 4), [&](auto V) { launch_long<Bf16Rows, V()>(q, s); });
+}
+
+}  // namespace gnx
 
 extern "C" {
 

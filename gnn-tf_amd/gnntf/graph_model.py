@@ -65,14 +65,19 @@ class GNN(Trainable):
         sparse.spmm ``storage``); every forward with grad enabled -- every training step -- runs the f32 path unchanged (``training_dtype`` is the
         separate switch for those).  Error:
         the APPNP loop is within (2^-8 / a) max_k ||H_k||_2 per column of the f32 result (first order), a GCN SpMM within
-        2^-8 |A| |X| elementwise.
+        2^-8 |A| |X| elementwise.  In GCNII a run of plain GCNIILayer layers runs as one bf16 chain (gnx_gcnii_step_bf16): the run's
+        input is rounded once, every layer but the run's last stores its rows rounded once to bf16, the last writes f32; sums, H0
+        (f32), the mix and the transform stay f32.  Elementwise the result is within E_L of the f32 stack to first order,
+        E_0 = 2^-8 |H|, E_{l+1} = ((1-a) |A| E_l) |M_l| + 2^-8 |out_l| (layers that store bf16).  GCNIISpectralPreservingLayer,
+        activations other than relu / the identity, add_eye and widths outside sparse.GCNII_BF16_MIN_WIDTH ...
+        GCNII_BF16_MAX_WIDTH keep f32 and its bits.
         ``training_dtype=torch.bfloat16`` (opt-in, not in the reference; separate from ``inference_dtype``, which keeps meaning eval
         only): training-mode PPR propagation with edge dropout (PPRLoop, fused runs of PPRIteration layers) gathers its iterate and
         its back-propagated gradient as bf16 (sparse.ppr_loop ``storage``): masks, degree scales, weights, sums, H0, the mix and
         both results of the step stay f32, a row is rounded once as it is handed to the next iteration.  It is an allowance: the
         loop keeps f32 -- today's bits -- where the fused chained form does not apply (relu, no edge dropout, a graph that cannot
         fuse its dropout), below sparse.BF16_TRAIN_MIN_WIDTH columns and on graphs of fewer than sparse.BF16_TRAIN_MIN_ROWS vertices
-        (where it measured slower).  It is ignored by GCNLayer / GCNIILayer training and by the
+        (where it measured slower).  It is ignored by GCNLayer / GCNIILayer training (GCNII training keeps gnx_gcnii_step) and by the
         vertex-partitioned path (sharded.py), which keep f32 whatever it says."""
         if inference_dtype not in (torch.float32, torch.bfloat16):
             raise Exception("GNN: inference_dtype must be torch.float32 or torch.bfloat16")
@@ -373,7 +378,62 @@ class GCNIILayer(Layer):
     """gcn.py:7-27: dropout(act(((1-a) A.H + a H0) . ((1-b) I + b W))), b = beta_transformer(l / (k+1)).
     ONE launch per layer for C in {16, 32, 64} -- the mixed rows stay in LDS and meet (1-b) I + b W on the matrix cores
     (gnx_gcnii_step); in training the same launch also writes the mixed rows once (dW needs them) instead of a second launch
-    reading them back."""
+    reading them back.
+
+    On a GNN with ``inference_dtype=torch.bfloat16`` a RUN of consecutive plain GCNIILayer layers (this class itself, relu or the
+    identity as activation, no add_eye) in an eval-mode forward without autograd executes as one bf16 chain
+    (sparse.gcnii_chain_bf16 over gnx_gcnii_step_bf16): the run's input is rounded to bf16 once, every layer but the run's last
+    stores its rows rounded once to bf16 -- what the next layer gathers -- and the last one writes f32; sums, each layer's f32 H0,
+    the mix and the transform stay f32 (dropout is the identity in eval mode, so nothing sits between the layers).  The ``.value``
+    of an inner layer of the run is the exact widening of its bf16 rows, computed when somebody reads it.  Widths outside
+    sparse.GCNII_BF16_MIN_WIDTH ... GCNII_BF16_MAX_WIDTH, every forward under autograd or in training mode, and
+    GCNIISpectralPreservingLayer keep the f32 path and its bits.  ``architecture.fuse_runs = False`` switches the chain off."""
+
+    # ``.value`` may be pending after a bf16 run: computed on first read (as PPRIteration's)
+    @property
+    def value(self):
+        pending = self.__dict__.get("_pending_value")
+        if pending is not None:
+            self.__dict__["_value"], self.__dict__["_pending_value"] = pending(), None
+        return self.__dict__.get("_value")
+
+    @value.setter
+    def value(self, v):
+        self.__dict__["_value"], self.__dict__["_pending_value"] = v, None
+
+    def _transform(self):
+        b = self.beta_transformer(self.l / (self.k + 1))
+        eye = torch.eye(self.W.shape[1], device=self.W.device, dtype=self.W.dtype)
+        return (1 - b) * eye + b * self.W
+
+    def _bf16_plain(self, gcn) -> bool:
+        """Whether this layer can be one step of a bf16 run (the caller has established eval mode without autograd)."""
+        width = self.W.shape[1]
+        return (type(self) is GCNIILayer and (self.activation is relu or self.activation is linear)
+                and isinstance(self.a, (int, float)) and not isinstance(self.a, bool)
+                and sparse.GCNII_BF16_MIN_WIDTH <= width <= sparse.GCNII_BF16_MAX_WIDTH
+                and isinstance(getattr(self.H0, "value", None), torch.Tensor)
+                and gcn.get_adjacency(self.graph_dropout).diag is None)
+
+    def __run__(self, gcn, features, stack, at):
+        if _eval_storage(gcn) is not torch.bfloat16 or not isinstance(features, torch.Tensor) or not features.is_cuda \
+                or not self._bf16_plain(gcn):
+            return None
+        run = [self]
+        for layer in stack[at + 1:]:
+            # (a layer whose H0 is a layer INSIDE the run would need that layer's value first: it ends the run)
+            if not (isinstance(layer, GCNIILayer) and layer._bf16_plain(gcn) and layer.graph_dropout == self.graph_dropout
+                    and all(layer is not seen and layer.H0 is not seen for seen in run)):
+                break
+            run.append(layer)
+        adjacency = gcn.get_adjacency(self.graph_dropout)
+        steps = [(layer.H0.value, float(layer.a), layer._transform(), layer.activation is relu) for layer in run]
+        out = sparse.gcnii_chain_bf16(adjacency, features, steps)
+        for k, layer in enumerate(run[:-1]):
+            layer.__dict__["_value"] = None
+            layer.__dict__["_pending_value"] = lambda k=k: sparse.gcnii_chain_bf16(adjacency, features, steps[:k + 1], widen_last=True)
+        run[-1].value = out
+        return len(run), out
 
     def __build__(self, architecture, H0: Layer, a: float, l: float, k: int = 0, activation=linear,
                   beta_transformer=math.log1p, dropout: float = 0.5, graph_dropout: float = 0.5, regularization=True):
@@ -388,9 +448,7 @@ class GCNIILayer(Layer):
         return architecture.top_shape()
 
     def __forward__(self, gcn, features):
-        b = self.beta_transformer(self.l / (self.k + 1))
-        eye = torch.eye(self.W.shape[1], device=self.W.device, dtype=self.W.dtype)
-        transform = (1 - b) * eye + b * self.W
+        transform = self._transform()
         adjacency = gcn.get_adjacency(self.graph_dropout)
         if features.is_cuda and adjacency.diag is None:
             fused_act = self.activation is relu or self.activation is linear

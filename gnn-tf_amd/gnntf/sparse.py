@@ -1030,16 +1030,84 @@ class _GCNIIStep(torch.autograd.Function):
         return gH, gH0, gM, None, None, None
 
 
-def gcnii_step(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, M: torch.Tensor, relu=True) -> torch.Tensor:
+def gcnii_step(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, M: torch.Tensor, relu=True, storage=torch.float32,
+               out_storage=torch.float32) -> torch.Tensor:
     """act(((A . H)(1-a) + H0 a) . M), M = (1-b) I + b W (gcn.py:22-27) -- ONE fused launch for C in {16, 32, 64}: the mixed
     rows stay in LDS and meet M on the matrix cores (gnx_gcnii_step).  Without autograd they never reach HBM; when gradients are
     needed the same launch also writes them (dM = T^T g needs them), once, and the transform does not read them back.  Other
-    widths run the fused SpMM+mix and then the matrix-core transform."""
+    widths run the fused SpMM+mix and then the matrix-core transform.
+    ``storage=torch.bfloat16`` (inference only: raises where autograd would need a gradient): the rows the launch GATHERS are bf16
+    (gnx_gcnii_step_bf16) -- a bf16 H as it is, an f32 H rounded once (gnx_cast_bf16) -- widened exactly; sums, H0, the mix and the
+    transform stay f32.  The result is f32, or with ``out_storage=torch.bfloat16`` rounded once as it is stored (what the next layer
+    of a stack gathers).  Over a bf16-representable H the f32 result is bit for bit the default path's."""
+    if _bf16(storage):
+        _no_grad_for_bf16("gcnii_step", H, H0, M)
+        return _gcnii_launch_bf16(adj, H, H0, a, M, relu, _bf16(out_storage))
+    if _bf16(out_storage):
+        raise Exception("gcnii_step: a bf16 result needs storage=torch.bfloat16")
     if torch.is_grad_enabled() and (H.requires_grad or H0.requires_grad or M.requires_grad):
         if isinstance(adj, DroppedAdjacency):                       # weights made inside the SpMM: the generic composition knows how
             return dense(ppr_step(adj, H, H0, a), M, None, relu)
         return _GCNIIStep.apply(H, H0, M, adj, float(a), bool(relu))
     return _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=False)[0]
+
+
+# the model-level bf16 path of GCNIILayer (graph_model.py) keeps f32 below this width.  tools/gcnii_bf16_bench.py is the measurement
+# it is to be set from (profiles/NOTES.md "bf16 storage in the GCNII layer": no table recorded yet); until then it stands where the
+# plain SpMM's measurements put it: up to 32 columns a gathered row is one 128-byte line in either format (a wash at C = 17 ... 32,
+# a loss at C <= 16).  The C entry and gcnii_step(storage=) themselves are not gated.
+GCNII_BF16_MIN_WIDTH = 33
+GCNII_BF16_MAX_WIDTH = 256      # a bf16 result of gnx_gcnii_step_bf16 is one column panel of the dense kernel
+
+
+def _gcnii_launch_bf16(adj: Adjacency, H, H0, a, M, relu, out_bf16, out=None, work=None):
+    """gnx_gcnii_step_bf16.  ``out`` / ``work``: buffers a stack of layers shares (contiguous [n, C]: bf16 or f32 / f32)."""
+    g = adj.graph
+    nat.require_cuda(H, H0, M)
+    _same_device(g, H, H0, M)
+    if H.dim() != 2:
+        raise Exception("gcnii_step: shape mismatch")
+    Hb = (H if H.is_contiguous() else H.contiguous()) if H.dtype == torch.bfloat16 else to_bf16(H)
+    H0, M = _as_f32_rows(H0).contiguous(), _as_f32_rows(M)
+    C = Hb.shape[1]
+    if g.n_rows != g.n_cols or Hb.shape[0] != g.n_rows or tuple(H0.shape) != tuple(Hb.shape) or tuple(M.shape) != (C, C):
+        raise Exception("gcnii_step: shape mismatch")
+    if adj.diag is not None:
+        raise Exception("gcnii_step: add_eye adjacencies are not supported by the fused step")
+    if out_bf16 and C > GCNII_BF16_MAX_WIDTH:                       # wider than one panel: the f32 result, rounded by gnx_cast_bf16
+        return to_bf16(_gcnii_launch_bf16(adj, Hb, H0, a, M, relu, False, work=work))
+    want = torch.bfloat16 if out_bf16 else torch.float32
+    if out is None:
+        out = torch.empty(Hb.shape, dtype=want, device=Hb.device)
+    if work is None:
+        work = torch.empty(Hb.shape, dtype=torch.float32, device=Hb.device)
+    if out.dtype != want or tuple(out.shape) != tuple(Hb.shape) or not out.is_contiguous() or work.dtype != torch.float32 \
+            or tuple(work.shape) != tuple(Hb.shape) or not work.is_contiguous() or out.device != Hb.device or work.device != Hb.device:
+        raise Exception("gcnii_step: bad output / work buffer")
+    with nat.on_device(Hb.device):
+        nat.check(nat.lib().gnx_gcnii_step_bf16(g.handle, nat.ptr(adj.vals), nat.ptr(Hb), nat.ptr(H0), float(a), C, nat.ptr(M),
+                                                M.stride(0), nat.ACT_RELU if relu else nat.ACT_NONE, nat.ptr(out), 1 if out_bf16 else 0,
+                                                nat.ptr(work), nat.current_stream()))
+    return out
+
+
+def gcnii_chain_bf16(adj: Adjacency, H: torch.Tensor, steps, widen_last=False) -> torch.Tensor:
+    """A stack of GCNII layers with the rows handed from layer to layer stored as bf16 (inference only).  ``steps``: per layer
+    (H0, a, M, relu).  The input is rounded once (a bf16 H is used as it is), every layer but the last stores bf(out), the last one
+    f32 -- bit for bit gcnii_step(storage=bf16, out_storage=bf16 ... f32) layer by layer; H0 stays f32.  One f32 work buffer and two
+    bf16 buffers serve the whole stack.  ``widen_last``: the last layer stores bf16 too and the exact widening of that row is returned
+    (the value an INNER layer of a longer stack hands on)."""
+    steps = list(steps)
+    _no_grad_for_bf16("gcnii_chain_bf16", H, *[t for H0, _, M, _ in steps for t in (H0, M)])
+    if not steps:
+        raise Exception("gcnii_chain_bf16: no layers")
+    X = H if H.dtype == torch.bfloat16 else to_bf16(H)
+    work = torch.empty(X.shape, dtype=torch.float32, device=X.device)
+    ping = [torch.empty(X.shape, dtype=torch.bfloat16, device=X.device) for _ in range(min(2, len(steps) - (0 if widen_last else 1)))]
+    for k, (H0, a, M, relu) in enumerate(steps):
+        last = k == len(steps) - 1 and not widen_last
+        X = _gcnii_launch_bf16(adj, X, H0, a, M, relu, not last, out=None if last else ping[k % 2], work=work)
+    return X.float() if widen_last else X
 
 
 class DeviceIndex:

@@ -56,7 +56,8 @@ const char *gnx_last_error(void);
  * 0.7 adds gnx_graph_enable_entry_dropout (the fused training entries accept handles with duplicate entries once it was called);
  * 0.8 adds the bf16 storage entries of the fused training loops (gnx_spmm_dropped_chained_bf16, gnx_spmm_dropped_back_bf16) and
  * changes nothing else; 0.9 adds the bf16 storage entries of the vertex-partitioned path (gnx_spmm_rows_bf16, gnx_halo_pack_bf16,
- * gnx_halo_exchange_bf16), likewise. */
+ * gnx_halo_exchange_bf16), likewise.  gnx_gcnii_step_bf16 was added WITHIN 0.9 (no existing signature changed, the number stays
+ * 900): a client that wants it probes the library for the symbol (dlsym) instead of comparing versions. */
 #define GNX_ABI_VERSION 900
 int gnx_version(void);
 
@@ -361,6 +362,27 @@ int gnx_spmm_dropped_back_bf16(gnx_graph_t g, const float *d_D, float dropout_p,
  * Other widths NEED d_mixed: they run gnx_spmm into it and then gnx_dense.  All matrices contiguous [n, C]; square graph. */
 int gnx_gcnii_step(gnx_graph_t g, const float *d_vals, const float *d_H, const float *d_H0, float a, int64_t C,
                    const float *d_M, int64_t ldm, int act, float *d_out, float *d_mixed, void *stream);
+/* gnx_gcnii_step_bf16 (opt-in bf16 feature storage, inference only; added within ABI 0.9 -- probe for the symbol): the same layer
+ * with the GATHERED rows d_H stored as bf16 (uint16_t bit patterns, [n, C] contiguous):
+ *   out = act( ((1-a) * A_hat . H~ + a * H0) . M )
+ * Rounding points (bf = the cast of gnx_cast_bf16: round to nearest even, NaN stays NaN; u = 2^-8): H~ is widened exactly as it
+ * arrives; the sums, H0 (f32), the mix and the transform (v_mfma_f32_16x16x4_f32, exact float32) are f32; out is f32 (out_bf16 = 0)
+ * or bf(.) (out_bf16 = 1, uint16_t [n, C]) -- that ONE store is the only rounding the entry adds.  In a stack of layers the first
+ * operand is bf(H) (gnx_cast_bf16), every layer but the last hands bf(out) to the next, the last writes f32; H0 stays f32.
+ * Per row the entry order, the summation order (chunk order for hub rows) and the transform are those of gnx_gcnii_step: over
+ * bf16-representable H, out_bf16 = 0 returns the bits of gnx_gcnii_step over the widened H (same dispatch class: buffers aligned
+ * alike), and out_bf16 = 1 the bits of gnx_cast_bf16 of that; two calls give the same bits.  No d_mixed is kept: training uses
+ * gnx_gcnii_step.  Square graphs; the argument checks of gnx_gcnii_step.
+ * Dispatch: C in {16, 32, 64} with d_H (and a bf16 d_out) 8-byte aligned and the f32 buffers 16-byte aligned: the one fused launch,
+ * bf16 rows loaded as 8-byte units of four columns; hub rows (longer than the handle's threshold) go through the bf16 long-row chunk
+ * kernels into f32 mixed rows in d_work, the dense kernel transforms those rows alone, and they are rounded on the way out when
+ * out_bf16 = 1.  Other widths / alignments: the SpMM + mix over bf16 rows into d_work (f32), the dense kernel, then the rounding
+ * pass when out_bf16 = 1 (that form needs C <= 256: GNX_ERR_UNSUPPORTED above -- take out_bf16 = 0 and gnx_cast_bf16 there).
+ * d_work: f32 [n, C], distinct from every other argument; may be NULL exactly when the fused launch applies and the handle has no hub
+ * rows, otherwise NULL returns GNX_ERR_INVALID naming d_work.  Allocation-free once the handle is reserved (gnx_graph_reserve: the
+ * long-row slab); under capture it returns GNX_ERR_UNSUPPORTED naming gnx_graph_reserve where the slab would have to grow. */
+int gnx_gcnii_step_bf16(gnx_graph_t g, const float *d_vals, const uint16_t *d_H, const float *d_H0, float a, int64_t C,
+                        const float *d_M, int64_t ldm, int act, void *d_out, int out_bf16, float *d_work, void *stream);
 
 /* ---- the dense ends of the path (matrix cores) -----------------------------------------------------------------------
  * gnx_dense: out = act(X . W + bias) -- Dense.__forward__ (gnntf/core/nn/layers.py:135-136) and the transform of
@@ -489,7 +511,8 @@ int gnx_probe_block_xcd(int64_t n_blocks, int32_t *d_xcd_out, void *stream);
  * "...+long_bf16" (hub rows through the chunk kernels) and "...+chunks_bf16" (gnx_spmm_rows_bf16 and the push half of
  * gnx_halo_pack_bf16 -- on the push graph's handle -- report these same names: no new suffix); the bf16 training entries report the f32 training
  * names with "_bf16" appended ("spmm_group16_drop_bf16", "spmm_wave_drop_entries_bf16", ...), "+long" after the row class when hub
- * rows went through the chunk kernels ("spmm_group8+long_drop_bf16"). */
+ * rows went through the chunk kernels ("spmm_group8+long_drop_bf16"); gnx_gcnii_step_bf16 reports "spmm_gcnii_mfma_bf16" (the fused
+ * launch, with or without hub rows) or "spmm+dense_mfma_bf16" (the other widths / alignments). */
 const char *gnx_graph_last_kernel(gnx_graph_t g);
 
 #ifdef __cplusplus
