@@ -240,6 +240,13 @@ __global__ void k_relabel_keys(const int64_t *__restrict__ rowptr, const int32_t
     ids[r] = (int32_t)r;
 }
 
+// gcol[k] = rank[colidx[k]]: the position of every entry's column in the gather order
+__global__ void k_gather_columns(const int32_t *__restrict__ colidx, const int32_t *__restrict__ rank, int64_t nnz,
+                                 int32_t *__restrict__ gcol) {
+    int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < nnz) gcol[k] = rank[colidx[k]];
+}
+
 __global__ void k_permute_vals(const float *__restrict__ vals, const int32_t *__restrict__ perm, int64_t n,
                                float *__restrict__ out) {
     int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -416,7 +423,7 @@ int build_long_plan(Csr &m, hipStream_t s) {
 }
 
 // A stream that is being captured into a hipGraph must not see hipMalloc / hipFree / synchronisation: the lazily built parts of
-// a handle (long-row slab, transposed structure, relabelled copy) refuse to grow there and say how to prepare them.
+// a handle (long-row slab, transposed structure, relabelled copy, gather order) refuse to grow there and say how to prepare them.
 bool stream_is_capturing(hipStream_t s) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
@@ -506,9 +513,17 @@ static void drop_relabel(gnx_graph *g) {
     free_csr(g->r);
     if (g->r_perm) (void)hipFree(g->r_perm);
     if (g->r_vals) (void)hipFree(g->r_vals);
-    if (g->r_order) (void)hipFree(g->r_order);
-    g->r_perm = nullptr; g->r_vals = nullptr; g->r_order = nullptr;
+    g->r_perm = nullptr; g->r_vals = nullptr;
     g->has_r = false;
+}
+
+// the gather order and the per-entry gather columns (the relabelled copy, which is numbered in that order, goes first)
+static void drop_gather_order(gnx_graph *g) {
+    if (g->go_order) (void)hipFree(g->go_order);
+    if (g->go_rank) (void)hipFree(g->go_rank);
+    if (g->a_gcol) (void)hipFree(g->a_gcol);
+    if (g->t_gcol) (void)hipFree(g->t_gcol);
+    g->go_order = nullptr; g->go_rank = nullptr; g->a_gcol = nullptr; g->t_gcol = nullptr;
 }
 
 int ensure_relabel_features(gnx_graph *g, size_t bytes, hipStream_t s) {
@@ -521,10 +536,44 @@ int ensure_relabel_features(gnx_graph *g, size_t bytes, hipStream_t s) {
     return GNX_OK;
 }
 
-// The matrix with its vertices renumbered in the degree-binned order (heaviest first; inside a bin by the degree rank of a vertex's
-// most popular neighbour -- profiles/NOTES.md round 4: -4 % time, -16 % of the long-row kernel's fabric bytes at C = 8): same
-// entries, rows and columns permuted alike, columns ascending inside a row.  Built once, on the first narrow-width propagation of
-// a large square graph.
+// The gather order of a square handle: the degree bins of a.row_order (heaviest first) and, inside a bin, the vertices by the degree
+// rank of their most popular neighbour, then by id (profiles/NOTES.md round 4: -4 % time, -16 % of the long-row kernel's fabric bytes
+// at C = 8 against the plain degree order).  Hub rows become neighbours in memory and share 128-byte lines, a hub's leaves sit in
+// consecutive lines.  go_order[i] = the vertex at position i, go_rank = its inverse.  Built once, on first use.
+int ensure_gather_order(gnx_graph *g, hipStream_t s) {
+    if (g->go_order) return GNX_OK;
+    GNX_NOT_WHILE_CAPTURING(s, "the gather order of this handle");
+    const Csr &a = g->a;
+    GNX_CHECK_ARG(a.n_rows == a.n_cols && a.row_order != nullptr && a.n_rows > 0, "the gather order needs a non-empty square graph");
+    const int64_t n = a.n_rows, nnz = a.nnz;
+    DevBuf order, rank, key, ids, k0, k1, otmp;
+    GNX_HIP(order.alloc(n * 4)); GNX_HIP(rank.alloc(n * 4)); GNX_HIP(key.alloc(n * 4)); GNX_HIP(ids.alloc(n * 4));
+    GNX_HIP(k0.alloc(n * 8)); GNX_HIP(k1.alloc(n * 8));
+    hipLaunchKernelGGL(k_invert_order, dim3(blocks_for(n)), dim3(256), 0, s, a.row_order, n, rank.as<int32_t>());   // degree rank
+    GNX_HIP(hipMemsetAsync(key.p, 0x7f, n * 4, s));                            // 0x7f7f7f7f: "no neighbour" sorts last
+    if (nnz > 0)
+        hipLaunchKernelGGL(k_min_neighbour_rank, dim3(blocks_for(nnz)), dim3(256), 0, s, g->rowidx, a.colidx, rank.as<int32_t>(), nnz,
+                           key.as<int32_t>());
+    const int clamp = a.long_row < 65535 ? a.long_row : 65535;                 // as build_long_plan binned the rows
+    hipLaunchKernelGGL(k_relabel_keys, dim3(blocks_for(n)), dim3(256), 0, s, a.rowptr, key.as<int32_t>(), n, clamp,
+                       k0.as<uint64_t>(), ids.as<int32_t>());
+    const unsigned order_bits = 32u + bits_for((uint64_t)clamp + 1);
+    size_t ob = 0;
+    GNX_HIP(rocprim::radix_sort_pairs(nullptr, ob, k0.as<uint64_t>(), k1.as<uint64_t>(), ids.as<int32_t>(), order.as<int32_t>(), (size_t)n,
+                                      0u, order_bits, s));
+    GNX_HIP(otmp.alloc(ob));
+    GNX_HIP(rocprim::radix_sort_pairs(otmp.p, ob, k0.as<uint64_t>(), k1.as<uint64_t>(), ids.as<int32_t>(), order.as<int32_t>(), (size_t)n,
+                                      0u, order_bits, s));
+    hipLaunchKernelGGL(k_invert_order, dim3(blocks_for(n)), dim3(256), 0, s, order.as<int32_t>(), n, rank.as<int32_t>());
+    GNX_HIP(hipStreamSynchronize(s));
+    GNX_HIP(hipGetLastError());
+    g->go_order = (int32_t *)order.release();
+    g->go_rank = (int32_t *)rank.release();
+    return GNX_OK;
+}
+
+// The matrix with its vertices renumbered in the gather order: same entries, rows and columns permuted alike, columns ascending
+// inside a row.  Built once, on the first narrow-width propagation of a large square graph.
 int ensure_relabel(gnx_graph *g, hipStream_t s) {
     if (g->has_r) return GNX_OK;
     GNX_NOT_WHILE_CAPTURING(s, "the relabelled copy of this handle");
@@ -532,36 +581,17 @@ int ensure_relabel(gnx_graph *g, hipStream_t s) {
     const Csr &a = g->a;
     Csr &r = g->r;
     GNX_CHECK_ARG(a.n_rows == a.n_cols && a.row_order != nullptr && a.nnz > 0, "relabelling needs a non-empty square graph");
+    int rc = ensure_gather_order(g, s);
+    if (rc != GNX_OK) return rc;
     const int64_t n = a.n_rows, nnz = a.nnz;
     r.n_rows = n; r.n_cols = n; r.nnz = nnz;
     GNX_HIP(hipMalloc((void **)&r.rowptr, (n + 1) * sizeof(int64_t)));
     GNX_HIP(hipMalloc((void **)&r.colidx, nnz * sizeof(int32_t)));
     GNX_HIP(hipMalloc((void **)&g->r_perm, nnz * sizeof(int32_t)));
     GNX_HIP(hipMalloc((void **)&g->r_vals, nnz * sizeof(float)));
-    GNX_HIP(hipMalloc((void **)&g->r_order, n * sizeof(int32_t)));
-    DevBuf newid, k0, k1, p0, rrow, tmp;
-    GNX_HIP(newid.alloc(n * 4)); GNX_HIP(k0.alloc(nnz * 8)); GNX_HIP(k1.alloc(nnz * 8)); GNX_HIP(p0.alloc(nnz * 4)); GNX_HIP(rrow.alloc(nnz * 4));
-    {   // the order: degree bins (heaviest first); inside a bin by the degree rank of the most popular neighbour, then by id
-        DevBuf key, ids, otmp;
-        GNX_HIP(key.alloc(n * 4)); GNX_HIP(ids.alloc(n * 4));
-        hipLaunchKernelGGL(k_invert_order, dim3(blocks_for(n)), dim3(256), 0, s, a.row_order, n, newid.as<int32_t>());   // degree rank
-        GNX_HIP(hipMemsetAsync(key.p, 0x7f, n * 4, s));                            // 0x7f7f7f7f: "no neighbour" sorts last
-        hipLaunchKernelGGL(k_min_neighbour_rank, dim3(blocks_for(nnz)), dim3(256), 0, s, g->rowidx, a.colidx, newid.as<int32_t>(), nnz,
-                           key.as<int32_t>());
-        const int clamp = a.long_row < 65535 ? a.long_row : 65535;                 // as build_long_plan binned the rows
-        hipLaunchKernelGGL(k_relabel_keys, dim3(blocks_for(n)), dim3(256), 0, s, a.rowptr, key.as<int32_t>(), n, clamp,
-                           k0.as<uint64_t>(), ids.as<int32_t>());
-        const unsigned order_bits = 32u + bits_for((uint64_t)clamp + 1);
-        size_t ob = 0;
-        GNX_HIP(rocprim::radix_sort_pairs(nullptr, ob, k0.as<uint64_t>(), k1.as<uint64_t>(), ids.as<int32_t>(), g->r_order, (size_t)n, 0u,
-                                          order_bits, s));
-        GNX_HIP(otmp.alloc(ob));
-        GNX_HIP(rocprim::radix_sort_pairs(otmp.p, ob, k0.as<uint64_t>(), k1.as<uint64_t>(), ids.as<int32_t>(), g->r_order, (size_t)n, 0u,
-                                          order_bits, s));
-        GNX_HIP(hipStreamSynchronize(s));
-    }
-    hipLaunchKernelGGL(k_invert_order, dim3(blocks_for(n)), dim3(256), 0, s, g->r_order, n, newid.as<int32_t>());
-    hipLaunchKernelGGL(k_make_rkeys, dim3(blocks_for(nnz)), dim3(256), 0, s, g->rowidx, a.colidx, newid.as<int32_t>(), nnz, n,
+    DevBuf k0, k1, p0, rrow, tmp;
+    GNX_HIP(k0.alloc(nnz * 8)); GNX_HIP(k1.alloc(nnz * 8)); GNX_HIP(p0.alloc(nnz * 4)); GNX_HIP(rrow.alloc(nnz * 4));
+    hipLaunchKernelGGL(k_make_rkeys, dim3(blocks_for(nnz)), dim3(256), 0, s, g->rowidx, a.colidx, g->go_rank, nnz, n,
                        k0.as<uint64_t>(), p0.as<int32_t>());
     const unsigned end_bit = bits_for((uint64_t)n * (uint64_t)n);
     size_t tb = 0;
@@ -573,9 +603,48 @@ int ensure_relabel(gnx_graph *g, hipStream_t s) {
     hipLaunchKernelGGL(k_split_tkeys, dim3(blocks_for(nnz)), dim3(256), 0, s, k1.as<uint64_t>(), nnz, n, rrow.as<int32_t>(), r.colidx);
     hipLaunchKernelGGL(k_lower_bound_rows, dim3(blocks_for(n + 1)), dim3(256), 0, s, rrow.as<int32_t>(), nnz, n, r.rowptr);
     GNX_HIP(hipStreamSynchronize(s));
-    int rc = build_long_plan(r, s);
+    rc = build_long_plan(r, s);
     if (rc != GNX_OK) return rc;
     g->has_r = true;
+    return GNX_OK;
+}
+
+// What gnx_spmm_dropped_chained_ord / gnx_spmm_dropped_back_ord walk: the transposed structure, the gather order, and per entry of
+// either structure the position of its column in that order (4 bytes per entry each).  Stand-alone square handles without
+// duplicate entries and without a row window (whose numbering carries its locality already).
+int ensure_train_gather(gnx_graph *g, const char *fn, hipStream_t s) {
+    if (g->blk_col_gid != nullptr) {
+        set_error("%s: the handle is a vertex block (gnx_graph_set_block): the gather order exists for stand-alone graphs only", fn);
+        return GNX_ERR_UNSUPPORTED;
+    }
+    if (g->has_dups) {
+        set_error("%s: the graph holds duplicate COO entries: the gather order exists for handles without duplicates only", fn);
+        return GNX_ERR_UNSUPPORTED;
+    }
+    if (g->a.order_window != 0) {
+        set_error("%s: the handle has a row window (gnx_graph_set_row_window): its numbering carries locality already, the gather "
+                  "order is not built", fn);
+        return GNX_ERR_UNSUPPORTED;
+    }
+    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "%s: needs a square graph", fn);
+    if (g->a_gcol != nullptr) return GNX_OK;
+    if (g->a.n_rows == 0) return GNX_OK;                             // nothing is ever launched
+    GNX_NOT_WHILE_CAPTURING(s, "the gather-order columns of this handle (GNX_RESERVE_TRAIN_GATHER)");
+    int rc = ensure_transpose(g, s);
+    if (rc != GNX_OK) return rc;
+    rc = ensure_gather_order(g, s);
+    if (rc != GNX_OK) return rc;
+    const int64_t nnz = g->a.nnz;
+    DevBuf ac, tc;
+    GNX_HIP(ac.alloc(nnz * 4)); GNX_HIP(tc.alloc(nnz * 4));
+    if (nnz > 0) {
+        hipLaunchKernelGGL(k_gather_columns, dim3(blocks_for(nnz)), dim3(256), 0, s, g->a.colidx, g->go_rank, nnz, ac.as<int32_t>());
+        hipLaunchKernelGGL(k_gather_columns, dim3(blocks_for(nnz)), dim3(256), 0, s, g->t.colidx, g->go_rank, nnz, tc.as<int32_t>());
+    }
+    GNX_HIP(hipStreamSynchronize(s));
+    GNX_HIP(hipGetLastError());
+    g->t_gcol = (int32_t *)tc.release();
+    g->a_gcol = (int32_t *)ac.release();
     return GNX_OK;
 }
 
@@ -618,15 +687,20 @@ int gnx_graph_destroy(gnx_graph_t g) {
     free_csr(g->r);
     if (g->r_perm) (void)hipFree(g->r_perm);
     if (g->r_vals) (void)hipFree(g->r_vals);
-    if (g->r_order) (void)hipFree(g->r_order);
     if (g->r_feat) (void)hipFree(g->r_feat);
+    if (g->go_order) (void)hipFree(g->go_order);
+    if (g->go_rank) (void)hipFree(g->go_rank);
+    if (g->a_gcol) (void)hipFree(g->a_gcol);
+    if (g->t_gcol) (void)hipFree(g->t_gcol);
     delete g;
     return GNX_OK;
 }
 
 int gnx_graph_reserve(gnx_graph_t g, int64_t C, int flags, void *stream) {
     GNX_CHECK_ARG(g != nullptr, "gnx_graph_reserve: NULL handle");
-    GNX_CHECK_ARG(C >= 1 && (flags & ~(GNX_RESERVE_TRANSPOSED | GNX_RESERVE_K_LOOP)) == 0, "gnx_graph_reserve: bad width / flags");
+    GNX_CHECK_ARG(C >= 1 && (flags & ~(GNX_RESERVE_TRANSPOSED | GNX_RESERVE_K_LOOP | GNX_RESERVE_TRAIN_GATHER)) == 0,
+                  "gnx_graph_reserve: bad width / flags");
+    if (flags & GNX_RESERVE_TRAIN_GATHER) flags |= GNX_RESERVE_TRANSPOSED;
     hipStream_t s = (hipStream_t)stream;
     GNX_CHECK_ARG(!stream_is_capturing(s), "gnx_graph_reserve: the stream is being captured -- reserve before the capture begins");
     int64_t chunks = g->a.n_chunks;
@@ -645,7 +719,24 @@ int gnx_graph_reserve(gnx_graph_t g, int64_t C, int flags, void *stream) {
         if (rc != GNX_OK) return rc;
         chunks = std::max(chunks, g->r.n_chunks);
     }
+    if (flags & GNX_RESERVE_TRAIN_GATHER) {
+        int rc = ensure_train_gather(g, "gnx_graph_reserve(GNX_RESERVE_TRAIN_GATHER)", s);
+        if (rc != GNX_OK) return rc;
+    }
     if (chunks > 0) return ensure_partial(g, (size_t)chunks * (size_t)C * sizeof(float), s);
+    return GNX_OK;
+}
+
+int gnx_graph_gather_order(gnx_graph_t g, const int32_t **d_order, const int32_t **d_rank) {
+    GNX_CHECK_ARG(g != nullptr, "gnx_graph_gather_order: NULL handle");
+    if (g->a.order_window != 0) {
+        set_error("gnx_graph_gather_order: the handle has a row window (gnx_graph_set_row_window): the gather order is not built");
+        return GNX_ERR_UNSUPPORTED;
+    }
+    int rc = ensure_gather_order(g, nullptr);
+    if (rc != GNX_OK) return rc;
+    if (d_order) *d_order = g->go_order;
+    if (d_rank) *d_rank = g->go_rank;
     return GNX_OK;
 }
 
@@ -676,7 +767,8 @@ int gnx_graph_set_row_window(gnx_graph_t g, int64_t window_rows, void *stream) {
             return rc;
         }
     }
-    if (g->has_r) drop_relabel(g);                                   // the degree-relabelled copy belongs to the default order
+    if (g->has_r) drop_relabel(g);                                   // the degree-relabelled copy belongs to the default order,
+    drop_gather_order(g);                                            // and so do the gather order and its per-entry columns
     GNX_HIP(hipGetLastError());
     return GNX_OK;
 }

@@ -118,17 +118,24 @@ struct gnx_graph {
     // scale of local row r sits at position blk_row0_buf + r of the per-column scale vector
     int64_t blk_row0_global = 0, blk_row0_buf = 0;
     int32_t *blk_col_gid = nullptr;            // [a.n_cols] global vertex id of every column (owned), or null
-    // degree-relabelled copy of a square matrix (lazy; narrow feature widths): vertex r_order[i] becomes vertex i, so the
-    // rows of the hubs -- which most gathers hit -- are neighbours in memory and share cache lines.  r_order = the degree bins
+    // degree-relabelled copy of a square matrix (lazy; narrow feature widths): vertex go_order[i] becomes vertex i, so the
+    // rows of the hubs -- which most gathers hit -- are neighbours in memory and share cache lines.  go_order (below) = the degree bins
     // of a.row_order (heaviest first) and, inside a bin, the vertices by the degree rank of their most popular neighbour: the
     // leaves of one hub become neighbours too, so the hub's row gathers them from consecutive lines
     bool has_r = false;
     gnx::Csr r;
-    int32_t *r_order = nullptr;  // [n] new id -> old id
     int32_t *r_perm = nullptr;   // [a.nnz] coalesced slot of every relabelled entry
     float *r_vals = nullptr;     // [a.nnz] scratch: values gathered into relabelled order
     float *r_feat = nullptr;     // scratch: H0 in relabelled row order
     size_t r_feat_bytes = 0;
+    // the gather order of a square handle (lazy): the order the relabelled copy numbers its vertices in (above), kept on its own so
+    // that it can exist without that copy.  go_order: position -> vertex (what the relabelled copy calls new id -> old id), go_rank its
+    // inverse.  a_gcol / t_gcol (gnx_spmm_dropped_chained_ord / _back_ord): go_rank of every column of the matrix / of the transposed
+    // structure, i.e. the row of a matrix STORED in gather order that an entry gathers
+    int32_t *go_order = nullptr; // [n]
+    int32_t *go_rank = nullptr;  // [n]
+    int32_t *a_gcol = nullptr;   // [a.nnz]
+    int32_t *t_gcol = nullptr;   // [a.nnz]
     const char *last_kernel = "";
 };
 
@@ -141,6 +148,10 @@ int ensure_transpose(gnx_graph *g, hipStream_t s);
 int ensure_partial(gnx_graph *g, size_t bytes, hipStream_t s);
 bool stream_is_capturing(hipStream_t s);
 int ensure_relabel(gnx_graph *g, hipStream_t s);
+int ensure_gather_order(gnx_graph *g, hipStream_t s);
+// the transposed structure, the gather order and a_gcol / t_gcol; GNX_ERR_UNSUPPORTED (naming `fn`) on a vertex block, a handle with
+// duplicate entries or a handle with a row window
+int ensure_train_gather(gnx_graph *g, const char *fn, hipStream_t s);
 int ensure_relabel_features(gnx_graph *g, size_t bytes, hipStream_t s);
 
 // ---- counter RNG of the edge dropout: the same integer arithmetic as oracle/gnntf_oracle.py:hash_u24 ----------

@@ -214,7 +214,7 @@ int gnx_appnp_propagate_act(gnx_graph_t g, const float *d_vals, const float *d_d
                            g->r_vals);
         GNX_HIP(hipGetLastError());
         hipLaunchKernelGGL(k_gather_rows32, dim3((unsigned)std::min<int64_t>(blocks_for(n * C, 256), 1 << 22)), dim3(256), 0, s, d_H0, C,
-                           g->r_order, n, (int)C, g->r_feat, C);
+                           g->go_order, n, (int)C, g->r_feat, C);
         GNX_HIP(hipGetLastError());
         const float *src = g->r_feat;
         for (int k = 0; k < K; ++k) {
@@ -226,7 +226,7 @@ int gnx_appnp_propagate_act(gnx_graph_t g, const float *d_vals, const float *d_d
             // (with a relu such a row is relu(a * H0) after every iteration: just as constant)
             p.act = (!last && (k >= 2 || g->r.empty_rows_unreferenced)) ? (act | GNX_ACT_SKIP_EMPTY) : act;
             p.out = dst; p.ldo = C; p.C = (int)C;
-            p.out_rows = last ? g->r_order : nullptr;               // relabelled row i is the caller's row r_order[i]
+            p.out_rows = last ? g->go_order : nullptr;              // relabelled row i is the caller's row go_order[i]
             rc = launch_spmm(g, g->r, p, s);
             if (rc != GNX_OK) return rc;
             src = dst;

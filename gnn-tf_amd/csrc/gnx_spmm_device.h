@@ -137,7 +137,8 @@ inline bool aligned(const void *p, size_t a) { return p == nullptr || ((uintptr_
 // (`at` = element offset of the row, c = first column); diag / out_rows / out_scale / has_out2 = the optional pieces of the epilogue,
 // runtime-null pointers where an entry point of that storage can set them and a constant null where none can; EXPERIMENTS = the
 // kernels carry the A/B switches of the tuning build (SpmmArgs::tune, the PIPE / U variants), which exist for f32 rows only.
-// BF16 / NAMES_LONG only pick the reported name (kernel_name).
+// BF16 / NAMES_LONG only pick the reported name (kernel_name).  GATHER_ORDER = the kernels read OrdArgs::gcol / out2_rows (F32RowsOrd
+// below); where it is false those loads do not exist in the kernel.
 struct F32Rows {
     using Args = SpmmArgs;
     using Elem = float;
@@ -145,6 +146,7 @@ struct F32Rows {
     static constexpr bool EXPERIMENTS = true;
     static constexpr int BF16 = 0;
     static constexpr bool NAMES_LONG = false;    // the reported name does not say whether hub rows went through the chunk kernels
+    static constexpr bool GATHER_ORDER = false;
     __device__ static const float *X(const Args &p) { return p.X; }
     template <int VEC>
     __device__ static void load(float (&x)[VEC], const float *__restrict__ q) { vload<VEC>(x, q); }
@@ -161,6 +163,24 @@ struct F32Rows {
     __device__ static void store2(const Args &p, int64_t at, int c, const float (&o)[VEC]) { vstore<VEC>(p.out2 + at + c, o); }
     // (the second result's row starts are not looked at: every caller so far keeps it laid out like the first)
     static int vec(const Args &p) { return pick_vec(p, MAX_VEC, p.X, 4, p.out, 4, nullptr, 0); }
+};
+
+// f32 rows of a training launch whose gathered operand and / or results live in the handle's gather order (gnx_spmm_dropped_chained_ord,
+// gnx_spmm_dropped_back_ord): the lane that owns an entry loads its gather column (OrdArgs::gcol) beside its column -- the draw, the
+// mask and D[col] keep the column, the gather address takes the gather column -- and the second result goes through out2_rows as
+// the first goes through out_rows.  Per row the same fused multiply-adds on the same values in the same order as F32Rows.
+// (the two arrays live in an argument struct of their own, behind SpmmArgs, as the bf16 buffers do: inside SpmmArgs they would move
+// the bf16 kernels' arguments, and those kernels would no longer be the ones measured so far)
+struct OrdArgs : SpmmArgs {
+    const int32_t *gcol;        // per entry the row of X to gather (gnx_graph::a_gcol / t_gcol: X is stored in gather order); null = colidx
+    const int32_t *out2_rows;   // destination row of every row of the second result; null = the row itself
+};
+
+struct F32RowsOrd : F32Rows {
+    using Args = OrdArgs;
+    static constexpr bool EXPERIMENTS = false;
+    static constexpr bool NAMES_LONG = true;
+    static constexpr bool GATHER_ORDER = true;
 };
 
 struct BfArgs : SpmmArgs {     // SpmmArgs::X / ::out / ::out2 stay null: the typed buffers are here
@@ -183,6 +203,7 @@ struct Bf16RowsT {
     static constexpr bool EXPERIMENTS = false;
     static constexpr int BF16 = 1;
     static constexpr bool NAMES_LONG = true;
+    static constexpr bool GATHER_ORDER = false;
     __device__ static const uint16_t *X(const Args &p) { return p.Xb; }
     template <int VEC>
     __device__ static void load(float (&x)[VEC], const uint16_t *__restrict__ q) { bload<VEC>(x, q); }
@@ -205,17 +226,28 @@ __device__ __forceinline__ float readlane_f(float v, int lane) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
 
+// per entry the row of X a training kernel gathers: the handle's gather columns under a GATHER_ORDER policy whose launch stores X
+// in gather order, the column itself otherwise (wave-uniform, chosen once per kernel)
+template <typename R>
+__device__ __forceinline__ const int32_t *gather_cols(const typename R::Args &p) {
+    if constexpr (R::GATHER_ORDER) return p.gcol ? p.gcol : p.colidx;
+    else return nullptr;
+}
+
 // Sum of w_e * X[col_e, c .. c+VEC) over entries [beg, end) of one row; the whole wave works
 // on the same entries (beg/end wave-uniform), lane `lane` owns columns c .. c+VEC.  ENTRIES (with FUSE): the handle holds duplicate
-// entries and the weight of a slot is its kept sum (dropped_weight_entries).
-template <typename R, int VEC, int U, bool FUSE = false, bool ENTRIES = false>
+// entries and the weight of a slot is its kept sum (dropped_weight_entries).  GCOL (with FUSE): the gathered row of an entry is
+// gcol[entry] instead of its column (gather_cols).
+template <typename R, int VEC, int U, bool FUSE = false, bool ENTRIES = false, bool GCOL = false>
 __device__ __forceinline__ void wave_accumulate(const int32_t *__restrict__ colidx, const float *__restrict__ vals,
                                                 const typename R::Elem *__restrict__ X, int64_t ldx, int64_t beg, int64_t end,
                                                 int c, int lane, float (&acc)[VEC], bool nt_index = false,
-                                                const DropFuse *fuse = nullptr, int64_t row = 0) {
+                                                const DropFuse *fuse = nullptr, int64_t row = 0,
+                                                const int32_t *__restrict__ gcol = nullptr) {
     for (int64_t base = beg; base < end; base += 64) {
         const int n = (int)((end - base) < 64 ? (end - base) : 64);
         int mycol = 0;
+        [[maybe_unused]] int mygcol = 0;
         float myval = 0.f;
         if (lane < n) {
             if (nt_index) {
@@ -225,6 +257,7 @@ __device__ __forceinline__ void wave_accumulate(const int32_t *__restrict__ coli
                 mycol = colidx[base + lane];
                 myval = vals[base + lane];
             }
+            if constexpr (GCOL) mygcol = gcol[base + lane];
             if (FUSE) myval = dropped_weight_at<ENTRIES>(*fuse, myval, base + lane, row, mycol);   // one entry per lane: 64 weights per wave instruction
         }
         int i = 0;
@@ -240,7 +273,9 @@ __device__ __forceinline__ void wave_accumulate(const int32_t *__restrict__ coli
                     idx[u] = keep ? (int)__builtin_ctzll(keep) : -1;
                     if (keep) keep &= keep - 1;
                     if (idx[u] >= 0) {
-                        const int j = readlane_i(mycol, idx[u]);
+                        int j;
+                        if constexpr (GCOL) j = readlane_i(mygcol, idx[u]);
+                        else j = readlane_i(mycol, idx[u]);
                         R::template load<VEC>(x[u], X + (int64_t)j * ldx + c);
                     }
                 }
@@ -309,7 +344,11 @@ __device__ __forceinline__ void epilogue_store(const typename R::Args &p, int64_
         float o2[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) o2[v] = (acc[v] * p.beta2) * f2;
-        R::template store2<VEC>(p, row * p.ldo2, c, o2);
+        int64_t row2 = row;
+        if constexpr (R::GATHER_ORDER) {
+            if (p.out2_rows) row2 = (int64_t)p.out2_rows[row];
+        }
+        R::template store2<VEC>(p, row2 * p.ldo2, c, o2);
     }
     float o[VEC];
     const int64_t orow = R::out_rows(p) ? (int64_t)R::out_rows(p)[row] : row;
@@ -500,14 +539,14 @@ RowClass with_group(int lanes, F &&f) {
     return ROWS_G8;
 }
 
-// "spmm_" class ["+long" | "+chunks"] ["_drop" ["_entries"]] ["_bf16"]: every name reported so far, byte for byte, from one scheme.
+// "spmm_" class ["+long" | "+chunks"] ["_drop" ["_entries"]] ["_bf16" | "_ord"]: every name reported so far, byte for byte, from one scheme.
 // (The table spells out the whole product; most of its combinations -- "spmm_wave+chunks", "spmm_group4_drop" -- cannot be reported.)
 enum NameHubs { HUBS_NONE, HUBS_LONG, HUBS_CHUNKS };      // hub rows: none (or not named), separate chunk launches, chunks in the row launch
 enum NameMode { MODE_EVAL, MODE_DROP, MODE_DROP_ENTRIES };
 #define GNX_NAMES6(mid, tail) {"spmm_none" mid tail, "spmm_wave" mid tail, "spmm_group32" mid tail, "spmm_group16" mid tail, "spmm_group8" mid tail, "spmm_group4" mid tail}
 #define GNX_NAMES3(tail) {GNX_NAMES6("", tail), GNX_NAMES6("+long", tail), GNX_NAMES6("+chunks", tail)}
 #define GNX_NAMES(tail) {GNX_NAMES3(tail), GNX_NAMES3("_drop" tail), GNX_NAMES3("_drop_entries" tail)}
-[[maybe_unused]] const char *const kKernelNames[2][3][3][6] = {GNX_NAMES(""), GNX_NAMES("_bf16")};
+[[maybe_unused]] const char *const kKernelNames[3][3][3][6] = {GNX_NAMES(""), GNX_NAMES("_bf16"), GNX_NAMES("_ord")};
 #undef GNX_NAMES
 #undef GNX_NAMES3
 #undef GNX_NAMES6
@@ -515,7 +554,7 @@ enum NameMode { MODE_EVAL, MODE_DROP, MODE_DROP_ENTRIES };
 template <typename R>
 const char *kernel_name(RowClass rows, NameMode mode, NameHubs hubs) {
     if (hubs == HUBS_LONG && !R::NAMES_LONG) hubs = HUBS_NONE;
-    return kKernelNames[R::BF16][mode][hubs][rows];
+    return kKernelNames[R::GATHER_ORDER ? 2 : R::BF16][mode][hubs][rows];
 }
 
 // the operand checks every SpMM entry starts with (the bf16 training entries make them BEFORE they look at the handle, so that they

@@ -13,6 +13,8 @@ namespace {
 // ENTRIES (the _entries instantiations, a handle with duplicate COO entries after gnx_graph_enable_entry_dropout): p.vals holds each
 // slot's uniform value and the lane that owns a slot makes its kept sum (dropped_weight_entries) -- one more hash round per further
 // duplicate; everything else, and the kernels without duplicates, as before.
+// R::GATHER_ORDER (F32RowsOrd): the lane that owns an entry also loads its gather column and the gather address takes that one; the
+// draw, the mask and D[col] keep the column (gather_cols).
 template <typename R, int VEC, int U, int WPB, bool ENTRIES = false>
 __global__ __launch_bounds__(64 * WPB) void k_spmm_wave_drop(const typename R::Args p) {
     const int lane = threadIdx.x & 63;
@@ -28,7 +30,8 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_wave_drop(const typename R::A
         float acc[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-        wave_accumulate<R, VEC, U, true, ENTRIES>(p.colidx, p.vals, R::X(p), p.ldx, beg, end, active ? c : 0, lane, acc, false, &p.fuse, row);
+        wave_accumulate<R, VEC, U, true, ENTRIES, R::GATHER_ORDER>(p.colidx, p.vals, R::X(p), p.ldx, beg, end, active ? c : 0, lane, acc, false, &p.fuse,
+                                                                  row, gather_cols<R>(p));
         epilogue_store<R, VEC>(p, row, c, active, acc);
     }
 }
@@ -44,6 +47,8 @@ __global__ __launch_bounds__(256) void k_spmm_group_drop(const typename R::Args 
     const auto [row, beg, end] = slot_row<false>(p, slot);
     if (end - beg > p.long_row) return;
     if (p.skip_empty && beg == end) return;   // GNX_ACT_SKIP_EMPTY
+    constexpr bool GC = R::GATHER_ORDER;
+    [[maybe_unused]] const int32_t *__restrict__ gcol = gather_cols<R>(p);
     for (int c0 = 0; c0 < p.C; c0 += G * VEC) {
         const int c = c0 + sub * VEC;
         const bool active = c < p.C;
@@ -57,14 +62,19 @@ __global__ __launch_bounds__(256) void k_spmm_group_drop(const typename R::Args 
         for (int64_t base = beg; base < end; base += G) {          // G entries per round: lane `sub` owns entry base + sub
             const int n = (int)((end - base) < G ? (end - base) : G);
             int mycol = 0;
+            [[maybe_unused]] int mygcol = 0;                           // GATHER_ORDER: the row of X the entry gathers
             float myw = 0.f;
             if (PIPE) {
                 const int ccol = ncol;
                 const float craw = nraw;
                 if (base + G + sub < end) { ncol = p.colidx[base + G + sub]; nraw = p.vals[base + G + sub]; }
-                if (sub < n) { mycol = ccol; myw = dropped_weight_at<ENTRIES>(p.fuse, craw, base + sub, row, ccol); }
+                if (sub < n) {
+                    mycol = ccol; myw = dropped_weight_at<ENTRIES>(p.fuse, craw, base + sub, row, ccol);
+                    if constexpr (GC) mygcol = gcol[base + sub];
+                }
             } else if (sub < n) {
                 mycol = p.colidx[base + sub];
+                if constexpr (GC) mygcol = gcol[base + sub];
                 myw = dropped_weight_at<ENTRIES>(p.fuse, p.vals[base + sub], base + sub, row, mycol);
             }
             // dropped entries (weight exactly 0) are not gathered: the group walks only the kept entries of its round, in order
@@ -78,7 +88,9 @@ __global__ __launch_bounds__(256) void k_spmm_group_drop(const typename R::Args 
                     if (keep) {
                         const int idx = __builtin_ctz(keep);
                         keep &= keep - 1;
-                        const int j = __shfl(mycol, idx, G);
+                        int j;
+                        if constexpr (GC) j = __shfl(mygcol, idx, G);
+                        else j = __shfl(mycol, idx, G);
                         w[u] = __shfl(myw, idx, G);
                         R::template load<VEC>(x[u], Xc + (int64_t)j * p.ldx);
                     } else {
@@ -110,7 +122,8 @@ __global__ __launch_bounds__(256) void k_spmm_long_partial_drop(const typename R
         float acc[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-        wave_accumulate<R, VEC, U, true, ENTRIES>(p.colidx, p.vals, R::X(p), p.ldx, beg, end, active ? c : 0, lane, acc, false, &p.fuse, row);
+        wave_accumulate<R, VEC, U, true, ENTRIES, R::GATHER_ORDER>(p.colidx, p.vals, R::X(p), p.ldx, beg, end, active ? c : 0, lane, acc, false, &p.fuse,
+                                                                  row, gather_cols<R>(p));
         if (active) vstore<VEC>(p.partial + chunk * (int64_t)p.C + c, acc);
     }
 }
@@ -129,6 +142,8 @@ __global__ __launch_bounds__(256) void k_spmm_long_partial_group_drop(const type
     const int c = (lane % G) * VEC;
     const bool active = c < p.C;
     const typename R::Elem *__restrict__ Xc = R::X(p) + (active ? c : 0);
+    constexpr bool GC = R::GATHER_ORDER;
+    [[maybe_unused]] const int32_t *__restrict__ gcol = gather_cols<R>(p);
     float acc[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
@@ -137,9 +152,11 @@ __global__ __launch_bounds__(256) void k_spmm_long_partial_group_drop(const type
     for (int64_t base = beg; base < end; base += 64) {
         const int n = (int)((end - base) < 64 ? (end - base) : 64);
         int mycol = 0;
+        [[maybe_unused]] int mygcol = 0;
         float myw = 0.f;
         if (lane < n) {
             mycol = p.colidx[base + lane];
+            if constexpr (GC) mygcol = gcol[base + lane];
             myw = dropped_weight_at<ENTRIES>(p.fuse, p.vals[base + lane], base + lane, row, mycol);
         }
 #pragma unroll 1
@@ -149,7 +166,9 @@ __global__ __launch_bounds__(256) void k_spmm_long_partial_group_drop(const type
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int src = sub + (k + u) * NS;                  // entry of the round this sub-group takes in slot k + u
-                const int j = __shfl(mycol, src);
+                int j;
+                if constexpr (GC) j = __shfl(mygcol, src);
+                else j = __shfl(mycol, src);
                 w[u] = __shfl(myw, src);
                 if (k + u < G && src < n && w[u] != 0.f) R::template load<VEC>(x[u], Xc + (int64_t)j * p.ldx);   // dropped: not gathered
                 else {

@@ -18,7 +18,8 @@ NORM = {"none": 0, "symmetric": 1, "bipartite": 2}
 EYE = {"none": 0, "before": 1, "after": 2}
 ACT_NONE, ACT_RELU, ACT_SKIP_EMPTY = 0, 1, 256
 HALO_ALL, HALO_PULL, HALO_PUSH = 0, 1, 2
-RESERVE_TRANSPOSED, RESERVE_K_LOOP = 1, 2
+RESERVE_TRANSPOSED, RESERVE_K_LOOP, RESERVE_TRAIN_GATHER = 1, 2, 4
+ORD_X, ORD_OUT = 1, 2     # `order` of the _ord training entries: X stored in the handle's gather order / the result written in it
 
 # name -> (restype, argtypes); must list every symbol include/gnx.h declares
 SIGNATURES = {
@@ -53,6 +54,12 @@ SIGNATURES = {
                                          c_int64, c_float, c_float, c_int, c_void_p, c_int64, c_void_p]),
     "gnx_spmm_dropped_back": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_int, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
                                       c_int64, c_float, c_float, c_void_p, c_int64, c_float, c_void_p, c_int64, c_int, c_void_p]),
+    "gnx_graph_gather_order": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p)]),
+    "gnx_spmm_dropped_chained_ord": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_int, c_void_p, c_void_p, c_int64, c_int64,
+                                             c_void_p, c_int64, c_float, c_float, c_int, c_void_p, c_int64, c_int, c_void_p]),
+    "gnx_spmm_dropped_back_ord": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_int, c_void_p, c_void_p, c_int64, c_int64,
+                                          c_void_p, c_int64, c_float, c_float, c_void_p, c_int64, c_float, c_void_p, c_int64, c_int, c_int,
+                                          c_void_p]),
     "gnx_spmm_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_float, c_float, c_int,
                               c_void_p, c_void_p, c_int64, c_void_p]),
     "gnx_spmm_tv": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_float, c_float,

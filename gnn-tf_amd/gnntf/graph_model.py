@@ -47,7 +47,7 @@ class GNN(Trainable):
     fuse_entry_dropout = True
 
     def __init__(self, graph, features, preprocessor: Layer = None, reorder=None, inference_dtype=torch.float32,
-                 training_dtype=torch.float32):
+                 training_dtype=torch.float32, train_gather_order="auto"):
         """``reorder`` (opt-in, not in the reference): store the graph and the feature rows with the vertices relabelled; every
         [N, .] tensor inside the model then lives in that order, and the model's OUTPUT is put back into the caller's order, so
         tasks, labels and node ids are unaffected.  Results agree with the unordered model to float32 rounding.
@@ -78,7 +78,17 @@ class GNN(Trainable):
         loop keeps f32 -- today's bits -- where the fused chained form does not apply (relu, no edge dropout, a graph that cannot
         fuse its dropout), below sparse.BF16_TRAIN_MIN_WIDTH columns and on graphs of fewer than sparse.BF16_TRAIN_MIN_ROWS vertices
         (where it measured slower).  It is ignored by GCNLayer / GCNIILayer training (GCNII training keeps gnx_gcnii_step) and by the
-        vertex-partitioned path (sharded.py), which keep f32 whatever it says."""
+        vertex-partitioned path (sharded.py), which keep f32 whatever it says.
+        ``train_gather_order`` (not in the reference): ``"caller"``, ``"relabelled"`` or ``"auto"`` (sparse.ppr_loop
+        ``gather_order``).  ``"relabelled"``: the fused f32 training loops (PPRLoop, fused runs of PPRIteration layers, with edge
+        dropout) keep the iterate and the back-propagated gradient in the library's hub-adjacent gather order BETWEEN their launches;
+        the model, its rows, masks and sums stay in the caller's numbering and every result is bit for bit that of ``"caller"``
+        (unlike ``reorder="degree"``, which renumbers the model and rounds differently).  Where the chained f32 loop does not apply
+        (relu, bf16 training storage, graphs with duplicate entries, ``reorder="locality"`` row windows, the vertex-partitioned path)
+        it is today's path.  ``"auto"`` (the default) takes the relabelled order only at the widths and graph sizes where it
+        measured faster (sparse.TRAIN_GATHER_MAX_WIDTH / TRAIN_GATHER_MIN_ROWS; profiles/NOTES.md)."""
+        if train_gather_order not in sparse.GATHER_ORDERS:
+            raise Exception("GNN: train_gather_order must be one of " + ", ".join(repr(o) for o in sparse.GATHER_ORDERS))
         if inference_dtype not in (torch.float32, torch.bfloat16):
             raise Exception("GNN: inference_dtype must be torch.float32 or torch.bfloat16")
         if training_dtype not in (torch.float32, torch.bfloat16):
@@ -86,6 +96,7 @@ class GNN(Trainable):
         super().__init__(features)
         self.inference_dtype = inference_dtype
         self.training_dtype = training_dtype
+        self.train_gather_order = train_gather_order
         self._order = self._newid = None
         self.reorder_used, self.locality_share = None, None
         if isinstance(graph, sparse.DeviceGraph):
@@ -199,7 +210,10 @@ def _propagation_run(architecture: "GNN", H0_value, a, iterations, graph_dropout
         run = lambda k: sparse.appnp_propagate(make_adj(0, False), H0_value, a, k, relu=with_relu, storage=storage)
     else:
         storage = getattr(architecture, "training_dtype", torch.float32) if training else torch.float32
-        run = lambda k: sparse.ppr_loop(make_adj, H0_value, a, k, relu=with_relu, storage=storage)
+        # (the argument is passed only where it can change the path: outside the allowance "auto" is today's call, argument for argument)
+        gather_order = getattr(architecture, "train_gather_order", "caller") if training else "caller"
+        ordered = dict(gather_order=gather_order) if training and sparse.may_use_train_gather(architecture.graph, gather_order) else dict()
+        run = lambda k: sparse.ppr_loop(make_adj, H0_value, a, k, relu=with_relu, storage=storage, **ordered)
     return run(iterations), run, (make_adj if cheap else None)
 
 

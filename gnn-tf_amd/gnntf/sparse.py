@@ -54,6 +54,13 @@ def as_coo(graph) -> SparseCOO:
     raise Exception("Unsupported graph container: " + str(type(graph)))
 
 
+class _BorrowedInt32:
+    """A device array of ``n`` int32 the library owns, for torch.as_tensor (copied by the caller before the handle can change it)."""
+
+    def __init__(self, pointer, n):
+        self.__cuda_array_interface__ = dict(shape=(int(n),), typestr="<i4", data=(int(pointer or 0), False), version=2)
+
+
 class DeviceGraph:
     """Owner of a gnx_graph_t (device CSR built from the COO)."""
 
@@ -126,14 +133,26 @@ class DeviceGraph:
     def last_kernel(self) -> str:
         return (nat.lib().gnx_graph_last_kernel(self._h) or b"").decode()
 
-    def reserve(self, C, transposed=False, k_loop=False):
+    def reserve(self, C, transposed=False, k_loop=False, train_gather=False):
         """Builds NOW what the launches otherwise build on first use, sized for feature rows of up to ``C`` floats (the long-row
         slab; with ``transposed`` the transposed structure a backward needs; with ``k_loop`` the relabelled copy appnp_propagate
-        runs narrow widths on): those lazy builds allocate and synchronise, which a stream under hipGraph capture must not see
-        (a launch that would have to grow something there raises instead).  Call before capturing (gnx_graph_reserve)."""
-        flags = (nat.RESERVE_TRANSPOSED if transposed else 0) | (nat.RESERVE_K_LOOP if k_loop else 0)
+        runs narrow widths on; with ``train_gather`` the gather order and gather columns of the training loops' relabelled operand
+        order, ppr_loop(gather_order="relabelled"), which implies ``transposed``): those lazy builds allocate and synchronise, which
+        a stream under hipGraph capture must not see (a launch that would have to grow something there raises instead).  Call
+        before capturing (gnx_graph_reserve)."""
+        flags = ((nat.RESERVE_TRANSPOSED if transposed else 0) | (nat.RESERVE_K_LOOP if k_loop else 0)
+                 | (nat.RESERVE_TRAIN_GATHER if train_gather else 0))
         with nat.on_device(self.device):
             nat.check(nat.lib().gnx_graph_reserve(self._h, int(C), flags, nat.current_stream()))
+
+    def gather_order(self):
+        """(order, rank), int32 [n] each, copies: the handle's gather order (gnx_graph_gather_order) -- ``order[i]`` = the vertex at
+        position i, ``rank`` its inverse.  ``X[order.long()]`` is X stored in gather order.  Builds the order on first use
+        (allocates and synchronises: not under capture)."""
+        order, rank = c_void_p(), c_void_p()
+        with nat.on_device(self.device):
+            nat.check(nat.lib().gnx_graph_gather_order(self._h, byref(order), byref(rank)))
+            return tuple(torch.as_tensor(_BorrowedInt32(p.value, self.n_rows), device=self.device).clone() for p in (order, rank))
 
     def set_row_window(self, window_rows):
         """Declares that the vertex numbering of THIS graph carries locality (a community / breadth-first order): launches take the
@@ -324,27 +343,37 @@ def _launch(adj: Adjacency, X, H0, beta, alpha, act, transposed=False, out=None,
     return out
 
 
-def _launch_chained(adj: "DroppedAdjacency", X, H0, beta, alpha, prescaled, D_next, skip_empty=False):
+def _launch_chained(adj: "DroppedAdjacency", X, H0, beta, alpha, prescaled, D_next, skip_empty=False, order=None):
     """One forward training iteration inside a loop (gnx_spmm_dropped_chained): X carries its column scale when ``prescaled``,
     the result carries ``D_next`` (the next iteration's column scale) unless that is None.  ``skip_empty``: rows without entries
-    are left untouched (every iteration but the last: nobody gathers them; the library ignores it on graphs where somebody does)."""
+    are left untouched (every iteration but the last: nobody gathers them; the library ignores it on graphs where somebody does).
+    ``order`` (an OR of nat.ORD_X / nat.ORD_OUT, or None): the launch goes through gnx_spmm_dropped_chained_ord -- X stored in / the
+    result written in the graph's gather order; same bits."""
     g = adj.graph
     nat.require_cuda(X, H0)
     _same_device(g, X, H0, adj.D, D_next)
     if X.shape[0] != g.n_cols or tuple(H0.shape) != (g.n_rows, X.shape[1]) or not X.is_contiguous() or not H0.is_contiguous():
         raise Exception("chained propagation: bad operand shapes")
     out = torch.empty((g.n_rows, X.shape[1]), dtype=torch.float32, device=X.device)
+    act = nat.ACT_NONE | (nat.ACT_SKIP_EMPTY if skip_empty else 0)
     with nat.on_device(X.device):
+        if order is not None:
+            nat.check(nat.lib().gnx_spmm_dropped_chained_ord(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, 1 if prescaled else 0,
+                                                             nat.ptr(D_next), nat.ptr(X), X.stride(0), X.shape[1], nat.ptr(H0), H0.stride(0),
+                                                             float(beta), float(alpha), act, nat.ptr(out), out.stride(0), int(order),
+                                                             nat.current_stream()))
+            return out
         nat.check(nat.lib().gnx_spmm_dropped_chained(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, 1 if prescaled else 0,
                                                      nat.ptr(D_next), nat.ptr(X), X.stride(0), X.shape[1], nat.ptr(H0), H0.stride(0),
-                                                     float(beta), float(alpha), nat.ACT_NONE | (nat.ACT_SKIP_EMPTY if skip_empty else 0),
-                                                     nat.ptr(out), out.stride(0), nat.current_stream()))
+                                                     float(beta), float(alpha), act, nat.ptr(out), out.stride(0), nat.current_stream()))
     return out
 
 
-def _launch_back(adj: "DroppedAdjacency", X, prescaled, D_next, S_in, s_alpha, s_beta, S_out, y_beta, Y_out, skip_empty=False):
+def _launch_back(adj: "DroppedAdjacency", X, prescaled, D_next, S_in, s_alpha, s_beta, S_out, y_beta, Y_out, skip_empty=False, order=None):
     """One backward training iteration inside a loop (gnx_spmm_dropped_back): acc = A_k^T X over the transposed structure, weights
-    made in the kernel; S_out = s_beta acc + s_alpha S_in (S_in may be S_out), Y_out = y_beta acc * D_next (skipped when None)."""
+    made in the kernel; S_out = s_beta acc + s_alpha S_in (S_in may be S_out), Y_out = y_beta acc * D_next (skipped when None).
+    ``order`` (an OR of nat.ORD_X / nat.ORD_OUT, or None): through gnx_spmm_dropped_back_ord -- X stored in / Y_out written in the
+    graph's gather order, the running sum in the caller's; same bits."""
     g = adj.graph
     nat.require_cuda(X, S_in, S_out)
     _same_device(g, X, S_in, S_out, Y_out, adj.D, D_next)
@@ -352,17 +381,24 @@ def _launch_back(adj: "DroppedAdjacency", X, prescaled, D_next, S_in, s_alpha, s
     if any(t is not None and (tuple(t.shape) != (g.n_rows, C) or not t.is_contiguous() or t.dtype != torch.float32) for t in (X, S_in, S_out, Y_out)):
         raise Exception("chained backward: bad operand shapes")
     with nat.on_device(X.device):
+        if order is not None:
+            nat.check(nat.lib().gnx_spmm_dropped_back_ord(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, 1 if prescaled else 0,
+                                                          nat.ptr(D_next), nat.ptr(X), C, C, nat.ptr(S_in), C, float(s_alpha), float(s_beta),
+                                                          nat.ptr(S_out), C, float(y_beta), nat.ptr(Y_out), C,
+                                                          nat.ACT_SKIP_EMPTY if skip_empty else nat.ACT_NONE, int(order), nat.current_stream()))
+            return
         nat.check(nat.lib().gnx_spmm_dropped_back(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, 1 if prescaled else 0, nat.ptr(D_next),
                                                   nat.ptr(X), C, C, nat.ptr(S_in), C, float(s_alpha), float(s_beta), nat.ptr(S_out), C,
                                                   float(y_beta), nat.ptr(Y_out), C, nat.ACT_SKIP_EMPTY if skip_empty else nat.ACT_NONE,
                                                   nat.current_stream()))
 
 
-def _backward_chained(adjs, g, a):
+def _backward_chained(adjs, g, a, relabelled=False):
     """dH0 of K chained training iterations for the upstream gradient ``g``: g_k = (1-a) A_k^T g_{k+1}, dH0 = g_0 + a (g_1 + ... +
     g_K), as K calls of gnx_spmm_dropped_back -- every call adds its g_k to the running sum in its epilogue and hands the next call
     its operand pre-scaled by that call's column scale, so no gradient of an iteration is kept, no per-entry scale is gathered
-    and no separate summation pass exists."""
+    and no separate summation pass exists.  ``relabelled`` (K > 1): the operand handed from call to call lives in the graph's gather
+    order (gnx_spmm_dropped_back_ord: the first call gathers ``g`` as it is, the running sum stays in the caller's order); same bits."""
     K = len(adjs)
     g = _as_f32_rows(g).contiguous()
     S = torch.empty_like(g)
@@ -370,9 +406,10 @@ def _backward_chained(adjs, g, a):
     for k in range(K - 1, -1, -1):
         first, last = k == K - 1, k == 0
         Y = None if last else torch.empty_like(g)
+        order = ((0 if first else nat.ORD_X) | (0 if last else nat.ORD_OUT)) if relabelled else None
         # rows without entries: their g_k is 0 -- after the first call their sum is final and their Y row is never gathered
         _launch_back(adjs[k], X, not first, None if last else adjs[k - 1].D, g if first else S, a if first else 1.0,
-                     (1.0 - a) if last else a * (1.0 - a), S, 1.0 - a, Y, skip_empty=not first)
+                     (1.0 - a) if last else a * (1.0 - a), S, 1.0 - a, Y, skip_empty=not first, order=order)
         X = Y
     return S
 
@@ -570,8 +607,9 @@ class _PPRLoop(torch.autograd.Function):
     masked by H_k > 0 before it goes through A_k^T: gz_k = g_k * (H_k > 0), g_{k-1} = (1-a) A_k^T gz_k, dH0 = g_0 + a sum_k gz_k."""
 
     @staticmethod
-    def forward(ctx, H0, make_adj, a, K, relu=False, storage=torch.float32):
+    def forward(ctx, H0, make_adj, a, K, relu=False, storage=torch.float32, gather_order="caller"):
         ctx.make_adj, ctx.a, ctx.K, ctx.relu = make_adj, a, K, relu
+        ctx.relabelled = False
         act = nat.ACT_RELU if relu else nat.ACT_NONE
         H0 = _as_f32_rows(H0).contiguous()
         ctx.C = C = H0.shape[1]
@@ -597,11 +635,14 @@ class _PPRLoop(torch.autograd.Function):
             adjs = made if made is not None else [first] + [make_adj(k, False) for k in range(1, K)]
             chained = all(isinstance(adj, DroppedAdjacency) and adj.graph is first.graph for adj in adjs)
             ctx.chained = chained and first.graph.n_rows == first.graph.n_cols
+            # the iterate handed from launch to launch in the graph's gather order (gnx_spmm_dropped_chained_ord): the same bits
+            ctx.relabelled = relabelled = ctx.chained and _train_gather_applies(gather_order, first.graph, H0.shape[1])
             for k, adj in enumerate(adjs):
                 if chained:
+                    order = ((nat.ORD_X if k > 0 else 0) | (nat.ORD_OUT if k + 1 < K else 0)) if relabelled else None
                     # (rows without entries are a * H0 in the result and gathered by nobody: only the last iteration writes them)
                     H = _launch_chained(adj, H, H0, 1.0 - a, a, prescaled=k > 0, D_next=adjs[k + 1].D if k + 1 < K else None,
-                                        skip_empty=k + 1 < K)
+                                        skip_empty=k + 1 < K, order=order)
                 else:
                     H = _launch(adj, H, H0, 1.0 - a, a, nat.ACT_NONE)
         else:
@@ -622,13 +663,13 @@ class _PPRLoop(torch.autograd.Function):
             if not all(isinstance(adj, DroppedAdjacency) for adj in adjs):
                 raise Exception("ppr_loop: the bf16 forward ran on fused adjacencies, the backward was handed others")
             gH0 = _backward_chained_bf16(adjs, _padded(_as_f32_rows(g).contiguous(), friendly_width_bf16(ctx.C, g.shape[0])), ctx.a)
-            return (gH0 if gH0.shape[1] == ctx.C else gH0[:, :ctx.C].contiguous()), None, None, None, None, None
+            return (gH0 if gH0.shape[1] == ctx.C else gH0[:, :ctx.C].contiguous()), None, None, None, None, None, None
         g = _padded(g.contiguous(), friendly_width(ctx.C, g.shape[0]))
         if getattr(ctx, "chained", False):
             adjs = [ctx.make_adj(k, True) for k in range(ctx.K)]
             if all(isinstance(adj, DroppedAdjacency) for adj in adjs):
-                gH0 = _backward_chained(adjs, g, ctx.a)
-                return (gH0 if gH0.shape[1] == ctx.C else gH0[:, :ctx.C].contiguous()), None, None, None, None, None
+                gH0 = _backward_chained(adjs, g, ctx.a, relabelled=ctx.relabelled)
+                return (gH0 if gH0.shape[1] == ctx.C else gH0[:, :ctx.C].contiguous()), None, None, None, None, None, None
         outs = ctx.saved_tensors if ctx.relu else None
         room = int(0.1 * torch.cuda.get_device_properties(g.device).total_memory) // max(g.numel() * 4, 1)
         limit = max(2, min(LINCOMB_TERMS - 1, room))
@@ -642,7 +683,7 @@ class _PPRLoop(torch.autograd.Function):
             g = _launch(ctx.make_adj(k, True), g, None, 1.0 - ctx.a, 0.0, nat.ACT_NONE, transposed=True)
         pending.append((g, 1.0))
         gH0 = linear_combination(([(total, 1.0)] if total is not None else []) + pending)
-        return (gH0 if gH0.shape[1] == ctx.C else gH0[:, :ctx.C].contiguous()), None, None, None, None, None
+        return (gH0 if gH0.shape[1] == ctx.C else gH0[:, :ctx.C].contiguous()), None, None, None, None, None, None
 
 
 LINCOMB_TERMS = 16
@@ -670,7 +711,51 @@ def linear_combination(terms) -> torch.Tensor:
     return out
 
 
-def ppr_loop(make_adj, H0: torch.Tensor, a: float, iterations: int, relu: bool = False, storage=torch.float32) -> torch.Tensor:
+GATHER_ORDERS = ("caller", "relabelled", "auto")
+
+# Training (ppr_loop gather_order="auto"): the allowance of the relabelled operand order, set from tools/train_gather_bench.py
+# (profiles/NOTES.md "Gather order of the training loops"): a launch width (the padded row width the loop runs at) / graph size gets
+# the relabelled order only where its K = 10 step measured faster than the caller-order step of the same run by more than the spread
+# of the two medians (its upper quartile below the caller step's lower quartile).  Measured (R-MAT, 10 entries per vertex, C = 7, 8,
+# 16, 32, 40, 64): NO width gains -- at 10^7 vertices the relabelled step is 4-14 % slower (C = 7 33.9 -> 37.3 ms, C = 32 35.6 ->
+# 41.5, C = 64 55.8 -> 59.0), at 10^6 vertices 1-6 % slower: the scattered result write and the second index stream cost more than
+# the shared hub lines save.  The allowance is therefore EMPTY (maximum width 0) and "auto" is "caller"; "relabelled" stays
+# available explicitly (bitwise equal results)
+TRAIN_GATHER_MAX_WIDTH = 0
+TRAIN_GATHER_MIN_ROWS = 1_000_000
+
+
+def _gather_order(gather_order) -> str:
+    if gather_order not in GATHER_ORDERS:
+        raise Exception(f"gather_order must be one of {GATHER_ORDERS}, not {gather_order!r}")
+    return gather_order
+
+
+def resolve_gather_order(gather_order, n_rows, width) -> str:
+    """"caller" or "relabelled": what ``gather_order`` means for a graph of ``n_rows`` vertices at a launch width of ``width``
+    floats -- "auto" takes the relabelled order only inside the measured allowance (TRAIN_GATHER_MAX_WIDTH / TRAIN_GATHER_MIN_ROWS)."""
+    if _gather_order(gather_order) != "auto":
+        return gather_order
+    return "relabelled" if width <= TRAIN_GATHER_MAX_WIDTH and n_rows >= TRAIN_GATHER_MIN_ROWS else "caller"
+
+
+def _train_gather_applies(gather_order, graph, width) -> bool:
+    """Whether the chained f32 loop over ``graph`` hands its iterate on in the graph's gather order: asked for (or allowed) and the
+    handle can have one (no row window: a numbering that carries locality keeps it)."""
+    return resolve_gather_order(gather_order, graph.n_rows, width) == "relabelled" and not getattr(graph, "row_window", 0)
+
+
+def may_use_train_gather(graph, gather_order) -> bool:
+    """Whether a training loop over ``graph`` under ``gather_order`` can take the relabelled operand order at SOME width (what a
+    captured training step reserves for: DeviceGraph.reserve(train_gather=True))."""
+    if _gather_order(gather_order) == "caller" or graph.n_rows != graph.n_cols or graph.nnz_entries != graph.nnz \
+            or getattr(graph, "row_window", 0):
+        return False
+    return gather_order == "relabelled" or (TRAIN_GATHER_MAX_WIDTH > 0 and graph.n_rows >= TRAIN_GATHER_MIN_ROWS)
+
+
+def ppr_loop(make_adj, H0: torch.Tensor, a: float, iterations: int, relu: bool = False, storage=torch.float32,
+             gather_order="caller") -> torch.Tensor:
     """``iterations`` fused PPR steps starting from H0; ``make_adj(k, for_backward)`` returns the Adjacency
     of iteration k (called again, with the same k and for_backward=True, during the backward, where only the
     transposed-order values are needed).  ``relu``: relu after every step (filter.py:22).
@@ -681,9 +766,16 @@ def ppr_loop(make_adj, H0: torch.Tensor, a: float, iterations: int, relu: bool =
     backward gathers bf(g), then bf((1-a) acc * D_{k-1}), while dH0 is summed in f32 from unrounded addends.  Masks, degree scales,
     weights, sums, H0 and the mix stay f32; two runs give the same bits.  bf16 is an allowance: the loop keeps f32 -- bit for bit
     the default -- with ``relu``, with any other adjacency, at K = 0, below BF16_TRAIN_MIN_WIDTH columns and on graphs of fewer than
-    BF16_TRAIN_MIN_ROWS vertices (launch-bound steps, where bf16 measured slower)."""
+    BF16_TRAIN_MIN_ROWS vertices (launch-bound steps, where bf16 measured slower).
+    ``gather_order``: where the chained f32 loop applies (K > 1, every adjacency a DroppedAdjacency of one square graph without
+    duplicate entries, no relu, f32 storage), ``"relabelled"`` keeps the iterate -- and, in the backward, the gradient handed from
+    call to call -- in the graph's gather order between the launches (gnx_spmm_dropped_chained_ord / gnx_spmm_dropped_back_ord: hub
+    rows share 128-byte lines): rows, entry order, masks, weights and sums stay the caller's, H0 enters and H_K / dH0 leave in the
+    caller's order, and the result is bit for bit that of ``"caller"`` (today's path, the default here).  Everywhere else
+    ``"relabelled"`` takes today's path.  ``"auto"`` takes the relabelled order inside the measured allowance only
+    (TRAIN_GATHER_MAX_WIDTH, TRAIN_GATHER_MIN_ROWS)."""
     _bf16(storage)
-    return _PPRLoop.apply(H0, make_adj, float(a), int(iterations), bool(relu), storage)
+    return _PPRLoop.apply(H0, make_adj, float(a), int(iterations), bool(relu), storage, _gather_order(gather_order))
 
 
 class _SpMMBiasAct(torch.autograd.Function):

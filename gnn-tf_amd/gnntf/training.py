@@ -13,6 +13,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import sparse
 from .params import default_device
 from .protocol import Layered
 
@@ -235,6 +236,9 @@ class Trainable(Layered):
         graphs = self._dropout_graphs()
         for g in graphs:
             g.set_dropout_counter(counter)
+        # the gather order and gather columns of the training loops (GNN.train_gather_order), built before anything is recorded
+        if hasattr(self, "graph") and sparse.may_use_train_gather(self.graph, getattr(self, "train_gather_order", "caller")):
+            self.graph.reserve(1, train_gather=True)
 
         def train_step(opt):
             with self:

@@ -57,7 +57,8 @@ const char *gnx_last_error(void);
  * 0.8 adds the bf16 storage entries of the fused training loops (gnx_spmm_dropped_chained_bf16, gnx_spmm_dropped_back_bf16) and
  * changes nothing else; 0.9 adds the bf16 storage entries of the vertex-partitioned path (gnx_spmm_rows_bf16, gnx_halo_pack_bf16,
  * gnx_halo_exchange_bf16), likewise.  gnx_gcnii_step_bf16 was added WITHIN 0.9 (no existing signature changed, the number stays
- * 900): a client that wants it probes the library for the symbol (dlsym) instead of comparing versions. */
+ * 900): a client that wants it probes the library for the symbol (dlsym) instead of comparing versions.  So were the gather-order
+ * entries (gnx_graph_gather_order, gnx_spmm_dropped_chained_ord, gnx_spmm_dropped_back_ord, GNX_RESERVE_TRAIN_GATHER), likewise. */
 #define GNX_ABI_VERSION 900
 int gnx_version(void);
 
@@ -109,12 +110,15 @@ int gnx_graph_normalize(gnx_graph_t g, int normalized, int add_eye, float dropou
 /* gnx_graph_reserve: builds, NOW, what the compute entries otherwise build on first use, sized for feature rows of up to C floats:
  * the slab the long rows' partial sums go through (every entry), with GNX_RESERVE_TRANSPOSED the transposed structure (gnx_spmm_t,
  * gnx_spmm_dropped(transposed), the column sums of a training step), with GNX_RESERVE_K_LOOP the relabelled copy
- * gnx_appnp_propagate runs narrow widths on.  Those lazy builds allocate and synchronise, which a stream that is being captured
- * into a hipGraph must not see: a compute entry that would have to grow something under capture fails with
+ * gnx_appnp_propagate runs narrow widths on, with
+ * GNX_RESERVE_TRAIN_GATHER what gnx_spmm_dropped_chained_ord / gnx_spmm_dropped_back_ord walk (the gather order and the gather
+ * columns of the matrix and of the transposed structure; implies GNX_RESERVE_TRANSPOSED; GNX_ERR_UNSUPPORTED on a vertex block, a
+ * handle with duplicate entries or a handle with a row window).  Those lazy builds allocate and synchronise, which a stream that is
+ * being captured into a hipGraph must not see: a compute entry that would have to grow something under capture fails with
  * GNX_ERR_UNSUPPORTED and a message naming this call.  Reserve (or run the launch once eagerly) BEFORE capturing; replays then
  * touch no allocator.  ("an optional caller-provided workspace" -- the workspace stays owned by the handle, the
  * caller decides when it is sized.)  Nothing in the reference corresponds: TensorFlow eager allocates per op. */
-enum { GNX_RESERVE_TRANSPOSED = 1, GNX_RESERVE_K_LOOP = 2 };
+enum { GNX_RESERVE_TRANSPOSED = 1, GNX_RESERVE_K_LOOP = 2, GNX_RESERVE_TRAIN_GATHER = 4 };
 int gnx_graph_reserve(gnx_graph_t g, int64_t C, int flags, void *stream);
 
 /* gnx_graph_enable_entry_dropout: builds, NOW, what the fused training entries (gnx_spmm_dropped, gnx_spmm_dropped_chained,
@@ -264,6 +268,42 @@ int gnx_spmm_dropped_back(gnx_graph_t g, const float *d_D, float dropout_p, uint
                           const float *d_D_next, const float *d_X, int64_t ldx, int64_t C, const float *d_S_in, int64_t lds_in,
                           float s_alpha, float s_beta, float *d_S_out, int64_t lds_out, float y_beta, float *d_Y_out, int64_t ldy,
                           int act, void *stream);
+
+/* ---- the training loops over the handle's gather order ---------------------------------------------------------------------
+ * At narrow widths a gather moves a whole 128-byte line for a 28..256-byte row, so what a training launch costs is how often that
+ * line is found in a cache; in the caller's numbering the rows that receive most gathers (the hubs) are scattered.  The GATHER
+ * ORDER of a square handle is the order gnx_appnp_propagate numbers its relabelled copy in: degree bins, heaviest first, and inside
+ * a bin the vertices by the degree rank of their most popular neighbour -- hub rows share lines, a hub's leaves sit in consecutive
+ * lines.  The two entries below keep rows, per-row entry order, masks, weights, scales and sums the caller's; only the matrix that
+ * is GATHERED (and the one the next launch of the loop gathers) is stored in gather order, reached through a second column array
+ * of 4 bytes per entry (built on first use or by gnx_graph_reserve(GNX_RESERVE_TRAIN_GATHER); under capture without it:
+ * GNX_ERR_UNSUPPORTED naming gnx_graph_reserve).  Per row the same fused multiply-adds on the same values in the same order: the
+ * results are BITWISE those of gnx_spmm_dropped_chained / gnx_spmm_dropped_back, whatever `order` says.
+ * gnx_graph_gather_order: borrowed device pointers (valid until destroy or gnx_graph_set_row_window), either may be NULL:
+ *   d_order int32 [n]: position in the gather order -> vertex; d_rank int32 [n]: vertex -> position.  "X stored in gather order"
+ *   means row i of the buffer holds vertex d_order[i].  Builds the order on first use (allocates and synchronises the default
+ *   stream: not under capture).  Square graphs; GNX_ERR_UNSUPPORTED on a handle with a row window.
+ * `order` = an OR of
+ *   GNX_ORD_X    the rows of d_X are stored in gather order;
+ *   GNX_ORD_OUT  d_out (gnx_spmm_dropped_chained_ord) or d_Y_out (gnx_spmm_dropped_back_ord) is written in gather order.
+ * Everything else -- d_H0, d_D, d_D_next, d_S_in / d_S_out -- is indexed by the caller's vertex ids; every other argument is the
+ * namesake's.  order == 0 IS the namesake.  A K-iteration forward loop: iteration 0 passes GNX_ORD_OUT with X = H0 as the caller
+ * holds it, the middle iterations both flags, the last one GNX_ORD_X, so H_K lands in the caller's order and no permute pass exists
+ * at either end.  The backward loop mirrors it: the first call gathers the upstream gradient in the caller's order and writes its
+ * Y_out in gather order, the last call has no Y_out.  GNX_ACT_SKIP_EMPTY keeps its rules.  Square stand-alone handles without
+ * duplicate entries only: a vertex block (gnx_graph_set_block), a handle with duplicate entries and a handle with a row window
+ * (its numbering carries locality already) get GNX_ERR_UNSUPPORTED and a message saying which.  gnx_graph_last_kernel reports the
+ * training names with "_ord" appended and the hub launches named ("spmm_group8_drop_ord", "spmm_group16+long_drop_ord").
+ * Nothing in the reference corresponds. */
+enum { GNX_ORD_X = 1, GNX_ORD_OUT = 2 };
+int gnx_graph_gather_order(gnx_graph_t g, const int32_t **d_order, const int32_t **d_rank);
+int gnx_spmm_dropped_chained_ord(gnx_graph_t g, const float *d_D, float dropout_p, uint64_t seed, uint64_t stream_id, int x_prescaled,
+                                 const float *d_D_next, const float *d_X, int64_t ldx, int64_t C, const float *d_H0, int64_t ldh0,
+                                 float beta, float alpha, int act, float *d_out, int64_t ldo, int order, void *stream);
+int gnx_spmm_dropped_back_ord(gnx_graph_t g, const float *d_D, float dropout_p, uint64_t seed, uint64_t stream_id, int x_prescaled,
+                              const float *d_D_next, const float *d_X, int64_t ldx, int64_t C, const float *d_S_in, int64_t lds_in,
+                              float s_alpha, float s_beta, float *d_S_out, int64_t lds_out, float y_beta, float *d_Y_out, int64_t ldy,
+                              int act, int order, void *stream);
 
 /* gnx_spmm_rows: the fused step for a handle that holds only a SUBSET of the output rows (the interior or the
  * boundary rows of a vertex block, compacted): result row r lands in out[d_rows[r], :] and mixes in
