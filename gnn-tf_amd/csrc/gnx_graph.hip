@@ -6,6 +6,9 @@
 
 #include "gnx_internal.h"
 #include <algorithm>
+#include <memory>
+#include <type_traits>
+#include <utility>
 
 #include <rocprim/rocprim.hpp>
 
@@ -19,15 +22,6 @@ void set_error(const char *fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
-
-// small RAII holder so early returns do not leak temporaries
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-    template <class T> T *as() { return static_cast<T *>(p); }
-    void *release() { void *q = p; p = nullptr; return q; }
-};
 
 static inline unsigned blocks_for(int64_t n, int bs = 256) { return (unsigned)((n + bs - 1) / bs); }
 
@@ -262,33 +256,73 @@ __global__ void k_split_tkeys(const uint64_t *__restrict__ keys, int64_t nnz, in
 }
 
 // ---- helpers -------------------------------------------------------------------------------
-void free_csr(Csr &m) {
-    if (m.rowptr) (void)hipFree(m.rowptr);
-    if (m.colidx) (void)hipFree(m.colidx);
-    if (m.long_rows) (void)hipFree(m.long_rows);
-    if (m.long_chunk_ptr) (void)hipFree(m.long_chunk_ptr);
-    if (m.chunk_long) (void)hipFree(m.chunk_long);
-    if (m.chunk_order) (void)hipFree(m.chunk_order);
-    if (m.row_order) (void)hipFree(m.row_order);
-    if (m.nonempty_rows) (void)hipFree(m.nonempty_rows);
-    if (m.slot_beg) (void)hipFree(m.slot_beg);
-    if (m.slot_cnt) (void)hipFree(m.slot_cnt);
-    m = Csr();
+#define GNX_TRY(...)                                                                    \
+    do {                                                                                \
+        const int _rc = (__VA_ARGS__);                                                  \
+        if (_rc != GNX_OK) return _rc;                                                  \
+    } while (0)
+
+// rocprim's calling convention: with a null temporary a call only reports the bytes it needs, the same call again with that many
+// does the work.  `call(tmp, bytes)` is that call.  Waits for the work, because the temporary goes when this returns.
+template <class Call>
+static int with_temporary(const char *what, Call call, hipStream_t s) {
+    DevArray<char> tmp;
+    size_t bytes = 0;
+    hipError_t e = call(nullptr, bytes);
+    if (e == hipSuccess) e = tmp.alloc(bytes);
+    if (e == hipSuccess) e = call(tmp.get(), bytes);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        set_error("rocprim::%s failed: %s", what, hipGetErrorString(e));
+        return GNX_ERR_HIP;
+    }
+    return GNX_OK;
 }
 
-// Everything build_long_plan makes (the structure itself stays): for a rebuild under another row order
-void free_plan(Csr &m) {
-    if (m.long_rows) (void)hipFree(m.long_rows);
-    if (m.long_chunk_ptr) (void)hipFree(m.long_chunk_ptr);
-    if (m.chunk_long) (void)hipFree(m.chunk_long);
-    if (m.chunk_order) (void)hipFree(m.chunk_order);
-    if (m.row_order) (void)hipFree(m.row_order);
-    if (m.nonempty_rows) (void)hipFree(m.nonempty_rows);
-    if (m.slot_beg) (void)hipFree(m.slot_beg);
-    if (m.slot_cnt) (void)hipFree(m.slot_cnt);
-    m.long_rows = nullptr; m.long_chunk_ptr = nullptr; m.chunk_long = nullptr; m.chunk_order = nullptr; m.row_order = nullptr;
-    m.nonempty_rows = nullptr; m.slot_beg = nullptr; m.slot_cnt = nullptr;
-    m.n_long = 0; m.n_chunks = 0; m.n_nonempty = 0;
+// Stable ascending sort of n (key, value) pairs by key bits [0, end_bit).  V is const where the caller's own array is sorted.
+template <class K, class V>
+static int sort_pairs(K *keys_in, K *keys_out, V *vals_in, std::remove_const_t<V> *vals_out, int64_t n, unsigned end_bit, hipStream_t s) {
+    return with_temporary("radix_sort_pairs", [&](void *tmp, size_t &bytes) {
+        return rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u, end_bit, s);
+    }, s);
+}
+
+static int sort_keys(int32_t *keys_in, int32_t *keys_out, int64_t n, unsigned end_bit, hipStream_t s) {
+    return with_temporary("radix_sort_keys", [&](void *tmp, size_t &bytes) {
+        return rocprim::radix_sort_keys(tmp, bytes, keys_in, keys_out, (size_t)n, 0u, end_bit, s);
+    }, s);
+}
+
+template <class T>
+static int exclusive_scan(T *in, T *out, int64_t n, hipStream_t s) {   // sums, from 0
+    return with_temporary("exclusive_scan", [&](void *tmp, size_t &bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, in, out, (T)0, (size_t)n, rocprim::plus<T>(), s);
+    }, s);
+}
+
+static int inclusive_scan(int32_t *in, int32_t *out, int64_t n, hipStream_t s) {
+    return with_temporary("inclusive_scan", [&](void *tmp, size_t &bytes) {
+        return rocprim::inclusive_scan(tmp, bytes, in, out, (size_t)n, rocprim::plus<int32_t>(), s);
+    }, s);
+}
+
+// one value of a device array, waited for
+template <class T>
+static int fetch(T &host, const T *dev, hipStream_t s) {
+    GNX_HIP(hipMemcpyAsync(&host, dev, sizeof(T), hipMemcpyDeviceToHost, s));
+    GNX_HIP(hipStreamSynchronize(s));
+    return GNX_OK;
+}
+
+// m.row_order = the rows in stable ascending order of the key_bits-wide keys of type K that `make_keys(keys, ids)` launches
+template <class K, class MakeKeys>
+static int order_rows(Csr &m, unsigned key_bits, MakeKeys make_keys, hipStream_t s) {
+    DevArray<K> k0, k1;
+    DevArray<int32_t> ids;
+    GNX_HIP(k0.alloc(m.n_rows)); GNX_HIP(k1.alloc(m.n_rows)); GNX_HIP(ids.alloc(m.n_rows));
+    GNX_HIP(m.row_order.alloc(m.n_rows));
+    make_keys(k0.get(), ids.get());
+    return sort_pairs<K, int32_t>(k0, k1, ids, m.row_order, m.n_rows, key_bits, s);
 }
 
 int build_long_plan(Csr &m, hipStream_t s) {
@@ -298,128 +332,88 @@ int build_long_plan(Csr &m, hipStream_t s) {
     m.long_chunk = small ? SMALL_LONG_ROW : LONG_CHUNK;
     const int order_clamp = m.long_row < 65535 ? m.long_row : 65535;
     if (m.n_rows == 0) return GNX_OK;
+    const dim3 row_blocks(blocks_for(m.n_rows)), threads(256);
+    const unsigned bin_bits = bits_for((uint64_t)order_clamp + 1);
     if (m.order_window > 0) {   // degree bins inside windows of the caller's numbering
-        DevBuf k0, k1, ids, t;
-        const unsigned bin_bits = bits_for((uint64_t)order_clamp + 1);
         const uint64_t n_windows = (uint64_t)((m.n_rows + m.order_window - 1) / m.order_window);
         const unsigned key_bits = bin_bits + bits_for(n_windows + 1);
         GNX_CHECK_ARG(key_bits <= 32, "row window: %lld windows of %lld rows do not fit the order key", (long long)n_windows,
                       (long long)m.order_window);
-        GNX_HIP(k0.alloc(m.n_rows * 4)); GNX_HIP(k1.alloc(m.n_rows * 4)); GNX_HIP(ids.alloc(m.n_rows * sizeof(int32_t)));
-        GNX_HIP(hipMalloc((void **)&m.row_order, m.n_rows * sizeof(int32_t)));
-        hipLaunchKernelGGL(k_order_keys_windowed, dim3(blocks_for(m.n_rows)), dim3(256), 0, s, m.rowptr, m.n_rows, order_clamp, m.order_window,
-                           (uint32_t)n_windows, bin_bits, k0.as<uint32_t>(), ids.as<int32_t>());
-        size_t tb = 0;
-        GNX_HIP(rocprim::radix_sort_pairs(nullptr, tb, k0.as<uint32_t>(), k1.as<uint32_t>(), ids.as<int32_t>(), m.row_order,
-                                          (size_t)m.n_rows, 0u, key_bits, s));
-        GNX_HIP(t.alloc(tb));
-        GNX_HIP(rocprim::radix_sort_pairs(t.p, tb, k0.as<uint32_t>(), k1.as<uint32_t>(), ids.as<int32_t>(), m.row_order,
-                                          (size_t)m.n_rows, 0u, key_bits, s));
-        GNX_HIP(hipStreamSynchronize(s));
+        GNX_TRY(order_rows<uint32_t>(m, key_bits, [&](uint32_t *keys, int32_t *ids) {
+            hipLaunchKernelGGL(k_order_keys_windowed, row_blocks, threads, 0, s, m.rowptr, m.n_rows, order_clamp, m.order_window,
+                               (uint32_t)n_windows, bin_bits, keys, ids);
+        }, s));
     } else {   // degree-binned row order
-        DevBuf k0, k1, ids, t;
-        GNX_HIP(k0.alloc(m.n_rows * 2)); GNX_HIP(k1.alloc(m.n_rows * 2)); GNX_HIP(ids.alloc(m.n_rows * sizeof(int32_t)));
-        GNX_HIP(hipMalloc((void **)&m.row_order, m.n_rows * sizeof(int32_t)));
-        hipLaunchKernelGGL(k_order_keys, dim3(blocks_for(m.n_rows)), dim3(256), 0, s, m.rowptr, m.n_rows, order_clamp, k0.as<uint16_t>(),
-                           ids.as<int32_t>());
-        const unsigned key_bits = bits_for((uint64_t)order_clamp + 1);
-        size_t tb = 0;
-        GNX_HIP(rocprim::radix_sort_pairs(nullptr, tb, k0.as<uint16_t>(), k1.as<uint16_t>(), ids.as<int32_t>(), m.row_order,
-                                          (size_t)m.n_rows, 0u, key_bits, s));
-        GNX_HIP(t.alloc(tb));
-        GNX_HIP(rocprim::radix_sort_pairs(t.p, tb, k0.as<uint16_t>(), k1.as<uint16_t>(), ids.as<int32_t>(), m.row_order,
-                                          (size_t)m.n_rows, 0u, key_bits, s));
-        GNX_HIP(hipStreamSynchronize(s));
+        GNX_TRY(order_rows<uint16_t>(m, bin_bits, [&](uint16_t *keys, int32_t *ids) {
+            hipLaunchKernelGGL(k_order_keys, row_blocks, threads, 0, s, m.rowptr, m.n_rows, order_clamp, keys, ids);
+        }, s));
     }
     if (m.n_rows >= SMALL_ROWS) {   // big structures: the rows' entry ranges in slot order
-        GNX_HIP(hipMalloc((void **)&m.slot_beg, m.n_rows * sizeof(int64_t)));
-        GNX_HIP(hipMalloc((void **)&m.slot_cnt, m.n_rows * sizeof(int32_t)));
-        hipLaunchKernelGGL(k_slot_ptrs, dim3(blocks_for(m.n_rows)), dim3(256), 0, s, m.rowptr, m.row_order, m.n_rows, m.slot_beg, m.slot_cnt);
+        GNX_HIP(m.slot_beg.alloc(m.n_rows));
+        GNX_HIP(m.slot_cnt.alloc(m.n_rows));
+        hipLaunchKernelGGL(k_slot_ptrs, row_blocks, threads, 0, s, m.rowptr, m.row_order, m.n_rows, m.slot_beg, m.slot_cnt);
     }
     {   // rows with entries: they lead the order (heaviest first), the empty ones trail it
-        DevBuf count;
-        GNX_HIP(count.alloc(sizeof(unsigned long long)));
-        GNX_HIP(hipMemsetAsync(count.p, 0, sizeof(unsigned long long), s));
-        hipLaunchKernelGGL(k_count_nonempty, dim3(blocks_for(m.n_rows)), dim3(256), 0, s, m.rowptr, m.n_rows, count.as<unsigned long long>());
+        DevArray<unsigned long long> count;
+        GNX_HIP(count.alloc(1));
+        GNX_HIP(hipMemsetAsync(count, 0, sizeof(unsigned long long), s));
+        hipLaunchKernelGGL(k_count_nonempty, row_blocks, threads, 0, s, m.rowptr, m.n_rows, count);
         unsigned long long host = 0;
-        GNX_HIP(hipMemcpyAsync(&host, count.p, sizeof(host), hipMemcpyDeviceToHost, s));
-        GNX_HIP(hipStreamSynchronize(s));
+        GNX_TRY(fetch(host, count.get(), s));
         m.n_nonempty = (int64_t)host;
     }
     m.empty_rows_unreferenced = false;
     if (m.n_nonempty < m.n_rows) {
         if (m.n_nonempty > 0) {   // the rows with entries in ascending order: the leading slots of row_order, sorted by id
-            DevBuf t;
-            GNX_HIP(hipMalloc((void **)&m.nonempty_rows, m.n_nonempty * sizeof(int32_t)));
-            size_t tb = 0;
-            GNX_HIP(rocprim::radix_sort_keys(nullptr, tb, m.row_order, m.nonempty_rows, (size_t)m.n_nonempty, 0u, bits_for((uint64_t)m.n_rows), s));
-            GNX_HIP(t.alloc(tb));
-            GNX_HIP(rocprim::radix_sort_keys(t.p, tb, m.row_order, m.nonempty_rows, (size_t)m.n_nonempty, 0u, bits_for((uint64_t)m.n_rows), s));
-            GNX_HIP(hipStreamSynchronize(s));
+            GNX_HIP(m.nonempty_rows.alloc(m.n_nonempty));
+            GNX_TRY(sort_keys(m.row_order, m.nonempty_rows, m.n_nonempty, bits_for((uint64_t)m.n_rows), s));
         }
         if (m.n_rows == m.n_cols) {   // does any entry point at a row that has no entries itself?
-            DevBuf flag, count;
-            GNX_HIP(flag.alloc(m.n_rows)); GNX_HIP(count.alloc(sizeof(int)));
-            GNX_HIP(hipMemsetAsync(flag.p, 0, m.n_rows, s));
-            GNX_HIP(hipMemsetAsync(count.p, 0, sizeof(int), s));
-            if (m.nnz > 0) hipLaunchKernelGGL(k_mark_referenced, dim3(blocks_for(m.nnz)), dim3(256), 0, s, m.colidx, m.nnz, flag.as<uint8_t>());
-            hipLaunchKernelGGL(k_count_empty_referenced, dim3(blocks_for(m.n_rows)), dim3(256), 0, s, m.rowptr, m.n_rows, flag.as<uint8_t>(), count.as<int>());
+            DevArray<uint8_t> flag;
+            DevArray<int> count;
+            GNX_HIP(flag.alloc(m.n_rows)); GNX_HIP(count.alloc(1));
+            GNX_HIP(hipMemsetAsync(flag, 0, m.n_rows, s));
+            GNX_HIP(hipMemsetAsync(count, 0, sizeof(int), s));
+            if (m.nnz > 0) hipLaunchKernelGGL(k_mark_referenced, dim3(blocks_for(m.nnz)), threads, 0, s, m.colidx, m.nnz, flag);
+            hipLaunchKernelGGL(k_count_empty_referenced, row_blocks, threads, 0, s, m.rowptr, m.n_rows, flag, count);
             int host_count = 1;
-            GNX_HIP(hipMemcpyAsync(&host_count, count.p, sizeof(int), hipMemcpyDeviceToHost, s));
-            GNX_HIP(hipStreamSynchronize(s));
+            GNX_TRY(fetch(host_count, count.get(), s));
             m.empty_rows_unreferenced = host_count == 0;
         }
     }
     if (m.nnz == 0) return GNX_OK;
-    DevBuf flag, cnt, pos, cpos, tmp;
-    GNX_HIP(flag.alloc(m.n_rows * sizeof(int32_t)));
-    GNX_HIP(cnt.alloc(m.n_rows * sizeof(int64_t)));
-    GNX_HIP(pos.alloc(m.n_rows * sizeof(int32_t)));
-    GNX_HIP(cpos.alloc(m.n_rows * sizeof(int64_t)));
-    hipLaunchKernelGGL(k_flag_long, dim3(blocks_for(m.n_rows)), dim3(256), 0, s, m.rowptr, m.n_rows, m.long_row, m.long_chunk,
-                       flag.as<int32_t>(), cnt.as<int64_t>());
-    size_t t1 = 0, t2 = 0;
-    GNX_HIP(rocprim::exclusive_scan(nullptr, t1, flag.as<int32_t>(), pos.as<int32_t>(), (int32_t)0, (size_t)m.n_rows,
-                                    rocprim::plus<int32_t>(), s));
-    GNX_HIP(rocprim::exclusive_scan(nullptr, t2, cnt.as<int64_t>(), cpos.as<int64_t>(), (int64_t)0, (size_t)m.n_rows,
-                                    rocprim::plus<int64_t>(), s));
-    GNX_HIP(tmp.alloc(t1 > t2 ? t1 : t2));
-    GNX_HIP(rocprim::exclusive_scan(tmp.p, t1, flag.as<int32_t>(), pos.as<int32_t>(), (int32_t)0, (size_t)m.n_rows,
-                                    rocprim::plus<int32_t>(), s));
-    GNX_HIP(rocprim::exclusive_scan(tmp.p, t2, cnt.as<int64_t>(), cpos.as<int64_t>(), (int64_t)0, (size_t)m.n_rows,
-                                    rocprim::plus<int64_t>(), s));
+    DevArray<int32_t> flag, pos;
+    DevArray<int64_t> cnt, cpos;
+    GNX_HIP(flag.alloc(m.n_rows));
+    GNX_HIP(cnt.alloc(m.n_rows));
+    GNX_HIP(pos.alloc(m.n_rows));
+    GNX_HIP(cpos.alloc(m.n_rows));
+    hipLaunchKernelGGL(k_flag_long, row_blocks, threads, 0, s, m.rowptr, m.n_rows, m.long_row, m.long_chunk, flag, cnt);
+    GNX_TRY(exclusive_scan<int32_t>(flag, pos, m.n_rows, s));
+    GNX_TRY(exclusive_scan<int64_t>(cnt, cpos, m.n_rows, s));
     int32_t last_flag = 0, last_pos = 0;
     int64_t last_cnt = 0, last_cpos = 0;
-    GNX_HIP(hipMemcpyAsync(&last_flag, flag.as<int32_t>() + m.n_rows - 1, 4, hipMemcpyDeviceToHost, s));
-    GNX_HIP(hipMemcpyAsync(&last_pos, pos.as<int32_t>() + m.n_rows - 1, 4, hipMemcpyDeviceToHost, s));
-    GNX_HIP(hipMemcpyAsync(&last_cnt, cnt.as<int64_t>() + m.n_rows - 1, 8, hipMemcpyDeviceToHost, s));
-    GNX_HIP(hipMemcpyAsync(&last_cpos, cpos.as<int64_t>() + m.n_rows - 1, 8, hipMemcpyDeviceToHost, s));
-    GNX_HIP(hipStreamSynchronize(s));
+    GNX_TRY(fetch(last_flag, flag + (m.n_rows - 1), s));
+    GNX_TRY(fetch(last_pos, pos + (m.n_rows - 1), s));
+    GNX_TRY(fetch(last_cnt, cnt + (m.n_rows - 1), s));
+    GNX_TRY(fetch(last_cpos, cpos + (m.n_rows - 1), s));
     m.n_long = (int64_t)last_flag + last_pos;
     m.n_chunks = last_cnt + last_cpos;
     if (m.n_long == 0) return GNX_OK;
-    GNX_HIP(hipMalloc((void **)&m.long_rows, m.n_long * sizeof(int32_t)));
-    GNX_HIP(hipMalloc((void **)&m.long_chunk_ptr, (m.n_long + 1) * sizeof(int64_t)));
-    GNX_HIP(hipMalloc((void **)&m.chunk_long, m.n_chunks * sizeof(int32_t)));
-    hipLaunchKernelGGL(k_fill_long, dim3(blocks_for(m.n_rows)), dim3(256), 0, s, m.rowptr, m.n_rows, m.long_row, m.long_chunk,
-                       pos.as<int32_t>(), cpos.as<int64_t>(), m.long_rows, m.long_chunk_ptr, m.chunk_long);
+    GNX_HIP(m.long_rows.alloc(m.n_long));
+    GNX_HIP(m.long_chunk_ptr.alloc(m.n_long + 1));
+    GNX_HIP(m.chunk_long.alloc(m.n_chunks));
+    hipLaunchKernelGGL(k_fill_long, row_blocks, threads, 0, s, m.rowptr, m.n_rows, m.long_row, m.long_chunk, pos, cpos, m.long_rows,
+                       m.long_chunk_ptr, m.chunk_long);
     GNX_HIP(hipMemcpyAsync(m.long_chunk_ptr + m.n_long, &m.n_chunks, 8, hipMemcpyHostToDevice, s));
-    {   // column-window order of the chunks
-        DevBuf k0, k1, ids, t;
-        GNX_HIP(k0.alloc(m.n_chunks * 4)); GNX_HIP(k1.alloc(m.n_chunks * 4)); GNX_HIP(ids.alloc(m.n_chunks * 4));
-        GNX_HIP(hipMalloc((void **)&m.chunk_order, m.n_chunks * sizeof(int32_t)));
-        hipLaunchKernelGGL(k_chunk_keys, dim3(blocks_for(m.n_chunks)), dim3(256), 0, s, m.rowptr, m.colidx, m.long_rows,
-                           m.long_chunk_ptr, m.chunk_long, m.n_chunks, m.long_chunk, k0.as<uint32_t>(), ids.as<int32_t>());
-        size_t tb = 0;
-        GNX_HIP(rocprim::radix_sort_pairs(nullptr, tb, k0.as<uint32_t>(), k1.as<uint32_t>(), ids.as<int32_t>(), m.chunk_order,
-                                          (size_t)m.n_chunks, 0u, 32u, s));
-        GNX_HIP(t.alloc(tb));
-        GNX_HIP(rocprim::radix_sort_pairs(t.p, tb, k0.as<uint32_t>(), k1.as<uint32_t>(), ids.as<int32_t>(), m.chunk_order,
-                                          (size_t)m.n_chunks, 0u, 32u, s));
-        GNX_HIP(hipStreamSynchronize(s));
-    }
-    GNX_HIP(hipStreamSynchronize(s));
-    return GNX_OK;
+    // column-window order of the chunks
+    DevArray<uint32_t> k0, k1;
+    DevArray<int32_t> ids;
+    GNX_HIP(k0.alloc(m.n_chunks)); GNX_HIP(k1.alloc(m.n_chunks)); GNX_HIP(ids.alloc(m.n_chunks));
+    GNX_HIP(m.chunk_order.alloc(m.n_chunks));
+    hipLaunchKernelGGL(k_chunk_keys, dim3(blocks_for(m.n_chunks)), threads, 0, s, m.rowptr, m.colidx, m.long_rows, m.long_chunk_ptr,
+                       m.chunk_long, m.n_chunks, m.long_chunk, k0, ids);
+    return sort_pairs<uint32_t, int32_t>(k0, k1, ids, m.chunk_order, m.n_chunks, 32u, s);
 }
 
 // A stream that is being captured into a hipGraph must not see hipMalloc / hipFree / synchronisation: the lazily built parts of
@@ -439,100 +433,68 @@ bool stream_is_capturing(hipStream_t s) {
         }                                                                                                                        \
     } while (0)
 
-// The slab the long-row chunks of a launch write their partial sums to ([chunks x C] floats).  It only ever grows; growing frees
-// and allocates (an implicit device synchronisation), which is why it never happens under capture (gnx_graph_reserve sizes it
-// ahead of time for the widest C a client will use).
+// A slab that only ever grows; growing frees, then allocates (one slab at the peak; an implicit device synchronisation), which is why
+// it never happens under capture.
+static int grow_slab(DevArray<float> &slab, size_t &held_bytes, size_t bytes) {
+    held_bytes = 0;
+    GNX_HIP(slab.alloc((bytes + sizeof(float) - 1) / sizeof(float)));
+    held_bytes = bytes;
+    return GNX_OK;
+}
+
+// The slab the long-row chunks of a launch write their partial sums to ([chunks x C] floats), grown on demand (gnx_graph_reserve
+// sizes it ahead of time for the widest C a client will use).
 int ensure_partial(gnx_graph *g, size_t bytes, hipStream_t s) {
     if (bytes <= g->partial_bytes) return GNX_OK;
     GNX_NOT_WHILE_CAPTURING(s, "the long-row slab of this handle");
-    if (g->partial) (void)hipFree(g->partial);
-    g->partial = nullptr; g->partial_bytes = 0;
-    GNX_HIP(hipMalloc((void **)&g->partial, bytes));
-    g->partial_bytes = bytes;
-    return GNX_OK;
-}
-
-static void drop_transpose(gnx_graph *g) {
-    free_csr(g->t);
-    if (g->t_perm) (void)hipFree(g->t_perm);
-    if (g->t_vals) (void)hipFree(g->t_vals);
-    if (g->t_raw) (void)hipFree(g->t_raw);
-    if (g->t_rowidx) (void)hipFree(g->t_rowidx);
-    if (g->t_mask) (void)hipFree(g->t_mask);
-    g->t_perm = nullptr; g->t_vals = nullptr; g->t_raw = nullptr; g->t_rowidx = nullptr; g->t_mask = nullptr;
-    g->has_t = false;
-}
-
-int ensure_transpose(gnx_graph *g, hipStream_t s) {
-    if (g->has_t) return GNX_OK;
-    GNX_NOT_WHILE_CAPTURING(s, "the transposed structure of this handle");
-    struct Undo { gnx_graph *g; ~Undo() { if (g && !g->has_t) drop_transpose(g); } } undo{g};   // no half-built state on failure
-    const Csr &a = g->a;
-    Csr &t = g->t;
-    t.n_rows = a.n_cols; t.n_cols = a.n_rows; t.nnz = a.nnz;
-    t.order_window = a.n_rows == a.n_cols ? a.order_window : 0;     // a square graph's columns share the rows' numbering
-    GNX_HIP(hipMalloc((void **)&t.rowptr, (t.n_rows + 1) * sizeof(int64_t)));
-    GNX_HIP(hipMalloc((void **)&t.colidx, (t.nnz ? t.nnz : 1) * sizeof(int32_t)));
-    GNX_HIP(hipMalloc((void **)&g->t_perm, (t.nnz ? t.nnz : 1) * sizeof(int32_t)));
-    GNX_HIP(hipMalloc((void **)&g->t_vals, (t.nnz ? t.nnz : 1) * sizeof(float)));
-    GNX_HIP(hipMalloc((void **)&g->t_raw, (t.nnz ? t.nnz : 1) * sizeof(float)));
-    if (t.nnz == 0) {
-        GNX_HIP(hipMemsetAsync(t.rowptr, 0, (t.n_rows + 1) * sizeof(int64_t), s));
-        GNX_HIP(hipStreamSynchronize(s));
-        int rc0 = build_long_plan(t, s);
-        if (rc0 != GNX_OK) return rc0;
-        g->has_t = true;
-        return GNX_OK;
-    }
-    DevBuf k0, k1, p0, tmp;
-    GNX_HIP(k0.alloc(t.nnz * 8)); GNX_HIP(k1.alloc(t.nnz * 8));
-    GNX_HIP(p0.alloc(t.nnz * 4));
-    GNX_HIP(hipMalloc((void **)&g->t_rowidx, t.nnz * sizeof(int32_t)));
-    hipLaunchKernelGGL(k_make_tkeys, dim3(blocks_for(t.nnz)), dim3(256), 0, s, g->rowidx, a.colidx, a.nnz, a.n_rows,
-                       k0.as<uint64_t>(), p0.as<int32_t>());
-    const unsigned end_bit = bits_for((uint64_t)a.n_rows * (uint64_t)a.n_cols);
-    size_t tb = 0;
-    GNX_HIP(rocprim::radix_sort_pairs(nullptr, tb, k0.as<uint64_t>(), k1.as<uint64_t>(), p0.as<int32_t>(), g->t_perm,
-                                      (size_t)t.nnz, 0u, end_bit, s));
-    GNX_HIP(tmp.alloc(tb));
-    GNX_HIP(rocprim::radix_sort_pairs(tmp.p, tb, k0.as<uint64_t>(), k1.as<uint64_t>(), p0.as<int32_t>(), g->t_perm,
-                                      (size_t)t.nnz, 0u, end_bit, s));
-    hipLaunchKernelGGL(k_split_tkeys, dim3(blocks_for(t.nnz)), dim3(256), 0, s, k1.as<uint64_t>(), t.nnz, a.n_rows,
-                       g->t_rowidx, t.colidx);
-    hipLaunchKernelGGL(k_lower_bound_rows, dim3(blocks_for(t.n_rows + 1)), dim3(256), 0, s, g->t_rowidx, t.nnz,
-                       t.n_rows, t.rowptr);
-    hipLaunchKernelGGL(k_permute_vals, dim3(blocks_for(t.nnz)), dim3(256), 0, s, g->raw_vals, g->t_perm, t.nnz, g->t_raw);
-    GNX_HIP(hipStreamSynchronize(s));
-    int rc = build_long_plan(t, s);
-    if (rc != GNX_OK) return rc;
-    g->has_t = true;
-    return GNX_OK;
-}
-
-static void drop_relabel(gnx_graph *g) {
-    free_csr(g->r);
-    if (g->r_perm) (void)hipFree(g->r_perm);
-    if (g->r_vals) (void)hipFree(g->r_vals);
-    g->r_perm = nullptr; g->r_vals = nullptr;
-    g->has_r = false;
-}
-
-// the gather order and the per-entry gather columns (the relabelled copy, which is numbered in that order, goes first)
-static void drop_gather_order(gnx_graph *g) {
-    if (g->go_order) (void)hipFree(g->go_order);
-    if (g->go_rank) (void)hipFree(g->go_rank);
-    if (g->a_gcol) (void)hipFree(g->a_gcol);
-    if (g->t_gcol) (void)hipFree(g->t_gcol);
-    g->go_order = nullptr; g->go_rank = nullptr; g->a_gcol = nullptr; g->t_gcol = nullptr;
+    return grow_slab(g->partial, g->partial_bytes, bytes);
 }
 
 int ensure_relabel_features(gnx_graph *g, size_t bytes, hipStream_t s) {
     if (bytes <= g->r_feat_bytes) return GNX_OK;
     GNX_NOT_WHILE_CAPTURING(s, "the feature scratch of this handle's relabelled copy");
-    if (g->r_feat) (void)hipFree(g->r_feat);
-    g->r_feat = nullptr; g->r_feat_bytes = 0;
-    GNX_HIP(hipMalloc((void **)&g->r_feat, bytes));
-    g->r_feat_bytes = bytes;
+    return grow_slab(g->r_feat, g->r_feat_bytes, bytes);
+}
+
+// Dropping a lazy part = assigning a fresh one (the parts: gnx_internal.h).  The gather order and the per-entry gather columns go
+// whenever the relabelled copy, which is numbered in that order, goes.
+static void drop_transpose(gnx_graph *g) { static_cast<TransposedPart &>(*g) = TransposedPart(); }
+static void drop_relabel(gnx_graph *g) { static_cast<RelabelledPart &>(*g) = RelabelledPart(); }
+static void drop_gather_order(gnx_graph *g) { static_cast<GatherOrderPart &>(*g) = GatherOrderPart(); }
+
+// Built aside and moved into the handle when complete: no half-built state on failure.
+int ensure_transpose(gnx_graph *g, hipStream_t s) {
+    if (g->has_t) return GNX_OK;
+    GNX_NOT_WHILE_CAPTURING(s, "the transposed structure of this handle");
+    const Csr &a = g->a;
+    TransposedPart part;
+    Csr &t = part.t;
+    t.n_rows = a.n_cols; t.n_cols = a.n_rows; t.nnz = a.nnz;
+    t.order_window = a.n_rows == a.n_cols ? a.order_window : 0;     // a square graph's columns share the rows' numbering
+    GNX_HIP(t.rowptr.alloc(t.n_rows + 1));
+    GNX_HIP(t.colidx.alloc(t.nnz));
+    GNX_HIP(part.t_perm.alloc(t.nnz));
+    GNX_HIP(part.t_vals.alloc(t.nnz));
+    GNX_HIP(part.t_raw.alloc(t.nnz));
+    DevArray<uint64_t> k0, k1;
+    DevArray<int32_t> p0;
+    if (t.nnz == 0) {
+        GNX_HIP(hipMemsetAsync(t.rowptr, 0, (t.n_rows + 1) * sizeof(int64_t), s));
+    } else {
+        const dim3 entry_blocks(blocks_for(t.nnz)), threads(256);
+        GNX_HIP(k0.alloc(t.nnz)); GNX_HIP(k1.alloc(t.nnz));
+        GNX_HIP(p0.alloc(t.nnz));
+        GNX_HIP(part.t_rowidx.alloc(t.nnz));
+        hipLaunchKernelGGL(k_make_tkeys, entry_blocks, threads, 0, s, g->rowidx, a.colidx, a.nnz, a.n_rows, k0, p0);
+        GNX_TRY(sort_pairs<uint64_t, int32_t>(k0, k1, p0, part.t_perm, t.nnz, bits_for((uint64_t)a.n_rows * (uint64_t)a.n_cols), s));
+        hipLaunchKernelGGL(k_split_tkeys, entry_blocks, threads, 0, s, k1, t.nnz, a.n_rows, part.t_rowidx, t.colidx);
+        hipLaunchKernelGGL(k_lower_bound_rows, dim3(blocks_for(t.n_rows + 1)), threads, 0, s, part.t_rowidx, t.nnz, t.n_rows, t.rowptr);
+        hipLaunchKernelGGL(k_permute_vals, entry_blocks, threads, 0, s, g->raw_vals, part.t_perm, t.nnz, part.t_raw);
+    }
+    GNX_HIP(hipStreamSynchronize(s));
+    GNX_TRY(build_long_plan(t, s));
+    part.has_t = true;
+    static_cast<TransposedPart &>(*g) = std::move(part);
     return GNX_OK;
 }
 
@@ -546,66 +508,54 @@ int ensure_gather_order(gnx_graph *g, hipStream_t s) {
     const Csr &a = g->a;
     GNX_CHECK_ARG(a.n_rows == a.n_cols && a.row_order != nullptr && a.n_rows > 0, "the gather order needs a non-empty square graph");
     const int64_t n = a.n_rows, nnz = a.nnz;
-    DevBuf order, rank, key, ids, k0, k1, otmp;
-    GNX_HIP(order.alloc(n * 4)); GNX_HIP(rank.alloc(n * 4)); GNX_HIP(key.alloc(n * 4)); GNX_HIP(ids.alloc(n * 4));
-    GNX_HIP(k0.alloc(n * 8)); GNX_HIP(k1.alloc(n * 8));
-    hipLaunchKernelGGL(k_invert_order, dim3(blocks_for(n)), dim3(256), 0, s, a.row_order, n, rank.as<int32_t>());   // degree rank
-    GNX_HIP(hipMemsetAsync(key.p, 0x7f, n * 4, s));                            // 0x7f7f7f7f: "no neighbour" sorts last
+    const dim3 row_blocks(blocks_for(n)), threads(256);
+    DevArray<int32_t> order, rank, key, ids;
+    DevArray<uint64_t> k0, k1;
+    GNX_HIP(order.alloc(n)); GNX_HIP(rank.alloc(n)); GNX_HIP(key.alloc(n)); GNX_HIP(ids.alloc(n));
+    GNX_HIP(k0.alloc(n)); GNX_HIP(k1.alloc(n));
+    hipLaunchKernelGGL(k_invert_order, row_blocks, threads, 0, s, a.row_order, n, rank);   // degree rank
+    GNX_HIP(hipMemsetAsync(key, 0x7f, n * 4, s));                              // 0x7f7f7f7f: "no neighbour" sorts last
     if (nnz > 0)
-        hipLaunchKernelGGL(k_min_neighbour_rank, dim3(blocks_for(nnz)), dim3(256), 0, s, g->rowidx, a.colidx, rank.as<int32_t>(), nnz,
-                           key.as<int32_t>());
+        hipLaunchKernelGGL(k_min_neighbour_rank, dim3(blocks_for(nnz)), threads, 0, s, g->rowidx, a.colidx, rank, nnz, key);
     const int clamp = a.long_row < 65535 ? a.long_row : 65535;                 // as build_long_plan binned the rows
-    hipLaunchKernelGGL(k_relabel_keys, dim3(blocks_for(n)), dim3(256), 0, s, a.rowptr, key.as<int32_t>(), n, clamp,
-                       k0.as<uint64_t>(), ids.as<int32_t>());
-    const unsigned order_bits = 32u + bits_for((uint64_t)clamp + 1);
-    size_t ob = 0;
-    GNX_HIP(rocprim::radix_sort_pairs(nullptr, ob, k0.as<uint64_t>(), k1.as<uint64_t>(), ids.as<int32_t>(), order.as<int32_t>(), (size_t)n,
-                                      0u, order_bits, s));
-    GNX_HIP(otmp.alloc(ob));
-    GNX_HIP(rocprim::radix_sort_pairs(otmp.p, ob, k0.as<uint64_t>(), k1.as<uint64_t>(), ids.as<int32_t>(), order.as<int32_t>(), (size_t)n,
-                                      0u, order_bits, s));
-    hipLaunchKernelGGL(k_invert_order, dim3(blocks_for(n)), dim3(256), 0, s, order.as<int32_t>(), n, rank.as<int32_t>());
+    hipLaunchKernelGGL(k_relabel_keys, row_blocks, threads, 0, s, a.rowptr, key, n, clamp, k0, ids);
+    GNX_TRY(sort_pairs<uint64_t, int32_t>(k0, k1, ids, order, n, 32u + bits_for((uint64_t)clamp + 1), s));
+    hipLaunchKernelGGL(k_invert_order, row_blocks, threads, 0, s, order, n, rank);
     GNX_HIP(hipStreamSynchronize(s));
     GNX_HIP(hipGetLastError());
-    g->go_order = (int32_t *)order.release();
-    g->go_rank = (int32_t *)rank.release();
+    g->go_order = std::move(order);
+    g->go_rank = std::move(rank);
     return GNX_OK;
 }
 
 // The matrix with its vertices renumbered in the gather order: same entries, rows and columns permuted alike, columns ascending
-// inside a row.  Built once, on the first narrow-width propagation of a large square graph.
+// inside a row.  Built once, on the first narrow-width propagation of a large square graph -- aside, like the transposed structure.
 int ensure_relabel(gnx_graph *g, hipStream_t s) {
     if (g->has_r) return GNX_OK;
     GNX_NOT_WHILE_CAPTURING(s, "the relabelled copy of this handle");
-    struct Undo { gnx_graph *g; ~Undo() { if (g && !g->has_r) drop_relabel(g); } } undo{g};
     const Csr &a = g->a;
-    Csr &r = g->r;
     GNX_CHECK_ARG(a.n_rows == a.n_cols && a.row_order != nullptr && a.nnz > 0, "relabelling needs a non-empty square graph");
-    int rc = ensure_gather_order(g, s);
-    if (rc != GNX_OK) return rc;
+    GNX_TRY(ensure_gather_order(g, s));
     const int64_t n = a.n_rows, nnz = a.nnz;
+    const dim3 entry_blocks(blocks_for(nnz)), threads(256);
+    RelabelledPart part;
+    Csr &r = part.r;
     r.n_rows = n; r.n_cols = n; r.nnz = nnz;
-    GNX_HIP(hipMalloc((void **)&r.rowptr, (n + 1) * sizeof(int64_t)));
-    GNX_HIP(hipMalloc((void **)&r.colidx, nnz * sizeof(int32_t)));
-    GNX_HIP(hipMalloc((void **)&g->r_perm, nnz * sizeof(int32_t)));
-    GNX_HIP(hipMalloc((void **)&g->r_vals, nnz * sizeof(float)));
-    DevBuf k0, k1, p0, rrow, tmp;
-    GNX_HIP(k0.alloc(nnz * 8)); GNX_HIP(k1.alloc(nnz * 8)); GNX_HIP(p0.alloc(nnz * 4)); GNX_HIP(rrow.alloc(nnz * 4));
-    hipLaunchKernelGGL(k_make_rkeys, dim3(blocks_for(nnz)), dim3(256), 0, s, g->rowidx, a.colidx, g->go_rank, nnz, n,
-                       k0.as<uint64_t>(), p0.as<int32_t>());
-    const unsigned end_bit = bits_for((uint64_t)n * (uint64_t)n);
-    size_t tb = 0;
-    GNX_HIP(rocprim::radix_sort_pairs(nullptr, tb, k0.as<uint64_t>(), k1.as<uint64_t>(), p0.as<int32_t>(), g->r_perm, (size_t)nnz, 0u,
-                                      end_bit, s));
-    GNX_HIP(tmp.alloc(tb));
-    GNX_HIP(rocprim::radix_sort_pairs(tmp.p, tb, k0.as<uint64_t>(), k1.as<uint64_t>(), p0.as<int32_t>(), g->r_perm, (size_t)nnz, 0u,
-                                      end_bit, s));
-    hipLaunchKernelGGL(k_split_tkeys, dim3(blocks_for(nnz)), dim3(256), 0, s, k1.as<uint64_t>(), nnz, n, rrow.as<int32_t>(), r.colidx);
-    hipLaunchKernelGGL(k_lower_bound_rows, dim3(blocks_for(n + 1)), dim3(256), 0, s, rrow.as<int32_t>(), nnz, n, r.rowptr);
+    GNX_HIP(r.rowptr.alloc(n + 1));
+    GNX_HIP(r.colidx.alloc(nnz));
+    GNX_HIP(part.r_perm.alloc(nnz));
+    GNX_HIP(part.r_vals.alloc(nnz));
+    DevArray<uint64_t> k0, k1;
+    DevArray<int32_t> p0, rrow;
+    GNX_HIP(k0.alloc(nnz)); GNX_HIP(k1.alloc(nnz)); GNX_HIP(p0.alloc(nnz)); GNX_HIP(rrow.alloc(nnz));
+    hipLaunchKernelGGL(k_make_rkeys, entry_blocks, threads, 0, s, g->rowidx, a.colidx, g->go_rank, nnz, n, k0, p0);
+    GNX_TRY(sort_pairs<uint64_t, int32_t>(k0, k1, p0, part.r_perm, nnz, bits_for((uint64_t)n * (uint64_t)n), s));
+    hipLaunchKernelGGL(k_split_tkeys, entry_blocks, threads, 0, s, k1, nnz, n, rrow, r.colidx);
+    hipLaunchKernelGGL(k_lower_bound_rows, dim3(blocks_for(n + 1)), threads, 0, s, rrow, nnz, n, r.rowptr);
     GNX_HIP(hipStreamSynchronize(s));
-    rc = build_long_plan(r, s);
-    if (rc != GNX_OK) return rc;
-    g->has_r = true;
+    GNX_TRY(build_long_plan(r, s));
+    part.has_r = true;
+    static_cast<RelabelledPart &>(*g) = std::move(part);
     return GNX_OK;
 }
 
@@ -630,27 +580,24 @@ int ensure_train_gather(gnx_graph *g, const char *fn, hipStream_t s) {
     if (g->a_gcol != nullptr) return GNX_OK;
     if (g->a.n_rows == 0) return GNX_OK;                             // nothing is ever launched
     GNX_NOT_WHILE_CAPTURING(s, "the gather-order columns of this handle (GNX_RESERVE_TRAIN_GATHER)");
-    int rc = ensure_transpose(g, s);
-    if (rc != GNX_OK) return rc;
-    rc = ensure_gather_order(g, s);
-    if (rc != GNX_OK) return rc;
+    GNX_TRY(ensure_transpose(g, s));
+    GNX_TRY(ensure_gather_order(g, s));
     const int64_t nnz = g->a.nnz;
-    DevBuf ac, tc;
-    GNX_HIP(ac.alloc(nnz * 4)); GNX_HIP(tc.alloc(nnz * 4));
+    DevArray<int32_t> ac, tc;
+    GNX_HIP(ac.alloc(nnz)); GNX_HIP(tc.alloc(nnz));
     if (nnz > 0) {
-        hipLaunchKernelGGL(k_gather_columns, dim3(blocks_for(nnz)), dim3(256), 0, s, g->a.colidx, g->go_rank, nnz, ac.as<int32_t>());
-        hipLaunchKernelGGL(k_gather_columns, dim3(blocks_for(nnz)), dim3(256), 0, s, g->t.colidx, g->go_rank, nnz, tc.as<int32_t>());
+        hipLaunchKernelGGL(k_gather_columns, dim3(blocks_for(nnz)), dim3(256), 0, s, g->a.colidx, g->go_rank, nnz, ac);
+        hipLaunchKernelGGL(k_gather_columns, dim3(blocks_for(nnz)), dim3(256), 0, s, g->t.colidx, g->go_rank, nnz, tc);
     }
     GNX_HIP(hipStreamSynchronize(s));
     GNX_HIP(hipGetLastError());
-    g->t_gcol = (int32_t *)tc.release();
-    g->a_gcol = (int32_t *)ac.release();
+    g->t_gcol = std::move(tc);
+    g->a_gcol = std::move(ac);
     return GNX_OK;
 }
 
 static int finish_graph(gnx_graph *g, hipStream_t s) {
-    int rc = build_long_plan(g->a, s);
-    if (rc != GNX_OK) return rc;
+    GNX_TRY(build_long_plan(g->a, s));
     GNX_HIP(hipGetLastError());
     return GNX_OK;
 }
@@ -665,33 +612,6 @@ const char *gnx_last_error(void) { return g_err; }
 int gnx_version(void) { return GNX_VERSION_NUM; }
 
 int gnx_graph_destroy(gnx_graph_t g) {
-    if (!g) return GNX_OK;
-    free_csr(g->a);
-    free_csr(g->t);
-    if (g->raw_vals) (void)hipFree(g->raw_vals);
-    if (g->rowidx) (void)hipFree(g->rowidx);
-    if (g->e_vals) (void)hipFree(g->e_vals);
-    if (g->slot_ptr) (void)hipFree(g->slot_ptr);
-    if (g->t_perm) (void)hipFree(g->t_perm);
-    if (g->t_vals) (void)hipFree(g->t_vals);
-    if (g->t_raw) (void)hipFree(g->t_raw);
-    if (g->t_rowidx) (void)hipFree(g->t_rowidx);
-    if (g->t_mask) (void)hipFree(g->t_mask);
-    if (g->ed_mult) (void)hipFree(g->ed_mult);
-    if (g->t_ed_mult) (void)hipFree(g->t_ed_mult);
-    if (g->ed_vals) (void)hipFree(g->ed_vals);
-    if (g->t_ed_vals) (void)hipFree(g->t_ed_vals);
-    if (g->partial) (void)hipFree(g->partial);
-    if (g->deg) (void)hipFree(g->deg);
-    if (g->blk_col_gid) (void)hipFree(g->blk_col_gid);
-    free_csr(g->r);
-    if (g->r_perm) (void)hipFree(g->r_perm);
-    if (g->r_vals) (void)hipFree(g->r_vals);
-    if (g->r_feat) (void)hipFree(g->r_feat);
-    if (g->go_order) (void)hipFree(g->go_order);
-    if (g->go_rank) (void)hipFree(g->go_rank);
-    if (g->a_gcol) (void)hipFree(g->a_gcol);
-    if (g->t_gcol) (void)hipFree(g->t_gcol);
     delete g;
     return GNX_OK;
 }
@@ -705,24 +625,18 @@ int gnx_graph_reserve(gnx_graph_t g, int64_t C, int flags, void *stream) {
     GNX_CHECK_ARG(!stream_is_capturing(s), "gnx_graph_reserve: the stream is being captured -- reserve before the capture begins");
     int64_t chunks = g->a.n_chunks;
     if (flags & GNX_RESERVE_TRANSPOSED) {
-        int rc = ensure_transpose(g, s);
-        if (rc != GNX_OK) return rc;
+        GNX_TRY(ensure_transpose(g, s));
         chunks = std::max(chunks, g->t.n_chunks);
         if (!g->t_mask && !g->has_dups && g->t.nnz > 0)      // the keep-bit scratch of a training step's column sums
-            GNX_HIP(hipMalloc((void **)&g->t_mask, (size_t)g->t.nnz * sizeof(uint16_t)));
+            GNX_HIP(g->t_mask.alloc(g->t.nnz));
     }
     if ((flags & GNX_RESERVE_K_LOOP) && g->a.order_window == 0 && C <= RELABEL_MAX_C && g->a.n_rows == g->a.n_cols &&
         g->a.n_rows >= (1 << 20) && g->a.nnz >= g->a.n_rows) {
-        int rc = ensure_relabel(g, s);
-        if (rc != GNX_OK) return rc;
-        rc = ensure_relabel_features(g, (size_t)g->a.n_rows * (size_t)C * sizeof(float), s);
-        if (rc != GNX_OK) return rc;
+        GNX_TRY(ensure_relabel(g, s));
+        GNX_TRY(ensure_relabel_features(g, (size_t)g->a.n_rows * (size_t)C * sizeof(float), s));
         chunks = std::max(chunks, g->r.n_chunks);
     }
-    if (flags & GNX_RESERVE_TRAIN_GATHER) {
-        int rc = ensure_train_gather(g, "gnx_graph_reserve(GNX_RESERVE_TRAIN_GATHER)", s);
-        if (rc != GNX_OK) return rc;
-    }
+    if (flags & GNX_RESERVE_TRAIN_GATHER) GNX_TRY(ensure_train_gather(g, "gnx_graph_reserve(GNX_RESERVE_TRAIN_GATHER)", s));
     if (chunks > 0) return ensure_partial(g, (size_t)chunks * (size_t)C * sizeof(float), s);
     return GNX_OK;
 }
@@ -733,8 +647,7 @@ int gnx_graph_gather_order(gnx_graph_t g, const int32_t **d_order, const int32_t
         set_error("gnx_graph_gather_order: the handle has a row window (gnx_graph_set_row_window): the gather order is not built");
         return GNX_ERR_UNSUPPORTED;
     }
-    int rc = ensure_gather_order(g, nullptr);
-    if (rc != GNX_OK) return rc;
+    GNX_TRY(ensure_gather_order(g, nullptr));
     if (d_order) *d_order = g->go_order;
     if (d_rank) *d_rank = g->go_rank;
     return GNX_OK;
@@ -749,17 +662,17 @@ int gnx_graph_set_row_window(gnx_graph_t g, int64_t window_rows, void *stream) {
     // launches in flight on this handle -- on ANY stream -- still read the old order's arrays, which are freed below
     GNX_HIP(hipDeviceSynchronize());
     const int64_t before = g->a.order_window;
-    free_plan(g->a);
+    g->a.drop_plan();
     g->a.order_window = window_rows;
     int rc = build_long_plan(g->a, s);
     if (rc != GNX_OK) {                                              // (a window count that does not fit the key: back to what it was)
-        free_plan(g->a);
+        g->a.drop_plan();
         g->a.order_window = before;
         const int rc2 = build_long_plan(g->a, s);
         return rc2 != GNX_OK ? rc2 : rc;
     }
     if (g->has_t) {
-        free_plan(g->t);
+        g->t.drop_plan();
         g->t.order_window = g->a.n_rows == g->a.n_cols ? window_rows : 0;
         rc = build_long_plan(g->t, s);
         if (rc != GNX_OK) {       // a half-built transposed plan must never be launched: the structure goes, the next user rebuilds it
@@ -782,74 +695,60 @@ int gnx_graph_create_coo(int64_t n_rows, int64_t n_cols, int64_t nnz, const int6
     GNX_CHECK_ARG(nnz < INT32_MAX, "gnx_graph_create_coo: more than 2^31-1 entries per handle");
     GNX_CHECK_ARG(nnz == 0 || (d_indices && d_values), "gnx_graph_create_coo: NULL indices/values");
     hipStream_t s = (hipStream_t)stream;
-    gnx_graph *g = new gnx_graph();
-    struct Guard { gnx_graph *g; ~Guard() { if (g) gnx_graph_destroy(g); } } guard{g};
+    std::unique_ptr<gnx_graph> g(new gnx_graph());
     Csr &a = g->a;
     a.n_rows = n_rows; a.n_cols = n_cols;
     g->nnz_entries = nnz;
-    GNX_HIP(hipMalloc((void **)&a.rowptr, (n_rows + 1) * sizeof(int64_t)));
+    GNX_HIP(a.rowptr.alloc(n_rows + 1));
     if (nnz == 0) {
         a.nnz = 0;
         GNX_HIP(hipMemsetAsync(a.rowptr, 0, (n_rows + 1) * sizeof(int64_t), s));
-        GNX_HIP(hipMalloc((void **)&a.colidx, 16));
-        GNX_HIP(hipMalloc((void **)&g->raw_vals, 16));
-        GNX_HIP(hipMalloc((void **)&g->rowidx, 16));
+        GNX_HIP(a.colidx.alloc(0));
+        GNX_HIP(g->raw_vals.alloc(0));
+        GNX_HIP(g->rowidx.alloc(0));
         GNX_HIP(hipStreamSynchronize(s));
-        int rc0 = finish_graph(g, s);
-        if (rc0 != GNX_OK) return rc0;
-        guard.g = nullptr; *out = g;
+        GNX_TRY(finish_graph(g.get(), s));
+        *out = g.release();
         return GNX_OK;
     }
-    DevBuf k0, k1, v1, head, scan, tmp, bad;
-    GNX_HIP(k0.alloc(nnz * 8)); GNX_HIP(k1.alloc(nnz * 8));
-    GNX_HIP(v1.alloc(nnz * 4));
-    GNX_HIP(bad.alloc(4));
-    GNX_HIP(hipMemsetAsync(bad.p, 0, 4, s));
-    hipLaunchKernelGGL(k_make_keys, dim3(blocks_for(nnz)), dim3(256), 0, s, d_indices, nnz, n_rows, n_cols,
-                       k0.as<uint64_t>(), bad.as<int>());
-    const unsigned end_bit = bits_for((uint64_t)n_rows * (uint64_t)n_cols);
-    size_t tb = 0;
-    GNX_HIP(rocprim::radix_sort_pairs(nullptr, tb, k0.as<uint64_t>(), k1.as<uint64_t>(), d_values, v1.as<float>(),
-                                      (size_t)nnz, 0u, end_bit, s));
-    GNX_HIP(tmp.alloc(tb));
-    GNX_HIP(rocprim::radix_sort_pairs(tmp.p, tb, k0.as<uint64_t>(), k1.as<uint64_t>(), d_values, v1.as<float>(),
-                                      (size_t)nnz, 0u, end_bit, s));
+    const dim3 entry_blocks(blocks_for(nnz)), threads(256);
+    DevArray<uint64_t> k0, k1;
+    DevArray<float> v1;
+    DevArray<int> bad;
+    GNX_HIP(k0.alloc(nnz)); GNX_HIP(k1.alloc(nnz));
+    GNX_HIP(v1.alloc(nnz));
+    GNX_HIP(bad.alloc(1));
+    GNX_HIP(hipMemsetAsync(bad, 0, 4, s));
+    hipLaunchKernelGGL(k_make_keys, entry_blocks, threads, 0, s, d_indices, nnz, n_rows, n_cols, k0, bad);
+    GNX_TRY(sort_pairs<uint64_t, const float>(k0, k1, d_values, v1, nnz, bits_for((uint64_t)n_rows * (uint64_t)n_cols), s));
     // k0 is free again: reuse as head flags + scan (2 x int32 per entry fits in 8 bytes/entry)
-    int32_t *d_head = k0.as<int32_t>();
+    int32_t *d_head = reinterpret_cast<int32_t *>(k0.get());
     int32_t *d_scan = d_head + nnz;
-    hipLaunchKernelGGL(k_heads, dim3(blocks_for(nnz)), dim3(256), 0, s, k1.as<uint64_t>(), nnz, d_head);
-    size_t sb = 0;
-    GNX_HIP(rocprim::inclusive_scan(nullptr, sb, d_head, d_scan, (size_t)nnz, rocprim::plus<int32_t>(), s));
-    if (sb > tb) { (void)hipFree(tmp.release()); GNX_HIP(tmp.alloc(sb)); }
-    GNX_HIP(rocprim::inclusive_scan(tmp.p, sb, d_head, d_scan, (size_t)nnz, rocprim::plus<int32_t>(), s));
+    hipLaunchKernelGGL(k_heads, entry_blocks, threads, 0, s, k1, nnz, d_head);
+    GNX_TRY(inclusive_scan(d_head, d_scan, nnz, s));
     int h_bad = 0; int32_t h_nslots = 0;
-    GNX_HIP(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, s));
-    GNX_HIP(hipMemcpyAsync(&h_nslots, d_scan + nnz - 1, 4, hipMemcpyDeviceToHost, s));
-    GNX_HIP(hipStreamSynchronize(s));
+    GNX_TRY(fetch(h_bad, bad.get(), s));
+    GNX_TRY(fetch(h_nslots, d_scan + (nnz - 1), s));
     GNX_CHECK_ARG(h_bad == 0, "gnx_graph_create_coo: an index lies outside the %lld x %lld shape", (long long)n_rows,
                   (long long)n_cols);
     a.nnz = h_nslots;
     g->has_dups = (a.nnz != nnz);
-    GNX_HIP(hipMalloc((void **)&a.colidx, a.nnz * sizeof(int32_t)));
-    GNX_HIP(hipMalloc((void **)&g->rowidx, a.nnz * sizeof(int32_t)));
-    if (g->has_dups) GNX_HIP(hipMalloc((void **)&g->slot_ptr, (a.nnz + 1) * sizeof(int64_t)));
-    hipLaunchKernelGGL(k_fill_slots, dim3(blocks_for(nnz)), dim3(256), 0, s, k1.as<uint64_t>(), d_scan, nnz, n_cols,
-                       a.colidx, g->rowidx, g->slot_ptr);
+    GNX_HIP(a.colidx.alloc(a.nnz));
+    GNX_HIP(g->rowidx.alloc(a.nnz));
+    if (g->has_dups) GNX_HIP(g->slot_ptr.alloc(a.nnz + 1));
+    hipLaunchKernelGGL(k_fill_slots, entry_blocks, threads, 0, s, k1, d_scan, nnz, n_cols, a.colidx, g->rowidx, g->slot_ptr);
     if (g->has_dups) {
         GNX_HIP(hipMemcpyAsync(g->slot_ptr + a.nnz, &nnz, 8, hipMemcpyHostToDevice, s));
-        g->e_vals = (float *)v1.release();
-        GNX_HIP(hipMalloc((void **)&g->raw_vals, a.nnz * sizeof(float)));
-        hipLaunchKernelGGL(k_sum_slots, dim3(blocks_for(a.nnz)), dim3(256), 0, s, g->e_vals, g->slot_ptr, a.nnz,
-                           g->raw_vals);
+        g->e_vals = std::move(v1);
+        GNX_HIP(g->raw_vals.alloc(a.nnz));
+        hipLaunchKernelGGL(k_sum_slots, dim3(blocks_for(a.nnz)), threads, 0, s, g->e_vals, g->slot_ptr, a.nnz, g->raw_vals);
     } else {
-        g->raw_vals = (float *)v1.release();
+        g->raw_vals = std::move(v1);
     }
-    hipLaunchKernelGGL(k_lower_bound_rows, dim3(blocks_for(n_rows + 1)), dim3(256), 0, s, g->rowidx, a.nnz, n_rows,
-                       a.rowptr);
+    hipLaunchKernelGGL(k_lower_bound_rows, dim3(blocks_for(n_rows + 1)), threads, 0, s, g->rowidx, a.nnz, n_rows, a.rowptr);
     GNX_HIP(hipStreamSynchronize(s));
-    int rc = finish_graph(g, s);
-    if (rc != GNX_OK) return rc;
-    guard.g = nullptr; *out = g;
+    GNX_TRY(finish_graph(g.get(), s));
+    *out = g.release();
     return GNX_OK;
 }
 
@@ -861,35 +760,30 @@ int gnx_graph_create_csr(int64_t n_rows, int64_t n_cols, int64_t nnz, const int6
     GNX_CHECK_ARG(n_rows < INT32_MAX && n_cols < INT32_MAX && nnz < INT32_MAX, "gnx_graph_create_csr: size over 2^31-1");
     GNX_CHECK_ARG(d_rowptr && (nnz == 0 || (d_colidx && d_values)), "gnx_graph_create_csr: NULL array");
     hipStream_t s = (hipStream_t)stream;
-    gnx_graph *g = new gnx_graph();
-    struct Guard { gnx_graph *g; ~Guard() { if (g) gnx_graph_destroy(g); } } guard{g};
+    std::unique_ptr<gnx_graph> g(new gnx_graph());
     Csr &a = g->a;
     a.n_rows = n_rows; a.n_cols = n_cols; a.nnz = nnz; g->nnz_entries = nnz;
-    const size_t nz = nnz ? nnz : 4;
-    GNX_HIP(hipMalloc((void **)&a.rowptr, (n_rows + 1) * sizeof(int64_t)));
-    GNX_HIP(hipMalloc((void **)&a.colidx, nz * sizeof(int32_t)));
-    GNX_HIP(hipMalloc((void **)&g->raw_vals, nz * sizeof(float)));
-    GNX_HIP(hipMalloc((void **)&g->rowidx, nz * sizeof(int32_t)));
+    GNX_HIP(a.rowptr.alloc(n_rows + 1));
+    GNX_HIP(a.colidx.alloc(nnz));
+    GNX_HIP(g->raw_vals.alloc(nnz));
+    GNX_HIP(g->rowidx.alloc(nnz));
     GNX_HIP(hipMemcpyAsync(a.rowptr, d_rowptr, (n_rows + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
     if (nnz) {
         GNX_HIP(hipMemcpyAsync(a.colidx, d_colidx, nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
         GNX_HIP(hipMemcpyAsync(g->raw_vals, d_values, nnz * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
-    DevBuf bad;
-    GNX_HIP(bad.alloc(4));
-    GNX_HIP(hipMemsetAsync(bad.p, 0, 4, s));
+    DevArray<int> bad;
+    GNX_HIP(bad.alloc(1));
+    GNX_HIP(hipMemsetAsync(bad, 0, 4, s));
     if (n_rows) {
-        hipLaunchKernelGGL(k_check_csr, dim3(blocks_for(n_rows)), dim3(256), 0, s, a.rowptr, a.colidx, n_rows, n_cols,
-                           nnz, bad.as<int>());
+        hipLaunchKernelGGL(k_check_csr, dim3(blocks_for(n_rows)), dim3(256), 0, s, a.rowptr, a.colidx, n_rows, n_cols, nnz, bad);
         hipLaunchKernelGGL(k_rows_from_ptr, dim3(blocks_for(n_rows)), dim3(256), 0, s, a.rowptr, n_rows, g->rowidx);
     }
     int h_bad = 0;
-    GNX_HIP(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, s));
-    GNX_HIP(hipStreamSynchronize(s));
+    GNX_TRY(fetch(h_bad, bad.get(), s));
     GNX_CHECK_ARG(h_bad == 0, "gnx_graph_create_csr: rowptr/colidx are not a valid sorted CSR for this shape");
-    int rc = finish_graph(g, s);
-    if (rc != GNX_OK) return rc;
-    guard.g = nullptr; *out = g;
+    GNX_TRY(finish_graph(g.get(), s));
+    *out = g.release();
     return GNX_OK;
 }
 

@@ -54,96 +54,142 @@ constexpr int TINY_ROWS = 1 << 15;      // below this everything is cache-reside
 constexpr int RELABEL_MAX_C = 16;
 constexpr int SMALL_LONG_ROW = GNX_LONG_ROW < 128 ? GNX_LONG_ROW : 128;
 
-// One CSR-like structure (the matrix itself, or its transpose).
-struct Csr {
-    int64_t n_rows = 0, n_cols = 0, nnz = 0;
-    int64_t *rowptr = nullptr;  // [n_rows+1]
-    int32_t *colidx = nullptr;  // [nnz]
+// An owned device array.  Everything a handle keeps on the device, and every temporary of its builds, is one of these, so dropping a
+// part of a handle is assigning a fresh value to it, and destroying a handle is `delete`.  Reads as the T * it holds: launches and
+// pointer arithmetic take it as they took the raw pointer.  alloc() frees what was held first and never allocates fewer than 16
+// bytes, so the array of a built part is never null, however empty the graph.
+template <class T>
+struct DevArray {
+    DevArray() = default;
+    DevArray(DevArray &&o) noexcept : p(o.release()) {}
+    DevArray &operator=(DevArray &&o) noexcept {
+        if (this != &o) { reset(); p = o.release(); }
+        return *this;
+    }
+    ~DevArray() { reset(); }
+    hipError_t alloc(size_t count) {
+        reset();
+        const size_t bytes = count * sizeof(T);
+        const hipError_t e = hipMalloc((void **)&p, bytes < 16 ? 16 : bytes);
+        if (e != hipSuccess) p = nullptr;
+        return e;
+    }
+    void reset() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    T *release() { T *q = p; p = nullptr; return q; }
+    T *get() const { return p; }
+    operator T *() const { return p; }
+private:
+    T *p = nullptr;
+};
+
+// Everything build_long_plan makes of a structure: what Csr::drop_plan drops for a rebuild under another row order.
+struct Plan {
     // long-row split plan
     int64_t n_long = 0, n_chunks = 0;
     int long_row = LONG_ROW, long_chunk = LONG_CHUNK;   // this structure's threshold / chunk length (set by build_long_plan)
-    int32_t *long_rows = nullptr;       // [n_long] row ids
-    int64_t *long_chunk_ptr = nullptr;  // [n_long+1] first chunk of each long row
-    int32_t *chunk_long = nullptr;      // [n_chunks] index into long_rows
-    int32_t *chunk_order = nullptr;     // [n_chunks] chunk ids sorted by the first column they touch (see gnx_graph.hip)
+    DevArray<int32_t> long_rows;        // [n_long] row ids
+    DevArray<int64_t> long_chunk_ptr;   // [n_long+1] first chunk of each long row
+    DevArray<int32_t> chunk_long;       // [n_chunks] index into long_rows
+    DevArray<int32_t> chunk_order;      // [n_chunks] chunk ids sorted by the first column they touch (see gnx_graph.hip)
     // rows in stable order of descending (clamped) entry count: the rows that share a wave in the
     // sub-wave kernels then have similar lengths (power-law graphs otherwise leave most lanes idle)
-    int32_t *row_order = nullptr;       // [n_rows]
-    // gnx_graph_set_row_window: > 0 = the caller's numbering carries locality; rows are then taken in windows of this many consecutive
-    // ids (degree-binned INSIDE a window, rows without entries still trailing everything) so that the rows in flight together are
-    // neighbours in the caller's order and gather from one neighbourhood
-    int64_t order_window = 0;
-    int64_t *slot_beg = nullptr;        // [n_rows] first entry of row row_order[slot] ...
-    int32_t *slot_cnt = nullptr;        // [n_rows] ... and its entry count: what the sub-wave kernels read instead of rowptr[row_order[slot]]
+    DevArray<int32_t> row_order;        // [n_rows]
+    DevArray<int64_t> slot_beg;         // [n_rows] first entry of row row_order[slot] ...
+    DevArray<int32_t> slot_cnt;         // [n_rows] ... and its entry count: what the sub-wave kernels read instead of rowptr[row_order[slot]]
                                         // (coalesced, and no load that depends on another load before the row's entries are known)
     int64_t n_nonempty = 0;             // rows with at least one entry: the first n_nonempty slots of row_order (the rest are the empty rows)
-    int32_t *nonempty_rows = nullptr;   // [n_nonempty] the same rows in ASCENDING order (only when some row is empty): what the one-wave-per-row
+    DevArray<int32_t> nonempty_rows;    // [n_nonempty] the same rows in ASCENDING order (only when some row is empty): what the one-wave-per-row
                                         // kernels walk while rows without entries are skipped
     // square structures: no row WITHOUT entries is referenced as a column by any entry (always so for a symmetric pattern).  Such rows
     // are alpha * H0 after every iteration and nobody gathers them: loops write them into their result only, never into work buffers
     bool empty_rows_unreferenced = false;
 };
 
+// One CSR-like structure (the matrix itself, or its transpose) and its plan.
+struct Csr : Plan {
+    int64_t n_rows = 0, n_cols = 0, nnz = 0;
+    DevArray<int64_t> rowptr;   // [n_rows+1]
+    DevArray<int32_t> colidx;   // [nnz]
+    // gnx_graph_set_row_window: > 0 = the caller's numbering carries locality; rows are then taken in windows of this many consecutive
+    // ids (degree-binned INSIDE a window, rows without entries still trailing everything) so that the rows in flight together are
+    // neighbours in the caller's order and gather from one neighbourhood
+    int64_t order_window = 0;
+    void drop_plan() { static_cast<Plan &>(*this) = Plan(); }
+};
+
+// The lazily built parts of a handle that are dropped as a whole (a failed build, another row order): gnx_graph inherits each, so the
+// fields read as the handle's own, and dropping a part is assigning a fresh one (drop_transpose and its like, gnx_graph.hip).
+
+// transposed structure (lazy)
+struct TransposedPart {
+    bool has_t = false;
+    Csr t;                       // t.n_rows = a.n_cols
+    DevArray<int32_t> t_perm;    // [a.nnz] coalesced slot of every transposed entry
+    DevArray<float> t_vals;      // [a.nnz] scratch: values gathered into transposed order
+    DevArray<float> t_raw;       // [a.nnz] raw values in transposed order (streaming column sums)
+    DevArray<int32_t> t_rowidx;  // [a.nnz] row of the transposed structure (= column of A) per transposed position
+    DevArray<uint16_t> t_mask;   // [a.nnz] scratch: keep bits of up to 16 dropout streams per transposed position (gnx_graph_colsum_streams)
+};
+
+// degree-relabelled copy of a square matrix (lazy; narrow feature widths): vertex go_order[i] becomes vertex i, so the
+// rows of the hubs -- which most gathers hit -- are neighbours in memory and share cache lines.  go_order (below) = the degree bins
+// of a.row_order (heaviest first) and, inside a bin, the vertices by the degree rank of their most popular neighbour: the
+// leaves of one hub become neighbours too, so the hub's row gathers them from consecutive lines
+struct RelabelledPart {
+    bool has_r = false;
+    Csr r;
+    DevArray<int32_t> r_perm;    // [a.nnz] coalesced slot of every relabelled entry
+    DevArray<float> r_vals;      // [a.nnz] scratch: values gathered into relabelled order
+};
+
+// the gather order of a square handle (lazy): the order the relabelled copy numbers its vertices in (above), kept on its own so
+// that it can exist without that copy.  go_order: position -> vertex (what the relabelled copy calls new id -> old id), go_rank its
+// inverse.  a_gcol / t_gcol (gnx_spmm_dropped_chained_ord / _back_ord): go_rank of every column of the matrix / of the transposed
+// structure, i.e. the row of a matrix STORED in gather order that an entry gathers
+struct GatherOrderPart {
+    DevArray<int32_t> go_order;  // [n]
+    DevArray<int32_t> go_rank;   // [n]
+    DevArray<int32_t> a_gcol;    // [a.nnz]
+    DevArray<int32_t> t_gcol;    // [a.nnz]
+};
+
 }  // namespace gnx
 
-struct gnx_graph {
+struct gnx_graph : gnx::TransposedPart, gnx::RelabelledPart, gnx::GatherOrderPart {
     gnx::Csr a;            // coalesced matrix
-    float *raw_vals = nullptr;   // [a.nnz] summed duplicate values
-    int32_t *rowidx = nullptr;   // [a.nnz] row of every coalesced entry
+    gnx::DevArray<float> raw_vals;     // [a.nnz] summed duplicate values
+    gnx::DevArray<int32_t> rowidx;     // [a.nnz] row of every coalesced entry
     // un-coalesced entries (only when duplicates exist; otherwise entries == coalesced)
     int64_t nnz_entries = 0;
     bool has_dups = false;
-    float *e_vals = nullptr;     // [nnz_entries] entry values, sorted by (row, col), input order among dups
-    int64_t *slot_ptr = nullptr; // [a.nnz+1] entry range of every coalesced slot
-    // transposed structure (lazy)
-    bool has_t = false;
-    gnx::Csr t;                  // t.n_rows = a.n_cols
-    int32_t *t_perm = nullptr;   // [a.nnz] coalesced slot of every transposed entry
-    float *t_vals = nullptr;     // [a.nnz] scratch: values gathered into transposed order
-    float *t_raw = nullptr;      // [a.nnz] raw values in transposed order (streaming column sums)
-    int32_t *t_rowidx = nullptr; // [a.nnz] row of the transposed structure (= column of A) per transposed position
+    gnx::DevArray<float> e_vals;       // [nnz_entries] entry values, sorted by (row, col), input order among dups
+    gnx::DevArray<int64_t> slot_ptr;   // [a.nnz+1] entry range of every coalesced slot
     // entry dropout of a handle with duplicates (gnx_graph_enable_entry_dropout): per slot the multiplicity (ENTRY_GENERAL: walk the
     // entry list) and the value its entries share, in CSR order and in transposed order (t_perm depends on the structure alone, so
     // the transposed tables stay valid if the transposed structure is ever rebuilt)
     bool entry_drop = false;
-    uint8_t *ed_mult = nullptr, *t_ed_mult = nullptr;
-    float *ed_vals = nullptr, *t_ed_vals = nullptr;
-    uint16_t *t_mask = nullptr;  // [a.nnz] scratch: keep bits of up to 16 dropout streams per transposed position (gnx_graph_colsum_streams)
+    gnx::DevArray<uint8_t> ed_mult, t_ed_mult;
+    gnx::DevArray<float> ed_vals, t_ed_vals;
     // partial slab for long rows (grown on demand)
-    float *partial = nullptr;
+    gnx::DevArray<float> partial;
     size_t partial_bytes = 0;
-    float *deg = nullptr;        // [a.n_cols] scratch for column sums / degree scales (lazy)
-    const uint64_t *stream_offset = nullptr;   // optional device counter added to every dropout stream id of this handle
+    gnx::DevArray<float> deg;          // [a.n_cols] scratch for column sums / degree scales (lazy)
+    const uint64_t *stream_offset = nullptr;   // NOT owned: optional device counter added to every dropout stream id of this handle
     // vertex block of a larger graph (gnx_graph_set_block): dropout draws are keyed by GLOBAL (row, col), and the degree
     // scale of local row r sits at position blk_row0_buf + r of the per-column scale vector
     int64_t blk_row0_global = 0, blk_row0_buf = 0;
-    int32_t *blk_col_gid = nullptr;            // [a.n_cols] global vertex id of every column (owned), or null
-    // degree-relabelled copy of a square matrix (lazy; narrow feature widths): vertex go_order[i] becomes vertex i, so the
-    // rows of the hubs -- which most gathers hit -- are neighbours in memory and share cache lines.  go_order (below) = the degree bins
-    // of a.row_order (heaviest first) and, inside a bin, the vertices by the degree rank of their most popular neighbour: the
-    // leaves of one hub become neighbours too, so the hub's row gathers them from consecutive lines
-    bool has_r = false;
-    gnx::Csr r;
-    int32_t *r_perm = nullptr;   // [a.nnz] coalesced slot of every relabelled entry
-    float *r_vals = nullptr;     // [a.nnz] scratch: values gathered into relabelled order
-    float *r_feat = nullptr;     // scratch: H0 in relabelled row order
+    gnx::DevArray<int32_t> blk_col_gid;        // [a.n_cols] global vertex id of every column (owned), or null
+    gnx::DevArray<float> r_feat;       // scratch of the relabelled copy: H0 in relabelled row order (grown on demand, outlives the copy)
     size_t r_feat_bytes = 0;
-    // the gather order of a square handle (lazy): the order the relabelled copy numbers its vertices in (above), kept on its own so
-    // that it can exist without that copy.  go_order: position -> vertex (what the relabelled copy calls new id -> old id), go_rank its
-    // inverse.  a_gcol / t_gcol (gnx_spmm_dropped_chained_ord / _back_ord): go_rank of every column of the matrix / of the transposed
-    // structure, i.e. the row of a matrix STORED in gather order that an entry gathers
-    int32_t *go_order = nullptr; // [n]
-    int32_t *go_rank = nullptr;  // [n]
-    int32_t *a_gcol = nullptr;   // [a.nnz]
-    int32_t *t_gcol = nullptr;   // [a.nnz]
-    const char *last_kernel = "";
+    const char *last_kernel = "";      // NOT owned: a string literal of the launcher
 };
 
 namespace gnx {
 
 int build_long_plan(Csr &m, hipStream_t s);
-void free_csr(Csr &m);
-void free_plan(Csr &m);
 int ensure_transpose(gnx_graph *g, hipStream_t s);
 int ensure_partial(gnx_graph *g, size_t bytes, hipStream_t s);
 bool stream_is_capturing(hipStream_t s);

@@ -3,6 +3,7 @@
 // (gnntf/core/nn/layered.py:47-50).  All of this is HBM-bound integer/float streaming over
 // nnz-sized arrays; no LDS tiling is needed, only coalesced slot-parallel passes.
 #include "gnx_internal.h"
+#include <utility>
 
 using namespace gnx;
 
@@ -401,7 +402,7 @@ int make_drop(gnx_graph *g, float p, uint64_t seed, uint64_t stream_id, Drop &d)
 
 int ensure_deg(gnx_graph *g) {
     if (g->deg) return GNX_OK;
-    GNX_HIP(hipMalloc((void **)&g->deg, (g->a.n_cols ? g->a.n_cols : 1) * sizeof(float)));
+    GNX_HIP(g->deg.alloc(g->a.n_cols));
     return GNX_OK;
 }
 
@@ -418,14 +419,14 @@ int gnx_graph_set_dropout_counter(gnx_graph_t g, const uint64_t *d_counter) {
 int gnx_graph_set_block(gnx_graph_t g, int64_t row0_global, int64_t row0_buf, const int32_t *d_col_gid, void *stream) {
     GNX_CHECK_ARG(g != nullptr, "gnx_graph_set_block: NULL handle");
     if (d_col_gid == nullptr) {                              // back to a stand-alone graph
-        if (g->blk_col_gid) (void)hipFree(g->blk_col_gid);
-        g->blk_col_gid = nullptr; g->blk_row0_global = 0; g->blk_row0_buf = 0;
+        g->blk_col_gid.reset();
+        g->blk_row0_global = 0; g->blk_row0_buf = 0;
         return GNX_OK;
     }
     GNX_CHECK_ARG(row0_global >= 0 && row0_buf >= 0 && row0_buf + g->a.n_rows <= g->a.n_cols,
                   "gnx_graph_set_block: the %lld rows do not fit behind column %lld of %lld", (long long)g->a.n_rows,
                   (long long)row0_buf, (long long)g->a.n_cols);
-    if (!g->blk_col_gid) GNX_HIP(hipMalloc((void **)&g->blk_col_gid, (g->a.n_cols ? g->a.n_cols : 1) * sizeof(int32_t)));
+    if (!g->blk_col_gid) GNX_HIP(g->blk_col_gid.alloc(g->a.n_cols));
     GNX_HIP(hipMemcpyAsync(g->blk_col_gid, d_col_gid, g->a.n_cols * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     g->blk_row0_global = row0_global; g->blk_row0_buf = row0_buf;
     return GNX_OK;
@@ -439,21 +440,17 @@ int gnx_graph_enable_entry_dropout(gnx_graph_t g, void *stream) {
     int rc = ensure_transpose(g, s);
     if (rc != GNX_OK) return rc;
     const int64_t nnz = g->a.nnz;
-    struct Tables {
-        uint8_t *m = nullptr, *tm = nullptr;
-        float *v = nullptr, *tv = nullptr;
-        ~Tables() { if (m) (void)hipFree(m); if (tm) (void)hipFree(tm); if (v) (void)hipFree(v); if (tv) (void)hipFree(tv); }
-    } tb;
-    GNX_HIP(hipMalloc((void **)&tb.m, nnz));
-    GNX_HIP(hipMalloc((void **)&tb.tm, nnz));
-    GNX_HIP(hipMalloc((void **)&tb.v, nnz * sizeof(float)));
-    GNX_HIP(hipMalloc((void **)&tb.tv, nnz * sizeof(float)));
-    hipLaunchKernelGGL(k_entry_tables, dim3(blocks_for(nnz)), dim3(256), 0, s, g->e_vals, g->slot_ptr, nnz, tb.m, tb.v);
-    hipLaunchKernelGGL(k_permute_entry_tables, dim3(blocks_for(nnz)), dim3(256), 0, s, g->t_perm, nnz, tb.m, tb.v, tb.tm, tb.tv);
+    DevArray<uint8_t> m, tm;                                  // handed to the handle once all four are made
+    DevArray<float> v, tv;
+    GNX_HIP(m.alloc(nnz));
+    GNX_HIP(tm.alloc(nnz));
+    GNX_HIP(v.alloc(nnz));
+    GNX_HIP(tv.alloc(nnz));
+    hipLaunchKernelGGL(k_entry_tables, dim3(blocks_for(nnz)), dim3(256), 0, s, g->e_vals, g->slot_ptr, nnz, m, v);
+    hipLaunchKernelGGL(k_permute_entry_tables, dim3(blocks_for(nnz)), dim3(256), 0, s, g->t_perm, nnz, m, v, tm, tv);
     GNX_HIP(hipGetLastError());
     GNX_HIP(hipStreamSynchronize(s));
-    g->ed_mult = tb.m; g->t_ed_mult = tb.tm; g->ed_vals = tb.v; g->t_ed_vals = tb.tv;
-    tb.m = tb.tm = nullptr; tb.v = tb.tv = nullptr;
+    g->ed_mult = std::move(m); g->t_ed_mult = std::move(tm); g->ed_vals = std::move(v); g->t_ed_vals = std::move(tv);
     g->entry_drop = true;
     return GNX_OK;
 }
@@ -540,7 +537,7 @@ int gnx_graph_colsum_streams(gnx_graph_t g, float dropout_p, uint64_t seed, uint
                           "captured: call gnx_graph_reserve(handle, C, GNX_RESERVE_TRANSPOSED) or run the call once eagerly before capturing");
                 return GNX_ERR_UNSUPPORTED;
             }
-            GNX_HIP(hipMalloc((void **)&g->t_mask, (size_t)t.nnz * sizeof(uint16_t)));
+            GNX_HIP(g->t_mask.alloc(t.nnz));
         }
         for (int k0 = 0; k0 < n_streams; k0 += 16) {
             const int ns = n_streams - k0 < 16 ? n_streams - k0 : 16;

@@ -417,6 +417,164 @@ def test_handles_release_their_memory(gnntf):
     assert free0 - free1 < 8 * 2 ** 20, f"leaked {(free0 - free1) / 2 ** 20:.1f} MiB over 25 create/destroy cycles"
 
 
+LEAK_BOUND = 8 * 2 ** 20            # as above.  The graphs below are sized so that ONE int32 [n_rows] array lost per cycle exceeds it twice
+
+
+def free_bytes():
+    torch.cuda.synchronize()
+    return torch.cuda.mem_get_info()[0]
+
+
+_LAZY_GRAPHS = {}
+
+
+def lazy_part_graphs(n):
+    """Device COOs of a symmetric R-MAT with about 8 entries per row, made once per n: (without duplicates, with a quarter of the
+    entries listed twice, shape)."""
+    if n not in _LAZY_GRAPHS:
+        coo, vals, shape = graphs.rmat_symmetric_coo(n, 4 * n, seed=31)
+        assert len(coo) >= 6 * n
+        idx, val = dev(coo), dev(vals)
+        q = len(coo) // 4
+        _LAZY_GRAPHS[n] = ((idx, val), (torch.cat([idx, idx[:q]]), torch.cat([val, val[:q]])), shape)
+    return _LAZY_GRAPHS[n]
+
+
+def fused_training_step(gnntf, g, C, gather_order):
+    """Forward and backward of a K = 2 loop over fused dropped adjacencies; the degree scales of its two streams come from ONE
+    gnx_graph_colsum_streams call (on a handle without duplicates that allocates the keep-bit scratch, t_mask)."""
+    sparse = gnntf.sparse
+    scales = sparse.dropped_degree_scales(g, 0.5, 77, 3, 2)
+    make_adj = lambda k, bwd=False: sparse.dropped_adjacency(g, 0.5, 77, 3 + k, D=scales[k])
+    H0 = torch.ones((g.n_rows, C), device="cuda").requires_grad_(True)
+    out = sparse.ppr_loop(make_adj, H0, 0.1, 2, gather_order=gather_order)
+    out.backward(torch.ones_like(out))
+    assert torch.isfinite(H0.grad).all()
+
+
+@pytest.mark.parametrize("n,cycles,C,k_loop", [(2 ** 18, 25, 64, False), (2 ** 20 + 3, 5, 8, True)])
+def test_handles_release_every_lazy_part(gnntf, n, cycles, C, k_loop):
+    """Create / destroy with EVERY lazily built part of a handle present: transposed structure, keep-bit scratch, gather order and
+    gather columns, entry-dropout tables, long-row slab, a row window set and taken back (plans rebuilt, gather order dropped), a
+    vertex block set and reset -- and, from 2^20 rows at C <= 16, the relabelled copy and its feature scratch.  One int32 [n] array
+    lost per cycle is 4 * n * cycles = 25 MiB (20 MiB at 2^20 + 3 rows) against the bound of 8.  Arrays sized by the number of LONG
+    rows or chunks are too small for mem_get_info to see at any size a test can afford: what covers them is that the handle holds
+    no raw owned pointer at all (gnx_internal.h)."""
+    import gc
+    nat = gnntf.sparse.nat
+    plain, doubled, shape = lazy_part_graphs(n)
+    gid = torch.arange(n, dtype=torch.int32, device="cuda")
+
+    def cycle():
+        g = gnntf.DeviceGraph(gnntf.SparseCOO(*plain, shape), device="cuda:0")
+        assert g.nnz == g.nnz_entries
+        g.reserve(C, transposed=True, train_gather=True, k_loop=k_loop)
+        order, rank = g.gather_order()
+        assert order.shape == rank.shape == (n,)
+        fused_training_step(gnntf, g, C, "relabelled")
+        g.set_row_window(4096)
+        g.set_row_window(0)
+        d = gnntf.DeviceGraph(gnntf.SparseCOO(*doubled, shape), device="cuda:0")
+        assert d.nnz < d.nnz_entries
+        d.enable_entry_dropout()
+        fused_training_step(gnntf, d, C, "caller")
+        b = gnntf.DeviceGraph(gnntf.SparseCOO(*plain, shape), device="cuda:0")
+        nat.check(nat.lib().gnx_graph_set_block(b.handle, 0, 0, nat.ptr(gid), nat.current_stream()))
+        nat.check(nat.lib().gnx_graph_set_block(b.handle, 0, 0, None, nat.current_stream()))
+        nat.check(nat.lib().gnx_graph_set_block(b.handle, 0, 0, nat.ptr(gid), nat.current_stream()))   # destroyed as a block
+        torch.cuda.synchronize()
+        del g, d, b, order, rank
+        gc.collect()
+
+    cycle()
+    free0 = free_bytes()
+    for _ in range(cycles):
+        cycle()
+    lost = free0 - free_bytes()
+    print(f"n = {n}: {lost / 2 ** 20:.2f} MiB less free after {cycles} cycles")
+    assert lost < LEAK_BOUND, f"leaked {lost / 2 ** 20:.1f} MiB over {cycles} create/destroy cycles"
+
+
+def test_row_window_toggles_on_a_live_handle_release_their_memory(gnntf):
+    """One handle of 2^18 rows with the transposed structure and the train-gather tables: 30 times a row window is set (two sizes
+    in turn) and taken back.  Every set frees and rebuilds both plans and drops the gather order and the gather columns, which the
+    gnx_spmm_dropped_chained_ord launch after every toggle rebuilds.  One int32 [n] array lost per toggle is 30 MiB.  The f32 SpMM
+    at C = 7 and C = 64 gives the same bits afterwards: the row order decides which rows share a launch, never a row's sum."""
+    sparse = gnntf.sparse
+    n = 2 ** 18
+    plain, _, shape = lazy_part_graphs(n)
+    g = gnntf.DeviceGraph(gnntf.SparseCOO(*plain, shape), device="cuda:0")
+    g.reserve(64, transposed=True, train_gather=True)
+    adj = gnntf.normalize(g, "symmetric")
+    X = {C: torch.randn((n, C), device="cuda", generator=torch.Generator(device="cuda").manual_seed(C)) for C in (7, 64)}
+    before = {C: gnntf.spmm(adj, X[C]) for C in X}
+    scales = sparse.dropped_degree_scales(g, 0.5, 77, 3, 2)
+    dropped = sparse.dropped_adjacency(g, 0.5, 77, 3, D=scales[0])
+    H0 = torch.ones((n, 8), device="cuda")
+
+    def toggle(window):
+        g.set_row_window(window)
+        assert torch.equal(gnntf.spmm(adj, X[7]), before[7])                # under the window as well
+        g.set_row_window(0)
+        sparse._launch_chained(dropped, H0, H0, 0.9, 0.1, False, scales[1], order=sparse.nat.ORD_OUT)
+        assert g.last_kernel().endswith("_ord"), g.last_kernel()
+
+    toggle(4096)
+    toggle(1000)
+    free0 = free_bytes()
+    for i in range(30):
+        toggle((4096, 1000)[i % 2])
+    lost = free0 - free_bytes()
+    print(f"{lost / 2 ** 20:.2f} MiB less free after 30 toggles")
+    for C in X:
+        assert torch.equal(gnntf.spmm(adj, X[C]), before[C]), C
+    assert lost < LEAK_BOUND, f"leaked {lost / 2 ** 20:.1f} MiB over 30 row-window toggles"
+
+
+def test_refused_row_window_rolls_back(gnntf):
+    """A window whose count does not fit the 32-bit order key is refused and the handle is as it was.  2^22 rows (a few hundred
+    entries: most rows are empty) are cut at LONG_ROW = 512 entries, so the degree bins take bits_for(513) = 10 bits of the key, and
+    windows of ONE row need bits_for(2^22 + 1) = 23 more: 33.  The ABI has no getter for the window; what reads it back is
+    gnx_graph_gather_order, which is refused exactly while a window is set.  The refused call frees the plan and rebuilds the
+    previous one: one int32 [n] array lost per call is 16 MiB, ten calls 160."""
+    nat = gnntf.sparse.nat
+    n = 2 ** 22
+    rng = np.random.default_rng(4)
+    pairs = np.unique(rng.integers(0, n, size=(300, 2)), axis=0)
+    pairs = pairs[pairs[:, 0] != pairs[:, 1]]
+    coo = np.unique(np.concatenate([pairs, pairs[:, ::-1]]), axis=0)
+    vals = rng.uniform(0.5, 1.5, size=len(coo)).astype(np.float32)
+    g = make_graph(gnntf, coo, vals, (n, n))
+    adj = gnntf.normalize(g, "symmetric")
+    X = torch.randn((n, 4), device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
+    before = gnntf.spmm(adj, X)
+    assert float(before.abs().max()) > 0
+
+    def refused():
+        rc = nat.lib().gnx_graph_set_row_window(g.handle, 1, nat.current_stream())
+        message = nat.lib().gnx_last_error().decode()
+        assert rc == -1 and "windows" in message and "order key" in message, (rc, message)      # GNX_ERR_INVALID
+
+    refused()
+    nat.check(nat.lib().gnx_graph_gather_order(g.handle, None, None))       # the window is still 0
+    assert torch.equal(gnntf.spmm(adj, X), before)
+    free0 = free_bytes()
+    for _ in range(10):
+        refused()
+    lost = free0 - free_bytes()
+    print(f"{lost / 2 ** 20:.2f} MiB less free after 10 refused calls")
+    assert torch.equal(gnntf.spmm(adj, X), before)
+    assert lost < LEAK_BOUND, f"leaked {lost / 2 ** 20:.1f} MiB over 10 refused set_row_window calls"
+    g.set_row_window(4096)                                                  # 1024 windows: 11 + 10 bits
+    refused()
+    assert nat.lib().gnx_graph_gather_order(g.handle, None, None) == -4     # GNX_ERR_UNSUPPORTED: the window of 4096 rows is still set
+    assert "row window" in nat.lib().gnx_last_error().decode()
+    assert torch.equal(gnntf.spmm(adj, X), before)
+    with pytest.raises(Exception, match="windows"):
+        g.set_row_window(1)
+    assert g.row_window == 4096
+
+
 def test_scatter_output_rows(gnntf):
     """gnx_spmm_scatter: result row i lands in out[perm[i]] (all dispatch classes incl. long rows)."""
     from gnntf.sparse import _launch
