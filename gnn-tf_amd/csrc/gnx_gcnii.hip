@@ -2,9 +2,42 @@
 // Shares the gathers' device code and the long-row path with gnx_spmm.hip (gnx_spmm_device.h, gnx::launch_long_rows).
 // gnx_gcnii_step_bf16 (inference, opt-in): the same kernel over bf16 feature rows (the row-storage policy of gnx_spmm_device.h), hub rows
 // and the other widths through the bf16 kernels of gnx_spmm_bf16.hip in the f32 launch's summation order; rounding points in gnx.h.
+// gnx_gcnii_step_back (training, opt-in): the layer's backward past the relu gate as one launch of the same shape over the transposed
+// structure (k_spmm_gcnii_back); the MFMA block of the two kernels is one device function (tile_times_Ms).
 #include "gnx_spmm_device.h"
 
 namespace {
+
+// tile <- act(tile . Ms) for one wave's 16-row tile T and the block's Ms (both row stride C + 4, C = 16 NT), on
+// v_mfma_f32_16x16x4_f32: the block the forward layer and its backward (k_spmm_gcnii_back) share.  The caller has put a wave
+// barrier between its writes of T and this call; on return the whole tile is written and visible to the wave.
+template <int NT>
+__device__ __forceinline__ void tile_times_Ms(float *__restrict__ T, const float *__restrict__ Ms, int lane, int act) {
+    constexpr int C = 16 * NT, STRIDE = C + 4;
+    // tile . M : A[m = lane & 15][k = 4 kk + (lane >> 4)] from the tile, B[k][n = lane & 15] from Ms
+    const int cc = lane & 15, g = lane >> 4;
+    f32x4 d[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) d[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int kk = 0; kk < C / 4; ++kk) {
+        const float a = T[cc * STRIDE + 4 * kk + g];
+        const float *__restrict__ mrow = Ms + (4 * kk + g) * STRIDE + cc;
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) d[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, mrow[16 * nt], d[nt], 0, 0, 0);
+    }
+    __builtin_amdgcn_wave_barrier();
+    // D: lane (cc, g), register r -> row 4g + r, column 16 nt + cc; back through the tile so that rows leave as whole float4 rows
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float v = d[nt][r];
+            if (act == GNX_ACT_RELU) v = fmaxf(v, 0.f);
+            T[(4 * g + r) * STRIDE + 16 * nt + cc] = v;
+        }
+    __builtin_amdgcn_wave_barrier();
+}
 
 // ---- GCNII layer: SpMM + mix + C x C transform on the matrix cores + activation, one launch ------------------------
 //   out[i,:] = act( (beta * sum_j A[i,j] X[j,:] + alpha * H0[i,:]) . M ),   M = (1-b) I + b W   (gcn.py:22-27)
@@ -78,29 +111,7 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args 
         vstore<4>(T + rr * STRIDE + c, acc);
     }
     __builtin_amdgcn_wave_barrier();
-    // tile . M : A[m = lane & 15][k = 4 kk + (lane >> 4)] from the tile, B[k][n = lane & 15] from Ms
-    const int cc = lane & 15, g = lane >> 4;
-    f32x4 d[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) d[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-    for (int kk = 0; kk < C / 4; ++kk) {
-        const float a = T[cc * STRIDE + 4 * kk + g];
-        const float *__restrict__ mrow = Ms + (4 * kk + g) * STRIDE + cc;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) d[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, mrow[16 * nt], d[nt], 0, 0, 0);
-    }
-    __builtin_amdgcn_wave_barrier();
-    // D: lane (cc, g), register r -> row 4g + r, column 16 nt + cc; back through the tile so that rows leave as whole float4 rows
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float v = d[nt][r];
-            if (p.act == GNX_ACT_RELU) v = fmaxf(v, 0.f);
-            T[(4 * g + r) * STRIDE + 16 * nt + cc] = v;
-        }
-    __builtin_amdgcn_wave_barrier();
+    tile_times_Ms<NT>(T, Ms, lane, p.act);
 #pragma unroll
     for (int ps = 0; ps < PASSES; ++ps) {
         if (!live[ps]) continue;
@@ -108,6 +119,115 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args 
         float o[4];
         vload<4>(o, T + rr * STRIDE + c);
         R::template store<4>(p, rows[ps] * p.ldo, c, o, false);
+    }
+}
+
+// ---- the layer's backward past the relu gate, one launch (gnx_gcnii_step_back) -----------------------------------------------
+//   dH[r,:] = (beta * sum_c At[r,c] G[c,:]) . N        S_out[r,:] = s_alpha * S_in[r,:] + (alpha * G[r,:]) . N,    N = M^T
+// (1-a) At (G N) = ((1-a) At G) N: the launch gathers the gated gradient G itself over the transposed structure (p), so g' M^T is
+// never written or gathered back, and the row's own a G[r] N -- the layer's term of dH0 -- rides on the same Ms.  The forward's
+// shape: 512 threads, a 16-row tile per wave in the transposed structure's degree-binned order, NT lanes of float4 per row, U entries
+// in flight, Ms with row stride C + 4.  The ONE tile of a wave serves both products, one after the other (first beta Z, then alpha G
+// of the same 16 rows), so the kernel's LDS is the forward's (51 KB at C = 64: three blocks per CU; a second tile would leave two,
+// and the forward's C = 128 experiment above shows what the gathers lose with fewer waves).  Every row below n takes part in the
+// second product, hub rows and rows without entries included; the gather and the dH store leave rows longer than p.long_row to the
+// long-row kernels + the dense kernel; a row without entries gets dH = 0, written.  S_in may be S_out (each lane reads the four
+// values it overwrites); dH aliases nothing.
+template <int NT, int U, int WPB>
+__global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii_back(const SpmmArgs p, const float *__restrict__ N, int64_t ldn, const float *S_in,
+                                                              float s_alpha, float *S_out) {
+    constexpr int C = 16 * NT, G = 4 * NT, RPP = 64 / G, PASSES = 16 / RPP, STRIDE = C + 4;
+    __shared__ float Ms[C * STRIDE];
+    __shared__ float Ts[WPB][16 * STRIDE];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    for (int idx = threadIdx.x; idx < C * C; idx += 64 * WPB) Ms[(idx / C) * STRIDE + idx % C] = N[(int64_t)(idx / C) * ldn + idx % C];
+    __syncthreads();
+    const int64_t tile = (int64_t)blockIdx.x * WPB + wave;
+    if (tile * 16 >= p.n_rows) return;
+    float *__restrict__ T = Ts[wave];
+    const int sub = lane % G, c = sub * 4;
+    int64_t rows[PASSES];
+    bool live[PASSES];
+#pragma unroll
+    for (int ps = 0; ps < PASSES; ++ps) {
+        const int rr = ps * RPP + lane / G;
+        const int64_t slot = tile * 16 + rr;
+        int64_t row = -1;
+        int64_t beg = 0, end = 0;
+        if (slot < p.n_rows) {
+            row = p.row_order ? (int64_t)p.row_order[slot] : slot;
+            beg = p.rowptr[row]; end = p.rowptr[row + 1];
+        }
+        live[ps] = row >= 0 && end - beg <= p.long_row;
+        rows[ps] = row;
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        if (live[ps]) {
+            const float *__restrict__ Xc = p.X + c;
+            for (int64_t e = beg; e < end; e += U) {
+                float x[U][4];
+                float w[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (e + u < end) {
+                        const int j = p.colidx[e + u];
+                        w[u] = p.vals[e + u];
+                        vload<4>(x[u], Xc + (int64_t)j * p.ldx);
+                    } else {
+                        w[u] = 0.f;
+#pragma unroll
+                        for (int v = 0; v < 4; ++v) x[u][v] = 0.f;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
+            }
+#pragma unroll
+            for (int v = 0; v < 4; ++v) acc[v] *= p.beta;
+        }
+        vstore<4>(T + rr * STRIDE + c, acc);
+    }
+    __builtin_amdgcn_wave_barrier();
+    tile_times_Ms<NT>(T, Ms, lane, GNX_ACT_NONE);
+#pragma unroll
+    for (int ps = 0; ps < PASSES; ++ps) {
+        if (!live[ps]) continue;
+        const int rr = ps * RPP + lane / G;
+        float o[4];
+        vload<4>(o, T + rr * STRIDE + c);
+        vstore<4>(p.out + rows[ps] * p.ldo + c, o);
+    }
+    if (S_out == nullptr) return;
+    __builtin_amdgcn_wave_barrier();      // every lane has read its rows of the first product before the tile is filled again
+#pragma unroll
+    for (int ps = 0; ps < PASSES; ++ps) {
+        const int rr = ps * RPP + lane / G;
+        float x[4] = {0.f, 0.f, 0.f, 0.f};
+        if (rows[ps] >= 0) {
+            vload<4>(x, p.X + rows[ps] * p.ldx + c);
+#pragma unroll
+            for (int v = 0; v < 4; ++v) x[v] *= p.alpha;
+        }
+        vstore<4>(T + rr * STRIDE + c, x);
+    }
+    __builtin_amdgcn_wave_barrier();
+    tile_times_Ms<NT>(T, Ms, lane, GNX_ACT_NONE);
+#pragma unroll
+    for (int ps = 0; ps < PASSES; ++ps) {
+        if (rows[ps] < 0) continue;
+        const int rr = ps * RPP + lane / G;
+        const int64_t at = rows[ps] * (int64_t)C + c;
+        float o[4];
+        vload<4>(o, T + rr * STRIDE + c);
+        if (S_in) {
+            float s[4];
+            vload<4>(s, S_in + at);
+#pragma unroll
+            for (int v = 0; v < 4; ++v) o[v] = fmaf(s_alpha, s[v], o[v]);
+        }
+        vstore<4>(S_out + at, o);
     }
 }
 
@@ -185,6 +305,71 @@ int gnx_gcnii_step(gnx_graph_t g, const float *d_vals, const float *d_H, const f
         p.out = rows_at;
         launch_long_rows(p, s);
         rc = dense_rows(rows_at, C, m.n_long, C, d_M, ldm, C, nullptr, act, m.long_rows, m.long_rows, d_out, C, s);
+        if (rc != GNX_OK) return rc;
+    }
+    GNX_HIP(hipGetLastError());
+    return GNX_OK;
+}
+
+int gnx_gcnii_step_back(gnx_graph_t g, const float *d_vals_t, const float *d_G, float a, int64_t C, const float *d_Mt, int64_t ldmt,
+                        float *d_dH, const float *d_S_in, float s_alpha, float *d_S_out, float *d_work, void *stream) {
+    int rc = check_common("gnx_gcnii_step_back", g, d_G, C, C, d_S_in, C, d_dH, C);
+    if (rc != GNX_OK) return rc;
+    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "gnx_gcnii_step_back: needs a square graph");
+    GNX_CHECK_ARG(d_Mt != nullptr && ldmt >= C, "gnx_gcnii_step_back: NULL Mt or ldmt < C");
+    GNX_CHECK_ARG(d_S_in == nullptr || d_S_out != nullptr, "gnx_gcnii_step_back: S_in without S_out");
+    GNX_CHECK_ARG(d_dH != d_S_in && d_dH != d_S_out && d_dH != d_Mt, "gnx_gcnii_step_back: dH must not alias S_in / S_out / Mt");
+    GNX_CHECK_ARG(d_S_out == nullptr || (d_S_out != d_G && d_S_out != d_Mt), "gnx_gcnii_step_back: S_out must not alias G / Mt");
+    GNX_CHECK_ARG(d_work == nullptr || (d_work != d_G && d_work != d_dH && d_work != d_S_in && d_work != d_S_out && d_work != d_Mt),
+                  "gnx_gcnii_step_back: d_work must be a buffer of its own");
+    hipStream_t s = (hipStream_t)stream;
+    const float beta = (float)(1.0 - (double)a);
+    const int64_t n = g->a.n_rows;
+    // (C = 128 stays with the two launches for the reason the forward gives: one block of eight waves per CU cannot keep the gathers fed)
+    const bool fusable = (C == 16 || C == 32 || C == 64) && aligned(d_G, 16) && aligned(d_dH, 16) && aligned(d_S_in, 16) && aligned(d_S_out, 16);
+    if (!fusable) {   // other widths / alignments, today's order: gT = G . Mt into d_work, dH = (1-a) At gT, S = s_alpha S_in + a gT
+        GNX_CHECK_ARG(d_work != nullptr, "gnx_gcnii_step_back: width %lld / this alignment needs d_work [n, C] (G . Mt goes through memory)",
+                      (long long)C);
+        GNX_CHECK_ARG(d_S_out == nullptr || (aligned(d_work, 16) && aligned(d_S_in, 16) && aligned(d_S_out, 16)),
+                      "gnx_gcnii_step_back: S_in, S_out and d_work must be 16-byte aligned (gnx_linear_combination adds them)");
+        rc = ensure_transpose(g, s);   // (before the first launch: under capture a part that would have to be built refuses the whole call)
+        if (rc != GNX_OK) return rc;
+        if (g->t.n_long > 0) {
+            rc = ensure_partial(g, (size_t)g->t.n_chunks * (size_t)C * sizeof(float), s);
+            if (rc != GNX_OK) return rc;
+        }
+        rc = gnx_dense(d_G, C, n, C, d_Mt, ldmt, C, nullptr, GNX_ACT_NONE, d_work, C, stream);
+        if (rc != GNX_OK) return rc;
+        rc = gnx_spmm_tv(g, d_vals_t ? d_vals_t : g->t_raw.get(), nullptr, d_work, C, C, nullptr, 0, beta, 0.f, GNX_ACT_NONE, d_dH, C, stream);
+        if (rc != GNX_OK) return rc;
+        g->last_kernel = "dense+spmm_back";
+        if (d_S_out == nullptr || n == 0) return GNX_OK;
+        const float *src[2] = {d_S_in, d_work};
+        const float coef[2] = {s_alpha, a};
+        return d_S_in ? gnx_linear_combination(2, src, coef, n * C, d_S_out, stream)
+                      : gnx_linear_combination(1, src + 1, coef + 1, n * C, d_S_out, stream);
+    }
+    rc = ensure_transpose(g, s);
+    if (rc != GNX_OK) return rc;
+    const Csr &m = g->t;
+    if (m.n_rows == 0) return GNX_OK;
+    if (m.n_long > 0) {   // (before the first launch, as above)
+        rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)C * sizeof(float), s);
+        if (rc != GNX_OK) return rc;
+    }
+    SpmmArgs p{};
+    p.vals = d_vals_t ? d_vals_t : g->t_raw.get();
+    p.X = d_G; p.ldx = C; p.beta = beta; p.alpha = a; p.act = GNX_ACT_NONE; p.out = d_dH; p.ldo = C; p.C = (int)C;
+    bind_fused(m, p);
+    const unsigned grid = blocks_for(blocks_for(m.n_rows, 16), 8);
+    if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii_back<4, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
+    else if (C == 32) hipLaunchKernelGGL((k_spmm_gcnii_back<2, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
+    else              hipLaunchKernelGGL((k_spmm_gcnii_back<1, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
+    g->last_kernel = "spmm_gcnii_back_mfma";
+    if (m.n_long > 0) {   // hub rows of the transposed structure: chunked partial sums -> (1-a) Z into dH -> those rows alone times Mt, in place
+        p.partial = g->partial;
+        launch_long_rows(p, s);
+        rc = dense_rows(d_dH, C, m.n_long, C, d_Mt, ldmt, C, nullptr, GNX_ACT_NONE, m.long_rows, m.long_rows, d_dH, C, s);
         if (rc != GNX_OK) return rc;
     }
     GNX_HIP(hipGetLastError());

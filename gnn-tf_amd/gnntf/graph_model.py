@@ -47,7 +47,7 @@ class GNN(Trainable):
     fuse_entry_dropout = True
 
     def __init__(self, graph, features, preprocessor: Layer = None, reorder=None, inference_dtype=torch.float32,
-                 training_dtype=torch.float32, train_gather_order="auto"):
+                 training_dtype=torch.float32, train_gather_order="auto", gcnii_backward="composed"):
         """``reorder`` (opt-in, not in the reference): store the graph and the feature rows with the vertices relabelled; every
         [N, .] tensor inside the model then lives in that order, and the model's OUTPUT is put back into the caller's order, so
         tasks, labels and node ids are unaffected.  Results agree with the unordered model to float32 rounding.
@@ -86,7 +86,15 @@ class GNN(Trainable):
         (unlike ``reorder="degree"``, which renumbers the model and rounds differently).  Where the chained f32 loop does not apply
         (relu, bf16 training storage, graphs with duplicate entries, ``reorder="locality"`` row windows, the vertex-partitioned path)
         it is today's path.  ``"auto"`` (the default) takes the relabelled order only at the widths and graph sizes where it
-        measured faster (sparse.TRAIN_GATHER_MAX_WIDTH / TRAIN_GATHER_MIN_ROWS; profiles/NOTES.md)."""
+        measured faster (sparse.TRAIN_GATHER_MAX_WIDTH / TRAIN_GATHER_MIN_ROWS; profiles/NOTES.md).
+        ``gcnii_backward`` (not in the reference): ``"composed"`` (the default) or ``"fused"`` (sparse.gcnii_step ``backward``).
+        ``"fused"``: the backward of every plain GCNIILayer on the device with a constant adjacency is the relu mask, the weight
+        gradient and ONE launch for dH and dH0 (gnx_gcnii_step_back) instead of the dense kernel, the transposed SpMM and a scaling;
+        the forward and the weight gradients keep their bits, dH and dH0 agree to float32 rounding.  GCNIISpectralPreservingLayer,
+        dropped adjacencies, add_eye and the CPU path keep their code whatever it says.  The default stays ``"composed"``: the other
+        order moves the roundings of existing gradients (measurement: profiles/NOTES.md "Fused GCNII backward")."""
+        if gcnii_backward not in sparse.GCNII_BACKWARDS:
+            raise Exception("GNN: gcnii_backward must be one of " + ", ".join(repr(b) for b in sparse.GCNII_BACKWARDS))
         if train_gather_order not in sparse.GATHER_ORDERS:
             raise Exception("GNN: train_gather_order must be one of " + ", ".join(repr(o) for o in sparse.GATHER_ORDERS))
         if inference_dtype not in (torch.float32, torch.bfloat16):
@@ -97,6 +105,7 @@ class GNN(Trainable):
         self.inference_dtype = inference_dtype
         self.training_dtype = training_dtype
         self.train_gather_order = train_gather_order
+        self.gcnii_backward = gcnii_backward
         self._order = self._newid = None
         self.reorder_used, self.locality_share = None, None
         if isinstance(graph, sparse.DeviceGraph):
@@ -466,7 +475,8 @@ class GCNIILayer(Layer):
         adjacency = gcn.get_adjacency(self.graph_dropout)
         if features.is_cuda and adjacency.diag is None:
             fused_act = self.activation is relu or self.activation is linear
-            out = sparse.gcnii_step(adjacency, features, self.H0.value, self.a, transform, relu=self.activation is relu)
+            out = sparse.gcnii_step(adjacency, features, self.H0.value, self.a, transform, relu=self.activation is relu,
+                                    backward=getattr(gcn, "gcnii_backward", "composed"))
             return gcn.dropout(out if fused_act else self.activation(out), self.dropout)
         tradeoff = sparse.ppr_step(adjacency, features, self.H0.value, self.a)
         return gcn.dropout(self.activation(torch.matmul(tradeoff, transform)), self.dropout)

@@ -1096,14 +1096,51 @@ def _gcnii_launch(adj: Adjacency, H, H0, a, M, relu, keep_mixed):
     return out, mixed
 
 
+GCNII_BACKWARDS = ("composed", "fused")
+
+
+def gcnii_step_back(adj: Adjacency, G: torch.Tensor, a: float, Mt: torch.Tensor, S_in=None, s_alpha=1.0, want_S=True):
+    """The backward of gcnii_step past the relu gate as ONE launch for C in {16, 32, 64} (gnx_gcnii_step_back; no autograd):
+    with ``G`` = g * (out > 0) and ``Mt`` = M^T,  dH = ((1-a) A^T G) . Mt  and  S = s_alpha S_in + (a G) . Mt  -- the gradient of H and
+    the layer's term of dH0 on top of a running sum ``S_in`` (None: no such term).  Returns (dH, S); ``want_S=False`` skips the
+    second product and returns (dH, None).  G is gathered over the transposed structure itself: G . Mt never reaches memory.
+    Other widths run gnx_dense, the transposed SpMM and one linear combination, through a work buffer allocated here."""
+    if isinstance(adj, DroppedAdjacency):
+        raise Exception("gcnii_step: the fused backward needs a constant adjacency (a DroppedAdjacency makes its weights in the SpMM)")
+    g = adj.graph
+    nat.require_cuda(G, Mt, S_in)
+    _same_device(g, G, Mt, S_in)
+    G, Mt = _as_f32_rows(G).contiguous(), _as_f32_rows(Mt)
+    C = G.shape[1]
+    if g.n_rows != g.n_cols or G.shape[0] != g.n_rows or tuple(Mt.shape) != (C, C):
+        raise Exception("gcnii_step: shape mismatch")
+    if adj.diag is not None:
+        raise Exception("gcnii_step: add_eye adjacencies are not supported by the fused step")
+    if S_in is not None:
+        if not want_S:
+            raise Exception("gcnii_step: S_in without want_S")
+        S_in = _as_f32_rows(S_in).contiguous()
+        if tuple(S_in.shape) != tuple(G.shape):
+            raise Exception("gcnii_step: shape mismatch")
+    dH = torch.empty_like(G)
+    S = torch.empty_like(G) if want_S else None
+    work = torch.empty_like(G) if C not in (16, 32, 64) else None
+    values = adj.transposed_values()
+    with nat.on_device(G.device):
+        nat.check(nat.lib().gnx_gcnii_step_back(g.handle, nat.ptr(values), nat.ptr(G), float(a), C, nat.ptr(Mt), Mt.stride(0), nat.ptr(dH),
+                                                nat.ptr(S_in), float(s_alpha), nat.ptr(S), nat.ptr(work), nat.current_stream()))
+    return dH, S
+
+
 class _GCNIIStep(torch.autograd.Function):
     """out = act(T . M), T = (A . H)(1-a) + H0 a, as ONE launch that also leaves T in memory for the backward (gcn.py:22-27 under
-    tf.GradientTape): with g' = g * (out > 0):  dM = T^T g' (gnx_dense_wgrad), dT = g' M^T (gnx_dense), dH = (1-a) A^T dT, dH0 = a dT."""
+    tf.GradientTape): with g' = g * (out > 0):  dM = T^T g' (gnx_dense_wgrad), dT = g' M^T (gnx_dense), dH = (1-a) A^T dT, dH0 = a dT.
+    ``backward="fused"``: dH = ((1-a) A^T g') M^T and dH0 = (a g') M^T from ONE launch (gcnii_step_back), dT never written."""
 
     @staticmethod
-    def forward(ctx, H, H0, M, adj, a, relu):
+    def forward(ctx, H, H0, M, adj, a, relu, backward="composed"):
         out, T = _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=True)
-        ctx.adj, ctx.a, ctx.relu = adj, a, relu
+        ctx.adj, ctx.a, ctx.relu, ctx.fused_backward = adj, a, relu, backward == "fused"
         ctx.save_for_backward(T, M, out if relu else None)
         return out
 
@@ -1113,17 +1150,21 @@ class _GCNIIStep(torch.autograd.Function):
         g = (_relu_mask(g, out) if ctx.relu else g).contiguous()
         gM = _dense_wgrad(T, g) if ctx.needs_input_grad[2] else None
         gH = gH0 = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+        if ctx.fused_backward and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            # (the launch always makes dH; a caller that wants dH0 alone is not what a GCNII stack asks for)
+            gH, gH0 = gcnii_step_back(ctx.adj, g, ctx.a, M.t().contiguous(), want_S=ctx.needs_input_grad[1])
+            gH = gH if ctx.needs_input_grad[0] else None
+        elif ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             gT = _dense_launch(g, M.t().contiguous(), None, False)
             if ctx.needs_input_grad[0]:
                 gH = _launch(ctx.adj, gT, None, 1.0 - ctx.a, 0.0, nat.ACT_NONE, transposed=True)
             if ctx.needs_input_grad[1]:
                 gH0 = gT * ctx.a
-        return gH, gH0, gM, None, None, None
+        return gH, gH0, gM, None, None, None, None
 
 
 def gcnii_step(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, M: torch.Tensor, relu=True, storage=torch.float32,
-               out_storage=torch.float32) -> torch.Tensor:
+               out_storage=torch.float32, backward="composed") -> torch.Tensor:
     """act(((A . H)(1-a) + H0 a) . M), M = (1-b) I + b W (gcn.py:22-27) -- ONE fused launch for C in {16, 32, 64}: the mixed
     rows stay in LDS and meet M on the matrix cores (gnx_gcnii_step).  Without autograd they never reach HBM; when gradients are
     needed the same launch also writes them (dM = T^T g needs them), once, and the transform does not read them back.  Other
@@ -1131,7 +1172,12 @@ def gcnii_step(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, M: t
     ``storage=torch.bfloat16`` (inference only: raises where autograd would need a gradient): the rows the launch GATHERS are bf16
     (gnx_gcnii_step_bf16) -- a bf16 H as it is, an f32 H rounded once (gnx_cast_bf16) -- widened exactly; sums, H0, the mix and the
     transform stay f32.  The result is f32, or with ``out_storage=torch.bfloat16`` rounded once as it is stored (what the next layer
-    of a stack gathers).  Over a bf16-representable H the f32 result is bit for bit the default path's."""
+    of a stack gathers).  Over a bf16-representable H the f32 result is bit for bit the default path's.
+    ``backward``: ``"composed"`` (the default: gnx_dense, the transposed SpMM and a scaling, today's bits) or ``"fused"`` (opt-in:
+    after the relu mask and gnx_dense_wgrad, dH and dH0 come from one launch, gcnii_step_back; the forward and dM keep their bits,
+    dH and dH0 agree to float32 rounding -- the products associate differently).  A DroppedAdjacency keeps the generic composition."""
+    if backward not in GCNII_BACKWARDS:
+        raise Exception("gcnii_step: backward must be one of " + ", ".join(repr(b) for b in GCNII_BACKWARDS))
     if _bf16(storage):
         _no_grad_for_bf16("gcnii_step", H, H0, M)
         return _gcnii_launch_bf16(adj, H, H0, a, M, relu, _bf16(out_storage))
@@ -1140,7 +1186,7 @@ def gcnii_step(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, M: t
     if torch.is_grad_enabled() and (H.requires_grad or H0.requires_grad or M.requires_grad):
         if isinstance(adj, DroppedAdjacency):                       # weights made inside the SpMM: the generic composition knows how
             return dense(ppr_step(adj, H, H0, a), M, None, relu)
-        return _GCNIIStep.apply(H, H0, M, adj, float(a), bool(relu))
+        return _GCNIIStep.apply(H, H0, M, adj, float(a), bool(relu), backward)
     return _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=False)[0]
 
 

@@ -58,7 +58,8 @@ const char *gnx_last_error(void);
  * changes nothing else; 0.9 adds the bf16 storage entries of the vertex-partitioned path (gnx_spmm_rows_bf16, gnx_halo_pack_bf16,
  * gnx_halo_exchange_bf16), likewise.  gnx_gcnii_step_bf16 was added WITHIN 0.9 (no existing signature changed, the number stays
  * 900): a client that wants it probes the library for the symbol (dlsym) instead of comparing versions.  So were the gather-order
- * entries (gnx_graph_gather_order, gnx_spmm_dropped_chained_ord, gnx_spmm_dropped_back_ord, GNX_RESERVE_TRAIN_GATHER), likewise. */
+ * entries (gnx_graph_gather_order, gnx_spmm_dropped_chained_ord, gnx_spmm_dropped_back_ord, GNX_RESERVE_TRAIN_GATHER), likewise, and
+ * gnx_gcnii_step_back (the fused backward of the GCNII layer), likewise. */
 #define GNX_ABI_VERSION 900
 int gnx_version(void);
 
@@ -424,6 +425,33 @@ int gnx_gcnii_step(gnx_graph_t g, const float *d_vals, const float *d_H, const f
 int gnx_gcnii_step_bf16(gnx_graph_t g, const float *d_vals, const uint16_t *d_H, const float *d_H0, float a, int64_t C,
                         const float *d_M, int64_t ldm, int act, void *d_out, int out_bf16, float *d_work, void *stream);
 
+/* gnx_gcnii_step_back (training, opt-in; added within ABI 0.9 -- probe for the symbol): the backward of gnx_gcnii_step past the relu
+ * gate.  With G = g * (out > 0) (the caller's: its neighbours' rows are gathered, so the gated gradient exists in memory anyway, and
+ * gnx_dense_wgrad reads the same array), Mt = M^T given by the caller as a [C, C] matrix (ldmt; the entry never transposes) and
+ *   Z[r] = sum_c A_hat[c][r] G[c]      over the handle's transposed structure, d_vals_t = the values in transposed order as
+ *                                      gnx_spmm_tv takes them (gnx_graph_permute_values_t / gnx_graph_normalize_t; NULL: the raw values),
+ *   dH[r]    = ((1-a) Z[r]) . Mt                          -- the gradient of H,
+ *   S_out[r] = s_alpha * S_in[r] + (a G[r]) . Mt          -- the layer's term of dH0, on top of a running sum.
+ * d_S_in == NULL drops the s_alpha term, d_S_out == NULL skips the second product (d_S_in must then be NULL too), d_S_in == d_S_out
+ * is allowed (in place).  G, dH, S_in, S_out: [n, C] contiguous f32; square graph; d_dH aliases neither d_G nor d_S_in / d_S_out.
+ * (1-a) A^T (G Mt) = ((1-a) A^T G) Mt, so for C in {16, 32, 64} with the four matrices 16-byte aligned this is ONE launch of the
+ * forward's shape for all rows of at most 512 entries of the transposed structure: G itself is gathered, G . Mt is never written or
+ * read back, the rows (1-a) Z meet Mt in LDS on the matrix cores (v_mfma_f32_16x16x4_f32, exact float32), and the same tile then takes
+ * a G[r] for the second product -- every row below n, hub rows and rows without entries included.  A row without entries gets
+ * dH = 0, written.  Hub rows of the transposed structure go through the long-row kernels into d_dH and the dense kernel transforms those
+ * rows alone, in place.  Other widths / alignments run today's order: gnx_dense(G, Mt) into d_work, gnx_spmm_tv(d_work) with
+ * beta = 1 - a into d_dH (bit for bit those two calls), S_out = s_alpha S_in + a d_work through gnx_linear_combination (S_in, S_out
+ * and d_work 16-byte aligned).
+ * d_work: f32 [n, C], a buffer of its own; needed exactly when the fused launch does not apply -- NULL there returns GNX_ERR_INVALID
+ * naming d_work.  No float atomics: per-row entry order, chunk order for hub rows and the k order of the MFMA are fixed, two calls give
+ * the same bits (the fused launch does not give the bits of the composed order: the products associate differently).
+ * Allocation-free once the handle is reserved with gnx_graph_reserve(C, GNX_RESERVE_TRANSPOSED); under capture it returns
+ * GNX_ERR_UNSUPPORTED naming gnx_graph_reserve where the transposed structure or the long-row slab would have to be built or grown. */
+int gnx_gcnii_step_back(gnx_graph_t g, const float *d_vals_t, const float *d_G, float a, int64_t C,
+                        const float *d_Mt, int64_t ldmt, float *d_dH,
+                        const float *d_S_in, float s_alpha, float *d_S_out,
+                        float *d_work, void *stream);
+
 /* ---- the dense ends of the path (matrix cores) -----------------------------------------------------------------------
  * gnx_dense: out = act(X . W + bias) -- Dense.__forward__ (gnntf/core/nn/layers.py:135-136) and the transform of
  * GCNLayer (gcn.py:89).  X [n, F] (ldx), W [F, O] (ldw), bias [O] or NULL, out [n, O] (ldo); float32 in and out, float32
@@ -552,7 +580,8 @@ int gnx_probe_block_xcd(int64_t n_blocks, int32_t *d_xcd_out, void *stream);
  * gnx_halo_pack_bf16 -- on the push graph's handle -- report these same names: no new suffix); the bf16 training entries report the f32 training
  * names with "_bf16" appended ("spmm_group16_drop_bf16", "spmm_wave_drop_entries_bf16", ...), "+long" after the row class when hub
  * rows went through the chunk kernels ("spmm_group8+long_drop_bf16"); gnx_gcnii_step_bf16 reports "spmm_gcnii_mfma_bf16" (the fused
- * launch, with or without hub rows) or "spmm+dense_mfma_bf16" (the other widths / alignments). */
+ * launch, with or without hub rows) or "spmm+dense_mfma_bf16" (the other widths / alignments); gnx_gcnii_step_back reports
+ * "spmm_gcnii_back_mfma" (the fused launch, with or without hub rows) or "dense+spmm_back" (the other widths / alignments). */
 const char *gnx_graph_last_kernel(gnx_graph_t g);
 
 #ifdef __cplusplus
