@@ -289,7 +289,7 @@ int gnx_gcnii_step(gnx_graph_t g, const float *d_vals, const float *d_H, const f
     if (m.n_rows == 0) return GNX_OK;
     SpmmArgs p{};
     p.vals = d_vals ? d_vals : g->raw_vals;
-    p.X = d_H; p.ldx = C; p.H0 = d_H0; p.ldh0 = C; p.beta = beta; p.alpha = a; p.act = act; p.out = d_out; p.ldo = C; p.C = (int)C;
+    set_operands<F32Rows>(p, d_H, C, d_H0, C, beta, a, act, d_out, 0, C, C);
     bind_fused(m, p);
     const unsigned grid = blocks_for(blocks_for(m.n_rows, 16), 8);
     if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii<F32Rows, 4, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);

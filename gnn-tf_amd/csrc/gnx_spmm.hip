@@ -55,21 +55,16 @@ int tune_override = -1;   // set through gnx_debug_set_tune (tuning builds only:
 #endif
 
 int launch_spmm(gnx_graph *g, const Csr &m, SpmmArgs &p, hipStream_t s) {
-    int rc = bind_csr(g, m, p, s);
-    if (rc != GNX_OK) return rc;
+    return launch_bound(g, m, p, s, [&](SpmmArgs &q) {
 #ifdef GNX_TUNING   // kernel-variant switches exist only in tuning builds (tools/tune_spmm.py); the product library has none
-    {
         static const int tune = [] { const char *e = getenv("GNX_TUNE"); return e ? atoi(e) : 0; }();
-        p.tune = tune_override >= 0 ? tune_override : tune;
-    }
-    if (p.tune & 16384) p.ldx = 0;             // (every gather reads row 0 -- what a launch costs without its gather misses; wrong results)
+        q.tune = tune_override >= 0 ? tune_override : tune;
+        if (q.tune & 16384) q.ldx = 0;         // (every gather reads row 0 -- what a launch costs without its gather misses; wrong results)
 #endif
-    if (m.n_rows == 0) return GNX_OK;
-    // (tried for C = 128: one wave per row with float2 lanes instead of 32-lane groups of float4 -- 10.9 vs 8.2 ms)
-    // a training iteration (p.fuse.D) goes to the kernels of gnx_spmm_train.hip
-    g->last_kernel = p.fuse.D != nullptr ? launch_spmm_dropped(p, F32Rows::vec(p), s) : launch_eval<F32Rows>(p, s);
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
+        // (tried for C = 128: one wave per row with float2 lanes instead of 32-lane groups of float4 -- 10.9 vs 8.2 ms)
+        // a training iteration (q.fuse.D) goes to the kernels of gnx_spmm_train.hip
+        return q.fuse.D != nullptr ? launch_spmm_dropped(q, F32Rows::vec(q), s) : launch_eval<F32Rows>(q, s);
+    });
 }
 
 // the long rows of a launch whose short rows another translation unit's kernel took (gnx_gcnii.hip): partial sums + reduce
@@ -94,8 +89,8 @@ int gnx_spmm(gnx_graph_t g, const float *d_vals, const float *d_diag, const floa
     GNX_CHECK_ARG(d_diag == nullptr || g->a.n_rows == g->a.n_cols, "gnx_spmm: diag needs a square graph");
     SpmmArgs p{};
     p.vals = d_vals ? d_vals : g->raw_vals;
-    p.diag = d_diag; p.X = d_X; p.ldx = ldx; p.H0 = d_H0; p.ldh0 = ldh0; p.beta = beta; p.alpha = alpha; p.act = act;
-    p.out = d_out; p.ldo = ldo; p.C = (int)C;
+    p.diag = d_diag;
+    set_operands<F32Rows>(p, d_X, ldx, d_H0, ldh0, beta, alpha, act, d_out, 0, ldo, C);
     return launch_spmm(g, g->a, p, (hipStream_t)stream);
 }
 
@@ -113,8 +108,8 @@ int gnx_spmm_t(gnx_graph_t g, const float *d_vals, const float *d_diag, const fl
         hipLaunchKernelGGL(k_gather_vals, dim3(blocks_for(g->a.nnz, 256)), dim3(256), 0, s, src, g->t_perm, g->a.nnz, g->t_vals);
     SpmmArgs p{};
     p.vals = g->t_vals;
-    p.diag = d_diag; p.X = d_X; p.ldx = ldx; p.H0 = d_H0; p.ldh0 = ldh0; p.beta = beta; p.alpha = alpha; p.act = act;
-    p.out = d_out; p.ldo = ldo; p.C = (int)C;
+    p.diag = d_diag;
+    set_operands<F32Rows>(p, d_X, ldx, d_H0, ldh0, beta, alpha, act, d_out, 0, ldo, C);
     return launch_spmm(g, g->t, p, s);
 }
 
@@ -127,8 +122,8 @@ int gnx_spmm_scatter(gnx_graph_t g, const float *d_vals, const float *d_diag, co
     GNX_CHECK_ARG(d_diag == nullptr || g->a.n_rows == g->a.n_cols, "gnx_spmm_scatter: diag needs a square graph");
     SpmmArgs p{};
     p.vals = d_vals ? d_vals : g->raw_vals;
-    p.diag = d_diag; p.X = d_X; p.ldx = ldx; p.H0 = d_H0; p.ldh0 = ldh0; p.beta = beta; p.alpha = alpha; p.act = act;
-    p.out = d_out; p.ldo = ldo; p.C = (int)C; p.out_rows = d_out_rows;
+    p.diag = d_diag; p.out_rows = d_out_rows;
+    set_operands<F32Rows>(p, d_X, ldx, d_H0, ldh0, beta, alpha, act, d_out, 0, ldo, C);
     return launch_spmm(g, g->a, p, (hipStream_t)stream);
 }
 
@@ -140,8 +135,8 @@ int gnx_spmm_rows(gnx_graph_t g, const float *d_vals, const float *d_X, int64_t 
     GNX_CHECK_ARG(d_rows != nullptr || g->a.n_rows == 0, "gnx_spmm_rows: NULL row map");
     SpmmArgs p{};
     p.vals = d_vals ? d_vals : g->raw_vals;
-    p.X = d_X; p.ldx = ldx; p.H0 = d_H0; p.ldh0 = ldh0; p.beta = beta; p.alpha = alpha; p.act = act;
-    p.out = d_out; p.ldo = ldo; p.C = (int)C; p.out_rows = d_rows; p.map_h0 = true;
+    p.out_rows = d_rows; p.map_h0 = true;
+    set_operands<F32Rows>(p, d_X, ldx, d_H0, ldh0, beta, alpha, act, d_out, 0, ldo, C);
     return launch_spmm(g, g->a, p, (hipStream_t)stream);
 }
 
@@ -170,8 +165,8 @@ int gnx_spmm_tv(gnx_graph_t g, const float *d_vals_t, const float *d_diag, const
     if (rc != GNX_OK) return rc;
     SpmmArgs p{};
     p.vals = d_vals_t;
-    p.diag = d_diag; p.X = d_X; p.ldx = ldx; p.H0 = d_H0; p.ldh0 = ldh0; p.beta = beta; p.alpha = alpha; p.act = act;
-    p.out = d_out; p.ldo = ldo; p.C = (int)C;
+    p.diag = d_diag;
+    set_operands<F32Rows>(p, d_X, ldx, d_H0, ldh0, beta, alpha, act, d_out, 0, ldo, C);
     return launch_spmm(g, g->t, p, s);
 }
 
@@ -221,11 +216,11 @@ int gnx_appnp_propagate_act(gnx_graph_t g, const float *d_vals, const float *d_d
             const bool last = k == K - 1;
             float *dst = last ? d_out : (((K - 2 - k) % 2 == 0) ? d_work : d_out);
             SpmmArgs p{};
-            p.vals = g->r_vals; p.X = src; p.ldx = C; p.H0 = g->r_feat; p.ldh0 = C; p.beta = (float)(1.0 - (double)a); p.alpha = a;
+            p.vals = g->r_vals;
             // rows without entries: written by the last iteration (it scatters every row); in between only if somebody gathers them
             // (with a relu such a row is relu(a * H0) after every iteration: just as constant)
-            p.act = (!last && (k >= 2 || g->r.empty_rows_unreferenced)) ? (act | GNX_ACT_SKIP_EMPTY) : act;
-            p.out = dst; p.ldo = C; p.C = (int)C;
+            const int act_k = (!last && (k >= 2 || g->r.empty_rows_unreferenced)) ? (act | GNX_ACT_SKIP_EMPTY) : act;
+            set_operands<F32Rows>(p, src, C, g->r_feat, C, (float)(1.0 - (double)a), a, act_k, dst, 0, C, C);
             p.out_rows = last ? g->go_order : nullptr;              // relabelled row i is the caller's row go_order[i]
             rc = launch_spmm(g, g->r, p, s);
             if (rc != GNX_OK) return rc;

@@ -34,12 +34,8 @@ __global__ __launch_bounds__(256) void k_cast_bf16(const float *__restrict__ src
 }
 
 int launch_bf_eval(gnx_graph *g, const Csr &m, BfArgs &p, hipStream_t s) {
-    int rc = bind_csr(g, m, p, s);
-    if (rc != GNX_OK) return rc;
-    if (m.n_rows == 0) return GNX_OK;
-    g->last_kernel = launch_eval<Bf16Rows>(p, s);    // "+long" in the name when hub rows went through the chunk kernels
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
+    // "+long" in the name when hub rows went through the chunk kernels
+    return launch_bound(g, m, p, s, [&](BfArgs &q) { return launch_eval<Bf16Rows>(q, s); });
 }
 
 int cast_bf16(const float *src, int64_t n_rows, int64_t C, int64_t lds, uint16_t *dst, int64_t ldd, hipStream_t s) {
@@ -70,20 +66,17 @@ namespace gnx {
 // chunk's entries to sub-groups, i.e. it IS the long rows' summation order.  The short rows keep 8 columns per lane wherever they have a
 // launch of their own (their entries are added in ascending order whatever the lane width).
 int launch_spmm_bf16_f32_order(gnx_graph *g, const Csr &m, const SpmmArgs &p, const uint16_t *Xb, float *out, hipStream_t s) {
-    BfArgs q = bf_rows_of(p, Xb, out);
-    int rc = bind_csr(g, m, q, s);
-    if (rc != GNX_OK) return rc;
-    if (m.n_rows == 0) return GNX_OK;
-    const int vec = Bf16Rows::vec(q);
-    g->last_kernel = with_vec<F32Rows>(std::min(vec, 4), [&](auto V4) {
-        RowClass rows = launch_rows_and_chunks<Bf16Rows, V4()>(q, s);
-        if (rows != ROWS_NONE) return kernel_name<Bf16Rows>(rows, MODE_EVAL, HUBS_CHUNKS);
-        rows = with_vec<Bf16Rows>(vec, [&](auto V) { return launch_rows<Bf16Rows, V()>(q, s); });
-        if (q.n_long > 0) launch_long<Bf16Rows, V4()>(q, s);
-        return kernel_name<Bf16Rows>(rows, MODE_EVAL, q.n_long > 0 ? HUBS_LONG : HUBS_NONE);
+    BfArgs bound = bf_rows_of(p, Xb, out);
+    return launch_bound(g, m, bound, s, [&](BfArgs &q) {
+        const int vec = Bf16Rows::vec(q);
+        return with_vec<F32Rows>(std::min(vec, 4), [&](auto V4) {
+            RowClass rows = launch_rows_and_chunks<Bf16Rows, V4()>(q, s);
+            if (rows != ROWS_NONE) return kernel_name<Bf16Rows>(rows, MODE_EVAL, HUBS_CHUNKS);
+            rows = with_vec<Bf16Rows>(vec, [&](auto V) { return launch_rows<Bf16Rows, V()>(q, s); });
+            if (q.n_long > 0) launch_long<Bf16Rows, V4()>(q, s);
+            return kernel_name<Bf16Rows>(rows, MODE_EVAL, q.n_long > 0 ? HUBS_LONG : HUBS_NONE);
+        });
     });
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
 }
 
 void launch_long_rows_bf16(const SpmmArgs &p, const uint16_t *Xb, float *out, hipStream_t s) {
@@ -114,8 +107,8 @@ int gnx_spmm_bf16(gnx_graph_t g, const float *d_vals, const float *d_diag, const
     GNX_CHECK_ARG(d_diag == nullptr || g->a.n_rows == g->a.n_cols, "gnx_spmm_bf16: diag needs a square graph");
     BfArgs p{};
     p.vals = d_vals ? d_vals : g->raw_vals;
-    p.diag = d_diag; p.Xb = d_X; p.ldx = ldx; p.H0 = d_H0; p.ldh0 = ldh0; p.beta = beta; p.alpha = alpha; p.act = act;
-    p.outv = d_out; p.out_bf16 = out_bf16; p.ldo = ldo; p.C = (int)C;
+    p.diag = d_diag;
+    set_operands<Bf16Rows>(p, d_X, ldx, d_H0, ldh0, beta, alpha, act, d_out, out_bf16, ldo, C);
     return launch_bf_eval(g, g->a, p, (hipStream_t)stream);
 }
 
@@ -128,8 +121,8 @@ int gnx_spmm_rows_bf16(gnx_graph_t g, const float *d_vals, const uint16_t *d_X, 
     GNX_CHECK_ARG(d_rows != nullptr || g->a.n_rows == 0, "gnx_spmm_rows_bf16: NULL row map");
     BfArgs p{};
     p.vals = d_vals ? d_vals : g->raw_vals;
-    p.Xb = d_X; p.ldx = ldx; p.H0 = d_H0; p.ldh0 = ldh0; p.beta = beta; p.alpha = alpha; p.act = act;
-    p.outv = d_out; p.out_bf16 = out_bf16; p.ldo = ldo; p.C = (int)C; p.out_rows = d_rows; p.map_h0 = true;
+    p.out_rows = d_rows; p.map_h0 = true;
+    set_operands<Bf16Rows>(p, d_X, ldx, d_H0, ldh0, beta, alpha, act, d_out, out_bf16, ldo, C);
     return launch_bf_eval(g, g->a, p, (hipStream_t)stream);
 }
 
@@ -162,9 +155,9 @@ int gnx_appnp_propagate_bf16(gnx_graph_t g, const float *d_vals, const float *d_
         const bool settled = !last && (k >= 2 || g->a.empty_rows_unreferenced);
         BfArgs p{};
         p.vals = d_vals ? d_vals : g->raw_vals;
-        p.diag = d_diag; p.Xb = buf[k % 2]; p.ldx = C; p.H0 = d_H0; p.ldh0 = C; p.beta = (float)(1.0 - (double)a); p.alpha = a;
-        p.act = (settled && d_diag == nullptr) ? (act | GNX_ACT_SKIP_EMPTY) : act;
-        p.outv = last ? (void *)d_out : (void *)buf[(k + 1) % 2]; p.out_bf16 = last ? 0 : 1; p.ldo = C; p.C = (int)C;
+        p.diag = d_diag;
+        set_operands<Bf16Rows>(p, buf[k % 2], C, d_H0, C, (float)(1.0 - (double)a), a, (settled && d_diag == nullptr) ? (act | GNX_ACT_SKIP_EMPTY) : act,
+                               last ? (void *)d_out : (void *)buf[(k + 1) % 2], last ? 0 : 1, C, C);
         rc = launch_bf_eval(g, g->a, p, s);
         if (rc != GNX_OK) return rc;
     }

@@ -138,10 +138,13 @@ inline bool aligned(const void *p, size_t a) { return p == nullptr || ((uintptr_
 // runtime-null pointers where an entry point of that storage can set them and a constant null where none can; EXPERIMENTS = the
 // kernels carry the A/B switches of the tuning build (SpmmArgs::tune, the PIPE / U variants), which exist for f32 rows only.
 // BF16 / NAMES_LONG only pick the reported name (kernel_name).  GATHER_ORDER = the kernels read OrdArgs::gcol / out2_rows (F32RowsOrd
-// below); where it is false those loads do not exist in the kernel.
+// below); where it is false those loads do not exist in the kernel.  Host side: Out / Out2 = how an entry point types the main and the
+// second result, bind_X / bind_out / bind_out2 = where Args keeps the typed buffers (set_operands fills the rest around them).
 struct F32Rows {
     using Args = SpmmArgs;
     using Elem = float;
+    using Out = float;
+    using Out2 = float;
     static constexpr int MAX_VEC = 4;
     static constexpr bool EXPERIMENTS = true;
     static constexpr int BF16 = 0;
@@ -163,6 +166,9 @@ struct F32Rows {
     __device__ static void store2(const Args &p, int64_t at, int c, const float (&o)[VEC]) { vstore<VEC>(p.out2 + at + c, o); }
     // (the second result's row starts are not looked at: every caller so far keeps it laid out like the first)
     static int vec(const Args &p) { return pick_vec(p, MAX_VEC, p.X, 4, p.out, 4, nullptr, 0); }
+    static void bind_X(Args &p, const float *X) { p.X = X; }
+    static void bind_out(Args &p, float *out, int /* out_bf16: f32 rows have no such choice */) { p.out = out; }
+    static void bind_out2(Args &p, float *out2) { p.out2 = out2; }
 };
 
 // f32 rows of a training launch whose gathered operand and / or results live in the handle's gather order (gnx_spmm_dropped_chained_ord,
@@ -199,6 +205,8 @@ template <bool TRAIN>
 struct Bf16RowsT {
     using Args = BfArgs;
     using Elem = uint16_t;
+    using Out = void;
+    using Out2 = uint16_t;
     static constexpr int MAX_VEC = 8;
     static constexpr bool EXPERIMENTS = false;
     static constexpr int BF16 = 1;
@@ -219,6 +227,9 @@ struct Bf16RowsT {
     template <int VEC>
     __device__ static void store2(const Args &p, int64_t at, int c, const float (&o)[VEC]) { bstore<VEC>(p.out2b + at + c, o); }
     static int vec(const Args &p) { return pick_vec(p, MAX_VEC, p.Xb, 2, p.outv, p.out_bf16 ? 2 : 4, p.out2b, 2); }
+    static void bind_X(Args &p, const uint16_t *X) { p.Xb = X; }
+    static void bind_out(Args &p, void *out, int out_bf16) { p.outv = out; p.out_bf16 = out_bf16; }
+    static void bind_out2(Args &p, uint16_t *out2) { p.out2b = out2; }
 };
 
 __device__ __forceinline__ int readlane_i(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
@@ -499,6 +510,18 @@ void launch_row_pieces(Kern kern, const Args &p, int rows_per_block, int threads
     return GNX_OK;
 }
 
+// The tail of every SpMM entry: p bound to structure m, nothing launched on a structure without rows, `pick(p)` launches and returns
+// the name gnx_graph_last_kernel reports.
+template <typename Args, typename Pick>
+int launch_bound(gnx_graph *g, const Csr &m, Args &p, hipStream_t s, Pick pick) {
+    int rc = bind_csr(g, m, p, s);
+    if (rc != GNX_OK) return rc;
+    if (m.n_rows == 0) return GNX_OK;
+    g->last_kernel = pick(p);
+    GNX_HIP(hipGetLastError());
+    return GNX_OK;
+}
+
 // GNX_ACT_SKIP_EMPTY in the row launchers: the sub-wave kernels walk the rows through row_order, whose trailing slots are exactly the
 // rows without entries -- those slots are not launched at all (on the R-MAT workloads 60 % of the rows: no wave, no row-pointer
 // read); the one-wave-per-row kernels keep the rows in ascending order and walk the ascending list of the rows that have entries.
@@ -555,6 +578,14 @@ template <typename R>
 const char *kernel_name(RowClass rows, NameMode mode, NameHubs hubs) {
     if (hubs == HUBS_LONG && !R::NAMES_LONG) hubs = HUBS_NONE;
     return kKernelNames[R::GATHER_ORDER ? 2 : R::BF16][mode][hubs][rows];
+}
+
+// the operands of one launch into its arguments: the gathered rows, the mix and the main result (`out_bf16` where the policy has the choice)
+template <typename R>
+void set_operands(typename R::Args &p, const typename R::Elem *X, int64_t ldx, const float *H0, int64_t ldh0, float beta, float alpha, int act,
+                  typename R::Out *out, int out_bf16, int64_t ldo, int64_t C) {
+    R::bind_X(p, X); p.ldx = ldx; p.H0 = H0; p.ldh0 = ldh0; p.beta = beta; p.alpha = alpha; p.act = act;
+    R::bind_out(p, out, out_bf16); p.ldo = ldo; p.C = (int)C;
 }
 
 // the operand checks every SpMM entry starts with (the bf16 training entries make them BEFORE they look at the handle, so that they

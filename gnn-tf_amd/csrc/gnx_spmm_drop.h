@@ -262,4 +262,105 @@ const char *launch_drop(const typename R::Args &p, int vec, hipStream_t s) {
     });
 }
 
+// ---- the fused-dropout entry points, written once over the policy ------------------------------------------------------------------
+// gnx_spmm_dropped_chained / _back and their _ord and _bf16 forms are calls of the two templates below with their own name.  Per
+// storage differ: where the NULL-handle check sits (bf16 rows: in `admit`, behind the handle-free checks, so that those can be
+// exercised without a device; f32 rows: first), which handles `admit(g, s)` lets through -- it runs behind the last handle-free check
+// and before anything is built or launched --, how X and the results are typed (the policy's binders) and, under a GATHER_ORDER
+// policy, `order`.  Only the messages of the bf16 entries name the entry in front of the dropout rate.
+template <typename R>
+int check_rate(const char *fn, float dropout_p) {
+    const bool ok = dropout_p >= 0.f && dropout_p < 1.f;
+    if constexpr (R::BF16) GNX_CHECK_ARG(ok, "%s: dropout rate %g outside [0, 1)", fn, (double)dropout_p);
+    else GNX_CHECK_ARG(ok, "dropout rate %g outside [0, 1)", (double)dropout_p);
+    return GNX_OK;
+}
+
+template <typename R>
+int check_handle_and_operands(const char *fn, gnx_graph *g, const void *X, int64_t ldx, int64_t C, const float *H0, int64_t ldh0, const void *out,
+                              int64_t ldo) {
+    if constexpr (!R::BF16) GNX_CHECK_ARG(g != nullptr, "%s: NULL handle", fn);
+    return check_operands(fn, X, ldx, C, H0, ldh0, out, ldo);
+}
+
+// the handle-free checks of the forward entries (gnx_spmm_dropped and the chained ones); act_flags = the bits `act` may carry beside
+// the activation
+template <typename R>
+int check_dropped_forward(const char *fn, gnx_graph *g, const void *X, int64_t ldx, int64_t C, const float *H0, int64_t ldh0, const void *out,
+                          int64_t ldo, int act, int act_flags, const float *d_D, float dropout_p) {
+    int rc = check_handle_and_operands<R>(fn, g, X, ldx, C, H0, ldh0, out, ldo);
+    if (rc != GNX_OK) return rc;
+    GNX_CHECK_ARG((act & ~act_flags) == GNX_ACT_NONE || (act & ~act_flags) == GNX_ACT_RELU, "%s: invalid activation %d", fn, act);
+    GNX_CHECK_ARG(d_D != nullptr, "%s: NULL degree scales", fn);
+    return check_rate<R>(fn, dropout_p);
+}
+
+// f32 rows launch through gnx_spmm.hip (where a tuning build switches kernel variants), the other storages from their own unit
+template <typename R>
+int launch_train(gnx_graph *g, const Csr &m, typename R::Args &p, hipStream_t s) {
+    if constexpr (std::is_same_v<typename R::Args, SpmmArgs>) return launch_spmm(g, m, p, s);
+    else return launch_bound(g, m, p, s, [&](typename R::Args &q) { return launch_drop<R>(q, R::vec(q), s); });
+}
+
+template <typename R, typename Admit>
+int spmm_dropped_chained(const char *fn, Admit admit, gnx_graph *g, const float *d_D, float dropout_p, uint64_t seed, uint64_t stream_id,
+                         int x_prescaled, const float *d_D_next, const typename R::Elem *d_X, int64_t ldx, int64_t C, const float *d_H0,
+                         int64_t ldh0, float beta, float alpha, int act, typename R::Out *d_out, int out_bf16, int64_t ldo, int order,
+                         void *stream) {
+    int rc = check_dropped_forward<R>(fn, g, d_X, ldx, C, d_H0, ldh0, d_out, ldo, act, GNX_ACT_SKIP_EMPTY, d_D, dropout_p);
+    if (rc != GNX_OK) return rc;
+    GNX_CHECK_ARG(out_bf16 == 0 || out_bf16 == 1, "%s: out_bf16 must be 0 or 1", fn);
+    GNX_CHECK_ARG((order & ~(GNX_ORD_X | GNX_ORD_OUT)) == 0, "%s: invalid order flags %d", fn, order);
+    hipStream_t s = (hipStream_t)stream;
+    rc = admit(g, s);
+    if (rc != GNX_OK) return rc;
+    if (!g->a.empty_rows_unreferenced) act &= ~GNX_ACT_SKIP_EMPTY;       // honoured only when nobody gathers the rows it would leave untouched
+    typename R::Args p{};
+    set_values(g, false, p);
+    set_operands<R>(p, d_X, ldx, d_H0, ldh0, beta, alpha, act, d_out, out_bf16, ldo, C);
+    p.out_scale = d_D_next ? d_D_next + g->blk_row0_buf : nullptr;       // (the offset is 0 on every handle that is no vertex block)
+    if constexpr (R::GATHER_ORDER) {
+        p.gcol = (order & GNX_ORD_X) ? g->a_gcol : nullptr;
+        p.out_rows = (order & GNX_ORD_OUT) ? g->go_rank : nullptr;       // H0 and the scales stay indexed by the caller's row (map_h0 false)
+    }
+    set_drop_fuse(g, dropout_p, seed, stream_id, d_D, 0, x_prescaled, p);
+    return launch_train<R>(g, g->a, p, s);
+}
+
+template <typename R, typename Admit>
+int spmm_dropped_back(const char *fn, Admit admit, gnx_graph *g, const float *d_D, float dropout_p, uint64_t seed, uint64_t stream_id,
+                      int x_prescaled, const float *d_D_next, const typename R::Elem *d_X, int64_t ldx, int64_t C, const float *d_S_in,
+                      int64_t lds_in, float s_alpha, float s_beta, float *d_S_out, int64_t lds_out, float y_beta, typename R::Out2 *d_Y_out,
+                      int64_t ldy, int act, int order, void *stream) {
+    int rc = check_handle_and_operands<R>(fn, g, d_X, ldx, C, d_S_in, lds_in, d_S_out, lds_out);
+    if (rc != GNX_OK) return rc;
+    GNX_CHECK_ARG((order & ~(GNX_ORD_X | GNX_ORD_OUT)) == 0, "%s: invalid order flags %d", fn, order);
+    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_SKIP_EMPTY, "%s: act must be GNX_ACT_NONE or GNX_ACT_SKIP_EMPTY", fn);
+    GNX_CHECK_ARG(act == GNX_ACT_NONE || (const void *)d_S_in == (const void *)d_S_out, "%s: GNX_ACT_SKIP_EMPTY needs the sum updated in place", fn);
+    GNX_CHECK_ARG(d_D != nullptr && d_S_in != nullptr, "%s: NULL degree scales / running sum", fn);
+    GNX_CHECK_ARG(d_Y_out == nullptr || (ldy >= C && (const void *)d_Y_out != (const void *)d_X && (const void *)d_Y_out != (const void *)d_S_out
+                                         && (const void *)d_Y_out != (const void *)d_S_in),
+                  "%s: the pre-scaled output needs a buffer of its own", fn);
+    rc = check_rate<R>(fn, dropout_p);
+    if (rc != GNX_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    rc = admit(g, s);
+    if (rc != GNX_OK) return rc;
+    if constexpr (!R::GATHER_ORDER) {                                    // (ensure_train_gather, the admission of _ord, built it)
+        rc = ensure_transpose(g, s);
+        if (rc != GNX_OK) return rc;
+    }
+    if (!g->t.empty_rows_unreferenced) act = GNX_ACT_NONE;               // honoured only when nobody gathers the rows it would leave untouched
+    typename R::Args p{};
+    set_values(g, true, p);
+    set_operands<R>(p, d_X, ldx, d_S_in, lds_in, s_beta, s_alpha, act, d_S_out, 0, lds_out, C);   // the running sum: f32, in the caller's order
+    R::bind_out2(p, d_Y_out); p.ldo2 = ldy; p.beta2 = y_beta; p.out2_scale = d_Y_out ? d_D_next : nullptr;
+    if constexpr (R::GATHER_ORDER) {
+        p.gcol = (order & GNX_ORD_X) ? g->t_gcol : nullptr;
+        p.out2_rows = (d_Y_out && (order & GNX_ORD_OUT)) ? g->go_rank : nullptr;
+    }
+    set_drop_fuse(g, dropout_p, seed, stream_id, d_D, 1, x_prescaled, p);   // (stand-alone handle: the block keys are 0 / null)
+    return launch_train<R>(g, g->t, p, s);
+}
+
 }  // namespace

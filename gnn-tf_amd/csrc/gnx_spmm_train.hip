@@ -1,8 +1,9 @@
 // Training-mode propagation on gfx950: the dropped + re-normalised adjacency values of one iteration (layered.py:47-50, gnn.py:37-42)
 // are produced INSIDE the SpMM kernels from the counter RNG, so a training iteration reads every stored entry's column and raw
 // value, gathers only the kept entries' rows, and writes no value array.  Entries: gnx_spmm_dropped, gnx_spmm_dropped_chained (forward
-// loop), gnx_spmm_dropped_back (backward loop, over the transposed structure).  The kernels and their launchers are written once over the
-// row-storage policy in gnx_spmm_drop.h; this unit instantiates them for f32 rows, gnx_spmm_train_bf16.hip for bf16 rows.
+// loop), gnx_spmm_dropped_back (backward loop, over the transposed structure).  The kernels, their launchers and the two loop entries are
+// written once over the row-storage policy in gnx_spmm_drop.h; this unit instantiates them for f32 rows, gnx_spmm_train_bf16.hip for bf16
+// rows, gnx_spmm_train_ord.hip for f32 rows in the handle's gather order.
 #include "gnx_spmm_drop.h"
 
 namespace gnx {
@@ -49,11 +50,8 @@ extern "C" {
 int gnx_spmm_dropped(gnx_graph_t g, const float *d_D, float dropout_p, uint64_t seed, uint64_t stream_id, int transposed,
                      const float *d_X, int64_t ldx, int64_t C, const float *d_H0, int64_t ldh0, float beta, float alpha, int act,
                      float *d_out, int64_t ldo, void *stream) {
-    int rc = check_common("gnx_spmm_dropped", g, d_X, ldx, C, d_H0, ldh0, d_out, ldo);
+    int rc = check_dropped_forward<F32Rows>("gnx_spmm_dropped", g, d_X, ldx, C, d_H0, ldh0, d_out, ldo, act, 0, d_D, dropout_p);
     if (rc != GNX_OK) return rc;
-    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU, "gnx_spmm_dropped: invalid activation %d", act);
-    GNX_CHECK_ARG(d_D != nullptr, "gnx_spmm_dropped: NULL degree scales");
-    GNX_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "dropout rate %g outside [0, 1)", (double)dropout_p);
     GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols || g->blk_col_gid != nullptr, "gnx_spmm_dropped: needs a square graph or a vertex block (gnx_graph_set_block)");
     rc = refuse_duplicates(g, "gnx_spmm_dropped");
     if (rc != GNX_OK) return rc;
@@ -64,8 +62,7 @@ int gnx_spmm_dropped(gnx_graph_t g, const float *d_D, float dropout_p, uint64_t 
     }
     SpmmArgs p{};
     set_values(g, transposed, p);
-    p.X = d_X; p.ldx = ldx; p.H0 = d_H0; p.ldh0 = ldh0; p.beta = beta; p.alpha = alpha; p.act = act;
-    p.out = d_out; p.ldo = ldo; p.C = (int)C;
+    set_operands<F32Rows>(p, d_X, ldx, d_H0, ldh0, beta, alpha, act, d_out, 0, ldo, C);
     set_drop_fuse(g, dropout_p, seed, stream_id, d_D, transposed ? 1 : 0, 0, p);
     return launch_spmm(g, transposed ? g->t : g->a, p, s);
 }
@@ -73,53 +70,26 @@ int gnx_spmm_dropped(gnx_graph_t g, const float *d_D, float dropout_p, uint64_t 
 int gnx_spmm_dropped_chained(gnx_graph_t g, const float *d_D, float dropout_p, uint64_t seed, uint64_t stream_id, int x_prescaled,
                              const float *d_D_next, const float *d_X, int64_t ldx, int64_t C, const float *d_H0, int64_t ldh0, float beta,
                              float alpha, int act, float *d_out, int64_t ldo, void *stream) {
-    int rc = check_common("gnx_spmm_dropped_chained", g, d_X, ldx, C, d_H0, ldh0, d_out, ldo);
-    if (rc != GNX_OK) return rc;
-    GNX_CHECK_ARG((act & ~GNX_ACT_SKIP_EMPTY) == GNX_ACT_NONE || (act & ~GNX_ACT_SKIP_EMPTY) == GNX_ACT_RELU,
-                  "gnx_spmm_dropped_chained: invalid activation %d", act);
-    if (!g->a.empty_rows_unreferenced) act &= ~GNX_ACT_SKIP_EMPTY;       // honoured only when nobody gathers the rows it would leave untouched
-    GNX_CHECK_ARG(d_D != nullptr, "gnx_spmm_dropped_chained: NULL degree scales");
-    GNX_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "dropout rate %g outside [0, 1)", (double)dropout_p);
-    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols || g->blk_col_gid != nullptr, "gnx_spmm_dropped_chained: needs a square graph or a vertex block");
-    rc = refuse_duplicates(g, "gnx_spmm_dropped_chained");
-    if (rc != GNX_OK) return rc;
-    SpmmArgs p{};
-    set_values(g, false, p);
-    p.X = d_X; p.ldx = ldx; p.H0 = d_H0; p.ldh0 = ldh0; p.beta = beta; p.alpha = alpha; p.act = act;
-    p.out = d_out; p.ldo = ldo; p.C = (int)C;
-    p.out_scale = d_D_next ? d_D_next + g->blk_row0_buf : nullptr;
-    set_drop_fuse(g, dropout_p, seed, stream_id, d_D, 0, x_prescaled, p);
-    return launch_spmm(g, g->a, p, (hipStream_t)stream);
+    const char *fn = "gnx_spmm_dropped_chained";
+    const auto admit = [fn](gnx_graph *g, hipStream_t) -> int {
+        GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols || g->blk_col_gid != nullptr, "%s: needs a square graph or a vertex block", fn);
+        return refuse_duplicates(g, fn);
+    };
+    return spmm_dropped_chained<F32Rows>(fn, admit, g, d_D, dropout_p, seed, stream_id, x_prescaled, d_D_next, d_X, ldx, C, d_H0, ldh0, beta,
+                                         alpha, act, d_out, 0, ldo, 0, stream);
 }
 
 int gnx_spmm_dropped_back(gnx_graph_t g, const float *d_D, float dropout_p, uint64_t seed, uint64_t stream_id, int x_prescaled,
                           const float *d_D_next, const float *d_X, int64_t ldx, int64_t C, const float *d_S_in, int64_t lds_in,
                           float s_alpha, float s_beta, float *d_S_out, int64_t lds_out, float y_beta, float *d_Y_out, int64_t ldy,
                           int act, void *stream) {
-    int rc = check_common("gnx_spmm_dropped_back", g, d_X, ldx, C, d_S_in, lds_in, d_S_out, lds_out);
-    if (rc != GNX_OK) return rc;
-    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_SKIP_EMPTY, "gnx_spmm_dropped_back: act must be GNX_ACT_NONE or GNX_ACT_SKIP_EMPTY");
-    GNX_CHECK_ARG(act == GNX_ACT_NONE || (const void *)d_S_in == (const void *)d_S_out,
-                  "gnx_spmm_dropped_back: GNX_ACT_SKIP_EMPTY needs the sum updated in place");
-    GNX_CHECK_ARG(d_D != nullptr && d_S_in != nullptr, "gnx_spmm_dropped_back: NULL degree scales / running sum");
-    GNX_CHECK_ARG(d_Y_out == nullptr || (ldy >= C && (const void *)d_Y_out != (const void *)d_X && (const void *)d_Y_out != (const void *)d_S_out
-                                         && (const void *)d_Y_out != (const void *)d_S_in),
-                  "gnx_spmm_dropped_back: the pre-scaled output needs a buffer of its own");
-    GNX_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "dropout rate %g outside [0, 1)", (double)dropout_p);
-    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols && g->blk_col_gid == nullptr, "gnx_spmm_dropped_back: needs a square stand-alone graph");
-    rc = refuse_duplicates(g, "gnx_spmm_dropped_back");
-    if (rc != GNX_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    rc = ensure_transpose(g, s);
-    if (rc != GNX_OK) return rc;
-    if (!g->t.empty_rows_unreferenced) act = GNX_ACT_NONE;               // honoured only when nobody gathers the rows it would leave untouched
-    SpmmArgs p{};
-    set_values(g, true, p);
-    p.X = d_X; p.ldx = ldx; p.H0 = d_S_in; p.ldh0 = lds_in; p.beta = s_beta; p.alpha = s_alpha; p.act = act;
-    p.out = d_S_out; p.ldo = lds_out; p.C = (int)C;
-    p.out2 = d_Y_out; p.ldo2 = ldy; p.beta2 = y_beta; p.out2_scale = d_Y_out ? d_D_next : nullptr;
-    set_drop_fuse(g, dropout_p, seed, stream_id, d_D, 1, x_prescaled, p);   // (stand-alone handle: the block keys are 0 / null)
-    return launch_spmm(g, g->t, p, s);
+    const char *fn = "gnx_spmm_dropped_back";
+    const auto admit = [fn](gnx_graph *g, hipStream_t) -> int {
+        GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols && g->blk_col_gid == nullptr, "%s: needs a square stand-alone graph", fn);
+        return refuse_duplicates(g, fn);
+    };
+    return spmm_dropped_back<F32Rows>(fn, admit, g, d_D, dropout_p, seed, stream_id, x_prescaled, d_D_next, d_X, ldx, C, d_S_in, lds_in, s_alpha,
+                                      s_beta, d_S_out, lds_out, y_beta, d_Y_out, ldy, act, 0, stream);
 }
 
 }  // extern "C"

@@ -294,6 +294,19 @@ def _same_device(g, *tensors):
             raise Exception(f"spmm: operand on {t.device}, the graph lives on {g.device}")
 
 
+def _mix_operand(H0, shape, bias=False):
+    """(H0 as f32 rows, ldh0) of a launch whose result has ``shape``; (None, 0) without one.  ``bias``: one row serves every output
+    row (ldh0 = 0)."""
+    if H0 is None:
+        return None, 0
+    H0 = _as_f32_rows(H0)
+    if bias and tuple(H0.shape) == (1, shape[1]) and shape[0] != 1:
+        return H0.contiguous(), 0
+    if tuple(H0.shape) != tuple(shape):
+        raise Exception("spmm: H0 shape mismatch")
+    return H0, H0.stride(0)
+
+
 def _launch(adj: Adjacency, X, H0, beta, alpha, act, transposed=False, out=None, out_rows=None):
     g = adj.graph
     nat.require_cuda(X, H0)
@@ -308,15 +321,7 @@ def _launch(adj: Adjacency, X, H0, beta, alpha, act, transposed=False, out=None,
         out = torch.empty((rows_out, C), dtype=torch.float32, device=X.device)
     elif (tuple(out.shape) != (rows_out, C) or out.dtype != torch.float32 or out.stride(1) != 1 or not out.is_cuda):
         raise Exception("spmm: bad output buffer")
-    ldh0 = 0
-    if H0 is not None:
-        H0 = _as_f32_rows(H0)
-        if tuple(H0.shape) == (1, C) and rows_out != 1:
-            H0, ldh0 = H0.contiguous(), 0                       # one row for every output row (bias)
-        elif tuple(H0.shape) != (rows_out, C):
-            raise Exception("spmm: H0 shape mismatch")
-        else:
-            ldh0 = H0.stride(0)
+    H0, ldh0 = _mix_operand(H0, (rows_out, C), bias=True)
     if isinstance(adj, DroppedAdjacency) and out_rows is None:       # weights produced inside the kernel
         with nat.on_device(X.device):
             nat.check(nat.lib().gnx_spmm_dropped(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, 1 if transposed else 0,
@@ -343,29 +348,36 @@ def _launch(adj: Adjacency, X, H0, beta, alpha, act, transposed=False, out=None,
     return out
 
 
-def _launch_chained(adj: "DroppedAdjacency", X, H0, beta, alpha, prescaled, D_next, skip_empty=False, order=None):
+def _launch_chained(adj: "DroppedAdjacency", X, H0, beta, alpha, prescaled, D_next, skip_empty=False, order=None, out_bf16=False):
     """One forward training iteration inside a loop (gnx_spmm_dropped_chained): X carries its column scale when ``prescaled``,
     the result carries ``D_next`` (the next iteration's column scale) unless that is None.  ``skip_empty``: rows without entries
     are left untouched (every iteration but the last: nobody gathers them; the library ignores it on graphs where somebody does).
     ``order`` (an OR of nat.ORD_X / nat.ORD_OUT, or None): the launch goes through gnx_spmm_dropped_chained_ord -- X stored in / the
-    result written in the graph's gather order; same bits."""
+    result written in the graph's gather order; same bits.
+    A bf16 X: the gathered rows are stored as bf16 (gnx_spmm_dropped_chained_bf16); f32 H0; the result is f32, or bf16 (rounded once,
+    after the D_next scale) with ``out_bf16``.  There is no gather-order entry for bf16 rows."""
     g = adj.graph
+    bf16 = X.dtype == torch.bfloat16
     nat.require_cuda(X, H0)
     _same_device(g, X, H0, adj.D, D_next)
-    if X.shape[0] != g.n_cols or tuple(H0.shape) != (g.n_rows, X.shape[1]) or not X.is_contiguous() or not H0.is_contiguous():
-        raise Exception("chained propagation: bad operand shapes")
-    out = torch.empty((g.n_rows, X.shape[1]), dtype=torch.float32, device=X.device)
-    act = nat.ACT_NONE | (nat.ACT_SKIP_EMPTY if skip_empty else 0)
+    C = X.shape[1]
+    if (X.dtype not in (torch.float32, torch.bfloat16) or H0.dtype != torch.float32 or X.shape[0] != g.n_cols
+            or tuple(H0.shape) != (g.n_rows, C) or not X.is_contiguous() or not H0.is_contiguous() or (out_bf16 and not bf16)):
+        raise Exception("chained bf16 propagation: bad operands" if bf16 else "chained propagation: bad operand shapes")
+    if bf16 and order is not None:
+        raise Exception("chained bf16 propagation: bf16 rows have no gather-order entry")
+    out = torch.empty((g.n_rows, C), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=X.device)
+    lib = nat.lib()
+    if bf16:
+        fn, tail = lib.gnx_spmm_dropped_chained_bf16, (1 if out_bf16 else 0, out.stride(0))
+    elif order is not None:
+        fn, tail = lib.gnx_spmm_dropped_chained_ord, (out.stride(0), int(order))
+    else:
+        fn, tail = lib.gnx_spmm_dropped_chained, (out.stride(0),)
     with nat.on_device(X.device):
-        if order is not None:
-            nat.check(nat.lib().gnx_spmm_dropped_chained_ord(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, 1 if prescaled else 0,
-                                                             nat.ptr(D_next), nat.ptr(X), X.stride(0), X.shape[1], nat.ptr(H0), H0.stride(0),
-                                                             float(beta), float(alpha), act, nat.ptr(out), out.stride(0), int(order),
-                                                             nat.current_stream()))
-            return out
-        nat.check(nat.lib().gnx_spmm_dropped_chained(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, 1 if prescaled else 0,
-                                                     nat.ptr(D_next), nat.ptr(X), X.stride(0), X.shape[1], nat.ptr(H0), H0.stride(0),
-                                                     float(beta), float(alpha), act, nat.ptr(out), out.stride(0), nat.current_stream()))
+        nat.check(fn(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, 1 if prescaled else 0, nat.ptr(D_next), nat.ptr(X), X.stride(0), C,
+                     nat.ptr(H0), H0.stride(0), float(beta), float(alpha), nat.ACT_NONE | (nat.ACT_SKIP_EMPTY if skip_empty else 0),
+                     nat.ptr(out), *tail, nat.current_stream()))
     return out
 
 
@@ -373,39 +385,65 @@ def _launch_back(adj: "DroppedAdjacency", X, prescaled, D_next, S_in, s_alpha, s
     """One backward training iteration inside a loop (gnx_spmm_dropped_back): acc = A_k^T X over the transposed structure, weights
     made in the kernel; S_out = s_beta acc + s_alpha S_in (S_in may be S_out), Y_out = y_beta acc * D_next (skipped when None).
     ``order`` (an OR of nat.ORD_X / nat.ORD_OUT, or None): through gnx_spmm_dropped_back_ord -- X stored in / Y_out written in the
-    graph's gather order, the running sum in the caller's; same bits."""
+    graph's gather order, the running sum in the caller's; same bits.
+    A bf16 X: the gathered rows and the pre-scaled result Y_out are stored as bf16 (gnx_spmm_dropped_back_bf16); the running sum
+    S_in / S_out is f32.  There is no gather-order entry for bf16 rows."""
     g = adj.graph
+    bf16 = X.dtype == torch.bfloat16
     nat.require_cuda(X, S_in, S_out)
     _same_device(g, X, S_in, S_out, Y_out, adj.D, D_next)
     C = X.shape[1]
-    if any(t is not None and (tuple(t.shape) != (g.n_rows, C) or not t.is_contiguous() or t.dtype != torch.float32) for t in (X, S_in, S_out, Y_out)):
-        raise Exception("chained backward: bad operand shapes")
+    rows = torch.bfloat16 if bf16 else torch.float32
+    if any(t is not None and (tuple(t.shape) != (g.n_rows, C) or not t.is_contiguous() or t.dtype != dt)
+           for t, dt in ((X, rows), (S_in, torch.float32), (S_out, torch.float32), (Y_out, rows))):
+        raise Exception("chained bf16 backward: bad operands" if bf16 else "chained backward: bad operand shapes")
+    if bf16 and order is not None:
+        raise Exception("chained bf16 backward: bf16 rows have no gather-order entry")
+    lib = nat.lib()
+    fn = lib.gnx_spmm_dropped_back_bf16 if bf16 else lib.gnx_spmm_dropped_back_ord if order is not None else lib.gnx_spmm_dropped_back
+    tail = () if order is None else (int(order),)
     with nat.on_device(X.device):
-        if order is not None:
-            nat.check(nat.lib().gnx_spmm_dropped_back_ord(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, 1 if prescaled else 0,
-                                                          nat.ptr(D_next), nat.ptr(X), C, C, nat.ptr(S_in), C, float(s_alpha), float(s_beta),
-                                                          nat.ptr(S_out), C, float(y_beta), nat.ptr(Y_out), C,
-                                                          nat.ACT_SKIP_EMPTY if skip_empty else nat.ACT_NONE, int(order), nat.current_stream()))
-            return
-        nat.check(nat.lib().gnx_spmm_dropped_back(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, 1 if prescaled else 0, nat.ptr(D_next),
-                                                  nat.ptr(X), C, C, nat.ptr(S_in), C, float(s_alpha), float(s_beta), nat.ptr(S_out), C,
-                                                  float(y_beta), nat.ptr(Y_out), C, nat.ACT_SKIP_EMPTY if skip_empty else nat.ACT_NONE,
-                                                  nat.current_stream()))
+        nat.check(fn(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, 1 if prescaled else 0, nat.ptr(D_next), nat.ptr(X), C, C,
+                     nat.ptr(S_in), C, float(s_alpha), float(s_beta), nat.ptr(S_out), C, float(y_beta), nat.ptr(Y_out), C,
+                     nat.ACT_SKIP_EMPTY if skip_empty else nat.ACT_NONE, *tail, nat.current_stream()))
 
 
-def _backward_chained(adjs, g, a, relabelled=False):
+_launch_chained_bf16 = _launch_chained     # (the dtype of X picks the entry)
+_launch_back_bf16 = _launch_back
+
+
+def _forward_chained(adjs, H0, a, relabelled=False, bf16=False):
+    """H_K of K >= 1 chained training iterations from f32 H0 ([n, C] contiguous), one gnx_spmm_dropped_chained each: the next
+    iteration's column scale rides out with the rows, so from k = 1 on no per-entry scale gather is left.  ``relabelled``: the iterate
+    is handed from launch to launch in the graph's gather order (gnx_spmm_dropped_chained_ord: H0 enters and H_K leaves in the caller's);
+    same bits.  ``bf16``: the iterate is stored as bf16 between launches: X_0 = bf(H0); iteration k gathers X_k and writes
+    bf(H_{k+1} * D_{k+1}), the last one f32 H_K."""
+    K = len(adjs)
+    X = to_bf16(H0) if bf16 else H0
+    for k, adj in enumerate(adjs):
+        last = k == K - 1
+        order = ((nat.ORD_X if k > 0 else 0) | (0 if last else nat.ORD_OUT)) if relabelled else None
+        # (rows without entries are a * H0 in the result and gathered by nobody: only the last iteration writes them)
+        X = _launch_chained(adj, X, H0, 1.0 - a, a, prescaled=k > 0, D_next=None if last else adjs[k + 1].D, skip_empty=not last,
+                            order=order, out_bf16=bf16 and not last)
+    return X
+
+
+def _backward_chained(adjs, g, a, relabelled=False, bf16=False):
     """dH0 of K chained training iterations for the upstream gradient ``g``: g_k = (1-a) A_k^T g_{k+1}, dH0 = g_0 + a (g_1 + ... +
     g_K), as K calls of gnx_spmm_dropped_back -- every call adds its g_k to the running sum in its epilogue and hands the next call
     its operand pre-scaled by that call's column scale, so no gradient of an iteration is kept, no per-entry scale is gathered
     and no separate summation pass exists.  ``relabelled`` (K > 1): the operand handed from call to call lives in the graph's gather
-    order (gnx_spmm_dropped_back_ord: the first call gathers ``g`` as it is, the running sum stays in the caller's order); same bits."""
+    order (gnx_spmm_dropped_back_ord: the first call gathers ``g`` as it is, the running sum stays in the caller's order); same bits.
+    ``bf16``: the gathered gradient is stored as bf16: the first call gathers bf(g), every later one the bf((1-a) acc * D) its
+    predecessor wrote; the running sum starts from f32 g and only ever adds f32 sums."""
     K = len(adjs)
     g = _as_f32_rows(g).contiguous()
     S = torch.empty_like(g)
-    X = g
+    X = to_bf16(g) if bf16 else g
     for k in range(K - 1, -1, -1):
         first, last = k == K - 1, k == 0
-        Y = None if last else torch.empty_like(g)
+        Y = None if last else torch.empty_like(X)
         order = ((0 if first else nat.ORD_X) | (0 if last else nat.ORD_OUT)) if relabelled else None
         # rows without entries: their g_k is 0 -- after the first call their sum is final and their Y row is never gathered
         _launch_back(adjs[k], X, not first, None if last else adjs[k - 1].D, g if first else S, a if first else 1.0,
@@ -414,69 +452,14 @@ def _backward_chained(adjs, g, a, relabelled=False):
     return S
 
 
-def _launch_chained_bf16(adj: "DroppedAdjacency", X, H0, beta, alpha, prescaled, D_next, skip_empty=False, out_bf16=False):
-    """_launch_chained with the gathered rows X stored as bf16 (gnx_spmm_dropped_chained_bf16); f32 H0; the result is f32, or bf16
-    (rounded once, after the D_next scale) with ``out_bf16``."""
-    g = adj.graph
-    nat.require_cuda(X, H0)
-    _same_device(g, X, H0, adj.D, D_next)
-    if (X.dtype != torch.bfloat16 or H0.dtype != torch.float32 or X.shape[0] != g.n_cols or tuple(H0.shape) != (g.n_rows, X.shape[1])
-            or not X.is_contiguous() or not H0.is_contiguous()):
-        raise Exception("chained bf16 propagation: bad operands")
-    out = torch.empty((g.n_rows, X.shape[1]), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=X.device)
-    with nat.on_device(X.device):
-        nat.check(nat.lib().gnx_spmm_dropped_chained_bf16(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, 1 if prescaled else 0,
-                                                          nat.ptr(D_next), nat.ptr(X), X.stride(0), X.shape[1], nat.ptr(H0), H0.stride(0),
-                                                          float(beta), float(alpha),
-                                                          nat.ACT_NONE | (nat.ACT_SKIP_EMPTY if skip_empty else 0), nat.ptr(out),
-                                                          1 if out_bf16 else 0, out.stride(0), nat.current_stream()))
-    return out
-
-
-def _launch_back_bf16(adj: "DroppedAdjacency", X, prescaled, D_next, S_in, s_alpha, s_beta, S_out, y_beta, Y_out, skip_empty=False):
-    """_launch_back with the gathered rows X and the pre-scaled result Y_out stored as bf16 (gnx_spmm_dropped_back_bf16); the running
-    sum S_in / S_out is f32."""
-    g = adj.graph
-    nat.require_cuda(X, S_in, S_out)
-    _same_device(g, X, S_in, S_out, Y_out, adj.D, D_next)
-    C = X.shape[1]
-    if any(t is not None and (tuple(t.shape) != (g.n_rows, C) or not t.is_contiguous() or t.dtype != dt)
-           for t, dt in ((X, torch.bfloat16), (S_in, torch.float32), (S_out, torch.float32), (Y_out, torch.bfloat16))):
-        raise Exception("chained bf16 backward: bad operands")
-    with nat.on_device(X.device):
-        nat.check(nat.lib().gnx_spmm_dropped_back_bf16(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, 1 if prescaled else 0,
-                                                       nat.ptr(D_next), nat.ptr(X), C, C, nat.ptr(S_in), C, float(s_alpha), float(s_beta),
-                                                       nat.ptr(S_out), C, float(y_beta), nat.ptr(Y_out), C,
-                                                       nat.ACT_SKIP_EMPTY if skip_empty else nat.ACT_NONE, nat.current_stream()))
-
-
 def _forward_chained_bf16(adjs, H0, a):
-    """H_K of K >= 1 chained training iterations from f32 H0 ([n, C] contiguous) with the iterate stored as bf16 between launches:
-    X_0 = bf(H0); iteration k gathers X_k and writes bf(H_{k+1} * D_{k+1}), the last one f32 H_K."""
-    K = len(adjs)
-    X = to_bf16(H0)
-    for k, adj in enumerate(adjs):
-        last = k == K - 1
-        # (rows without entries are a * H0 in the result and gathered by nobody: only the last iteration writes them)
-        X = _launch_chained_bf16(adj, X, H0, 1.0 - a, a, prescaled=k > 0, D_next=None if last else adjs[k + 1].D, skip_empty=not last,
-                                 out_bf16=not last)
-    return X
+    """_forward_chained with the iterate stored as bf16 between launches."""
+    return _forward_chained(adjs, H0, a, bf16=True)
 
 
 def _backward_chained_bf16(adjs, g, a):
-    """_backward_chained with the gathered gradient stored as bf16: the first call gathers bf(g), every later one the
-    bf((1-a) acc * D) its predecessor wrote; the running sum starts from f32 g and only ever adds f32 sums."""
-    K = len(adjs)
-    g = _as_f32_rows(g).contiguous()
-    S = torch.empty_like(g)
-    X = to_bf16(g)
-    for k in range(K - 1, -1, -1):
-        first, last = k == K - 1, k == 0
-        Y = None if last else torch.empty(g.shape, dtype=torch.bfloat16, device=g.device)
-        _launch_back_bf16(adjs[k], X, not first, None if last else adjs[k - 1].D, g if first else S, a if first else 1.0,
-                          (1.0 - a) if last else a * (1.0 - a), S, 1.0 - a, Y, skip_empty=not first)
-        X = Y
-    return S
+    """_backward_chained with the gathered gradient stored as bf16."""
+    return _backward_chained(adjs, g, a, bf16=True)
 
 
 def launch_rows(adj: Adjacency, X, H0, beta, alpha, rows, out, act=nat.ACT_NONE):
@@ -493,12 +476,7 @@ def launch_rows(adj: Adjacency, X, H0, beta, alpha, rows, out, act=nat.ACT_NONE)
         raise Exception("spmm: bad row map")
     if out.dtype != torch.float32 or out.dim() != 2 or out.shape[1] != C or out.stride(1) != 1:
         raise Exception("spmm: bad output buffer")
-    ldh0 = 0
-    if H0 is not None:
-        H0 = _as_f32_rows(H0)
-        if tuple(H0.shape) != tuple(out.shape):
-            raise Exception("spmm: H0 shape mismatch")
-        ldh0 = H0.stride(0)
+    H0, ldh0 = _mix_operand(H0, out.shape)
     with nat.on_device(X.device):
         nat.check(nat.lib().gnx_spmm_rows(g.handle, nat.ptr(adj.vals), nat.ptr(X), X.stride(0), C, nat.ptr(H0), ldh0, float(beta),
                                           float(alpha), int(act), nat.ptr(rows), nat.ptr(out), out.stride(0),
@@ -596,6 +574,15 @@ def _padded(H: torch.Tensor, Cp: int) -> torch.Tensor:
     return out
 
 
+def _unpadded(H: torch.Tensor, C: int) -> torch.Tensor:
+    return H if H.shape[1] == C else H[:, :C].contiguous()
+
+
+def _one_fused_graph(adjs) -> bool:
+    """Every iteration's adjacency makes its weights in the kernels, over one graph: what the chained loops need."""
+    return all(isinstance(adj, DroppedAdjacency) and adj.graph is adjs[0].graph for adj in adjs)
+
+
 class _PPRLoop(torch.autograd.Function):
     """K PPRIteration steps as ONE autograd node.  The step is linear in H, so the backward needs no
     stored activations: g_k = (1-a) A_k^T g_{k+1}, dH0 = g_0 + a * sum_k g_{k+1}.  In training mode
@@ -609,67 +596,66 @@ class _PPRLoop(torch.autograd.Function):
     @staticmethod
     def forward(ctx, H0, make_adj, a, K, relu=False, storage=torch.float32, gather_order="caller"):
         ctx.make_adj, ctx.a, ctx.K, ctx.relu = make_adj, a, K, relu
-        ctx.relabelled = False
         act = nat.ACT_RELU if relu else nat.ACT_NONE
         H0 = _as_f32_rows(H0).contiguous()
         ctx.C = C = H0.shape[1]
+        n = H0.shape[0]
         first = make_adj(0, False) if K > 0 else None
-        ctx.bf16 = False
-        made = None                     # the K adjacencies if the bf16 branch asked for them: make_adj is called once per iteration
+        adjs = None                     # the K adjacencies once a chained loop asked for them: make_adj is called once per iteration
+        # which loop runs, decided once (the backward reads it): "bf16" / "caller" / "relabelled" = the chained loops, "layers" = one
+        # launch per iteration through _launch
+        ctx.loop = "layers"
         if _bf16(storage) and _bf16_training_applies(first, K, relu, C):
             # opt-in bf16 storage of the gathered operand (gnx_spmm_dropped_chained_bf16 / _back_bf16): the chained loop, on graphs
             # with duplicate entries too (there is no materialised bf16 form whose bits it would have to keep)
-            made = adjs = [first] + [make_adj(k, False) for k in range(1, K)]
-            if all(isinstance(adj, DroppedAdjacency) and adj.graph is first.graph for adj in adjs):
-                ctx.bf16 = True
-                H = _forward_chained_bf16(adjs, _padded(H0, friendly_width_bf16(C, H0.shape[0])), a)
-                return H if H.shape[1] == C else H[:, :C].contiguous()
-        H0 = _padded(H0, friendly_width(C, H0.shape[0]))
-        H = H0
-        kept = []
-        if K > 1 and isinstance(first, DroppedAdjacency) and not relu and first.graph.nnz_entries == first.graph.nnz:
+            adjs = [first] + [make_adj(k, False) for k in range(1, K)]
+            if _one_fused_graph(adjs):
+                ctx.loop = "bf16"
+        if ctx.loop == "layers" and K > 1 and isinstance(first, DroppedAdjacency) and not relu and first.graph.nnz_entries == first.graph.nnz:
             # weights made in the kernels (only the K degree-scale vectors exist): the next iteration's column scale rides out with
             # the rows, so from k = 1 on no per-entry scale gather is left (gnx_spmm_dropped_chained).  Not on graphs with duplicate
             # entries: their fused form replaces the materialised one, whose results it keeps bit for bit (one gnx_spmm_dropped per
             # iteration, below), where the chained loop would round differently
-            adjs = made if made is not None else [first] + [make_adj(k, False) for k in range(1, K)]
-            chained = all(isinstance(adj, DroppedAdjacency) and adj.graph is first.graph for adj in adjs)
-            ctx.chained = chained and first.graph.n_rows == first.graph.n_cols
-            # the iterate handed from launch to launch in the graph's gather order (gnx_spmm_dropped_chained_ord): the same bits
-            ctx.relabelled = relabelled = ctx.chained and _train_gather_applies(gather_order, first.graph, H0.shape[1])
-            for k, adj in enumerate(adjs):
-                if chained:
-                    order = ((nat.ORD_X if k > 0 else 0) | (nat.ORD_OUT if k + 1 < K else 0)) if relabelled else None
-                    # (rows without entries are a * H0 in the result and gathered by nobody: only the last iteration writes them)
-                    H = _launch_chained(adj, H, H0, 1.0 - a, a, prescaled=k > 0, D_next=adjs[k + 1].D if k + 1 < K else None,
-                                        skip_empty=k + 1 < K, order=order)
-                else:
-                    H = _launch(adj, H, H0, 1.0 - a, a, nat.ACT_NONE)
-        else:
-            for k in range(K):           # one adjacency alive at a time (a materialised one is an nnz-sized array)
-                H = _launch(first if k == 0 else made[k] if made is not None else make_adj(k, False), H, H0, 1.0 - a, a, act)
-                if relu:
-                    kept.append(H)
+            adjs = adjs if adjs is not None else [first] + [make_adj(k, False) for k in range(1, K)]
+            if _one_fused_graph(adjs) and first.graph.n_rows == first.graph.n_cols:
+                # the iterate handed from launch to launch in the graph's gather order (gnx_spmm_dropped_chained_ord): the same bits
+                ctx.loop = "relabelled" if _train_gather_applies(gather_order, first.graph, friendly_width(C, n)) else "caller"
+        if ctx.loop == "bf16":
+            return _unpadded(_forward_chained_bf16(adjs, _padded(H0, friendly_width_bf16(C, n)), a), C)
+        H0 = _padded(H0, friendly_width(C, n))
+        if ctx.loop != "layers":
+            return _unpadded(_forward_chained(adjs, H0, a, relabelled=ctx.loop == "relabelled"), C)
+        H = H0
+        kept = []
+        for k in range(K):               # one adjacency alive at a time (a materialised one is an nnz-sized array)
+            H = _launch(first if k == 0 else adjs[k] if adjs is not None else make_adj(k, False), H, H0, 1.0 - a, a, act)
+            if relu:
+                kept.append(H)
         if relu:
             ctx.save_for_backward(*kept)
-        return H if H.shape[1] == C else H[:, :C].contiguous()
+        return _unpadded(H, C)
 
     @staticmethod
     def backward(ctx, g):
+        gH0 = None
+        if ctx.loop != "layers":
+            adjs = [ctx.make_adj(k, True) for k in range(ctx.K)]
+            fused = all(isinstance(adj, DroppedAdjacency) for adj in adjs)
+            if ctx.loop == "bf16":
+                if not fused:
+                    raise Exception("ppr_loop: the bf16 forward ran on fused adjacencies, the backward was handed others")
+                gH0 = _backward_chained_bf16(adjs, _padded(_as_f32_rows(g).contiguous(), friendly_width_bf16(ctx.C, g.shape[0])), ctx.a)
+            elif fused:
+                gH0 = _backward_chained(adjs, _padded(g.contiguous(), friendly_width(ctx.C, g.shape[0])), ctx.a,
+                                        relabelled=ctx.loop == "relabelled")
+        if gH0 is None:
+            gH0 = _PPRLoop._backward_layers(ctx, _padded(g.contiguous(), friendly_width(ctx.C, g.shape[0])))
+        return _unpadded(gH0, ctx.C), None, None, None, None, None, None
+
+    @staticmethod
+    def _backward_layers(ctx, g):
         # dH0 = g_0 + a (g_1 + ... + g_K): the gradients of the iterations are KEPT (as many as a tenth of the card's memory
         # holds, at most 15) and added up by one pass (gnx_linear_combination) instead of a read-modify-write of dH0 per iteration
-        if ctx.bf16:
-            adjs = [ctx.make_adj(k, True) for k in range(ctx.K)]
-            if not all(isinstance(adj, DroppedAdjacency) for adj in adjs):
-                raise Exception("ppr_loop: the bf16 forward ran on fused adjacencies, the backward was handed others")
-            gH0 = _backward_chained_bf16(adjs, _padded(_as_f32_rows(g).contiguous(), friendly_width_bf16(ctx.C, g.shape[0])), ctx.a)
-            return (gH0 if gH0.shape[1] == ctx.C else gH0[:, :ctx.C].contiguous()), None, None, None, None, None, None
-        g = _padded(g.contiguous(), friendly_width(ctx.C, g.shape[0]))
-        if getattr(ctx, "chained", False):
-            adjs = [ctx.make_adj(k, True) for k in range(ctx.K)]
-            if all(isinstance(adj, DroppedAdjacency) for adj in adjs):
-                gH0 = _backward_chained(adjs, g, ctx.a, relabelled=ctx.relabelled)
-                return (gH0 if gH0.shape[1] == ctx.C else gH0[:, :ctx.C].contiguous()), None, None, None, None, None, None
         outs = ctx.saved_tensors if ctx.relu else None
         room = int(0.1 * torch.cuda.get_device_properties(g.device).total_memory) // max(g.numel() * 4, 1)
         limit = max(2, min(LINCOMB_TERMS - 1, room))
@@ -682,8 +668,7 @@ class _PPRLoop(torch.autograd.Function):
                 total, pending = linear_combination(([(total, 1.0)] if total is not None else []) + pending), []
             g = _launch(ctx.make_adj(k, True), g, None, 1.0 - ctx.a, 0.0, nat.ACT_NONE, transposed=True)
         pending.append((g, 1.0))
-        gH0 = linear_combination(([(total, 1.0)] if total is not None else []) + pending)
-        return (gH0 if gH0.shape[1] == ctx.C else gH0[:, :ctx.C].contiguous()), None, None, None, None, None, None
+        return linear_combination(([(total, 1.0)] if total is not None else []) + pending)
 
 
 LINCOMB_TERMS = 16
@@ -853,7 +838,7 @@ def appnp_propagate(adj: Adjacency, H0: torch.Tensor, a: float = 0.1, iterations
         nat.check(nat.lib().gnx_appnp_propagate_act(g.handle, nat.ptr(adj.vals), nat.ptr(adj.diag), nat.ptr(H0), float(a),
                                                     int(iterations), H0.shape[1], nat.ACT_RELU if relu else nat.ACT_NONE,
                                                     nat.ptr(out), nat.ptr(work), nat.current_stream()))
-    return out if out.shape[1] == C else out[:, :C].contiguous()
+    return _unpadded(out, C)
 
 
 # ---- opt-in bf16 feature storage (inference only) ----------------------------------------------------------------------------
@@ -930,15 +915,7 @@ def _launch_bf16(adj: Adjacency, X, H0, beta, alpha, act, out_bf16=False, out=No
                 or out.stride(0) < C or not out.is_cuda):
             raise Exception("spmm: bad output buffer")
         out_bf16 = out.dtype == torch.bfloat16
-    ldh0 = 0
-    if H0 is not None:
-        H0 = _as_f32_rows(H0)
-        if tuple(H0.shape) == (1, C) and g.n_rows != 1:
-            H0, ldh0 = H0.contiguous(), 0                       # one row for every output row (bias)
-        elif tuple(H0.shape) != (g.n_rows, C):
-            raise Exception("spmm: H0 shape mismatch")
-        else:
-            ldh0 = H0.stride(0)
+    H0, ldh0 = _mix_operand(H0, (g.n_rows, C), bias=True)
     with nat.on_device(Xb.device):
         nat.check(nat.lib().gnx_spmm_bf16(g.handle, nat.ptr(adj.vals), nat.ptr(adj.diag), nat.ptr(Xb), Xb.stride(0), C, nat.ptr(H0),
                                           ldh0, float(beta), float(alpha), int(act), nat.ptr(out), 1 if out_bf16 else 0, out.stride(0),
@@ -975,12 +952,7 @@ def launch_rows_bf16(adj: Adjacency, X, H0, beta, alpha, rows, out, act=nat.ACT_
         raise Exception("spmm: bad row map")
     if out.dtype not in (torch.float32, torch.bfloat16) or out.dim() != 2 or out.shape[1] != C or out.stride(1) != 1 or out.stride(0) < C:
         raise Exception("spmm: bad output buffer")
-    ldh0 = 0
-    if H0 is not None:
-        H0 = _as_f32_rows(H0)
-        if tuple(H0.shape) != tuple(out.shape):
-            raise Exception("spmm: H0 shape mismatch")
-        ldh0 = H0.stride(0)
+    H0, ldh0 = _mix_operand(H0, out.shape)
     with nat.on_device(X.device):
         nat.check(nat.lib().gnx_spmm_rows_bf16(g.handle, nat.ptr(adj.vals), nat.ptr(X), X.stride(0), C, nat.ptr(H0), ldh0, float(beta),
                                                float(alpha), int(act), nat.ptr(rows), nat.ptr(out),
@@ -999,7 +971,7 @@ def _appnp_propagate_bf16(adj: Adjacency, H0: torch.Tensor, a, iterations, relu)
         nat.check(nat.lib().gnx_appnp_propagate_bf16(g.handle, nat.ptr(adj.vals), nat.ptr(adj.diag), nat.ptr(H0), float(a),
                                                      int(iterations), H0.shape[1], nat.ACT_RELU if relu else nat.ACT_NONE,
                                                      nat.ptr(out), nat.ptr(work), nat.current_stream()))
-    return out if out.shape[1] == C else out[:, :C].contiguous()
+    return _unpadded(out, C)
 
 
 def gather_rows(X: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
