@@ -4,9 +4,27 @@
 // and the other widths through the bf16 kernels of gnx_spmm_bf16.hip in the f32 launch's summation order; rounding points in gnx.h.
 // gnx_gcnii_step_back (training, opt-in): the layer's backward past the relu gate as one launch of the same shape over the transposed
 // structure (k_spmm_gcnii_back); the MFMA block of the two kernels is one device function (tile_times_Ms).
+// gnx_gcnii_step_drop (training, opt-in): the forward with the layer's feature dropout (gcn.py:27, layered.py:44-45) in the store loop of
+// the same launch (k_spmm_gcnii<.., DROP>), masks from the counter RNG of the edge dropout; gnx_feature_dropout / gnx_feature_dropout_back are
+// the mask as a pass of its own (hub rows, the other widths, the generic composition) and the backward's gate.
 #include "gnx_spmm_device.h"
 
 namespace {
+
+// Feature dropout of a [n, C] matrix from the counter RNG of the edge dropout (hash_u24, gnx_internal.h), its parameters in the DropFuse
+// of the edge dropout (seed, stream, offset, thr, scale; nothing else of it is read): element (i, c) is kept iff
+// hash_u24(seed, stream + counter, i, c, 0) >= thr -- i the row id, c the column, duplicate rank 0, counter the handle's device-side
+// dropout counter (read when the kernel runs) -- and a kept value leaves as v * scale, a dropped one as +0.  thr == 0 keeps everything:
+// nothing is hashed (p == 0: scale = 1, the values leave as they are).
+__device__ __forceinline__ uint64_t drop_stream(const DropFuse &f) { return f.stream + (f.offset ? *f.offset : 0); }
+
+// x[v] <- drop(x[v]) for columns c .. c + VEC - 1 of row `row` (the row's round of the hash is shared by the columns)
+template <int VEC>
+__device__ __forceinline__ void drop_values(const DropFuse &f, uint64_t stream, int64_t row, int64_t c, float (&x)[VEC]) {
+#pragma unroll
+    for (int v = 0; v < VEC; ++v)
+        x[v] = (f.thr == 0 || hash_u24(f.seed, stream, (uint64_t)row, (uint64_t)(c + v), 0) >= f.thr) ? x[v] * f.scale : 0.f;
+}
 
 // tile <- act(tile . Ms) for one wave's 16-row tile T and the block's Ms (both row stride C + 4, C = 16 NT), on
 // v_mfma_f32_16x16x4_f32: the block the forward layer and its backward (k_spmm_gcnii_back) share.  The caller has put a wave
@@ -52,7 +70,11 @@ __device__ __forceinline__ void tile_times_Ms(float *__restrict__ T, const float
 // Written once over the row-storage policy R (gnx_spmm_device.h): F32Rows gathers float4 pieces of f32 rows, Bf16RowsT 8-byte pieces of
 // bf16 rows (four columns, widened exactly) and stores the finished row as f32 or rounded once to bf16; entry order, summation order,
 // the mix and the transform are the same code, so the bf16 instantiation over bf16-representable rows gives the bits of the f32 one.
-template <typename R, int NT, int U, int WPB>
+// DROP (gnx_gcnii_step_drop): the finished rows leave as drop(act(T . M)) -- the mask is made in the store loop, after the MFMA block,
+// where a lane holds row rows[ps] and columns c .. c + 3, so that the hash costs the gather loop no register; `mixed` still gets the
+// undropped T.  The mask's parameters are p.fuse (this kernel has no other use for it), so the
+// switch is a template argument alone and the instantiations without it are the kernel as it was.
+template <typename R, int NT, int U, int WPB, bool DROP = false>
 __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args p, const float *__restrict__ M, int64_t ldm, float *__restrict__ mixed) {
     constexpr int C = 16 * NT, G = 4 * NT, RPP = 64 / G, PASSES = 16 / RPP, STRIDE = C + 4;
     __shared__ float Ms[C * STRIDE];
@@ -118,6 +140,7 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args 
         const int rr = ps * RPP + lane / G;
         float o[4];
         vload<4>(o, T + rr * STRIDE + c);
+        if constexpr (DROP) drop_values<4>(p.fuse, drop_stream(p.fuse), rows[ps], c, o);
         R::template store<4>(p, rows[ps] * p.ldo, c, o, false);
     }
 }
@@ -261,30 +284,92 @@ void bind_fused(const Csr &m, SpmmArgs &p) {
     p.n_long = m.n_long; p.n_chunks = m.n_chunks; p.long_row = m.long_row; p.long_chunk = m.long_chunk;
 }
 
-}  // namespace
+// out[r, :] = drop(X[r, :]) for the rows listed (null: rows 0 .. n), r the row id the mask is keyed by; out may be X (each lane reads the
+// values it overwrites).  VEC = 4: 16-byte accesses (C, both row strides and both bases allow them)
+template <int VEC>
+__global__ __launch_bounds__(256) void k_feature_dropout(const float *X, int64_t ldx, const int32_t *__restrict__ rows, int64_t n, int64_t C,
+                                                        const DropFuse fd, float *out, int64_t ldo) {
+    const int64_t per_row = C / VEC, total = n * per_row, stride = (int64_t)gridDim.x * blockDim.x;
+    const uint64_t stream = drop_stream(fd);
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const int64_t i = e / per_row, r = rows ? (int64_t)rows[i] : i, c = (e % per_row) * VEC;
+        float x[VEC];
+        vload<VEC>(x, X + r * ldx + c);
+        drop_values<VEC>(fd, stream, r, c, x);
+        vstore<VEC>(out + r * ldo + c, x);
+    }
+}
 
-extern "C" {
+// The backward's gate in one pass: G = kept ? g * scale : +0, and with RELU also +0 where y <= 0 (y = the DROPPED forward output, so
+// y > 0 implies kept: the hash is taken only where y lets the value through, the same bits either way).  G may be g.
+template <int VEC, bool RELU>
+__global__ __launch_bounds__(256) void k_feature_dropout_back(const float *g, int64_t ldg, const float *__restrict__ y, int64_t ldy, int64_t n,
+                                                             int64_t C, const DropFuse fd, float *G, int64_t ldG) {
+    const int64_t per_row = C / VEC, total = n * per_row, stride = (int64_t)gridDim.x * blockDim.x;
+    const uint64_t stream = drop_stream(fd);
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const int64_t r = e / per_row, c = (e % per_row) * VEC;
+        float x[VEC];
+        vload<VEC>(x, g + r * ldg + c);
+        if constexpr (RELU) {
+            float out[VEC];
+            vload<VEC>(out, y + r * ldy + c);
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) {
+                if (out[v] <= 0.f) x[v] = 0.f;
+                else x[v] = (fd.thr == 0 || hash_u24(fd.seed, stream, (uint64_t)r, (uint64_t)(c + v), 0) >= fd.thr) ? x[v] * fd.scale : 0.f;
+            }
+        } else {
+            drop_values<VEC>(fd, stream, r, c, x);
+        }
+        vstore<VEC>(G + r * ldG + c, x);
+    }
+}
 
-int gnx_gcnii_step(gnx_graph_t g, const float *d_vals, const float *d_H, const float *d_H0, float a, int64_t C, const float *d_M,
-                   int64_t ldm, int act, float *d_out, float *d_mixed, void *stream) {
-    int rc = check_common("gnx_gcnii_step", g, d_H, C, C, d_H0, C, d_out, C);
+// the mask of one call: keep iff hash >= int(p * 2^24) (oracle/gnntf_oracle.py:dropout_threshold, over the caller's double), kept values
+// times the f32 scale of the edge dropout, 1.0f / (1.0f - (float)p); the handle lends its dropout counter
+int make_feat_drop(const char *fn, const gnx_graph *g, double p, uint64_t seed, uint64_t stream_id, DropFuse &fd) {
+    GNX_CHECK_ARG(p >= 0.0 && p < 1.0, "%s: dropout rate %g outside [0, 1)", fn, p);
+    fd.seed = seed; fd.stream = stream_id; fd.offset = g->stream_offset;
+    fd.thr = (uint32_t)(p * 16777216.0);
+    fd.scale = 1.0f / (1.0f - (float)p);
+    return GNX_OK;
+}
+
+void launch_feature_dropout(const float *X, int64_t ldx, const int32_t *rows, int64_t n, int64_t C, const DropFuse &fd, float *out, int64_t ldo,
+                            hipStream_t s) {
+    if (n == 0 || C == 0) return;
+    const bool v4 = C % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0 && aligned(X, 16) && aligned(out, 16);
+    const unsigned grid = (unsigned)std::min<int64_t>(blocks_for(n * (v4 ? C / 4 : C), 256), 1 << 20);
+    if (v4) hipLaunchKernelGGL(k_feature_dropout<4>, dim3(grid), dim3(256), 0, s, X, ldx, rows, n, C, fd, out, ldo);
+    else    hipLaunchKernelGGL(k_feature_dropout<1>, dim3(grid), dim3(256), 0, s, X, ldx, rows, n, C, fd, out, ldo);
+}
+
+// gnx_gcnii_step (fd == null) and gnx_gcnii_step_drop: one host path
+int gcnii_step(const char *fn, gnx_graph *g, const float *d_vals, const float *d_H, const float *d_H0, float a, int64_t C, const float *d_M,
+               int64_t ldm, int act, const DropFuse *fd, float *d_out, float *d_mixed, void *stream) {
+    int rc = check_common(fn, g, d_H, C, C, d_H0, C, d_out, C);
     if (rc != GNX_OK) return rc;
-    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU, "gnx_gcnii_step: invalid activation %d", act);
-    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "gnx_gcnii_step: needs a square graph");
-    GNX_CHECK_ARG(d_H0 != nullptr && d_M != nullptr && ldm >= C, "gnx_gcnii_step: NULL H0 / M or ldm < C");
+    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU, "%s: invalid activation %d", fn, act);
+    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "%s: needs a square graph", fn);
+    GNX_CHECK_ARG(d_H0 != nullptr && d_M != nullptr && ldm >= C, "%s: NULL H0 / M or ldm < C", fn);
     hipStream_t s = (hipStream_t)stream;
     const Csr &m = g->a;
     const float beta = (float)(1.0 - (double)a);
-    GNX_CHECK_ARG(d_mixed == nullptr || (d_mixed != d_out && d_mixed != d_H && d_mixed != d_H0), "gnx_gcnii_step: d_mixed must be a buffer of its own");
+    GNX_CHECK_ARG(d_mixed == nullptr || (d_mixed != d_out && d_mixed != d_H && d_mixed != d_H0), "%s: d_mixed must be a buffer of its own", fn);
     // C = 128 fits the kernel (135 KB of LDS: one block of eight waves per CU) and was measured: 19.2 ms against 11.8 ms for the two
     // launches on the config-4 graph -- eight waves per CU cannot keep the gathers fed -- so it takes the two-launch form
     const bool fusable = (C == 16 || C == 32 || C == 64) && aligned(d_H, 16) && aligned(d_H0, 16) && aligned(d_out, 16) && aligned(d_mixed, 16);
-    if (!fusable) {   // other widths: the fused SpMM+mix into d_mixed, then the transform on the matrix cores
-        GNX_CHECK_ARG(d_mixed != nullptr, "gnx_gcnii_step: width %lld needs d_mixed [n, C] (the mixed rows go through memory)", (long long)C);
+    if (!fusable) {   // other widths: the fused SpMM+mix into d_mixed, then the transform on the matrix cores (then the mask over all rows, in place)
+        GNX_CHECK_ARG(d_mixed != nullptr, "%s: width %lld needs d_mixed [n, C] (the mixed rows go through memory)", fn, (long long)C);
         rc = gnx_spmm(g, d_vals, nullptr, d_H, C, C, d_H0, C, beta, a, GNX_ACT_NONE, d_mixed, C, stream);
         if (rc != GNX_OK) return rc;
-        g->last_kernel = "spmm+dense_mfma";
-        return dense_rows(d_mixed, C, m.n_rows, C, d_M, ldm, C, nullptr, act, nullptr, nullptr, d_out, C, s);
+        g->last_kernel = fd ? "spmm+dense_mfma_drop" : "spmm+dense_mfma";
+        rc = dense_rows(d_mixed, C, m.n_rows, C, d_M, ldm, C, nullptr, act, nullptr, nullptr, d_out, C, s);
+        if (rc != GNX_OK || !fd) return rc;
+        launch_feature_dropout(d_out, C, nullptr, m.n_rows, C, *fd, d_out, C, s);
+        GNX_HIP(hipGetLastError());
+        return GNX_OK;
     }
     if (m.n_rows == 0) return GNX_OK;
     SpmmArgs p{};
@@ -292,10 +377,17 @@ int gnx_gcnii_step(gnx_graph_t g, const float *d_vals, const float *d_H, const f
     set_operands<F32Rows>(p, d_H, C, d_H0, C, beta, a, act, d_out, 0, C, C);
     bind_fused(m, p);
     const unsigned grid = blocks_for(blocks_for(m.n_rows, 16), 8);
-    if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii<F32Rows, 4, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
-    else if (C == 32) hipLaunchKernelGGL((k_spmm_gcnii<F32Rows, 2, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
-    else              hipLaunchKernelGGL((k_spmm_gcnii<F32Rows, 1, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
-    g->last_kernel = "spmm_gcnii_mfma";
+    if (fd) {
+        p.fuse = *fd;
+        if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii<F32Rows, 4, 4, 8, true>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
+        else if (C == 32) hipLaunchKernelGGL((k_spmm_gcnii<F32Rows, 2, 4, 8, true>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
+        else              hipLaunchKernelGGL((k_spmm_gcnii<F32Rows, 1, 4, 8, true>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
+    } else {
+        if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii<F32Rows, 4, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
+        else if (C == 32) hipLaunchKernelGGL((k_spmm_gcnii<F32Rows, 2, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
+        else              hipLaunchKernelGGL((k_spmm_gcnii<F32Rows, 1, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
+    }
+    g->last_kernel = fd ? "spmm_gcnii_mfma_drop" : "spmm_gcnii_mfma";
     if (m.n_long > 0) {   // hub rows: chunked partial sums -> mixed rows (into d_mixed when kept, else in place) -> transform of those rows alone
         rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)C * sizeof(float), s);
         if (rc != GNX_OK) return rc;
@@ -306,7 +398,68 @@ int gnx_gcnii_step(gnx_graph_t g, const float *d_vals, const float *d_H, const f
         launch_long_rows(p, s);
         rc = dense_rows(rows_at, C, m.n_long, C, d_M, ldm, C, nullptr, act, m.long_rows, m.long_rows, d_out, C, s);
         if (rc != GNX_OK) return rc;
+        if (fd) launch_feature_dropout(d_out, C, m.long_rows, m.n_long, C, *fd, d_out, C, s);      // ... -> the mask of those rows, in place
     }
+    GNX_HIP(hipGetLastError());
+    return GNX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gnx_gcnii_step(gnx_graph_t g, const float *d_vals, const float *d_H, const float *d_H0, float a, int64_t C, const float *d_M,
+                   int64_t ldm, int act, float *d_out, float *d_mixed, void *stream) {
+    return gcnii_step("gnx_gcnii_step", g, d_vals, d_H, d_H0, a, C, d_M, ldm, act, nullptr, d_out, d_mixed, stream);
+}
+
+int gnx_gcnii_step_drop(gnx_graph_t g, const float *d_vals, const float *d_H, const float *d_H0, float a, int64_t C, const float *d_M,
+                        int64_t ldm, int act, double dropout_p, uint64_t seed, uint64_t stream_id, float *d_out, float *d_mixed,
+                        void *stream) {
+    GNX_CHECK_ARG(g != nullptr, "gnx_gcnii_step_drop: NULL handle");
+    DropFuse fd{};
+    int rc = make_feat_drop("gnx_gcnii_step_drop", g, dropout_p, seed, stream_id, fd);
+    if (rc != GNX_OK) return rc;
+    // p == 0 hashes nothing: the plain path
+    return gcnii_step("gnx_gcnii_step_drop", g, d_vals, d_H, d_H0, a, C, d_M, ldm, act, dropout_p == 0.0 ? nullptr : &fd, d_out,
+                      d_mixed, stream);
+}
+
+int gnx_feature_dropout(gnx_graph_t g, const float *d_X, int64_t ldx, int64_t n_rows, int64_t C, const int32_t *d_rows, double dropout_p,
+                        uint64_t seed, uint64_t stream_id, float *d_out, int64_t ldo, void *stream) {
+    GNX_CHECK_ARG(g != nullptr, "gnx_feature_dropout: NULL handle");
+    GNX_CHECK_ARG(n_rows >= 0 && C >= 1, "gnx_feature_dropout: negative row count or C < 1");
+    GNX_CHECK_ARG(d_X != nullptr && d_out != nullptr && ldx >= C && ldo >= C, "gnx_feature_dropout: NULL X / out or a row stride below C");
+    GNX_CHECK_ARG(d_out != d_X || ldo == ldx, "gnx_feature_dropout: in place needs ldo == ldx");
+    DropFuse fd{};
+    int rc = make_feat_drop("gnx_feature_dropout", g, dropout_p, seed, stream_id, fd);
+    if (rc != GNX_OK) return rc;
+    if (dropout_p == 0.0 && d_out == d_X) return GNX_OK;
+    launch_feature_dropout(d_X, ldx, d_rows, n_rows, C, fd, d_out, ldo, (hipStream_t)stream);
+    GNX_HIP(hipGetLastError());
+    return GNX_OK;
+}
+
+int gnx_feature_dropout_back(gnx_graph_t g, const float *d_g, int64_t ldg, const float *d_y, int64_t ldy, int64_t n_rows, int64_t C,
+                             double dropout_p, uint64_t seed, uint64_t stream_id, int act, float *d_G, int64_t ldG, void *stream) {
+    GNX_CHECK_ARG(g != nullptr, "gnx_feature_dropout_back: NULL handle");
+    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU, "gnx_feature_dropout_back: invalid activation %d", act);
+    GNX_CHECK_ARG(n_rows >= 0 && C >= 1, "gnx_feature_dropout_back: negative row count or C < 1");
+    GNX_CHECK_ARG(d_g != nullptr && d_G != nullptr && ldg >= C && ldG >= C, "gnx_feature_dropout_back: NULL g / G or a row stride below C");
+    GNX_CHECK_ARG(d_G != d_g || ldG == ldg, "gnx_feature_dropout_back: in place needs ldG == ldg");
+    const bool relu = act == GNX_ACT_RELU;
+    GNX_CHECK_ARG(!relu || (d_y != nullptr && ldy >= C && d_y != d_G), "gnx_feature_dropout_back: relu needs y (not G itself) with ldy >= C");
+    DropFuse fd{};
+    int rc = make_feat_drop("gnx_feature_dropout_back", g, dropout_p, seed, stream_id, fd);
+    if (rc != GNX_OK) return rc;
+    if (n_rows == 0) return GNX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const bool v4 = C % 4 == 0 && ldg % 4 == 0 && ldG % 4 == 0 && aligned(d_g, 16) && aligned(d_G, 16) && (!relu || (ldy % 4 == 0 && aligned(d_y, 16)));
+    const unsigned grid = (unsigned)std::min<int64_t>(blocks_for(n_rows * (v4 ? C / 4 : C), 256), 1 << 20);
+    if (v4 && relu)  hipLaunchKernelGGL((k_feature_dropout_back<4, true>), dim3(grid), dim3(256), 0, s, d_g, ldg, d_y, ldy, n_rows, C, fd, d_G, ldG);
+    else if (v4)     hipLaunchKernelGGL((k_feature_dropout_back<4, false>), dim3(grid), dim3(256), 0, s, d_g, ldg, d_y, ldy, n_rows, C, fd, d_G, ldG);
+    else if (relu)   hipLaunchKernelGGL((k_feature_dropout_back<1, true>), dim3(grid), dim3(256), 0, s, d_g, ldg, d_y, ldy, n_rows, C, fd, d_G, ldG);
+    else             hipLaunchKernelGGL((k_feature_dropout_back<1, false>), dim3(grid), dim3(256), 0, s, d_g, ldg, d_y, ldy, n_rows, C, fd, d_G, ldG);
     GNX_HIP(hipGetLastError());
     return GNX_OK;
 }

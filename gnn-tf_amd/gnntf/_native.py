@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int64, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 ABI_VERSION = 900         # include/gnx.h GNX_ABI_VERSION: the header this binding was written against
@@ -99,6 +99,12 @@ SIGNATURES = {
                                     c_int, c_void_p, c_void_p]),
     "gnx_gcnii_step_back": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_float,
                                     c_void_p, c_void_p, c_void_p]),
+    "gnx_gcnii_step_drop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_int64, c_int, c_double, c_uint64,
+                                    c_uint64, c_void_p, c_void_p, c_void_p]),
+    "gnx_feature_dropout": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_double, c_uint64, c_uint64, c_void_p, c_int64,
+                                    c_void_p]),
+    "gnx_feature_dropout_back": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_double, c_uint64, c_uint64,
+                                         c_int, c_void_p, c_int64, c_void_p]),
     "gnx_dense": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int64,
                           c_void_p]),
     "gnx_dense_wgrad": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),

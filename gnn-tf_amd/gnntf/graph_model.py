@@ -38,6 +38,9 @@ class Structural(Layer):
         return table if features.shape[1] == 0 else torch.cat([table, features], dim=1)
 
 
+FEATURE_DROPOUTS = ("torch", "fused")
+
+
 class GNN(Trainable):
     """gnn.py:29-50."""
 
@@ -47,7 +50,7 @@ class GNN(Trainable):
     fuse_entry_dropout = True
 
     def __init__(self, graph, features, preprocessor: Layer = None, reorder=None, inference_dtype=torch.float32,
-                 training_dtype=torch.float32, train_gather_order="auto", gcnii_backward="composed"):
+                 training_dtype=torch.float32, train_gather_order="auto", gcnii_backward="composed", feature_dropout="torch"):
         """``reorder`` (opt-in, not in the reference): store the graph and the feature rows with the vertices relabelled; every
         [N, .] tensor inside the model then lives in that order, and the model's OUTPUT is put back into the caller's order, so
         tasks, labels and node ids are unaffected.  Results agree with the unordered model to float32 rounding.
@@ -92,7 +95,18 @@ class GNN(Trainable):
         gradient and ONE launch for dH and dH0 (gnx_gcnii_step_back) instead of the dense kernel, the transposed SpMM and a scaling;
         the forward and the weight gradients keep their bits, dH and dH0 agree to float32 rounding.  GCNIISpectralPreservingLayer,
         dropped adjacencies, add_eye and the CPU path keep their code whatever it says.  The default stays ``"composed"``: the other
-        order moves the roundings of existing gradients (measurement: profiles/NOTES.md "Fused GCNII backward")."""
+        order moves the roundings of existing gradients (measurement: profiles/NOTES.md "Fused GCNII backward").
+        ``feature_dropout`` (not in the reference): ``"torch"`` (the default: torch.nn.functional.dropout behind every layer, today's
+        calls and bits) or ``"fused"``.  ``"fused"``: the feature dropout of every plain GCNIILayer (this class itself, relu or the
+        identity as activation, 0 < ``dropout`` < 1, device tensors, no add_eye) in training mode leaves the layer's launch
+        (sparse.gcnii_step ``dropout``, gnx_gcnii_step_drop) with a mask of the counter RNG the edge dropout uses: element (i, c) of
+        the layer's ``_next_mask_stream()`` stream is kept iff hash_u24(seed, stream, i, c, 0) >= int(p * 2^24), kept values times the
+        f32 1 / (1 - p).  The masks differ from torch's, which is why it is opt-in; a training step is then reproducible from
+        (seed, stream) alone, and ``train(capture=True)`` equals the eager run bit for bit.  GCNIISpectralPreservingLayer, other
+        activations, CPU tensors, Dense / Dropout layers and the vertex-partitioned path keep torch's dropout whatever it says
+        (measurement: profiles/NOTES.md "Fused GCNII feature dropout")."""
+        if feature_dropout not in FEATURE_DROPOUTS:
+            raise Exception("GNN: feature_dropout must be one of " + ", ".join(repr(f) for f in FEATURE_DROPOUTS))
         if gcnii_backward not in sparse.GCNII_BACKWARDS:
             raise Exception("GNN: gcnii_backward must be one of " + ", ".join(repr(b) for b in sparse.GCNII_BACKWARDS))
         if train_gather_order not in sparse.GATHER_ORDERS:
@@ -106,6 +120,7 @@ class GNN(Trainable):
         self.training_dtype = training_dtype
         self.train_gather_order = train_gather_order
         self.gcnii_backward = gcnii_backward
+        self.feature_dropout = feature_dropout
         self._order = self._newid = None
         self.reorder_used, self.locality_share = None, None
         if isinstance(graph, sparse.DeviceGraph):
@@ -401,7 +416,8 @@ class GCNIILayer(Layer):
     """gcn.py:7-27: dropout(act(((1-a) A.H + a H0) . ((1-b) I + b W))), b = beta_transformer(l / (k+1)).
     ONE launch per layer for C in {16, 32, 64} -- the mixed rows stay in LDS and meet (1-b) I + b W on the matrix cores
     (gnx_gcnii_step); in training the same launch also writes the mixed rows once (dW needs them) instead of a second launch
-    reading them back.
+    reading them back.  On a GNN with ``feature_dropout="fused"`` the training-mode dropout is part of that launch too
+    (gnx_gcnii_step_drop; GNN.__init__).
 
     On a GNN with ``inference_dtype=torch.bfloat16`` a RUN of consecutive plain GCNIILayer layers (this class itself, relu or the
     identity as activation, no add_eye) in an eval-mode forward without autograd executes as one bf16 chain
@@ -475,6 +491,12 @@ class GCNIILayer(Layer):
         adjacency = gcn.get_adjacency(self.graph_dropout)
         if features.is_cuda and adjacency.diag is None:
             fused_act = self.activation is relu or self.activation is linear
+            if (getattr(gcn, "feature_dropout", "torch") == "fused" and type(self) is GCNIILayer and fused_act and gcn.is_training()
+                    and 0 < self.dropout < 1):                      # (a rate of 1 or more stays with gcn.dropout and what torch makes of it)
+                # GNN(feature_dropout="fused"): dropout(act(...)) leaves the layer's launch, its mask from the counter RNG
+                seed, stream = gcn._next_mask_stream()
+                return sparse.gcnii_step(adjacency, features, self.H0.value, self.a, transform, relu=self.activation is relu,
+                                         backward=getattr(gcn, "gcnii_backward", "composed"), dropout=(self.dropout, seed, stream))
             out = sparse.gcnii_step(adjacency, features, self.H0.value, self.a, transform, relu=self.activation is relu,
                                     backward=getattr(gcn, "gcnii_backward", "composed"))
             return gcn.dropout(out if fused_act else self.activation(out), self.dropout)

@@ -1050,8 +1050,84 @@ def dense(X: torch.Tensor, W: torch.Tensor, bias=None, relu=False) -> torch.Tens
     return _DenseAct.apply(X, W, bias, bool(relu))
 
 
-def _gcnii_launch(adj: Adjacency, H, H0, a, M, relu, keep_mixed):
-    """gnx_gcnii_step; returns (out, T or None).  T = the mixed rows (A.H)(1-a) + H0 a, written by the same launch when kept."""
+def _dropout_triple(dropout, what):
+    """(p, seed, stream) of a counter-RNG feature dropout as (float, uint64, uint64), or None for ``None`` / a rate of 0."""
+    if dropout is None:
+        return None
+    p, seed, stream = dropout
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise Exception(f"{what}: dropout rate {p} outside [0, 1)")
+    return (p, int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFFFFFFFFFF) if p > 0 else None
+
+
+def _feature_dropout_launch(graph: DeviceGraph, X, p, seed, stream, rows=None, out=None):
+    """gnx_feature_dropout: drop(X) into ``out`` (None: a new tensor; X itself: in place), over the row ids ``rows`` (int32) or all rows."""
+    nat.require_cuda(X, rows, out)
+    _same_device(graph, X, rows, out)
+    if X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1 or X.stride(0) < X.shape[1]:
+        raise Exception("feature_dropout: needs float32 rows")
+    if out is None:
+        out = torch.empty_like(X, memory_format=torch.contiguous_format)
+        if rows is not None:
+            out.copy_(X)
+    elif tuple(out.shape) != tuple(X.shape) or out.dtype != torch.float32 or out.stride(1) != 1 or out.stride(0) < out.shape[1]:
+        raise Exception("feature_dropout: bad output buffer")
+    if rows is not None and (rows.dtype != torch.int32 or rows.dim() != 1 or not rows.is_contiguous()):
+        raise Exception("feature_dropout: the row list must be a contiguous int32 vector")
+    n = X.shape[0] if rows is None else rows.numel()
+    if X.shape[1] == 0:
+        return out
+    with nat.on_device(X.device):
+        nat.check(nat.lib().gnx_feature_dropout(graph.handle, nat.ptr(X), X.stride(0), n, X.shape[1], nat.ptr(rows), float(p), seed, stream,
+                                                nat.ptr(out), out.stride(0), nat.current_stream()))
+    return out
+
+
+def _feature_dropout_back(graph: DeviceGraph, g, y, p, seed, stream, relu):
+    """gnx_feature_dropout_back: G = kept ? g * s : 0, with ``relu`` also 0 where the dropped forward output ``y`` is <= 0."""
+    g = _as_f32_rows(g).contiguous()
+    nat.require_cuda(g, y)
+    _same_device(graph, g, y)
+    G = torch.empty_like(g)
+    if g.numel() == 0:
+        return G
+    y = y if relu else None
+    with nat.on_device(g.device):
+        nat.check(nat.lib().gnx_feature_dropout_back(graph.handle, nat.ptr(g), g.stride(0), nat.ptr(y), 0 if y is None else y.stride(0),
+                                                     g.shape[0], g.shape[1], float(p), seed, stream,
+                                                     nat.ACT_RELU if relu else nat.ACT_NONE, nat.ptr(G), G.stride(0), nat.current_stream()))
+    return G
+
+
+class _FeatureDropout(torch.autograd.Function):
+    """out = drop(X) with the counter RNG's mask of (seed, stream); backward G = kept ? g * s : 0, the mask made again from the triple."""
+
+    @staticmethod
+    def forward(ctx, X, graph, p, seed, stream):
+        ctx.graph, ctx.triple = graph, (p, seed, stream)
+        return _feature_dropout_launch(graph, _as_f32_rows(X), p, seed, stream)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _feature_dropout_back(ctx.graph, g, None, *ctx.triple, relu=False), None, None, None, None
+
+
+def feature_dropout(graph: DeviceGraph, X: torch.Tensor, p, seed, stream) -> torch.Tensor:
+    """tf.nn.dropout(X, p) (layered.py:44-45) with the mask of the counter RNG instead of torch's generator (gnx_feature_dropout):
+    element (i, c) is kept iff hash_u24(seed, stream + counter, i, c, 0) >= int(p * 2^24), kept values are scaled by the f32
+    1 / (1 - p), dropped ones are +0.  ``graph`` lends its dropout counter (DeviceGraph.set_dropout_counter: a replayed hipGraph then
+    draws fresh masks) and is otherwise not read.  Reproducible from (seed, stream); differentiable w.r.t. X; device tensors only."""
+    triple = _dropout_triple((p, seed, stream), "feature_dropout")
+    nat.require_cuda(X)
+    if triple is None:
+        return X
+    return _FeatureDropout.apply(X, graph, *triple)
+
+
+def _gcnii_launch(adj: Adjacency, H, H0, a, M, relu, keep_mixed, dropout=None):
+    """gnx_gcnii_step; returns (out, T or None).  T = the mixed rows (A.H)(1-a) + H0 a, written by the same launch when kept.
+    ``dropout`` = (p, seed, stream): gnx_gcnii_step_drop, out = drop(act(T . M)); T stays undropped."""
     g = adj.graph
     nat.require_cuda(H, H0, M)
     H, H0, M = _as_f32_rows(H).contiguous(), _as_f32_rows(H0).contiguous(), _as_f32_rows(M)
@@ -1063,6 +1139,11 @@ def _gcnii_launch(adj: Adjacency, H, H0, a, M, relu, keep_mixed):
     out = torch.empty_like(H)
     mixed = torch.empty_like(H) if keep_mixed or C not in (16, 32, 64) else None
     with nat.on_device(H.device):
+        if dropout is not None:
+            nat.check(nat.lib().gnx_gcnii_step_drop(g.handle, nat.ptr(adj.vals), nat.ptr(H), nat.ptr(H0), float(a), C, nat.ptr(M), M.stride(0),
+                                                    nat.ACT_RELU if relu else nat.ACT_NONE, *dropout, nat.ptr(out), nat.ptr(mixed),
+                                                    nat.current_stream()))
+            return out, mixed
         nat.check(nat.lib().gnx_gcnii_step(g.handle, nat.ptr(adj.vals), nat.ptr(H), nat.ptr(H0), float(a), C, nat.ptr(M), M.stride(0),
                                            nat.ACT_RELU if relu else nat.ACT_NONE, nat.ptr(out), nat.ptr(mixed), nat.current_stream()))
     return out, mixed
@@ -1107,19 +1188,24 @@ def gcnii_step_back(adj: Adjacency, G: torch.Tensor, a: float, Mt: torch.Tensor,
 class _GCNIIStep(torch.autograd.Function):
     """out = act(T . M), T = (A . H)(1-a) + H0 a, as ONE launch that also leaves T in memory for the backward (gcn.py:22-27 under
     tf.GradientTape): with g' = g * (out > 0):  dM = T^T g' (gnx_dense_wgrad), dT = g' M^T (gnx_dense), dH = (1-a) A^T dT, dH0 = a dT.
-    ``backward="fused"``: dH = ((1-a) A^T g') M^T and dH0 = (a g') M^T from ONE launch (gcnii_step_back), dT never written."""
+    ``backward="fused"``: dH = ((1-a) A^T g') M^T and dH0 = (a g') M^T from ONE launch (gcnii_step_back), dT never written.
+    ``dropout`` = (p, seed, stream): out = drop(act(T . M)) from the same launch (gnx_gcnii_step_drop); the dropped out is what is
+    saved, and g' = kept ? g * s : 0 gated by out > 0 comes from one pass (gnx_feature_dropout_back) in place of the relu mask."""
 
     @staticmethod
-    def forward(ctx, H, H0, M, adj, a, relu, backward="composed"):
-        out, T = _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=True)
-        ctx.adj, ctx.a, ctx.relu, ctx.fused_backward = adj, a, relu, backward == "fused"
-        ctx.save_for_backward(T, M, out if relu else None)
+    def forward(ctx, H, H0, M, adj, a, relu, backward="composed", dropout=None):
+        out, T = _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=True, dropout=dropout)
+        ctx.adj, ctx.a, ctx.relu, ctx.fused_backward, ctx.dropout = adj, a, relu, backward == "fused", dropout
+        ctx.save_for_backward(T, M, out if relu or dropout is not None else None)
         return out
 
     @staticmethod
     def backward(ctx, g):
         T, M, out = ctx.saved_tensors
-        g = (_relu_mask(g, out) if ctx.relu else g).contiguous()
+        if ctx.dropout is not None:
+            g = _feature_dropout_back(ctx.adj.graph, g, out, *ctx.dropout, relu=ctx.relu)
+        else:
+            g = (_relu_mask(g, out) if ctx.relu else g).contiguous()
         gM = _dense_wgrad(T, g) if ctx.needs_input_grad[2] else None
         gH = gH0 = None
         if ctx.fused_backward and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
@@ -1132,11 +1218,11 @@ class _GCNIIStep(torch.autograd.Function):
                 gH = _launch(ctx.adj, gT, None, 1.0 - ctx.a, 0.0, nat.ACT_NONE, transposed=True)
             if ctx.needs_input_grad[1]:
                 gH0 = gT * ctx.a
-        return gH, gH0, gM, None, None, None, None
+        return gH, gH0, gM, None, None, None, None, None
 
 
 def gcnii_step(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, M: torch.Tensor, relu=True, storage=torch.float32,
-               out_storage=torch.float32, backward="composed") -> torch.Tensor:
+               out_storage=torch.float32, backward="composed", dropout=None) -> torch.Tensor:
     """act(((A . H)(1-a) + H0 a) . M), M = (1-b) I + b W (gcn.py:22-27) -- ONE fused launch for C in {16, 32, 64}: the mixed
     rows stay in LDS and meet M on the matrix cores (gnx_gcnii_step).  Without autograd they never reach HBM; when gradients are
     needed the same launch also writes them (dM = T^T g needs them), once, and the transform does not read them back.  Other
@@ -1147,9 +1233,20 @@ def gcnii_step(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, M: t
     of a stack gathers).  Over a bf16-representable H the f32 result is bit for bit the default path's.
     ``backward``: ``"composed"`` (the default: gnx_dense, the transposed SpMM and a scaling, today's bits) or ``"fused"`` (opt-in:
     after the relu mask and gnx_dense_wgrad, dH and dH0 come from one launch, gcnii_step_back; the forward and dM keep their bits,
-    dH and dH0 agree to float32 rounding -- the products associate differently).  A DroppedAdjacency keeps the generic composition."""
+    dH and dH0 agree to float32 rounding -- the products associate differently).  A DroppedAdjacency keeps the generic composition.
+    ``dropout`` = ``(p, seed, stream)`` (opt-in; None, the default, is today's call): the layer's feature dropout (gcn.py:27) leaves
+    the same launch, out = drop(act(...)) (gnx_gcnii_step_drop) with the mask of ``feature_dropout`` -- the counter RNG of the edge
+    dropout, not torch's generator; the mixed rows kept for dM stay undropped, and the backward starts with one pass
+    (gnx_feature_dropout_back) instead of torch's dropout backward and the relu mask.  Behind the generic composition of a
+    DroppedAdjacency the mask is ``feature_dropout``'s pass.  Training only: raises together with ``storage=torch.bfloat16``."""
     if backward not in GCNII_BACKWARDS:
         raise Exception("gcnii_step: backward must be one of " + ", ".join(repr(b) for b in GCNII_BACKWARDS))
+    if dropout is not None:
+        if _bf16(storage) or _bf16(out_storage):
+            raise Exception("gcnii_step: dropout belongs to training, bf16 storage is inference only")
+        dropout = _dropout_triple(dropout, "gcnii_step")
+        if dropout is not None:
+            return _gcnii_step_dropped(adj, H, H0, a, M, relu, backward, dropout)
     if _bf16(storage):
         _no_grad_for_bf16("gcnii_step", H, H0, M)
         return _gcnii_launch_bf16(adj, H, H0, a, M, relu, _bf16(out_storage))
@@ -1160,6 +1257,15 @@ def gcnii_step(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, M: t
             return dense(ppr_step(adj, H, H0, a), M, None, relu)
         return _GCNIIStep.apply(H, H0, M, adj, float(a), bool(relu), backward)
     return _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=False)[0]
+
+
+def _gcnii_step_dropped(adj, H, H0, a, M, relu, backward, dropout):
+    """gcnii_step with a feature dropout of rate > 0 (``dropout`` = the checked triple)."""
+    if torch.is_grad_enabled() and (H.requires_grad or H0.requires_grad or M.requires_grad):
+        if isinstance(adj, DroppedAdjacency):
+            return feature_dropout(adj.graph, dense(ppr_step(adj, H, H0, a), M, None, relu), *dropout)
+        return _GCNIIStep.apply(H, H0, M, adj, float(a), bool(relu), backward, dropout)
+    return _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=False, dropout=dropout)[0]
 
 
 # the model-level bf16 path of GCNIILayer (graph_model.py) keeps f32 below this width.  tools/gcnii_bf16_bench.py is the measurement

@@ -59,7 +59,8 @@ const char *gnx_last_error(void);
  * gnx_halo_exchange_bf16), likewise.  gnx_gcnii_step_bf16 was added WITHIN 0.9 (no existing signature changed, the number stays
  * 900): a client that wants it probes the library for the symbol (dlsym) instead of comparing versions.  So were the gather-order
  * entries (gnx_graph_gather_order, gnx_spmm_dropped_chained_ord, gnx_spmm_dropped_back_ord, GNX_RESERVE_TRAIN_GATHER), likewise, and
- * gnx_gcnii_step_back (the fused backward of the GCNII layer), likewise. */
+ * gnx_gcnii_step_back (the fused backward of the GCNII layer), likewise, and the feature dropout of the GCNII training layer
+ * (gnx_gcnii_step_drop, gnx_feature_dropout, gnx_feature_dropout_back), likewise. */
 #define GNX_ABI_VERSION 900
 int gnx_version(void);
 
@@ -452,6 +453,39 @@ int gnx_gcnii_step_back(gnx_graph_t g, const float *d_vals_t, const float *d_G, 
                         const float *d_S_in, float s_alpha, float *d_S_out,
                         float *d_work, void *stream);
 
+/* Feature dropout of the GCNII training layer from the counter RNG of the edge dropout (opt-in; added within ABI 0.9 -- probe for the
+ * symbols): gcn.py:27 / layered.py:44-45, dropout(act(...)), without a framework op, a byte mask or a second pass over the rows.
+ * The mask: for a matrix [n, C], a rate 0 <= p < 1 and (seed, stream_id), element (i, c) is KEPT iff
+ *   hash_u24(seed, stream_id + counter, i, c, 0) >= (uint32_t)(p * 2^24)
+ * -- the 24-bit counter hash of the edge dropout with i = the handle's row id (not a launch slot), c = the column, duplicate rank 0,
+ * counter = the handle's dropout counter (gnx_graph_set_dropout_counter; 0 when none is set), and
+ *   drop(v) = kept ? v * s : +0.0f,   s = 1.0f / (1.0f - (float)p)      (the f32 scale of the edge dropout).
+ * dropout_p is a double: the threshold is taken from the caller's value, so that 0.6 means (uint32_t)(0.6 * 2^24) = 10066329 and not
+ * the 10066330 its float rounding would give.  p == 0 hashes nothing and is the plain path.  No float atomics, nothing random beyond
+ * (seed, stream_id, counter): two calls give the same bits, and a captured launch draws fresh masks per replay through the counter.
+ *
+ * gnx_gcnii_step_drop: gnx_gcnii_step with out = drop(act(T . M)); d_mixed still receives the UNDROPPED mixed rows T (dM = T^T G needs
+ * them).  For C in {16, 32, 64} with 16-byte aligned buffers it is the one launch of gnx_gcnii_step, the mask applied to a row's
+ * values as they leave the tile (after the matrix-core block); hub rows go through the long-row kernels and the dense kernel as there
+ * and then take the mask from the row-list pass below, in place.  Other widths / alignments run gnx_spmm and the dense kernel as
+ * there, then the pass over all rows in place.  Rows without entries are masked like every other row.  The argument checks of
+ * gnx_gcnii_step, plus 0 <= p < 1; its capture and reserve rules (nothing new is allocated).
+ *
+ * gnx_feature_dropout: the mask as a pass of its own, out[r] = drop(X[r]) for row ids r = d_rows[0 .. n_rows) (int32), or r = 0 ..
+ * n_rows - 1 with d_rows == NULL; any width (16-byte accesses where C, the strides and the bases allow them), d_out may be d_X (with
+ * ldo == ldx).  The handle is read for its dropout counter only: any handle will do.
+ *
+ * gnx_feature_dropout_back: the backward's gate in one pass over rows 0 .. n_rows - 1, G = kept ? g * s : +0, and with
+ * act == GNX_ACT_RELU also +0 where y <= 0, y being the DROPPED forward output (y > 0 then implies kept: the hash is taken only where
+ * y lets the value through).  d_y may be NULL with GNX_ACT_NONE; d_G may be d_g (with ldG == ldg). */
+int gnx_gcnii_step_drop(gnx_graph_t g, const float *d_vals, const float *d_H, const float *d_H0, float a, int64_t C,
+                        const float *d_M, int64_t ldm, int act, double dropout_p, uint64_t seed, uint64_t stream_id,
+                        float *d_out, float *d_mixed, void *stream);
+int gnx_feature_dropout(gnx_graph_t g, const float *d_X, int64_t ldx, int64_t n_rows, int64_t C, const int32_t *d_rows,
+                        double dropout_p, uint64_t seed, uint64_t stream_id, float *d_out, int64_t ldo, void *stream);
+int gnx_feature_dropout_back(gnx_graph_t g, const float *d_g, int64_t ldg, const float *d_y, int64_t ldy, int64_t n_rows, int64_t C,
+                             double dropout_p, uint64_t seed, uint64_t stream_id, int act, float *d_G, int64_t ldG, void *stream);
+
 /* ---- the dense ends of the path (matrix cores) -----------------------------------------------------------------------
  * gnx_dense: out = act(X . W + bias) -- Dense.__forward__ (gnntf/core/nn/layers.py:135-136) and the transform of
  * GCNLayer (gcn.py:89).  X [n, F] (ldx), W [F, O] (ldw), bias [O] or NULL, out [n, O] (ldo); float32 in and out, float32
@@ -581,7 +615,9 @@ int gnx_probe_block_xcd(int64_t n_blocks, int32_t *d_xcd_out, void *stream);
  * names with "_bf16" appended ("spmm_group16_drop_bf16", "spmm_wave_drop_entries_bf16", ...), "+long" after the row class when hub
  * rows went through the chunk kernels ("spmm_group8+long_drop_bf16"); gnx_gcnii_step_bf16 reports "spmm_gcnii_mfma_bf16" (the fused
  * launch, with or without hub rows) or "spmm+dense_mfma_bf16" (the other widths / alignments); gnx_gcnii_step_back reports
- * "spmm_gcnii_back_mfma" (the fused launch, with or without hub rows) or "dense+spmm_back" (the other widths / alignments). */
+ * "spmm_gcnii_back_mfma" (the fused launch, with or without hub rows) or "dense+spmm_back" (the other widths / alignments);
+ * gnx_gcnii_step_drop reports "spmm_gcnii_mfma_drop" or "spmm+dense_mfma_drop" likewise (with p == 0 the names of gnx_gcnii_step); the
+ * two dropout passes report nothing. */
 const char *gnx_graph_last_kernel(gnx_graph_t g);
 
 #ifdef __cplusplus
