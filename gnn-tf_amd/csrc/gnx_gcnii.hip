@@ -156,8 +156,12 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args 
 // second product, hub rows and rows without entries included; the gather and the dH store leave rows longer than p.long_row to the
 // long-row kernels + the dense kernel; a row without entries gets dH = 0, written.  S_in may be S_out (each lane reads the four
 // values it overwrites); dH aliases nothing.
-template <int NT, int U, int WPB>
-__global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii_back(const SpmmArgs p, const float *__restrict__ N, int64_t ldn, const float *S_in,
+// Written once over the row-storage policy R, as the forward is: Bf16RowsT gathers 8-byte pieces of the bf16 copy Gb of the gated
+// gradient (gnx_gcnii_step_back_bf16) and widens them exactly; dH (p.out) is f32 under either policy, and the row's own G[r] of the
+// second product is read from the f32 p.X under either policy too -- the bf16 entry binds the f32 G there beside Gb, so the running dH0
+// sum never sees a rounded addend.  Same entry order, sums and transform: over bf16-representable G both give the same bits.
+template <typename R, int NT, int U, int WPB>
+__global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii_back(const typename R::Args p, const float *__restrict__ N, int64_t ldn, const float *S_in,
                                                               float s_alpha, float *S_out) {
     constexpr int C = 16 * NT, G = 4 * NT, RPP = 64 / G, PASSES = 16 / RPP, STRIDE = C + 4;
     __shared__ float Ms[C * STRIDE];
@@ -186,7 +190,11 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii_back(const SpmmArgs p, 
         rows[ps] = row;
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
         if (live[ps]) {
-            const float *__restrict__ Xc = p.X + c;
+            // (the operand and its load are named directly, not through R::X / R::load: through the accessors the compiler structures the
+            // gather loop of the f32 instantiation differently, and that kernel stays instruction for instruction the one measured so far)
+            const typename R::Elem *__restrict__ Xc;
+            if constexpr (R::BF16) Xc = p.Xb + c;
+            else Xc = p.X + c;
             for (int64_t e = beg; e < end; e += U) {
                 float x[U][4];
                 float w[U];
@@ -195,7 +203,8 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii_back(const SpmmArgs p, 
                     if (e + u < end) {
                         const int j = p.colidx[e + u];
                         w[u] = p.vals[e + u];
-                        vload<4>(x[u], Xc + (int64_t)j * p.ldx);
+                        if constexpr (R::BF16) bload<4>(x[u], Xc + (int64_t)j * p.ldx);
+                        else vload<4>(x[u], Xc + (int64_t)j * p.ldx);
                     } else {
                         w[u] = 0.f;
 #pragma unroll
@@ -326,6 +335,35 @@ __global__ __launch_bounds__(256) void k_feature_dropout_back(const float *g, in
     }
 }
 
+// k_feature_dropout_back over the STORED bf16 forward output y (gnx_feature_dropout_back_bf16), the gated gradient written twice: G
+// in f32 (what gnx_dense_wgrad and the row's own product of the backward read) and Gb = bf(G) (what the backward gathers).  The gate is
+// on the stored value: a positive f32 output that rounded to bf16 zero was stored as zero and passes nothing.
+template <int VEC, bool RELU>
+__global__ __launch_bounds__(256) void k_feature_dropout_back_bf16(const float *g, int64_t ldg, const uint16_t *__restrict__ y, int64_t ldy,
+                                                                  int64_t n, int64_t C, const DropFuse fd, float *G, int64_t ldG,
+                                                                  uint16_t *__restrict__ Gb, int64_t ldGb) {
+    const int64_t per_row = C / VEC, total = n * per_row, stride = (int64_t)gridDim.x * blockDim.x;
+    const uint64_t stream = drop_stream(fd);
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const int64_t r = e / per_row, c = (e % per_row) * VEC;
+        float x[VEC];
+        vload<VEC>(x, g + r * ldg + c);
+        if constexpr (RELU) {
+            float out[VEC];
+            bload<VEC>(out, y + r * ldy + c);
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) {
+                if (out[v] <= 0.f) x[v] = 0.f;
+                else x[v] = (fd.thr == 0 || hash_u24(fd.seed, stream, (uint64_t)r, (uint64_t)(c + v), 0) >= fd.thr) ? x[v] * fd.scale : 0.f;
+            }
+        } else {
+            drop_values<VEC>(fd, stream, r, c, x);
+        }
+        vstore<VEC>(G + r * ldG + c, x);
+        bstore<VEC>(Gb + r * ldGb + c, x);
+    }
+}
+
 // the mask of one call: keep iff hash >= int(p * 2^24) (oracle/gnntf_oracle.py:dropout_threshold, over the caller's double), kept values
 // times the f32 scale of the edge dropout, 1.0f / (1.0f - (float)p); the handle lends its dropout counter
 int make_feat_drop(const char *fn, const gnx_graph *g, double p, uint64_t seed, uint64_t stream_id, DropFuse &fd) {
@@ -402,6 +440,14 @@ int gcnii_step(const char *fn, gnx_graph *g, const float *d_vals, const float *d
     }
     GNX_HIP(hipGetLastError());
     return GNX_OK;
+}
+
+// what the two launch entries refuse: they have no composed form, the callers keep f32 there
+int refuse_unfused(const char *fn, int64_t C, bool aligned_ok) {
+    if (C != 16 && C != 32 && C != 64) set_error("%s: width %lld is not supported (the fused launch takes C = 16, 32 or 64; keep f32 storage elsewhere)", fn, (long long)C);
+    else if (!aligned_ok) set_error("%s: misaligned buffer (the f32 buffers must be 16-byte aligned, the bf16 buffers 8-byte aligned)", fn);
+    else return GNX_OK;
+    return GNX_ERR_UNSUPPORTED;
 }
 
 }  // namespace
@@ -515,9 +561,9 @@ int gnx_gcnii_step_back(gnx_graph_t g, const float *d_vals_t, const float *d_G, 
     p.X = d_G; p.ldx = C; p.beta = beta; p.alpha = a; p.act = GNX_ACT_NONE; p.out = d_dH; p.ldo = C; p.C = (int)C;
     bind_fused(m, p);
     const unsigned grid = blocks_for(blocks_for(m.n_rows, 16), 8);
-    if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii_back<4, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
-    else if (C == 32) hipLaunchKernelGGL((k_spmm_gcnii_back<2, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
-    else              hipLaunchKernelGGL((k_spmm_gcnii_back<1, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
+    if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii_back<F32Rows, 4, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
+    else if (C == 32) hipLaunchKernelGGL((k_spmm_gcnii_back<F32Rows, 2, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
+    else              hipLaunchKernelGGL((k_spmm_gcnii_back<F32Rows, 1, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
     g->last_kernel = "spmm_gcnii_back_mfma";
     if (m.n_long > 0) {   // hub rows of the transposed structure: chunked partial sums -> (1-a) Z into dH -> those rows alone times Mt, in place
         p.partial = g->partial;
@@ -592,6 +638,148 @@ int gnx_gcnii_step_bf16(gnx_graph_t g, const float *d_vals, const uint16_t *d_H,
         rc = dense_rows(d_work, C, m.n_long, C, d_M, ldm, C, nullptr, act, m.long_rows, m.long_rows, rows_to, C, s);
         if (rc != GNX_OK) return rc;
         if (out_bf16) round_rows(d_work, m.long_rows, m.n_long, C, (uint16_t *)d_out, s);
+    }
+    GNX_HIP(hipGetLastError());
+    return GNX_OK;
+}
+
+
+// ---- bf16 row storage for GCNII training (gnx.h) ------------------------------------------------------------------------------------
+int gnx_gcnii_step_train_bf16(gnx_graph_t g, const float *d_vals, const uint16_t *d_H, const float *d_H0, float a, int64_t C, const float *d_M,
+                              int64_t ldm, int act, double dropout_p, uint64_t seed, uint64_t stream_id, void *d_out, int out_bf16,
+                              float *d_mixed, float *d_work, void *stream) {
+    const char *fn = "gnx_gcnii_step_train_bf16";
+    int rc = check_common(fn, g, d_H, C, C, d_H0, C, d_out, C);
+    if (rc != GNX_OK) return rc;
+    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU, "%s: invalid activation %d", fn, act);
+    GNX_CHECK_ARG(out_bf16 == 0 || out_bf16 == 1, "%s: out_bf16 must be 0 or 1", fn);
+    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "%s: needs a square graph", fn);
+    GNX_CHECK_ARG(d_H0 != nullptr && d_M != nullptr && ldm >= C, "%s: NULL H0 / M or ldm < C", fn);
+    GNX_CHECK_ARG(d_mixed != nullptr, "%s: needs d_mixed [n, C] f32 (the mixed rows T are kept for the weight gradient)", fn);
+    GNX_CHECK_ARG((const void *)d_out != (const void *)d_H0 && (const void *)d_out != (const void *)d_M, "%s: out must not alias H0 / M", fn);
+    GNX_CHECK_ARG((const void *)d_mixed != (const void *)d_out && (const void *)d_mixed != (const void *)d_H && d_mixed != d_H0 && d_mixed != d_M &&
+                  d_mixed != d_vals, "%s: d_mixed must be a buffer of its own", fn);
+    GNX_CHECK_ARG(d_work == nullptr || ((const void *)d_work != (const void *)d_out && (const void *)d_work != (const void *)d_H && d_work != d_H0 &&
+                                        d_work != d_M && d_work != d_vals && d_work != d_mixed), "%s: d_work must be a buffer of its own", fn);
+    DropFuse fd{};
+    rc = make_feat_drop(fn, g, dropout_p, seed, stream_id, fd);
+    if (rc != GNX_OK) return rc;
+    rc = refuse_unfused(fn, C, aligned(d_H, 8) && aligned(d_H0, 16) && aligned(d_out, out_bf16 ? 8 : 16) && aligned(d_mixed, 16) && aligned(d_work, 16));
+    if (rc != GNX_OK) return rc;
+    const Csr &m = g->a;
+    GNX_CHECK_ARG(d_work != nullptr || m.n_long == 0, "%s: needs d_work [n, C] f32 (the graph has hub rows: they are transformed and masked in memory)", fn);
+    if (m.n_rows == 0) return GNX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const bool drop = dropout_p != 0.0;      // p == 0 hashes nothing: the instantiation without the mask
+    SpmmArgs p{};
+    p.vals = d_vals ? d_vals : g->raw_vals;
+    p.ldx = C; p.H0 = d_H0; p.ldh0 = C; p.beta = (float)(1.0 - (double)a); p.alpha = a; p.ldo = C; p.C = (int)C;
+    bind_fused(m, p);
+    if (m.n_long > 0) {   // (before the first launch: under capture a slab that would have to grow refuses the whole call)
+        rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)C * sizeof(float), s);
+        if (rc != GNX_OK) return rc;
+    }
+    BfArgs q{};
+    static_cast<SpmmArgs &>(q) = p;
+    q.act = act; q.Xb = d_H; q.outv = d_out; q.out_bf16 = out_bf16;
+    if (drop) q.fuse = fd;
+    const unsigned grid = blocks_for(blocks_for(m.n_rows, 16), 8);
+    if (drop) {
+        if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii<Bf16Rows, 4, 4, 8, true>), dim3(grid), dim3(512), 0, s, q, d_M, ldm, d_mixed);
+        else if (C == 32) hipLaunchKernelGGL((k_spmm_gcnii<Bf16Rows, 2, 4, 8, true>), dim3(grid), dim3(512), 0, s, q, d_M, ldm, d_mixed);
+        else              hipLaunchKernelGGL((k_spmm_gcnii<Bf16Rows, 1, 4, 8, true>), dim3(grid), dim3(512), 0, s, q, d_M, ldm, d_mixed);
+    } else {
+        if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii<Bf16Rows, 4, 4, 8>), dim3(grid), dim3(512), 0, s, q, d_M, ldm, d_mixed);
+        else if (C == 32) hipLaunchKernelGGL((k_spmm_gcnii<Bf16Rows, 2, 4, 8>), dim3(grid), dim3(512), 0, s, q, d_M, ldm, d_mixed);
+        else              hipLaunchKernelGGL((k_spmm_gcnii<Bf16Rows, 1, 4, 8>), dim3(grid), dim3(512), 0, s, q, d_M, ldm, d_mixed);
+    }
+    g->last_kernel = "spmm_gcnii_mfma_train_bf16";
+    if (m.n_long > 0) {   // hub rows: chunked partial sums over the bf16 rows -> f32 mixed rows in d_mixed -> transform of those rows alone ...
+        p.partial = g->partial;
+        p.act = GNX_ACT_NONE;
+        launch_long_rows_bf16(p, d_H, d_mixed, s);
+        float *rows_to = out_bf16 ? d_work : (float *)d_out;      // (T stays as it is: a bf16 result is transformed into d_work, then rounded)
+        rc = dense_rows(d_mixed, C, m.n_long, C, d_M, ldm, C, nullptr, act, m.long_rows, m.long_rows, rows_to, C, s);
+        if (rc != GNX_OK) return rc;
+        if (drop) launch_feature_dropout(rows_to, C, m.long_rows, m.n_long, C, fd, rows_to, C, s);      // ... -> their mask, in place
+        if (out_bf16) round_rows(d_work, m.long_rows, m.n_long, C, (uint16_t *)d_out, s);
+    }
+    GNX_HIP(hipGetLastError());
+    return GNX_OK;
+}
+
+int gnx_feature_dropout_back_bf16(gnx_graph_t g, const float *d_g, int64_t ldg, const uint16_t *d_y, int64_t ldy, int64_t n_rows, int64_t C,
+                                  double dropout_p, uint64_t seed, uint64_t stream_id, int act, float *d_G, int64_t ldG, uint16_t *d_Gb,
+                                  int64_t ldGb, void *stream) {
+    const char *fn = "gnx_feature_dropout_back_bf16";
+    GNX_CHECK_ARG(g != nullptr, "%s: NULL handle", fn);
+    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU, "%s: invalid activation %d", fn, act);
+    GNX_CHECK_ARG(n_rows >= 0 && C >= 1, "%s: negative row count or C < 1", fn);
+    GNX_CHECK_ARG(d_g != nullptr && d_G != nullptr && d_Gb != nullptr && ldg >= C && ldG >= C && ldGb >= C,
+                  "%s: NULL g / G / Gb or a row stride below C", fn);
+    GNX_CHECK_ARG(d_G != d_g || ldG == ldg, "%s: in place needs ldG == ldg", fn);
+    GNX_CHECK_ARG((const void *)d_Gb != (const void *)d_g && (const void *)d_Gb != (const void *)d_G, "%s: Gb must not alias g / G", fn);
+    const bool relu = act == GNX_ACT_RELU;
+    GNX_CHECK_ARG(!relu || (d_y != nullptr && ldy >= C && d_y != d_Gb), "%s: relu needs y (not Gb itself) with ldy >= C", fn);
+    DropFuse fd{};
+    int rc = make_feat_drop(fn, g, dropout_p, seed, stream_id, fd);
+    if (rc != GNX_OK) return rc;
+    if (n_rows == 0) return GNX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const bool v4 = C % 4 == 0 && ldg % 4 == 0 && ldG % 4 == 0 && ldGb % 4 == 0 && aligned(d_g, 16) && aligned(d_G, 16) && aligned(d_Gb, 8) &&
+                    (!relu || (ldy % 4 == 0 && aligned(d_y, 8)));
+    const unsigned grid = (unsigned)std::min<int64_t>(blocks_for(n_rows * (v4 ? C / 4 : C), 256), 1 << 20);
+#define GNX_GATE(VEC, RELU) hipLaunchKernelGGL((k_feature_dropout_back_bf16<VEC, RELU>), dim3(grid), dim3(256), 0, s, d_g, ldg, d_y, ldy, n_rows, C, fd, d_G, ldG, d_Gb, ldGb)
+    if (v4 && relu)  GNX_GATE(4, true);
+    else if (v4)     GNX_GATE(4, false);
+    else if (relu)   GNX_GATE(1, true);
+    else             GNX_GATE(1, false);
+#undef GNX_GATE
+    GNX_HIP(hipGetLastError());
+    return GNX_OK;
+}
+
+int gnx_gcnii_step_back_bf16(gnx_graph_t g, const float *d_vals_t, const uint16_t *d_Gb, const float *d_G, float a, int64_t C, const float *d_Mt,
+                             int64_t ldmt, float *d_dH, const float *d_S_in, float s_alpha, float *d_S_out, float *d_work, void *stream) {
+    const char *fn = "gnx_gcnii_step_back_bf16";
+    int rc = check_common(fn, g, d_Gb, C, C, d_S_in, C, d_dH, C);
+    if (rc != GNX_OK) return rc;
+    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "%s: needs a square graph", fn);
+    GNX_CHECK_ARG(d_Mt != nullptr && ldmt >= C, "%s: NULL Mt or ldmt < C", fn);
+    GNX_CHECK_ARG(d_S_in == nullptr || d_S_out != nullptr, "%s: S_in without S_out", fn);
+    GNX_CHECK_ARG((d_G == nullptr) == (d_S_out == nullptr), "%s: d_G (the f32 gated gradient of the row's own product) goes with d_S_out: both or neither", fn);
+    GNX_CHECK_ARG(d_dH != d_S_in && d_dH != d_S_out && d_dH != d_Mt && d_dH != d_G, "%s: dH must not alias G / S_in / S_out / Mt", fn);
+    GNX_CHECK_ARG(d_S_out == nullptr || (d_S_out != d_G && d_S_out != d_Mt && (const void *)d_S_out != (const void *)d_Gb), "%s: S_out must not alias G / Gb / Mt", fn);
+    GNX_CHECK_ARG(d_work == nullptr || (d_work != d_G && (const void *)d_work != (const void *)d_Gb && d_work != d_dH && d_work != d_S_in &&
+                                        d_work != d_S_out && d_work != d_Mt), "%s: d_work must be a buffer of its own", fn);
+    rc = refuse_unfused(fn, C, aligned(d_Gb, 8) && aligned(d_G, 16) && aligned(d_dH, 16) && aligned(d_S_in, 16) && aligned(d_S_out, 16));
+    if (rc != GNX_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    rc = ensure_transpose(g, s);
+    if (rc != GNX_OK) return rc;
+    const Csr &m = g->t;
+    if (m.n_rows == 0) return GNX_OK;
+    if (m.n_long > 0) {   // (before the first launch, as in gnx_gcnii_step_back)
+        rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)C * sizeof(float), s);
+        if (rc != GNX_OK) return rc;
+    }
+    SpmmArgs p{};
+    p.vals = d_vals_t ? d_vals_t : g->t_raw.get();
+    p.ldx = C; p.beta = (float)(1.0 - (double)a); p.alpha = a; p.act = GNX_ACT_NONE; p.out = d_dH; p.ldo = C; p.C = (int)C;
+    bind_fused(m, p);
+    BfArgs q{};
+    static_cast<SpmmArgs &>(q) = p;
+    q.Xb = d_Gb; q.X = d_G;       // the gathered rows / the row's own f32 row (k_spmm_gcnii_back); dH is the f32 p.out
+    const unsigned grid = blocks_for(blocks_for(m.n_rows, 16), 8);
+    if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii_back<Bf16Rows, 4, 4, 8>), dim3(grid), dim3(512), 0, s, q, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
+    else if (C == 32) hipLaunchKernelGGL((k_spmm_gcnii_back<Bf16Rows, 2, 4, 8>), dim3(grid), dim3(512), 0, s, q, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
+    else              hipLaunchKernelGGL((k_spmm_gcnii_back<Bf16Rows, 1, 4, 8>), dim3(grid), dim3(512), 0, s, q, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
+    g->last_kernel = "spmm_gcnii_back_mfma_bf16";
+    if (m.n_long > 0) {   // hub rows of the transposed structure: chunked partial sums over Gb -> (1-a) Z into dH -> those rows alone times Mt, in place
+        p.partial = g->partial;
+        launch_long_rows_bf16(p, d_Gb, d_dH, s);
+        rc = dense_rows(d_dH, C, m.n_long, C, d_Mt, ldmt, C, nullptr, GNX_ACT_NONE, m.long_rows, m.long_rows, d_dH, C, s);
+        if (rc != GNX_OK) return rc;
     }
     GNX_HIP(hipGetLastError());
     return GNX_OK;

@@ -50,7 +50,8 @@ class GNN(Trainable):
     fuse_entry_dropout = True
 
     def __init__(self, graph, features, preprocessor: Layer = None, reorder=None, inference_dtype=torch.float32,
-                 training_dtype=torch.float32, train_gather_order="auto", gcnii_backward="composed", feature_dropout="torch"):
+                 training_dtype=torch.float32, train_gather_order="auto", gcnii_backward="composed", feature_dropout="torch",
+                 gcnii_training_dtype=torch.float32):
         """``reorder`` (opt-in, not in the reference): store the graph and the feature rows with the vertices relabelled; every
         [N, .] tensor inside the model then lives in that order, and the model's OUTPUT is put back into the caller's order, so
         tasks, labels and node ids are unaffected.  Results agree with the unordered model to float32 rounding.
@@ -80,8 +81,8 @@ class GNN(Trainable):
         both results of the step stay f32, a row is rounded once as it is handed to the next iteration.  It is an allowance: the
         loop keeps f32 -- today's bits -- where the fused chained form does not apply (relu, no edge dropout, a graph that cannot
         fuse its dropout), below sparse.BF16_TRAIN_MIN_WIDTH columns and on graphs of fewer than sparse.BF16_TRAIN_MIN_ROWS vertices
-        (where it measured slower).  It is ignored by GCNLayer / GCNIILayer training (GCNII training keeps gnx_gcnii_step) and by the
-        vertex-partitioned path (sharded.py), which keep f32 whatever it says.
+        (where it measured slower).  It is ignored by GCNLayer / GCNIILayer training (GCNII training has a switch of its own,
+        ``gcnii_training_dtype`` below) and by the vertex-partitioned path (sharded.py), which keep f32 whatever it says.
         ``train_gather_order`` (not in the reference): ``"caller"``, ``"relabelled"`` or ``"auto"`` (sparse.ppr_loop
         ``gather_order``).  ``"relabelled"``: the fused f32 training loops (PPRLoop, fused runs of PPRIteration layers, with edge
         dropout) keep the iterate and the back-propagated gradient in the library's hub-adjacent gather order BETWEEN their launches;
@@ -104,7 +105,21 @@ class GNN(Trainable):
         f32 1 / (1 - p).  The masks differ from torch's, which is why it is opt-in; a training step is then reproducible from
         (seed, stream) alone, and ``train(capture=True)`` equals the eager run bit for bit.  GCNIISpectralPreservingLayer, other
         activations, CPU tensors, Dense / Dropout layers and the vertex-partitioned path keep torch's dropout whatever it says
-        (measurement: profiles/NOTES.md "Fused GCNII feature dropout")."""
+        (measurement: profiles/NOTES.md "Fused GCNII feature dropout").
+        ``gcnii_training_dtype=torch.bfloat16`` (opt-in, not in the reference; a keyword of its own, so that ``training_dtype`` on an
+        existing GCNII model keeps today's bits): in training mode with grad enabled a RUN of at least two consecutive plain GCNIILayer
+        layers (the class itself, relu or the identity as activation, a float ``a``, no add_eye, ``graph_dropout`` 0 -- a constant
+        adjacency --, and ``dropout`` 0 or ``feature_dropout="fused"`` with 0 < dropout < 1, so that nothing sits between two layers)
+        executes as ONE autograd node over bf16 rows (sparse.gcnii_train_run_bf16): the run's input is rounded once, every layer but
+        the run's last stores its (dropped) output rounded once to bf16 -- what the next layer gathers and what is saved for the
+        backward --, the last writes f32; on the way back the gated gradient is gathered as bf16.  Sums, H0, the mixed rows T, the
+        mix, the transform, the weight gradients and the running dH0 sums stay f32.  The layers draw their mask streams in layer
+        order, so the masks are those of the f32 ``"fused"`` path under the same seed; the backward is always the fused one.  The
+        ``.value`` of an inner layer is the detached exact widening of its stored rows, made on first read.  It is an allowance:
+        widths outside {16, 32, 64} or below sparse.GCNII_BF16_TRAIN_MIN_WIDTH, graphs of fewer than
+        sparse.GCNII_BF16_TRAIN_MIN_ROWS rows (where the step measured slower: profiles/NOTES.md "bf16 storage in GCNII training" --
+        4 % faster at C = 32 / 64 on 10^7 vertices, slower at C = 16 and at 10^6 vertices and below), GCNIISpectralPreservingLayer,
+        torch dropout, eval mode, the vertex-partitioned path and ``fuse_runs = False`` keep today's path and today's bits."""
         if feature_dropout not in FEATURE_DROPOUTS:
             raise Exception("GNN: feature_dropout must be one of " + ", ".join(repr(f) for f in FEATURE_DROPOUTS))
         if gcnii_backward not in sparse.GCNII_BACKWARDS:
@@ -115,9 +130,12 @@ class GNN(Trainable):
             raise Exception("GNN: inference_dtype must be torch.float32 or torch.bfloat16")
         if training_dtype not in (torch.float32, torch.bfloat16):
             raise Exception("GNN: training_dtype must be torch.float32 or torch.bfloat16")
+        if gcnii_training_dtype not in (torch.float32, torch.bfloat16):
+            raise Exception("GNN: gcnii_training_dtype must be torch.float32 or torch.bfloat16")
         super().__init__(features)
         self.inference_dtype = inference_dtype
         self.training_dtype = training_dtype
+        self.gcnii_training_dtype = gcnii_training_dtype
         self.train_gather_order = train_gather_order
         self.gcnii_backward = gcnii_backward
         self.feature_dropout = feature_dropout
@@ -426,7 +444,10 @@ class GCNIILayer(Layer):
     the mix and the transform stay f32 (dropout is the identity in eval mode, so nothing sits between the layers).  The ``.value``
     of an inner layer of the run is the exact widening of its bf16 rows, computed when somebody reads it.  Widths outside
     sparse.GCNII_BF16_MIN_WIDTH ... GCNII_BF16_MAX_WIDTH, every forward under autograd or in training mode, and
-    GCNIISpectralPreservingLayer keep the f32 path and its bits.  ``architecture.fuse_runs = False`` switches the chain off."""
+    GCNIISpectralPreservingLayer keep the f32 path and its bits.  ``architecture.fuse_runs = False`` switches the chain off.
+
+    On a GNN with ``gcnii_training_dtype=torch.bfloat16`` a run of such layers in TRAINING mode executes as one autograd node over
+    bf16 rows (sparse.gcnii_train_run_bf16; the conditions and the rounding points: GNN.__init__)."""
 
     # ``.value`` may be pending after a bf16 run: computed on first read (as PPRIteration's)
     @property
@@ -454,7 +475,54 @@ class GCNIILayer(Layer):
                 and isinstance(getattr(self.H0, "value", None), torch.Tensor)
                 and gcn.get_adjacency(self.graph_dropout).diag is None)
 
+    def _bf16_train_plain(self, gcn, first) -> bool:
+        """Whether this layer can be one step of a training-mode bf16 run that ``first`` starts (the run's own conditions: _bf16_train_run)."""
+        fused_drop = getattr(gcn, "feature_dropout", "torch") == "fused" and 0 < self.dropout < 1
+        return (type(self) is GCNIILayer and (self.activation is relu or self.activation is linear)
+                and isinstance(self.a, (int, float)) and not isinstance(self.a, bool)
+                and (self.dropout == 0 or fused_drop) and self.graph_dropout == first.graph_dropout
+                and self.W.shape[1] == first.W.shape[1] and isinstance(getattr(self.H0, "value", None), torch.Tensor))
+
+    def _bf16_train_run(self, gcn, stack, at):
+        """The layers of the training-mode bf16 run that starts with this layer (GNN.__init__ ``gcnii_training_dtype``), or None where
+        today's path applies.  Looks at the model alone -- no tensor is read, no mask stream is drawn -- so it can be asked anywhere."""
+        if not (isinstance(gcn, GNN) and getattr(gcn, "gcnii_training_dtype", torch.float32) is torch.bfloat16 and gcn.fuse_runs
+                and gcn.is_training() and torch.is_grad_enabled()):
+            return None
+        width = self.W.shape[1]
+        # (graph_dropout != 0 is a DroppedAdjacency in training mode: its weights are made in the SpMM, and asking for it draws a stream)
+        if (self.graph_dropout != 0 or width not in sparse.GCNII_BF16_TRAIN_WIDTHS or width < sparse.GCNII_BF16_TRAIN_MIN_WIDTH
+                or gcn.graph.n_rows < sparse.GCNII_BF16_TRAIN_MIN_ROWS or gcn.graph.n_rows != gcn.graph.n_cols
+                or not self._bf16_train_plain(gcn, self) or gcn.get_adjacency(self.graph_dropout).diag is not None):
+            return None
+        run = [self]
+        for layer in stack[at + 1:]:
+            # (a layer whose H0 is a layer INSIDE the run would need that layer's value first: it ends the run)
+            if not (isinstance(layer, GCNIILayer) and layer._bf16_train_plain(gcn, self)
+                    and all(layer is not seen and layer.H0 is not seen for seen in run)):
+                break
+            run.append(layer)
+        return run if len(run) >= 2 else None
+
+    def _run_bf16_training(self, gcn, features, run):
+        adjacency = gcn.get_adjacency(self.graph_dropout)
+        steps = []
+        for layer in run:                                       # the mask streams in layer order: those of the f32 "fused" path
+            triple = (layer.dropout,) + tuple(gcn._next_mask_stream()) if layer.dropout != 0 else None
+            steps.append((layer.H0.value, float(layer.a), layer._transform(), layer.activation is relu, triple))
+        stored = []
+        out = sparse.gcnii_train_run_bf16(adjacency, features, steps, stored=stored)
+        for k, layer in enumerate(run[:-1]):
+            layer.__dict__["_value"] = None
+            layer.__dict__["_pending_value"] = lambda k=k: stored[k].float()
+        run[-1].value = out
+        return len(run), out
+
     def __run__(self, gcn, features, stack, at):
+        if isinstance(features, torch.Tensor) and features.is_cuda and features.dtype == torch.float32:
+            run = self._bf16_train_run(gcn, stack, at)
+            if run is not None:
+                return self._run_bf16_training(gcn, features, run)
         if _eval_storage(gcn) is not torch.bfloat16 or not isinstance(features, torch.Tensor) or not features.is_cuda \
                 or not self._bf16_plain(gcn):
             return None

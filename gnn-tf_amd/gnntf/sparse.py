@@ -1326,6 +1326,164 @@ def gcnii_chain_bf16(adj: Adjacency, H: torch.Tensor, steps, widen_last=False) -
     return X.float() if widen_last else X
 
 
+# ---- bf16 row storage for GCNII training (opt-in): gnx_gcnii_step_train_bf16, gnx_feature_dropout_back_bf16, gnx_gcnii_step_back_bf16 ----
+# the model-level path (GCNIILayer.__run__, GNN(gcnii_training_dtype=torch.bfloat16)) keeps f32 below this width and on graphs of fewer
+# rows: the allowance, set from tools/gcnii_bf16_train_bench.py (profiles/NOTES.md "bf16 storage in GCNII training"; the training step of
+# an 8-layer stack, f32 "fused" against bf16 interleaved): a width / graph size gets bf16 only where its step measured faster with the
+# quartile ranges apart.  At 10^7 vertices / 10^8 entries C = 32 and C = 64 gain 1.04 x and C = 16 loses 9 %; at 10^6 vertices every
+# width loses 4 - 8 %, on the Cora-shaped graph 1 - 4 %; nothing between 10^6 and 10^7 was measured, so the smallest size that measured a
+# gain is the threshold.  The functions below are not gated.
+GCNII_BF16_TRAIN_MIN_WIDTH = 32
+GCNII_BF16_TRAIN_MIN_ROWS = 10_000_000
+GCNII_BF16_TRAIN_WIDTHS = (16, 32, 64)
+
+
+def _gcnii_bf16_operands(what, adj, rows, *f32):
+    """The checks the three bf16 training pieces share: a constant square adjacency without a diagonal, device tensors on its device,
+    ``rows`` (bf16 or f32, [n, C]) and every ``f32`` matrix of that shape; returns (graph, C)."""
+    if isinstance(adj, DroppedAdjacency):
+        raise Exception(f"{what}: bf16 training storage needs a constant adjacency (a DroppedAdjacency makes its weights in the SpMM)")
+    if adj.diag is not None:
+        raise Exception(f"{what}: add_eye adjacencies are not supported by the fused step")
+    g = adj.graph
+    nat.require_cuda(rows, *f32)
+    _same_device(g, rows, *f32)
+    if rows.dim() != 2 or g.n_rows != g.n_cols or rows.shape[0] != g.n_rows:
+        raise Exception(f"{what}: shape mismatch")
+    for t in f32:
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != tuple(rows.shape) or not t.is_contiguous()):
+            raise Exception(f"{what}: shape mismatch")
+    return g, rows.shape[1]
+
+
+def gcnii_step_train_bf16(adj: Adjacency, Hb: torch.Tensor, H0: torch.Tensor, a: float, M: torch.Tensor, relu=True, dropout=None,
+                          out_bf16=True, work=None):
+    """The training forward of one GCNII layer over bf16 gathered rows (gnx_gcnii_step_train_bf16; no autograd): returns (out, T) with
+    T = (1-a) A.H~ + a H0 in f32, undropped, and out = drop(act(T . M)) as bf16 (``out_bf16``) or f32.  ``Hb``: bf16 [n, C] contiguous,
+    C in {16, 32, 64}; ``dropout`` = (p, seed, stream) or None; ``work``: an f32 [n, C] buffer a run of layers shares (graphs with hub
+    rows need one; None allocates it)."""
+    H0, M = _as_f32_rows(H0).contiguous(), _as_f32_rows(M)
+    g, C = _gcnii_bf16_operands("gcnii_step_train_bf16", adj, Hb, H0, work)
+    nat.require_cuda(M)
+    if Hb.dtype != torch.bfloat16 or not Hb.is_contiguous() or tuple(M.shape) != (C, C):
+        raise Exception("gcnii_step_train_bf16: needs contiguous bf16 rows [n, C] and M [C, C]")
+    p, seed, stream = _dropout_triple(dropout, "gcnii_step_train_bf16") or (0.0, 0, 0)
+    out = torch.empty(Hb.shape, dtype=torch.bfloat16 if out_bf16 else torch.float32, device=Hb.device)
+    T = torch.empty(Hb.shape, dtype=torch.float32, device=Hb.device)
+    if work is None:
+        work = torch.empty_like(T)
+    with nat.on_device(Hb.device):
+        nat.check(nat.lib().gnx_gcnii_step_train_bf16(g.handle, nat.ptr(adj.vals), nat.ptr(Hb), nat.ptr(H0), float(a), C, nat.ptr(M), M.stride(0),
+                                                      nat.ACT_RELU if relu else nat.ACT_NONE, p, seed, stream, nat.ptr(out),
+                                                      1 if out_bf16 else 0, nat.ptr(T), nat.ptr(work), nat.current_stream()))
+    return out, T
+
+
+def feature_dropout_back_bf16(graph: DeviceGraph, g: torch.Tensor, yb, dropout=None, relu=True):
+    """The backward's gate over the STORED bf16 output ``yb`` of a layer (gnx_feature_dropout_back_bf16): returns (G, Gb) with
+    G = kept ? g * s : 0 in f32 -- with ``relu`` also 0 where the stored y <= 0 -- and Gb = bf(G).  ``dropout`` = (p, seed, stream) or
+    None (the relu gate plus the cast); any width."""
+    g = _as_f32_rows(g).contiguous()
+    nat.require_cuda(g, yb)
+    _same_device(graph, g, yb)
+    if relu and (yb is None or yb.dtype != torch.bfloat16 or tuple(yb.shape) != tuple(g.shape) or not yb.is_contiguous()):
+        raise Exception("feature_dropout_back_bf16: relu needs the stored bf16 output, contiguous, in the gradient's shape")
+    p, seed, stream = _dropout_triple(dropout, "feature_dropout_back_bf16") or (0.0, 0, 0)
+    G, Gb = torch.empty_like(g), torch.empty(g.shape, dtype=torch.bfloat16, device=g.device)
+    if g.numel() == 0:
+        return G, Gb
+    yb = yb if relu else None
+    with nat.on_device(g.device):
+        nat.check(nat.lib().gnx_feature_dropout_back_bf16(graph.handle, nat.ptr(g), g.stride(0), nat.ptr(yb), 0 if yb is None else yb.stride(0),
+                                                          g.shape[0], g.shape[1], p, seed, stream, nat.ACT_RELU if relu else nat.ACT_NONE,
+                                                          nat.ptr(G), G.stride(0), nat.ptr(Gb), Gb.stride(0), nat.current_stream()))
+    return G, Gb
+
+
+def gcnii_step_back_bf16(adj: Adjacency, Gb: torch.Tensor, G, a: float, Mt: torch.Tensor, S_in=None, s_alpha=1.0, want_S=True, in_place=False):
+    """gcnii_step_back with the gathered operand in bf16 (gnx_gcnii_step_back_bf16; no autograd): dH = ((1-a) A^T Gb~) . Mt in f32 and
+    S = s_alpha S_in + (a G) . Mt from the f32 ``G`` (None with ``want_S=False``).  Returns (dH, S); ``in_place``: S is S_in itself."""
+    Mt = _as_f32_rows(Mt)
+    g, C = _gcnii_bf16_operands("gcnii_step_back_bf16", adj, Gb, G, S_in)
+    nat.require_cuda(Mt)
+    if Gb.dtype != torch.bfloat16 or not Gb.is_contiguous() or tuple(Mt.shape) != (C, C):
+        raise Exception("gcnii_step_back_bf16: needs contiguous bf16 rows [n, C] and Mt [C, C]")
+    if want_S == (G is None) or (S_in is not None and not want_S) or (in_place and S_in is None):
+        raise Exception("gcnii_step_back_bf16: the f32 G goes with want_S, S_in needs want_S, in_place needs S_in")
+    dH = torch.empty(Gb.shape, dtype=torch.float32, device=Gb.device)
+    S = (S_in if in_place else torch.empty_like(dH)) if want_S else None
+    values = adj.transposed_values()
+    with nat.on_device(Gb.device):
+        nat.check(nat.lib().gnx_gcnii_step_back_bf16(g.handle, nat.ptr(values), nat.ptr(Gb), nat.ptr(G), float(a), C, nat.ptr(Mt), Mt.stride(0),
+                                                     nat.ptr(dH), nat.ptr(S_in), float(s_alpha), nat.ptr(S), None, nat.current_stream()))
+    return dH, S
+
+
+class _GCNIITrainRunBf16(torch.autograd.Function):
+    """A run of GCNII training layers over bf16 rows as ONE autograd node (as _PPRLoop is for K iterations).  forward: the f32 input is
+    rounded once, layer l gathers the stored rows of layer l - 1, every layer but the last stores bf(out), the last f32; saved per layer:
+    the f32 T and the stored out.  backward, last layer first: the gate (G, Gb) -> dM = T^T G (gnx_dense_wgrad, f32) -> one launch for
+    dH (the next upstream gradient) and the layer's term of dH0; consecutive layers that share one H0 tensor add their terms into one
+    running sum (S_in = S_out, s_alpha = 1), another H0 starts a new sum.  Tensor arguments: H, then (H0, M) per layer."""
+
+    @staticmethod
+    def forward(ctx, adj, meta, same_H0, stored, H, *tensors):
+        X = to_bf16(H)
+        work = torch.empty(H.shape, dtype=torch.float32, device=H.device)
+        saved, n = [], len(meta)
+        for k, (a, relu, dropout) in enumerate(meta):
+            H0, M = tensors[2 * k], tensors[2 * k + 1]
+            X, T = gcnii_step_train_bf16(adj, X, H0, a, M, relu, dropout, out_bf16=k < n - 1, work=work)
+            saved += [T, M, X]
+            if stored is not None and k < n - 1:
+                stored.append(X)
+        ctx.adj, ctx.meta, ctx.same_H0 = adj, meta, same_H0
+        ctx.save_for_backward(*saved)
+        return X
+
+    @staticmethod
+    def backward(ctx, g):
+        adj, meta, saved = ctx.adj, ctx.meta, ctx.saved_tensors
+        n = len(meta)
+        need = ctx.needs_input_grad[5:]
+        grads = [None] * (2 * n)
+        S = None                                                    # the running dH0 sum of the layers k .. that share one H0
+        for k in range(n - 1, -1, -1):
+            (a, relu, dropout), (T, M, out) = meta[k], saved[3 * k:3 * k + 3]
+            if k == n - 1:                                          # the run's f32 output: the existing gate, then the cast
+                G = _feature_dropout_back(adj.graph, g, out, *(dropout or (0.0, 0, 0)), relu=relu)
+                Gb = to_bf16(G)
+            else:
+                G, Gb = feature_dropout_back_bf16(adj.graph, g, out, dropout, relu)
+            if need[2 * k + 1]:
+                grads[2 * k + 1] = _dense_wgrad(T, G)
+            want_S = need[2 * k]
+            continues = want_S and S is not None                    # (S is not None: layer k + 1 shares this layer's H0 and wanted its sum)
+            g, S = gcnii_step_back_bf16(adj, Gb, G if want_S else None, a, M.t().contiguous(), S_in=S if continues else None,
+                                        want_S=want_S, in_place=continues)
+            if not ctx.same_H0[k]:                                  # the sum ends with the first layer of its H0: one gradient per sum
+                grads[2 * k], S = S, None
+        return (None, None, None, None, g if ctx.needs_input_grad[4] else None) + tuple(grads)
+
+
+def gcnii_train_run_bf16(adj: Adjacency, H: torch.Tensor, steps, stored=None) -> torch.Tensor:
+    """A run of GCNII layers in TRAINING with the rows handed from layer to layer -- and the gated gradient on the way back -- stored as
+    bf16 (opt-in; one autograd node for the whole run).  ``steps``: per layer (H0, a, M, relu, dropout) with dropout = (p, seed, stream)
+    of the fused feature dropout or None.  The run's f32 input is rounded once (its gradient passes straight through), every layer but
+    the last stores bf(out), the last writes f32; sums, H0, T, the mix, the transform, dM and the running dH0 sums stay f32.  Widths 16,
+    32 and 64 on a constant square adjacency without a diagonal; device tensors.  ``stored``: a list that receives the bf16 rows of
+    every layer but the last (what an inner layer's ``.value`` widens).  The backward is the fused one (gcnii_step_back_bf16)."""
+    steps = [(H0, float(a), M, bool(relu), _dropout_triple(dropout, "gcnii_train_run_bf16")) for H0, a, M, relu, dropout in steps]
+    if not steps:
+        raise Exception("gcnii_train_run_bf16: no layers")
+    g, C = _gcnii_bf16_operands("gcnii_train_run_bf16", adj, H, *[H0 for H0, *_ in steps])
+    if H.dtype != torch.float32 or C not in GCNII_BF16_TRAIN_WIDTHS:
+        raise Exception("gcnii_train_run_bf16: needs f32 rows of width 16, 32 or 64")
+    tensors = [t for H0, _, M, _, _ in steps for t in (H0, M)]
+    same_H0 = tuple(k > 0 and steps[k][0] is steps[k - 1][0] for k in range(len(steps)))          # layer k shares its H0 tensor with layer k - 1
+    return _GCNIITrainRunBf16.apply(adj, tuple((a, relu, dropout) for _, a, _, relu, dropout in steps), same_H0, stored, H.contiguous(), *tensors)
+
+
 class DeviceIndex:
     """Node ids / labels / edges of a task, checked ONCE on the host (range) and kept on the device: a task evaluates the same
     index lists every epoch, and on small graphs an upload + a device-side check per call would dominate the epoch.

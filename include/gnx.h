@@ -60,7 +60,8 @@ const char *gnx_last_error(void);
  * 900): a client that wants it probes the library for the symbol (dlsym) instead of comparing versions.  So were the gather-order
  * entries (gnx_graph_gather_order, gnx_spmm_dropped_chained_ord, gnx_spmm_dropped_back_ord, GNX_RESERVE_TRAIN_GATHER), likewise, and
  * gnx_gcnii_step_back (the fused backward of the GCNII layer), likewise, and the feature dropout of the GCNII training layer
- * (gnx_gcnii_step_drop, gnx_feature_dropout, gnx_feature_dropout_back), likewise. */
+ * (gnx_gcnii_step_drop, gnx_feature_dropout, gnx_feature_dropout_back), likewise, and the bf16 row storage of GCNII training
+ * (gnx_gcnii_step_train_bf16, gnx_feature_dropout_back_bf16, gnx_gcnii_step_back_bf16), likewise. */
 #define GNX_ABI_VERSION 900
 int gnx_version(void);
 
@@ -486,6 +487,46 @@ int gnx_feature_dropout(gnx_graph_t g, const float *d_X, int64_t ldx, int64_t n_
 int gnx_feature_dropout_back(gnx_graph_t g, const float *d_g, int64_t ldg, const float *d_y, int64_t ldy, int64_t n_rows, int64_t C,
                              double dropout_p, uint64_t seed, uint64_t stream_id, int act, float *d_G, int64_t ldG, void *stream);
 
+/* bf16 row storage for GCNII TRAINING (opt-in; added within ABI 0.9 -- probe for the symbols): the rows a training-mode stack of GCNII
+ * layers gathers -- the layer's input on the way forward, the gated gradient on the way back -- are stored as bf16 (uint16_t bit
+ * patterns, [n, C] contiguous; bf = the cast of gnx_cast_bf16), everything that is summed stays f32.  With the feature dropout in the
+ * launch (above) nothing sits between two layers, so layer l hands bf(out_l) straight to layer l + 1, as gnx_gcnii_step_bf16 does in
+ * inference.  The two launch entries take C in {16, 32, 64} with the f32 buffers 16-byte and the bf16 buffers 8-byte aligned and
+ * return GNX_ERR_UNSUPPORTED (naming the width or the alignment) for anything else, nothing launched: callers keep f32 there.  Square
+ * stand-alone graphs without a diagonal.  No float atomics: two calls give the same bits.
+ *
+ * gnx_gcnii_step_train_bf16, the forward: gnx_gcnii_step_drop over bf16 gathered rows d_H,
+ *   T = (1-a) * A_hat . H~ + a * H0 (f32, UNDROPPED, into d_mixed by the same launch: required),   out = drop(act(T . M)),
+ * stored as f32 (out_bf16 = 0, float [n, C]) or as bf(.) (out_bf16 = 1, uint16_t [n, C]): that one store is the only rounding the
+ * entry adds.  p == 0 hashes nothing.  Over bf16-representable H, d_mixed and an f32 out are bit for bit those of gnx_gcnii_step_drop
+ * (gnx_gcnii_step at p == 0) over the widened H, a bf16 out the bits of gnx_cast_bf16 of that.  Hub rows go through the bf16 long-row
+ * chunk kernels straight into d_mixed; the dense kernel transforms those rows alone (into d_out, or into d_work when out_bf16 = 1), the
+ * row-list dropout pass masks them in place and they are rounded into d_out when out_bf16 = 1.  d_work: f32 [n, C], a buffer of its
+ * own; may be NULL exactly when the handle has no hub rows (GNX_ERR_INVALID naming d_work otherwise).  Capture and reserve: as
+ * gnx_gcnii_step_bf16.  Reports "spmm_gcnii_mfma_train_bf16".
+ *
+ * gnx_feature_dropout_back_bf16, the gate: gnx_feature_dropout_back reading the STORED bf16 forward output y and writing the gated
+ * gradient twice, G = kept ? g * s : +0 (f32; with GNX_ACT_RELU also +0 where the stored y <= 0 -- a positive f32 value that rounded
+ * to bf16 zero was stored as zero and passes no gradient) and Gb = bf(G), the operand the backward gathers.  One pass, any width;
+ * p == 0 is the relu gate plus the cast.  d_y may be NULL with GNX_ACT_NONE; d_G may be d_g (with ldG == ldg).  Reports nothing.
+ *
+ * gnx_gcnii_step_back_bf16, the backward: gnx_gcnii_step_back with the GATHERED operand in bf16,
+ *   Z[r] = sum_c A_hat[c][r] Gb~[c],   dH[r] = ((1-a) Z[r]) . Mt (f32),   S_out[r] = s_alpha * S_in[r] + (a G[r]) . Mt
+ * -- the row's own product reads the f32 d_G, so the running dH0 sum never sees a rounded addend.  d_G may be NULL exactly when
+ * d_S_out is NULL.  Over bf16-representable G (Gb = bf(G) exactly) dH and S_out are bit for bit those of gnx_gcnii_step_back.  Hub rows
+ * of the transposed structure go through the bf16 long-row chunk kernels into d_dH and the dense kernel transforms those rows alone,
+ * in place.  d_work is not used (the other widths are refused, not composed) and may be NULL.  The aliasing, capture and reserve rules
+ * of gnx_gcnii_step_back.  Reports "spmm_gcnii_back_mfma_bf16". */
+int gnx_gcnii_step_train_bf16(gnx_graph_t g, const float *d_vals, const uint16_t *d_H, const float *d_H0, float a, int64_t C,
+                              const float *d_M, int64_t ldm, int act, double dropout_p, uint64_t seed, uint64_t stream_id,
+                              void *d_out, int out_bf16, float *d_mixed, float *d_work, void *stream);
+int gnx_feature_dropout_back_bf16(gnx_graph_t g, const float *d_g, int64_t ldg, const uint16_t *d_y, int64_t ldy, int64_t n_rows,
+                                  int64_t C, double dropout_p, uint64_t seed, uint64_t stream_id, int act, float *d_G, int64_t ldG,
+                                  uint16_t *d_Gb, int64_t ldGb, void *stream);
+int gnx_gcnii_step_back_bf16(gnx_graph_t g, const float *d_vals_t, const uint16_t *d_Gb, const float *d_G, float a, int64_t C,
+                             const float *d_Mt, int64_t ldmt, float *d_dH, const float *d_S_in, float s_alpha, float *d_S_out,
+                             float *d_work, void *stream);
+
 /* ---- the dense ends of the path (matrix cores) -----------------------------------------------------------------------
  * gnx_dense: out = act(X . W + bias) -- Dense.__forward__ (gnntf/core/nn/layers.py:135-136) and the transform of
  * GCNLayer (gcn.py:89).  X [n, F] (ldx), W [F, O] (ldw), bias [O] or NULL, out [n, O] (ldo); float32 in and out, float32
@@ -617,7 +658,8 @@ int gnx_probe_block_xcd(int64_t n_blocks, int32_t *d_xcd_out, void *stream);
  * launch, with or without hub rows) or "spmm+dense_mfma_bf16" (the other widths / alignments); gnx_gcnii_step_back reports
  * "spmm_gcnii_back_mfma" (the fused launch, with or without hub rows) or "dense+spmm_back" (the other widths / alignments);
  * gnx_gcnii_step_drop reports "spmm_gcnii_mfma_drop" or "spmm+dense_mfma_drop" likewise (with p == 0 the names of gnx_gcnii_step); the
- * two dropout passes report nothing. */
+ * two dropout passes report nothing; gnx_gcnii_step_train_bf16 reports "spmm_gcnii_mfma_train_bf16" and gnx_gcnii_step_back_bf16
+ * "spmm_gcnii_back_mfma_bf16" (the fused launches, with or without hub rows: those two entries have no other form). */
 const char *gnx_graph_last_kernel(gnx_graph_t g);
 
 #ifdef __cplusplus
