@@ -1,12 +1,21 @@
-// The GCNII layer (gcn.py:7-27,54-74) in one launch on gfx950: SpMM + residual mix + the C x C transform on the matrix cores.
-// Shares the gathers' device code and the long-row path with gnx_spmm.hip (gnx_spmm_device.h, gnx::launch_long_rows).
-// gnx_gcnii_step_bf16 (inference, opt-in): the same kernel over bf16 feature rows (the row-storage policy of gnx_spmm_device.h), hub rows
-// and the other widths through the bf16 kernels of gnx_spmm_bf16.hip in the f32 launch's summation order; rounding points in gnx.h.
-// gnx_gcnii_step_back (training, opt-in): the layer's backward past the relu gate as one launch of the same shape over the transposed
-// structure (k_spmm_gcnii_back); the MFMA block of the two kernels is one device function (tile_times_Ms).
-// gnx_gcnii_step_drop (training, opt-in): the forward with the layer's feature dropout (gcn.py:27, layered.py:44-45) in the store loop of
-// the same launch (k_spmm_gcnii<.., DROP>), masks from the counter RNG of the edge dropout; gnx_feature_dropout / gnx_feature_dropout_back are
-// the mask as a pass of its own (hub rows, the other widths, the generic composition) and the backward's gate.
+// The GCNII layer (gcn.py:7-27,54-74) on gfx950.  The unit holds two fused kernels, three row passes, and ONE host path for each.
+//   k_spmm_gcnii       the layer in one launch: SpMM + residual mix + the C x C transform on the matrix cores (+ the layer's feature
+//                      dropout in the store loop, DROP), written once over the row-storage policy R of gnx_spmm_device.h
+//   k_spmm_gcnii_back  the layer's backward past the relu gate, one launch of the same shape over the transposed structure; the MFMA
+//                      block of the two is one device function (tile_times_Ms)
+//   row passes         k_round_rows (f32 rows -> bf16), k_feature_dropout (the mask as a pass of its own: hub rows, the other widths, the
+//                      generic composition) and the backward's gate (k_feature_dropout_back, .._back_bf16); one launcher
+//                      (launch_row_pass) picks their vector width and grid
+//   gcnii_forward<R>   the host path of gnx_gcnii_step, gnx_gcnii_step_drop (F32Rows), gnx_gcnii_step_bf16 and gnx_gcnii_step_train_bf16
+//                      (Bf16Rows); a ForwardForm says what differs: the mask, where mixed rows are kept or pass through memory, the format
+//                      of the result, and whether the widths other than 16 / 32 / 64 run as two launches or are refused.  The checks, the
+//                      operand fill, ensure_partial (before the first launch), the launch (with_tile_width) and the tail of the rows
+//                      that go through memory (transform_rows) each stand once
+//   gcnii_backward<R>  the host path of gnx_gcnii_step_back and gnx_gcnii_step_back_bf16, likewise; the f32 entry's composed form of the
+//                      other widths is its f32 branch
+// Hub rows share the long-row path of gnx_spmm.hip / gnx_spmm_bf16.hip (launch_long_rows, launch_long_rows_bf16: the f32 launch's
+// summation order) and the dense kernel on those rows alone; rounding points in gnx.h.  The masks come from the counter RNG of the edge
+// dropout.
 #include "gnx_spmm_device.h"
 
 namespace {
@@ -265,6 +274,28 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii_back(const typename R::
 
 using Bf16Rows = Bf16RowsT<false>;
 
+// f(IntC<NT>, grid) for the two fused kernels at width C = 16 NT in {16, 32, 64}: blocks of 512 threads, a 16-row tile per wave
+template <typename F>
+void with_tile_width(int64_t C, int64_t n_rows, F &&f) {
+    const dim3 grid(blocks_for(blocks_for(n_rows, 16), 8));
+    if (C == 64)      f(IntC<4>{}, grid);
+    else if (C == 32) f(IntC<2>{}, grid);
+    else              f(IntC<1>{}, grid);
+}
+
+// ---- the row passes: a thread per VEC columns of an [n, C] matrix, grid-stride above 2^20 blocks of 256 -------------------------------
+// launch(IntC<VEC>, grid): VEC = 4 (16-byte f32 / 8-byte bf16 accesses) where C and every buffer of the pass allow it, else 1
+struct RowsAt { const void *base; size_t align; int64_t ld; };      // a buffer of the pass: its base, the alignment VEC = 4 needs, its row stride
+
+template <typename F>
+void launch_row_pass(int64_t n, int64_t C, std::initializer_list<RowsAt> buffers, F &&launch) {
+    bool v4 = C % 4 == 0;
+    for (const RowsAt &b : buffers) v4 = v4 && b.ld % 4 == 0 && aligned(b.base, b.align);
+    const unsigned grid = (unsigned)std::min<int64_t>(blocks_for(n * (v4 ? C / 4 : C), 256), 1 << 20);
+    if (v4) launch(IntC<4>{}, grid);
+    else    launch(IntC<1>{}, grid);
+}
+
 // dst[r, :] = bf(src[r, :]) for the rows listed (null: rows 0 .. n), both [., C] contiguous; VEC = 4: 16-byte loads, 8-byte stores
 template <int VEC>
 __global__ __launch_bounds__(256) void k_round_rows(const float *__restrict__ src, const int32_t *__restrict__ rows, int64_t n, int64_t C,
@@ -280,17 +311,7 @@ __global__ __launch_bounds__(256) void k_round_rows(const float *__restrict__ sr
 
 void round_rows(const float *src, const int32_t *rows, int64_t n, int64_t C, uint16_t *dst, hipStream_t s) {
     if (n == 0) return;
-    const bool v4 = C % 4 == 0 && aligned(src, 16) && aligned(dst, 8);
-    const unsigned grid = (unsigned)std::min<int64_t>(blocks_for(n * (v4 ? C / 4 : C), 256), 1 << 20);
-    if (v4) hipLaunchKernelGGL(k_round_rows<4>, dim3(grid), dim3(256), 0, s, src, rows, n, C, dst);
-    else    hipLaunchKernelGGL(k_round_rows<1>, dim3(grid), dim3(256), 0, s, src, rows, n, C, dst);
-}
-
-// the structure and the long-row plan of a fused launch (its short rows need nothing else of bind_csr)
-void bind_fused(const Csr &m, SpmmArgs &p) {
-    p.rowptr = m.rowptr; p.colidx = m.colidx; p.n_rows = m.n_rows; p.n_nonempty = m.n_nonempty; p.row_order = m.row_order;
-    p.long_rows = m.long_rows; p.long_chunk_ptr = m.long_chunk_ptr; p.chunk_long = m.chunk_long; p.chunk_order = m.chunk_order;
-    p.n_long = m.n_long; p.n_chunks = m.n_chunks; p.long_row = m.long_row; p.long_chunk = m.long_chunk;
+    launch_row_pass(n, C, {{src, 16, C}, {dst, 8, C}}, [&](auto V, unsigned grid) { GNX_LAUNCH(k_round_rows<V()>, grid, src, rows, n, C, dst); });
 }
 
 // out[r, :] = drop(X[r, :]) for the rows listed (null: rows 0 .. n), r the row id the mask is keyed by; out may be X (each lane reads the
@@ -307,6 +328,13 @@ __global__ __launch_bounds__(256) void k_feature_dropout(const float *X, int64_t
         drop_values<VEC>(fd, stream, r, c, x);
         vstore<VEC>(out + r * ldo + c, x);
     }
+}
+
+void launch_feature_dropout(const float *X, int64_t ldx, const int32_t *rows, int64_t n, int64_t C, const DropFuse &fd, float *out, int64_t ldo,
+                            hipStream_t s) {
+    if (n == 0 || C == 0) return;
+    launch_row_pass(n, C, {{X, 16, ldx}, {out, 16, ldo}},
+                    [&](auto V, unsigned grid) { GNX_LAUNCH(k_feature_dropout<V()>, grid, X, ldx, rows, n, C, fd, out, ldo); });
 }
 
 // The backward's gate in one pass: G = kept ? g * scale : +0, and with RELU also +0 where y <= 0 (y = the DROPPED forward output, so
@@ -367,6 +395,7 @@ __global__ __launch_bounds__(256) void k_feature_dropout_back_bf16(const float *
 // the mask of one call: keep iff hash >= int(p * 2^24) (oracle/gnntf_oracle.py:dropout_threshold, over the caller's double), kept values
 // times the f32 scale of the edge dropout, 1.0f / (1.0f - (float)p); the handle lends its dropout counter
 int make_feat_drop(const char *fn, const gnx_graph *g, double p, uint64_t seed, uint64_t stream_id, DropFuse &fd) {
+    GNX_CHECK_ARG(g != nullptr, "%s: NULL handle", fn);
     GNX_CHECK_ARG(p >= 0.0 && p < 1.0, "%s: dropout rate %g outside [0, 1)", fn, p);
     fd.seed = seed; fd.stream = stream_id; fd.offset = g->stream_offset;
     fd.thr = (uint32_t)(p * 16777216.0);
@@ -374,80 +403,230 @@ int make_feat_drop(const char *fn, const gnx_graph *g, double p, uint64_t seed, 
     return GNX_OK;
 }
 
-void launch_feature_dropout(const float *X, int64_t ldx, const int32_t *rows, int64_t n, int64_t C, const DropFuse &fd, float *out, int64_t ldo,
-                            hipStream_t s) {
-    if (n == 0 || C == 0) return;
-    const bool v4 = C % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0 && aligned(X, 16) && aligned(out, 16);
-    const unsigned grid = (unsigned)std::min<int64_t>(blocks_for(n * (v4 ? C / 4 : C), 256), 1 << 20);
-    if (v4) hipLaunchKernelGGL(k_feature_dropout<4>, dim3(grid), dim3(256), 0, s, X, ldx, rows, n, C, fd, out, ldo);
-    else    hipLaunchKernelGGL(k_feature_dropout<1>, dim3(grid), dim3(256), 0, s, X, ldx, rows, n, C, fd, out, ldo);
-}
-
-// gnx_gcnii_step (fd == null) and gnx_gcnii_step_drop: one host path
-int gcnii_step(const char *fn, gnx_graph *g, const float *d_vals, const float *d_H, const float *d_H0, float a, int64_t C, const float *d_M,
-               int64_t ldm, int act, const DropFuse *fd, float *d_out, float *d_mixed, void *stream) {
-    int rc = check_common(fn, g, d_H, C, C, d_H0, C, d_out, C);
-    if (rc != GNX_OK) return rc;
+// gnx_feature_dropout_back (F32Rows: no Gb) and gnx_feature_dropout_back_bf16: one host path
+template <typename R>
+int feature_dropout_back(const char *fn, gnx_graph *g, const float *d_g, int64_t ldg, const typename R::Elem *d_y, int64_t ldy, int64_t n_rows,
+                         int64_t C, double dropout_p, uint64_t seed, uint64_t stream_id, int act, float *d_G, int64_t ldG, uint16_t *d_Gb,
+                         int64_t ldGb, void *stream) {
+    constexpr bool BF = R::BF16 != 0;
+    GNX_CHECK_ARG(g != nullptr, "%s: NULL handle", fn);
     GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU, "%s: invalid activation %d", fn, act);
-    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "%s: needs a square graph", fn);
-    GNX_CHECK_ARG(d_H0 != nullptr && d_M != nullptr && ldm >= C, "%s: NULL H0 / M or ldm < C", fn);
+    GNX_CHECK_ARG(n_rows >= 0 && C >= 1, "%s: negative row count or C < 1", fn);
+    GNX_CHECK_ARG(d_g != nullptr && d_G != nullptr && ldg >= C && ldG >= C && (!BF || (d_Gb != nullptr && ldGb >= C)),
+                  "%s: NULL g / G%s or a row stride below C", fn, BF ? " / Gb" : "");
+    GNX_CHECK_ARG(d_G != d_g || ldG == ldg, "%s: in place needs ldG == ldg", fn);
+    GNX_CHECK_ARG(!BF || ((const void *)d_Gb != (const void *)d_g && (const void *)d_Gb != (const void *)d_G), "%s: Gb must not alias g / G", fn);
+    const bool relu = act == GNX_ACT_RELU;
+    const void *written = BF ? (const void *)d_Gb : (const void *)d_G;      // the result in y's format
+    GNX_CHECK_ARG(!relu || (d_y != nullptr && ldy >= C && (const void *)d_y != written), "%s: relu needs y (not %s itself) with ldy >= C", fn,
+                  BF ? "Gb" : "G");
+    DropFuse fd{};
+    int rc = make_feat_drop(fn, g, dropout_p, seed, stream_id, fd);
+    if (rc != GNX_OK) return rc;
+    if (n_rows == 0) return GNX_OK;
     hipStream_t s = (hipStream_t)stream;
-    const Csr &m = g->a;
-    const float beta = (float)(1.0 - (double)a);
-    GNX_CHECK_ARG(d_mixed == nullptr || (d_mixed != d_out && d_mixed != d_H && d_mixed != d_H0), "%s: d_mixed must be a buffer of its own", fn);
-    // C = 128 fits the kernel (135 KB of LDS: one block of eight waves per CU) and was measured: 19.2 ms against 11.8 ms for the two
-    // launches on the config-4 graph -- eight waves per CU cannot keep the gathers fed -- so it takes the two-launch form
-    const bool fusable = (C == 16 || C == 32 || C == 64) && aligned(d_H, 16) && aligned(d_H0, 16) && aligned(d_out, 16) && aligned(d_mixed, 16);
-    if (!fusable) {   // other widths: the fused SpMM+mix into d_mixed, then the transform on the matrix cores (then the mask over all rows, in place)
-        GNX_CHECK_ARG(d_mixed != nullptr, "%s: width %lld needs d_mixed [n, C] (the mixed rows go through memory)", fn, (long long)C);
-        rc = gnx_spmm(g, d_vals, nullptr, d_H, C, C, d_H0, C, beta, a, GNX_ACT_NONE, d_mixed, C, stream);
-        if (rc != GNX_OK) return rc;
-        g->last_kernel = fd ? "spmm+dense_mfma_drop" : "spmm+dense_mfma";
-        rc = dense_rows(d_mixed, C, m.n_rows, C, d_M, ldm, C, nullptr, act, nullptr, nullptr, d_out, C, s);
-        if (rc != GNX_OK || !fd) return rc;
-        launch_feature_dropout(d_out, C, nullptr, m.n_rows, C, *fd, d_out, C, s);
-        GNX_HIP(hipGetLastError());
-        return GNX_OK;
-    }
-    if (m.n_rows == 0) return GNX_OK;
-    SpmmArgs p{};
-    p.vals = d_vals ? d_vals : g->raw_vals;
-    set_operands<F32Rows>(p, d_H, C, d_H0, C, beta, a, act, d_out, 0, C, C);
-    bind_fused(m, p);
-    const unsigned grid = blocks_for(blocks_for(m.n_rows, 16), 8);
-    if (fd) {
-        p.fuse = *fd;
-        if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii<F32Rows, 4, 4, 8, true>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
-        else if (C == 32) hipLaunchKernelGGL((k_spmm_gcnii<F32Rows, 2, 4, 8, true>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
-        else              hipLaunchKernelGGL((k_spmm_gcnii<F32Rows, 1, 4, 8, true>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
-    } else {
-        if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii<F32Rows, 4, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
-        else if (C == 32) hipLaunchKernelGGL((k_spmm_gcnii<F32Rows, 2, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
-        else              hipLaunchKernelGGL((k_spmm_gcnii<F32Rows, 1, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_M, ldm, d_mixed);
-    }
-    g->last_kernel = fd ? "spmm_gcnii_mfma_drop" : "spmm_gcnii_mfma";
-    if (m.n_long > 0) {   // hub rows: chunked partial sums -> mixed rows (into d_mixed when kept, else in place) -> transform of those rows alone
-        rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)C * sizeof(float), s);
-        if (rc != GNX_OK) return rc;
-        p.partial = g->partial;
-        p.act = GNX_ACT_NONE;
-        float *rows_at = d_mixed ? d_mixed : d_out;
-        p.out = rows_at;
-        launch_long_rows(p, s);
-        rc = dense_rows(rows_at, C, m.n_long, C, d_M, ldm, C, nullptr, act, m.long_rows, m.long_rows, d_out, C, s);
-        if (rc != GNX_OK) return rc;
-        if (fd) launch_feature_dropout(d_out, C, m.long_rows, m.n_long, C, *fd, d_out, C, s);      // ... -> the mask of those rows, in place
-    }
+    const RowsAt y_rows = relu ? RowsAt{d_y, 4 * sizeof(typename R::Elem), ldy} : RowsAt{nullptr, 1, 0};      // y is read with relu only
+    const RowsAt gb_rows = BF ? RowsAt{d_Gb, 8, ldGb} : RowsAt{nullptr, 1, 0};                                 // Gb exists for bf16 only
+    auto gate = [&](auto V, auto RELU, unsigned grid) {
+        if constexpr (BF) GNX_LAUNCH((k_feature_dropout_back_bf16<V(), RELU()>), grid, d_g, ldg, d_y, ldy, n_rows, C, fd, d_G, ldG, d_Gb, ldGb);
+        else GNX_LAUNCH((k_feature_dropout_back<V(), RELU()>), grid, d_g, ldg, d_y, ldy, n_rows, C, fd, d_G, ldG);
+    };
+    launch_row_pass(n_rows, C, {{d_g, 16, ldg}, {d_G, 16, ldG}, gb_rows, y_rows}, [&](auto V, unsigned grid) {
+        if (relu) gate(V, std::true_type{}, grid);
+        else      gate(V, std::false_type{}, grid);
+    });
     GNX_HIP(hipGetLastError());
     return GNX_OK;
 }
 
-// what the two launch entries refuse: they have no composed form, the callers keep f32 there
-int refuse_unfused(const char *fn, int64_t C, bool aligned_ok) {
-    if (C != 16 && C != 32 && C != 64) set_error("%s: width %lld is not supported (the fused launch takes C = 16, 32 or 64; keep f32 storage elsewhere)", fn, (long long)C);
-    else if (!aligned_ok) set_error("%s: misaligned buffer (the f32 buffers must be 16-byte aligned, the bf16 buffers 8-byte aligned)", fn);
-    else return GNX_OK;
+// the structure and the long-row plan of a fused launch (its short rows need nothing else of bind_csr)
+void bind_fused(const Csr &m, SpmmArgs &p) {
+    p.rowptr = m.rowptr; p.colidx = m.colidx; p.n_rows = m.n_rows; p.n_nonempty = m.n_nonempty; p.row_order = m.row_order;
+    p.long_rows = m.long_rows; p.long_chunk_ptr = m.long_chunk_ptr; p.chunk_long = m.chunk_long; p.chunk_order = m.chunk_order;
+    p.n_long = m.n_long; p.n_chunks = m.n_chunks; p.long_row = m.long_row; p.long_chunk = m.long_chunk;
+}
+
+// the chunked partial sums of the hub rows of a fused launch, mixed as p says, into f32 rows at `out` (p.partial set)
+template <typename R>
+void launch_hub_rows(typename R::Args &p, const typename R::Elem *X, float *out, hipStream_t s) {
+    if constexpr (R::BF16) launch_long_rows_bf16(p, X, out, s);
+    else { p.out = out; launch_long_rows(p, s); }
+}
+
+// the fused launch takes C = 16, 32 or 64 (C = 128 fits the kernel -- 135 KB of LDS: one block of eight waves per CU -- and was measured:
+// 19.2 ms against 11.8 ms for the two launches on the config-4 graph; eight waves per CU cannot keep the gathers fed)
+bool fused_width(int64_t C) { return C == 16 || C == 32 || C == 64; }
+
+// what the entries without a composed form answer to the other widths and alignments: the callers keep f32 there
+int refuse_unfused(const char *fn, int64_t C) {
+    if (!fused_width(C)) set_error("%s: width %lld is not supported (the fused launch takes C = 16, 32 or 64; keep f32 storage elsewhere)", fn, (long long)C);
+    else set_error("%s: misaligned buffer (the f32 buffers must be 16-byte aligned, the bf16 buffers 8-byte aligned)", fn);
     return GNX_ERR_UNSUPPORTED;
+}
+
+// ---- the forward's host path, once over the row storage R of H --------------------------------------------------------------------------
+struct ForwardForm {             // what differs between its entries
+    const DropFuse *fd;          // the mask of the finished rows (gnx_gcnii_step_drop, gnx_gcnii_step_train_bf16 at a rate above 0) or null
+    float *mixed;                // f32 [n, C] or null: where the mixed rows T are kept (training)
+    float *work;                 // f32 [n, C] or null: the bf16 entries' rows on their way through memory
+    int out_bf16;                // the result is stored as bf16 (the bf16 entries)
+    bool composes;               // the other widths / alignments run as two launches; false: they are refused (refuse_unfused)
+    const char *fused, *composed;   // what gnx_graph_last_kernel reports
+};
+
+template <typename R>
+int gcnii_forward(const char *fn, gnx_graph *g, const float *d_vals, const typename R::Elem *d_H, const float *d_H0, float a, int64_t C,
+                  const float *d_M, int64_t ldm, int act, typename R::Out *d_out, const ForwardForm &f, void *stream) {
+    int rc = check_common(fn, g, d_H, C, C, d_H0, C, d_out, C);
+    if (rc != GNX_OK) return rc;
+    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU, "%s: invalid activation %d", fn, act);
+    GNX_CHECK_ARG(f.out_bf16 == 0 || f.out_bf16 == 1, "%s: out_bf16 must be 0 or 1", fn);
+    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "%s: needs a square graph", fn);
+    GNX_CHECK_ARG(d_H0 != nullptr && d_M != nullptr && ldm >= C, "%s: NULL H0 / M or ldm < C", fn);
+    const void *out = d_out, *H = d_H;
+    GNX_CHECK_ARG(out != d_H0 && out != d_M, "%s: out must not alias H0 / M", fn);
+    GNX_CHECK_ARG(f.mixed == nullptr || (f.mixed != out && f.mixed != H && f.mixed != d_H0 && f.mixed != d_M && f.mixed != d_vals),
+                  "%s: d_mixed must be a buffer of its own", fn);
+    GNX_CHECK_ARG(f.work == nullptr || (f.work != out && f.work != H && f.work != d_H0 && f.work != d_M && f.work != d_vals && f.work != f.mixed),
+                  "%s: d_work must be a buffer of its own", fn);
+    const bool fusable = fused_width(C) && aligned(d_H, 4 * sizeof(typename R::Elem)) && aligned(d_H0, 16) && aligned(d_out, f.out_bf16 ? 8 : 16) &&
+                         aligned(f.mixed, 16) && aligned(f.work, 16);
+    if (!fusable && !f.composes) return refuse_unfused(fn, C);
+    const Csr &m = g->a;
+    // the rows that go through memory -- every row of the two launches, the hub rows of the fused one -- need a place to be
+    if constexpr (R::BF16)
+        GNX_CHECK_ARG(f.work != nullptr || (fusable && m.n_long == 0), "%s: needs d_work [n, C] f32 (%s)", fn,
+                      !fusable ? "this width / alignment runs the SpMM and the transform as two launches"
+                      : f.mixed ? "the graph has hub rows: they are transformed and masked in memory"
+                                : "the graph has hub rows: their mixed rows go through memory");
+    else
+        GNX_CHECK_ARG(fusable || f.mixed != nullptr, "%s: width %lld needs d_mixed [n, C] (the mixed rows go through memory)", fn, (long long)C);
+    hipStream_t s = (hipStream_t)stream;
+    const float beta = (float)(1.0 - (double)a);
+    typename R::Args p{};
+    p.vals = d_vals ? d_vals : g->raw_vals;
+    set_operands<R>(p, d_H, C, d_H0, C, beta, a, act, d_out, f.out_bf16, C, C);
+    if (f.fd) p.fuse = *f.fd;
+    // mixed rows at T (the n listed; null: rows 0 .. n) -> act(T . M) of those rows alone, into d_out, or into d_work where the result is
+    // bf16 -> their mask, in place -> the rows rounded into d_out.  (T may be d_work itself: every wave of the dense kernels reads whole
+    // rows of its own tile before it stores them, as long as the result is ONE column panel)
+    auto transform_rows = [&](float *T, const int32_t *rows, int64_t n) -> int {
+        float *to = f.out_bf16 ? f.work : static_cast<float *>(d_out);
+        const int err = dense_rows(T, C, n, C, d_M, ldm, C, nullptr, act, rows, rows, to, C, s);
+        if (err != GNX_OK) return err;
+        if (f.fd) launch_feature_dropout(to, C, rows, n, C, *f.fd, to, C, s);
+        if (f.out_bf16) round_rows(to, rows, n, C, (uint16_t *)d_out, s);
+        GNX_HIP(hipGetLastError());
+        return GNX_OK;
+    };
+    if (!fusable) {   // other widths: the fused SpMM + mix into f32 rows (d_mixed, else d_work), then the transform on the matrix cores
+        float *T = f.mixed ? f.mixed : f.work;
+        if constexpr (R::BF16) {
+            p.act = GNX_ACT_NONE;
+            rc = launch_spmm_bf16_f32_order(g, m, p, d_H, T, s);
+        } else {
+            rc = gnx_spmm(g, d_vals, nullptr, d_H, C, C, d_H0, C, beta, a, GNX_ACT_NONE, T, C, stream);
+        }
+        if (rc != GNX_OK) return rc;
+        g->last_kernel = f.composed;
+        if (f.out_bf16 && C > 256) {
+            set_error("%s: a bf16 result needs C <= 256 (wider: out_bf16 = 0, then gnx_cast_bf16)", fn);
+            return GNX_ERR_UNSUPPORTED;
+        }
+        return transform_rows(T, nullptr, m.n_rows);
+    }
+    if (m.n_rows == 0) return GNX_OK;
+    bind_fused(m, p);
+    if (m.n_long > 0) {   // (before the first launch: under capture a slab that would have to grow refuses the whole call)
+        rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)C * sizeof(float), s);
+        if (rc != GNX_OK) return rc;
+    }
+    with_tile_width(C, m.n_rows, [&](auto NT, dim3 grid) {
+        if (f.fd) hipLaunchKernelGGL((k_spmm_gcnii<R, NT(), 4, 8, true>), grid, dim3(512), 0, s, p, d_M, ldm, f.mixed);
+        else      hipLaunchKernelGGL((k_spmm_gcnii<R, NT(), 4, 8>), grid, dim3(512), 0, s, p, d_M, ldm, f.mixed);
+    });
+    g->last_kernel = f.fused;
+    if (m.n_long == 0) {
+        GNX_HIP(hipGetLastError());
+        return GNX_OK;
+    }
+    // hub rows: chunked partial sums -> mixed rows (into d_mixed when kept, else d_work, else in place) -> the transform of those rows alone
+    float *T = f.mixed ? f.mixed : f.work ? f.work : static_cast<float *>(d_out);
+    p.partial = g->partial;
+    p.act = GNX_ACT_NONE;
+    launch_hub_rows<R>(p, d_H, T, s);
+    return transform_rows(T, m.long_rows, m.n_long);
+}
+
+// ---- the backward's host path, once over the row storage R of the gathered gradient X (the f32 G itself, or its bf16 copy Gb) ------------
+template <typename R>
+int gcnii_backward(const char *fn, gnx_graph *g, const float *d_vals_t, const typename R::Elem *d_X, const float *d_G, float a, int64_t C,
+                   const float *d_Mt, int64_t ldmt, float *d_dH, const float *d_S_in, float s_alpha, float *d_S_out, float *d_work, void *stream) {
+    int rc = check_common(fn, g, d_X, C, C, d_S_in, C, d_dH, C);
+    if (rc != GNX_OK) return rc;
+    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "%s: needs a square graph", fn);
+    GNX_CHECK_ARG(d_Mt != nullptr && ldmt >= C, "%s: NULL Mt or ldmt < C", fn);
+    GNX_CHECK_ARG(d_S_in == nullptr || d_S_out != nullptr, "%s: S_in without S_out", fn);
+    if constexpr (R::BF16)
+        GNX_CHECK_ARG((d_G == nullptr) == (d_S_out == nullptr), "%s: d_G (the f32 gated gradient of the row's own product) goes with d_S_out: both or neither", fn);
+    const void *X = d_X;
+    GNX_CHECK_ARG(d_dH != d_S_in && d_dH != d_S_out && d_dH != d_Mt && d_dH != d_G, "%s: dH must not alias %sS_in / S_out / Mt", fn, R::BF16 ? "G / " : "");
+    GNX_CHECK_ARG(d_S_out == nullptr || (d_S_out != d_G && d_S_out != d_Mt && d_S_out != X), "%s: S_out must not alias G / %sMt", fn, R::BF16 ? "Gb / " : "");
+    GNX_CHECK_ARG(d_work == nullptr || (d_work != d_G && d_work != X && d_work != d_dH && d_work != d_S_in && d_work != d_S_out && d_work != d_Mt),
+                  "%s: d_work must be a buffer of its own", fn);
+    hipStream_t s = (hipStream_t)stream;
+    const float beta = (float)(1.0 - (double)a);
+    const bool fusable = fused_width(C) && aligned(d_X, 4 * sizeof(typename R::Elem)) && aligned(d_G, 16) && aligned(d_dH, 16) && aligned(d_S_in, 16) &&
+                         aligned(d_S_out, 16);
+    if constexpr (R::BF16) {
+        if (!fusable) return refuse_unfused(fn, C);
+    } else if (!fusable) {   // other widths / alignments, the composed order: gT = G . Mt into d_work, dH = (1-a) At gT, S = s_alpha S_in + a gT
+        const int64_t n = g->a.n_rows;
+        GNX_CHECK_ARG(d_work != nullptr, "%s: width %lld / this alignment needs d_work [n, C] (G . Mt goes through memory)", fn, (long long)C);
+        GNX_CHECK_ARG(d_S_out == nullptr || (aligned(d_work, 16) && aligned(d_S_in, 16) && aligned(d_S_out, 16)),
+                      "%s: S_in, S_out and d_work must be 16-byte aligned (gnx_linear_combination adds them)", fn);
+        rc = ensure_transpose(g, s);   // (before the first launch: under capture a part that would have to be built refuses the whole call)
+        if (rc != GNX_OK) return rc;
+        if (g->t.n_long > 0) {
+            rc = ensure_partial(g, (size_t)g->t.n_chunks * (size_t)C * sizeof(float), s);
+            if (rc != GNX_OK) return rc;
+        }
+        rc = gnx_dense(d_G, C, n, C, d_Mt, ldmt, C, nullptr, GNX_ACT_NONE, d_work, C, stream);
+        if (rc != GNX_OK) return rc;
+        rc = gnx_spmm_tv(g, d_vals_t ? d_vals_t : g->t_raw.get(), nullptr, d_work, C, C, nullptr, 0, beta, 0.f, GNX_ACT_NONE, d_dH, C, stream);
+        if (rc != GNX_OK) return rc;
+        g->last_kernel = "dense+spmm_back";
+        if (d_S_out == nullptr || n == 0) return GNX_OK;
+        const float *src[2] = {d_S_in, d_work};
+        const float coef[2] = {s_alpha, a};
+        return d_S_in ? gnx_linear_combination(2, src, coef, n * C, d_S_out, stream)
+                      : gnx_linear_combination(1, src + 1, coef + 1, n * C, d_S_out, stream);
+    }
+    rc = ensure_transpose(g, s);   // (the two before the first launch, as above)
+    if (rc != GNX_OK) return rc;
+    const Csr &m = g->t;
+    if (m.n_rows == 0) return GNX_OK;
+    if (m.n_long > 0) {
+        rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)C * sizeof(float), s);
+        if (rc != GNX_OK) return rc;
+    }
+    typename R::Args p{};
+    p.vals = d_vals_t ? d_vals_t : g->t_raw.get();
+    set_operands<R>(p, d_X, C, nullptr, 0, beta, a, GNX_ACT_NONE, d_dH, 0, C, C);
+    p.X = d_G; p.out = d_dH;      // the row's own f32 row and the f32 dH are SpmmArgs' own under either policy (k_spmm_gcnii_back)
+    bind_fused(m, p);
+    with_tile_width(C, m.n_rows, [&](auto NT, dim3 grid) {
+        hipLaunchKernelGGL((k_spmm_gcnii_back<R, NT(), 4, 8>), grid, dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
+    });
+    g->last_kernel = R::BF16 ? "spmm_gcnii_back_mfma_bf16" : "spmm_gcnii_back_mfma";
+    if (m.n_long > 0) {   // hub rows of the transposed structure: chunked partial sums -> (1-a) Z into dH -> those rows alone times Mt, in place
+        p.partial = g->partial;
+        launch_hub_rows<R>(p, d_X, d_dH, s);
+        rc = dense_rows(d_dH, C, m.n_long, C, d_Mt, ldmt, C, nullptr, GNX_ACT_NONE, m.long_rows, m.long_rows, d_dH, C, s);
+        if (rc != GNX_OK) return rc;
+    }
+    GNX_HIP(hipGetLastError());
+    return GNX_OK;
 }
 
 }  // namespace
@@ -456,19 +635,49 @@ extern "C" {
 
 int gnx_gcnii_step(gnx_graph_t g, const float *d_vals, const float *d_H, const float *d_H0, float a, int64_t C, const float *d_M,
                    int64_t ldm, int act, float *d_out, float *d_mixed, void *stream) {
-    return gcnii_step("gnx_gcnii_step", g, d_vals, d_H, d_H0, a, C, d_M, ldm, act, nullptr, d_out, d_mixed, stream);
+    const ForwardForm f{nullptr, d_mixed, nullptr, 0, true, "spmm_gcnii_mfma", "spmm+dense_mfma"};
+    return gcnii_forward<F32Rows>("gnx_gcnii_step", g, d_vals, d_H, d_H0, a, C, d_M, ldm, act, d_out, f, stream);
 }
 
 int gnx_gcnii_step_drop(gnx_graph_t g, const float *d_vals, const float *d_H, const float *d_H0, float a, int64_t C, const float *d_M,
                         int64_t ldm, int act, double dropout_p, uint64_t seed, uint64_t stream_id, float *d_out, float *d_mixed,
                         void *stream) {
-    GNX_CHECK_ARG(g != nullptr, "gnx_gcnii_step_drop: NULL handle");
     DropFuse fd{};
     int rc = make_feat_drop("gnx_gcnii_step_drop", g, dropout_p, seed, stream_id, fd);
     if (rc != GNX_OK) return rc;
-    // p == 0 hashes nothing: the plain path
-    return gcnii_step("gnx_gcnii_step_drop", g, d_vals, d_H, d_H0, a, C, d_M, ldm, act, dropout_p == 0.0 ? nullptr : &fd, d_out,
-                      d_mixed, stream);
+    const bool drop = dropout_p != 0.0;      // p == 0 hashes nothing: the plain path
+    const ForwardForm f{drop ? &fd : nullptr, d_mixed, nullptr, 0, true, drop ? "spmm_gcnii_mfma_drop" : "spmm_gcnii_mfma",
+                        drop ? "spmm+dense_mfma_drop" : "spmm+dense_mfma"};
+    return gcnii_forward<F32Rows>("gnx_gcnii_step_drop", g, d_vals, d_H, d_H0, a, C, d_M, ldm, act, d_out, f, stream);
+}
+
+int gnx_gcnii_step_bf16(gnx_graph_t g, const float *d_vals, const uint16_t *d_H, const float *d_H0, float a, int64_t C, const float *d_M,
+                        int64_t ldm, int act, void *d_out, int out_bf16, float *d_work, void *stream) {
+    const ForwardForm f{nullptr, nullptr, d_work, out_bf16, true, "spmm_gcnii_mfma_bf16", "spmm+dense_mfma_bf16"};
+    return gcnii_forward<Bf16Rows>("gnx_gcnii_step_bf16", g, d_vals, d_H, d_H0, a, C, d_M, ldm, act, d_out, f, stream);
+}
+
+// (training: T is kept, so d_mixed is not optional; no composed form -- the callers keep f32 at the other widths)
+int gnx_gcnii_step_train_bf16(gnx_graph_t g, const float *d_vals, const uint16_t *d_H, const float *d_H0, float a, int64_t C, const float *d_M,
+                              int64_t ldm, int act, double dropout_p, uint64_t seed, uint64_t stream_id, void *d_out, int out_bf16,
+                              float *d_mixed, float *d_work, void *stream) {
+    const char *fn = "gnx_gcnii_step_train_bf16";
+    DropFuse fd{};
+    int rc = make_feat_drop(fn, g, dropout_p, seed, stream_id, fd);
+    if (rc != GNX_OK) return rc;
+    GNX_CHECK_ARG(d_mixed != nullptr, "%s: needs d_mixed [n, C] f32 (the mixed rows T are kept for the weight gradient)", fn);
+    const ForwardForm f{dropout_p != 0.0 ? &fd : nullptr, d_mixed, d_work, out_bf16, false, "spmm_gcnii_mfma_train_bf16", nullptr};
+    return gcnii_forward<Bf16Rows>(fn, g, d_vals, d_H, d_H0, a, C, d_M, ldm, act, d_out, f, stream);
+}
+
+int gnx_gcnii_step_back(gnx_graph_t g, const float *d_vals_t, const float *d_G, float a, int64_t C, const float *d_Mt, int64_t ldmt,
+                        float *d_dH, const float *d_S_in, float s_alpha, float *d_S_out, float *d_work, void *stream) {
+    return gcnii_backward<F32Rows>("gnx_gcnii_step_back", g, d_vals_t, d_G, d_G, a, C, d_Mt, ldmt, d_dH, d_S_in, s_alpha, d_S_out, d_work, stream);
+}
+
+int gnx_gcnii_step_back_bf16(gnx_graph_t g, const float *d_vals_t, const uint16_t *d_Gb, const float *d_G, float a, int64_t C, const float *d_Mt,
+                             int64_t ldmt, float *d_dH, const float *d_S_in, float s_alpha, float *d_S_out, float *d_work, void *stream) {
+    return gcnii_backward<Bf16Rows>("gnx_gcnii_step_back_bf16", g, d_vals_t, d_Gb, d_G, a, C, d_Mt, ldmt, d_dH, d_S_in, s_alpha, d_S_out, d_work, stream);
 }
 
 int gnx_feature_dropout(gnx_graph_t g, const float *d_X, int64_t ldx, int64_t n_rows, int64_t C, const int32_t *d_rows, double dropout_p,
@@ -488,301 +697,15 @@ int gnx_feature_dropout(gnx_graph_t g, const float *d_X, int64_t ldx, int64_t n_
 
 int gnx_feature_dropout_back(gnx_graph_t g, const float *d_g, int64_t ldg, const float *d_y, int64_t ldy, int64_t n_rows, int64_t C,
                              double dropout_p, uint64_t seed, uint64_t stream_id, int act, float *d_G, int64_t ldG, void *stream) {
-    GNX_CHECK_ARG(g != nullptr, "gnx_feature_dropout_back: NULL handle");
-    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU, "gnx_feature_dropout_back: invalid activation %d", act);
-    GNX_CHECK_ARG(n_rows >= 0 && C >= 1, "gnx_feature_dropout_back: negative row count or C < 1");
-    GNX_CHECK_ARG(d_g != nullptr && d_G != nullptr && ldg >= C && ldG >= C, "gnx_feature_dropout_back: NULL g / G or a row stride below C");
-    GNX_CHECK_ARG(d_G != d_g || ldG == ldg, "gnx_feature_dropout_back: in place needs ldG == ldg");
-    const bool relu = act == GNX_ACT_RELU;
-    GNX_CHECK_ARG(!relu || (d_y != nullptr && ldy >= C && d_y != d_G), "gnx_feature_dropout_back: relu needs y (not G itself) with ldy >= C");
-    DropFuse fd{};
-    int rc = make_feat_drop("gnx_feature_dropout_back", g, dropout_p, seed, stream_id, fd);
-    if (rc != GNX_OK) return rc;
-    if (n_rows == 0) return GNX_OK;
-    hipStream_t s = (hipStream_t)stream;
-    const bool v4 = C % 4 == 0 && ldg % 4 == 0 && ldG % 4 == 0 && aligned(d_g, 16) && aligned(d_G, 16) && (!relu || (ldy % 4 == 0 && aligned(d_y, 16)));
-    const unsigned grid = (unsigned)std::min<int64_t>(blocks_for(n_rows * (v4 ? C / 4 : C), 256), 1 << 20);
-    if (v4 && relu)  hipLaunchKernelGGL((k_feature_dropout_back<4, true>), dim3(grid), dim3(256), 0, s, d_g, ldg, d_y, ldy, n_rows, C, fd, d_G, ldG);
-    else if (v4)     hipLaunchKernelGGL((k_feature_dropout_back<4, false>), dim3(grid), dim3(256), 0, s, d_g, ldg, d_y, ldy, n_rows, C, fd, d_G, ldG);
-    else if (relu)   hipLaunchKernelGGL((k_feature_dropout_back<1, true>), dim3(grid), dim3(256), 0, s, d_g, ldg, d_y, ldy, n_rows, C, fd, d_G, ldG);
-    else             hipLaunchKernelGGL((k_feature_dropout_back<1, false>), dim3(grid), dim3(256), 0, s, d_g, ldg, d_y, ldy, n_rows, C, fd, d_G, ldG);
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
-}
-
-int gnx_gcnii_step_back(gnx_graph_t g, const float *d_vals_t, const float *d_G, float a, int64_t C, const float *d_Mt, int64_t ldmt,
-                        float *d_dH, const float *d_S_in, float s_alpha, float *d_S_out, float *d_work, void *stream) {
-    int rc = check_common("gnx_gcnii_step_back", g, d_G, C, C, d_S_in, C, d_dH, C);
-    if (rc != GNX_OK) return rc;
-    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "gnx_gcnii_step_back: needs a square graph");
-    GNX_CHECK_ARG(d_Mt != nullptr && ldmt >= C, "gnx_gcnii_step_back: NULL Mt or ldmt < C");
-    GNX_CHECK_ARG(d_S_in == nullptr || d_S_out != nullptr, "gnx_gcnii_step_back: S_in without S_out");
-    GNX_CHECK_ARG(d_dH != d_S_in && d_dH != d_S_out && d_dH != d_Mt, "gnx_gcnii_step_back: dH must not alias S_in / S_out / Mt");
-    GNX_CHECK_ARG(d_S_out == nullptr || (d_S_out != d_G && d_S_out != d_Mt), "gnx_gcnii_step_back: S_out must not alias G / Mt");
-    GNX_CHECK_ARG(d_work == nullptr || (d_work != d_G && d_work != d_dH && d_work != d_S_in && d_work != d_S_out && d_work != d_Mt),
-                  "gnx_gcnii_step_back: d_work must be a buffer of its own");
-    hipStream_t s = (hipStream_t)stream;
-    const float beta = (float)(1.0 - (double)a);
-    const int64_t n = g->a.n_rows;
-    // (C = 128 stays with the two launches for the reason the forward gives: one block of eight waves per CU cannot keep the gathers fed)
-    const bool fusable = (C == 16 || C == 32 || C == 64) && aligned(d_G, 16) && aligned(d_dH, 16) && aligned(d_S_in, 16) && aligned(d_S_out, 16);
-    if (!fusable) {   // other widths / alignments, today's order: gT = G . Mt into d_work, dH = (1-a) At gT, S = s_alpha S_in + a gT
-        GNX_CHECK_ARG(d_work != nullptr, "gnx_gcnii_step_back: width %lld / this alignment needs d_work [n, C] (G . Mt goes through memory)",
-                      (long long)C);
-        GNX_CHECK_ARG(d_S_out == nullptr || (aligned(d_work, 16) && aligned(d_S_in, 16) && aligned(d_S_out, 16)),
-                      "gnx_gcnii_step_back: S_in, S_out and d_work must be 16-byte aligned (gnx_linear_combination adds them)");
-        rc = ensure_transpose(g, s);   // (before the first launch: under capture a part that would have to be built refuses the whole call)
-        if (rc != GNX_OK) return rc;
-        if (g->t.n_long > 0) {
-            rc = ensure_partial(g, (size_t)g->t.n_chunks * (size_t)C * sizeof(float), s);
-            if (rc != GNX_OK) return rc;
-        }
-        rc = gnx_dense(d_G, C, n, C, d_Mt, ldmt, C, nullptr, GNX_ACT_NONE, d_work, C, stream);
-        if (rc != GNX_OK) return rc;
-        rc = gnx_spmm_tv(g, d_vals_t ? d_vals_t : g->t_raw.get(), nullptr, d_work, C, C, nullptr, 0, beta, 0.f, GNX_ACT_NONE, d_dH, C, stream);
-        if (rc != GNX_OK) return rc;
-        g->last_kernel = "dense+spmm_back";
-        if (d_S_out == nullptr || n == 0) return GNX_OK;
-        const float *src[2] = {d_S_in, d_work};
-        const float coef[2] = {s_alpha, a};
-        return d_S_in ? gnx_linear_combination(2, src, coef, n * C, d_S_out, stream)
-                      : gnx_linear_combination(1, src + 1, coef + 1, n * C, d_S_out, stream);
-    }
-    rc = ensure_transpose(g, s);
-    if (rc != GNX_OK) return rc;
-    const Csr &m = g->t;
-    if (m.n_rows == 0) return GNX_OK;
-    if (m.n_long > 0) {   // (before the first launch, as above)
-        rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)C * sizeof(float), s);
-        if (rc != GNX_OK) return rc;
-    }
-    SpmmArgs p{};
-    p.vals = d_vals_t ? d_vals_t : g->t_raw.get();
-    p.X = d_G; p.ldx = C; p.beta = beta; p.alpha = a; p.act = GNX_ACT_NONE; p.out = d_dH; p.ldo = C; p.C = (int)C;
-    bind_fused(m, p);
-    const unsigned grid = blocks_for(blocks_for(m.n_rows, 16), 8);
-    if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii_back<F32Rows, 4, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
-    else if (C == 32) hipLaunchKernelGGL((k_spmm_gcnii_back<F32Rows, 2, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
-    else              hipLaunchKernelGGL((k_spmm_gcnii_back<F32Rows, 1, 4, 8>), dim3(grid), dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
-    g->last_kernel = "spmm_gcnii_back_mfma";
-    if (m.n_long > 0) {   // hub rows of the transposed structure: chunked partial sums -> (1-a) Z into dH -> those rows alone times Mt, in place
-        p.partial = g->partial;
-        launch_long_rows(p, s);
-        rc = dense_rows(d_dH, C, m.n_long, C, d_Mt, ldmt, C, nullptr, GNX_ACT_NONE, m.long_rows, m.long_rows, d_dH, C, s);
-        if (rc != GNX_OK) return rc;
-    }
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
-}
-
-int gnx_gcnii_step_bf16(gnx_graph_t g, const float *d_vals, const uint16_t *d_H, const float *d_H0, float a, int64_t C, const float *d_M,
-                        int64_t ldm, int act, void *d_out, int out_bf16, float *d_work, void *stream) {
-    int rc = check_common("gnx_gcnii_step_bf16", g, d_H, C, C, d_H0, C, d_out, C);
-    if (rc != GNX_OK) return rc;
-    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU, "gnx_gcnii_step_bf16: invalid activation %d", act);
-    GNX_CHECK_ARG(out_bf16 == 0 || out_bf16 == 1, "gnx_gcnii_step_bf16: out_bf16 must be 0 or 1");
-    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "gnx_gcnii_step_bf16: needs a square graph");
-    GNX_CHECK_ARG(d_H0 != nullptr && d_M != nullptr && ldm >= C, "gnx_gcnii_step_bf16: NULL H0 / M or ldm < C");
-    GNX_CHECK_ARG((const void *)d_out != (const void *)d_H0 && (const void *)d_out != (const void *)d_M, "gnx_gcnii_step_bf16: out must not alias H0 / M");
-    GNX_CHECK_ARG(d_work == nullptr || ((const void *)d_work != (const void *)d_out && (const void *)d_work != (const void *)d_H && d_work != d_H0 &&
-                                        d_work != d_M && d_work != d_vals),
-                  "gnx_gcnii_step_bf16: d_work must be a buffer of its own");
-    hipStream_t s = (hipStream_t)stream;
-    const Csr &m = g->a;
-    const float beta = (float)(1.0 - (double)a);
-    const bool fusable = (C == 16 || C == 32 || C == 64) && aligned(d_H, 8) && aligned(d_H0, 16) && aligned(d_out, out_bf16 ? 8 : 16) &&
-                         aligned(d_work, 16);
-    GNX_CHECK_ARG(d_work != nullptr || (fusable && m.n_long == 0),
-                  "gnx_gcnii_step_bf16: needs d_work [n, C] f32 (%s)", fusable ? "the graph has hub rows: their mixed rows go through memory"
-                                                                               : "this width / alignment runs the SpMM and the transform as two launches");
-    SpmmArgs p{};
-    p.vals = d_vals ? d_vals : g->raw_vals;
-    p.ldx = C; p.H0 = d_H0; p.ldh0 = C; p.beta = beta; p.alpha = a; p.ldo = C; p.C = (int)C;
-    if (!fusable) {   // other widths: the SpMM + mix over bf16 rows into d_work (f32), the transform on the matrix cores, the rounding last
-        p.act = GNX_ACT_NONE;
-        rc = launch_spmm_bf16_f32_order(g, m, p, d_H, d_work, s);
-        if (rc != GNX_OK) return rc;
-        g->last_kernel = "spmm+dense_mfma_bf16";
-        if (!out_bf16) return dense_rows(d_work, C, m.n_rows, C, d_M, ldm, C, nullptr, act, nullptr, nullptr, (float *)d_out, C, s);
-        // a bf16 result: the transform runs in place (every wave of the dense kernels reads whole rows of its own tile before it stores
-        // them -- what the hub rows of gnx_gcnii_step rely on -- as long as the result is ONE column panel), then the rows are rounded
-        if (C > 256) {
-            set_error("gnx_gcnii_step_bf16: a bf16 result needs C <= 256 (wider: out_bf16 = 0, then gnx_cast_bf16)");
-            return GNX_ERR_UNSUPPORTED;
-        }
-        rc = dense_rows(d_work, C, m.n_rows, C, d_M, ldm, C, nullptr, act, nullptr, nullptr, d_work, C, s);
-        if (rc != GNX_OK) return rc;
-        round_rows(d_work, nullptr, m.n_rows, C, (uint16_t *)d_out, s);
-        GNX_HIP(hipGetLastError());
-        return GNX_OK;
-    }
-    if (m.n_rows == 0) return GNX_OK;
-    bind_fused(m, p);
-    if (m.n_long > 0) {   // (before the first launch: under capture a slab that would have to grow refuses the whole call)
-        rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)C * sizeof(float), s);
-        if (rc != GNX_OK) return rc;
-    }
-    BfArgs q{};
-    static_cast<SpmmArgs &>(q) = p;
-    q.act = act; q.Xb = d_H; q.outv = d_out; q.out_bf16 = out_bf16;
-    const unsigned grid = blocks_for(blocks_for(m.n_rows, 16), 8);
-    if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii<Bf16Rows, 4, 4, 8>), dim3(grid), dim3(512), 0, s, q, d_M, ldm, (float *)nullptr);
-    else if (C == 32) hipLaunchKernelGGL((k_spmm_gcnii<Bf16Rows, 2, 4, 8>), dim3(grid), dim3(512), 0, s, q, d_M, ldm, (float *)nullptr);
-    else              hipLaunchKernelGGL((k_spmm_gcnii<Bf16Rows, 1, 4, 8>), dim3(grid), dim3(512), 0, s, q, d_M, ldm, (float *)nullptr);
-    g->last_kernel = "spmm_gcnii_mfma_bf16";
-    if (m.n_long > 0) {   // hub rows: chunked partial sums over the bf16 rows -> f32 mixed rows in d_work -> transform of those rows alone
-        p.partial = g->partial;
-        p.act = GNX_ACT_NONE;
-        launch_long_rows_bf16(p, d_H, d_work, s);
-        float *rows_to = out_bf16 ? d_work : (float *)d_out;      // (bf16: transformed in place, then rounded into d_out)
-        rc = dense_rows(d_work, C, m.n_long, C, d_M, ldm, C, nullptr, act, m.long_rows, m.long_rows, rows_to, C, s);
-        if (rc != GNX_OK) return rc;
-        if (out_bf16) round_rows(d_work, m.long_rows, m.n_long, C, (uint16_t *)d_out, s);
-    }
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
-}
-
-
-// ---- bf16 row storage for GCNII training (gnx.h) ------------------------------------------------------------------------------------
-int gnx_gcnii_step_train_bf16(gnx_graph_t g, const float *d_vals, const uint16_t *d_H, const float *d_H0, float a, int64_t C, const float *d_M,
-                              int64_t ldm, int act, double dropout_p, uint64_t seed, uint64_t stream_id, void *d_out, int out_bf16,
-                              float *d_mixed, float *d_work, void *stream) {
-    const char *fn = "gnx_gcnii_step_train_bf16";
-    int rc = check_common(fn, g, d_H, C, C, d_H0, C, d_out, C);
-    if (rc != GNX_OK) return rc;
-    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU, "%s: invalid activation %d", fn, act);
-    GNX_CHECK_ARG(out_bf16 == 0 || out_bf16 == 1, "%s: out_bf16 must be 0 or 1", fn);
-    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "%s: needs a square graph", fn);
-    GNX_CHECK_ARG(d_H0 != nullptr && d_M != nullptr && ldm >= C, "%s: NULL H0 / M or ldm < C", fn);
-    GNX_CHECK_ARG(d_mixed != nullptr, "%s: needs d_mixed [n, C] f32 (the mixed rows T are kept for the weight gradient)", fn);
-    GNX_CHECK_ARG((const void *)d_out != (const void *)d_H0 && (const void *)d_out != (const void *)d_M, "%s: out must not alias H0 / M", fn);
-    GNX_CHECK_ARG((const void *)d_mixed != (const void *)d_out && (const void *)d_mixed != (const void *)d_H && d_mixed != d_H0 && d_mixed != d_M &&
-                  d_mixed != d_vals, "%s: d_mixed must be a buffer of its own", fn);
-    GNX_CHECK_ARG(d_work == nullptr || ((const void *)d_work != (const void *)d_out && (const void *)d_work != (const void *)d_H && d_work != d_H0 &&
-                                        d_work != d_M && d_work != d_vals && d_work != d_mixed), "%s: d_work must be a buffer of its own", fn);
-    DropFuse fd{};
-    rc = make_feat_drop(fn, g, dropout_p, seed, stream_id, fd);
-    if (rc != GNX_OK) return rc;
-    rc = refuse_unfused(fn, C, aligned(d_H, 8) && aligned(d_H0, 16) && aligned(d_out, out_bf16 ? 8 : 16) && aligned(d_mixed, 16) && aligned(d_work, 16));
-    if (rc != GNX_OK) return rc;
-    const Csr &m = g->a;
-    GNX_CHECK_ARG(d_work != nullptr || m.n_long == 0, "%s: needs d_work [n, C] f32 (the graph has hub rows: they are transformed and masked in memory)", fn);
-    if (m.n_rows == 0) return GNX_OK;
-    hipStream_t s = (hipStream_t)stream;
-    const bool drop = dropout_p != 0.0;      // p == 0 hashes nothing: the instantiation without the mask
-    SpmmArgs p{};
-    p.vals = d_vals ? d_vals : g->raw_vals;
-    p.ldx = C; p.H0 = d_H0; p.ldh0 = C; p.beta = (float)(1.0 - (double)a); p.alpha = a; p.ldo = C; p.C = (int)C;
-    bind_fused(m, p);
-    if (m.n_long > 0) {   // (before the first launch: under capture a slab that would have to grow refuses the whole call)
-        rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)C * sizeof(float), s);
-        if (rc != GNX_OK) return rc;
-    }
-    BfArgs q{};
-    static_cast<SpmmArgs &>(q) = p;
-    q.act = act; q.Xb = d_H; q.outv = d_out; q.out_bf16 = out_bf16;
-    if (drop) q.fuse = fd;
-    const unsigned grid = blocks_for(blocks_for(m.n_rows, 16), 8);
-    if (drop) {
-        if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii<Bf16Rows, 4, 4, 8, true>), dim3(grid), dim3(512), 0, s, q, d_M, ldm, d_mixed);
-        else if (C == 32) hipLaunchKernelGGL((k_spmm_gcnii<Bf16Rows, 2, 4, 8, true>), dim3(grid), dim3(512), 0, s, q, d_M, ldm, d_mixed);
-        else              hipLaunchKernelGGL((k_spmm_gcnii<Bf16Rows, 1, 4, 8, true>), dim3(grid), dim3(512), 0, s, q, d_M, ldm, d_mixed);
-    } else {
-        if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii<Bf16Rows, 4, 4, 8>), dim3(grid), dim3(512), 0, s, q, d_M, ldm, d_mixed);
-        else if (C == 32) hipLaunchKernelGGL((k_spmm_gcnii<Bf16Rows, 2, 4, 8>), dim3(grid), dim3(512), 0, s, q, d_M, ldm, d_mixed);
-        else              hipLaunchKernelGGL((k_spmm_gcnii<Bf16Rows, 1, 4, 8>), dim3(grid), dim3(512), 0, s, q, d_M, ldm, d_mixed);
-    }
-    g->last_kernel = "spmm_gcnii_mfma_train_bf16";
-    if (m.n_long > 0) {   // hub rows: chunked partial sums over the bf16 rows -> f32 mixed rows in d_mixed -> transform of those rows alone ...
-        p.partial = g->partial;
-        p.act = GNX_ACT_NONE;
-        launch_long_rows_bf16(p, d_H, d_mixed, s);
-        float *rows_to = out_bf16 ? d_work : (float *)d_out;      // (T stays as it is: a bf16 result is transformed into d_work, then rounded)
-        rc = dense_rows(d_mixed, C, m.n_long, C, d_M, ldm, C, nullptr, act, m.long_rows, m.long_rows, rows_to, C, s);
-        if (rc != GNX_OK) return rc;
-        if (drop) launch_feature_dropout(rows_to, C, m.long_rows, m.n_long, C, fd, rows_to, C, s);      // ... -> their mask, in place
-        if (out_bf16) round_rows(d_work, m.long_rows, m.n_long, C, (uint16_t *)d_out, s);
-    }
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
+    return feature_dropout_back<F32Rows>("gnx_feature_dropout_back", g, d_g, ldg, d_y, ldy, n_rows, C, dropout_p, seed, stream_id, act, d_G, ldG,
+                                         nullptr, 0, stream);
 }
 
 int gnx_feature_dropout_back_bf16(gnx_graph_t g, const float *d_g, int64_t ldg, const uint16_t *d_y, int64_t ldy, int64_t n_rows, int64_t C,
                                   double dropout_p, uint64_t seed, uint64_t stream_id, int act, float *d_G, int64_t ldG, uint16_t *d_Gb,
                                   int64_t ldGb, void *stream) {
-    const char *fn = "gnx_feature_dropout_back_bf16";
-    GNX_CHECK_ARG(g != nullptr, "%s: NULL handle", fn);
-    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU, "%s: invalid activation %d", fn, act);
-    GNX_CHECK_ARG(n_rows >= 0 && C >= 1, "%s: negative row count or C < 1", fn);
-    GNX_CHECK_ARG(d_g != nullptr && d_G != nullptr && d_Gb != nullptr && ldg >= C && ldG >= C && ldGb >= C,
-                  "%s: NULL g / G / Gb or a row stride below C", fn);
-    GNX_CHECK_ARG(d_G != d_g || ldG == ldg, "%s: in place needs ldG == ldg", fn);
-    GNX_CHECK_ARG((const void *)d_Gb != (const void *)d_g && (const void *)d_Gb != (const void *)d_G, "%s: Gb must not alias g / G", fn);
-    const bool relu = act == GNX_ACT_RELU;
-    GNX_CHECK_ARG(!relu || (d_y != nullptr && ldy >= C && d_y != d_Gb), "%s: relu needs y (not Gb itself) with ldy >= C", fn);
-    DropFuse fd{};
-    int rc = make_feat_drop(fn, g, dropout_p, seed, stream_id, fd);
-    if (rc != GNX_OK) return rc;
-    if (n_rows == 0) return GNX_OK;
-    hipStream_t s = (hipStream_t)stream;
-    const bool v4 = C % 4 == 0 && ldg % 4 == 0 && ldG % 4 == 0 && ldGb % 4 == 0 && aligned(d_g, 16) && aligned(d_G, 16) && aligned(d_Gb, 8) &&
-                    (!relu || (ldy % 4 == 0 && aligned(d_y, 8)));
-    const unsigned grid = (unsigned)std::min<int64_t>(blocks_for(n_rows * (v4 ? C / 4 : C), 256), 1 << 20);
-#define GNX_GATE(VEC, RELU) hipLaunchKernelGGL((k_feature_dropout_back_bf16<VEC, RELU>), dim3(grid), dim3(256), 0, s, d_g, ldg, d_y, ldy, n_rows, C, fd, d_G, ldG, d_Gb, ldGb)
-    if (v4 && relu)  GNX_GATE(4, true);
-    else if (v4)     GNX_GATE(4, false);
-    else if (relu)   GNX_GATE(1, true);
-    else             GNX_GATE(1, false);
-#undef GNX_GATE
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
-}
-
-int gnx_gcnii_step_back_bf16(gnx_graph_t g, const float *d_vals_t, const uint16_t *d_Gb, const float *d_G, float a, int64_t C, const float *d_Mt,
-                             int64_t ldmt, float *d_dH, const float *d_S_in, float s_alpha, float *d_S_out, float *d_work, void *stream) {
-    const char *fn = "gnx_gcnii_step_back_bf16";
-    int rc = check_common(fn, g, d_Gb, C, C, d_S_in, C, d_dH, C);
-    if (rc != GNX_OK) return rc;
-    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "%s: needs a square graph", fn);
-    GNX_CHECK_ARG(d_Mt != nullptr && ldmt >= C, "%s: NULL Mt or ldmt < C", fn);
-    GNX_CHECK_ARG(d_S_in == nullptr || d_S_out != nullptr, "%s: S_in without S_out", fn);
-    GNX_CHECK_ARG((d_G == nullptr) == (d_S_out == nullptr), "%s: d_G (the f32 gated gradient of the row's own product) goes with d_S_out: both or neither", fn);
-    GNX_CHECK_ARG(d_dH != d_S_in && d_dH != d_S_out && d_dH != d_Mt && d_dH != d_G, "%s: dH must not alias G / S_in / S_out / Mt", fn);
-    GNX_CHECK_ARG(d_S_out == nullptr || (d_S_out != d_G && d_S_out != d_Mt && (const void *)d_S_out != (const void *)d_Gb), "%s: S_out must not alias G / Gb / Mt", fn);
-    GNX_CHECK_ARG(d_work == nullptr || (d_work != d_G && (const void *)d_work != (const void *)d_Gb && d_work != d_dH && d_work != d_S_in &&
-                                        d_work != d_S_out && d_work != d_Mt), "%s: d_work must be a buffer of its own", fn);
-    rc = refuse_unfused(fn, C, aligned(d_Gb, 8) && aligned(d_G, 16) && aligned(d_dH, 16) && aligned(d_S_in, 16) && aligned(d_S_out, 16));
-    if (rc != GNX_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    rc = ensure_transpose(g, s);
-    if (rc != GNX_OK) return rc;
-    const Csr &m = g->t;
-    if (m.n_rows == 0) return GNX_OK;
-    if (m.n_long > 0) {   // (before the first launch, as in gnx_gcnii_step_back)
-        rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)C * sizeof(float), s);
-        if (rc != GNX_OK) return rc;
-    }
-    SpmmArgs p{};
-    p.vals = d_vals_t ? d_vals_t : g->t_raw.get();
-    p.ldx = C; p.beta = (float)(1.0 - (double)a); p.alpha = a; p.act = GNX_ACT_NONE; p.out = d_dH; p.ldo = C; p.C = (int)C;
-    bind_fused(m, p);
-    BfArgs q{};
-    static_cast<SpmmArgs &>(q) = p;
-    q.Xb = d_Gb; q.X = d_G;       // the gathered rows / the row's own f32 row (k_spmm_gcnii_back); dH is the f32 p.out
-    const unsigned grid = blocks_for(blocks_for(m.n_rows, 16), 8);
-    if (C == 64)      hipLaunchKernelGGL((k_spmm_gcnii_back<Bf16Rows, 4, 4, 8>), dim3(grid), dim3(512), 0, s, q, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
-    else if (C == 32) hipLaunchKernelGGL((k_spmm_gcnii_back<Bf16Rows, 2, 4, 8>), dim3(grid), dim3(512), 0, s, q, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
-    else              hipLaunchKernelGGL((k_spmm_gcnii_back<Bf16Rows, 1, 4, 8>), dim3(grid), dim3(512), 0, s, q, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
-    g->last_kernel = "spmm_gcnii_back_mfma_bf16";
-    if (m.n_long > 0) {   // hub rows of the transposed structure: chunked partial sums over Gb -> (1-a) Z into dH -> those rows alone times Mt, in place
-        p.partial = g->partial;
-        launch_long_rows_bf16(p, d_Gb, d_dH, s);
-        rc = dense_rows(d_dH, C, m.n_long, C, d_Mt, ldmt, C, nullptr, GNX_ACT_NONE, m.long_rows, m.long_rows, d_dH, C, s);
-        if (rc != GNX_OK) return rc;
-    }
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
+    return feature_dropout_back<Bf16Rows>("gnx_feature_dropout_back_bf16", g, d_g, ldg, d_y, ldy, n_rows, C, dropout_p, seed, stream_id, act, d_G,
+                                          ldG, d_Gb, ldGb, stream);
 }
 
 }  // extern "C"

@@ -1084,20 +1084,30 @@ def _feature_dropout_launch(graph: DeviceGraph, X, p, seed, stream, rows=None, o
     return out
 
 
-def _feature_dropout_back(graph: DeviceGraph, g, y, p, seed, stream, relu):
-    """gnx_feature_dropout_back: G = kept ? g * s : 0, with ``relu`` also 0 where the dropped forward output ``y`` is <= 0."""
+def _gate_launch(graph: DeviceGraph, g, y, p, seed, stream, relu, bf16):
+    """The backward's gate, gnx_feature_dropout_back or (``bf16``: y is the stored bf16 output) gnx_feature_dropout_back_bf16: returns
+    (G, Gb) with G = kept ? g * s : 0 -- with ``relu`` also 0 where ``y`` <= 0 -- and Gb = bf(G), None without ``bf16``."""
     g = _as_f32_rows(g).contiguous()
     nat.require_cuda(g, y)
     _same_device(graph, g, y)
     G = torch.empty_like(g)
+    Gb = torch.empty(g.shape, dtype=torch.bfloat16, device=g.device) if bf16 else None
     if g.numel() == 0:
-        return G
+        return G, Gb
     y = y if relu else None
+    args = (graph.handle, nat.ptr(g), g.stride(0), nat.ptr(y), 0 if y is None else y.stride(0), g.shape[0], g.shape[1], float(p), seed, stream,
+            nat.ACT_RELU if relu else nat.ACT_NONE, nat.ptr(G), G.stride(0))
     with nat.on_device(g.device):
-        nat.check(nat.lib().gnx_feature_dropout_back(graph.handle, nat.ptr(g), g.stride(0), nat.ptr(y), 0 if y is None else y.stride(0),
-                                                     g.shape[0], g.shape[1], float(p), seed, stream,
-                                                     nat.ACT_RELU if relu else nat.ACT_NONE, nat.ptr(G), G.stride(0), nat.current_stream()))
-    return G
+        if bf16:
+            nat.check(nat.lib().gnx_feature_dropout_back_bf16(*args, nat.ptr(Gb), Gb.stride(0), nat.current_stream()))
+        else:
+            nat.check(nat.lib().gnx_feature_dropout_back(*args, nat.current_stream()))
+    return G, Gb
+
+
+def _feature_dropout_back(graph: DeviceGraph, g, y, p, seed, stream, relu):
+    """gnx_feature_dropout_back: G = kept ? g * s : 0, with ``relu`` also 0 where the dropped forward output ``y`` is <= 0."""
+    return _gate_launch(graph, g, y, p, seed, stream, relu, bf16=False)[0]
 
 
 class _FeatureDropout(torch.autograd.Function):
@@ -1125,27 +1135,41 @@ def feature_dropout(graph: DeviceGraph, X: torch.Tensor, p, seed, stream) -> tor
     return _FeatureDropout.apply(X, graph, *triple)
 
 
+def _gcnii_operands(what, adj, rows, f32=(), M=None, constant=None, device=True):
+    """The checks the GCNII launches share: a square adjacency without a diagonal -- with ``constant`` (what it is that needs one) no
+    DroppedAdjacency either -- with ``device`` device tensors on its device, ``rows`` (bf16 or f32, [n, C]), every ``f32`` matrix of
+    that shape (float32, contiguous; None passes) and ``M`` [C, C]; returns (graph, C).  (It sits on every launch of launch-bound
+    steps: nothing is looked at twice, and the f32 forward, which never compared devices, passes ``device=False``.)"""
+    if constant is not None and isinstance(adj, DroppedAdjacency):
+        raise Exception(f"{what}: {constant} needs a constant adjacency (a DroppedAdjacency makes its weights in the SpMM)")
+    if adj.diag is not None:
+        raise Exception(f"{what}: add_eye adjacencies are not supported by the fused step")
+    g, shape = adj.graph, rows.shape
+    if device:
+        nat.require_cuda(rows, M, *f32)
+        _same_device(g, rows, M, *f32)
+    if len(shape) != 2 or g.n_rows != g.n_cols or shape[0] != g.n_rows or (M is not None and M.shape != (shape[1], shape[1])):
+        raise Exception(f"{what}: shape mismatch")
+    for t in f32:
+        if t is not None and (t.shape != shape or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise Exception(f"{what}: shape mismatch")
+    return g, shape[1]
+
+
 def _gcnii_launch(adj: Adjacency, H, H0, a, M, relu, keep_mixed, dropout=None):
     """gnx_gcnii_step; returns (out, T or None).  T = the mixed rows (A.H)(1-a) + H0 a, written by the same launch when kept.
     ``dropout`` = (p, seed, stream): gnx_gcnii_step_drop, out = drop(act(T . M)); T stays undropped."""
-    g = adj.graph
     nat.require_cuda(H, H0, M)
     H, H0, M = _as_f32_rows(H).contiguous(), _as_f32_rows(H0).contiguous(), _as_f32_rows(M)
-    C = H.shape[1]
-    if g.n_rows != g.n_cols or H.shape[0] != g.n_rows or tuple(H0.shape) != tuple(H.shape) or tuple(M.shape) != (C, C):
-        raise Exception("gcnii_step: shape mismatch")
-    if adj.diag is not None:
-        raise Exception("gcnii_step: add_eye adjacencies are not supported by the fused step")
+    g, C = _gcnii_operands("gcnii_step", adj, H, (H0,), M, device=False)
     out = torch.empty_like(H)
     mixed = torch.empty_like(H) if keep_mixed or C not in (16, 32, 64) else None
+    layer = (g.handle, nat.ptr(adj.vals), nat.ptr(H), nat.ptr(H0), float(a), C, nat.ptr(M), M.stride(0), nat.ACT_RELU if relu else nat.ACT_NONE)
     with nat.on_device(H.device):
         if dropout is not None:
-            nat.check(nat.lib().gnx_gcnii_step_drop(g.handle, nat.ptr(adj.vals), nat.ptr(H), nat.ptr(H0), float(a), C, nat.ptr(M), M.stride(0),
-                                                    nat.ACT_RELU if relu else nat.ACT_NONE, *dropout, nat.ptr(out), nat.ptr(mixed),
-                                                    nat.current_stream()))
-            return out, mixed
-        nat.check(nat.lib().gnx_gcnii_step(g.handle, nat.ptr(adj.vals), nat.ptr(H), nat.ptr(H0), float(a), C, nat.ptr(M), M.stride(0),
-                                           nat.ACT_RELU if relu else nat.ACT_NONE, nat.ptr(out), nat.ptr(mixed), nat.current_stream()))
+            nat.check(nat.lib().gnx_gcnii_step_drop(*layer, *dropout, nat.ptr(out), nat.ptr(mixed), nat.current_stream()))
+        else:
+            nat.check(nat.lib().gnx_gcnii_step(*layer, nat.ptr(out), nat.ptr(mixed), nat.current_stream()))
     return out, mixed
 
 
@@ -1158,30 +1182,37 @@ def gcnii_step_back(adj: Adjacency, G: torch.Tensor, a: float, Mt: torch.Tensor,
     the layer's term of dH0 on top of a running sum ``S_in`` (None: no such term).  Returns (dH, S); ``want_S=False`` skips the
     second product and returns (dH, None).  G is gathered over the transposed structure itself: G . Mt never reaches memory.
     Other widths run gnx_dense, the transposed SpMM and one linear combination, through a work buffer allocated here."""
-    if isinstance(adj, DroppedAdjacency):
-        raise Exception("gcnii_step: the fused backward needs a constant adjacency (a DroppedAdjacency makes its weights in the SpMM)")
-    g = adj.graph
-    nat.require_cuda(G, Mt, S_in)
-    _same_device(g, G, Mt, S_in)
-    G, Mt = _as_f32_rows(G).contiguous(), _as_f32_rows(Mt)
-    C = G.shape[1]
-    if g.n_rows != g.n_cols or G.shape[0] != g.n_rows or tuple(Mt.shape) != (C, C):
-        raise Exception("gcnii_step: shape mismatch")
-    if adj.diag is not None:
-        raise Exception("gcnii_step: add_eye adjacencies are not supported by the fused step")
-    if S_in is not None:
-        if not want_S:
+    G, S_in = _as_f32_rows(G).contiguous(), None if S_in is None else _as_f32_rows(S_in).contiguous()
+    return _gcnii_back_launch(False, adj, G, None, a, Mt, S_in, s_alpha, want_S, False)
+
+
+def _gcnii_back_launch(bf16, adj, X, G, a, Mt, S_in, s_alpha, want_S, in_place):
+    """gnx_gcnii_step_back over the f32 rows ``X`` (the gated gradient itself; ``G`` is None), or with ``bf16``
+    gnx_gcnii_step_back_bf16 over its bf16 copy ``X`` beside the f32 ``G``: the checks, the buffers -- dH, S (``in_place``: S_in itself;
+    None without ``want_S``), and for f32 rows of the other widths the work buffer of the composed form -- and the call.
+    Returns (dH, S)."""
+    Mt = _as_f32_rows(Mt)
+    if bf16:
+        g, C = _gcnii_operands("gcnii_step_back_bf16", adj, X, (G, S_in), Mt, "bf16 training storage")
+        if X.dtype != torch.bfloat16 or not X.is_contiguous():
+            raise Exception("gcnii_step_back_bf16: needs contiguous bf16 rows [n, C] and Mt [C, C]")
+        if want_S == (G is None) or (S_in is not None and not want_S) or (in_place and S_in is None):
+            raise Exception("gcnii_step_back_bf16: the f32 G goes with want_S, S_in needs want_S, in_place needs S_in")
+    else:
+        g, C = _gcnii_operands("gcnii_step", adj, X, (S_in,), Mt, "the fused backward")
+        if S_in is not None and not want_S:
             raise Exception("gcnii_step: S_in without want_S")
-        S_in = _as_f32_rows(S_in).contiguous()
-        if tuple(S_in.shape) != tuple(G.shape):
-            raise Exception("gcnii_step: shape mismatch")
-    dH = torch.empty_like(G)
-    S = torch.empty_like(G) if want_S else None
-    work = torch.empty_like(G) if C not in (16, 32, 64) else None
+    dH = torch.empty_like(X, dtype=torch.float32) if bf16 else torch.empty_like(X)
+    S = (S_in if in_place else torch.empty_like(dH)) if want_S else None
+    work = torch.empty_like(dH) if not bf16 and C not in (16, 32, 64) else None
     values = adj.transposed_values()
-    with nat.on_device(G.device):
-        nat.check(nat.lib().gnx_gcnii_step_back(g.handle, nat.ptr(values), nat.ptr(G), float(a), C, nat.ptr(Mt), Mt.stride(0), nat.ptr(dH),
-                                                nat.ptr(S_in), float(s_alpha), nat.ptr(S), nat.ptr(work), nat.current_stream()))
+    with nat.on_device(X.device):
+        if bf16:
+            nat.check(nat.lib().gnx_gcnii_step_back_bf16(g.handle, nat.ptr(values), nat.ptr(X), nat.ptr(G), float(a), C, nat.ptr(Mt), Mt.stride(0),
+                                                         nat.ptr(dH), nat.ptr(S_in), float(s_alpha), nat.ptr(S), None, nat.current_stream()))
+        else:
+            nat.check(nat.lib().gnx_gcnii_step_back(g.handle, nat.ptr(values), nat.ptr(X), float(a), C, nat.ptr(Mt), Mt.stride(0), nat.ptr(dH),
+                                                    nat.ptr(S_in), float(s_alpha), nat.ptr(S), nat.ptr(work), nat.current_stream()))
     return dH, S
 
 
@@ -1278,18 +1309,12 @@ GCNII_BF16_MAX_WIDTH = 256      # a bf16 result of gnx_gcnii_step_bf16 is one co
 
 def _gcnii_launch_bf16(adj: Adjacency, H, H0, a, M, relu, out_bf16, out=None, work=None):
     """gnx_gcnii_step_bf16.  ``out`` / ``work``: buffers a stack of layers shares (contiguous [n, C]: bf16 or f32 / f32)."""
-    g = adj.graph
-    nat.require_cuda(H, H0, M)
-    _same_device(g, H, H0, M)
+    nat.require_cuda(H)
     if H.dim() != 2:
         raise Exception("gcnii_step: shape mismatch")
     Hb = (H if H.is_contiguous() else H.contiguous()) if H.dtype == torch.bfloat16 else to_bf16(H)
     H0, M = _as_f32_rows(H0).contiguous(), _as_f32_rows(M)
-    C = Hb.shape[1]
-    if g.n_rows != g.n_cols or Hb.shape[0] != g.n_rows or tuple(H0.shape) != tuple(Hb.shape) or tuple(M.shape) != (C, C):
-        raise Exception("gcnii_step: shape mismatch")
-    if adj.diag is not None:
-        raise Exception("gcnii_step: add_eye adjacencies are not supported by the fused step")
+    g, C = _gcnii_operands("gcnii_step", adj, Hb, (H0,), M)
     if out_bf16 and C > GCNII_BF16_MAX_WIDTH:                       # wider than one panel: the f32 result, rounded by gnx_cast_bf16
         return to_bf16(_gcnii_launch_bf16(adj, Hb, H0, a, M, relu, False, work=work))
     want = torch.bfloat16 if out_bf16 else torch.float32
@@ -1339,21 +1364,8 @@ GCNII_BF16_TRAIN_WIDTHS = (16, 32, 64)
 
 
 def _gcnii_bf16_operands(what, adj, rows, *f32):
-    """The checks the three bf16 training pieces share: a constant square adjacency without a diagonal, device tensors on its device,
-    ``rows`` (bf16 or f32, [n, C]) and every ``f32`` matrix of that shape; returns (graph, C)."""
-    if isinstance(adj, DroppedAdjacency):
-        raise Exception(f"{what}: bf16 training storage needs a constant adjacency (a DroppedAdjacency makes its weights in the SpMM)")
-    if adj.diag is not None:
-        raise Exception(f"{what}: add_eye adjacencies are not supported by the fused step")
-    g = adj.graph
-    nat.require_cuda(rows, *f32)
-    _same_device(g, rows, *f32)
-    if rows.dim() != 2 or g.n_rows != g.n_cols or rows.shape[0] != g.n_rows:
-        raise Exception(f"{what}: shape mismatch")
-    for t in f32:
-        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != tuple(rows.shape) or not t.is_contiguous()):
-            raise Exception(f"{what}: shape mismatch")
-    return g, rows.shape[1]
+    """_gcnii_operands as the bf16 training pieces call it (the name it had while only they used it): a constant adjacency."""
+    return _gcnii_operands(what, adj, rows, f32, None, "bf16 training storage")
 
 
 def gcnii_step_train_bf16(adj: Adjacency, Hb: torch.Tensor, H0: torch.Tensor, a: float, M: torch.Tensor, relu=True, dropout=None,
@@ -1363,9 +1375,8 @@ def gcnii_step_train_bf16(adj: Adjacency, Hb: torch.Tensor, H0: torch.Tensor, a:
     C in {16, 32, 64}; ``dropout`` = (p, seed, stream) or None; ``work``: an f32 [n, C] buffer a run of layers shares (graphs with hub
     rows need one; None allocates it)."""
     H0, M = _as_f32_rows(H0).contiguous(), _as_f32_rows(M)
-    g, C = _gcnii_bf16_operands("gcnii_step_train_bf16", adj, Hb, H0, work)
-    nat.require_cuda(M)
-    if Hb.dtype != torch.bfloat16 or not Hb.is_contiguous() or tuple(M.shape) != (C, C):
+    g, C = _gcnii_operands("gcnii_step_train_bf16", adj, Hb, (H0, work), M, "bf16 training storage")
+    if Hb.dtype != torch.bfloat16 or not Hb.is_contiguous():
         raise Exception("gcnii_step_train_bf16: needs contiguous bf16 rows [n, C] and M [C, C]")
     p, seed, stream = _dropout_triple(dropout, "gcnii_step_train_bf16") or (0.0, 0, 0)
     out = torch.empty(Hb.shape, dtype=torch.bfloat16 if out_bf16 else torch.float32, device=Hb.device)
@@ -1383,40 +1394,16 @@ def feature_dropout_back_bf16(graph: DeviceGraph, g: torch.Tensor, yb, dropout=N
     """The backward's gate over the STORED bf16 output ``yb`` of a layer (gnx_feature_dropout_back_bf16): returns (G, Gb) with
     G = kept ? g * s : 0 in f32 -- with ``relu`` also 0 where the stored y <= 0 -- and Gb = bf(G).  ``dropout`` = (p, seed, stream) or
     None (the relu gate plus the cast); any width."""
-    g = _as_f32_rows(g).contiguous()
     nat.require_cuda(g, yb)
-    _same_device(graph, g, yb)
     if relu and (yb is None or yb.dtype != torch.bfloat16 or tuple(yb.shape) != tuple(g.shape) or not yb.is_contiguous()):
         raise Exception("feature_dropout_back_bf16: relu needs the stored bf16 output, contiguous, in the gradient's shape")
-    p, seed, stream = _dropout_triple(dropout, "feature_dropout_back_bf16") or (0.0, 0, 0)
-    G, Gb = torch.empty_like(g), torch.empty(g.shape, dtype=torch.bfloat16, device=g.device)
-    if g.numel() == 0:
-        return G, Gb
-    yb = yb if relu else None
-    with nat.on_device(g.device):
-        nat.check(nat.lib().gnx_feature_dropout_back_bf16(graph.handle, nat.ptr(g), g.stride(0), nat.ptr(yb), 0 if yb is None else yb.stride(0),
-                                                          g.shape[0], g.shape[1], p, seed, stream, nat.ACT_RELU if relu else nat.ACT_NONE,
-                                                          nat.ptr(G), G.stride(0), nat.ptr(Gb), Gb.stride(0), nat.current_stream()))
-    return G, Gb
+    return _gate_launch(graph, g, yb, *(_dropout_triple(dropout, "feature_dropout_back_bf16") or (0.0, 0, 0)), relu, bf16=True)
 
 
 def gcnii_step_back_bf16(adj: Adjacency, Gb: torch.Tensor, G, a: float, Mt: torch.Tensor, S_in=None, s_alpha=1.0, want_S=True, in_place=False):
     """gcnii_step_back with the gathered operand in bf16 (gnx_gcnii_step_back_bf16; no autograd): dH = ((1-a) A^T Gb~) . Mt in f32 and
     S = s_alpha S_in + (a G) . Mt from the f32 ``G`` (None with ``want_S=False``).  Returns (dH, S); ``in_place``: S is S_in itself."""
-    Mt = _as_f32_rows(Mt)
-    g, C = _gcnii_bf16_operands("gcnii_step_back_bf16", adj, Gb, G, S_in)
-    nat.require_cuda(Mt)
-    if Gb.dtype != torch.bfloat16 or not Gb.is_contiguous() or tuple(Mt.shape) != (C, C):
-        raise Exception("gcnii_step_back_bf16: needs contiguous bf16 rows [n, C] and Mt [C, C]")
-    if want_S == (G is None) or (S_in is not None and not want_S) or (in_place and S_in is None):
-        raise Exception("gcnii_step_back_bf16: the f32 G goes with want_S, S_in needs want_S, in_place needs S_in")
-    dH = torch.empty(Gb.shape, dtype=torch.float32, device=Gb.device)
-    S = (S_in if in_place else torch.empty_like(dH)) if want_S else None
-    values = adj.transposed_values()
-    with nat.on_device(Gb.device):
-        nat.check(nat.lib().gnx_gcnii_step_back_bf16(g.handle, nat.ptr(values), nat.ptr(Gb), nat.ptr(G), float(a), C, nat.ptr(Mt), Mt.stride(0),
-                                                     nat.ptr(dH), nat.ptr(S_in), float(s_alpha), nat.ptr(S), None, nat.current_stream()))
-    return dH, S
+    return _gcnii_back_launch(True, adj, Gb, G, a, Mt, S_in, s_alpha, want_S, in_place)
 
 
 class _GCNIITrainRunBf16(torch.autograd.Function):

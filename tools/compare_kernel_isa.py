@@ -9,8 +9,10 @@
 
 Per .amdhsa_kernel: the instruction text with symbol names, .LBB<n>_ label numbers, comments and directives stripped, and the
 metadata counts .vgpr_count / .sgpr_count / .private_segment_fixed_size / .group_segment_fixed_size.  Kernels are paired by name:
-a "_bf16" suffix and a leading row-storage policy argument are dropped, the first two template arguments must agree and the rest of
-the shorter list must be a subsequence of the longer one (the hand-copied bf16 kernels carried no U / PIPE arguments)."""
+first those whose full name is the same on both sides (reported under the family as it is spelled, so that k_x and k_x_bf16, or
+the instantiations of one kernel over two row-storage policies, stay apart); for the rest a "_bf16" suffix and a leading row-storage
+policy argument are dropped, the first two template arguments must agree and the rest of the shorter list must be a subsequence of
+the longer one (the hand-copied bf16 kernels carried no U / PIPE arguments)."""
 import glob
 import os
 import re
@@ -38,7 +40,13 @@ def kernels(path):
         out[name] = (lines, meta[name])
     names = list(out)
     plain = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
-    return {key(p): out[n] for n, p in zip(names, plain)}
+    return {p: out[n] for n, p in zip(names, plain)}            # by full name: no two kernels of a unit share an entry
+
+
+def spelled(demangled):
+    """(family, template arguments) as the source spells them"""
+    fam, _, args = re.sub(r"\(anonymous namespace\)::|^void |\(.*\)$", "", demangled).partition("<")
+    return fam, (args.rstrip(">"),)
 
 
 def key(demangled):
@@ -59,14 +67,18 @@ def main(old_dir, new_dir):
         unit = os.path.basename(new_s)
         old, new = kernels(os.path.join(old_dir, unit)), kernels(new_s)
         print(f"### {unit[:-2]}.hip: {len(old)} kernels before, {len(new)} after")
-        left, fams = dict(old), {}
-        for (fam, args), (body, counts) in sorted(new.items()):
+        same_name = sorted(set(old) & set(new))
+        left, fams = {key(n): v for n, v in old.items() if n not in new}, {}
+        assert len(left) + len(same_name) == len(old), "two kernels of the old build share a pairing key"
+        pairs = [(spelled(n), new[n], old[n]) for n in same_name]
+        for (fam, args), found in sorted((key(n), v) for n, v in new.items() if n not in old):
             match = [k for k in left if k[0] == fam and k[1][:2] == args[:2]
                      and subsequence(*sorted((k[1], args), key=len))]
             if not match:
                 print(f"  no kernel before for {fam}<{', '.join(args)}>")
                 continue
-            obody, ocounts = left.pop(sorted(match, key=lambda k: abs(len(k[1]) - len(args)))[0])
+            pairs.append(((fam, args), found, left.pop(sorted(match, key=lambda k: abs(len(k[1]) - len(args)))[0])))
+        for (fam, args), (body, counts), (obody, ocounts) in pairs:
             same = body == obody and counts == ocounts
             fams.setdefault(fam, []).append(None if same else
                 f"    <{', '.join(args)}>: instructions {len(obody)} -> {len(body)}, "
