@@ -1035,6 +1035,11 @@ int dense_rows(const float *X, int64_t ldx, int64_t n, int64_t F, const float *W
     return GNX_OK;
 }
 
+// the [elems] partials of n_slabs row slabs added in slab order into out: the last pass of gnx_dense_wgrad and of gnx_gcnii_wgrad
+void sum_slabs(const float *partial, int64_t n_slabs, int64_t elems, float *out, hipStream_t s) {
+    hipLaunchKernelGGL(k_sum_slabs, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, s, partial, n_slabs, elems, out);
+}
+
 }  // namespace gnx
 
 extern "C" {
@@ -1083,9 +1088,9 @@ int gnx_dense_wgrad(const float *d_X, int64_t ldx, const float *d_G, int64_t ldg
             if (waves > 64 && work_floats >= (waves + groups) * fo) {
                 float *tmp = d_work + waves * fo;
                 hipLaunchKernelGGL(k_sum_slab_groups, dim3((unsigned)((fo + 255) / 256), (unsigned)groups), dim3(256), 0, s, d_work, waves, per, fo, tmp);
-                hipLaunchKernelGGL(k_sum_slabs, dim3((unsigned)((fo + 255) / 256)), dim3(256), 0, s, tmp, groups, fo, d_dW);
+                sum_slabs(tmp, groups, fo, d_dW, s);
             } else {
-                hipLaunchKernelGGL(k_sum_slabs, dim3((unsigned)((fo + 255) / 256)), dim3(256), 0, s, d_work, waves, fo, d_dW);
+                sum_slabs(d_work, waves, fo, d_dW, s);
             }
             GNX_HIP(hipGetLastError());
             return GNX_OK;
@@ -1097,7 +1102,7 @@ int gnx_dense_wgrad(const float *d_X, int64_t ldx, const float *d_G, int64_t ldg
     if (NTsel == 4)      hipLaunchKernelGGL(k_wgrad_mfma<4>, grid, dim3(256), 0, s, d_X, ldx, d_G, ldg, n, (int)F, (int)O, rows_per_slab, al, d_work);
     else if (NTsel == 2) hipLaunchKernelGGL(k_wgrad_mfma<2>, grid, dim3(256), 0, s, d_X, ldx, d_G, ldg, n, (int)F, (int)O, rows_per_slab, al, d_work);
     else                 hipLaunchKernelGGL(k_wgrad_mfma<1>, grid, dim3(256), 0, s, d_X, ldx, d_G, ldg, n, (int)F, (int)O, rows_per_slab, al, d_work);
-    hipLaunchKernelGGL(k_sum_slabs, dim3((unsigned)((fo + 255) / 256)), dim3(256), 0, s, d_work, n_slabs, fo, d_dW);
+    sum_slabs(d_work, n_slabs, fo, d_dW, s);
     GNX_HIP(hipGetLastError());
     return GNX_OK;
 }

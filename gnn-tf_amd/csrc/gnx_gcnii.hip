@@ -3,16 +3,19 @@
 //                      dropout in the store loop, DROP), written once over the row-storage policy R of gnx_spmm_device.h
 //   k_spmm_gcnii_back  the layer's backward past the relu gate, one launch of the same shape over the transposed structure; the MFMA
 //                      block of the two is one device function (tile_times_Ms)
+//   k_gcnii_wgrad      the layer's weight gradient dM = T^T G with the mixed rows T made again in LDS and never stored, one launch; a
+//                      row's gather and mix is one device function with the forward (mixed_row)
 //   row passes         k_round_rows (f32 rows -> bf16), k_feature_dropout (the mask as a pass of its own: hub rows, the other widths, the
 //                      generic composition) and the backward's gate (k_feature_dropout_back, .._back_bf16); one launcher
 //                      (launch_row_pass) picks their vector width and grid
-//   gcnii_forward<R>   the host path of gnx_gcnii_step, gnx_gcnii_step_drop (F32Rows), gnx_gcnii_step_bf16 and gnx_gcnii_step_train_bf16
-//                      (Bf16Rows); a ForwardForm says what differs: the mask, where mixed rows are kept or pass through memory, the format
+//   gcnii_forward<R>   the host path of gnx_gcnii_step, gnx_gcnii_step_drop (F32Rows), gnx_gcnii_step_bf16, gnx_gcnii_step_train_bf16
+//                      and gnx_gcnii_step_drop_bf16 (Bf16Rows); a ForwardForm says what differs: the mask, where mixed rows are kept or pass through memory, the format
 //                      of the result, and whether the widths other than 16 / 32 / 64 run as two launches or are refused.  The checks, the
 //                      operand fill, ensure_partial (before the first launch), the launch (with_tile_width) and the tail of the rows
 //                      that go through memory (transform_rows) each stand once
 //   gcnii_backward<R>  the host path of gnx_gcnii_step_back and gnx_gcnii_step_back_bf16, likewise; the f32 entry's composed form of the
 //                      other widths is its f32 branch
+//   gcnii_wgrad<R>     the host path of gnx_gcnii_wgrad and gnx_gcnii_wgrad_bf16
 // Hub rows share the long-row path of gnx_spmm.hip / gnx_spmm_bf16.hip (launch_long_rows, launch_long_rows_bf16: the f32 launch's
 // summation order) and the dense kernel on those rows alone; rounding points in gnx.h.  The masks come from the counter RNG of the edge
 // dropout.
@@ -66,6 +69,38 @@ __device__ __forceinline__ void tile_times_Ms(float *__restrict__ T, const float
     __builtin_amdgcn_wave_barrier();
 }
 
+// One mixed row of the fused layer, columns c .. c + 3 of row `row` (entries beg .. end) into acc (zeros on entry): the gather loop, the
+// entry order and the mix, written once -- the forward (k_spmm_gcnii) and the weight gradient that makes T again (k_gcnii_wgrad) run this
+// code, so a row made again has the bits of the row the forward stored.  U entries in flight per lane.
+template <typename R, int U>
+__device__ __forceinline__ void mixed_row(const typename R::Args &p, int64_t row, int64_t beg, int64_t end, int c, float (&acc)[4]) {
+    const typename R::Elem *__restrict__ Xc = R::X(p) + c;
+    for (int64_t e = beg; e < end; e += U) {
+        float x[U][4];
+        float w[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (e + u < end) {
+                const int j = p.colidx[e + u];
+                w[u] = p.vals[e + u];
+                R::template load<4>(x[u], Xc + (int64_t)j * p.ldx);
+            } else {
+                w[u] = 0.f;
+#pragma unroll
+                for (int v = 0; v < 4; ++v) x[u][v] = 0.f;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
+    }
+    float h0[4];
+    vload<4>(h0, p.H0 + row * p.ldh0 + c);
+#pragma unroll
+    for (int v = 0; v < 4; ++v) acc[v] = fmaf(acc[v], p.beta, h0[v] * p.alpha);      // filter.py:20-21 / gcn.py:25
+}
+
 // ---- GCNII layer: SpMM + mix + C x C transform on the matrix cores + activation, one launch ------------------------
 //   out[i,:] = act( (beta * sum_j A[i,j] X[j,:] + alpha * H0[i,:]) . M ),   M = (1-b) I + b W   (gcn.py:22-27)
 // A 512-thread block: every wave gathers a tile of 16 rows (4 NT lanes of float4 per row, U entries in flight per lane,
@@ -112,31 +147,7 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args 
         rows[ps] = row;
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
         if (live[ps]) {
-            const typename R::Elem *__restrict__ Xc = R::X(p) + c;
-            for (int64_t e = beg; e < end; e += U) {
-                float x[U][4];
-                float w[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    if (e + u < end) {
-                        const int j = p.colidx[e + u];
-                        w[u] = p.vals[e + u];
-                        R::template load<4>(x[u], Xc + (int64_t)j * p.ldx);
-                    } else {
-                        w[u] = 0.f;
-#pragma unroll
-                        for (int v = 0; v < 4; ++v) x[u][v] = 0.f;
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
-            }
-            float h0[4];
-            vload<4>(h0, p.H0 + row * p.ldh0 + c);
-#pragma unroll
-            for (int v = 0; v < 4; ++v) acc[v] = fmaf(acc[v], p.beta, h0[v] * p.alpha);      // filter.py:20-21 / gcn.py:25
+            mixed_row<R, U>(p, row, beg, end, c, acc);
             if (mixed) vstore<4>(mixed + row * (int64_t)C + c, acc);
         }
         vstore<4>(T + rr * STRIDE + c, acc);
@@ -270,6 +281,97 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii_back(const typename R::
         }
         vstore<4>(S_out + at, o);
     }
+}
+
+// ---- the layer's weight gradient without stored mixed rows, one launch (gnx_gcnii_wgrad) -------------------------------------------
+//   dM = T^T . G,   T = beta * A . X + alpha * H0 made again by mixed_row -- the forward's gather, entry order and mix, so T[r] has the
+// bits the forward would have stored -- and never written.  The forward's block (512 threads, a 16-row tile per wave in LDS, row stride
+// C + 4) without Ms: a wave fills its tile, multiplies T_tile^T . G_tile into NT x NT accumulator blocks on v_mfma_f32_16x16x4_f32 (k =
+// the tile's 16 row slots, four per instruction) and goes on to its next tile with the accumulators live.  Block (mt, nt) holds the
+// columns NT m + mt of T against the columns NT n + nt of G: A[m][k] is then one 4 NT-byte LDS read of row k of the tile for all mt, and
+// B[k][n] one 4 NT-byte global load of G's row for all nt (16 lanes read the row's 64 NT contiguous bytes; no second LDS tile: at C = 64
+// the kernel keeps 34 KB of LDS and its registers set the occupancy: the 64 accumulators leave two blocks per CU, and only because the G
+// rows of a tile are loaded AFTER its gather -- requested before it, they are live through the gather loop and cost the second block;
+// profiles/NOTES.md has the compiler's report).  A slot past n holds zeros on both sides; a row without entries contributes alpha * H0[r]; a hub row's T
+// comes from `hub`, where the long-row kernels put it before this launch.
+// No float atomics, nothing depends on the device: wave w of block b takes the tiles b WPB + w + k gridDim.x WPB in ascending k (the
+// tiles are in degree-binned order, so striding spreads every degree bin over all blocks), the block adds its waves' accumulators in
+// wave order through LDS and writes one [C, C] partial, slab b of `work`; the host's grid is a function of (n, C, slabs) alone and the
+// slabs are added in index order by sum_slabs (gnx_dense.hip).
+template <typename R, int NT, int U, int WPB>
+__global__ __launch_bounds__(64 * WPB) void k_gcnii_wgrad(const typename R::Args p, const float *__restrict__ Gm, const float *__restrict__ hub,
+                                                          float *__restrict__ work) {
+    constexpr int C = 16 * NT, G = 4 * NT, RPP = 64 / G, PASSES = 16 / RPP, STRIDE = C + 4;
+    static_assert(WPB * 16 * STRIDE >= C * C, "the block's partial reuses the tiles");
+    __shared__ __attribute__((aligned(16))) float Ts[WPB * 16 * STRIDE];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int cc = lane & 15, g = lane >> 4, c = (lane % G) * 4;
+    float *T = Ts + wave * 16 * STRIDE;
+    f32x4 d[NT][NT];
+#pragma unroll
+    for (int mt = 0; mt < NT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) d[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int64_t n_tiles = (p.n_rows + 15) / 16, step = (int64_t)gridDim.x * WPB;
+    for (int64_t tile = (int64_t)blockIdx.x * WPB + wave; tile < n_tiles; tile += step) {
+        // the tile as the forward fills it (4 NT lanes of float4 per row, RPP rows per pass), a hub row from `hub`
+#pragma unroll
+        for (int ps = 0; ps < PASSES; ++ps) {
+            const int rr = ps * RPP + lane / G;
+            const int64_t slot = tile * 16 + rr;
+            float acc[4] = {0.f, 0.f, 0.f, 0.f};
+            if (slot < p.n_rows) {
+                const int64_t row = p.row_order ? (int64_t)p.row_order[slot] : slot;
+                const int64_t beg = p.rowptr[row], end = p.rowptr[row + 1];
+                if (end - beg <= p.long_row) mixed_row<R, U>(p, row, beg, end, c, acc);
+                else vload<4>(acc, hub + row * (int64_t)C + c);
+            }
+            vstore<4>(T + rr * STRIDE + c, acc);
+        }
+        // B[k = 4 kk + g][n = cc] of block nt = G[row of slot k][NT cc + nt]
+        float b[4][NT];
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            const int64_t slot = tile * 16 + 4 * kk + g;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) b[kk][nt] = 0.f;
+            if (slot < p.n_rows) {
+                const int64_t row = p.row_order ? (int64_t)p.row_order[slot] : slot;
+                vload<NT>(b[kk], Gm + row * (int64_t)C + NT * cc);
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        // A[m = cc][k = 4 kk + g] of block mt = T[slot k][NT cc + mt]
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            float a[NT];
+            vload<NT>(a, T + (4 * kk + g) * STRIDE + NT * cc);
+#pragma unroll
+            for (int mt = 0; mt < NT; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) d[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mt], b[kk][nt], d[mt][nt], 0, 0, 0);
+        }
+        __builtin_amdgcn_wave_barrier();      // every lane has read the tile before it is filled again
+    }
+    // D of block (mt, nt): lane (cc, g), register r -> dM[NT (4 g + r) + mt][NT cc + nt]; the waves in wave order into the block's partial
+    __syncthreads();
+    for (int w = 0; w < WPB; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int mt = 0; mt < NT; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int at = (NT * (4 * g + r) + mt) * C + NT * cc + nt;
+                        Ts[at] = w == 0 ? d[mt][nt][r] : Ts[at] + d[mt][nt][r];
+                    }
+        }
+        __syncthreads();
+    }
+    float *__restrict__ slab = work + (int64_t)blockIdx.x * (C * C);
+    for (int idx = threadIdx.x; idx < C * C; idx += 64 * WPB) slab[idx] = Ts[idx];
 }
 
 using Bf16Rows = Bf16RowsT<false>;
@@ -629,6 +731,55 @@ int gcnii_backward(const char *fn, gnx_graph *g, const float *d_vals_t, const ty
     return GNX_OK;
 }
 
+// ---- the weight gradient's host path, once over the row storage R of H (gnx_gcnii_wgrad, gnx_gcnii_wgrad_bf16) -------------------------
+// No composed form: the other widths / alignments are refused (refuse_unfused) and the callers keep the stored rows there.
+template <typename R>
+int gcnii_wgrad(const char *fn, const char *reports, gnx_graph *g, const float *d_vals, const typename R::Elem *d_H, const float *d_H0, float a,
+                int64_t C, const float *d_G, float *d_dM, float *d_hub_rows, float *d_work, int64_t work_floats, void *stream) {
+    GNX_CHECK_ARG(g != nullptr, "%s: NULL handle", fn);
+    GNX_CHECK_ARG(C >= 1 && C <= (1 << 20), "%s: feature width %lld not in [1, 2^20]", fn, (long long)C);
+    GNX_CHECK_ARG(d_H != nullptr && d_H0 != nullptr && d_G != nullptr && d_dM != nullptr, "%s: NULL H / H0 / G / dM", fn);
+    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "%s: needs a square graph", fn);
+    const void *H = d_H;
+    auto own = [&](const void *b) { return b != H && b != d_H0 && b != d_G && b != d_vals; };
+    GNX_CHECK_ARG(own(d_dM), "%s: dM must not alias H / H0 / G / the values", fn);
+    GNX_CHECK_ARG(d_work != nullptr && own(d_work) && d_work != d_dM, "%s: d_work must be a buffer of its own", fn);
+    GNX_CHECK_ARG(d_hub_rows == nullptr || (own(d_hub_rows) && d_hub_rows != d_dM && d_hub_rows != d_work), "%s: d_hub_rows must be a buffer of its own", fn);
+    GNX_CHECK_ARG(work_floats >= C * C, "%s: work_floats %lld below C * C (every slab of d_work holds a [C, C] partial)", fn, (long long)work_floats);
+    if (!(fused_width(C) && aligned(d_H, 4 * sizeof(typename R::Elem)) && aligned(d_H0, 16) && aligned(d_G, 16) && aligned(d_dM, 16) &&
+          aligned(d_hub_rows, 16) && aligned(d_work, 16)))
+        return refuse_unfused(fn, C);
+    const Csr &m = g->a;
+    GNX_CHECK_ARG(d_hub_rows != nullptr || m.n_long == 0, "%s: needs d_hub_rows [n, C] f32 (the graph has hub rows: their mixed rows go through memory)", fn);
+    hipStream_t s = (hipStream_t)stream;
+    if (m.n_rows == 0) {
+        GNX_HIP(hipMemsetAsync(d_dM, 0, (size_t)(C * C) * sizeof(float), s));
+        return GNX_OK;
+    }
+    if (m.n_long > 0) {   // (before the first launch: under capture a slab that would have to grow refuses the whole call)
+        const int rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)C * sizeof(float), s);
+        if (rc != GNX_OK) return rc;
+    }
+    typename R::Args p{};
+    p.vals = d_vals ? d_vals : g->raw_vals;
+    set_operands<R>(p, d_H, C, d_H0, C, (float)(1.0 - (double)a), a, GNX_ACT_NONE, static_cast<typename R::Out *>(d_hub_rows), 0, C, C);
+    bind_fused(m, p);
+    if (m.n_long > 0) {   // hub rows: chunked partial sums -> mixed rows at their row ids of d_hub_rows, where the launch below finds them
+        p.partial = g->partial;
+        launch_hub_rows<R>(p, d_H, d_hub_rows, s);
+    }
+    // as many slabs as the scratch holds, at most 2048 (gnx_dense_wgrad's cap) and at most one per block of eight tiles: a function of
+    // (n, C, work_floats) alone, like the tile -> wave -> block assignment that follows from it
+    const int64_t slabs = std::min<int64_t>(std::min<int64_t>(work_floats / (C * C), 2048), blocks_for(blocks_for(m.n_rows, 16), 8));
+    with_tile_width(C, m.n_rows, [&](auto NT, dim3) {
+        hipLaunchKernelGGL((k_gcnii_wgrad<R, NT(), 4, 8>), dim3((unsigned)slabs), dim3(512), 0, s, p, d_G, m.n_long > 0 ? d_hub_rows : nullptr, d_work);
+    });
+    sum_slabs(d_work, slabs, C * C, d_dM, s);
+    g->last_kernel = reports;
+    GNX_HIP(hipGetLastError());
+    return GNX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -668,6 +819,29 @@ int gnx_gcnii_step_train_bf16(gnx_graph_t g, const float *d_vals, const uint16_t
     GNX_CHECK_ARG(d_mixed != nullptr, "%s: needs d_mixed [n, C] f32 (the mixed rows T are kept for the weight gradient)", fn);
     const ForwardForm f{dropout_p != 0.0 ? &fd : nullptr, d_mixed, d_work, out_bf16, false, "spmm_gcnii_mfma_train_bf16", nullptr};
     return gcnii_forward<Bf16Rows>(fn, g, d_vals, d_H, d_H0, a, C, d_M, ldm, act, d_out, f, stream);
+}
+
+// (gnx_gcnii_step_train_bf16 without d_mixed: the forward of a layer whose weight gradient makes T again, gnx_gcnii_wgrad_bf16)
+int gnx_gcnii_step_drop_bf16(gnx_graph_t g, const float *d_vals, const uint16_t *d_H, const float *d_H0, float a, int64_t C, const float *d_M,
+                             int64_t ldm, int act, double dropout_p, uint64_t seed, uint64_t stream_id, void *d_out, int out_bf16, float *d_work,
+                             void *stream) {
+    const char *fn = "gnx_gcnii_step_drop_bf16";
+    DropFuse fd{};
+    int rc = make_feat_drop(fn, g, dropout_p, seed, stream_id, fd);
+    if (rc != GNX_OK) return rc;
+    const ForwardForm f{dropout_p != 0.0 ? &fd : nullptr, nullptr, d_work, out_bf16, false, "spmm_gcnii_mfma_drop_bf16", nullptr};
+    return gcnii_forward<Bf16Rows>(fn, g, d_vals, d_H, d_H0, a, C, d_M, ldm, act, d_out, f, stream);
+}
+
+int gnx_gcnii_wgrad(gnx_graph_t g, const float *d_vals, const float *d_H, const float *d_H0, float a, int64_t C, const float *d_G, float *d_dM,
+                    float *d_hub_rows, float *d_work, int64_t work_floats, void *stream) {
+    return gcnii_wgrad<F32Rows>("gnx_gcnii_wgrad", "gcnii_wgrad_mfma", g, d_vals, d_H, d_H0, a, C, d_G, d_dM, d_hub_rows, d_work, work_floats, stream);
+}
+
+int gnx_gcnii_wgrad_bf16(gnx_graph_t g, const float *d_vals, const uint16_t *d_H, const float *d_H0, float a, int64_t C, const float *d_G,
+                         float *d_dM, float *d_hub_rows, float *d_work, int64_t work_floats, void *stream) {
+    return gcnii_wgrad<Bf16Rows>("gnx_gcnii_wgrad_bf16", "gcnii_wgrad_mfma_bf16", g, d_vals, d_H, d_H0, a, C, d_G, d_dM, d_hub_rows, d_work,
+                                 work_floats, stream);
 }
 
 int gnx_gcnii_step_back(gnx_graph_t g, const float *d_vals_t, const float *d_G, float a, int64_t C, const float *d_Mt, int64_t ldmt,

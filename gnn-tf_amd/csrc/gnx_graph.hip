@@ -796,6 +796,13 @@ int gnx_graph_info(gnx_graph_t g, int64_t *n_rows, int64_t *n_cols, int64_t *nnz
     return GNX_OK;
 }
 
+int gnx_graph_hub_rows(gnx_graph_t g, int64_t *n_hub_rows, int64_t *threshold) {
+    GNX_CHECK_ARG(g != nullptr, "gnx_graph_hub_rows: NULL handle");
+    if (n_hub_rows) *n_hub_rows = g->a.n_long;
+    if (threshold) *threshold = g->a.long_row;
+    return GNX_OK;
+}
+
 int gnx_graph_csr(gnx_graph_t g, const int64_t **d_rowptr, const int32_t **d_colidx, const float **d_raw_values) {
     GNX_CHECK_ARG(g != nullptr, "gnx_graph_csr: NULL handle");
     if (d_rowptr) *d_rowptr = g->a.rowptr;

@@ -29,6 +29,7 @@ SIGNATURES = {
     "gnx_graph_create_csr": (c_int, [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
     "gnx_graph_destroy": (c_int, [c_void_p]),
     "gnx_graph_info": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
+    "gnx_graph_hub_rows": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64)]),
     "gnx_graph_csr": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p)]),
     "gnx_graph_export": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gnx_graph_normalize": (c_int, [c_void_p, c_int, c_int, c_float, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
@@ -111,6 +112,12 @@ SIGNATURES = {
                                               c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "gnx_gcnii_step_back_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                          c_float, c_void_p, c_void_p, c_void_p]),
+    "gnx_gcnii_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                c_void_p]),
+    "gnx_gcnii_wgrad_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                     c_void_p]),
+    "gnx_gcnii_step_drop_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_int64, c_int, c_double,
+                                         c_uint64, c_uint64, c_void_p, c_int, c_void_p, c_void_p]),
     "gnx_dense": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int64,
                           c_void_p]),
     "gnx_dense_wgrad": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),

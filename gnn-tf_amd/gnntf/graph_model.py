@@ -51,7 +51,7 @@ class GNN(Trainable):
 
     def __init__(self, graph, features, preprocessor: Layer = None, reorder=None, inference_dtype=torch.float32,
                  training_dtype=torch.float32, train_gather_order="auto", gcnii_backward="composed", feature_dropout="torch",
-                 gcnii_training_dtype=torch.float32):
+                 gcnii_training_dtype=torch.float32, gcnii_weight_gradient="stored"):
         """``reorder`` (opt-in, not in the reference): store the graph and the feature rows with the vertices relabelled; every
         [N, .] tensor inside the model then lives in that order, and the model's OUTPUT is put back into the caller's order, so
         tasks, labels and node ids are unaffected.  Results agree with the unordered model to float32 rounding.
@@ -119,7 +119,21 @@ class GNN(Trainable):
         widths outside {16, 32, 64} or below sparse.GCNII_BF16_TRAIN_MIN_WIDTH, graphs of fewer than
         sparse.GCNII_BF16_TRAIN_MIN_ROWS rows (where the step measured slower: profiles/NOTES.md "bf16 storage in GCNII training" --
         4 % faster at C = 32 / 64 on 10^7 vertices, slower at C = 16 and at 10^6 vertices and below), GCNIISpectralPreservingLayer,
-        torch dropout, eval mode, the vertex-partitioned path and ``fuse_runs = False`` keep today's path and today's bits."""
+        torch dropout, eval mode, the vertex-partitioned path and ``fuse_runs = False`` keep today's path and today's bits.
+        ``gcnii_weight_gradient`` (not in the reference): ``"stored"`` (the default) or ``"recomputed"`` (sparse.gcnii_step /
+        sparse.gcnii_train_run_bf16 ``weight_gradient``).  A training GCNII layer saves two [n, C] matrices for its backward: its output
+        and the mixed rows T = (1-a) A.H + a H0, the latter for dW alone.  ``"recomputed"``: every plain GCNIILayer (this class itself,
+        relu or the identity as activation, width 16, 32 or 64, device tensors, a constant adjacency without add_eye), on the f32 path
+        and in a ``gcnii_training_dtype=torch.bfloat16`` run alike, writes no T in its forward and saves its input and H0 in T's place;
+        dW then comes from one launch that makes T again in LDS and multiplies T^T G on the matrix cores (gnx_gcnii_wgrad).  Where it
+        saves memory: with ``feature_dropout="fused"`` or a layer ``dropout`` of 0 the layer's input IS the previous layer's saved
+        output and H0 is saved by the layer that made it, so a layer keeps 4 bytes per element and layer less -- 8 -> 4 in f32,
+        6 -> 2 with bf16 rows; with torch's dropout the input is a tensor of its own (the dropout's result) and the saving is nil.  The
+        logits, the loss, dH, dH0 and the gradient of the run's input keep their bits, every dW agrees to float32 rounding (another
+        summation order: why it is opt-in); works with either ``gcnii_backward``; ``train(capture=True)`` equals the eager run bit for
+        bit under fused dropout, as before.  GCNIISpectralPreservingLayer, other activations, add_eye, other widths, dropped
+        adjacencies, CPU tensors and the vertex-partitioned path keep today's path whatever it says (measurement: profiles/NOTES.md
+        "GCNII weight gradient without stored rows")."""
         if feature_dropout not in FEATURE_DROPOUTS:
             raise Exception("GNN: feature_dropout must be one of " + ", ".join(repr(f) for f in FEATURE_DROPOUTS))
         if gcnii_backward not in sparse.GCNII_BACKWARDS:
@@ -132,12 +146,15 @@ class GNN(Trainable):
             raise Exception("GNN: training_dtype must be torch.float32 or torch.bfloat16")
         if gcnii_training_dtype not in (torch.float32, torch.bfloat16):
             raise Exception("GNN: gcnii_training_dtype must be torch.float32 or torch.bfloat16")
+        if gcnii_weight_gradient not in sparse.GCNII_WEIGHT_GRADIENTS:
+            raise Exception("GNN: gcnii_weight_gradient must be one of " + ", ".join(repr(w) for w in sparse.GCNII_WEIGHT_GRADIENTS))
         super().__init__(features)
         self.inference_dtype = inference_dtype
         self.training_dtype = training_dtype
         self.gcnii_training_dtype = gcnii_training_dtype
         self.train_gather_order = train_gather_order
         self.gcnii_backward = gcnii_backward
+        self.gcnii_weight_gradient = gcnii_weight_gradient
         self.feature_dropout = feature_dropout
         self._order = self._newid = None
         self.reorder_used, self.locality_share = None, None
@@ -511,7 +528,8 @@ class GCNIILayer(Layer):
             triple = (layer.dropout,) + tuple(gcn._next_mask_stream()) if layer.dropout != 0 else None
             steps.append((layer.H0.value, float(layer.a), layer._transform(), layer.activation is relu, triple))
         stored = []
-        out = sparse.gcnii_train_run_bf16(adjacency, features, steps, stored=stored)
+        out = sparse.gcnii_train_run_bf16(adjacency, features, steps, stored=stored,
+                                          weight_gradient=getattr(gcn, "gcnii_weight_gradient", "stored"))
         for k, layer in enumerate(run[:-1]):
             layer.__dict__["_value"] = None
             layer.__dict__["_pending_value"] = lambda k=k: stored[k].float()
@@ -559,14 +577,17 @@ class GCNIILayer(Layer):
         adjacency = gcn.get_adjacency(self.graph_dropout)
         if features.is_cuda and adjacency.diag is None:
             fused_act = self.activation is relu or self.activation is linear
+            # GNN(gcnii_weight_gradient="recomputed"): plain layers alone (the argument is passed only where it can change the path)
+            wgrad = dict(weight_gradient="recomputed") if (getattr(gcn, "gcnii_weight_gradient", "stored") == "recomputed"
+                                                           and type(self) is GCNIILayer and fused_act) else dict()
             if (getattr(gcn, "feature_dropout", "torch") == "fused" and type(self) is GCNIILayer and fused_act and gcn.is_training()
                     and 0 < self.dropout < 1):                      # (a rate of 1 or more stays with gcn.dropout and what torch makes of it)
                 # GNN(feature_dropout="fused"): dropout(act(...)) leaves the layer's launch, its mask from the counter RNG
                 seed, stream = gcn._next_mask_stream()
                 return sparse.gcnii_step(adjacency, features, self.H0.value, self.a, transform, relu=self.activation is relu,
-                                         backward=getattr(gcn, "gcnii_backward", "composed"), dropout=(self.dropout, seed, stream))
+                                         backward=getattr(gcn, "gcnii_backward", "composed"), dropout=(self.dropout, seed, stream), **wgrad)
             out = sparse.gcnii_step(adjacency, features, self.H0.value, self.a, transform, relu=self.activation is relu,
-                                    backward=getattr(gcn, "gcnii_backward", "composed"))
+                                    backward=getattr(gcn, "gcnii_backward", "composed"), **wgrad)
             return gcn.dropout(out if fused_act else self.activation(out), self.dropout)
         tradeoff = sparse.ppr_step(adjacency, features, self.H0.value, self.a)
         return gcn.dropout(self.activation(torch.matmul(tradeoff, transform)), self.dropout)

@@ -98,6 +98,10 @@ class DeviceGraph:
         nat.check(lib.gnx_graph_info(self._h, byref(n_rows), byref(n_cols), byref(nnz_e), byref(nnz_c)))
         self.n_rows, self.n_cols = n_rows.value, n_cols.value
         self.nnz_entries, self.nnz = nnz_e.value, nnz_c.value
+        n_hub, threshold = c_int64(), c_int64()
+        nat.check(lib.gnx_graph_hub_rows(self._h, byref(n_hub), byref(threshold)))
+        # rows longer than ``long_row_threshold`` entries: the fused launches leave them to the long-row kernels (gnx_graph_hub_rows)
+        self.n_hub_rows, self.long_row_threshold = n_hub.value, threshold.value
         self._entry_dropout = False
 
     @property
@@ -1174,6 +1178,40 @@ def _gcnii_launch(adj: Adjacency, H, H0, a, M, relu, keep_mixed, dropout=None):
 
 
 GCNII_BACKWARDS = ("composed", "fused")
+GCNII_WEIGHT_GRADIENTS = ("stored", "recomputed")
+GCNII_FUSED_WIDTHS = (16, 32, 64)
+
+
+def _weight_gradient(what, weight_gradient) -> bool:
+    """Whether ``weight_gradient`` asks for the recomputed form; raises on anything but the two names."""
+    if weight_gradient not in GCNII_WEIGHT_GRADIENTS:
+        raise Exception(f"{what}: weight_gradient must be one of " + ", ".join(repr(w) for w in GCNII_WEIGHT_GRADIENTS))
+    return weight_gradient == "recomputed"
+
+
+def gcnii_wgrad(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, G: torch.Tensor, hub_rows=None) -> torch.Tensor:
+    """dM = T^T . G of one GCNII layer with the mixed rows T = (1-a) A.H + a H0 made again inside the launch and never stored
+    (gnx_gcnii_wgrad; a bf16 ``H`` -- the rows a bf16 training layer gathered -- takes gnx_gcnii_wgrad_bf16; no autograd).  ``H``, ``H0``
+    and the gated gradient ``G`` (f32) are contiguous [n, C], C in {16, 32, 64}, on a constant square adjacency without a diagonal; a row
+    of T has the bits the forward stores, the sum over the rows is ordered differently from gnx_dense_wgrad's (float32 rounding).
+    ``hub_rows``: an f32 [n, C] scratch the caller owns (a backward shares one among its layers); None allocates one, and only when the
+    graph has hub rows (DeviceGraph.n_hub_rows).  The slabs of the partial sums are sized as gnx_dense_wgrad's."""
+    g, C = _gcnii_operands("gcnii_wgrad", adj, H, (H0, G, hub_rows) if H.dtype == torch.bfloat16 else (H, H0, G, hub_rows), None,
+                           "the recomputed weight gradient")
+    bf16 = H.dtype == torch.bfloat16
+    if C not in GCNII_FUSED_WIDTHS or (bf16 and not H.is_contiguous()):
+        raise Exception("gcnii_wgrad: needs contiguous f32 or bf16 rows of width 16, 32 or 64")
+    n = H.shape[0]
+    if hub_rows is None and g.n_hub_rows > 0:
+        hub_rows = torch.empty((n, C), dtype=torch.float32, device=H.device)
+    slabs = max(1, min(2048, (n + 255) // 256, (1 << 28) // (C * C)))        # _dense_wgrad's sizing
+    work = torch.empty(slabs * C * C, dtype=torch.float32, device=H.device)
+    dM = torch.empty((C, C), dtype=torch.float32, device=H.device)
+    entry = nat.lib().gnx_gcnii_wgrad_bf16 if bf16 else nat.lib().gnx_gcnii_wgrad
+    with nat.on_device(H.device):
+        nat.check(entry(g.handle, nat.ptr(adj.vals), nat.ptr(H), nat.ptr(H0), float(a), C, nat.ptr(G), nat.ptr(dM), nat.ptr(hub_rows),
+                        nat.ptr(work), work.numel(), nat.current_stream()))
+    return dM
 
 
 def gcnii_step_back(adj: Adjacency, G: torch.Tensor, a: float, Mt: torch.Tensor, S_in=None, s_alpha=1.0, want_S=True):
@@ -1221,23 +1259,38 @@ class _GCNIIStep(torch.autograd.Function):
     tf.GradientTape): with g' = g * (out > 0):  dM = T^T g' (gnx_dense_wgrad), dT = g' M^T (gnx_dense), dH = (1-a) A^T dT, dH0 = a dT.
     ``backward="fused"``: dH = ((1-a) A^T g') M^T and dH0 = (a g') M^T from ONE launch (gcnii_step_back), dT never written.
     ``dropout`` = (p, seed, stream): out = drop(act(T . M)) from the same launch (gnx_gcnii_step_drop); the dropped out is what is
-    saved, and g' = kept ? g * s : 0 gated by out > 0 comes from one pass (gnx_feature_dropout_back) in place of the relu mask."""
+    saved, and g' = kept ? g * s : 0 gated by out > 0 comes from one pass (gnx_feature_dropout_back) in place of the relu mask.
+    ``recompute``: T is neither written nor saved -- (H, H0, M, out) are saved instead of (T, M, out), where H is the previous layer's
+    saved output and H0 the stack's -- and dM comes from gcnii_wgrad, which makes T again (widths 16, 32, 64 only)."""
 
     @staticmethod
-    def forward(ctx, H, H0, M, adj, a, relu, backward="composed", dropout=None):
+    def forward(ctx, H, H0, M, adj, a, relu, backward="composed", dropout=None, recompute=False):
+        ctx.adj, ctx.a, ctx.relu, ctx.fused_backward, ctx.dropout, ctx.recompute = adj, a, relu, backward == "fused", dropout, recompute
+        if recompute:   # T is not written: the backward makes it again from H and H0 (gcnii_wgrad), which are saved in its place
+            H, H0 = _as_f32_rows(H).contiguous(), _as_f32_rows(H0).contiguous()
+            out, _ = _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=False, dropout=dropout)
+            ctx.save_for_backward(H, H0, M, out if relu or dropout is not None else None)
+            return out
         out, T = _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=True, dropout=dropout)
-        ctx.adj, ctx.a, ctx.relu, ctx.fused_backward, ctx.dropout = adj, a, relu, backward == "fused", dropout
         ctx.save_for_backward(T, M, out if relu or dropout is not None else None)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        T, M, out = ctx.saved_tensors
+        if ctx.recompute:
+            H, H0, M, out = ctx.saved_tensors
+        else:
+            T, M, out = ctx.saved_tensors
         if ctx.dropout is not None:
             g = _feature_dropout_back(ctx.adj.graph, g, out, *ctx.dropout, relu=ctx.relu)
         else:
             g = (_relu_mask(g, out) if ctx.relu else g).contiguous()
-        gM = _dense_wgrad(T, g) if ctx.needs_input_grad[2] else None
+        if not ctx.needs_input_grad[2]:
+            gM = None
+        elif ctx.recompute:
+            gM = gcnii_wgrad(ctx.adj, H, H0, ctx.a, _as_f32_rows(g).contiguous())
+        else:
+            gM = _dense_wgrad(T, g)
         gH = gH0 = None
         if ctx.fused_backward and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
             # (the launch always makes dH; a caller that wants dH0 alone is not what a GCNII stack asks for)
@@ -1249,11 +1302,11 @@ class _GCNIIStep(torch.autograd.Function):
                 gH = _launch(ctx.adj, gT, None, 1.0 - ctx.a, 0.0, nat.ACT_NONE, transposed=True)
             if ctx.needs_input_grad[1]:
                 gH0 = gT * ctx.a
-        return gH, gH0, gM, None, None, None, None, None
+        return gH, gH0, gM, None, None, None, None, None, None
 
 
 def gcnii_step(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, M: torch.Tensor, relu=True, storage=torch.float32,
-               out_storage=torch.float32, backward="composed", dropout=None) -> torch.Tensor:
+               out_storage=torch.float32, backward="composed", dropout=None, weight_gradient="stored") -> torch.Tensor:
     """act(((A . H)(1-a) + H0 a) . M), M = (1-b) I + b W (gcn.py:22-27) -- ONE fused launch for C in {16, 32, 64}: the mixed
     rows stay in LDS and meet M on the matrix cores (gnx_gcnii_step).  Without autograd they never reach HBM; when gradients are
     needed the same launch also writes them (dM = T^T g needs them), once, and the transform does not read them back.  Other
@@ -1269,15 +1322,21 @@ def gcnii_step(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, M: t
     the same launch, out = drop(act(...)) (gnx_gcnii_step_drop) with the mask of ``feature_dropout`` -- the counter RNG of the edge
     dropout, not torch's generator; the mixed rows kept for dM stay undropped, and the backward starts with one pass
     (gnx_feature_dropout_back) instead of torch's dropout backward and the relu mask.  Behind the generic composition of a
-    DroppedAdjacency the mask is ``feature_dropout``'s pass.  Training only: raises together with ``storage=torch.bfloat16``."""
+    DroppedAdjacency the mask is ``feature_dropout``'s pass.  Training only: raises together with ``storage=torch.bfloat16``.
+    ``weight_gradient``: ``"stored"`` (the default: the launch writes T, it is saved, dM = T^T g comes from gnx_dense_wgrad -- today's
+    bits) or ``"recomputed"`` (opt-in, C in {16, 32, 64} on a constant adjacency, device tensors): the launch writes no T and the layer
+    saves (H, H0, M, out) instead of (T, M, out) -- in a stack H is the previous layer's saved output, so a layer keeps 4 bytes per
+    element less -- and dM comes from ``gcnii_wgrad``, which makes T again.  out, dH and dH0 keep their bits; dM agrees to float32
+    rounding (another summation order).  Other widths, a DroppedAdjacency and the inference paths ignore it."""
     if backward not in GCNII_BACKWARDS:
         raise Exception("gcnii_step: backward must be one of " + ", ".join(repr(b) for b in GCNII_BACKWARDS))
+    recompute = _weight_gradient("gcnii_step", weight_gradient)
     if dropout is not None:
         if _bf16(storage) or _bf16(out_storage):
             raise Exception("gcnii_step: dropout belongs to training, bf16 storage is inference only")
         dropout = _dropout_triple(dropout, "gcnii_step")
         if dropout is not None:
-            return _gcnii_step_dropped(adj, H, H0, a, M, relu, backward, dropout)
+            return _gcnii_step_dropped(adj, H, H0, a, M, relu, backward, dropout, recompute)
     if _bf16(storage):
         _no_grad_for_bf16("gcnii_step", H, H0, M)
         return _gcnii_launch_bf16(adj, H, H0, a, M, relu, _bf16(out_storage))
@@ -1286,16 +1345,16 @@ def gcnii_step(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, M: t
     if torch.is_grad_enabled() and (H.requires_grad or H0.requires_grad or M.requires_grad):
         if isinstance(adj, DroppedAdjacency):                       # weights made inside the SpMM: the generic composition knows how
             return dense(ppr_step(adj, H, H0, a), M, None, relu)
-        return _GCNIIStep.apply(H, H0, M, adj, float(a), bool(relu), backward)
+        return _GCNIIStep.apply(H, H0, M, adj, float(a), bool(relu), backward, None, recompute and H.shape[-1] in GCNII_FUSED_WIDTHS)
     return _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=False)[0]
 
 
-def _gcnii_step_dropped(adj, H, H0, a, M, relu, backward, dropout):
+def _gcnii_step_dropped(adj, H, H0, a, M, relu, backward, dropout, recompute=False):
     """gcnii_step with a feature dropout of rate > 0 (``dropout`` = the checked triple)."""
     if torch.is_grad_enabled() and (H.requires_grad or H0.requires_grad or M.requires_grad):
         if isinstance(adj, DroppedAdjacency):
             return feature_dropout(adj.graph, dense(ppr_step(adj, H, H0, a), M, None, relu), *dropout)
-        return _GCNIIStep.apply(H, H0, M, adj, float(a), bool(relu), backward, dropout)
+        return _GCNIIStep.apply(H, H0, M, adj, float(a), bool(relu), backward, dropout, recompute and H.shape[-1] in GCNII_FUSED_WIDTHS)
     return _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=False, dropout=dropout)[0]
 
 
@@ -1369,24 +1428,28 @@ def _gcnii_bf16_operands(what, adj, rows, *f32):
 
 
 def gcnii_step_train_bf16(adj: Adjacency, Hb: torch.Tensor, H0: torch.Tensor, a: float, M: torch.Tensor, relu=True, dropout=None,
-                          out_bf16=True, work=None):
+                          out_bf16=True, work=None, keep_mixed=True):
     """The training forward of one GCNII layer over bf16 gathered rows (gnx_gcnii_step_train_bf16; no autograd): returns (out, T) with
     T = (1-a) A.H~ + a H0 in f32, undropped, and out = drop(act(T . M)) as bf16 (``out_bf16``) or f32.  ``Hb``: bf16 [n, C] contiguous,
     C in {16, 32, 64}; ``dropout`` = (p, seed, stream) or None; ``work``: an f32 [n, C] buffer a run of layers shares (graphs with hub
-    rows need one; None allocates it)."""
+    rows need one; None allocates it).  ``keep_mixed=False``: T is not written (gnx_gcnii_step_drop_bf16: the layer's weight gradient
+    makes it again, gcnii_wgrad) and (out, None) is returned, out with the same bits; ``work`` is then allocated only for hub rows."""
     H0, M = _as_f32_rows(H0).contiguous(), _as_f32_rows(M)
     g, C = _gcnii_operands("gcnii_step_train_bf16", adj, Hb, (H0, work), M, "bf16 training storage")
     if Hb.dtype != torch.bfloat16 or not Hb.is_contiguous():
         raise Exception("gcnii_step_train_bf16: needs contiguous bf16 rows [n, C] and M [C, C]")
     p, seed, stream = _dropout_triple(dropout, "gcnii_step_train_bf16") or (0.0, 0, 0)
     out = torch.empty(Hb.shape, dtype=torch.bfloat16 if out_bf16 else torch.float32, device=Hb.device)
-    T = torch.empty(Hb.shape, dtype=torch.float32, device=Hb.device)
-    if work is None:
-        work = torch.empty_like(T)
+    T = torch.empty(Hb.shape, dtype=torch.float32, device=Hb.device) if keep_mixed else None
+    if work is None and (keep_mixed or g.n_hub_rows > 0):
+        work = torch.empty(Hb.shape, dtype=torch.float32, device=Hb.device)
+    layer = (g.handle, nat.ptr(adj.vals), nat.ptr(Hb), nat.ptr(H0), float(a), C, nat.ptr(M), M.stride(0), nat.ACT_RELU if relu else nat.ACT_NONE,
+             p, seed, stream, nat.ptr(out), 1 if out_bf16 else 0)
     with nat.on_device(Hb.device):
-        nat.check(nat.lib().gnx_gcnii_step_train_bf16(g.handle, nat.ptr(adj.vals), nat.ptr(Hb), nat.ptr(H0), float(a), C, nat.ptr(M), M.stride(0),
-                                                      nat.ACT_RELU if relu else nat.ACT_NONE, p, seed, stream, nat.ptr(out),
-                                                      1 if out_bf16 else 0, nat.ptr(T), nat.ptr(work), nat.current_stream()))
+        if keep_mixed:
+            nat.check(nat.lib().gnx_gcnii_step_train_bf16(*layer, nat.ptr(T), nat.ptr(work), nat.current_stream()))
+        else:
+            nat.check(nat.lib().gnx_gcnii_step_drop_bf16(*layer, nat.ptr(work), nat.current_stream()))
     return out, T
 
 
@@ -1411,20 +1474,27 @@ class _GCNIITrainRunBf16(torch.autograd.Function):
     rounded once, layer l gathers the stored rows of layer l - 1, every layer but the last stores bf(out), the last f32; saved per layer:
     the f32 T and the stored out.  backward, last layer first: the gate (G, Gb) -> dM = T^T G (gnx_dense_wgrad, f32) -> one launch for
     dH (the next upstream gradient) and the layer's term of dH0; consecutive layers that share one H0 tensor add their terms into one
-    running sum (S_in = S_out, s_alpha = 1), another H0 starts a new sum.  Tensor arguments: H, then (H0, M) per layer."""
+    running sum (S_in = S_out, s_alpha = 1), another H0 starts a new sum.  Tensor arguments: H, then (H0, M) per layer.
+    ``recompute``: no T is written or saved -- per layer (M, stored out) only, beside the run's input and the H0 tensors, which their
+    producers hold anyway -- and dM comes from gcnii_wgrad over the rows the layer gathered: layer k - 1's stored out, and for the first
+    layer the input rounded again (the same bits; a saved copy would cost the run 2 bytes per element).  One hub-row scratch serves
+    the whole backward."""
 
     @staticmethod
-    def forward(ctx, adj, meta, same_H0, stored, H, *tensors):
+    def forward(ctx, adj, meta, same_H0, stored, recompute, H, *tensors):
         X = to_bf16(H)
-        work = torch.empty(H.shape, dtype=torch.float32, device=H.device)
+        hubs = adj.graph.n_hub_rows > 0
+        work = torch.empty(H.shape, dtype=torch.float32, device=H.device) if hubs or not recompute else None
         saved, n = [], len(meta)
         for k, (a, relu, dropout) in enumerate(meta):
             H0, M = tensors[2 * k], tensors[2 * k + 1]
-            X, T = gcnii_step_train_bf16(adj, X, H0, a, M, relu, dropout, out_bf16=k < n - 1, work=work)
-            saved += [T, M, X]
+            X, T = gcnii_step_train_bf16(adj, X, H0, a, M, relu, dropout, out_bf16=k < n - 1, work=work, keep_mixed=not recompute)
+            saved += [M, X] if recompute else [T, M, X]
             if stored is not None and k < n - 1:
                 stored.append(X)
-        ctx.adj, ctx.meta, ctx.same_H0 = adj, meta, same_H0
+        ctx.adj, ctx.meta, ctx.same_H0, ctx.recompute = adj, meta, same_H0, recompute
+        if recompute:
+            saved = [H] + [tensors[2 * k] for k in range(n)] + saved
         ctx.save_for_backward(*saved)
         return X
 
@@ -1432,17 +1502,26 @@ class _GCNIITrainRunBf16(torch.autograd.Function):
     def backward(ctx, g):
         adj, meta, saved = ctx.adj, ctx.meta, ctx.saved_tensors
         n = len(meta)
-        need = ctx.needs_input_grad[5:]
+        need = ctx.needs_input_grad[6:]
         grads = [None] * (2 * n)
         S = None                                                    # the running dH0 sum of the layers k .. that share one H0
+        if ctx.recompute:
+            H, H0s, saved = saved[0], saved[1:n + 1], saved[n + 1:]
+            hub = torch.empty(H.shape, dtype=torch.float32, device=H.device) if adj.graph.n_hub_rows > 0 else None
         for k in range(n - 1, -1, -1):
-            (a, relu, dropout), (T, M, out) = meta[k], saved[3 * k:3 * k + 3]
+            a, relu, dropout = meta[k]
+            if ctx.recompute:
+                M, out = saved[2 * k:2 * k + 2]
+            else:
+                T, M, out = saved[3 * k:3 * k + 3]
             if k == n - 1:                                          # the run's f32 output: the existing gate, then the cast
                 G = _feature_dropout_back(adj.graph, g, out, *(dropout or (0.0, 0, 0)), relu=relu)
                 Gb = to_bf16(G)
             else:
                 G, Gb = feature_dropout_back_bf16(adj.graph, g, out, dropout, relu)
-            if need[2 * k + 1]:
+            if need[2 * k + 1] and ctx.recompute:                   # the rows layer k gathered: layer k - 1's stored out / the rounded input
+                grads[2 * k + 1] = gcnii_wgrad(adj, saved[2 * k - 1] if k > 0 else to_bf16(H), H0s[k], a, G, hub_rows=hub)
+            elif need[2 * k + 1]:
                 grads[2 * k + 1] = _dense_wgrad(T, G)
             want_S = need[2 * k]
             continues = want_S and S is not None                    # (S is not None: layer k + 1 shares this layer's H0 and wanted its sum)
@@ -1450,16 +1529,21 @@ class _GCNIITrainRunBf16(torch.autograd.Function):
                                         want_S=want_S, in_place=continues)
             if not ctx.same_H0[k]:                                  # the sum ends with the first layer of its H0: one gradient per sum
                 grads[2 * k], S = S, None
-        return (None, None, None, None, g if ctx.needs_input_grad[4] else None) + tuple(grads)
+        return (None, None, None, None, None, g if ctx.needs_input_grad[5] else None) + tuple(grads)
 
 
-def gcnii_train_run_bf16(adj: Adjacency, H: torch.Tensor, steps, stored=None) -> torch.Tensor:
+def gcnii_train_run_bf16(adj: Adjacency, H: torch.Tensor, steps, stored=None, weight_gradient="stored") -> torch.Tensor:
     """A run of GCNII layers in TRAINING with the rows handed from layer to layer -- and the gated gradient on the way back -- stored as
     bf16 (opt-in; one autograd node for the whole run).  ``steps``: per layer (H0, a, M, relu, dropout) with dropout = (p, seed, stream)
     of the fused feature dropout or None.  The run's f32 input is rounded once (its gradient passes straight through), every layer but
     the last stores bf(out), the last writes f32; sums, H0, T, the mix, the transform, dM and the running dH0 sums stay f32.  Widths 16,
     32 and 64 on a constant square adjacency without a diagonal; device tensors.  ``stored``: a list that receives the bf16 rows of
-    every layer but the last (what an inner layer's ``.value`` widens).  The backward is the fused one (gcnii_step_back_bf16)."""
+    every layer but the last (what an inner layer's ``.value`` widens).  The backward is the fused one (gcnii_step_back_bf16).
+    ``weight_gradient="recomputed"`` (opt-in): the forward goes through gnx_gcnii_step_drop_bf16, which writes no T; a layer then saves
+    its M and its stored out alone -- 2 bytes per element for an inner layer instead of 6 -- and its dM comes from gnx_gcnii_wgrad_bf16
+    over the rows it gathered (``gcnii_wgrad``).  The run's output, dH, dH0 and the input's gradient keep their bits; every dM agrees
+    to float32 rounding."""
+    recompute = _weight_gradient("gcnii_train_run_bf16", weight_gradient)
     steps = [(H0, float(a), M, bool(relu), _dropout_triple(dropout, "gcnii_train_run_bf16")) for H0, a, M, relu, dropout in steps]
     if not steps:
         raise Exception("gcnii_train_run_bf16: no layers")
@@ -1468,7 +1552,8 @@ def gcnii_train_run_bf16(adj: Adjacency, H: torch.Tensor, steps, stored=None) ->
         raise Exception("gcnii_train_run_bf16: needs f32 rows of width 16, 32 or 64")
     tensors = [t for H0, _, M, _, _ in steps for t in (H0, M)]
     same_H0 = tuple(k > 0 and steps[k][0] is steps[k - 1][0] for k in range(len(steps)))          # layer k shares its H0 tensor with layer k - 1
-    return _GCNIITrainRunBf16.apply(adj, tuple((a, relu, dropout) for _, a, _, relu, dropout in steps), same_H0, stored, H.contiguous(), *tensors)
+    return _GCNIITrainRunBf16.apply(adj, tuple((a, relu, dropout) for _, a, _, relu, dropout in steps), same_H0, stored, recompute,
+                                    H.contiguous(), *tensors)
 
 
 class DeviceIndex:

@@ -61,7 +61,8 @@ const char *gnx_last_error(void);
  * entries (gnx_graph_gather_order, gnx_spmm_dropped_chained_ord, gnx_spmm_dropped_back_ord, GNX_RESERVE_TRAIN_GATHER), likewise, and
  * gnx_gcnii_step_back (the fused backward of the GCNII layer), likewise, and the feature dropout of the GCNII training layer
  * (gnx_gcnii_step_drop, gnx_feature_dropout, gnx_feature_dropout_back), likewise, and the bf16 row storage of GCNII training
- * (gnx_gcnii_step_train_bf16, gnx_feature_dropout_back_bf16, gnx_gcnii_step_back_bf16), likewise. */
+ * (gnx_gcnii_step_train_bf16, gnx_feature_dropout_back_bf16, gnx_gcnii_step_back_bf16), likewise, and the GCNII weight gradient
+ * without stored mixed rows (gnx_gcnii_wgrad, gnx_gcnii_wgrad_bf16, gnx_gcnii_step_drop_bf16, gnx_graph_hub_rows), likewise. */
 #define GNX_ABI_VERSION 900
 int gnx_version(void);
 
@@ -87,6 +88,11 @@ int gnx_graph_destroy(gnx_graph_t g);
 /* Sizes: stored COO entries and coalesced (unique (row, col)) entries. */
 int gnx_graph_info(gnx_graph_t g, int64_t *n_rows, int64_t *n_cols, int64_t *nnz_entries,
                    int64_t *nnz_coalesced);
+/* The hub rows of the matrix (added within ABI 0.9 -- probe for the symbol): how many rows are longer than the handle's long-row
+ * threshold -- the rows the fused launches leave to the long-row kernels, and for which gnx_gcnii_wgrad needs d_hub_rows -- and the
+ * threshold itself (entries; 512, or 128 between 2^15 and 2^20 rows).  Either pointer may be NULL.  A row window
+ * (gnx_graph_set_row_window) re-plans the handle under the same threshold: the count does not change. */
+int gnx_graph_hub_rows(gnx_graph_t g, int64_t *n_hub_rows, int64_t *threshold);
 
 /* Borrowed device pointers to the coalesced CSR (valid until destroy):
  * rowptr int64 [n_rows+1], colidx int32 [nnz_coalesced], raw summed values float32. */
@@ -527,6 +533,42 @@ int gnx_gcnii_step_back_bf16(gnx_graph_t g, const float *d_vals_t, const uint16_
                              const float *d_Mt, int64_t ldmt, float *d_dH, const float *d_S_in, float s_alpha, float *d_S_out,
                              float *d_work, void *stream);
 
+/* The GCNII weight gradient WITHOUT stored mixed rows (training, opt-in; added within ABI 0.9 -- probe for the symbols):
+ *   dM = T^T . G,   T = (1-a) * A_hat . H + a * H0   made again from its operands inside the launch and never written,
+ * so a training layer keeps neither T between its forward and its backward (4 bytes per element and layer) nor writes it in the forward
+ * (gnx_gcnii_step / gnx_gcnii_step_drop with d_mixed == NULL, gnx_gcnii_step_drop_bf16 below), and gnx_dense_wgrad does not read it.
+ * H (the rows the forward gathered: f32, or bf16 for gnx_gcnii_wgrad_bf16, widened exactly), H0 and G (the gated gradient in f32, the
+ * array gnx_dense_wgrad reads) are [n, C] contiguous, dM is [C, C] contiguous f32; d_vals as in gnx_gcnii_step (NULL: the raw values).
+ * Square stand-alone graphs without a diagonal.  C in {16, 32, 64} with the f32 buffers 16-byte and a bf16 d_H 8-byte aligned;
+ * anything else returns GNX_ERR_UNSUPPORTED (naming the width or the alignment), nothing launched: callers keep the stored rows there.
+ * One launch of the forward's shape: a wave makes a 16-row tile of T in LDS with the forward's gather loop, entry order and mix -- the
+ * same device code, so a row of T has the bits gnx_gcnii_step would have stored in d_mixed -- and multiplies T_tile^T . G_tile into its
+ * accumulators on the matrix cores (v_mfma_f32_16x16x4_f32, exact float32: a k-ordered fmaf chain over the tile's row slots), tile after
+ * tile; slots past n contribute nothing, a row without entries a * H0[r].  Hub rows (longer than the handle's threshold:
+ * gnx_graph_hub_rows) go through the long-row chunk kernels first, into d_hub_rows (f32 [n, C], indexed by row id; only the hub rows
+ * are written), where the launch reads their T: one summation structure, no second weight gradient.  d_hub_rows may be NULL exactly
+ * when the handle has no hub rows (GNX_ERR_INVALID naming d_hub_rows otherwise).
+ * d_work: work_floats >= C * C floats, used as min(work_floats / (C * C), 2048, ceil(n / 128)) slabs of one [C, C] partial each -- a
+ * block per slab, eight waves per block; the tile -> wave -> block assignment is a function of (n, C, the number of slabs) alone, never
+ * of the device -- added in slab order into d_dM by the last pass of gnx_dense_wgrad.  No float atomics: two calls with the same
+ * arguments give the same bits; another work_floats gives another summation order.  d_dM, d_work and d_hub_rows are each a buffer of
+ * their own.  The summation order is not gnx_dense_wgrad's over the stored T: the two agree to float32 rounding.
+ * Capture and reserve: as gnx_gcnii_step_bf16 (the long-row slab; nothing else is allocated).
+ * Reports "gcnii_wgrad_mfma" / "gcnii_wgrad_mfma_bf16".
+ *
+ * gnx_gcnii_step_drop_bf16, the forward that goes with gnx_gcnii_wgrad_bf16: gnx_gcnii_step_train_bf16 without d_mixed -- T never
+ * reaches memory except for hub rows, which go through d_work (f32 [n, C], a buffer of its own; may be NULL exactly when the handle has
+ * no hub rows) as in gnx_gcnii_step_bf16.  out has the bits of gnx_gcnii_step_train_bf16's out; its checks, widths and alignments
+ * (GNX_ERR_UNSUPPORTED elsewhere).  Reports "spmm_gcnii_mfma_drop_bf16".  (The f32 side needs no new forward: gnx_gcnii_step and
+ * gnx_gcnii_step_drop take d_mixed == NULL at these widths.) */
+int gnx_gcnii_wgrad(gnx_graph_t g, const float *d_vals, const float *d_H, const float *d_H0, float a, int64_t C,
+                    const float *d_G, float *d_dM, float *d_hub_rows, float *d_work, int64_t work_floats, void *stream);
+int gnx_gcnii_wgrad_bf16(gnx_graph_t g, const float *d_vals, const uint16_t *d_H, const float *d_H0, float a, int64_t C,
+                         const float *d_G, float *d_dM, float *d_hub_rows, float *d_work, int64_t work_floats, void *stream);
+int gnx_gcnii_step_drop_bf16(gnx_graph_t g, const float *d_vals, const uint16_t *d_H, const float *d_H0, float a, int64_t C,
+                             const float *d_M, int64_t ldm, int act, double dropout_p, uint64_t seed, uint64_t stream_id,
+                             void *d_out, int out_bf16, float *d_work, void *stream);
+
 /* ---- the dense ends of the path (matrix cores) -----------------------------------------------------------------------
  * gnx_dense: out = act(X . W + bias) -- Dense.__forward__ (gnntf/core/nn/layers.py:135-136) and the transform of
  * GCNLayer (gcn.py:89).  X [n, F] (ldx), W [F, O] (ldw), bias [O] or NULL, out [n, O] (ldo); float32 in and out, float32
@@ -659,7 +701,9 @@ int gnx_probe_block_xcd(int64_t n_blocks, int32_t *d_xcd_out, void *stream);
  * "spmm_gcnii_back_mfma" (the fused launch, with or without hub rows) or "dense+spmm_back" (the other widths / alignments);
  * gnx_gcnii_step_drop reports "spmm_gcnii_mfma_drop" or "spmm+dense_mfma_drop" likewise (with p == 0 the names of gnx_gcnii_step); the
  * two dropout passes report nothing; gnx_gcnii_step_train_bf16 reports "spmm_gcnii_mfma_train_bf16" and gnx_gcnii_step_back_bf16
- * "spmm_gcnii_back_mfma_bf16" (the fused launches, with or without hub rows: those two entries have no other form). */
+ * "spmm_gcnii_back_mfma_bf16" (the fused launches, with or without hub rows: those two entries have no other form), and so do
+ * gnx_gcnii_step_drop_bf16 ("spmm_gcnii_mfma_drop_bf16"), gnx_gcnii_wgrad ("gcnii_wgrad_mfma") and gnx_gcnii_wgrad_bf16
+ * ("gcnii_wgrad_mfma_bf16"). */
 const char *gnx_graph_last_kernel(gnx_graph_t g);
 
 #ifdef __cplusplus
