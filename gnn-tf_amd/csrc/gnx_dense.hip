@@ -1,9 +1,7 @@
-// The dense ends of the path on gfx950 matrix cores: the pre-MLP transform and the task head.
+// The dense transform on gfx950 matrix cores: the pre-MLP, the Dense layers and the transform of the GCN / GCNII layers.
 //
 //   gnx_dense      out = act(X . W + b)                      reference gnntf/core/nn/layers.py:135-136 (Dense),
 //                                                            gnntf/core/gnn/architectures/gcn.py:89 (the transform of GCNLayer)
-//   gnx_node_ce    mean_i CE(log_softmax(logits[nodes_i]))   reference gnntf/core/gnn/graph_predictor.py:19-25
-//   gnx_node_argmax  argmax(logits[nodes_i])                 reference gnntf/core/gnn/graph_predictor.py:16-17, 27-31
 //
 // gnx_dense is a tall-and-skinny GEMM (N rows in the millions, F and O in the tens to hundreds): float32 in, float32
 // accumulate on v_mfma_f32_16x16x4_f32 (bit-for-bit a k-ordered fmaf chain, no reduced precision).  A 256-thread block owns
@@ -13,22 +11,15 @@
 // of a wave read disjoint banks).  Arithmetic intensity is O/2 flop per byte of X: HBM-bound up to O = 32, MFMA-bound beyond.
 // Tall inputs (n >= 16K rows) take one of two persistent kernels instead: k_dense_wreg (W in registers, shapes up to 256 x 64) or
 // k_dense_ring (W in LDS); both stream X through per-wave LDS-DMA rings and add the k terms in the same order as this kernel.
-// gnx_dense_wgrad: k_wgrad_acc (accumulators stationary, tall inputs) or k_wgrad_mfma.
+// Which of the three a column panel takes: dense_kernel_for.  (The weight gradient: gnx_dense_wgrad.hip; the task heads: gnx_heads.hip.)
 // Tried and dropped (round 2): a persistent W-resident variant (W once in LDS, the whole K extent of a 16-row tile in
 // registers, next tile prefetched, no barrier in the loop) -- 5.1 ms vs 4.2 ms at 10M x 256 -> 64: with two waves per SIMD the
 // 64-byte-per-row A loads no longer hide (a 256 -> 7 product ran at 3.2 TB/s); the chunked kernel's eight blocks per CU do.
-#include <stdlib.h>
-#include <algorithm>
-#include <type_traits>
-
-#include "gnx_internal.h"
 #include <mutex>
 
-using namespace gnx;
+#include "gnx_dense_device.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct DenseArgs {
     const float *X; int64_t ldx; int64_t n; int F;
@@ -145,6 +136,12 @@ __global__ __launch_bounds__(64 * DENSE_WAVES) void k_dense_mfma(const DenseArgs
 // order as k_dense_mfma: same bits.
 constexpr int RING_BK = 64;            // floats of one row per stage
 
+// One stage of either ring is 16 rows x 64 floats, the 16-byte pieces of a row XOR-swizzled by the row index on the source address.
+// Read back by lane (c, g): the A fragment X[row c][16 T + 4 g .. + 3] of the stage at A, one conflict-free ds_read_b128.
+__device__ __forceinline__ f32x4 stage_fragment(const float *A, int c, int g, int T) {
+    return *reinterpret_cast<const f32x4 *>(A + c * RING_BK + 4 * ((4 * T + g) ^ c));
+}
+
 template <int NT, int WAVES, int RING>
 __global__ __launch_bounds__(64 * WAVES) void k_dense_ring(const DenseArgs p, int64_t n_tiles) {
     static_assert(NT % 4 == 0, "the W image groups the accumulator columns in fours");
@@ -213,7 +210,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_dense_ring(const DenseArgs p, in
                 // them: the wave hides its own LDS latency instead of waiting for every fragment it has just asked for
                 f32x4 a4[RING_BK / 16];
 #pragma unroll
-                for (int T = 0; T < RING_BK / 16; ++T) a4[T] = *reinterpret_cast<const f32x4 *>(A + c * RING_BK + 4 * ((4 * T + g) ^ c));
+                for (int T = 0; T < RING_BK / 16; ++T) a4[T] = stage_fragment(A, c, g, T);
                 const float *__restrict__ Wk = Wl + ((kc * RING_BK + 4 * g) * NQ) * 64 + c * 4;      // fragment of k = kc 64 + 4 g (+ 16 T + t)
                 f32x4 b[2][NQ];
 #pragma unroll
@@ -244,7 +241,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_dense_ring(const DenseArgs p, in
                 // wide outputs (O = 192 / 256): sixteen accumulator tiles leave no room for fragments in flight (measured: +5 % with them)
 #pragma unroll
                 for (int T = 0; T < RING_BK / 16; ++T) {
-                    const f32x4 a4 = *reinterpret_cast<const f32x4 *>(A + c * RING_BK + 4 * ((4 * T + g) ^ c));
+                    const f32x4 a4 = stage_fragment(A, c, g, T);
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
                         const int k = kc * RING_BK + 16 * T + 4 * g + t;
@@ -275,25 +272,12 @@ __global__ __launch_bounds__(64 * WAVES) void k_dense_ring(const DenseArgs p, in
     }
 }
 
-// the ring kernel takes: whole float4 rows of X, F a multiple of 64, W image of at most 64 KB, accumulator columns in groups of four
-bool ring_eligible(const DenseArgs &p, bool x_aligned, int nt) {
-    return x_aligned && p.in_rows == nullptr && p.out_rows == nullptr && p.F % RING_BK == 0 && nt % 4 == 0 && (int64_t)p.F * nt * 16 * 4 <= (64 << 10) &&
-           p.n >= 16 * 1024;
-}
-
 template <int NT, int WAVES, int RING>
 int launch_ring_as(const DenseArgs &p, hipStream_t s) {
     const size_t lds_bytes = ((size_t)p.F * NT * 16 + (size_t)WAVES * RING * 16 * RING_BK) * sizeof(float);
-    static PerDeviceOnce configured;
-    const int attr_dev = PerDeviceOnce::device();
-    if (configured.need(attr_dev)) {
-        GNX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dense_ring<NT, WAVES, RING>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10));
-        configured.set(attr_dev);
-    }
+    const int cus = persistent_launch<k_dense_ring<NT, WAVES, RING>>();
+    if (cus < 0) return cus;
     const int64_t n_tiles = (p.n + 15) / 16;
-    int cus = 256;
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const unsigned grid = (unsigned)std::min<int64_t>((n_tiles + WAVES - 1) / WAVES, cus);
     hipLaunchKernelGGL((k_dense_ring<NT, WAVES, RING>), dim3(grid), dim3(64 * WAVES), lds_bytes, s, p, n_tiles);
     return GNX_OK;
@@ -303,7 +287,7 @@ int launch_ring_as(const DenseArgs &p, hipStream_t s) {
 // 10M x 256 -> 64: 4 waves x 4 stages 4.14 ms, 8 x 2 3.54, 8 x 3 3.61, 12 x 2 3.41 (k_dense_mfma: 3.59); the matrix pipe wants
 // three waves per SIMD more than it wants a deeper ring.
 template <int NT>
-int launch_ring(const DenseArgs &p, hipStream_t s) {
+int launch_ring(const DenseArgs &p, bool, hipStream_t s) {
     const size_t w_bytes = (size_t)p.F * NT * 16 * sizeof(float);
     const size_t rings = ((160u << 10) - w_bytes) / (2 * 16 * RING_BK * sizeof(float));
     if (rings >= 16) return launch_ring_as<NT, 16, 2>(p, s);
@@ -383,7 +367,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     auto fragments = [&](int slot, f32x4 (&a)[4]) {               // X[row c][16 T + 4 g .. + 3] of the stage in `slot`
         const float *__restrict__ A = ring + slot * STAGE;
 #pragma unroll
-        for (int T = 0; T < 4; ++T) a[T] = *reinterpret_cast<const f32x4 *>(A + c * RING_BK + 4 * ((4 * T + g) ^ c));
+        for (int T = 0; T < 4; ++T) a[T] = stage_fragment(A, c, g, T);
     };
     // D layout with W as the A operand: lane (c, g), register r -> row c, column 16 nt + 4 g + r
     auto finish = [&](const f32x4 &acc, int nt) {
@@ -394,20 +378,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }
         return v;
     };
-    auto store_tile = [&](f32x4 (&acc)[NT], uint32_t tile) {      // a full tile: no guards
-        char *o = Ob + (uint64_t)(tile * 16u + c) * o_pitch + 16u * g;
+    auto store_row = [&](f32x4 (&acc)[NT], uint32_t row) {
+        char *o = Ob + (uint64_t)row * o_pitch + 16u * g;
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
             if (!PAD || 16 * nt + 4 * g < p.O) *reinterpret_cast<f32x4 *>(o + 64 * nt) = finish(acc[nt], nt);
     };
+    auto store_tile = [&](f32x4 (&acc)[NT], uint32_t tile) { store_row(acc, tile * 16u + c); };      // a full tile: no guards
     auto store_last = [&](f32x4 (&acc)[NT], uint32_t tile) {      // the wave's last tile: may be the ragged one
-        const uint32_t row = tile * 16u + c;
-        if (row < n_rows) {
-            char *o = Ob + (uint64_t)row * o_pitch + 16u * g;
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                if (!PAD || 16 * nt + 4 * g < p.O) *reinterpret_cast<f32x4 *>(o + 64 * nt) = finish(acc[nt], nt);
-        }
+        if (tile * 16u + c < n_rows) store_row(acc, tile * 16u + c);
     };
     f32x4 afrag[2][4];                                            // the X fragments of the stage being multiplied and of the next one
     // one tile: KS stages; `slot0` is the ring slot of its first stage (compile-time).  With EPI, the stores of the wave's previous tile
@@ -466,13 +445,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // nothing of this wave may still be writing LDS when the block retires
 }
 
-// registers for W: 16 KS x NT fragments per lane (F <= 64 KS, O <= 16 NT), at most 256 of the wave's 512; widths multiples of 4
-bool wreg_eligible(const DenseArgs &p, bool x_aligned) {
-    const bool out_aligned = reinterpret_cast<uintptr_t>(p.out) % 16 == 0 && p.ldo % 4 == 0;
-    return x_aligned && out_aligned && p.in_rows == nullptr && p.out_rows == nullptr && p.F % 4 == 0 && p.O % 4 == 0 && p.F > 64 && p.F <= 256 &&
-           p.n >= 16 * 1024 && p.n < (1ll << 31) && p.ldx < (1ll << 30) && p.ldo < (1ll << 30);
-}
-
 // a block of zeros on the CURRENT device (one per device the process drives; never freed)
 const float *device_zeros() {
     static std::mutex lock;
@@ -492,24 +464,16 @@ const float *device_zeros() {
 template <int NT, int KS, int RING, bool RELU, bool PAD>
 int launch_wreg_as(const DenseArgs &p, hipStream_t s) {
     const size_t lds_bytes = (size_t)4 * RING * 16 * RING_BK * sizeof(float);
-    static PerDeviceOnce configured;
-    const int attr_dev = PerDeviceOnce::device();
-    if (configured.need(attr_dev)) {
-        GNX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dense_wreg<NT, KS, RING, RELU, PAD>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10));
-        configured.set(attr_dev);
-    }
+    const int cus = persistent_launch<k_dense_wreg<NT, KS, RING, RELU, PAD>>();
+    if (cus < 0) return cus;
     const int64_t n_tiles = (p.n + 15) / 16;
-    int cus = 256;
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const unsigned grid = (unsigned)std::min<int64_t>((n_tiles + 3) / 4, cus);
     hipLaunchKernelGGL((k_dense_wreg<NT, KS, RING, RELU, PAD>), dim3(grid), dim3(256), lds_bytes, s, p, n_tiles);
     return GNX_OK;
 }
 
 template <int NT, int KS, int RING>
-int launch_wreg(const DenseArgs &p0, hipStream_t s) {
+int launch_wreg(const DenseArgs &p0, bool, hipStream_t s) {
     DenseArgs p = p0;
     const bool pad = p.F != 64 * KS || p.O != 16 * NT;
     if (pad) {
@@ -521,523 +485,67 @@ int launch_wreg(const DenseArgs &p0, hipStream_t s) {
 }
 
 template <int NT>
-void launch_dense(const DenseArgs &p, bool aligned, hipStream_t s) {
+int launch_dense(const DenseArgs &p, bool aligned, hipStream_t s) {
     const unsigned grid = (unsigned)((p.n + 16 * DENSE_WAVES - 1) / (16 * DENSE_WAVES));
     if (aligned) hipLaunchKernelGGL((k_dense_mfma<NT, true>), dim3(grid), dim3(64 * DENSE_WAVES), 0, s, p);
     else         hipLaunchKernelGGL((k_dense_mfma<NT, false>), dim3(grid), dim3(64 * DENSE_WAVES), 0, s, p);
-}
-
-// ---- weight gradient of the dense layer: dW[F, O] = X^T . G, a reduction over the N rows ------------------------------------
-// M = F, N = O, K = rows.  grid.x = row slabs, grid.y = panels of 256 features, grid.z = panels of 16 NT outputs.  A block
-// stages 32-row tiles of X (its 256 features) and G (its outputs) in LDS with coalesced 16-byte loads; wave w owns features
-// [64 w, 64 w + 64) of the panel as 4 x NT accumulator tiles: A[m = feature][k = row] and B[k = row][n = output] fragments are
-// read from LDS (row stride = 16 mod 32 banks, so the two k-groups of a half-wave hit disjoint banks).  Every slab writes its
-// partial dW; a second kernel adds the slabs in order (fixed order: reproducible, no float atomics).
-template <int NT>
-__global__ __launch_bounds__(256) void k_wgrad_mfma(const float *__restrict__ X, int64_t ldx, const float *__restrict__ G, int64_t ldg,
-                                                     int64_t n, int F, int O, int64_t rows_per_slab, bool aligned,
-                                                     float *__restrict__ partial) {
-    constexpr int R = 32, XS = 256 + 16, GS = 16 * NT + 16;
-    __shared__ float Xs[R * XS];
-    __shared__ float Gs[R * GS];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = lane & 15, g = lane >> 4;
-    const int f0 = blockIdx.y * 256, o0 = blockIdx.z * 16 * NT;
-    const int64_t r_beg = (int64_t)blockIdx.x * rows_per_slab;
-    const int64_t r_end = r_beg + rows_per_slab < n ? r_beg + rows_per_slab : n;
-    f32x4 acc[4][NT];
-#pragma unroll
-    for (int ft = 0; ft < 4; ++ft)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[ft][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int64_t r0 = r_beg; r0 < r_end; r0 += R) {
-        __syncthreads();
-        for (int idx = threadIdx.x; idx < R * 64; idx += 256) {                 // X tile: 32 rows x 256 features
-            const int rr = idx / 64, cc = (idx % 64) * 4;
-            const int64_t row = r0 + rr;
-            f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (row < r_end) {
-                const float *__restrict__ src = X + row * ldx + f0 + cc;
-                if (aligned && f0 + cc + 3 < F) v = *reinterpret_cast<const f32x4 *>(src);
-                else {
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) if (f0 + cc + t < F) v[t] = src[t];
-                }
-            }
-            *reinterpret_cast<f32x4 *>(Xs + rr * XS + cc) = v;
-        }
-        for (int idx = threadIdx.x; idx < R * 4 * NT; idx += 256) {             // G tile: 32 rows x 16 NT outputs
-            const int rr = idx / (4 * NT), cc = (idx % (4 * NT)) * 4;
-            const int64_t row = r0 + rr;
-            f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (row < r_end) {
-                const float *__restrict__ src = G + row * ldg + o0 + cc;
-                if (aligned && o0 + cc + 3 < O) v = *reinterpret_cast<const f32x4 *>(src);
-                else {
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) if (o0 + cc + t < O) v[t] = src[t];
-                }
-            }
-            *reinterpret_cast<f32x4 *>(Gs + rr * GS + cc) = v;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < R / 4; ++kk) {
-            const float *__restrict__ xrow = Xs + (4 * kk + g) * XS + 64 * wave + c;
-            const float *__restrict__ grow = Gs + (4 * kk + g) * GS + c;
-            float b[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) b[nt] = grow[16 * nt];
-#pragma unroll
-            for (int ft = 0; ft < 4; ++ft) {
-                const float a = xrow[16 * ft];
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[ft][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b[nt], acc[ft][nt], 0, 0, 0);
-            }
-        }
-    }
-    float *__restrict__ out = partial + (int64_t)blockIdx.x * F * O;
-#pragma unroll
-    for (int ft = 0; ft < 4; ++ft)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int o = o0 + 16 * nt + c;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int f = f0 + 64 * wave + 16 * ft + 4 * g + r;
-                if (f < F && o < O) out[(int64_t)f * O + o] = acc[ft][nt][r];
-            }
-        }
-}
-
-// ---- the same gradient with the ACCUMULATORS stationary: every wave keeps a whole F x O partial in its registers --------------------
-// For F x O <= 16384 (256 x 64, 128 x 128, 64 x 64, ...: the layers of the path) one wave's 512 registers hold the complete result,
-// (F / 16) x (O / 16) accumulator tiles (wider layers: one panel of at most 128 outputs x 16384 / 128 features per wave, every slab of
-// rows walked once per panel; widths that are not 32 / 64 / 128 / 256 are padded inside the LDS image only).  A wave then needs
-// nobody: it owns a slab of rows, streams X[rows, :] and G[rows, :] through a
-// private LDS ring by LDS-DMA (whole lines, no VGPR staging, RING - 1 stages in flight behind a counted s_waitcnt vmcnt), and per 4 rows
-// reads F / 16 + O / 16 single-word fragments for (F / 16) (O / 16) MFMAs -- no barrier anywhere, nothing recomputed, and shapes narrower
-// than k_wgrad_mfma's 256-feature panel waste nothing.  The LDS image is lane-linear (an LDS-DMA cannot scatter), so the 16-byte pieces
-// of ODD rows are swapped in groups of four (piece ^ 4) on the source address: a half-wave's fragment read -- 2 rows x 16 consecutive
-// words -- then covers all 32 banks once.  G is the MFMA's A operand: a lane ends up with four consecutive outputs of one feature row
-// (16-byte stores of the partial).  The partials of the waves are added in wave order by k_sum_slabs (fixed order: reproducible).
-template <int MT, int NT> struct WgradAcc {
-    static constexpr int F = 16 * MT, O = 16 * NT, R = 8;                 // rows per stage
-    static constexpr int XI = R * F / 256, GI = R * O / 256, NI = XI + GI; // LDS-DMA instructions per stage
-    static constexpr int STAGE = R * (F + O);                             // floats
-    static constexpr int RING_FIT = (36 << 10) / (STAGE * 4);
-    static constexpr int RING = RING_FIT > 8 ? 8 : (RING_FIT < 2 ? 2 : RING_FIT);
-    static_assert(NI * (RING - 1) <= 63, "vmcnt is a 6-bit counter");
-    static_assert(MT * NT <= 64, "the accumulators must fit the register file");
-};
-
-template <int MT, int NT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void k_wgrad_acc(const float *__restrict__ X, uint32_t x_pitch, int f_all, const float *__restrict__ G, uint32_t g_pitch, int o_all, uint32_t n,
-                 uint32_t rows_per_wave, uint32_t f_panels, uint32_t panels, float *__restrict__ partial) {
-    using Cfg = WgradAcc<MT, NT>;
-    // F x O: the PANEL this wave accumulates (padded to whole 16-column tiles of a power-of-two count).  Columns past the real widths
-    // stage a piece that exists (piece 0 of the row) and feed only accumulator cells that are never stored.
-    // Block -> (row slabs, panel): the panels of one group of slabs are 8 blocks apart, i.e. dispatched together AND on the same XCD
-    // (blocks go round the 8 XCDs), so the rows of G that every panel reads again come out of that XCD's L2.
-    constexpr int F = Cfg::F, O = Cfg::O, R = Cfg::R, RING = Cfg::RING, STAGE = Cfg::STAGE;
-    const uint32_t bgroup = blockIdx.x / (8 * panels), brem = blockIdx.x % (8 * panels);
-    const uint32_t slab_block = bgroup * 8 + brem % 8;
-    const int f0 = (int)((brem / 8) % f_panels) * F, o0 = (int)((brem / 8) / f_panels) * O;       // panels = feature panels x output panels
-    const uint32_t f_pieces = (uint32_t)((f_all - f0 < F ? f_all - f0 : F) / 4), o_pieces = (uint32_t)((o_all - o0 < O ? o_all - o0 : O) / 4);
-    X += f0;
-    G += o0;
-    extern __shared__ float lds[];                                // [4 waves][RING][STAGE: R rows of X | R rows of G]
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int c = lane & 15, g = lane >> 4;
-    const uint32_t wid = slab_block * 4 + wave;
-    const uint32_t r_beg = wid * rows_per_wave;
-    if (r_beg >= n) return;                                       // (whole waves; there is no barrier in this kernel)
-    const uint32_t r_end = r_beg + rows_per_wave < n ? r_beg + rows_per_wave : n;
-    const uint32_t n_stages = (r_end - r_beg + R - 1) / R;
-    float *__restrict__ ring = lds + wave * (RING * STAGE);
-    const char *__restrict__ Xb = reinterpret_cast<const char *>(X);
-    const char *__restrict__ Gb = reinterpret_cast<const char *>(G);
-
-    // staging: instruction i of the X part fills slots 64 i .. 64 i + 63 of the stage's X image (slot = 16-byte piece, F / 4 per row)
-    uint32_t pf = 0, pf_slot = 0;
-    auto issue_next = [&]() {
-        const uint32_t row0 = r_beg + (pf < n_stages ? pf : n_stages - 1) * R;      // past the slab: the last stage again, which nobody reads
-        float *dst = ring + pf_slot * STAGE;
-#pragma unroll
-        for (int i = 0; i < Cfg::XI; ++i) {
-            const uint32_t q = 64 * i + lane, r = q / (F / 4);
-            uint32_t piece = (q % (F / 4)) ^ (4 * (r & 1));
-            piece = piece < f_pieces ? piece : 0;
-            uint32_t row = row0 + r;
-            row = row < n ? row : n - 1;                          // rows past the end read a valid row; their fragments are zeroed
-            __builtin_amdgcn_global_load_lds(reinterpret_cast<const float *>(Xb + (uint64_t)row * x_pitch + 16 * piece), dst + i * 256, 16, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < Cfg::GI; ++i) {
-            const uint32_t q = 64 * i + lane, r = q / (O / 4);
-            uint32_t piece = (q % (O / 4)) ^ (4 * (r & 1));
-            piece = piece < o_pieces ? piece : 0;
-            uint32_t row = row0 + r;
-            row = row < n ? row : n - 1;
-            __builtin_amdgcn_global_load_lds(reinterpret_cast<const float *>(Gb + (uint64_t)row * g_pitch + 16 * piece), dst + R * F + i * 256, 16, 0, 0);
-        }
-        ++pf;
-        pf_slot = pf_slot + 1 == RING ? 0 : pf_slot + 1;
-    };
-    // fragments of k step s (rows 4 s + g): word 16 t + c of the row sits in piece group t ^ (g & 1)
-    const int flip = g & 1;
-    const int x_lane = g * F + c, g_lane = g * O + c;
-    f32x4 acc[MT][NT];
-#pragma unroll
-    for (int ft = 0; ft < MT; ++ft)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[ft][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto multiply = [&](auto masked, uint32_t slot, uint32_t valid_rows) {
-        const float *__restrict__ Xs = ring + slot * STAGE + x_lane;
-        const float *__restrict__ Gs = ring + slot * STAGE + R * F + g_lane;
-#pragma unroll
-        for (int s = 0; s < R / 4; ++s) {
-            float a[MT], b[NT];
-#pragma unroll
-            for (int ft = 0; ft < MT; ++ft) a[ft] = Xs[4 * s * F + 16 * (ft ^ flip)];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) b[nt] = Gs[4 * s * O + 16 * (nt ^ flip)];
-            if constexpr (decltype(masked)::value) {
-                if ((uint32_t)(4 * s + g) >= valid_rows) {        // 0 x 0: a row past the slab adds nothing, whatever the row that was read holds
-#pragma unroll
-                    for (int ft = 0; ft < MT; ++ft) a[ft] = 0.f;
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) b[nt] = 0.f;
-                }
-            }
-#pragma unroll
-            for (int ft = 0; ft < MT; ++ft)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[ft][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[nt], a[ft], acc[ft][nt], 0, 0, 0);
-        }
-    };
-#pragma unroll
-    for (int s0 = 0; s0 < RING - 1; ++s0) issue_next();
-    uint32_t slot = 0;
-    for (uint32_t st = 0; st + 1 < n_stages; ++st) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // the fragments of the stage whose slot is restaged next have been read
-        issue_next();
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(Cfg::NI * (RING - 1)) : "memory");    // all but the youngest RING - 1 stages: stage st has landed
-        multiply(std::false_type{}, slot, R);
-        slot = slot + 1 == RING ? 0 : slot + 1;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // (also: nothing of this wave may still be writing LDS when it retires)
-    multiply(std::true_type{}, slot, r_end - (r_beg + (n_stages - 1) * R));
-    // D layout with G as the A operand: lane (c, g), register r -> feature 16 ft + c, output 16 nt + 4 g + r
-    float *__restrict__ out = partial + (uint64_t)wid * ((uint32_t)f_all * (uint32_t)o_all) + (uint32_t)f0 * (uint32_t)o_all + o0;
-#pragma unroll
-    for (int ft = 0; ft < MT; ++ft)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-            if (f0 + 16 * ft + c < f_all && o0 + 16 * nt + 4 * g < o_all)
-                *reinterpret_cast<f32x4 *>(out + (16 * ft + c) * o_all + 16 * nt + 4 * g) = acc[ft][nt];
-}
-
-template <int MT, int NT>
-int launch_wgrad_acc(const float *X, int64_t ldx, int64_t F, const float *G, int64_t ldg, int64_t O, int64_t n, float *work, int64_t max_slabs,
-                     int64_t *n_slabs, hipStream_t s) {
-    using Cfg = WgradAcc<MT, NT>;
-    const size_t lds_bytes = (size_t)4 * Cfg::RING * Cfg::STAGE * sizeof(float);
-    static PerDeviceOnce configured;
-    const int attr_dev = PerDeviceOnce::device();
-    if (configured.need(attr_dev)) {
-        GNX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_wgrad_acc<MT, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10));
-        configured.set(attr_dev);
-    }
-    int cus = 256;
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const int64_t f_panels = (F + Cfg::F - 1) / Cfg::F, panels = f_panels * ((O + Cfg::O - 1) / Cfg::O);
-    int64_t waves = std::min<int64_t>(std::max<int64_t>((int64_t)cus * 4 / panels, 64), max_slabs);        // row slabs; every slab is walked once per panel
-    int64_t rows_per_wave = (n + waves - 1) / waves;
-    rows_per_wave = std::max<int64_t>((rows_per_wave + Cfg::R - 1) / Cfg::R * Cfg::R, 8 * Cfg::R);
-    waves = (n + rows_per_wave - 1) / rows_per_wave;
-    const int64_t slab_blocks = (waves + 3) / 4, grid = (slab_blocks + 7) / 8 * 8 * panels;
-    hipLaunchKernelGGL((k_wgrad_acc<MT, NT>), dim3((unsigned)grid), dim3(256), lds_bytes, s, X, (uint32_t)(ldx * 4), (int)F, G, (uint32_t)(ldg * 4), (int)O,
-                       (uint32_t)n, (uint32_t)rows_per_wave, (uint32_t)f_panels, (uint32_t)panels, work);
-    *n_slabs = waves;
     return GNX_OK;
 }
 
-// Whole aligned rows, F and O multiples of 4: the result is cut into panels of FP features x OP outputs, FP x OP <= 16384, each of which
-// one wave holds (OP = 32 / 64 / 128 >= O where that exists; FP = 16384 / OP, at most 256, narrower for narrow inputs); widths that
-// are not a power of two are padded inside the LDS image.  Returns < 0 when the shape is not taken.
-int wgrad_acc_dispatch(const float *X, int64_t ldx, const float *G, int64_t ldg, int64_t n, int64_t F, int64_t O, bool aligned, float *work,
-                       int64_t max_slabs, int64_t *n_slabs, hipStream_t s) {
-    if (!aligned || n < 16 * 1024 || n >= (1ll << 31) || ldx >= (1ll << 30) || ldg >= (1ll << 30) || F % 4 || O % 4 || F * O >= (1ll << 31) || max_slabs < 64)
-        return -1;
-    const int op = O <= 32 ? 32 : O <= 64 ? 64 : 128;
-    int fp = std::min(16384 / op, 256);
-    while (fp > 32 && fp / 2 >= F) fp /= 2;                                   // a narrow input does not need the widest panel
-    const int64_t panels = ((F + fp - 1) / fp) * ((O + op - 1) / op);
-    if (panels > 64) return -1;                                                // (very wide layers: every slab would be walked too often)
-#define GNX_WGRAD_ACC(MT_, NT_) if (fp == 16 * MT_ && op == 16 * NT_) return launch_wgrad_acc<MT_, NT_>(X, ldx, F, G, ldg, O, n, work, max_slabs, n_slabs, s)
-    GNX_WGRAD_ACC(2, 2); GNX_WGRAD_ACC(2, 4); GNX_WGRAD_ACC(2, 8);
-    GNX_WGRAD_ACC(4, 2); GNX_WGRAD_ACC(4, 4); GNX_WGRAD_ACC(4, 8);
-    GNX_WGRAD_ACC(8, 2); GNX_WGRAD_ACC(8, 4); GNX_WGRAD_ACC(8, 8);
-    GNX_WGRAD_ACC(16, 2); GNX_WGRAD_ACC(16, 4);
-#undef GNX_WGRAD_ACC
-    return -1;
-}
+// Which kernel, with which template arguments, a column panel takes (p: the panel, at most 256 outputs, nt = its 16-column accumulator
+// tiles; x_aligned: X in whole float4 rows, i.e. a 16-byte base and ldx % 4 == 0).  The rules, in this order:
+//   tall = x_aligned, no row maps, n >= 16K rows: what both persistent kernels need.
+//   1. k_dense_wreg<NT, KS, RING>: tall; n < 2^31 and ldx, ldo < 2^30 (it addresses by 32-bit row x byte pitch); out in whole float4 rows
+//      (16-byte base, ldo % 4 == 0); F and O multiples of 4; and W within 256 registers per lane once padded to 64 KS x 16 NT:
+//        128 < F <= 256:   O <= 32 -> <2, 4, 8>    O <= 64 -> <4, 4, 8>     wider: not this kernel
+//         64 < F <= 128:   O <= 64 -> <4, 2, 4>    O <= 128 -> <8, 2, 4>    wider: not this kernel
+//   2. k_dense_ring<NT = nt>: tall; F a multiple of 64; nt a multiple of 4 (accumulator columns go in groups of four); the W image of
+//      F x 16 nt floats within 64 KB.
+//   3. k_dense_mfma<NT, ALIGNED = x_aligned>: every other panel, row maps included; NT = nt rounded up to one of 1 2 3 4 6 8 12 16.
+// The alignment of W decides nothing here: p.w_aligned only picks how k_dense_mfma loads W; the other two load it once, by the word.
+// (tuning builds: GNX_DENSE_WREG=0 skips rule 1, GNX_DENSE_RING=0 rule 2, for A/B runs)
+typedef int (*DenseLaunch)(const DenseArgs &p, bool x_aligned, hipStream_t s);
 
-// slabs [group * per, min(group * per + per, n_slabs)) added in order into out[group]: the first level of a two-level sum whose second
-// level is k_sum_slabs over the groups (fixed association: reproducible); blockIdx.y = group
-__global__ void k_sum_slab_groups(const float *__restrict__ partial, int64_t n_slabs, int64_t per, int64_t elems, float *__restrict__ out) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= elems) return;
-    const int64_t s0 = (int64_t)blockIdx.y * per, s1 = s0 + per < n_slabs ? s0 + per : n_slabs;
-    float acc = 0.f;
-    for (int64_t s = s0; s < s1; ++s) acc += partial[s * elems + e];
-    out[(int64_t)blockIdx.y * elems + e] = acc;
-}
-
-__global__ void k_sum_slabs(const float *__restrict__ partial, int64_t n_slabs, int64_t elems, float *__restrict__ out) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= elems) return;
-    float acc = 0.f;
-    for (int64_t s = 0; s < n_slabs; ++s) acc += partial[s * elems + e];      // slab order
-    out[e] = acc;
-}
-
-// ---- task head -----------------------------------------------------------------------------------------------------------
-// One 16-lane group per listed node: gather the row, max, sum of exponentials, loss_i = logsumexp - x[label]
-// (graph_predictor.py:24-25: CE-from-logits applied to log_softmax(x); softmax(log_softmax(x)) = softmax(x), so this IS the
-// plain cross entropy).  Fixed reduction trees: bitwise reproducible.
-__device__ __forceinline__ float group16_max(float v) {
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-__device__ __forceinline__ float group16_sum(float v) {
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__global__ __launch_bounds__(256) void k_node_ce_fwd(const float *__restrict__ logits, int64_t ldl, int C, int64_t n_rows,
-                                                      const int64_t *__restrict__ nodes, const int64_t *__restrict__ labels, int64_t m,
-                                                      float *__restrict__ loss) {
-    const int sub = threadIdx.x & 15;
-    const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-    if (i >= m) return;
-    const int64_t node = nodes[i], label = labels[i];
-    if (node < 0 || node >= n_rows || label < 0 || label >= C) {      // never read out of bounds: the loss of such an item is NaN
-        if (sub == 0) loss[i] = NAN;
-        return;
+DenseLaunch dense_kernel_for(const DenseArgs &p, bool x_aligned) {
+    const int nt = (p.O + 15) / 16;
+    const bool tall = x_aligned && p.in_rows == nullptr && p.out_rows == nullptr && p.n >= 16 * 1024;
+    const bool out_aligned = aligned(p.out, 16) && p.ldo % 4 == 0;
+    if (tall && tuning_switch("GNX_DENSE_WREG") && out_aligned && p.F % 4 == 0 && p.O % 4 == 0 && p.n < (1ll << 31) && p.ldx < (1ll << 30) &&
+        p.ldo < (1ll << 30)) {
+        if (p.F > 128 && p.F <= 256) {
+            if (p.O <= 32) return launch_wreg<2, 4, 8>;
+            if (p.O <= 64) return launch_wreg<4, 4, 8>;
+        } else if (p.F > 64 && p.F <= 128) {
+            if (p.O <= 64) return launch_wreg<4, 2, 4>;
+            if (p.O <= 128) return launch_wreg<8, 2, 4>;
+        }
     }
-    const float *__restrict__ x = logits + node * ldl;
-    float mx = -INFINITY;
-    for (int c = sub; c < C; c += 16) mx = fmaxf(mx, x[c]);
-    mx = group16_max(mx);
-    float se = 0.f;
-    for (int c = sub; c < C; c += 16) se += expf(x[c] - mx);
-    se = group16_sum(se);
-    if (sub == 0) loss[i] = (logf(se) + mx) - x[label];
+    if (tall && tuning_switch("GNX_DENSE_RING") && p.F % RING_BK == 0 && nt % 4 == 0 && (int64_t)p.F * nt * 16 * 4 <= (64 << 10))
+        return nt == 4 ? launch_ring<4> : nt == 8 ? launch_ring<8> : nt == 12 ? launch_ring<12> : launch_ring<16>;
+    return nt <= 1 ? launch_dense<1> : nt <= 2 ? launch_dense<2> : nt <= 3 ? launch_dense<3> : nt <= 4 ? launch_dense<4> :
+           nt <= 6 ? launch_dense<6> : nt <= 8 ? launch_dense<8> : nt <= 12 ? launch_dense<12> : launch_dense<16>;
 }
-
-// d logits[node_i, :] += scale * (softmax(x) - onehot(label)); atomics because a node may be listed twice
-__global__ __launch_bounds__(256) void k_node_ce_bwd(const float *__restrict__ logits, int64_t ldl, int C, int64_t n_rows,
-                                                      const int64_t *__restrict__ nodes, const int64_t *__restrict__ labels, int64_t m,
-                                                      const float *__restrict__ gout, float inv_m, float *__restrict__ grad, int64_t ldg) {
-    const int sub = threadIdx.x & 15;
-    const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-    if (i >= m) return;
-    const int64_t node = nodes[i], label = labels[i];
-    if (node < 0 || node >= n_rows || label < 0 || label >= C) return;
-    const float *__restrict__ x = logits + node * ldl;
-    float mx = -INFINITY;
-    for (int c = sub; c < C; c += 16) mx = fmaxf(mx, x[c]);
-    mx = group16_max(mx);
-    float se = 0.f;
-    for (int c = sub; c < C; c += 16) se += expf(x[c] - mx);
-    se = group16_sum(se);
-    const float scale = gout[0] * inv_m, inv = 1.0f / se;
-    for (int c = sub; c < C; c += 16) {
-        const float pr = expf(x[c] - mx) * inv;
-        atomicAdd(grad + node * ldg + c, scale * (pr - (c == label ? 1.0f : 0.0f)));
-    }
-}
-
-// mean of m values in a fixed order: MEAN_BLOCKS blocks each reduce a contiguous slice (strided partial sums + a fixed LDS
-// tree) into partial[block]; one block then adds the partials in the same way and divides
-constexpr int MEAN_BLOCKS = 256;
-__global__ __launch_bounds__(256) void k_mean_partial(const float *__restrict__ v, int64_t m, float *__restrict__ partial) {
-    __shared__ float red[256];
-    const int64_t per = (m + MEAN_BLOCKS - 1) / MEAN_BLOCKS;
-    const int64_t b = (int64_t)blockIdx.x * per, e = b + per < m ? b + per : m;
-    float acc = 0.f;
-    for (int64_t i = b + threadIdx.x; i < e; i += 256) acc += v[i];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
-
-__global__ __launch_bounds__(256) void k_mean(const float *__restrict__ v, int64_t n_partial, int64_t m, float *__restrict__ out) {
-    __shared__ float red[256];
-    float acc = 0.f;
-    for (int64_t i = threadIdx.x; i < n_partial; i += 256) acc += v[i];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = red[0] / (float)m;
-}
-
-// first index of the row maximum (tf.argmax / np.argmax tie rule)
-__global__ __launch_bounds__(256) void k_node_argmax(const float *__restrict__ logits, int64_t ldl, int C, int64_t n_rows,
-                                                      const int64_t *__restrict__ nodes, int64_t m, int64_t *__restrict__ out) {
-    const int sub = threadIdx.x & 15;
-    const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-    if (i >= m) return;
-    const int64_t node = nodes ? nodes[i] : i;
-    if (node < 0 || node >= n_rows) {                                   // out of range: -1
-        if (sub == 0) out[i] = -1;
-        return;
-    }
-    const float *__restrict__ x = logits + node * ldl;
-    float best = -INFINITY;
-    int arg = C;                                           // rows of NaNs: no element compares greater; report 0 like np.argmax of all-equal
-    for (int c = sub; c < C; c += 16) {
-        const float v = x[c];
-        if (v > best || (v == best && c < arg)) { best = v; arg = c; }
-    }
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) {
-        const float ob = __shfl_xor(best, off);
-        const int oa = __shfl_xor(arg, off);
-        if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-    }
-    if (sub == 0) out[i] = arg < C ? arg : 0;
-}
-
-// ---- link head: logit_i = sum_c F[u_i, c] * F[v_i, c] * (r[c] or 1)   (graph_predictor.py:122-126) ---------------------
-__global__ __launch_bounds__(256) void k_edge_scores(const float *__restrict__ F, int64_t ldf, int C, int64_t n_rows,
-                                                      const int64_t *__restrict__ edges, int64_t m, const float *__restrict__ r,
-                                                      float *__restrict__ out) {
-    const int sub = threadIdx.x & 15;
-    const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-    if (i >= m) return;
-    const int64_t u = edges[2 * i], v = edges[2 * i + 1];
-    if (u < 0 || u >= n_rows || v < 0 || v >= n_rows) {                 // out of range: NaN
-        if (sub == 0) out[i] = NAN;
-        return;
-    }
-    const float *__restrict__ fu = F + u * ldf, *__restrict__ fv = F + v * ldf;
-    float acc = 0.f;
-    for (int c = sub; c < C; c += 16) acc = fmaf(fu[c] * fv[c], r ? r[c] : 1.0f, acc);
-    acc = group16_sum(acc);
-    if (sub == 0) out[i] = acc;
-}
-
-// dF[u_i, :] += g_i * F[v_i, :] * r,  dF[v_i, :] += g_i * F[u_i, :] * r   (atomics: endpoints repeat across edges)
-__global__ __launch_bounds__(256) void k_edge_scores_bwd(const float *__restrict__ F, int64_t ldf, int C, int64_t n_rows,
-                                                          const int64_t *__restrict__ edges, int64_t m, const float *__restrict__ r,
-                                                          const float *__restrict__ g, float *__restrict__ dF, int64_t ldg) {
-    const int sub = threadIdx.x & 15;
-    const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-    if (i >= m) return;
-    const int64_t u = edges[2 * i], v = edges[2 * i + 1];
-    if (u < 0 || u >= n_rows || v < 0 || v >= n_rows) return;
-    const float gi = g[i];
-    for (int c = sub; c < C; c += 16) {
-        const float w = gi * (r ? r[c] : 1.0f);
-        atomicAdd(dF + u * ldg + c, w * F[v * ldf + c]);
-        atomicAdd(dF + v * ldg + c, w * F[u * ldf + c]);
-    }
-}
-
-inline bool aligned16(const void *p) { return ((uintptr_t)p % 16) == 0; }
 
 }  // namespace
 
 namespace gnx {
 
-// used by gnx_spmm.hip (GCNII's long rows go through the dense kernel with a row scatter)
-// (tuning builds: GNX_DENSE_RING=0 keeps the register-staged kernel, for A/B runs)
-static bool ring_enabled() {
-#ifdef GNX_TUNING
-    static const bool on = [] { const char *e = getenv("GNX_DENSE_RING"); return !(e && e[0] == '0'); }();
-    return on;
-#else
-    return true;
-#endif
-}
-
-// (tuning builds: GNX_WGRAD_ACC=0 keeps the panel kernel)
-static bool wgrad_acc_enabled() {
-#ifdef GNX_TUNING
-    static const bool on = [] { const char *e = getenv("GNX_WGRAD_ACC"); return !(e && e[0] == '0'); }();
-    return on;
-#else
-    return true;
-#endif
-}
-
-// (tuning builds: GNX_DENSE_WREG=0 skips the W-in-registers kernel)
-static bool wreg_enabled() {
-#ifdef GNX_TUNING
-    static const bool on = [] { const char *e = getenv("GNX_DENSE_WREG"); return !(e && e[0] == '0'); }();
-    return on;
-#else
-    return true;
-#endif
-}
-
+// used by gnx_gcnii.hip too (GCNII's long rows go through the dense kernel with a row scatter)
 int dense_rows(const float *X, int64_t ldx, int64_t n, int64_t F, const float *W, int64_t ldw, int64_t O, const float *bias, int act,
                const int32_t *in_rows, const int32_t *out_rows, float *out, int64_t ldo, hipStream_t s) {
     if (n == 0) return GNX_OK;
     DenseArgs p{X, ldx, n, (int)F, W, ldw, (int)O, bias, act, out, ldo, out_rows, in_rows, false};
-    const bool al = ldx % 4 == 0 && aligned16(X);
+    const bool al = ldx % 4 == 0 && aligned(X, 16);
     for (int64_t o0 = 0; o0 < O; o0 += 256) {                         // column panels of at most 256 outputs
         DenseArgs q = p;
         q.W = W + o0; q.bias = bias ? bias + o0 : nullptr; q.out = out + o0;
-        q.w_aligned = ldw % 4 == 0 && aligned16(q.W);
+        q.w_aligned = ldw % 4 == 0 && aligned(q.W, 16);
         q.O = (int)(O - o0 < 256 ? O - o0 : 256);
-        const int nt = (q.O + 15) / 16;
-        const int nt4 = nt;                                                // the ring kernel takes accumulator columns in whole groups of four
-        if (wreg_enabled() && wreg_eligible(q, al)) {                     // shapes whose W fits the registers (padded to 128 / 256 x 32 / 64 / 128)
-            int rc = 1;                                                       // (> 0: no shape of this kernel)
-            if (q.F > 128 && q.O <= 32)       rc = launch_wreg<2, 4, 8>(q, s);
-            else if (q.F > 128 && q.O <= 64)  rc = launch_wreg<4, 4, 8>(q, s);
-            else if (q.F <= 128 && q.O <= 64) rc = launch_wreg<4, 2, 4>(q, s);
-            else if (q.F <= 128 && q.O <= 128) rc = launch_wreg<8, 2, 4>(q, s);
-            if (rc < 0) return rc;
-            if (rc == GNX_OK) continue;
-        }
-        if (ring_enabled() && nt % 4 == 0 && ring_eligible(q, al, nt4) && nt4 <= 16) {
-            int rc = nt4 == 4 ? launch_ring<4>(q, s) : nt4 == 8 ? launch_ring<8>(q, s) : nt4 == 12 ? launch_ring<12>(q, s) : launch_ring<16>(q, s);
-            if (rc != GNX_OK) return rc;
-            continue;
-        }
-        if (nt <= 1) launch_dense<1>(q, al, s);
-        else if (nt <= 2) launch_dense<2>(q, al, s);
-        else if (nt <= 3) launch_dense<3>(q, al, s);
-        else if (nt <= 4) launch_dense<4>(q, al, s);
-        else if (nt <= 6) launch_dense<6>(q, al, s);
-        else if (nt <= 8) launch_dense<8>(q, al, s);
-        else if (nt <= 12) launch_dense<12>(q, al, s);
-        else launch_dense<16>(q, al, s);
+        const int rc = dense_kernel_for(q, al)(q, al, s);
+        if (rc != GNX_OK) return rc;
     }
     GNX_HIP(hipGetLastError());
     return GNX_OK;
-}
-
-// the [elems] partials of n_slabs row slabs added in slab order into out: the last pass of gnx_dense_wgrad and of gnx_gcnii_wgrad
-void sum_slabs(const float *partial, int64_t n_slabs, int64_t elems, float *out, hipStream_t s) {
-    hipLaunchKernelGGL(k_sum_slabs, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, s, partial, n_slabs, elems, out);
 }
 
 }  // namespace gnx
@@ -1054,118 +562,6 @@ int gnx_dense(const float *d_X, int64_t ldx, int64_t n, int64_t F, const float *
     GNX_CHECK_ARG(d_X && d_W && d_out, "gnx_dense: NULL pointer");
     GNX_CHECK_ARG((const void *)d_X != (const void *)d_out, "gnx_dense: out must not alias X");
     return dense_rows(d_X, ldx, n, F, d_W, ldw, O, d_bias, act, nullptr, nullptr, d_out, ldo, (hipStream_t)stream);
-}
-
-int gnx_dense_wgrad(const float *d_X, int64_t ldx, const float *d_G, int64_t ldg, int64_t n, int64_t F, int64_t O, float *d_dW,
-                    float *d_work, int64_t work_floats, void *stream) {
-    GNX_CHECK_ARG(n >= 0 && F >= 1 && O >= 1 && F <= (1 << 20) && O <= (1 << 20), "gnx_dense_wgrad: bad sizes");
-    GNX_CHECK_ARG(ldx >= F && ldg >= O, "gnx_dense_wgrad: leading dimension smaller than the row");
-    GNX_CHECK_ARG(d_dW != nullptr, "gnx_dense_wgrad: NULL output");
-    hipStream_t s = (hipStream_t)stream;
-    if (n == 0) {
-        GNX_HIP(hipMemsetAsync(d_dW, 0, (size_t)F * O * sizeof(float), s));
-        return GNX_OK;
-    }
-    GNX_CHECK_ARG(d_X && d_G, "gnx_dense_wgrad: NULL input");
-    // row slabs: as many as the scratch holds (each slab leaves an F x O partial), at least 256 rows each, at most 2048 slabs
-    const int64_t fo = F * O;
-    int64_t max_slabs = work_floats / fo;
-    GNX_CHECK_ARG(d_work != nullptr && max_slabs >= 1, "gnx_dense_wgrad: the scratch must hold at least F * O floats");
-    if (max_slabs > 2048) max_slabs = 2048;
-    int64_t rows_per_slab = (n + max_slabs - 1) / max_slabs;
-    if (rows_per_slab < 256) rows_per_slab = 256;
-    rows_per_slab = (rows_per_slab + 31) / 32 * 32;
-    const int64_t n_slabs = (n + rows_per_slab - 1) / rows_per_slab;
-    const bool al = ldx % 4 == 0 && ldg % 4 == 0 && aligned16(d_X) && aligned16(d_G);
-    if (wgrad_acc_enabled() && aligned16(d_work)) {                          // the shapes whose whole result fits one wave's registers
-        int64_t waves = 0;
-        const int rc = wgrad_acc_dispatch(d_X, ldx, d_G, ldg, n, F, O, al, d_work, work_floats / fo > 2048 ? 2048 : work_floats / fo, &waves, s);
-        if (rc > 0) return rc;
-        if (rc == GNX_OK) {
-            // the waves' partials, added in wave order: in groups of 32 first when the scratch has room for the group sums (a sum over a
-            // thousand slabs of a few thousand elements is otherwise a launch of a few blocks walking a long chain each)
-            const int64_t per = 32, groups = (waves + per - 1) / per;
-            if (waves > 64 && work_floats >= (waves + groups) * fo) {
-                float *tmp = d_work + waves * fo;
-                hipLaunchKernelGGL(k_sum_slab_groups, dim3((unsigned)((fo + 255) / 256), (unsigned)groups), dim3(256), 0, s, d_work, waves, per, fo, tmp);
-                sum_slabs(tmp, groups, fo, d_dW, s);
-            } else {
-                sum_slabs(d_work, waves, fo, d_dW, s);
-            }
-            GNX_HIP(hipGetLastError());
-            return GNX_OK;
-        }
-    }
-    const int nt_all = (int)((O + 15) / 16);
-    const int NTsel = nt_all >= 4 ? 4 : (nt_all >= 2 ? 2 : 1);
-    dim3 grid((unsigned)n_slabs, (unsigned)((F + 255) / 256), (unsigned)((nt_all + NTsel - 1) / NTsel));
-    if (NTsel == 4)      hipLaunchKernelGGL(k_wgrad_mfma<4>, grid, dim3(256), 0, s, d_X, ldx, d_G, ldg, n, (int)F, (int)O, rows_per_slab, al, d_work);
-    else if (NTsel == 2) hipLaunchKernelGGL(k_wgrad_mfma<2>, grid, dim3(256), 0, s, d_X, ldx, d_G, ldg, n, (int)F, (int)O, rows_per_slab, al, d_work);
-    else                 hipLaunchKernelGGL(k_wgrad_mfma<1>, grid, dim3(256), 0, s, d_X, ldx, d_G, ldg, n, (int)F, (int)O, rows_per_slab, al, d_work);
-    sum_slabs(d_work, n_slabs, fo, d_dW, s);
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
-}
-
-int gnx_node_ce(const float *d_logits, int64_t ldl, int64_t n_rows, int64_t C, const int64_t *d_nodes, const int64_t *d_labels, int64_t m,
-                float *d_loss_per_node, float *d_mean_loss, void *stream) {
-    GNX_CHECK_ARG(m >= 1 && C >= 1 && n_rows >= 1 && ldl >= C, "gnx_node_ce: bad sizes");
-    GNX_CHECK_ARG(d_logits && d_nodes && d_labels && d_loss_per_node && d_mean_loss, "gnx_node_ce: NULL pointer");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_node_ce_fwd, dim3((unsigned)((m + 15) / 16)), dim3(256), 0, s, d_logits, ldl, (int)C, n_rows, d_nodes, d_labels, m,
-                       d_loss_per_node);
-    if (m > 4096) {      // two-level mean; the partial sums live in the scratch tail of d_loss_per_node
-        float *partial = d_loss_per_node + m;
-        hipLaunchKernelGGL(k_mean_partial, dim3(MEAN_BLOCKS), dim3(256), 0, s, d_loss_per_node, m, partial);
-        hipLaunchKernelGGL(k_mean, dim3(1), dim3(256), 0, s, partial, (int64_t)MEAN_BLOCKS, m, d_mean_loss);
-    } else {
-        hipLaunchKernelGGL(k_mean, dim3(1), dim3(256), 0, s, d_loss_per_node, m, m, d_mean_loss);
-    }
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
-}
-
-int gnx_node_ce_backward(const float *d_logits, int64_t ldl, int64_t n_rows, int64_t C, const int64_t *d_nodes, const int64_t *d_labels,
-                         int64_t m, const float *d_grad_loss, float *d_grad_logits, int64_t ldg, void *stream) {
-    GNX_CHECK_ARG(m >= 1 && C >= 1 && n_rows >= 1 && ldl >= C && ldg >= C, "gnx_node_ce_backward: bad sizes");
-    GNX_CHECK_ARG(d_logits && d_nodes && d_labels && d_grad_loss && d_grad_logits, "gnx_node_ce_backward: NULL pointer");
-    hipLaunchKernelGGL(k_node_ce_bwd, dim3((unsigned)((m + 15) / 16)), dim3(256), 0, (hipStream_t)stream, d_logits, ldl, (int)C, n_rows,
-                       d_nodes, d_labels, m, d_grad_loss, 1.0f / (float)m, d_grad_logits, ldg);
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
-}
-
-int gnx_edge_scores(const float *d_F, int64_t ldf, int64_t n_rows, int64_t C, const int64_t *d_edges, int64_t m, const float *d_r,
-                    float *d_out, void *stream) {
-    GNX_CHECK_ARG(m >= 0 && C >= 1 && n_rows >= 0 && ldf >= C, "gnx_edge_scores: bad sizes");
-    if (m == 0) return GNX_OK;
-    GNX_CHECK_ARG(d_F && d_edges && d_out, "gnx_edge_scores: NULL pointer");
-    hipLaunchKernelGGL(k_edge_scores, dim3((unsigned)((m + 15) / 16)), dim3(256), 0, (hipStream_t)stream, d_F, ldf, (int)C, n_rows, d_edges, m,
-                       d_r, d_out);
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
-}
-
-int gnx_edge_scores_backward(const float *d_F, int64_t ldf, int64_t n_rows, int64_t C, const int64_t *d_edges, int64_t m, const float *d_r,
-                             const float *d_grad_out, float *d_grad_F, int64_t ldg, void *stream) {
-    GNX_CHECK_ARG(m >= 0 && C >= 1 && ldf >= C && ldg >= C, "gnx_edge_scores_backward: bad sizes");
-    if (m == 0) return GNX_OK;
-    GNX_CHECK_ARG(d_F && d_edges && d_grad_out && d_grad_F, "gnx_edge_scores_backward: NULL pointer");
-    hipLaunchKernelGGL(k_edge_scores_bwd, dim3((unsigned)((m + 15) / 16)), dim3(256), 0, (hipStream_t)stream, d_F, ldf, (int)C, n_rows, d_edges,
-                       m, d_r, d_grad_out, d_grad_F, ldg);
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
-}
-
-int gnx_node_argmax(const float *d_logits, int64_t ldl, int64_t n_rows, int64_t C, const int64_t *d_nodes, int64_t m, int64_t *d_out,
-                    void *stream) {
-    GNX_CHECK_ARG(m >= 0 && C >= 1 && n_rows >= 0 && ldl >= C, "gnx_node_argmax: bad sizes");
-    if (m == 0) return GNX_OK;
-    GNX_CHECK_ARG(d_logits && d_out, "gnx_node_argmax: NULL pointer");
-    hipLaunchKernelGGL(k_node_argmax, dim3((unsigned)((m + 15) / 16)), dim3(256), 0, (hipStream_t)stream, d_logits, ldl, (int)C, n_rows, d_nodes, m,
-                       d_out);
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
 }
 
 }  // extern "C"

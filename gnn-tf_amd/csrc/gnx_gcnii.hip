@@ -297,7 +297,7 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii_back(const typename R::
 // No float atomics, nothing depends on the device: wave w of block b takes the tiles b WPB + w + k gridDim.x WPB in ascending k (the
 // tiles are in degree-binned order, so striding spreads every degree bin over all blocks), the block adds its waves' accumulators in
 // wave order through LDS and writes one [C, C] partial, slab b of `work`; the host's grid is a function of (n, C, slabs) alone and the
-// slabs are added in index order by sum_slabs (gnx_dense.hip).
+// slabs are added in index order by sum_slabs (gnx_dense_wgrad.hip).
 template <typename R, int NT, int U, int WPB>
 __global__ __launch_bounds__(64 * WPB) void k_gcnii_wgrad(const typename R::Args p, const float *__restrict__ Gm, const float *__restrict__ hub,
                                                           float *__restrict__ work) {

@@ -378,7 +378,7 @@ void set_drop_fuse(const gnx_graph *g, float dropout_p, uint64_t seed, uint64_t 
 // out[out_rows[r]] = act(X[in_rows[r]] . W + bias) on the matrix cores (gnx_dense.hip); row maps optional
 int dense_rows(const float *X, int64_t ldx, int64_t n, int64_t F, const float *W, int64_t ldw, int64_t O, const float *bias, int act,
                const int32_t *in_rows, const int32_t *out_rows, float *out, int64_t ldo, hipStream_t s);
-// out[e] = partial[0][e] + partial[1][e] + ... in slab order, e < elems (gnx_dense.hip): the last pass of the weight gradients
+// out[e] = partial[0][e] + partial[1][e] + ... in slab order, e < elems (gnx_dense_wgrad.hip): the last pass of the weight gradients
 void sum_slabs(const float *partial, int64_t n_slabs, int64_t elems, float *out, hipStream_t s);
 #ifdef GNX_TUNING
 extern int tune_override;

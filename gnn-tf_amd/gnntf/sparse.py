@@ -990,7 +990,7 @@ def gather_rows(X: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return out
 
 
-# ---- the dense ends of the path: matrix-core kernels of libgnx.so (csrc/gnx_dense.hip) ----------------------------------
+# ---- the dense ends of the path: libgnx.so's csrc/gnx_dense.hip, gnx_dense_wgrad.hip (matrix cores), gnx_heads.hip ---
 def _dense_launch(X, W, bias, relu):
     nat.require_cuda(X, W, bias)
     X, W = _as_f32_rows(X), _as_f32_rows(W)

@@ -1,4 +1,4 @@
-"""The dense ends of the path on the matrix cores (csrc/gnx_dense.hip, k_spmm_gcnii) against float64 numpy / the oracle:
+"""The dense ends of the path on the matrix cores (csrc/gnx_dense.hip, gnx_dense_wgrad.hip, gnx_heads.hip, k_spmm_gcnii) against float64 numpy / the oracle:
 Dense (layers.py:135-136), the GCNII layer (gcn.py:22-27), the NodeClassification head (graph_predictor.py:16-31) and the
 sparse-input form of the first Dense.  float32 tolerance of BASELINE.json: rtol 1e-4 (+ atol for sums that cancel)."""
 import numpy as np
@@ -70,6 +70,29 @@ def test_dense_tall_kernels(gnntf, n, F, O, relu, with_bias):
     Wa = (torch.arange(F * O, device="cuda", dtype=torch.float32).reshape(F, O) * 0.5 - 7)
     out = gnntf.dense(eye, Wa, None)
     assert torch.equal(out, Wa[torch.arange(n, device="cuda") % F])
+
+
+@pytest.mark.parametrize("n,F,O", [
+    # more than 256 outputs at a tall n (one row over the threshold: a ragged last tile): the column panels of ONE call take different kernels
+    (16385, 128, 300),    # k_dense_mfma<16> (W image beyond the ring's 64 KB), then 44 columns padded in k_dense_wreg: W and out column slices at 1024 bytes
+    (16385, 64, 320),     # k_dense_ring<16> at exactly the 64 KB W image, then k_dense_ring<4>
+    (16385, 256, 260),    # k_dense_mfma<16> (not a ring shape), then a 4-column padded k_dense_wreg panel
+    # the two sides of the tall threshold
+    (16383, 256, 64), (16384, 256, 64)])
+def test_dense_column_panels_and_tall_threshold(gnntf, n, F, O):
+    """Which kernel a column panel takes (dense_kernel_for) must not show in the result: with bias and relu, BITWISE the same product
+    computed in row slabs of 8192 (k_dense_mfma throughout, as in test_dense_tall_kernels), and float64 on the first, the last and
+    2048 random rows."""
+    g = torch.Generator(device="cuda").manual_seed(n + F + O)
+    X = torch.randn(n, F, device="cuda", generator=g)
+    W = torch.randn(F, O, device="cuda", generator=g)
+    b = torch.randn(1, O, device="cuda", generator=g)
+    got = gnntf.dense(X, W, b, relu=True)
+    slabs = torch.cat([gnntf.dense(X[i:i + 8192], W, b, relu=True) for i in range(0, n, 8192)])
+    assert torch.equal(got, slabs)
+    rows = torch.cat([torch.arange(0, 64), torch.randint(0, n, (2048,)), torch.arange(n - 64, n)]).cuda()
+    want = torch.relu(X[rows].double() @ W.double() + b.double())
+    np.testing.assert_allclose(got[rows].cpu().numpy(), want.cpu().numpy(), rtol=RTOL, atol=1e-4 * np.sqrt(F))
 
 
 @pytest.mark.parametrize("F,O", [(256, 64), (128, 128), (256, 128), (64, 64)])

@@ -2,10 +2,13 @@
 """Did a refactor of csrc/ leave the generated kernels alone?  Compares the device assembly of two builds kernel by kernel (no GPU).
 
     for f in gnx_graph gnx_prep gnx_spmm gnx_spmm_bf16 gnx_spmm_train gnx_spmm_train_ord gnx_spmm_train_bf16 gnx_gcnii gnx_util \
-             gnx_dense gnx_halo; do                    # every unit of the Makefile's SRCS (gnx_graph's kernels include rocprim's)
+             gnx_dense gnx_dense_wgrad gnx_heads gnx_halo; do    # every unit of the Makefile's SRCS (gnx_graph's kernels include rocprim's)
         hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 --cuda-device-only -S gnn-tf_amd/csrc/$f.hip -o $DIR/$f.s
     done                                               # once in a checkout of the old commit, once in the new one
     python tools/compare_kernel_isa.py OLD_DIR NEW_DIR > profiles/notes/<name>.txt
+
+Units are paired by file name.  Where a change splits a unit, concatenate the new units' .s files under the old unit's name in NEW_DIR
+(cat gnx_dense.s gnx_dense_wgrad.s gnx_heads.s > NEW_DIR/gnx_dense.s, and leave the parts out of NEW_DIR): kernel names are unique.
 
 Per .amdhsa_kernel: the instruction text with symbol names, .LBB<n>_ label numbers, comments and directives stripped, and the
 metadata counts .vgpr_count / .sgpr_count / .private_segment_fixed_size / .group_segment_fixed_size.  Kernels are paired by name:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""gnx_dense (float32 MFMA, csrc/gnx_dense.hip) timings -- the one script that replaces the former one-offs
+"""gnx_dense (float32 MFMA, csrc/gnx_dense.hip: the forward kernels and their dispatch) timings -- the one script that replaces the former one-offs
 dense_one / dense_only / dense_ab / dense_time / dense_wreg_ab.
 
     python3 tools/dense_bench.py                                  # the standard shapes, with torch beside them
