@@ -500,8 +500,8 @@ int make_feat_drop(const char *fn, const gnx_graph *g, double p, uint64_t seed, 
     GNX_CHECK_ARG(g != nullptr, "%s: NULL handle", fn);
     GNX_CHECK_ARG(p >= 0.0 && p < 1.0, "%s: dropout rate %g outside [0, 1)", fn, p);
     fd.seed = seed; fd.stream = stream_id; fd.offset = g->stream_offset;
-    fd.thr = (uint32_t)(p * 16777216.0);
-    fd.scale = 1.0f / (1.0f - (float)p);
+    fd.thr = drop_threshold(p);
+    fd.scale = drop_scale((float)p);
     return GNX_OK;
 }
 

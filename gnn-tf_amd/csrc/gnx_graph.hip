@@ -23,8 +23,6 @@ void set_error(const char *fmt, ...) {
     va_end(ap);
 }
 
-static inline unsigned blocks_for(int64_t n, int bs = 256) { return (unsigned)((n + bs - 1) / bs); }
-
 static unsigned bits_for(uint64_t max_key_exclusive) {
     unsigned b = 1;
     while (b < 64 && (max_key_exclusive >> b) != 0) ++b;

@@ -200,6 +200,14 @@ int ensure_gather_order(gnx_graph *g, hipStream_t s);
 int ensure_train_gather(gnx_graph *g, const char *fn, hipStream_t s);
 int ensure_relabel_features(gnx_graph *g, size_t bytes, hipStream_t s);
 
+// blocks of `per_block` items that cover n items
+inline unsigned blocks_for(int64_t n, int per_block = 256) { return (unsigned)((n + per_block - 1) / per_block); }
+
+// a dropout rate as the kernels take it: keep iff hash >= int(p * 2^24) (oracle/gnntf_oracle.py:dropout_threshold), kept values times
+// the f32 scale 1 / (1 - p)
+inline uint32_t drop_threshold(double p) { return (uint32_t)(p * 16777216.0); }
+inline float drop_scale(float p) { return 1.0f / (1.0f - p); }
+
 // ---- counter RNG of the edge dropout: the same integer arithmetic as oracle/gnntf_oracle.py:hash_u24 ----------
 __device__ __forceinline__ uint64_t rng_fin(uint64_t z) {
     z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;

@@ -3,13 +3,12 @@
 // (gnntf/core/nn/layered.py:47-50).  All of this is HBM-bound integer/float streaming over
 // nnz-sized arrays; no LDS tiling is needed, only coalesced slot-parallel passes.
 #include "gnx_internal.h"
+#include <type_traits>
 #include <utility>
 
 using namespace gnx;
 
 namespace {
-
-inline unsigned blocks_for(int64_t n, int bs = 256) { return (unsigned)((n + bs - 1) / bs); }
 
 struct Drop {
     uint64_t seed, stream;
@@ -53,121 +52,54 @@ __device__ __forceinline__ float t_value(const float *__restrict__ raw, const fl
     return hash_u24(d.seed, stream_of(d), key_row(d, row), key_col(d, col), 0) >= d.thr ? v * d.scale : 0.f;
 }
 
-// column sums over the transposed structure: 8 lanes per column, fixed reduction tree.
+// ---- column sums over the transposed structure ---------------------------------------------------------------------------------
+// Two walks, each written once.  k_colsum_short: 8 lanes per column, lane `sub` adds the positions b + sub, b + sub + 8, ... of its
+// column in that order from 0.f, then the xor tree 4, 2, 1.  k_colsum_long: one 256-thread block per column of more than long_row
+// entries (the short walk leaves those alone), thread i adds the positions b + i, b + i + 256, ..., then an LDS tree from 128 down
+// to 1.  What ONE position contributes is the walk's Term: add(acc, ns, p, c) adds position p of a column into acc[NS], one sum per
+// dropout stream of the batch (out[s * n_cols + j], s < ns <= NS; a batch holds at least one stream); c = column(j) is what the
+// term wants to know of column j, made once per column (the dropout key of a vertex block's column is a gather, and the compiler
+// does not move it out of the walk on its own).  The lane mapping, the order of additions and the reduction trees do not depend on
+// the term, so every stream's sums are bit for bit the single-stream sums, whichever term made them.  A term that is LISTED may be
+// launched over the list of the columns that have entries.
+
+// one stream: the slot's value after dropout (gnx_graph_colsum; a handle with duplicates but without entry tables walks its entry lists)
 template <bool DROPOUT>
-__global__ void k_colsum_short(const int64_t *__restrict__ t_rowptr, const int32_t *__restrict__ t_colidx,
-                               const int32_t *__restrict__ t_perm, const float *__restrict__ raw,
-                               const float *__restrict__ t_raw, Drop d, int64_t n_cols, int long_row, float *__restrict__ out) {
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t j = gid >> 3;
-    const int sub = (int)(gid & 7);
-    float acc = 0.f;
-    bool is_long = false;
-    if (j < n_cols) {
-        const int64_t b = t_rowptr[j], e = t_rowptr[j + 1];
-        is_long = (e - b) > long_row;
-        if (!is_long)
-            for (int64_t p = b + sub; p < e; p += 8) acc += t_value<DROPOUT>(raw, t_raw, t_perm, d, p, t_colidx[p], (int32_t)j);
+struct SlotTerm {
+    static constexpr int MAX_NS = 1;
+    static constexpr bool LISTED = false;
+    const int32_t *t_colidx, *t_perm;
+    const float *raw, *t_raw;
+    Drop d;
+    template <int NS>
+    __device__ __forceinline__ void add(float (&acc)[NS], int, int64_t p, int32_t j) const {
+        acc[0] += t_value<DROPOUT>(raw, t_raw, t_perm, d, p, t_colidx[p], j);
     }
-    acc += __shfl_xor(acc, 4);
-    acc += __shfl_xor(acc, 2);
-    acc += __shfl_xor(acc, 1);
-    if (j < n_cols && sub == 0 && !is_long) out[j] = acc;
-}
+    __device__ __forceinline__ int32_t column(int64_t j) const { return (int32_t)j; }
+};
 
-// one 256-thread block per long column; strided partial sums, then a fixed LDS tree.
-template <bool DROPOUT>
-__global__ __launch_bounds__(256) void k_colsum_long(const int64_t *__restrict__ t_rowptr, const int32_t *__restrict__ t_colidx,
-                                                     const int32_t *__restrict__ t_perm, const float *__restrict__ raw,
-                                                     const float *__restrict__ t_raw, Drop d,
-                                                     const int32_t *__restrict__ long_rows, float *__restrict__ out) {
-    __shared__ float red[256];
-    const int32_t j = long_rows[blockIdx.x];
-    const int64_t b = t_rowptr[j], e = t_rowptr[j + 1];
-    float acc = 0.f;
-    for (int64_t p = b + threadIdx.x; p < e; p += 256) acc += t_value<DROPOUT>(raw, t_raw, t_perm, d, p, t_colidx[p], j);
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[j] = red[0];
-}
-
-// Column sums of NS consecutive dropout streams in ONE pass over the transposed structure (no duplicate entries): the K
-// iterations of a training step each drop the edges independently, so their column sums differ only in the hash -- the
-// structure and the raw values are read once for all of them.  Same lane mapping and reduction tree as k_colsum_short / _long,
-// so every stream's sums are bit for bit what the single-stream kernels give.  out[s * n_cols + j].
-template <int NS>
-__global__ void k_colsum_short_multi(const int64_t *__restrict__ t_rowptr, const int32_t *__restrict__ t_colidx,
-                                     const float *__restrict__ t_raw, Drop d, int64_t n_cols, int long_row, float *__restrict__ out) {
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t j = gid >> 3;
-    const int sub = (int)(gid & 7);
-    float acc[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) acc[s] = 0.f;
-    bool is_long = false;
-    if (j < n_cols) {
-        const int64_t b = t_rowptr[j], e = t_rowptr[j + 1];
-        is_long = (e - b) > long_row;
-        if (!is_long) {
-            const uint64_t kc = key_col(d, j);
-            for (int64_t p = b + sub; p < e; p += 8) {
-                const float v = t_raw[p] * d.scale;
-                const uint64_t row = key_row(d, t_colidx[p]);
-#pragma unroll
-                for (int s = 0; s < NS; ++s) acc[s] += hash_u24(d.seed, stream_of(d) + s, row, kc, 0) >= d.thr ? v : 0.f;
-            }
-        }
-    }
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        float a = acc[s];
-        a += __shfl_xor(a, 4);
-        a += __shfl_xor(a, 2);
-        a += __shfl_xor(a, 1);
-        if (j < n_cols && sub == 0 && !is_long) out[(int64_t)s * n_cols + j] = a;
-    }
-}
-
-template <int NS>
-__global__ __launch_bounds__(256) void k_colsum_long_multi(const int64_t *__restrict__ t_rowptr, const int32_t *__restrict__ t_colidx,
-                                                           const float *__restrict__ t_raw, Drop d, const int32_t *__restrict__ long_rows,
-                                                           int64_t n_cols, float *__restrict__ out) {
-    __shared__ float red[256];
-    const int32_t j = long_rows[blockIdx.x];
-    const int64_t b = t_rowptr[j], e = t_rowptr[j + 1];
-    float acc[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) acc[s] = 0.f;
-    const uint64_t kc = key_col(d, j);
-    for (int64_t p = b + threadIdx.x; p < e; p += 256) {
+// one stream of a handle without duplicates (gnx_graph_colsum_streams with one stream): SlotTerm<true>'s sum without its entry-list
+// branch and the t_perm it would gather through, the column's key made once (profiles/NOTES.md, "The column sums written once":
+// 5 to 8 % of the config-4 graph's one-stream sums)
+struct StreamTerm {
+    static constexpr int MAX_NS = 1;
+    static constexpr bool LISTED = false;
+    const int32_t *t_colidx;
+    const float *t_raw;
+    Drop d;
+    template <int NS>
+    __device__ __forceinline__ void add(float (&acc)[NS], int, int64_t p, uint64_t kc) const {
         const float v = t_raw[p] * d.scale;
-        const uint64_t row = key_row(d, t_colidx[p]);
-#pragma unroll
-        for (int s = 0; s < NS; ++s) acc[s] += hash_u24(d.seed, stream_of(d) + s, row, kc, 0) >= d.thr ? v : 0.f;
+        acc[0] += hash_u24(d.seed, stream_of(d), key_row(d, t_colidx[p]), kc, 0) >= d.thr ? v : 0.f;
     }
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        __syncthreads();
-        red[threadIdx.x] = acc[s];
-        __syncthreads();
-        for (int w = 128; w > 0; w >>= 1) {
-            if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) out[(int64_t)s * n_cols + j] = red[0];
-    }
-}
+    __device__ __forceinline__ uint64_t column(int64_t j) const { return key_col(d, j); }
+};
 
-// The same sums in TWO passes (training steps: K streams at once, gnx_graph_colsum_streams).  In the kernels above the hashes sit
-// inside a loop whose trip count differs from lane to lane (8 lanes per column, columns of every length in one wave): most of the
-// VALU time goes to lanes that have run out of entries (measured round 4: 5.5 ms for 8 streams over 10^8 entries, hash-bound).
-// Pass 1 hashes with EVERY lane busy -- one lane per transposed position, all streams of the batch, the keep bits packed into one
-// 16-bit word per entry; pass 2 is the column walk of k_colsum_short_multi with a 2-byte read where the hashes were.  Same lane
-// mapping, same order of additions, same reduction tree: bit for bit the sums of the kernels above.
+// The sums of up to 16 streams in TWO passes (training steps: K streams at once, gnx_graph_colsum_streams; no duplicate entries).  With
+// the hashes inside the column walk, the loop's trip count differs from lane to lane (8 lanes per column, columns of every length in
+// one wave): most of the VALU time goes to lanes that have run out of entries (measured round 4: 5.5 ms for 8 streams over 10^8
+// entries, hash-bound).  Pass 1 hashes with EVERY lane busy -- one lane per transposed position, all streams of the batch, the keep
+// bits packed into one 16-bit word per entry; pass 2 is the column walk over MaskTerm, a 2-byte read where the hashes were.
 __global__ __launch_bounds__(256) void k_keep_masks(const int32_t *__restrict__ t_rowidx /* column of A */, const int32_t *__restrict__ t_colidx /* row of A */,
                                                     int64_t nnz, Drop d, int ns, uint16_t *__restrict__ mask) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -180,94 +112,54 @@ __global__ __launch_bounds__(256) void k_keep_masks(const int32_t *__restrict__ 
     mask[p] = (uint16_t)bits;
 }
 
-// ``list`` / ``n_slots``: the columns WITH entries in ascending order (the transposed structure's nonempty_rows; the sums of the others
-// are zeroed by the caller and their lanes never launched), or null / n_cols.
-template <int NS>
-__global__ void k_colsum_short_masked(const int64_t *__restrict__ t_rowptr, const float *__restrict__ t_raw, const uint16_t *__restrict__ mask,
-                                      float scale, int ns, int64_t n_cols, int long_row, const int32_t *__restrict__ list, int64_t n_slots,
-                                      float *__restrict__ out) {
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t slot = gid >> 3;
-    const int64_t j = slot < n_slots ? (list ? (int64_t)list[slot] : slot) : n_cols;
-    const int sub = (int)(gid & 7);
-    float acc[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) acc[s] = 0.f;
-    bool is_long = false;
-    if (j < n_cols) {
-        const int64_t b = t_rowptr[j], e = t_rowptr[j + 1];
-        is_long = (e - b) > long_row;
-        if (!is_long) {
-            for (int64_t p = b + sub; p < e; p += 8) {
-                const float v = t_raw[p] * scale;
-                const uint32_t m = mask[p];
-#pragma unroll
-                for (int s = 0; s < NS; ++s) acc[s] += ((m >> s) & 1u) ? v : 0.f;
-            }
-        }
-    }
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        float a = acc[s];
-        a += __shfl_xor(a, 4);
-        a += __shfl_xor(a, 2);
-        a += __shfl_xor(a, 1);
-        if (j < n_cols && sub == 0 && !is_long && s < ns) out[(int64_t)s * n_cols + j] = a;
-    }
-}
-
-template <int NS>
-__global__ __launch_bounds__(256) void k_colsum_long_masked(const int64_t *__restrict__ t_rowptr, const float *__restrict__ t_raw,
-                                                            const uint16_t *__restrict__ mask, float scale, int ns,
-                                                            const int32_t *__restrict__ long_rows, int64_t n_cols, float *__restrict__ out) {
-    __shared__ float red[256];
-    const int32_t j = long_rows[blockIdx.x];
-    const int64_t b = t_rowptr[j], e = t_rowptr[j + 1];
-    float acc[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) acc[s] = 0.f;
-    for (int64_t p = b + threadIdx.x; p < e; p += 256) {
+struct MaskTerm {
+    static constexpr int MAX_NS = 16;
+    static constexpr bool LISTED = true;
+    const float *t_raw;
+    const uint16_t *mask;    // k_keep_masks
+    float scale;
+    template <int NS>
+    __device__ __forceinline__ void add(float (&acc)[NS], int, int64_t p, int) const {
         const float v = t_raw[p] * scale;
         const uint32_t m = mask[p];
 #pragma unroll
         for (int s = 0; s < NS; ++s) acc[s] += ((m >> s) & 1u) ? v : 0.f;
     }
+    __device__ __forceinline__ int column(int64_t) const { return 0; }
+};
+
+// up to 16 streams on a handle with duplicate entries (gnx_graph_enable_entry_dropout): each position's kept slot sum made per stream
+// from the entry tables in transposed order (slot_kept_sum: a uniform slot reads its multiplicity and value, a general one walks its
+// entries through t_perm), the structure read once for all of them
+struct EntryTerm {
+    static constexpr int MAX_NS = 16;
+    static constexpr bool LISTED = false;
+    const int32_t *t_colidx, *t_perm;
+    const uint8_t *t_mult;
+    const float *t_uval;
+    Drop d;
+    template <int NS>
+    __device__ __forceinline__ void add(float (&acc)[NS], int ns, int64_t p, uint64_t kc) const {
+        const uint64_t row = key_row(d, t_colidx[p]), stream = stream_of(d);
+        const uint32_t m = t_mult[p];
+        const float uval = t_uval[p];
+        const int64_t slot = m == ENTRY_GENERAL ? (int64_t)t_perm[p] : 0;
 #pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        if (s < ns) {                                                // (block-uniform)
-            __syncthreads();
-            red[threadIdx.x] = acc[s];
-            __syncthreads();
-            for (int w = 128; w > 0; w >>= 1) {
-                if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-                __syncthreads();
-            }
-            if (threadIdx.x == 0) out[(int64_t)s * n_cols + j] = red[0];
-        }
+        for (int s = 0; s < NS; ++s)
+            if (NS == 1 || s < ns) acc[s] += slot_kept_sum(hash_key(d.seed, stream + s, row, kc), d.thr, d.scale, m, uval, d.e_vals, d.slot_ptr, slot);
     }
-}
+    __device__ __forceinline__ uint64_t column(int64_t j) const { return key_col(d, j); }
+};
 
-// The column sums of NS streams on a handle with duplicate entries (gnx_graph_enable_entry_dropout): the walk and the reduction tree
-// of k_colsum_short<true> / k_colsum_long<true>, each position's kept slot sum made per stream from the entry tables in transposed
-// order (slot_kept_sum: a uniform slot reads its multiplicity and value, a general one walks its entries through t_perm) -- so every
-// stream's sums are bit for bit what gnx_graph_colsum gives, and the structure is read once for all of them.
-template <int NS>
-__device__ __forceinline__ void entry_sums(float (&acc)[NS], const Drop &d, int ns, uint64_t row, uint64_t kc, uint32_t m, float uval,
-                                           const int32_t *__restrict__ t_perm, int64_t p) {
-    const int64_t slot = m == ENTRY_GENERAL ? (int64_t)t_perm[p] : 0;
-    const uint64_t stream = stream_of(d);
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-        if (s < ns) acc[s] += slot_kept_sum(hash_key(d.seed, stream + s, row, kc), d.thr, d.scale, m, uval, d.e_vals, d.slot_ptr, slot);
-}
-
-template <int NS>
-__global__ void k_colsum_short_entries(const int64_t *__restrict__ t_rowptr, const int32_t *__restrict__ t_colidx,
-                                       const int32_t *__restrict__ t_perm, const uint8_t *__restrict__ t_mult,
-                                       const float *__restrict__ t_uval, Drop d, int ns, int64_t n_cols, int long_row,
-                                       float *__restrict__ out) {
+// ``list`` / ``n_slots`` (a LISTED term): the columns WITH entries in ascending order (the transposed structure's nonempty_rows; the
+// sums of the others are zeroed by the caller and their lanes never launched), or null / n_cols.  Compiled in for such a term only:
+// the columns of an R-MAT graph hold ten entries on average, and the look-up showed in the time of the one-stream sums.
+template <int NS, class Term>
+__global__ void k_colsum_short(const int64_t *__restrict__ t_rowptr, Term term, int ns, int64_t n_cols, int long_row,
+                               const int32_t *__restrict__ list, int64_t n_slots, float *__restrict__ out) {
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t j = gid >> 3;
+    int64_t j = gid >> 3;
+    if constexpr (Term::LISTED) j = j < n_slots ? (list ? (int64_t)list[j] : j) : n_cols;
     const int sub = (int)(gid & 7);
     float acc[NS];
 #pragma unroll
@@ -277,9 +169,8 @@ __global__ void k_colsum_short_entries(const int64_t *__restrict__ t_rowptr, con
         const int64_t b = t_rowptr[j], e = t_rowptr[j + 1];
         is_long = (e - b) > long_row;
         if (!is_long) {
-            const uint64_t kc = key_col(d, j);
-            for (int64_t p = b + sub; p < e; p += 8)
-                entry_sums<NS>(acc, d, ns, key_row(d, t_colidx[p]), kc, t_mult[p], t_uval[p], t_perm, p);
+            const auto c = term.column(j);
+            for (int64_t p = b + sub; p < e; p += 8) term.add(acc, ns, p, c);
         }
     }
 #pragma unroll
@@ -288,28 +179,25 @@ __global__ void k_colsum_short_entries(const int64_t *__restrict__ t_rowptr, con
         a += __shfl_xor(a, 4);
         a += __shfl_xor(a, 2);
         a += __shfl_xor(a, 1);
-        if (j < n_cols && sub == 0 && !is_long && s < ns) out[(int64_t)s * n_cols + j] = a;
+        if (j < n_cols && sub == 0 && !is_long && (NS == 1 || s < ns)) out[(int64_t)s * n_cols + j] = a;
     }
 }
 
-template <int NS>
-__global__ __launch_bounds__(256) void k_colsum_long_entries(const int64_t *__restrict__ t_rowptr, const int32_t *__restrict__ t_colidx,
-                                                             const int32_t *__restrict__ t_perm, const uint8_t *__restrict__ t_mult,
-                                                             const float *__restrict__ t_uval, Drop d, int ns,
-                                                             const int32_t *__restrict__ long_rows, int64_t n_cols, float *__restrict__ out) {
+template <int NS, class Term>
+__global__ __launch_bounds__(256) void k_colsum_long(const int64_t *__restrict__ t_rowptr, Term term, int ns,
+                                                     const int32_t *__restrict__ long_rows, int64_t n_cols, float *__restrict__ out) {
     __shared__ float red[256];
     const int32_t j = long_rows[blockIdx.x];
     const int64_t b = t_rowptr[j], e = t_rowptr[j + 1];
     float acc[NS];
 #pragma unroll
     for (int s = 0; s < NS; ++s) acc[s] = 0.f;
-    const uint64_t kc = key_col(d, j);
-    for (int64_t p = b + threadIdx.x; p < e; p += 256)
-        entry_sums<NS>(acc, d, ns, key_row(d, t_colidx[p]), kc, t_mult[p], t_uval[p], t_perm, p);
+    const auto c = term.column(j);
+    for (int64_t p = b + threadIdx.x; p < e; p += 256) term.add(acc, ns, p, c);
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-        if (s < ns) {                                                // (block-uniform)
-            __syncthreads();
+        if (NS == 1 || s < ns) {                                     // (block-uniform)
+            if (s > 0) __syncthreads();                              // red[] of stream s - 1 has been read
             red[threadIdx.x] = acc[s];
             __syncthreads();
             for (int w = 128; w > 0; w >>= 1) {
@@ -352,34 +240,20 @@ __global__ void k_degree_scale(float *__restrict__ d, int64_t n, int normalized,
     d[j] = (x != 0.f) ? 1.0f / x : 0.f;   // tf.math.divide_no_nan(1., x)
 }
 
-// gnn.py:42 / :45: v_ij <- (rs[i] * v_ij) * cs[j]
-template <bool DROPOUT>
+// gnn.py:42 / :45: v_ij <- (rs[i] * v_ij) * cs[j], written in slot order or, TRANSPOSED, in the order of the transposed structure:
+// position k then holds entry (row = t_colidx[k], col = t_rowidx[k]) of A, which the caller passes as rowidx / colidx
+template <bool DROPOUT, bool TRANSPOSED>
 __global__ void k_scale_values(const int32_t *__restrict__ rowidx, const int32_t *__restrict__ colidx,
-                               const float *__restrict__ raw, Drop d, const float *__restrict__ rs,
+                               const int32_t *__restrict__ t_perm, const float *__restrict__ raw,
+                               const float *__restrict__ t_raw, Drop d, const float *__restrict__ rs,
                                const float *__restrict__ cs, int64_t nnz, float *__restrict__ out) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= nnz) return;
     const int32_t r = rowidx[k], c = colidx[k];
-    float v = slot_value<DROPOUT>(raw, d, k, r, c);
+    float v = TRANSPOSED ? t_value<DROPOUT>(raw, t_raw, t_perm, d, k, r, c) : slot_value<DROPOUT>(raw, d, k, r, c);
     if (rs) v = rs[r] * v;
     if (cs) v = v * cs[c];
     out[k] = v;
-}
-
-// the same values written in the order of the transposed structure: position p holds entry
-// (row = t_colidx[p], col = t_rowidx[p]) of A
-template <bool DROPOUT>
-__global__ void k_scale_values_t(const int32_t *__restrict__ t_rowidx, const int32_t *__restrict__ t_colidx,
-                                 const int32_t *__restrict__ t_perm, const float *__restrict__ raw,
-                                 const float *__restrict__ t_raw, Drop d, const float *__restrict__ rs,
-                                 const float *__restrict__ cs, int64_t nnz, float *__restrict__ out) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= nnz) return;
-    const int32_t r = t_colidx[p], c = t_rowidx[p];
-    float v = t_value<DROPOUT>(raw, t_raw, t_perm, d, p, r, c);
-    if (rs) v = rs[r] * v;
-    if (cs) v = v * cs[c];
-    out[p] = v;
 }
 
 // diagonal weight of the identity added by add_eye (gnn.py:39,49)
@@ -392,8 +266,8 @@ __global__ void k_diag(const float *__restrict__ deg, int64_t n, int mode /*0: o
 int make_drop(gnx_graph *g, float p, uint64_t seed, uint64_t stream_id, Drop &d) {
     GNX_CHECK_ARG(p >= 0.f && p < 1.f, "dropout rate %g outside [0, 1)", (double)p);
     d.seed = seed; d.stream = stream_id; d.offset = g->stream_offset;
-    d.thr = (uint32_t)((double)p * 16777216.0);
-    d.scale = 1.0f / (1.0f - p);
+    d.thr = drop_threshold(p);
+    d.scale = drop_scale(p);
     d.e_vals = g->has_dups ? g->e_vals : nullptr;
     d.slot_ptr = g->has_dups ? g->slot_ptr : nullptr;
     d.row0 = g->blk_row0_global; d.gid = g->blk_col_gid;
@@ -405,6 +279,45 @@ int ensure_deg(gnx_graph *g) {
     GNX_HIP(g->deg.alloc(g->a.n_cols));
     return GNX_OK;
 }
+
+template <int N> using IntC = std::integral_constant<int, N>;
+
+// f(IntC<NS>) for the accumulators per lane a batch of ns streams takes (one for a term that only ever sums one stream)
+template <class Term, typename F>
+void with_streams(int ns, F &&f) {
+    if constexpr (Term::MAX_NS > 1) {
+        if (ns > 8) return f(IntC<16>{});
+        if (ns > 4) return f(IntC<8>{});
+        if (ns > 2) return f(IntC<4>{});
+        if (ns > 1) return f(IntC<2>{});
+    }
+    return f(IntC<1>{});
+}
+
+// f(std::true_type) with dropout, f(std::false_type) without
+template <typename F>
+void with_dropout(float p, F &&f) {
+    if (p > 0.f) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// the column sums of one batch of ns streams over the transposed structure t (t.n_rows > 0) into out[s * t.n_rows + j]: the short walk
+// and, where the plan has long columns, the long one.  ``trim`` (a LISTED term): only the columns that have entries are launched
+// (ascending: the stores stay in order); the caller has zeroed the sums of the others
+template <class Term>
+void launch_colsums(const Csr &t, const Term &term, int ns, bool trim, float *out, hipStream_t s) {
+    const int64_t n_slots = trim ? t.n_nonempty : t.n_rows;
+    with_streams<Term>(ns, [&](auto NS) {
+        hipLaunchKernelGGL((k_colsum_short<NS(), Term>), dim3(blocks_for(n_slots * 8)), dim3(256), 0, s, t.rowptr, term, ns, t.n_rows,
+                           t.long_row, trim ? t.nonempty_rows : nullptr, n_slots, out);
+        if (t.n_long > 0)
+            hipLaunchKernelGGL((k_colsum_long<NS(), Term>), dim3((unsigned)t.n_long), dim3(256), 0, s, t.rowptr, term, ns, t.long_rows,
+                               t.n_rows, out);
+    });
+}
+
+template <bool DROPOUT>
+SlotTerm<DROPOUT> slot_term(const gnx_graph *g, const Drop &d) { return {g->t.colidx, g->t_perm, g->raw_vals, g->t_raw, d}; }
 
 }  // namespace
 
@@ -465,18 +378,7 @@ int gnx_graph_colsum(gnx_graph_t g, float dropout_p, uint64_t seed, uint64_t str
     if (rc != GNX_OK) return rc;
     const Csr &t = g->t;
     if (t.n_rows == 0) return GNX_OK;
-    const bool drop = dropout_p > 0.f;
-    const unsigned nb = blocks_for(t.n_rows * 8);
-    if (drop) hipLaunchKernelGGL(k_colsum_short<true>, dim3(nb), dim3(256), 0, s, t.rowptr, t.colidx, g->t_perm, g->raw_vals, g->t_raw, d,
-                                 t.n_rows, t.long_row, d_colsum_out);
-    else      hipLaunchKernelGGL(k_colsum_short<false>, dim3(nb), dim3(256), 0, s, t.rowptr, t.colidx, g->t_perm, g->raw_vals, g->t_raw, d,
-                                 t.n_rows, t.long_row, d_colsum_out);
-    if (t.n_long > 0) {
-        if (drop) hipLaunchKernelGGL(k_colsum_long<true>, dim3((unsigned)t.n_long), dim3(256), 0, s, t.rowptr, t.colidx, g->t_perm, g->raw_vals,
-                                     g->t_raw, d, t.long_rows, d_colsum_out);
-        else      hipLaunchKernelGGL(k_colsum_long<false>, dim3((unsigned)t.n_long), dim3(256), 0, s, t.rowptr, t.colidx, g->t_perm, g->raw_vals,
-                                     g->t_raw, d, t.long_rows, d_colsum_out);
-    }
+    with_dropout(dropout_p, [&](auto DROPOUT) { launch_colsums(t, slot_term<DROPOUT()>(g, d), 1, false, d_colsum_out, s); });
     GNX_HIP(hipGetLastError());
     return GNX_OK;
 }
@@ -487,37 +389,8 @@ int gnx_graph_colsum_streams(gnx_graph_t g, float dropout_p, uint64_t seed, uint
     GNX_CHECK_ARG(n_streams >= 1 && n_streams <= 4096, "gnx_graph_colsum_streams: bad stream count %d", n_streams);
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = g->a.n_cols;
-    if (g->has_dups && g->entry_drop && dropout_p > 0.f) {   // entry tables (gnx_graph_enable_entry_dropout): one pass per 16 streams
-        int rc = ensure_transpose(g, s);
-        if (rc != GNX_OK) return rc;
-        const Csr &t = g->t;
-        if (t.n_rows == 0) return GNX_OK;
-        const unsigned nb = blocks_for(t.n_rows * 8);
-        for (int k0 = 0; k0 < n_streams; k0 += 16) {
-            const int ns = n_streams - k0 < 16 ? n_streams - k0 : 16;
-            Drop d;
-            rc = make_drop(g, dropout_p, seed, first_stream + k0, d);
-            if (rc != GNX_OK) return rc;
-            float *out = d_colsum_out + (int64_t)k0 * n;
-#define GNX_ENTRY_SUMS(NS)                                                                                                             \
-            do {                                                                                                                       \
-                hipLaunchKernelGGL(k_colsum_short_entries<NS>, dim3(nb), dim3(256), 0, s, t.rowptr, t.colidx, g->t_perm, g->t_ed_mult,  \
-                                   g->t_ed_vals, d, ns, t.n_rows, t.long_row, out);                                                    \
-                if (t.n_long > 0)                                                                                                      \
-                    hipLaunchKernelGGL(k_colsum_long_entries<NS>, dim3((unsigned)t.n_long), dim3(256), 0, s, t.rowptr, t.colidx,       \
-                                       g->t_perm, g->t_ed_mult, g->t_ed_vals, d, ns, t.long_rows, t.n_rows, out);                      \
-            } while (0)
-            if (ns > 8) GNX_ENTRY_SUMS(16);
-            else if (ns > 4) GNX_ENTRY_SUMS(8);
-            else if (ns > 2) GNX_ENTRY_SUMS(4);
-            else if (ns > 1) GNX_ENTRY_SUMS(2);
-            else GNX_ENTRY_SUMS(1);
-#undef GNX_ENTRY_SUMS
-        }
-        GNX_HIP(hipGetLastError());
-        return GNX_OK;
-    }
-    if (g->has_dups || dropout_p <= 0.f) {              // entry lists / no dropout: one stream at a time through the general kernels
+    const bool tables = g->has_dups && g->entry_drop;        // gnx_graph_enable_entry_dropout
+    if (dropout_p <= 0.f || (g->has_dups && !tables)) {      // no dropout / entry lists: one stream at a time through gnx_graph_colsum
         for (int k = 0; k < n_streams; ++k) {
             int rc = gnx_graph_colsum(g, dropout_p, seed, first_stream + k, d_colsum_out + (int64_t)k * n, stream);
             if (rc != GNX_OK) return rc;
@@ -528,56 +401,34 @@ int gnx_graph_colsum_streams(gnx_graph_t g, float dropout_p, uint64_t seed, uint
     if (rc != GNX_OK) return rc;
     const Csr &t = g->t;
     if (t.n_rows == 0) return GNX_OK;
-    const unsigned nb = blocks_for(t.n_rows * 8);
-    if (n_streams >= 2 && t.nnz > 0) {
-        // two passes per batch of up to 16 streams: keep bits with every lane busy, then the column walk over 2-byte masks
-        if (!g->t_mask) {
-            if (stream_is_capturing(s)) {
-                set_error("gnx_graph_colsum_streams: the keep-bit scratch of this handle would have to be allocated while the stream is being "
-                          "captured: call gnx_graph_reserve(handle, C, GNX_RESERVE_TRANSPOSED) or run the call once eagerly before capturing");
-                return GNX_ERR_UNSUPPORTED;
-            }
-            GNX_HIP(g->t_mask.alloc(t.nnz));
+    // without entry tables, two passes per batch: keep bits with every lane busy, then the column walk over 2-byte masks
+    const bool masked = !tables && n_streams >= 2 && t.nnz > 0;
+    if (masked && !g->t_mask) {
+        if (stream_is_capturing(s)) {
+            set_error("gnx_graph_colsum_streams: the keep-bit scratch of this handle would have to be allocated while the stream is being "
+                      "captured: call gnx_graph_reserve(handle, C, GNX_RESERVE_TRANSPOSED) or run the call once eagerly before capturing");
+            return GNX_ERR_UNSUPPORTED;
         }
-        for (int k0 = 0; k0 < n_streams; k0 += 16) {
-            const int ns = n_streams - k0 < 16 ? n_streams - k0 : 16;
-            Drop d;
-            rc = make_drop(g, dropout_p, seed, first_stream + k0, d);
-            if (rc != GNX_OK) return rc;
-            float *out = d_colsum_out + (int64_t)k0 * n;
-            hipLaunchKernelGGL(k_keep_masks, dim3(blocks_for(t.nnz)), dim3(256), 0, s, g->t_rowidx, t.colidx, t.nnz, d, ns, g->t_mask);
-            // only the columns that have entries (ascending: the stores stay in order); the sums of the others are zero
-            const bool trim = t.nonempty_rows != nullptr && t.n_nonempty < t.n_rows;
-            const int64_t n_slots = trim ? t.n_nonempty : t.n_rows;
-            if (trim) GNX_HIP(hipMemsetAsync(out, 0, (size_t)ns * (size_t)n * sizeof(float), s));
-            const unsigned nbm = blocks_for(n_slots * 8);
-#define GNX_MASKED(NS)                                                                                                                 \
-            do {                                                                                                                       \
-                hipLaunchKernelGGL(k_colsum_short_masked<NS>, dim3(nbm), dim3(256), 0, s, t.rowptr, g->t_raw, g->t_mask, d.scale, ns, \
-                                   t.n_rows, t.long_row, trim ? t.nonempty_rows : nullptr, n_slots, out);                              \
-                if (t.n_long > 0)                                                                                                      \
-                    hipLaunchKernelGGL(k_colsum_long_masked<NS>, dim3((unsigned)t.n_long), dim3(256), 0, s, t.rowptr, g->t_raw,        \
-                                       g->t_mask, d.scale, ns, t.long_rows, t.n_rows, out);                                            \
-            } while (0)
-            if (ns > 8) GNX_MASKED(16);
-            else if (ns > 4) GNX_MASKED(8);
-            else if (ns > 2) GNX_MASKED(4);
-            else GNX_MASKED(2);
-#undef GNX_MASKED
-        }
-        GNX_HIP(hipGetLastError());
-        return GNX_OK;
+        GNX_HIP(g->t_mask.alloc(t.nnz));
     }
-    for (int k0 = 0; k0 < n_streams;) {                 // one stream: a single pass
+    const int per_batch = tables || masked ? 16 : 1;         // one stream (or no entry at all): a single pass per stream
+    for (int k0 = 0; k0 < n_streams; k0 += per_batch) {
+        const int ns = n_streams - k0 < per_batch ? n_streams - k0 : per_batch;
         Drop d;
         rc = make_drop(g, dropout_p, seed, first_stream + k0, d);
         if (rc != GNX_OK) return rc;
         float *out = d_colsum_out + (int64_t)k0 * n;
-        hipLaunchKernelGGL(k_colsum_short_multi<1>, dim3(nb), dim3(256), 0, s, t.rowptr, t.colidx, g->t_raw, d, t.n_rows, t.long_row, out);
-        if (t.n_long > 0)
-            hipLaunchKernelGGL(k_colsum_long_multi<1>, dim3((unsigned)t.n_long), dim3(256), 0, s, t.rowptr, t.colidx, g->t_raw, d,
-                               t.long_rows, t.n_rows, out);
-        k0 += 1;
+        if (tables) {
+            launch_colsums(t, EntryTerm{t.colidx, g->t_perm, g->t_ed_mult, g->t_ed_vals, d}, ns, false, out, s);
+        } else if (masked) {
+            hipLaunchKernelGGL(k_keep_masks, dim3(blocks_for(t.nnz)), dim3(256), 0, s, g->t_rowidx, t.colidx, t.nnz, d, ns, g->t_mask);
+            // only the columns that have entries; the sums of the others are zero
+            const bool trim = t.nonempty_rows != nullptr && t.n_nonempty < t.n_rows;
+            if (trim) GNX_HIP(hipMemsetAsync(out, 0, (size_t)ns * (size_t)n * sizeof(float), s));
+            launch_colsums(t, MaskTerm{g->t_raw, g->t_mask, d.scale}, ns, trim, out, s);
+        } else {
+            launch_colsums(t, StreamTerm{t.colidx, g->t_raw, d}, 1, false, out, s);
+        }
     }
     GNX_HIP(hipGetLastError());
     return GNX_OK;
@@ -594,41 +445,32 @@ int gnx_degree_scale(float *d_deg, int64_t n, int normalized, int add_eye_before
     return GNX_OK;
 }
 
-int gnx_graph_scale_values(gnx_graph_t g, float dropout_p, uint64_t seed, uint64_t stream_id, const float *d_row_scale,
-                           const float *d_col_scale, float *d_vals_out, void *stream) {
-    GNX_CHECK_ARG(g != nullptr, "gnx_graph_scale_values: NULL handle");
-    GNX_CHECK_ARG(g->a.nnz == 0 || d_vals_out != nullptr, "gnx_graph_scale_values: NULL output");
-    Drop d;
-    int rc = make_drop(g, dropout_p, seed, stream_id, d);
-    if (rc != GNX_OK) return rc;
-    if (g->a.nnz == 0) return GNX_OK;
-    const unsigned nb = blocks_for(g->a.nnz);
-    hipStream_t s = (hipStream_t)stream;
-    if (dropout_p > 0.f) hipLaunchKernelGGL(k_scale_values<true>, dim3(nb), dim3(256), 0, s, g->rowidx, g->a.colidx, g->raw_vals, d, d_row_scale,
-                                            d_col_scale, g->a.nnz, d_vals_out);
-    else                 hipLaunchKernelGGL(k_scale_values<false>, dim3(nb), dim3(256), 0, s, g->rowidx, g->a.colidx, g->raw_vals, d, d_row_scale,
-                                            d_col_scale, g->a.nnz, d_vals_out);
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
-}
-
+// the values in slot order or in transposed order (k_scale_values)
 static int scale_values_any(gnx_graph_t g, bool transposed, float dropout_p, uint64_t seed, uint64_t stream_id,
                             const float *rs, const float *cs, float *out, void *stream) {
-    if (!transposed) return gnx_graph_scale_values(g, dropout_p, seed, stream_id, rs, cs, out, stream);
     hipStream_t s = (hipStream_t)stream;
-    int rc = ensure_transpose(g, s);
+    int rc = transposed ? ensure_transpose(g, s) : GNX_OK;
     if (rc != GNX_OK) return rc;
     Drop d;
     rc = make_drop(g, dropout_p, seed, stream_id, d);
     if (rc != GNX_OK) return rc;
-    if (g->a.nnz == 0) return GNX_OK;
-    const unsigned nb = blocks_for(g->a.nnz);
-    if (dropout_p > 0.f) hipLaunchKernelGGL(k_scale_values_t<true>, dim3(nb), dim3(256), 0, s, g->t_rowidx, g->t.colidx, g->t_perm, g->raw_vals,
-                                            g->t_raw, d, rs, cs, g->a.nnz, out);
-    else                 hipLaunchKernelGGL(k_scale_values_t<false>, dim3(nb), dim3(256), 0, s, g->t_rowidx, g->t.colidx, g->t_perm, g->raw_vals,
-                                            g->t_raw, d, rs, cs, g->a.nnz, out);
+    const int64_t nnz = g->a.nnz;
+    if (nnz == 0) return GNX_OK;
+    with_dropout(dropout_p, [&](auto DROPOUT) {
+        if (transposed) hipLaunchKernelGGL((k_scale_values<DROPOUT(), true>), dim3(blocks_for(nnz)), dim3(256), 0, s, g->t.colidx, g->t_rowidx,
+                                           g->t_perm, g->raw_vals, g->t_raw, d, rs, cs, nnz, out);
+        else            hipLaunchKernelGGL((k_scale_values<DROPOUT(), false>), dim3(blocks_for(nnz)), dim3(256), 0, s, g->rowidx, g->a.colidx,
+                                           nullptr, g->raw_vals, nullptr, d, rs, cs, nnz, out);
+    });
     GNX_HIP(hipGetLastError());
     return GNX_OK;
+}
+
+int gnx_graph_scale_values(gnx_graph_t g, float dropout_p, uint64_t seed, uint64_t stream_id, const float *d_row_scale,
+                           const float *d_col_scale, float *d_vals_out, void *stream) {
+    GNX_CHECK_ARG(g != nullptr, "gnx_graph_scale_values: NULL handle");
+    GNX_CHECK_ARG(g->a.nnz == 0 || d_vals_out != nullptr, "gnx_graph_scale_values: NULL output");
+    return scale_values_any(g, false, dropout_p, seed, stream_id, d_row_scale, d_col_scale, d_vals_out, stream);
 }
 
 static int normalize_impl(const char *fn, gnx_graph_t g, bool transposed, int normalized, int add_eye, float dropout_p,

@@ -461,8 +461,6 @@ __global__ __launch_bounds__(256) void k_spmm_long_reduce(const typename R::Args
     }
 }
 
-inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
-
 #define GNX_LAUNCH(kern, grid, ...) hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, __VA_ARGS__)
 
 // One launch holds at most 2^32 work-items (the dispatch packet's grid size is 32 bits).  A wave per row reaches that at 67M rows,

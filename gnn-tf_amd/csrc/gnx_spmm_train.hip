@@ -34,8 +34,8 @@ void set_values(const gnx_graph *g, bool transposed, SpmmArgs &p) {
 void set_drop_fuse(const gnx_graph *g, float dropout_p, uint64_t seed, uint64_t stream_id, const float *d_D, int transposed,
                    int x_prescaled, SpmmArgs &p) {
     p.fuse.D = d_D; p.fuse.seed = seed; p.fuse.stream = stream_id; p.fuse.offset = g->stream_offset;
-    p.fuse.thr = (uint32_t)((double)dropout_p * 16777216.0);
-    p.fuse.scale = 1.0f / (1.0f - dropout_p);
+    p.fuse.thr = drop_threshold(dropout_p);
+    p.fuse.scale = drop_scale(dropout_p);
     p.fuse.transposed = transposed;
     p.fuse.col_prescaled = x_prescaled ? 1 : 0;
     p.fuse.row0_key = g->blk_row0_global; p.fuse.row0_D = g->blk_row0_buf; p.fuse.gid = g->blk_col_gid;
