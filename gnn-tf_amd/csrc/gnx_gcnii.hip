@@ -5,6 +5,9 @@
 //                      block of the two is one device function (tile_times_Ms)
 //   k_gcnii_wgrad      the layer's weight gradient dM = T^T G with the mixed rows T made again in LDS and never stored, one launch; a
 //                      row's gather and mix is one device function with the forward (mixed_row)
+//                      SPEC: the spectral-preserving form (gnx_gcnii_step_spectral) -- the bias in the MFMA block's epilogue, -bias, the
+//                      mask and x 2 in the store loop, one gate bit per element; k_spectral_tail is the same epilogue as a row pass
+//                      (hub rows, the other widths) and k_spectral_back the backward's first pass (gate, bias gradient)
 //   row passes         k_round_rows (f32 rows -> bf16), k_feature_dropout (the mask as a pass of its own: hub rows, the other widths, the
 //                      generic composition) and the backward's gate (k_feature_dropout_back, .._back_bf16); one launcher
 //                      (launch_row_pass) picks their vector width and grid
@@ -38,14 +41,48 @@ __device__ __forceinline__ void drop_values(const DropFuse &f, uint64_t stream, 
         x[v] = (f.thr == 0 || hash_u24(f.seed, stream, (uint64_t)row, (uint64_t)(c + v), 0) >= f.thr) ? x[v] * f.scale : 0.f;
 }
 
+// ---- the spectral-preserving form (gcn.py:30-51, gnx_gcnii_step_spectral): out = 2 drop(act(P') - bias), P' = T . M + bias ------------
+// What a launch needs beside the plain layer's arguments; the plain instantiations carry an empty struct.
+template <bool SPEC> struct SpectralArgs {};
+template <> struct SpectralArgs<true> {
+    const float *bias;     // [C]
+    uint32_t *gate;        // [n, ceil(C / 32)] or null: bit c & 31 of word row * ceil(C / 32) + (c >> 5) = (P'[row, c] > 0)
+};
+
+// x[v] = act(P') of columns c .. c + VEC - 1 of row `row`  ->  2 drop(x[v] - bias[v]): the ONE place the finished value is formed, for
+// the store loop of the fused launch and for the row pass behind the dense kernel (k_spectral_tail), so that a row has the same bits
+// whichever path made it.  Returns the gate bits of the VEC columns, bit v = (x[v] > 0): with the relu act(P') > 0 iff P' > 0, so the
+// gate is that of the pre-activation itself and never a guess from the finished value (relu(P') - bias rounds to -bias for a tiny P').
+template <int VEC, bool DROP>
+__device__ __forceinline__ uint32_t spectral_finish(const DropFuse &f, uint64_t stream, int64_t row, int64_t c, const float (&bias)[VEC],
+                                                    float (&x)[VEC]) {
+    uint32_t bits = 0;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+        bits |= (x[v] > 0.f ? 1u : 0u) << v;
+        x[v] -= bias[v];
+    }
+    if constexpr (DROP) drop_values<VEC>(f, stream, row, c, x);
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) x[v] *= 2.f;
+    return bits;
+}
+
 // tile <- act(tile . Ms) for one wave's 16-row tile T and the block's Ms (both row stride C + 4, C = 16 NT), on
 // v_mfma_f32_16x16x4_f32: the block the forward layer and its backward (k_spmm_gcnii_back) share.  The caller has put a wave
 // barrier between its writes of T and this call; on return the whole tile is written and visible to the wave.
-template <int NT>
-__device__ __forceinline__ void tile_times_Ms(float *__restrict__ T, const float *__restrict__ Ms, int lane, int act) {
+// BIAS (the spectral form): tile <- act(tile . Ms + bias[c]), the bias added to the accumulator value as it leaves the MFMA block.
+template <int NT, bool BIAS = false>
+__device__ __forceinline__ void tile_times_Ms(float *__restrict__ T, const float *__restrict__ Ms, int lane, int act,
+                                              const float *__restrict__ bias = nullptr) {
     constexpr int C = 16 * NT, STRIDE = C + 4;
     // tile . M : A[m = lane & 15][k = 4 kk + (lane >> 4)] from the tile, B[k][n = lane & 15] from Ms
     const int cc = lane & 15, g = lane >> 4;
+    [[maybe_unused]] float bv[NT];
+    if constexpr (BIAS) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) bv[nt] = bias[16 * nt + cc];
+    }
     f32x4 d[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) d[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -63,6 +100,7 @@ __device__ __forceinline__ void tile_times_Ms(float *__restrict__ T, const float
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             float v = d[nt][r];
+            if constexpr (BIAS) v += bv[nt];
             if (act == GNX_ACT_RELU) v = fmaxf(v, 0.f);
             T[(4 * g + r) * STRIDE + 16 * nt + cc] = v;
         }
@@ -118,8 +156,13 @@ __device__ __forceinline__ void mixed_row(const typename R::Args &p, int64_t row
 // where a lane holds row rows[ps] and columns c .. c + 3, so that the hash costs the gather loop no register; `mixed` still gets the
 // undropped T.  The mask's parameters are p.fuse (this kernel has no other use for it), so the
 // switch is a template argument alone and the instantiations without it are the kernel as it was.
-template <typename R, int NT, int U, int WPB, bool DROP = false>
-__global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args p, const float *__restrict__ M, int64_t ldm, float *__restrict__ mixed) {
+// SPEC (gnx_gcnii_step_spectral, f32 rows): the bias joins the accumulator in the MFMA block's epilogue, before the activation, and the
+// store loop forms 2 drop(act(P') - bias) (spectral_finish); with sp.gate the launch also writes one bit per element, P' > 0, which is
+// all the backward needs of the forward: a lane holds four columns of a row, the 4 NT lanes of a row (eight of them per 32-column
+// word) OR their bits together through xor-shuffles and one lane stores the word.  Like DROP a template argument alone.
+template <typename R, int NT, int U, int WPB, bool DROP = false, bool SPEC = false>
+__global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args p, const float *__restrict__ M, int64_t ldm, float *__restrict__ mixed,
+                                                         const SpectralArgs<SPEC> sp = SpectralArgs<SPEC>{}) {
     constexpr int C = 16 * NT, G = 4 * NT, RPP = 64 / G, PASSES = 16 / RPP, STRIDE = C + 4;
     __shared__ float Ms[C * STRIDE];
     __shared__ float Ts[WPB][16 * STRIDE];
@@ -153,6 +196,28 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args 
         vstore<4>(T + rr * STRIDE + c, acc);
     }
     __builtin_amdgcn_wave_barrier();
+    if constexpr (SPEC) {
+        constexpr int GW = G < 8 ? G : 8, WORDS = (C + 31) / 32;      // lanes per gate word, words per row
+        tile_times_Ms<NT, true>(T, Ms, lane, p.act, sp.bias);
+        float b[4];
+        vload<4>(b, sp.bias + c);
+        uint64_t stream = 0;
+        if constexpr (DROP) stream = drop_stream(p.fuse);
+#pragma unroll
+        for (int ps = 0; ps < PASSES; ++ps) {
+            const int rr = ps * RPP + lane / G;
+            float o[4];
+            vload<4>(o, T + rr * STRIDE + c);
+            // (every lane of the wave takes part in the shuffles; a row's lanes are live or not together, and a dead row stores nothing)
+            uint32_t word = spectral_finish<4, DROP>(p.fuse, stream, rows[ps], c, b, o) << (c & 31);
+#pragma unroll
+            for (int m = 1; m < GW; m <<= 1) word |= (uint32_t)__shfl_xor((int)word, m);
+            if (!live[ps]) continue;
+            R::template store<4>(p, rows[ps] * p.ldo, c, o, false);
+            if (sp.gate != nullptr && sub % GW == 0) sp.gate[rows[ps] * WORDS + (c >> 5)] = word;
+        }
+        return;
+    }
     tile_times_Ms<NT>(T, Ms, lane, p.act);
 #pragma unroll
     for (int ps = 0; ps < PASSES; ++ps) {
@@ -439,6 +504,87 @@ void launch_feature_dropout(const float *X, int64_t ldx, const int32_t *rows, in
                     [&](auto V, unsigned grid) { GNX_LAUNCH(k_feature_dropout<V()>, grid, X, ldx, rows, n, C, fd, out, ldo); });
 }
 
+// The spectral form's row pass behind the dense kernel (hub rows; every row of the other widths): out[r, :] holds act(P') and leaves as
+// 2 drop(act(P') - bias) in place, the row's gate words written beside it (gate may be null) -- spectral_finish, the store loop's own
+// code.  A thread per gate word: up to 32 columns of row rows[i] (null: row i), any width and row stride.
+template <bool DROP>
+__global__ __launch_bounds__(256) void k_spectral_tail(float *out, int64_t ldo, const int32_t *__restrict__ rows, int64_t n, int64_t C,
+                                                      const float *__restrict__ bias, const DropFuse fd, uint32_t *__restrict__ gate) {
+    const int64_t words = (C + 31) / 32, total = n * words, stride = (int64_t)gridDim.x * blockDim.x;
+    uint64_t stream = 0;
+    if constexpr (DROP) stream = drop_stream(fd);
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const int64_t i = e / words, w = e % words, r = rows ? (int64_t)rows[i] : i;
+        const int64_t c0 = 32 * w, c1 = c0 + 32 < C ? c0 + 32 : C;
+        float *o = out + r * ldo;
+        uint32_t word = 0;
+        for (int64_t c = c0; c < c1; ++c) {
+            float x[1] = {o[c]};
+            const float b[1] = {bias[c]};
+            word |= spectral_finish<1, DROP>(fd, stream, r, c, b, x) << (c - c0);
+            o[c] = x[0];
+        }
+        if (gate != nullptr) gate[r * words + w] = word;
+    }
+}
+
+void launch_spectral_tail(float *out, int64_t ldo, const int32_t *rows, int64_t n, int64_t C, const float *bias, const DropFuse *fd,
+                          uint32_t *gate, hipStream_t s) {
+    if (n == 0 || C == 0) return;
+    const unsigned grid = (unsigned)std::min<int64_t>(blocks_for(n * ((C + 31) / 32), 256), 1 << 20);
+    if (fd) GNX_LAUNCH(k_spectral_tail<true>, grid, out, ldo, rows, n, C, bias, *fd, gate);
+    else    GNX_LAUNCH(k_spectral_tail<false>, grid, out, ldo, rows, n, C, bias, DropFuse{}, gate);
+}
+
+// The first pass of the spectral form's backward (gnx_gcnii_spectral_back): u = 2 drop(g) with the forward's mask, G' = gate ? u : 0
+// (RELU; the identity has no gate: G' = u) and the bias gradient dbias[c] = -sum_i (gate ? 0 : u[i, c]): act(P') - bias depends on
+// the bias through the -bias alone where the relu is shut, and not at all where it is open.
+// No float atomics, nothing depends on the device: block b takes the rows b rpb .. (b + 1) rpb - 1, rpb = ceil(n / gridDim.x); a
+// thread holds VEC columns and walks its rows -- every RL-th of the block's, RL = 256 / (threads per row) -- in ascending order, the
+// block adds its RL row lanes in lane order through LDS and writes slab b of `work` ([C] each); the host's grid is a function of
+// (n, C) alone and the slabs are added in index order by sum_slabs.  blockIdx.y: panels of 256 VEC columns.  G may be g.
+template <int VEC, bool RELU>
+__global__ __launch_bounds__(256) void k_spectral_back(const float *g, int64_t ldg, const uint32_t *__restrict__ gate, int64_t n, int64_t C,
+                                                      const DropFuse fd, float *G, int64_t ldG, float *__restrict__ work) {
+    __shared__ float sm[256 * VEC];
+    const int64_t per_row = C / VEC, first = (int64_t)blockIdx.y * 256, words = (C + 31) / 32;
+    const int tpr = (int)(per_row - first < 256 ? per_row - first : 256), RL = 256 / tpr;
+    const int cg = threadIdx.x % tpr, rl = threadIdx.x / tpr;
+    const int64_t c = (first + cg) * VEC;
+    const int64_t rpb = (n + gridDim.x - 1) / gridDim.x, row0 = (int64_t)blockIdx.x * rpb, row1 = row0 + rpb < n ? row0 + rpb : n;
+    const uint64_t stream = drop_stream(fd);
+    float acc[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
+    if (rl < RL) {
+        for (int64_t r = row0 + rl; r < row1; r += RL) {
+            float x[VEC];
+            vload<VEC>(x, g + r * ldg + c);
+            drop_values<VEC>(fd, stream, r, c, x);
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) x[v] *= 2.f;
+            if constexpr (RELU) {
+                const uint32_t word = gate[r * words + (c >> 5)] >> (c & 31);      // (VEC columns from c: one word, c % VEC == 0)
+#pragma unroll
+                for (int v = 0; v < VEC; ++v)
+                    if (!((word >> v) & 1u)) { acc[v] -= x[v]; x[v] = 0.f; }
+            }
+            vstore<VEC>(G + r * ldG + c, x);
+        }
+    }
+    if constexpr (RELU) {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) sm[threadIdx.x * VEC + v] = acc[v];
+        __syncthreads();
+        if (rl == 0) {
+            for (int k = 1; k < RL; ++k)
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) acc[v] += sm[(k * tpr + cg) * VEC + v];
+            vstore<VEC>(work + (int64_t)blockIdx.x * C + c, acc);
+        }
+    }
+}
+
 // The backward's gate in one pass: G = kept ? g * scale : +0, and with RELU also +0 where y <= 0 (y = the DROPPED forward output, so
 // y > 0 implies kept: the hash is taken only where y lets the value through, the same bits either way).  G may be g.
 template <int VEC, bool RELU>
@@ -574,6 +720,8 @@ struct ForwardForm {             // what differs between its entries
     int out_bf16;                // the result is stored as bf16 (the bf16 entries)
     bool composes;               // the other widths / alignments run as two launches; false: they are refused (refuse_unfused)
     const char *fused, *composed;   // what gnx_graph_last_kernel reports
+    const float *bias = nullptr;    // [C]: the spectral form (gnx_gcnii_step_spectral, F32Rows only), out = 2 drop(act(T . M + bias) - bias)
+    uint32_t *gate = nullptr;       // the spectral form's gate words [n, ceil(C / 32)], or null
 };
 
 template <typename R>
@@ -591,8 +739,11 @@ int gcnii_forward(const char *fn, gnx_graph *g, const float *d_vals, const typen
                   "%s: d_mixed must be a buffer of its own", fn);
     GNX_CHECK_ARG(f.work == nullptr || (f.work != out && f.work != H && f.work != d_H0 && f.work != d_M && f.work != d_vals && f.work != f.mixed),
                   "%s: d_work must be a buffer of its own", fn);
+    auto own = [&](const void *b) { return b != out && b != H && b != d_H0 && b != d_M && b != d_vals && b != f.mixed && b != f.work; };
+    GNX_CHECK_ARG(f.bias == nullptr || own(f.bias), "%s: d_bias must be a buffer of its own", fn);
+    GNX_CHECK_ARG(f.gate == nullptr || (own(f.gate) && (const void *)f.gate != f.bias), "%s: d_gate must be a buffer of its own", fn);
     const bool fusable = fused_width(C) && aligned(d_H, 4 * sizeof(typename R::Elem)) && aligned(d_H0, 16) && aligned(d_out, f.out_bf16 ? 8 : 16) &&
-                         aligned(f.mixed, 16) && aligned(f.work, 16);
+                         aligned(f.mixed, 16) && aligned(f.work, 16) && aligned(f.bias, 16);
     if (!fusable && !f.composes) return refuse_unfused(fn, C);
     const Csr &m = g->a;
     // the rows that go through memory -- every row of the two launches, the hub rows of the fused one -- need a place to be
@@ -614,9 +765,10 @@ int gcnii_forward(const char *fn, gnx_graph *g, const float *d_vals, const typen
     // rows of its own tile before it stores them, as long as the result is ONE column panel)
     auto transform_rows = [&](float *T, const int32_t *rows, int64_t n) -> int {
         float *to = f.out_bf16 ? f.work : static_cast<float *>(d_out);
-        const int err = dense_rows(T, C, n, C, d_M, ldm, C, nullptr, act, rows, rows, to, C, s);
+        const int err = dense_rows(T, C, n, C, d_M, ldm, C, f.bias, act, rows, rows, to, C, s);
         if (err != GNX_OK) return err;
-        if (f.fd) launch_feature_dropout(to, C, rows, n, C, *f.fd, to, C, s);
+        if (f.bias) launch_spectral_tail(to, C, rows, n, C, f.bias, f.fd, f.gate, s);      // (- bias, the mask, x 2 and the gate words)
+        else if (f.fd) launch_feature_dropout(to, C, rows, n, C, *f.fd, to, C, s);
         if (f.out_bf16) round_rows(to, rows, n, C, (uint16_t *)d_out, s);
         GNX_HIP(hipGetLastError());
         return GNX_OK;
@@ -644,8 +796,16 @@ int gcnii_forward(const char *fn, gnx_graph *g, const float *d_vals, const typen
         if (rc != GNX_OK) return rc;
     }
     with_tile_width(C, m.n_rows, [&](auto NT, dim3 grid) {
-        if (f.fd) hipLaunchKernelGGL((k_spmm_gcnii<R, NT(), 4, 8, true>), grid, dim3(512), 0, s, p, d_M, ldm, f.mixed);
-        else      hipLaunchKernelGGL((k_spmm_gcnii<R, NT(), 4, 8>), grid, dim3(512), 0, s, p, d_M, ldm, f.mixed);
+        if constexpr (!R::BF16) {
+            if (f.bias) {
+                const SpectralArgs<true> sp{f.bias, f.gate};
+                if (f.fd) hipLaunchKernelGGL((k_spmm_gcnii<R, NT(), 4, 8, true, true>), grid, dim3(512), 0, s, p, d_M, ldm, f.mixed, sp);
+                else      hipLaunchKernelGGL((k_spmm_gcnii<R, NT(), 4, 8, false, true>), grid, dim3(512), 0, s, p, d_M, ldm, f.mixed, sp);
+                return;
+            }
+        }
+        if (f.fd) hipLaunchKernelGGL((k_spmm_gcnii<R, NT(), 4, 8, true>), grid, dim3(512), 0, s, p, d_M, ldm, f.mixed, SpectralArgs<false>{});
+        else      hipLaunchKernelGGL((k_spmm_gcnii<R, NT(), 4, 8>), grid, dim3(512), 0, s, p, d_M, ldm, f.mixed, SpectralArgs<false>{});
     });
     g->last_kernel = f.fused;
     if (m.n_long == 0) {
@@ -800,6 +960,62 @@ int gnx_gcnii_step_drop(gnx_graph_t g, const float *d_vals, const float *d_H, co
     const ForwardForm f{drop ? &fd : nullptr, d_mixed, nullptr, 0, true, drop ? "spmm_gcnii_mfma_drop" : "spmm_gcnii_mfma",
                         drop ? "spmm+dense_mfma_drop" : "spmm+dense_mfma"};
     return gcnii_forward<F32Rows>("gnx_gcnii_step_drop", g, d_vals, d_H, d_H0, a, C, d_M, ldm, act, d_out, f, stream);
+}
+
+// (the gate words are the relu's: with the identity there is nothing to gate and d_gate is not looked at)
+int gnx_gcnii_step_spectral(gnx_graph_t g, const float *d_vals, const float *d_H, const float *d_H0, float a, int64_t C, const float *d_M,
+                            int64_t ldm, const float *d_bias, int act, double dropout_p, uint64_t seed, uint64_t stream_id, float *d_out,
+                            float *d_mixed, uint32_t *d_gate, void *stream) {
+    const char *fn = "gnx_gcnii_step_spectral";
+    DropFuse fd{};
+    int rc = make_feat_drop(fn, g, dropout_p, seed, stream_id, fd);
+    if (rc != GNX_OK) return rc;
+    GNX_CHECK_ARG(d_bias != nullptr, "%s: NULL bias", fn);
+    // (at the other widths d_mixed is the buffer every call passes its mixed rows through, and says nothing about training)
+    GNX_CHECK_ARG(act != GNX_ACT_RELU || d_mixed == nullptr || d_gate != nullptr || !fused_width(C),
+                  "%s: relu with d_mixed (training) needs d_gate [n, ceil(C / 32)] (the backward's gate)", fn);
+    const bool drop = dropout_p != 0.0;      // p == 0 hashes nothing
+    const ForwardForm f{drop ? &fd : nullptr, d_mixed, nullptr, 0, true, drop ? "spmm_gcnii_spectral_mfma_drop" : "spmm_gcnii_spectral_mfma",
+                        drop ? "spmm+dense_mfma_spectral_drop" : "spmm+dense_mfma_spectral", d_bias, act == GNX_ACT_RELU ? d_gate : nullptr};
+    return gcnii_forward<F32Rows>(fn, g, d_vals, d_H, d_H0, a, C, d_M, ldm, act, d_out, f, stream);
+}
+
+int gnx_gcnii_spectral_back(gnx_graph_t g, const float *d_g, int64_t ldg, const uint32_t *d_gate, int64_t n_rows, int64_t C, int act,
+                            double dropout_p, uint64_t seed, uint64_t stream_id, float *d_G, int64_t ldG, float *d_dbias, float *d_work,
+                            int64_t work_floats, void *stream) {
+    const char *fn = "gnx_gcnii_spectral_back";
+    GNX_CHECK_ARG(g != nullptr, "%s: NULL handle", fn);
+    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU, "%s: invalid activation %d", fn, act);
+    GNX_CHECK_ARG(n_rows >= 0 && C >= 1 && C <= (1 << 20), "%s: negative row count or C not in [1, 2^20]", fn);
+    GNX_CHECK_ARG(d_g != nullptr && d_G != nullptr && d_dbias != nullptr && ldg >= C && ldG >= C, "%s: NULL g / G / dbias or a row stride below C", fn);
+    GNX_CHECK_ARG(d_G != d_g || ldG == ldg, "%s: in place needs ldG == ldg", fn);
+    const bool relu = act == GNX_ACT_RELU;
+    const int64_t slabs = std::max<int64_t>(1, std::min<int64_t>(2048, blocks_for(n_rows, 256)));      // a function of n alone
+    const void *gate = d_gate, *work = d_work;
+    GNX_CHECK_ARG(!relu || (gate != nullptr && gate != d_g && gate != d_G), "%s: relu needs d_gate (not g / G itself)", fn);
+    GNX_CHECK_ARG(d_dbias != d_g && d_dbias != d_G && (!relu || d_dbias != gate), "%s: dbias must be a buffer of its own", fn);
+    GNX_CHECK_ARG(!relu || (work != nullptr && work != d_g && work != d_G && work != gate && work != d_dbias),
+                  "%s: d_work must be a buffer of its own", fn);
+    GNX_CHECK_ARG(!relu || work_floats >= slabs * C, "%s: work_floats %lld below %lld = min(2048, ceil(n_rows / 256)) slabs of C floats", fn,
+                  (long long)work_floats, (long long)(slabs * C));
+    DropFuse fd{};
+    int rc = make_feat_drop(fn, g, dropout_p, seed, stream_id, fd);
+    if (rc != GNX_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (!relu || n_rows == 0) GNX_HIP(hipMemsetAsync(d_dbias, 0, (size_t)C * sizeof(float), s));      // the identity: exact zeros
+    if (n_rows == 0) return GNX_OK;
+    const bool v4 = C % 4 == 0 && ldg % 4 == 0 && ldG % 4 == 0 && aligned(d_g, 16) && aligned(d_G, 16) && (!relu || aligned(d_work, 16));
+    const dim3 grid((unsigned)slabs, blocks_for(v4 ? C / 4 : C, 256));
+    if (v4) {
+        if (relu) GNX_LAUNCH((k_spectral_back<4, true>), grid, d_g, ldg, d_gate, n_rows, C, fd, d_G, ldG, d_work);
+        else      GNX_LAUNCH((k_spectral_back<4, false>), grid, d_g, ldg, d_gate, n_rows, C, fd, d_G, ldG, d_work);
+    } else {
+        if (relu) GNX_LAUNCH((k_spectral_back<1, true>), grid, d_g, ldg, d_gate, n_rows, C, fd, d_G, ldG, d_work);
+        else      GNX_LAUNCH((k_spectral_back<1, false>), grid, d_g, ldg, d_gate, n_rows, C, fd, d_G, ldG, d_work);
+    }
+    if (relu) sum_slabs(d_work, slabs, C, d_dbias, s);
+    GNX_HIP(hipGetLastError());
+    return GNX_OK;
 }
 
 int gnx_gcnii_step_bf16(gnx_graph_t g, const float *d_vals, const uint16_t *d_H, const float *d_H0, float a, int64_t C, const float *d_M,

@@ -51,7 +51,7 @@ class GNN(Trainable):
 
     def __init__(self, graph, features, preprocessor: Layer = None, reorder=None, inference_dtype=torch.float32,
                  training_dtype=torch.float32, train_gather_order="auto", gcnii_backward="composed", feature_dropout="torch",
-                 gcnii_training_dtype=torch.float32, gcnii_weight_gradient="stored"):
+                 gcnii_training_dtype=torch.float32, gcnii_weight_gradient="stored", gcnii_spectral="composed"):
         """``reorder`` (opt-in, not in the reference): store the graph and the feature rows with the vertices relabelled; every
         [N, .] tensor inside the model then lives in that order, and the model's OUTPUT is put back into the caller's order, so
         tasks, labels and node ids are unaffected.  Results agree with the unordered model to float32 rounding.
@@ -133,7 +133,24 @@ class GNN(Trainable):
         summation order: why it is opt-in); works with either ``gcnii_backward``; ``train(capture=True)`` equals the eager run bit for
         bit under fused dropout, as before.  GCNIISpectralPreservingLayer, other activations, add_eye, other widths, dropped
         adjacencies, CPU tensors and the vertex-partitioned path keep today's path whatever it says (measurement: profiles/NOTES.md
-        "GCNII weight gradient without stored rows")."""
+        "GCNII weight gradient without stored rows").
+        ``gcnii_spectral`` (not in the reference): ``"composed"`` (the default: today's calls and bits) or ``"fused"``
+        (sparse.gcnii_step_spectral).  ``"fused"``: every GCNIISpectralPreservingLayer (that class itself, relu or the identity as
+        activation, float32 device tensors, a constant adjacency without add_eye) runs 2 * dropout(act(T . M + bias) - bias) as ONE
+        launch (gnx_gcnii_step_spectral) instead of the SpMM+mix, the dense kernel and three elementwise passes, in eval mode and in
+        training mode alike.  In training mode with 0 < ``dropout`` < 1 the mask leaves the same launch and is the COUNTER RNG's, not
+        torch's: element (i, c) of the layer's ``_next_mask_stream()`` stream is kept iff hash_u24(seed, stream, i, c, 0) >= int(p * 2^24),
+        kept values times the f32 1 / (1 - p), as for ``feature_dropout="fused"`` -- the masks differ from torch's, which is why the
+        switch is opt-in; a training step is then reproducible from (seed, stream) alone and ``train(capture=True)`` equals the eager
+        run bit for bit.  For its backward the layer saves the mixed rows T and ONE BIT per element (the sign of the pre-activation) --
+        4 bytes and a bit per element instead of 9 bytes -- and starts it with one gate pass (gnx_gcnii_spectral_back) that also makes
+        the bias gradient; it honours ``gcnii_backward``.  The eval-mode result agrees with the composed one to float32 rounding (the
+        same sums; the bias is added inside the matrix-core epilogue either way).  Plain GCNIILayer stacks and every other keyword on
+        them, ``feature_dropout="fused"`` on a spectral stack (which that switch never touched), the bf16 switches, other activations,
+        a rate of 1 or more, dropped adjacencies, add_eye, CPU tensors, GCNSpectralPreservingLayer and the vertex-partitioned path keep
+        today's path and bits whatever it says (measurement: profiles/NOTES.md "Fused spectral-preserving GCNII layer")."""
+        if gcnii_spectral not in sparse.GCNII_SPECTRALS:
+            raise Exception("GNN: gcnii_spectral must be one of " + ", ".join(repr(f) for f in sparse.GCNII_SPECTRALS))
         if feature_dropout not in FEATURE_DROPOUTS:
             raise Exception("GNN: feature_dropout must be one of " + ", ".join(repr(f) for f in FEATURE_DROPOUTS))
         if gcnii_backward not in sparse.GCNII_BACKWARDS:
@@ -156,6 +173,7 @@ class GNN(Trainable):
         self.gcnii_backward = gcnii_backward
         self.gcnii_weight_gradient = gcnii_weight_gradient
         self.feature_dropout = feature_dropout
+        self.gcnii_spectral = gcnii_spectral
         self._order = self._newid = None
         self.reorder_used, self.locality_share = None, None
         if isinstance(graph, sparse.DeviceGraph):
@@ -596,17 +614,34 @@ class GCNIILayer(Layer):
 class GCNIISpectralPreservingLayer(GCNIILayer):
     """gcn.py:30-51: GCNIILayer with a bias added before the activation and removed after it, and the dropout's survivors
     doubled: 2 * dropout(act(T.M + bias) - bias), T = (1-a) A.H + a H0, M = (1-b) I + b W.  The propagation + mix is the fused
-    SpMM kernel; the transform carries the bias and the relu in the matrix-core kernel's epilogue."""
+    SpMM kernel; the transform carries the bias and the relu in the matrix-core kernel's epilogue.
+    On a GNN with ``gcnii_spectral="fused"`` the whole layer is ONE launch (gnx_gcnii_step_spectral), in training mode with the
+    counter RNG's dropout mask instead of torch's, and its backward keeps the mixed rows and one gate bit per element (GNN.__init__)."""
 
     def __build__(self, architecture, H0, a, l, k=0, **kwargs):
         shape = super().__build__(architecture, H0, a, l, k, **kwargs)
         self.bias = architecture.create_var((1, shape[1]), "zero")
         return shape
 
+    def _fused_spectral(self, gcn, features, adjacency) -> bool:
+        """Whether GNN(gcnii_spectral="fused") applies to this forward (no tensor is read, no mask stream is drawn)."""
+        return (getattr(gcn, "gcnii_spectral", "composed") == "fused" and type(self) is GCNIISpectralPreservingLayer
+                and (self.activation is relu or self.activation is linear)
+                and isinstance(features, torch.Tensor) and features.is_cuda and features.dtype == torch.float32
+                and isinstance(self.a, (int, float)) and not isinstance(self.a, bool)
+                and not isinstance(adjacency, sparse.DroppedAdjacency) and adjacency.diag is None
+                and (not gcn.is_training() or 0 <= self.dropout < 1))       # (a rate of 1 or more stays with torch and what it makes of it)
+
     def __forward__(self, gcn, features):
+        adjacency = gcn.get_adjacency(self.graph_dropout)
+        if self._fused_spectral(gcn, features, adjacency):
+            triple = (self.dropout,) + tuple(gcn._next_mask_stream()) if gcn.is_training() and self.dropout != 0 else None
+            return sparse.gcnii_step_spectral(adjacency, features, self.H0.value, self.a, self._transform(), self.bias,
+                                              relu=self.activation is relu, dropout=triple,
+                                              backward=getattr(gcn, "gcnii_backward", "composed"))
         b = self.beta_transformer(self.l / (self.k + 1))
         eye = torch.eye(self.W.shape[1], device=self.W.device, dtype=self.W.dtype)
-        tradeoff = sparse.ppr_step(gcn.get_adjacency(self.graph_dropout), features, self.H0.value, self.a)
+        tradeoff = sparse.ppr_step(adjacency, features, self.H0.value, self.a)
         activated = affine(tradeoff, (1 - b) * eye + b * self.W, self.bias, self.activation)
         return 2 * gcn.dropout(activated - self.bias, self.dropout)
 

@@ -1358,6 +1358,132 @@ def _gcnii_step_dropped(adj, H, H0, a, M, relu, backward, dropout, recompute=Fal
     return _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=False, dropout=dropout)[0]
 
 
+GCNII_SPECTRALS = ("composed", "fused")
+
+
+def _gate_words(C: int) -> int:
+    """Words per row of the spectral layer's gate bits (include/gnx.h: bit c & 31 of word row * ceil(C / 32) + (c >> 5))."""
+    return (C + 31) // 32
+
+
+def _gcnii_spectral_launch(adj: Adjacency, H, H0, a, M, bias, relu, keep, dropout=None):
+    """gnx_gcnii_step_spectral; returns (out, T, gate).  ``keep`` (training): the launch also writes the undropped mixed rows T and, with
+    ``relu``, the gate words (int32 [n, ceil(C / 32)]: one bit per element, P' > 0); both None otherwise, except that the widths
+    other than 16 / 32 / 64 pass their mixed rows through memory in any case.  ``dropout`` = the checked (p, seed, stream) or None."""
+    nat.require_cuda(H, H0, M, bias)
+    H, H0, M = _as_f32_rows(H).contiguous(), _as_f32_rows(H0).contiguous(), _as_f32_rows(M)
+    g, C = _gcnii_operands("gcnii_step_spectral", adj, H, (H0,), M, "the fused spectral layer")
+    b = bias.to(torch.float32).reshape(-1).contiguous()
+    if b.numel() != C or b.device != H.device:
+        raise Exception("gcnii_step_spectral: the bias must hold one value per column, on the rows' device")
+    out = torch.empty_like(H)
+    mixed = torch.empty_like(H) if keep or C not in GCNII_FUSED_WIDTHS else None
+    gate = torch.empty((H.shape[0], _gate_words(C)), dtype=torch.int32, device=H.device) if keep and relu else None
+    p, seed, stream = dropout if dropout is not None else (0.0, 0, 0)
+    with nat.on_device(H.device):
+        nat.check(nat.lib().gnx_gcnii_step_spectral(g.handle, nat.ptr(adj.vals), nat.ptr(H), nat.ptr(H0), float(a), C, nat.ptr(M), M.stride(0),
+                                                    nat.ptr(b), nat.ACT_RELU if relu else nat.ACT_NONE, p, seed, stream, nat.ptr(out),
+                                                    nat.ptr(mixed), nat.ptr(gate), nat.current_stream()))
+    return out, mixed if keep else None, gate
+
+
+def _gcnii_spectral_gate(graph: DeviceGraph, g, gate, relu, dropout=None):
+    """gnx_gcnii_spectral_back: (G', dbias) from the upstream gradient ``g``, the forward's gate words and its dropout triple:
+    u = 2 drop(g), G' = gate ? u : 0, dbias[c] = -sum_i (gate ? 0 : u[i, c]); without ``relu`` G' = u and dbias = 0."""
+    g = _as_f32_rows(g).contiguous()
+    nat.require_cuda(g, gate)
+    _same_device(graph, g, gate)
+    n, C = g.shape
+    if relu and (gate is None or gate.dtype != torch.int32 or tuple(gate.shape) != (n, _gate_words(C)) or not gate.is_contiguous()):
+        raise Exception("gcnii_step_spectral: the gate words must be a contiguous int32 [n, ceil(C / 32)]")
+    G = torch.empty_like(g)
+    dbias = torch.empty(C, dtype=torch.float32, device=g.device)
+    if C == 0:
+        return G, dbias
+    slabs = max(1, min(2048, (n + 255) // 256))                      # include/gnx.h: a function of n alone
+    work = torch.empty(slabs * C, dtype=torch.float32, device=g.device) if relu else None
+    p, seed, stream = dropout if dropout is not None else (0.0, 0, 0)
+    with nat.on_device(g.device):
+        nat.check(nat.lib().gnx_gcnii_spectral_back(graph.handle, nat.ptr(g), g.stride(0), nat.ptr(gate) if relu else None, n, C,
+                                                    nat.ACT_RELU if relu else nat.ACT_NONE, p, seed, stream, nat.ptr(G), G.stride(0),
+                                                    nat.ptr(dbias), nat.ptr(work), 0 if work is None else work.numel(),
+                                                    nat.current_stream()))
+    return G, dbias
+
+
+class _GCNIISpectralStep(torch.autograd.Function):
+    """out = 2 drop(act(T . M + bias) - bias), T = (A . H)(1-a) + H0 a, as ONE launch (gnx_gcnii_step_spectral) that leaves T and one
+    gate bit per element (P' > 0) for the backward: (T, M, gate) is all that is saved -- neither act(P') nor out.  backward: the gate
+    pass (gnx_gcnii_spectral_back: u = 2 drop(g), G' = gate ? u : 0, dbias = -sum of the gated-off u), dM = T^T G' (gnx_dense_wgrad),
+    then dH and dH0 from G' as in _GCNIIStep: composed (gnx_dense + the transposed SpMM) or ``backward="fused"`` (gcnii_step_back)."""
+
+    @staticmethod
+    def forward(ctx, H, H0, M, bias, adj, a, relu, backward, dropout):
+        ctx.adj, ctx.a, ctx.relu, ctx.fused_backward, ctx.dropout, ctx.bias_shape = adj, a, relu, backward == "fused", dropout, tuple(bias.shape)
+        out, T, gate = _gcnii_spectral_launch(adj, H, H0, a, M, bias, relu, keep=True, dropout=dropout)
+        ctx.save_for_backward(T, M, gate)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        T, M, gate = ctx.saved_tensors
+        G, gbias = _gcnii_spectral_gate(ctx.adj.graph, g, gate, ctx.relu, ctx.dropout)
+        gM = _dense_wgrad(T, G) if ctx.needs_input_grad[2] else None
+        gH = gH0 = None
+        if ctx.fused_backward and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            gH, gH0 = gcnii_step_back(ctx.adj, G, ctx.a, M.t().contiguous(), want_S=ctx.needs_input_grad[1])
+            gH = gH if ctx.needs_input_grad[0] else None
+        elif ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            gT = _dense_launch(G, M.t().contiguous(), None, False)
+            if ctx.needs_input_grad[0]:
+                gH = _launch(ctx.adj, gT, None, 1.0 - ctx.a, 0.0, nat.ACT_NONE, transposed=True)
+            if ctx.needs_input_grad[1]:
+                gH0 = gT * ctx.a
+        gbias = gbias.reshape(ctx.bias_shape) if ctx.needs_input_grad[3] else None
+        return gH, gH0, gM, gbias, None, None, None, None, None
+
+
+def _spectral_composed(adj, H, H0, a, M, bias, relu, dropout):
+    """The layer as today's ops: ppr_step, the dense kernel with bias and relu, then torch's elementwise tail (torch's dropout)."""
+    T = ppr_step(adj, H, H0, a)
+    if T.is_cuda:
+        activated = dense(T, M, bias, relu)
+    else:
+        activated = torch.matmul(T, M) + bias
+        activated = torch.relu(activated) if relu else activated
+    y = activated - bias
+    p = 0.0 if dropout is None else float(dropout[0])
+    return 2 * (torch.nn.functional.dropout(y, p=p, training=True) if p != 0 else y)
+
+
+def gcnii_step_spectral(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, M: torch.Tensor, bias: torch.Tensor, relu=True,
+                        dropout=None, backward="composed") -> torch.Tensor:
+    """GCNIISpectralPreservingLayer (gcn.py:30-51) as one launch (gnx_gcnii_step_spectral; opt-in, GNN(gcnii_spectral="fused")):
+    2 * drop(act(T . M + bias) - bias) with T = (A . H)(1-a) + H0 a, M = (1-b) I + b W and ``bias`` [C] / [1, C].  The bias joins the
+    product on the matrix cores before the activation; - bias, the mask and the doubling happen as the rows are stored.  C in
+    {16, 32, 64} is ONE launch; other widths run the SpMM+mix, the dense kernel and one row pass.
+    ``dropout`` = ``(p, seed, stream)`` or None: the mask of ``feature_dropout`` -- the counter RNG of the edge dropout, NOT torch's
+    generator: element (i, c) is kept iff hash_u24(seed, stream + counter, i, c, 0) >= int(p * 2^24), kept values times the f32 1 / (1 - p).
+    Without autograd nothing but the result is written.  Under autograd it is one node that saves (T, M, gate) -- the mixed rows for
+    dM = T^T G', and ONE BIT per element (P' > 0) packed into int32 words [n, ceil(C / 32)] instead of the activated rows, the result and
+    a byte mask -- and returns the gradients of H, H0, M and bias: first one gate pass (gnx_gcnii_spectral_back: G' = gate ? 2 drop(g) : 0
+    and dbias, a fixed-order sum without atomics), then gnx_dense_wgrad, then by ``backward`` the composed gnx_dense + transposed SpMM or
+    ``gcnii_step_back`` (gcnii_step's ``backward``).
+    The composed path -- ppr_step, the dense kernel, torch's elementwise tail with TORCH's dropout at rate p -- is kept for a
+    DroppedAdjacency, an adjacency with a diagonal, CPU tensors and a rate outside [0, 1).  (``weight_gradient="recomputed"`` is not
+    offered: the layer would save its input in place of T, the same 4 bytes per element.)"""
+    if backward not in GCNII_BACKWARDS:
+        raise Exception("gcnii_step_spectral: backward must be one of " + ", ".join(repr(b) for b in GCNII_BACKWARDS))
+    rate = 0.0 if dropout is None else float(dropout[0])
+    if (isinstance(adj, DroppedAdjacency) or adj.diag is not None or not (H.is_cuda and H0.is_cuda and M.is_cuda and bias.is_cuda)
+            or not 0.0 <= rate < 1.0):
+        return _spectral_composed(adj, H, H0, a, M, bias, bool(relu), dropout)
+    dropout = _dropout_triple(dropout, "gcnii_step_spectral")
+    if torch.is_grad_enabled() and (H.requires_grad or H0.requires_grad or M.requires_grad or bias.requires_grad):
+        return _GCNIISpectralStep.apply(H, H0, M, bias, adj, float(a), bool(relu), backward, dropout)
+    return _gcnii_spectral_launch(adj, H, H0, a, M, bias, bool(relu), keep=False, dropout=dropout)[0]
+
+
 # the model-level bf16 path of GCNIILayer (graph_model.py) keeps f32 below this width.  tools/gcnii_bf16_bench.py is the measurement
 # it is to be set from (profiles/NOTES.md "bf16 storage in the GCNII layer": no table recorded yet); until then it stands where the
 # plain SpMM's measurements put it: up to 32 columns a gathered row is one 128-byte line in either format (a wash at C = 17 ... 32,

@@ -62,7 +62,8 @@ const char *gnx_last_error(void);
  * gnx_gcnii_step_back (the fused backward of the GCNII layer), likewise, and the feature dropout of the GCNII training layer
  * (gnx_gcnii_step_drop, gnx_feature_dropout, gnx_feature_dropout_back), likewise, and the bf16 row storage of GCNII training
  * (gnx_gcnii_step_train_bf16, gnx_feature_dropout_back_bf16, gnx_gcnii_step_back_bf16), likewise, and the GCNII weight gradient
- * without stored mixed rows (gnx_gcnii_wgrad, gnx_gcnii_wgrad_bf16, gnx_gcnii_step_drop_bf16, gnx_graph_hub_rows), likewise. */
+ * without stored mixed rows (gnx_gcnii_wgrad, gnx_gcnii_wgrad_bf16, gnx_gcnii_step_drop_bf16, gnx_graph_hub_rows), likewise, and the
+ * spectral-preserving GCNII layer in one launch (gnx_gcnii_step_spectral, gnx_gcnii_spectral_back), likewise. */
 #define GNX_ABI_VERSION 900
 int gnx_version(void);
 
@@ -569,6 +570,44 @@ int gnx_gcnii_step_drop_bf16(gnx_graph_t g, const float *d_vals, const uint16_t 
                              const float *d_M, int64_t ldm, int act, double dropout_p, uint64_t seed, uint64_t stream_id,
                              void *d_out, int out_bf16, float *d_work, void *stream);
 
+/* The spectral-preserving GCNII layer (gcn.py:30-51) as one launch (opt-in; added within ABI 0.9 -- probe for the symbols), f32 rows:
+ *   out = 2 * drop(act(P') - bias),   P' = T . M + bias,   T = (1-a) A . H + a H0
+ * with drop, its mask and its scale s those of gnx_gcnii_step_drop above (p == 0 hashes nothing: out = 2 * (act(P') - bias)).
+ *
+ * gnx_gcnii_step_spectral: the launch of gnx_gcnii_step / gnx_gcnii_step_drop with another epilogue; d_bias is [C] f32.  Rounding
+ * points: P' = fl(T . M + bias[c]), the bias added to the accumulator value as it leaves the matrix-core block, before the
+ * activation; then Y = fl(act(P') - bias[c]), and out = 2 * (kept ? fl(Y * s) : +0).  d_mixed, when given, receives the undropped T,
+ * bit for bit that of gnx_gcnii_step.
+ * d_gate (uint32_t [n, ceil(C / 32)] contiguous; written for GNX_ACT_RELU only, may be NULL in inference): one bit per element,
+ *   bit (c & 31) of word row * ceil(C / 32) + (c >> 5)  =  (P'[row, c] > 0);
+ * the bits above C of a row's last word (the upper 16 at C = 16, the upper 8 of the one word at C = 24) are 0.  The gate is taken from
+ * the pre-activation itself -- fl(relu(P') - bias) equals -bias for a tiny positive P', so it cannot be read back from out -- and is all
+ * the backward needs of the forward: neither act(P') nor out has to be kept.  Every row's words are written whole by ONE lane with a
+ * plain vector store (the lanes of a row OR their bits together first): no atomics.
+ * Hub rows take the long-row kernels and the dense kernel (with the bias) on those rows alone, as in gnx_gcnii_step, and then a row-list
+ * pass that applies - bias, the mask, x 2 and writes their gate words with the store loop's own code: a row has the same bits whichever
+ * path made it.  Widths other than 16 / 32 / 64 (they need d_mixed) and unaligned buffers run gnx_spmm, the dense kernel and that pass
+ * over all rows.  The argument checks of gnx_gcnii_step_drop, and: d_bias non-NULL; d_gate non-NULL when act is GNX_ACT_RELU and
+ * d_mixed is given at one of the three widths (training; at the other widths every call passes d_mixed); d_bias and d_gate buffers of their own.  Its capture and reserve rules.  Reports
+ * "spmm_gcnii_spectral_mfma" / "spmm_gcnii_spectral_mfma_drop" (p > 0), the other widths "spmm+dense_mfma_spectral" /
+ * "spmm+dense_mfma_spectral_drop".
+ *
+ * gnx_gcnii_spectral_back: the first pass of the layer's backward, over rows 0 .. n_rows - 1 of the upstream gradient g (ldg) and the
+ * gate words the forward wrote, with the forward's (p, seed, stream_id):  u = 2 * (kept ? fl(g * s) : +0),
+ *   G'[i, c]  = gate ? u : +0          -- the gradient with respect to P': what gnx_dense_wgrad (dM = T^T G') and the dH / dH0 launches take;
+ *   dbias[c]  = - sum_i (gate ? 0 : u[i, c])   -- where the relu is open the + bias and the - bias cancel, where it is shut - bias is left.
+ * With GNX_ACT_NONE there is no gate (d_gate, d_work may be NULL): G' = u and dbias is written as exact zeros.  d_G may be d_g (with
+ * ldG == ldg); d_dbias is [C].  No float atomics: block b of min(2048, ceil(n_rows / 256)) blocks -- a function of n_rows alone --
+ * takes a contiguous range of rows, adds them in a fixed order into slab b ([C] floats) of d_work, and the slabs are added in index
+ * order, as in gnx_gcnii_wgrad: two calls give the same bits on every device.  work_floats >= min(2048, ceil(n_rows / 256)) * C.  The
+ * handle is read for its dropout counter only.  Reports nothing. */
+int gnx_gcnii_step_spectral(gnx_graph_t g, const float *d_vals, const float *d_H, const float *d_H0, float a, int64_t C,
+                            const float *d_M, int64_t ldm, const float *d_bias, int act, double dropout_p, uint64_t seed,
+                            uint64_t stream_id, float *d_out, float *d_mixed, uint32_t *d_gate, void *stream);
+int gnx_gcnii_spectral_back(gnx_graph_t g, const float *d_g, int64_t ldg, const uint32_t *d_gate, int64_t n_rows, int64_t C, int act,
+                            double dropout_p, uint64_t seed, uint64_t stream_id, float *d_G, int64_t ldG, float *d_dbias,
+                            float *d_work, int64_t work_floats, void *stream);
+
 /* ---- the dense ends of the path (matrix cores) -----------------------------------------------------------------------
  * gnx_dense: out = act(X . W + bias) -- Dense.__forward__ (gnntf/core/nn/layers.py:135-136) and the transform of
  * GCNLayer (gcn.py:89).  X [n, F] (ldx), W [F, O] (ldw), bias [O] or NULL, out [n, O] (ldo); float32 in and out, float32
@@ -703,7 +742,8 @@ int gnx_probe_block_xcd(int64_t n_blocks, int32_t *d_xcd_out, void *stream);
  * two dropout passes report nothing; gnx_gcnii_step_train_bf16 reports "spmm_gcnii_mfma_train_bf16" and gnx_gcnii_step_back_bf16
  * "spmm_gcnii_back_mfma_bf16" (the fused launches, with or without hub rows: those two entries have no other form), and so do
  * gnx_gcnii_step_drop_bf16 ("spmm_gcnii_mfma_drop_bf16"), gnx_gcnii_wgrad ("gcnii_wgrad_mfma") and gnx_gcnii_wgrad_bf16
- * ("gcnii_wgrad_mfma_bf16"). */
+ * ("gcnii_wgrad_mfma_bf16"); gnx_gcnii_step_spectral reports "spmm_gcnii_spectral_mfma" / "spmm_gcnii_spectral_mfma_drop" or
+ * "spmm+dense_mfma_spectral" / "spmm+dense_mfma_spectral_drop" (the other widths / alignments). */
 const char *gnx_graph_last_kernel(gnx_graph_t g);
 
 #ifdef __cplusplus
