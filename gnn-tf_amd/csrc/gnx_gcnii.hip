@@ -8,15 +8,17 @@
 //                      SPEC: the spectral-preserving form (gnx_gcnii_step_spectral) -- the bias in the MFMA block's epilogue, -bias, the
 //                      mask and x 2 in the store loop, one gate bit per element; k_spectral_tail is the same epilogue as a row pass
 //                      (hub rows, the other widths) and k_spectral_back the backward's first pass (gate, bias gradient)
+//                      EDGE: the layer and its backward under edge dropout (gnx_gcnii_step_dropped, gnx_gcnii_step_back_dropped, f32 rows) --
+//                      the gather loops make their weights from the counter RNG (edge_gather) instead of loading them
 //   row passes         k_round_rows (f32 rows -> bf16), k_feature_dropout (the mask as a pass of its own: hub rows, the other widths, the
 //                      generic composition) and the backward's gate (k_feature_dropout_back, .._back_bf16); one launcher
 //                      (launch_row_pass) picks their vector width and grid
-//   gcnii_forward<R>   the host path of gnx_gcnii_step, gnx_gcnii_step_drop (F32Rows), gnx_gcnii_step_bf16, gnx_gcnii_step_train_bf16
+//   gcnii_forward<R>   the host path of gnx_gcnii_step, gnx_gcnii_step_drop, gnx_gcnii_step_dropped (F32Rows), gnx_gcnii_step_bf16, gnx_gcnii_step_train_bf16
 //                      and gnx_gcnii_step_drop_bf16 (Bf16Rows); a ForwardForm says what differs: the mask, where mixed rows are kept or pass through memory, the format
 //                      of the result, and whether the widths other than 16 / 32 / 64 run as two launches or are refused.  The checks, the
 //                      operand fill, ensure_partial (before the first launch), the launch (with_tile_width) and the tail of the rows
 //                      that go through memory (transform_rows) each stand once
-//   gcnii_backward<R>  the host path of gnx_gcnii_step_back and gnx_gcnii_step_back_bf16, likewise; the f32 entry's composed form of the
+//   gcnii_backward<R>  the host path of gnx_gcnii_step_back, gnx_gcnii_step_back_dropped and gnx_gcnii_step_back_bf16, likewise; the f32 entry's composed form of the
 //                      other widths is its f32 branch
 //   gcnii_wgrad<R>     the host path of gnx_gcnii_wgrad and gnx_gcnii_wgrad_bf16
 // Hub rows share the long-row path of gnx_spmm.hip / gnx_spmm_bf16.hip (launch_long_rows, launch_long_rows_bf16: the f32 launch's
@@ -48,6 +50,19 @@ template <> struct SpectralArgs<true> {
     const float *bias;     // [C]
     uint32_t *gate;        // [n, ceil(C / 32)] or null: bit c & 31 of word row * ceil(C / 32) + (c >> 5) = (P'[row, c] > 0)
 };
+
+// ---- the layer under edge dropout (gnx_gcnii_step_dropped, gnx_gcnii_step_back_dropped; EDGE) ---------------------------------------------
+// p.fuse belongs to the edge dropout there -- the weights of the gather loop come from it (dropped_weight_at) -- so the feature mask of
+// DROP arrives beside it; the instantiations without EDGE carry an empty struct and keep reading p.fuse.
+template <bool EDGE> struct EdgeArgs {};
+template <> struct EdgeArgs<true> {
+    DropFuse feat;         // the mask of the finished rows (seed, stream, offset, thr, scale); read by the DROP instantiations only
+};
+template <bool EDGE>
+__device__ __forceinline__ const DropFuse &feature_mask(const SpmmArgs &p, const EdgeArgs<EDGE> &ed) {
+    if constexpr (EDGE) return ed.feat;
+    else return p.fuse;
+}
 
 // x[v] = act(P') of columns c .. c + VEC - 1 of row `row`  ->  2 drop(x[v] - bias[v]): the ONE place the finished value is formed, for
 // the store loop of the fused launch and for the row pass behind the dense kernel (k_spectral_tail), so that a row has the same bits
@@ -107,31 +122,78 @@ __device__ __forceinline__ void tile_times_Ms(float *__restrict__ T, const float
     __builtin_amdgcn_wave_barrier();
 }
 
+// The gather loop of the EDGE forms (k_spmm_gcnii, k_spmm_gcnii_back under edge dropout), columns c .. c + 3 of row `row` into acc: the
+// entries in ascending order, U in flight per lane and one fmaf chain, as in the loops that load their weights -- the weight of an entry is
+// (D[row] * drop(raw)) * D[col] from p.fuse, the arithmetic of k_scale_values, so it has the bits of the value gnx_graph_normalize would
+// have stored there (ENTRIES: a handle with duplicate entries, p.vals = each slot's uniform value).  The G lanes of a row share the work
+// of making the weights, as the lane groups of k_spmm_group_drop do: lane `sub` draws entry base + sub of a round of G entries -- one hash
+// per stored entry, not one per lane -- and the round is walked U entries at a time through shuffles inside the group (the lanes of a row
+// run the loop together: same beg and end).  A weight of exactly 0 -- a dropped entry, or a slot past the end of the row -- gathers
+// nothing and adds fmaf(0, 0, acc) = acc (the DroppedAdjacency precondition of finite features).
+template <bool ENTRIES, int G, int U>
+__device__ __forceinline__ void edge_gather(const SpmmArgs &p, const float *__restrict__ Xc, int64_t row, int64_t beg, int64_t end,
+                                            float (&acc)[4]) {
+    static_assert(G % U == 0, "a round of G entries is whole batches of U");
+    const int sub = (int)(threadIdx.x % G);
+    for (int64_t base = beg; base < end; base += G) {
+        int mycol = 0;
+        float myw = 0.f;
+        if (base + sub < end) {
+            mycol = p.colidx[base + sub];
+            myw = dropped_weight_at<ENTRIES>(p.fuse, p.vals[base + sub], base + sub, row, mycol);
+        }
+        const int n = (int)(end - base < G ? end - base : G);
+        for (int k = 0; k < n; k += U) {
+            float x[U][4];
+            float w[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = __shfl(mycol, k + u, G);
+                w[u] = __shfl(myw, k + u, G);
+                if (w[u] != 0.f) vload<4>(x[u], Xc + (int64_t)j * p.ldx);
+                else {
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) x[u][v] = 0.f;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
+        }
+    }
+}
+
 // One mixed row of the fused layer, columns c .. c + 3 of row `row` (entries beg .. end) into acc (zeros on entry): the gather loop, the
 // entry order and the mix, written once -- the forward (k_spmm_gcnii) and the weight gradient that makes T again (k_gcnii_wgrad) run this
 // code, so a row made again has the bits of the row the forward stored.  U entries in flight per lane.
-template <typename R, int U>
+// EDGE (G = the lanes of a row): the entry's weight is made, not loaded (edge_gather above); the mix is the same code.
+template <typename R, int U, bool EDGE = false, bool ENTRIES = false, int G = 0>
 __device__ __forceinline__ void mixed_row(const typename R::Args &p, int64_t row, int64_t beg, int64_t end, int c, float (&acc)[4]) {
     const typename R::Elem *__restrict__ Xc = R::X(p) + c;
-    for (int64_t e = beg; e < end; e += U) {
-        float x[U][4];
-        float w[U];
+    if constexpr (EDGE) {
+        edge_gather<ENTRIES, G, U>(p, Xc, row, beg, end, acc);
+    } else {
+        for (int64_t e = beg; e < end; e += U) {
+            float x[U][4];
+            float w[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (e + u < end) {
-                const int j = p.colidx[e + u];
-                w[u] = p.vals[e + u];
-                R::template load<4>(x[u], Xc + (int64_t)j * p.ldx);
-            } else {
-                w[u] = 0.f;
+            for (int u = 0; u < U; ++u) {
+                if (e + u < end) {
+                    const int j = p.colidx[e + u];
+                    w[u] = p.vals[e + u];
+                    R::template load<4>(x[u], Xc + (int64_t)j * p.ldx);
+                } else {
+                    w[u] = 0.f;
 #pragma unroll
-                for (int v = 0; v < 4; ++v) x[u][v] = 0.f;
+                    for (int v = 0; v < 4; ++v) x[u][v] = 0.f;
+                }
             }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
         }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
     }
     float h0[4];
     vload<4>(h0, p.H0 + row * p.ldh0 + c);
@@ -160,9 +222,14 @@ __device__ __forceinline__ void mixed_row(const typename R::Args &p, int64_t row
 // store loop forms 2 drop(act(P') - bias) (spectral_finish); with sp.gate the launch also writes one bit per element, P' > 0, which is
 // all the backward needs of the forward: a lane holds four columns of a row, the 4 NT lanes of a row (eight of them per 32-column
 // word) OR their bits together through xor-shuffles and one lane stores the word.  Like DROP a template argument alone.
-template <typename R, int NT, int U, int WPB, bool DROP = false, bool SPEC = false>
+// EDGE (gnx_gcnii_step_dropped, f32 rows, with ENTRIES on a handle after gnx_graph_enable_entry_dropout): the gather loop makes its
+// weights from p.fuse (mixed_row, edge_gather) and the mask of DROP comes from ed.feat; entry order, U, the fmaf chain, the mix and
+// everything behind them are those of the other instantiations.
+template <typename R, int NT, int U, int WPB, bool DROP = false, bool SPEC = false, bool EDGE = false, bool ENTRIES = false>
 __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args p, const float *__restrict__ M, int64_t ldm, float *__restrict__ mixed,
-                                                         const SpectralArgs<SPEC> sp = SpectralArgs<SPEC>{}) {
+                                                         const SpectralArgs<SPEC> sp = SpectralArgs<SPEC>{},
+                                                         const EdgeArgs<EDGE> ed = EdgeArgs<EDGE>{}) {
+    static_assert(!EDGE || (!SPEC && !R::BF16), "the edge-dropout form exists for the plain layer over f32 rows");
     constexpr int C = 16 * NT, G = 4 * NT, RPP = 64 / G, PASSES = 16 / RPP, STRIDE = C + 4;
     __shared__ float Ms[C * STRIDE];
     __shared__ float Ts[WPB][16 * STRIDE];
@@ -190,7 +257,7 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args 
         rows[ps] = row;
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
         if (live[ps]) {
-            mixed_row<R, U>(p, row, beg, end, c, acc);
+            mixed_row<R, U, EDGE, ENTRIES, G>(p, row, beg, end, c, acc);
             if (mixed) vstore<4>(mixed + row * (int64_t)C + c, acc);
         }
         vstore<4>(T + rr * STRIDE + c, acc);
@@ -225,7 +292,10 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args 
         const int rr = ps * RPP + lane / G;
         float o[4];
         vload<4>(o, T + rr * STRIDE + c);
-        if constexpr (DROP) drop_values<4>(p.fuse, drop_stream(p.fuse), rows[ps], c, o);
+        if constexpr (DROP) {
+            const DropFuse &fd = feature_mask<EDGE>(p, ed);
+            drop_values<4>(fd, drop_stream(fd), rows[ps], c, o);
+        }
         R::template store<4>(p, rows[ps] * p.ldo, c, o, false);
     }
 }
@@ -245,9 +315,13 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args 
 // gradient (gnx_gcnii_step_back_bf16) and widens them exactly; dH (p.out) is f32 under either policy, and the row's own G[r] of the
 // second product is read from the f32 p.X under either policy too -- the bf16 entry binds the f32 G there beside Gb, so the running dH0
 // sum never sees a rounded addend.  Same entry order, sums and transform: over bf16-representable G both give the same bits.
-template <typename R, int NT, int U, int WPB>
+// EDGE (gnx_gcnii_step_back_dropped, f32 rows; ENTRIES as in the forward): the weights of the transposed walk are made from p.fuse
+// (fuse.transposed = 1; on an entry-dropout handle with its mult / perm / slot_ptr tables, as gnx_spmm_dropped_back walks it):
+// edge_gather, the forward's loop.
+template <typename R, int NT, int U, int WPB, bool EDGE = false, bool ENTRIES = false>
 __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii_back(const typename R::Args p, const float *__restrict__ N, int64_t ldn, const float *S_in,
                                                               float s_alpha, float *S_out) {
+    static_assert(!EDGE || !R::BF16, "the edge-dropout form exists for f32 rows");
     constexpr int C = 16 * NT, G = 4 * NT, RPP = 64 / G, PASSES = 16 / RPP, STRIDE = C + 4;
     __shared__ float Ms[C * STRIDE];
     __shared__ float Ts[WPB][16 * STRIDE];
@@ -280,26 +354,30 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii_back(const typename R::
             const typename R::Elem *__restrict__ Xc;
             if constexpr (R::BF16) Xc = p.Xb + c;
             else Xc = p.X + c;
-            for (int64_t e = beg; e < end; e += U) {
-                float x[U][4];
-                float w[U];
+            if constexpr (EDGE) {
+                edge_gather<ENTRIES, G, U>(p, Xc, row, beg, end, acc);
+            } else {
+                for (int64_t e = beg; e < end; e += U) {
+                    float x[U][4];
+                    float w[U];
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    if (e + u < end) {
-                        const int j = p.colidx[e + u];
-                        w[u] = p.vals[e + u];
-                        if constexpr (R::BF16) bload<4>(x[u], Xc + (int64_t)j * p.ldx);
-                        else vload<4>(x[u], Xc + (int64_t)j * p.ldx);
-                    } else {
-                        w[u] = 0.f;
+                    for (int u = 0; u < U; ++u) {
+                        if (e + u < end) {
+                            const int j = p.colidx[e + u];
+                            w[u] = p.vals[e + u];
+                            if constexpr (R::BF16) bload<4>(x[u], Xc + (int64_t)j * p.ldx);
+                            else vload<4>(x[u], Xc + (int64_t)j * p.ldx);
+                        } else {
+                            w[u] = 0.f;
 #pragma unroll
-                        for (int v = 0; v < 4; ++v) x[u][v] = 0.f;
+                            for (int v = 0; v < 4; ++v) x[u][v] = 0.f;
+                        }
                     }
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+#pragma unroll
+                        for (int v = 0; v < 4; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
                 }
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
             }
 #pragma unroll
             for (int v = 0; v < 4; ++v) acc[v] *= p.beta;
@@ -695,10 +773,26 @@ void bind_fused(const Csr &m, SpmmArgs &p) {
 }
 
 // the chunked partial sums of the hub rows of a fused launch, mixed as p says, into f32 rows at `out` (p.partial set)
+// (`dropped`, f32 rows: p.fuse is an edge dropout and the chunks make their weights from it, launch_long_drop of gnx_spmm_drop.h)
 template <typename R>
-void launch_hub_rows(typename R::Args &p, const typename R::Elem *X, float *out, hipStream_t s) {
+void launch_hub_rows(typename R::Args &p, const typename R::Elem *X, float *out, hipStream_t s, bool dropped = false) {
     if constexpr (R::BF16) launch_long_rows_bf16(p, X, out, s);
-    else { p.out = out; launch_long_rows(p, s); }
+    else {
+        p.out = out;
+        if (dropped) launch_long_rows_dropped(p, s);
+        else launch_long_rows(p, s);
+    }
+}
+
+// the edge dropout of gnx_gcnii_step_dropped / gnx_gcnii_step_back_dropped: what gnx_spmm_dropped takes
+struct EdgeDrop { const float *D; float p; uint64_t seed, stream; };
+
+// what those two entries check before anything is built or launched, as gnx_spmm_dropped_back does
+int admit_edge_drop(const char *fn, gnx_graph *g, const EdgeDrop &e) {
+    GNX_CHECK_ARG(e.D != nullptr, "%s: NULL degree scales", fn);
+    GNX_CHECK_ARG(e.p >= 0.f && e.p < 1.f, "%s: dropout rate %g outside [0, 1)", fn, (double)e.p);
+    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols && g->blk_col_gid == nullptr, "%s: needs a square stand-alone graph", fn);
+    return refuse_duplicates(g, fn);
 }
 
 // the fused launch takes C = 16, 32 or 64 (C = 128 fits the kernel -- 135 KB of LDS: one block of eight waves per CU -- and was measured:
@@ -722,6 +816,7 @@ struct ForwardForm {             // what differs between its entries
     const char *fused, *composed;   // what gnx_graph_last_kernel reports
     const float *bias = nullptr;    // [C]: the spectral form (gnx_gcnii_step_spectral, F32Rows only), out = 2 drop(act(T . M + bias) - bias)
     uint32_t *gate = nullptr;       // the spectral form's gate words [n, ceil(C / 32)], or null
+    const EdgeDrop *edge = nullptr; // gnx_gcnii_step_dropped (F32Rows only): the weights are made in the gather loop; d_vals is null
 };
 
 template <typename R>
@@ -742,6 +837,10 @@ int gcnii_forward(const char *fn, gnx_graph *g, const float *d_vals, const typen
     auto own = [&](const void *b) { return b != out && b != H && b != d_H0 && b != d_M && b != d_vals && b != f.mixed && b != f.work; };
     GNX_CHECK_ARG(f.bias == nullptr || own(f.bias), "%s: d_bias must be a buffer of its own", fn);
     GNX_CHECK_ARG(f.gate == nullptr || (own(f.gate) && (const void *)f.gate != f.bias), "%s: d_gate must be a buffer of its own", fn);
+    if (f.edge) {
+        rc = admit_edge_drop(fn, g, *f.edge);
+        if (rc != GNX_OK) return rc;
+    }
     const bool fusable = fused_width(C) && aligned(d_H, 4 * sizeof(typename R::Elem)) && aligned(d_H0, 16) && aligned(d_out, f.out_bf16 ? 8 : 16) &&
                          aligned(f.mixed, 16) && aligned(f.work, 16) && aligned(f.bias, 16);
     if (!fusable && !f.composes) return refuse_unfused(fn, C);
@@ -757,9 +856,14 @@ int gcnii_forward(const char *fn, gnx_graph *g, const float *d_vals, const typen
     hipStream_t s = (hipStream_t)stream;
     const float beta = (float)(1.0 - (double)a);
     typename R::Args p{};
-    p.vals = d_vals ? d_vals : g->raw_vals;
+    if (f.edge) {      // p.fuse is the edge dropout's; the mask travels beside it (EdgeArgs)
+        set_values(g, false, p);
+        set_drop_fuse(g, f.edge->p, f.edge->seed, f.edge->stream, f.edge->D, 0, 0, p);
+    } else {
+        p.vals = d_vals ? d_vals : g->raw_vals;
+        if (f.fd) p.fuse = *f.fd;
+    }
     set_operands<R>(p, d_H, C, d_H0, C, beta, a, act, d_out, f.out_bf16, C, C);
-    if (f.fd) p.fuse = *f.fd;
     // mixed rows at T (the n listed; null: rows 0 .. n) -> act(T . M) of those rows alone, into d_out, or into d_work where the result is
     // bf16 -> their mask, in place -> the rows rounded into d_out.  (T may be d_work itself: every wave of the dense kernels reads whole
     // rows of its own tile before it stores them, as long as the result is ONE column panel)
@@ -778,6 +882,8 @@ int gcnii_forward(const char *fn, gnx_graph *g, const float *d_vals, const typen
         if constexpr (R::BF16) {
             p.act = GNX_ACT_NONE;
             rc = launch_spmm_bf16_f32_order(g, m, p, d_H, T, s);
+        } else if (f.edge) {
+            rc = gnx_spmm_dropped(g, f.edge->D, f.edge->p, f.edge->seed, f.edge->stream, 0, d_H, C, C, d_H0, C, beta, a, GNX_ACT_NONE, T, C, stream);
         } else {
             rc = gnx_spmm(g, d_vals, nullptr, d_H, C, C, d_H0, C, beta, a, GNX_ACT_NONE, T, C, stream);
         }
@@ -797,6 +903,16 @@ int gcnii_forward(const char *fn, gnx_graph *g, const float *d_vals, const typen
     }
     with_tile_width(C, m.n_rows, [&](auto NT, dim3 grid) {
         if constexpr (!R::BF16) {
+            if (f.edge) {
+                const EdgeArgs<true> ed{f.fd ? *f.fd : DropFuse{}};
+                auto launch = [&](auto DROP, auto ENTRIES) {
+                    hipLaunchKernelGGL((k_spmm_gcnii<R, NT(), 4, 8, DROP(), false, true, ENTRIES()>), grid, dim3(512), 0, s, p, d_M, ldm, f.mixed,
+                                       SpectralArgs<false>{}, ed);
+                };
+                if (f.fd) { if (p.fuse.mult) launch(std::true_type{}, std::true_type{}); else launch(std::true_type{}, std::false_type{}); }
+                else      { if (p.fuse.mult) launch(std::false_type{}, std::true_type{}); else launch(std::false_type{}, std::false_type{}); }
+                return;
+            }
             if (f.bias) {
                 const SpectralArgs<true> sp{f.bias, f.gate};
                 if (f.fd) hipLaunchKernelGGL((k_spmm_gcnii<R, NT(), 4, 8, true, true>), grid, dim3(512), 0, s, p, d_M, ldm, f.mixed, sp);
@@ -816,17 +932,22 @@ int gcnii_forward(const char *fn, gnx_graph *g, const float *d_vals, const typen
     float *T = f.mixed ? f.mixed : f.work ? f.work : static_cast<float *>(d_out);
     p.partial = g->partial;
     p.act = GNX_ACT_NONE;
-    launch_hub_rows<R>(p, d_H, T, s);
+    launch_hub_rows<R>(p, d_H, T, s, f.edge != nullptr);
     return transform_rows(T, m.long_rows, m.n_long);
 }
 
 // ---- the backward's host path, once over the row storage R of the gathered gradient X (the f32 G itself, or its bf16 copy Gb) ------------
 template <typename R>
 int gcnii_backward(const char *fn, gnx_graph *g, const float *d_vals_t, const typename R::Elem *d_X, const float *d_G, float a, int64_t C,
-                   const float *d_Mt, int64_t ldmt, float *d_dH, const float *d_S_in, float s_alpha, float *d_S_out, float *d_work, void *stream) {
+                   const float *d_Mt, int64_t ldmt, float *d_dH, const float *d_S_in, float s_alpha, float *d_S_out, float *d_work, void *stream,
+                   const EdgeDrop *edge = nullptr) {
     int rc = check_common(fn, g, d_X, C, C, d_S_in, C, d_dH, C);
     if (rc != GNX_OK) return rc;
     GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "%s: needs a square graph", fn);
+    if (edge) {      // (gnx_gcnii_step_back_dropped, f32 rows: the weights of the transposed walk are made from the edge dropout; d_vals_t is null)
+        rc = admit_edge_drop(fn, g, *edge);
+        if (rc != GNX_OK) return rc;
+    }
     GNX_CHECK_ARG(d_Mt != nullptr && ldmt >= C, "%s: NULL Mt or ldmt < C", fn);
     GNX_CHECK_ARG(d_S_in == nullptr || d_S_out != nullptr, "%s: S_in without S_out", fn);
     if constexpr (R::BF16)
@@ -855,9 +976,10 @@ int gcnii_backward(const char *fn, gnx_graph *g, const float *d_vals_t, const ty
         }
         rc = gnx_dense(d_G, C, n, C, d_Mt, ldmt, C, nullptr, GNX_ACT_NONE, d_work, C, stream);
         if (rc != GNX_OK) return rc;
-        rc = gnx_spmm_tv(g, d_vals_t ? d_vals_t : g->t_raw.get(), nullptr, d_work, C, C, nullptr, 0, beta, 0.f, GNX_ACT_NONE, d_dH, C, stream);
+        if (edge) rc = gnx_spmm_dropped(g, edge->D, edge->p, edge->seed, edge->stream, 1, d_work, C, C, nullptr, 0, beta, 0.f, GNX_ACT_NONE, d_dH, C, stream);
+        else rc = gnx_spmm_tv(g, d_vals_t ? d_vals_t : g->t_raw.get(), nullptr, d_work, C, C, nullptr, 0, beta, 0.f, GNX_ACT_NONE, d_dH, C, stream);
         if (rc != GNX_OK) return rc;
-        g->last_kernel = "dense+spmm_back";
+        g->last_kernel = edge ? "dense+spmm_back_edrop" : "dense+spmm_back";
         if (d_S_out == nullptr || n == 0) return GNX_OK;
         const float *src[2] = {d_S_in, d_work};
         const float coef[2] = {s_alpha, a};
@@ -873,17 +995,29 @@ int gcnii_backward(const char *fn, gnx_graph *g, const float *d_vals_t, const ty
         if (rc != GNX_OK) return rc;
     }
     typename R::Args p{};
-    p.vals = d_vals_t ? d_vals_t : g->t_raw.get();
+    if (edge) {
+        set_values(g, true, p);
+        set_drop_fuse(g, edge->p, edge->seed, edge->stream, edge->D, 1, 0, p);
+    } else {
+        p.vals = d_vals_t ? d_vals_t : g->t_raw.get();
+    }
     set_operands<R>(p, d_X, C, nullptr, 0, beta, a, GNX_ACT_NONE, d_dH, 0, C, C);
     p.X = d_G; p.out = d_dH;      // the row's own f32 row and the f32 dH are SpmmArgs' own under either policy (k_spmm_gcnii_back)
     bind_fused(m, p);
     with_tile_width(C, m.n_rows, [&](auto NT, dim3 grid) {
+        if constexpr (!R::BF16) {
+            if (edge) {
+                if (p.fuse.mult) hipLaunchKernelGGL((k_spmm_gcnii_back<R, NT(), 4, 8, true, true>), grid, dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
+                else             hipLaunchKernelGGL((k_spmm_gcnii_back<R, NT(), 4, 8, true, false>), grid, dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
+                return;
+            }
+        }
         hipLaunchKernelGGL((k_spmm_gcnii_back<R, NT(), 4, 8>), grid, dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
     });
-    g->last_kernel = R::BF16 ? "spmm_gcnii_back_mfma_bf16" : "spmm_gcnii_back_mfma";
+    g->last_kernel = R::BF16 ? "spmm_gcnii_back_mfma_bf16" : edge ? "spmm_gcnii_back_mfma_edrop" : "spmm_gcnii_back_mfma";
     if (m.n_long > 0) {   // hub rows of the transposed structure: chunked partial sums -> (1-a) Z into dH -> those rows alone times Mt, in place
         p.partial = g->partial;
-        launch_hub_rows<R>(p, d_X, d_dH, s);
+        launch_hub_rows<R>(p, d_X, d_dH, s, edge != nullptr);
         rc = dense_rows(d_dH, C, m.n_long, C, d_Mt, ldmt, C, nullptr, GNX_ACT_NONE, m.long_rows, m.long_rows, d_dH, C, s);
         if (rc != GNX_OK) return rc;
     }
@@ -960,6 +1094,30 @@ int gnx_gcnii_step_drop(gnx_graph_t g, const float *d_vals, const float *d_H, co
     const ForwardForm f{drop ? &fd : nullptr, d_mixed, nullptr, 0, true, drop ? "spmm_gcnii_mfma_drop" : "spmm_gcnii_mfma",
                         drop ? "spmm+dense_mfma_drop" : "spmm+dense_mfma"};
     return gcnii_forward<F32Rows>("gnx_gcnii_step_drop", g, d_vals, d_H, d_H0, a, C, d_M, ldm, act, d_out, f, stream);
+}
+
+// (feat_p == 0: no feature mask -- nothing is hashed for the finished rows; the edge dropout acts at any rate in [0, 1))
+int gnx_gcnii_step_dropped(gnx_graph_t g, const float *d_D, float edge_p, uint64_t edge_seed, uint64_t edge_stream, const float *d_H,
+                           const float *d_H0, float a, int64_t C, const float *d_M, int64_t ldm, int act, double feat_p, uint64_t feat_seed,
+                           uint64_t feat_stream, float *d_out, float *d_mixed, void *stream) {
+    const char *fn = "gnx_gcnii_step_dropped";
+    DropFuse fd{};
+    int rc = make_feat_drop(fn, g, feat_p, feat_seed, feat_stream, fd);
+    if (rc != GNX_OK) return rc;
+    const EdgeDrop edge{d_D, edge_p, edge_seed, edge_stream};
+    const bool drop = feat_p != 0.0;
+    ForwardForm f{drop ? &fd : nullptr, d_mixed, nullptr, 0, true, drop ? "spmm_gcnii_mfma_edrop_drop" : "spmm_gcnii_mfma_edrop",
+                  drop ? "spmm+dense_mfma_edrop_drop" : "spmm+dense_mfma_edrop"};
+    f.edge = &edge;
+    return gcnii_forward<F32Rows>(fn, g, nullptr, d_H, d_H0, a, C, d_M, ldm, act, d_out, f, stream);
+}
+
+int gnx_gcnii_step_back_dropped(gnx_graph_t g, const float *d_D, float edge_p, uint64_t edge_seed, uint64_t edge_stream, const float *d_G, float a,
+                                int64_t C, const float *d_Mt, int64_t ldmt, float *d_dH, const float *d_S_in, float s_alpha, float *d_S_out,
+                                float *d_work, void *stream) {
+    const EdgeDrop edge{d_D, edge_p, edge_seed, edge_stream};
+    return gcnii_backward<F32Rows>("gnx_gcnii_step_back_dropped", g, nullptr, d_G, d_G, a, C, d_Mt, ldmt, d_dH, d_S_in, s_alpha, d_S_out, d_work,
+                                   stream, &edge);
 }
 
 // (the gate words are the relu's: with the identity there is nothing to gate and d_gate is not looked at)

@@ -377,6 +377,7 @@ void launch_long_rows(const SpmmArgs &p, hipStream_t s);                        
 int launch_spmm_bf16_f32_order(gnx_graph *g, const Csr &m, const SpmmArgs &p, const uint16_t *Xb, float *out, hipStream_t s);
 void launch_long_rows_bf16(const SpmmArgs &p, const uint16_t *Xb, float *out, hipStream_t s);   // launch_long_rows, likewise
 const char *launch_spmm_dropped(const SpmmArgs &p, int vec, hipStream_t s);              // gnx_spmm_train.hip
+void launch_long_rows_dropped(const SpmmArgs &p, hipStream_t s);                         // gnx_spmm_train.hip: launch_long_rows under p.fuse
 // gnx_spmm_train.hip, shared with gnx_spmm_train_bf16.hip: a handle with duplicate entries needs gnx_graph_enable_entry_dropout
 // (GNX_ERR_UNSUPPORTED otherwise); the per-slot values and entry tables a fused launch over the handle reads
 int refuse_duplicates(const gnx_graph *g, const char *fn);

@@ -51,7 +51,8 @@ class GNN(Trainable):
 
     def __init__(self, graph, features, preprocessor: Layer = None, reorder=None, inference_dtype=torch.float32,
                  training_dtype=torch.float32, train_gather_order="auto", gcnii_backward="composed", feature_dropout="torch",
-                 gcnii_training_dtype=torch.float32, gcnii_weight_gradient="stored", gcnii_spectral="composed"):
+                 gcnii_training_dtype=torch.float32, gcnii_weight_gradient="stored", gcnii_spectral="composed",
+                 gcnii_edge_dropout="composed"):
         """``reorder`` (opt-in, not in the reference): store the graph and the feature rows with the vertices relabelled; every
         [N, .] tensor inside the model then lives in that order, and the model's OUTPUT is put back into the caller's order, so
         tasks, labels and node ids are unaffected.  Results agree with the unordered model to float32 rounding.
@@ -148,7 +149,23 @@ class GNN(Trainable):
         same sums; the bias is added inside the matrix-core epilogue either way).  Plain GCNIILayer stacks and every other keyword on
         them, ``feature_dropout="fused"`` on a spectral stack (which that switch never touched), the bf16 switches, other activations,
         a rate of 1 or more, dropped adjacencies, add_eye, CPU tensors, GCNSpectralPreservingLayer and the vertex-partitioned path keep
-        today's path and bits whatever it says (measurement: profiles/NOTES.md "Fused spectral-preserving GCNII layer")."""
+        today's path and bits whatever it says (measurement: profiles/NOTES.md "Fused spectral-preserving GCNII layer").
+        ``gcnii_edge_dropout`` (not in the reference): ``"composed"`` (the default: today's calls and bits) or ``"fused"``
+        (sparse.gcnii_step ``edge_dropout``).  ``"fused"``: a plain GCNIILayer (the class itself, relu or the identity as activation, a
+        float ``a``, float32 device tensors, no add_eye) in training mode with ``graph_dropout`` != 0 on a graph that can fuse its
+        dropout -- the reference's default, ``GCNIILayer(..., graph_dropout=0.5)`` -- runs as the ONE launch of a constant adjacency
+        (gnx_gcnii_step_dropped): every entry's weight (D[row] * drop(raw)) * D[col] is made in the gather loop, the mixed rows are
+        written once, and with ``feature_dropout="fused"`` and 0 < ``dropout`` < 1 the feature mask leaves the same launch (otherwise
+        torch's dropout follows as today).  The backward is the existing gate, gnx_dense_wgrad and, with ``gcnii_backward="fused"``, one
+        launch over the transposed structure (gnx_gcnii_step_back_dropped); with ``"composed"`` gnx_dense, the transposed dropped SpMM and
+        a scaling.  The layer draws its mask streams in today's order and number (the adjacency's first, then the feature mask's), so a
+        seed means the masks it means under ``"composed"``; every tensor has the bits of the same layer over the materialised adjacency,
+        and against ``"composed"`` agrees to float32 rounding (the transform runs in the fused launch's order).  Eval mode, constant
+        adjacencies, GCNIISpectralPreservingLayer, other activations, ``gcnii_weight_gradient="recomputed"``,
+        ``gcnii_training_dtype=torch.bfloat16``, add_eye, graphs that cannot fuse their dropout, CPU tensors and the vertex-partitioned
+        path keep today's path whatever it says (measurement: profiles/NOTES.md "Fused GCNII layer under edge dropout")."""
+        if gcnii_edge_dropout not in sparse.GCNII_EDGE_DROPOUTS:
+            raise Exception("GNN: gcnii_edge_dropout must be one of " + ", ".join(repr(e) for e in sparse.GCNII_EDGE_DROPOUTS))
         if gcnii_spectral not in sparse.GCNII_SPECTRALS:
             raise Exception("GNN: gcnii_spectral must be one of " + ", ".join(repr(f) for f in sparse.GCNII_SPECTRALS))
         if feature_dropout not in FEATURE_DROPOUTS:
@@ -174,6 +191,7 @@ class GNN(Trainable):
         self.gcnii_weight_gradient = gcnii_weight_gradient
         self.feature_dropout = feature_dropout
         self.gcnii_spectral = gcnii_spectral
+        self.gcnii_edge_dropout = gcnii_edge_dropout
         self._order = self._newid = None
         self.reorder_used, self.locality_share = None, None
         if isinstance(graph, sparse.DeviceGraph):
@@ -598,6 +616,11 @@ class GCNIILayer(Layer):
             # GNN(gcnii_weight_gradient="recomputed"): plain layers alone (the argument is passed only where it can change the path)
             wgrad = dict(weight_gradient="recomputed") if (getattr(gcn, "gcnii_weight_gradient", "stored") == "recomputed"
                                                            and type(self) is GCNIILayer and fused_act) else dict()
+            # GNN(gcnii_edge_dropout="fused"): plain training layers over a DroppedAdjacency alone (passed only where it can change the path)
+            if (getattr(gcn, "gcnii_edge_dropout", "composed") == "fused" and type(self) is GCNIILayer and fused_act and gcn.is_training()
+                    and isinstance(adjacency, sparse.DroppedAdjacency) and features.dtype == torch.float32 and not wgrad
+                    and isinstance(self.a, (int, float)) and not isinstance(self.a, bool)):
+                wgrad = dict(edge_dropout="fused")
             if (getattr(gcn, "feature_dropout", "torch") == "fused" and type(self) is GCNIILayer and fused_act and gcn.is_training()
                     and 0 < self.dropout < 1):                      # (a rate of 1 or more stays with gcn.dropout and what torch makes of it)
                 # GNN(feature_dropout="fused"): dropout(act(...)) leaves the layer's launch, its mask from the counter RNG

@@ -1160,15 +1160,25 @@ def _gcnii_operands(what, adj, rows, f32=(), M=None, constant=None, device=True)
     return g, shape[1]
 
 
-def _gcnii_launch(adj: Adjacency, H, H0, a, M, relu, keep_mixed, dropout=None):
+def _gcnii_launch(adj: Adjacency, H, H0, a, M, relu, keep_mixed, dropout=None, fused_edge=False):
     """gnx_gcnii_step; returns (out, T or None).  T = the mixed rows (A.H)(1-a) + H0 a, written by the same launch when kept.
-    ``dropout`` = (p, seed, stream): gnx_gcnii_step_drop, out = drop(act(T . M)); T stays undropped."""
+    ``dropout`` = (p, seed, stream): gnx_gcnii_step_drop, out = drop(act(T . M)); T stays undropped.
+    ``fused_edge`` (``adj`` is a DroppedAdjacency): gnx_gcnii_step_dropped -- the weights are made in the launch's gather loop from the
+    adjacency's (D, p, seed, stream) and ``adj.vals`` is never materialised."""
     nat.require_cuda(H, H0, M)
     H, H0, M = _as_f32_rows(H).contiguous(), _as_f32_rows(H0).contiguous(), _as_f32_rows(M)
-    g, C = _gcnii_operands("gcnii_step", adj, H, (H0,), M, device=False)
+    g, C = _gcnii_operands("gcnii_step", adj, H, (H0,), M, device=fused_edge)
     out = torch.empty_like(H)
     mixed = torch.empty_like(H) if keep_mixed or C not in (16, 32, 64) else None
-    layer = (g.handle, nat.ptr(adj.vals), nat.ptr(H), nat.ptr(H0), float(a), C, nat.ptr(M), M.stride(0), nat.ACT_RELU if relu else nat.ACT_NONE)
+    act = nat.ACT_RELU if relu else nat.ACT_NONE
+    if fused_edge:
+        _same_device(g, adj.D)
+        mask = dropout if dropout is not None else (0.0, 0, 0)
+        with nat.on_device(H.device):
+            nat.check(nat.lib().gnx_gcnii_step_dropped(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, nat.ptr(H), nat.ptr(H0), float(a), C,
+                                                       nat.ptr(M), M.stride(0), act, *mask, nat.ptr(out), nat.ptr(mixed), nat.current_stream()))
+        return out, mixed
+    layer = (g.handle, nat.ptr(adj.vals), nat.ptr(H), nat.ptr(H0), float(a), C, nat.ptr(M), M.stride(0), act)
     with nat.on_device(H.device):
         if dropout is not None:
             nat.check(nat.lib().gnx_gcnii_step_drop(*layer, *dropout, nat.ptr(out), nat.ptr(mixed), nat.current_stream()))
@@ -1179,7 +1189,15 @@ def _gcnii_launch(adj: Adjacency, H, H0, a, M, relu, keep_mixed, dropout=None):
 
 GCNII_BACKWARDS = ("composed", "fused")
 GCNII_WEIGHT_GRADIENTS = ("stored", "recomputed")
+GCNII_EDGE_DROPOUTS = ("composed", "fused")
 GCNII_FUSED_WIDTHS = (16, 32, 64)
+
+
+def _edge_dropout(what, edge_dropout) -> bool:
+    """Whether ``edge_dropout`` asks for the fused form; raises on anything but the two names."""
+    if edge_dropout not in GCNII_EDGE_DROPOUTS:
+        raise Exception(f"{what}: edge_dropout must be one of " + ", ".join(repr(e) for e in GCNII_EDGE_DROPOUTS))
+    return edge_dropout == "fused"
 
 
 def _weight_gradient(what, weight_gradient) -> bool:
@@ -1214,17 +1232,21 @@ def gcnii_wgrad(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, G: 
     return dM
 
 
-def gcnii_step_back(adj: Adjacency, G: torch.Tensor, a: float, Mt: torch.Tensor, S_in=None, s_alpha=1.0, want_S=True):
+def gcnii_step_back(adj: Adjacency, G: torch.Tensor, a: float, Mt: torch.Tensor, S_in=None, s_alpha=1.0, want_S=True, edge_dropout="composed"):
     """The backward of gcnii_step past the relu gate as ONE launch for C in {16, 32, 64} (gnx_gcnii_step_back; no autograd):
     with ``G`` = g * (out > 0) and ``Mt`` = M^T,  dH = ((1-a) A^T G) . Mt  and  S = s_alpha S_in + (a G) . Mt  -- the gradient of H and
     the layer's term of dH0 on top of a running sum ``S_in`` (None: no such term).  Returns (dH, S); ``want_S=False`` skips the
     second product and returns (dH, None).  G is gathered over the transposed structure itself: G . Mt never reaches memory.
-    Other widths run gnx_dense, the transposed SpMM and one linear combination, through a work buffer allocated here."""
+    Other widths run gnx_dense, the transposed SpMM and one linear combination, through a work buffer allocated here.
+    ``edge_dropout="fused"`` with a DroppedAdjacency (which is refused otherwise): gnx_gcnii_step_back_dropped, the same launch with
+    the weights of the transposed walk made from the adjacency's (D, p, seed, stream) -- bit for bit the results over the materialised
+    adjacency ``normalize(graph, "symmetric", "none", p, seed, stream)``."""
+    fused_edge = _edge_dropout("gcnii_step_back", edge_dropout) and isinstance(adj, DroppedAdjacency)
     G, S_in = _as_f32_rows(G).contiguous(), None if S_in is None else _as_f32_rows(S_in).contiguous()
-    return _gcnii_back_launch(False, adj, G, None, a, Mt, S_in, s_alpha, want_S, False)
+    return _gcnii_back_launch(False, adj, G, None, a, Mt, S_in, s_alpha, want_S, False, fused_edge=fused_edge)
 
 
-def _gcnii_back_launch(bf16, adj, X, G, a, Mt, S_in, s_alpha, want_S, in_place):
+def _gcnii_back_launch(bf16, adj, X, G, a, Mt, S_in, s_alpha, want_S, in_place, fused_edge=False):
     """gnx_gcnii_step_back over the f32 rows ``X`` (the gated gradient itself; ``G`` is None), or with ``bf16``
     gnx_gcnii_step_back_bf16 over its bf16 copy ``X`` beside the f32 ``G``: the checks, the buffers -- dH, S (``in_place``: S_in itself;
     None without ``want_S``), and for f32 rows of the other widths the work buffer of the composed form -- and the call.
@@ -1237,12 +1259,19 @@ def _gcnii_back_launch(bf16, adj, X, G, a, Mt, S_in, s_alpha, want_S, in_place):
         if want_S == (G is None) or (S_in is not None and not want_S) or (in_place and S_in is None):
             raise Exception("gcnii_step_back_bf16: the f32 G goes with want_S, S_in needs want_S, in_place needs S_in")
     else:
-        g, C = _gcnii_operands("gcnii_step", adj, X, (S_in,), Mt, "the fused backward")
+        g, C = _gcnii_operands("gcnii_step", adj, X, (S_in,), Mt, None if fused_edge else "the fused backward")
         if S_in is not None and not want_S:
             raise Exception("gcnii_step: S_in without want_S")
     dH = torch.empty_like(X, dtype=torch.float32) if bf16 else torch.empty_like(X)
     S = (S_in if in_place else torch.empty_like(dH)) if want_S else None
     work = torch.empty_like(dH) if not bf16 and C not in (16, 32, 64) else None
+    if fused_edge:      # (f32 rows: gnx_gcnii_step_back_dropped makes the transposed weights itself; no value array is written)
+        _same_device(g, adj.D)
+        with nat.on_device(X.device):
+            nat.check(nat.lib().gnx_gcnii_step_back_dropped(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, nat.ptr(X), float(a), C,
+                                                            nat.ptr(Mt), Mt.stride(0), nat.ptr(dH), nat.ptr(S_in), float(s_alpha), nat.ptr(S),
+                                                            nat.ptr(work), nat.current_stream()))
+        return dH, S
     values = adj.transposed_values()
     with nat.on_device(X.device):
         if bf16:
@@ -1261,17 +1290,20 @@ class _GCNIIStep(torch.autograd.Function):
     ``dropout`` = (p, seed, stream): out = drop(act(T . M)) from the same launch (gnx_gcnii_step_drop); the dropped out is what is
     saved, and g' = kept ? g * s : 0 gated by out > 0 comes from one pass (gnx_feature_dropout_back) in place of the relu mask.
     ``recompute``: T is neither written nor saved -- (H, H0, M, out) are saved instead of (T, M, out), where H is the previous layer's
-    saved output and H0 the stack's -- and dM comes from gcnii_wgrad, which makes T again (widths 16, 32, 64 only)."""
+    saved output and H0 the stack's -- and dM comes from gcnii_wgrad, which makes T again (widths 16, 32, 64 only).
+    ``fused_edge``: ``adj`` is a DroppedAdjacency and stays one (it keeps its D; no value array): the forward is
+    gnx_gcnii_step_dropped with T written, the fused backward gnx_gcnii_step_back_dropped, the composed one the transposed dropped SpMM."""
 
     @staticmethod
-    def forward(ctx, H, H0, M, adj, a, relu, backward="composed", dropout=None, recompute=False):
+    def forward(ctx, H, H0, M, adj, a, relu, backward="composed", dropout=None, recompute=False, fused_edge=False):
         ctx.adj, ctx.a, ctx.relu, ctx.fused_backward, ctx.dropout, ctx.recompute = adj, a, relu, backward == "fused", dropout, recompute
+        ctx.fused_edge = fused_edge
         if recompute:   # T is not written: the backward makes it again from H and H0 (gcnii_wgrad), which are saved in its place
             H, H0 = _as_f32_rows(H).contiguous(), _as_f32_rows(H0).contiguous()
             out, _ = _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=False, dropout=dropout)
             ctx.save_for_backward(H, H0, M, out if relu or dropout is not None else None)
             return out
-        out, T = _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=True, dropout=dropout)
+        out, T = _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=True, dropout=dropout, fused_edge=fused_edge)
         ctx.save_for_backward(T, M, out if relu or dropout is not None else None)
         return out
 
@@ -1294,7 +1326,8 @@ class _GCNIIStep(torch.autograd.Function):
         gH = gH0 = None
         if ctx.fused_backward and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
             # (the launch always makes dH; a caller that wants dH0 alone is not what a GCNII stack asks for)
-            gH, gH0 = gcnii_step_back(ctx.adj, g, ctx.a, M.t().contiguous(), want_S=ctx.needs_input_grad[1])
+            gH, gH0 = gcnii_step_back(ctx.adj, g, ctx.a, M.t().contiguous(), want_S=ctx.needs_input_grad[1],
+                                      edge_dropout="fused" if ctx.fused_edge else "composed")
             gH = gH if ctx.needs_input_grad[0] else None
         elif ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             gT = _dense_launch(g, M.t().contiguous(), None, False)
@@ -1302,11 +1335,11 @@ class _GCNIIStep(torch.autograd.Function):
                 gH = _launch(ctx.adj, gT, None, 1.0 - ctx.a, 0.0, nat.ACT_NONE, transposed=True)
             if ctx.needs_input_grad[1]:
                 gH0 = gT * ctx.a
-        return gH, gH0, gM, None, None, None, None, None, None
+        return gH, gH0, gM, None, None, None, None, None, None, None
 
 
 def gcnii_step(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, M: torch.Tensor, relu=True, storage=torch.float32,
-               out_storage=torch.float32, backward="composed", dropout=None, weight_gradient="stored") -> torch.Tensor:
+               out_storage=torch.float32, backward="composed", dropout=None, weight_gradient="stored", edge_dropout="composed") -> torch.Tensor:
     """act(((A . H)(1-a) + H0 a) . M), M = (1-b) I + b W (gcn.py:22-27) -- ONE fused launch for C in {16, 32, 64}: the mixed
     rows stay in LDS and meet M on the matrix cores (gnx_gcnii_step).  Without autograd they never reach HBM; when gradients are
     needed the same launch also writes them (dM = T^T g needs them), once, and the transform does not read them back.  Other
@@ -1327,31 +1360,51 @@ def gcnii_step(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, M: t
     bits) or ``"recomputed"`` (opt-in, C in {16, 32, 64} on a constant adjacency, device tensors): the launch writes no T and the layer
     saves (H, H0, M, out) instead of (T, M, out) -- in a stack H is the previous layer's saved output, so a layer keeps 4 bytes per
     element less -- and dM comes from ``gcnii_wgrad``, which makes T again.  out, dH and dH0 keep their bits; dM agrees to float32
-    rounding (another summation order).  Other widths, a DroppedAdjacency and the inference paths ignore it."""
+    rounding (another summation order).  Other widths, a DroppedAdjacency and the inference paths ignore it.
+    ``edge_dropout``: ``"composed"`` (the default: a DroppedAdjacency under autograd is the generic composition -- the dropped SpMM + mix,
+    gnx_dense, the mask as a pass of its own -- today's calls and bits) or ``"fused"`` (opt-in): with a DroppedAdjacency, float32
+    device tensors and gradients needed the step is the one autograd node of a constant adjacency -- gnx_gcnii_step_dropped makes
+    every entry's weight in the gather loop of the fused launch and writes T, ``dropout`` leaves the same launch, and the backward
+    honours ``backward`` (``"fused"``: gnx_gcnii_step_back_dropped; ``"composed"``: gnx_dense, the transposed dropped SpMM and a
+    scaling).  out, dH, dH0 and dM are bit for bit those of the same call over the materialised adjacency
+    ``normalize(graph, "symmetric", "none", p, seed, stream)``; against ``"composed"`` the forward keeps its bits at the other widths
+    and agrees to float32 rounding at 16 / 32 / 64 (matrix-core transform order).  A dropped entry is skipped, not multiplied by 0
+    (the DroppedAdjacency precondition of finite features).  Constant adjacencies, calls without autograd, bf16 storage and
+    ``weight_gradient="recomputed"`` keep today's path whatever it says."""
     if backward not in GCNII_BACKWARDS:
         raise Exception("gcnii_step: backward must be one of " + ", ".join(repr(b) for b in GCNII_BACKWARDS))
     recompute = _weight_gradient("gcnii_step", weight_gradient)
+    fused_edge = _edge_dropout("gcnii_step", edge_dropout) and not recompute and _fused_edge_applies(adj, H, H0, M)
     if dropout is not None:
         if _bf16(storage) or _bf16(out_storage):
             raise Exception("gcnii_step: dropout belongs to training, bf16 storage is inference only")
         dropout = _dropout_triple(dropout, "gcnii_step")
         if dropout is not None:
-            return _gcnii_step_dropped(adj, H, H0, a, M, relu, backward, dropout, recompute)
+            return _gcnii_step_dropped(adj, H, H0, a, M, relu, backward, dropout, recompute, fused_edge)
     if _bf16(storage):
         _no_grad_for_bf16("gcnii_step", H, H0, M)
         return _gcnii_launch_bf16(adj, H, H0, a, M, relu, _bf16(out_storage))
     if _bf16(out_storage):
         raise Exception("gcnii_step: a bf16 result needs storage=torch.bfloat16")
     if torch.is_grad_enabled() and (H.requires_grad or H0.requires_grad or M.requires_grad):
+        if fused_edge:                                              # weights made inside the fused launch itself (gnx_gcnii_step_dropped)
+            return _GCNIIStep.apply(H, H0, M, adj, float(a), bool(relu), backward, None, False, True)
         if isinstance(adj, DroppedAdjacency):                       # weights made inside the SpMM: the generic composition knows how
             return dense(ppr_step(adj, H, H0, a), M, None, relu)
         return _GCNIIStep.apply(H, H0, M, adj, float(a), bool(relu), backward, None, recompute and H.shape[-1] in GCNII_FUSED_WIDTHS)
     return _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=False)[0]
 
 
-def _gcnii_step_dropped(adj, H, H0, a, M, relu, backward, dropout, recompute=False):
+def _fused_edge_applies(adj, H, H0, M) -> bool:
+    """Whether gcnii_step(edge_dropout="fused") can take the fused launch: a DroppedAdjacency and float32 device tensors."""
+    return isinstance(adj, DroppedAdjacency) and all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 for t in (H, H0, M))
+
+
+def _gcnii_step_dropped(adj, H, H0, a, M, relu, backward, dropout, recompute=False, fused_edge=False):
     """gcnii_step with a feature dropout of rate > 0 (``dropout`` = the checked triple)."""
     if torch.is_grad_enabled() and (H.requires_grad or H0.requires_grad or M.requires_grad):
+        if fused_edge:
+            return _GCNIIStep.apply(H, H0, M, adj, float(a), bool(relu), backward, dropout, False, True)
         if isinstance(adj, DroppedAdjacency):
             return feature_dropout(adj.graph, dense(ppr_step(adj, H, H0, a), M, None, relu), *dropout)
         return _GCNIIStep.apply(H, H0, M, adj, float(a), bool(relu), backward, dropout, recompute and H.shape[-1] in GCNII_FUSED_WIDTHS)

@@ -608,6 +608,43 @@ int gnx_gcnii_spectral_back(gnx_graph_t g, const float *d_g, int64_t ldg, const 
                             double dropout_p, uint64_t seed, uint64_t stream_id, float *d_G, int64_t ldG, float *d_dbias,
                             float *d_work, int64_t work_floats, void *stream);
 
+/* The GCNII layer UNDER EDGE DROPOUT as one launch, forward and backward (training, opt-in; added within ABI 0.9 -- probe for the
+ * symbols), f32 rows: gnx_gcnii_step / gnx_gcnii_step_drop and gnx_gcnii_step_back over the dropped + symmetrically re-normalised
+ * adjacency of one training iteration WITHOUT its value array.  (d_D, edge_p, edge_seed, edge_stream) are the arguments of
+ * gnx_spmm_dropped: d_D the degree scales of that (seed, stream) (gnx_graph_colsum + gnx_degree_scale), and the weight of stored entry
+ * (r, c) is made in the gather loop with the arithmetic of gnx_graph_scale_values,
+ *   w = fl(fl(D[r] * fl(raw * s_e)) * D[c]) if hash_u24(edge_seed, edge_stream + counter, r, c, 0) >= int(edge_p * 2^24), else 0,
+ * s_e the f32 1 / (1 - edge_p) -- bit for bit the value gnx_graph_normalize(symmetric, no add_eye, edge_p, edge_seed, edge_stream)
+ * stores there; on a handle after gnx_graph_enable_entry_dropout a slot's weight is its kept sum, as in gnx_spmm_dropped.  Entry order,
+ * the entries in flight, the fmaf chain, the mix, the transform and the long-row path are those of the constant-adjacency entries, so
+ * every result has the bits of that entry over the materialised values.  SKIP SEMANTICS: an entry of weight exactly 0 (dropped, or a
+ * kept sum of 0) does not gather its row, where the materialised form multiplies it by 0: the precondition of gnx_spmm_dropped --
+ * finite features and finite degree scales -- holds here unchanged (0 * inf and 0 * NaN make a NaN there and not here).  A row all
+ * of whose entries are dropped gives out = act((a H0[r]) . M) and dH[r] = 0.
+ *
+ * gnx_gcnii_step_dropped: out = drop_f(act(T . M)), T = (1-a) A_d . H + a H0; (feat_p, feat_seed, feat_stream) the feature mask of
+ * gnx_gcnii_step_drop, keyed by (row, column) and made in the store loop -- feat_p == 0 means no mask and hashes nothing.  Rounding
+ * points: those of gnx_gcnii_step_drop, with w above in place of the loaded value.  d_mixed receives the undropped T (NULL allowed at
+ * C = 16 / 32 / 64 with aligned buffers).  Hub rows: the chunk kernels of gnx_spmm_dropped over the same weights, then the dense kernel
+ * and the mask pass on those rows alone, as in gnx_gcnii_step_drop.  Other widths and misaligned buffers (they need d_mixed) run
+ * gnx_spmm_dropped, the dense kernel and the mask pass.  Reports "spmm_gcnii_mfma_edrop" / "spmm_gcnii_mfma_edrop_drop" (feat_p > 0),
+ * the other widths "spmm+dense_mfma_edrop" / "spmm+dense_mfma_edrop_drop".
+ *
+ * gnx_gcnii_step_back_dropped: the contract of gnx_gcnii_step_back (dH, S_in / s_alpha / S_out, d_work for the other widths, the
+ * aliasing rules) with the weights of the transposed walk made from the same (d_D, edge_p, edge_seed, edge_stream): transposed entry
+ * (r, c) is A_d[c][r] and draws with (c, r).  Reports "spmm_gcnii_back_mfma_edrop", the other widths "dense+spmm_back_edrop".
+ *
+ * Both refuse (GNX_ERR_UNSUPPORTED) a handle with duplicate COO entries and no entry tables, need a square stand-alone graph (no
+ * vertex block), honour the handle's dropout counter for both masks, and follow the capture and reserve rules of the entries they
+ * mirror (gnx_graph_reserve with GNX_RESERVE_TRANSPOSED before a captured backward).  No float atomics; no scratch beyond the
+ * handle's long-row slab. */
+int gnx_gcnii_step_dropped(gnx_graph_t g, const float *d_D, float edge_p, uint64_t edge_seed, uint64_t edge_stream, const float *d_H,
+                           const float *d_H0, float a, int64_t C, const float *d_M, int64_t ldm, int act, double feat_p,
+                           uint64_t feat_seed, uint64_t feat_stream, float *d_out, float *d_mixed, void *stream);
+int gnx_gcnii_step_back_dropped(gnx_graph_t g, const float *d_D, float edge_p, uint64_t edge_seed, uint64_t edge_stream,
+                                const float *d_G, float a, int64_t C, const float *d_Mt, int64_t ldmt, float *d_dH,
+                                const float *d_S_in, float s_alpha, float *d_S_out, float *d_work, void *stream);
+
 /* ---- the dense ends of the path (matrix cores) -----------------------------------------------------------------------
  * gnx_dense: out = act(X . W + bias) -- Dense.__forward__ (gnntf/core/nn/layers.py:135-136) and the transform of
  * GCNLayer (gcn.py:89).  X [n, F] (ldx), W [F, O] (ldw), bias [O] or NULL, out [n, O] (ldo); float32 in and out, float32
