@@ -280,7 +280,7 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args 
 #pragma unroll
             for (int m = 1; m < GW; m <<= 1) word |= (uint32_t)__shfl_xor((int)word, m);
             if (!live[ps]) continue;
-            R::template store<4>(p, rows[ps] * p.ldo, c, o, false);
+            R::template store<4>(p, rows[ps] * p.ldo, c, o);
             if (sp.gate != nullptr && sub % GW == 0) sp.gate[rows[ps] * WORDS + (c >> 5)] = word;
         }
         return;
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args 
             const DropFuse &fd = feature_mask<EDGE>(p, ed);
             drop_values<4>(fd, drop_stream(fd), rows[ps], c, o);
         }
-        R::template store<4>(p, rows[ps] * p.ldo, c, o, false);
+        R::template store<4>(p, rows[ps] * p.ldo, c, o);
     }
 }
 

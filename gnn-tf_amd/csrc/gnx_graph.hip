@@ -239,6 +239,23 @@ __global__ void k_gather_columns(const int32_t *__restrict__ colidx, const int32
     if (k < nnz) gcol[k] = rank[colidx[k]];
 }
 
+// gather hints: rows by descending entry count (a stable sort of these keys keeps ties in id order) ...
+__global__ void k_hint_keys(const int64_t *__restrict__ rowptr, int64_t n, uint64_t *__restrict__ keys, int32_t *__restrict__ ids) {
+    int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    keys[r] = (uint64_t)(0x7fffffff - (rowptr[r + 1] - rowptr[r]));
+    ids[r] = (int32_t)r;
+}
+
+// ... and per entry its column, bit 31 set when the column is not among the first `hot` rows of that order
+__global__ void k_hint_columns(const int32_t *__restrict__ colidx, const int32_t *__restrict__ rank, int64_t nnz, int64_t hot,
+                               int32_t *__restrict__ hint_cols) {
+    int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nnz) return;
+    const int32_t c = colidx[k];
+    hint_cols[k] = rank[c] < hot ? c : (int32_t)((uint32_t)c | 0x80000000u);
+}
+
 __global__ void k_permute_vals(const float *__restrict__ vals, const int32_t *__restrict__ perm, int64_t n,
                                float *__restrict__ out) {
     int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -459,6 +476,7 @@ int ensure_relabel_features(gnx_graph *g, size_t bytes, hipStream_t s) {
 static void drop_transpose(gnx_graph *g) { static_cast<TransposedPart &>(*g) = TransposedPart(); }
 static void drop_relabel(gnx_graph *g) { static_cast<RelabelledPart &>(*g) = RelabelledPart(); }
 static void drop_gather_order(gnx_graph *g) { static_cast<GatherOrderPart &>(*g) = GatherOrderPart(); }
+static void drop_gather_hints(gnx_graph *g) { static_cast<GatherHintsPart &>(*g) = GatherHintsPart(); }
 
 // Built aside and moved into the handle when complete: no half-built state on failure.
 int ensure_transpose(gnx_graph *g, hipStream_t s) {
@@ -594,6 +612,71 @@ int ensure_train_gather(gnx_graph *g, const char *fn, hipStream_t s) {
     return GNX_OK;
 }
 
+// ---- gather hints (gnx_graph_set_gather_hints; GatherHintsPart) -----------------------------------------------------------------
+static bool takes_gather_hints(const gnx_graph *g) {
+    return g->a.n_rows == g->a.n_cols && g->blk_col_gid == nullptr && g->a.order_window == 0 && g->a.nnz > 0;
+}
+
+// the hot_rows in force for a launch of C columns; 0 = the launch takes no hints
+static int64_t hint_hot_rows(const gnx_graph *g, int64_t C) {
+    if (!takes_gather_hints(g) || g->hint_setting == 0 || C * (int64_t)sizeof(float) < HINT_MIN_ROW_BYTES) return 0;
+    const int64_t n = g->a.n_rows;
+    if (g->hint_setting > 0) return std::min(g->hint_setting, n);
+    if (n < HINT_MIN_ROWS) return 0;
+    return std::min(n, std::max<int64_t>(1, HINT_HOT_BYTES / (C * (int64_t)sizeof(float))));
+}
+
+// hint_cols marked for `hot` rows: the degree order and the array on first use (built aside; not under capture), one pass over
+// the entries whenever `hot` changes (in place and stream-ordered: only bit 31 changes, a launch that reads the array meanwhile
+// still reads the right columns; under capture the array stays as it is).  An allocation that fails turns the hints off.
+static int ensure_gather_hints(gnx_graph *g, int64_t hot, hipStream_t s) {
+    const Csr &a = g->a;
+    const dim3 threads(256);
+    if (g->hint_cols == nullptr) {
+        GNX_NOT_WHILE_CAPTURING(s, "the gather hints of this handle (GNX_RESERVE_GATHER_HINTS)");
+        GatherHintsPart part;
+        DevArray<uint64_t> k0, k1;
+        DevArray<int32_t> ids, order;
+        const size_t n = (size_t)a.n_rows;
+        hipError_t e = part.hint_cols.alloc(a.nnz);
+        if (e == hipSuccess) e = part.hint_rank.alloc(n);
+        if (e == hipSuccess) e = k0.alloc(n);
+        if (e == hipSuccess) e = k1.alloc(n);
+        if (e == hipSuccess) e = ids.alloc(n);
+        if (e == hipSuccess) e = order.alloc(n);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            g->hint_failed = true;
+            set_error("gather hints: %s while allocating %lld bytes for the hinted columns: this handle runs unhinted", hipGetErrorString(e),
+                      (long long)a.nnz * 4);
+            return GNX_OK;
+        }
+        hipLaunchKernelGGL(k_hint_keys, dim3(blocks_for(a.n_rows)), threads, 0, s, a.rowptr, a.n_rows, k0, ids);
+        GNX_TRY(sort_pairs<uint64_t, int32_t>(k0, k1, ids, order, a.n_rows, 31u, s));
+        hipLaunchKernelGGL(k_invert_order, dim3(blocks_for(a.n_rows)), threads, 0, s, order, a.n_rows, part.hint_rank);   // kept as ranks
+        GNX_HIP(hipStreamSynchronize(s));
+        GNX_HIP(hipGetLastError());
+        part.hint_hot = -1;
+        static_cast<GatherHintsPart &>(*g) = std::move(part);
+    }
+    if (g->hint_hot != hot && !stream_is_capturing(s)) {
+        hipLaunchKernelGGL(k_hint_columns, dim3(blocks_for(a.nnz)), threads, 0, s, a.colidx, g->hint_rank, a.nnz, hot, g->hint_cols);
+        GNX_HIP(hipGetLastError());
+        g->hint_hot = hot;
+    }
+    return GNX_OK;
+}
+
+int gather_hints_for(gnx_graph *g, const Csr &m, int64_t C, hipStream_t s, const int32_t **hint_cols) {
+    *hint_cols = nullptr;
+    if (&m != &g->a || g->hint_failed) return GNX_OK;
+    const int64_t hot = hint_hot_rows(g, C);
+    if (hot == 0) return GNX_OK;
+    if (g->hint_cols == nullptr || g->hint_hot != hot) GNX_TRY(ensure_gather_hints(g, hot, s));
+    *hint_cols = g->hint_cols;     // (null after a failed allocation)
+    return GNX_OK;
+}
+
 static int finish_graph(gnx_graph *g, hipStream_t s) {
     GNX_TRY(build_long_plan(g->a, s));
     GNX_HIP(hipGetLastError());
@@ -616,7 +699,7 @@ int gnx_graph_destroy(gnx_graph_t g) {
 
 int gnx_graph_reserve(gnx_graph_t g, int64_t C, int flags, void *stream) {
     GNX_CHECK_ARG(g != nullptr, "gnx_graph_reserve: NULL handle");
-    GNX_CHECK_ARG(C >= 1 && (flags & ~(GNX_RESERVE_TRANSPOSED | GNX_RESERVE_K_LOOP | GNX_RESERVE_TRAIN_GATHER)) == 0,
+    GNX_CHECK_ARG(C >= 1 && (flags & ~(GNX_RESERVE_TRANSPOSED | GNX_RESERVE_K_LOOP | GNX_RESERVE_TRAIN_GATHER | GNX_RESERVE_GATHER_HINTS)) == 0,
                   "gnx_graph_reserve: bad width / flags");
     if (flags & GNX_RESERVE_TRAIN_GATHER) flags |= GNX_RESERVE_TRANSPOSED;
     hipStream_t s = (hipStream_t)stream;
@@ -635,6 +718,10 @@ int gnx_graph_reserve(gnx_graph_t g, int64_t C, int flags, void *stream) {
         chunks = std::max(chunks, g->r.n_chunks);
     }
     if (flags & GNX_RESERVE_TRAIN_GATHER) GNX_TRY(ensure_train_gather(g, "gnx_graph_reserve(GNX_RESERVE_TRAIN_GATHER)", s));
+    if (flags & GNX_RESERVE_GATHER_HINTS) {
+        const int32_t *unused;
+        GNX_TRY(gather_hints_for(g, g->a, C, s, &unused));
+    }
     if (chunks > 0) return ensure_partial(g, (size_t)chunks * (size_t)C * sizeof(float), s);
     return GNX_OK;
 }
@@ -648,6 +735,31 @@ int gnx_graph_gather_order(gnx_graph_t g, const int32_t **d_order, const int32_t
     GNX_TRY(ensure_gather_order(g, nullptr));
     if (d_order) *d_order = g->go_order;
     if (d_rank) *d_rank = g->go_rank;
+    return GNX_OK;
+}
+
+int gnx_graph_set_gather_hints(gnx_graph_t g, int64_t hot_rows, void *stream) {
+    GNX_CHECK_ARG(g != nullptr, "gnx_graph_set_gather_hints: NULL handle");
+    GNX_CHECK_ARG(hot_rows >= -1, "gnx_graph_set_gather_hints: hot_rows %lld is neither -1 (automatic), 0 (off) nor a row count", (long long)hot_rows);
+    hipStream_t s = (hipStream_t)stream;
+    GNX_CHECK_ARG(!stream_is_capturing(s), "gnx_graph_set_gather_hints: the stream is being captured -- set the hints before the capture begins");
+    g->hint_setting = hot_rows;
+    g->hint_failed = false;
+    if (hot_rows == 0) {
+        GNX_HIP(hipDeviceSynchronize());        // launches in flight on any stream may still gather through the array freed here
+        drop_gather_hints(g);
+    } else if (hot_rows > 0 && takes_gather_hints(g)) {
+        GNX_TRY(ensure_gather_hints(g, std::min(hot_rows, g->a.n_rows), s));
+    }
+    return GNX_OK;
+}
+
+int gnx_graph_gather_hints(gnx_graph_t g, const int32_t **d_hint_cols, int64_t *hot_rows, int64_t *last_launch_hot_rows) {
+    GNX_CHECK_ARG(g != nullptr, "gnx_graph_gather_hints: NULL handle");
+    const bool built = takes_gather_hints(g) && g->hint_cols != nullptr && g->hint_hot >= 0;
+    if (d_hint_cols) *d_hint_cols = built ? g->hint_cols.get() : nullptr;
+    if (hot_rows) *hot_rows = built ? g->hint_hot : 0;
+    if (last_launch_hot_rows) *last_launch_hot_rows = g->last_hint_hot;
     return GNX_OK;
 }
 
@@ -680,6 +792,7 @@ int gnx_graph_set_row_window(gnx_graph_t g, int64_t window_rows, void *stream) {
     }
     if (g->has_r) drop_relabel(g);                                   // the degree-relabelled copy belongs to the default order,
     drop_gather_order(g);                                            // and so do the gather order and its per-entry columns
+    drop_gather_hints(g);                                            // (a handle with a window takes no hints; back at 0 they are rebuilt)
     GNX_HIP(hipGetLastError());
     return GNX_OK;
 }

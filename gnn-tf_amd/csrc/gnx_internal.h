@@ -52,6 +52,18 @@ constexpr int TINY_ROWS = 1 << 15;      // below this everything is cache-reside
 // 10M / 100M, K = 10) with the threshold at 32: C = 32 gains 7 % from the order and pays it back for the value permutation, the
 // H0 permutation and the scattered last iteration (22.77 vs 22.78 ms); C = 64 loses.  16 stays.
 constexpr int RELABEL_MAX_C = 16;
+// Gather hints (gnx_graph_set_gather_hints).  The automatic rule marks as hot the rows that fill HINT_HOT_BYTES, the 256 MiB of the
+// Infinity Cache, at the width of the call, on structures of at least HINT_MIN_ROWS rows; rows narrower than HINT_MIN_ROW_BYTES
+// never take hints (they run on the narrow kernels).  Measured (profiles/NOTES.md, gather hints; R-MAT, K = 10, hints against none in
+// one process): an L2-sized hot set LOSES 9-34 % -- most "cold" rows are gathered a few times per launch and a non-temporal load
+// gives that reuse up -- an Infinity-Cache-sized one gains with the size of the graph: C = 128 +6.5 % at 10M rows, +2.3 % at 20M,
+// -1.1 % at 40M, -5.2 % at 80M; C = 64 -0.6 / +3.4 / -5.7 / -5.0 %.  Hence on from 2^25 rows, and opt-in below.
+constexpr int64_t HINT_HOT_BYTES = (int64_t)256 << 20;
+constexpr int64_t HINT_MIN_ROWS = 1 << 25;
+constexpr int64_t HINT_MIN_ROW_BYTES = 256;
+#ifndef GNX_GATHER_HINTS_DEFAULT
+#define GNX_GATHER_HINTS_DEFAULT (-1)
+#endif
 constexpr int SMALL_LONG_ROW = GNX_LONG_ROW < 128 ? GNX_LONG_ROW : 128;
 
 // An owned device array.  Everything a handle keeps on the device, and every temporary of its builds, is one of these, so dropping a
@@ -156,9 +168,21 @@ struct GatherOrderPart {
     DevArray<int32_t> t_gcol;    // [a.nnz]
 };
 
+// gather hints of a square stand-alone handle without a row window (lazy; gnx_graph_set_gather_hints): per entry of the matrix its
+// column with bit 31 set when that column is COLD, i.e. not among the hint_hot rows with the most stored entries (ties to the
+// smaller id).  The wide f32 eval kernels gather a cold row non-temporally, so that the hot rows stay in the L2s.  Only bit 31 is a
+// hint: an array built for another hot_rows still names the right columns, so a launch that must not rebuild (a captured stream)
+// uses the array as it is.
+struct GatherHintsPart {
+    DevArray<int32_t> hint_cols;     // [a.nnz], or null: not built
+    DevArray<int32_t> hint_rank;     // [n] position of every row in the order of descending entry count, ties to the smaller id (kept: another hot_rows is one pass)
+    int64_t hint_hot = 0;            // the hot_rows hint_cols was built for
+    bool hint_failed = false;        // the arrays could not be allocated: the handle runs unhinted and does not try again
+};
+
 }  // namespace gnx
 
-struct gnx_graph : gnx::TransposedPart, gnx::RelabelledPart, gnx::GatherOrderPart {
+struct gnx_graph : gnx::TransposedPart, gnx::RelabelledPart, gnx::GatherOrderPart, gnx::GatherHintsPart {
     gnx::Csr a;            // coalesced matrix
     gnx::DevArray<float> raw_vals;     // [a.nnz] summed duplicate values
     gnx::DevArray<int32_t> rowidx;     // [a.nnz] row of every coalesced entry
@@ -185,6 +209,8 @@ struct gnx_graph : gnx::TransposedPart, gnx::RelabelledPart, gnx::GatherOrderPar
     gnx::DevArray<float> r_feat;       // scratch of the relabelled copy: H0 in relabelled row order (grown on demand, outlives the copy)
     size_t r_feat_bytes = 0;
     const char *last_kernel = "";      // NOT owned: a string literal of the launcher
+    int64_t last_hint_hot = 0;         // hot rows the last SpMM launch over this handle gathered with; 0 = it took no hints
+    int64_t hint_setting = GNX_GATHER_HINTS_DEFAULT;   // gnx_graph_set_gather_hints: -1 automatic, 0 off, n > 0 that many hot rows
 };
 
 namespace gnx {
@@ -199,6 +225,11 @@ int ensure_gather_order(gnx_graph *g, hipStream_t s);
 // duplicate entries or a handle with a row window
 int ensure_train_gather(gnx_graph *g, const char *fn, hipStream_t s);
 int ensure_relabel_features(gnx_graph *g, size_t bytes, hipStream_t s);
+// The hinted columns a wide f32 eval launch of C columns over structure m gathers through, or null: hints are off, the handle or
+// the width does not take them, or their arrays could not be allocated (then gnx_last_error says so; never a failure).  Builds or
+// re-marks the array on first use and when the hot_rows in force changes; GNX_ERR_UNSUPPORTED, naming gnx_graph_reserve, where
+// that would allocate under capture.
+int gather_hints_for(gnx_graph *g, const Csr &m, int64_t C, hipStream_t s, const int32_t **hint_cols);
 
 // blocks of `per_block` items that cover n items
 inline unsigned blocks_for(int64_t n, int per_block = 256) { return (unsigned)((n + per_block - 1) / per_block); }

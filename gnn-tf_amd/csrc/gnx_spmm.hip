@@ -55,6 +55,12 @@ int tune_override = -1;   // set through gnx_debug_set_tune (tuning builds only:
 #endif
 
 int launch_spmm(gnx_graph *g, const Csr &m, SpmmArgs &p, hipStream_t s) {
+    // eval launches of 4 values per lane over the handle's own matrix gather through its hinted columns, where it keeps any
+    const int32_t *hint_cols = nullptr;
+    if (p.fuse.D == nullptr && F32Rows::vec(p) == 4) {
+        const int rc = gather_hints_for(g, m, p.C, s, &hint_cols);
+        if (rc != GNX_OK) return rc;
+    }
     return launch_bound(g, m, p, s, [&](SpmmArgs &q) {
 #ifdef GNX_TUNING   // kernel-variant switches exist only in tuning builds (tools/tune_spmm.py); the product library has none
         static const int tune = [] { const char *e = getenv("GNX_TUNE"); return e ? atoi(e) : 0; }();
@@ -63,6 +69,11 @@ int launch_spmm(gnx_graph *g, const Csr &m, SpmmArgs &p, hipStream_t s) {
 #endif
         // (tried for C = 128: one wave per row with float2 lanes instead of 32-lane groups of float4 -- 10.9 vs 8.2 ms)
         // a training iteration (q.fuse.D) goes to the kernels of gnx_spmm_train.hip
+        if (hint_cols != nullptr) {
+            q.colidx = hint_cols;
+            g->last_hint_hot = g->hint_hot;
+            return launch_eval<F32Rows, true>(q, s);
+        }
         return q.fuse.D != nullptr ? launch_spmm_dropped(q, F32Rows::vec(q), s) : launch_eval<F32Rows>(q, s);
     });
 }

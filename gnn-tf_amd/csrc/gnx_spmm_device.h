@@ -52,29 +52,60 @@ template <> struct NatT<1> { using type = float; };
 template <> struct NatT<2> { using type = f32x2; };
 template <> struct NatT<4> { using type = f32x4; };
 
-// streaming (touched once per launch) data: non-temporal so it does not evict gathered rows
-template <int VEC>
-__device__ __forceinline__ void vload_nt(float (&x)[VEC], const float *__restrict__ p) {
-    if constexpr (VEC == 8) {
-        vload_nt<4>(*reinterpret_cast<float(*)[4]>(&x[0]), p);
-        vload_nt<4>(*reinterpret_cast<float(*)[4]>(&x[4]), p + 4);
-    } else {
-        using T = typename NatT<VEC>::type;
-        const T v = __builtin_nontemporal_load(reinterpret_cast<const T *>(p));
-        __builtin_memcpy(x, &v, sizeof(T));
-    }
+// ---- hinted gathers (gnx_graph_set_gather_hints; f32 rows, 16 bytes per lane) ----------------------------------------------------
+// A hinted column (gnx_graph::hint_cols) carries in bit 31 whether the gathered row is COLD: not one of the handle's hot rows, the
+// ones with the most entries, which are gathered again and again.  A cold row is loaded non-temporally: gfx950's caches then replace
+// it first, and the hot rows stay (tools/gather_policy_probe.hip: hit rate of a 2 MiB hot table beside cold gathers 41 % -> 99 %,
+// the cold gathers themselves 8 % faster; what that is worth in these kernels, and for which hot sets: gnx_internal.h, HINT_HOT_BYTES).
+// Source-level selection between a plain and a non-temporal load does not survive the compiler (it merges the two into one plain
+// load, or speculates both), so one asm statement holds both forms.  hipcc counts nothing inside asm: a batch of gathers is followed by ONE gather_wait over the batch's registers, and nothing reads them before.
+// The statements carry no "memory" clobber on purpose: the gathered matrix is only read by its launch, and the index loads of the
+// compiler must stay free to move ahead of the gathers (behind one, their wait would drain it).
+constexpr int HINT_NONE = -1;            // hinted column of an entry that does not exist (ragged batch): neither form loads
+__device__ __forceinline__ int hint_col(int j) { return j & 0x7fffffff; }
+
+// per lane: the lanes of one wave may hold rows of either kind (two 32-lane groups), so the choice is by exec mask, restored at the
+// end; a form that no lane takes is branched over (an instruction without lanes still takes its turn in the address unit)
+__device__ __forceinline__ void gather16_hinted(f32x4 &x, const float *q, int j) {
+    uint64_t keep;
+    asm volatile("s_mov_b64 %[keep], exec\n\t"
+                 "v_cmp_gt_i32_e32 vcc, -1, %[j]\n\t"              // cold: bit 31 set, and not HINT_NONE
+                 "s_and_b64 exec, %[keep], vcc\n\t"
+                 "s_cbranch_scc0 .Lgnx_nocold%=\n\t"
+                 "global_load_dwordx4 %[x], %[q], off nt\n"
+                 ".Lgnx_nocold%=:\n\t"
+                 "s_mov_b64 exec, %[keep]\n\t"
+                 "v_cmp_lt_i32_e32 vcc, -1, %[j]\n\t"              // hot: bit 31 clear
+                 "s_and_b64 exec, %[keep], vcc\n\t"
+                 "s_cbranch_scc0 .Lgnx_nohot%=\n\t"
+                 "global_load_dwordx4 %[x], %[q], off\n"
+                 ".Lgnx_nohot%=:\n\t"
+                 "s_mov_b64 exec, %[keep]"
+                 : [x] "+v"(x), [keep] "=&s"(keep)
+                 : [q] "v"(q), [j] "v"(j)
+                 : "vcc", "scc");
 }
-template <int VEC>
-__device__ __forceinline__ void vstore_nt(float *__restrict__ p, const float (&x)[VEC]) {
-    if constexpr (VEC == 8) {
-        vstore_nt<4>(p, *reinterpret_cast<const float(*)[4]>(&x[0]));
-        vstore_nt<4>(p + 4, *reinterpret_cast<const float(*)[4]>(&x[4]));
-    } else {
-        using T = typename NatT<VEC>::type;
-        T v;
-        __builtin_memcpy(&v, x, sizeof(T));
-        __builtin_nontemporal_store(v, reinterpret_cast<T *>(p));
-    }
+
+// the column is wave-uniform (v_readlane): a scalar branch picks the form
+__device__ __forceinline__ void gather16_hinted_uniform(f32x4 &x, const float *q, int j) {
+    asm volatile("s_bitcmp1_b32 %[j], 31\n\t"
+                 "s_cbranch_scc1 .Lgnx_cold%=\n\t"
+                 "global_load_dwordx4 %[x], %[q], off\n\t"
+                 "s_branch .Lgnx_done%=\n"
+                 ".Lgnx_cold%=:\n\t"
+                 "global_load_dwordx4 %[x], %[q], off nt\n"
+                 ".Lgnx_done%=:"
+                 : [x] "+v"(x)
+                 : [q] "v"(q), [j] "s"(j)
+                 : "scc");
+}
+
+// every hinted gather of a batch has landed; the batch's registers are operands so that nothing reads them ahead of the wait
+template <int U>
+__device__ __forceinline__ void gather_wait(f32x4 (&x)[U]) {
+    static_assert(U == 4 || U == 8, "batches of 4 or 8 gathers");
+    if constexpr (U == 4) asm volatile("s_waitcnt vmcnt(0)" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]));
+    else asm volatile("s_waitcnt vmcnt(0)" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]));
 }
 
 // ---- bf16 rows: one load of up to 8 bf16 (16 bytes) widened exactly to f32, and the rounding store ----
@@ -158,10 +189,7 @@ struct F32Rows {
     __device__ static bool has_out2(const Args &p) { return p.out2 != nullptr; }
     __device__ static const float *out_scale(const Args &p) { return p.out_scale; }
     template <int VEC>
-    __device__ static void store(const Args &p, int64_t at, int c, const float (&o)[VEC], bool nt) {
-        if (nt) vstore_nt<VEC>(p.out + at + c, o);
-        else vstore<VEC>(p.out + at + c, o);
-    }
+    __device__ static void store(const Args &p, int64_t at, int c, const float (&o)[VEC]) { vstore<VEC>(p.out + at + c, o); }
     template <int VEC>
     __device__ static void store2(const Args &p, int64_t at, int c, const float (&o)[VEC]) { vstore<VEC>(p.out2 + at + c, o); }
     // (the second result's row starts are not looked at: every caller so far keeps it laid out like the first)
@@ -220,7 +248,7 @@ struct Bf16RowsT {
     __device__ static bool has_out2(const Args &p) { return TRAIN && p.out2b != nullptr; }
     __device__ static const float *out_scale(const Args &p) { return TRAIN ? p.out_scale : nullptr; }
     template <int VEC>
-    __device__ static void store(const Args &p, int64_t at, int c, const float (&o)[VEC], bool) {
+    __device__ static void store(const Args &p, int64_t at, int c, const float (&o)[VEC]) {
         if (p.out_bf16) bstore<VEC>(static_cast<uint16_t *>(p.outv) + at + c, o);
         else vstore<VEC>(static_cast<float *>(p.outv) + at + c, o);
     }
@@ -248,8 +276,11 @@ __device__ __forceinline__ const int32_t *gather_cols(const typename R::Args &p)
 // Sum of w_e * X[col_e, c .. c+VEC) over entries [beg, end) of one row; the whole wave works
 // on the same entries (beg/end wave-uniform), lane `lane` owns columns c .. c+VEC.  ENTRIES (with FUSE): the handle holds duplicate
 // entries and the weight of a slot is its kept sum (dropped_weight_entries).  GCOL (with FUSE): the gathered row of an entry is
-// gcol[entry] instead of its column (gather_cols).
-template <typename R, int VEC, int U, bool FUSE = false, bool ENTRIES = false, bool GCOL = false>
+// gcol[entry] instead of its column (gather_cols).  HINT (eval, f32 rows of 4 values per lane): `colidx` holds the handle's hinted
+// columns and the gathers go through gather16_hinted_uniform; the same entries in the same order into the same fused multiply-adds.
+// (nt_index: no caller sets it any more -- the tuning switch that did measured +-0 % and is gone -- but taking the parameter out
+// changes the instruction schedule of the training kernels, which are kept as measured)
+template <typename R, int VEC, int U, bool FUSE = false, bool ENTRIES = false, bool GCOL = false, bool HINT = false>
 __device__ __forceinline__ void wave_accumulate(const int32_t *__restrict__ colidx, const float *__restrict__ vals,
                                                 const typename R::Elem *__restrict__ X, int64_t ldx, int64_t beg, int64_t end,
                                                 int c, int lane, float (&acc)[VEC], bool nt_index = false,
@@ -301,6 +332,46 @@ __device__ __forceinline__ void wave_accumulate(const int32_t *__restrict__ coli
             }
             continue;
         }
+        if constexpr (HINT) {
+            static_assert(VEC == 4 && !FUSE && std::is_same_v<typename R::Elem, float>, "hinted gathers: f32 rows, 16 bytes per lane, eval");
+            for (; i + U <= n; i += U) {
+                f32x4 x[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int j = readlane_i(mycol, i + u);
+                    x[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    gather16_hinted_uniform(x[u], X + (int64_t)hint_col(j) * ldx + c, j);
+                }
+                gather_wait<U>(x);
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const float w = readlane_f(myval, i + u);
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w, x[u][v], acc[v]);
+                }
+            }
+            if (i < n) {  // 1 .. U-1 entries left (wave-uniform branches)
+                f32x4 x[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    x[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    if (u < U - 1 && i + u < n) {
+                        const int j = readlane_i(mycol, i + u);
+                        gather16_hinted_uniform(x[u], X + (int64_t)hint_col(j) * ldx + c, j);
+                    }
+                }
+                gather_wait<U>(x);
+#pragma unroll
+                for (int u = 0; u < U - 1; ++u) {
+                    if (i + u < n) {
+                        const float w = readlane_f(myval, i + u);
+#pragma unroll
+                        for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w, x[u][v], acc[v]);
+                    }
+                }
+            }
+            continue;
+        }
         for (; i + U <= n; i += U) {
             float x[U][VEC];
 #pragma unroll
@@ -340,8 +411,7 @@ __device__ __forceinline__ void wave_accumulate(const int32_t *__restrict__ coli
 // (every optional piece hangs on a wave-uniform null test of the policy's pointer: diag, the second result, the row map, the next
 // iteration's scale)
 template <typename R, int VEC>
-__device__ __forceinline__ void epilogue_store(const typename R::Args &p, int64_t row, int c, bool active, float (&acc)[VEC],
-                                               bool nt = false) {
+__device__ __forceinline__ void epilogue_store(const typename R::Args &p, int64_t row, int c, bool active, float (&acc)[VEC]) {
     if (!active) return;
     if (R::diag(p)) {
         const float d = R::diag(p)[row];
@@ -366,8 +436,7 @@ __device__ __forceinline__ void epilogue_store(const typename R::Args &p, int64_
     if (p.H0) {
         const int64_t hrow = p.map_h0 ? orow : row;   // gnx_spmm_rows: H0 is indexed like the output
         float h0[VEC];
-        if (nt) vload_nt<VEC>(h0, p.H0 + hrow * p.ldh0 + c);
-        else vload<VEC>(h0, p.H0 + hrow * p.ldh0 + c);
+        vload<VEC>(h0, p.H0 + hrow * p.ldh0 + c);
 #pragma unroll
         for (int v = 0; v < VEC; ++v) o[v] = fmaf(acc[v], p.beta, h0[v] * p.alpha);   // spelled out: every kernel variant rounds alike
     } else {
@@ -383,7 +452,7 @@ __device__ __forceinline__ void epilogue_store(const typename R::Args &p, int64_
 #pragma unroll
         for (int v = 0; v < VEC; ++v) o[v] *= os;
     }
-    R::template store<VEC>(p, orow * p.ldo, c, o, nt);
+    R::template store<VEC>(p, orow * p.ldo, c, o);
 }
 
 // Which block of row slots this workgroup takes.  Default: its own index.  With a locality order (SpmmArgs::xcd_rows > 0) the index
@@ -515,6 +584,7 @@ int launch_bound(gnx_graph *g, const Csr &m, Args &p, hipStream_t s, Pick pick) 
     int rc = bind_csr(g, m, p, s);
     if (rc != GNX_OK) return rc;
     if (m.n_rows == 0) return GNX_OK;
+    g->last_hint_hot = 0;          // (set again by a launch that gathers through the hinted columns: launch_spmm)
     g->last_kernel = pick(p);
     GNX_HIP(hipGetLastError());
     return GNX_OK;
@@ -561,6 +631,8 @@ RowClass with_group(int lanes, F &&f) {
 }
 
 // "spmm_" class ["+long" | "+chunks"] ["_drop" ["_entries"]] ["_bf16" | "_ord"]: every name reported so far, byte for byte, from one scheme.
+// (A launch that gathers through the handle's hinted columns reports the name of its class unchanged -- clients and tests compare
+// these names -- and gnx_graph_gather_hints says how many hot rows the last launch ran with.)
 // (The table spells out the whole product; most of its combinations -- "spmm_wave+chunks", "spmm_group4_drop" -- cannot be reported.)
 enum NameHubs { HUBS_NONE, HUBS_LONG, HUBS_CHUNKS };      // hub rows: none (or not named), separate chunk launches, chunks in the row launch
 enum NameMode { MODE_EVAL, MODE_DROP, MODE_DROP_ENTRIES };

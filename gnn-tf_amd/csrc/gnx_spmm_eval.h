@@ -7,9 +7,10 @@
 namespace {
 
 // ---- wide path: one wave per row -----------------------------------------------------------
-// tune bits (GNX_TUNE, experiments): 1 = degree-binned row order, 2 = non-temporal H0/out, 4 = non-temporal col/val
-// (f32 rows only: R::EXPERIMENTS)
-template <typename R, int VEC, int U, int WPB>
+// tune bits (GNX_TUNE, experiments): 1 = degree-binned row order (f32 rows only: R::EXPERIMENTS)
+// HINT, here and in every kernel below: p.colidx holds the handle's hinted columns and a cold row is gathered non-temporally
+// (gnx_spmm_device.h, hinted gathers); false = the kernel as it always was.
+template <typename R, int VEC, int U, int WPB, bool HINT = false>
 __global__ __launch_bounds__(64 * WPB) void k_spmm_wave(const typename R::Args p) {
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -25,14 +26,14 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_wave(const typename R::Args p
         float acc[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-        wave_accumulate<R, VEC, U>(p.colidx, p.vals, R::X(p), p.ldx, beg, end, active ? c : 0, lane, acc, (tune & 4) != 0);
-        epilogue_store<R, VEC>(p, row, c, active, acc, (tune & 2) != 0);
+        wave_accumulate<R, VEC, U, false, false, false, HINT>(p.colidx, p.vals, R::X(p), p.ldx, beg, end, active ? c : 0, lane, acc);
+        epilogue_store<R, VEC>(p, row, c, active, acc);
     }
 }
 
 // ---- narrow path: G lanes per row, 256/G rows per block ---------------------------------------
 // PIPE: the (col, val) pairs of batch b+1 are fetched while the gathers of batch b are in flight.
-template <typename R, int VEC, int G, int U, bool PIPE>
+template <typename R, int VEC, int G, int U, bool PIPE, bool HINT = false>
 __device__ __forceinline__ void group_rows(const typename R::Args &p, int64_t block) {
     constexpr int RPB = 256 / G;
     const int sub = threadIdx.x % G;
@@ -48,7 +49,30 @@ __device__ __forceinline__ void group_rows(const typename R::Args &p, int64_t bl
         float acc[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-        if (PIPE) {
+        if constexpr (HINT) {
+            static_assert(VEC == 4 && !PIPE && std::is_same_v<typename R::Elem, float>, "hinted gathers: f32 rows, 16 bytes per lane");
+            for (int64_t e = beg; e < end; e += U) {   // the batches of the plain form; an entry past the row's end loads nothing
+                int j[U];
+                float w[U];
+                f32x4 x[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const bool ok = e + u < end;
+                    j[u] = ok ? p.colidx[e + u] : HINT_NONE;
+                    w[u] = ok ? p.vals[e + u] : 0.f;
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    x[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    gather16_hinted(x[u], Xc + (int64_t)hint_col(j[u]) * p.ldx, j[u]);
+                }
+                gather_wait<U>(x);
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
+            }
+        } else if (PIPE) {
             int jn[U];
             float wn[U];
 #pragma unroll
@@ -159,14 +183,14 @@ __device__ __forceinline__ void group_rows_coop(const typename R::Args &p, int64
     }
 }
 
-template <typename R, int VEC, int G, int U, bool PIPE>
+template <typename R, int VEC, int G, int U, bool PIPE, bool HINT = false>
 __global__ __launch_bounds__(256) void k_spmm_group(const typename R::Args p) {
     if (G <= 8) group_rows_coop<R, VEC, G, 4>(p, xcd_block(p));
-    else group_rows<R, VEC, G, U, PIPE>(p, xcd_block(p));
+    else group_rows<R, VEC, G, U, PIPE, HINT>(p, xcd_block(p));
 }
 
 // ---- long rows ---------------------------------------------------------------------------------
-template <typename R, int VEC, int U>
+template <typename R, int VEC, int U, bool HINT = false>
 __global__ __launch_bounds__(256) void k_spmm_long_partial(const typename R::Args p) {
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -179,14 +203,14 @@ __global__ __launch_bounds__(256) void k_spmm_long_partial(const typename R::Arg
         float acc[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-        wave_accumulate<R, VEC, U>(p.colidx, p.vals, R::X(p), p.ldx, beg, end, active ? c : 0, lane, acc);
+        wave_accumulate<R, VEC, U, false, false, false, HINT>(p.colidx, p.vals, R::X(p), p.ldx, beg, end, active ? c : 0, lane, acc);
         if (active) vstore<VEC>(p.partial + chunk * (int64_t)p.C + c, acc);
     }
 }
 
 // Narrow features: a chunk's entries are dealt round-robin to the wave's 64/G sub-groups of G lanes
 // (each sub-group gathers whole C-wide rows), then the sub-group sums are added with a fixed xor tree.
-template <typename R, int VEC, int G, int U>
+template <typename R, int VEC, int G, int U, bool HINT = false>
 __device__ __forceinline__ void long_chunks_group(const typename R::Args &p, int64_t block) {
     constexpr int NS = 64 / G;
     const int lane = threadIdx.x & 63;
@@ -202,6 +226,29 @@ __device__ __forceinline__ void long_chunks_group(const typename R::Args &p, int
 #pragma unroll
     for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
     for (int64_t e = beg + sub; e < end; e += (int64_t)NS * U) {
+        if constexpr (HINT) {
+            static_assert(VEC == 4 && std::is_same_v<typename R::Elem, float>, "hinted gathers: f32 rows, 16 bytes per lane");
+            int j[U];
+            float w[U];
+            f32x4 x[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t eu = e + (int64_t)u * NS;
+                j[u] = eu < end ? p.colidx[eu] : HINT_NONE;
+                w[u] = eu < end ? p.vals[eu] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                x[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+                gather16_hinted(x[u], Xc + (int64_t)hint_col(j[u]) * p.ldx, j[u]);
+            }
+            gather_wait<U>(x);
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
+            continue;
+        }
         float x[U][VEC];
         float w[U];
 #pragma unroll
@@ -229,25 +276,25 @@ __device__ __forceinline__ void long_chunks_group(const typename R::Args &p, int
     if (sub == 0 && active) vstore<VEC>(p.partial + chunk * (int64_t)p.C + c, acc);
 }
 
-template <typename R, int VEC, int G, int U>
+template <typename R, int VEC, int G, int U, bool HINT = false>
 __global__ __launch_bounds__(256) void k_spmm_long_partial_group(const typename R::Args p) {
-    long_chunks_group<R, VEC, G, U>(p, blockIdx.x);
+    long_chunks_group<R, VEC, G, U, HINT>(p, blockIdx.x);
 }
 
 // Short rows and the chunks of the long rows in ONE launch, for graphs with few chunks (a citation-graph-sized matrix has a few
 // hundred): a chunk is one wave walking 512 entries, so a launch of a few hundred waves is bound by the latency of that walk
 // (0.11 ms at C = 128) while most of the card idles; here the chunk blocks are dealt first and the short rows fill the rest of
 // the card under them.  Same per-row arithmetic as the two separate launches; k_spmm_long_reduce follows as before.
-template <typename R, int VEC, int G>
+template <typename R, int VEC, int G, bool HINT = false>
 __global__ __launch_bounds__(256) void k_spmm_group_and_chunks(const typename R::Args p, int chunk_blocks) {
-    if ((int)blockIdx.x < chunk_blocks) long_chunks_group<R, VEC, G, 4>(p, blockIdx.x);
+    if ((int)blockIdx.x < chunk_blocks) long_chunks_group<R, VEC, G, 4, HINT>(p, blockIdx.x);
     else if (G <= 8) group_rows_coop<R, VEC, G, 4>(p, (int64_t)blockIdx.x - chunk_blocks);
-    else group_rows<R, VEC, G, 4, false>(p, (int64_t)blockIdx.x - chunk_blocks);
+    else group_rows<R, VEC, G, 4, false, HINT>(p, (int64_t)blockIdx.x - chunk_blocks);
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------
 // the short rows; the class that took them
-template <typename R, int VEC>
+template <typename R, int VEC, bool HINT = false>
 RowClass launch_rows(const typename R::Args &p0, hipStream_t s) {
     typename R::Args p = p0;
     const int lanes = (p.C + VEC - 1) / VEC;  // lanes needed to cover one row
@@ -259,11 +306,12 @@ RowClass launch_rows(const typename R::Args &p0, hipStream_t s) {
     if (p.n_rows == 0) return ROWS_NONE;
     if (lanes > 32) {
         // measured: U = 8 rows in flight is the plateau (U=4 +0.7 %, U=16 +17 %, forcing 8 waves/SIMD +14 %,
-        // degree-ordered rows +9 %, non-temporal H0/out/index loads +-0 %)
+        // degree-ordered rows +9 %; non-temporal index loads +-0 % -- the "non-temporal H0/out" switch measured beside them compiled
+        // to plain accesses and said nothing: both switches are gone)
         // measured (tools/tune_spmm.py): 8 waves per block are 1.6 % faster than 4 when the row is one tile wide
         // (C = 256), 0.6 % slower at two tiles (C = 512); 2 and 16 waves per block lose 3-11 %
-        if (p.C <= 64 * VEC) GNX_ROW_PIECES((k_spmm_wave<R, VEC, 8, 8>), 8, 512);
-        else                 GNX_ROW_PIECES((k_spmm_wave<R, VEC, 8, 4>), 4, 256);
+        if (p.C <= 64 * VEC) GNX_ROW_PIECES((k_spmm_wave<R, VEC, 8, 8, HINT>), 8, 512);
+        else                 GNX_ROW_PIECES((k_spmm_wave<R, VEC, 8, 4, HINT>), 4, 256);
         return ROWS_WAVE;
     }
     // measured (tools/tune_spmm.py, RMAT 10M/100M): prefetching the next (col, val) batch behind the gathers pays for G <= 8
@@ -283,12 +331,12 @@ RowClass launch_rows(const typename R::Args &p0, hipStream_t s) {
             }
         }
 #endif
-        GNX_ROW_PIECES((k_spmm_group<R, VEC, G(), 4, false>), 256 / G(), 256);
+        GNX_ROW_PIECES((k_spmm_group<R, VEC, G(), 4, false, HINT && G() >= 16>), 256 / G(), 256);
     });
 }
 
 // few chunks (see k_spmm_group_and_chunks): one launch for the short rows and the chunks, then the reduce; ROWS_NONE = not taken
-template <typename R, int VEC>
+template <typename R, int VEC, bool HINT = false>
 RowClass launch_rows_and_chunks(const typename R::Args &p, hipStream_t s) {
     const int lanes = (p.C + VEC - 1) / VEC;
     // (tune bit 65536: tuning builds' A/B of the merged launch on big graphs)
@@ -296,29 +344,31 @@ RowClass launch_rows_and_chunks(const typename R::Args &p, hipStream_t s) {
     const unsigned cb = blocks_for(p.n_chunks, 4);
     // (4-lane groups: these launches are latency-bound)
     const RowClass rows = with_group<true>(lanes, [&](auto G) {
-        hipLaunchKernelGGL((k_spmm_group_and_chunks<R, VEC, G()>), dim3(cb + blocks_for(p.n_rows, 256 / G())), dim3(256), 0, s, p, (int)cb);
+        hipLaunchKernelGGL((k_spmm_group_and_chunks<R, VEC, G(), HINT && G() >= 16>), dim3(cb + blocks_for(p.n_rows, 256 / G())), dim3(256), 0, s, p, (int)cb);
     });
     GNX_LAUNCH((k_spmm_long_reduce<R, VEC>), blocks_for(p.n_long, 4), p);
     return rows;
 }
 
 // the long rows in launches of their own: partial sums per chunk, then the reduce
-template <typename R, int VEC>
+template <typename R, int VEC, bool HINT = false>
 void launch_long(const typename R::Args &p, hipStream_t s) {
     const int lanes = (p.C + VEC - 1) / VEC;
-    if (lanes > 32) GNX_LAUNCH((k_spmm_long_partial<R, VEC, 8>), blocks_for(p.n_chunks, 4), p);
-    else with_group<true>(lanes, [&](auto G) { GNX_LAUNCH((k_spmm_long_partial_group<R, VEC, G(), 4>), blocks_for(p.n_chunks, 4), p); });
+    if (lanes > 32) GNX_LAUNCH((k_spmm_long_partial<R, VEC, 8, HINT>), blocks_for(p.n_chunks, 4), p);
+    else with_group<true>(lanes, [&](auto G) { GNX_LAUNCH((k_spmm_long_partial_group<R, VEC, G(), 4, HINT && G() >= 16>), blocks_for(p.n_chunks, 4), p); });
     GNX_LAUNCH((k_spmm_long_reduce<R, VEC>), blocks_for(p.n_long, 4), p);
 }
 
-// one eval-mode SpMM over bound arguments (bind_csr); the name gnx_graph_last_kernel reports
-template <typename R>
+// one eval-mode SpMM over bound arguments (bind_csr); the name gnx_graph_last_kernel reports.  HINT: p.colidx holds the handle's
+// hinted columns (the caller made sure that the launch runs 4 values per lane on at least 16 lanes: launch_spmm, gather_hints_for).
+template <typename R, bool HINT = false>
 const char *launch_eval(const typename R::Args &p, hipStream_t s) {
     return with_vec<R>(R::vec(p), [&](auto V) {
-        RowClass rows = launch_rows_and_chunks<R, V()>(p, s);
+        constexpr bool H = HINT && V() == 4;
+        RowClass rows = launch_rows_and_chunks<R, V(), H>(p, s);
         if (rows != ROWS_NONE) return kernel_name<R>(rows, MODE_EVAL, HUBS_CHUNKS);
-        rows = launch_rows<R, V()>(p, s);
-        if (p.n_long > 0) launch_long<R, V()>(p, s);
+        rows = launch_rows<R, V(), H>(p, s);
+        if (p.n_long > 0) launch_long<R, V(), H>(p, s);
         return kernel_name<R>(rows, MODE_EVAL, p.n_long > 0 ? HUBS_LONG : HUBS_NONE);
     });
 }

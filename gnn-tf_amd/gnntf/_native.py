@@ -18,7 +18,7 @@ NORM = {"none": 0, "symmetric": 1, "bipartite": 2}
 EYE = {"none": 0, "before": 1, "after": 2}
 ACT_NONE, ACT_RELU, ACT_SKIP_EMPTY = 0, 1, 256
 HALO_ALL, HALO_PULL, HALO_PUSH = 0, 1, 2
-RESERVE_TRANSPOSED, RESERVE_K_LOOP, RESERVE_TRAIN_GATHER = 1, 2, 4
+RESERVE_TRANSPOSED, RESERVE_K_LOOP, RESERVE_TRAIN_GATHER, RESERVE_GATHER_HINTS = 1, 2, 4, 8
 ORD_X, ORD_OUT = 1, 2     # `order` of the _ord training entries: X stored in the handle's gather order / the result written in it
 
 # name -> (restype, argtypes); must list every symbol include/gnx.h declares
@@ -37,6 +37,8 @@ SIGNATURES = {
     "gnx_graph_reserve": (c_int, [c_void_p, c_int64, c_int, c_void_p]),
     "gnx_graph_enable_entry_dropout": (c_int, [c_void_p, c_void_p]),
     "gnx_graph_set_row_window": (c_int, [c_void_p, c_int64, c_void_p]),
+    "gnx_graph_set_gather_hints": (c_int, [c_void_p, c_int64, c_void_p]),
+    "gnx_graph_gather_hints": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64)]),
     "gnx_graph_set_dropout_counter": (c_int, [c_void_p, c_void_p]),
     "gnx_graph_set_block": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "gnx_graph_colsum": (c_int, [c_void_p, c_float, c_uint64, c_uint64, c_void_p, c_void_p]),

@@ -137,15 +137,16 @@ class DeviceGraph:
     def last_kernel(self) -> str:
         return (nat.lib().gnx_graph_last_kernel(self._h) or b"").decode()
 
-    def reserve(self, C, transposed=False, k_loop=False, train_gather=False):
+    def reserve(self, C, transposed=False, k_loop=False, train_gather=False, gather_hints=False):
         """Builds NOW what the launches otherwise build on first use, sized for feature rows of up to ``C`` floats (the long-row
         slab; with ``transposed`` the transposed structure a backward needs; with ``k_loop`` the relabelled copy appnp_propagate
         runs narrow widths on; with ``train_gather`` the gather order and gather columns of the training loops' relabelled operand
-        order, ppr_loop(gather_order="relabelled"), which implies ``transposed``): those lazy builds allocate and synchronise, which
+        order, ppr_loop(gather_order="relabelled"), which implies ``transposed``; with ``gather_hints`` the hinted columns of
+        set_gather_hints at this width): those lazy builds allocate and synchronise, which
         a stream under hipGraph capture must not see (a launch that would have to grow something there raises instead).  Call
         before capturing (gnx_graph_reserve)."""
         flags = ((nat.RESERVE_TRANSPOSED if transposed else 0) | (nat.RESERVE_K_LOOP if k_loop else 0)
-                 | (nat.RESERVE_TRAIN_GATHER if train_gather else 0))
+                 | (nat.RESERVE_TRAIN_GATHER if train_gather else 0) | (nat.RESERVE_GATHER_HINTS if gather_hints else 0))
         with nat.on_device(self.device):
             nat.check(nat.lib().gnx_graph_reserve(self._h, int(C), flags, nat.current_stream()))
 
@@ -157,6 +158,30 @@ class DeviceGraph:
         with nat.on_device(self.device):
             nat.check(nat.lib().gnx_graph_gather_order(self._h, byref(order), byref(rank)))
             return tuple(torch.as_tensor(_BorrowedInt32(p.value, self.n_rows), device=self.device).clone() for p in (order, rank))
+
+    def set_gather_hints(self, hot_rows=-1):
+        """Gather hints of the wide float32 eval launches (gnx_graph_set_gather_hints): the ``hot_rows`` rows with the most entries
+        are the ones worth keeping in the L2s; every other row is gathered with a non-temporal load.  -1 = automatic (large graphs,
+        the rows that fill half an L2 at the width of the call), 0 = off, n > 0 = that many hot rows.  Same bits either way."""
+        with nat.on_device(self.device):
+            nat.check(nat.lib().gnx_graph_set_gather_hints(self._h, int(hot_rows), nat.current_stream()))
+
+    def gather_hints(self):
+        """(hinted columns int32 [nnz] or None, hot_rows): a copy of the handle's hinted column array -- the column of every entry,
+        bit 31 set where the column is not a hot row -- and the hot-row count it was built for (gnx_graph_gather_hints)."""
+        cols, hot = c_void_p(), c_int64()
+        with nat.on_device(self.device):
+            nat.check(nat.lib().gnx_graph_gather_hints(self._h, byref(cols), byref(hot), None))
+            if not cols.value:
+                return None, 0
+            torch.cuda.current_stream().synchronize()
+            return torch.as_tensor(_BorrowedInt32(cols.value, self.nnz), device=self.device).clone(), hot.value
+
+    def last_launch_hot_rows(self) -> int:
+        """Hot rows the last SpMM launch over this graph gathered with; 0 = it took no gather hints (last_kernel() does not say)."""
+        last = c_int64()
+        nat.check(nat.lib().gnx_graph_gather_hints(self._h, None, None, byref(last)))
+        return last.value
 
     def set_row_window(self, window_rows):
         """Declares that the vertex numbering of THIS graph carries locality (a community / breadth-first order): launches take the

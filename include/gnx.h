@@ -63,7 +63,8 @@ const char *gnx_last_error(void);
  * (gnx_gcnii_step_drop, gnx_feature_dropout, gnx_feature_dropout_back), likewise, and the bf16 row storage of GCNII training
  * (gnx_gcnii_step_train_bf16, gnx_feature_dropout_back_bf16, gnx_gcnii_step_back_bf16), likewise, and the GCNII weight gradient
  * without stored mixed rows (gnx_gcnii_wgrad, gnx_gcnii_wgrad_bf16, gnx_gcnii_step_drop_bf16, gnx_graph_hub_rows), likewise, and the
- * spectral-preserving GCNII layer in one launch (gnx_gcnii_step_spectral, gnx_gcnii_spectral_back), likewise. */
+ * spectral-preserving GCNII layer in one launch (gnx_gcnii_step_spectral, gnx_gcnii_spectral_back), likewise, and the gather hints of
+ * the wide eval launches (gnx_graph_set_gather_hints, gnx_graph_gather_hints, GNX_RESERVE_GATHER_HINTS), likewise. */
 #define GNX_ABI_VERSION 900
 int gnx_version(void);
 
@@ -123,13 +124,34 @@ int gnx_graph_normalize(gnx_graph_t g, int normalized, int add_eye, float dropou
  * gnx_appnp_propagate runs narrow widths on, with
  * GNX_RESERVE_TRAIN_GATHER what gnx_spmm_dropped_chained_ord / gnx_spmm_dropped_back_ord walk (the gather order and the gather
  * columns of the matrix and of the transposed structure; implies GNX_RESERVE_TRANSPOSED; GNX_ERR_UNSUPPORTED on a vertex block, a
- * handle with duplicate entries or a handle with a row window).  Those lazy builds allocate and synchronise, which a stream that is
+ * handle with duplicate entries or a handle with a row window), with GNX_RESERVE_GATHER_HINTS the hinted columns an eval launch of
+ * width C would otherwise build on first use (gnx_graph_set_gather_hints; nothing where the handle or the width takes none).  Those lazy builds allocate and synchronise, which a stream that is
  * being captured into a hipGraph must not see: a compute entry that would have to grow something under capture fails with
  * GNX_ERR_UNSUPPORTED and a message naming this call.  Reserve (or run the launch once eagerly) BEFORE capturing; replays then
  * touch no allocator.  ("an optional caller-provided workspace" -- the workspace stays owned by the handle, the
  * caller decides when it is sized.)  Nothing in the reference corresponds: TensorFlow eager allocates per op. */
-enum { GNX_RESERVE_TRANSPOSED = 1, GNX_RESERVE_K_LOOP = 2, GNX_RESERVE_TRAIN_GATHER = 4 };
+enum { GNX_RESERVE_TRANSPOSED = 1, GNX_RESERVE_K_LOOP = 2, GNX_RESERVE_TRAIN_GATHER = 4, GNX_RESERVE_GATHER_HINTS = 8 };
 int gnx_graph_reserve(gnx_graph_t g, int64_t C, int flags, void *stream);
+
+/* Gather hints (added within ABI 0.9 -- probe for the symbols).  On a power-law graph a few rows of the gathered matrix receive a
+ * large share of all gathers; they are worth more in the caches than the many rows a launch gathers once or twice.  With hints
+ * the handle keeps, per entry of the matrix, its column with bit 31 set when the column is COLD -- not one of the `hot_rows` rows
+ * with the most stored entries, ties to the smaller id -- and the wide float32 eval launches (gnx_spmm and the loops built on it:
+ * feature rows of at least 256 bytes, 4 values per lane) gather a cold row with a non-temporal load, which the L2 replaces first.
+ * Same entries, same order, same fused multiply-adds: results are bitwise those without hints; gnx_graph_last_kernel reports the
+ * same name either way (gnx_graph_gather_hints says whether the last launch took hints).  Costs 4 bytes per entry plus 4 per row; built on first use or by
+ * gnx_graph_reserve(GNX_RESERVE_GATHER_HINTS) (under capture without it: GNX_ERR_UNSUPPORTED naming that call).  If the arrays
+ * cannot be allocated the handle runs unhinted, the calls succeed and gnx_last_error says so.  Square stand-alone handles without a
+ * row window only: a vertex block, a non-square handle and a handle with a row window take no hints, whatever is set.
+ * gnx_graph_set_gather_hints: hot_rows = -1 automatic, the default (on structures of at least 2^25 rows: the rows that fill 256 MiB,
+ * the Infinity Cache, at the width of the call; measured on R-MAT graphs: -5 % per propagation at 80M rows and C = 128 or 64, -1 to
+ * -6 % at 40M, a loss of 2-7 % at 20M rows and below, which is why smaller structures take hints only when asked), 0 off (frees the arrays; synchronises the device), n > 0 that many hot rows (built now).  Not
+ * capturable.  gnx_graph_gather_hints: the borrowed device array [nnz_coalesced] (NULL: none built, or the handle takes none) and
+ * the hot_rows it was built for, and the hot_rows the LAST SpMM launch over the handle gathered with (0: it took no hints -- a narrow
+ * width, a training or bf16 launch, hints off); any pointer may be NULL.  The training, GCNII and bf16 entries keep the plain columns.
+ * Nothing in the reference corresponds. */
+int gnx_graph_set_gather_hints(gnx_graph_t g, int64_t hot_rows, void *stream);
+int gnx_graph_gather_hints(gnx_graph_t g, const int32_t **d_hint_cols, int64_t *hot_rows, int64_t *last_launch_hot_rows);
 
 /* gnx_graph_enable_entry_dropout: builds, NOW, what the fused training entries (gnx_spmm_dropped, gnx_spmm_dropped_chained,
  * gnx_spmm_dropped_back) and the one-pass column sums of gnx_graph_colsum_streams need on a handle whose COO held duplicate entries
