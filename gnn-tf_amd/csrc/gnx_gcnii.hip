@@ -10,6 +10,9 @@
 //                      (hub rows, the other widths) and k_spectral_back the backward's first pass (gate, bias gradient)
 //                      EDGE: the layer and its backward under edge dropout (gnx_gcnii_step_dropped, gnx_gcnii_step_back_dropped, f32 rows) --
 //                      the gather loops make their weights from the counter RNG (edge_gather) instead of loading them
+//   k_spmm_gcn         the GCN layer (gcn.py:77-89) in one launch, gnx_gcn_step / gnx_gcn_step_dropped: k_spmm_gcnii's block without the
+//                      residual operand -- the same gather (gathered_row, which mixed_row mixes behind), a rectangular W [C_in, C_out <= C_in]
+//                      in LDS, the MFMA block with the bias in its epilogue, DROP / EDGE / ENTRIES as above; host path gcn_forward
 //   row passes         k_round_rows (f32 rows -> bf16), k_feature_dropout (the mask as a pass of its own: hub rows, the other widths, the
 //                      generic composition) and the backward's gate (k_feature_dropout_back, .._back_bf16); one launcher
 //                      (launch_row_pass) picks their vector width and grid
@@ -87,31 +90,34 @@ __device__ __forceinline__ uint32_t spectral_finish(const DropFuse &f, uint64_t 
 // v_mfma_f32_16x16x4_f32: the block the forward layer and its backward (k_spmm_gcnii_back) share.  The caller has put a wave
 // barrier between its writes of T and this call; on return the whole tile is written and visible to the wave.
 // BIAS (the spectral form): tile <- act(tile . Ms + bias[c]), the bias added to the accumulator value as it leaves the MFMA block.
-template <int NT, bool BIAS = false>
+// NTN (k_spmm_gcn): Ms holds 16 NTN <= C columns -- a rectangular transform -- and the result tile has that many, over the tile's
+// first columns; its bias has n_bias entries, the columns from there on add 0 (n_bias = 0: no bias at all, the pointer is not read).
+template <int NT, bool BIAS = false, int NTN = NT>
 __device__ __forceinline__ void tile_times_Ms(float *__restrict__ T, const float *__restrict__ Ms, int lane, int act,
-                                              const float *__restrict__ bias = nullptr) {
+                                              const float *__restrict__ bias = nullptr, int n_bias = 16 * NTN) {
     constexpr int C = 16 * NT, STRIDE = C + 4;
+    static_assert(NTN >= 1 && NTN <= NT, "the result tile overwrites the gathered one");
     // tile . M : A[m = lane & 15][k = 4 kk + (lane >> 4)] from the tile, B[k][n = lane & 15] from Ms
     const int cc = lane & 15, g = lane >> 4;
-    [[maybe_unused]] float bv[NT];
+    [[maybe_unused]] float bv[NTN];
     if constexpr (BIAS) {
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) bv[nt] = bias[16 * nt + cc];
+        for (int nt = 0; nt < NTN; ++nt) bv[nt] = 16 * nt + cc < n_bias ? bias[16 * nt + cc] : 0.f;
     }
-    f32x4 d[NT];
+    f32x4 d[NTN];
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) d[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int nt = 0; nt < NTN; ++nt) d[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
     for (int kk = 0; kk < C / 4; ++kk) {
         const float a = T[cc * STRIDE + 4 * kk + g];
         const float *__restrict__ mrow = Ms + (4 * kk + g) * STRIDE + cc;
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) d[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, mrow[16 * nt], d[nt], 0, 0, 0);
+        for (int nt = 0; nt < NTN; ++nt) d[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, mrow[16 * nt], d[nt], 0, 0, 0);
     }
     __builtin_amdgcn_wave_barrier();
     // D: lane (cc, g), register r -> row 4g + r, column 16 nt + cc; back through the tile so that rows leave as whole float4 rows
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
+    for (int nt = 0; nt < NTN; ++nt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             float v = d[nt][r];
@@ -164,12 +170,12 @@ __device__ __forceinline__ void edge_gather(const SpmmArgs &p, const float *__re
     }
 }
 
-// One mixed row of the fused layer, columns c .. c + 3 of row `row` (entries beg .. end) into acc (zeros on entry): the gather loop, the
-// entry order and the mix, written once -- the forward (k_spmm_gcnii) and the weight gradient that makes T again (k_gcnii_wgrad) run this
-// code, so a row made again has the bits of the row the forward stored.  U entries in flight per lane.
-// EDGE (G = the lanes of a row): the entry's weight is made, not loaded (edge_gather above); the mix is the same code.
+// One aggregated row sum_j A[row, j] X[j, c .. c + 3] (entries beg .. end) into acc (zeros on entry): the gather loop and the entry
+// order, written once -- U entries in flight per lane and one fmaf chain.  The GCNII kernels mix the sum behind it (mixed_row), the GCN
+// layer (k_spmm_gcn) takes it as it is.
+// EDGE (G = the lanes of a row): the entry's weight is made, not loaded (edge_gather above).
 template <typename R, int U, bool EDGE = false, bool ENTRIES = false, int G = 0>
-__device__ __forceinline__ void mixed_row(const typename R::Args &p, int64_t row, int64_t beg, int64_t end, int c, float (&acc)[4]) {
+__device__ __forceinline__ void gathered_row(const typename R::Args &p, int64_t row, int64_t beg, int64_t end, int c, float (&acc)[4]) {
     const typename R::Elem *__restrict__ Xc = R::X(p) + c;
     if constexpr (EDGE) {
         edge_gather<ENTRIES, G, U>(p, Xc, row, beg, end, acc);
@@ -195,6 +201,14 @@ __device__ __forceinline__ void mixed_row(const typename R::Args &p, int64_t row
                 for (int v = 0; v < 4; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
         }
     }
+}
+
+// One mixed row of the fused layer, columns c .. c + 3 of row `row` (entries beg .. end) into acc (zeros on entry): the gather
+// (gathered_row) and the mix, written once -- the forward (k_spmm_gcnii) and the weight gradient that makes T again (k_gcnii_wgrad) run
+// this code, so a row made again has the bits of the row the forward stored.
+template <typename R, int U, bool EDGE = false, bool ENTRIES = false, int G = 0>
+__device__ __forceinline__ void mixed_row(const typename R::Args &p, int64_t row, int64_t beg, int64_t end, int c, float (&acc)[4]) {
+    gathered_row<R, U, EDGE, ENTRIES, G>(p, row, beg, end, c, acc);
     float h0[4];
     vload<4>(h0, p.H0 + row * p.ldh0 + c);
 #pragma unroll
@@ -297,6 +311,80 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args 
             drop_values<4>(fd, drop_stream(fd), rows[ps], c, o);
         }
         R::template store<4>(p, rows[ps] * p.ldo, c, o);
+    }
+}
+
+// ---- GCN layer: SpMM + the C_in x C_out transform on the matrix cores + bias + activation, one launch (gnx_gcn_step) --------------------
+//   out[i,:] = drop( act( (sum_j A[i,j] X[j,:]) . W + bias ) )      (gcn.py:88-89)
+// k_spmm_gcnii's shape without the residual operand: a 512-thread block, a 16-row tile per wave in degree-binned order, 4 NTI lanes of
+// float4 per row, the gather of gathered_row (the loop the GCNII kernels mix behind) -- C_in = 16 NTI.  W [C_in, C_out], 1 <= C_out <= C_in,
+// sits in LDS with row stride C_in + 4, its columns from C_out to 16 NTO zero-filled (NTO = ceil(C_out / 16): the padding exists in LDS
+// alone); the product is tile_times_Ms with NTN = NTO, the bias (null: none) joins the accumulator as it leaves the MFMA block, before the
+// activation, and the result tile overwrites the gathered one (C_out <= C_in: no second tile; the LDS is k_spmm_gcnii's).  `agg` (null: not
+// kept) gets the aggregated rows, [n, C_in] contiguous, from the lanes that made them: training keeps them for dW = agg^T G', and the
+// transform never reads them back.  A lane stores its columns below C_out: a whole float4 where `vec_out` says the row starts of out allow
+// it (ldo % 4 == 0 and a 16-byte aligned base) and the four columns exist, scalars otherwise -- nothing is written past column C_out - 1 of
+// any row.  DROP: the mask of the finished rows (`feat`, keyed by row and column) in the store loop, as in k_spmm_gcnii; agg stays
+// undropped.  EDGE / ENTRIES: the weights are made from p.fuse in the gather loop (edge_gather), as in k_spmm_gcnii.  Rows longer than
+// p.long_row are left to the long-row kernels + the dense kernel.  f32 rows only.
+template <typename R, int NTI, int NTO, int U, int WPB, bool DROP = false, bool EDGE = false, bool ENTRIES = false>
+__global__ __launch_bounds__(64 * WPB) void k_spmm_gcn(const typename R::Args p, const float *__restrict__ W, int64_t ldw, int C_out,
+                                                       const float *__restrict__ bias, float *__restrict__ agg, bool vec_out, const DropFuse feat) {
+    static_assert(!R::BF16, "the GCN layer exists over f32 rows");
+    static_assert(NTO >= 1 && NTO <= NTI, "C_out <= C_in: the result tile overwrites the gathered one");
+    constexpr int C = 16 * NTI, CO = 16 * NTO, G = 4 * NTI, RPP = 64 / G, PASSES = 16 / RPP, STRIDE = C + 4;
+    __shared__ float Ws[C * STRIDE];
+    __shared__ float Ts[WPB][16 * STRIDE];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    for (int idx = threadIdx.x; idx < C * CO; idx += 64 * WPB) {
+        const int k = idx / CO, n = idx % CO;
+        Ws[k * STRIDE + n] = n < C_out ? W[(int64_t)k * ldw + n] : 0.f;
+    }
+    __syncthreads();
+    const int64_t tile = (int64_t)blockIdx.x * WPB + wave;
+    if (tile * 16 >= p.n_rows) return;
+    float *__restrict__ T = Ts[wave];
+    const int sub = lane % G, c = sub * 4;
+    int64_t rows[PASSES];
+    bool live[PASSES];
+#pragma unroll
+    for (int ps = 0; ps < PASSES; ++ps) {
+        const int rr = ps * RPP + lane / G;
+        const int64_t slot = tile * 16 + rr;
+        int64_t row = -1;
+        int64_t beg = 0, end = 0;
+        if (slot < p.n_rows) {
+            row = p.row_order ? (int64_t)p.row_order[slot] : slot;
+            beg = p.rowptr[row]; end = p.rowptr[row + 1];
+        }
+        live[ps] = row >= 0 && end - beg <= p.long_row;
+        rows[ps] = row;
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        if (live[ps]) {
+            gathered_row<R, U, EDGE, ENTRIES, G>(p, row, beg, end, c, acc);
+            if (agg) vstore<4>(agg + row * (int64_t)C + c, acc);
+        }
+        vstore<4>(T + rr * STRIDE + c, acc);
+    }
+    __builtin_amdgcn_wave_barrier();
+    tile_times_Ms<NTI, true, NTO>(T, Ws, lane, p.act, bias, bias ? C_out : 0);
+    if (c >= C_out) return;
+    const bool whole = vec_out && c + 4 <= C_out;
+#pragma unroll
+    for (int ps = 0; ps < PASSES; ++ps) {
+        if (!live[ps]) continue;
+        const int rr = ps * RPP + lane / G;
+        float o[4];
+        vload<4>(o, T + rr * STRIDE + c);
+        if constexpr (DROP) drop_values<4>(feat, drop_stream(feat), rows[ps], c, o);
+        float *__restrict__ dst = p.out + rows[ps] * p.ldo + c;
+        if (whole) vstore<4>(dst, o);
+        else {
+#pragma unroll
+            for (int v = 0; v < 4; ++v)
+                if (c + v < C_out) dst[v] = o[v];
+        }
     }
 }
 
@@ -1074,9 +1162,141 @@ int gcnii_wgrad(const char *fn, const char *reports, gnx_graph *g, const float *
     return GNX_OK;
 }
 
+// ---- the GCN layer's host path (gnx_gcn_step, gnx_gcn_step_dropped) -----------------------------------------------------------------------
+// what gnx_graph_last_kernel reports: [C_in = 16, 32, 64][mask << 1 | edge dropout][hub rows ran]; the composed form [..][..] alone
+#define GNX_GCN_NAMES2(c, tail) {"k_spmm_gcn<" c ">" tail, "k_spmm_gcn<" c ">" tail "+long"}
+#define GNX_GCN_NAMES(c) {GNX_GCN_NAMES2(c, ""), GNX_GCN_NAMES2(c, "_edrop"), GNX_GCN_NAMES2(c, "_drop"), GNX_GCN_NAMES2(c, "_edrop_drop")}
+const char *const kGcnFused[3][4][2] = {GNX_GCN_NAMES("16"), GNX_GCN_NAMES("32"), GNX_GCN_NAMES("64")};
+const char *const kGcnComposed[4] = {"spmm+dense_mfma_gcn", "spmm+dense_mfma_gcn_edrop", "spmm+dense_mfma_gcn_drop", "spmm+dense_mfma_gcn_edrop_drop"};
+#undef GNX_GCN_NAMES
+#undef GNX_GCN_NAMES2
+
+struct GcnOut { float *out; int64_t ldo; float *agg, *work; };      // the result, and where aggregated rows are kept / may pass through memory
+
+// out = drop(act((A . X) . W + bias)), A from d_vals or made from `edge`; `fd` the mask of the finished rows or null.  The fused launch
+// takes C_in = 16, 32 or 64 with C_out <= C_in over 16-byte aligned rows; everything else runs the SpMM, the dense kernel and the mask
+// pass inside this call, as gcnii_forward treats its other widths.  Nothing is launched before the last check has passed.
+int gcn_forward(const char *fn, gnx_graph *g, const float *d_vals, const EdgeDrop *edge, const float *d_X, int64_t ldx, int64_t C_in,
+                const float *d_W, int64_t ldw, int64_t C_out, const float *d_bias, int act, const DropFuse *fd, const GcnOut &o, void *stream) {
+    GNX_CHECK_ARG(g != nullptr, "%s: NULL handle", fn);
+    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU, "%s: invalid activation %d", fn, act);
+    GNX_CHECK_ARG(C_in >= 1 && C_in <= (1 << 20) && C_out >= 1 && C_out <= (1 << 20), "%s: widths %lld -> %lld not in [1, 2^20]", fn,
+                  (long long)C_in, (long long)C_out);
+    GNX_CHECK_ARG(d_X != nullptr && d_W != nullptr && o.out != nullptr, "%s: NULL X / W / out", fn);
+    GNX_CHECK_ARG(ldx >= C_in, "%s: ldx %lld < C_in %lld", fn, (long long)ldx, (long long)C_in);
+    GNX_CHECK_ARG(ldw >= C_out, "%s: ldw %lld < C_out %lld", fn, (long long)ldw, (long long)C_out);
+    GNX_CHECK_ARG(o.ldo >= C_out, "%s: ldo %lld < C_out %lld", fn, (long long)o.ldo, (long long)C_out);
+    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "%s: needs a square graph", fn);
+    const void *D = edge ? edge->D : nullptr;
+    auto input = [&](const void *b) { return b == d_X || b == d_W || (d_bias && b == d_bias) || (d_vals && b == d_vals) || (D && b == D); };
+    GNX_CHECK_ARG(!input(o.out), "%s: out must not alias an input (X / W / bias / the values)", fn);
+    GNX_CHECK_ARG(o.agg == nullptr || (!input(o.agg) && o.agg != o.out), "%s: d_agg must be a buffer of its own", fn);
+    GNX_CHECK_ARG(o.work == nullptr || (!input(o.work) && o.work != o.out && o.work != o.agg), "%s: d_work must be a buffer of its own", fn);
+    if (edge) {
+        const int rc = admit_edge_drop(fn, g, *edge);
+        if (rc != GNX_OK) return rc;
+    }
+    const Csr &m = g->a;
+    const bool fusable = fused_width(C_in) && C_out <= C_in && ldx % 4 == 0 && aligned(d_X, 16) && aligned(o.agg, 16) && aligned(o.work, 16);
+    float *T = o.agg ? o.agg : o.work;      // where rows [n, C_in] go through memory: every row of the composed form, the hub rows of the fused one
+    GNX_CHECK_ARG(fusable || T != nullptr, "%s: needs d_agg or d_work [n, C_in] f32 (%s: the SpMM and the transform run as two launches)", fn,
+                  !fused_width(C_in) ? "C_in is not 16, 32 or 64" : C_out > C_in ? "C_out > C_in" : "misaligned rows");
+    GNX_CHECK_ARG(!fusable || m.n_long == 0 || T != nullptr,
+                  "%s: needs d_agg or d_work [n, C_in] f32 (the graph has hub rows: their aggregated rows go through memory)", fn);
+    hipStream_t s = (hipStream_t)stream;
+    const int mode = (fd ? 2 : 0) | (edge ? 1 : 0);
+    // aggregated rows at T (the n listed; null: rows 0 .. n) -> act(T . W + bias) of those rows alone -> their mask, in place
+    auto transform_rows = [&](const int32_t *rows, int64_t n) -> int {
+        const int err = dense_rows(T, C_in, n, C_in, d_W, ldw, C_out, d_bias, act, rows, rows, o.out, o.ldo, s);
+        if (err != GNX_OK) return err;
+        if (fd) launch_feature_dropout(o.out, o.ldo, rows, n, C_out, *fd, o.out, o.ldo, s);
+        GNX_HIP(hipGetLastError());
+        return GNX_OK;
+    };
+    if (!fusable) {
+        const int rc = edge ? gnx_spmm_dropped(g, edge->D, edge->p, edge->seed, edge->stream, 0, d_X, ldx, C_in, nullptr, 0, 1.f, 0.f, GNX_ACT_NONE, T,
+                                               C_in, stream)
+                            : gnx_spmm(g, d_vals, nullptr, d_X, ldx, C_in, nullptr, 0, 1.f, 0.f, GNX_ACT_NONE, T, C_in, stream);
+        if (rc != GNX_OK) return rc;
+        g->last_kernel = kGcnComposed[mode];
+        return transform_rows(nullptr, m.n_rows);
+    }
+    if (m.n_rows == 0) return GNX_OK;
+    if (m.n_long > 0) {   // (before the first launch: under capture a slab that would have to grow refuses the whole call)
+        const int rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)C_in * sizeof(float), s);
+        if (rc != GNX_OK) return rc;
+    }
+    SpmmArgs p{};
+    if (edge) {      // p.fuse is the edge dropout's; the mask travels beside it
+        set_values(g, false, p);
+        set_drop_fuse(g, edge->p, edge->seed, edge->stream, edge->D, 0, 0, p);
+    } else {
+        p.vals = d_vals ? d_vals : g->raw_vals;
+    }
+    set_operands<F32Rows>(p, d_X, ldx, nullptr, 0, 1.f, 0.f, act, o.out, 0, o.ldo, C_in);
+    bind_fused(m, p);
+    const bool vec_out = o.ldo % 4 == 0 && aligned(o.out, 16);
+    const DropFuse feat = fd ? *fd : DropFuse{};
+    const int nto = (int)blocks_for(C_out, 16);
+    with_tile_width(C_in, m.n_rows, [&](auto NTI, dim3 grid) {
+        auto launch = [&](auto NTO, auto DROP, auto ENTRIES) {
+            if constexpr (NTO() <= NTI()) {
+                if (edge) hipLaunchKernelGGL((k_spmm_gcn<F32Rows, NTI(), NTO(), 4, 8, DROP(), true, ENTRIES()>), grid, dim3(512), 0, s, p, d_W, ldw,
+                                             (int)C_out, d_bias, o.agg, vec_out, feat);
+                else if constexpr (!ENTRIES()) hipLaunchKernelGGL((k_spmm_gcn<F32Rows, NTI(), NTO(), 4, 8, DROP()>), grid, dim3(512), 0, s, p, d_W, ldw,
+                                                                  (int)C_out, d_bias, o.agg, vec_out, feat);
+            }
+        };
+        auto with_mode = [&](auto NTO) {
+            const bool entries = edge && p.fuse.mult;
+            if (fd) { if (entries) launch(NTO, std::true_type{}, std::true_type{}); else launch(NTO, std::true_type{}, std::false_type{}); }
+            else    { if (entries) launch(NTO, std::false_type{}, std::true_type{}); else launch(NTO, std::false_type{}, std::false_type{}); }
+        };
+        if (nto == 1)      with_mode(IntC<1>{});
+        else if (nto == 2) with_mode(IntC<2>{});
+        else if (nto == 3) with_mode(IntC<3>{});
+        else               with_mode(IntC<4>{});
+    });
+    g->last_kernel = kGcnFused[C_in == 16 ? 0 : C_in == 32 ? 1 : 2][mode][m.n_long > 0];
+    if (m.n_long == 0) {
+        GNX_HIP(hipGetLastError());
+        return GNX_OK;
+    }
+    // hub rows: chunked partial sums -> aggregated rows at their row ids of T -> the transform and the mask of those rows alone
+    p.partial = g->partial;
+    p.act = GNX_ACT_NONE;
+    p.ldo = C_in;
+    launch_hub_rows<F32Rows>(p, d_X, T, s, edge != nullptr);
+    return transform_rows(m.long_rows, m.n_long);
+}
+
 }  // namespace
 
 extern "C" {
+
+int gnx_gcn_step(gnx_graph_t g, const float *d_vals, const float *d_X, int64_t ldx, int64_t C_in, const float *d_W, int64_t ldw, int64_t C_out,
+                 const float *d_bias, int act, double dropout_p, uint64_t seed, uint64_t stream_id, float *d_out, int64_t ldo, float *d_agg,
+                 float *d_work, void *stream) {
+    const char *fn = "gnx_gcn_step";
+    DropFuse fd{};
+    const int rc = make_feat_drop(fn, g, dropout_p, seed, stream_id, fd);
+    if (rc != GNX_OK) return rc;
+    return gcn_forward(fn, g, d_vals, nullptr, d_X, ldx, C_in, d_W, ldw, C_out, d_bias, act, dropout_p != 0.0 ? &fd : nullptr,
+                       GcnOut{d_out, ldo, d_agg, d_work}, stream);
+}
+
+// (dropout_p == 0: no feature mask -- nothing is hashed for the finished rows; the edge dropout acts at any rate in [0, 1))
+int gnx_gcn_step_dropped(gnx_graph_t g, const float *d_D, float edge_p, uint64_t edge_seed, uint64_t edge_stream, const float *d_X, int64_t ldx,
+                         int64_t C_in, const float *d_W, int64_t ldw, int64_t C_out, const float *d_bias, int act, double dropout_p, uint64_t seed,
+                         uint64_t stream_id, float *d_out, int64_t ldo, float *d_agg, float *d_work, void *stream) {
+    const char *fn = "gnx_gcn_step_dropped";
+    DropFuse fd{};
+    const int rc = make_feat_drop(fn, g, dropout_p, seed, stream_id, fd);
+    if (rc != GNX_OK) return rc;
+    const EdgeDrop edge{d_D, edge_p, edge_seed, edge_stream};
+    return gcn_forward(fn, g, nullptr, &edge, d_X, ldx, C_in, d_W, ldw, C_out, d_bias, act, dropout_p != 0.0 ? &fd : nullptr,
+                       GcnOut{d_out, ldo, d_agg, d_work}, stream);
+}
 
 int gnx_gcnii_step(gnx_graph_t g, const float *d_vals, const float *d_H, const float *d_H0, float a, int64_t C, const float *d_M,
                    int64_t ldm, int act, float *d_out, float *d_mixed, void *stream) {

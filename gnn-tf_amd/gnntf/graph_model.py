@@ -52,7 +52,7 @@ class GNN(Trainable):
     def __init__(self, graph, features, preprocessor: Layer = None, reorder=None, inference_dtype=torch.float32,
                  training_dtype=torch.float32, train_gather_order="auto", gcnii_backward="composed", feature_dropout="torch",
                  gcnii_training_dtype=torch.float32, gcnii_weight_gradient="stored", gcnii_spectral="composed",
-                 gcnii_edge_dropout="composed"):
+                 gcnii_edge_dropout="composed", gcn_layer="composed"):
         """``reorder`` (opt-in, not in the reference): store the graph and the feature rows with the vertices relabelled; every
         [N, .] tensor inside the model then lives in that order, and the model's OUTPUT is put back into the caller's order, so
         tasks, labels and node ids are unaffected.  Results agree with the unordered model to float32 rounding.
@@ -163,7 +163,21 @@ class GNN(Trainable):
         and against ``"composed"`` agrees to float32 rounding (the transform runs in the fused launch's order).  Eval mode, constant
         adjacencies, GCNIISpectralPreservingLayer, other activations, ``gcnii_weight_gradient="recomputed"``,
         ``gcnii_training_dtype=torch.bfloat16``, add_eye, graphs that cannot fuse their dropout, CPU tensors and the vertex-partitioned
-        path keep today's path whatever it says (measurement: profiles/NOTES.md "Fused GCNII layer under edge dropout")."""
+        path keep today's path whatever it says (measurement: profiles/NOTES.md "Fused GCNII layer under edge dropout").
+        ``gcn_layer`` (not in the reference): ``"composed"`` (the default: today's calls and bits) or ``"fused"`` (sparse.gcn_step).
+        ``"fused"``: a GCNLayer (the class itself, no ``transform_first``, relu or the identity as activation, float32 device rows of
+        width 16, 32 or 64, at most as many outputs, no add_eye, not a bf16 ``inference_dtype`` forward) runs
+        act((A . X) . W + b) as ONE launch (gnx_gcn_step) instead of the SpMM and the dense kernel with A . X written and read back
+        between them, in eval mode and in training mode alike; in training mode over a DroppedAdjacency the launch makes the weights
+        itself (gnx_gcn_step_dropped), and with ``feature_dropout="fused"`` and 0 < ``dropout`` < 1 the mask leaves the same launch
+        (otherwise torch's dropout follows as today).  The layer draws its mask streams in today's order and number: the adjacency's,
+        then the mask's.  In ``GCN(latent_dims=[64])`` this is the 64 -> num_classes layer (the first layer gathers at the feature
+        width); in ``[64, 64, 64]`` every layer but the first.  The backward is composed from today's kernels.  The result agrees with
+        the composed one to float32 rounding.  GCNSpectralPreservingLayer and other subclasses, ``transform_first``, other
+        activations, other widths, add_eye, CPU tensors and the vertex-partitioned path keep today's path and bits whatever it says
+        (measurement: profiles/NOTES.md "Fused GCN layer")."""
+        if gcn_layer not in sparse.GCN_LAYERS:
+            raise Exception("GNN: gcn_layer must be one of " + ", ".join(repr(f) for f in sparse.GCN_LAYERS))
         if gcnii_edge_dropout not in sparse.GCNII_EDGE_DROPOUTS:
             raise Exception("GNN: gcnii_edge_dropout must be one of " + ", ".join(repr(e) for e in sparse.GCNII_EDGE_DROPOUTS))
         if gcnii_spectral not in sparse.GCNII_SPECTRALS:
@@ -192,6 +206,7 @@ class GNN(Trainable):
         self.feature_dropout = feature_dropout
         self.gcnii_spectral = gcnii_spectral
         self.gcnii_edge_dropout = gcnii_edge_dropout
+        self.gcn_layer = gcn_layer
         self._order = self._newid = None
         self.reorder_used, self.locality_share = None, None
         if isinstance(graph, sparse.DeviceGraph):
@@ -447,8 +462,24 @@ class GCNLayer(Layer):
         self.transform_first = bool(transform_first) and outputs < gcn.top_shape()[1]
         return (gcn.top_shape()[0], outputs)
 
+    def _fused_gcn(self, gcn, features, adjacency) -> bool:
+        """Whether GNN(gcn_layer="fused") applies to this forward (no tensor is read, no mask stream is drawn)."""
+        return (getattr(gcn, "gcn_layer", "composed") == "fused" and type(self) is GCNLayer and not self.transform_first
+                and (self.activation is relu or self.activation is linear)
+                and isinstance(features, torch.Tensor) and features.is_cuda and features.dtype == torch.float32
+                and features.shape[1] in sparse.GCN_FUSED_WIDTHS and self.W.shape[1] <= features.shape[1]
+                and adjacency.diag is None and _eval_storage(gcn) is not torch.bfloat16)
+
     def __forward__(self, gcn, features):
         adjacency = gcn.get_adjacency(self.graph_dropout)
+        if self._fused_gcn(gcn, features, adjacency):
+            # GNN(gcn_layer="fused"): the aggregation and the transform in one launch; with feature_dropout="fused" the mask too
+            triple = None
+            if getattr(gcn, "feature_dropout", "torch") == "fused" and gcn.is_training() and 0 < self.dropout < 1:
+                triple = (self.dropout,) + tuple(gcn._next_mask_stream())
+            out = sparse.gcn_step(adjacency, features, self.W, self.b if isinstance(self.b, torch.Tensor) else None,
+                                  relu=self.activation is relu, dropout=triple, edge_dropout="fused")
+            return out if triple is not None else gcn.dropout(out, self.dropout)
         if self.transform_first:
             bias = self.b if isinstance(self.b, torch.Tensor) else None
             projected = affine(features, self.W, 0)

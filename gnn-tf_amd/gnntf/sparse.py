@@ -1436,6 +1436,116 @@ def _gcnii_step_dropped(adj, H, H0, a, M, relu, backward, dropout, recompute=Fal
     return _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=False, dropout=dropout)[0]
 
 
+GCN_LAYERS = ("composed", "fused")
+GCN_FUSED_WIDTHS = (16, 32, 64)       # C_in of the one-launch form of gnx_gcn_step; its C_out is any width up to C_in
+
+
+def _gcn_launch(adj: Adjacency, X, W, bias, relu, keep_agg, dropout=None, fused_edge=False):
+    """gnx_gcn_step, or with ``fused_edge`` (``adj`` is a DroppedAdjacency) gnx_gcn_step_dropped; returns (out, agg or None).
+    ``keep_agg`` (training): the launch also writes the aggregated rows A . X, which dW needs.  Without it the rows that have to pass
+    through memory -- hub rows, and every row of the widths the one launch does not take -- go through a scratch buffer.
+    ``dropout`` = the checked (p, seed, stream) or None."""
+    nat.require_cuda(X, W, bias)
+    X, W = _as_f32_rows(X), _as_f32_rows(W)
+    g = adj.graph
+    if not fused_edge and adj.vals is None and adj.vals_t is not None:
+        raise Exception("gcn_step: this adjacency only holds transposed-order values")
+    _same_device(g, X, W, bias, adj.vals if not fused_edge else adj.D)
+    n, C_in = X.shape
+    C_out = W.shape[1]
+    if g.n_rows != g.n_cols or n != g.n_rows or W.shape[0] != C_in or C_in < 1 or C_out < 1:
+        raise Exception("gcn_step: shape mismatch")
+    b = None if bias is None else bias.to(torch.float32).reshape(-1).contiguous()
+    if b is not None and b.numel() != C_out:
+        raise Exception("gcn_step: bias width mismatch")
+    one_launch = C_in in GCN_FUSED_WIDTHS and C_out <= C_in and X.stride(0) % 4 == 0 and X.data_ptr() % 16 == 0
+    out = torch.empty((n, C_out), dtype=torch.float32, device=X.device)
+    rows = torch.empty((n, C_in), dtype=torch.float32, device=X.device) if keep_agg or not one_launch or g.n_hub_rows > 0 else None
+    agg, work = (rows, None) if keep_agg else (None, rows)
+    p, seed, stream = dropout if dropout is not None else (0.0, 0, 0)
+    layer = (nat.ptr(X), X.stride(0), C_in, nat.ptr(W), W.stride(0), C_out, nat.ptr(b), nat.ACT_RELU if relu else nat.ACT_NONE, p, seed, stream,
+             nat.ptr(out), out.stride(0), nat.ptr(agg), nat.ptr(work))
+    with nat.on_device(X.device):
+        if fused_edge:
+            nat.check(nat.lib().gnx_gcn_step_dropped(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, *layer, nat.current_stream()))
+        else:
+            nat.check(nat.lib().gnx_gcn_step(g.handle, nat.ptr(adj.vals), *layer, nat.current_stream()))
+    return out, agg
+
+
+class _GCNStep(torch.autograd.Function):
+    """out = drop(act((A . X) . W + b)) as ONE launch that also leaves agg = A . X for the backward (gcn.py:88-89 under
+    tf.GradientTape); (agg, W, out) is what is saved.  backward, composed from what exists: g' = g * (out > 0), or with a fused mask
+    one pass (gnx_feature_dropout_back); dW = agg^T g' (gnx_dense_wgrad); db = column sums of g'; dX = A^T (g' W^T) -- gnx_dense, then
+    the transposed SpMM, the dropped one under ``fused_edge`` (``adj`` stays a DroppedAdjacency: no value array)."""
+
+    @staticmethod
+    def forward(ctx, X, W, bias, adj, relu, dropout, fused_edge):
+        ctx.adj, ctx.relu, ctx.dropout = adj, relu, dropout
+        ctx.bias_shape = None if bias is None else tuple(bias.shape)
+        out, agg = _gcn_launch(adj, X, W, bias, relu, keep_agg=True, dropout=dropout, fused_edge=fused_edge)
+        ctx.save_for_backward(agg, W, out if relu or dropout is not None else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        agg, W, out = ctx.saved_tensors
+        if ctx.dropout is not None:
+            g = _feature_dropout_back(ctx.adj.graph, g, out, *ctx.dropout, relu=ctx.relu)
+        else:
+            g = (_relu_mask(g, out) if ctx.relu else g).contiguous()
+        gW = _dense_wgrad(agg, g) if ctx.needs_input_grad[1] else None
+        gb = g.sum(dim=0).reshape(ctx.bias_shape) if ctx.bias_shape is not None and ctx.needs_input_grad[2] else None
+        gX = None
+        if ctx.needs_input_grad[0]:
+            gT = _dense_launch(g, W.t().contiguous(), None, False)
+            del g                                           # (the gated gradient is done with: the transposed SpMM runs without it)
+            gX = _launch(ctx.adj, gT, None, 1.0, 0.0, nat.ACT_NONE, transposed=True)
+        return gX, gW, gb, None, None, None, None
+
+
+def _gcn_composed(adj, X, W, bias, relu, dropout):
+    """The layer as today's ops: spmm, then the dense kernel with bias and relu (CPU tensors: torch), then the mask as a pass of its own."""
+    agg = spmm(adj, X)
+    if agg.is_cuda:
+        out = dense(agg, W, bias, relu)
+    else:
+        out = torch.matmul(agg, W) + (bias if bias is not None else 0)
+        out = torch.relu(out) if relu else out
+    if dropout is None or float(dropout[0]) == 0:
+        return out
+    if out.is_cuda:
+        return feature_dropout(adj.graph, out, *dropout)
+    return torch.nn.functional.dropout(out, p=float(dropout[0]), training=True)
+
+
+def gcn_step(adj: Adjacency, X: torch.Tensor, W: torch.Tensor, bias=None, relu=True, dropout=None, edge_dropout="composed") -> torch.Tensor:
+    """GCNLayer (gcn.py:77-89) as one launch (gnx_gcn_step; opt-in, GNN(gcn_layer="fused")): drop(act((A . X) . W + bias)) with
+    ``X`` [n, C_in], ``W`` [C_in, C_out] and ``bias`` [C_out] / [1, C_out] or None.  For C_in in {16, 32, 64} and C_out <= C_in the
+    aggregated rows stay in LDS and meet W on the matrix cores: A . X, which ``spmm`` + ``dense`` write and read back, never reaches
+    memory without autograd.  Other widths run the SpMM, the dense kernel and the mask pass inside the same call.
+    ``dropout`` = ``(p, seed, stream)`` or None: the mask of ``feature_dropout`` (the counter RNG of the edge dropout, not torch's
+    generator) over the finished rows, from the same launch.
+    Under autograd it is one node that saves (A . X, W, out) -- the launch writes A . X once, for dW -- and returns the gradients of X,
+    W and bias from today's kernels: the relu gate (or gnx_feature_dropout_back), gnx_dense_wgrad, the column sums, gnx_dense and
+    the transposed SpMM.  (The fused backward, dX = (A^T G') W^T gathered at the output width, is the follow-up.)
+    ``edge_dropout``: ``"composed"`` (the default) or ``"fused"``: with a DroppedAdjacency the launch makes every entry's weight in
+    its gather loop (gnx_gcn_step_dropped) -- out and A . X bit for bit those over the materialised adjacency
+    ``normalize(graph, "symmetric", "none", p, seed, stream)`` -- and the backward's transposed SpMM is the dropped one.
+    CPU tensors, an adjacency with a diagonal and a DroppedAdjacency without ``edge_dropout="fused"`` run ``spmm`` + ``dense``:
+    today's calls and bits."""
+    fused_edge = _edge_dropout("gcn_step", edge_dropout)
+    tensors = (X, W) if bias is None else (X, W, bias)
+    if (not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors) or adj.diag is not None
+            or (isinstance(adj, DroppedAdjacency) and not fused_edge)):
+        return _gcn_composed(adj, X, W, bias, bool(relu), dropout)
+    dropout = _dropout_triple(dropout, "gcn_step")
+    fused_edge = fused_edge and isinstance(adj, DroppedAdjacency)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        return _GCNStep.apply(X, W, bias, adj, bool(relu), dropout, fused_edge)
+    return _gcn_launch(adj, X, W, bias, bool(relu), keep_agg=False, dropout=dropout, fused_edge=fused_edge)[0]
+
+
 GCNII_SPECTRALS = ("composed", "fused")
 
 

@@ -667,6 +667,49 @@ int gnx_gcnii_step_back_dropped(gnx_graph_t g, const float *d_D, float edge_p, u
                                 const float *d_G, float a, int64_t C, const float *d_Mt, int64_t ldmt, float *d_dH,
                                 const float *d_S_in, float s_alpha, float *d_S_out, float *d_work, void *stream);
 
+/* ---- the GCN layer in one launch (opt-in; added within ABI 0.9 -- probe for the symbols) -------------------------------
+ * GCNLayer.__forward__ (gcn.py:88-89): out = drop(act((A . X) . W + bias)) -- the aggregation at the input width and the transform,
+ * which gnx_spmm + gnx_dense run as two launches with the [n, C_in] matrix A . X written and read back between them.  X [n, C_in]
+ * (ldx), W [C_in, C_out] (ldw), bias [C_out] or NULL, out [n, C_out] (ldo), all f32; act GNX_ACT_NONE or GNX_ACT_RELU.
+ *
+ * gnx_gcn_step: d_vals as in gnx_spmm (NULL: the handle's raw values).  For C_in in {16, 32, 64}, 1 <= C_out <= C_in, ldx % 4 == 0 and
+ * 16-byte aligned X / d_agg / d_work it is ONE launch: a wave gathers a 16-row tile into LDS (entries in ascending order, four in
+ * flight, one fmaf chain: the loop of gnx_gcnii_step without the mix), multiplies it by W -- in LDS, its columns padded with zeros to
+ * a multiple of 16 there and nowhere else -- on v_mfma_f32_16x16x4_f32, adds the bias to the accumulator as it leaves the matrix
+ * cores, applies the activation and stores the columns below C_out: whole 16-byte pieces where ldo % 4 == 0 and out is 16-byte
+ * aligned, single values otherwise (C_out = 7 with ldo = 7 is fine); nothing is written past column C_out - 1 of any row.
+ * Rounding points: each aggregated value is one fmaf chain over the row's entries; each output the f32 MFMA sum over k in
+ * ascending order, then + bias, then the activation, then the mask.
+ * d_agg [n, C_in] f32 contiguous or NULL: receives the aggregated rows A . X, written once by the lanes that made them and never
+ * read back for the transform (training keeps them for dW = agg^T G'); it does not change a bit of out.
+ * (dropout_p, seed, stream_id): the feature mask of gnx_gcnii_step_drop over the finished rows -- element (i, c) is kept iff
+ * hash_u24(seed, stream_id + counter, i, c, 0) >= int(dropout_p * 2^24), kept values times the f32 1 / (1 - dropout_p), dropped ones
+ * +0; dropout_p == 0 hashes nothing.  d_agg stays undropped.
+ * Rows longer than the handle's long-row threshold (hub rows) take the long-row kernels of gnx_spmm, then the dense kernel on those
+ * rows alone, then the mask pass on them; their aggregated rows go through d_agg, else through d_work (f32, at least n * C_in).
+ * Every other case -- C_in outside {16, 32, 64}, C_out > C_in, misaligned rows -- runs gnx_spmm, the dense kernel and the mask pass
+ * inside the call, through d_agg, else d_work.  Where a place for those rows is needed and both are NULL the call is refused, and
+ * the message says which case needs it.
+ * Checked before anything is launched (a refused call writes nothing): NULL handle / X / W / out, the activation, the rate in
+ * [0, 1), ldx >= C_in, ldw >= C_out, ldo >= C_out, a square graph; out, d_agg and d_work are buffers of their own (none aliases
+ * X, W, bias, the values, or another of the three).  Stream-ordered; under capture the long-row slab must already cover C_in
+ * (gnx_graph_reserve), as for gnx_spmm.  No float atomics.
+ * Reports "k_spmm_gcn<C_in>" (+ "_edrop" under edge dropout, + "_drop" with a mask, + "+long" when hub rows ran), the composed
+ * form "spmm+dense_mfma_gcn" with the same suffixes.
+ *
+ * gnx_gcn_step_dropped: the same layer under the edge dropout of gnx_spmm_dropped -- (d_D, edge_p, edge_seed, edge_stream) as in
+ * gnx_gcnii_step_dropped: every entry's weight is made in the gather loop, bit for bit the value gnx_graph_normalize(symmetric, no
+ * add_eye, edge_p, edge_seed, edge_stream) stores, so out and d_agg have the bits of gnx_gcn_step over the materialised values (skip
+ * semantics and the finite-features precondition of gnx_spmm_dropped).  Admission as gnx_gcnii_step_dropped: a square stand-alone
+ * graph; a handle with duplicate COO entries needs gnx_graph_enable_entry_dropout. */
+int gnx_gcn_step(gnx_graph_t g, const float *d_vals, const float *d_X, int64_t ldx, int64_t C_in, const float *d_W, int64_t ldw,
+                 int64_t C_out, const float *d_bias, int act, double dropout_p, uint64_t seed, uint64_t stream_id, float *d_out,
+                 int64_t ldo, float *d_agg, float *d_work, void *stream);
+int gnx_gcn_step_dropped(gnx_graph_t g, const float *d_D, float edge_p, uint64_t edge_seed, uint64_t edge_stream, const float *d_X,
+                         int64_t ldx, int64_t C_in, const float *d_W, int64_t ldw, int64_t C_out, const float *d_bias, int act,
+                         double dropout_p, uint64_t seed, uint64_t stream_id, float *d_out, int64_t ldo, float *d_agg,
+                         float *d_work, void *stream);
+
 /* ---- the dense ends of the path (matrix cores) -----------------------------------------------------------------------
  * gnx_dense: out = act(X . W + bias) -- Dense.__forward__ (gnntf/core/nn/layers.py:135-136) and the transform of
  * GCNLayer (gcn.py:89).  X [n, F] (ldx), W [F, O] (ldw), bias [O] or NULL, out [n, O] (ldo); float32 in and out, float32
