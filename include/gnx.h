@@ -732,7 +732,8 @@ int gnx_dense_wgrad(const float *d_X, int64_t ldx, const float *d_G, int64_t ldg
  *                   d_loss_per_node must hold m + 256 floats (the tail is scratch of the fixed-order two-level mean).
  * gnx_node_ce_backward: d_grad_logits[nodes[i], :] += d_grad_loss[0] / m * (softmax(logits[nodes[i], :]) - onehot(labels[i]));
  *                   the caller zero-fills d_grad_logits [n_rows, C] first.
- * gnx_node_argmax:  d_out[i] = first index of the maximum of logits[nodes[i], :] (d_nodes NULL: row i); graph_predictor.py:17. */
+ * gnx_node_argmax:  d_out[i] = first index of the maximum of logits[nodes[i], :] (d_nodes NULL: row i); graph_predictor.py:17.
+ *                   A NaN entry never wins: the maximum is taken over the other entries, and a row of only NaNs reports 0. */
 int gnx_node_ce(const float *d_logits, int64_t ldl, int64_t n_rows, int64_t C, const int64_t *d_nodes,
                 const int64_t *d_labels, int64_t m, float *d_loss_per_node, float *d_mean_loss, void *stream);
 int gnx_node_ce_backward(const float *d_logits, int64_t ldl, int64_t n_rows, int64_t C, const int64_t *d_nodes,
