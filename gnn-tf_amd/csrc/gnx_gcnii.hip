@@ -1,29 +1,26 @@
-// The GCNII layer (gcn.py:7-27,54-74) on gfx950.  The unit holds two fused kernels, three row passes, and ONE host path for each.
-//   k_spmm_gcnii       the layer in one launch: SpMM + residual mix + the C x C transform on the matrix cores (+ the layer's feature
-//                      dropout in the store loop, DROP), written once over the row-storage policy R of gnx_spmm_device.h
-//   k_spmm_gcnii_back  the layer's backward past the relu gate, one launch of the same shape over the transposed structure; the MFMA
-//                      block of the two is one device function (tile_times_Ms)
-//   k_gcnii_wgrad      the layer's weight gradient dM = T^T G with the mixed rows T made again in LDS and never stored, one launch; a
-//                      row's gather and mix is one device function with the forward (mixed_row)
-//                      SPEC: the spectral-preserving form (gnx_gcnii_step_spectral) -- the bias in the MFMA block's epilogue, -bias, the
-//                      mask and x 2 in the store loop, one gate bit per element; k_spectral_tail is the same epilogue as a row pass
-//                      (hub rows, the other widths) and k_spectral_back the backward's first pass (gate, bias gradient)
-//                      EDGE: the layer and its backward under edge dropout (gnx_gcnii_step_dropped, gnx_gcnii_step_back_dropped, f32 rows) --
-//                      the gather loops make their weights from the counter RNG (edge_gather) instead of loading them
-//   k_spmm_gcn         the GCN layer (gcn.py:77-89) in one launch, gnx_gcn_step / gnx_gcn_step_dropped: k_spmm_gcnii's block without the
-//                      residual operand -- the same gather (gathered_row, which mixed_row mixes behind), a rectangular W [C_in, C_out <= C_in]
-//                      in LDS, the MFMA block with the bias in its epilogue, DROP / EDGE / ENTRIES as above; host path gcn_forward
+// The GCNII layer (gcn.py:7-27,54-74) and the GCN layer (gcn.py:77-89) on gfx950: four kernels on one 16-row tile frame, the row passes
+// around them, and ONE host path per kernel over the launch plumbing they share.
+//   the frame          Tile<NT> (the geometry of a width), slot_row, tile_times_Ms (the MFMA block); described once above Tile
+//   the gathers        gathered_row (a row of A . X; edge_gather where the weights are made from the edge dropout: EDGE / ENTRIES) and
+//                      mixed_row (the residual mix behind it), written once over the row-storage policy R of gnx_spmm_device.h
+//   k_spmm_gcnii       the GCNII layer in one launch: SpMM + mix + the C x C transform (DROP: + the feature mask in the store loop; SPEC:
+//                      the spectral-preserving form, gnx_gcnii_step_spectral -- k_spectral_tail is its epilogue as a row pass,
+//                      k_spectral_back the backward's first pass)
+//   k_spmm_gcn         the GCN layer in one launch: the gather without the residual operand, a rectangular W [C_in, C_out <= C_in]
+//   k_spmm_gcnii_back  the GCNII layer's backward past the relu gate, one launch over the transposed structure
+//   k_gcnii_wgrad      the GCNII weight gradient dM = T^T G with the mixed rows T made again in LDS (mixed_row) and never stored
 //   row passes         k_round_rows (f32 rows -> bf16), k_feature_dropout (the mask as a pass of its own: hub rows, the other widths, the
-//                      generic composition) and the backward's gate (k_feature_dropout_back, .._back_bf16); one launcher
-//                      (launch_row_pass) picks their vector width and grid
-//   gcnii_forward<R>   the host path of gnx_gcnii_step, gnx_gcnii_step_drop, gnx_gcnii_step_dropped (F32Rows), gnx_gcnii_step_bf16, gnx_gcnii_step_train_bf16
-//                      and gnx_gcnii_step_drop_bf16 (Bf16Rows); a ForwardForm says what differs: the mask, where mixed rows are kept or pass through memory, the format
-//                      of the result, and whether the widths other than 16 / 32 / 64 run as two launches or are refused.  The checks, the
-//                      operand fill, ensure_partial (before the first launch), the launch (with_tile_width) and the tail of the rows
-//                      that go through memory (transform_rows) each stand once
-//   gcnii_backward<R>  the host path of gnx_gcnii_step_back, gnx_gcnii_step_back_dropped and gnx_gcnii_step_back_bf16, likewise; the f32 entry's composed form of the
-//                      other widths is its f32 branch
-//   gcnii_wgrad<R>     the host path of gnx_gcnii_wgrad and gnx_gcnii_wgrad_bf16
+//                      generic composition) and the backward's gate (k_feature_dropout_back, .._back_bf16); launch_row_pass picks
+//                      their vector width and grid
+//   the plumbing       bind_values (loaded values, or the edge dropout into p), reserve_partial (the hub rows' slab, before the first
+//                      launch), with_tile_width x with_flags (runtime width and switches -> template arguments), hub_rows_tail (the
+//                      long-row kernels, then the caller's transform of those rows alone)
+//   gcnii_forward<R>   gnx_gcnii_step, _step_drop, _step_dropped, _step_spectral (F32Rows), _step_bf16, _step_train_bf16, _step_drop_bf16
+//                      (Bf16Rows); a ForwardForm says what differs: the mask, where mixed rows are kept or pass through memory, the
+//                      format of the result, and whether the widths other than 16 / 32 / 64 run as two launches or are refused
+//   gcnii_backward<R>  gnx_gcnii_step_back, _step_back_dropped, _step_back_bf16; the composed form of the other widths is its f32 branch
+//   gcnii_wgrad<R>     gnx_gcnii_wgrad, gnx_gcnii_wgrad_bf16
+//   gcn_forward        gnx_gcn_step, gnx_gcn_step_dropped
 // Hub rows share the long-row path of gnx_spmm.hip / gnx_spmm_bf16.hip (launch_long_rows, launch_long_rows_bf16: the f32 launch's
 // summation order) and the dense kernel on those rows alone; rounding points in gnx.h.  The masks come from the counter RNG of the edge
 // dropout.
@@ -86,6 +83,25 @@ __device__ __forceinline__ uint32_t spectral_finish(const DropFuse &f, uint64_t 
     return bits;
 }
 
+// ---- the 16-row tile frame of k_spmm_gcnii, k_spmm_gcn, k_spmm_gcnii_back and k_gcnii_wgrad ------------------------------------------------
+// A block is WPB = 8 waves; wave w of block b owns tile b WPB + w: 16 row SLOTS of the structure's launch order (slot_row).  At width
+// C = 16 NT a row is held by G = 4 NT lanes of four columns each, so a wave holds RPP = 64 / G rows at a time and walks its tile in
+// PASSES = 16 / RPP passes: in pass ps lane l holds slot rr = ps RPP + l / G of the tile and columns c = 4 (l % G) .. c + 3.  The wave's
+// tile and the block's matrix (filled by the whole block before the waves past n_rows return) live in LDS with row stride C + 4 (= 4
+// mod 32 banks).  A slot past n_rows -- the ragged last tile -- has row -1; a slot is LIVE when it has a row of at most p.long_row
+// entries (hub rows are left to the long-row kernels + the dense kernel).  A dead slot holds zeros in the tile and stores nothing.  The
+// three tile kernels fill the tile pass by pass (rows[] / live[] keep what a pass found), put a wave barrier behind it, multiply
+// (tile_times_Ms) and walk the finished tile: a float4 of the lane's columns per live pass.
+// The geometry and the slot's row are written once below.  The fill, the slot -> row -> extent -> live step and the walk stand in each
+// kernel: written as __forceinline__ functions (over a lambda row body; the slot as a struct or through references) every one of them
+// changed instructions of some instantiation (profiles/NOTES.md, "The layer kernels' tile frame"), and the kernels stay the ones measured.
+template <int NT> struct Tile {
+    static constexpr int C = 16 * NT, G = 4 * NT, RPP = 64 / G, PASSES = 16 / RPP, STRIDE = C + 4;
+};
+
+// the row of slot `slot` < p.n_rows: the launch order is p.row_order (degree-binned; another one under a row window), null = the rows as numbered
+__device__ __forceinline__ int64_t slot_row(const SpmmArgs &p, int64_t slot) { return p.row_order ? (int64_t)p.row_order[slot] : slot; }
+
 // tile <- act(tile . Ms) for one wave's 16-row tile T and the block's Ms (both row stride C + 4, C = 16 NT), on
 // v_mfma_f32_16x16x4_f32: the block the forward layer and its backward (k_spmm_gcnii_back) share.  The caller has put a wave
 // barrier between its writes of T and this call; on return the whole tile is written and visible to the wave.
@@ -95,7 +111,7 @@ __device__ __forceinline__ uint32_t spectral_finish(const DropFuse &f, uint64_t 
 template <int NT, bool BIAS = false, int NTN = NT>
 __device__ __forceinline__ void tile_times_Ms(float *__restrict__ T, const float *__restrict__ Ms, int lane, int act,
                                               const float *__restrict__ bias = nullptr, int n_bias = 16 * NTN) {
-    constexpr int C = 16 * NT, STRIDE = C + 4;
+    constexpr int C = Tile<NT>::C, STRIDE = Tile<NT>::STRIDE;
     static_assert(NTN >= 1 && NTN <= NT, "the result tile overwrites the gathered one");
     // tile . M : A[m = lane & 15][k = 4 kk + (lane >> 4)] from the tile, B[k][n = lane & 15] from Ms
     const int cc = lane & 15, g = lane >> 4;
@@ -217,14 +233,12 @@ __device__ __forceinline__ void mixed_row(const typename R::Args &p, int64_t row
 
 // ---- GCNII layer: SpMM + mix + C x C transform on the matrix cores + activation, one launch ------------------------
 //   out[i,:] = act( (beta * sum_j A[i,j] X[j,:] + alpha * H0[i,:]) . M ),   M = (1-b) I + b W   (gcn.py:22-27)
-// A 512-thread block: every wave gathers a tile of 16 rows (4 NT lanes of float4 per row, U entries in flight per lane,
-// rows in degree-binned order), leaves the mixed rows in its LDS tile -- in inference they never go to HBM; in training
-// (`mixed` given) each lane also stores its piece of the mixed row, which the backward needs for dM = T^T g, so that the row is
-// written once and NOT read back for the transform -- multiplies the tile by M (shared by the block in LDS, row stride = 4 mod 32
-// banks) with v_mfma_f32_16x16x4_f32 (exact f32), and stores whole rows.  C = 16 NT for NT in {1, 2, 4}.  (NT = 8, C = 128, fits --
-// 135 KB of the CU's 160 KB of LDS -- but leaves one block of eight waves per CU: measured 19.2 ms against 11.8 ms for SpMM+mix
-// followed by the dense kernel, so wide layers keep the two launches.)  Rows longer than p.long_row are left to the long-row
-// kernels + the dense kernel.
+// The frame with mixed_row as the row's body (U entries in flight per lane): the mixed rows stay in the wave's LDS tile -- in inference
+// they never go to HBM; in training (`mixed` given) each lane also stores its piece of the mixed row, which the backward needs for
+// dM = T^T g, so that the row is written once and NOT read back for the transform -- meet M on v_mfma_f32_16x16x4_f32 (exact f32) and
+// leave as whole rows.  C = 16 NT for NT in {1, 2, 4}.  (NT = 8, C = 128, fits -- 135 KB of the CU's 160 KB of LDS -- but leaves one
+// block of eight waves per CU: measured 19.2 ms against 11.8 ms for SpMM+mix followed by the dense kernel, so wide layers keep the two
+// launches.)
 // Written once over the row-storage policy R (gnx_spmm_device.h): F32Rows gathers float4 pieces of f32 rows, Bf16RowsT 8-byte pieces of
 // bf16 rows (four columns, widened exactly) and stores the finished row as f32 or rounded once to bf16; entry order, summation order,
 // the mix and the transform are the same code, so the bf16 instantiation over bf16-representable rows gives the bits of the f32 one.
@@ -244,7 +258,8 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args 
                                                          const SpectralArgs<SPEC> sp = SpectralArgs<SPEC>{},
                                                          const EdgeArgs<EDGE> ed = EdgeArgs<EDGE>{}) {
     static_assert(!EDGE || (!SPEC && !R::BF16), "the edge-dropout form exists for the plain layer over f32 rows");
-    constexpr int C = 16 * NT, G = 4 * NT, RPP = 64 / G, PASSES = 16 / RPP, STRIDE = C + 4;
+    using TL = Tile<NT>;
+    constexpr int C = TL::C, G = TL::G, RPP = TL::RPP, PASSES = TL::PASSES, STRIDE = TL::STRIDE;
     __shared__ float Ms[C * STRIDE];
     __shared__ float Ts[WPB][16 * STRIDE];
     const int lane = threadIdx.x & 63;
@@ -264,7 +279,7 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args 
         int64_t row = -1;
         int64_t beg = 0, end = 0;
         if (slot < p.n_rows) {
-            row = p.row_order ? (int64_t)p.row_order[slot] : slot;
+            row = slot_row(p, slot);
             beg = p.rowptr[row]; end = p.rowptr[row + 1];
         }
         live[ps] = row >= 0 && end - beg <= p.long_row;
@@ -316,23 +331,21 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii(const typename R::Args 
 
 // ---- GCN layer: SpMM + the C_in x C_out transform on the matrix cores + bias + activation, one launch (gnx_gcn_step) --------------------
 //   out[i,:] = drop( act( (sum_j A[i,j] X[j,:]) . W + bias ) )      (gcn.py:88-89)
-// k_spmm_gcnii's shape without the residual operand: a 512-thread block, a 16-row tile per wave in degree-binned order, 4 NTI lanes of
-// float4 per row, the gather of gathered_row (the loop the GCNII kernels mix behind) -- C_in = 16 NTI.  W [C_in, C_out], 1 <= C_out <= C_in,
-// sits in LDS with row stride C_in + 4, its columns from C_out to 16 NTO zero-filled (NTO = ceil(C_out / 16): the padding exists in LDS
+// The frame at C_in = 16 NTI with gathered_row (the loop the GCNII kernels mix behind) as the row's body.  The block's matrix is
+// W [C_in, C_out], 1 <= C_out <= C_in, its columns from C_out to 16 NTO zero-filled (NTO = ceil(C_out / 16): the padding exists in LDS
 // alone); the product is tile_times_Ms with NTN = NTO, the bias (null: none) joins the accumulator as it leaves the MFMA block, before the
 // activation, and the result tile overwrites the gathered one (C_out <= C_in: no second tile; the LDS is k_spmm_gcnii's).  `agg` (null: not
 // kept) gets the aggregated rows, [n, C_in] contiguous, from the lanes that made them: training keeps them for dW = agg^T G', and the
 // transform never reads them back.  A lane stores its columns below C_out: a whole float4 where `vec_out` says the row starts of out allow
 // it (ldo % 4 == 0 and a 16-byte aligned base) and the four columns exist, scalars otherwise -- nothing is written past column C_out - 1 of
-// any row.  DROP: the mask of the finished rows (`feat`, keyed by row and column) in the store loop, as in k_spmm_gcnii; agg stays
-// undropped.  EDGE / ENTRIES: the weights are made from p.fuse in the gather loop (edge_gather), as in k_spmm_gcnii.  Rows longer than
-// p.long_row are left to the long-row kernels + the dense kernel.  f32 rows only.
+// any row.  DROP (`feat`, keyed by row and column; agg stays undropped) and EDGE / ENTRIES as in k_spmm_gcnii.  f32 rows only.
 template <typename R, int NTI, int NTO, int U, int WPB, bool DROP = false, bool EDGE = false, bool ENTRIES = false>
 __global__ __launch_bounds__(64 * WPB) void k_spmm_gcn(const typename R::Args p, const float *__restrict__ W, int64_t ldw, int C_out,
                                                        const float *__restrict__ bias, float *__restrict__ agg, bool vec_out, const DropFuse feat) {
     static_assert(!R::BF16, "the GCN layer exists over f32 rows");
     static_assert(NTO >= 1 && NTO <= NTI, "C_out <= C_in: the result tile overwrites the gathered one");
-    constexpr int C = 16 * NTI, CO = 16 * NTO, G = 4 * NTI, RPP = 64 / G, PASSES = 16 / RPP, STRIDE = C + 4;
+    using TL = Tile<NTI>;
+    constexpr int C = TL::C, CO = 16 * NTO, G = TL::G, RPP = TL::RPP, PASSES = TL::PASSES, STRIDE = TL::STRIDE;
     __shared__ float Ws[C * STRIDE];
     __shared__ float Ts[WPB][16 * STRIDE];
     const int lane = threadIdx.x & 63;
@@ -355,7 +368,7 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcn(const typename R::Args p,
         int64_t row = -1;
         int64_t beg = 0, end = 0;
         if (slot < p.n_rows) {
-            row = p.row_order ? (int64_t)p.row_order[slot] : slot;
+            row = slot_row(p, slot);
             beg = p.rowptr[row]; end = p.rowptr[row + 1];
         }
         live[ps] = row >= 0 && end - beg <= p.long_row;
@@ -391,14 +404,12 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcn(const typename R::Args p,
 // ---- the layer's backward past the relu gate, one launch (gnx_gcnii_step_back) -----------------------------------------------
 //   dH[r,:] = (beta * sum_c At[r,c] G[c,:]) . N        S_out[r,:] = s_alpha * S_in[r,:] + (alpha * G[r,:]) . N,    N = M^T
 // (1-a) At (G N) = ((1-a) At G) N: the launch gathers the gated gradient G itself over the transposed structure (p), so g' M^T is
-// never written or gathered back, and the row's own a G[r] N -- the layer's term of dH0 -- rides on the same Ms.  The forward's
-// shape: 512 threads, a 16-row tile per wave in the transposed structure's degree-binned order, NT lanes of float4 per row, U entries
-// in flight, Ms with row stride C + 4.  The ONE tile of a wave serves both products, one after the other (first beta Z, then alpha G
-// of the same 16 rows), so the kernel's LDS is the forward's (51 KB at C = 64: three blocks per CU; a second tile would leave two,
-// and the forward's C = 128 experiment above shows what the gathers lose with fewer waves).  Every row below n takes part in the
-// second product, hub rows and rows without entries included; the gather and the dH store leave rows longer than p.long_row to the
-// long-row kernels + the dense kernel; a row without entries gets dH = 0, written.  S_in may be S_out (each lane reads the four
-// values it overwrites); dH aliases nothing.
+// never written or gathered back, and the row's own a G[r] N -- the layer's term of dH0 -- rides on the same Ms.  The frame over the
+// transposed structure, with beta times the gather as the row's body.  The ONE tile of a wave serves both products, one after the other
+// (first beta Z, then alpha G of the same 16 slots), so the kernel's LDS is the forward's (51 KB at C = 64: three blocks per CU; a
+// second tile would leave two, and the forward's C = 128 experiment above shows what the gathers lose with fewer waves).  Every row
+// below n takes part in the second product, hub rows and rows without entries included (rows[ps] >= 0, not live[ps]); a row without
+// entries gets dH = 0, written.  S_in may be S_out (each lane reads the four values it overwrites); dH aliases nothing.
 // Written once over the row-storage policy R, as the forward is: Bf16RowsT gathers 8-byte pieces of the bf16 copy Gb of the gated
 // gradient (gnx_gcnii_step_back_bf16) and widens them exactly; dH (p.out) is f32 under either policy, and the row's own G[r] of the
 // second product is read from the f32 p.X under either policy too -- the bf16 entry binds the f32 G there beside Gb, so the running dH0
@@ -410,7 +421,8 @@ template <typename R, int NT, int U, int WPB, bool EDGE = false, bool ENTRIES = 
 __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii_back(const typename R::Args p, const float *__restrict__ N, int64_t ldn, const float *S_in,
                                                               float s_alpha, float *S_out) {
     static_assert(!EDGE || !R::BF16, "the edge-dropout form exists for f32 rows");
-    constexpr int C = 16 * NT, G = 4 * NT, RPP = 64 / G, PASSES = 16 / RPP, STRIDE = C + 4;
+    using TL = Tile<NT>;
+    constexpr int C = TL::C, G = TL::G, RPP = TL::RPP, PASSES = TL::PASSES, STRIDE = TL::STRIDE;
     __shared__ float Ms[C * STRIDE];
     __shared__ float Ts[WPB][16 * STRIDE];
     const int lane = threadIdx.x & 63;
@@ -430,15 +442,16 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii_back(const typename R::
         int64_t row = -1;
         int64_t beg = 0, end = 0;
         if (slot < p.n_rows) {
-            row = p.row_order ? (int64_t)p.row_order[slot] : slot;
+            row = p.row_order ? (int64_t)p.row_order[slot] : slot;      // (slot_row spelled out: through it 6 of the 12 instantiations move)
             beg = p.rowptr[row]; end = p.rowptr[row + 1];
         }
         live[ps] = row >= 0 && end - beg <= p.long_row;
         rows[ps] = row;
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
         if (live[ps]) {
-            // (the operand and its load are named directly, not through R::X / R::load: through the accessors the compiler structures the
-            // gather loop of the f32 instantiation differently, and that kernel stays instruction for instruction the one measured so far)
+            // (gathered_row's loop, copied by hand: with gathered_row<R, U, EDGE, ENTRIES, G> in its place -- tried again with the tile
+            // frame -- all 12 instantiations of this kernel move, f32 and bf16 alike (register allocation and the order of the fmaf
+            // chain's packed halves), and the kernel stays instruction for instruction the one measured so far)
             const typename R::Elem *__restrict__ Xc;
             if constexpr (R::BF16) Xc = p.Xb + c;
             else Xc = p.X + c;
@@ -516,8 +529,8 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii_back(const typename R::
 
 // ---- the layer's weight gradient without stored mixed rows, one launch (gnx_gcnii_wgrad) -------------------------------------------
 //   dM = T^T . G,   T = beta * A . X + alpha * H0 made again by mixed_row -- the forward's gather, entry order and mix, so T[r] has the
-// bits the forward would have stored -- and never written.  The forward's block (512 threads, a 16-row tile per wave in LDS, row stride
-// C + 4) without Ms: a wave fills its tile, multiplies T_tile^T . G_tile into NT x NT accumulator blocks on v_mfma_f32_16x16x4_f32 (k =
+// bits the forward would have stored -- and never written.  The frame's tiles without a block matrix, and with a wave that walks several
+// of them: it fills its tile, multiplies T_tile^T . G_tile into NT x NT accumulator blocks on v_mfma_f32_16x16x4_f32 (k =
 // the tile's 16 row slots, four per instruction) and goes on to its next tile with the accumulators live.  Block (mt, nt) holds the
 // columns NT m + mt of T against the columns NT n + nt of G: A[m][k] is then one 4 NT-byte LDS read of row k of the tile for all mt, and
 // B[k][n] one 4 NT-byte global load of G's row for all nt (16 lanes read the row's 64 NT contiguous bytes; no second LDS tile: at C = 64
@@ -532,7 +545,8 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii_back(const typename R::
 template <typename R, int NT, int U, int WPB>
 __global__ __launch_bounds__(64 * WPB) void k_gcnii_wgrad(const typename R::Args p, const float *__restrict__ Gm, const float *__restrict__ hub,
                                                           float *__restrict__ work) {
-    constexpr int C = 16 * NT, G = 4 * NT, RPP = 64 / G, PASSES = 16 / RPP, STRIDE = C + 4;
+    using TL = Tile<NT>;
+    constexpr int C = TL::C, G = TL::G, RPP = TL::RPP, PASSES = TL::PASSES, STRIDE = TL::STRIDE;
     static_assert(WPB * 16 * STRIDE >= C * C, "the block's partial reuses the tiles");
     __shared__ __attribute__((aligned(16))) float Ts[WPB * 16 * STRIDE];
     const int lane = threadIdx.x & 63;
@@ -553,7 +567,7 @@ __global__ __launch_bounds__(64 * WPB) void k_gcnii_wgrad(const typename R::Args
             const int64_t slot = tile * 16 + rr;
             float acc[4] = {0.f, 0.f, 0.f, 0.f};
             if (slot < p.n_rows) {
-                const int64_t row = p.row_order ? (int64_t)p.row_order[slot] : slot;
+                const int64_t row = slot_row(p, slot);
                 const int64_t beg = p.rowptr[row], end = p.rowptr[row + 1];
                 if (end - beg <= p.long_row) mixed_row<R, U>(p, row, beg, end, c, acc);
                 else vload<4>(acc, hub + row * (int64_t)C + c);
@@ -568,7 +582,7 @@ __global__ __launch_bounds__(64 * WPB) void k_gcnii_wgrad(const typename R::Args
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) b[kk][nt] = 0.f;
             if (slot < p.n_rows) {
-                const int64_t row = p.row_order ? (int64_t)p.row_order[slot] : slot;
+                const int64_t row = slot_row(p, slot);
                 vload<NT>(b[kk], Gm + row * (int64_t)C + NT * cc);
             }
         }
@@ -883,6 +897,49 @@ int admit_edge_drop(const char *fn, gnx_graph *g, const EdgeDrop &e) {
     return refuse_duplicates(g, fn);
 }
 
+// ---- the launch plumbing the host paths share --------------------------------------------------------------------------------------------
+// The values a fused launch walks with, into p: under `edge` they are made in the gather loop (p.fuse becomes the edge dropout's, over the
+// handle's per-slot values of that side), else they are loaded -- the caller's d_vals, or the handle's raw values of that side.
+void bind_values(const gnx_graph *g, const EdgeDrop *edge, bool transposed, const float *d_vals, SpmmArgs &p) {
+    if (edge) {
+        set_values(g, transposed, p);
+        set_drop_fuse(g, edge->p, edge->seed, edge->stream, edge->D, transposed ? 1 : 0, 0, p);
+    } else {
+        p.vals = d_vals ? d_vals : transposed ? g->t_raw.get() : g->raw_vals.get();
+    }
+}
+
+// The slab of the hub rows' chunked partial sums at width C, reserved before the first launch of a call: under capture a slab that would
+// have to grow refuses the whole call.
+int reserve_partial(gnx_graph *g, const Csr &m, int64_t C, hipStream_t s) {
+    return m.n_long > 0 ? ensure_partial(g, (size_t)m.n_chunks * (size_t)C * sizeof(float), s) : GNX_OK;
+}
+
+// The tail of a fused launch.  Hub rows: their chunked partial sums, finished as p says (the caller has set the p.act / p.ldo of rows that
+// go through memory), into f32 rows at their row ids of `to`, then transform(m.long_rows, m.n_long) -- what the caller does with those
+// rows alone.  Then, hub rows or none, the launches' error state.
+template <typename R, typename F>
+int hub_rows_tail(gnx_graph *g, const Csr &m, typename R::Args &p, const typename R::Elem *X, float *to, bool dropped, hipStream_t s, F &&transform) {
+    if (m.n_long > 0) {
+        p.partial = g->partial;
+        launch_hub_rows<R>(p, X, to, s, dropped);
+        const int rc = transform(m.long_rows, m.n_long);
+        if (rc != GNX_OK) return rc;
+    }
+    GNX_HIP(hipGetLastError());
+    return GNX_OK;
+}
+
+// f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...): runtime switches as template arguments.  Every combination of the flags is
+// instantiated in f, which guards the ones that have no kernel with `if constexpr`.
+template <typename F>
+void with_flags(F &&f) { f(); }
+template <typename F, typename... Flags>
+void with_flags(F &&f, bool flag, Flags... rest) {
+    if (flag) with_flags([&](auto... tail) { f(std::true_type{}, tail...); }, rest...);
+    else      with_flags([&](auto... tail) { f(std::false_type{}, tail...); }, rest...);
+}
+
 // the fused launch takes C = 16, 32 or 64 (C = 128 fits the kernel -- 135 KB of LDS: one block of eight waves per CU -- and was measured:
 // 19.2 ms against 11.8 ms for the two launches on the config-4 graph; eight waves per CU cannot keep the gathers fed)
 bool fused_width(int64_t C) { return C == 16 || C == 32 || C == 64; }
@@ -944,13 +1001,8 @@ int gcnii_forward(const char *fn, gnx_graph *g, const float *d_vals, const typen
     hipStream_t s = (hipStream_t)stream;
     const float beta = (float)(1.0 - (double)a);
     typename R::Args p{};
-    if (f.edge) {      // p.fuse is the edge dropout's; the mask travels beside it (EdgeArgs)
-        set_values(g, false, p);
-        set_drop_fuse(g, f.edge->p, f.edge->seed, f.edge->stream, f.edge->D, 0, 0, p);
-    } else {
-        p.vals = d_vals ? d_vals : g->raw_vals;
-        if (f.fd) p.fuse = *f.fd;
-    }
+    bind_values(g, f.edge, false, d_vals, p);
+    if (!f.edge && f.fd) p.fuse = *f.fd;      // (under f.edge p.fuse is the edge dropout's; the mask travels beside it, EdgeArgs)
     set_operands<R>(p, d_H, C, d_H0, C, beta, a, act, d_out, f.out_bf16, C, C);
     // mixed rows at T (the n listed; null: rows 0 .. n) -> act(T . M) of those rows alone, into d_out, or into d_work where the result is
     // bf16 -> their mask, in place -> the rows rounded into d_out.  (T may be d_work itself: every wave of the dense kernels reads whole
@@ -985,43 +1037,26 @@ int gcnii_forward(const char *fn, gnx_graph *g, const float *d_vals, const typen
     }
     if (m.n_rows == 0) return GNX_OK;
     bind_fused(m, p);
-    if (m.n_long > 0) {   // (before the first launch: under capture a slab that would have to grow refuses the whole call)
-        rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)C * sizeof(float), s);
-        if (rc != GNX_OK) return rc;
-    }
+    rc = reserve_partial(g, m, C, s);
+    if (rc != GNX_OK) return rc;
+    // the edge-dropout form and the spectral form exist over f32 rows; ENTRIES goes with EDGE
+    const bool edged = !R::BF16 && f.edge, spectral = !R::BF16 && f.bias && !f.edge;
     with_tile_width(C, m.n_rows, [&](auto NT, dim3 grid) {
-        if constexpr (!R::BF16) {
-            if (f.edge) {
-                const EdgeArgs<true> ed{f.fd ? *f.fd : DropFuse{}};
-                auto launch = [&](auto DROP, auto ENTRIES) {
-                    hipLaunchKernelGGL((k_spmm_gcnii<R, NT(), 4, 8, DROP(), false, true, ENTRIES()>), grid, dim3(512), 0, s, p, d_M, ldm, f.mixed,
-                                       SpectralArgs<false>{}, ed);
-                };
-                if (f.fd) { if (p.fuse.mult) launch(std::true_type{}, std::true_type{}); else launch(std::true_type{}, std::false_type{}); }
-                else      { if (p.fuse.mult) launch(std::false_type{}, std::true_type{}); else launch(std::false_type{}, std::false_type{}); }
-                return;
+        with_flags([&](auto DROP, auto SPEC, auto EDGE, auto ENTRIES) {
+            if constexpr (!(R::BF16 && (SPEC() || EDGE())) && !(SPEC() && EDGE()) && (EDGE() || !ENTRIES())) {
+                SpectralArgs<SPEC()> sp{};
+                if constexpr (SPEC()) sp = {f.bias, f.gate};
+                EdgeArgs<EDGE()> ed{};
+                if constexpr (EDGE()) ed.feat = f.fd ? *f.fd : DropFuse{};
+                hipLaunchKernelGGL((k_spmm_gcnii<R, NT(), 4, 8, DROP(), SPEC(), EDGE(), ENTRIES()>), grid, dim3(512), 0, s, p, d_M, ldm, f.mixed, sp, ed);
             }
-            if (f.bias) {
-                const SpectralArgs<true> sp{f.bias, f.gate};
-                if (f.fd) hipLaunchKernelGGL((k_spmm_gcnii<R, NT(), 4, 8, true, true>), grid, dim3(512), 0, s, p, d_M, ldm, f.mixed, sp);
-                else      hipLaunchKernelGGL((k_spmm_gcnii<R, NT(), 4, 8, false, true>), grid, dim3(512), 0, s, p, d_M, ldm, f.mixed, sp);
-                return;
-            }
-        }
-        if (f.fd) hipLaunchKernelGGL((k_spmm_gcnii<R, NT(), 4, 8, true>), grid, dim3(512), 0, s, p, d_M, ldm, f.mixed, SpectralArgs<false>{});
-        else      hipLaunchKernelGGL((k_spmm_gcnii<R, NT(), 4, 8>), grid, dim3(512), 0, s, p, d_M, ldm, f.mixed, SpectralArgs<false>{});
+        }, f.fd != nullptr, spectral, edged, edged && p.fuse.mult);
     });
     g->last_kernel = f.fused;
-    if (m.n_long == 0) {
-        GNX_HIP(hipGetLastError());
-        return GNX_OK;
-    }
     // hub rows: chunked partial sums -> mixed rows (into d_mixed when kept, else d_work, else in place) -> the transform of those rows alone
     float *T = f.mixed ? f.mixed : f.work ? f.work : static_cast<float *>(d_out);
-    p.partial = g->partial;
     p.act = GNX_ACT_NONE;
-    launch_hub_rows<R>(p, d_H, T, s, f.edge != nullptr);
-    return transform_rows(T, m.long_rows, m.n_long);
+    return hub_rows_tail<R>(g, m, p, d_H, T, f.edge != nullptr, s, [&](const int32_t *rows, int64_t n) { return transform_rows(T, rows, n); });
 }
 
 // ---- the backward's host path, once over the row storage R of the gathered gradient X (the f32 G itself, or its bf16 copy Gb) ------------
@@ -1078,39 +1113,25 @@ int gcnii_backward(const char *fn, gnx_graph *g, const float *d_vals_t, const ty
     if (rc != GNX_OK) return rc;
     const Csr &m = g->t;
     if (m.n_rows == 0) return GNX_OK;
-    if (m.n_long > 0) {
-        rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)C * sizeof(float), s);
-        if (rc != GNX_OK) return rc;
-    }
+    rc = reserve_partial(g, m, C, s);
+    if (rc != GNX_OK) return rc;
     typename R::Args p{};
-    if (edge) {
-        set_values(g, true, p);
-        set_drop_fuse(g, edge->p, edge->seed, edge->stream, edge->D, 1, 0, p);
-    } else {
-        p.vals = d_vals_t ? d_vals_t : g->t_raw.get();
-    }
+    bind_values(g, edge, true, d_vals_t, p);
     set_operands<R>(p, d_X, C, nullptr, 0, beta, a, GNX_ACT_NONE, d_dH, 0, C, C);
     p.X = d_G; p.out = d_dH;      // the row's own f32 row and the f32 dH are SpmmArgs' own under either policy (k_spmm_gcnii_back)
     bind_fused(m, p);
+    const bool edged = !R::BF16 && edge;      // (the edge-dropout form exists over f32 rows; ENTRIES goes with EDGE)
     with_tile_width(C, m.n_rows, [&](auto NT, dim3 grid) {
-        if constexpr (!R::BF16) {
-            if (edge) {
-                if (p.fuse.mult) hipLaunchKernelGGL((k_spmm_gcnii_back<R, NT(), 4, 8, true, true>), grid, dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
-                else             hipLaunchKernelGGL((k_spmm_gcnii_back<R, NT(), 4, 8, true, false>), grid, dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
-                return;
-            }
-        }
-        hipLaunchKernelGGL((k_spmm_gcnii_back<R, NT(), 4, 8>), grid, dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
+        with_flags([&](auto EDGE, auto ENTRIES) {
+            if constexpr (!(R::BF16 && EDGE()) && (EDGE() || !ENTRIES()))
+                hipLaunchKernelGGL((k_spmm_gcnii_back<R, NT(), 4, 8, EDGE(), ENTRIES()>), grid, dim3(512), 0, s, p, d_Mt, ldmt, d_S_in, s_alpha, d_S_out);
+        }, edged, edged && p.fuse.mult);
     });
     g->last_kernel = R::BF16 ? "spmm_gcnii_back_mfma_bf16" : edge ? "spmm_gcnii_back_mfma_edrop" : "spmm_gcnii_back_mfma";
-    if (m.n_long > 0) {   // hub rows of the transposed structure: chunked partial sums -> (1-a) Z into dH -> those rows alone times Mt, in place
-        p.partial = g->partial;
-        launch_hub_rows<R>(p, d_X, d_dH, s, edge != nullptr);
-        rc = dense_rows(d_dH, C, m.n_long, C, d_Mt, ldmt, C, nullptr, GNX_ACT_NONE, m.long_rows, m.long_rows, d_dH, C, s);
-        if (rc != GNX_OK) return rc;
-    }
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
+    // hub rows of the transposed structure: chunked partial sums -> (1-a) Z into dH -> those rows alone times Mt, in place
+    return hub_rows_tail<R>(g, m, p, d_X, d_dH, edge != nullptr, s, [&](const int32_t *rows, int64_t n) {
+        return dense_rows(d_dH, C, n, C, d_Mt, ldmt, C, nullptr, GNX_ACT_NONE, rows, rows, d_dH, C, s);
+    });
 }
 
 // ---- the weight gradient's host path, once over the row storage R of H (gnx_gcnii_wgrad, gnx_gcnii_wgrad_bf16) -------------------------
@@ -1138,18 +1159,15 @@ int gcnii_wgrad(const char *fn, const char *reports, gnx_graph *g, const float *
         GNX_HIP(hipMemsetAsync(d_dM, 0, (size_t)(C * C) * sizeof(float), s));
         return GNX_OK;
     }
-    if (m.n_long > 0) {   // (before the first launch: under capture a slab that would have to grow refuses the whole call)
-        const int rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)C * sizeof(float), s);
-        if (rc != GNX_OK) return rc;
-    }
+    int rc = reserve_partial(g, m, C, s);
+    if (rc != GNX_OK) return rc;
     typename R::Args p{};
-    p.vals = d_vals ? d_vals : g->raw_vals;
+    bind_values(g, nullptr, false, d_vals, p);
     set_operands<R>(p, d_H, C, d_H0, C, (float)(1.0 - (double)a), a, GNX_ACT_NONE, static_cast<typename R::Out *>(d_hub_rows), 0, C, C);
     bind_fused(m, p);
-    if (m.n_long > 0) {   // hub rows: chunked partial sums -> mixed rows at their row ids of d_hub_rows, where the launch below finds them
-        p.partial = g->partial;
-        launch_hub_rows<R>(p, d_H, d_hub_rows, s);
-    }
+    // hub rows: chunked partial sums -> mixed rows at their row ids of d_hub_rows, where the launch below finds them
+    rc = hub_rows_tail<R>(g, m, p, d_H, d_hub_rows, false, s, [](const int32_t *, int64_t) { return GNX_OK; });
+    if (rc != GNX_OK) return rc;
     // as many slabs as the scratch holds, at most 2048 (gnx_dense_wgrad's cap) and at most one per block of eight tiles: a function of
     // (n, C, work_floats) alone, like the tile -> wave -> block assignment that follows from it
     const int64_t slabs = std::min<int64_t>(std::min<int64_t>(work_floats / (C * C), 2048), blocks_for(blocks_for(m.n_rows, 16), 8));
@@ -1222,35 +1240,22 @@ int gcn_forward(const char *fn, gnx_graph *g, const float *d_vals, const EdgeDro
         return transform_rows(nullptr, m.n_rows);
     }
     if (m.n_rows == 0) return GNX_OK;
-    if (m.n_long > 0) {   // (before the first launch: under capture a slab that would have to grow refuses the whole call)
-        const int rc = ensure_partial(g, (size_t)m.n_chunks * (size_t)C_in * sizeof(float), s);
-        if (rc != GNX_OK) return rc;
-    }
+    int rc = reserve_partial(g, m, C_in, s);
+    if (rc != GNX_OK) return rc;
     SpmmArgs p{};
-    if (edge) {      // p.fuse is the edge dropout's; the mask travels beside it
-        set_values(g, false, p);
-        set_drop_fuse(g, edge->p, edge->seed, edge->stream, edge->D, 0, 0, p);
-    } else {
-        p.vals = d_vals ? d_vals : g->raw_vals;
-    }
+    bind_values(g, edge, false, d_vals, p);      // (under `edge` p.fuse is the edge dropout's; the mask travels beside it, `feat`)
     set_operands<F32Rows>(p, d_X, ldx, nullptr, 0, 1.f, 0.f, act, o.out, 0, o.ldo, C_in);
     bind_fused(m, p);
     const bool vec_out = o.ldo % 4 == 0 && aligned(o.out, 16);
     const DropFuse feat = fd ? *fd : DropFuse{};
     const int nto = (int)blocks_for(C_out, 16);
     with_tile_width(C_in, m.n_rows, [&](auto NTI, dim3 grid) {
-        auto launch = [&](auto NTO, auto DROP, auto ENTRIES) {
-            if constexpr (NTO() <= NTI()) {
-                if (edge) hipLaunchKernelGGL((k_spmm_gcn<F32Rows, NTI(), NTO(), 4, 8, DROP(), true, ENTRIES()>), grid, dim3(512), 0, s, p, d_W, ldw,
-                                             (int)C_out, d_bias, o.agg, vec_out, feat);
-                else if constexpr (!ENTRIES()) hipLaunchKernelGGL((k_spmm_gcn<F32Rows, NTI(), NTO(), 4, 8, DROP()>), grid, dim3(512), 0, s, p, d_W, ldw,
-                                                                  (int)C_out, d_bias, o.agg, vec_out, feat);
-            }
-        };
-        auto with_mode = [&](auto NTO) {
-            const bool entries = edge && p.fuse.mult;
-            if (fd) { if (entries) launch(NTO, std::true_type{}, std::true_type{}); else launch(NTO, std::true_type{}, std::false_type{}); }
-            else    { if (entries) launch(NTO, std::false_type{}, std::true_type{}); else launch(NTO, std::false_type{}, std::false_type{}); }
+        auto with_mode = [&](auto NTO) {      // (C_out <= C_in: no NTO above NTI; ENTRIES goes with EDGE)
+            with_flags([&](auto DROP, auto EDGE, auto ENTRIES) {
+                if constexpr (NTO() <= NTI() && (EDGE() || !ENTRIES()))
+                    hipLaunchKernelGGL((k_spmm_gcn<F32Rows, NTI(), NTO(), 4, 8, DROP(), EDGE(), ENTRIES()>), grid, dim3(512), 0, s, p, d_W, ldw,
+                                       (int)C_out, d_bias, o.agg, vec_out, feat);
+            }, fd != nullptr, edge != nullptr, edge && p.fuse.mult);
         };
         if (nto == 1)      with_mode(IntC<1>{});
         else if (nto == 2) with_mode(IntC<2>{});
@@ -1258,16 +1263,10 @@ int gcn_forward(const char *fn, gnx_graph *g, const float *d_vals, const EdgeDro
         else               with_mode(IntC<4>{});
     });
     g->last_kernel = kGcnFused[C_in == 16 ? 0 : C_in == 32 ? 1 : 2][mode][m.n_long > 0];
-    if (m.n_long == 0) {
-        GNX_HIP(hipGetLastError());
-        return GNX_OK;
-    }
     // hub rows: chunked partial sums -> aggregated rows at their row ids of T -> the transform and the mask of those rows alone
-    p.partial = g->partial;
     p.act = GNX_ACT_NONE;
     p.ldo = C_in;
-    launch_hub_rows<F32Rows>(p, d_X, T, s, edge != nullptr);
-    return transform_rows(m.long_rows, m.n_long);
+    return hub_rows_tail<F32Rows>(g, m, p, d_X, T, edge != nullptr, s, transform_rows);
 }
 
 }  // namespace

@@ -1164,6 +1164,34 @@ def feature_dropout(graph: DeviceGraph, X: torch.Tensor, p, seed, stream) -> tor
     return _FeatureDropout.apply(X, graph, *triple)
 
 
+def _dropout_args(dropout):
+    """The (p, seed, stream) an entry takes for ``dropout`` = the checked triple or None (rate 0: nothing is hashed)."""
+    return dropout or (0.0, 0, 0)
+
+
+def _gated_gradient(graph: DeviceGraph, g, out, relu, dropout):
+    """g' of a fused layer from the upstream gradient ``g`` and the saved ``out``: with a fused mask one pass (gnx_feature_dropout_back:
+    kept ? g * s : 0, gated by out > 0 under ``relu``), else the relu mask; contiguous."""
+    if dropout is not None:
+        return _feature_dropout_back(graph, g, out, *dropout, relu=relu)
+    return (_relu_mask(g, out) if relu else g).contiguous()
+
+
+def _gcnii_input_grads(adj, G, a, M, want_H, want_H0, fused_backward, fused_edge=False):
+    """(dH, dH0) of a GCNII layer from its gated gradient ``G``; None where not wanted.  ``fused_backward``: one launch
+    (gcnii_step_back: dH = ((1-a) A^T G) M^T, dH0 = (a G) M^T -- it always makes dH; a caller that wants dH0 alone is not what a GCNII
+    stack asks for); else dT = G M^T (gnx_dense), dH = (1-a) A^T dT, dH0 = a dT."""
+    if not (want_H or want_H0):
+        return None, None
+    Mt = M.t().contiguous()
+    if fused_backward:
+        gH, gH0 = gcnii_step_back(adj, G, a, Mt, want_S=want_H0, edge_dropout="fused" if fused_edge else "composed")
+        return (gH if want_H else None), gH0
+    gT = _dense_launch(G, Mt, None, False)
+    gH = _launch(adj, gT, None, 1.0 - a, 0.0, nat.ACT_NONE, transposed=True) if want_H else None
+    return gH, (gT * a if want_H0 else None)
+
+
 def _gcnii_operands(what, adj, rows, f32=(), M=None, constant=None, device=True):
     """The checks the GCNII launches share: a square adjacency without a diagonal -- with ``constant`` (what it is that needs one) no
     DroppedAdjacency either -- with ``device`` device tensors on its device, ``rows`` (bf16 or f32, [n, C]), every ``f32`` matrix of
@@ -1198,10 +1226,10 @@ def _gcnii_launch(adj: Adjacency, H, H0, a, M, relu, keep_mixed, dropout=None, f
     act = nat.ACT_RELU if relu else nat.ACT_NONE
     if fused_edge:
         _same_device(g, adj.D)
-        mask = dropout if dropout is not None else (0.0, 0, 0)
         with nat.on_device(H.device):
             nat.check(nat.lib().gnx_gcnii_step_dropped(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, nat.ptr(H), nat.ptr(H0), float(a), C,
-                                                       nat.ptr(M), M.stride(0), act, *mask, nat.ptr(out), nat.ptr(mixed), nat.current_stream()))
+                                                       nat.ptr(M), M.stride(0), act, *_dropout_args(dropout), nat.ptr(out), nat.ptr(mixed),
+                                                       nat.current_stream()))
         return out, mixed
     layer = (g.handle, nat.ptr(adj.vals), nat.ptr(H), nat.ptr(H0), float(a), C, nat.ptr(M), M.stride(0), act)
     with nat.on_device(H.device):
@@ -1338,28 +1366,14 @@ class _GCNIIStep(torch.autograd.Function):
             H, H0, M, out = ctx.saved_tensors
         else:
             T, M, out = ctx.saved_tensors
-        if ctx.dropout is not None:
-            g = _feature_dropout_back(ctx.adj.graph, g, out, *ctx.dropout, relu=ctx.relu)
-        else:
-            g = (_relu_mask(g, out) if ctx.relu else g).contiguous()
+        g = _gated_gradient(ctx.adj.graph, g, out, ctx.relu, ctx.dropout)
         if not ctx.needs_input_grad[2]:
             gM = None
         elif ctx.recompute:
             gM = gcnii_wgrad(ctx.adj, H, H0, ctx.a, _as_f32_rows(g).contiguous())
         else:
             gM = _dense_wgrad(T, g)
-        gH = gH0 = None
-        if ctx.fused_backward and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
-            # (the launch always makes dH; a caller that wants dH0 alone is not what a GCNII stack asks for)
-            gH, gH0 = gcnii_step_back(ctx.adj, g, ctx.a, M.t().contiguous(), want_S=ctx.needs_input_grad[1],
-                                      edge_dropout="fused" if ctx.fused_edge else "composed")
-            gH = gH if ctx.needs_input_grad[0] else None
-        elif ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            gT = _dense_launch(g, M.t().contiguous(), None, False)
-            if ctx.needs_input_grad[0]:
-                gH = _launch(ctx.adj, gT, None, 1.0 - ctx.a, 0.0, nat.ACT_NONE, transposed=True)
-            if ctx.needs_input_grad[1]:
-                gH0 = gT * ctx.a
+        gH, gH0 = _gcnii_input_grads(ctx.adj, g, ctx.a, M, ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.fused_backward, ctx.fused_edge)
         return gH, gH0, gM, None, None, None, None, None, None, None
 
 
@@ -1462,7 +1476,7 @@ def _gcn_launch(adj: Adjacency, X, W, bias, relu, keep_agg, dropout=None, fused_
     out = torch.empty((n, C_out), dtype=torch.float32, device=X.device)
     rows = torch.empty((n, C_in), dtype=torch.float32, device=X.device) if keep_agg or not one_launch or g.n_hub_rows > 0 else None
     agg, work = (rows, None) if keep_agg else (None, rows)
-    p, seed, stream = dropout if dropout is not None else (0.0, 0, 0)
+    p, seed, stream = _dropout_args(dropout)
     layer = (nat.ptr(X), X.stride(0), C_in, nat.ptr(W), W.stride(0), C_out, nat.ptr(b), nat.ACT_RELU if relu else nat.ACT_NONE, p, seed, stream,
              nat.ptr(out), out.stride(0), nat.ptr(agg), nat.ptr(work))
     with nat.on_device(X.device):
@@ -1490,10 +1504,7 @@ class _GCNStep(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         agg, W, out = ctx.saved_tensors
-        if ctx.dropout is not None:
-            g = _feature_dropout_back(ctx.adj.graph, g, out, *ctx.dropout, relu=ctx.relu)
-        else:
-            g = (_relu_mask(g, out) if ctx.relu else g).contiguous()
+        g = _gated_gradient(ctx.adj.graph, g, out, ctx.relu, ctx.dropout)
         gW = _dense_wgrad(agg, g) if ctx.needs_input_grad[1] else None
         gb = g.sum(dim=0).reshape(ctx.bias_shape) if ctx.bias_shape is not None and ctx.needs_input_grad[2] else None
         gX = None
@@ -1567,7 +1578,7 @@ def _gcnii_spectral_launch(adj: Adjacency, H, H0, a, M, bias, relu, keep, dropou
     out = torch.empty_like(H)
     mixed = torch.empty_like(H) if keep or C not in GCNII_FUSED_WIDTHS else None
     gate = torch.empty((H.shape[0], _gate_words(C)), dtype=torch.int32, device=H.device) if keep and relu else None
-    p, seed, stream = dropout if dropout is not None else (0.0, 0, 0)
+    p, seed, stream = _dropout_args(dropout)
     with nat.on_device(H.device):
         nat.check(nat.lib().gnx_gcnii_step_spectral(g.handle, nat.ptr(adj.vals), nat.ptr(H), nat.ptr(H0), float(a), C, nat.ptr(M), M.stride(0),
                                                     nat.ptr(b), nat.ACT_RELU if relu else nat.ACT_NONE, p, seed, stream, nat.ptr(out),
@@ -1590,7 +1601,7 @@ def _gcnii_spectral_gate(graph: DeviceGraph, g, gate, relu, dropout=None):
         return G, dbias
     slabs = max(1, min(2048, (n + 255) // 256))                      # include/gnx.h: a function of n alone
     work = torch.empty(slabs * C, dtype=torch.float32, device=g.device) if relu else None
-    p, seed, stream = dropout if dropout is not None else (0.0, 0, 0)
+    p, seed, stream = _dropout_args(dropout)
     with nat.on_device(g.device):
         nat.check(nat.lib().gnx_gcnii_spectral_back(graph.handle, nat.ptr(g), g.stride(0), nat.ptr(gate) if relu else None, n, C,
                                                     nat.ACT_RELU if relu else nat.ACT_NONE, p, seed, stream, nat.ptr(G), G.stride(0),
@@ -1617,16 +1628,7 @@ class _GCNIISpectralStep(torch.autograd.Function):
         T, M, gate = ctx.saved_tensors
         G, gbias = _gcnii_spectral_gate(ctx.adj.graph, g, gate, ctx.relu, ctx.dropout)
         gM = _dense_wgrad(T, G) if ctx.needs_input_grad[2] else None
-        gH = gH0 = None
-        if ctx.fused_backward and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
-            gH, gH0 = gcnii_step_back(ctx.adj, G, ctx.a, M.t().contiguous(), want_S=ctx.needs_input_grad[1])
-            gH = gH if ctx.needs_input_grad[0] else None
-        elif ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            gT = _dense_launch(G, M.t().contiguous(), None, False)
-            if ctx.needs_input_grad[0]:
-                gH = _launch(ctx.adj, gT, None, 1.0 - ctx.a, 0.0, nat.ACT_NONE, transposed=True)
-            if ctx.needs_input_grad[1]:
-                gH0 = gT * ctx.a
+        gH, gH0 = _gcnii_input_grads(ctx.adj, G, ctx.a, M, ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.fused_backward)
         gbias = gbias.reshape(ctx.bias_shape) if ctx.needs_input_grad[3] else None
         return gH, gH0, gM, gbias, None, None, None, None, None
 
