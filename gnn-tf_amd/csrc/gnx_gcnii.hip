@@ -1,4 +1,4 @@
-// The GCNII layer (gcn.py:7-27,54-74) and the GCN layer (gcn.py:77-89) on gfx950: four kernels on one 16-row tile frame, the row passes
+// The GCNII layer (gcn.py:7-27,54-74) and the GCN layer (gcn.py:77-89) on gfx950: five kernels on one 16-row tile frame, the row passes
 // around them, and ONE host path per kernel over the launch plumbing they share.
 //   the frame          Tile<NT> (the geometry of a width), slot_row, tile_times_Ms (the MFMA block); described once above Tile
 //   the gathers        gathered_row (a row of A . X; edge_gather where the weights are made from the edge dropout: EDGE / ENTRIES) and
@@ -8,6 +8,8 @@
 //                      k_spectral_back the backward's first pass)
 //   k_spmm_gcn         the GCN layer in one launch: the gather without the residual operand, a rectangular W [C_in, C_out <= C_in]
 //   k_spmm_gcnii_back  the GCNII layer's backward past the relu gate, one launch over the transposed structure
+//   k_spmm_gcn_back    the GCN layer's input gradient past the gate, one launch over the transposed structure: the gated gradient
+//                      gathered at the OUTPUT width, stored at the input width (two geometries of the one tile)
 //   k_gcnii_wgrad      the GCNII weight gradient dM = T^T G with the mixed rows T made again in LDS (mixed_row) and never stored
 //   row passes         k_round_rows (f32 rows -> bf16), k_feature_dropout (the mask as a pass of its own: hub rows, the other widths, the
 //                      generic composition) and the backward's gate (k_feature_dropout_back, .._back_bf16); launch_row_pass picks
@@ -21,6 +23,7 @@
 //   gcnii_backward<R>  gnx_gcnii_step_back, _step_back_dropped, _step_back_bf16; the composed form of the other widths is its f32 branch
 //   gcnii_wgrad<R>     gnx_gcnii_wgrad, gnx_gcnii_wgrad_bf16
 //   gcn_forward        gnx_gcn_step, gnx_gcn_step_dropped
+//   gcn_backward       gnx_gcn_step_back, gnx_gcn_step_back_dropped; the composed order of the other widths / strides is its branch
 // Hub rows share the long-row path of gnx_spmm.hip / gnx_spmm_bf16.hip (launch_long_rows, launch_long_rows_bf16: the f32 launch's
 // summation order) and the dense kernel on those rows alone; rounding points in gnx.h.  The masks come from the counter RNG of the edge
 // dropout.
@@ -83,7 +86,7 @@ __device__ __forceinline__ uint32_t spectral_finish(const DropFuse &f, uint64_t 
     return bits;
 }
 
-// ---- the 16-row tile frame of k_spmm_gcnii, k_spmm_gcn, k_spmm_gcnii_back and k_gcnii_wgrad ------------------------------------------------
+// ---- the 16-row tile frame of k_spmm_gcnii, k_spmm_gcn, k_spmm_gcnii_back, k_spmm_gcn_back and k_gcnii_wgrad ----------------------------
 // A block is WPB = 8 waves; wave w of block b owns tile b WPB + w: 16 row SLOTS of the structure's launch order (slot_row).  At width
 // C = 16 NT a row is held by G = 4 NT lanes of four columns each, so a wave holds RPP = 64 / G rows at a time and walks its tile in
 // PASSES = 16 / RPP passes: in pass ps lane l holds slot rr = ps RPP + l / G of the tile and columns c = 4 (l % G) .. c + 3.  The wave's
@@ -108,11 +111,13 @@ __device__ __forceinline__ int64_t slot_row(const SpmmArgs &p, int64_t slot) { r
 // BIAS (the spectral form): tile <- act(tile . Ms + bias[c]), the bias added to the accumulator value as it leaves the MFMA block.
 // NTN (k_spmm_gcn): Ms holds 16 NTN <= C columns -- a rectangular transform -- and the result tile has that many, over the tile's
 // first columns; its bias has n_bias entries, the columns from there on add 0 (n_bias = 0: no bias at all, the pointer is not read).
-template <int NT, bool BIAS = false, int NTN = NT>
+// NTK (k_spmm_gcn_back): the k extent -- the tile's first 16 NTK <= C columns are the gathered ones and Ms has that many rows.
+template <int NT, bool BIAS = false, int NTN = NT, int NTK = NT>
 __device__ __forceinline__ void tile_times_Ms(float *__restrict__ T, const float *__restrict__ Ms, int lane, int act,
                                               const float *__restrict__ bias = nullptr, int n_bias = 16 * NTN) {
-    constexpr int C = Tile<NT>::C, STRIDE = Tile<NT>::STRIDE;
+    constexpr int C = 16 * NTK, STRIDE = Tile<NT>::STRIDE;
     static_assert(NTN >= 1 && NTN <= NT, "the result tile overwrites the gathered one");
+    static_assert(NTK >= 1 && NTK <= NT, "the gathered columns are the tile's first");
     // tile . M : A[m = lane & 15][k = 4 kk + (lane >> 4)] from the tile, B[k][n = lane & 15] from Ms
     const int cc = lane & 15, g = lane >> 4;
     [[maybe_unused]] float bv[NTN];
@@ -152,9 +157,11 @@ __device__ __forceinline__ void tile_times_Ms(float *__restrict__ T, const float
 // per stored entry, not one per lane -- and the round is walked U entries at a time through shuffles inside the group (the lanes of a row
 // run the loop together: same beg and end).  A weight of exactly 0 -- a dropped entry, or a slot past the end of the row -- gathers
 // nothing and adds fmaf(0, 0, acc) = acc (the DroppedAdjacency precondition of finite features).
+// `loads` (k_spmm_gcn_back, whose rows are narrower than its lane groups): a lane without columns of its own draws its share of the
+// weights and takes part in the shuffles, and gathers nothing.
 template <bool ENTRIES, int G, int U>
 __device__ __forceinline__ void edge_gather(const SpmmArgs &p, const float *__restrict__ Xc, int64_t row, int64_t beg, int64_t end,
-                                            float (&acc)[4]) {
+                                            float (&acc)[4], bool loads = true) {
     static_assert(G % U == 0, "a round of G entries is whole batches of U");
     const int sub = (int)(threadIdx.x % G);
     for (int64_t base = beg; base < end; base += G) {
@@ -172,7 +179,7 @@ __device__ __forceinline__ void edge_gather(const SpmmArgs &p, const float *__re
             for (int u = 0; u < U; ++u) {
                 const int j = __shfl(mycol, k + u, G);
                 w[u] = __shfl(myw, k + u, G);
-                if (w[u] != 0.f) vload<4>(x[u], Xc + (int64_t)j * p.ldx);
+                if (w[u] != 0.f && loads) vload<4>(x[u], Xc + (int64_t)j * p.ldx);
                 else {
 #pragma unroll
                     for (int v = 0; v < 4; ++v) x[u][v] = 0.f;
@@ -524,6 +531,84 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcnii_back(const typename R::
             for (int v = 0; v < 4; ++v) o[v] = fmaf(s_alpha, s[v], o[v]);
         }
         vstore<4>(S_out + at, o);
+    }
+}
+
+// ---- the GCN layer's backward past the gate, one launch (gnx_gcn_step_back) ------------------------------------------------------------
+//   dX[r, 0 .. C_in) = (sum_c At[r,c] G'[c, 0 .. C_out)) . Wt        Wt = W^T [C_out, C_in], 1 <= C_out <= C_in
+// At (G' Wt) = (At G') Wt, as in k_spmm_gcnii_back -- and here the reassociation also narrows the gather: the rows of G' are gathered at
+// the OUTPUT width, CG = 16 NTG >= C_out columns (NTG the smallest of 1, 2, 4), by 4 NTG lanes per row, and leave at the input width
+// C_in = 16 NTI, by 4 NTI lanes per row.  The frame at C_in over the transposed structure (p), with two geometries of the one tile:
+//   gather  Tile<NTG>'s lanes, rows per pass and passes (C_out <= 16: one pass fills the 16 rows) over Tile<NTI>'s row stride; the
+//           gathered rows are the tile's first CG columns.  A row of G' is (p.X, p.ldx) with ldx % 4 == 0, ldx >= roundup4(C_out) and a
+//           16-byte aligned base, so every gather is a whole 16-byte load; a lane whose columns start at or beyond roundup4(C_out)
+//           loads nothing, and what a load brings of the columns C_out .. roundup4(C_out) - 1 is SELECTED away behind the loop, not
+//           multiplied by 0: the padding of a row may hold anything, a NaN included.
+//   store   Tile<NTI>'s.  The lane that stores a row is not the lane that gathered it, so the gather leaves each slot's row id -- -1
+//           for a dead slot -- in the slot's first padding column of the tile (column C_in of the stride C_in + 4, which neither the
+//           product nor the walk touches): no second tile and no LDS beyond the forward's.
+// The block's matrix is Wt in LDS as [CG, C_in], its rows from C_out on zero-filled (the padding exists in LDS alone); the product is
+// tile_times_Ms with the k loop over the gathered width (NTK = NTG) and all NTI result blocks in registers.  A row without entries gets
+// dX = 0, written; a slot past n and a hub row write nothing (hub rows: the long-row kernels at width C_out, then the dense kernel on
+// those rows alone).  EDGE / ENTRIES as in k_spmm_gcnii_back (edge_gather over the gather's lane groups).  f32 rows only.
+template <typename R, int NTI, int NTG, int U, int WPB, bool EDGE = false, bool ENTRIES = false>
+__global__ __launch_bounds__(64 * WPB) void k_spmm_gcn_back(const typename R::Args p, const float *__restrict__ Wt, int64_t ldwt, int C_out) {
+    static_assert(!R::BF16, "the GCN layer exists over f32 rows");
+    static_assert(NTG >= 1 && NTG <= NTI, "C_out <= C_in: the gathered rows are the tile's first columns");
+    using TL = Tile<NTI>;
+    using TG = Tile<NTG>;
+    constexpr int C = TL::C, CG = TG::C, STRIDE = TL::STRIDE;
+    __shared__ float Ws[CG * STRIDE];
+    __shared__ float Ts[WPB][16 * STRIDE];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    for (int idx = threadIdx.x; idx < CG * C; idx += 64 * WPB) {
+        const int k = idx / C, n = idx % C;
+        Ws[k * STRIDE + n] = k < C_out ? Wt[(int64_t)k * ldwt + n] : 0.f;
+    }
+    __syncthreads();
+    const int64_t tile = (int64_t)blockIdx.x * WPB + wave;
+    if (tile * 16 >= p.n_rows) return;
+    float *__restrict__ T = Ts[wave];
+    {
+        constexpr int G = TG::G, RPP = TG::RPP, PASSES = TG::PASSES;
+        const int sub = lane % G, c = sub * 4;
+        const bool loads = c < ((C_out + 3) & ~3);
+#pragma unroll
+        for (int ps = 0; ps < PASSES; ++ps) {
+            const int rr = ps * RPP + lane / G;
+            const int64_t slot = tile * 16 + rr;
+            int64_t row = -1;
+            int64_t beg = 0, end = 0;
+            if (slot < p.n_rows) {
+                row = slot_row(p, slot);
+                beg = p.rowptr[row]; end = p.rowptr[row + 1];
+            }
+            const bool live = row >= 0 && end - beg <= p.long_row;
+            float acc[4] = {0.f, 0.f, 0.f, 0.f};
+            if (live) {
+                // (the lanes of a row run edge_gather together, those without columns included: they make weights for the others)
+                if constexpr (EDGE) edge_gather<ENTRIES, G, U>(p, p.X + c, row, beg, end, acc, loads);
+                else if (loads) gathered_row<R, U>(p, row, beg, end, c, acc);
+#pragma unroll
+                for (int v = 0; v < 4; ++v) acc[v] = c + v < C_out ? acc[v] : 0.f;
+            }
+            vstore<4>(T + rr * STRIDE + c, acc);
+            if (sub == 0) T[rr * STRIDE + C] = __int_as_float(live ? (int)row : -1);
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    tile_times_Ms<NTI, false, NTI, NTG>(T, Ws, lane, GNX_ACT_NONE);
+    constexpr int G = TL::G, RPP = TL::RPP, PASSES = TL::PASSES;
+    const int c = (lane % G) * 4;
+#pragma unroll
+    for (int ps = 0; ps < PASSES; ++ps) {
+        const int rr = ps * RPP + lane / G;
+        const int row = __float_as_int(T[rr * STRIDE + C]);
+        if (row < 0) continue;
+        float o[4];
+        vload<4>(o, T + rr * STRIDE + c);
+        vstore<4>(p.out + (int64_t)row * p.ldo + c, o);
     }
 }
 
@@ -1269,6 +1354,92 @@ int gcn_forward(const char *fn, gnx_graph *g, const float *d_vals, const EdgeDro
     return hub_rows_tail<F32Rows>(g, m, p, d_X, T, edge != nullptr, s, transform_rows);
 }
 
+// ---- the GCN layer's backward host path (gnx_gcn_step_back, gnx_gcn_step_back_dropped) ----------------------------------------------------
+// what gnx_graph_last_kernel reports: [C_in = 16, 32, 64][edge dropout][hub rows ran]; the composed form [edge dropout]
+#define GNX_GCN_BACK_NAMES(c) {{"k_spmm_gcn_back<" c ">", "k_spmm_gcn_back<" c ">+long"}, {"k_spmm_gcn_back<" c ">_edrop", "k_spmm_gcn_back<" c ">_edrop+long"}}
+const char *const kGcnBackFused[3][2][2] = {GNX_GCN_BACK_NAMES("16"), GNX_GCN_BACK_NAMES("32"), GNX_GCN_BACK_NAMES("64")};
+const char *const kGcnBackComposed[2] = {"dense+spmm_back_gcn", "dense+spmm_back_gcn_edrop"};
+#undef GNX_GCN_BACK_NAMES
+
+// dX = (At . G') . Wt, At from d_vals_t or made from `edge`.  The fused launch takes C_in = 16, 32 or 64 with C_out <= C_in over rows of
+// G' padded to whole 16-byte pieces (ldg % 4 == 0, ldg >= roundup4(C_out), aligned base) and 16-byte aligned rows of dX; everything
+// else runs today's order inside this call: gnx_dense(G', Wt) into d_work, then the transposed SpMM.  The checks that need no look at
+// the handle come first; nothing is launched before the last check has passed.
+int gcn_backward(const char *fn, gnx_graph *g, const float *d_vals_t, const EdgeDrop *edge, const float *d_G, int64_t ldg, int64_t C_out,
+                 const float *d_Wt, int64_t ldwt, int64_t C_in, float *d_dX, int64_t lddx, float *d_work, int64_t work_floats, void *stream) {
+    GNX_CHECK_ARG(g != nullptr, "%s: NULL handle", fn);
+    GNX_CHECK_ARG(C_in >= 1 && C_in <= (1 << 20) && C_out >= 1 && C_out <= (1 << 20), "%s: widths %lld <- %lld not in [1, 2^20]", fn,
+                  (long long)C_in, (long long)C_out);
+    GNX_CHECK_ARG(d_G != nullptr && d_Wt != nullptr && d_dX != nullptr, "%s: NULL G / Wt / dX", fn);
+    GNX_CHECK_ARG(ldg >= C_out, "%s: ldg %lld < C_out %lld", fn, (long long)ldg, (long long)C_out);
+    GNX_CHECK_ARG(ldwt >= C_in, "%s: ldwt %lld < C_in %lld", fn, (long long)ldwt, (long long)C_in);
+    GNX_CHECK_ARG(lddx >= C_in, "%s: lddx %lld < C_in %lld", fn, (long long)lddx, (long long)C_in);
+    GNX_CHECK_ARG(work_floats >= 0 && (d_work != nullptr || work_floats == 0), "%s: work_floats %lld without d_work, or negative", fn,
+                  (long long)work_floats);
+    const void *D = edge ? edge->D : nullptr;
+    auto input = [&](const void *b) { return b == d_G || b == d_Wt || (d_vals_t && b == d_vals_t) || (D && b == D); };
+    GNX_CHECK_ARG(!input(d_dX), "%s: dX must not alias an input (G / Wt / the values)", fn);
+    GNX_CHECK_ARG(d_work == nullptr || (!input(d_work) && d_work != d_dX), "%s: d_work must be a buffer of its own", fn);
+    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "%s: needs a square graph", fn);
+    if (edge) {
+        const int rc = admit_edge_drop(fn, g, *edge);
+        if (rc != GNX_OK) return rc;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = g->a.n_rows, c4 = (C_out + 3) / 4 * 4;
+    const bool fusable = fused_width(C_in) && C_out <= C_in && ldg % 4 == 0 && ldg >= c4 && aligned(d_G, 16) && lddx % 4 == 0 &&
+                         aligned(d_dX, 16) && aligned(d_work, 16);
+    if (!fusable) {      // the composed order: gT = G' . Wt into d_work, dX = At gT
+        GNX_CHECK_ARG(work_floats >= n * C_in, "%s: needs d_work of n * C_in = %lld floats, has %lld (%s: G' . Wt goes through memory, gnx_dense and the transposed SpMM run as two launches)",
+                      fn, (long long)(n * C_in), (long long)work_floats,
+                      !fused_width(C_in) ? "C_in is not 16, 32 or 64" : C_out > C_in ? "C_out > C_in"
+                      : (ldg % 4 != 0 || ldg < c4) ? "the rows of G' are not padded to whole 16-byte pieces: ldg % 4 != 0 or ldg < roundup4(C_out)"
+                                                   : "misaligned rows");
+        int rc = ensure_transpose(g, s);   // (before the first launch: under capture a part that would have to be built refuses the whole call)
+        if (rc != GNX_OK) return rc;
+        rc = reserve_partial(g, g->t, C_in, s);
+        if (rc != GNX_OK) return rc;
+        rc = gnx_dense(d_G, ldg, n, C_out, d_Wt, ldwt, C_in, nullptr, GNX_ACT_NONE, d_work, C_in, stream);
+        if (rc != GNX_OK) return rc;
+        if (edge) rc = gnx_spmm_dropped(g, edge->D, edge->p, edge->seed, edge->stream, 1, d_work, C_in, C_in, nullptr, 0, 1.f, 0.f, GNX_ACT_NONE, d_dX, lddx, stream);
+        else rc = gnx_spmm_tv(g, d_vals_t ? d_vals_t : g->t_raw.get(), nullptr, d_work, C_in, C_in, nullptr, 0, 1.f, 0.f, GNX_ACT_NONE, d_dX, lddx, stream);
+        if (rc != GNX_OK) return rc;
+        g->last_kernel = kGcnBackComposed[edge ? 1 : 0];
+        return GNX_OK;
+    }
+    int rc = ensure_transpose(g, s);   // (the structure says whether hub rows need d_work; it and the slab before the first launch)
+    if (rc != GNX_OK) return rc;
+    const Csr &m = g->t;
+    GNX_CHECK_ARG(m.n_long == 0 || work_floats >= n * C_out,
+                  "%s: needs d_work of n * C_out = %lld floats, has %lld (the transposed structure has hub rows: their rows of At . G' go through memory)",
+                  fn, (long long)(n * C_out), (long long)work_floats);
+    if (m.n_rows == 0) return GNX_OK;
+    rc = reserve_partial(g, m, C_out, s);
+    if (rc != GNX_OK) return rc;
+    SpmmArgs p{};
+    bind_values(g, edge, true, d_vals_t, p);
+    set_operands<F32Rows>(p, d_G, ldg, nullptr, 0, 1.f, 0.f, GNX_ACT_NONE, d_dX, 0, lddx, C_out);
+    bind_fused(m, p);
+    const int ntg = C_out <= 16 ? 1 : C_out <= 32 ? 2 : 4;
+    with_tile_width(C_in, m.n_rows, [&](auto NTI, dim3 grid) {
+        auto with_gather = [&](auto NTG) {      // (C_out <= C_in: no NTG above NTI; ENTRIES goes with EDGE)
+            with_flags([&](auto EDGE, auto ENTRIES) {
+                if constexpr (NTG() <= NTI() && (EDGE() || !ENTRIES()))
+                    hipLaunchKernelGGL((k_spmm_gcn_back<F32Rows, NTI(), NTG(), 4, 8, EDGE(), ENTRIES()>), grid, dim3(512), 0, s, p, d_Wt, ldwt, (int)C_out);
+            }, edge != nullptr, edge && p.fuse.mult);
+        };
+        if (ntg == 1)      with_gather(IntC<1>{});
+        else if (ntg == 2) with_gather(IntC<2>{});
+        else               with_gather(IntC<4>{});
+    });
+    g->last_kernel = kGcnBackFused[C_in == 16 ? 0 : C_in == 32 ? 1 : 2][edge ? 1 : 0][m.n_long > 0];
+    // hub rows of the transposed structure: chunked partial sums -> At . G' at their row ids of d_work, width C_out -> those rows alone times Wt
+    p.ldo = C_out;
+    return hub_rows_tail<F32Rows>(g, m, p, d_G, d_work, edge != nullptr, s, [&](const int32_t *rows, int64_t k) {
+        return dense_rows(d_work, C_out, k, C_out, d_Wt, ldwt, C_in, nullptr, GNX_ACT_NONE, rows, rows, d_dX, lddx, s);
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1295,6 +1466,18 @@ int gnx_gcn_step_dropped(gnx_graph_t g, const float *d_D, float edge_p, uint64_t
     const EdgeDrop edge{d_D, edge_p, edge_seed, edge_stream};
     return gcn_forward(fn, g, nullptr, &edge, d_X, ldx, C_in, d_W, ldw, C_out, d_bias, act, dropout_p != 0.0 ? &fd : nullptr,
                        GcnOut{d_out, ldo, d_agg, d_work}, stream);
+}
+
+int gnx_gcn_step_back(gnx_graph_t g, const float *d_vals_t, const float *d_G, int64_t ldg, int64_t C_out, const float *d_Wt, int64_t ldwt,
+                      int64_t C_in, float *d_dX, int64_t lddx, float *d_work, int64_t work_floats, void *stream) {
+    return gcn_backward("gnx_gcn_step_back", g, d_vals_t, nullptr, d_G, ldg, C_out, d_Wt, ldwt, C_in, d_dX, lddx, d_work, work_floats, stream);
+}
+
+int gnx_gcn_step_back_dropped(gnx_graph_t g, const float *d_D, float edge_p, uint64_t edge_seed, uint64_t edge_stream, const float *d_G,
+                              int64_t ldg, int64_t C_out, const float *d_Wt, int64_t ldwt, int64_t C_in, float *d_dX, int64_t lddx,
+                              float *d_work, int64_t work_floats, void *stream) {
+    const EdgeDrop edge{d_D, edge_p, edge_seed, edge_stream};
+    return gcn_backward("gnx_gcn_step_back_dropped", g, nullptr, &edge, d_G, ldg, C_out, d_Wt, ldwt, C_in, d_dX, lddx, d_work, work_floats, stream);
 }
 
 int gnx_gcnii_step(gnx_graph_t g, const float *d_vals, const float *d_H, const float *d_H0, float a, int64_t C, const float *d_M,

@@ -132,6 +132,10 @@ SIGNATURES = {
                              c_uint64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "gnx_gcn_step_dropped": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
                                      c_void_p, c_int, c_double, c_uint64, c_uint64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "gnx_gcn_step_back": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p,
+                                  c_int64, c_void_p]),
+    "gnx_gcn_step_back_dropped": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_void_p, c_int64, c_int64, c_void_p, c_int64,
+                                          c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "gnx_dense": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int64,
                           c_void_p]),
     "gnx_dense_wgrad": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),

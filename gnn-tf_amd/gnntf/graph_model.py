@@ -52,7 +52,7 @@ class GNN(Trainable):
     def __init__(self, graph, features, preprocessor: Layer = None, reorder=None, inference_dtype=torch.float32,
                  training_dtype=torch.float32, train_gather_order="auto", gcnii_backward="composed", feature_dropout="torch",
                  gcnii_training_dtype=torch.float32, gcnii_weight_gradient="stored", gcnii_spectral="composed",
-                 gcnii_edge_dropout="composed", gcn_layer="composed"):
+                 gcnii_edge_dropout="composed", gcn_layer="composed", gcn_backward="composed"):
         """``reorder`` (opt-in, not in the reference): store the graph and the feature rows with the vertices relabelled; every
         [N, .] tensor inside the model then lives in that order, and the model's OUTPUT is put back into the caller's order, so
         tasks, labels and node ids are unaffected.  Results agree with the unordered model to float32 rounding.
@@ -175,7 +175,19 @@ class GNN(Trainable):
         width); in ``[64, 64, 64]`` every layer but the first.  The backward is composed from today's kernels.  The result agrees with
         the composed one to float32 rounding.  GCNSpectralPreservingLayer and other subclasses, ``transform_first``, other
         activations, other widths, add_eye, CPU tensors and the vertex-partitioned path keep today's path and bits whatever it says
-        (measurement: profiles/NOTES.md "Fused GCN layer")."""
+        (measurement: profiles/NOTES.md "Fused GCN layer").
+        ``gcn_backward`` (not in the reference): ``"composed"`` (the default: today's calls and bits) or ``"fused"`` (sparse.gcn_step
+        ``backward``).  It acts on the layers that run as the one autograd node of ``gcn_layer="fused"`` and is inert otherwise.
+        ``"fused"``: after the gate, gnx_dense_wgrad and the column sums, the gradient of the layer's input is ONE launch over the
+        transposed structure (gnx_gcn_step_back, under edge dropout gnx_gcn_step_back_dropped) that gathers the gated gradient at the
+        OUTPUT width and multiplies by W^T on the matrix cores -- dX = (A^T G') W^T -- instead of gnx_dense and the transposed SpMM with
+        the [n, C_in] matrix G' W^T written, read back and gathered at the input width.  The forward, dW and db keep their bits; dX
+        agrees to float32 rounding (the products associate differently: why the default stays ``"composed"``; measurement:
+        profiles/NOTES.md "Fused GCN backward").  Such a layer lets its saved A . X go once dW is made, before dX is allocated, so
+        its backward never holds the two side by side; in return it runs its backward once (a second backward over a retained
+        graph raises and asks for a new forward)."""
+        if gcn_backward not in sparse.GCN_BACKWARDS:
+            raise Exception("GNN: gcn_backward must be one of " + ", ".join(repr(b) for b in sparse.GCN_BACKWARDS))
         if gcn_layer not in sparse.GCN_LAYERS:
             raise Exception("GNN: gcn_layer must be one of " + ", ".join(repr(f) for f in sparse.GCN_LAYERS))
         if gcnii_edge_dropout not in sparse.GCNII_EDGE_DROPOUTS:
@@ -207,6 +219,7 @@ class GNN(Trainable):
         self.gcnii_spectral = gcnii_spectral
         self.gcnii_edge_dropout = gcnii_edge_dropout
         self.gcn_layer = gcn_layer
+        self.gcn_backward = gcn_backward
         self._order = self._newid = None
         self.reorder_used, self.locality_share = None, None
         if isinstance(graph, sparse.DeviceGraph):
@@ -478,7 +491,8 @@ class GCNLayer(Layer):
             if getattr(gcn, "feature_dropout", "torch") == "fused" and gcn.is_training() and 0 < self.dropout < 1:
                 triple = (self.dropout,) + tuple(gcn._next_mask_stream())
             out = sparse.gcn_step(adjacency, features, self.W, self.b if isinstance(self.b, torch.Tensor) else None,
-                                  relu=self.activation is relu, dropout=triple, edge_dropout="fused")
+                                  relu=self.activation is relu, dropout=triple, edge_dropout="fused",
+                                  backward=getattr(gcn, "gcn_backward", "composed"))
             return out if triple is not None else gcn.dropout(out, self.dropout)
         if self.transform_first:
             bias = self.b if isinstance(self.b, torch.Tensor) else None

@@ -109,6 +109,19 @@ class DeviceGraph:
         return self._h
 
     @property
+    def n_hub_rows_t(self) -> int:
+        """``n_hub_rows`` of the TRANSPOSED structure: the columns with more than ``long_row_threshold`` entries, which the fused
+        backward launches leave to the long-row kernels.  Counted once from a copy of the column indices and kept (it synchronises:
+        the first use must not be under capture)."""
+        if getattr(self, "_n_hub_rows_t", None) is None:
+            if self.nnz == 0:
+                self._n_hub_rows_t = 0
+            else:
+                counts = torch.bincount(self.csr_arrays()[1].long(), minlength=self.n_cols)
+                self._n_hub_rows_t = int((counts > self.long_row_threshold).sum())
+        return self._n_hub_rows_t
+
+    @property
     def entry_dropout(self) -> bool:
         """Whether enable_entry_dropout() has run on this graph: the fused training kernels then accept its duplicate entries."""
         return getattr(self, "_entry_dropout", False)
@@ -1113,13 +1126,20 @@ def _feature_dropout_launch(graph: DeviceGraph, X, p, seed, stream, rows=None, o
     return out
 
 
-def _gate_launch(graph: DeviceGraph, g, y, p, seed, stream, relu, bf16):
+def _padded_rows(n, C, device):
+    """An uninitialised f32 [n, C] view of rows of stride roundup4(C): every row starts 16-byte aligned and can be read in whole 16-byte
+    pieces (what the fused GCN backward gathers; the padding columns are never written and their content does not matter)."""
+    return torch.empty((n, (C + 3) // 4 * 4), dtype=torch.float32, device=device)[:, :C]
+
+
+def _gate_launch(graph: DeviceGraph, g, y, p, seed, stream, relu, bf16, padded=False):
     """The backward's gate, gnx_feature_dropout_back or (``bf16``: y is the stored bf16 output) gnx_feature_dropout_back_bf16: returns
-    (G, Gb) with G = kept ? g * s : 0 -- with ``relu`` also 0 where ``y`` <= 0 -- and Gb = bf(G), None without ``bf16``."""
+    (G, Gb) with G = kept ? g * s : 0 -- with ``relu`` also 0 where ``y`` <= 0 -- and Gb = bf(G), None without ``bf16``.
+    ``padded``: G is written into rows of stride roundup4(C) (_padded_rows; the pass takes the stride as its ldG)."""
     g = _as_f32_rows(g).contiguous()
     nat.require_cuda(g, y)
     _same_device(graph, g, y)
-    G = torch.empty_like(g)
+    G = _padded_rows(g.shape[0], g.shape[1], g.device) if padded else torch.empty_like(g)
     Gb = torch.empty(g.shape, dtype=torch.bfloat16, device=g.device) if bf16 else None
     if g.numel() == 0:
         return G, Gb
@@ -1134,9 +1154,9 @@ def _gate_launch(graph: DeviceGraph, g, y, p, seed, stream, relu, bf16):
     return G, Gb
 
 
-def _feature_dropout_back(graph: DeviceGraph, g, y, p, seed, stream, relu):
+def _feature_dropout_back(graph: DeviceGraph, g, y, p, seed, stream, relu, padded=False):
     """gnx_feature_dropout_back: G = kept ? g * s : 0, with ``relu`` also 0 where the dropped forward output ``y`` is <= 0."""
-    return _gate_launch(graph, g, y, p, seed, stream, relu, bf16=False)[0]
+    return _gate_launch(graph, g, y, p, seed, stream, relu, bf16=False, padded=padded)[0]
 
 
 class _FeatureDropout(torch.autograd.Function):
@@ -1451,6 +1471,7 @@ def _gcnii_step_dropped(adj, H, H0, a, M, relu, backward, dropout, recompute=Fal
 
 
 GCN_LAYERS = ("composed", "fused")
+GCN_BACKWARDS = ("composed", "fused")
 GCN_FUSED_WIDTHS = (16, 32, 64)       # C_in of the one-launch form of gnx_gcn_step; its C_out is any width up to C_in
 
 
@@ -1491,18 +1512,29 @@ class _GCNStep(torch.autograd.Function):
     """out = drop(act((A . X) . W + b)) as ONE launch that also leaves agg = A . X for the backward (gcn.py:88-89 under
     tf.GradientTape); (agg, W, out) is what is saved.  backward, composed from what exists: g' = g * (out > 0), or with a fused mask
     one pass (gnx_feature_dropout_back); dW = agg^T g' (gnx_dense_wgrad); db = column sums of g'; dX = A^T (g' W^T) -- gnx_dense, then
-    the transposed SpMM, the dropped one under ``fused_edge`` (``adj`` stays a DroppedAdjacency: no value array)."""
+    the transposed SpMM, the dropped one under ``fused_edge`` (``adj`` stays a DroppedAdjacency: no value array).
+    ``backward="fused"``: the gate writes g' into rows of stride roundup4(C_out) and dX = (A^T g') W^T comes from ONE launch that gathers
+    g' at the output width (gcn_step_back); g' W^T is never written.  dW and db read the same g' and keep their bits.  The node then
+    keeps agg itself (``ctx.agg``; (W, out) are what is saved) and lets it go as soon as dW is made, BEFORE dX is allocated: the
+    backward never holds agg beside dX.  The price: such a node runs its backward once -- a second one (``retain_graph=True``) raises
+    and asks for a new forward."""
 
     @staticmethod
-    def forward(ctx, X, W, bias, adj, relu, dropout, fused_edge):
-        ctx.adj, ctx.relu, ctx.dropout = adj, relu, dropout
+    def forward(ctx, X, W, bias, adj, relu, dropout, fused_edge, backward="composed"):
+        ctx.adj, ctx.relu, ctx.dropout, ctx.fused_edge, ctx.fused_backward = adj, relu, dropout, fused_edge, backward == "fused"
         ctx.bias_shape = None if bias is None else tuple(bias.shape)
         out, agg = _gcn_launch(adj, X, W, bias, relu, keep_agg=True, dropout=dropout, fused_edge=fused_edge)
+        if ctx.fused_backward:      # (agg is neither an input nor an output of the node: it may live on ctx, which can let it go early)
+            ctx.agg = agg
+            ctx.save_for_backward(W, out if relu or dropout is not None else None)
+            return out
         ctx.save_for_backward(agg, W, out if relu or dropout is not None else None)
         return out
 
     @staticmethod
     def backward(ctx, g):
+        if ctx.fused_backward:
+            return _gcn_fused_backward(ctx, g) + (None, None, None, None, None)
         agg, W, out = ctx.saved_tensors
         g = _gated_gradient(ctx.adj.graph, g, out, ctx.relu, ctx.dropout)
         gW = _dense_wgrad(agg, g) if ctx.needs_input_grad[1] else None
@@ -1512,7 +1544,95 @@ class _GCNStep(torch.autograd.Function):
             gT = _dense_launch(g, W.t().contiguous(), None, False)
             del g                                           # (the gated gradient is done with: the transposed SpMM runs without it)
             gX = _launch(ctx.adj, gT, None, 1.0, 0.0, nat.ACT_NONE, transposed=True)
-        return gX, gW, gb, None, None, None, None
+        return gX, gW, gb, None, None, None, None, None
+
+
+def _gcn_fused_backward(ctx, g):
+    """(dX, dW, db) of _GCNStep with ``backward="fused"``.  The gated gradient g' has the values of the composed backward's; where dX is
+    wanted it lives in rows of stride roundup4(C_out) (the gate pass writes them there; the relu mask and the ungated gradient take one
+    narrow copy when C_out is no multiple of 4), which gnx_dense_wgrad reads as an [n, C_out] view.  The column sums run over contiguous
+    rows, as the composed backward's do (torch picks its reduction by the strides).  agg = A . X [n, C_in] is released once dW is made,
+    before dX [n, C_in] is allocated."""
+    W, out = ctx.saved_tensors
+    agg, ctx.agg = ctx.agg, None
+    if agg is None:
+        raise Exception("gcn_step(backward=\"fused\"): the node let its aggregated rows go in its first backward; run the forward again "
+                        "(or use backward=\"composed\" where a graph is retained)")
+    want_X = ctx.needs_input_grad[0]
+    want_b = ctx.bias_shape is not None and ctx.needs_input_grad[2]
+    C_out = g.shape[1]
+    padded = want_X and C_out % 4 != 0
+    gb = None
+    if ctx.dropout is not None:
+        G = _feature_dropout_back(ctx.adj.graph, g, out, *ctx.dropout, relu=ctx.relu, padded=padded)
+        if want_b:
+            gb = G.contiguous().sum(dim=0)
+    else:
+        G = (_relu_mask(g, out) if ctx.relu else g).contiguous()
+        if want_b:
+            gb = G.sum(dim=0)
+        if padded:
+            narrow, G = G, _padded_rows(G.shape[0], C_out, G.device)
+            G.copy_(narrow)
+            del narrow
+    gW = _dense_wgrad(agg, G) if ctx.needs_input_grad[1] else None
+    del agg                                                 # (the last reference: the rows are free before dX is made)
+    gX = _gcn_back_launch(ctx.adj, G, W.t().contiguous(), ctx.fused_edge) if want_X else None
+    return gX, gW, None if gb is None else gb.reshape(ctx.bias_shape)
+
+
+def _gcn_back_launch(adj: Adjacency, G, Wt, fused_edge=False):
+    """gnx_gcn_step_back over the gated gradient ``G`` [n, C_out] (f32 rows of any stride) and ``Wt`` = W^T [C_out, C_in], or with
+    ``fused_edge`` (``adj`` is a DroppedAdjacency) gnx_gcn_step_back_dropped: the checks, dX, the work buffer -- [n, C_out] where the one
+    launch applies and the transposed structure has hub rows, [n, C_in] where the entry runs gnx_dense and the transposed SpMM, none
+    otherwise -- and the call.  Returns dX [n, C_in]."""
+    nat.require_cuda(G, Wt)
+    G, Wt = _as_f32_rows(G), _as_f32_rows(Wt)
+    g = adj.graph
+    _same_device(g, G, Wt, adj.D if fused_edge else None)
+    n, C_out = G.shape
+    C_in = Wt.shape[1]
+    if g.n_rows != g.n_cols or n != g.n_rows or Wt.shape[0] != C_out or C_in < 1 or C_out < 1:
+        raise Exception("gcn_step_back: shape mismatch")
+    one_launch = (C_in in GCN_FUSED_WIDTHS and C_out <= C_in and G.stride(0) % 4 == 0 and G.stride(0) >= (C_out + 3) // 4 * 4
+                  and G.data_ptr() % 16 == 0)
+    dX = torch.empty((n, C_in), dtype=torch.float32, device=G.device)
+    if not one_launch:
+        work = torch.empty((n, C_in), dtype=torch.float32, device=G.device)
+    elif g.n_hub_rows_t > 0:
+        work = torch.empty((n, C_out), dtype=torch.float32, device=G.device)
+    else:
+        work = None
+    ldwt = Wt.stride(0) if C_out > 1 else C_in             # (torch calls a one-row matrix contiguous whatever its row stride says)
+    tail = (nat.ptr(G), G.stride(0), C_out, nat.ptr(Wt), ldwt, C_in, nat.ptr(dX), dX.stride(0), nat.ptr(work),
+            0 if work is None else work.numel(), nat.current_stream())
+    with nat.on_device(G.device):
+        if fused_edge:
+            nat.check(nat.lib().gnx_gcn_step_back_dropped(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, *tail))
+        else:
+            nat.check(nat.lib().gnx_gcn_step_back(g.handle, nat.ptr(adj.transposed_values()), *tail))
+    return dX
+
+
+def gcn_step_back(adj: Adjacency, G: torch.Tensor, W: torch.Tensor, edge_dropout="composed") -> torch.Tensor:
+    """The gradient of X of gcn_step past the gate as ONE launch (gnx_gcn_step_back; no autograd): with ``G`` [n, C_out] the gated
+    gradient and ``W`` [C_in, C_out] the layer's weights,  dX = (A^T G) . W^T  -- G is gathered over the transposed structure at the
+    OUTPUT width and G . W^T never reaches memory -- for C_in in {16, 32, 64} and C_out <= C_in.  A ``G`` whose rows are not whole
+    16-byte pieces (C_out no multiple of 4 in contiguous rows) is copied once into padded rows.  Other widths run gnx_dense and the
+    transposed SpMM inside the entry, through a work buffer allocated here.  Hub rows of the transposed structure pass through an
+    [n, C_out] buffer.  ``edge_dropout="fused"`` with a DroppedAdjacency: gnx_gcn_step_back_dropped, the weights of the transposed walk
+    made from the adjacency's (D, p, seed, stream) -- bit for bit the result over the materialised adjacency; a DroppedAdjacency
+    without it uses its materialised transposed values."""
+    fused_edge = _edge_dropout("gcn_step_back", edge_dropout) and isinstance(adj, DroppedAdjacency)
+    G, W = _as_f32_rows(G), _as_f32_rows(W)
+    if G.dim() != 2 or W.dim() != 2 or W.shape[1] != G.shape[1]:
+        raise Exception("gcn_step_back: shape mismatch")
+    C_in, C_out = W.shape
+    if C_in in GCN_FUSED_WIDTHS and C_out <= C_in and (G.stride(0) % 4 != 0 or G.data_ptr() % 16 != 0):
+        padded = _padded_rows(G.shape[0], C_out, G.device)
+        padded.copy_(G)
+        G = padded
+    return _gcn_back_launch(adj, G, W.t().contiguous(), fused_edge)
 
 
 def _gcn_composed(adj, X, W, bias, relu, dropout):
@@ -1530,7 +1650,8 @@ def _gcn_composed(adj, X, W, bias, relu, dropout):
     return torch.nn.functional.dropout(out, p=float(dropout[0]), training=True)
 
 
-def gcn_step(adj: Adjacency, X: torch.Tensor, W: torch.Tensor, bias=None, relu=True, dropout=None, edge_dropout="composed") -> torch.Tensor:
+def gcn_step(adj: Adjacency, X: torch.Tensor, W: torch.Tensor, bias=None, relu=True, dropout=None, edge_dropout="composed",
+             backward="composed") -> torch.Tensor:
     """GCNLayer (gcn.py:77-89) as one launch (gnx_gcn_step; opt-in, GNN(gcn_layer="fused")): drop(act((A . X) . W + bias)) with
     ``X`` [n, C_in], ``W`` [C_in, C_out] and ``bias`` [C_out] / [1, C_out] or None.  For C_in in {16, 32, 64} and C_out <= C_in the
     aggregated rows stay in LDS and meet W on the matrix cores: A . X, which ``spmm`` + ``dense`` write and read back, never reaches
@@ -1539,13 +1660,21 @@ def gcn_step(adj: Adjacency, X: torch.Tensor, W: torch.Tensor, bias=None, relu=T
     generator) over the finished rows, from the same launch.
     Under autograd it is one node that saves (A . X, W, out) -- the launch writes A . X once, for dW -- and returns the gradients of X,
     W and bias from today's kernels: the relu gate (or gnx_feature_dropout_back), gnx_dense_wgrad, the column sums, gnx_dense and
-    the transposed SpMM.  (The fused backward, dX = (A^T G') W^T gathered at the output width, is the follow-up.)
+    the transposed SpMM.
+    ``backward``: ``"composed"`` (the default: those calls, today's bits) or ``"fused"`` (opt-in): the gate writes G' into rows of
+    stride roundup4(C_out) and dX = (A^T G') W^T comes from ONE launch that gathers G' at the output width (gcn_step_back,
+    gnx_gcn_step_back; under ``edge_dropout="fused"`` gnx_gcn_step_back_dropped) -- neither G' W^T [n, C_in] nor gnx_dense appears;
+    out, dW and db keep their bits, dX agrees to float32 rounding (the products associate differently).  It acts under autograd only.
+    The node then lets A . X go once dW is made, before dX is allocated, and therefore runs its backward once: a second backward over
+    a retained graph raises and asks for a new forward.
     ``edge_dropout``: ``"composed"`` (the default) or ``"fused"``: with a DroppedAdjacency the launch makes every entry's weight in
     its gather loop (gnx_gcn_step_dropped) -- out and A . X bit for bit those over the materialised adjacency
     ``normalize(graph, "symmetric", "none", p, seed, stream)`` -- and the backward's transposed SpMM is the dropped one.
     CPU tensors, an adjacency with a diagonal and a DroppedAdjacency without ``edge_dropout="fused"`` run ``spmm`` + ``dense``:
     today's calls and bits."""
     fused_edge = _edge_dropout("gcn_step", edge_dropout)
+    if backward not in GCN_BACKWARDS:
+        raise Exception("gcn_step: backward must be one of " + ", ".join(repr(b) for b in GCN_BACKWARDS))
     tensors = (X, W) if bias is None else (X, W, bias)
     if (not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors) or adj.diag is not None
             or (isinstance(adj, DroppedAdjacency) and not fused_edge)):
@@ -1553,7 +1682,7 @@ def gcn_step(adj: Adjacency, X: torch.Tensor, W: torch.Tensor, bias=None, relu=T
     dropout = _dropout_triple(dropout, "gcn_step")
     fused_edge = fused_edge and isinstance(adj, DroppedAdjacency)
     if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
-        return _GCNStep.apply(X, W, bias, adj, bool(relu), dropout, fused_edge)
+        return _GCNStep.apply(X, W, bias, adj, bool(relu), dropout, fused_edge, backward)
     return _gcn_launch(adj, X, W, bias, bool(relu), keep_agg=False, dropout=dropout, fused_edge=fused_edge)[0]
 
 

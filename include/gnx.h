@@ -64,7 +64,8 @@ const char *gnx_last_error(void);
  * (gnx_gcnii_step_train_bf16, gnx_feature_dropout_back_bf16, gnx_gcnii_step_back_bf16), likewise, and the GCNII weight gradient
  * without stored mixed rows (gnx_gcnii_wgrad, gnx_gcnii_wgrad_bf16, gnx_gcnii_step_drop_bf16, gnx_graph_hub_rows), likewise, and the
  * spectral-preserving GCNII layer in one launch (gnx_gcnii_step_spectral, gnx_gcnii_spectral_back), likewise, and the gather hints of
- * the wide eval launches (gnx_graph_set_gather_hints, gnx_graph_gather_hints, GNX_RESERVE_GATHER_HINTS), likewise. */
+ * the wide eval launches (gnx_graph_set_gather_hints, gnx_graph_gather_hints, GNX_RESERVE_GATHER_HINTS), likewise, and the GCN layer
+ * in one launch (gnx_gcn_step, gnx_gcn_step_dropped) with its input gradient (gnx_gcn_step_back, gnx_gcn_step_back_dropped), likewise. */
 #define GNX_ABI_VERSION 900
 int gnx_version(void);
 
@@ -709,6 +710,43 @@ int gnx_gcn_step_dropped(gnx_graph_t g, const float *d_D, float edge_p, uint64_t
                          int64_t ldx, int64_t C_in, const float *d_W, int64_t ldw, int64_t C_out, const float *d_bias, int act,
                          double dropout_p, uint64_t seed, uint64_t stream_id, float *d_out, int64_t ldo, float *d_agg,
                          float *d_work, void *stream);
+
+/* gnx_gcn_step_back (training, opt-in; added within ABI 0.9 -- probe for the symbols): the gradient of X of gnx_gcn_step past the gate,
+ *   dX[r, 0 .. C_in) = (sum_c A_hat[c][r] G'[c, 0 .. C_out)) . Wt,
+ * G' [n, C_out] (ldg) the gated gradient the caller holds (gnx_dense_wgrad and the column sums read the same array), Wt = W^T given by
+ * the caller as a [C_out, C_in] matrix (ldwt; the entry never transposes), dX [n, C_in] (lddx), d_vals_t the values in transposed
+ * order as gnx_spmm_tv takes them (NULL: the raw values).  A^T (G' Wt) = (A^T G') Wt: for C_in in {16, 32, 64}, 1 <= C_out <= C_in,
+ * ldg % 4 == 0, ldg >= roundup4(C_out), lddx % 4 == 0 and 16-byte aligned G' / dX / d_work it is ONE launch over the rows of at most the
+ * long-row threshold of the transposed structure, and G' is gathered AT THE OUTPUT WIDTH: a row is walked by 4 NTG lanes, 16 NTG the
+ * smallest of 16, 32, 64 that holds C_out (entries in ascending order, four in flight, one fmaf chain: the loop of
+ * gnx_gcnii_step_back), every gather a whole 16-byte load -- the columns C_out .. roundup4(C_out) - 1 of a row of G' must be readable
+ * and their content does not matter (they are selected away, never multiplied: a NaN there stays out of dX) -- and the gathered tile
+ * meets Wt, in LDS with its rows from C_out on zero-filled there and nowhere else, on v_mfma_f32_16x16x4_f32 with k over the gathered
+ * width in ascending order.  The [n, C_in] product G' . Wt is never written or gathered back.  A row without entries gets dX = 0,
+ * written.  Hub rows of the transposed structure go through the long-row kernels at width C_out into d_work, at their row ids
+ * ([n, C_out] contiguous), and the dense kernel transforms those rows alone into d_dX.  At C_out == C_in the result is bit for bit
+ * gnx_gcnii_step_back(a = 0, Mt = Wt, S_out = NULL).
+ * Every other case -- C_in outside {16, 32, 64}, C_out > C_in, ldg % 4 != 0 or ldg < roundup4(C_out), misaligned rows -- runs today's
+ * order inside the call: gnx_dense(G', Wt) into d_work [n, C_in], then gnx_spmm_tv into d_dX; bit for bit those two calls.
+ * d_work / work_floats: NULL (with 0) only where nothing passes through memory -- the one launch on a graph whose transposed structure
+ * has no hub rows; else at least n * C_out floats (the one launch with hub rows) or n * C_in (the composed order).  Too little returns
+ * GNX_ERR_INVALID and names what is needed and why.
+ * Checked before anything is launched (a refused call writes nothing): NULL handle / G' / Wt / dX, the widths, ldg >= C_out,
+ * ldwt >= C_in, lddx >= C_in, work_floats, a square graph; dX aliases no input and d_work is a buffer of its own.  No float atomics:
+ * two calls give the same bits (the one launch does not give the bits of the composed order: the products associate differently).
+ * Capture and reserve rules of gnx_gcnii_step_back (gnx_graph_reserve(C, GNX_RESERVE_TRANSPOSED) before a captured call).
+ * Reports "k_spmm_gcn_back<C_in>" (+ "_edrop" under edge dropout, + "+long" when hub rows ran), the composed order
+ * "dense+spmm_back_gcn" (+ "_edrop").
+ *
+ * gnx_gcn_step_back_dropped: the same under the edge dropout of gnx_spmm_dropped, the weights of the transposed walk made from
+ * (d_D, edge_p, edge_seed, edge_stream) as in gnx_gcnii_step_back_dropped -- bit for bit gnx_gcn_step_back over the transposed values
+ * of the materialised adjacency (skip semantics: finite G'); the composed order runs gnx_spmm_dropped(transposed = 1).  Admission as
+ * gnx_gcnii_step_dropped. */
+int gnx_gcn_step_back(gnx_graph_t g, const float *d_vals_t, const float *d_G, int64_t ldg, int64_t C_out, const float *d_Wt,
+                      int64_t ldwt, int64_t C_in, float *d_dX, int64_t lddx, float *d_work, int64_t work_floats, void *stream);
+int gnx_gcn_step_back_dropped(gnx_graph_t g, const float *d_D, float edge_p, uint64_t edge_seed, uint64_t edge_stream,
+                              const float *d_G, int64_t ldg, int64_t C_out, const float *d_Wt, int64_t ldwt, int64_t C_in,
+                              float *d_dX, int64_t lddx, float *d_work, int64_t work_floats, void *stream);
 
 /* ---- the dense ends of the path (matrix cores) -----------------------------------------------------------------------
  * gnx_dense: out = act(X . W + bias) -- Dense.__forward__ (gnntf/core/nn/layers.py:135-136) and the transform of
