@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("GNX_LIBRARY") or os.path.join(os.path.dirname(_HERE),
 NORM = {"none": 0, "symmetric": 1, "bipartite": 2}
 EYE = {"none": 0, "before": 1, "after": 2}
 ACT_NONE, ACT_RELU, ACT_SKIP_EMPTY = 0, 1, 256
+ACT_LEAKY = 2             # tf.nn.leaky_relu at slope 0.2: gnx_ngcf_step and gnx_ngcf_back_gate only
 HALO_ALL, HALO_PULL, HALO_PUSH = 0, 1, 2
 RESERVE_TRANSPOSED, RESERVE_K_LOOP, RESERVE_TRAIN_GATHER, RESERVE_GATHER_HINTS = 1, 2, 4, 8
 ORD_X, ORD_OUT = 1, 2     # `order` of the _ord training entries: X stored in the handle's gather order / the result written in it
@@ -136,6 +137,11 @@ SIGNATURES = {
                                   c_int64, c_void_p]),
     "gnx_gcn_step_back_dropped": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_void_p, c_int64, c_int64, c_void_p, c_int64,
                                           c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "gnx_ngcf_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                              c_int, c_double, c_uint64, c_uint64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                              c_void_p]),
+    "gnx_ngcf_back_gate": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_double,
+                                   c_uint64, c_uint64, c_void_p, c_void_p, c_int64, c_void_p]),
     "gnx_dense": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int64,
                           c_void_p]),
     "gnx_dense_wgrad": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),

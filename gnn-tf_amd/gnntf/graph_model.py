@@ -52,7 +52,7 @@ class GNN(Trainable):
     def __init__(self, graph, features, preprocessor: Layer = None, reorder=None, inference_dtype=torch.float32,
                  training_dtype=torch.float32, train_gather_order="auto", gcnii_backward="composed", feature_dropout="torch",
                  gcnii_training_dtype=torch.float32, gcnii_weight_gradient="stored", gcnii_spectral="composed",
-                 gcnii_edge_dropout="composed", gcn_layer="composed", gcn_backward="composed"):
+                 gcnii_edge_dropout="composed", gcn_layer="composed", gcn_backward="composed", ngcf_layer="composed"):
         """``reorder`` (opt-in, not in the reference): store the graph and the feature rows with the vertices relabelled; every
         [N, .] tensor inside the model then lives in that order, and the model's OUTPUT is put back into the caller's order, so
         tasks, labels and node ids are unaffected.  Results agree with the unordered model to float32 rounding.
@@ -185,7 +185,19 @@ class GNN(Trainable):
         agrees to float32 rounding (the products associate differently: why the default stays ``"composed"``; measurement:
         profiles/NOTES.md "Fused GCN backward").  Such a layer lets its saved A . X go once dW is made, before dX is allocated, so
         its backward never holds the two side by side; in return it runs its backward once (a second backward over a retained
-        graph raises and asks for a new forward)."""
+        graph raises and asks for a new forward).
+        ``ngcf_layer`` (not in the reference): ``"composed"`` (the default: today's calls and bits) or ``"fused"`` (sparse.ngcf_step).
+        Every layer whose class is NGCFLayer itself -- leaky_relu, relu or the identity, both biases or none, f32 rows on the device,
+        an input width of 16, 32 or 64 that the layer does not widen, an adjacency without a diagonal -- then runs
+        l2_normalize(dropout(act((X * (A . X)) . W1 + b1) + act((A . X) . W2 + b2))) as ONE launch (gnx_ngcf_step) instead of one SpMM, a
+        multiply, two transforms, two activations, an add, the dropout and the normalisation as passes of their own.  In training
+        with 0 < ``dropout`` < 1 the mask leaves the same launch under ``feature_dropout="fused"`` (the counter RNG; a
+        ``_next_mask_stream()`` stream per layer); with torch's dropout the launch stops before the norm and torch's dropout and
+        normalize follow as today.  The backward is one gate pass (gnx_ngcf_back_gate) and today's kernels.  The results agree with
+        the composed layer to float32 rounding.  Subclasses, CPU tensors, bf16 rows, other widths (128, the width of the
+        library_recommendation demo, among them) and the sharded layers keep today's path and bits."""
+        if ngcf_layer not in sparse.NGCF_LAYERS:
+            raise Exception("GNN: ngcf_layer must be one of " + ", ".join(repr(f) for f in sparse.NGCF_LAYERS))
         if gcn_backward not in sparse.GCN_BACKWARDS:
             raise Exception("GNN: gcn_backward must be one of " + ", ".join(repr(b) for b in sparse.GCN_BACKWARDS))
         if gcn_layer not in sparse.GCN_LAYERS:
@@ -220,6 +232,7 @@ class GNN(Trainable):
         self.gcnii_edge_dropout = gcnii_edge_dropout
         self.gcn_layer = gcn_layer
         self.gcn_backward = gcn_backward
+        self.ngcf_layer = ngcf_layer
         self._order = self._newid = None
         self.reorder_used, self.locality_share = None, None
         if isinstance(graph, sparse.DeviceGraph):
@@ -751,7 +764,27 @@ class NGCFLayer(Layer):
         self.adjacency = gcn.get_adjacency(self.node_dropout, add_eye="none", normalized="bipartite")
         return rows, outputs
 
+    def _fused_ngcf(self, gcn, features) -> bool:
+        """Whether GNN(ngcf_layer="fused") applies to this forward (no tensor is read, no mask stream is drawn)."""
+        return (getattr(gcn, "ngcf_layer", "composed") == "fused" and type(self) is NGCFLayer
+                and (self.activation is leaky_relu or self.activation is relu or self.activation is linear)
+                and isinstance(self.b1, torch.Tensor) == isinstance(self.b2, torch.Tensor)
+                and isinstance(features, torch.Tensor) and features.is_cuda and features.dtype == torch.float32
+                and features.shape[1] in sparse.NGCF_FUSED_WIDTHS and self.W1.shape[1] <= features.shape[1]
+                and self.adjacency.diag is None)
+
     def __forward__(self, gcn, features):
+        if self._fused_ngcf(gcn, features):
+            # GNN(ngcf_layer="fused"): the whole layer in one launch; with torch's dropout in training the launch stops before the norm
+            act = "leaky" if self.activation is leaky_relu else "relu" if self.activation is relu else "none"
+            b1, b2 = (self.b1, self.b2) if isinstance(self.b1, torch.Tensor) else (None, None)
+            if not gcn.is_training() or self.dropout == 0:
+                return sparse.ngcf_step(self.adjacency, features, self.W1, b1, self.W2, b2, activation=act)
+            if getattr(gcn, "feature_dropout", "torch") == "fused" and 0 < self.dropout < 1:
+                triple = (self.dropout,) + tuple(gcn._next_mask_stream())
+                return sparse.ngcf_step(self.adjacency, features, self.W1, b1, self.W2, b2, activation=act, dropout=triple)
+            summed = sparse.ngcf_step(self.adjacency, features, self.W1, b1, self.W2, b2, activation=act, normalize=False)
+            return torch.nn.functional.normalize(gcn.dropout(summed, self.dropout), dim=1, eps=1e-12)
         aggregated = sparse.spmm(self.adjacency, features)                       # the propagation kernel
         interaction = self.activation(affine(features * aggregated, self.W1, self.b1))
         message = self.activation(affine(aggregated, self.W2, self.b2))

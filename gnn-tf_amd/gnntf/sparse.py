@@ -1686,6 +1686,161 @@ def gcn_step(adj: Adjacency, X: torch.Tensor, W: torch.Tensor, bias=None, relu=T
     return _gcn_launch(adj, X, W, bias, bool(relu), keep_agg=False, dropout=dropout, fused_edge=fused_edge)[0]
 
 
+NGCF_LAYERS = ("composed", "fused")
+NGCF_FUSED_WIDTHS = (16, 32, 64)      # C_in of the one-launch form of gnx_ngcf_step; its C_out is any width up to C_in
+NGCF_ACTIVATIONS = {"none": nat.ACT_NONE, "relu": nat.ACT_RELU, "leaky": nat.ACT_LEAKY}
+NGCF_SLOPES = {"none": 1.0, "relu": 0.0, "leaky": 0.2}
+
+
+def _ngcf_work_floats(n, C_in, C_out, composed_rows, has_agg):
+    """include/gnx.h, gnx_ngcf_step: the scratch of ``composed_rows`` rows that pass through memory (the hub rows of the one launch,
+    every row otherwise) -- an [n, C_in] share for their aggregated rows where d_agg does not hold them, then their products with X
+    and their first pre-activations as compact rows."""
+    if composed_rows == 0:
+        return 0
+    up4 = lambda x: (x + 3) // 4 * 4
+    return (0 if has_agg else up4(n * C_in)) + up4(composed_rows * C_in) + composed_rows * C_out
+
+
+def _ngcf_launch(adj: Adjacency, X, W1, b1, W2, b2, activation, keep, dropout=None, normalize=True):
+    """gnx_ngcf_step; returns (out, agg, gate, rnorm).  ``keep`` (training): the launch also writes the aggregated rows A . X, the gate
+    words (int32 [n, 2 ceil(C_out / 32)]: the P1 words, then the P2 words; none for the identity) and, with ``normalize``, the rows'
+    reciprocal norms (negative where the clamp acted); all None otherwise.  ``dropout`` = the checked (p, seed, stream) or None."""
+    nat.require_cuda(X, W1, W2, b1, b2)
+    X, W1, W2 = _as_f32_rows(X), _as_f32_rows(W1), _as_f32_rows(W2)
+    g = adj.graph
+    if adj.vals is None and adj.vals_t is not None:
+        raise Exception("ngcf_step: this adjacency only holds transposed-order values")
+    _same_device(g, X, W1, W2, b1, b2, adj.vals)
+    n, C_in = X.shape
+    C_out = W1.shape[1]
+    if g.n_rows != g.n_cols or n != g.n_rows or tuple(W1.shape) != (C_in, C_out) or tuple(W2.shape) != (C_in, C_out) or C_in < 1 or C_out < 1:
+        raise Exception("ngcf_step: shape mismatch")
+    biases = []
+    for b in (b1, b2):
+        b = None if b is None else b.to(torch.float32).reshape(-1).contiguous()
+        if b is not None and b.numel() != C_out:
+            raise Exception("ngcf_step: bias width mismatch")
+        biases.append(b)
+    one_launch = C_in in NGCF_FUSED_WIDTHS and C_out <= C_in and X.stride(0) % 4 == 0 and X.data_ptr() % 16 == 0
+    out = torch.empty((n, C_out), dtype=torch.float32, device=X.device)
+    agg = torch.empty((n, C_in), dtype=torch.float32, device=X.device) if keep else None
+    gated = keep and activation != "none"
+    gate = torch.empty((n, 2 * _gate_words(C_out)), dtype=torch.int32, device=X.device) if gated else None
+    rnorm = torch.empty(n, dtype=torch.float32, device=X.device) if keep and normalize else None
+    floats = _ngcf_work_floats(n, C_in, C_out, g.n_hub_rows if one_launch else n, keep)
+    work = torch.empty(floats, dtype=torch.float32, device=X.device) if floats else None
+    p, seed, stream = _dropout_args(dropout)
+    ldw = lambda W: W.stride(0) if C_in > 1 else C_out     # (torch calls a one-row matrix contiguous whatever its row stride says)
+    with nat.on_device(X.device):
+        nat.check(nat.lib().gnx_ngcf_step(g.handle, nat.ptr(adj.vals), nat.ptr(X), X.stride(0), C_in, nat.ptr(W1), ldw(W1), nat.ptr(W2), ldw(W2),
+                                          C_out, nat.ptr(biases[0]), nat.ptr(biases[1]), NGCF_ACTIVATIONS[activation], p, seed, stream,
+                                          1 if normalize else 0, nat.ptr(out), out.stride(0), nat.ptr(agg), nat.ptr(gate), nat.ptr(rnorm),
+                                          nat.ptr(work), floats, nat.current_stream()))
+    return out, agg, gate, rnorm
+
+
+def _ngcf_back_gate(graph: DeviceGraph, g, y, rnorm, gate, activation, dropout=None):
+    """gnx_ngcf_back_gate: (G1, G2), [n, C_out] views of rows of stride roundup4(C_out) whose padding is zero, from the upstream gradient
+    ``g``, the forward's output ``y``, its reciprocal norms (None: no norm was applied) and gate words, and its dropout triple."""
+    g = _as_f32_rows(g)
+    nat.require_cuda(g, y, rnorm, gate)
+    _same_device(graph, g, y, rnorm, gate)
+    n, C = g.shape
+    if activation != "none" and (gate is None or gate.dtype != torch.int32 or tuple(gate.shape) != (n, 2 * _gate_words(C)) or not gate.is_contiguous()):
+        raise Exception("ngcf_step: the gate words must be a contiguous int32 [n, 2 ceil(C_out / 32)]")
+    if rnorm is not None and (y is None or tuple(y.shape) != (n, C) or rnorm.numel() != n or not rnorm.is_contiguous()):
+        raise Exception("ngcf_step: the reciprocal norms go with the forward's output")
+    y = None if rnorm is None else _as_f32_rows(y)
+    G1, G2 = _padded_rows(n, C, g.device), _padded_rows(n, C, g.device)
+    p, seed, stream = _dropout_args(dropout)
+    with nat.on_device(g.device):
+        nat.check(nat.lib().gnx_ngcf_back_gate(graph.handle, nat.ptr(g), g.stride(0), nat.ptr(y), 0 if y is None else y.stride(0), nat.ptr(rnorm),
+                                               nat.ptr(gate) if activation != "none" else None, n, C, NGCF_ACTIVATIONS[activation], p, seed, stream,
+                                               nat.ptr(G1), nat.ptr(G2), G1.stride(0), nat.current_stream()))
+    return G1, G2
+
+
+class _NGCFStep(torch.autograd.Function):
+    """out = l2_normalize(drop(act((X * A) . W1 + b1) + act(A . W2 + b2))), A = A_hat . X, as ONE launch (gnx_ngcf_step) that leaves A,
+    two gate bits per element (P1 > 0, P2 > 0) and the rows' reciprocal norms; (A, gate, rnorm, out, W1, W2) and the input X are what
+    is saved.  backward, composed from today's kernels around one gate pass (gnx_ngcf_back_gate -> G1, G2): db = the column sums,
+    dW1 = (X * A)^T G1 and dW2 = A^T G2 (gnx_dense_wgrad), Q1 = G1 W1^T and Q2 = G2 W2^T (gnx_dense), dA = Q1 * X + Q2 and
+    dX = Q1 * A + A_hat^T dA (the transposed SpMM); the elementwise products in torch."""
+
+    @staticmethod
+    def forward(ctx, X, W1, b1, W2, b2, adj, activation, dropout, normalize):
+        ctx.adj, ctx.activation, ctx.dropout = adj, activation, dropout
+        ctx.bias_shapes = tuple(None if b is None else tuple(b.shape) for b in (b1, b2))
+        out, agg, gate, rnorm = _ngcf_launch(adj, X, W1, b1, W2, b2, activation, keep=True, dropout=dropout, normalize=normalize)
+        ctx.save_for_backward(X, agg, gate, rnorm, out if normalize else None, W1, W2)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        X, A, gate, rnorm, out, W1, W2 = ctx.saved_tensors
+        X = _as_f32_rows(X)
+        G1, G2 = _ngcf_back_gate(ctx.adj.graph, g, out, rnorm, gate, ctx.activation, ctx.dropout)
+        need = ctx.needs_input_grad
+        gb1 = G1.contiguous().sum(dim=0).reshape(ctx.bias_shapes[0]) if ctx.bias_shapes[0] is not None and need[2] else None
+        gb2 = G2.contiguous().sum(dim=0).reshape(ctx.bias_shapes[1]) if ctx.bias_shapes[1] is not None and need[4] else None
+        gW1 = _dense_wgrad(X * A, G1) if need[1] else None
+        gW2 = _dense_wgrad(A, G2) if need[3] else None
+        gX = None
+        if need[0]:
+            Q1 = _dense_launch(G1, W1.t().contiguous(), None, False)
+            Q2 = _dense_launch(G2, W2.t().contiguous(), None, False)
+            del G1, G2
+            dA = torch.addcmul(Q2, Q1, X)                   # Q1 * X + Q2
+            del Q2
+            gX = torch.addcmul(_launch(ctx.adj, dA, None, 1.0, 0.0, nat.ACT_NONE, transposed=True), Q1, A)
+        return gX, gW1, gb1, gW2, gb2, None, None, None, None
+
+
+def _ngcf_act(x, activation):
+    if activation == "leaky":
+        return torch.nn.functional.leaky_relu(x, 0.2)
+    return torch.relu(x) if activation == "relu" else x
+
+
+def _ngcf_composed(adj, X, W1, b1, W2, b2, activation, dropout, normalize):
+    """The layer as today's ops: spmm, a torch multiply, two transforms (the dense kernel on the device), torch's activations and sum,
+    the mask as a pass of its own (torch's dropout on CPU tensors), torch's normalize."""
+    agg = spmm(adj, X)
+    if agg.is_cuda:
+        P1, P2 = dense(X * agg, W1, b1, False), dense(agg, W2, b2, False)
+    else:
+        P1 = torch.matmul(X * agg, W1) + (b1 if b1 is not None else 0)
+        P2 = torch.matmul(agg, W2) + (b2 if b2 is not None else 0)
+    u = _ngcf_act(P1, activation) + _ngcf_act(P2, activation)
+    if dropout is not None and float(dropout[0]) != 0:
+        u = feature_dropout(adj.graph, u, *dropout) if u.is_cuda else torch.nn.functional.dropout(u, p=float(dropout[0]), training=True)
+    return torch.nn.functional.normalize(u, dim=1, eps=1e-12) if normalize else u
+
+
+def ngcf_step(adj: Adjacency, X: torch.Tensor, W1: torch.Tensor, b1, W2: torch.Tensor, b2, activation="leaky", dropout=None,
+              normalize=True) -> torch.Tensor:
+    """NGCFLayer (gcn.py:116-135) as one launch (gnx_ngcf_step; opt-in, GNN(ngcf_layer="fused")):
+    l2_normalize(drop(act((X * (A . X)) . W1 + b1) + act((A . X) . W2 + b2))) with ``X`` [n, C_in], ``W1`` / ``W2`` [C_in, C_out], ``b1`` /
+    ``b2`` [C_out] / [1, C_out] or None and ``activation`` ``"leaky"`` (tf.nn.leaky_relu's slope 0.2), ``"relu"`` or ``"none"``.  For
+    C_in in {16, 32, 64} and C_out <= C_in the aggregated rows stay in LDS, meet W2 and -- multiplied in place by the row's own X -- W1
+    on the matrix cores, and leave masked and normalised; other widths run the SpMM, the dense kernel and the row passes inside the call.
+    ``dropout`` = ``(p, seed, stream)`` or None: the mask of ``feature_dropout`` (the counter RNG, not torch's generator), applied
+    before the norm in the same launch.  ``normalize=False`` stops before the norm (what a caller with torch's dropout needs).
+    Under autograd it is one node that saves (A . X, the gate bits, the reciprocal norms, out, W1, W2) beside its input X; the backward
+    is one gate pass (gnx_ngcf_back_gate) and today's kernels: the column sums, gnx_dense_wgrad, gnx_dense and the transposed SpMM.
+    CPU tensors, an adjacency with a diagonal and a DroppedAdjacency run today's ops."""
+    if activation not in NGCF_ACTIVATIONS:
+        raise Exception("ngcf_step: activation must be one of " + ", ".join(repr(a) for a in NGCF_ACTIVATIONS))
+    tensors = tuple(t for t in (X, W1, b1, W2, b2) if t is not None)
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors) or adj.diag is not None or isinstance(adj, DroppedAdjacency):
+        return _ngcf_composed(adj, X, W1, b1, W2, b2, activation, dropout, bool(normalize))
+    dropout = _dropout_triple(dropout, "ngcf_step")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        return _NGCFStep.apply(X, W1, b1, W2, b2, adj, activation, dropout, bool(normalize))
+    return _ngcf_launch(adj, X, W1, b1, W2, b2, activation, keep=False, dropout=dropout, normalize=bool(normalize))[0]
+
+
 GCNII_SPECTRALS = ("composed", "fused")
 
 

@@ -39,6 +39,9 @@ enum { GNX_NORM_NONE = 0, GNX_NORM_SYMMETRIC = 1, GNX_NORM_BIPARTITE = 2 };
 enum { GNX_EYE_NONE = 0, GNX_EYE_BEFORE = 1, GNX_EYE_AFTER = 2 };
 /* epilogue activation: identity (filter.py:8 default) or relu (gcn.py:78 default) */
 enum { GNX_ACT_NONE = 0, GNX_ACT_RELU = 1 };
+/* tf.nn.leaky_relu at its default slope, v > 0 ? v : 0.2f * v (gcn.py:119): accepted by gnx_ngcf_step and gnx_ngcf_back_gate ONLY;
+ * every other entry refuses it as an invalid activation */
+enum { GNX_ACT_LEAKY = 2 };
 /* flag OR'ed into `act` of gnx_spmm / gnx_spmm_rows: rows without stored entries are NOT written (their output would be
  * alpha * H0[row], which is what an earlier iteration of a propagation loop already left there) -- and cost nothing: the kernels
  * that walk the rows in degree-binned order do not launch their slots at all, the one-wave-per-row kernels walk the ascending
@@ -65,7 +68,8 @@ const char *gnx_last_error(void);
  * without stored mixed rows (gnx_gcnii_wgrad, gnx_gcnii_wgrad_bf16, gnx_gcnii_step_drop_bf16, gnx_graph_hub_rows), likewise, and the
  * spectral-preserving GCNII layer in one launch (gnx_gcnii_step_spectral, gnx_gcnii_spectral_back), likewise, and the gather hints of
  * the wide eval launches (gnx_graph_set_gather_hints, gnx_graph_gather_hints, GNX_RESERVE_GATHER_HINTS), likewise, and the GCN layer
- * in one launch (gnx_gcn_step, gnx_gcn_step_dropped) with its input gradient (gnx_gcn_step_back, gnx_gcn_step_back_dropped), likewise. */
+ * in one launch (gnx_gcn_step, gnx_gcn_step_dropped) with its input gradient (gnx_gcn_step_back, gnx_gcn_step_back_dropped), likewise,
+ * and the NGCF layer in one launch with its backward's gate (gnx_ngcf_step, gnx_ngcf_back_gate, GNX_ACT_LEAKY), likewise. */
 #define GNX_ABI_VERSION 900
 int gnx_version(void);
 
@@ -747,6 +751,66 @@ int gnx_gcn_step_back(gnx_graph_t g, const float *d_vals_t, const float *d_G, in
 int gnx_gcn_step_back_dropped(gnx_graph_t g, const float *d_D, float edge_p, uint64_t edge_seed, uint64_t edge_stream,
                               const float *d_G, int64_t ldg, int64_t C_out, const float *d_Wt, int64_t ldwt, int64_t C_in,
                               float *d_dX, int64_t lddx, float *d_work, int64_t work_floats, void *stream);
+
+/* ---- the NGCF layer in one launch (opt-in; added within ABI 0.9 -- probe for the symbols) ------------------------------
+ * NGCFLayer.__forward__ (gcn.py:116-135), A_hat the bipartite-normalised adjacency the caller built once:
+ *   A = A_hat . X      P1 = (X * A) . W1 + b1      P2 = A . W2 + b2      u = act(P1) + act(P2)      out = l2_normalize(drop(u))
+ * X [n, C_in] (ldx), W1 and W2 [C_in, C_out] (ldw1, ldw2), b1 and b2 [C_out] or NULL (each on its own), out [n, C_out] (ldo), all f32;
+ * act GNX_ACT_NONE, GNX_ACT_RELU or GNX_ACT_LEAKY; normalize 0 or 1 (0: out = drop(u)).  d_vals as in gnx_spmm.
+ *
+ * gnx_ngcf_step: for C_in in {16, 32, 64}, 1 <= C_out <= C_in, ldx % 4 == 0 and 16-byte aligned X / d_agg / d_work it is ONE launch
+ * over the rows of at most the long-row threshold: a wave gathers a 16-row tile into LDS exactly as gnx_gcn_step does (d_agg, when
+ * given, is bit for bit gnx_gcn_step's d_agg); tile . W2 runs on v_mfma_f32_16x16x4_f32 with + b2 and the activation applied as the
+ * accumulator leaves the matrix cores, and that term STAYS in the accumulator registers; each lane multiplies its four columns of
+ * the tile in place by the row's own X[row, c .. c + 3]; tile . W1 runs, + b1, the activation, and act(P1) + act(P2) -- one f32 add
+ * per element -- goes back through the same tile (one tile per wave).  Both weights sit in LDS, zero-padded to a multiple of 16
+ * columns there and nowhere else.
+ * Rounding points: A as in gnx_gcn_step; X * A one multiply; each P the f32 MFMA sum over k ascending, then + bias; the activation
+ * (leaky: one multiply by 0.2f where P <= 0); one add; the mask (x * scale); with normalize the row's sum of squares over the
+ * columns below C_out -- per lane one fmaf chain over its four columns ascending from 0, then the row's 4, 8 or 16 lanes added
+ * through xor-shuffles at strides 1, 2, 4, 8 --, r = 1 / sqrt(max(sum, 1e-12f)) with the IEEE square root and division (each
+ * correctly rounded), and out = x * r.
+ * d_gate (uint32_t [n, 2 * ceil(C_out / 32)] contiguous; written for GNX_ACT_RELU and GNX_ACT_LEAKY, may be NULL): per row first the
+ * ceil(C_out / 32) words of P1, then those of P2; bit c & 31 of word c >> 5 = (P[row, c] > 0), taken from the biased
+ * pre-activation itself.  Bits beyond C_out are 0.
+ * d_rnorm (float [n], only with normalize, may be NULL): r of the row, NEGATED where the clamp acted (sum < 1e-12f: r = -1e6f) --
+ * the sign is how gnx_ngcf_back_gate tells the two derivatives apart; |d_rnorm| is the factor either way.
+ * (dropout_p, seed, stream_id): the feature mask of gnx_gcn_step, applied to u before the norm.  d_agg, d_gate and d_rnorm do not
+ * change a bit of out.  Nothing is written past column C_out - 1 of any row of out (whole 16-byte stores where ldo % 4 == 0 and out
+ * is 16-byte aligned, single values otherwise).
+ * Hub rows take the long-row kernels of gnx_spmm into d_agg, else into the first roundup4(n * C_in) floats of d_work, at their row
+ * ids; on those rows alone the call then runs a product pass (X * A into compact rows), the dense kernel twice without activation,
+ * and a row pass that runs the store loop's own code (activations, sum, gate words, mask, norm).  Every other case -- C_in outside
+ * {16, 32, 64}, C_out > C_in, misaligned rows -- runs gnx_spmm and the same composition over all rows inside the call.
+ * d_work / work_floats: with k = the handle's hub rows (gnx_graph_hub_rows) on the fused widths, k = n in the composed form,
+ *     work_floats >= (k > 0 ? (d_agg ? 0 : roundup4(n * C_in)) + roundup4(k * C_in) + k * C_out : 0)
+ * -- beyond gnx_gcn_step's [n, C_in] share the scratch of the fused widths grows with the hub rows, not with n.  NULL with 0 where
+ * the formula gives 0.  Too little is refused and the message names the figure.
+ * Checked before anything is launched (a refused call writes nothing): the checks of gnx_gcn_step, and W2 / ldw2, normalize in
+ * {0, 1}, d_rnorm only with normalize, work_floats; out, d_agg, d_gate, d_rnorm and d_work are buffers of their own.  Stream-ordered;
+ * no float atomics; under capture the long-row slab must already cover C_in (gnx_graph_reserve), as for gnx_gcn_step.
+ * Reports "k_spmm_ngcf<C_in>" (+ "_drop" with a mask, + "_norm" with normalize, + "+long" when hub rows ran), the composed form
+ * "spmm+dense_mfma_ngcf" with the same suffixes.
+ *
+ * gnx_ngcf_back_gate: the backward's first pass, elementwise with one row reduction.  g [n_rows, C_out] (ldg) the gradient of out,
+ * y (ldy) the forward's out, d_rnorm and d_gate what the forward wrote:
+ *   g_s = r (g - y (y . g))   where d_rnorm[row] = r > 0
+ *   g_s = |r| g               where d_rnorm[row] < 0 (the clamp acted: out = 1e6f x there)
+ *   g_s = g                   with d_rnorm == NULL: no normalisation was applied (d_y may then be NULL)
+ *   g_u = kept ? g_s * scale : +0          the forward's mask made again from (dropout_p, seed, stream_id, the handle's counter)
+ *   G1  = bit1 ? g_u : g_u * slope         G2 likewise with bit2; slope = 0.2f (LEAKY), 0 (RELU); GNX_ACT_NONE: G1 = G2 = g_u and
+ *                                          d_gate is not looked at
+ * G1 and G2 [n_rows, C_out] are written at row stride ldG; the columns C_out .. min(ldG, roundup4(C_out)) - 1 are written as zeros,
+ * so that rows of stride roundup4(C_out) are whole 16-byte pieces for gnx_dense_wgrad, gnx_dense and the column sums.  y . g is
+ * summed per lane as one fmaf chain (16 lanes per row, lane l the columns 4 l .. 4 l + 3 of every 64), then through xor-shuffles: no
+ * float atomics, two calls give the same bits.  G1 and G2 are buffers of their own.  Reports nothing. */
+int gnx_ngcf_step(gnx_graph_t g, const float *d_vals, const float *d_X, int64_t ldx, int64_t C_in, const float *d_W1, int64_t ldw1,
+                  const float *d_W2, int64_t ldw2, int64_t C_out, const float *d_b1, const float *d_b2, int act, double dropout_p,
+                  uint64_t seed, uint64_t stream_id, int normalize, float *d_out, int64_t ldo, float *d_agg, uint32_t *d_gate,
+                  float *d_rnorm, float *d_work, int64_t work_floats, void *stream);
+int gnx_ngcf_back_gate(gnx_graph_t g, const float *d_g, int64_t ldg, const float *d_y, int64_t ldy, const float *d_rnorm,
+                       const uint32_t *d_gate, int64_t n_rows, int64_t C_out, int act, double dropout_p, uint64_t seed,
+                       uint64_t stream_id, float *d_G1, float *d_G2, int64_t ldG, void *stream);
 
 /* ---- the dense ends of the path (matrix cores) -----------------------------------------------------------------------
  * gnx_dense: out = act(X . W + bias) -- Dense.__forward__ (gnntf/core/nn/layers.py:135-136) and the transform of
