@@ -152,6 +152,13 @@ SIGNATURES = {
     "gnx_edge_scores": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "gnx_edge_scores_backward": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                          c_void_p]),
+    "gnx_sample_negatives": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_uint64, c_uint64, c_void_p, c_void_p,
+                                     c_void_p]),
+    "gnx_edge_plan_bytes": (c_int64, [c_int64]),
+    "gnx_edge_plan": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "gnx_edge_sorted_work_floats": (c_int64, [c_int64, c_int64]),
+    "gnx_edge_scores_backward_sorted": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                                c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "gnx_linear_combination": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "gnx_stream_read": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "gnx_stream_copy": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

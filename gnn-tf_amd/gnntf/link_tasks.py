@@ -65,27 +65,89 @@ class negative_sampling:
         return self.edges, self.labels
 
 
-def _edge_logits(features, edges, r):
+class device_negative_sampling:
+    """negative_sampling on the device (graph_predictor.py:52-98; the layout and the acceptance rule are the reference's, the draws are
+    this build's counter RNG): the positive pairs, the candidates, the labels and ONE [m (1 + samples), 2] edge buffer live on the
+    device of ``model``; each call takes the model's next mask stream and fills the buffer with one launch of gnx_sample_negatives
+    over ``model.graph`` -- no host loop, no upload, and a call records into a device graph (train(capture=True)).  A slot whose
+    ``max_tries`` draws were all rejected keeps its last draw; ``fallbacks()`` counts those (it synchronises: not for the loop).
+    ``negative_nodes``: the candidate ids (default: every node).  The reference's ``pool`` stays with the host sampler."""
+
+    def __init__(self, positive_edges, model, samples=1, negative_nodes=None, max_tries=32):
+        graph = model.graph
+        if int(samples) < 1 or int(max_tries) < 1:
+            raise Exception("device_negative_sampling: samples and max_tries must be at least 1")
+        self.model, self.graph, self.samples, self.max_tries = model, graph, int(samples), int(max_tries)
+        self.positive_edges = sparse.DeviceIndex(positive_edges, graph.device, graph.n_rows, "edge endpoint").tensor.reshape(-1, 2)
+        self.negative_nodes = None if negative_nodes is None else \
+            sparse.DeviceIndex(negative_nodes, graph.device, graph.n_rows, "candidate node").tensor.reshape(-1)
+        m = self.positive_edges.shape[0]
+        self.labels = torch.tensor([1.] + [0.] * self.samples, dtype=torch.float32, device=graph.device).repeat(m)
+        # no upper bound on the index: the embedding rows it is scored against may outnumber the graph's (NGCF stacks its layers' rows)
+        self.edges = sparse.DeviceIndex(torch.full((m * (1 + self.samples), 2), -1, dtype=torch.int64, device=graph.device), graph.device,
+                                        fixed=False)
+        self._fallbacks = torch.zeros(1, dtype=torch.int64, device=graph.device)
+        self()
+
+    def __call__(self):
+        seed, stream = self.model._next_mask_stream()
+        sparse.sample_negatives(self.graph, self.positive_edges, self.samples, self.negative_nodes, seed, stream, out=self.edges.tensor,
+                                max_tries=self.max_tries, fallbacks=self._fallbacks)
+        return self.edges, self.labels
+
+    def fallbacks(self) -> int:
+        return int(self._fallbacks.item())
+
+
+def _on_device(edges) -> bool:
+    return isinstance(edges, sparse.DeviceIndex) or (isinstance(edges, torch.Tensor) and edges.is_cuda)
+
+
+def _edge_logits(features, edges, r, backward="atomic"):
     if features.is_cuda:
-        return sparse.edge_scores(features, edges, r)
+        return sparse.edge_scores(features, edges, r, backward=backward)
     e = torch.as_tensor(np.asarray(edges), dtype=torch.int64)
     prod = features[e[:, 0]] * features[e[:, 1]]
     return prod.sum(dim=1) if r is None else (prod @ r).reshape(-1)
 
 
+def _as_labels(labels):
+    if labels is None:
+        return None
+    if isinstance(labels, torch.Tensor) and labels.is_cuda:             # a device sampler's labels stay where they are
+        return labels.to(torch.float32).reshape(-1, 1)
+    return np.asarray(labels, dtype=np.float32).reshape(-1, 1)
+
+
 class LinkPrediction(Predictor):
     """graph_predictor.py:101-151.  ``edges`` is an [m, 2] array or a sampler (called again before every use);
     ``similarity`` "dot" or "cos"; ``loss`` "diff" (pairwise: -mean log sigmoid(logit_even - logit_odd), for samplers with one
-    negative per positive) or anything else for binary cross entropy on the labels; ``gnn``: adds the shared DistMult weights."""
+    negative per positive) or anything else for binary cross entropy on the labels; ``gnn``: adds the shared DistMult weights.
+    ``edges`` may also live on the device -- a device_negative_sampling, a sparse.DeviceIndex or a device tensor -- and then stays
+    there: nothing is uploaded per call, which is what train(capture=True) needs.  ``edge_backward``: how the gradient of the edge
+    logits is summed into the embedding rows (sparse.edge_scores): "atomic" or "sorted" (fixed order: a step repeats bit for bit);
+    default "sorted" for a device_negative_sampling and "atomic" for everything else."""
 
-    def __init__(self, edges, labels=None, gnn=None, similarity="dot", loss="diff", regularize=0, batch_size=float('inf')):
+    def __init__(self, edges, labels=None, gnn=None, similarity="dot", loss="diff", regularize=0, batch_size=float('inf'),
+                 edge_backward=None):
+        if edge_backward is None:
+            edge_backward = "sorted" if isinstance(edges, device_negative_sampling) else "atomic"
+        if edge_backward not in ("atomic", "sorted"):
+            raise Exception('LinkPrediction: edge_backward must be "atomic" or "sorted"')
+        self.edge_backward = edge_backward
         self.edge_sampler = edges if callable(edges) else None
         if self.edge_sampler is not None:
             edges, labels = self.edge_sampler()
         self.batch_size = batch_size
-        self.edges = np.array(edges)
+        if _on_device(edges):
+            if batch_size != float('inf'):
+                raise Exception("LinkPrediction: batch_size subsamples the edge list with the host's `random`, which edges kept on "
+                                "the device (device_negative_sampling, DeviceIndex, device tensor) cannot follow: leave it infinite")
+            self.edges = edges if isinstance(edges, sparse.DeviceIndex) else sparse.DeviceIndex(edges.reshape(-1, 2), edges.device, fixed=False)
+        else:
+            self.edges = np.array(edges)
         self.loss_func = loss
-        self.labels = None if labels is None else np.asarray(labels, dtype=np.float32).reshape(-1, 1)
+        self.labels = _as_labels(labels)
         self.r = None if gnn is None else gnn.create_var(shape=(gnn.top_shape()[1], 1), regularize=0, shared_name="distmult",
                                                           normalization="ones", trainable=True)
         self.similarity = similarity
@@ -95,14 +157,14 @@ class LinkPrediction(Predictor):
         if self.edge_sampler is not None:
             edges, labels = self.edge_sampler()
             self.edges = edges
-            self.labels = None if labels is None else np.asarray(labels, dtype=np.float32).reshape(-1, 1)
+            self.labels = _as_labels(labels)
 
     def _embed(self, features):
         return torch.nn.functional.normalize(features, dim=1, eps=1e-12) if self.similarity == "cos" else features
 
     def predict(self, features, to_logits=False):
         self._update_labels()
-        logits = _edge_logits(self._embed(features), self.edges, self.r)
+        logits = _edge_logits(self._embed(features), self.edges, self.r, self.edge_backward)
         return logits if to_logits else torch.sigmoid(logits)
 
     def loss(self, features):
@@ -113,9 +175,9 @@ class LinkPrediction(Predictor):
             take = min(self.batch_size, len(edges))
             if take != len(edges):
                 edges = edges[random.sample(range(len(edges)), take), :]
-            logits = _edge_logits(features, edges, self.r)
+            logits = _edge_logits(features, edges, self.r, self.edge_backward)
             return -torch.nn.functional.logsigmoid(logits[0::2] - logits[1::2]).mean()
-        logits = _edge_logits(features, self.edges, self.r)
+        logits = _edge_logits(features, self.edges, self.r, self.edge_backward)
         target = torch.as_tensor(self.labels, dtype=torch.float32, device=logits.device).reshape(-1)
         return torch.nn.functional.binary_cross_entropy_with_logits(logits, target)
 

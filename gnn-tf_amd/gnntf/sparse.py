@@ -2162,7 +2162,9 @@ class DeviceIndex:
     The kernels themselves never dereference an out-of-range id (NaN / -1 instead); device tensors handed in directly skip the
     host check."""
 
-    def __init__(self, values, device, upper=None, what="node id"):
+    def __init__(self, values, device, upper=None, what="node id", fixed=True):
+        """``fixed=False``: the tensor is a buffer that its owner rewrites between uses (device_negative_sampling); nothing derived
+        from its contents -- the plan of the sorted edge-score backward -- is then kept."""
         if isinstance(values, torch.Tensor):
             self.tensor = values.to(device=device, dtype=torch.int64).contiguous()
         else:
@@ -2170,7 +2172,11 @@ class DeviceIndex:
             if upper is not None and host.size and (int(host.min()) < 0 or int(host.max()) >= upper):
                 raise Exception(f"{what} out of range [0, {upper})")
             self.tensor = torch.from_numpy(host).to(device)
-        self.upper = upper
+        self.upper, self.fixed = upper, bool(fixed)
+        self._edge_plan = None                  # (n_rows, EdgePlan) of a fixed edge list: edge_scores(backward="sorted") sorts it once
+
+    def __len__(self):
+        return self.tensor.shape[0]
 
 
 def _as_index(x, device, upper, what):
@@ -2317,8 +2323,104 @@ class _EdgeScores(torch.autograd.Function):
         return gF, None, gr
 
 
-def edge_scores(F: torch.Tensor, edges, r=None) -> torch.Tensor:
-    """Logits of the listed edges ([m, 2] node ids): <F[u], F[v]> or, with DistMult weights r [C, 1], <F[u] * F[v], r>."""
+class EdgePlan:
+    """gnx_edge_plan of one [m, 2] edge list over ``n_rows`` nodes: the positions of the flattened list stably sorted by the node they
+    name (keys, pos) and the sorted index at which every chunk of 256 positions of a node begins (chunks[0] = their number)."""
+
+    _bytes = dict()                             # gnx_edge_plan_bytes by m (a host query; the same for every list of that length)
+
+    def __init__(self, edges: torch.Tensor, n_rows: int):
+        m = edges.shape[0]
+        self.m, self.n_rows = m, int(n_rows)
+        self.keys = torch.empty(2 * m, dtype=torch.int32, device=edges.device)              # uint32 in the library
+        self.pos = torch.empty(2 * m, dtype=torch.int32, device=edges.device)
+        self.chunks = torch.empty(2 * m + 1, dtype=torch.int32, device=edges.device)
+        with nat.on_device(edges.device):
+            if m not in EdgePlan._bytes:
+                EdgePlan._bytes[m] = int(nat.lib().gnx_edge_plan_bytes(m))
+                if EdgePlan._bytes[m] < 0:
+                    del EdgePlan._bytes[m]
+                    nat.check(-1)
+            workspace = torch.empty(max(EdgePlan._bytes[m], 16), dtype=torch.uint8, device=edges.device)
+            nat.check(nat.lib().gnx_edge_plan(nat.ptr(edges), m, self.n_rows, nat.ptr(self.keys), nat.ptr(self.pos), nat.ptr(self.chunks),
+                                              nat.ptr(workspace), workspace.numel(), nat.current_stream()))
+
+
+def _edge_plan_of(index, edges: torch.Tensor, n_rows: int) -> EdgePlan:
+    """The plan of ``edges``: kept on ``index`` when that is a DeviceIndex over a fixed list, built anew otherwise."""
+    if not (isinstance(index, DeviceIndex) and index.fixed):
+        return EdgePlan(edges, n_rows)
+    if index._edge_plan is None or index._edge_plan[0] != n_rows:
+        index._edge_plan = (n_rows, EdgePlan(edges, n_rows))
+    return index._edge_plan[1]
+
+
+class _EdgeScoresSorted(torch.autograd.Function):
+    """_EdgeScores with the backward of gnx_edge_scores_backward_sorted: every row of dF is summed in the fixed order of the plan
+    (made in the forward), so two runs give the same bits."""
+
+    @staticmethod
+    def forward(ctx, F, edges, r, index):
+        out = _EdgeScores.forward(ctx, F, edges, r)
+        ctx.plan = _edge_plan_of(index, edges, F.shape[0]) if ctx.needs_input_grad[0] else None
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        F, edges, rr = ctx.saved_tensors
+        g = g.to(torch.float32).contiguous()
+        gF = gr = None
+        if ctx.needs_input_grad[0]:
+            m, C, plan = edges.shape[0], F.shape[1], ctx.plan
+            gF = torch.zeros((F.shape[0], C), dtype=torch.float32, device=F.device)
+            with nat.on_device(F.device):
+                floats = int(nat.lib().gnx_edge_sorted_work_floats(m, C))
+                work = torch.empty(max(floats, 4), dtype=torch.float32, device=F.device)
+                nat.check(nat.lib().gnx_edge_scores_backward_sorted(
+                    nat.ptr(F), F.stride(0), F.shape[0], C, nat.ptr(edges), m, nat.ptr(rr), nat.ptr(g), nat.ptr(gF), gF.stride(0),
+                    nat.ptr(plan.keys), nat.ptr(plan.pos), nat.ptr(plan.chunks), nat.ptr(work), work.numel(), nat.current_stream()))
+        if rr is not None and ctx.needs_input_grad[2]:
+            gr = (g[:, None] * F[edges[:, 0]] * F[edges[:, 1]]).sum(0).reshape(ctx.r_shape)
+        return gF, None, gr, None
+
+
+def edge_scores(F: torch.Tensor, edges, r=None, backward="atomic") -> torch.Tensor:
+    """Logits of the listed edges ([m, 2] node ids): <F[u], F[v]> or, with DistMult weights r [C, 1], <F[u] * F[v], r>.
+    ``backward``: "atomic" adds the gradient into the endpoint rows with float atomics (gnx_edge_scores_backward: the sum of a row
+    depends on scheduling); "sorted" sorts the endpoints once per call -- once per list for a DeviceIndex over a fixed list -- and sums
+    every row in that fixed order (gnx_edge_plan + gnx_edge_scores_backward_sorted)."""
+    if backward not in ("atomic", "sorted"):
+        raise Exception('edge_scores: backward must be "atomic" or "sorted"')
     nat.require_cuda(F, r)
     e = _as_index(edges, F.device, F.shape[0], "edge endpoint").reshape(-1, 2)
+    if backward == "sorted":
+        return _EdgeScoresSorted.apply(F, e, r, edges)
     return _EdgeScores.apply(F, e, r)
+
+
+def sample_negatives(graph: DeviceGraph, positives: torch.Tensor, samples, candidates, seed, stream, out=None, max_tries=32,
+                     fallbacks=None) -> torch.Tensor:
+    """negative_sampling's draw (graph_predictor.py:52-98) as one launch of gnx_sample_negatives: ``out`` [m (1 + samples), 2] (made when
+    None) receives every pair of ``positives`` [m, 2] followed by ``samples`` pairs (u, w), w drawn from ``candidates`` (device ids; None:
+    every node of ``graph``) by the counter RNG at (seed, stream + the graph's dropout counter) until it is neither u, v nor linked to u
+    in ``graph``, at most ``max_tries`` times.  ``fallbacks``: an int64 device counter of the slots that kept a rejected draw."""
+    nat.require_cuda(positives, candidates, out)
+    positives = positives.to(torch.int64).reshape(-1, 2).contiguous()
+    m, samples = positives.shape[0], int(samples)
+    if candidates is not None:
+        candidates = candidates.to(torch.int64).reshape(-1).contiguous()
+    if samples < 1:
+        raise Exception("sample_negatives: samples must be at least 1")
+    if out is None:
+        out = torch.empty((m * (1 + samples), 2), dtype=torch.int64, device=positives.device)
+    if out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != 2 * m * (1 + samples):
+        raise Exception("sample_negatives: out must be a contiguous int64 [m (1 + samples), 2] tensor")
+    if fallbacks is None:
+        fallbacks = torch.zeros(1, dtype=torch.int64, device=positives.device)
+    _same_device(graph, positives, candidates, out, fallbacks)
+    with nat.on_device(graph.device):
+        nat.check(nat.lib().gnx_sample_negatives(graph.handle, nat.ptr(positives), m, samples, nat.ptr(candidates),
+                                                 graph.n_rows if candidates is None else candidates.numel(), int(max_tries),
+                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFFFFFFFFFF, nat.ptr(out),
+                                                 nat.ptr(fallbacks), nat.current_stream()))
+    return out

@@ -183,7 +183,8 @@ class Trainable(Layered):
               batches: int = 1,
               optimizer=None,
               capture: bool = False):
-        """trainable.py:41-52.  ``capture=True`` (not in the reference; device models with fixed index lists only) records
+        """trainable.py:41-52.  ``capture=True`` (not in the reference; device models with index lists that stay on the device: fixed
+        ones, or a link_tasks.device_negative_sampling, whose draws follow the device counter of the mask streams) records
         ONE training step and ONE validation forward as hipGraphs and replays them every epoch: on small graphs an epoch is
         ~200 kernel launches of a few microseconds each, and the host loop around them is what takes the time."""
         self.reset()
@@ -263,13 +264,16 @@ class Trainable(Layered):
             optimizer = make_optimizer()
             with torch.cuda.stream(side):
                 for _ in range(2):                                          # also creates the optimizer's state tensors: their
-                    train_step(optimizer)                                   # initialisation must not end up inside the graph
+                    before = self._mask_calls                               # initialisation must not end up inside the graph
+                    train_step(optimizer)
+                    stepped = self._mask_calls
                     validate()
+                    # streams one step draws, and one validation (a task that samples its edges on the device draws there too)
+                    step_streams, eval_streams = stepped - before, self._mask_calls - stepped
             torch.cuda.current_stream(device).wait_stream(side)
             torch.cuda.synchronize(device)
             for v, value in zip(self.vars(), start):
                 v.assign(value)
-            masks_per_step = (self._mask_calls - first_mask) // 2
             self._mask_calls = first_mask
             for state in optimizer.state.values():                          # back to a fresh optimizer: moments and step counts zero
                 for item in state.values():
@@ -279,17 +283,20 @@ class Trainable(Layered):
             step_graph, eval_graph = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             with torch.cuda.graph(step_graph):
                 fitted_value = train_step(optimizer)
-                counter.add_(masks_per_step)
+                counter.add_(step_streams)
             self._mask_calls = first_mask                                    # the device counter does the numbering from here on
-            with torch.cuda.graph(eval_graph):
-                logits, held_out_value = validate()
+            with torch.cuda.graph(eval_graph):                               # recorded from first_mask as well: the counter holds
+                logits, held_out_value = validate()                          # everything drawn before a replay, of either graph
+                if eval_streams:
+                    counter.add_(eval_streams)
+            self._mask_calls = first_mask
         except Exception as error:
             for g in graphs:
                 g.set_dropout_counter(None)
             raise Exception("train(capture=True): this model / task cannot be recorded as a device graph (" + str(error) + ")")
         counter.zero_()
         best = _BestSoFar(self.vars(), patience)
-        steps = 0
+        steps = validations = 0
         for epoch in range(epochs):
             self._fast_predict = None
             scale.fill_(float(degradation(epoch)))
@@ -297,6 +304,7 @@ class Trainable(Layered):
                 step_graph.replay()
                 steps += 1
             eval_graph.replay()
+            validations += 1
             held_out = float(held_out_value)                                # the one synchronisation of the epoch
             if best.observe(held_out):
                 if verbose:
@@ -307,7 +315,7 @@ class Trainable(Layered):
         best.restore()
         for g in graphs:
             g.set_dropout_counter(None)
-        self._mask_calls = first_mask + steps * masks_per_step
+        self._mask_calls = first_mask + steps * step_streams + validations * eval_streams
         self._training = False
         self._fast_predict = None
         print('\r')

@@ -69,7 +69,9 @@ const char *gnx_last_error(void);
  * spectral-preserving GCNII layer in one launch (gnx_gcnii_step_spectral, gnx_gcnii_spectral_back), likewise, and the gather hints of
  * the wide eval launches (gnx_graph_set_gather_hints, gnx_graph_gather_hints, GNX_RESERVE_GATHER_HINTS), likewise, and the GCN layer
  * in one launch (gnx_gcn_step, gnx_gcn_step_dropped) with its input gradient (gnx_gcn_step_back, gnx_gcn_step_back_dropped), likewise,
- * and the NGCF layer in one launch with its backward's gate (gnx_ngcf_step, gnx_ngcf_back_gate, GNX_ACT_LEAKY), likewise. */
+ * and the NGCF layer in one launch with its backward's gate (gnx_ngcf_step, gnx_ngcf_back_gate, GNX_ACT_LEAKY), likewise, and the link
+ * task on the device (gnx_sample_negatives, gnx_edge_plan_bytes, gnx_edge_plan, gnx_edge_sorted_work_floats,
+ * gnx_edge_scores_backward_sorted), likewise. */
 #define GNX_ABI_VERSION 900
 int gnx_version(void);
 
@@ -913,6 +915,48 @@ int gnx_edge_scores(const float *d_F, int64_t ldf, int64_t n_rows, int64_t C, co
                     const float *d_r, float *d_out, void *stream);
 int gnx_edge_scores_backward(const float *d_F, int64_t ldf, int64_t n_rows, int64_t C, const int64_t *d_edges, int64_t m,
                              const float *d_r, const float *d_grad_out, float *d_grad_F, int64_t ldg, void *stream);
+
+/* The edge sampler of the link task, negative_sampling.__call__ (gnntf/core/gnn/graph_predictor.py:52-98), as one launch: d_edges
+ * int64 [m (1 + samples), 2] receives, per positive pair (u_i, v_i) of d_positive [m, 2], the pair itself and then `samples` rows
+ * (u_i, w) -- the reference's layout.  One thread per slot e = i * samples + s.  Try t = 0, 1, ... of a slot draws
+ *   hi = hash_u24(seed, stream_id + counter, e, 2 t, 0), lo = hash_u24(seed, stream_id + counter, e, 2 t + 1, 0)   (the counter RNG of
+ *   the dropout masks, oracle/gnntf_oracle.py:hash_u24; counter = the handle's gnx_graph_set_dropout_counter value, 0 without one: a
+ *   replayed hipGraph draws fresh negatives), x = hi 2^24 + lo, j = floor(x K / 2^48), w = d_candidates ? d_candidates[j] : j
+ * and the first w is taken with w != u, w != v and neither (u, w) nor (w, u) a stored entry of the handle's coalesced pattern (binary
+ * search in rows u and w; values are not read; a w outside [0, n_rows) has no stored entry).  After max_tries rejected tries the slot
+ * keeps the LAST w drawn and *d_fallbacks is incremented (an integer atomic: order-free) -- the loop is bounded.  A positive row with an
+ * endpoint outside [0, n_rows) is copied as it is and its negatives are (u, -1), which gnx_edge_scores answers with NaN.  d_candidates
+ * int64 [K], or NULL: every row id, K == n_rows.  Refused: K < 1, K >= 2^31, samples < 1, max_tries < 1, m < 0, m * samples >= 2^31,
+ * NULL pointers.  m == 0 writes nothing.  Stream-ordered, allocation-free. */
+int gnx_sample_negatives(gnx_graph_t g, const int64_t *d_positive, int64_t m, int64_t samples, const int64_t *d_candidates, int64_t K,
+                         int64_t max_tries, uint64_t seed, uint64_t stream_id, int64_t *d_edges, unsigned long long *d_fallbacks,
+                         void *stream);
+
+/* The link head's backward (graph_predictor.py:122-146 under the gradient tape) in a FIXED summation order: no float atomics, so a
+ * training step repeats bit for bit.
+ * gnx_edge_plan: position q = 2 i + side of the flattened list d_edges [m, 2] names node edges[q]; its other endpoint is edges[q ^ 1].
+ *   d_keys uint32 [2 m], d_pos int32 [2 m] receive the STABLE ascending sort of the positions by named node (positions ascend inside a
+ *   node); both positions of an edge with an endpoint outside [0, n_rows) are keyed n_rows and form a trailing bucket that the backward
+ *   skips.  d_chunks int32 [2 m + 1]: d_chunks[0] = the number of chunks, then the sorted index at which every chunk begins, ascending
+ *   -- a node's run of sorted indices is cut into chunks of 256 counted from the run's first index.  d_workspace: gnx_edge_plan_bytes(m)
+ *   bytes (-1: failed), 16-byte aligned, the caller's; the sort and the compaction run in it (rocPRIM), so the call allocates nothing,
+ *   waits for nothing and records into a hipGraph.  m < 2^30, n_rows < 2^31; m == 0 writes d_chunks[0] = 0 alone.
+ * gnx_edge_scores_backward_sorted: the operands and the += contract of gnx_edge_scores_backward, the plan of the SAME list and n_rows,
+ *   and d_work of gnx_edge_sorted_work_floats(m, C) floats.  The sum of a row is part of the interface:
+ *     term of position q, i = q >> 1:  t_q[c] = fl(w_i[c] * F[edges[q ^ 1], c]),  w_i[c] = fl(g_i * r[c]), or g_i without d_r;
+ *     a chunk's sum is sequential in ascending sorted index: s = t_first, s = fl(s + t_next), ...;
+ *     a node of one chunk:  dF[x, c] = fl(dF[x, c] + s);  a node of several: S = s_0, S = fl(S + s_1), ... in chunk order (the chunk
+ *     sums pass through d_work), then dF[x, c] = fl(dF[x, c] + S).
+ *   Every named row of d_grad_F is read and written once, by one owner; rows that no position names and the columns from C on keep their
+ *   bits.  A self-loop contributes both its positions to its node.  One lane group per chunk, lanes own columns; F rows are read with
+ *   16-byte loads where C % 4 == 0, ldf % 4 == 0 and d_F is 16-byte aligned. */
+int64_t gnx_edge_plan_bytes(int64_t m);
+int gnx_edge_plan(const int64_t *d_edges, int64_t m, int64_t n_rows, uint32_t *d_keys, int32_t *d_pos, int32_t *d_chunks,
+                  void *d_workspace, int64_t bytes, void *stream);
+int64_t gnx_edge_sorted_work_floats(int64_t m, int64_t C);
+int gnx_edge_scores_backward_sorted(const float *d_F, int64_t ldf, int64_t n_rows, int64_t C, const int64_t *d_edges, int64_t m,
+                                    const float *d_r, const float *d_grad_out, float *d_grad_F, int64_t ldg, const uint32_t *d_keys,
+                                    const int32_t *d_pos, const int32_t *d_chunks, float *d_work, int64_t work_floats, void *stream);
 
 /* Halo packing for the vertex-partitioned path: out[r,:] = X[idx[r],:], idx int64 [n_idx]. */
 int gnx_gather_rows(const float *d_X, int64_t ldx, const int64_t *d_idx, int64_t n_idx, int64_t C,
