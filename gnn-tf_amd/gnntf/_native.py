@@ -159,6 +159,10 @@ SIGNATURES = {
     "gnx_edge_sorted_work_floats": (c_int64, [c_int64, c_int64]),
     "gnx_edge_scores_backward_sorted": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "gnx_rank_candidates_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int64, c_int64]),
+    "gnx_rank_candidates": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                    c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "gnx_linear_combination": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "gnx_stream_read": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "gnx_stream_copy": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

@@ -186,22 +186,123 @@ class LinkPrediction(Predictor):
         return metrics.auc(self.labels.reshape(-1), self.predict(features))
 
 
+def recommend(F, nodes, k, graph, candidates=None, r=None):
+    """The ``k`` best candidates of every node of ``nodes`` that are neither the node itself nor linked to it in ``graph`` (a
+    sparse.DeviceGraph, or a model for its graph), by the link head's score <F[u] * r, F[v]>: (ids [S, k], scores [S, k]) on the device,
+    best first, ties to the larger id; a row with fewer than ``k`` such candidates ends in ids of -1 (scores -inf).  ``candidates``:
+    node ids (default: every node of the graph).  One call of sparse.rank_candidates without held-out neighbours: no score matrix is
+    stored."""
+    graph = graph if isinstance(graph, sparse.DeviceGraph) else graph.graph
+    if candidates is None:
+        candidates = torch.arange(graph.n_rows, dtype=torch.int64, device=graph.device)
+    elif isinstance(candidates, torch.Tensor):
+        candidates = torch.unique(candidates.to(graph.device, torch.int64).reshape(-1))      # sorted and de-duplicated
+    else:
+        candidates = torch.from_numpy(np.unique(np.asarray(candidates, dtype=np.int64))).to(graph.device)
+    ranked = sparse.rank_candidates(graph, F, nodes, None, candidates, k, r=r)
+    return ranked.top_ids, ranked.top_scores
+
+
+def ranking_metrics(n_pos, n_neg, less, equal, top_ids, top_is_pos, k, n_candidates):
+    """The per-source metrics of MeanLinkPrediction.evaluate from what sparse.rank_candidates returns, as host arrays: AUC from the rank
+    statistic (NaN without a stranger), and average precision, precision (over min(k, list length) entries), recall and F1 of the top-k
+    list -- the definitions of metrics.py, in its order of operations -- plus the coverage: distinct ids in the top-k lists over the
+    number of candidates.  Returns ({name: float64 [S]}, coverage)."""
+    n_pos, n_neg = np.asarray(n_pos, dtype=np.int64), np.asarray(n_neg, dtype=np.int64)
+    less, equal = np.asarray(less, dtype=np.float64), np.asarray(equal, dtype=np.float64)
+    top_ids, labels = np.asarray(top_ids).reshape(len(n_pos), -1), np.asarray(top_is_pos, dtype=np.float64).reshape(len(n_pos), -1)
+    if (n_neg < 0).any():
+        raise Exception("ranking_metrics: a source or one of its held-out nodes is not a row of the embeddings")
+    taken = np.minimum(k, n_pos + n_neg)                                 # entries of the top-k list; the columns beyond them are padding
+    real = np.arange(labels.shape[1])[None, :] < taken[:, None]
+    labels = np.where(real, labels, 0.0)
+    hits = labels.sum(axis=1)
+    gain = np.zeros(len(n_pos))
+    for position in range(labels.shape[1]):                              # best first, added in metrics.avprec's order
+        gain = gain + labels[:, position] / (position + 1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        pairs = (n_pos * n_neg).astype(np.float64)
+        auc = np.where(pairs > 0, (less + equal / 2.0) / pairs, np.nan)
+        avprec = np.where(gain == 0, 0.0, gain / hits)
+        precision, recall = hits / taken, hits / n_pos
+        f1 = np.where(precision + recall == 0, 0.0, 2 * precision * recall / (precision + recall))
+    scores = {"auc": auc, "avprec": avprec, "prec": precision, "rec": recall, "f1": f1}
+    return scores, len(np.unique(top_ids[real])) / n_candidates
+
+
 class MeanLinkPrediction(LinkPrediction):
     """graph_predictor.py:154-203: per-node ranking quality -- for every positive node, its held-out edges against all
     non-linked candidates; prints mean AUC / MAP / precision / recall / F1 at k and the coverage of the top-k lists,
-    returns the mean F1."""
+    returns the mean F1.
+    ``ranking``: "host" (default) walks the sources in Python, one launch of the link head per source.  "device" ranks every source in
+    ONE call of sparse.rank_candidates on device embeddings and downloads O(sources * k) numbers; the constructor then lays out, once,
+    the sources, the CSR list of their held-out neighbours (in ``parsed_edges`` order) and the sorted candidates, and ``graph`` may be a
+    networkx graph whose nodes are numbered 0 .. n - 1 in order (graph2adj's numbering) or a sparse.DeviceGraph; a networkx graph
+    becomes a pattern-only DeviceGraph at the first evaluation, on the device of the embeddings it is given.  Scores that tie are
+    ordered as np.argsort(kind="stable") orders the host list built in ascending candidate order."""
 
-    def __init__(self, *args, graph, positive_nodes=None, negative_nodes=None, k=5, **kwargs):
+    def __init__(self, *args, graph, positive_nodes=None, negative_nodes=None, k=5, ranking="host", **kwargs):
         super().__init__(*args, **kwargs)
-        self.positive_nodes, self.negative_nodes, self.k, self.graph = positive_nodes, negative_nodes, k, graph
+        if ranking not in ("host", "device"):
+            raise Exception('MeanLinkPrediction: ranking must be "host" or "device"')
+        self.positive_nodes, self.negative_nodes, self.k, self.graph, self.ranking = positive_nodes, negative_nodes, k, graph, ranking
         self.parsed_edges = dict()
         for u, v in self.edges:
             self.parsed_edges.setdefault(u, list())
             self.parsed_edges.setdefault(v, list())
             self.parsed_edges[u].append(v)
             self.parsed_edges[v].append(u)
+        if ranking == "device":
+            self._lay_out_ranking()
+
+    def _lay_out_ranking(self):
+        if not 1 <= int(self.k) <= sparse.RANK_MAX_K:
+            raise Exception(f'MeanLinkPrediction: ranking="device" takes k in [1, {sparse.RANK_MAX_K}]')
+        sources = list(self.parsed_edges) if self.positive_nodes is None else list(self.positive_nodes)
+        for node in sources:
+            if node not in self.parsed_edges:
+                raise Exception("Node not found")
+        lengths = [len(self.parsed_edges[node]) for node in sources]
+        candidates = set(v for neighbors in self.parsed_edges.values() for v in neighbors) if self.negative_nodes is None \
+            else set(self.negative_nodes)
+        self._rank_host = (np.asarray(sources, dtype=np.int64).reshape(-1), np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64),
+                           np.asarray([v for node in sources for v in self.parsed_edges[node]], dtype=np.int64).reshape(-1),
+                           np.asarray(sorted(candidates), dtype=np.int64).reshape(-1))
+        self._rank_device = None                                         # (graph, sources, (ptr, ids), candidates) on the device
+        if isinstance(self.graph, sparse.DeviceGraph):
+            self._upload_ranking(self.graph.device)
+        elif list(self.graph) != list(range(len(self.graph))):
+            raise Exception('MeanLinkPrediction: ranking="device" needs a graph whose nodes are numbered 0 .. n - 1 in order '
+                            '(graph2adj numbers them so), or a DeviceGraph')
+
+    def _upload_ranking(self, device):
+        graph = self.graph
+        if not isinstance(graph, sparse.DeviceGraph):
+            from .graph_io import graph2adj
+            graph = sparse.DeviceGraph(graph2adj(graph, directed=True), device=device)      # the pattern: either direction links a pair
+        sources, ptr, ids, candidates = (torch.from_numpy(x).to(graph.device) for x in self._rank_host)
+        self._rank_device = (graph, sources, (ptr, ids), candidates)
+
+    def _evaluate_on_device(self, features):
+        if not features.is_cuda:
+            raise Exception('MeanLinkPrediction: ranking="device" runs on the GPU only (embeddings on %s); ranking="host" evaluates '
+                            'CPU embeddings' % features.device)
+        if self._rank_device is None:
+            self._upload_ranking(features.device)
+        graph, sources, positives, candidates = self._rank_device
+        with torch.no_grad():
+            ranked = sparse.rank_candidates(graph, self._embed(features), sources, positives, candidates, self.k, r=self.r)
+            counts = torch.stack([ranked.n_pos, ranked.n_neg, ranked.less, ranked.equal]).cpu().numpy()
+            top_ids, top_is_pos = ranked.top_ids.cpu().numpy(), ranked.top_is_pos.cpu().numpy()
+        scores, coverage = ranking_metrics(*counts, top_ids, top_is_pos, self.k, len(candidates))
+        mean = {name: float(np.mean(v)) for name, v in scores.items()}
+        print("per-node ranking: AUC %.3f  MAP %.3f  precision %.3f  recall %.3f  F1 %.3f  coverage %.3f"
+              % (mean["auc"], mean["avprec"], mean["prec"], mean["rec"], mean["f1"], coverage))
+        return np.mean(scores["f1"])
 
     def evaluate(self, features):
+        if self.ranking == "device":
+            return self._evaluate_on_device(features)
         k = self.k
         sources = list(self.parsed_edges) if self.positive_nodes is None else self.positive_nodes
         # default candidates: every node that appears in the held-out edges.  (The reference iterates the dict's KEYS here,

@@ -7,6 +7,7 @@ gnntf/core/gnn/architectures/gcn.py:88).
 from __future__ import annotations
 
 import math
+from collections import namedtuple
 from ctypes import byref, c_float, c_int64, c_void_p
 
 import numpy as np
@@ -2424,3 +2425,55 @@ def sample_negatives(graph: DeviceGraph, positives: torch.Tensor, samples, candi
                                                  int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFFFFFFFFFF, nat.ptr(out),
                                                  nat.ptr(fallbacks), nat.current_stream()))
     return out
+
+
+# ---- ranking evaluation: every candidate of every source in one call ------------------------------------------------------
+RANK_MAX_K = 32          # GNX_RANK_MAX_K
+RANK_POS_PASS = 32       # GNX_RANK_POS_PASS: positive scores of a source the tile kernel keeps in LDS; further ones are read from memory
+
+RankResult = namedtuple("RankResult", "n_pos n_neg less equal top_ids top_scores top_is_pos scores")
+
+
+def rank_candidates(graph: DeviceGraph, F: torch.Tensor, sources, positives, candidates, k, r=None, scores=False, splits=0) -> RankResult:
+    """MeanLinkPrediction.evaluate's ranking (graph_predictor.py:154-203) for all ``sources`` in one call of gnx_rank_candidates: the list
+    of a source is its held-out neighbours (``positives`` = (ptr [S + 1], ids [P]), a CSR list, or None) followed by every id of
+    ``candidates`` -- STRICTLY ASCENDING -- that is neither the source nor linked to it in ``graph`` in either direction.  Returns device
+    tensors: ``n_pos``, ``n_neg`` (-1: the source or one of its held-out ids is out of range), ``less`` / ``equal`` (over the positives,
+    the strangers that score below / equal: AUC = (less + equal / 2) / (n_pos n_neg)), and the ``k`` best entries of the list,
+    ``top_ids`` (-1 where the list is shorter), ``top_scores`` (-inf there), ``top_is_pos``: higher score first, on a tie the entry later in
+    the list.  ``scores=True`` adds the raw [S, K] scores of every in-range pair (cells of out-of-range ids are NaN).  ``r``: DistMult
+    weights [C].  ``splits``: candidate parts, 0 = the library's choice; no output depends on it.  Finite ``F`` is a precondition."""
+    nat.require_cuda(F, r)
+    F = _as_f32_rows(F.detach())
+    device = F.device
+    sources = _as_index(sources, device, None, "source node").reshape(-1)
+    candidates = _as_index(candidates, device, None, "candidate node").reshape(-1)
+    S, K, k = sources.numel(), candidates.numel(), int(k)
+    if positives is None:
+        ptr, ids = torch.zeros(S + 1, dtype=torch.int64, device=device), torch.zeros(0, dtype=torch.int64, device=device)
+    else:
+        ptr, ids = (_as_index(x, device, None, "held-out node").reshape(-1) for x in positives)
+    if ptr.numel() != S + 1:
+        raise Exception("rank_candidates: positives = (ptr, ids) needs one more pointer than there are sources")
+    if not 1 <= k <= RANK_MAX_K:
+        raise Exception(f"rank_candidates: k must be in [1, {RANK_MAX_K}]")
+    rr = None if r is None else r.detach().to(torch.float32).reshape(-1).contiguous()
+    if rr is not None and rr.numel() != F.shape[1]:
+        raise Exception("rank_candidates: r must hold one weight per column of F")
+    _same_device(graph, F, rr, sources, ptr, ids, candidates)
+    counts = torch.empty((4, S), dtype=torch.int64, device=device)
+    top_ids = torch.empty((S, k), dtype=torch.int64, device=device)
+    top_scores = torch.empty((S, k), dtype=torch.float32, device=device)
+    top_is_pos = torch.empty((S, k), dtype=torch.uint8, device=device)
+    raw = torch.full((S, K), float("nan"), dtype=torch.float32, device=device) if scores else None
+    with nat.on_device(device):
+        nbytes = int(nat.lib().gnx_rank_candidates_bytes(S, ids.numel(), K, k, int(splits)))
+        if nbytes < 0:
+            nat.check(-1)
+        workspace = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+        nat.check(nat.lib().gnx_rank_candidates(
+            graph.handle, nat.ptr(F), F.stride(0), F.shape[0], F.shape[1], nat.ptr(rr), nat.ptr(sources), S, nat.ptr(ptr), nat.ptr(ids),
+            ids.numel(), nat.ptr(candidates), K, k, int(splits), nat.ptr(counts[0]), nat.ptr(counts[1]), nat.ptr(counts[2]),
+            nat.ptr(counts[3]), nat.ptr(top_ids), nat.ptr(top_scores), nat.ptr(top_is_pos), nat.ptr(raw), nat.ptr(workspace),
+            workspace.numel(), nat.current_stream()))
+    return RankResult(counts[0], counts[1], counts[2], counts[3], top_ids, top_scores, top_is_pos, raw)

@@ -71,7 +71,8 @@ const char *gnx_last_error(void);
  * in one launch (gnx_gcn_step, gnx_gcn_step_dropped) with its input gradient (gnx_gcn_step_back, gnx_gcn_step_back_dropped), likewise,
  * and the NGCF layer in one launch with its backward's gate (gnx_ngcf_step, gnx_ngcf_back_gate, GNX_ACT_LEAKY), likewise, and the link
  * task on the device (gnx_sample_negatives, gnx_edge_plan_bytes, gnx_edge_plan, gnx_edge_sorted_work_floats,
- * gnx_edge_scores_backward_sorted), likewise. */
+ * gnx_edge_scores_backward_sorted), likewise, and the ranking evaluation of the link task (gnx_rank_candidates_bytes,
+ * gnx_rank_candidates, GNX_RANK_MAX_K, GNX_RANK_POS_PASS, GNX_RANK_MAX_SPLITS), likewise. */
 #define GNX_ABI_VERSION 900
 int gnx_version(void);
 
@@ -957,6 +958,47 @@ int64_t gnx_edge_sorted_work_floats(int64_t m, int64_t C);
 int gnx_edge_scores_backward_sorted(const float *d_F, int64_t ldf, int64_t n_rows, int64_t C, const int64_t *d_edges, int64_t m,
                                     const float *d_r, const float *d_grad_out, float *d_grad_F, int64_t ldg, const uint32_t *d_keys,
                                     const int32_t *d_pos, const int32_t *d_chunks, float *d_work, int64_t work_floats, void *stream);
+
+/* The ranking evaluation of the link task, MeanLinkPrediction.evaluate (gnntf/core/gnn/graph_predictor.py:154-203), for all source
+ * nodes at once (added within ABI 0.9 -- probe for the symbols).  The list of source s = d_sources[i] is its held-out neighbours
+ * d_pos_ids[d_pos_ptr[i] .. d_pos_ptr[i + 1]) in the order given (the positives), followed by the strangers: every candidate v of
+ * d_candidates [K] (int64, STRICTLY ASCENDING) inside [0, n_rows_F) with v != s and neither (s, v) nor (v, s) a stored entry of the
+ * handle's coalesced pattern (values are not read; an id at or beyond the handle's rows is linked to nothing).  A held-out neighbour
+ * that is also a non-linked candidate is in the list twice, as in the reference.  A candidate outside [0, n_rows_F) is skipped.
+ *   score(s, v) = sum_c fl(F[s, c] * r[c]) * F[v, c]  (d_r NULL: F[s, c] * F[v, c]), accumulated in f32 on v_mfma_f32_16x16x4_f32 in
+ *   ascending groups of 16 columns; the score of a pair is the same bits wherever the call needs it.  d_F: f32 rows of any C >= 1 and
+ *   any pitch ldf >= C (16-byte loads where ldf % 4 == 0 and d_F is 16-byte aligned); nothing from column C on is read.  FINITE
+ *   embeddings and weights are a precondition: the order of NaN scores is not defined.
+ * Outputs per source i, the caller's:
+ *   d_n_pos[i]    the length of its held-out list;
+ *   d_n_neg[i]    the number of strangers, or -1: the source, one of its held-out ids or its d_pos_ptr range is out of range -- then
+ *                 less = equal = 0 and the top-k row is padding;
+ *   d_less[i], d_equal[i]   summed over the positives p, the strangers whose score is < resp. == the score of p (-0 == +0): the
+ *                 rank-statistic AUC is exactly (less + equal / 2) / (n_pos * n_neg);
+ *   d_top_ids [S, k] int64, d_top_scores [S, k] f32, d_top_is_pos [S, k] uint8: the k first entries of the list in this TOTAL order --
+ *                 a higher score comes first; among equal scores the entry LATER in the list comes first (what
+ *                 np.argsort(scores, kind="stable")[-k:] selects, reversed): a stranger beats a positive, and among strangers the larger
+ *                 candidate id wins.  Where the list is shorter than k: id -1, score -inf, is_pos 0.  1 <= k <= GNX_RANK_MAX_K.
+ *   d_scores [S, K] f32, or NULL: the raw score of every (source, candidate) pair whose ids are in range, excluded or not; other
+ *                 cells keep their bits.
+ * The order is total and the counts are integers (integer atomics only, no float atomics), so no output depends on `splits` or on the
+ * schedule.  splits: 0 = the library cuts the candidate tiles into as many parts as fill the device; n > 0 = into n parts (at most
+ * GNX_RANK_MAX_SPLITS, never more than there are tiles of 64 candidates).  Positive scores beyond the first GNX_RANK_POS_PASS of a
+ * source are compared from memory instead of LDS.  d_workspace: gnx_rank_candidates_bytes(S, P, K, k, splits) bytes (-1: refused),
+ * 16-byte aligned.  The counts are taken over every candidate and corrected over the excluded pairs, which are found from the rows of
+ * the source in the handle and in its TRANSPOSED structure: that is built on the first call (gnx_graph_reserve(GNX_RESERVE_TRANSPOSED)
+ * before a capture); otherwise the call allocates nothing, waits for nothing and records into a hipGraph.  S == 0 does nothing.
+ * Refused: S, P, K outside [0, 2^31), k outside [1, GNX_RANK_MAX_K], splits outside [0, GNX_RANK_MAX_SPLITS], C < 1, ldf < C, NULL
+ * handle / operands / outputs, a short or misaligned workspace. */
+#define GNX_RANK_MAX_K 32
+#define GNX_RANK_POS_PASS 32
+#define GNX_RANK_MAX_SPLITS 256
+int64_t gnx_rank_candidates_bytes(int64_t S, int64_t P, int64_t K, int64_t k, int64_t splits);
+int gnx_rank_candidates(gnx_graph_t g, const float *d_F, int64_t ldf, int64_t n_rows_F, int64_t C, const float *d_r,
+                        const int64_t *d_sources, int64_t S, const int64_t *d_pos_ptr, const int64_t *d_pos_ids, int64_t P,
+                        const int64_t *d_candidates, int64_t K, int64_t k, int64_t splits, int64_t *d_n_pos, int64_t *d_n_neg,
+                        int64_t *d_less, int64_t *d_equal, int64_t *d_top_ids, float *d_top_scores, uint8_t *d_top_is_pos, float *d_scores,
+                        void *d_workspace, int64_t bytes, void *stream);
 
 /* Halo packing for the vertex-partitioned path: out[r,:] = X[idx[r],:], idx int64 [n_idx]. */
 int gnx_gather_rows(const float *d_X, int64_t ldx, const int64_t *d_idx, int64_t n_idx, int64_t C,
