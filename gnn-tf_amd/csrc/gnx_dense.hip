@@ -530,7 +530,7 @@ DenseLaunch dense_kernel_for(const DenseArgs &p, bool x_aligned) {
 
 namespace gnx {
 
-// used by gnx_gcnii.hip too (GCNII's long rows go through the dense kernel with a row scatter)
+// used by the fused layer units too (their long rows go through the dense kernel with a row scatter)
 int dense_rows(const float *X, int64_t ldx, int64_t n, int64_t F, const float *W, int64_t ldw, int64_t O, const float *bias, int act,
                const int32_t *in_rows, const int32_t *out_rows, float *out, int64_t ldo, hipStream_t s) {
     if (n == 0) return GNX_OK;

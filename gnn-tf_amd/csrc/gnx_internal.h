@@ -420,6 +420,10 @@ int dense_rows(const float *X, int64_t ldx, int64_t n, int64_t F, const float *W
                const int32_t *in_rows, const int32_t *out_rows, float *out, int64_t ldo, hipStream_t s);
 // out[e] = partial[0][e] + partial[1][e] + ... in slab order, e < elems (gnx_dense_wgrad.hip): the last pass of the weight gradients
 void sum_slabs(const float *partial, int64_t n_slabs, int64_t elems, float *out, hipStream_t s);
+// out[r, :] = drop(X[r, :]) for the rows listed (null: rows 0 .. n), the mask keyed by row id and column (gnx_feature_dropout.hip): the
+// fused layers' rows that go through memory; out may be X
+void launch_feature_dropout(const float *X, int64_t ldx, const int32_t *rows, int64_t n, int64_t C, const DropFuse &fd, float *out, int64_t ldo,
+                            hipStream_t s);
 #ifdef GNX_TUNING
 extern int tune_override;
 #endif

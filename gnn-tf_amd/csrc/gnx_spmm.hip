@@ -78,7 +78,7 @@ int launch_spmm(gnx_graph *g, const Csr &m, SpmmArgs &p, hipStream_t s) {
     });
 }
 
-// the long rows of a launch whose short rows another translation unit's kernel took (gnx_gcnii.hip): partial sums + reduce
+// the long rows of a launch whose short rows another translation unit's kernel took (the fused layer units): partial sums + reduce
 void launch_long_rows(const SpmmArgs &p, hipStream_t s) {
     with_vec<F32Rows>(F32Rows::vec(p), [&](auto V) { launch_long<F32Rows, V()>(p, s); });
 }

@@ -43,7 +43,7 @@ void set_drop_fuse(const gnx_graph *g, float dropout_p, uint64_t seed, uint64_t 
 
 const char *launch_spmm_dropped(const SpmmArgs &p, int vec, hipStream_t s) { return launch_drop<F32Rows>(p, vec, s); }
 
-// the long rows of a fused-dropout launch whose short rows another translation unit's kernel took (gnx_gcnii.hip): the chunk kernels of
+// the long rows of a fused-dropout launch whose short rows another translation unit's kernel took (the fused layer units): the chunk kernels of
 // launch_drop over the same DropFuse + the reduce
 void launch_long_rows_dropped(const SpmmArgs &p, hipStream_t s) {
     with_vec<F32Rows>(F32Rows::vec(p), [&](auto V) {

@@ -1,4 +1,4 @@
-"""The 16-row tile frame of the fused layer kernels (csrc/gnx_gcnii.hip) on the MI355X at the sizes where only the frame can go wrong:
+"""The 16-row tile frame of the fused layer kernels (csrc/gnx_layer_device.h; the kernels called here are in gnx_gcnii.hip and gnx_gcn.hip) on the MI355X at the sizes where only the frame can go wrong:
 n = 1 (one partial tile), 15, 16 (a full tile), 17 (a tile plus one row) and 129 (a second block with a single live wave), each at
 C = 16, 32, 64 (1, 2 and 4 passes over a tile).  Rows of 0 to 3 entries, row 0 without any (at n = 1 the only row); no hub rows -- their
 path is that of tests/test_gpu_gcnii_shapes.py, test_gpu_gcnii_wgrad.py and test_gpu_gcn_fused.py.  Every handle runs as built and
