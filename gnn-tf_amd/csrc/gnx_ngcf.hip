@@ -3,7 +3,9 @@
 //   k_spmm_ngcf        the NGCF layer in one launch: k_spmm_gcn's fill, two matrices in LDS, the message product kept in the accumulators
 //                      while the tile is multiplied by the rows' own X, the mask and the row norm in the store loop (k_ngcf_product and
 //                      k_ngcf_tail: the same layer as row passes around the dense kernel; k_ngcf_back_gate: the backward's first pass)
-//   ngcf_forward       gnx_ngcf_step (gnx_ngcf_back_gate is an entry of its own: one launch)
+//   k_ngcf_back        the backward around the transposed SpMM in one launch (gnx_step_back_ngcf): the gate, G1 . W1^T and G2 . W2^T
+//                      through one tile per wave, dA, R and P from the walk, the bias sums as slabs (k_ngcf_back_sums adds them)
+//   ngcf_forward       gnx_ngcf_step (gnx_ngcf_back_gate and gnx_step_back_ngcf are entries of their own)
 #include "gnx_layer_device.h"
 
 namespace {
@@ -314,6 +316,8 @@ void launch_ngcf_tail(const float *P1, int64_t ldp, float *out, int64_t ldo, con
 // lane's fmaf chain over its columns in ascending order, then the xor-shuffles; rnorm[r] < 0: the clamp acted, y = |r| x and
 // g_s = |r| g; rnorm == null: g_s = g.  g_u = kept ? g_s * scale : +0 (the forward's mask, made again), G1 = bit1 ? g_u : g_u * slope
 // and G2 likewise (gate == null: every bit counts as set); the columns C_out .. pad - 1 of G1 / G2 are written as zeros.
+// THE ROW BODY HAS A TWIN: ngcf_gate_row below (k_ngcf_back) repeats it statement for statement and must keep its bits -- change both
+// (tests/test_gpu_ngcf_back.py compares G1 / G2 of the two bit for bit).
 __global__ __launch_bounds__(256) void k_ngcf_back_gate(const float *__restrict__ g, int64_t ldg, const float *__restrict__ y, int64_t ldy,
                                                        const float *__restrict__ rnorm, const uint32_t *__restrict__ gate, int64_t n,
                                                        int64_t C_out, int64_t pad, float slope, const DropFuse fd, float *__restrict__ G1,
@@ -357,6 +361,200 @@ __global__ __launch_bounds__(256) void k_ngcf_back_gate(const float *__restrict_
             }
     }
 }
+
+// ---- the NGCF layer's backward around the transposed SpMM, one launch (gnx_step_back_ngcf) ------------------------------------------------
+//   G1, G2 = the gate pass      Q1 = G1 . W1^T      Q2 = G2 . W2^T      dA = Q1 * X + Q2      R = Q1 * A      P = X * A      db = sum_rows G
+// Row-local, no gather: the 16-row tile frame over the rows as numbered.  ngcf_gate_row is the row body of k_ngcf_back_gate, statement
+// for statement -- the gate pass itself keeps its own text: every way of calling one function from both kernels changed its instructions
+// (profiles/NOTES.md, "Fused NGCF backward"), as with the tile frame's fill and walk -- so G1 / G2 have the gate pass's bits; the tests
+// compare them bit for bit.
+struct NgcfBack {
+    const float *g; int64_t ldg; const float *y; int64_t ldy; const float *rnorm; const uint32_t *gate;      // the gate pass's operands
+    int64_t n; int C_out, pad; float slope; DropFuse fd;
+    const float *X; int64_t ldx; const float *A;                                                               // A [n, C_in] contiguous
+    const float *W1; int64_t ldw1; const float *W2; int64_t ldw2;
+    float *G1, *G2; int64_t ldG;
+    float *P, *dA, *R;                   // [n, C_in] contiguous each; P may be null; dA == null: no products at all (R is null too)
+    float *work;                         // the bias slabs, 2 C_out floats per block, or null
+    int64_t tiles_per_block;
+};
+
+// G1 / G2 of the columns 4 sub .. 4 sub + 3 of row r (zeros from C_out on), 16 lanes per row: the arithmetic of k_ngcf_back_gate
+template <bool DROP>
+__device__ __forceinline__ void ngcf_gate_row(const NgcfBack &a, int64_t r, int sub, uint64_t stream, float (&g1)[4], float (&g2)[4]) {
+    const int64_t C_out = a.C_out, words = (C_out + 31) >> 5, c = 4 * sub;
+    const float *__restrict__ g = a.g, *__restrict__ y = a.y;
+    const uint32_t *__restrict__ gate = a.gate;
+    const float rn = a.rnorm ? a.rnorm[r] : 1.f;
+    const bool project = a.rnorm != nullptr && rn > 0.f;
+    float dot = 0.f;
+    if (project) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+            if (c + v < C_out) dot = fmaf(y[r * a.ldy + c + v], g[r * a.ldg + c + v], dot);
+        dot = ngcf_row_sum<16>(dot);
+    }
+    const float scale = fabsf(rn);
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+        const int64_t cv = c + v;
+        g1[v] = 0.f; g2[v] = 0.f;
+        if (cv < C_out) {
+            float x[1] = {g[r * a.ldg + cv]};
+            if (project) x[0] = scale * (x[0] - y[r * a.ldy + cv] * dot);
+            else if (a.rnorm != nullptr) x[0] = scale * x[0];
+            if constexpr (DROP) drop_values<1>(a.fd, stream, r, cv, x);      // (without a mask the gate pass multiplies by a scale of 1)
+            bool bit1 = true, bit2 = true;
+            if (gate != nullptr) {
+                bit1 = (gate[r * (2 * words) + (cv >> 5)] >> (cv & 31)) & 1u;
+                bit2 = (gate[r * (2 * words) + words + (cv >> 5)] >> (cv & 31)) & 1u;
+            }
+            g1[v] = bit1 ? x[0] : x[0] * a.slope;
+            g2[v] = bit2 ? x[0] : x[0] * a.slope;
+        }
+    }
+}
+
+// Block b takes the tiles b tiles_per_block .. (b + 1) tiles_per_block - 1 (tile t: rows 16 t .. 16 t + 15), wave w every WPB-th of
+// them from the w-th on: which rows a block and a wave take follows from (n, the grid) alone.  Both matrices sit TRANSPOSED in LDS --
+// W^T [16 NTK, C_in], read from W as stored, the rows from C_out on zero -- and a wave holds ONE tile, which both products pass through:
+//   gate      four passes of four rows, 16 lanes per row (ngcf_gate_row): G1 / G2 to memory as whole float4 rows up to pad =
+//             roundup4(C_out); a lane keeps its 16 + 16 values in registers and adds them to its column sums
+//   message   G2 into the first 16 NTK columns of the tile, tile <- tile . W2^T on the matrix cores (tile_times_Ms with the k extent
+//             16 NTK, k ascending): Q2, which each lane of the walk takes into registers -- a float4 of its row per pass
+//   interaction  G1 into the tile from the registers, tile <- tile . W1^T: Q1
+//   walk      a float4 of the lane's row per pass: dA = fmaf(Q1, X, Q2), R = Q1 * A, P = X * A
+//   sums      a lane's sums over its rows in ascending order, then the block's 4 WPB row lanes of a column in (wave, lane) order through
+//             LDS into slab b of `work` (db1, then db2); k_ngcf_back_sums adds the slabs in index order.  No float atomics.
+// WPB = 4, three waves per SIMD asked of the compiler (121 .. 165 VGPRs, no scratch): LDS at C_in = 64 is 2 x 17 408 B + 4 x 4 352 B =
+// 51 KiB, three blocks of four waves per CU by LDS and by registers alike (profiles/NOTES.md, "Fused NGCF backward").  The one
+// instantiation that would spill under that bound -- 64 -> up to 16 columns with the mask -- is asked for two.
+constexpr int ngcf_back_waves(int NTI, int NTK, bool DROP) { return NTI == 4 && NTK == 1 && DROP ? 2 : 3; }
+
+template <int NTI, int NTK, int WPB, bool DROP>
+__global__ __launch_bounds__(64 * WPB, ngcf_back_waves(NTI, NTK, DROP)) void k_ngcf_back(const NgcfBack a) {
+    static_assert(NTK >= 1 && NTK <= NTI, "C_out <= C_in: the products overwrite the gradient tile");
+    using TL = Tile<NTI>;
+    constexpr int C = TL::C, CK = 16 * NTK, G = TL::G, RPP = TL::RPP, PASSES = TL::PASSES, STRIDE = TL::STRIDE;
+    constexpr int TS = WPB * (16 * STRIDE > 512 ? 16 * STRIDE : 512);      // the tiles, and at the end eight column sums per thread
+    __shared__ float W1t[CK * STRIDE];
+    __shared__ float W2t[CK * STRIDE];
+    __shared__ float Ts[TS];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const bool products = a.dA != nullptr;
+    if (products) {
+        for (int idx = threadIdx.x; idx < C * CK; idx += 64 * WPB) {
+            const int c = idx / CK, k = idx % CK;
+            W1t[k * STRIDE + c] = k < a.C_out ? a.W1[(int64_t)c * a.ldw1 + k] : 0.f;
+            W2t[k * STRIDE + c] = k < a.C_out ? a.W2[(int64_t)c * a.ldw2 + k] : 0.f;
+        }
+    }
+    __syncthreads();
+    float *T = Ts + wave * (16 * STRIDE);
+    const int64_t n_tiles = (a.n + 15) / 16;
+    const int64_t first = (int64_t)blockIdx.x * a.tiles_per_block;
+    const int64_t last = first + a.tiles_per_block < n_tiles ? first + a.tiles_per_block : n_tiles;
+    const int gsub = lane & 15, grow = lane >> 4;          // the gate's lanes: 16 per row, four rows per pass
+    const int sub = lane % G, c = sub * 4;                 // the walk's lanes: G per row
+    uint64_t stream = 0;
+    if constexpr (DROP) stream = drop_stream(a.fd);
+    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t tile = first + wave; tile < last; tile += WPB) {
+        float g1[4][4], q2[PASSES][4];
+#pragma unroll
+        for (int ps = 0; ps < 4; ++ps) {
+            const int rr = 4 * ps + grow;
+            const int64_t r = tile * 16 + rr;
+            float g2[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int v = 0; v < 4; ++v) g1[ps][v] = 0.f;
+            if (r < a.n) {                                  // (the 16 lanes of a row together: the shuffles of y . g stay inside them)
+                ngcf_gate_row<DROP>(a, r, gsub, stream, g1[ps], g2);
+                if (4 * gsub < a.pad) {
+                    vstore<4>(a.G1 + r * a.ldG + 4 * gsub, g1[ps]);
+                    vstore<4>(a.G2 + r * a.ldG + 4 * gsub, g2);
+                }
+#pragma unroll
+                for (int v = 0; v < 4; ++v) { s1[v] += g1[ps][v]; s2[v] += g2[v]; }
+            }
+            if (4 * gsub < CK) vstore<4>(T + rr * STRIDE + 4 * gsub, g2);
+        }
+        if (products) {
+            __builtin_amdgcn_wave_barrier();
+            tile_times_Ms<NTI, false, NTI, NTK>(T, W2t, lane, GNX_ACT_NONE);
+#pragma unroll
+            for (int ps = 0; ps < PASSES; ++ps) vload<4>(q2[ps], T + (ps * RPP + lane / G) * STRIDE + c);
+            __builtin_amdgcn_wave_barrier();                // (every lane has its Q2 before G1 takes the tile)
+#pragma unroll
+            for (int ps = 0; ps < 4; ++ps)
+                if (4 * gsub < CK) vstore<4>(T + (4 * ps + grow) * STRIDE + 4 * gsub, g1[ps]);
+            __builtin_amdgcn_wave_barrier();
+            tile_times_Ms<NTI, false, NTI, NTK>(T, W1t, lane, GNX_ACT_NONE);
+        }
+        if (products || a.P != nullptr) {
+#pragma unroll
+            for (int ps = 0; ps < PASSES; ++ps) {
+                const int rr = ps * RPP + lane / G;
+                const int64_t r = tile * 16 + rr;
+                if (r >= a.n) continue;
+                float x[4], t[4];
+                vload<4>(x, a.X + r * a.ldx + c);
+                vload<4>(t, a.A + r * C + c);
+                if (a.P != nullptr) {
+                    float p[4];
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) p[v] = x[v] * t[v];
+                    vstore<4>(a.P + r * C + c, p);
+                }
+                if (products) {
+                    float q1[4], d[4];
+                    vload<4>(q1, T + rr * STRIDE + c);
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) { d[v] = fmaf(q1[v], x[v], q2[ps][v]); q1[v] *= t[v]; }
+                    vstore<4>(a.dA + r * C + c, d);
+                    vstore<4>(a.R + r * C + c, q1);
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();                    // (the walk has read the tile before the next gate writes it)
+    }
+    if (a.work == nullptr) return;                          // (uniform)
+    __syncthreads();
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+        Ts[threadIdx.x * 8 + v] = s1[v];
+        Ts[threadIdx.x * 8 + 4 + v] = s2[v];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < 2 * a.C_out) {
+        const int which = threadIdx.x / a.C_out, col = threadIdx.x % a.C_out;
+        float acc = 0.f;
+        for (int k = 0; k < 4 * WPB; ++k) acc += Ts[(k * 16 + (col >> 2)) * 8 + 4 * which + (col & 3)];
+        a.work[(int64_t)blockIdx.x * (2 * a.C_out) + threadIdx.x] = acc;
+    }
+}
+
+// Block q adds the slabs q per .. min((q + 1) per, n_slabs) - 1 in index order.  `group` given (the first level of a two-level sum:
+// fixed association, reproducible): the sum is slab q of `group`; else (one block) db1 = its first C_out columns, db2 the second
+// (either may be null).
+__global__ __launch_bounds__(128) void k_ngcf_back_sums(const float *__restrict__ work, int64_t n_slabs, int64_t per, int C_out,
+                                                       float *__restrict__ group, float *__restrict__ db1, float *__restrict__ db2) {
+    const int e = threadIdx.x;
+    if (e >= 2 * C_out) return;
+    const int64_t s0 = (int64_t)blockIdx.x * per, s1 = s0 + per < n_slabs ? s0 + per : n_slabs;
+    float acc = 0.f;
+#pragma unroll 8
+    for (int64_t s = s0; s < s1; ++s) acc += work[s * (2 * C_out) + e];
+    if (group != nullptr) { group[(int64_t)blockIdx.x * (2 * C_out) + e] = acc; return; }
+    float *out = e < C_out ? db1 : db2;
+    if (out != nullptr) out[e < C_out ? e : e - C_out] = acc;
+}
+
+// what gnx_graph_last_kernel reports for gnx_step_back_ngcf: [C_in = 16, 32, 64][mask][dX ran]
+#define GNX_NGCF_BACK_NAMES(c) {{"k_ngcf_back<" c ">", "k_ngcf_back<" c ">+spmm_tv"}, {"k_ngcf_back<" c ">_drop", "k_ngcf_back<" c ">_drop+spmm_tv"}}
+const char *const kNgcfBack[3][2][2] = {GNX_NGCF_BACK_NAMES("16"), GNX_NGCF_BACK_NAMES("32"), GNX_NGCF_BACK_NAMES("64")};
+#undef GNX_NGCF_BACK_NAMES
 
 // ---- the NGCF layer's host path (gnx_ngcf_step) -------------------------------------------------------------------------------------------
 // what gnx_graph_last_kernel reports: [C_in = 16, 32, 64][mask][norm][hub rows ran]; the composed form [mask][norm]
@@ -495,6 +693,106 @@ int gnx_ngcf_back_gate(gnx_graph_t g, const float *d_g, int64_t ldg, const float
     const unsigned grid = (unsigned)std::min<int64_t>(blocks_for(n_rows, 16), 1 << 20);
     GNX_LAUNCH(k_ngcf_back_gate, grid, d_g, ldg, d_y, ldy, d_rnorm, act == GNX_ACT_NONE ? nullptr : d_gate, n_rows, C_out, pad, slope, fd, d_G1, d_G2, ldG);
     GNX_HIP(hipGetLastError());
+    return GNX_OK;
+}
+
+// The backward of gnx_ngcf_step around the two weight gradients: k_ngcf_back, the slab sum, and -- for dX -- the transposed SpMM over dA
+// with R mixed in.  Everything is checked before the first launch; the widths and alignments without the launch are refused.
+int gnx_step_back_ngcf(gnx_graph_t g, const float *d_vals_t, const float *d_g, int64_t ldg, const float *d_y, int64_t ldy, const float *d_rnorm,
+                       const uint32_t *d_gate, int64_t C_out, int act, double dropout_p, uint64_t seed, uint64_t stream_id, const float *d_X,
+                       int64_t ldx, const float *d_agg, int64_t C_in, const float *d_W1, int64_t ldw1, const float *d_W2, int64_t ldw2,
+                       float *d_G1, float *d_G2, int64_t ldG, float *d_P, float *d_db1, float *d_db2, float *d_dA, float *d_R, float *d_dX,
+                       int64_t lddx, float *d_work, int64_t work_floats, void *stream) {
+    const char *fn = "gnx_step_back_ngcf";
+    GNX_CHECK_ARG(g != nullptr, "%s: NULL handle", fn);
+    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU || act == GNX_ACT_LEAKY, "%s: invalid activation %d", fn, act);
+    GNX_CHECK_ARG(dropout_p >= 0.0 && dropout_p < 1.0, "%s: dropout rate %g outside [0, 1)", fn, dropout_p);
+    GNX_CHECK_ARG(C_in >= 1 && C_in <= (1 << 20) && C_out >= 1 && C_out <= (1 << 20), "%s: widths %lld -> %lld not in [1, 2^20]", fn,
+                  (long long)C_in, (long long)C_out);
+    if (!fused_width(C_in)) return refuse_unfused(fn, C_in);
+    if (C_out > C_in) {
+        set_error("%s: C_out %lld > C_in %lld is not supported (the fused backward takes C_out <= C_in; keep the composed backward elsewhere)", fn,
+                  (long long)C_out, (long long)C_in);
+        return GNX_ERR_UNSUPPORTED;
+    }
+    GNX_CHECK_ARG(d_g != nullptr && d_G1 != nullptr && d_G2 != nullptr && ldg >= C_out && ldG >= C_out, "%s: NULL g / G1 / G2 or a row stride below C_out", fn);
+    GNX_CHECK_ARG(d_rnorm == nullptr || (d_y != nullptr && ldy >= C_out), "%s: d_rnorm needs y (the normalised forward output) with ldy >= C_out", fn);
+    GNX_CHECK_ARG(act == GNX_ACT_NONE || d_gate != nullptr, "%s: relu / leaky_relu need d_gate", fn);
+    GNX_CHECK_ARG(d_X != nullptr && d_agg != nullptr && ldx >= C_in, "%s: NULL X / agg, or ldx %lld < C_in %lld", fn, (long long)ldx, (long long)C_in);
+    const bool products = d_dX != nullptr;
+    GNX_CHECK_ARG(!products || (d_W1 != nullptr && d_W2 != nullptr && d_dA != nullptr && d_R != nullptr), "%s: dX needs W1, W2, d_dA and d_R", fn);
+    GNX_CHECK_ARG(!products || (ldw1 >= C_out && ldw2 >= C_out), "%s: ldw1 %lld or ldw2 %lld < C_out %lld", fn, (long long)ldw1, (long long)ldw2,
+                  (long long)C_out);
+    GNX_CHECK_ARG(!products || lddx >= C_in, "%s: lddx %lld < C_in %lld", fn, (long long)lddx, (long long)C_in);
+    GNX_CHECK_ARG(work_floats >= 0 && (d_work != nullptr || work_floats == 0), "%s: work_floats %lld without d_work, or negative", fn,
+                  (long long)work_floats);
+    // buffers of their own: no output is an input or another output (d_dA and d_R are looked at only where they are written)
+    const void *in[] = {d_vals_t, d_g, d_y, d_rnorm, d_gate, d_X, d_agg, d_W1, d_W2};
+    const void *out[] = {d_G1, d_G2, d_P, d_db1, d_db2, products ? d_dA : nullptr, products ? d_R : nullptr, d_dX, d_work};
+    const char *names[] = {"d_G1", "d_G2", "d_P", "d_db1", "d_db2", "d_dA", "d_R", "d_dX", "d_work"};
+    for (size_t i = 0; i < sizeof(out) / sizeof(out[0]); ++i) {
+        if (out[i] == nullptr) continue;
+        bool own = true;
+        for (const void *b : in) own = own && out[i] != b;
+        for (size_t j = 0; j < i; ++j) own = own && out[i] != out[j];
+        GNX_CHECK_ARG(own, "%s: %s must be a buffer of its own", fn, names[i]);
+    }
+    if (ldx % 4 != 0 || ldG % 4 != 0 || !aligned(d_X, 16) || !aligned(d_agg, 16) || !aligned(d_G1, 16) || !aligned(d_G2, 16) || !aligned(d_P, 16) ||
+        (products && (!aligned(d_dA, 16) || !aligned(d_R, 16))))
+        return refuse_unfused(fn, C_in);
+    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols && g->blk_col_gid == nullptr, "%s: needs a square stand-alone graph", fn);
+    const int64_t n = g->a.n_rows, n_tiles = blocks_for(n, 16);
+    const bool sums = d_db1 != nullptr || d_db2 != nullptr;
+    constexpr int WPB = 4;
+    // the bias slabs: one per block, at most 8192 -- ten rounds of the 768 blocks a device of 256 CUs holds at once, so that the last,
+    // partly filled round is a small share of the launch -- and one per group of 64 of them behind those (the two-level sum): a function
+    // of n alone; a block takes whole rounds of its four waves
+    const int64_t slabs = std::max<int64_t>(1, std::min<int64_t>(8192, blocks_for(n_tiles, WPB))), group_slabs = blocks_for(slabs, 64);
+    GNX_CHECK_ARG(!sums || work_floats >= (slabs + group_slabs) * 2 * C_out,
+                  "%s: needs d_work of %lld floats, has %lld (s = max(1, min(8192, ceil(ceil(n / 16) / 4))) = %lld slabs and ceil(s / 64) = %lld "
+                  "group sums of 2 * C_out floats)", fn, (long long)((slabs + group_slabs) * 2 * C_out), (long long)work_floats, (long long)slabs,
+                  (long long)group_slabs);
+    DropFuse fd{};
+    int rc = make_feat_drop(fn, g, dropout_p, seed, stream_id, fd);
+    if (rc != GNX_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (products) {      // (the transposed structure and the hub rows' slab before the first launch: under capture a part that would have to be built refuses the whole call)
+        rc = ensure_transpose(g, s);
+        if (rc != GNX_OK) return rc;
+        rc = reserve_partial(g, g->t, C_in, s);
+        if (rc != GNX_OK) return rc;
+    }
+    if (n == 0) {
+        if (d_db1) GNX_HIP(hipMemsetAsync(d_db1, 0, (size_t)C_out * sizeof(float), s));
+        if (d_db2) GNX_HIP(hipMemsetAsync(d_db2, 0, (size_t)C_out * sizeof(float), s));
+        return GNX_OK;
+    }
+    const bool drop = dropout_p != 0.0;      // p == 0 hashes nothing
+    const int64_t tiles_per_block = (blocks_for(n_tiles, (int)slabs) + WPB - 1) / WPB * WPB;
+    const int64_t blocks = (n_tiles + tiles_per_block - 1) / tiles_per_block;      // <= slabs
+    NgcfBack a{d_g, ldg, d_y, ldy, d_rnorm, act == GNX_ACT_NONE ? nullptr : d_gate, n, (int)C_out, (int)roundup4(C_out),
+               act == GNX_ACT_LEAKY ? 0.2f : act == GNX_ACT_RELU ? 0.f : 1.f, fd, d_X, ldx, d_agg, d_W1, ldw1, d_W2, ldw2, d_G1, d_G2, ldG, d_P,
+               products ? d_dA : nullptr, products ? d_R : nullptr, sums ? d_work : nullptr, tiles_per_block};
+    with_tile_width(C_in, n, [&](auto NTI, dim3) {
+        with_out_tiles((int)blocks_for(C_out, 16), [&](auto NTK) {      // (C_out <= C_in: no NTK above NTI)
+            with_flags([&](auto DROP) {
+                if constexpr (NTK() <= NTI())
+                    hipLaunchKernelGGL((k_ngcf_back<NTI(), NTK(), WPB, DROP()>), dim3((unsigned)blocks), dim3(64 * WPB), 0, s, a);
+            }, drop);
+        });
+    });
+    if (sums) {      // the blocks' slabs in groups of 64, then the groups: index order at both levels
+        float *groups = d_work + slabs * 2 * C_out;
+        const int64_t n_groups = blocks_for(blocks, 64);
+        hipLaunchKernelGGL(k_ngcf_back_sums, dim3((unsigned)n_groups), dim3(128), 0, s, d_work, blocks, (int64_t)64, (int)C_out, groups, nullptr, nullptr);
+        hipLaunchKernelGGL(k_ngcf_back_sums, dim3(1), dim3(128), 0, s, groups, n_groups, n_groups, (int)C_out, nullptr, d_db1, d_db2);
+    }
+    GNX_HIP(hipGetLastError());
+    if (products) {
+        rc = gnx_spmm_tv(g, d_vals_t ? d_vals_t : g->t_raw.get(), nullptr, d_dA, C_in, C_in, d_R, C_in, 1.f, 1.f, GNX_ACT_NONE, d_dX, lddx, stream);
+        if (rc != GNX_OK) return rc;
+    }
+    g->last_kernel = kNgcfBack[C_in == 16 ? 0 : C_in == 32 ? 1 : 2][drop][products];
     return GNX_OK;
 }
 

@@ -52,7 +52,8 @@ class GNN(Trainable):
     def __init__(self, graph, features, preprocessor: Layer = None, reorder=None, inference_dtype=torch.float32,
                  training_dtype=torch.float32, train_gather_order="auto", gcnii_backward="composed", feature_dropout="torch",
                  gcnii_training_dtype=torch.float32, gcnii_weight_gradient="stored", gcnii_spectral="composed",
-                 gcnii_edge_dropout="composed", gcn_layer="composed", gcn_backward="composed", ngcf_layer="composed"):
+                 gcnii_edge_dropout="composed", gcn_layer="composed", gcn_backward="composed", ngcf_layer="composed",
+                 ngcf_backward="composed"):
         """``reorder`` (opt-in, not in the reference): store the graph and the feature rows with the vertices relabelled; every
         [N, .] tensor inside the model then lives in that order, and the model's OUTPUT is put back into the caller's order, so
         tasks, labels and node ids are unaffected.  Results agree with the unordered model to float32 rounding.
@@ -193,11 +194,22 @@ class GNN(Trainable):
         multiply, two transforms, two activations, an add, the dropout and the normalisation as passes of their own.  In training
         with 0 < ``dropout`` < 1 the mask leaves the same launch under ``feature_dropout="fused"`` (the counter RNG; a
         ``_next_mask_stream()`` stream per layer); with torch's dropout the launch stops before the norm and torch's dropout and
-        normalize follow as today.  The backward is one gate pass (gnx_ngcf_back_gate) and today's kernels.  The results agree with
+        normalize follow as today.  The backward is one gate pass (gnx_ngcf_back_gate) and today's kernels (``ngcf_backward``, below, folds
+        it into one launch around the transposed SpMM).  The results agree with
         the composed layer to float32 rounding.  Subclasses, CPU tensors, bf16 rows, other widths (128, the width of the
-        library_recommendation demo, among them) and the sharded layers keep today's path and bits."""
+        library_recommendation demo, among them) and the sharded layers keep today's path and bits.
+        ``ngcf_backward`` (not in the reference): ``"composed"`` (the default: today's calls and bits) or ``"fused"`` (sparse.ngcf_step
+        ``backward``).  It acts on the layers that run as the one autograd node of ``ngcf_layer="fused"`` and is inert otherwise.
+        ``"fused"``: the gate pass, both bias sums, X * A, G1 W1^T and G2 W2^T, dA = Q1 * X + Q2 and Q1 * A come from ONE row-local
+        launch (gnx_step_back_ngcf: the products on the matrix cores, the weights read as stored), the transposed SpMM mixes Q1 * A
+        in, and gnx_dense_wgrad runs twice -- instead of the column sums, a torch multiply, gnx_dense twice and two addcmul passes.
+        It works with the mask in the launch and with torch's dropout and normalize alike.  The forward, dW1 and dW2 keep their
+        bits; dX and the bias gradients agree to float32 rounding (why the default stays ``"composed"``; measurement:
+        profiles/NOTES.md "Fused NGCF backward").  The node keeps its saved tensors: a second backward over a retained graph works."""
         if ngcf_layer not in sparse.NGCF_LAYERS:
             raise Exception("GNN: ngcf_layer must be one of " + ", ".join(repr(f) for f in sparse.NGCF_LAYERS))
+        if ngcf_backward not in sparse.NGCF_BACKWARDS:
+            raise Exception("GNN: ngcf_backward must be one of " + ", ".join(repr(b) for b in sparse.NGCF_BACKWARDS))
         if gcn_backward not in sparse.GCN_BACKWARDS:
             raise Exception("GNN: gcn_backward must be one of " + ", ".join(repr(b) for b in sparse.GCN_BACKWARDS))
         if gcn_layer not in sparse.GCN_LAYERS:
@@ -233,6 +245,7 @@ class GNN(Trainable):
         self.gcn_layer = gcn_layer
         self.gcn_backward = gcn_backward
         self.ngcf_layer = ngcf_layer
+        self.ngcf_backward = ngcf_backward
         self._order = self._newid = None
         self.reorder_used, self.locality_share = None, None
         if isinstance(graph, sparse.DeviceGraph):
@@ -778,12 +791,15 @@ class NGCFLayer(Layer):
             # GNN(ngcf_layer="fused"): the whole layer in one launch; with torch's dropout in training the launch stops before the norm
             act = "leaky" if self.activation is leaky_relu else "relu" if self.activation is relu else "none"
             b1, b2 = (self.b1, self.b2) if isinstance(self.b1, torch.Tensor) else (None, None)
+            # GNN(ngcf_backward=): named only where it is not the default, so the default's calls stay today's, argument for argument
+            how = getattr(gcn, "ngcf_backward", "composed")
+            back = dict() if how == "composed" else dict(backward=how)
             if not gcn.is_training() or self.dropout == 0:
-                return sparse.ngcf_step(self.adjacency, features, self.W1, b1, self.W2, b2, activation=act)
+                return sparse.ngcf_step(self.adjacency, features, self.W1, b1, self.W2, b2, activation=act, **back)
             if getattr(gcn, "feature_dropout", "torch") == "fused" and 0 < self.dropout < 1:
                 triple = (self.dropout,) + tuple(gcn._next_mask_stream())
-                return sparse.ngcf_step(self.adjacency, features, self.W1, b1, self.W2, b2, activation=act, dropout=triple)
-            summed = sparse.ngcf_step(self.adjacency, features, self.W1, b1, self.W2, b2, activation=act, normalize=False)
+                return sparse.ngcf_step(self.adjacency, features, self.W1, b1, self.W2, b2, activation=act, dropout=triple, **back)
+            summed = sparse.ngcf_step(self.adjacency, features, self.W1, b1, self.W2, b2, activation=act, normalize=False, **back)
             return torch.nn.functional.normalize(gcn.dropout(summed, self.dropout), dim=1, eps=1e-12)
         aggregated = sparse.spmm(self.adjacency, features)                       # the propagation kernel
         interaction = self.activation(affine(features * aggregated, self.W1, self.b1))

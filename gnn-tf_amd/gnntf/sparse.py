@@ -1688,6 +1688,7 @@ def gcn_step(adj: Adjacency, X: torch.Tensor, W: torch.Tensor, bias=None, relu=T
 
 
 NGCF_LAYERS = ("composed", "fused")
+NGCF_BACKWARDS = ("composed", "fused")
 NGCF_FUSED_WIDTHS = (16, 32, 64)      # C_in of the one-launch form of gnx_ngcf_step; its C_out is any width up to C_in
 NGCF_ACTIVATIONS = {"none": nat.ACT_NONE, "relu": nat.ACT_RELU, "leaky": nat.ACT_LEAKY}
 NGCF_SLOPES = {"none": 1.0, "relu": 0.0, "leaky": 0.2}
@@ -1762,16 +1763,70 @@ def _ngcf_back_gate(graph: DeviceGraph, g, y, rnorm, gate, activation, dropout=N
     return G1, G2
 
 
+def _ngcf_back_work_floats(n, C_out):
+    """include/gnx.h, gnx_step_back_ngcf: the bias slabs -- one per block of the launch, at most 8192, and one per group of 64 of them, 2 C_out
+    floats each."""
+    slabs = max(1, min(8192, ((n + 15) // 16 + 3) // 4))
+    return (slabs + (slabs + 63) // 64) * 2 * C_out
+
+
+def _ngcf_back_fusable(X, A, W1):
+    """Where gnx_step_back_ngcf has a launch: C_in in {16, 32, 64}, C_out <= C_in, 16-byte aligned rows of X and A."""
+    C_in, C_out = W1.shape
+    return (C_in in NGCF_FUSED_WIDTHS and C_out <= C_in and X.stride(0) % 4 == 0 and X.data_ptr() % 16 == 0 and A.is_contiguous()
+            and A.data_ptr() % 16 == 0)
+
+
+def _ngcf_back_launch(adj: Adjacency, g, y, rnorm, gate, activation, dropout, X, A, W1, W2, want_P=True, want_db=(True, True), want_dX=True):
+    """gnx_step_back_ngcf, one call: returns dict(G1, G2, P, db1, db2, dA, R, dX).  G1 / G2 are [n, C_out] views of rows of stride
+    roundup4(C_out) whose padding is zero; P = X * A only with ``want_P`` (dW1 needs it), db1 / db2 [C_out] with ``want_db``, and with
+    ``want_dX`` the products dA = (G1 W1^T) * X + G2 W2^T and R = (G1 W1^T) * A and dX = A_hat^T dA + R (None each otherwise: no products
+    and no transposed SpMM).  W1 / W2 are read as stored: no transposed copy.  ``dropout`` = the checked (p, seed, stream) or None."""
+    g, X, A, W1, W2 = _as_f32_rows(g), _as_f32_rows(X), _as_f32_rows(A), _as_f32_rows(W1), _as_f32_rows(W2)
+    nat.require_cuda(g, y, rnorm, gate, X, A, W1, W2)
+    graph = adj.graph
+    _same_device(graph, g, y, rnorm, gate, X, A, W1, W2)
+    n, C_out = g.shape
+    C_in = X.shape[1]
+    if (graph.n_rows != graph.n_cols or n != graph.n_rows or tuple(X.shape) != (n, C_in) or tuple(A.shape) != (n, C_in) or not A.is_contiguous()
+            or tuple(W1.shape) != (C_in, C_out) or tuple(W2.shape) != (C_in, C_out)):
+        raise Exception("ngcf_step: shape mismatch in the backward")
+    if activation != "none" and (gate is None or gate.dtype != torch.int32 or tuple(gate.shape) != (n, 2 * _gate_words(C_out)) or not gate.is_contiguous()):
+        raise Exception("ngcf_step: the gate words must be a contiguous int32 [n, 2 ceil(C_out / 32)]")
+    if rnorm is not None and (y is None or tuple(y.shape) != (n, C_out) or rnorm.numel() != n or not rnorm.is_contiguous()):
+        raise Exception("ngcf_step: the reciprocal norms go with the forward's output")
+    y = None if rnorm is None else _as_f32_rows(y)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=g.device)
+    G1, G2 = _padded_rows(n, C_out, g.device), _padded_rows(n, C_out, g.device)
+    P = new(n, C_in) if want_P else None
+    db1, db2 = (new(C_out) if w else None for w in want_db)
+    dA, R, dX = (new(n, C_in), new(n, C_in), new(n, C_in)) if want_dX else (None, None, None)
+    floats = _ngcf_back_work_floats(n, C_out) if any(want_db) else 0
+    work = new(floats) if floats else None
+    p, seed, stream = _dropout_args(dropout)
+    ldw = lambda W: W.stride(0) if C_in > 1 else C_out     # (torch calls a one-row matrix contiguous whatever its row stride says)
+    with nat.on_device(g.device):
+        nat.check(nat.lib().gnx_step_back_ngcf(
+            graph.handle, nat.ptr(adj.transposed_values()) if want_dX else None, nat.ptr(g), g.stride(0), nat.ptr(y), 0 if y is None else y.stride(0),
+            nat.ptr(rnorm), nat.ptr(gate) if activation != "none" else None, C_out, NGCF_ACTIVATIONS[activation], p, seed, stream, nat.ptr(X),
+            X.stride(0), nat.ptr(A), C_in, nat.ptr(W1), ldw(W1), nat.ptr(W2), ldw(W2), nat.ptr(G1), nat.ptr(G2), G1.stride(0), nat.ptr(P), nat.ptr(db1),
+            nat.ptr(db2), nat.ptr(dA), nat.ptr(R), nat.ptr(dX), C_in, nat.ptr(work), floats, nat.current_stream()))
+    return dict(G1=G1, G2=G2, P=P, db1=db1, db2=db2, dA=dA, R=R, dX=dX)
+
+
 class _NGCFStep(torch.autograd.Function):
     """out = l2_normalize(drop(act((X * A) . W1 + b1) + act(A . W2 + b2))), A = A_hat . X, as ONE launch (gnx_ngcf_step) that leaves A,
     two gate bits per element (P1 > 0, P2 > 0) and the rows' reciprocal norms; (A, gate, rnorm, out, W1, W2) and the input X are what
     is saved.  backward, composed from today's kernels around one gate pass (gnx_ngcf_back_gate -> G1, G2): db = the column sums,
     dW1 = (X * A)^T G1 and dW2 = A^T G2 (gnx_dense_wgrad), Q1 = G1 W1^T and Q2 = G2 W2^T (gnx_dense), dA = Q1 * X + Q2 and
-    dX = Q1 * A + A_hat^T dA (the transposed SpMM); the elementwise products in torch."""
+    dX = Q1 * A + A_hat^T dA (the transposed SpMM); the elementwise products in torch.
+    ``backward="fused"``, where gnx_step_back_ngcf has a launch (_ngcf_back_fusable): that entry once -- the gate, the column sums, X * A,
+    both products, dA and Q1 * A from one launch, then the transposed SpMM with Q1 * A mixed in -- and gnx_dense_wgrad twice.  The saved
+    tensors stay: a second backward over a retained graph gives the same bits."""
 
     @staticmethod
-    def forward(ctx, X, W1, b1, W2, b2, adj, activation, dropout, normalize):
-        ctx.adj, ctx.activation, ctx.dropout = adj, activation, dropout
+    def forward(ctx, X, W1, b1, W2, b2, adj, activation, dropout, normalize, backward="composed"):
+        ctx.adj, ctx.activation, ctx.dropout, ctx.backward = adj, activation, dropout, backward
         ctx.bias_shapes = tuple(None if b is None else tuple(b.shape) for b in (b1, b2))
         out, agg, gate, rnorm = _ngcf_launch(adj, X, W1, b1, W2, b2, activation, keep=True, dropout=dropout, normalize=normalize)
         ctx.save_for_backward(X, agg, gate, rnorm, out if normalize else None, W1, W2)
@@ -1781,8 +1836,19 @@ class _NGCFStep(torch.autograd.Function):
     def backward(ctx, g):
         X, A, gate, rnorm, out, W1, W2 = ctx.saved_tensors
         X = _as_f32_rows(X)
-        G1, G2 = _ngcf_back_gate(ctx.adj.graph, g, out, rnorm, gate, ctx.activation, ctx.dropout)
         need = ctx.needs_input_grad
+        if ctx.backward == "fused" and _ngcf_back_fusable(X, A, W1):
+            want_db = tuple(ctx.bias_shapes[k] is not None and need[2 + 2 * k] for k in (0, 1))
+            made = _ngcf_back_launch(ctx.adj, g, out, rnorm, gate, ctx.activation, ctx.dropout, X, A, W1, W2, want_P=need[1], want_db=want_db,
+                                     want_dX=need[0])
+            del made["dA"], made["R"]                      # (the transposed SpMM inside the call was their last reader)
+            gW1 = _dense_wgrad(made["P"], made["G1"]) if need[1] else None
+            gW2 = _dense_wgrad(A, made["G2"]) if need[3] else None
+            gb1, gb2 = (None if made[k] is None else made[k].reshape(shape) for k, shape in zip(("db1", "db2"), ctx.bias_shapes))
+            gX = made["dX"]
+            del made                                       # (P, G1, G2, dA and R are free before the caller allocates anything)
+            return gX, gW1, gb1, gW2, gb2, None, None, None, None, None
+        G1, G2 = _ngcf_back_gate(ctx.adj.graph, g, out, rnorm, gate, ctx.activation, ctx.dropout)
         gb1 = G1.contiguous().sum(dim=0).reshape(ctx.bias_shapes[0]) if ctx.bias_shapes[0] is not None and need[2] else None
         gb2 = G2.contiguous().sum(dim=0).reshape(ctx.bias_shapes[1]) if ctx.bias_shapes[1] is not None and need[4] else None
         gW1 = _dense_wgrad(X * A, G1) if need[1] else None
@@ -1795,7 +1861,7 @@ class _NGCFStep(torch.autograd.Function):
             dA = torch.addcmul(Q2, Q1, X)                   # Q1 * X + Q2
             del Q2
             gX = torch.addcmul(_launch(ctx.adj, dA, None, 1.0, 0.0, nat.ACT_NONE, transposed=True), Q1, A)
-        return gX, gW1, gb1, gW2, gb2, None, None, None, None
+        return gX, gW1, gb1, gW2, gb2, None, None, None, None, None
 
 
 def _ngcf_act(x, activation):
@@ -1820,7 +1886,7 @@ def _ngcf_composed(adj, X, W1, b1, W2, b2, activation, dropout, normalize):
 
 
 def ngcf_step(adj: Adjacency, X: torch.Tensor, W1: torch.Tensor, b1, W2: torch.Tensor, b2, activation="leaky", dropout=None,
-              normalize=True) -> torch.Tensor:
+              normalize=True, backward="composed") -> torch.Tensor:
     """NGCFLayer (gcn.py:116-135) as one launch (gnx_ngcf_step; opt-in, GNN(ngcf_layer="fused")):
     l2_normalize(drop(act((X * (A . X)) . W1 + b1) + act((A . X) . W2 + b2))) with ``X`` [n, C_in], ``W1`` / ``W2`` [C_in, C_out], ``b1`` /
     ``b2`` [C_out] / [1, C_out] or None and ``activation`` ``"leaky"`` (tf.nn.leaky_relu's slope 0.2), ``"relu"`` or ``"none"``.  For
@@ -1830,15 +1896,23 @@ def ngcf_step(adj: Adjacency, X: torch.Tensor, W1: torch.Tensor, b1, W2: torch.T
     before the norm in the same launch.  ``normalize=False`` stops before the norm (what a caller with torch's dropout needs).
     Under autograd it is one node that saves (A . X, the gate bits, the reciprocal norms, out, W1, W2) beside its input X; the backward
     is one gate pass (gnx_ngcf_back_gate) and today's kernels: the column sums, gnx_dense_wgrad, gnx_dense and the transposed SpMM.
+    ``backward``: ``"composed"`` (the default: those calls, today's bits) or ``"fused"`` (opt-in; GNN(ngcf_backward="fused")): for
+    C_in in {16, 32, 64}, C_out <= C_in and aligned rows ONE launch (gnx_step_back_ngcf) makes the gated gradients, both bias sums,
+    X * A, G1 W1^T and G2 W2^T on the matrix cores (W1 / W2 read as stored), dA and Q1 * A; the transposed SpMM mixes Q1 * A in, and
+    gnx_dense_wgrad runs twice.  out, dW1 and dW2 keep their bits; dX and the bias gradients agree to float32 rounding (one fused
+    multiply-add where torch rounds twice; slab-ordered sums).  P and dX are made only where W1 and X need a gradient.  A second
+    backward over a retained graph works and gives the same bits.  It acts under autograd only; other widths keep the composed calls.
     CPU tensors, an adjacency with a diagonal and a DroppedAdjacency run today's ops."""
     if activation not in NGCF_ACTIVATIONS:
         raise Exception("ngcf_step: activation must be one of " + ", ".join(repr(a) for a in NGCF_ACTIVATIONS))
+    if backward not in NGCF_BACKWARDS:
+        raise Exception("ngcf_step: backward must be one of " + ", ".join(repr(b) for b in NGCF_BACKWARDS))
     tensors = tuple(t for t in (X, W1, b1, W2, b2) if t is not None)
     if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors) or adj.diag is not None or isinstance(adj, DroppedAdjacency):
         return _ngcf_composed(adj, X, W1, b1, W2, b2, activation, dropout, bool(normalize))
     dropout = _dropout_triple(dropout, "ngcf_step")
     if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
-        return _NGCFStep.apply(X, W1, b1, W2, b2, adj, activation, dropout, bool(normalize))
+        return _NGCFStep.apply(X, W1, b1, W2, b2, adj, activation, dropout, bool(normalize), backward)
     return _ngcf_launch(adj, X, W1, b1, W2, b2, activation, keep=False, dropout=dropout, normalize=bool(normalize))[0]
 
 

@@ -69,7 +69,8 @@ const char *gnx_last_error(void);
  * spectral-preserving GCNII layer in one launch (gnx_gcnii_step_spectral, gnx_gcnii_spectral_back), likewise, and the gather hints of
  * the wide eval launches (gnx_graph_set_gather_hints, gnx_graph_gather_hints, GNX_RESERVE_GATHER_HINTS), likewise, and the GCN layer
  * in one launch (gnx_gcn_step, gnx_gcn_step_dropped) with its input gradient (gnx_gcn_step_back, gnx_gcn_step_back_dropped), likewise,
- * and the NGCF layer in one launch with its backward's gate (gnx_ngcf_step, gnx_ngcf_back_gate, GNX_ACT_LEAKY), likewise, and the link
+ * and the NGCF layer in one launch with its backward's gate (gnx_ngcf_step, gnx_ngcf_back_gate, GNX_ACT_LEAKY) and the rest of its backward in
+ * one launch (gnx_step_back_ngcf), likewise, and the link
  * task on the device (gnx_sample_negatives, gnx_edge_plan_bytes, gnx_edge_plan, gnx_edge_sorted_work_floats,
  * gnx_edge_scores_backward_sorted), likewise, and the ranking evaluation of the link task (gnx_rank_candidates_bytes,
  * gnx_rank_candidates, GNX_RANK_MAX_K, GNX_RANK_POS_PASS, GNX_RANK_MAX_SPLITS), likewise. */
@@ -814,6 +815,44 @@ int gnx_ngcf_step(gnx_graph_t g, const float *d_vals, const float *d_X, int64_t 
 int gnx_ngcf_back_gate(gnx_graph_t g, const float *d_g, int64_t ldg, const float *d_y, int64_t ldy, const float *d_rnorm,
                        const uint32_t *d_gate, int64_t n_rows, int64_t C_out, int act, double dropout_p, uint64_t seed,
                        uint64_t stream_id, float *d_G1, float *d_G2, int64_t ldG, void *stream);
+
+/* gnx_step_back_ngcf (training, opt-in; added within ABI 0.9 -- probe for the symbol): the backward of gnx_ngcf_step around its two
+ * weight gradients, from what the forward kept -- X (ldx), A = d_agg [n, C_in] contiguous, d_gate, d_rnorm, y (ldy) -- and the
+ * upstream gradient g (ldg), over the handle's n rows:
+ *   G1, G2 = gnx_ngcf_back_gate's        db1 = sum_rows G1       db2 = sum_rows G2       P = X * A
+ *   Q1 = G1 . W1^T      Q2 = G2 . W2^T      dA = Q1 * X + Q2      R = Q1 * A      dX = A_hat^T . dA + R
+ * (dW1 = P^T . G1 and dW2 = A^T . G2 stay with gnx_dense_wgrad.)  For C_in in {16, 32, 64}, 1 <= C_out <= C_in, ldx % 4 == 0,
+ * ldG % 4 == 0 and 16-byte aligned X / d_agg / G1 / G2 / P / dA / R; anything else returns GNX_ERR_UNSUPPORTED naming the width or the
+ * alignment, nothing launched: there is no composed form inside the entry, callers keep the composed backward there.
+ * ONE row-local launch without a gather: a wave takes 16 rows, makes their G1 / G2 with the arithmetic of gnx_ngcf_back_gate -- bit
+ * for bit its results; written at row stride ldG with zeros in the columns C_out .. roundup4(C_out) - 1 --, puts G2 and then G1
+ * through one tile in LDS against W2^T and W1^T (read from W1 / W2 [C_in, C_out] as stored, ldw1 / ldw2, laid down transposed in LDS:
+ * no transposed copy is needed) on v_mfma_f32_16x16x4_f32, and walks the rows.
+ * Rounding points: G1 / G2 as gnx_ngcf_back_gate; P one multiply; each Q the f32 MFMA sum over the output columns ascending;
+ * dA = fmaf(Q1, X, Q2), one rounding; R one multiply.  db: a block covers a contiguous range of rows that depends on n alone, adds
+ * the G1 / G2 columns of its rows in a fixed order into slab b of d_work, and two finishing launches add the slabs in index order, in groups of 64 and then the group sums -- no
+ * float atomics: two calls give the same bits.
+ * Then, when d_dX is given, gnx_spmm_tv(d_dA, H0 = d_R, beta = 1, alpha = 1) into d_dX (lddx) inside the call: d_vals_t the
+ * adjacency's values in transposed order (NULL: the raw values); hub rows of the transposed structure are that launch's business.
+ * d_dA and d_R: caller buffers [n, C_in] contiguous, observable afterwards.  d_dX == NULL: no products and no SpMM (X needs no
+ * gradient); d_dA, d_R, d_W1 and d_W2 may then be NULL and are not looked at.  d_P, d_db1, d_db2 may each be NULL.  d_dX is a buffer
+ * of its own (it may NOT be d_R).
+ * d_work / work_floats (only where d_db1 or d_db2 is given): with s = max(1, min(8192, ceil(ceil(n / 16) / 4))) slabs,
+ *     work_floats >= (s + ceil(s / 64)) * 2 * C_out
+ * -- a slab per block and, behind them, a sum per group of 64 slabs (the finishing launches add the groups, then the group sums).
+ * Too little is refused and the message names the figure.
+ * Checked before anything is launched (a refused call writes nothing): the checks of gnx_ngcf_back_gate, the widths, pointers and
+ * strides, a square stand-alone graph; every output -- G1, G2, P, db1, db2, dA, R, dX, d_work -- is a buffer of its own.
+ * Stream-ordered and allocation-free once the handle is reserved; under capture the transposed structure and the long-row slab at
+ * width C_in must exist already (gnx_graph_reserve with GNX_RESERVE_TRANSPOSED), as for gnx_spmm_tv.
+ * Reports "k_ngcf_back<C_in>" (+ "_drop" with a mask, + "+spmm_tv" when dX ran).
+ * (The layer's name stands behind the verb in this entry's name; gnx_ngcf_step and gnx_ngcf_back_gate keep theirs.) */
+int gnx_step_back_ngcf(gnx_graph_t g, const float *d_vals_t, const float *d_g, int64_t ldg, const float *d_y, int64_t ldy,
+                       const float *d_rnorm, const uint32_t *d_gate, int64_t C_out, int act, double dropout_p, uint64_t seed,
+                       uint64_t stream_id, const float *d_X, int64_t ldx, const float *d_agg, int64_t C_in, const float *d_W1,
+                       int64_t ldw1, const float *d_W2, int64_t ldw2, float *d_G1, float *d_G2, int64_t ldG, float *d_P, float *d_db1,
+                       float *d_db2, float *d_dA, float *d_R, float *d_dX, int64_t lddx, float *d_work, int64_t work_floats,
+                       void *stream);
 
 /* ---- the dense ends of the path (matrix cores) -----------------------------------------------------------------------
  * gnx_dense: out = act(X . W + bias) -- Dense.__forward__ (gnntf/core/nn/layers.py:135-136) and the transform of
