@@ -6,46 +6,15 @@
 //   k_ngcf_back        the backward around the transposed SpMM in one launch (gnx_step_back_ngcf): the gate, G1 . W1^T and G2 . W2^T
 //                      through one tile per wave, dA, R and P from the walk, the bias sums as slabs (k_ngcf_back_sums adds them)
 //   ngcf_forward       gnx_ngcf_step (gnx_ngcf_back_gate and gnx_step_back_ngcf are entries of their own)
-#include "gnx_layer_device.h"
+#include "gnx_ngcf_device.h"
 
 namespace {
 
 // ---- NGCF layer: SpMM + both transforms + the activations' sum + mask + row norm, one launch (gnx_ngcf_step) ------------------------------
 //   A = sum_j Ahat[i,j] X[j,:]   P1 = (X[i,:] * A) . W1 + b1   P2 = A . W2 + b2   out = l2_normalize(drop(act(P1) + act(P2)))  (gcn.py:116-135)
-// The pieces of the finished value that the fused launch and the row pass behind the dense kernel (k_ngcf_tail) share, so that a row is
-// finished by the same code whichever path made its pre-activations:
-//   ngcf_act        act(v): the identity, the relu of tile_times_Ms, or tf.nn.leaky_relu's v > 0 ? v : 0.2f v
-//   ngcf_mask_sq    x <- drop(x) for columns c .. c + VEC - 1 of a row, then ss <- fmaf(x[v], x[v], ss) over the columns below C_out in
-//                   ascending order: a lane's share of the row's sum of squares, one fmaf chain
-//   ngcf_row_sum    the lanes of a row (GL consecutive lanes, GL a power of two) add their shares through xor-shuffles, strides 1, 2, ..
-//                   GL / 2: every lane ends with the same bits, and lanes that hold +0 beyond a narrower row leave them unchanged
-//   ngcf_rnorm      r = 1 / sqrt(max(ss, 1e-12f)) -- IEEE sqrt and divide, correctly rounded each -- and whether the clamp acted
-__device__ __forceinline__ float ngcf_act(float v, int act) {
-    if (act == GNX_ACT_RELU) return fmaxf(v, 0.f);
-    if (act == GNX_ACT_LEAKY) return v > 0.f ? v : 0.2f * v;
-    return v;
-}
-
-template <int VEC, bool DROP>
-__device__ __forceinline__ float ngcf_mask_sq(const DropFuse &f, uint64_t stream, int64_t row, int64_t c, int64_t C_out, float (&x)[VEC], float ss) {
-    if constexpr (DROP) drop_values<VEC>(f, stream, row, c, x);
-#pragma unroll
-    for (int v = 0; v < VEC; ++v)
-        if (c + v < C_out) ss = fmaf(x[v], x[v], ss);
-    return ss;
-}
-
-template <int GL>
-__device__ __forceinline__ float ngcf_row_sum(float ss) {
-#pragma unroll
-    for (int m = 1; m < GL; m <<= 1) ss += __shfl_xor(ss, m);
-    return ss;
-}
-
-__device__ __forceinline__ float ngcf_rnorm(float ss, bool &clamped) {
-    clamped = !(ss >= 1e-12f);
-    return 1.0f / sqrtf(fmaxf(ss, 1e-12f));
-}
+// The pieces of the finished value that the fused launch and the row pass behind the dense kernel (k_ngcf_tail) share -- ngcf_act,
+// ngcf_mask_sq, ngcf_row_sum, ngcf_rnorm -- stand in gnx_ngcf_device.h, beside the checks of the forward entries: the row-local launch
+// of gnx_ngcf_wide.hip finishes its rows with them too.
 
 // d <- tile . Ms + bias, KEPT IN THE ACCUMULATOR REGISTERS: tile_times_Ms (BIAS, NTN) without the activation and without the way back
 // through the tile -- a sibling, not more template parameters of tile_times_Ms, so that its instantiations stay the ones measured.  On
@@ -563,8 +532,6 @@ const char *const kNgcfFused[3][2][2][2] = {GNX_NGCF_NAMES("16"), GNX_NGCF_NAMES
 const char *const kNgcfComposed[2][2] = {{"spmm+dense_mfma_ngcf", "spmm+dense_mfma_ngcf_norm"}, {"spmm+dense_mfma_ngcf_drop", "spmm+dense_mfma_ngcf_drop_norm"}};
 #undef GNX_NGCF_NAMES
 
-struct NgcfOut { float *out; int64_t ldo; float *agg; uint32_t *gate; float *rnorm; float *work; int64_t work_floats; };
-
 // out = l2_normalize(drop(act((X * (A . X)) . W1 + b1) + act((A . X) . W2 + b2))).  The fused launch takes C_in = 16, 32 or 64 with
 // C_out <= C_in over 16-byte aligned rows; its hub rows, and every row of everything else, are composed inside this call: the
 // aggregated rows at T (d_agg, else the first roundup4(n C_in) floats of d_work), the product pass into compact rows, the dense kernel
@@ -572,29 +539,8 @@ struct NgcfOut { float *out; int64_t ldo; float *agg; uint32_t *gate; float *rno
 int ngcf_forward(const char *fn, gnx_graph *g, const float *d_vals, const float *d_X, int64_t ldx, int64_t C_in, const float *d_W1, int64_t ldw1,
                  const float *d_W2, int64_t ldw2, int64_t C_out, const float *d_b1, const float *d_b2, int act, const DropFuse *fd, int normalize,
                  const NgcfOut &o, void *stream) {
-    GNX_CHECK_ARG(g != nullptr, "%s: NULL handle", fn);
-    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU || act == GNX_ACT_LEAKY, "%s: invalid activation %d", fn, act);
-    GNX_CHECK_ARG(normalize == 0 || normalize == 1, "%s: normalize must be 0 or 1", fn);
-    GNX_CHECK_ARG(C_in >= 1 && C_in <= (1 << 20) && C_out >= 1 && C_out <= (1 << 20), "%s: widths %lld -> %lld not in [1, 2^20]", fn,
-                  (long long)C_in, (long long)C_out);
-    GNX_CHECK_ARG(d_X != nullptr && d_W1 != nullptr && d_W2 != nullptr && o.out != nullptr, "%s: NULL X / W1 / W2 / out", fn);
-    GNX_CHECK_ARG(ldx >= C_in, "%s: ldx %lld < C_in %lld", fn, (long long)ldx, (long long)C_in);
-    GNX_CHECK_ARG(ldw1 >= C_out && ldw2 >= C_out, "%s: ldw1 %lld or ldw2 %lld < C_out %lld", fn, (long long)ldw1, (long long)ldw2, (long long)C_out);
-    GNX_CHECK_ARG(o.ldo >= C_out, "%s: ldo %lld < C_out %lld", fn, (long long)o.ldo, (long long)C_out);
-    GNX_CHECK_ARG(o.rnorm == nullptr || normalize, "%s: d_rnorm without normalize", fn);
-    GNX_CHECK_ARG(o.work_floats >= 0 && (o.work != nullptr || o.work_floats == 0), "%s: work_floats %lld without d_work, or negative", fn,
-                  (long long)o.work_floats);
-    GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "%s: needs a square graph", fn);
-    auto input = [&](const void *b) {
-        return b == d_X || b == d_W1 || b == d_W2 || (d_b1 && b == d_b1) || (d_b2 && b == d_b2) || (d_vals && b == d_vals);
-    };
-    const void *gate = o.gate, *rnorm = o.rnorm;
-    GNX_CHECK_ARG(!input(o.out), "%s: out must not alias an input (X / W1 / W2 / the biases / the values)", fn);
-    GNX_CHECK_ARG(o.agg == nullptr || (!input(o.agg) && o.agg != o.out), "%s: d_agg must be a buffer of its own", fn);
-    GNX_CHECK_ARG(gate == nullptr || (!input(gate) && gate != o.out && gate != o.agg), "%s: d_gate must be a buffer of its own", fn);
-    GNX_CHECK_ARG(rnorm == nullptr || (!input(rnorm) && rnorm != o.out && rnorm != o.agg && rnorm != gate), "%s: d_rnorm must be a buffer of its own", fn);
-    GNX_CHECK_ARG(o.work == nullptr || (!input(o.work) && o.work != o.out && o.work != o.agg && o.work != gate && o.work != rnorm),
-                  "%s: d_work must be a buffer of its own", fn);
+    const int admitted = ngcf_admit(fn, g, d_vals, d_X, ldx, C_in, d_W1, ldw1, d_W2, ldw2, C_out, d_b1, d_b2, act, normalize, o);
+    if (admitted != GNX_OK) return admitted;
     const Csr &m = g->a;
     const int64_t n = m.n_rows;
     const bool fusable = fused_width(C_in) && C_out <= C_in && ldx % 4 == 0 && aligned(d_X, 16) && aligned(o.agg, 16) && aligned(o.work, 16);

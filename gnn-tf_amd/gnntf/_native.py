@@ -146,6 +146,9 @@ SIGNATURES = {
                                    c_uint64, c_uint64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                    c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
                                    c_void_p]),
+    "gnx_step_wide_ngcf": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p,
+                                   c_void_p, c_int, c_double, c_uint64, c_uint64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_int64, c_void_p]),
     "gnx_dense": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int64,
                           c_void_p]),
     "gnx_dense_wgrad": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
@@ -174,7 +177,15 @@ SIGNATURES = {
     "gnx_graph_last_kernel": (c_char_p, [c_void_p]),
 }
 
+# entries added within ABI 0.9 that a library of the same minor version may lack: found by probing (has_symbol); their callers raise
+PROBED = ("gnx_step_wide_ngcf",)
+
 _lib = None
+
+
+def has_symbol(name: str) -> bool:
+    """Whether the loaded library exports ``name`` (the entries of PROBED)."""
+    return hasattr(lib(), name)
 
 
 def lib():
@@ -186,6 +197,8 @@ def lib():
                             f"`make -C gnn-tf_amd/csrc` (or __graft_entry__.build()); there is no CPU fallback")
         handle = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in SIGNATURES.items():
+            if name in PROBED and not hasattr(handle, name):
+                continue
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

@@ -53,7 +53,7 @@ class GNN(Trainable):
                  training_dtype=torch.float32, train_gather_order="auto", gcnii_backward="composed", feature_dropout="torch",
                  gcnii_training_dtype=torch.float32, gcnii_weight_gradient="stored", gcnii_spectral="composed",
                  gcnii_edge_dropout="composed", gcn_layer="composed", gcn_backward="composed", ngcf_layer="composed",
-                 ngcf_backward="composed"):
+                 ngcf_backward="composed", ngcf_wide="composed"):
         """``reorder`` (opt-in, not in the reference): store the graph and the feature rows with the vertices relabelled; every
         [N, .] tensor inside the model then lives in that order, and the model's OUTPUT is put back into the caller's order, so
         tasks, labels and node ids are unaffected.  Results agree with the unordered model to float32 rounding.
@@ -205,11 +205,22 @@ class GNN(Trainable):
         in, and gnx_dense_wgrad runs twice -- instead of the column sums, a torch multiply, gnx_dense twice and two addcmul passes.
         It works with the mask in the launch and with torch's dropout and normalize alike.  The forward, dW1 and dW2 keep their
         bits; dX and the bias gradients agree to float32 rounding (why the default stays ``"composed"``; measurement:
-        profiles/NOTES.md "Fused NGCF backward").  The node keeps its saved tensors: a second backward over a retained graph works."""
+        profiles/NOTES.md "Fused NGCF backward").  The node keeps its saved tensors: a second backward over a retained graph works.
+        ``ngcf_wide`` (not in the reference): ``"composed"`` (the default: today's calls and bits) or ``"fused"`` (sparse.ngcf_step
+        ``wide``).  It acts together with ``ngcf_layer="fused"`` and is inert otherwise: a layer of input width 128 -- the width of the
+        library_recommendation demo -- that meets every other condition of ``ngcf_layer`` then runs as the SpMM and ONE row-local launch
+        (gnx_step_wide_ngcf: both transforms on the matrix cores with the weights in LDS, the gate words, the activations' sum, the mask
+        and the norm over rows read once) instead of the SpMM and the sixteen torch passes around it, in the same three forms: eval mode
+        or a dropout of 0, the mask in the launch under ``feature_dropout="fused"``, or the launch without the norm followed by
+        torch's dropout and normalize.  The backward is the composed one of ``ngcf_layer`` (``ngcf_backward="fused"`` has no launch at
+        this width).  The results agree with the composed layer to float32 rounding (measurement: profiles/NOTES.md "NGCF layer at
+        width 128").  A model built without the keyword makes today's calls at every width."""
         if ngcf_layer not in sparse.NGCF_LAYERS:
             raise Exception("GNN: ngcf_layer must be one of " + ", ".join(repr(f) for f in sparse.NGCF_LAYERS))
         if ngcf_backward not in sparse.NGCF_BACKWARDS:
             raise Exception("GNN: ngcf_backward must be one of " + ", ".join(repr(b) for b in sparse.NGCF_BACKWARDS))
+        if ngcf_wide not in sparse.NGCF_WIDES:
+            raise Exception("GNN: ngcf_wide must be one of " + ", ".join(repr(w) for w in sparse.NGCF_WIDES))
         if gcn_backward not in sparse.GCN_BACKWARDS:
             raise Exception("GNN: gcn_backward must be one of " + ", ".join(repr(b) for b in sparse.GCN_BACKWARDS))
         if gcn_layer not in sparse.GCN_LAYERS:
@@ -246,6 +257,7 @@ class GNN(Trainable):
         self.gcn_backward = gcn_backward
         self.ngcf_layer = ngcf_layer
         self.ngcf_backward = ngcf_backward
+        self.ngcf_wide = ngcf_wide
         self._order = self._newid = None
         self.reorder_used, self.locality_share = None, None
         if isinstance(graph, sparse.DeviceGraph):
@@ -778,12 +790,14 @@ class NGCFLayer(Layer):
         return rows, outputs
 
     def _fused_ngcf(self, gcn, features) -> bool:
-        """Whether GNN(ngcf_layer="fused") applies to this forward (no tensor is read, no mask stream is drawn)."""
+        """Whether GNN(ngcf_layer="fused") applies to this forward (no tensor is read, no mask stream is drawn); at an input width of
+        128 only together with GNN(ngcf_wide="fused")."""
+        widths = sparse.NGCF_FUSED_WIDTHS + (sparse.NGCF_WIDE_WIDTHS if getattr(gcn, "ngcf_wide", "composed") == "fused" else ())
         return (getattr(gcn, "ngcf_layer", "composed") == "fused" and type(self) is NGCFLayer
                 and (self.activation is leaky_relu or self.activation is relu or self.activation is linear)
                 and isinstance(self.b1, torch.Tensor) == isinstance(self.b2, torch.Tensor)
                 and isinstance(features, torch.Tensor) and features.is_cuda and features.dtype == torch.float32
-                and features.shape[1] in sparse.NGCF_FUSED_WIDTHS and self.W1.shape[1] <= features.shape[1]
+                and features.shape[1] in widths and self.W1.shape[1] <= features.shape[1]
                 and self.adjacency.diag is None)
 
     def __forward__(self, gcn, features):
@@ -794,6 +808,10 @@ class NGCFLayer(Layer):
             # GNN(ngcf_backward=): named only where it is not the default, so the default's calls stay today's, argument for argument
             how = getattr(gcn, "ngcf_backward", "composed")
             back = dict() if how == "composed" else dict(backward=how)
+            # GNN(ngcf_wide=): likewise, and only at the widths it acts on
+            wide = getattr(gcn, "ngcf_wide", "composed")
+            if wide != "composed" and features.shape[1] in sparse.NGCF_WIDE_WIDTHS:
+                back["wide"] = wide
             if not gcn.is_training() or self.dropout == 0:
                 return sparse.ngcf_step(self.adjacency, features, self.W1, b1, self.W2, b2, activation=act, **back)
             if getattr(gcn, "feature_dropout", "torch") == "fused" and 0 < self.dropout < 1:

@@ -1690,6 +1690,8 @@ def gcn_step(adj: Adjacency, X: torch.Tensor, W: torch.Tensor, bias=None, relu=T
 NGCF_LAYERS = ("composed", "fused")
 NGCF_BACKWARDS = ("composed", "fused")
 NGCF_FUSED_WIDTHS = (16, 32, 64)      # C_in of the one-launch form of gnx_ngcf_step; its C_out is any width up to C_in
+NGCF_WIDES = ("composed", "fused")
+NGCF_WIDE_WIDTHS = (128,)             # C_in of gnx_step_wide_ngcf (the SpMM, then one row-local launch); C_out any width up to C_in
 NGCF_ACTIVATIONS = {"none": nat.ACT_NONE, "relu": nat.ACT_RELU, "leaky": nat.ACT_LEAKY}
 NGCF_SLOPES = {"none": 1.0, "relu": 0.0, "leaky": 0.2}
 
@@ -1704,10 +1706,17 @@ def _ngcf_work_floats(n, C_in, C_out, composed_rows, has_agg):
     return (0 if has_agg else up4(n * C_in)) + up4(composed_rows * C_in) + composed_rows * C_out
 
 
-def _ngcf_launch(adj: Adjacency, X, W1, b1, W2, b2, activation, keep, dropout=None, normalize=True):
+def _ngcf_wide_fusable(wide, X, C_in, C_out):
+    """Where ``wide="fused"`` has a launch (gnx_step_wide_ngcf): C_in = 128, C_out <= C_in, 16-byte aligned rows of X."""
+    return wide == "fused" and C_in in NGCF_WIDE_WIDTHS and C_out <= C_in and X.stride(0) % 4 == 0 and X.data_ptr() % 16 == 0
+
+
+def _ngcf_launch(adj: Adjacency, X, W1, b1, W2, b2, activation, keep, dropout=None, normalize=True, wide="composed"):
     """gnx_ngcf_step; returns (out, agg, gate, rnorm).  ``keep`` (training): the launch also writes the aggregated rows A . X, the gate
     words (int32 [n, 2 ceil(C_out / 32)]: the P1 words, then the P2 words; none for the identity) and, with ``normalize``, the rows'
-    reciprocal norms (negative where the clamp acted); all None otherwise.  ``dropout`` = the checked (p, seed, stream) or None."""
+    reciprocal norms (negative where the clamp acted); all None otherwise.  ``dropout`` = the checked (p, seed, stream) or None.
+    ``wide="fused"``: where _ngcf_wide_fusable says so the call is gnx_step_wide_ngcf -- the same arguments, outputs and formats, and a
+    scratch of the aggregated rows alone where they are not kept; everything else is gnx_ngcf_step with today's arguments."""
     nat.require_cuda(X, W1, W2, b1, b2)
     X, W1, W2 = _as_f32_rows(X), _as_f32_rows(W1), _as_f32_rows(W2)
     g = adj.graph
@@ -1730,15 +1739,22 @@ def _ngcf_launch(adj: Adjacency, X, W1, b1, W2, b2, activation, keep, dropout=No
     gated = keep and activation != "none"
     gate = torch.empty((n, 2 * _gate_words(C_out)), dtype=torch.int32, device=X.device) if gated else None
     rnorm = torch.empty(n, dtype=torch.float32, device=X.device) if keep and normalize else None
-    floats = _ngcf_work_floats(n, C_in, C_out, g.n_hub_rows if one_launch else n, keep)
+    rows_launch = _ngcf_wide_fusable(wide, X, C_in, C_out)
+    if rows_launch and not nat.has_symbol("gnx_step_wide_ngcf"):
+        raise Exception("ngcf_step: wide=\"fused\" needs gnx_step_wide_ngcf, which this libgnx.so does not export: rebuild the library")
+    if rows_launch:
+        floats = 0 if keep else (n * C_in + 3) // 4 * 4
+    else:
+        floats = _ngcf_work_floats(n, C_in, C_out, g.n_hub_rows if one_launch else n, keep)
     work = torch.empty(floats, dtype=torch.float32, device=X.device) if floats else None
     p, seed, stream = _dropout_args(dropout)
     ldw = lambda W: W.stride(0) if C_in > 1 else C_out     # (torch calls a one-row matrix contiguous whatever its row stride says)
     with nat.on_device(X.device):
-        nat.check(nat.lib().gnx_ngcf_step(g.handle, nat.ptr(adj.vals), nat.ptr(X), X.stride(0), C_in, nat.ptr(W1), ldw(W1), nat.ptr(W2), ldw(W2),
-                                          C_out, nat.ptr(biases[0]), nat.ptr(biases[1]), NGCF_ACTIVATIONS[activation], p, seed, stream,
-                                          1 if normalize else 0, nat.ptr(out), out.stride(0), nat.ptr(agg), nat.ptr(gate), nat.ptr(rnorm),
-                                          nat.ptr(work), floats, nat.current_stream()))
+        entry = nat.lib().gnx_step_wide_ngcf if rows_launch else nat.lib().gnx_ngcf_step
+        nat.check(entry(g.handle, nat.ptr(adj.vals), nat.ptr(X), X.stride(0), C_in, nat.ptr(W1), ldw(W1), nat.ptr(W2), ldw(W2),
+                        C_out, nat.ptr(biases[0]), nat.ptr(biases[1]), NGCF_ACTIVATIONS[activation], p, seed, stream,
+                        1 if normalize else 0, nat.ptr(out), out.stride(0), nat.ptr(agg), nat.ptr(gate), nat.ptr(rnorm),
+                        nat.ptr(work), floats, nat.current_stream()))
     return out, agg, gate, rnorm
 
 
@@ -1825,10 +1841,11 @@ class _NGCFStep(torch.autograd.Function):
     tensors stay: a second backward over a retained graph gives the same bits."""
 
     @staticmethod
-    def forward(ctx, X, W1, b1, W2, b2, adj, activation, dropout, normalize, backward="composed"):
+    def forward(ctx, X, W1, b1, W2, b2, adj, activation, dropout, normalize, backward="composed", wide="composed"):
         ctx.adj, ctx.activation, ctx.dropout, ctx.backward = adj, activation, dropout, backward
         ctx.bias_shapes = tuple(None if b is None else tuple(b.shape) for b in (b1, b2))
-        out, agg, gate, rnorm = _ngcf_launch(adj, X, W1, b1, W2, b2, activation, keep=True, dropout=dropout, normalize=normalize)
+        how = dict() if wide == "composed" else dict(wide=wide)      # (named only where it is not the default: today's call otherwise)
+        out, agg, gate, rnorm = _ngcf_launch(adj, X, W1, b1, W2, b2, activation, keep=True, dropout=dropout, normalize=normalize, **how)
         ctx.save_for_backward(X, agg, gate, rnorm, out if normalize else None, W1, W2)
         return out
 
@@ -1847,7 +1864,7 @@ class _NGCFStep(torch.autograd.Function):
             gb1, gb2 = (None if made[k] is None else made[k].reshape(shape) for k, shape in zip(("db1", "db2"), ctx.bias_shapes))
             gX = made["dX"]
             del made                                       # (P, G1, G2, dA and R are free before the caller allocates anything)
-            return gX, gW1, gb1, gW2, gb2, None, None, None, None, None
+            return gX, gW1, gb1, gW2, gb2, None, None, None, None, None, None
         G1, G2 = _ngcf_back_gate(ctx.adj.graph, g, out, rnorm, gate, ctx.activation, ctx.dropout)
         gb1 = G1.contiguous().sum(dim=0).reshape(ctx.bias_shapes[0]) if ctx.bias_shapes[0] is not None and need[2] else None
         gb2 = G2.contiguous().sum(dim=0).reshape(ctx.bias_shapes[1]) if ctx.bias_shapes[1] is not None and need[4] else None
@@ -1861,7 +1878,7 @@ class _NGCFStep(torch.autograd.Function):
             dA = torch.addcmul(Q2, Q1, X)                   # Q1 * X + Q2
             del Q2
             gX = torch.addcmul(_launch(ctx.adj, dA, None, 1.0, 0.0, nat.ACT_NONE, transposed=True), Q1, A)
-        return gX, gW1, gb1, gW2, gb2, None, None, None, None, None
+        return gX, gW1, gb1, gW2, gb2, None, None, None, None, None, None
 
 
 def _ngcf_act(x, activation):
@@ -1886,7 +1903,7 @@ def _ngcf_composed(adj, X, W1, b1, W2, b2, activation, dropout, normalize):
 
 
 def ngcf_step(adj: Adjacency, X: torch.Tensor, W1: torch.Tensor, b1, W2: torch.Tensor, b2, activation="leaky", dropout=None,
-              normalize=True, backward="composed") -> torch.Tensor:
+              normalize=True, backward="composed", wide="composed") -> torch.Tensor:
     """NGCFLayer (gcn.py:116-135) as one launch (gnx_ngcf_step; opt-in, GNN(ngcf_layer="fused")):
     l2_normalize(drop(act((X * (A . X)) . W1 + b1) + act((A . X) . W2 + b2))) with ``X`` [n, C_in], ``W1`` / ``W2`` [C_in, C_out], ``b1`` /
     ``b2`` [C_out] / [1, C_out] or None and ``activation`` ``"leaky"`` (tf.nn.leaky_relu's slope 0.2), ``"relu"`` or ``"none"``.  For
@@ -1902,18 +1919,26 @@ def ngcf_step(adj: Adjacency, X: torch.Tensor, W1: torch.Tensor, b1, W2: torch.T
     gnx_dense_wgrad runs twice.  out, dW1 and dW2 keep their bits; dX and the bias gradients agree to float32 rounding (one fused
     multiply-add where torch rounds twice; slab-ordered sums).  P and dX are made only where W1 and X need a gradient.  A second
     backward over a retained graph works and gives the same bits.  It acts under autograd only; other widths keep the composed calls.
+    ``wide``: ``"composed"`` (the default: today's call) or ``"fused"`` (opt-in; GNN(ngcf_wide="fused")): for C_in = 128, C_out <= C_in
+    and aligned rows the call is gnx_step_wide_ngcf -- gnx_spmm into A . X, then ONE row-local launch that reads X and A . X once and
+    writes the finished rows, the gate words and the reciprocal norms in gnx_ngcf_step's formats -- instead of the SpMM, a product pass,
+    the dense kernel twice and a row pass inside gnx_ngcf_step.  The node and its composed backward are unchanged (``backward="fused"``
+    stays inert at this width); the results agree with the composed call to float32 rounding.  Other widths make today's call.
     CPU tensors, an adjacency with a diagonal and a DroppedAdjacency run today's ops."""
     if activation not in NGCF_ACTIVATIONS:
         raise Exception("ngcf_step: activation must be one of " + ", ".join(repr(a) for a in NGCF_ACTIVATIONS))
     if backward not in NGCF_BACKWARDS:
         raise Exception("ngcf_step: backward must be one of " + ", ".join(repr(b) for b in NGCF_BACKWARDS))
+    if wide not in NGCF_WIDES:
+        raise Exception("ngcf_step: wide must be one of " + ", ".join(repr(w) for w in NGCF_WIDES))
     tensors = tuple(t for t in (X, W1, b1, W2, b2) if t is not None)
     if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors) or adj.diag is not None or isinstance(adj, DroppedAdjacency):
         return _ngcf_composed(adj, X, W1, b1, W2, b2, activation, dropout, bool(normalize))
     dropout = _dropout_triple(dropout, "ngcf_step")
     if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
-        return _NGCFStep.apply(X, W1, b1, W2, b2, adj, activation, dropout, bool(normalize), backward)
-    return _ngcf_launch(adj, X, W1, b1, W2, b2, activation, keep=False, dropout=dropout, normalize=bool(normalize))[0]
+        return _NGCFStep.apply(X, W1, b1, W2, b2, adj, activation, dropout, bool(normalize), backward, wide)
+    how = dict() if wide == "composed" else dict(wide=wide)
+    return _ngcf_launch(adj, X, W1, b1, W2, b2, activation, keep=False, dropout=dropout, normalize=bool(normalize), **how)[0]
 
 
 GCNII_SPECTRALS = ("composed", "fused")

@@ -70,7 +70,7 @@ const char *gnx_last_error(void);
  * the wide eval launches (gnx_graph_set_gather_hints, gnx_graph_gather_hints, GNX_RESERVE_GATHER_HINTS), likewise, and the GCN layer
  * in one launch (gnx_gcn_step, gnx_gcn_step_dropped) with its input gradient (gnx_gcn_step_back, gnx_gcn_step_back_dropped), likewise,
  * and the NGCF layer in one launch with its backward's gate (gnx_ngcf_step, gnx_ngcf_back_gate, GNX_ACT_LEAKY) and the rest of its backward in
- * one launch (gnx_step_back_ngcf), likewise, and the link
+ * one launch (gnx_step_back_ngcf) and the layer at width 128 as the SpMM and one row-local launch (gnx_step_wide_ngcf), likewise, and the link
  * task on the device (gnx_sample_negatives, gnx_edge_plan_bytes, gnx_edge_plan, gnx_edge_sorted_work_floats,
  * gnx_edge_scores_backward_sorted), likewise, and the ranking evaluation of the link task (gnx_rank_candidates_bytes,
  * gnx_rank_candidates, GNX_RANK_MAX_K, GNX_RANK_POS_PASS, GNX_RANK_MAX_SPLITS), likewise. */
@@ -853,6 +853,38 @@ int gnx_step_back_ngcf(gnx_graph_t g, const float *d_vals_t, const float *d_g, i
                        int64_t ldw1, const float *d_W2, int64_t ldw2, float *d_G1, float *d_G2, int64_t ldG, float *d_P, float *d_db1,
                        float *d_db2, float *d_dA, float *d_R, float *d_dX, int64_t lddx, float *d_work, int64_t work_floats,
                        void *stream);
+
+/* gnx_step_wide_ngcf (opt-in; added within ABI 0.9 -- probe for the symbol): the layer of gnx_ngcf_step at C_in = 128, the width of
+ * the reference's library_recommendation demo, as the SpMM and ONE row-local launch.  The parameter list, the outputs and their
+ * formats are gnx_ngcf_step's -- d_gate [n, 2 * ceil(C_out / 32)], the P1 words then the P2 words, zero bits beyond C_out; d_rnorm
+ * negated (-1e6f) where the clamp acted; out written only below column C_out, whole 16-byte stores where ldo % 4 == 0 and out is
+ * 16-byte aligned, single values otherwise -- so gnx_ngcf_back_gate and a composed backward read them unchanged.
+ * Supported: C_in == 128, 1 <= C_out <= 128, ldx % 4 == 0, and X, d_agg and d_work 16-byte aligned.  Anything else returns
+ * GNX_ERR_UNSUPPORTED naming the widths or the alignment, nothing launched: callers keep gnx_ngcf_step there.
+ * Step A: gnx_spmm(X) into d_agg -- bit for bit gnx_spmm's result, hub rows included -- or, when d_agg is NULL, into the first
+ * roundup4(n * C_in) floats of d_work:
+ *     work_floats >= (d_agg ? 0 : roundup4(n * C_in))
+ * Too little is refused and the message names the figure.
+ * Step B: one launch over all n rows without a gather (hub rows need nothing of their own once A is in memory), a block of eight
+ * waves per CU, persistent over 16-row tiles; W1 and W2 sit in LDS in f32 (16 KiB per 16 output columns, 128 KiB at C_out > 112),
+ * zero-padded to a multiple of 16 columns there and nowhere else; a wave holds its rows of X and A as MFMA operand fragments in
+ * registers.
+ * Rounding points: A as in gnx_spmm; X * A one multiply; each P the f32 sum of v_mfma_f32_16x16x4_f32 over k ascending, then + bias;
+ * the activation (leaky: one multiply by 0.2f where P <= 0); one add; the mask (x * scale); with normalize the row's sum of squares
+ * over the columns below C_out -- lane cc of the row's 16 lanes holds the columns cc, 16 + cc, 32 + cc, ..: one fmaf chain over them
+ * ascending from 0, then the 16 lanes added through xor-shuffles at strides 1, 2, 4, 8 --, r = 1 / sqrt(max(sum, 1e-12f)) with the
+ * IEEE square root and division (each correctly rounded), and out = x * r.  (The lanes of a row hold other columns than in
+ * gnx_ngcf_step, so the sum of squares associates differently: the two entries agree to float32 rounding, not bit for bit.)  The
+ * order depends neither on n, nor on the grid, nor on the wave that takes a row; no float atomics: two calls give the same bits.
+ * Checked before anything is launched (a refused call writes nothing): the NULL handle and the dropout rate, the widths and the
+ * alignment (above), then the checks of gnx_ngcf_step, then work_floats.  Stream-ordered; under capture the long-row slab must
+ * already cover C_in (gnx_graph_reserve), as for gnx_spmm.
+ * Reports "spmm+k_ngcf_rows<128>" (+ "_drop" with a mask, + "_norm" with normalize).
+ * (The layer's name stands behind the verb in this entry's name, as in gnx_step_back_ngcf.) */
+int gnx_step_wide_ngcf(gnx_graph_t g, const float *d_vals, const float *d_X, int64_t ldx, int64_t C_in, const float *d_W1, int64_t ldw1,
+                       const float *d_W2, int64_t ldw2, int64_t C_out, const float *d_b1, const float *d_b2, int act, double dropout_p,
+                       uint64_t seed, uint64_t stream_id, int normalize, float *d_out, int64_t ldo, float *d_agg, uint32_t *d_gate,
+                       float *d_rnorm, float *d_work, int64_t work_floats, void *stream);
 
 /* ---- the dense ends of the path (matrix cores) -----------------------------------------------------------------------
  * gnx_dense: out = act(X . W + bias) -- Dense.__forward__ (gnntf/core/nn/layers.py:135-136) and the transform of
