@@ -256,6 +256,68 @@ __global__ void k_hint_columns(const int32_t *__restrict__ colidx, const int32_t
     hint_cols[k] = rank[c] < hot ? c : (int32_t)((uint32_t)c | 0x80000000u);
 }
 
+// pendant elision, plan.  A candidate: one entry (i, h), h != i, and h stores at least two ...
+__global__ void k_pend_candidates(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, int64_t n, uint8_t *__restrict__ flag) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t b = rowptr[i];
+    uint8_t f = 0;
+    if (rowptr[i + 1] - b == 1) {
+        const int64_t h = colidx[b];
+        f = h != i && rowptr[h + 1] - rowptr[h] >= 2;
+    }
+    flag[i] = f;
+}
+
+// ... which no row but h stores as a column (an integer store of 0; every writer writes the same value)
+__global__ void k_pend_disqualify(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx, const int32_t *__restrict__ rowidx,
+                                  int64_t nnz, uint8_t *__restrict__ flag) {
+    int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nnz) return;
+    const int32_t c = colidx[k];
+    if (flag[c] && colidx[rowptr[c]] != rowidx[k]) flag[c] = 0;
+}
+
+// rows with flag f (count[0]) and rows of exactly one entry (count[1])
+__global__ void k_pend_count(const int64_t *__restrict__ rowptr, const uint8_t *__restrict__ flag, int64_t n, unsigned long long *__restrict__ count) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool in = i < n;
+    const unsigned long long f = __popcll(__ballot(in && flag[i])), one = __popcll(__ballot(in && rowptr[i + 1] - rowptr[i] == 1));
+    if ((threadIdx.x & 63) == 0) {
+        if (f) atomicAdd(count, f);
+        if (one) atomicAdd(count + 1, one);
+    }
+}
+
+// out[k] = flag[rows[k]]: the sort key that moves the elidable rows of the one-entry bin behind the others, and the per-slot mark
+__global__ void k_pend_gather_flag(const int32_t *__restrict__ rows, const uint8_t *__restrict__ flag, int64_t n, uint8_t *__restrict__ out) {
+    int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) out[k] = flag[rows[k]];
+}
+
+// per entry the hinted column with PEND_COL_BIT where the column is elidable; a row that stores such an entry is marked
+__global__ void k_pend_columns(const int32_t *__restrict__ hint_cols, const int32_t *__restrict__ rowidx, const uint8_t *__restrict__ flag,
+                               int64_t nnz, int32_t *__restrict__ pend_cols, uint8_t *__restrict__ row_mark) {
+    int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nnz) return;
+    const int32_t j = hint_cols[k];
+    if (flag[j & 0x7fffffff]) {
+        pend_cols[k] = j | PEND_COL_BIT;
+        row_mark[rowidx[k]] = 1;
+    } else {
+        pend_cols[k] = j;
+    }
+}
+
+// per call: pend_w[i] = the value of the one entry of every elidable row i (`rows` = their slots of the row order)
+__global__ void k_pend_weights(const int32_t *__restrict__ rows, int64_t n, const int64_t *__restrict__ rowptr, const float *__restrict__ vals,
+                               float *__restrict__ pend_w) {
+    int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const int32_t i = rows[k];
+    pend_w[i] = vals[rowptr[i]];
+}
+
 __global__ void k_permute_vals(const float *__restrict__ vals, const int32_t *__restrict__ perm, int64_t n,
                                float *__restrict__ out) {
     int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -677,6 +739,107 @@ int gather_hints_for(gnx_graph *g, const Csr &m, int64_t C, hipStream_t s, const
     return GNX_OK;
 }
 
+// ---- pendant elision (gnx_graph_set_pendant_elision; PendantPart) ---------------------------------------------------------------
+static void drop_pendants(gnx_graph *g) { static_cast<PendantPart &>(*g) = PendantPart(); }
+
+static bool takes_pendant_elision(const gnx_graph *g) { return takes_gather_hints(g) && g->a.n_cols < (int64_t)PEND_COL_BIT; }
+
+// The elidable rows, their place at the end of the one-entry bin of a.row_order, and the marks.  Not under capture.  Launches in
+// flight on any stream may walk the row order while its last bin is rearranged: the device is synchronised first.  An allocation
+// that fails leaves the handle without elision (and the row order as it was).
+static int ensure_pendant_plan(gnx_graph *g, hipStream_t s) {
+    if (g->pend_built || g->pend_failed) return GNX_OK;
+    GNX_NOT_WHILE_CAPTURING(s, "the pendant plan of this handle (GNX_RESERVE_GATHER_HINTS)");
+    Csr &a = g->a;
+    const int64_t n = a.n_rows;
+    const dim3 threads(256), row_blocks(blocks_for(n));
+    PendantPart part;
+    DevArray<unsigned long long> count;
+    hipError_t e = part.pend_flag.alloc(n);
+    if (e == hipSuccess) e = part.pend_row_mark.alloc(n);
+    if (e == hipSuccess) e = part.pend_slot_mark.alloc(n);
+    if (e == hipSuccess) e = part.pend_cols.alloc(a.nnz);
+    if (e == hipSuccess) e = part.pend_w.alloc(n);
+    if (e == hipSuccess) e = count.alloc(2);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        g->pend_failed = true;
+        set_error("pendant elision: %s while allocating %lld bytes for the plan: this handle runs without it", hipGetErrorString(e),
+                  (long long)a.nnz * 4 + (long long)n * 7);
+        return GNX_OK;
+    }
+    GNX_HIP(hipMemsetAsync(count, 0, 2 * sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(k_pend_candidates, row_blocks, threads, 0, s, a.rowptr, a.colidx, n, part.pend_flag);
+    hipLaunchKernelGGL(k_pend_disqualify, dim3(blocks_for(a.nnz)), threads, 0, s, a.rowptr, a.colidx, g->rowidx, a.nnz, part.pend_flag);
+    hipLaunchKernelGGL(k_pend_count, row_blocks, threads, 0, s, a.rowptr, part.pend_flag, n, count);
+    unsigned long long host[2] = {0, 0};
+    GNX_HIP(hipMemcpyAsync(host, count, sizeof(host), hipMemcpyDeviceToHost, s));
+    GNX_HIP(hipStreamSynchronize(s));
+    part.n_pend = (int64_t)host[0];
+    part.pend_slot0 = a.n_nonempty - part.n_pend;
+    const int64_t n_one = (int64_t)host[1], one0 = a.n_nonempty - n_one;     // the one-entry bin: the last slots with entries
+    if (part.n_pend > 0 && part.n_pend < n_one) {
+        DevArray<uint8_t> k0, k1;
+        DevArray<int32_t> moved;
+        e = k0.alloc(n_one);
+        if (e == hipSuccess) e = k1.alloc(n_one);
+        if (e == hipSuccess) e = moved.alloc(n_one);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            g->pend_failed = true;
+            set_error("pendant elision: %s while allocating the scratch of the plan: this handle runs without it", hipGetErrorString(e));
+            return GNX_OK;
+        }
+        hipLaunchKernelGGL(k_pend_gather_flag, dim3(blocks_for(n_one)), threads, 0, s, a.row_order + one0, part.pend_flag, n_one, k0);
+        GNX_TRY((sort_pairs<uint8_t, int32_t>(k0, k1, a.row_order + one0, moved, n_one, 1u, s)));
+        GNX_HIP(hipDeviceSynchronize());
+        GNX_HIP(hipMemcpyAsync(a.row_order + one0, moved, (size_t)n_one * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        if (a.slot_beg != nullptr)
+            hipLaunchKernelGGL(k_slot_ptrs, dim3(blocks_for(n_one)), threads, 0, s, a.rowptr, a.row_order + one0, n_one, a.slot_beg + one0,
+                               a.slot_cnt + one0);
+    }
+    GNX_HIP(hipMemsetAsync(part.pend_row_mark, 0, (size_t)n, s));
+    GNX_HIP(hipStreamSynchronize(s));
+    GNX_HIP(hipGetLastError());
+    part.pend_built = true;
+    static_cast<PendantPart &>(*g) = std::move(part);
+    return GNX_OK;
+}
+
+// whether a K loop of C columns elides under the handle's setting: 1 wherever its launches take hints, -1 where the automatic hints are on
+static bool pendant_setting_on(const gnx_graph *g, int64_t C) {
+    if (g->pend_setting == 0 || !takes_pendant_elision(g) || hint_hot_rows(g, C) == 0) return false;
+    return g->pend_setting > 0 || g->hint_setting == -1;
+}
+
+int pendant_plan_for(gnx_graph *g, int64_t C, hipStream_t s, const int32_t **pend_cols) {
+    *pend_cols = nullptr;
+    if (!pendant_setting_on(g, C) || g->hint_cols == nullptr || g->pend_failed) return GNX_OK;
+    if (!g->pend_built) GNX_TRY(ensure_pendant_plan(g, s));
+    if (!g->pend_built || g->n_pend == 0) return GNX_OK;
+    if (g->pend_hot != g->hint_hot) {       // bit 31 of the hinted columns changed (or first use): one pass over the entries
+        if (stream_is_capturing(s)) {
+            if (g->pend_hot == -2) GNX_NOT_WHILE_CAPTURING(s, "the pendant plan of this handle (GNX_RESERVE_GATHER_HINTS)");
+        } else {
+            hipLaunchKernelGGL(k_pend_columns, dim3(blocks_for(g->a.nnz)), dim3(256), 0, s, g->hint_cols, g->rowidx, g->pend_flag, g->a.nnz,
+                               g->pend_cols, g->pend_row_mark);
+            hipLaunchKernelGGL(k_pend_gather_flag, dim3(blocks_for(g->a.n_rows)), dim3(256), 0, s, g->a.row_order, g->pend_row_mark, g->a.n_rows,
+                               g->pend_slot_mark);
+            GNX_HIP(hipGetLastError());
+            g->pend_hot = g->hint_hot;
+        }
+    }
+    *pend_cols = g->pend_cols;
+    return GNX_OK;
+}
+
+int pendant_weights(gnx_graph *g, const float *vals, hipStream_t s) {
+    hipLaunchKernelGGL(k_pend_weights, dim3(blocks_for(g->n_pend)), dim3(256), 0, s, g->a.row_order + g->pend_slot0, g->n_pend, g->a.rowptr, vals,
+                       g->pend_w);
+    GNX_HIP(hipGetLastError());
+    return GNX_OK;
+}
+
 static int finish_graph(gnx_graph *g, hipStream_t s) {
     GNX_TRY(build_long_plan(g->a, s));
     GNX_HIP(hipGetLastError());
@@ -721,6 +884,7 @@ int gnx_graph_reserve(gnx_graph_t g, int64_t C, int flags, void *stream) {
     if (flags & GNX_RESERVE_GATHER_HINTS) {
         const int32_t *unused;
         GNX_TRY(gather_hints_for(g, g->a, C, s, &unused));
+        if (unused != nullptr) GNX_TRY(pendant_plan_for(g, C, s, &unused));     // (the K loop's pendant plan rides on the hints)
     }
     if (chunks > 0) return ensure_partial(g, (size_t)chunks * (size_t)C * sizeof(float), s);
     return GNX_OK;
@@ -763,6 +927,25 @@ int gnx_graph_gather_hints(gnx_graph_t g, const int32_t **d_hint_cols, int64_t *
     return GNX_OK;
 }
 
+int gnx_graph_set_pendant_elision(gnx_graph_t g, int mode, void *stream) {
+    GNX_CHECK_ARG(g != nullptr, "gnx_graph_set_pendant_elision: NULL handle");
+    GNX_CHECK_ARG(mode >= -1 && mode <= 1, "gnx_graph_set_pendant_elision: mode %d is neither -1 (automatic), 0 (off) nor 1 (on)", mode);
+    hipStream_t s = (hipStream_t)stream;
+    GNX_CHECK_ARG(!stream_is_capturing(s), "gnx_graph_set_pendant_elision: the stream is being captured -- set the mode before the capture begins");
+    g->pend_setting = mode;
+    g->pend_failed = false;
+    if (mode == 1 && takes_pendant_elision(g)) GNX_TRY(ensure_pendant_plan(g, s));
+    return GNX_OK;
+}
+
+int gnx_graph_pendant_elision(gnx_graph_t g, int64_t *n_elidable, const uint8_t **d_elidable, int *last_loop_elided) {
+    GNX_CHECK_ARG(g != nullptr, "gnx_graph_pendant_elision: NULL handle");
+    if (n_elidable) *n_elidable = g->pend_built ? g->n_pend : 0;
+    if (d_elidable) *d_elidable = g->pend_built ? g->pend_flag.get() : nullptr;
+    if (last_loop_elided) *last_loop_elided = g->last_pend ? 1 : 0;
+    return GNX_OK;
+}
+
 int gnx_graph_set_row_window(gnx_graph_t g, int64_t window_rows, void *stream) {
     GNX_CHECK_ARG(g != nullptr, "gnx_graph_set_row_window: NULL handle");
     GNX_CHECK_ARG(window_rows >= 0, "gnx_graph_set_row_window: negative window");
@@ -793,6 +976,7 @@ int gnx_graph_set_row_window(gnx_graph_t g, int64_t window_rows, void *stream) {
     if (g->has_r) drop_relabel(g);                                   // the degree-relabelled copy belongs to the default order,
     drop_gather_order(g);                                            // and so do the gather order and its per-entry columns
     drop_gather_hints(g);                                            // (a handle with a window takes no hints; back at 0 they are rebuilt)
+    drop_pendants(g);                                                // (nor pendant elision: its slots belong to the order dropped above)
     GNX_HIP(hipGetLastError());
     return GNX_OK;
 }

@@ -64,6 +64,12 @@ constexpr int64_t HINT_MIN_ROW_BYTES = 256;
 #ifndef GNX_GATHER_HINTS_DEFAULT
 #define GNX_GATHER_HINTS_DEFAULT (-1)
 #endif
+// Pendant elision (gnx_graph_set_pendant_elision): -1 = automatic, on exactly where the automatic gather hints are on; 0 = only on request
+#ifndef GNX_PENDANT_ELISION_DEFAULT
+#define GNX_PENDANT_ELISION_DEFAULT (-1)
+#endif
+constexpr int32_t PEND_COL_BIT = 1 << 30;             // pend_cols: the column is an elidable row
+constexpr int32_t PEND_COL_MASK = PEND_COL_BIT - 1;   // ... and its number (bit 31 stays the gather hint)
 constexpr int SMALL_LONG_ROW = GNX_LONG_ROW < 128 ? GNX_LONG_ROW : 128;
 
 // An owned device array.  Everything a handle keeps on the device, and every temporary of its builds, is one of these, so dropping a
@@ -180,9 +186,27 @@ struct GatherHintsPart {
     bool hint_failed = false;        // the arrays could not be allocated: the handle runs unhinted and does not try again
 };
 
+// pendant elision of the K loop (lazy; gnx_graph_set_pendant_elision; handles that take gather hints, fewer than 2^30 columns).
+// An ELIDABLE row i stores exactly one entry (i, h), h != i, h stores at least two entries, and no row but h stores an entry in
+// column i: the iterates of i between H0 and the result are read by h alone, which can form them itself from H0[i], pend_w[i] and
+// its own row of two iterations ago (gnx_spmm_eval.h, PEND).  Building the part moves the elidable rows to the END of the
+// one-entry bin of a.row_order (order inside a bin is free: equal lengths), so that the launches of the iterations between leave
+// them out by their slot numbers.
+struct PendantPart {
+    bool pend_built = false, pend_failed = false;
+    int64_t n_pend = 0;                     // elidable rows = slots [pend_slot0, a.n_nonempty) of a.row_order
+    int64_t pend_slot0 = 0;
+    DevArray<uint8_t> pend_flag;            // [n] 1 = the row is elidable
+    DevArray<uint8_t> pend_row_mark;        // [n] 1 = the row stores an entry whose column is elidable (read by the chunk kernels)
+    DevArray<uint8_t> pend_slot_mark;       // [n] the same per slot of a.row_order (read by the row kernels, coalesced)
+    DevArray<int32_t> pend_cols;            // [a.nnz] hint_cols with PEND_COL_BIT set where the column is elidable
+    int64_t pend_hot = -2;                  // the hint_hot whose bit 31 pend_cols carries
+    DevArray<float> pend_w;                 // [n] per call: the value of the one entry of every elidable row
+};
+
 }  // namespace gnx
 
-struct gnx_graph : gnx::TransposedPart, gnx::RelabelledPart, gnx::GatherOrderPart, gnx::GatherHintsPart {
+struct gnx_graph : gnx::TransposedPart, gnx::RelabelledPart, gnx::GatherOrderPart, gnx::GatherHintsPart, gnx::PendantPart {
     gnx::Csr a;            // coalesced matrix
     gnx::DevArray<float> raw_vals;     // [a.nnz] summed duplicate values
     gnx::DevArray<int32_t> rowidx;     // [a.nnz] row of every coalesced entry
@@ -211,6 +235,8 @@ struct gnx_graph : gnx::TransposedPart, gnx::RelabelledPart, gnx::GatherOrderPar
     const char *last_kernel = "";      // NOT owned: a string literal of the launcher
     int64_t last_hint_hot = 0;         // hot rows the last SpMM launch over this handle gathered with; 0 = it took no hints
     int64_t hint_setting = GNX_GATHER_HINTS_DEFAULT;   // gnx_graph_set_gather_hints: -1 automatic, 0 off, n > 0 that many hot rows
+    int pend_setting = GNX_PENDANT_ELISION_DEFAULT;    // gnx_graph_set_pendant_elision: -1 automatic, 0 off, 1 on wherever admissible
+    bool last_pend = false;                            // the last K loop over this handle elided its pendant rows
 };
 
 namespace gnx {
@@ -230,6 +256,12 @@ int ensure_relabel_features(gnx_graph *g, size_t bytes, hipStream_t s);
 // re-marks the array on first use and when the hot_rows in force changes; GNX_ERR_UNSUPPORTED, naming gnx_graph_reserve, where
 // that would allocate under capture.
 int gather_hints_for(gnx_graph *g, const Csr &m, int64_t C, hipStream_t s, const int32_t **hint_cols);
+// The pendant plan of a K loop of C columns over the handle's own matrix whose launches gather through `hint_cols` (not null), or
+// *pend_cols = null: elision is off, the handle does not take it, it has no elidable row, or the arrays could not be allocated.
+// Builds the part on first use and re-marks pend_cols when the hints' hot rows changed; GNX_ERR_UNSUPPORTED where that would
+// allocate under capture.
+int pendant_plan_for(gnx_graph *g, int64_t C, hipStream_t s, const int32_t **pend_cols);
+int pendant_weights(gnx_graph *g, const float *vals, hipStream_t s);   // per call: g->pend_w from the call's values
 
 // blocks of `per_block` items that cover n items
 inline unsigned blocks_for(int64_t n, int per_block = 256) { return (unsigned)((n + per_block - 1) / per_block); }

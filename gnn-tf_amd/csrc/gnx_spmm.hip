@@ -200,6 +200,7 @@ int gnx_appnp_propagate_act(gnx_graph_t g, const float *d_vals, const float *d_d
     GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols, "gnx_appnp_propagate: needs a square graph");
     GNX_CHECK_ARG(d_H0 && d_out && (K < 2 || d_work), "gnx_appnp_propagate: NULL buffer");
     GNX_CHECK_ARG(d_out != d_H0 && d_work != d_H0 && d_out != d_work, "gnx_appnp_propagate: H0, out and work must be distinct");
+    g->last_pend = false;
     if (K == 0) {
         GNX_HIP(hipMemcpyAsync(d_out, d_H0, (size_t)g->a.n_rows * C * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
         return GNX_OK;
@@ -242,6 +243,47 @@ int gnx_appnp_propagate_act(gnx_graph_t g, const float *d_vals, const float *d_d
     // A row without entries is act(a * H0) after every iteration and nobody's sum depends on when it was written: such rows are
     // computed the first time each of the two buffers is a destination (k = 0, 1) and left alone afterwards (GNX_ACT_SKIP_EMPTY)
     // -- on the R-MAT workloads 60 % of the rows, 7-10 % of an iteration's bytes.  Same arithmetic, same bits.
+    // Pendant rows (gnx_graph_set_pendant_elision): an elidable row's iterates between H0 and the result have one reader, its
+    // neighbour, which forms them itself (gnx_spmm_eval.h, PEND): the row is computed by the last iteration only, and no buffer
+    // receives it, or is read at it, before.  Where the launches take hints, at 4 values per lane on 16 or 32 lanes.
+    const int32_t *pend_cols = nullptr;
+    if (K >= 2 && d_diag == nullptr && C <= 128) {
+        SpmmArgs probe{};
+        set_operands<F32Rows>(probe, d_H0, C, d_H0, C, 0.f, 0.f, act, d_out, 0, C, C);
+        const int32_t *hint_cols = nullptr;
+        if (F32Rows::vec(probe) == 4 && aligned(d_work, 16)) {
+            int rc = gather_hints_for(g, g->a, C, s, &hint_cols);
+            if (rc == GNX_OK && hint_cols != nullptr) rc = pendant_plan_for(g, C, s, &pend_cols);
+            if (rc != GNX_OK) return rc;
+        }
+    }
+    if (pend_cols != nullptr) {
+        const float *vals = d_vals ? d_vals : g->raw_vals.get();
+        int rc = pendant_weights(g, vals, s);
+        if (rc != GNX_OK) return rc;
+        const float *src = d_H0;
+        for (int k = 0; k < K; ++k) {
+            float *dst = ((K - 1 - k) % 2 == 0) ? d_out : d_work;
+            const bool settled = k >= 2 || (g->a.empty_rows_unreferenced && dst == d_work);     // (as below)
+            PendArgs p{};
+            p.vals = vals;
+            set_operands<F32Rows>(p, src, C, d_H0, C, (float)(1.0 - (double)a), a, settled ? (act | GNX_ACT_SKIP_EMPTY) : act, dst, 0, C, C);
+            p.P = k == 1 ? d_H0 : dst;      // iterate k - 1 of every row: H0 itself, or what iteration k - 2 left in this destination
+            p.ldp = C;
+            p.pend_raw = k == 0;
+            p.pend_w = g->pend_w; p.pend_slot_mark = g->pend_slot_mark; p.pend_row_mark = g->pend_row_mark;
+            if (k < K - 1) { p.skip_beg = g->pend_slot0; p.skip_end = g->pend_slot0 + g->n_pend; }
+            rc = launch_bound(g, g->a, p, s, [&](PendArgs &q) {
+                q.colidx = pend_cols;
+                g->last_hint_hot = g->hint_hot;
+                return launch_eval_pend(q, s);
+            });
+            if (rc != GNX_OK) return rc;
+            src = dst;
+        }
+        g->last_pend = true;
+        return GNX_OK;
+    }
     const float *src = d_H0;
     for (int k = 0; k < K; ++k) {
         float *dst = ((K - 1 - k) % 2 == 0) ? d_out : d_work;

@@ -217,6 +217,41 @@ struct F32RowsOrd : F32Rows {
     static constexpr bool GATHER_ORDER = true;
 };
 
+// f32 rows of a K-loop launch that elides the handle's pendant rows (gnx_graph_set_pendant_elision; gnx_internal.h, PendantPart):
+// the sub-wave hinted kernels of 4 values per lane only.  SpmmArgs::colidx holds the handle's pend_cols.  An entry whose column is
+// elidable gathers that column's H0 row instead of its iterate -- nobody wrote one -- and forms the iterate from it, from pend_w and
+// from the gathering row's own values of two iterations ago, P[row] (pendant_iterate).  (An argument struct of its own, behind
+// SpmmArgs, as for OrdArgs: no other kernel takes a new argument.)
+struct PendArgs : SpmmArgs {
+    const float *P;                  // [n, ldp] the gathering rows' iterate of two iterations ago: H0, or the destination buffer as the launch finds it
+    int64_t ldp;
+    const float *pend_w;             // [n] per elidable row the value of its one entry
+    const uint8_t *pend_slot_mark;   // [n] per row slot: the row stores an entry whose column is elidable
+    const uint8_t *pend_row_mark;    // [n] the same per row (the chunk kernels)
+    int pend_raw;                    // the first iteration: the gathered operand IS H0, an elidable column's H0 row is its iterate
+    int64_t skip_beg, skip_end;      // row slots this launch leaves out: the elidable rows, in every iteration but the last
+};
+
+struct F32RowsPend : F32Rows {
+    using Args = PendArgs;
+    static constexpr bool EXPERIMENTS = false;
+};
+template <typename R> constexpr bool IS_PEND = std::is_same_v<typename R::Args, PendArgs>;
+
+__device__ __forceinline__ bool pend_col(int j) { return (j & PEND_COL_BIT) != 0 && j != HINT_NONE; }
+
+// One value of iterate k+1 of an elidable row i, as its neighbour h forms it: x = H0[i], prev = iterate k of h, w = pend_w[i].  The
+// very operations the row's own launch ran on it: a batch of four entries of which three do not exist -- fmaf(0, 0, t) turns -0
+// into +0 -- and the epilogue of epilogue_store for a row with H0 and nothing optional.
+__device__ __forceinline__ float pendant_iterate(float w, float prev, float x, float beta, float alpha, int act) {
+    float t = fmaf(w, prev, 0.f);
+#pragma unroll
+    for (int u = 1; u < 4; ++u) t = fmaf(0.f, 0.f, t);
+    float o = fmaf(t, beta, x * alpha);
+    if (act == GNX_ACT_RELU) o = fmaxf(o, 0.f);
+    return o;
+}
+
 struct BfArgs : SpmmArgs {     // SpmmArgs::X / ::out / ::out2 stay null: the typed buffers are here
     const uint16_t *Xb;        // bf16 [rows, ldx]: the gathered operand
     void *outv;                // f32 or bf16 [n_rows, ldo]

@@ -33,8 +33,10 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_wave(const typename R::Args p
 
 // ---- narrow path: G lanes per row, 256/G rows per block ---------------------------------------
 // PIPE: the (col, val) pairs of batch b+1 are fetched while the gathers of batch b are in flight.
+// PEND, here and in long_chunks_group: the launch elides the handle's pendant rows (IS_PEND: the policy whose arguments are PendArgs).
 template <typename R, int VEC, int G, int U, bool PIPE, bool HINT = false>
 __device__ __forceinline__ void group_rows(const typename R::Args &p, int64_t block) {
+    constexpr bool PEND = IS_PEND<R>;
     constexpr int RPB = 256 / G;
     const int sub = threadIdx.x % G;
     const int64_t slot = p.slot0 + block * RPB + threadIdx.x / G;
@@ -42,6 +44,9 @@ __device__ __forceinline__ void group_rows(const typename R::Args &p, int64_t bl
     const auto [row, beg, end] = slot_row<false>(p, slot);
     if (end - beg > p.long_row) return;       // the chunk kernels take it
     if (p.skip_empty && beg == end) return;   // GNX_ACT_SKIP_EMPTY: the row already holds alpha * H0, or a later launch writes it
+    if constexpr (PEND) {
+        if (slot >= p.skip_beg && slot < p.skip_end) return;   // an elidable row: only the last iteration computes it
+    }
     for (int c0 = 0; c0 < p.C; c0 += G * VEC) {
         const int c = c0 + sub * VEC;
         const bool active = c < p.C;
@@ -49,7 +54,42 @@ __device__ __forceinline__ void group_rows(const typename R::Args &p, int64_t bl
         float acc[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-        if constexpr (HINT) {
+        if constexpr (PEND) {
+            static_assert(HINT && VEC == 4 && !PIPE && G >= 16, "pendant elision: the hinted sub-wave kernels");
+            // the row's own values of two iterations ago, read before this lane overwrites them (P may be the destination buffer)
+            float prev[VEC] = {0.f, 0.f, 0.f, 0.f};
+            if (p.pend_slot_mark[slot] && !p.pend_raw) vload<VEC>(prev, p.P + row * p.ldp + (active ? c : 0));
+            const float *H0c = p.H0 + (active ? c : 0);
+            for (int64_t e = beg; e < end; e += U) {   // the batches of the hinted form
+                int j[U];
+                float w[U], pw[U];
+                f32x4 x[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const bool ok = e + u < end;
+                    j[u] = ok ? p.colidx[e + u] : HINT_NONE;
+                    w[u] = ok ? p.vals[e + u] : 0.f;
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int64_t col = j[u] & PEND_COL_MASK;
+                    const bool pend = pend_col(j[u]);
+                    x[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    gather16_hinted(x[u], pend ? H0c + col * p.ldh0 : Xc + col * p.ldx, j[u]);
+                    pw[u] = pend ? p.pend_w[col] : 0.f;
+                }
+                gather_wait<U>(x);
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (pend_col(j[u]) && !p.pend_raw) {
+#pragma unroll
+                        for (int v = 0; v < VEC; ++v) x[u][v] = pendant_iterate(pw[u], prev[v], x[u][v], p.beta, p.alpha, p.act);
+                    }
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
+                }
+            }
+        } else if constexpr (HINT) {
             static_assert(VEC == 4 && !PIPE && std::is_same_v<typename R::Elem, float>, "hinted gathers: f32 rows, 16 bytes per lane");
             for (int64_t e = beg; e < end; e += U) {   // the batches of the plain form; an entry past the row's end loads nothing
                 int j[U];
@@ -212,6 +252,7 @@ __global__ __launch_bounds__(256) void k_spmm_long_partial(const typename R::Arg
 // (each sub-group gathers whole C-wide rows), then the sub-group sums are added with a fixed xor tree.
 template <typename R, int VEC, int G, int U, bool HINT = false>
 __device__ __forceinline__ void long_chunks_group(const typename R::Args &p, int64_t block) {
+    constexpr bool PEND = IS_PEND<R>;
     constexpr int NS = 64 / G;
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -225,8 +266,46 @@ __device__ __forceinline__ void long_chunks_group(const typename R::Args &p, int
     float acc[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
+    [[maybe_unused]] float prev[VEC];
+    if constexpr (PEND) {
+        static_assert(HINT && VEC == 4 && G >= 16, "pendant elision: the hinted sub-wave kernels");
+        // the hub row's own values of two iterations ago (P may be the destination buffer: the reduce launch writes the row later)
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) prev[v] = 0.f;
+        if (p.pend_row_mark[row] && !p.pend_raw) vload<VEC>(prev, p.P + row * p.ldp + (active ? c : 0));
+    }
     for (int64_t e = beg + sub; e < end; e += (int64_t)NS * U) {
-        if constexpr (HINT) {
+        if constexpr (PEND) {
+            const float *H0c = p.H0 + (active ? c : 0);
+            int j[U];
+            float w[U], pw[U];
+            f32x4 x[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t eu = e + (int64_t)u * NS;
+                j[u] = eu < end ? p.colidx[eu] : HINT_NONE;
+                w[u] = eu < end ? p.vals[eu] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t col = j[u] & PEND_COL_MASK;
+                const bool pend = pend_col(j[u]);
+                x[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+                gather16_hinted(x[u], pend ? H0c + col * p.ldh0 : Xc + col * p.ldx, j[u]);
+                pw[u] = pend ? p.pend_w[col] : 0.f;
+            }
+            gather_wait<U>(x);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (pend_col(j[u]) && !p.pend_raw) {
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) x[u][v] = pendant_iterate(pw[u], prev[v], x[u][v], p.beta, p.alpha, p.act);
+                }
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) acc[v] = fmaf(w[u], x[u][v], acc[v]);
+            }
+            continue;
+        } else if constexpr (HINT) {
             static_assert(VEC == 4 && std::is_same_v<typename R::Elem, float>, "hinted gathers: f32 rows, 16 bytes per lane");
             int j[U];
             float w[U];
@@ -371,6 +450,44 @@ const char *launch_eval(const typename R::Args &p, hipStream_t s) {
         if (p.n_long > 0) launch_long<R, V(), H>(p, s);
         return kernel_name<R>(rows, MODE_EVAL, p.n_long > 0 ? HUBS_LONG : HUBS_NONE);
     });
+}
+
+// launch_eval<F32Rows, true> for one iteration of a K loop that elides the handle's pendant rows (the caller made sure of 4 values
+// per lane on 16 or 32 lanes, and set p.colidx to the handle's pend_cols): the same three launch shapes over the PEND kernels.  An
+// iteration but the last leaves the slots [skip_beg, skip_end) out -- it is not launched beyond them where the rows without entries,
+// which follow them in the row order, are left alone as well.  The reduce of the hub rows is the plain one: it reads nothing new.
+[[maybe_unused]] const char *launch_eval_pend(const PendArgs &p0, hipStream_t s) {
+    using R = F32RowsPend;
+    PendArgs p = p0;
+    const int lanes = (p.C + 3) / 4;
+    const SpmmArgs &plain = p;
+    if (p.n_long > 0 && p.n_rows < SMALL_ROWS) {      // launch_rows_and_chunks
+        const unsigned cb = blocks_for(p.n_chunks, 4);
+        if (p.skip_empty && p.skip_end > p.skip_beg) p.n_rows = p.skip_beg;
+        const RowClass rows = with_group<true>(lanes, [&](auto G) {
+            if constexpr (G() >= 16)
+                hipLaunchKernelGGL((k_spmm_group_and_chunks<R, 4, G(), true>), dim3(cb + blocks_for(p.n_rows, 256 / G())), dim3(256), 0, s, p, (int)cb);
+        });
+        GNX_LAUNCH((k_spmm_long_reduce<F32Rows, 4>), blocks_for(p.n_long, 4), plain);
+        return kernel_name<F32Rows>(rows, MODE_EVAL, HUBS_CHUNKS);
+    }
+    RowClass rows = ROWS_NONE;
+    {   // launch_rows
+        PendArgs q = p;
+        trim_empty_rows(q, lanes);
+        if (q.skip_end > q.skip_beg && q.n_rows <= q.skip_end) q.n_rows = q.skip_beg;
+        if (q.n_rows > 0)
+            rows = with_group<false>(lanes, [&](auto G) {
+                if constexpr (G() >= 16) launch_row_pieces((k_spmm_group<R, 4, G(), 4, false, true>), q, 256 / G(), 256, s);
+            });
+    }
+    if (p.n_long > 0) {                               // launch_long
+        with_group<true>(lanes, [&](auto G) {
+            if constexpr (G() >= 16) GNX_LAUNCH((k_spmm_long_partial_group<R, 4, G(), 4, true>), blocks_for(p.n_chunks, 4), p);
+        });
+        GNX_LAUNCH((k_spmm_long_reduce<F32Rows, 4>), blocks_for(p.n_long, 4), plain);
+    }
+    return kernel_name<F32Rows>(rows, MODE_EVAL, p.n_long > 0 ? HUBS_LONG : HUBS_NONE);
 }
 
 }  // namespace

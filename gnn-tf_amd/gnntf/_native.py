@@ -40,6 +40,8 @@ SIGNATURES = {
     "gnx_graph_set_row_window": (c_int, [c_void_p, c_int64, c_void_p]),
     "gnx_graph_set_gather_hints": (c_int, [c_void_p, c_int64, c_void_p]),
     "gnx_graph_gather_hints": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64)]),
+    "gnx_graph_set_pendant_elision": (c_int, [c_void_p, c_int, c_void_p]),
+    "gnx_graph_pendant_elision": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_void_p), POINTER(c_int)]),
     "gnx_graph_set_dropout_counter": (c_int, [c_void_p, c_void_p]),
     "gnx_graph_set_block": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "gnx_graph_colsum": (c_int, [c_void_p, c_float, c_uint64, c_uint64, c_void_p, c_void_p]),

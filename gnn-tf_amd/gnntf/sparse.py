@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import math
 from collections import namedtuple
-from ctypes import byref, c_float, c_int64, c_void_p
+from ctypes import byref, c_float, c_int, c_int64, c_void_p
 
 import numpy as np
 import torch
@@ -156,7 +156,7 @@ class DeviceGraph:
         slab; with ``transposed`` the transposed structure a backward needs; with ``k_loop`` the relabelled copy appnp_propagate
         runs narrow widths on; with ``train_gather`` the gather order and gather columns of the training loops' relabelled operand
         order, ppr_loop(gather_order="relabelled"), which implies ``transposed``; with ``gather_hints`` the hinted columns of
-        set_gather_hints at this width): those lazy builds allocate and synchronise, which
+        set_gather_hints at this width, and with them the pendant plan of set_pendant_elision): those lazy builds allocate and synchronise, which
         a stream under hipGraph capture must not see (a launch that would have to grow something there raises instead).  Call
         before capturing (gnx_graph_reserve)."""
         flags = ((nat.RESERVE_TRANSPOSED if transposed else 0) | (nat.RESERVE_K_LOOP if k_loop else 0)
@@ -196,6 +196,28 @@ class DeviceGraph:
         last = c_int64()
         nat.check(nat.lib().gnx_graph_gather_hints(self._h, None, None, byref(last)))
         return last.value
+
+    def set_pendant_elision(self, mode=-1):
+        """Pendant elision of appnp_propagate's K loop (gnx_graph_set_pendant_elision): a row whose one entry points at a row that
+        alone points back is computed by the last iteration only; its neighbour forms the iterates between itself.  -1 = automatic
+        (where the automatic gather hints are on), 0 = off, 1 = on wherever the launches take gather hints.  Same bits either way."""
+        with nat.on_device(self.device):
+            nat.check(nat.lib().gnx_graph_set_pendant_elision(self._h, int(mode), nat.current_stream()))
+
+    def pendant_elision(self):
+        """(elidable rows as a bool tensor [n] or None when no plan is built, whether the last K loop elided them)
+        (gnx_graph_pendant_elision)."""
+        count, flags, last = c_int64(), c_void_p(), c_int()
+        with nat.on_device(self.device):
+            nat.check(nat.lib().gnx_graph_pendant_elision(self._h, byref(count), byref(flags), byref(last)))
+            if not flags.value:
+                return None, bool(last.value)
+            torch.cuda.current_stream().synchronize()
+            borrowed = _BorrowedInt32(flags.value, self.n_rows)
+            borrowed.__cuda_array_interface__["typestr"] = "|u1"
+            rows = torch.as_tensor(borrowed, device=self.device).clone().bool()
+            assert int(rows.sum()) == count.value
+            return rows, bool(last.value)
 
     def set_row_window(self, window_rows):
         """Declares that the vertex numbering of THIS graph carries locality (a community / breadth-first order): launches take the

@@ -162,6 +162,23 @@ int gnx_graph_reserve(gnx_graph_t g, int64_t C, int flags, void *stream);
 int gnx_graph_set_gather_hints(gnx_graph_t g, int64_t hot_rows, void *stream);
 int gnx_graph_gather_hints(gnx_graph_t g, const int32_t **d_hint_cols, int64_t *hot_rows, int64_t *last_launch_hot_rows);
 
+/* Pendant elision of the K loop (added within ABI 0.9 -- probe for the symbols).  A PENDANT row i stores exactly one entry (i, h).  It
+ * is ELIDABLE when h != i, h stores at least two entries and no row but h stores an entry in column i: the iterates of i between
+ * H0 and the result are then read by h alone.  gnx_appnp_propagate / _act (the wide float32 branch, K >= 2, no diagonal) then
+ * launches such rows in the LAST iteration only; in the others h gathers H0[i] where it gathered the iterate -- the same bytes -- and
+ * forms the iterate itself, from the value of entry (i, h) and its own row of two iterations ago, with the very operations the row's
+ * own launch ran: results are bitwise those without elision, and the work buffer never holds an elidable row.  Rides on the
+ * gather hints: active only where the loop's launches take them (gnx_graph_set_gather_hints), on handles of fewer than 2^30
+ * columns.  Costs 4 bytes per entry and 7 per row; built on first use, by mode 1 or by gnx_graph_reserve(GNX_RESERVE_GATHER_HINTS)
+ * (under capture without it: GNX_ERR_UNSUPPORTED naming that call); the build moves the elidable rows to the end of the one-entry
+ * rows of the handle's launch order and synchronises the device.  If the arrays cannot be allocated the handle runs without it.
+ * gnx_graph_set_pendant_elision: mode = -1 automatic, the default (exactly where the AUTOMATIC gather hints are on), 0 off, 1 on
+ * wherever admissible (built now).  Not capturable.  gnx_graph_pendant_elision: the number of elidable rows, the borrowed device
+ * array [n_rows] of bytes (1 = elidable; NULL and 0: no plan built) and whether the last gnx_appnp_propagate(_act) over the handle
+ * elided; any pointer may be NULL.  Every other entry is untouched.  Nothing in the reference corresponds. */
+int gnx_graph_set_pendant_elision(gnx_graph_t g, int mode, void *stream);
+int gnx_graph_pendant_elision(gnx_graph_t g, int64_t *n_elidable, const uint8_t **d_elidable, int *last_loop_elided);
+
 /* gnx_graph_enable_entry_dropout: builds, NOW, what the fused training entries (gnx_spmm_dropped, gnx_spmm_dropped_chained,
  * gnx_spmm_dropped_back) and the one-pass column sums of gnx_graph_colsum_streams need on a handle whose COO held duplicate entries
  * -- what graph2adj makes of a graph that stores both directions already (graph_manipulation.py:28-30): every (row, col) twice.
