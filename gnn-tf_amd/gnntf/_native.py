@@ -148,6 +148,10 @@ SIGNATURES = {
                                    c_uint64, c_uint64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                    c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
                                    c_void_p]),
+    "gnx_step_back_wide_ngcf": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_double,
+                                        c_uint64, c_uint64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                        c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                        c_void_p]),
     "gnx_step_wide_ngcf": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p,
                                    c_void_p, c_int, c_double, c_uint64, c_uint64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_int64, c_void_p]),
@@ -180,7 +184,7 @@ SIGNATURES = {
 }
 
 # entries added within ABI 0.9 that a library of the same minor version may lack: found by probing (has_symbol); their callers raise
-PROBED = ("gnx_step_wide_ngcf",)
+PROBED = ("gnx_step_wide_ngcf", "gnx_step_back_wide_ngcf")
 
 _lib = None
 

@@ -53,7 +53,7 @@ class GNN(Trainable):
                  training_dtype=torch.float32, train_gather_order="auto", gcnii_backward="composed", feature_dropout="torch",
                  gcnii_training_dtype=torch.float32, gcnii_weight_gradient="stored", gcnii_spectral="composed",
                  gcnii_edge_dropout="composed", gcn_layer="composed", gcn_backward="composed", ngcf_layer="composed",
-                 ngcf_backward="composed", ngcf_wide="composed"):
+                 ngcf_backward="composed", ngcf_wide="composed", ngcf_wide_backward="composed"):
         """``reorder`` (opt-in, not in the reference): store the graph and the feature rows with the vertices relabelled; every
         [N, .] tensor inside the model then lives in that order, and the model's OUTPUT is put back into the caller's order, so
         tasks, labels and node ids are unaffected.  Results agree with the unordered model to float32 rounding.
@@ -214,13 +214,23 @@ class GNN(Trainable):
         or a dropout of 0, the mask in the launch under ``feature_dropout="fused"``, or the launch without the norm followed by
         torch's dropout and normalize.  The backward is the composed one of ``ngcf_layer`` (``ngcf_backward="fused"`` has no launch at
         this width).  The results agree with the composed layer to float32 rounding (measurement: profiles/NOTES.md "NGCF layer at
-        width 128").  A model built without the keyword makes today's calls at every width."""
+        width 128").  A model built without the keyword makes today's calls at every width.
+        ``ngcf_wide_backward`` (not in the reference): ``"composed"`` (the default: today's calls and bits) or ``"fused"``
+        (sparse.ngcf_step ``wide_backward``).  It acts on the layers that ``ngcf_layer="fused"`` and ``ngcf_wide="fused"`` together run
+        at input width 128 and is inert otherwise: their backward is then ONE call of gnx_step_back_wide_ngcf -- the gate pass with the
+        slab-ordered bias sums, one row-local launch (G1 W1^T and G2 W2^T on the matrix cores with the weights in LDS, read as stored;
+        dA, Q1 * A and X * A written once) and the transposed SpMM with Q1 * A mixed in -- and gnx_dense_wgrad twice, instead of the
+        column sums, a torch multiply, two transposed weight copies, gnx_dense twice and two addcmul passes.  The forward, dW1 and dW2
+        keep their bits; dX and the bias gradients agree to float32 rounding (why the default stays ``"composed"``; measurement:
+        profiles/NOTES.md "NGCF backward at width 128").  A second backward over a retained graph works."""
         if ngcf_layer not in sparse.NGCF_LAYERS:
             raise Exception("GNN: ngcf_layer must be one of " + ", ".join(repr(f) for f in sparse.NGCF_LAYERS))
         if ngcf_backward not in sparse.NGCF_BACKWARDS:
             raise Exception("GNN: ngcf_backward must be one of " + ", ".join(repr(b) for b in sparse.NGCF_BACKWARDS))
         if ngcf_wide not in sparse.NGCF_WIDES:
             raise Exception("GNN: ngcf_wide must be one of " + ", ".join(repr(w) for w in sparse.NGCF_WIDES))
+        if ngcf_wide_backward not in sparse.NGCF_WIDE_BACKWARDS:
+            raise Exception("GNN: ngcf_wide_backward must be one of " + ", ".join(repr(w) for w in sparse.NGCF_WIDE_BACKWARDS))
         if gcn_backward not in sparse.GCN_BACKWARDS:
             raise Exception("GNN: gcn_backward must be one of " + ", ".join(repr(b) for b in sparse.GCN_BACKWARDS))
         if gcn_layer not in sparse.GCN_LAYERS:
@@ -258,6 +268,7 @@ class GNN(Trainable):
         self.ngcf_layer = ngcf_layer
         self.ngcf_backward = ngcf_backward
         self.ngcf_wide = ngcf_wide
+        self.ngcf_wide_backward = ngcf_wide_backward
         self._order = self._newid = None
         self.reorder_used, self.locality_share = None, None
         if isinstance(graph, sparse.DeviceGraph):
@@ -812,6 +823,10 @@ class NGCFLayer(Layer):
             wide = getattr(gcn, "ngcf_wide", "composed")
             if wide != "composed" and features.shape[1] in sparse.NGCF_WIDE_WIDTHS:
                 back["wide"] = wide
+            # GNN(ngcf_wide_backward=): likewise
+            wide_back = getattr(gcn, "ngcf_wide_backward", "composed")
+            if wide_back != "composed" and features.shape[1] in sparse.NGCF_WIDE_WIDTHS:
+                back["wide_backward"] = wide_back
             if not gcn.is_training() or self.dropout == 0:
                 return sparse.ngcf_step(self.adjacency, features, self.W1, b1, self.W2, b2, activation=act, **back)
             if getattr(gcn, "feature_dropout", "torch") == "fused" and 0 < self.dropout < 1:

@@ -1714,6 +1714,7 @@ NGCF_BACKWARDS = ("composed", "fused")
 NGCF_FUSED_WIDTHS = (16, 32, 64)      # C_in of the one-launch form of gnx_ngcf_step; its C_out is any width up to C_in
 NGCF_WIDES = ("composed", "fused")
 NGCF_WIDE_WIDTHS = (128,)             # C_in of gnx_step_wide_ngcf (the SpMM, then one row-local launch); C_out any width up to C_in
+NGCF_WIDE_BACKWARDS = ("composed", "fused")      # the backward at those widths: today's calls, or gnx_step_back_wide_ngcf
 NGCF_ACTIVATIONS = {"none": nat.ACT_NONE, "relu": nat.ACT_RELU, "leaky": nat.ACT_LEAKY}
 NGCF_SLOPES = {"none": 1.0, "relu": 0.0, "leaky": 0.2}
 
@@ -1815,10 +1816,11 @@ def _ngcf_back_fusable(X, A, W1):
             and A.data_ptr() % 16 == 0)
 
 
-def _ngcf_back_launch(adj: Adjacency, g, y, rnorm, gate, activation, dropout, X, A, W1, W2, want_P=True, want_db=(True, True), want_dX=True):
-    """gnx_step_back_ngcf, one call: returns dict(G1, G2, P, db1, db2, dA, R, dX).  G1 / G2 are [n, C_out] views of rows of stride
-    roundup4(C_out) whose padding is zero; P = X * A only with ``want_P`` (dW1 needs it), db1 / db2 [C_out] with ``want_db``, and with
-    ``want_dX`` the products dA = (G1 W1^T) * X + G2 W2^T and R = (G1 W1^T) * A and dX = A_hat^T dA + R (None each otherwise: no products
+def _ngcf_back_launch(adj: Adjacency, g, y, rnorm, gate, activation, dropout, X, A, W1, W2, want_P=True, want_db=(True, True), want_dX=True,
+                      entry="gnx_step_back_ngcf", work_floats=_ngcf_back_work_floats):
+    """gnx_step_back_ngcf (or ``entry``, an entry of the same parameter list, with its ``work_floats(n, C_out)``), one call: returns
+    dict(G1, G2, P, db1, db2, dA, R, dX).  G1 / G2 are [n, C_out] views of rows of stride roundup4(C_out) whose padding is zero;
+    P = X * A only with ``want_P`` (dW1 needs it), db1 / db2 [C_out] with ``want_db``, and with ``want_dX`` the products dA = (G1 W1^T) * X + G2 W2^T and R = (G1 W1^T) * A and dX = A_hat^T dA + R (None each otherwise: no products
     and no transposed SpMM).  W1 / W2 are read as stored: no transposed copy.  ``dropout`` = the checked (p, seed, stream) or None."""
     g, X, A, W1, W2 = _as_f32_rows(g), _as_f32_rows(X), _as_f32_rows(A), _as_f32_rows(W1), _as_f32_rows(W2)
     nat.require_cuda(g, y, rnorm, gate, X, A, W1, W2)
@@ -1839,17 +1841,38 @@ def _ngcf_back_launch(adj: Adjacency, g, y, rnorm, gate, activation, dropout, X,
     P = new(n, C_in) if want_P else None
     db1, db2 = (new(C_out) if w else None for w in want_db)
     dA, R, dX = (new(n, C_in), new(n, C_in), new(n, C_in)) if want_dX else (None, None, None)
-    floats = _ngcf_back_work_floats(n, C_out) if any(want_db) else 0
+    floats = work_floats(n, C_out) if any(want_db) else 0
     work = new(floats) if floats else None
     p, seed, stream = _dropout_args(dropout)
     ldw = lambda W: W.stride(0) if C_in > 1 else C_out     # (torch calls a one-row matrix contiguous whatever its row stride says)
     with nat.on_device(g.device):
-        nat.check(nat.lib().gnx_step_back_ngcf(
+        nat.check(getattr(nat.lib(), entry)(
             graph.handle, nat.ptr(adj.transposed_values()) if want_dX else None, nat.ptr(g), g.stride(0), nat.ptr(y), 0 if y is None else y.stride(0),
             nat.ptr(rnorm), nat.ptr(gate) if activation != "none" else None, C_out, NGCF_ACTIVATIONS[activation], p, seed, stream, nat.ptr(X),
             X.stride(0), nat.ptr(A), C_in, nat.ptr(W1), ldw(W1), nat.ptr(W2), ldw(W2), nat.ptr(G1), nat.ptr(G2), G1.stride(0), nat.ptr(P), nat.ptr(db1),
             nat.ptr(db2), nat.ptr(dA), nat.ptr(R), nat.ptr(dX), C_in, nat.ptr(work), floats, nat.current_stream()))
     return dict(G1=G1, G2=G2, P=P, db1=db1, db2=db2, dA=dA, R=R, dX=dX)
+
+
+def _ngcf_wide_back_work_floats(n, C_out):
+    """include/gnx.h, gnx_step_back_wide_ngcf: the bias slabs -- one per 512 rows, at most 1024, 2 C_out floats each."""
+    return max(1, min(1024, (n + 511) // 512)) * 2 * C_out
+
+
+def _ngcf_wide_back_fusable(wide_backward, X, A, W1):
+    """Where ``wide_backward="fused"`` has a launch (gnx_step_back_wide_ngcf): C_in = 128, C_out <= C_in, 16-byte aligned rows of X and A."""
+    C_in, C_out = W1.shape
+    return (wide_backward == "fused" and C_in in NGCF_WIDE_WIDTHS and C_out <= C_in and X.stride(0) % 4 == 0 and X.data_ptr() % 16 == 0
+            and A.is_contiguous() and A.data_ptr() % 16 == 0)
+
+
+def _ngcf_wide_back_launch(adj: Adjacency, g, y, rnorm, gate, activation, dropout, X, A, W1, W2, want_P=True, want_db=(True, True), want_dX=True):
+    """gnx_step_back_wide_ngcf, one call: what _ngcf_back_launch returns, from the gate pass, one row-local launch and the transposed SpMM
+    at C_in = 128.  A library without the entry raises: nothing falls back."""
+    if not nat.has_symbol("gnx_step_back_wide_ngcf"):
+        raise Exception("ngcf_step: wide_backward=\"fused\" needs gnx_step_back_wide_ngcf, which this libgnx.so does not export: rebuild the library")
+    return _ngcf_back_launch(adj, g, y, rnorm, gate, activation, dropout, X, A, W1, W2, want_P=want_P, want_db=want_db, want_dX=want_dX,
+                             entry="gnx_step_back_wide_ngcf", work_floats=_ngcf_wide_back_work_floats)
 
 
 class _NGCFStep(torch.autograd.Function):
@@ -1860,11 +1883,13 @@ class _NGCFStep(torch.autograd.Function):
     dX = Q1 * A + A_hat^T dA (the transposed SpMM); the elementwise products in torch.
     ``backward="fused"``, where gnx_step_back_ngcf has a launch (_ngcf_back_fusable): that entry once -- the gate, the column sums, X * A,
     both products, dA and Q1 * A from one launch, then the transposed SpMM with Q1 * A mixed in -- and gnx_dense_wgrad twice.  The saved
-    tensors stay: a second backward over a retained graph gives the same bits."""
+    tensors stay: a second backward over a retained graph gives the same bits.
+    ``wide_backward="fused"``, where gnx_step_back_wide_ngcf has a launch (_ngcf_wide_back_fusable: C_in = 128): the same route through
+    that entry.  What is saved has one format from gnx_ngcf_step and from gnx_step_wide_ngcf, so the route does not depend on ``wide``."""
 
     @staticmethod
-    def forward(ctx, X, W1, b1, W2, b2, adj, activation, dropout, normalize, backward="composed", wide="composed"):
-        ctx.adj, ctx.activation, ctx.dropout, ctx.backward = adj, activation, dropout, backward
+    def forward(ctx, X, W1, b1, W2, b2, adj, activation, dropout, normalize, backward="composed", wide="composed", wide_backward="composed"):
+        ctx.adj, ctx.activation, ctx.dropout, ctx.backward, ctx.wide_backward = adj, activation, dropout, backward, wide_backward
         ctx.bias_shapes = tuple(None if b is None else tuple(b.shape) for b in (b1, b2))
         how = dict() if wide == "composed" else dict(wide=wide)      # (named only where it is not the default: today's call otherwise)
         out, agg, gate, rnorm = _ngcf_launch(adj, X, W1, b1, W2, b2, activation, keep=True, dropout=dropout, normalize=normalize, **how)
@@ -1876,17 +1901,18 @@ class _NGCFStep(torch.autograd.Function):
         X, A, gate, rnorm, out, W1, W2 = ctx.saved_tensors
         X = _as_f32_rows(X)
         need = ctx.needs_input_grad
-        if ctx.backward == "fused" and _ngcf_back_fusable(X, A, W1):
+        launch = (_ngcf_wide_back_launch if _ngcf_wide_back_fusable(ctx.wide_backward, X, A, W1)
+                  else _ngcf_back_launch if ctx.backward == "fused" and _ngcf_back_fusable(X, A, W1) else None)
+        if launch is not None:
             want_db = tuple(ctx.bias_shapes[k] is not None and need[2 + 2 * k] for k in (0, 1))
-            made = _ngcf_back_launch(ctx.adj, g, out, rnorm, gate, ctx.activation, ctx.dropout, X, A, W1, W2, want_P=need[1], want_db=want_db,
-                                     want_dX=need[0])
+            made = launch(ctx.adj, g, out, rnorm, gate, ctx.activation, ctx.dropout, X, A, W1, W2, want_P=need[1], want_db=want_db, want_dX=need[0])
             del made["dA"], made["R"]                      # (the transposed SpMM inside the call was their last reader)
             gW1 = _dense_wgrad(made["P"], made["G1"]) if need[1] else None
             gW2 = _dense_wgrad(A, made["G2"]) if need[3] else None
             gb1, gb2 = (None if made[k] is None else made[k].reshape(shape) for k, shape in zip(("db1", "db2"), ctx.bias_shapes))
             gX = made["dX"]
             del made                                       # (P, G1, G2, dA and R are free before the caller allocates anything)
-            return gX, gW1, gb1, gW2, gb2, None, None, None, None, None, None
+            return gX, gW1, gb1, gW2, gb2, None, None, None, None, None, None, None
         G1, G2 = _ngcf_back_gate(ctx.adj.graph, g, out, rnorm, gate, ctx.activation, ctx.dropout)
         gb1 = G1.contiguous().sum(dim=0).reshape(ctx.bias_shapes[0]) if ctx.bias_shapes[0] is not None and need[2] else None
         gb2 = G2.contiguous().sum(dim=0).reshape(ctx.bias_shapes[1]) if ctx.bias_shapes[1] is not None and need[4] else None
@@ -1900,7 +1926,7 @@ class _NGCFStep(torch.autograd.Function):
             dA = torch.addcmul(Q2, Q1, X)                   # Q1 * X + Q2
             del Q2
             gX = torch.addcmul(_launch(ctx.adj, dA, None, 1.0, 0.0, nat.ACT_NONE, transposed=True), Q1, A)
-        return gX, gW1, gb1, gW2, gb2, None, None, None, None, None, None
+        return gX, gW1, gb1, gW2, gb2, None, None, None, None, None, None, None
 
 
 def _ngcf_act(x, activation):
@@ -1925,7 +1951,7 @@ def _ngcf_composed(adj, X, W1, b1, W2, b2, activation, dropout, normalize):
 
 
 def ngcf_step(adj: Adjacency, X: torch.Tensor, W1: torch.Tensor, b1, W2: torch.Tensor, b2, activation="leaky", dropout=None,
-              normalize=True, backward="composed", wide="composed") -> torch.Tensor:
+              normalize=True, backward="composed", wide="composed", wide_backward="composed") -> torch.Tensor:
     """NGCFLayer (gcn.py:116-135) as one launch (gnx_ngcf_step; opt-in, GNN(ngcf_layer="fused")):
     l2_normalize(drop(act((X * (A . X)) . W1 + b1) + act((A . X) . W2 + b2))) with ``X`` [n, C_in], ``W1`` / ``W2`` [C_in, C_out], ``b1`` /
     ``b2`` [C_out] / [1, C_out] or None and ``activation`` ``"leaky"`` (tf.nn.leaky_relu's slope 0.2), ``"relu"`` or ``"none"``.  For
@@ -1946,6 +1972,12 @@ def ngcf_step(adj: Adjacency, X: torch.Tensor, W1: torch.Tensor, b1, W2: torch.T
     writes the finished rows, the gate words and the reciprocal norms in gnx_ngcf_step's formats -- instead of the SpMM, a product pass,
     the dense kernel twice and a row pass inside gnx_ngcf_step.  The node and its composed backward are unchanged (``backward="fused"``
     stays inert at this width); the results agree with the composed call to float32 rounding.  Other widths make today's call.
+    ``wide_backward``: ``"composed"`` (the default: today's backward) or ``"fused"`` (opt-in; GNN(ngcf_wide_backward="fused")): for
+    C_in = 128, C_out <= C_in and aligned rows the backward is ONE call of gnx_step_back_wide_ngcf -- the gate pass and the slab-ordered
+    bias sums, one row-local launch that forms G1 W1^T and G2 W2^T on the matrix cores (W1 / W2 read as stored) and writes dA, Q1 * A
+    and X * A, then the transposed SpMM with Q1 * A mixed in -- and gnx_dense_wgrad twice, whichever call made the forward.  out, dW1
+    and dW2 keep their bits; dX and the bias gradients agree with the composed backward to float32 rounding.  A second backward over a
+    retained graph gives the same bits.  It acts under autograd only; other widths and misaligned rows keep the composed backward.
     CPU tensors, an adjacency with a diagonal and a DroppedAdjacency run today's ops."""
     if activation not in NGCF_ACTIVATIONS:
         raise Exception("ngcf_step: activation must be one of " + ", ".join(repr(a) for a in NGCF_ACTIVATIONS))
@@ -1953,12 +1985,14 @@ def ngcf_step(adj: Adjacency, X: torch.Tensor, W1: torch.Tensor, b1, W2: torch.T
         raise Exception("ngcf_step: backward must be one of " + ", ".join(repr(b) for b in NGCF_BACKWARDS))
     if wide not in NGCF_WIDES:
         raise Exception("ngcf_step: wide must be one of " + ", ".join(repr(w) for w in NGCF_WIDES))
+    if wide_backward not in NGCF_WIDE_BACKWARDS:
+        raise Exception("ngcf_step: wide_backward must be one of " + ", ".join(repr(w) for w in NGCF_WIDE_BACKWARDS))
     tensors = tuple(t for t in (X, W1, b1, W2, b2) if t is not None)
     if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors) or adj.diag is not None or isinstance(adj, DroppedAdjacency):
         return _ngcf_composed(adj, X, W1, b1, W2, b2, activation, dropout, bool(normalize))
     dropout = _dropout_triple(dropout, "ngcf_step")
     if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
-        return _NGCFStep.apply(X, W1, b1, W2, b2, adj, activation, dropout, bool(normalize), backward, wide)
+        return _NGCFStep.apply(X, W1, b1, W2, b2, adj, activation, dropout, bool(normalize), backward, wide, wide_backward)
     how = dict() if wide == "composed" else dict(wide=wide)
     return _ngcf_launch(adj, X, W1, b1, W2, b2, activation, keep=False, dropout=dropout, normalize=bool(normalize), **how)[0]
 

@@ -70,7 +70,8 @@ const char *gnx_last_error(void);
  * the wide eval launches (gnx_graph_set_gather_hints, gnx_graph_gather_hints, GNX_RESERVE_GATHER_HINTS), likewise, and the GCN layer
  * in one launch (gnx_gcn_step, gnx_gcn_step_dropped) with its input gradient (gnx_gcn_step_back, gnx_gcn_step_back_dropped), likewise,
  * and the NGCF layer in one launch with its backward's gate (gnx_ngcf_step, gnx_ngcf_back_gate, GNX_ACT_LEAKY) and the rest of its backward in
- * one launch (gnx_step_back_ngcf) and the layer at width 128 as the SpMM and one row-local launch (gnx_step_wide_ngcf), likewise, and the link
+ * one launch (gnx_step_back_ngcf) and the layer at width 128 as the SpMM and one row-local launch (gnx_step_wide_ngcf) with its
+ * backward as the gate, one row-local launch and the transposed SpMM (gnx_step_back_wide_ngcf), likewise, and the link
  * task on the device (gnx_sample_negatives, gnx_edge_plan_bytes, gnx_edge_plan, gnx_edge_sorted_work_floats,
  * gnx_edge_scores_backward_sorted), likewise, and the ranking evaluation of the link task (gnx_rank_candidates_bytes,
  * gnx_rank_candidates, GNX_RANK_MAX_K, GNX_RANK_POS_PASS, GNX_RANK_MAX_SPLITS), likewise. */
@@ -902,6 +903,49 @@ int gnx_step_wide_ngcf(gnx_graph_t g, const float *d_vals, const float *d_X, int
                        const float *d_W2, int64_t ldw2, int64_t C_out, const float *d_b1, const float *d_b2, int act, double dropout_p,
                        uint64_t seed, uint64_t stream_id, int normalize, float *d_out, int64_t ldo, float *d_agg, uint32_t *d_gate,
                        float *d_rnorm, float *d_work, int64_t work_floats, void *stream);
+
+/* gnx_step_back_wide_ngcf (training, opt-in; added within ABI 0.9 -- probe for the symbol): the backward of gnx_step_wide_ngcf /
+ * gnx_ngcf_step at C_in = 128 around its two weight gradients.  The parameter list, the meanings and the output formats are
+ * gnx_step_back_ngcf's: G1, G2 [n, C_out] at row stride ldG with zeros in the columns C_out .. roundup4(C_out) - 1; P, dA, R [n, C_in]
+ * contiguous; db1, db2 [C_out]; dX (lddx); d_P, d_db1, d_db2 may each be NULL; d_dX == NULL: no products and no SpMM, and d_dA, d_R,
+ * d_W1 and d_W2 may then be NULL and are not looked at.
+ *   G1, G2 = gnx_ngcf_back_gate's        db1 = sum_rows G1       db2 = sum_rows G2       P = X * A
+ *   Q1 = G1 . W1^T      Q2 = G2 . W2^T      dA = Q1 * X + Q2      R = Q1 * A      dX = A_hat^T . dA + R
+ * Supported: C_in == 128, 1 <= C_out <= 128, ldx % 4 == 0, ldG % 4 == 0, ldG >= roundup4(C_out), and X / d_agg / G1 / G2 / P / dA / R
+ * 16-byte aligned.  Anything else returns GNX_ERR_UNSUPPORTED naming the widths or the alignment, nothing launched and nothing
+ * written: there is no composed form inside the entry, callers keep the composed backward there.
+ * Three stream-ordered steps inside the call:
+ * Step A: the gate pass, gnx_ngcf_back_gate's own kernel -- G1 / G2 are bit for bit its results -- and, where d_db1 or d_db2 is
+ * given, the column sums of G1 / G2: slab s of d_work holds the sums of the rows s * per .. min((s + 1) * per, n) - 1, per =
+ * ceil(n / slabs) -- within a slab 256 / (roundup4(C_out) / 4) row lanes add every that-many-th row in ascending order and are then
+ * added in lane order --, and one finishing launch adds the slabs in index order.
+ * Step B: one launch over all n rows without a gather, a block of eight waves per CU, persistent over 16-row tiles.  W1^T and W2^T
+ * sit in LDS in f32, read from W1 / W2 [C_in, C_out] as stored (ldw1 / ldw2; no transposed copy exists), 16 KiB per 16 output
+ * columns, 128 KiB at C_out > 112, zero from column C_out on; a wave holds its rows of G1 and G2 as MFMA operand fragments in
+ * registers (the columns from roundup4(C_out) on are never loaded), forms Q1 and Q2 on v_mfma_f32_16x16x4_f32 and writes dA, R and --
+ * where d_P is given -- P as whole 16-byte stores.  With d_dX == NULL the launch makes P alone (nothing where d_P is NULL too).
+ * Step C, when d_dX is given: gnx_spmm_tv(d_dA, H0 = d_R, beta = 1, alpha = 1) into d_dX (lddx): d_vals_t the adjacency's values in
+ * transposed order (NULL: the raw values); hub rows of the transposed structure are that launch's business.
+ * Rounding points: G1 / G2 as gnx_ngcf_back_gate; P one multiply; each Q the f32 MFMA sum over the output columns ascending (four
+ * columns a step); dA = fmaf(Q1, X, Q2), one rounding; R one multiply; db the fixed slab order above; dX as gnx_spmm_tv.  The order
+ * depends on (n, C_out) alone -- not on the CU count, the grid or the wave that takes a tile; no float atomics: two calls give the
+ * same bits.  (The composed backward rounds dA twice and its products associate otherwise: the two agree to float32 rounding.)
+ * d_work / work_floats (only where d_db1 or d_db2 is given): with s = max(1, min(1024, ceil(n / 512))) slabs,
+ *     work_floats >= s * 2 * C_out
+ * Too little is refused and the message names the figure.
+ * Checked before anything is launched (a refused call writes nothing): the NULL handle, the checks of gnx_ngcf_back_gate, the widths,
+ * pointers and strides, a square stand-alone graph; every output -- G1, G2, P, db1, db2, dA, R, dX, d_work -- is a buffer of its own
+ * (d_dX may NOT be d_R); the alignment; work_floats.
+ * Stream-ordered and allocation-free once the handle is reserved; under capture the transposed structure and the long-row slab at
+ * width 128 must exist already (gnx_graph_reserve with GNX_RESERVE_TRANSPOSED), as for gnx_spmm_tv.
+ * Reports "k_ngcf_rows_back<128>" (+ "_drop" with a mask, + "+spmm_tv" when dX ran).
+ * (The layer's name stands behind the verb in this entry's name, as in gnx_step_back_ngcf and gnx_step_wide_ngcf.) */
+int gnx_step_back_wide_ngcf(gnx_graph_t g, const float *d_vals_t, const float *d_g, int64_t ldg, const float *d_y, int64_t ldy,
+                            const float *d_rnorm, const uint32_t *d_gate, int64_t C_out, int act, double dropout_p, uint64_t seed,
+                            uint64_t stream_id, const float *d_X, int64_t ldx, const float *d_agg, int64_t C_in, const float *d_W1,
+                            int64_t ldw1, const float *d_W2, int64_t ldw2, float *d_G1, float *d_G2, int64_t ldG, float *d_P,
+                            float *d_db1, float *d_db2, float *d_dA, float *d_R, float *d_dX, int64_t lddx, float *d_work,
+                            int64_t work_floats, void *stream);
 
 /* ---- the dense ends of the path (matrix cores) -----------------------------------------------------------------------
  * gnx_dense: out = act(X . W + bias) -- Dense.__forward__ (gnntf/core/nn/layers.py:135-136) and the transform of
