@@ -216,17 +216,18 @@ class Trainable(Layered):
         """Every DeviceGraph whose kernels draw edge / input-dropout masks for this model."""
         graphs = [self.graph] if hasattr(self, "graph") else []
         rows = self._input_features()
-        if rows is not self.features:
+        if isinstance(rows, sparse.SparseRows):         # given sparse or converted: the input dropout draws over its stored entries
             graphs.append(rows.graph)
         return graphs
 
     def _train_captured(self, train, valid, test, patience, learning_rate, regularization, verbose, epochs, degradation, batches,
                         optimizer):
-        if not self.features.is_cuda:
+        # features given sparse live on their graph's device (a SparseRows is no tensor)
+        device = self.features.graph.device if isinstance(self.features, sparse.SparseRows) else self.features.device
+        if torch.device(device).type != "cuda":
             raise Exception("train(capture=True) needs the model on the GPU")
         if optimizer is not None and isinstance(optimizer, torch.optim.Optimizer):
             raise Exception("train(capture=True) builds its own capturable optimizer: pass a factory or nothing")
-        device = self.features.device
         params = [v.var for v in self.vars() if v.trainable]
         make_optimizer = (lambda: optimizer(params)) if optimizer is not None else \
             (lambda: torch.optim.Adam(params, lr=learning_rate, eps=1e-7, capturable=True))
@@ -235,11 +236,11 @@ class Trainable(Layered):
         scale = torch.ones((), dtype=torch.float32, device=device)           # degradation(epoch), refreshed before every replay
         counter = torch.zeros(1, dtype=torch.int64, device=device)           # added to every dropout stream id on the device
         graphs = self._dropout_graphs()
-        for g in graphs:
-            g.set_dropout_counter(counter)
         # the gather order and gather columns of the training loops (GNN.train_gather_order), built before anything is recorded
         if hasattr(self, "graph") and sparse.may_use_train_gather(self.graph, getattr(self, "train_gather_order", "caller")):
             self.graph.reserve(1, train_gather=True)
+        for g in graphs:                                                     # (last: nothing between here and the try can raise)
+            g.set_dropout_counter(counter)
 
         def train_step(opt):
             with self:
@@ -297,24 +298,26 @@ class Trainable(Layered):
         counter.zero_()
         best = _BestSoFar(self.vars(), patience)
         steps = validations = 0
-        for epoch in range(epochs):
-            self._fast_predict = None
-            scale.fill_(float(degradation(epoch)))
-            for _ in range(batches):
-                step_graph.replay()
-                steps += 1
-            eval_graph.replay()
-            validations += 1
-            held_out = float(held_out_value)                                # the one synchronisation of the epoch
-            if best.observe(held_out):
-                if verbose:
-                    self._report(epoch, best.countdown, float(fitted_value) * batches, held_out, logits, train, judge, test)
-                best.rearm()
-            if best.exhausted:
-                break
+        try:
+            for epoch in range(epochs):
+                self._fast_predict = None
+                scale.fill_(float(degradation(epoch)))
+                for _ in range(batches):
+                    step_graph.replay()
+                    steps += 1
+                eval_graph.replay()
+                validations += 1
+                held_out = float(held_out_value)                            # the one synchronisation of the epoch
+                if best.observe(held_out):
+                    if verbose:
+                        self._report(epoch, best.countdown, float(fitted_value) * batches, held_out, logits, train, judge, test)
+                    best.rearm()
+                if best.exhausted:
+                    break
+        finally:                                                             # a failing replay or degradation() leaves no handle counting
+            for g in graphs:
+                g.set_dropout_counter(None)
         best.restore()
-        for g in graphs:
-            g.set_dropout_counter(None)
         self._mask_calls = first_mask + steps * step_streams + validations * eval_streams
         self._training = False
         self._fast_predict = None

@@ -5,8 +5,9 @@
     python tests/fuzz_kernels.py --dump CASE SEED OUT.npz    write one case's drawn inputs as a fixture (no GPU needed)
 
 ``draw_case`` makes every random draw of a case on the host (numpy only: replaying a seed needs no GPU), ``check_case`` runs the
-kernels on it.  ``draw_extra`` draws the inputs of the two riders ("entries": the training kernels on a COO with duplicates after
-enable_entry_dropout, on the kind-1 cases; "bf16": gnx_spmm_bf16 / gnx_appnp_propagate_bf16, on the kind-0 and kind-2 cases) from a
+kernels on it.  ``draw_extra`` draws the inputs of the three riders ("entries": the training kernels on a COO with duplicates after
+enable_entry_dropout, on the kind-1 cases; "bf16": gnx_spmm_bf16 / gnx_appnp_propagate_bf16, on the kind-0 and kind-2 cases; "f32":
+every f32 eval entry -- gnx_spmm, _scatter, _rows, _t, _tv -- with its optional operands, on the kind-0 cases) from a
 child generator of (seed, case, tag), so the stream ``draw_case`` reads stays what it was (tests/test_fuzz_draws.py pins it).
 tests/test_gpu_fuzz.py runs a fixed 200-case slice under ``-m gpu`` and pins the one miss the long runs ever produced (seed 303,
 case 1081; tests/golden/fuzz_seed303_case1081.npz)."""
@@ -15,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "gnn-tf_amd"), os.path.join(ROOT, "tests")]
 import numpy as np
 
-KINDS = ("spmm", "dropped", "kloop", "gcnii", "dense", "wgrad", "head", "edge", "entries", "bf16")
+KINDS = ("spmm", "dropped", "kloop", "gcnii", "dense", "wgrad", "head", "edge", "entries", "bf16", "f32")
 DROP_SEED = 5                                    # seed of the counter RNG in the edge-dropout cases (streams = case number + k)
 
 
@@ -150,6 +151,26 @@ def draw_extra(seed, case, s):
         x["b_off"] = int(rng.integers(0, x["b_pad"] + 1))
         x["b_relu"] = bool(rng.random() < 0.5)                            # (the K loop; the single SpMM takes the case's own relu draw)
         x["b_d"] = rng.uniform(0.5, 1.5, s["n"]).astype(np.float32)
+    if kind == 0:
+        rng = np.random.default_rng([seed, case, 3])
+        n, n_cols = s["n"], s["n_cols"]
+        for e in F32_ENTRIES:
+            tall = n_cols if e in ("t", "tv") else n
+            x[f"f_{e}_h0"] = int(rng.integers(3))                           # F32_H0: none / full / one bias row (ldh0 = 0)
+            x[f"f_{e}_diag"] = bool(rng.random() < 0.5) and s["sq"] and e != "rows"
+            x[f"f_{e}_relu"] = bool(rng.random() < 0.5)
+            x[f"f_{e}_skip"] = bool(rng.random() < 0.5) and e in ("spmm", "rows")
+            # X, H0, out: columns off ... off + C of a buffer C + pad wide; pads and offsets are multiples of ``unit``, which is what
+            # decides the per-lane vector width where C allows 4
+            unit = int(rng.choice([4, 2, 1], p=[0.4, 0.3, 0.3]))
+            x[f"f_{e}_pad"] = unit * rng.integers(0, 5, size=3)
+            x[f"f_{e}_off"] = unit * rng.integers(0, x[f"f_{e}_pad"] // unit + 1)
+            x[f"f_{e}_d"] = rng.uniform(0.5, 1.5, tall).astype(np.float32)
+        x["f_perm"] = rng.permutation(n).astype(np.int32)                   # gnx_spmm_scatter's map
+        x["f_n_out"] = n + int(rng.integers(0, 40))                         # gnx_spmm_rows: an ascending map into a taller buffer
+        x["f_rows"] = np.sort(rng.choice(x["f_n_out"], size=n, replace=False)).astype(np.int32)
+        x["f_H0_cols"] = rng.standard_normal((n_cols, s["C"])).astype(np.float32)      # the mix operand of the transposed entries
+        x["f_H0_tall"] = rng.standard_normal((x["f_n_out"], s["C"])).astype(np.float32)  # and of gnx_spmm_rows
     return x
 
 
@@ -408,6 +429,129 @@ def check_bf16_loop(s, g):
     assert err <= 1e-3, (what, "against the emulation", err)
 
 
+F32_ENTRIES = ("spmm", "scatter", "rows", "t", "tv")
+F32_H0 = ("none", "full", "bias")
+F32_SENTINEL = 7.0
+F32_BETA, F32_ALPHA = 0.8, 0.2
+
+
+def f32_layout(s, e):
+    """(ldx, ldh0 or None, ldo), (byte offsets of X, H0 or None, out) and the per-lane vector width pick_vec must choose for them."""
+    C, pad, off = s["C"], s[f"f_{e}_pad"], s[f"f_{e}_off"]
+    h0 = F32_H0[s[f"f_{e}_h0"]]
+    lds = (C + int(pad[0]), None if h0 == "none" else 0 if h0 == "bias" else C + int(pad[1]), C + int(pad[2]))
+    offs = (4 * int(off[0]), None if h0 == "none" else 4 * int(off[1]), 4 * int(off[2]))
+    vec = 1
+    for v in (4, 2):
+        if C % v == 0 and all(ld % v == 0 for ld in lds if ld is not None) and all(b % (4 * v) == 0 for b in offs if b is not None):
+            vec = v
+            break
+    return lds, offs, vec
+
+
+def f32_reference(s, e):
+    """(want, mag, to, live) of entry ``e`` of the f32 rider: float64 result and mag = |beta| (|A| |x| + |d| |x|) + |alpha h0| per
+    COMPACT result row, the buffer row each lands in, and whether the launch writes it (GNX_ACT_SKIP_EMPTY without a diagonal
+    leaves the rows without entries alone)."""
+    import scipy.sparse as sp
+    n, n_cols, idx, vals = s["n"], s["n_cols"], s["idx"], s["vals"]
+    A = sp.coo_matrix((vals.astype(np.float64), (idx[:, 0], idx[:, 1])), shape=(n, n_cols)).tocsr()      # duplicates are summed
+    tr = e in ("t", "tv")
+    if tr:
+        A = sp.csr_matrix(A.T)
+    x = (s["H0"] if tr else s["X"]).astype(np.float64)
+    S, M = A @ x, abs(A) @ np.abs(x)
+    if s[f"f_{e}_diag"]:
+        d = s[f"f_{e}_d"].astype(np.float64)
+        S, M = S + d[:, None] * x, M + d[:, None] * np.abs(x)
+    to = s["f_perm"] if e == "scatter" else s["f_rows"] if e == "rows" else np.arange(A.shape[0])
+    b, a = float(np.float32(F32_BETA)), float(np.float32(F32_ALPHA))
+    pre, mag = b * S, abs(b) * M
+    h0 = f32_mix_operand(s, e)
+    if h0 is not None:
+        h0 = h0.astype(np.float64)
+        h0 = np.broadcast_to(h0, pre.shape) if len(h0) == 1 and F32_H0[s[f"f_{e}_h0"]] == "bias" else h0[to] if e == "rows" else h0
+        pre, mag = pre + a * h0, mag + np.abs(a * h0)
+    live = np.ones(A.shape[0], dtype=bool)
+    if s[f"f_{e}_skip"] and not s[f"f_{e}_diag"]:
+        live = np.diff(A.indptr) > 0
+    return (np.maximum(pre, 0) if s[f"f_{e}_relu"] else pre), mag, to.astype(np.int64), live
+
+
+def f32_mix_operand(s, e):
+    """H0 as entry ``e`` is handed it: None, [rows of the result buffer, C], or the first of those rows as a bias."""
+    form = F32_H0[s[f"f_{e}_h0"]]
+    if form == "none":
+        return None
+    full = s["f_H0_cols"] if e in ("t", "tv") else s["f_H0_tall"] if e == "rows" else s["H0"]
+    return full[:1] if form == "bias" else full
+
+
+def check_f32_spmm(s, g):
+    """Rider "f32" on a kind-0 case: every f32 eval entry with drawn optional operands against float64, by the bf16 rider's rule for
+    float32 results, |got - ref| <= 1e-5 |ref| + 1e-5 mag, and a sentinel wherever the launch has nothing to write.  Returns the worst
+    |got - ref| / (1e-5 |ref| + 1e-5 mag) of the case."""
+    import torch
+    from gnntf import _native as nat
+    case, n, n_cols, C = s["case"], s["n"], s["n_cols"], s["C"]
+    lib, worst = nat.lib(), 0.0
+    vals_t = torch.empty(g.nnz, dtype=torch.float32, device="cuda:0")
+    nat.check(lib.gnx_graph_permute_values_t(g.handle, None, nat.ptr(vals_t), nat.current_stream()))
+
+    def window(values, pad, off, fill):
+        buf = torch.full((values.shape[0], C + pad), fill, dtype=torch.float32, device="cuda:0")
+        buf[:, off:off + C] = values
+        return buf, buf[:, off:off + C]
+
+    for e in F32_ENTRIES:
+        tr = e in ("t", "tv")
+        pad, off = s[f"f_{e}_pad"], s[f"f_{e}_off"]
+        lds, offs, vec = f32_layout(s, e)
+        want, mag, to, live = f32_reference(s, e)
+        n_res = n_cols if tr else n
+        tall = s["f_n_out"] if e == "rows" else n_res
+        _, X = window(dev(s["H0"] if tr else s["X"]), int(pad[0]), int(off[0]), float("nan"))
+        h0 = f32_mix_operand(s, e)
+        H0 = None if h0 is None else window(dev(h0), int(pad[1]), int(off[1]), float("nan"))[1]
+        d = dev(s[f"f_{e}_d"]) if s[f"f_{e}_diag"] else None
+        buf, out = window(torch.full((tall, C), F32_SENTINEL, device="cuda:0"), int(pad[2]), int(off[2]), F32_SENTINEL)
+        assert (X.stride(0), out.stride(0)) == (lds[0], lds[2]) and (X.data_ptr() % 16, out.data_ptr() % 16) == (offs[0] % 16, offs[2] % 16)
+        act = (nat.ACT_RELU if s[f"f_{e}_relu"] else nat.ACT_NONE) | (nat.ACT_SKIP_EMPTY if s[f"f_{e}_skip"] else 0)
+        mid = (nat.ptr(X), X.stride(0), C, nat.ptr(H0), lds[1] or 0, F32_BETA, F32_ALPHA, act)
+        end = (nat.ptr(out), out.stride(0), nat.current_stream())
+        if e == "spmm":
+            rc = lib.gnx_spmm(g.handle, None, nat.ptr(d), *mid, *end)
+        elif e == "scatter":
+            rc = lib.gnx_spmm_scatter(g.handle, None, nat.ptr(d), *mid, nat.ptr(dev(s["f_perm"])), *end)
+        elif e == "rows":
+            rc = lib.gnx_spmm_rows(g.handle, None, *mid, nat.ptr(dev(s["f_rows"])), *end)
+        elif e == "t":
+            rc = lib.gnx_spmm_t(g.handle, None, nat.ptr(d), *mid, *end)
+        else:
+            rc = lib.gnx_spmm_tv(g.handle, nat.ptr(vals_t), nat.ptr(d), *mid, *end)
+        nat.check(rc)
+        what = (f"f32 case {case} {e}: n={n} n_cols={n_cols} C={C} vec={vec} " +
+                " ".join(f"{k[len(e) + 3:]}={s[k]}" for k in sorted(s) if k.startswith(f"f_{e}_") and not k.endswith("_d")))
+        whole = buf.cpu().numpy()
+        o = int(off[2])
+        got = whole[:, o:o + C]
+        written = np.zeros(tall, dtype=bool)
+        written[to[live]] = True
+        assert (whole[:, :o] == F32_SENTINEL).all() and (whole[:, o + C:] == F32_SENTINEL).all(), (what, "padding columns written")
+        assert (got[~written] == F32_SENTINEL).all(), (what, "a row outside the map or without entries was written")
+        gv = got[to[live]].astype(np.float64)
+        ref, allowed = want[live], 1e-5 * np.abs(want[live]) + 1e-5 * mag[live]
+        bad = ~(np.abs(gv - ref) <= allowed)                                 # (a NaN from the padding fails here)
+        assert not bad.any(), (what, np.argwhere(bad)[:5], float(np.abs(gv - ref).max()))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            share = np.where(allowed > 0, np.abs(gv - ref) / allowed, 0.0)
+        worst = max(worst, float(share.max()) if share.size else 0.0)
+    return worst
+
+
+F32_WORST = [0.0]                                 # worst share of the f32 rider's allowance used in this process (run() reports it)
+
+
 def check_case(s):
     """Runs the kernels on one drawn case; returns the names of the statistics it counts for (none: an empty graph, nothing run):
     the case's own kind and, with the rider's draws present (draw_extra), its rider's."""
@@ -417,6 +561,8 @@ def check_case(s):
         kinds.append(check_entries(s))
     if "b_pad" in s and kind is not None:            # (checked inside the case: it shares the case's device graph)
         kinds.append("bf16")
+    if "f_perm" in s and kind is not None:
+        kinds.append("f32")
     return kinds
 
 
@@ -445,6 +591,8 @@ def _check_case(s):
                 np.testing.assert_allclose(gt, wt, rtol=1e-4, atol=2e-4 + 1e-5 * np.sqrt(int(np.bincount(idx[:, 1], minlength=n_cols).max())), err_msg=f"spmm_t case {case}")
             if "b_pad" in s:
                 check_bf16_spmm(s, g)
+            if "f_perm" in s:
+                F32_WORST[0] = max(F32_WORST[0], check_f32_spmm(s, g))
             return "spmm"
         if kind == 1 and nnz:
             p, K = s["p"], s["K"]
@@ -569,6 +717,8 @@ def run(cases, seed, first=0, verbose=True):
         if verbose and case % 50 == 49:
             print(f"{case + 1} cases, {time.time() - t0:.0f} s", stats, flush=True)
     torch.cuda.synchronize()
+    if verbose and stats["f32"]:
+        print(f"f32 rider: worst |got - ref| / (1e-5 |ref| + 1e-5 mag) over {stats['f32']} cases: {F32_WORST[0]:.4f}", flush=True)
     if verbose or PASSED_ONLY_WITH_THE_FLOOR[0]:
         print(f"backward comparisons that pass only with the 1 % floor of rel_rows: {PASSED_ONLY_WITH_THE_FLOOR[0]} of {stats['dropped']}", flush=True)
     return stats

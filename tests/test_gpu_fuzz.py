@@ -21,9 +21,12 @@ pytestmark = pytest.mark.gpu
 EPS = 2.0 ** -24                                  # one float32 rounding (half an ulp, relative)
 
 
-def test_fixed_slice_of_the_fuzz():
+def test_fixed_slice_of_the_fuzz(capsys):
     stats = fz.run(200, seed=11, verbose=False)
     assert sum(stats.values()) >= 190 and all(stats[k] >= 20 for k in fz.KINDS), stats
+    with capsys.disabled():
+        print(f"\n[fuzz slice, seed 11] f32 rider: worst |got - ref| / (1e-5 |ref| + 1e-5 mag) over {stats['f32']} cases: {fz.F32_WORST[0]:.4f}")
+    assert 0 < fz.F32_WORST[0] <= 1.0
 
 
 def test_pinned_fixture_is_the_replayed_case(golden_dir):
