@@ -5,7 +5,8 @@
 //                      k_ngcf_tail: the same layer as row passes around the dense kernel; k_ngcf_back_gate: the backward's first pass)
 //   k_ngcf_back        the backward around the transposed SpMM in one launch (gnx_step_back_ngcf): the gate, G1 . W1^T and G2 . W2^T
 //                      through one tile per wave, dA, R and P from the walk, the bias sums as slabs (k_ngcf_back_sums adds them)
-//   ngcf_forward       gnx_ngcf_step (gnx_ngcf_back_gate and gnx_step_back_ngcf are entries of their own)
+//   ngcf_forward       gnx_ngcf_step (gnx_ngcf_back_gate and gnx_step_back_ngcf are entries of their own; the backward's checks, prelude
+//                      and transposed SpMM are NgcfBackCall's in gnx_ngcf_device.h, which gnx_step_back_wide_ngcf goes through too)
 #include "gnx_ngcf_device.h"
 
 namespace {
@@ -623,14 +624,13 @@ int gnx_ngcf_back_gate(gnx_graph_t g, const float *d_g, int64_t ldg, const float
     GNX_CHECK_ARG(g != nullptr, "%s: NULL handle", fn);
     GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU || act == GNX_ACT_LEAKY, "%s: invalid activation %d", fn, act);
     GNX_CHECK_ARG(n_rows >= 0 && C_out >= 1 && C_out <= (1 << 20), "%s: negative row count or C_out not in [1, 2^20]", fn);
-    GNX_CHECK_ARG(d_g != nullptr && d_G1 != nullptr && d_G2 != nullptr && ldg >= C_out && ldG >= C_out, "%s: NULL g / G1 / G2 or a row stride below C_out", fn);
-    GNX_CHECK_ARG(d_rnorm == nullptr || (d_y != nullptr && ldy >= C_out), "%s: d_rnorm needs y (the normalised forward output) with ldy >= C_out", fn);
-    GNX_CHECK_ARG(act == GNX_ACT_NONE || d_gate != nullptr, "%s: relu / leaky_relu need d_gate", fn);
+    int rc = NgcfBackCall{g, d_g, ldg, d_y, ldy, d_rnorm, d_gate, C_out, act, d_G1, d_G2, ldG}.grads(fn);
+    if (rc != GNX_OK) return rc;
     const void *gate = d_gate;
     GNX_CHECK_ARG(d_G1 != d_G2 && d_G1 != d_g && d_G2 != d_g && d_G1 != d_y && d_G2 != d_y && d_G1 != d_rnorm && d_G2 != d_rnorm &&
                   (const void *)d_G1 != gate && (const void *)d_G2 != gate, "%s: G1 and G2 must be buffers of their own", fn);
     DropFuse fd{};
-    const int rc = make_feat_drop(fn, g, dropout_p, seed, stream_id, fd);
+    rc = make_feat_drop(fn, g, dropout_p, seed, stream_id, fd);
     if (rc != GNX_OK) return rc;
     if (n_rows == 0) return GNX_OK;
     hipStream_t s = (hipStream_t)stream;
@@ -650,43 +650,22 @@ int gnx_step_back_ngcf(gnx_graph_t g, const float *d_vals_t, const float *d_g, i
                        float *d_G1, float *d_G2, int64_t ldG, float *d_P, float *d_db1, float *d_db2, float *d_dA, float *d_R, float *d_dX,
                        int64_t lddx, float *d_work, int64_t work_floats, void *stream) {
     const char *fn = "gnx_step_back_ngcf";
-    GNX_CHECK_ARG(g != nullptr, "%s: NULL handle", fn);
-    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU || act == GNX_ACT_LEAKY, "%s: invalid activation %d", fn, act);
-    GNX_CHECK_ARG(dropout_p >= 0.0 && dropout_p < 1.0, "%s: dropout rate %g outside [0, 1)", fn, dropout_p);
-    GNX_CHECK_ARG(C_in >= 1 && C_in <= (1 << 20) && C_out >= 1 && C_out <= (1 << 20), "%s: widths %lld -> %lld not in [1, 2^20]", fn,
-                  (long long)C_in, (long long)C_out);
+    const NgcfBackCall c{g, d_g, ldg, d_y, ldy, d_rnorm, d_gate, C_out, act, d_G1, d_G2, ldG, dropout_p, seed, stream_id, d_vals_t, d_X, ldx, d_agg,
+                         C_in, d_W1, ldw1, d_W2, ldw2, d_P, d_db1, d_db2, d_dA, d_R, d_dX, lddx, d_work, work_floats, stream};
+    int rc = c.front(fn);
+    if (rc != GNX_OK) return rc;
     if (!fused_width(C_in)) return refuse_unfused(fn, C_in);
     if (C_out > C_in) {
         set_error("%s: C_out %lld > C_in %lld is not supported (the fused backward takes C_out <= C_in; keep the composed backward elsewhere)", fn,
                   (long long)C_out, (long long)C_in);
         return GNX_ERR_UNSUPPORTED;
     }
-    GNX_CHECK_ARG(d_g != nullptr && d_G1 != nullptr && d_G2 != nullptr && ldg >= C_out && ldG >= C_out, "%s: NULL g / G1 / G2 or a row stride below C_out", fn);
-    GNX_CHECK_ARG(d_rnorm == nullptr || (d_y != nullptr && ldy >= C_out), "%s: d_rnorm needs y (the normalised forward output) with ldy >= C_out", fn);
-    GNX_CHECK_ARG(act == GNX_ACT_NONE || d_gate != nullptr, "%s: relu / leaky_relu need d_gate", fn);
-    GNX_CHECK_ARG(d_X != nullptr && d_agg != nullptr && ldx >= C_in, "%s: NULL X / agg, or ldx %lld < C_in %lld", fn, (long long)ldx, (long long)C_in);
-    const bool products = d_dX != nullptr;
-    GNX_CHECK_ARG(!products || (d_W1 != nullptr && d_W2 != nullptr && d_dA != nullptr && d_R != nullptr), "%s: dX needs W1, W2, d_dA and d_R", fn);
-    GNX_CHECK_ARG(!products || (ldw1 >= C_out && ldw2 >= C_out), "%s: ldw1 %lld or ldw2 %lld < C_out %lld", fn, (long long)ldw1, (long long)ldw2,
-                  (long long)C_out);
-    GNX_CHECK_ARG(!products || lddx >= C_in, "%s: lddx %lld < C_in %lld", fn, (long long)lddx, (long long)C_in);
-    GNX_CHECK_ARG(work_floats >= 0 && (d_work != nullptr || work_floats == 0), "%s: work_floats %lld without d_work, or negative", fn,
-                  (long long)work_floats);
-    // buffers of their own: no output is an input or another output (d_dA and d_R are looked at only where they are written)
-    const void *in[] = {d_vals_t, d_g, d_y, d_rnorm, d_gate, d_X, d_agg, d_W1, d_W2};
-    const void *out[] = {d_G1, d_G2, d_P, d_db1, d_db2, products ? d_dA : nullptr, products ? d_R : nullptr, d_dX, d_work};
-    const char *names[] = {"d_G1", "d_G2", "d_P", "d_db1", "d_db2", "d_dA", "d_R", "d_dX", "d_work"};
-    for (size_t i = 0; i < sizeof(out) / sizeof(out[0]); ++i) {
-        if (out[i] == nullptr) continue;
-        bool own = true;
-        for (const void *b : in) own = own && out[i] != b;
-        for (size_t j = 0; j < i; ++j) own = own && out[i] != out[j];
-        GNX_CHECK_ARG(own, "%s: %s must be a buffer of its own", fn, names[i]);
-    }
-    if (ldx % 4 != 0 || ldG % 4 != 0 || !aligned(d_X, 16) || !aligned(d_agg, 16) || !aligned(d_G1, 16) || !aligned(d_G2, 16) || !aligned(d_P, 16) ||
-        (products && (!aligned(d_dA, 16) || !aligned(d_R, 16))))
-        return refuse_unfused(fn, C_in);
+    rc = c.args(fn);
+    if (rc == GNX_OK) rc = c.own(fn);
+    if (rc != GNX_OK) return rc;
+    if (!c.aligned16()) return refuse_unfused(fn, C_in);
     GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols && g->blk_col_gid == nullptr, "%s: needs a square stand-alone graph", fn);
+    const bool products = c.products();
     const int64_t n = g->a.n_rows, n_tiles = blocks_for(n, 16);
     const bool sums = d_db1 != nullptr || d_db2 != nullptr;
     constexpr int WPB = 4;
@@ -699,20 +678,9 @@ int gnx_step_back_ngcf(gnx_graph_t g, const float *d_vals_t, const float *d_g, i
                   "group sums of 2 * C_out floats)", fn, (long long)((slabs + group_slabs) * 2 * C_out), (long long)work_floats, (long long)slabs,
                   (long long)group_slabs);
     DropFuse fd{};
-    int rc = make_feat_drop(fn, g, dropout_p, seed, stream_id, fd);
-    if (rc != GNX_OK) return rc;
+    rc = c.prelude(fn, fd);
+    if (rc != GNX_OK || n == 0) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (products) {      // (the transposed structure and the hub rows' slab before the first launch: under capture a part that would have to be built refuses the whole call)
-        rc = ensure_transpose(g, s);
-        if (rc != GNX_OK) return rc;
-        rc = reserve_partial(g, g->t, C_in, s);
-        if (rc != GNX_OK) return rc;
-    }
-    if (n == 0) {
-        if (d_db1) GNX_HIP(hipMemsetAsync(d_db1, 0, (size_t)C_out * sizeof(float), s));
-        if (d_db2) GNX_HIP(hipMemsetAsync(d_db2, 0, (size_t)C_out * sizeof(float), s));
-        return GNX_OK;
-    }
     const bool drop = dropout_p != 0.0;      // p == 0 hashes nothing
     const int64_t tiles_per_block = (blocks_for(n_tiles, (int)slabs) + WPB - 1) / WPB * WPB;
     const int64_t blocks = (n_tiles + tiles_per_block - 1) / tiles_per_block;      // <= slabs
@@ -734,12 +702,7 @@ int gnx_step_back_ngcf(gnx_graph_t g, const float *d_vals_t, const float *d_g, i
         hipLaunchKernelGGL(k_ngcf_back_sums, dim3(1), dim3(128), 0, s, groups, n_groups, n_groups, (int)C_out, nullptr, d_db1, d_db2);
     }
     GNX_HIP(hipGetLastError());
-    if (products) {
-        rc = gnx_spmm_tv(g, d_vals_t ? d_vals_t : g->t_raw.get(), nullptr, d_dA, C_in, C_in, d_R, C_in, 1.f, 1.f, GNX_ACT_NONE, d_dX, lddx, stream);
-        if (rc != GNX_OK) return rc;
-    }
-    g->last_kernel = kNgcfBack[C_in == 16 ? 0 : C_in == 32 ? 1 : 2][drop][products];
-    return GNX_OK;
+    return c.finish(kNgcfBack[C_in == 16 ? 0 : C_in == 32 ? 1 : 2][drop][products]);
 }
 
 }  // extern "C"

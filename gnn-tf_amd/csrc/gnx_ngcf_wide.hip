@@ -4,14 +4,15 @@
 //   gnx_step_wide_ngcf gnx_spmm into d_agg (or d_work), then k_ngcf_rows over all n rows
 // Why two launches and not k_spmm_ngcf at a fourth width: profiles/NOTES.md, "NGCF layer at width 128" (eight waves per CU cannot keep
 // the gathers in flight beside 128 KiB of weights; the wide SpMM alone already runs at the random-gather rate).
-#include "gnx_dense_device.h"
+// The constants of the launch shape it shares with k_ngcf_rows_back, the launch and the dispatch of the block count stand in
+// gnx_ngcf_wide_device.h (which also says why the kernel keeps its own text); the pieces of a finished value and the entry's checks in
+// gnx_ngcf_device.h.
 #include "gnx_ngcf_device.h"
+#include "gnx_ngcf_wide_device.h"
 
 namespace {
 
-constexpr int WIDE_C = 128;       // C_in of the launch
-constexpr int WIDE_KK = 32;       // its MFMA steps of four k
-constexpr int WIDE_WPB = 8;       // waves per block: one block per CU, two waves per SIMD
+constexpr int WIDE_KK = WIDE_C / 4;      // the MFMA steps of four k
 
 struct NgcfRows {
     const float *X; int64_t ldx; const float *A; int64_t n;       // A [n, 128] contiguous
@@ -95,10 +96,7 @@ __global__ __launch_bounds__(64 * WIDE_WPB) void k_ngcf_rows(const NgcfRows a) {
         f32x4 d1[NTO], d2[NTO];
 #pragma unroll
         for (int nt = 0; nt < NTO; ++nt) { d1[nt] = f32x4{0.f, 0.f, 0.f, 0.f}; d2[nt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        // (the lane's place in the images, made opaque per tile: read as a loop invariant, the images of the narrow outputs are hoisted
-        // out of the tile loop into registers -- up to 160 of them -- and the instantiations of 32 to 80 columns spill)
-        int at = lane;
-        asm volatile("" : "+v"(at));
+        const int at = ngcf_image_at(lane);
 #pragma unroll
         for (int kk = 0; kk < WIDE_KK; ++kk) {
             const float av = aa[kk], mv = xa[kk] * aa[kk];
@@ -192,25 +190,6 @@ __global__ __launch_bounds__(64 * WIDE_WPB) void k_ngcf_rows(const NgcfRows a) {
 const char *const kNgcfWide[2][2] = {{"spmm+k_ngcf_rows<128>", "spmm+k_ngcf_rows<128>_norm"},
                                      {"spmm+k_ngcf_rows<128>_drop", "spmm+k_ngcf_rows<128>_drop_norm"}};
 
-// the launch at NTO blocks of 16 output columns: the dynamic-LDS limit once per device and instantiation, a block per CU
-template <int NTO, bool DROP>
-int launch_ngcf_rows(const NgcfRows &a, hipStream_t s) {
-    const int cus = persistent_launch<k_ngcf_rows<NTO, DROP>>();
-    if (cus < 0) return cus;
-    const int64_t blocks = std::min<int64_t>(cus, blocks_for(blocks_for(a.n, 16), WIDE_WPB));
-    const size_t lds_bytes = (size_t)2 * WIDE_KK * NTO * 64 * sizeof(float);
-    hipLaunchKernelGGL((k_ngcf_rows<NTO, DROP>), dim3((unsigned)blocks), dim3(64 * WIDE_WPB), lds_bytes, s, a);
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
-}
-
-template <int NTO>
-int launch_ngcf_rows_at(int nto, bool drop, const NgcfRows &a, hipStream_t s) {
-    if (nto == NTO) return drop ? launch_ngcf_rows<NTO, true>(a, s) : launch_ngcf_rows<NTO, false>(a, s);
-    if constexpr (NTO < WIDE_C / 16) return launch_ngcf_rows_at<NTO + 1>(nto, drop, a, s);
-    else return GNX_ERR_INVALID;      // (not reached: 1 <= nto <= 8 was checked)
-}
-
 }  // namespace
 
 extern "C" {
@@ -253,7 +232,11 @@ int gnx_step_wide_ngcf(gnx_graph_t g, const float *d_vals, const float *d_X, int
     const NgcfRows a{d_X, ldx, T, n, d_W1, ldw1, d_W2, ldw2, (int)C_out, d_b1, d_b2, act, d_out, ldo,
                      act == GNX_ACT_NONE ? nullptr : d_gate,      // (the identity has nothing to gate)
                      d_rnorm, normalize != 0, ldo % 4 == 0 && aligned(d_out, 16), fd};
-    rc = launch_ngcf_rows_at<1>((int)blocks_for(C_out, 16), drop, a, (hipStream_t)stream);
+    rc = with_wide_tiles<1>((int)blocks_for(C_out, 16), [&](auto NTO) {      // (both weight images as dynamic LDS)
+        constexpr size_t lds_bytes = (size_t)2 * WIDE_KK * NTO() * 64 * sizeof(float);
+        return drop ? launch_ngcf_rows_kernel<k_ngcf_rows<NTO(), true>>(a, lds_bytes, n, (hipStream_t)stream)
+                    : launch_ngcf_rows_kernel<k_ngcf_rows<NTO(), false>>(a, lds_bytes, n, (hipStream_t)stream);
+    });
     if (rc != GNX_OK) return rc;
     g->last_kernel = kNgcfWide[drop ? 1 : 0][normalize];
     return GNX_OK;

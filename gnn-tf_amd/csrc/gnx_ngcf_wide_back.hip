@@ -5,15 +5,12 @@
 //   k_ngcf_wide_colsums, k_ngcf_wide_slabsum   db1 / db2: the column sums of G1 / G2 in slabs of rows, the slabs added in index order
 //   gnx_step_back_wide_ngcf   gnx_ngcf_back_gate, the two sums, k_ngcf_rows_back over all n rows, gnx_spmm_tv over dA with R mixed in
 // The launch shape is k_ngcf_rows' (gnx_ngcf_wide.hip): a block of eight waves per CU, persistent over 16-row tiles, both weight
-// matrices in LDS.  Measured against the composed backward in profiles/NOTES.md, "NGCF backward at width 128".
-#include "gnx_dense_device.h"
-#include "gnx_layer_device.h"
+// matrices in LDS; what the two units share of it stands in gnx_ngcf_wide_device.h, and the entry's host path, which is
+// gnx_step_back_ngcf's, in gnx_ngcf_device.h.  Measured against the composed backward in profiles/NOTES.md, "NGCF backward at width 128".
+#include "gnx_ngcf_device.h"
+#include "gnx_ngcf_wide_device.h"
 
 namespace {
-
-constexpr int WIDE_C = 128;       // C_in of the launch: the width of Q1, Q2, X, A, dA, R and P
-constexpr int WIDE_NT = 8;        // its blocks of 16 result columns
-constexpr int WIDE_WPB = 8;       // waves per block: one block per CU, two waves per SIMD
 
 struct NgcfRowsBack {
     const float *G1, *G2; int64_t ldG; int C_out, pad;              // pad = roundup4(C_out): the columns of G1 / G2 that exist
@@ -21,19 +18,6 @@ struct NgcfRowsBack {
     const float *W1; int64_t ldw1; const float *W2; int64_t ldw2;
     float *P, *dA, *R;                                              // [n, 128] contiguous each; P may be null
 };
-
-// The four lanes 4 q .. 4 q + 3 of a row exchange a 4 x 4 block (k_ngcf_rows' store): v[i] is the lane's value -- column 16 (4 h + i) +
-// cc of its row -- of result block 4 h + i; afterwards w[e] is column 64 h + 16 j + 4 q + e, (j, q) = (cc & 3, cc >> 2).
-__device__ __forceinline__ void ngcf_exchange(const float (&v)[4], int j, float (&w)[4]) {
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {      // lane j ^ s sends its value of block j
-        const int i = j ^ s;
-        const float t = i == 0 ? v[0] : i == 1 ? v[1] : i == 2 ? v[2] : v[3];
-        const float got = s ? __shfl_xor(t, s) : t;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) w[e] = e == i ? got : w[e];
-    }
-}
 
 // One block of eight waves per CU, persistent: block b takes the tiles 8 b + w, 8 (b + gridDim.x) + w, .. (tile t: rows 16 t .. 16 t + 15)
 // with its wave w.  Which wave finishes a row changes no bit of it: nothing below depends on the tile but the row ids.  No gather.
@@ -92,10 +76,7 @@ __global__ __launch_bounds__(64 * WIDE_WPB) void k_ngcf_rows_back(const NgcfRows
             // both products
 #pragma unroll
             for (int nt = 0; nt < WIDE_NT; ++nt) { d1[nt] = f32x4{0.f, 0.f, 0.f, 0.f}; d2[nt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-            // (the lane's place in the images, made opaque per tile: read as a loop invariant, the images of the narrow instantiations
-            // are hoisted out of the tile loop into registers and spill -- profiles/NOTES.md, "NGCF layer at width 128")
-            int at = lane;
-            asm volatile("" : "+v"(at));
+            const int at = ngcf_image_at(lane);
             const float *W1s = lds, *W2s = lds + IMG;
 #pragma unroll
             for (int kk = 0; kk < KK; ++kk) {
@@ -190,25 +171,6 @@ __global__ __launch_bounds__(256) void k_ngcf_wide_slabsum(const float *__restri
 const char *const kNgcfWideBack[2][2] = {{"k_ngcf_rows_back<128>", "k_ngcf_rows_back<128>+spmm_tv"},
                                          {"k_ngcf_rows_back<128>_drop", "k_ngcf_rows_back<128>_drop+spmm_tv"}};
 
-// the launch at NTK blocks of 16 output columns (0: P alone): the dynamic-LDS limit once per device and instantiation, a block per CU
-template <int NTK>
-int launch_ngcf_rows_back(const NgcfRowsBack &a, hipStream_t s) {
-    const int cus = persistent_launch<k_ngcf_rows_back<NTK>>();
-    if (cus < 0) return cus;
-    const int64_t blocks = std::min<int64_t>(cus, blocks_for(blocks_for(a.n, 16), WIDE_WPB));
-    const size_t lds_bytes = (size_t)2 * 4 * NTK * WIDE_NT * 64 * sizeof(float);
-    hipLaunchKernelGGL((k_ngcf_rows_back<NTK>), dim3((unsigned)blocks), dim3(64 * WIDE_WPB), lds_bytes, s, a);
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
-}
-
-template <int NTK>
-int launch_ngcf_rows_back_at(int ntk, const NgcfRowsBack &a, hipStream_t s) {
-    if (ntk == NTK) return launch_ngcf_rows_back<NTK>(a, s);
-    if constexpr (NTK < WIDE_C / 16) return launch_ngcf_rows_back_at<NTK + 1>(ntk, a, s);
-    else return GNX_ERR_INVALID;      // (not reached: 0 <= ntk <= 8)
-}
-
 // the slabs of the column sums: a function of n alone
 int64_t ngcf_wide_slabs(int64_t n) { return std::max<int64_t>(1, std::min<int64_t>(1024, blocks_for(n, 512))); }
 
@@ -224,42 +186,23 @@ int gnx_step_back_wide_ngcf(gnx_graph_t g, const float *d_vals_t, const float *d
                             float *d_db2, float *d_dA, float *d_R, float *d_dX, int64_t lddx, float *d_work, int64_t work_floats,
                             void *stream) {
     const char *fn = "gnx_step_back_wide_ngcf";
-    GNX_CHECK_ARG(g != nullptr, "%s: NULL handle", fn);
-    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU || act == GNX_ACT_LEAKY, "%s: invalid activation %d", fn, act);
-    GNX_CHECK_ARG(dropout_p >= 0.0 && dropout_p < 1.0, "%s: dropout rate %g outside [0, 1)", fn, dropout_p);
-    GNX_CHECK_ARG(C_in >= 1 && C_in <= (1 << 20) && C_out >= 1 && C_out <= (1 << 20), "%s: widths %lld -> %lld not in [1, 2^20]", fn,
-                  (long long)C_in, (long long)C_out);
+    const NgcfBackCall c{g, d_g, ldg, d_y, ldy, d_rnorm, d_gate, C_out, act, d_G1, d_G2, ldG, dropout_p, seed, stream_id, d_vals_t, d_X, ldx, d_agg,
+                         C_in, d_W1, ldw1, d_W2, ldw2, d_P, d_db1, d_db2, d_dA, d_R, d_dX, lddx, d_work, work_floats, stream};
+    int rc = c.front(fn);
+    if (rc != GNX_OK) return rc;
     if (C_in != WIDE_C || C_out > C_in) {
         set_error("%s: widths %lld -> %lld are not supported (the row-local launch takes C_in = 128 and C_out <= 128; keep the composed backward "
                   "elsewhere)", fn, (long long)C_in, (long long)C_out);
         return GNX_ERR_UNSUPPORTED;
     }
-    GNX_CHECK_ARG(d_g != nullptr && d_G1 != nullptr && d_G2 != nullptr && ldg >= C_out && ldG >= C_out, "%s: NULL g / G1 / G2 or a row stride below C_out", fn);
-    GNX_CHECK_ARG(d_rnorm == nullptr || (d_y != nullptr && ldy >= C_out), "%s: d_rnorm needs y (the normalised forward output) with ldy >= C_out", fn);
-    GNX_CHECK_ARG(act == GNX_ACT_NONE || d_gate != nullptr, "%s: relu / leaky_relu need d_gate", fn);
-    GNX_CHECK_ARG(d_X != nullptr && d_agg != nullptr && ldx >= C_in, "%s: NULL X / agg, or ldx %lld < C_in %lld", fn, (long long)ldx, (long long)C_in);
-    const bool products = d_dX != nullptr;
-    GNX_CHECK_ARG(!products || (d_W1 != nullptr && d_W2 != nullptr && d_dA != nullptr && d_R != nullptr), "%s: dX needs W1, W2, d_dA and d_R", fn);
-    GNX_CHECK_ARG(!products || (ldw1 >= C_out && ldw2 >= C_out), "%s: ldw1 %lld or ldw2 %lld < C_out %lld", fn, (long long)ldw1, (long long)ldw2,
-                  (long long)C_out);
-    GNX_CHECK_ARG(!products || lddx >= C_in, "%s: lddx %lld < C_in %lld", fn, (long long)lddx, (long long)C_in);
-    GNX_CHECK_ARG(work_floats >= 0 && (d_work != nullptr || work_floats == 0), "%s: work_floats %lld without d_work, or negative", fn,
-                  (long long)work_floats);
+    rc = c.args(fn);
+    if (rc != GNX_OK) return rc;
     GNX_CHECK_ARG(g->a.n_rows == g->a.n_cols && g->blk_col_gid == nullptr, "%s: needs a square stand-alone graph", fn);
-    // buffers of their own: no output is an input or another output (d_dA and d_R are looked at only where they are written)
-    const void *in[] = {d_vals_t, d_g, d_y, d_rnorm, d_gate, d_X, d_agg, d_W1, d_W2};
-    const void *out[] = {d_G1, d_G2, d_P, d_db1, d_db2, products ? d_dA : nullptr, products ? d_R : nullptr, d_dX, d_work};
-    const char *names[] = {"d_G1", "d_G2", "d_P", "d_db1", "d_db2", "d_dA", "d_R", "d_dX", "d_work"};
-    for (size_t i = 0; i < sizeof(out) / sizeof(out[0]); ++i) {
-        if (out[i] == nullptr) continue;
-        bool own = true;
-        for (const void *b : in) own = own && out[i] != b;
-        for (size_t k = 0; k < i; ++k) own = own && out[i] != out[k];
-        GNX_CHECK_ARG(own, "%s: %s must be a buffer of its own", fn, names[i]);
-    }
+    rc = c.own(fn);
+    if (rc != GNX_OK) return rc;
+    const bool products = c.products();
     const int64_t pad = roundup4(C_out);
-    if (ldx % 4 != 0 || ldG % 4 != 0 || ldG < pad || !aligned(d_X, 16) || !aligned(d_agg, 16) || !aligned(d_G1, 16) || !aligned(d_G2, 16) ||
-        !aligned(d_P, 16) || (products && (!aligned(d_dA, 16) || !aligned(d_R, 16)))) {
+    if (!c.aligned16() || ldG < pad) {
         set_error("%s: misaligned rows (ldx %lld and ldG %lld must be multiples of 4, ldG >= roundup4(C_out) = %lld, and X / d_agg / G1 / G2 / P / "
                   "dA / R 16-byte aligned; keep the composed backward elsewhere)", fn, (long long)ldx, (long long)ldG, (long long)pad);
         return GNX_ERR_UNSUPPORTED;
@@ -270,21 +213,10 @@ int gnx_step_back_wide_ngcf(gnx_graph_t g, const float *d_vals_t, const float *d
     GNX_CHECK_ARG(!sums || work_floats >= slabs * 2 * C_out,
                   "%s: needs d_work of %lld floats, has %lld (s = max(1, min(1024, ceil(n / 512))) = %lld slabs of 2 * C_out floats)", fn,
                   (long long)(slabs * 2 * C_out), (long long)work_floats, (long long)slabs);
-    DropFuse fd{};
-    int rc = make_feat_drop(fn, g, dropout_p, seed, stream_id, fd);
-    if (rc != GNX_OK) return rc;
+    DropFuse fd{};      // (the gate pass makes its own: the prelude checks the rate under this entry's name)
+    rc = c.prelude(fn, fd);
+    if (rc != GNX_OK || n == 0) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (products) {      // (the transposed structure and the hub rows' slab before the first launch: under capture a part that would have to be built refuses the whole call)
-        rc = ensure_transpose(g, s);
-        if (rc != GNX_OK) return rc;
-        rc = reserve_partial(g, g->t, C_in, s);
-        if (rc != GNX_OK) return rc;
-    }
-    if (n == 0) {
-        if (d_db1) GNX_HIP(hipMemsetAsync(d_db1, 0, (size_t)C_out * sizeof(float), s));
-        if (d_db2) GNX_HIP(hipMemsetAsync(d_db2, 0, (size_t)C_out * sizeof(float), s));
-        return GNX_OK;
-    }
     // step A: the gate pass, its own kernel (every argument it checks was checked above, under this entry's name)
     rc = gnx_ngcf_back_gate(g, d_g, ldg, d_y, ldy, d_rnorm, d_gate, n, C_out, act, dropout_p, seed, stream_id, d_G1, d_G2, ldG, stream);
     if (rc != GNX_OK) return rc;
@@ -298,16 +230,13 @@ int gnx_step_back_wide_ngcf(gnx_graph_t g, const float *d_vals_t, const float *d
     if (products || d_P != nullptr) {
         const NgcfRowsBack a{d_G1, d_G2, ldG, (int)C_out, (int)pad, d_X, ldx, d_agg, n, d_W1, ldw1, d_W2, ldw2, d_P, products ? d_dA : nullptr,
                              products ? d_R : nullptr};
-        rc = launch_ngcf_rows_back_at<0>(products ? (int)blocks_for(C_out, 16) : 0, a, s);
+        rc = with_wide_tiles<0>(products ? (int)blocks_for(C_out, 16) : 0, [&](auto NTK) {      // (0: P alone; both weight images as dynamic LDS)
+            return launch_ngcf_rows_kernel<k_ngcf_rows_back<NTK()>>(a, (size_t)2 * 4 * NTK() * WIDE_NT * 64 * sizeof(float), n, s);
+        });
         if (rc != GNX_OK) return rc;
     }
     // step C
-    if (products) {
-        rc = gnx_spmm_tv(g, d_vals_t ? d_vals_t : g->t_raw.get(), nullptr, d_dA, C_in, C_in, d_R, C_in, 1.f, 1.f, GNX_ACT_NONE, d_dX, lddx, stream);
-        if (rc != GNX_OK) return rc;
-    }
-    g->last_kernel = kNgcfWideBack[dropout_p != 0.0 ? 1 : 0][products];
-    return GNX_OK;
+    return c.finish(kNgcfWideBack[dropout_p != 0.0 ? 1 : 0][products]);
 }
 
 }  // extern "C"

@@ -1729,9 +1729,28 @@ def _ngcf_work_floats(n, C_in, C_out, composed_rows, has_agg):
     return (0 if has_agg else up4(n * C_in)) + up4(composed_rows * C_in) + composed_rows * C_out
 
 
+def _ngcf_rows_fit(widths, C_in, C_out, X, A=None):
+    """What every fused NGCF launch asks: C_in in ``widths``, C_out <= C_in, 16-byte aligned rows of X and, where given, of a contiguous A."""
+    return (C_in in widths and C_out <= C_in and X.stride(0) % 4 == 0 and X.data_ptr() % 16 == 0
+            and (A is None or (A.is_contiguous() and A.data_ptr() % 16 == 0)))
+
+
+def _ngcf_need_symbol(keyword, entry):
+    if not nat.has_symbol(entry):      # (a library without the entry raises: nothing falls back)
+        raise Exception(f"ngcf_step: {keyword}=\"fused\" needs {entry}, which this libgnx.so does not export: rebuild the library")
+
+
+def _ngcf_check_saved(n, C_out, activation, gate, y, rnorm):
+    """What the backward reads of the forward's: the gate words, and the reciprocal norms with the output they go with."""
+    if activation != "none" and (gate is None or gate.dtype != torch.int32 or tuple(gate.shape) != (n, 2 * _gate_words(C_out)) or not gate.is_contiguous()):
+        raise Exception("ngcf_step: the gate words must be a contiguous int32 [n, 2 ceil(C_out / 32)]")
+    if rnorm is not None and (y is None or tuple(y.shape) != (n, C_out) or rnorm.numel() != n or not rnorm.is_contiguous()):
+        raise Exception("ngcf_step: the reciprocal norms go with the forward's output")
+
+
 def _ngcf_wide_fusable(wide, X, C_in, C_out):
     """Where ``wide="fused"`` has a launch (gnx_step_wide_ngcf): C_in = 128, C_out <= C_in, 16-byte aligned rows of X."""
-    return wide == "fused" and C_in in NGCF_WIDE_WIDTHS and C_out <= C_in and X.stride(0) % 4 == 0 and X.data_ptr() % 16 == 0
+    return wide == "fused" and _ngcf_rows_fit(NGCF_WIDE_WIDTHS, C_in, C_out, X)
 
 
 def _ngcf_launch(adj: Adjacency, X, W1, b1, W2, b2, activation, keep, dropout=None, normalize=True, wide="composed"):
@@ -1756,16 +1775,15 @@ def _ngcf_launch(adj: Adjacency, X, W1, b1, W2, b2, activation, keep, dropout=No
         if b is not None and b.numel() != C_out:
             raise Exception("ngcf_step: bias width mismatch")
         biases.append(b)
-    one_launch = C_in in NGCF_FUSED_WIDTHS and C_out <= C_in and X.stride(0) % 4 == 0 and X.data_ptr() % 16 == 0
+    one_launch = _ngcf_rows_fit(NGCF_FUSED_WIDTHS, C_in, C_out, X)
     out = torch.empty((n, C_out), dtype=torch.float32, device=X.device)
     agg = torch.empty((n, C_in), dtype=torch.float32, device=X.device) if keep else None
     gated = keep and activation != "none"
     gate = torch.empty((n, 2 * _gate_words(C_out)), dtype=torch.int32, device=X.device) if gated else None
     rnorm = torch.empty(n, dtype=torch.float32, device=X.device) if keep and normalize else None
     rows_launch = _ngcf_wide_fusable(wide, X, C_in, C_out)
-    if rows_launch and not nat.has_symbol("gnx_step_wide_ngcf"):
-        raise Exception("ngcf_step: wide=\"fused\" needs gnx_step_wide_ngcf, which this libgnx.so does not export: rebuild the library")
     if rows_launch:
+        _ngcf_need_symbol("wide", "gnx_step_wide_ngcf")
         floats = 0 if keep else (n * C_in + 3) // 4 * 4
     else:
         floats = _ngcf_work_floats(n, C_in, C_out, g.n_hub_rows if one_launch else n, keep)
@@ -1788,10 +1806,7 @@ def _ngcf_back_gate(graph: DeviceGraph, g, y, rnorm, gate, activation, dropout=N
     nat.require_cuda(g, y, rnorm, gate)
     _same_device(graph, g, y, rnorm, gate)
     n, C = g.shape
-    if activation != "none" and (gate is None or gate.dtype != torch.int32 or tuple(gate.shape) != (n, 2 * _gate_words(C)) or not gate.is_contiguous()):
-        raise Exception("ngcf_step: the gate words must be a contiguous int32 [n, 2 ceil(C_out / 32)]")
-    if rnorm is not None and (y is None or tuple(y.shape) != (n, C) or rnorm.numel() != n or not rnorm.is_contiguous()):
-        raise Exception("ngcf_step: the reciprocal norms go with the forward's output")
+    _ngcf_check_saved(n, C, activation, gate, y, rnorm)
     y = None if rnorm is None else _as_f32_rows(y)
     G1, G2 = _padded_rows(n, C, g.device), _padded_rows(n, C, g.device)
     p, seed, stream = _dropout_args(dropout)
@@ -1811,9 +1826,7 @@ def _ngcf_back_work_floats(n, C_out):
 
 def _ngcf_back_fusable(X, A, W1):
     """Where gnx_step_back_ngcf has a launch: C_in in {16, 32, 64}, C_out <= C_in, 16-byte aligned rows of X and A."""
-    C_in, C_out = W1.shape
-    return (C_in in NGCF_FUSED_WIDTHS and C_out <= C_in and X.stride(0) % 4 == 0 and X.data_ptr() % 16 == 0 and A.is_contiguous()
-            and A.data_ptr() % 16 == 0)
+    return _ngcf_rows_fit(NGCF_FUSED_WIDTHS, *W1.shape, X, A)
 
 
 def _ngcf_back_launch(adj: Adjacency, g, y, rnorm, gate, activation, dropout, X, A, W1, W2, want_P=True, want_db=(True, True), want_dX=True,
@@ -1831,10 +1844,7 @@ def _ngcf_back_launch(adj: Adjacency, g, y, rnorm, gate, activation, dropout, X,
     if (graph.n_rows != graph.n_cols or n != graph.n_rows or tuple(X.shape) != (n, C_in) or tuple(A.shape) != (n, C_in) or not A.is_contiguous()
             or tuple(W1.shape) != (C_in, C_out) or tuple(W2.shape) != (C_in, C_out)):
         raise Exception("ngcf_step: shape mismatch in the backward")
-    if activation != "none" and (gate is None or gate.dtype != torch.int32 or tuple(gate.shape) != (n, 2 * _gate_words(C_out)) or not gate.is_contiguous()):
-        raise Exception("ngcf_step: the gate words must be a contiguous int32 [n, 2 ceil(C_out / 32)]")
-    if rnorm is not None and (y is None or tuple(y.shape) != (n, C_out) or rnorm.numel() != n or not rnorm.is_contiguous()):
-        raise Exception("ngcf_step: the reciprocal norms go with the forward's output")
+    _ngcf_check_saved(n, C_out, activation, gate, y, rnorm)
     y = None if rnorm is None else _as_f32_rows(y)
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=g.device)
     G1, G2 = _padded_rows(n, C_out, g.device), _padded_rows(n, C_out, g.device)
@@ -1861,16 +1871,13 @@ def _ngcf_wide_back_work_floats(n, C_out):
 
 def _ngcf_wide_back_fusable(wide_backward, X, A, W1):
     """Where ``wide_backward="fused"`` has a launch (gnx_step_back_wide_ngcf): C_in = 128, C_out <= C_in, 16-byte aligned rows of X and A."""
-    C_in, C_out = W1.shape
-    return (wide_backward == "fused" and C_in in NGCF_WIDE_WIDTHS and C_out <= C_in and X.stride(0) % 4 == 0 and X.data_ptr() % 16 == 0
-            and A.is_contiguous() and A.data_ptr() % 16 == 0)
+    return wide_backward == "fused" and _ngcf_rows_fit(NGCF_WIDE_WIDTHS, *W1.shape, X, A)
 
 
 def _ngcf_wide_back_launch(adj: Adjacency, g, y, rnorm, gate, activation, dropout, X, A, W1, W2, want_P=True, want_db=(True, True), want_dX=True):
     """gnx_step_back_wide_ngcf, one call: what _ngcf_back_launch returns, from the gate pass, one row-local launch and the transposed SpMM
     at C_in = 128.  A library without the entry raises: nothing falls back."""
-    if not nat.has_symbol("gnx_step_back_wide_ngcf"):
-        raise Exception("ngcf_step: wide_backward=\"fused\" needs gnx_step_back_wide_ngcf, which this libgnx.so does not export: rebuild the library")
+    _ngcf_need_symbol("wide_backward", "gnx_step_back_wide_ngcf")
     return _ngcf_back_launch(adj, g, y, rnorm, gate, activation, dropout, X, A, W1, W2, want_P=want_P, want_db=want_db, want_dX=want_dX,
                              entry="gnx_step_back_wide_ngcf", work_floats=_ngcf_wide_back_work_floats)
 

@@ -54,6 +54,30 @@ def test_checks_that_need_no_device():
         assert rc < 0 and message.startswith("gnx_step_back_ngcf: ") and cause in message, (cause, rc, message)
 
 
+SHARED_FAULTS = (("d_g", None, "NULL g / G1 / G2 or a row stride below C_out"), ("ldg", 1, "NULL g / G1 / G2 or a row stride below C_out"),
+                 ("d_y", None, "d_rnorm needs y"), ("d_gate", None, "relu / leaky_relu need d_gate"), ("d_X", None, "NULL X / agg, or ldx"),
+                 ("ldx", 1, "NULL X / agg, or ldx 1 < C_in"), ("d_dA", None, "dX needs W1, W2, d_dA and d_R"), ("ldw1", 1, "ldw1 1 or ldw2"),
+                 ("lddx", 1, "lddx 1 < C_in"), ("work_floats", -1, "work_floats -1 without d_work, or negative"),
+                 ("d_work", None, "work_floats 5 without d_work, or negative"))
+
+
+def test_both_backward_entries_answer_the_shared_argument_faults_alike():
+    """One table of the argument faults that the two entries of this parameter list check with one piece of code, against
+    gnx_step_back_ngcf at 16 -> 16 and gnx_step_back_wide_ngcf at 128 -> 128: each is refused, under the entry's own name and with the same
+    cause, before the handle (the one below is not one) or any buffer is looked at."""
+    from gnntf import _native
+    lib = _native.lib()
+    names = [arg.rsplit(" ", 1)[1].lstrip("*") for arg in PROTOTYPE]
+    for entry, C in (("gnx_step_back_ngcf", 16), ("gnx_step_back_wide_ngcf", 128)):
+        good = {name: ctypes.c_void_p(256 * (k + 1)) if "*" in arg else C for k, (name, arg) in enumerate(zip(names, PROTOTYPE))}
+        good.update(g=ctypes.c_void_p(16), act=1, dropout_p=0.0, seed=1, stream_id=2, work_floats=5, stream=None)
+        for name, value, cause in SHARED_FAULTS:
+            assert name in good
+            rc = getattr(lib, entry)(*[value if n == name else good[n] for n in names])
+            message = lib.gnx_last_error().decode()
+            assert rc < 0 and message.startswith(entry + ": ") and cause in message, (entry, name, rc, message)
+
+
 def test_keywords_are_validated():
     import gnntf
     from gnntf import sparse

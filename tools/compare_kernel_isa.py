@@ -2,7 +2,7 @@
 """Did a refactor of csrc/ leave the generated kernels alone?  Compares the device assembly of two builds kernel by kernel (no GPU).
 
     for f in gnx_graph gnx_prep gnx_spmm gnx_spmm_bf16 gnx_spmm_train gnx_spmm_train_ord gnx_spmm_train_bf16 gnx_gcnii gnx_gcn gnx_ngcf \
-             gnx_feature_dropout gnx_util gnx_dense gnx_dense_wgrad gnx_heads gnx_link gnx_rank gnx_halo; do
+             gnx_ngcf_wide gnx_ngcf_wide_back gnx_feature_dropout gnx_util gnx_dense gnx_dense_wgrad gnx_heads gnx_link gnx_rank gnx_halo; do
                                                        # every unit of the Makefile's SRCS (gnx_graph's kernels include rocprim's)
         hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 --cuda-device-only -S gnn-tf_amd/csrc/$f.hip -o $DIR/$f.s
     done                                               # once in a checkout of the old commit, once in the new one
