@@ -3,10 +3,11 @@
 //   k_spmm_gcn         the GCN layer in one launch: the gather without the residual operand, a rectangular W [C_in, C_out <= C_in]
 //   k_spmm_gcn_back    the GCN layer's input gradient past the gate, one launch over the transposed structure: the gated gradient
 //                      gathered at the OUTPUT width, stored at the input width (two geometries of the one tile)
-//   gcn_forward        gnx_gcn_step, gnx_gcn_step_dropped
+//   gcn_forward        gnx_gcn_step, gnx_gcn_step_dropped, and with the SPEC form of the kernel (GCNSpectralPreservingLayer, gcn.py:92-105)
+//                      gnx_step_spectral_gcn, gnx_step_spectral_gcn_dropped
 //   gcn_backward       gnx_gcn_step_back, gnx_gcn_step_back_dropped; the composed order of the other widths / strides is its branch
 // The mask of the rows that go through memory is launch_feature_dropout of gnx_feature_dropout.hip.
-#include "gnx_layer_device.h"
+#include "gnx_spectral_device.h"
 
 namespace {
 
@@ -20,9 +21,22 @@ namespace {
 // transform never reads them back.  A lane stores its columns below C_out: a whole float4 where `vec_out` says the row starts of out allow
 // it (ldo % 4 == 0 and a 16-byte aligned base) and the four columns exist, scalars otherwise -- nothing is written past column C_out - 1 of
 // any row.  DROP (`feat`, keyed by row and column; agg stays undropped) and EDGE / ENTRIES as in k_spmm_gcnii.  f32 rows only.
-template <typename R, int NTI, int NTO, int U, int WPB, bool DROP = false, bool EDGE = false, bool ENTRIES = false>
+// SPEC (gnx_step_spectral_gcn, gcn.py:92-105): the store loop forms 2 drop(act(P') - bias), P' the value the bias joined in the MFMA
+// block's epilogue, through spectral_finish (a null bias: zeros), and with sp.gate the launch writes one bit per element, P' > 0, in the
+// words of k_spmm_gcnii's SPEC form at the OUTPUT width: [n, ceil(C_out / 32)].  The lanes of a gate word -- those without a column
+// below C_out included, which is why this form has no early return -- OR their bits together through xor-shuffles; a column at or
+// beyond C_out contributes a 0 bit by selection (the zero-filled columns of W in LDS are not relied upon, and the tile's columns from
+// 16 NTO on still hold gathered values), stores nothing, and the word's lowest lane stores the word if the word exists.  A template
+// argument alone: the instantiations without it are the kernel as it was.
+template <bool SPEC> struct GateArgs {};
+template <> struct GateArgs<true> {
+    uint32_t *gate;        // [n, ceil(C_out / 32)] or null: bit c & 31 of word row * ceil(C_out / 32) + (c >> 5) = (P'[row, c] > 0)
+};
+
+template <typename R, int NTI, int NTO, int U, int WPB, bool DROP = false, bool EDGE = false, bool ENTRIES = false, bool SPEC = false>
 __global__ __launch_bounds__(64 * WPB) void k_spmm_gcn(const typename R::Args p, const float *__restrict__ W, int64_t ldw, int C_out,
-                                                       const float *__restrict__ bias, float *__restrict__ agg, bool vec_out, const DropFuse feat) {
+                                                       const float *__restrict__ bias, float *__restrict__ agg, bool vec_out, const DropFuse feat,
+                                                       const GateArgs<SPEC> sp = GateArgs<SPEC>{}) {
     static_assert(!R::BF16, "the GCN layer exists over f32 rows");
     static_assert(NTO >= 1 && NTO <= NTI, "C_out <= C_in: the result tile overwrites the gathered one");
     using TL = Tile<NTI>;
@@ -63,6 +77,38 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcn(const typename R::Args p,
     }
     __builtin_amdgcn_wave_barrier();
     tile_times_Ms<NTI, true, NTO>(T, Ws, lane, p.act, bias, bias ? C_out : 0);
+    if constexpr (SPEC) {
+        constexpr int GW = G < 8 ? G : 8;      // lanes per gate word
+        const int words = (C_out + 31) >> 5;
+        const int left = C_out - c;            // the lane's columns below C_out: all four, the first `left`, or none
+        const uint32_t valid = left >= 4 ? 0xfu : left > 0 ? (1u << left) - 1u : 0u;
+        float b[4];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) b[v] = bias != nullptr && v < left ? bias[c + v] : 0.f;
+        uint64_t stream = 0;
+        if constexpr (DROP) stream = drop_stream(feat);
+        const bool whole = vec_out && left >= 4;
+#pragma unroll
+        for (int ps = 0; ps < PASSES; ++ps) {
+            const int rr = ps * RPP + lane / G;
+            float o[4];
+            vload<4>(o, T + rr * STRIDE + c);
+            // (every lane of the wave takes part in the shuffles; a row's lanes are live or not together, and a dead row stores nothing)
+            uint32_t word = (spectral_finish<4, DROP>(feat, stream, rows[ps], c, b, o) & valid) << (c & 31);
+#pragma unroll
+            for (int m = 1; m < GW; m <<= 1) word |= (uint32_t)__shfl_xor((int)word, m);
+            if (!live[ps] || left <= 0) continue;
+            float *__restrict__ dst = p.out + rows[ps] * p.ldo + c;
+            if (whole) vstore<4>(dst, o);
+            else {
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+                    if (v < left) dst[v] = o[v];
+            }
+            if (sp.gate != nullptr && sub % GW == 0) sp.gate[rows[ps] * words + (c >> 5)] = word;
+        }
+        return;
+    }
     if (c >= C_out) return;
     const bool whole = vec_out && c + 4 <= C_out;
 #pragma unroll
@@ -165,13 +211,23 @@ __global__ __launch_bounds__(64 * WPB) void k_spmm_gcn_back(const typename R::Ar
 #define GNX_GCN_NAMES(c) {GNX_TILE_NAMES("k_spmm_gcn", c, ""), GNX_TILE_NAMES("k_spmm_gcn", c, "_edrop"), GNX_TILE_NAMES("k_spmm_gcn", c, "_drop"), GNX_TILE_NAMES("k_spmm_gcn", c, "_edrop_drop")}
 const char *const kGcnFused[3][4][2] = {GNX_GCN_NAMES("16"), GNX_GCN_NAMES("32"), GNX_GCN_NAMES("64")};
 const char *const kGcnComposed[4] = {"spmm+dense_mfma_gcn", "spmm+dense_mfma_gcn_edrop", "spmm+dense_mfma_gcn_drop", "spmm+dense_mfma_gcn_edrop_drop"};
+// the spectral form (gnx_step_spectral_gcn), likewise
+#define GNX_GCN_SPEC_NAMES(c) {GNX_TILE_NAMES("k_spmm_gcn_spectral", c, ""), GNX_TILE_NAMES("k_spmm_gcn_spectral", c, "_edrop"), GNX_TILE_NAMES("k_spmm_gcn_spectral", c, "_drop"), GNX_TILE_NAMES("k_spmm_gcn_spectral", c, "_edrop_drop")}
+const char *const kGcnSpecFused[3][4][2] = {GNX_GCN_SPEC_NAMES("16"), GNX_GCN_SPEC_NAMES("32"), GNX_GCN_SPEC_NAMES("64")};
+const char *const kGcnSpecComposed[4] = {"spmm+dense_mfma_gcn_spectral", "spmm+dense_mfma_gcn_spectral_edrop", "spmm+dense_mfma_gcn_spectral_drop",
+                                         "spmm+dense_mfma_gcn_spectral_edrop_drop"};
+#undef GNX_GCN_SPEC_NAMES
 #undef GNX_GCN_NAMES
 
-struct GcnOut { float *out; int64_t ldo; float *agg, *work; };      // the result, and where aggregated rows are kept / may pass through memory
+// the result, and where aggregated rows are kept / may pass through memory; `spectral`: out = 2 drop(act(P') - bias) and the gate words
+// [n, ceil(C_out / 32)] of P' > 0 at `gate` (null: not kept)
+struct GcnOut { float *out; int64_t ldo; float *agg, *work; bool spectral = false; uint32_t *gate = nullptr; };
 
 // out = drop(act((A . X) . W + bias)), A from d_vals or made from `edge`; `fd` the mask of the finished rows or null.  The fused launch
 // takes C_in = 16, 32 or 64 with C_out <= C_in over 16-byte aligned rows; everything else runs the SpMM, the dense kernel and the mask
-// pass inside this call, as gcnii_forward treats its other widths.  Nothing is launched before the last check has passed.
+// pass inside this call, as gcnii_forward treats its other widths.  o.spectral (gnx_step_spectral_gcn): the SPEC form of the launch, and
+// for the rows that go through memory the dense kernel with the bias, then k_spectral_tail (- bias, the mask, x 2, the gate words) in
+// the mask pass's place.  Nothing is launched before the last check has passed.
 int gcn_forward(const char *fn, gnx_graph *g, const float *d_vals, const EdgeDrop *edge, const float *d_X, int64_t ldx, int64_t C_in,
                 const float *d_W, int64_t ldw, int64_t C_out, const float *d_bias, int act, const DropFuse *fd, const GcnOut &o, void *stream) {
     GNX_CHECK_ARG(g != nullptr, "%s: NULL handle", fn);
@@ -188,6 +244,8 @@ int gcn_forward(const char *fn, gnx_graph *g, const float *d_vals, const EdgeDro
     GNX_CHECK_ARG(!input(o.out), "%s: out must not alias an input (X / W / bias / the values)", fn);
     GNX_CHECK_ARG(o.agg == nullptr || (!input(o.agg) && o.agg != o.out), "%s: d_agg must be a buffer of its own", fn);
     GNX_CHECK_ARG(o.work == nullptr || (!input(o.work) && o.work != o.out && o.work != o.agg), "%s: d_work must be a buffer of its own", fn);
+    const void *gate = o.gate;
+    GNX_CHECK_ARG(gate == nullptr || (!input(gate) && gate != o.out && gate != o.agg && gate != o.work), "%s: d_gate must be a buffer of its own", fn);
     if (edge) {
         const int rc = admit_edge_drop(fn, g, *edge);
         if (rc != GNX_OK) return rc;
@@ -205,7 +263,8 @@ int gcn_forward(const char *fn, gnx_graph *g, const float *d_vals, const EdgeDro
     auto transform_rows = [&](const int32_t *rows, int64_t n) -> int {
         const int err = dense_rows(T, C_in, n, C_in, d_W, ldw, C_out, d_bias, act, rows, rows, o.out, o.ldo, s);
         if (err != GNX_OK) return err;
-        if (fd) launch_feature_dropout(o.out, o.ldo, rows, n, C_out, *fd, o.out, o.ldo, s);
+        if (o.spectral) launch_spectral_tail(o.out, o.ldo, rows, n, C_out, d_bias, fd, o.gate, s);
+        else if (fd) launch_feature_dropout(o.out, o.ldo, rows, n, C_out, *fd, o.out, o.ldo, s);
         GNX_HIP(hipGetLastError());
         return GNX_OK;
     };
@@ -214,7 +273,7 @@ int gcn_forward(const char *fn, gnx_graph *g, const float *d_vals, const EdgeDro
                                                C_in, stream)
                             : gnx_spmm(g, d_vals, nullptr, d_X, ldx, C_in, nullptr, 0, 1.f, 0.f, GNX_ACT_NONE, T, C_in, stream);
         if (rc != GNX_OK) return rc;
-        g->last_kernel = kGcnComposed[mode];
+        g->last_kernel = (o.spectral ? kGcnSpecComposed : kGcnComposed)[mode];
         return transform_rows(nullptr, m.n_rows);
     }
     if (m.n_rows == 0) return GNX_OK;
@@ -228,14 +287,17 @@ int gcn_forward(const char *fn, gnx_graph *g, const float *d_vals, const EdgeDro
     const DropFuse feat = fd ? *fd : DropFuse{};
     with_tile_width(C_in, m.n_rows, [&](auto NTI, dim3 grid) {
         with_out_tiles((int)blocks_for(C_out, 16), [&](auto NTO) {      // (C_out <= C_in: no NTO above NTI; ENTRIES goes with EDGE)
-            with_flags([&](auto DROP, auto EDGE, auto ENTRIES) {
-                if constexpr (NTO() <= NTI() && (EDGE() || !ENTRIES()))
-                    hipLaunchKernelGGL((k_spmm_gcn<F32Rows, NTI(), NTO(), 4, 8, DROP(), EDGE(), ENTRIES()>), grid, dim3(512), 0, s, p, d_W, ldw,
-                                       (int)C_out, d_bias, o.agg, vec_out, feat);
-            }, fd != nullptr, edge != nullptr, edge && p.fuse.mult);
+            with_flags([&](auto DROP, auto EDGE, auto ENTRIES, auto SPEC) {
+                if constexpr (NTO() <= NTI() && (EDGE() || !ENTRIES())) {
+                    GateArgs<SPEC()> sp{};
+                    if constexpr (SPEC()) sp.gate = o.gate;
+                    hipLaunchKernelGGL((k_spmm_gcn<F32Rows, NTI(), NTO(), 4, 8, DROP(), EDGE(), ENTRIES(), SPEC()>), grid, dim3(512), 0, s, p, d_W,
+                                       ldw, (int)C_out, d_bias, o.agg, vec_out, feat, sp);
+                }
+            }, fd != nullptr, edge != nullptr, edge && p.fuse.mult, o.spectral);
         });
     });
-    g->last_kernel = kGcnFused[C_in == 16 ? 0 : C_in == 32 ? 1 : 2][mode][m.n_long > 0];
+    g->last_kernel = (o.spectral ? kGcnSpecFused : kGcnFused)[C_in == 16 ? 0 : C_in == 32 ? 1 : 2][mode][m.n_long > 0];
     // hub rows: chunked partial sums -> aggregated rows at their row ids of T -> the transform and the mask of those rows alone
     p.act = GNX_ACT_NONE;
     p.ldo = C_in;
@@ -344,6 +406,35 @@ int gnx_gcn_step_dropped(gnx_graph_t g, const float *d_D, float edge_p, uint64_t
     const EdgeDrop edge{d_D, edge_p, edge_seed, edge_stream};
     return gcn_forward(fn, g, nullptr, &edge, d_X, ldx, C_in, d_W, ldw, C_out, d_bias, act, dropout_p != 0.0 ? &fd : nullptr,
                        GcnOut{d_out, ldo, d_agg, d_work}, stream);
+}
+
+// (the gate words are the relu's: with the identity there is nothing to gate and d_gate is not looked at)
+int gnx_step_spectral_gcn(gnx_graph_t g, const float *d_vals, const float *d_X, int64_t ldx, int64_t C_in, const float *d_W, int64_t ldw,
+                          int64_t C_out, const float *d_bias, int act, double dropout_p, uint64_t seed, uint64_t stream_id, float *d_out, int64_t ldo,
+                          float *d_agg, uint32_t *d_gate, float *d_work, void *stream) {
+    const char *fn = "gnx_step_spectral_gcn";
+    DropFuse fd{};
+    const int rc = make_feat_drop(fn, g, dropout_p, seed, stream_id, fd);
+    if (rc != GNX_OK) return rc;
+    GNX_CHECK_ARG(act != GNX_ACT_RELU || d_agg == nullptr || d_gate != nullptr,
+                  "%s: relu with d_agg (training) needs d_gate [n, ceil(C_out / 32)] (the backward's gate)", fn);
+    return gcn_forward(fn, g, d_vals, nullptr, d_X, ldx, C_in, d_W, ldw, C_out, d_bias, act, dropout_p != 0.0 ? &fd : nullptr,
+                       GcnOut{d_out, ldo, d_agg, d_work, true, act == GNX_ACT_RELU ? d_gate : nullptr}, stream);
+}
+
+int gnx_step_spectral_gcn_dropped(gnx_graph_t g, const float *d_D, float edge_p, uint64_t edge_seed, uint64_t edge_stream, const float *d_X,
+                                  int64_t ldx, int64_t C_in, const float *d_W, int64_t ldw, int64_t C_out, const float *d_bias, int act,
+                                  double dropout_p, uint64_t seed, uint64_t stream_id, float *d_out, int64_t ldo, float *d_agg, uint32_t *d_gate,
+                                  float *d_work, void *stream) {
+    const char *fn = "gnx_step_spectral_gcn_dropped";
+    DropFuse fd{};
+    const int rc = make_feat_drop(fn, g, dropout_p, seed, stream_id, fd);
+    if (rc != GNX_OK) return rc;
+    GNX_CHECK_ARG(act != GNX_ACT_RELU || d_agg == nullptr || d_gate != nullptr,
+                  "%s: relu with d_agg (training) needs d_gate [n, ceil(C_out / 32)] (the backward's gate)", fn);
+    const EdgeDrop edge{d_D, edge_p, edge_seed, edge_stream};
+    return gcn_forward(fn, g, nullptr, &edge, d_X, ldx, C_in, d_W, ldw, C_out, d_bias, act, dropout_p != 0.0 ? &fd : nullptr,
+                       GcnOut{d_out, ldo, d_agg, d_work, true, act == GNX_ACT_RELU ? d_gate : nullptr}, stream);
 }
 
 int gnx_gcn_step_back(gnx_graph_t g, const float *d_vals_t, const float *d_G, int64_t ldg, int64_t C_out, const float *d_Wt, int64_t ldwt,

@@ -13,8 +13,9 @@
 //                      format of the result, and whether the widths other than 16 / 32 / 64 run as two launches or are refused
 //   gcnii_backward<R>  gnx_gcnii_step_back, _step_back_dropped, _step_back_bf16; the composed form of the other widths is its f32 branch
 //   gcnii_wgrad<R>     gnx_gcnii_wgrad, gnx_gcnii_wgrad_bf16
-// (gnx_gcnii_spectral_back is an entry of its own: one launch and the slab sum.)
-#include "gnx_layer_device.h"
+// (gnx_gcnii_spectral_back is an entry of its own: one launch and the slab sum.  spectral_finish stands in gnx_spectral_device.h and
+// k_spectral_tail is launched through gnx::launch_spectral_tail, for the spectral GCN layer of gnx_gcn.hip too.)
+#include "gnx_spectral_device.h"
 
 namespace {
 
@@ -25,25 +26,6 @@ template <> struct SpectralArgs<true> {
     const float *bias;     // [C]
     uint32_t *gate;        // [n, ceil(C / 32)] or null: bit c & 31 of word row * ceil(C / 32) + (c >> 5) = (P'[row, c] > 0)
 };
-
-// x[v] = act(P') of columns c .. c + VEC - 1 of row `row`  ->  2 drop(x[v] - bias[v]): the ONE place the finished value is formed, for
-// the store loop of the fused launch and for the row pass behind the dense kernel (k_spectral_tail), so that a row has the same bits
-// whichever path made it.  Returns the gate bits of the VEC columns, bit v = (x[v] > 0): with the relu act(P') > 0 iff P' > 0, so the
-// gate is that of the pre-activation itself and never a guess from the finished value (relu(P') - bias rounds to -bias for a tiny P').
-template <int VEC, bool DROP>
-__device__ __forceinline__ uint32_t spectral_finish(const DropFuse &f, uint64_t stream, int64_t row, int64_t c, const float (&bias)[VEC],
-                                                    float (&x)[VEC]) {
-    uint32_t bits = 0;
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-        bits |= (x[v] > 0.f ? 1u : 0u) << v;
-        x[v] -= bias[v];
-    }
-    if constexpr (DROP) drop_values<VEC>(f, stream, row, c, x);
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) x[v] *= 2.f;
-    return bits;
-}
 
 // One mixed row of the fused layer, columns c .. c + 3 of row `row` (entries beg .. end) into acc (zeros on entry): the gather
 // (gathered_row) and the mix, written once -- the forward (k_spmm_gcnii) and the weight gradient that makes T again (k_gcnii_wgrad) run
@@ -394,7 +376,7 @@ void round_rows(const float *src, const int32_t *rows, int64_t n, int64_t C, uin
 // The spectral form's row pass behind the dense kernel (hub rows; every row of the other widths): out[r, :] holds act(P') and leaves as
 // 2 drop(act(P') - bias) in place, the row's gate words written beside it (gate may be null) -- spectral_finish, the store loop's own
 // code.  A thread per gate word: up to 32 columns of row rows[i] (null: row i), any width and row stride.
-template <bool DROP>
+template <bool DROP, bool BIAS = true>
 __global__ __launch_bounds__(256) void k_spectral_tail(float *out, int64_t ldo, const int32_t *__restrict__ rows, int64_t n, int64_t C,
                                                       const float *__restrict__ bias, const DropFuse fd, uint32_t *__restrict__ gate) {
     const int64_t words = (C + 31) / 32, total = n * words, stride = (int64_t)gridDim.x * blockDim.x;
@@ -407,20 +389,13 @@ __global__ __launch_bounds__(256) void k_spectral_tail(float *out, int64_t ldo, 
         uint32_t word = 0;
         for (int64_t c = c0; c < c1; ++c) {
             float x[1] = {o[c]};
-            const float b[1] = {bias[c]};
+            float b[1] = {0.f};
+            if constexpr (BIAS) b[0] = bias[c];
             word |= spectral_finish<1, DROP>(fd, stream, r, c, b, x) << (c - c0);
             o[c] = x[0];
         }
         if (gate != nullptr) gate[r * words + w] = word;
     }
-}
-
-void launch_spectral_tail(float *out, int64_t ldo, const int32_t *rows, int64_t n, int64_t C, const float *bias, const DropFuse *fd,
-                          uint32_t *gate, hipStream_t s) {
-    if (n == 0 || C == 0) return;
-    const unsigned grid = (unsigned)std::min<int64_t>(blocks_for(n * ((C + 31) / 32), 256), 1 << 20);
-    if (fd) GNX_LAUNCH(k_spectral_tail<true>, grid, out, ldo, rows, n, C, bias, *fd, gate);
-    else    GNX_LAUNCH(k_spectral_tail<false>, grid, out, ldo, rows, n, C, bias, DropFuse{}, gate);
 }
 
 // The first pass of the spectral form's backward (gnx_gcnii_spectral_back): u = 2 drop(g) with the forward's mask, G' = gate ? u : 0
@@ -693,6 +668,20 @@ int gcnii_wgrad(const char *fn, const char *reports, gnx_graph *g, const float *
 }
 
 }  // namespace
+
+// (declared in gnx_internal.h: gnx_gcn.hip launches the pass for its spectral form; a null bias is a bias of zeros)
+void gnx::launch_spectral_tail(float *out, int64_t ldo, const int32_t *rows, int64_t n, int64_t C, const float *bias, const DropFuse *fd,
+                               uint32_t *gate, hipStream_t s) {
+    if (n == 0 || C == 0) return;
+    const unsigned grid = (unsigned)std::min<int64_t>(blocks_for(n * ((C + 31) / 32), 256), 1 << 20);
+    if (bias == nullptr) {
+        if (fd) GNX_LAUNCH((k_spectral_tail<true, false>), grid, out, ldo, rows, n, C, bias, *fd, gate);
+        else    GNX_LAUNCH((k_spectral_tail<false, false>), grid, out, ldo, rows, n, C, bias, DropFuse{}, gate);
+    } else {
+        if (fd) GNX_LAUNCH(k_spectral_tail<true>, grid, out, ldo, rows, n, C, bias, *fd, gate);
+        else    GNX_LAUNCH(k_spectral_tail<false>, grid, out, ldo, rows, n, C, bias, DropFuse{}, gate);
+    }
+}
 
 extern "C" {
 

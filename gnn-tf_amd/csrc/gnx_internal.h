@@ -456,6 +456,11 @@ void sum_slabs(const float *partial, int64_t n_slabs, int64_t elems, float *out,
 // fused layers' rows that go through memory; out may be X
 void launch_feature_dropout(const float *X, int64_t ldx, const int32_t *rows, int64_t n, int64_t C, const DropFuse &fd, float *out, int64_t ldo,
                             hipStream_t s);
+// out[r, :] holds act(P') of the rows listed (null: rows 0 .. n) and leaves as 2 drop(act(P') - bias) in place, the rows' gate words
+// [., ceil(C / 32)] written beside it (gnx_gcnii.hip, k_spectral_tail: the spectral layers' rows that go through memory); bias null:
+// zeros, fd null: no mask, gate null: no words
+void launch_spectral_tail(float *out, int64_t ldo, const int32_t *rows, int64_t n, int64_t C, const float *bias, const DropFuse *fd,
+                          uint32_t *gate, hipStream_t s);
 #ifdef GNX_TUNING
 extern int tune_override;
 #endif

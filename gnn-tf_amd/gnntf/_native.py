@@ -139,6 +139,11 @@ SIGNATURES = {
                                   c_int64, c_void_p]),
     "gnx_gcn_step_back_dropped": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_void_p, c_int64, c_int64, c_void_p, c_int64,
                                           c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "gnx_step_spectral_gcn": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_double,
+                                      c_uint64, c_uint64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gnx_step_spectral_gcn_dropped": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_void_p, c_int64, c_int64, c_void_p, c_int64,
+                                              c_int64, c_void_p, c_int, c_double, c_uint64, c_uint64, c_void_p, c_int64, c_void_p, c_void_p,
+                                              c_void_p, c_void_p]),
     "gnx_ngcf_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                               c_int, c_double, c_uint64, c_uint64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                               c_void_p]),
@@ -184,7 +189,7 @@ SIGNATURES = {
 }
 
 # entries added within ABI 0.9 that a library of the same minor version may lack: found by probing (has_symbol); their callers raise
-PROBED = ("gnx_step_wide_ngcf", "gnx_step_back_wide_ngcf")
+PROBED = ("gnx_step_wide_ngcf", "gnx_step_back_wide_ngcf", "gnx_step_spectral_gcn", "gnx_step_spectral_gcn_dropped")
 
 _lib = None
 

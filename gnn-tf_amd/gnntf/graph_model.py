@@ -53,7 +53,7 @@ class GNN(Trainable):
                  training_dtype=torch.float32, train_gather_order="auto", gcnii_backward="composed", feature_dropout="torch",
                  gcnii_training_dtype=torch.float32, gcnii_weight_gradient="stored", gcnii_spectral="composed",
                  gcnii_edge_dropout="composed", gcn_layer="composed", gcn_backward="composed", ngcf_layer="composed",
-                 ngcf_backward="composed", ngcf_wide="composed", ngcf_wide_backward="composed"):
+                 ngcf_backward="composed", ngcf_wide="composed", ngcf_wide_backward="composed", gcn_spectral="composed"):
         """``reorder`` (opt-in, not in the reference): store the graph and the feature rows with the vertices relabelled; every
         [N, .] tensor inside the model then lives in that order, and the model's OUTPUT is put back into the caller's order, so
         tasks, labels and node ids are unaffected.  Results agree with the unordered model to float32 rounding.
@@ -222,7 +222,27 @@ class GNN(Trainable):
         dA, Q1 * A and X * A written once) and the transposed SpMM with Q1 * A mixed in -- and gnx_dense_wgrad twice, instead of the
         column sums, a torch multiply, two transposed weight copies, gnx_dense twice and two addcmul passes.  The forward, dW1 and dW2
         keep their bits; dX and the bias gradients agree to float32 rounding (why the default stays ``"composed"``; measurement:
-        profiles/NOTES.md "NGCF backward at width 128").  A second backward over a retained graph works."""
+        profiles/NOTES.md "NGCF backward at width 128").  A second backward over a retained graph works.
+        ``gcn_spectral`` (not in the reference): ``"composed"`` (the default: today's calls and bits) or ``"fused"``
+        (sparse.gcn_step_spectral).  ``"fused"``: a GCNSpectralPreservingLayer (the class itself, no ``transform_first``, relu or the
+        identity as activation, float32 device rows of width 16, 32 or 64, at most as many outputs, no add_eye, not a bf16
+        ``inference_dtype`` forward) runs 2 * dropout(act((A . X) . W + b) - b) as ONE launch (gnx_step_spectral_gcn) instead of the
+        SpMM, the dense kernel and three elementwise passes, in eval mode and in training mode alike; in training mode over a
+        DroppedAdjacency the launch makes the weights itself (gnx_step_spectral_gcn_dropped).  In training mode with 0 < ``dropout`` < 1
+        the mask leaves the same launch and is the COUNTER RNG's, not torch's: element (i, c) of the layer's ``_next_mask_stream()``
+        stream -- drawn after the adjacency's, in today's order -- is kept iff hash_u24(seed, stream, i, c, 0) >= int(p * 2^24), kept
+        values times the f32 1 / (1 - p), as for ``gcnii_spectral="fused"``: the masks differ from torch's, which is why the switch is
+        opt-in; a training step is then reproducible from (seed, stream) alone and ``train(capture=True)`` equals the eager run bit
+        for bit.  For its backward the layer saves A . X and ONE BIT per element (the sign of the pre-activation) instead of A . X, the
+        activated rows, the subtraction's result and a byte mask, and starts it with one gate pass (gnx_gcnii_spectral_back) that also
+        makes the bias gradient; it honours ``gcn_backward``.  In ``GCN(latent_dims=[64], layer_type=GCNSpectralPreservingLayer)`` this
+        is the 64 -> num_classes layer (the first layer gathers at the feature width); in ``[64, 64, 64]`` every layer but the first.
+        The eval-mode result agrees with the composed one to float32 rounding.  GCNLayer and ``gcn_layer="fused"`` (which keeps
+        ignoring this class), other subclasses, ``transform_first``, other activations, other widths, a rate of 1 or more, add_eye, CPU
+        tensors and the vertex-partitioned path keep today's path and bits whatever it says (measurement: profiles/NOTES.md "Fused
+        spectral-preserving GCN layer")."""
+        if gcn_spectral not in sparse.GCN_SPECTRALS:
+            raise Exception("GNN: gcn_spectral must be one of " + ", ".join(repr(f) for f in sparse.GCN_SPECTRALS))
         if ngcf_layer not in sparse.NGCF_LAYERS:
             raise Exception("GNN: ngcf_layer must be one of " + ", ".join(repr(f) for f in sparse.NGCF_LAYERS))
         if ngcf_backward not in sparse.NGCF_BACKWARDS:
@@ -269,6 +289,7 @@ class GNN(Trainable):
         self.ngcf_backward = ngcf_backward
         self.ngcf_wide = ngcf_wide
         self.ngcf_wide_backward = ngcf_wide_backward
+        self.gcn_spectral = gcn_spectral
         self._order = self._newid = None
         self.reorder_used, self.locality_share = None, None
         if isinstance(graph, sparse.DeviceGraph):
@@ -559,10 +580,27 @@ class GCNLayer(Layer):
 class GCNSpectralPreservingLayer(GCNLayer):
     """gcn.py:92-105: the GCN layer with its bias taken back out after the activation and the surviving half of the dropout
     doubled -- 2 * dropout(act((A.X).W + b) - b).  Same kernels as GCNLayer (the SpMM, then the matrix-core transform with the
-    bias and a relu fused); the correction is an elementwise tail."""
+    bias and a relu fused); the correction is an elementwise tail.
+    On a GNN with ``gcn_spectral="fused"`` the whole layer is ONE launch (gnx_step_spectral_gcn), in training mode with the counter RNG's
+    dropout mask instead of torch's, and its backward keeps A . X and one gate bit per element (GNN.__init__)."""
+
+    def _fused_spectral(self, gcn, features, adjacency) -> bool:
+        """Whether GNN(gcn_spectral="fused") applies to this forward (no tensor is read, no mask stream is drawn)."""
+        return (getattr(gcn, "gcn_spectral", "composed") == "fused" and type(self) is GCNSpectralPreservingLayer and not self.transform_first
+                and (self.activation is relu or self.activation is linear)
+                and isinstance(features, torch.Tensor) and features.is_cuda and features.dtype == torch.float32
+                and features.shape[1] in sparse.GCN_FUSED_WIDTHS and self.W.shape[1] <= features.shape[1]
+                and adjacency.diag is None and _eval_storage(gcn) is not torch.bfloat16
+                and (not gcn.is_training() or 0 <= self.dropout < 1))       # (a rate of 1 or more stays with torch and what it makes of it)
 
     def __forward__(self, gcn, features):
-        activated = affine(sparse.spmm(gcn.get_adjacency(self.graph_dropout), features), self.W, self.b, self.activation)
+        adjacency = gcn.get_adjacency(self.graph_dropout)
+        if self._fused_spectral(gcn, features, adjacency):
+            triple = (self.dropout,) + tuple(gcn._next_mask_stream()) if gcn.is_training() and self.dropout != 0 else None
+            return sparse.gcn_step_spectral(adjacency, features, self.W, self.b if isinstance(self.b, torch.Tensor) else None,
+                                            relu=self.activation is relu, dropout=triple, edge_dropout="fused",
+                                            backward=getattr(gcn, "gcn_backward", "composed"))
+        activated = affine(sparse.spmm(adjacency, features), self.W, self.b, self.activation)
         return 2 * gcn.dropout(activated - self.b, self.dropout)
 
 

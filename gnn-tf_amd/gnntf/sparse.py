@@ -1498,8 +1498,15 @@ GCN_BACKWARDS = ("composed", "fused")
 GCN_FUSED_WIDTHS = (16, 32, 64)       # C_in of the one-launch form of gnx_gcn_step; its C_out is any width up to C_in
 
 
-def _gcn_launch(adj: Adjacency, X, W, bias, relu, keep_agg, dropout=None, fused_edge=False):
+def _need_symbol(what, entry):
+    if not nat.has_symbol(entry):      # (a library without the entry raises: nothing falls back)
+        raise Exception(f"{what}: needs {entry}, which this libgnx.so does not export: rebuild the library")
+
+
+def _gcn_launch(adj: Adjacency, X, W, bias, relu, keep_agg, dropout=None, fused_edge=False, spectral=False):
     """gnx_gcn_step, or with ``fused_edge`` (``adj`` is a DroppedAdjacency) gnx_gcn_step_dropped; returns (out, agg or None).
+    ``spectral``: gnx_step_spectral_gcn / gnx_step_spectral_gcn_dropped -- out = 2 drop(act(P') - bias) -- and a third result, the gate
+    words (int32 [n, ceil(C_out / 32)]: one bit per element, P' > 0) with ``keep_agg`` and ``relu``, else None.
     ``keep_agg`` (training): the launch also writes the aggregated rows A . X, which dW needs.  Without it the rows that have to pass
     through memory -- hub rows, and every row of the widths the one launch does not take -- go through a scratch buffer.
     ``dropout`` = the checked (p, seed, stream) or None."""
@@ -1522,13 +1529,20 @@ def _gcn_launch(adj: Adjacency, X, W, bias, relu, keep_agg, dropout=None, fused_
     agg, work = (rows, None) if keep_agg else (None, rows)
     p, seed, stream = _dropout_args(dropout)
     layer = (nat.ptr(X), X.stride(0), C_in, nat.ptr(W), W.stride(0), C_out, nat.ptr(b), nat.ACT_RELU if relu else nat.ACT_NONE, p, seed, stream,
-             nat.ptr(out), out.stride(0), nat.ptr(agg), nat.ptr(work))
+             nat.ptr(out), out.stride(0), nat.ptr(agg))
+    if spectral:
+        _need_symbol("gcn_step_spectral", "gnx_step_spectral_gcn_dropped" if fused_edge else "gnx_step_spectral_gcn")
+        gate = torch.empty((n, _gate_words(C_out)), dtype=torch.int32, device=X.device) if keep_agg and relu else None
+        layer = layer + (nat.ptr(gate),)
+        plain, dropped = nat.lib().gnx_step_spectral_gcn, nat.lib().gnx_step_spectral_gcn_dropped
+    else:
+        plain, dropped = nat.lib().gnx_gcn_step, nat.lib().gnx_gcn_step_dropped
     with nat.on_device(X.device):
         if fused_edge:
-            nat.check(nat.lib().gnx_gcn_step_dropped(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, *layer, nat.current_stream()))
+            nat.check(dropped(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, *layer, nat.ptr(work), nat.current_stream()))
         else:
-            nat.check(nat.lib().gnx_gcn_step(g.handle, nat.ptr(adj.vals), *layer, nat.current_stream()))
-    return out, agg
+            nat.check(plain(g.handle, nat.ptr(adj.vals), *layer, nat.ptr(work), nat.current_stream()))
+    return (out, agg, gate) if spectral else (out, agg)
 
 
 class _GCNStep(torch.autograd.Function):
@@ -2033,16 +2047,17 @@ def _gcnii_spectral_launch(adj: Adjacency, H, H0, a, M, bias, relu, keep, dropou
     return out, mixed if keep else None, gate
 
 
-def _gcnii_spectral_gate(graph: DeviceGraph, g, gate, relu, dropout=None):
+def _gcnii_spectral_gate(graph: DeviceGraph, g, gate, relu, dropout=None, padded=False):
     """gnx_gcnii_spectral_back: (G', dbias) from the upstream gradient ``g``, the forward's gate words and its dropout triple:
-    u = 2 drop(g), G' = gate ? u : 0, dbias[c] = -sum_i (gate ? 0 : u[i, c]); without ``relu`` G' = u and dbias = 0."""
+    u = 2 drop(g), G' = gate ? u : 0, dbias[c] = -sum_i (gate ? 0 : u[i, c]); without ``relu`` G' = u and dbias = 0.
+    ``padded``: G' is written into rows of stride roundup4(C) (_padded_rows; the pass takes the stride as its ldG)."""
     g = _as_f32_rows(g).contiguous()
     nat.require_cuda(g, gate)
     _same_device(graph, g, gate)
     n, C = g.shape
     if relu and (gate is None or gate.dtype != torch.int32 or tuple(gate.shape) != (n, _gate_words(C)) or not gate.is_contiguous()):
         raise Exception("gcnii_step_spectral: the gate words must be a contiguous int32 [n, ceil(C / 32)]")
-    G = torch.empty_like(g)
+    G = _padded_rows(n, C, g.device) if padded else torch.empty_like(g)
     dbias = torch.empty(C, dtype=torch.float32, device=g.device)
     if C == 0:
         return G, dbias
@@ -2119,6 +2134,106 @@ def gcnii_step_spectral(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: fl
     if torch.is_grad_enabled() and (H.requires_grad or H0.requires_grad or M.requires_grad or bias.requires_grad):
         return _GCNIISpectralStep.apply(H, H0, M, bias, adj, float(a), bool(relu), backward, dropout)
     return _gcnii_spectral_launch(adj, H, H0, a, M, bias, bool(relu), keep=False, dropout=dropout)[0]
+
+
+GCN_SPECTRALS = ("composed", "fused")
+
+
+class _GCNSpectralStep(torch.autograd.Function):
+    """out = 2 drop(act((A . X) . W + bias) - bias) as ONE launch (gnx_step_spectral_gcn; under ``fused_edge`` gnx_step_spectral_gcn_dropped)
+    that leaves agg = A . X and one gate bit per element (P' > 0) for the backward: (agg, W, gate) is all that is saved -- neither
+    act(P') nor out nor a byte mask.  backward: the gate pass (gnx_gcnii_spectral_back at width C_out: u = 2 drop(g), G' = gate ? u : 0,
+    dbias = -sum of the gated-off u), dW = agg^T G' (gnx_dense_wgrad), then dX from G' as in _GCNStep: composed (gnx_dense + the
+    transposed SpMM) or ``backward="fused"`` -- the gate pass writes G' into rows of stride roundup4(C_out), dX = (A^T G') W^T is ONE launch
+    (gcn_step_back), and the node keeps agg itself (``ctx.agg``; (W, gate) are what is saved), lets it go once dW is made, before dX is
+    allocated, and therefore runs its backward once."""
+
+    @staticmethod
+    def forward(ctx, X, W, bias, adj, relu, dropout, fused_edge, backward):
+        ctx.adj, ctx.relu, ctx.dropout, ctx.fused_edge, ctx.fused_backward = adj, relu, dropout, fused_edge, backward == "fused"
+        ctx.bias_shape = None if bias is None else tuple(bias.shape)
+        out, agg, gate = _gcn_launch(adj, X, W, bias, relu, keep_agg=True, dropout=dropout, fused_edge=fused_edge, spectral=True)
+        if ctx.fused_backward:      # (agg is neither an input nor an output of the node: it may live on ctx, which can let it go early)
+            ctx.agg = agg
+            ctx.save_for_backward(W, gate)
+            return out
+        ctx.save_for_backward(agg, W, gate)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        want_X, want_W = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        want_b = ctx.bias_shape is not None and ctx.needs_input_grad[2]
+        if ctx.fused_backward:
+            W, gate = ctx.saved_tensors
+            agg, ctx.agg = ctx.agg, None
+            if agg is None:
+                raise Exception("gcn_step_spectral(backward=\"fused\"): the node let its aggregated rows go in its first backward; run the "
+                                "forward again (or use backward=\"composed\" where a graph is retained)")
+        else:
+            agg, W, gate = ctx.saved_tensors
+        G, gb = _gcnii_spectral_gate(ctx.adj.graph, g, gate, ctx.relu, ctx.dropout, padded=ctx.fused_backward and want_X)
+        gb = gb.reshape(ctx.bias_shape) if want_b else None
+        gW = _dense_wgrad(agg, G) if want_W else None
+        del agg                                                 # (under backward="fused" the last reference: the rows are free before dX is made)
+        gX = None
+        if want_X and ctx.fused_backward:
+            gX = _gcn_back_launch(ctx.adj, G, W.t().contiguous(), ctx.fused_edge)
+        elif want_X:
+            gT = _dense_launch(G, W.t().contiguous(), None, False)
+            del G                                               # (the gated gradient is done with: the transposed SpMM runs without it)
+            gX = _launch(ctx.adj, gT, None, 1.0, 0.0, nat.ACT_NONE, transposed=True)
+        return gX, gW, gb, None, None, None, None, None
+
+
+def _gcn_spectral_composed(adj, X, W, bias, relu, dropout):
+    """The layer as today's ops (_gcn_composed's shape): spmm, the dense kernel with bias and relu (CPU tensors: torch), then torch's
+    elementwise tail with TORCH's dropout."""
+    agg = spmm(adj, X)
+    b = bias if bias is not None else 0
+    if agg.is_cuda:
+        activated = dense(agg, W, bias, relu)
+    else:
+        activated = torch.matmul(agg, W) + b
+        activated = torch.relu(activated) if relu else activated
+    y = activated - b
+    p = 0.0 if dropout is None else float(dropout[0])
+    return 2 * (torch.nn.functional.dropout(y, p=p, training=True) if p != 0 else y)
+
+
+def gcn_step_spectral(adj: Adjacency, X: torch.Tensor, W: torch.Tensor, bias=None, relu=True, dropout=None, edge_dropout="composed",
+                      backward="composed") -> torch.Tensor:
+    """GCNSpectralPreservingLayer (gcn.py:92-105) as one launch (gnx_step_spectral_gcn; opt-in, GNN(gcn_spectral="fused")):
+    2 * drop(act((A . X) . W + bias) - bias) with ``X`` [n, C_in], ``W`` [C_in, C_out] and ``bias`` [C_out] / [1, C_out] or None (zeros).
+    For C_in in {16, 32, 64} and C_out <= C_in the aggregated rows stay in LDS and meet W on the matrix cores, the bias joins the
+    product there before the activation, and - bias, the mask and the doubling happen as the rows are stored; other widths run the
+    SpMM, the dense kernel and one row pass inside the same call.
+    ``dropout`` = ``(p, seed, stream)`` or None: the mask of ``feature_dropout`` -- the counter RNG of the edge dropout, NOT torch's
+    generator: element (i, c) is kept iff hash_u24(seed, stream + counter, i, c, 0) >= int(p * 2^24), kept values times the f32 1 / (1 - p).
+    Without autograd nothing but the result is written.  Under autograd it is one node that saves (A . X, W, gate) -- the aggregated rows
+    for dW, and ONE BIT per element (P' > 0) packed into int32 words [n, ceil(C_out / 32)] instead of the activated rows, the result
+    and a byte mask -- and returns the gradients of X, W and bias: one gate pass (gnx_gcnii_spectral_back: G' = gate ? 2 drop(g) : 0
+    and dbias, a fixed-order sum without atomics), gnx_dense_wgrad, then dX by ``backward`` exactly as in ``gcn_step``: ``"composed"``
+    (gnx_dense + the transposed SpMM) or ``"fused"`` (G' in rows of stride roundup4(C_out), ONE launch gcn_step_back, A . X let go once
+    dW is made: such a node runs its backward once).
+    ``edge_dropout="fused"`` with a DroppedAdjacency: gnx_step_spectral_gcn_dropped makes every entry's weight in its gather loop -- bit
+    for bit the result over ``normalize(graph, "symmetric", "none", p, seed, stream)`` -- and the backward's transposed SpMM is the
+    dropped one.
+    CPU tensors, an adjacency with a diagonal, a DroppedAdjacency without ``edge_dropout="fused"`` and a rate outside [0, 1) run
+    ``spmm`` + ``dense`` and torch's elementwise tail with TORCH's dropout: today's calls and bits."""
+    fused_edge = _edge_dropout("gcn_step_spectral", edge_dropout)
+    if backward not in GCN_BACKWARDS:
+        raise Exception("gcn_step_spectral: backward must be one of " + ", ".join(repr(b) for b in GCN_BACKWARDS))
+    tensors = (X, W) if bias is None else (X, W, bias)
+    rate = 0.0 if dropout is None else float(dropout[0])
+    if (not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors) or adj.diag is not None
+            or (isinstance(adj, DroppedAdjacency) and not fused_edge) or not 0.0 <= rate < 1.0):
+        return _gcn_spectral_composed(adj, X, W, bias, bool(relu), dropout)
+    dropout = _dropout_triple(dropout, "gcn_step_spectral")
+    fused_edge = fused_edge and isinstance(adj, DroppedAdjacency)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        return _GCNSpectralStep.apply(X, W, bias, adj, bool(relu), dropout, fused_edge, backward)
+    return _gcn_launch(adj, X, W, bias, bool(relu), keep_agg=False, dropout=dropout, fused_edge=fused_edge, spectral=True)[0]
 
 
 # the model-level bf16 path of GCNIILayer (graph_model.py) keeps f32 below this width.  tools/gcnii_bf16_bench.py is the measurement

@@ -74,7 +74,8 @@ const char *gnx_last_error(void);
  * backward as the gate, one row-local launch and the transposed SpMM (gnx_step_back_wide_ngcf), likewise, and the link
  * task on the device (gnx_sample_negatives, gnx_edge_plan_bytes, gnx_edge_plan, gnx_edge_sorted_work_floats,
  * gnx_edge_scores_backward_sorted), likewise, and the ranking evaluation of the link task (gnx_rank_candidates_bytes,
- * gnx_rank_candidates, GNX_RANK_MAX_K, GNX_RANK_POS_PASS, GNX_RANK_MAX_SPLITS), likewise. */
+ * gnx_rank_candidates, GNX_RANK_MAX_K, GNX_RANK_POS_PASS, GNX_RANK_MAX_SPLITS), likewise, and the spectral-preserving GCN layer in
+ * one launch (gnx_step_spectral_gcn, gnx_step_spectral_gcn_dropped), likewise. */
 #define GNX_ABI_VERSION 900
 int gnx_version(void);
 
@@ -736,6 +737,40 @@ int gnx_gcn_step_dropped(gnx_graph_t g, const float *d_D, float edge_p, uint64_t
                          int64_t ldx, int64_t C_in, const float *d_W, int64_t ldw, int64_t C_out, const float *d_bias, int act,
                          double dropout_p, uint64_t seed, uint64_t stream_id, float *d_out, int64_t ldo, float *d_agg,
                          float *d_work, void *stream);
+
+/* The spectral-preserving GCN layer (GCNSpectralPreservingLayer, gcn.py:92-105) as one launch (opt-in; added within ABI 0.9 -- probe
+ * for the symbols), f32 rows:
+ *   out = 2 * drop(act(P') - bias),   P' = (A . X) . W + bias
+ * gnx_step_spectral_gcn is the launch of gnx_gcn_step with another store loop, gnx_step_spectral_gcn_dropped that of
+ * gnx_gcn_step_dropped; the arguments, widths, strides, d_agg / d_work, the hub rows, the composed form of the other cases, the checks
+ * (before any launch: a refused call writes nothing), the aliasing, capture and reserve rules, the skip semantics and the admission
+ * under edge dropout are those entries', and d_agg is bit for bit theirs.  act is GNX_ACT_NONE or GNX_ACT_RELU.
+ * Rounding points: each aggregated value is one fmaf chain over the row's entries; P' = fl(sum + bias[c]), the f32 MFMA sum over k
+ * in ascending order with the bias added to the accumulator value as it leaves the matrix-core block, before the activation; then
+ * Y = fl(act(P') - bias[c]); then out = 2 * (kept ? fl(Y * s) : +0), the mask and its f32 scale s = 1 / (1 - dropout_p) those of
+ * gnx_gcn_step (dropout_p == 0 hashes nothing: out = 2 * Y).  d_bias NULL means a bias of zeros: out = 2 * drop(act(P')), and the
+ * gate is still written.  With d_bias of zeros and dropout_p == 0, out is exactly twice gnx_gcn_step's.
+ * d_gate (uint32_t [n, ceil(C_out / 32)] contiguous; written for GNX_ACT_RELU only, may be NULL in inference): one bit per element,
+ *   bit (c & 31) of word row * ceil(C_out / 32) + (c >> 5)  =  (P'[row, c] > 0),
+ * the format of gnx_gcnii_step_spectral at the OUTPUT width: the bits at or above C_out of a row's last word are 0, and no word at or
+ * above ceil(C_out / 32) exists or is written.  The gate is taken from the pre-activation itself and is all the backward needs of
+ * the forward (gnx_gcnii_spectral_back takes it at any width and row stride, then gnx_dense_wgrad and gnx_gcn_step_back).  Every
+ * word is written whole by ONE lane with a plain vector store, after the lanes of the word OR their bits together: no atomics.  The
+ * partial-piece store rules of gnx_gcn_step hold (C_out = 7 with ldo = 7 is fine): nothing is written past column C_out - 1.
+ * Hub rows take the long-row kernels, the dense kernel with the bias on those rows alone, and a row-list pass that applies - bias, the
+ * mask, x 2 and writes their gate words with the store loop's own code: a row has the same bits whichever path made it.  C_in
+ * outside {16, 32, 64}, C_out > C_in and misaligned rows run gnx_spmm (gnx_spmm_dropped), the dense kernel and that pass over all
+ * rows, through d_agg, else d_work.
+ * Beyond gnx_gcn_step's checks: d_gate non-NULL when act is GNX_ACT_RELU and d_agg is given (training); d_gate a buffer of its own.
+ * Reports "k_spmm_gcn_spectral<C_in>" (+ "_edrop" under edge dropout, + "_drop" with a mask, + "+long" when hub rows ran), the
+ * composed form "spmm+dense_mfma_gcn_spectral" with the same suffixes. */
+int gnx_step_spectral_gcn(gnx_graph_t g, const float *d_vals, const float *d_X, int64_t ldx, int64_t C_in, const float *d_W,
+                          int64_t ldw, int64_t C_out, const float *d_bias, int act, double dropout_p, uint64_t seed,
+                          uint64_t stream_id, float *d_out, int64_t ldo, float *d_agg, uint32_t *d_gate, float *d_work, void *stream);
+int gnx_step_spectral_gcn_dropped(gnx_graph_t g, const float *d_D, float edge_p, uint64_t edge_seed, uint64_t edge_stream,
+                                  const float *d_X, int64_t ldx, int64_t C_in, const float *d_W, int64_t ldw, int64_t C_out,
+                                  const float *d_bias, int act, double dropout_p, uint64_t seed, uint64_t stream_id, float *d_out,
+                                  int64_t ldo, float *d_agg, uint32_t *d_gate, float *d_work, void *stream);
 
 /* gnx_gcn_step_back (training, opt-in; added within ABI 0.9 -- probe for the symbols): the gradient of X of gnx_gcn_step past the gate,
  *   dX[r, 0 .. C_in) = (sum_c A_hat[c][r] G'[c, 0 .. C_out)) . Wt,
