@@ -2,6 +2,9 @@
 //
 //   gnx_dense      out = act(X . W + b)                      reference gnntf/core/nn/layers.py:135-136 (Dense),
 //                                                            gnntf/core/gnn/architectures/gcn.py:89 (the transform of GCNLayer)
+//   gnx_dense_drop out = drop_out(act(drop_in(X) . W + b))   a Dropout layer, the Dense behind it and the Dense's own dropout
+//                                                            (layers.py:125-136, 175-181) in the same launch: the DROP form of the
+//                                                            three kernels below, the masks of drop_values (gnx_layer_device.h)
 //
 // gnx_dense is a tall-and-skinny GEMM (N rows in the millions, F and O in the tens to hundreds): float32 in, float32
 // accumulate on v_mfma_f32_16x16x4_f32 (bit-for-bit a k-ordered fmaf chain, no reduced precision).  A 256-thread block owns
@@ -18,6 +21,7 @@
 #include <mutex>
 
 #include "gnx_dense_device.h"
+#include "gnx_layer_device.h"
 
 namespace {
 
@@ -33,6 +37,23 @@ struct DenseArgs {
     const float *zeros = nullptr; // 16 bytes of device zeros (k_dense_wreg with padded widths stages them for the columns past F)
 };
 
+// What the DROP instantiations take beside the panel (gnx_dense_drop): the two masks of out = drop_out(act(drop_in(X) . W + b)) as the
+// feature-dropout pass takes them (DropFuse: seed, stream, offset, thr, scale; drop_values, gnx_layer_device.h) and the panel's first
+// output column (the output mask is keyed by the column of the whole result).  thr == 0 on a side: nothing is hashed there.  The
+// instantiations without DROP take DenseArgs as it stands.
+template <bool DROP> struct DenseArgsD : DenseArgs {};
+template <> struct DenseArgsD<true> : DenseArgs {
+    DropFuse din, dout;
+    int col0;
+};
+
+// x <- drop(x) for the four consecutive columns col .. col + 3 of row `row` that a lane holds as one fragment
+__device__ __forceinline__ void drop_fragment(const DropFuse &f, uint64_t stream, int64_t row, int64_t col, f32x4 &x) {
+    float v[4] = {x[0], x[1], x[2], x[3]};
+    drop_values<4>(f, stream, row, col, v);
+    x = f32x4{v[0], v[1], v[2], v[3]};
+}
+
 template <int NT> struct DenseCfg {
     static constexpr int OP = NT * 16;                 // padded output width
     static constexpr int KC = NT <= 4 ? 64 : 32;       // W rows per LDS chunk
@@ -41,8 +62,8 @@ template <int NT> struct DenseCfg {
 
 constexpr int DENSE_WAVES = 8;       // waves (16-row strips) per block: 128 rows share one W chunk in LDS
 
-template <int NT, bool ALIGNED>
-__global__ __launch_bounds__(64 * DENSE_WAVES) void k_dense_mfma(const DenseArgs p) {
+template <int NT, bool ALIGNED, bool DROP = false>
+__global__ __launch_bounds__(64 * DENSE_WAVES) void k_dense_mfma(const DenseArgsD<DROP> p) {
     using Cfg = DenseCfg<NT>;
     __shared__ float Ws[Cfg::KC * Cfg::STRIDE];
     const int lane = threadIdx.x & 63;
@@ -52,6 +73,8 @@ __global__ __launch_bounds__(64 * DENSE_WAVES) void k_dense_mfma(const DenseArgs
     int64_t arow = row0 + c < p.n ? row0 + c : p.n - 1;                  // rows past the end read a valid row and are not stored
     if (p.in_rows) arow = p.in_rows[arow];
     const float *__restrict__ xrow = p.X + arow * p.ldx;
+    [[maybe_unused]] uint64_t in_stream = 0, out_stream = 0;
+    if constexpr (DROP) { in_stream = drop_stream(p.din); out_stream = drop_stream(p.dout); }
     f32x4 acc[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -66,6 +89,9 @@ __global__ __launch_bounds__(64 * DENSE_WAVES) void k_dense_mfma(const DenseArgs
             } else {
 #pragma unroll
                 for (int t = 0; t < 4; ++t) a[T][t] = kb + t < p.F ? xrow[kb + t] : 0.f;
+            }
+            if constexpr (DROP) {                                          // the input mask, on the fragment as loaded (columns past F hold zeros)
+                if (p.din.thr != 0 && kb < p.F) drop_values<4>(p.din, in_stream, arow, kb, a[T]);
             }
         }
     };
@@ -116,6 +142,13 @@ __global__ __launch_bounds__(64 * DENSE_WAVES) void k_dense_mfma(const DenseArgs
             if (row >= p.n) continue;
             float v = acc[nt][r] + b;
             if (p.act == GNX_ACT_RELU) v = fmaxf(v, 0.f);
+            if constexpr (DROP) {                                          // the output mask, after bias and relu
+                if (p.dout.thr != 0) {
+                    float one[1] = {v};
+                    drop_values<1>(p.dout, out_stream, row, p.col0 + col, one);
+                    v = one[0];
+                }
+            }
             const int64_t orow = p.out_rows ? (int64_t)p.out_rows[row] : row;
             p.out[orow * p.ldo + col] = v;
         }
@@ -142,8 +175,8 @@ __device__ __forceinline__ f32x4 stage_fragment(const float *A, int c, int g, in
     return *reinterpret_cast<const f32x4 *>(A + c * RING_BK + 4 * ((4 * T + g) ^ c));
 }
 
-template <int NT, int WAVES, int RING>
-__global__ __launch_bounds__(64 * WAVES) void k_dense_ring(const DenseArgs p, int64_t n_tiles) {
+template <int NT, int WAVES, int RING, bool DROP = false>
+__global__ __launch_bounds__(64 * WAVES) void k_dense_ring(const DenseArgsD<DROP> p, int64_t n_tiles) {
     static_assert(NT % 4 == 0, "the W image groups the accumulator columns in fours");
     constexpr int NQ = NT / 4;                                    // column groups of 4 x 16 outputs
     constexpr int STAGE = 16 * RING_BK;                           // floats per stage: 16 rows x 64
@@ -163,6 +196,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_dense_ring(const DenseArgs p, in
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) bias[nt] = (p.bias && 16 * nt + c < p.O) ? p.bias[16 * nt + c] : 0.f;
     __syncthreads();                                              // the only barrier: W is in place
+    [[maybe_unused]] uint64_t in_stream = 0, out_stream = 0;
+    if constexpr (DROP) { in_stream = drop_stream(p.din); out_stream = drop_stream(p.dout); }
 
     const int kchunks = p.F / RING_BK;
     const int64_t tile_stride = (int64_t)gridDim.x * WAVES;
@@ -211,6 +246,12 @@ __global__ __launch_bounds__(64 * WAVES) void k_dense_ring(const DenseArgs p, in
                 f32x4 a4[RING_BK / 16];
 #pragma unroll
                 for (int T = 0; T < RING_BK / 16; ++T) a4[T] = stage_fragment(A, c, g, T);
+                if constexpr (DROP) {                                         // the input mask, on the fragments as read back (the LDS-DMA cannot mask)
+                    if (p.din.thr != 0) {
+#pragma unroll
+                        for (int T = 0; T < RING_BK / 16; ++T) drop_fragment(p.din, in_stream, tile * 16 + c, kc * RING_BK + 16 * T + 4 * g, a4[T]);
+                    }
+                }
                 const float *__restrict__ Wk = Wl + ((kc * RING_BK + 4 * g) * NQ) * 64 + c * 4;      // fragment of k = kc 64 + 4 g (+ 16 T + t)
                 f32x4 b[2][NQ];
 #pragma unroll
@@ -241,7 +282,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_dense_ring(const DenseArgs p, in
                 // wide outputs (O = 192 / 256): sixteen accumulator tiles leave no room for fragments in flight (measured: +5 % with them)
 #pragma unroll
                 for (int T = 0; T < RING_BK / 16; ++T) {
-                    const f32x4 a4 = stage_fragment(A, c, g, T);
+                    f32x4 a4 = stage_fragment(A, c, g, T);
+                    if constexpr (DROP) {
+                        if (p.din.thr != 0) drop_fragment(p.din, in_stream, tile * 16 + c, kc * RING_BK + 16 * T + 4 * g, a4);
+                    }
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
                         const int k = kc * RING_BK + 16 * T + 4 * g + t;
@@ -265,6 +309,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_dense_ring(const DenseArgs p, in
                 const int64_t row = tile * 16 + 4 * g + r;
                 float v = acc[nt][r] + bias[nt];
                 if (p.act == GNX_ACT_RELU) v = fmaxf(v, 0.f);
+                if constexpr (DROP) {                                         // the output mask, after bias and relu
+                    if (p.dout.thr != 0 && col < p.O && row < p.n) {
+                        float one[1] = {v};
+                        drop_values<1>(p.dout, out_stream, row, p.col0 + col, one);
+                        v = one[0];
+                    }
+                }
                 if (col < p.O && row < p.n) p.out[row * p.ldo + col] = v;
             }
             acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -272,27 +323,33 @@ __global__ __launch_bounds__(64 * WAVES) void k_dense_ring(const DenseArgs p, in
     }
 }
 
-template <int NT, int WAVES, int RING>
-int launch_ring_as(const DenseArgs &p, hipStream_t s) {
+template <int NT, int WAVES, int RING, bool DROP>
+int launch_ring_as(const DenseArgsD<DROP> &p, hipStream_t s) {
     const size_t lds_bytes = ((size_t)p.F * NT * 16 + (size_t)WAVES * RING * 16 * RING_BK) * sizeof(float);
-    const int cus = persistent_launch<k_dense_ring<NT, WAVES, RING>>();
+    const int cus = persistent_launch<k_dense_ring<NT, WAVES, RING, DROP>>();
     if (cus < 0) return cus;
     const int64_t n_tiles = (p.n + 15) / 16;
     const unsigned grid = (unsigned)std::min<int64_t>((n_tiles + WAVES - 1) / WAVES, cus);
-    hipLaunchKernelGGL((k_dense_ring<NT, WAVES, RING>), dim3(grid), dim3(64 * WAVES), lds_bytes, s, p, n_tiles);
+    hipLaunchKernelGGL((k_dense_ring<NT, WAVES, RING, DROP>), dim3(grid), dim3(64 * WAVES), lds_bytes, s, p, n_tiles);
     return GNX_OK;
 }
 
 // Waves per block: as many 2-stage rings (8 KB each) as fit beside the W image in the CU's 160 KB of LDS, up to 16 -- measured at
 // 10M x 256 -> 64: 4 waves x 4 stages 4.14 ms, 8 x 2 3.54, 8 x 3 3.61, 12 x 2 3.41 (k_dense_mfma: 3.59); the matrix pipe wants
 // three waves per SIMD more than it wants a deeper ring.
-template <int NT>
-int launch_ring(const DenseArgs &p, bool, hipStream_t s) {
+template <int NT, bool DROP>
+int launch_ring(const DenseArgsD<DROP> &p, bool, hipStream_t s) {
     const size_t w_bytes = (size_t)p.F * NT * 16 * sizeof(float);
     const size_t rings = ((160u << 10) - w_bytes) / (2 * 16 * RING_BK * sizeof(float));
-    if (rings >= 16) return launch_ring_as<NT, 16, 2>(p, s);
-    if (rings >= 12) return launch_ring_as<NT, 12, 2>(p, s);
-    return launch_ring_as<NT, 8, 2>(p, s);
+    // DROP: the hashes in flight need registers -- no more waves than build without scratch at NT accumulator tiles (12 at NT = 8, 8 above)
+    constexpr int MOST = !DROP || NT <= 4 ? 16 : NT <= 8 ? 12 : 8;
+    if constexpr (MOST >= 16) {
+        if (rings >= 16) return launch_ring_as<NT, 16, 2, DROP>(p, s);
+    }
+    if constexpr (MOST >= 12) {
+        if (rings >= 12) return launch_ring_as<NT, 12, 2, DROP>(p, s);
+    }
+    return launch_ring_as<NT, 8, 2, DROP>(p, s);
 }
 
 // ---- W in REGISTERS, X through a deep LDS-DMA ring ---------------------------------------------------------------------------------
@@ -311,8 +368,10 @@ int launch_ring(const DenseArgs &p, bool, hipStream_t s) {
 // 4 stages up and the staging waits are never taken -- what the launch costs beyond the MFMAs is issue slots and the clock.
 // PAD: F < 64 KS and / or O < 16 NT (both multiples of 4): the columns of X past F are staged from a block of zeros (times the zero rows
 // W gets there: exact, whatever X holds), the columns past O are neither loaded from W nor stored.
-template <int NT, int KS, int RING, bool RELU, bool PAD>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_dense_wreg(const DenseArgs p, int64_t n_tiles64) {
+// DROP: the input mask is applied to a stage's fragments as they are read back from the ring (`fragments` is told the tile and the K
+// chunk of the stage it reads), the output mask in `finish`; the hash runs in the issue slots between the MFMAs.
+template <int NT, int KS, int RING, bool RELU, bool PAD, bool DROP = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_dense_wreg(const DenseArgsD<DROP> p, int64_t n_tiles64) {
     constexpr int STAGE = 16 * RING_BK;
     extern __shared__ float lds[];                                // [4 waves][RING][STAGE]
     const int lane = threadIdx.x & 63;
@@ -346,6 +405,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const uint32_t x_pitch = (uint32_t)p.ldx * 4u, o_pitch = (uint32_t)p.ldo * 4u;      // bytes
     const char *__restrict__ Xb = reinterpret_cast<const char *>(p.X);
     char *__restrict__ Ob = reinterpret_cast<char *>(p.out);
+    [[maybe_unused]] uint64_t in_stream = 0, out_stream = 0;
+    if constexpr (DROP) { in_stream = drop_stream(p.din); out_stream = drop_stream(p.dout); }
     uint32_t piece[4];                                            // byte offset of this lane's 16-byte piece inside the stage's 256 bytes of row 4 i + g
 #pragma unroll
     for (int i = 0; i < 4; ++i) piece[i] = 16u * (uint32_t)(c ^ (4 * i + g));
@@ -364,17 +425,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }
         if (pf_kc == KS - 1) pf_tile += tile_stride;
     };
-    auto fragments = [&](int slot, f32x4 (&a)[4]) {               // X[row c][16 T + 4 g .. + 3] of the stage in `slot`
+    // X[row c][16 T + 4 g .. + 3] of the stage in `slot`; DROP: the stage is K chunk `kc` of tile `tile`
+    auto fragments = [&](int slot, f32x4 (&a)[4], [[maybe_unused]] uint32_t tile, [[maybe_unused]] int kc) {
         const float *__restrict__ A = ring + slot * STAGE;
 #pragma unroll
         for (int T = 0; T < 4; ++T) a[T] = stage_fragment(A, c, g, T);
+        if constexpr (DROP) {
+            if (p.din.thr != 0) {
+#pragma unroll
+                for (int T = 0; T < 4; ++T) {
+                    const int col = kc * RING_BK + 16 * T + 4 * g;
+                    if (!PAD || col < p.F) drop_fragment(p.din, in_stream, (int64_t)(tile * 16u + c), col, a[T]);     // (the zeros past F need no hash)
+                }
+            }
+        }
     };
     // D layout with W as the A operand: lane (c, g), register r -> row c, column 16 nt + 4 g + r
-    auto finish = [&](const f32x4 &acc, int nt) {
+    auto finish = [&](const f32x4 &acc, int nt, [[maybe_unused]] uint32_t row) {
         f32x4 v = acc + bias[nt];
         if constexpr (RELU) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+        }
+        if constexpr (DROP) {                                     // the output mask, after bias and relu
+            if (p.dout.thr != 0) drop_fragment(p.dout, out_stream, (int64_t)row, p.col0 + 16 * nt + 4 * g, v);
         }
         return v;
     };
@@ -382,7 +456,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         char *o = Ob + (uint64_t)row * o_pitch + 16u * g;
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
-            if (!PAD || 16 * nt + 4 * g < p.O) *reinterpret_cast<f32x4 *>(o + 64 * nt) = finish(acc[nt], nt);
+            if (!PAD || 16 * nt + 4 * g < p.O) *reinterpret_cast<f32x4 *>(o + 64 * nt) = finish(acc[nt], nt, row);
     };
     auto store_tile = [&](f32x4 (&acc)[NT], uint32_t tile) { store_row(acc, tile * 16u + c); };      // a full tile: no guards
     auto store_last = [&](f32x4 (&acc)[NT], uint32_t tile) {      // the wave's last tile: may be the ragged one
@@ -391,7 +465,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     f32x4 afrag[2][4];                                            // the X fragments of the stage being multiplied and of the next one
     // one tile: KS stages; `slot0` is the ring slot of its first stage (compile-time).  With EPI, the stores of the wave's previous tile
     // sit among the first stage's MFMAs.
-    auto tile_body = [&](auto epi, int slot0, f32x4 (&acc)[NT], f32x4 (&prev)[NT], uint32_t prev_tile) {
+    // `tile`: the tile being multiplied (DROP: the row key of the fragments read for its stages and for the first stage of the next one)
+    auto tile_body = [&](auto epi, int slot0, f32x4 (&acc)[NT], f32x4 (&prev)[NT], uint32_t prev_tile, [[maybe_unused]] uint32_t tile) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -414,7 +489,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                         acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[kc][T][t][nt], a_cur[T][t], acc[nt], 0, 0, 0);
             // the next stage: RING - 2 younger stages may still be in flight behind it
             asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 * (RING - 2)) : "memory");
-            fragments((slot + 1) % RING, a_nxt);
+            fragments((slot + 1) % RING, a_nxt, kc == KS - 1 ? tile + tile_stride : tile, (kc + 1) % KS);
 #pragma unroll
             for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -428,17 +503,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
         for (int s0 = 0; s0 < RING - 1; ++s0) issue(s0 % KS, s0);
         asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 * (RING - 2)) : "memory");          // stage 0 has landed
-        fragments(0, afrag[0]);
+        fragments(0, afrag[0], first, 0);
         f32x4 accA[NT], accB[NT];
         uint32_t tile = first;
         constexpr int SLOT_B = KS % RING;                         // first slot of every second tile
-        tile_body(std::false_type{}, 0, accA, accB, 0u);
+        tile_body(std::false_type{}, 0, accA, accB, 0u, tile);
         for (;;) {
             if (tile + tile_stride >= n_tiles) { store_last(accA, tile); break; }
-            tile_body(std::true_type{}, SLOT_B, accB, accA, tile);
+            tile_body(std::true_type{}, SLOT_B, accB, accA, tile, tile + tile_stride);
             tile += tile_stride;
             if (tile + tile_stride >= n_tiles) { store_last(accB, tile); break; }
-            tile_body(std::true_type{}, 0, accA, accB, tile);
+            tile_body(std::true_type{}, 0, accA, accB, tile, tile + tile_stride);
             tile += tile_stride;
         }
     }
@@ -461,34 +536,34 @@ const float *device_zeros() {
     return z[dev];
 }
 
-template <int NT, int KS, int RING, bool RELU, bool PAD>
-int launch_wreg_as(const DenseArgs &p, hipStream_t s) {
+template <int NT, int KS, int RING, bool RELU, bool PAD, bool DROP>
+int launch_wreg_as(const DenseArgsD<DROP> &p, hipStream_t s) {
     const size_t lds_bytes = (size_t)4 * RING * 16 * RING_BK * sizeof(float);
-    const int cus = persistent_launch<k_dense_wreg<NT, KS, RING, RELU, PAD>>();
+    const int cus = persistent_launch<k_dense_wreg<NT, KS, RING, RELU, PAD, DROP>>();
     if (cus < 0) return cus;
     const int64_t n_tiles = (p.n + 15) / 16;
     const unsigned grid = (unsigned)std::min<int64_t>((n_tiles + 3) / 4, cus);
-    hipLaunchKernelGGL((k_dense_wreg<NT, KS, RING, RELU, PAD>), dim3(grid), dim3(256), lds_bytes, s, p, n_tiles);
+    hipLaunchKernelGGL((k_dense_wreg<NT, KS, RING, RELU, PAD, DROP>), dim3(grid), dim3(256), lds_bytes, s, p, n_tiles);
     return GNX_OK;
 }
 
-template <int NT, int KS, int RING>
-int launch_wreg(const DenseArgs &p0, bool, hipStream_t s) {
-    DenseArgs p = p0;
+template <int NT, int KS, int RING, bool DROP>
+int launch_wreg(const DenseArgsD<DROP> &p0, bool, hipStream_t s) {
+    DenseArgsD<DROP> p = p0;
     const bool pad = p.F != 64 * KS || p.O != 16 * NT;
     if (pad) {
         p.zeros = device_zeros();
         if (!p.zeros) return GNX_ERR_ALLOC;
-        return p.act == GNX_ACT_RELU ? launch_wreg_as<NT, KS, RING, true, true>(p, s) : launch_wreg_as<NT, KS, RING, false, true>(p, s);
+        return p.act == GNX_ACT_RELU ? launch_wreg_as<NT, KS, RING, true, true, DROP>(p, s) : launch_wreg_as<NT, KS, RING, false, true, DROP>(p, s);
     }
-    return p.act == GNX_ACT_RELU ? launch_wreg_as<NT, KS, RING, true, false>(p, s) : launch_wreg_as<NT, KS, RING, false, false>(p, s);
+    return p.act == GNX_ACT_RELU ? launch_wreg_as<NT, KS, RING, true, false, DROP>(p, s) : launch_wreg_as<NT, KS, RING, false, false, DROP>(p, s);
 }
 
-template <int NT>
-int launch_dense(const DenseArgs &p, bool aligned, hipStream_t s) {
+template <int NT, bool DROP>
+int launch_dense(const DenseArgsD<DROP> &p, bool aligned, hipStream_t s) {
     const unsigned grid = (unsigned)((p.n + 16 * DENSE_WAVES - 1) / (16 * DENSE_WAVES));
-    if (aligned) hipLaunchKernelGGL((k_dense_mfma<NT, true>), dim3(grid), dim3(64 * DENSE_WAVES), 0, s, p);
-    else         hipLaunchKernelGGL((k_dense_mfma<NT, false>), dim3(grid), dim3(64 * DENSE_WAVES), 0, s, p);
+    if (aligned) hipLaunchKernelGGL((k_dense_mfma<NT, true, DROP>), dim3(grid), dim3(64 * DENSE_WAVES), 0, s, p);
+    else         hipLaunchKernelGGL((k_dense_mfma<NT, false, DROP>), dim3(grid), dim3(64 * DENSE_WAVES), 0, s, p);
     return GNX_OK;
 }
 
@@ -504,26 +579,54 @@ int launch_dense(const DenseArgs &p, bool aligned, hipStream_t s) {
 //   3. k_dense_mfma<NT, ALIGNED = x_aligned>: every other panel, row maps included; NT = nt rounded up to one of 1 2 3 4 6 8 12 16.
 // The alignment of W decides nothing here: p.w_aligned only picks how k_dense_mfma loads W; the other two load it once, by the word.
 // (tuning builds: GNX_DENSE_WREG=0 skips rule 1, GNX_DENSE_RING=0 rule 2, for A/B runs)
-typedef int (*DenseLaunch)(const DenseArgs &p, bool x_aligned, hipStream_t s);
+// DROP (gnx_dense_drop) takes the same rules: whichever kernel carries a shape adds the k terms in the same order and hashes the same keys.
+template <bool DROP> using DenseLaunch = int (*)(const DenseArgsD<DROP> &p, bool x_aligned, hipStream_t s);
 
-DenseLaunch dense_kernel_for(const DenseArgs &p, bool x_aligned) {
+template <bool DROP>
+DenseLaunch<DROP> dense_kernel_for(const DenseArgsD<DROP> &p, bool x_aligned) {
     const int nt = (p.O + 15) / 16;
     const bool tall = x_aligned && p.in_rows == nullptr && p.out_rows == nullptr && p.n >= 16 * 1024;
     const bool out_aligned = aligned(p.out, 16) && p.ldo % 4 == 0;
     if (tall && tuning_switch("GNX_DENSE_WREG") && out_aligned && p.F % 4 == 0 && p.O % 4 == 0 && p.n < (1ll << 31) && p.ldx < (1ll << 30) &&
         p.ldo < (1ll << 30)) {
+        // DROP: with W in 256 registers (<4, 4, 8>, <8, 2, 4>) the hashes of a stage do not fit beside it (the build spills 132 .. 472
+        // bytes per lane): those panels take rule 2 or 3
         if (p.F > 128 && p.F <= 256) {
-            if (p.O <= 32) return launch_wreg<2, 4, 8>;
-            if (p.O <= 64) return launch_wreg<4, 4, 8>;
+            if (p.O <= 32) return launch_wreg<2, 4, 8, DROP>;
+            if constexpr (!DROP) {
+                if (p.O <= 64) return launch_wreg<4, 4, 8, DROP>;
+            }
         } else if (p.F > 64 && p.F <= 128) {
-            if (p.O <= 64) return launch_wreg<4, 2, 4>;
-            if (p.O <= 128) return launch_wreg<8, 2, 4>;
+            if (p.O <= 64) return launch_wreg<4, 2, 4, DROP>;
+            if constexpr (!DROP) {
+                if (p.O <= 128) return launch_wreg<8, 2, 4, DROP>;
+            }
         }
     }
     if (tall && tuning_switch("GNX_DENSE_RING") && p.F % RING_BK == 0 && nt % 4 == 0 && (int64_t)p.F * nt * 16 * 4 <= (64 << 10))
-        return nt == 4 ? launch_ring<4> : nt == 8 ? launch_ring<8> : nt == 12 ? launch_ring<12> : launch_ring<16>;
-    return nt <= 1 ? launch_dense<1> : nt <= 2 ? launch_dense<2> : nt <= 3 ? launch_dense<3> : nt <= 4 ? launch_dense<4> :
-           nt <= 6 ? launch_dense<6> : nt <= 8 ? launch_dense<8> : nt <= 12 ? launch_dense<12> : launch_dense<16>;
+        return nt == 4 ? launch_ring<4, DROP> : nt == 8 ? launch_ring<8, DROP> : nt == 12 ? launch_ring<12, DROP> : launch_ring<16, DROP>;
+    return nt <= 1 ? launch_dense<1, DROP> : nt <= 2 ? launch_dense<2, DROP> : nt <= 3 ? launch_dense<3, DROP> : nt <= 4 ? launch_dense<4, DROP> :
+           nt <= 6 ? launch_dense<6, DROP> : nt <= 8 ? launch_dense<8, DROP> : nt <= 12 ? launch_dense<12, DROP> : launch_dense<16, DROP>;
+}
+
+// the column panels of at most 256 outputs of one product, each through dense_kernel_for (DROP: p.col0 = the panel's first column)
+template <bool DROP>
+int dense_panels(const DenseArgsD<DROP> &p, hipStream_t s) {
+    const float *W = p.W, *bias = p.bias;
+    float *out = p.out;
+    const int O = p.O;
+    const bool al = p.ldx % 4 == 0 && aligned(p.X, 16);
+    for (int o0 = 0; o0 < O; o0 += 256) {
+        DenseArgsD<DROP> q = p;
+        q.W = W + o0; q.bias = bias ? bias + o0 : nullptr; q.out = out + o0;
+        q.w_aligned = p.ldw % 4 == 0 && aligned(q.W, 16);
+        q.O = O - o0 < 256 ? O - o0 : 256;
+        if constexpr (DROP) q.col0 = o0;
+        const int rc = dense_kernel_for<DROP>(q, al)(q, al, s);
+        if (rc != GNX_OK) return rc;
+    }
+    GNX_HIP(hipGetLastError());
+    return GNX_OK;
 }
 
 }  // namespace
@@ -534,18 +637,9 @@ namespace gnx {
 int dense_rows(const float *X, int64_t ldx, int64_t n, int64_t F, const float *W, int64_t ldw, int64_t O, const float *bias, int act,
                const int32_t *in_rows, const int32_t *out_rows, float *out, int64_t ldo, hipStream_t s) {
     if (n == 0) return GNX_OK;
-    DenseArgs p{X, ldx, n, (int)F, W, ldw, (int)O, bias, act, out, ldo, out_rows, in_rows, false};
-    const bool al = ldx % 4 == 0 && aligned(X, 16);
-    for (int64_t o0 = 0; o0 < O; o0 += 256) {                         // column panels of at most 256 outputs
-        DenseArgs q = p;
-        q.W = W + o0; q.bias = bias ? bias + o0 : nullptr; q.out = out + o0;
-        q.w_aligned = ldw % 4 == 0 && aligned(q.W, 16);
-        q.O = (int)(O - o0 < 256 ? O - o0 : 256);
-        const int rc = dense_kernel_for(q, al)(q, al, s);
-        if (rc != GNX_OK) return rc;
-    }
-    GNX_HIP(hipGetLastError());
-    return GNX_OK;
+    DenseArgsD<false> p;
+    static_cast<DenseArgs &>(p) = DenseArgs{X, ldx, n, (int)F, W, ldw, (int)O, bias, act, out, ldo, out_rows, in_rows, false};
+    return dense_panels<false>(p, s);
 }
 
 }  // namespace gnx
@@ -562,6 +656,32 @@ int gnx_dense(const float *d_X, int64_t ldx, int64_t n, int64_t F, const float *
     GNX_CHECK_ARG(d_X && d_W && d_out, "gnx_dense: NULL pointer");
     GNX_CHECK_ARG((const void *)d_X != (const void *)d_out, "gnx_dense: out must not alias X");
     return dense_rows(d_X, ldx, n, F, d_W, ldw, O, d_bias, act, nullptr, nullptr, d_out, ldo, (hipStream_t)stream);
+}
+
+int gnx_dense_drop(gnx_graph_t g, const float *d_X, int64_t ldx, int64_t n, int64_t F, const float *d_W, int64_t ldw, int64_t O,
+                   const float *d_bias, int act, double in_p, uint64_t in_seed, uint64_t in_stream, double out_p, uint64_t out_seed,
+                   uint64_t out_stream, float *d_out, int64_t ldo, void *stream) {
+    GNX_CHECK_ARG(n >= 0 && F >= 1 && O >= 1 && F <= (1 << 24) && O <= (1 << 20), "gnx_dense_drop: bad sizes (n=%lld, F=%lld, O=%lld)",
+                  (long long)n, (long long)F, (long long)O);
+    GNX_CHECK_ARG(ldx >= F && ldw >= O && ldo >= O, "gnx_dense_drop: leading dimension smaller than the row");
+    GNX_CHECK_ARG(act == GNX_ACT_NONE || act == GNX_ACT_RELU, "gnx_dense_drop: invalid activation %d", act);
+    // (the handle is read -- for its dropout counter -- only once every other argument has passed)
+    GNX_CHECK_ARG(g != nullptr, "gnx_dense_drop: NULL handle");
+    GNX_CHECK_ARG(in_p >= 0.0 && in_p < 1.0 && out_p >= 0.0 && out_p < 1.0, "gnx_dense_drop: dropout rate %g outside [0, 1)",
+                  in_p >= 0.0 && in_p < 1.0 ? out_p : in_p);
+    if (n == 0) return GNX_OK;
+    GNX_CHECK_ARG(d_X && d_W && d_out, "gnx_dense_drop: NULL pointer");
+    GNX_CHECK_ARG((const void *)d_X != (const void *)d_out, "gnx_dense_drop: out must not alias X");
+    DenseArgsD<true> p;
+    int rc = make_feat_drop("gnx_dense_drop", g, in_p, in_seed, in_stream, p.din);
+    if (rc != GNX_OK) return rc;
+    rc = make_feat_drop("gnx_dense_drop", g, out_p, out_seed, out_stream, p.dout);
+    if (rc != GNX_OK) return rc;
+    if (p.din.thr == 0 && p.dout.thr == 0)          // no mask on either side: the plain product (same kernels, same bits, nothing hashed)
+        return dense_rows(d_X, ldx, n, F, d_W, ldw, O, d_bias, act, nullptr, nullptr, d_out, ldo, (hipStream_t)stream);
+    static_cast<DenseArgs &>(p) = DenseArgs{d_X, ldx, n, (int)F, d_W, ldw, (int)O, d_bias, act, d_out, ldo, nullptr, nullptr, false};
+    p.col0 = 0;
+    return dense_panels<true>(p, (hipStream_t)stream);
 }
 
 }  // extern "C"

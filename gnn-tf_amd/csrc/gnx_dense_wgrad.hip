@@ -1,12 +1,19 @@
 // The weight gradient of the dense transform (gnx_dense.hip) on gfx950 matrix cores.
 //
 //   gnx_dense_wgrad  dW[F, O] = X^T . G      what tf.GradientTape derives for gnntf/core/nn/layers.py:136
+//   gnx_dense_wgrad_drop  dW = drop_in(X)^T . G   the same behind gnx_dense_drop: the DROP form of both kernels makes the input mask again
 //
 // k_wgrad_acc (accumulators stationary: tall inputs, widths multiples of 4) or k_wgrad_mfma (every other shape) leaves one partial dW
 // per row slab in the caller's scratch; k_sum_slabs adds them in slab order, as it does for gnx_gcnii_wgrad (gnx_gcnii.hip).
 #include "gnx_dense_device.h"
+#include "gnx_layer_device.h"
 
 namespace {
+
+// The input mask of the DROP instantiations (gnx_dense_wgrad_drop: dW = drop_in(X)^T . G, the mask of gnx_dense_drop made again from its
+// triple -- drop_values, gnx_layer_device.h); the instantiations without DROP take an empty struct in its place.
+template <bool DROP> struct WgradMask {};
+template <> struct WgradMask<true> { DropFuse din; };
 
 // ---- dW[F, O] = X^T . G, a reduction over the N rows, in panels ---------------------------------------------------------------
 // M = F, N = O, K = rows.  grid.x = row slabs, grid.y = panels of 256 features, grid.z = panels of 16 NT outputs.  A block
@@ -14,10 +21,11 @@ namespace {
 // [64 w, 64 w + 64) of the panel as 4 x NT accumulator tiles: A[m = feature][k = row] and B[k = row][n = output] fragments are
 // read from LDS (row stride = 16 mod 32 banks, so the two k-groups of a half-wave hit disjoint banks).  Every slab writes its
 // partial dW; a second kernel adds the slabs in order (fixed order: reproducible, no float atomics).
-template <int NT>
+// DROP: the tile of X is masked between its global load and its LDS store.
+template <int NT, bool DROP = false>
 __global__ __launch_bounds__(256) void k_wgrad_mfma(const float *__restrict__ X, int64_t ldx, const float *__restrict__ G, int64_t ldg,
                                                      int64_t n, int F, int O, int64_t rows_per_slab, bool aligned,
-                                                     float *__restrict__ partial) {
+                                                     float *__restrict__ partial, const WgradMask<DROP> mask) {
     constexpr int R = 32, XS = 256 + 16, GS = 16 * NT + 16;
     __shared__ float Xs[R * XS];
     __shared__ float Gs[R * GS];
@@ -26,6 +34,8 @@ __global__ __launch_bounds__(256) void k_wgrad_mfma(const float *__restrict__ X,
     const int f0 = blockIdx.y * 256, o0 = blockIdx.z * 16 * NT;
     const int64_t r_beg = (int64_t)blockIdx.x * rows_per_slab;
     const int64_t r_end = r_beg + rows_per_slab < n ? r_beg + rows_per_slab : n;
+    [[maybe_unused]] uint64_t in_stream = 0;
+    if constexpr (DROP) in_stream = drop_stream(mask.din);
     f32x4 acc[4][NT];
 #pragma unroll
     for (int ft = 0; ft < 4; ++ft)
@@ -43,6 +53,13 @@ __global__ __launch_bounds__(256) void k_wgrad_mfma(const float *__restrict__ X,
                 else {
 #pragma unroll
                     for (int t = 0; t < 4; ++t) if (f0 + cc + t < F) v[t] = src[t];
+                }
+                if constexpr (DROP) {
+                    if (f0 + cc < F) {                                          // (columns past F hold zeros)
+                        float x[4] = {v[0], v[1], v[2], v[3]};
+                        drop_values<4>(mask.din, in_stream, row, f0 + cc, x);
+                        v = f32x4{x[0], x[1], x[2], x[3]};
+                    }
                 }
             }
             *reinterpret_cast<f32x4 *>(Xs + rr * XS + cc) = v;
@@ -112,10 +129,11 @@ template <int MT, int NT> struct WgradAcc {
     static_assert(MT * NT <= 64, "the accumulators must fit the register file");
 };
 
-template <int MT, int NT>
+// DROP: the single-word X fragments are masked as they are read from the ring (each element of X is read by one lane, once per panel).
+template <int MT, int NT, bool DROP = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void k_wgrad_acc(const float *__restrict__ X, uint32_t x_pitch, int f_all, const float *__restrict__ G, uint32_t g_pitch, int o_all, uint32_t n,
-                 uint32_t rows_per_wave, uint32_t f_panels, uint32_t panels, float *__restrict__ partial) {
+                 uint32_t rows_per_wave, uint32_t f_panels, uint32_t panels, float *__restrict__ partial, const WgradMask<DROP> mask) {
     using Cfg = WgradAcc<MT, NT>;
     // F x O: the PANEL this wave accumulates (padded to whole 16-column tiles of a power-of-two count).  Columns past the real widths
     // stage a piece that exists (piece 0 of the row) and feed only accumulator cells that are never stored.
@@ -166,12 +184,15 @@ void k_wgrad_acc(const float *__restrict__ X, uint32_t x_pitch, int f_all, const
     // fragments of k step s (rows 4 s + g): word 16 t + c of the row sits in piece group t ^ (g & 1)
     const int flip = g & 1;
     const int x_lane = g * F + c, g_lane = g * O + c;
+    [[maybe_unused]] uint64_t in_stream = 0;
+    if constexpr (DROP) in_stream = drop_stream(mask.din);
     f32x4 acc[MT][NT];
 #pragma unroll
     for (int ft = 0; ft < MT; ++ft)
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) acc[ft][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto multiply = [&](auto masked, uint32_t slot, uint32_t valid_rows) {
+    // `row0` (DROP): the first row of the stage in `slot`
+    auto multiply = [&](auto masked, uint32_t slot, uint32_t valid_rows, [[maybe_unused]] uint32_t row0) {
         const float *__restrict__ Xs = ring + slot * STAGE + x_lane;
         const float *__restrict__ Gs = ring + slot * STAGE + R * F + g_lane;
 #pragma unroll
@@ -181,6 +202,14 @@ void k_wgrad_acc(const float *__restrict__ X, uint32_t x_pitch, int f_all, const
             for (int ft = 0; ft < MT; ++ft) a[ft] = Xs[4 * s * F + 16 * (ft ^ flip)];
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) b[nt] = Gs[4 * s * O + 16 * (nt ^ flip)];
+            if constexpr (DROP) {                                 // a[ft] = X[row0 + 4 s + g][f0 + 16 ft + c]; the row's round of the hash is shared
+#pragma unroll
+                for (int ft = 0; ft < MT; ++ft) {
+                    float x[1] = {a[ft]};
+                    drop_values<1>(mask.din, in_stream, (int64_t)(row0 + 4 * s + g), f0 + 16 * ft + c, x);
+                    a[ft] = x[0];
+                }
+            }
             if constexpr (decltype(masked)::value) {
                 if ((uint32_t)(4 * s + g) >= valid_rows) {        // 0 x 0: a row past the slab adds nothing, whatever the row that was read holds
 #pragma unroll
@@ -202,11 +231,11 @@ void k_wgrad_acc(const float *__restrict__ X, uint32_t x_pitch, int f_all, const
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // the fragments of the stage whose slot is restaged next have been read
         issue_next();
         asm volatile("s_waitcnt vmcnt(%0)" :: "n"(Cfg::NI * (RING - 1)) : "memory");    // all but the youngest RING - 1 stages: stage st has landed
-        multiply(std::false_type{}, slot, R);
+        multiply(std::false_type{}, slot, R, r_beg + st * R);
         slot = slot + 1 == RING ? 0 : slot + 1;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // (also: nothing of this wave may still be writing LDS when it retires)
-    multiply(std::true_type{}, slot, r_end - (r_beg + (n_stages - 1) * R));
+    multiply(std::true_type{}, slot, r_end - (r_beg + (n_stages - 1) * R), r_beg + (n_stages - 1) * R);
     // D layout with G as the A operand: lane (c, g), register r -> feature 16 ft + c, output 16 nt + 4 g + r
     float *__restrict__ out = partial + (uint64_t)wid * ((uint32_t)f_all * (uint32_t)o_all) + (uint32_t)f0 * (uint32_t)o_all + o0;
 #pragma unroll
@@ -217,12 +246,12 @@ void k_wgrad_acc(const float *__restrict__ X, uint32_t x_pitch, int f_all, const
                 *reinterpret_cast<f32x4 *>(out + (16 * ft + c) * o_all + 16 * nt + 4 * g) = acc[ft][nt];
 }
 
-template <int MT, int NT>
+template <int MT, int NT, bool DROP>
 int launch_wgrad_acc(const float *X, int64_t ldx, int64_t F, const float *G, int64_t ldg, int64_t O, int64_t n, float *work, int64_t max_slabs,
-                     int64_t *n_slabs, hipStream_t s) {
+                     int64_t *n_slabs, const WgradMask<DROP> &mask, hipStream_t s) {
     using Cfg = WgradAcc<MT, NT>;
     const size_t lds_bytes = (size_t)4 * Cfg::RING * Cfg::STAGE * sizeof(float);
-    const int cus = persistent_launch<k_wgrad_acc<MT, NT>>();
+    const int cus = persistent_launch<k_wgrad_acc<MT, NT, DROP>>();
     if (cus < 0) return cus;
     const int64_t f_panels = (F + Cfg::F - 1) / Cfg::F, panels = f_panels * ((O + Cfg::O - 1) / Cfg::O);
     int64_t waves = std::min<int64_t>(std::max<int64_t>((int64_t)cus * 4 / panels, 64), max_slabs);        // row slabs; every slab is walked once per panel
@@ -230,8 +259,8 @@ int launch_wgrad_acc(const float *X, int64_t ldx, int64_t F, const float *G, int
     rows_per_wave = std::max<int64_t>((rows_per_wave + Cfg::R - 1) / Cfg::R * Cfg::R, 8 * Cfg::R);
     waves = (n + rows_per_wave - 1) / rows_per_wave;
     const int64_t slab_blocks = (waves + 3) / 4, grid = (slab_blocks + 7) / 8 * 8 * panels;
-    hipLaunchKernelGGL((k_wgrad_acc<MT, NT>), dim3((unsigned)grid), dim3(256), lds_bytes, s, X, (uint32_t)(ldx * 4), (int)F, G, (uint32_t)(ldg * 4), (int)O,
-                       (uint32_t)n, (uint32_t)rows_per_wave, (uint32_t)f_panels, (uint32_t)panels, work);
+    hipLaunchKernelGGL((k_wgrad_acc<MT, NT, DROP>), dim3((unsigned)grid), dim3(256), lds_bytes, s, X, (uint32_t)(ldx * 4), (int)F, G, (uint32_t)(ldg * 4), (int)O,
+                       (uint32_t)n, (uint32_t)rows_per_wave, (uint32_t)f_panels, (uint32_t)panels, work, mask);
     *n_slabs = waves;
     return GNX_OK;
 }
@@ -239,8 +268,9 @@ int launch_wgrad_acc(const float *X, int64_t ldx, int64_t F, const float *G, int
 // Whole aligned rows, F and O multiples of 4: the result is cut into panels of FP features x OP outputs, FP x OP <= 16384, each of which
 // one wave holds (OP = 32 / 64 / 128 >= O where that exists; FP = 16384 / OP, at most 256, narrower for narrow inputs); widths that
 // are not a power of two are padded inside the LDS image.  GNX_OK: launched; < 0: not taken, the panel kernel runs.
+template <bool DROP>
 int wgrad_acc_dispatch(const float *X, int64_t ldx, const float *G, int64_t ldg, int64_t n, int64_t F, int64_t O, bool aligned, float *work,
-                       int64_t max_slabs, int64_t *n_slabs, hipStream_t s) {
+                       int64_t max_slabs, int64_t *n_slabs, const WgradMask<DROP> &mask, hipStream_t s) {
     if (!aligned || n < 16 * 1024 || n >= (1ll << 31) || ldx >= (1ll << 30) || ldg >= (1ll << 30) || F % 4 || O % 4 || F * O >= (1ll << 31) || max_slabs < 64)
         return -1;
     const int op = O <= 32 ? 32 : O <= 64 ? 64 : 128;
@@ -248,7 +278,7 @@ int wgrad_acc_dispatch(const float *X, int64_t ldx, const float *G, int64_t ldg,
     while (fp > 32 && fp / 2 >= F) fp /= 2;                                   // a narrow input does not need the widest panel
     const int64_t panels = ((F + fp - 1) / fp) * ((O + op - 1) / op);
     if (panels > 64) return -1;                                                // (very wide layers: every slab would be walked too often)
-#define GNX_WGRAD_ACC(MT_, NT_) if (fp == 16 * MT_ && op == 16 * NT_) return launch_wgrad_acc<MT_, NT_>(X, ldx, F, G, ldg, O, n, work, max_slabs, n_slabs, s)
+#define GNX_WGRAD_ACC(MT_, NT_) if (fp == 16 * MT_ && op == 16 * NT_) return launch_wgrad_acc<MT_, NT_, DROP>(X, ldx, F, G, ldg, O, n, work, max_slabs, n_slabs, mask, s)
     GNX_WGRAD_ACC(2, 2); GNX_WGRAD_ACC(2, 4); GNX_WGRAD_ACC(2, 8);
     GNX_WGRAD_ACC(4, 2); GNX_WGRAD_ACC(4, 4); GNX_WGRAD_ACC(4, 8);
     GNX_WGRAD_ACC(8, 2); GNX_WGRAD_ACC(8, 4); GNX_WGRAD_ACC(8, 8);
@@ -279,23 +309,33 @@ void sum_slabs(const float *partial, int64_t n_slabs, int64_t elems, float *out,
 
 }  // namespace gnx
 
-extern "C" {
+namespace {
 
-int gnx_dense_wgrad(const float *d_X, int64_t ldx, const float *d_G, int64_t ldg, int64_t n, int64_t F, int64_t O, float *d_dW,
-                    float *d_work, int64_t work_floats, void *stream) {
-    GNX_CHECK_ARG(n >= 0 && F >= 1 && O >= 1 && F <= (1 << 20) && O <= (1 << 20), "gnx_dense_wgrad: bad sizes");
-    GNX_CHECK_ARG(ldx >= F && ldg >= O, "gnx_dense_wgrad: leading dimension smaller than the row");
-    GNX_CHECK_ARG(d_dW != nullptr, "gnx_dense_wgrad: NULL output");
+// what gnx_dense_wgrad and gnx_dense_wgrad_drop check before anything is read or launched
+int check_wgrad_args(const char *fn, const float *d_X, int64_t ldx, const float *d_G, int64_t ldg, int64_t n, int64_t F, int64_t O, float *d_dW,
+                     float *d_work, int64_t work_floats) {
+    GNX_CHECK_ARG(n >= 0 && F >= 1 && O >= 1 && F <= (1 << 20) && O <= (1 << 20), "%s: bad sizes", fn);
+    GNX_CHECK_ARG(ldx >= F && ldg >= O, "%s: leading dimension smaller than the row", fn);
+    GNX_CHECK_ARG(d_dW != nullptr, "%s: NULL output", fn);
+    if (n == 0) return GNX_OK;
+    GNX_CHECK_ARG(d_X && d_G, "%s: NULL input", fn);
+    GNX_CHECK_ARG(d_work != nullptr && work_floats / (F * O) >= 1, "%s: the scratch must hold at least F * O floats", fn);
+    return GNX_OK;
+}
+
+// gnx_dense_wgrad and gnx_dense_wgrad_drop (DROP: X under `mask`) behind their checks: one host path -- the same slabs, wave -> slab
+// assignment and summation order
+template <bool DROP>
+int dense_wgrad(const float *d_X, int64_t ldx, const float *d_G, int64_t ldg, int64_t n, int64_t F, int64_t O, float *d_dW,
+                float *d_work, int64_t work_floats, const WgradMask<DROP> &mask, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) {
         GNX_HIP(hipMemsetAsync(d_dW, 0, (size_t)F * O * sizeof(float), s));
         return GNX_OK;
     }
-    GNX_CHECK_ARG(d_X && d_G, "gnx_dense_wgrad: NULL input");
     // row slabs: as many as the scratch holds (each slab leaves an F x O partial), at least 256 rows each, at most 2048 slabs
     const int64_t fo = F * O;
     int64_t max_slabs = work_floats / fo;
-    GNX_CHECK_ARG(d_work != nullptr && max_slabs >= 1, "gnx_dense_wgrad: the scratch must hold at least F * O floats");
     if (max_slabs > 2048) max_slabs = 2048;
     int64_t rows_per_slab = (n + max_slabs - 1) / max_slabs;
     if (rows_per_slab < 256) rows_per_slab = 256;
@@ -304,7 +344,7 @@ int gnx_dense_wgrad(const float *d_X, int64_t ldx, const float *d_G, int64_t ldg
     const bool al = ldx % 4 == 0 && ldg % 4 == 0 && aligned(d_X, 16) && aligned(d_G, 16);
     int64_t waves = 0;                                // k_wgrad_acc's slabs  (tuning builds: GNX_WGRAD_ACC=0 keeps the panel kernel)
     if (tuning_switch("GNX_WGRAD_ACC") && aligned(d_work, 16) &&
-        wgrad_acc_dispatch(d_X, ldx, d_G, ldg, n, F, O, al, d_work, max_slabs, &waves, s) == GNX_OK) {
+        wgrad_acc_dispatch<DROP>(d_X, ldx, d_G, ldg, n, F, O, al, d_work, max_slabs, &waves, mask, s) == GNX_OK) {
         // the waves' partials, added in wave order: in groups of 32 first when the scratch has room for the group sums (a sum over a
         // thousand slabs of a few thousand elements is otherwise a launch of a few blocks walking a long chain each)
         const int64_t per = 32, groups = (waves + per - 1) / per;
@@ -319,13 +359,39 @@ int gnx_dense_wgrad(const float *d_X, int64_t ldx, const float *d_G, int64_t ldg
         const int nt_all = (int)((O + 15) / 16);
         const int NTsel = nt_all >= 4 ? 4 : (nt_all >= 2 ? 2 : 1);
         dim3 grid((unsigned)n_slabs, (unsigned)((F + 255) / 256), (unsigned)((nt_all + NTsel - 1) / NTsel));
-        if (NTsel == 4)      hipLaunchKernelGGL(k_wgrad_mfma<4>, grid, dim3(256), 0, s, d_X, ldx, d_G, ldg, n, (int)F, (int)O, rows_per_slab, al, d_work);
-        else if (NTsel == 2) hipLaunchKernelGGL(k_wgrad_mfma<2>, grid, dim3(256), 0, s, d_X, ldx, d_G, ldg, n, (int)F, (int)O, rows_per_slab, al, d_work);
-        else                 hipLaunchKernelGGL(k_wgrad_mfma<1>, grid, dim3(256), 0, s, d_X, ldx, d_G, ldg, n, (int)F, (int)O, rows_per_slab, al, d_work);
+        if (NTsel == 4)      hipLaunchKernelGGL((k_wgrad_mfma<4, DROP>), grid, dim3(256), 0, s, d_X, ldx, d_G, ldg, n, (int)F, (int)O, rows_per_slab, al, d_work, mask);
+        else if (NTsel == 2) hipLaunchKernelGGL((k_wgrad_mfma<2, DROP>), grid, dim3(256), 0, s, d_X, ldx, d_G, ldg, n, (int)F, (int)O, rows_per_slab, al, d_work, mask);
+        else                 hipLaunchKernelGGL((k_wgrad_mfma<1, DROP>), grid, dim3(256), 0, s, d_X, ldx, d_G, ldg, n, (int)F, (int)O, rows_per_slab, al, d_work, mask);
         sum_slabs(d_work, n_slabs, fo, d_dW, s);
     }
     GNX_HIP(hipGetLastError());
     return GNX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gnx_dense_wgrad(const float *d_X, int64_t ldx, const float *d_G, int64_t ldg, int64_t n, int64_t F, int64_t O, float *d_dW,
+                    float *d_work, int64_t work_floats, void *stream) {
+    const int rc = check_wgrad_args("gnx_dense_wgrad", d_X, ldx, d_G, ldg, n, F, O, d_dW, d_work, work_floats);
+    if (rc != GNX_OK) return rc;
+    return dense_wgrad<false>(d_X, ldx, d_G, ldg, n, F, O, d_dW, d_work, work_floats, WgradMask<false>{}, stream);
+}
+
+int gnx_dense_wgrad_drop(gnx_graph_t g, const float *d_X, int64_t ldx, const float *d_G, int64_t ldg, int64_t n, int64_t F, int64_t O,
+                         double in_p, uint64_t in_seed, uint64_t in_stream, float *d_dW, float *d_work, int64_t work_floats, void *stream) {
+    // (the handle is read -- for its dropout counter -- only once every other argument has passed)
+    GNX_CHECK_ARG(g != nullptr, "gnx_dense_wgrad_drop: NULL handle");
+    GNX_CHECK_ARG(in_p >= 0.0 && in_p < 1.0, "gnx_dense_wgrad_drop: dropout rate %g outside [0, 1)", in_p);
+    int rc = check_wgrad_args("gnx_dense_wgrad_drop", d_X, ldx, d_G, ldg, n, F, O, d_dW, d_work, work_floats);
+    if (rc != GNX_OK) return rc;
+    WgradMask<true> mask{};
+    rc = make_feat_drop("gnx_dense_wgrad_drop", g, in_p, in_seed, in_stream, mask.din);
+    if (rc != GNX_OK) return rc;
+    if (mask.din.thr == 0)                           // no mask: the plain gradient, nothing hashed
+        return dense_wgrad<false>(d_X, ldx, d_G, ldg, n, F, O, d_dW, d_work, work_floats, WgradMask<false>{}, stream);
+    return dense_wgrad<true>(d_X, ldx, d_G, ldg, n, F, O, d_dW, d_work, work_floats, mask, stream);
 }
 
 }  // extern "C"

@@ -163,6 +163,10 @@ SIGNATURES = {
     "gnx_dense": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int64,
                           c_void_p]),
     "gnx_dense_wgrad": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "gnx_dense_drop": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_double, c_uint64,
+                               c_uint64, c_double, c_uint64, c_uint64, c_void_p, c_int64, c_void_p]),
+    "gnx_dense_wgrad_drop": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_double, c_uint64, c_uint64,
+                                     c_void_p, c_void_p, c_int64, c_void_p]),
     "gnx_node_ce": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "gnx_node_ce_backward": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
                                      c_void_p]),
@@ -189,7 +193,8 @@ SIGNATURES = {
 }
 
 # entries added within ABI 0.9 that a library of the same minor version may lack: found by probing (has_symbol); their callers raise
-PROBED = ("gnx_step_wide_ngcf", "gnx_step_back_wide_ngcf", "gnx_step_spectral_gcn", "gnx_step_spectral_gcn_dropped")
+PROBED = ("gnx_step_wide_ngcf", "gnx_step_back_wide_ngcf", "gnx_step_spectral_gcn", "gnx_step_spectral_gcn_dropped", "gnx_dense_drop",
+          "gnx_dense_wgrad_drop")
 
 _lib = None
 

@@ -39,8 +39,19 @@ def affine(features, W, b, activation=linear):
     return out if fused_act else activation(out)
 
 
+def fused_dense_dropout(architecture, features, rate) -> bool:
+    """Whether GNN(dense_dropout="fused") applies to a dropout of ``rate`` over ``features`` in this forward (no tensor is read, no mask
+    stream is drawn): a model with the keyword and a graph handle (whose dropout counter the masks read) in training mode, float32
+    device rows, a rate in (0, 1)."""
+    return (getattr(architecture, "dense_dropout", "torch") == "fused" and isinstance(getattr(architecture, "graph", None), sparse.DeviceGraph)
+            and architecture.is_training() and isinstance(features, torch.Tensor) and features.is_cuda and features.dtype == torch.float32
+            and features.dim() == 2 and isinstance(rate, (int, float)) and not isinstance(rate, bool) and 0 < rate < 1)
+
+
 class Dense(Layer):
-    """layers.py:125-136: dropout(activation(X.W + b))."""
+    """layers.py:125-136: dropout(activation(X.W + b)).
+    On a GNN with ``dense_dropout="fused"`` the layer's training-mode dropout is the counter RNG's and leaves the dense kernel's launch
+    (sparse.dense_step); behind a Dropout layer the pair runs as one launch (Dropout.__run__; the conditions: GNN.__init__)."""
 
     def __build__(self, architecture: Layered, outputs: int = None, activation=linear, bias: bool = True,
                   dropout: float = 0, regularize: bool = True):
@@ -52,19 +63,65 @@ class Dense(Layer):
         self.dropout = dropout
         return (architecture.top_shape()[0], outputs)
 
+    def _fusable(self) -> bool:
+        """Whether sparse.dense_step can run this layer: the class itself, relu or the identity in the kernel's epilogue."""
+        return type(self) is Dense and (self.activation is relu or self.activation is linear)
+
+    def _step(self, architecture, features, in_triple):
+        """The layer through sparse.dense_step: ``in_triple`` = the mask of a Dropout layer in front (or None), the layer's own dropout
+        as the output mask where GNN(dense_dropout="fused") applies to it -- its stream drawn here, after the Dropout's -- else
+        ``architecture.dropout`` behind the launch, as today."""
+        own = fused_dense_dropout(architecture, features, self.dropout)
+        out_triple = (self.dropout,) + tuple(architecture._next_mask_stream()) if own else None
+        out = sparse.dense_step(architecture.graph, features, self.W, self.b if isinstance(self.b, torch.Tensor) else None,
+                                relu=self.activation is relu, in_dropout=in_triple, out_dropout=out_triple)
+        return out if own else architecture.dropout(out, self.dropout)
+
     def __forward__(self, architecture: Layered, features):
+        if self._fusable() and fused_dense_dropout(architecture, features, self.dropout):
+            return self._step(architecture, features, None)       # GNN(dense_dropout="fused"): the mask leaves the dense launch
         return architecture.dropout(affine(features, self.W, self.b, self.activation), self.dropout)
 
 
 class Dropout(Layer):
-    """layers.py:175-181."""
+    """layers.py:175-181.
+    On a GNN with ``dense_dropout="fused"`` the training-mode mask is the counter RNG's (sparse.feature_dropout), and a Dropout directly
+    followed by a Dense executes with it as ONE launch (sparse.dense_step through __run__): the mask is applied where the dense kernel
+    picks up its rows, no dropped copy of the features exists, and this layer's ``.value`` is made when somebody reads it -- the same
+    triple, hence the same bits the launch consumed.  ``architecture.fuse_runs = False`` keeps the two layers apart (each still with
+    the counter RNG's mask)."""
 
     def __build__(self, gcn, rate: float = 0.5):
         self.rate = rate
         return gcn.top_shape()
 
     def __forward__(self, gcn, features):
+        if type(self) is Dropout and fused_dense_dropout(gcn, features, self.rate):
+            return sparse.feature_dropout(gcn.graph, features, self.rate, *gcn._next_mask_stream())
         return gcn.dropout(features, self.rate)
+
+    # ``.value`` (layered.py:79-81) may be pending after a fused pair: computed on first read
+    @property
+    def value(self):
+        pending = self.__dict__.get("_pending_value")
+        if pending is not None:
+            self.__dict__["_value"], self.__dict__["_pending_value"] = pending(), None
+        return self.__dict__.get("_value")
+
+    @value.setter
+    def value(self, v):
+        self.__dict__["_value"], self.__dict__["_pending_value"] = v, None
+
+    def __run__(self, gcn, features, stack, at):
+        follower = stack[at + 1] if at + 1 < len(stack) else None
+        if not (type(self) is Dropout and fused_dense_dropout(gcn, features, self.rate) and isinstance(follower, Dense)
+                and follower._fusable() and follower is not self and self.output_regularize == 0):
+            return None
+        graph, triple = gcn.graph, (self.rate,) + tuple(gcn._next_mask_stream())
+        out = follower._step(gcn, features, triple)
+        self.__dict__["_value"], self.__dict__["_pending_value"] = None, (lambda: sparse.feature_dropout(graph, features, *triple))
+        follower.value = out
+        return 2, out
 
 
 def _scalar(architecture, init="zero"):

@@ -53,7 +53,8 @@ class GNN(Trainable):
                  training_dtype=torch.float32, train_gather_order="auto", gcnii_backward="composed", feature_dropout="torch",
                  gcnii_training_dtype=torch.float32, gcnii_weight_gradient="stored", gcnii_spectral="composed",
                  gcnii_edge_dropout="composed", gcn_layer="composed", gcn_backward="composed", ngcf_layer="composed",
-                 ngcf_backward="composed", ngcf_wide="composed", ngcf_wide_backward="composed", gcn_spectral="composed"):
+                 ngcf_backward="composed", ngcf_wide="composed", ngcf_wide_backward="composed", gcn_spectral="composed",
+                 dense_dropout="torch"):
         """``reorder`` (opt-in, not in the reference): store the graph and the feature rows with the vertices relabelled; every
         [N, .] tensor inside the model then lives in that order, and the model's OUTPUT is put back into the caller's order, so
         tasks, labels and node ids are unaffected.  Results agree with the unordered model to float32 rounding.
@@ -240,7 +241,27 @@ class GNN(Trainable):
         The eval-mode result agrees with the composed one to float32 rounding.  GCNLayer and ``gcn_layer="fused"`` (which keeps
         ignoring this class), other subclasses, ``transform_first``, other activations, other widths, a rate of 1 or more, add_eye, CPU
         tensors and the vertex-partitioned path keep today's path and bits whatever it says (measurement: profiles/NOTES.md "Fused
-        spectral-preserving GCN layer")."""
+        spectral-preserving GCN layer").
+        ``dense_dropout`` (not in the reference): ``"torch"`` (the default: torch.nn.functional.dropout behind every Dense and in every
+        Dropout layer, today's calls and bits) or ``"fused"`` (sparse.dense_step).  A keyword of its own: ``feature_dropout="fused"``
+        keeps leaving these layers to torch.  ``"fused"`` acts in training mode on Dropout and Dense layers (the classes themselves) over
+        float32 device rows, for rates in (0, 1) and relu or the identity as the Dense's activation.  A Dropout directly followed by a
+        Dense -- the front of APPNP (filter.py:30-33) and of GCNII (gcn.py:68-70) -- executes as ONE launch of the dense kernels
+        (gnx_dense_drop): the mask is applied to a row's values as the matrix cores pick them up, the Dense's own dropout in the
+        epilogue, and neither a dropped copy of the feature matrix nor a mask is written; the backward makes the input mask again
+        inside the weight-gradient kernels (gnx_dense_wgrad_drop) and saves the feature matrix itself.  The Dropout layer's ``.value``
+        is made on first read (sparse.feature_dropout with the same triple: the bits the launch consumed).  A Dense with a rate and no
+        Dropout in front runs the same launch with its output mask alone; a Dropout followed by anything else is the pass
+        sparse.feature_dropout.  The masks are the COUNTER RNG's, not torch's: element (i, c) of a layer's ``_next_mask_stream()``
+        stream -- drawn in layer order, the Dropout's, then the Dense's -- is kept iff hash_u24(seed, stream, i, c, 0) >= int(p * 2^24),
+        kept values times the f32 1 / (1 - p); that is why the switch is opt-in.  Every mask of an APPNP or GCNII training step (with
+        ``feature_dropout="fused"`` for the GCNII layers) is then the counter RNG's: a step is reproducible from its seed and
+        ``train(capture=True)`` equals the eager run.  Eval mode, SparseRows features (they have masks of their own), CPU tensors, a
+        Layered without a graph handle (MLP), other activations, subclasses, rates of 0 and of 1 or more, and the vertex-partitioned
+        path keep today's path and bits whatever it says; ``fuse_runs = False`` keeps the layers apart, each with the counter RNG's pass
+        (measurement: profiles/NOTES.md "Fused dropout around Dense")."""
+        if dense_dropout not in sparse.DENSE_DROPOUTS:
+            raise Exception("GNN: dense_dropout must be one of " + ", ".join(repr(d) for d in sparse.DENSE_DROPOUTS))
         if gcn_spectral not in sparse.GCN_SPECTRALS:
             raise Exception("GNN: gcn_spectral must be one of " + ", ".join(repr(f) for f in sparse.GCN_SPECTRALS))
         if ngcf_layer not in sparse.NGCF_LAYERS:
@@ -290,6 +311,7 @@ class GNN(Trainable):
         self.ngcf_wide = ngcf_wide
         self.ngcf_wide_backward = ngcf_wide_backward
         self.gcn_spectral = gcn_spectral
+        self.dense_dropout = dense_dropout
         self._order = self._newid = None
         self.reorder_used, self.locality_share = None, None
         if isinstance(graph, sparse.DeviceGraph):

@@ -1220,6 +1220,91 @@ def _gated_gradient(graph: DeviceGraph, g, out, relu, dropout):
     return (_relu_mask(g, out) if relu else g).contiguous()
 
 
+DENSE_DROPOUTS = ("torch", "fused")
+
+
+def _dense_drop_launch(graph: DeviceGraph, X, W, bias, relu, din, dout):
+    """gnx_dense_drop: drop_out(act(drop_in(X) . W + bias)) in the dense kernels' launch; ``din`` / ``dout`` = checked triples or None."""
+    _need_symbol("dense_step", "gnx_dense_drop")
+    nat.require_cuda(X, W, bias)
+    _same_device(graph, X, W, bias)
+    if X.shape[1] != W.shape[0]:
+        raise Exception(f"dense_step: features have {X.shape[1]} columns, the weights expect {W.shape[0]}")
+    out = torch.empty((X.shape[0], W.shape[1]), dtype=torch.float32, device=X.device)
+    b = None if bias is None else bias.to(torch.float32).reshape(-1).contiguous()
+    if b is not None and b.numel() != W.shape[1]:
+        raise Exception("dense_step: bias width mismatch")
+    with nat.on_device(X.device):
+        nat.check(nat.lib().gnx_dense_drop(graph.handle, nat.ptr(X), X.stride(0), X.shape[0], X.shape[1], nat.ptr(W), W.stride(0), W.shape[1],
+                                           nat.ptr(b), nat.ACT_RELU if relu else nat.ACT_NONE, *_dropout_args(din), *_dropout_args(dout),
+                                           nat.ptr(out), out.stride(0), nat.current_stream()))
+    return out
+
+
+def _dense_wgrad_drop(graph: DeviceGraph, X, G, din):
+    """dW = drop_in(X)^T . G with the mask made again in the weight-gradient kernels (gnx_dense_wgrad_drop): _dense_wgrad's slabs and
+    summation order, no dropped copy of X.  ``din`` None: _dense_wgrad itself."""
+    if din is None:
+        return _dense_wgrad(X, G)
+    _need_symbol("dense_step", "gnx_dense_wgrad_drop")
+    X, G = _as_f32_rows(X), _as_f32_rows(G)
+    _same_device(graph, X, G)
+    n, F = X.shape
+    O = G.shape[1]
+    slabs = max(1, min(2048, (n + 255) // 256, (1 << 28) // max(F * O, 1)))        # _dense_wgrad's scratch: the same slabs, the same bits
+    work = torch.empty(slabs * F * O, dtype=torch.float32, device=X.device)
+    dW = torch.empty((F, O), dtype=torch.float32, device=X.device)
+    with nat.on_device(X.device):
+        nat.check(nat.lib().gnx_dense_wgrad_drop(graph.handle, nat.ptr(X), X.stride(0), nat.ptr(G), G.stride(0), n, F, O, *din, nat.ptr(dW),
+                                                 nat.ptr(work), work.numel(), nat.current_stream()))
+    return dW
+
+
+class _DenseStep(torch.autograd.Function):
+    """out = drop_out(act(drop_in(X) . W + b)) as one launch (gnx_dense_drop).  Saves (X, W, out): X is the caller's tensor, no dropped
+    copy and no mask exist.  backward: G' = the gate over out (gnx_feature_dropout_back: output mask, scale and relu in one pass; the
+    relu mask without an output dropout); dW = drop_in(X)^T . G' with the mask made again (gnx_dense_wgrad_drop); db = column sums;
+    dX, where wanted, = drop_in's backward over G' . W^T (gnx_dense, then gnx_feature_dropout_back with the input triple)."""
+
+    @staticmethod
+    def forward(ctx, X, W, bias, graph, relu, din, dout):
+        out = _dense_drop_launch(graph, X, W, bias, relu, din, dout)
+        ctx.graph, ctx.relu, ctx.din, ctx.dout = graph, relu, din, dout
+        ctx.has_bias, ctx.bias_shape = bias is not None, None if bias is None else tuple(bias.shape)
+        ctx.save_for_backward(X, W, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        X, W, out = ctx.saved_tensors
+        G = _gated_gradient(ctx.graph, g, out, ctx.relu, ctx.dout)
+        gW = _dense_wgrad_drop(ctx.graph, X, G, ctx.din) if ctx.needs_input_grad[1] else None
+        gb = G.sum(dim=0).reshape(ctx.bias_shape) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        gX = None
+        if ctx.needs_input_grad[0]:
+            gX = _dense_launch(G, W.t().contiguous(), None, False)
+            if ctx.din is not None:
+                gX = _feature_dropout_back(ctx.graph, gX, None, *ctx.din, relu=False)
+        return gX, gW, gb, None, None, None, None
+
+
+def dense_step(graph: DeviceGraph, X: torch.Tensor, W: torch.Tensor, bias=None, relu=False, in_dropout=None, out_dropout=None) -> torch.Tensor:
+    """drop_out(act(drop_in(X) . W + bias)) -- a Dropout layer, a Dense layer and the Dense's own dropout (layers.py:125-136, 175-181;
+    filter.py:30-33) -- as ONE launch of the dense kernels (gnx_dense_drop) and one autograd node.  ``in_dropout`` / ``out_dropout`` =
+    ``(p, seed, stream)`` or None, as ``gcnii_step(dropout=)`` takes them: the masks are ``feature_dropout``'s -- element (i, c) is
+    kept iff hash_u24(seed, stream + counter, i, c, 0) >= int(p * 2^24), kept values times the f32 1 / (1 - p) -- made where the
+    kernels pick up a row of X and where they finish a row of the result, so the result is bit for bit
+    ``feature_dropout(dense(feature_dropout(X, in), W, bias, relu), out)`` while no dropped copy of X and no mask reach memory.  The node
+    saves X itself, W and the result; its weight gradient makes the input mask again (gnx_dense_wgrad_drop).  ``graph`` lends its
+    dropout counter and is otherwise not read.  Without either triple (or with rates of 0) it is ``dense``.  float32 device tensors."""
+    din, dout = _dropout_triple(in_dropout, "dense_step"), _dropout_triple(out_dropout, "dense_step")
+    if din is None and dout is None:
+        return dense(X, W, bias, relu)
+    nat.require_cuda(X, W, bias)
+    X, W = _as_f32_rows(X), _as_f32_rows(W)
+    return _DenseStep.apply(X, W, bias, graph, bool(relu), din, dout)
+
+
 def _gcnii_input_grads(adj, G, a, M, want_H, want_H0, fused_backward, fused_edge=False):
     """(dH, dH0) of a GCNII layer from its gated gradient ``G``; None where not wanted.  ``fused_backward``: one launch
     (gcnii_step_back: dH = ((1-a) A^T G) M^T, dH0 = (a G) M^T -- it always makes dH; a caller that wants dH0 alone is not what a GCNII

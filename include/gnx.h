@@ -996,6 +996,29 @@ int gnx_dense(const float *d_X, int64_t ldx, int64_t n, int64_t F, const float *
 int gnx_dense_wgrad(const float *d_X, int64_t ldx, const float *d_G, int64_t ldg, int64_t n, int64_t F, int64_t O, float *d_dW,
                     float *d_work, int64_t work_floats, void *stream);
 
+/* Feature dropout around the dense transform, made inside its launches (opt-in; added within ABI 0.9 -- probe for the symbols):
+ * layers.py:135-136 behind a Dropout layer (filter.py:30-33), out = drop_out(act(drop_in(X) . W + bias)), without a dropped copy of X,
+ * a mask in memory or a pass of its own.  Both masks are the one of gnx_feature_dropout (above): element (i, c) of a side with rate
+ * 0 <= p < 1 and (seed, stream_id) is KEPT iff hash_u24(seed, stream_id + counter, i, c, 0) >= (uint32_t)(p * 2^24), i the row, c the
+ * column of X (input side) or of the WHOLE result (output side: column panels past the first are keyed by their global column), counter
+ * the handle's dropout counter; drop(v) = kept ? v * s : +0.0f, s = 1.0f / (1.0f - (float)p).  The handle is read for its dropout counter
+ * only: any handle will do.  A rate of 0 on a side hashes nothing there; both 0 is gnx_dense itself.
+ *
+ * gnx_dense_drop: the argument list and checks of gnx_dense plus the handle and the two triples; no row maps.  Rounding points, per
+ * element: x' = fl(x * s_in) for a kept x (+0 for a dropped one), made as a lane picks up its four consecutive floats of a row for the
+ * matrix cores; the k-ascending fmaf chain of gnx_dense over x' (whichever kernel carries the shape: the same order, the same bits);
+ * + bias; relu; then fl(v * s_out) for a kept v, +0 for a dropped one.  Bit for bit
+ *   gnx_feature_dropout(in) -> gnx_dense -> gnx_feature_dropout(out, in place).
+ *
+ * gnx_dense_wgrad_drop: dW = drop_in(X)^T . G, the argument list and checks of gnx_dense_wgrad plus the handle and the input triple; the
+ * mask is made again from the triple as the rows of X are picked up (x' = fl(x * s_in) or +0, as above), the slabs, their assignment and
+ * the summation order are those of gnx_dense_wgrad: bit for bit that entry over a materialised drop_in(X). */
+int gnx_dense_drop(gnx_graph_t g, const float *d_X, int64_t ldx, int64_t n, int64_t F, const float *d_W, int64_t ldw, int64_t O,
+                   const float *d_bias, int act, double in_p, uint64_t in_seed, uint64_t in_stream, double out_p, uint64_t out_seed,
+                   uint64_t out_stream, float *d_out, int64_t ldo, void *stream);
+int gnx_dense_wgrad_drop(gnx_graph_t g, const float *d_X, int64_t ldx, const float *d_G, int64_t ldg, int64_t n, int64_t F, int64_t O,
+                         double in_p, uint64_t in_seed, uint64_t in_stream, float *d_dW, float *d_work, int64_t work_floats, void *stream);
+
 /* The task head, NodeClassification (gnntf/core/gnn/graph_predictor.py:16-31), fused over the listed nodes.  All three are
  * stream-ordered and allocation-free (no synchronisation: they sit in the per-epoch loop of small graphs); node ids / labels
  * out of range are never dereferenced -- such an item's loss is NaN (and so is the mean), its argmax -1, its gradient zero.
