@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import graphs
+from model_step_ref import FixedMasks, counter_mask
 from oracle import gnntf_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -18,28 +19,11 @@ def gnntf():
     gnntf.set_default_device(None)
 
 
-class FixedMasks:
-    """Feature-dropout masks drawn once on the host, handed out in call order: the same masks drive the HIP model
-    (patched into Layered.dropout) and the dense reference, so the two computations are comparable bit for bit."""
-
-    def __init__(self, seed):
-        self.rng, self.masks, self.cursor = np.random.default_rng(seed), [], 0
-
-    def mask(self, shape, p):
-        if self.cursor == len(self.masks):
-            self.masks.append((self.rng.random(shape) >= p).astype(np.float64) / (1.0 - p))
-        m = self.masks[self.cursor]
-        self.cursor += 1
-        return m
-
-    def rewind(self):
-        self.cursor = 0
-
-
-@pytest.mark.parametrize("fused", [False, True])
-def test_whole_model_training_step_matches_dense_float64(gnntf, fused):
+def whole_model_training_step(gnntf, monkeypatch, fused, dense_dropout):
     """trainable.py:69-79: training-mode forward (input Dropout 0.5, Dense(relu, dropout 0.6), Dense, K x PPRIteration with
-    per-iteration edge dropout 0.5 + renormalisation), CE + L2, backward: compare loss, dW1, db1, dW2, db2."""
+    per-iteration edge dropout 0.5 + renormalisation), CE + L2, backward: compare loss, dW1, db1, dW2, db2.
+    ``dense_dropout="fused"``: the two feature masks are the counter RNG's and leave the dense launch (gnx_dense_drop); they take the
+    step's first two streams -- the Dropout's, then the Dense's --, the K adjacencies the streams after them."""
     n, F, hidden, classes, K, a, wd = 600, 40, 16, 5, 10, 0.1, 5e-4
     coo, vals, shape = graphs.rmat_symmetric_coo(n, 4000, seed=3)
     coo = np.concatenate([coo, coo[:300]])                                        # stored duplicates: dropout acts per stored entry
@@ -49,7 +33,8 @@ def test_whole_model_training_step_matches_dense_float64(gnntf, fused):
     labels = rng.integers(0, classes, size=n)
     train = np.arange(0, 200)
     gnntf.set_seed(17)
-    model = gnntf.APPNP(gnntf.SparseCOO(coo, vals, shape), X, num_classes=classes, latent_dims=[hidden], iterations=K, a=a, fused=fused)
+    model = gnntf.APPNP(gnntf.SparseCOO(coo, vals, shape), X, num_classes=classes, latent_dims=[hidden], iterations=K, a=a, fused=fused,
+                        dense_dropout=dense_dropout)
     model.reset()
     dense = [l for l in model.layers() if isinstance(l, gnntf.Dense)]
     params = [dense[0].W, dense[0].b, dense[1].W, dense[1].b]
@@ -63,17 +48,30 @@ def test_whole_model_training_step_matches_dense_float64(gnntf, fused):
     from gnntf.training import _Objective
     from gnntf import metrics
     seed, first_stream = metrics.current_seed(), model._mask_calls
+    nat = gnntf.sparse.nat
+    asked, real = set(), nat.lib()
+    spy = type("Spy", (), {"__getattr__": lambda self, name: (asked.add(name), getattr(real, name))[1]})()
+    monkeypatch.setattr(nat, "lib", lambda: spy)
     with model:
         loss = _Objective(model, task, wd)()
         loss.backward()
+    # the switch ran its launches (and the default none of them): a fall-back would pass as the composed path
+    assert ("gnx_dense_drop" in asked) == ("gnx_dense_wgrad_drop" in asked) == (dense_dropout == "fused")
+    if dense_dropout == "fused":                        # the counter RNG's masks, in layer order, ahead of the adjacencies' streams
+        streams = iter((first_stream, first_stream + 1))
+        first_stream += 2
+        feature_mask = lambda shape, p: counter_mask(shape, p, seed, next(streams))
+    else:
+        feature_mask = masks.mask
+    assert model._mask_calls == first_stream + K
     got = [float(loss)] + [p.grad.cpu().numpy().astype(np.float64) for p in params]
 
     # ---- the same step in dense float64 on the CPU -------------------------------------------------------------------------
     masks.rewind()
     W1, b1, W2, b2 = [torch.tensor(p.detach().cpu().numpy().astype(np.float64), requires_grad=True) for p in params]
-    H = torch.from_numpy(X.astype(np.float64)) * torch.from_numpy(masks.mask((n, F), 0.5))              # Dropout(0.5), filter.py:30
+    H = torch.from_numpy(X.astype(np.float64)) * torch.from_numpy(feature_mask((n, F), 0.5))            # Dropout(0.5), filter.py:30
     H = torch.relu(H @ W1 + b1)
-    H = H * torch.from_numpy(masks.mask((n, hidden), 0.6))                                              # Dense(..., dropout=0.6), filter.py:31-32
+    H = H * torch.from_numpy(feature_mask((n, hidden), 0.6))                                            # Dense(..., dropout=0.6), filter.py:31-32
     H0 = H @ W2 + b2                                                                                    # Dense(num_classes) has dropout 0, filter.py:33
     Hk = H0
     for k in range(K):                                                                                  # filter.py:17-22, a fresh adjacency per iteration
@@ -90,6 +88,16 @@ def test_whole_model_training_step_matches_dense_float64(gnntf, fused):
         scale = np.abs(w_).max()
         np.testing.assert_allclose(g_, w_, rtol=1e-3, atol=2e-5 * scale, err_msg=name)
     assert np.abs(want[1]).max() > 1e-4 and np.abs(want[3]).max() > 1e-4                                # the gradients are not trivially zero
+
+
+@pytest.mark.parametrize("fused", [False, True])
+def test_whole_model_training_step_matches_dense_float64(gnntf, monkeypatch, fused):
+    whole_model_training_step(gnntf, monkeypatch, fused, "torch")
+
+
+@pytest.mark.parametrize("fused", [False, True])
+def test_whole_model_training_step_with_fused_dense_dropout(gnntf, monkeypatch, fused):
+    whole_model_training_step(gnntf, monkeypatch, fused, "fused")
 
 
 def test_captured_training_equals_eager(gnntf):
