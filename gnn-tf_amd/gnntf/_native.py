@@ -185,6 +185,12 @@ SIGNATURES = {
     "gnx_rank_candidates": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
                                     c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "gnx_signal_project": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
+    "gnx_signal_spmv": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p]),
+    "gnx_signal_ppr": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p]),
+    "gnx_signal_smoothness": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gnx_signal_smoothness_back": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gnx_signal_uniform": (c_int, [c_void_p, c_int64, c_float, c_uint64, c_uint64, c_void_p, c_void_p]),
     "gnx_linear_combination": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "gnx_stream_read": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "gnx_stream_copy": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
@@ -194,7 +200,8 @@ SIGNATURES = {
 
 # entries added within ABI 0.9 that a library of the same minor version may lack: found by probing (has_symbol); their callers raise
 PROBED = ("gnx_step_wide_ngcf", "gnx_step_back_wide_ngcf", "gnx_step_spectral_gcn", "gnx_step_spectral_gcn_dropped", "gnx_dense_drop",
-          "gnx_dense_wgrad_drop")
+          "gnx_dense_wgrad_drop", "gnx_signal_project", "gnx_signal_spmv", "gnx_signal_ppr", "gnx_signal_smoothness",
+          "gnx_signal_smoothness_back", "gnx_signal_uniform")
 
 _lib = None
 

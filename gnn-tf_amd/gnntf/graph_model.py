@@ -350,6 +350,7 @@ class GNN(Trainable):
             if reorder == "locality":
                 self.graph.set_row_window(ordering.LOCALITY_WINDOW)
         self._adjacency_cache = dict()
+        self._signal_cache = dict()              # eval-mode node signals of the constant adjacency (PPRSweep): constants of the graph
         if preprocessor is not None:
             self.add(preprocessor)
 
@@ -547,6 +548,81 @@ class APPNP(GNN):
                 raise Exception("APPNP(fused=True) needs a float restart probability and the identity activation")
             self.add(PPRLoop(H0, a, iterations, graph_dropout=graph_dropout))
             return
+        for _ in range(iterations):
+            self.add(PPRIteration(H0, self.create_var() if a is None else a, graph_dropout=graph_dropout, activation=activation))
+
+
+class PPRSweep(Layer):
+    """experimental_filter.py:7-19: features / HN, HN = ten PPR iterations of ``features * 0 + 1``.  Every column of that operand is
+    the same, so HN is ONE scalar per node (sparse.signal_ppr over the width-1 kernels) and the layer one division.  ``get_adjacency()``
+    is asked once per forward, with the reference's default ``graph_dropout = 0.5``: in training mode one dropped adjacency serves all
+    ten iterations (its values materialised once); in eval mode the signal is a constant of the graph and is kept on the model.
+    Where the composition measured faster -- up to 16 feature columns on graphs of at least 2^20 vertices, where appnp_propagate over
+    the matrix of ones runs on the relabelled copy -- a training-mode forward takes it (sparse.sweep)."""
+
+    ITERATIONS = 10                             # experimental_filter.py:16
+
+    def __build__(self, architecture: GNN, restart_probability: float = 0.1):
+        self.restart_probability = restart_probability
+        return architecture.top_shape()  # preserves the feature shape
+
+    def __forward__(self, architecture: GNN, features):
+        self.G = architecture.get_adjacency()
+        a = float(self.restart_probability)
+        cache = getattr(architecture, "_signal_cache", None)
+        if cache is None or self.G is not getattr(architecture, "_adjacency_cache", {}).get(("symmetric", "none")):
+            return sparse.sweep(self.G, features, a, self.ITERATIONS)
+        key = ("ppr", a, self.ITERATIONS)
+        if key not in cache:
+            cache[key] = sparse.signal_ppr(self.G, None, a, self.ITERATIONS)
+        return sparse.sweep(self.G, features, a, self.ITERATIONS, signal=cache[key])
+
+
+class FastReg(Layer):
+    """experimental_filter.py:22-43: passes its input on unchanged and adds -lambda to the objective, lambda the Rayleigh quotient
+    sum (f - G f)^2 / sum D f^2 of the one-column signal f = sigmoid(features . W) over the un-normalised adjacency
+    (sparse.smoothness: one autograd node over the width-1 kernels).  In training mode that adjacency is dropped at the reference's
+    default 0.5 and D is the column sums of those same dropped values (same seed and stream).
+    The reference calls ``create_var`` inside ``__forward__``: W is a fresh [C, 1] draw on every forward, is never trained, and the
+    model's variable list grows by one per forward.  Here W is drawn afresh per training-mode forward with create_var's default
+    initialiser, U(+-1/sqrt(shape[1])) = U(+-1), from the counter RNG of the edge dropout (one mask stream: reproducible from the seed,
+    fresh on every replay of a captured step) and is NOT registered among the model's variables -- the leak only moved the reported
+    loss through weight decay.  An eval-mode forward keeps the last draw: nothing reads it.
+    On CPU tensors the forward still runs (W from torch's generator), but ``loss()`` needs the device: the adjacency is a GPU handle
+    and sparse.smoothness has no CPU form."""
+
+    def __build__(self, architecture: GNN):
+        self.output_regularize = 1
+        self.internal_shape = (architecture.top_shape()[1], 1)
+        self.W = None
+        return architecture.top_shape()
+
+    def __forward__(self, architecture: GNN, features):
+        self.features = features
+        self.architecture = architecture
+        if architecture.is_training() or self.W is None:
+            width, bound = self.internal_shape[0], self.internal_shape[1] ** -0.5
+            if isinstance(features, torch.Tensor) and features.is_cuda:
+                seed, stream = architecture._next_mask_stream()
+                self.W = sparse.signal_uniform(architecture.graph, width, bound, seed, stream).reshape(width, 1)
+            else:                                   # CPU tensors: torch's generator, as create_var's initialisers draw
+                self.W = (torch.rand(self.internal_shape, device=features.device) * 2 - 1) * bound
+        return features
+
+    def loss(self):
+        G = self.architecture.get_adjacency(normalized="none")
+        return -sparse.smoothness(G, self.features, self.W)
+
+
+class APPNPReg(GNN):
+    """experimental_filter.py:46-55: APPNP without the leading Dropout (its FastReg is commented out in the reference)."""
+
+    def __init__(self, G, features, num_classes: int, a: float = 0.1, latent_dims=[64], iterations=10,
+                 dropout=0.6, graph_dropout=0.5, activation=linear, **kwargs):
+        super().__init__(G, features, **kwargs)
+        for latent_dim in latent_dims:
+            self.add(Dense(latent_dim, activation=relu, dropout=dropout))
+        H0 = self.add(Dense(num_classes, regularize=False))
         for _ in range(iterations):
             self.add(PPRIteration(H0, self.create_var() if a is None else a, graph_dropout=graph_dropout, activation=activation))
 
@@ -835,6 +911,23 @@ class GCNII(GNN):
         H0 = self.top_layer()
         for iteration in range(iterations):
             self.add(layer_type(H0, a, l, iteration, activation=relu, dropout=dropout, graph_dropout=0,
+                                regularization=convolution_regularization))
+        self.add(Dense(num_classes, dropout=0, regularize=False))
+
+
+class GCNIIReg(GNN):
+    """experimental_gcn.py:9-29: GCNII whose pre-MLP Dense layers carry the feature dropout themselves, with FastReg behind H0."""
+
+    def __init__(self, graph, features, num_classes, a: float = 0.1, l: float = 0.5, latent_dims=[64], iterations=64,
+                 dropout=0.6, convolution_regularization=True, **kwargs):
+        super().__init__(graph, features, **kwargs)
+        self.add(Dropout(dropout))
+        for latent_dim in latent_dims:
+            self.add(Dense(latent_dim, dropout=dropout, activation=relu))
+        H0 = self.top_layer()
+        self.add(FastReg())
+        for iteration in range(iterations):
+            self.add(GCNIILayer(H0, a, l, iteration, activation=relu, dropout=dropout, graph_dropout=0,
                                 regularization=convolution_regularization))
         self.add(Dense(num_classes, dropout=0, regularize=False))
 

@@ -254,6 +254,8 @@ class Adjacency:
         self.vals = vals          # values in coalesced-CSR order (None: the handle's raw values)
         self.diag = diag
         self.vals_t = vals_t      # the same values in the order of the transposed structure (backward), or None
+        self.transposed_only = False   # normalize(..., transposed_only=True): ``vals`` is None because only ``vals_t`` was written, not because the values are the raw ones
+        self.raw_dropout = None   # (p, seed, stream) when the values are the dropped RAW ones (normalize(..., "none", "none", p, ...)): signal_colsum
 
     def transposed_values(self):
         """Values in transposed order, permuted once and kept (a constant adjacency is reused by every backward)."""
@@ -339,7 +341,11 @@ def normalize(graph: DeviceGraph, normalized="symmetric", add_eye="none", dropou
     with nat.on_device(graph.device):
         nat.check(fn(graph.handle, nat.NORM[normalized], nat.EYE[add_eye], float(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF,
                      int(stream_id) & 0xFFFFFFFFFFFFFFFF, nat.ptr(vals), nat.ptr(diag), nat.current_stream()))
-    return Adjacency(graph, None, diag, vals_t=vals) if transposed_only else Adjacency(graph, vals, diag)
+    adj = Adjacency(graph, None, diag, vals_t=vals) if transposed_only else Adjacency(graph, vals, diag)
+    adj.transposed_only = bool(transposed_only)
+    if normalized == "none" and add_eye == "none":
+        adj.raw_dropout = (float(dropout), int(seed), int(stream_id))
+    return adj
 
 
 def _as_f32_rows(x: torch.Tensor) -> torch.Tensor:
@@ -2839,3 +2845,193 @@ def rank_candidates(graph: DeviceGraph, F: torch.Tensor, sources, positives, can
             nat.ptr(counts[3]), nat.ptr(top_ids), nat.ptr(top_scores), nat.ptr(top_is_pos), nat.ptr(raw), nat.ptr(workspace),
             workspace.numel(), nat.current_stream()))
     return RankResult(counts[0], counts[1], counts[2], counts[3], top_ids, top_scores, top_is_pos, raw)
+
+
+# ---- node signals at width 1: libgnx.so's csrc/gnx_signal.hip (experimental_filter.py:7-43 of the reference) ------------------------
+def _signal_adjacency(what, adj: Adjacency, transposed=False):
+    """(graph, values in the order of the structure walked or None for the raw values) of a width-1 launch.  A DroppedAdjacency is
+    used through its materialised values: one array, shared by every launch over it."""
+    for entry in ("gnx_signal_project", "gnx_signal_spmv", "gnx_signal_ppr", "gnx_signal_smoothness", "gnx_signal_smoothness_back"):
+        _need_symbol(what, entry)
+    if adj.diag is not None:
+        raise Exception(f"{what}: an adjacency with an added identity is not supported at width 1")
+    if not transposed:
+        if adj.transposed_only:
+            raise Exception(f"{what}: this adjacency only holds transposed-order values")
+        return adj.graph, adj.vals
+    raw = not isinstance(adj, DroppedAdjacency) and adj.vals is None and not adj.transposed_only
+    return adj.graph, (None if raw else adj.transposed_values())
+
+
+def _signal_vector(what, g: DeviceGraph, x, n, name):
+    """``x`` as a contiguous float32 [n] tensor on the graph's device (None stays None); no gradient flows through a signal launch."""
+    if x is None:
+        return None
+    nat.require_cuda(x)
+    _same_device(g, x)
+    x = x.detach().to(torch.float32).reshape(-1).contiguous()
+    if x.numel() != n:
+        raise Exception(f"{what}: {name} holds {x.numel()} values, the adjacency expects {n}")
+    return x
+
+
+def signal_project(X: torch.Tensor, w: torch.Tensor, sigmoid=True) -> torch.Tensor:
+    """f = sigmoid(X . w) as an [n] tensor (``sigmoid=False``: the dot product), one launch of gnx_signal_project; X may be a column
+    slice of a wider matrix.  No autograd node: smoothness() differentiates through it."""
+    nat.require_cuda(X, w)
+    _need_symbol("signal_project", "gnx_signal_project")
+    X = _as_f32_rows(X.detach())
+    w = w.detach().to(torch.float32).reshape(-1).contiguous()
+    if w.numel() != X.shape[1] or w.device != X.device:
+        raise Exception("signal_project: w must hold one weight per column of X, on X's device")
+    out = torch.empty(X.shape[0], dtype=torch.float32, device=X.device)
+    with nat.on_device(X.device):
+        nat.check(nat.lib().gnx_signal_project(nat.ptr(X), X.stride(0), X.shape[0], X.shape[1], nat.ptr(w), 1 if sigmoid else 0, nat.ptr(out),
+                                               nat.current_stream()))
+    return out
+
+
+def signal_spmv(adj: Adjacency, x: torch.Tensor, h0=None, beta=1.0, alpha=0.0, transposed=False) -> torch.Tensor:
+    """beta * (A . x) + alpha * h0 for ONE scalar per node, [n] tensors throughout (``transposed``: A^T; ``h0=None``: the constant 1,
+    bit for bit a vector of ones).  The lanes of a group split a row's entries (gnx_signal_spmv): fixed summation order, no float
+    atomics, a row without entries gives alpha * h0.  Not differentiable."""
+    g, vals = _signal_adjacency("signal_spmv", adj, transposed)
+    n_in, n_out = (g.n_rows, g.n_cols) if transposed else (g.n_cols, g.n_rows)
+    x = _signal_vector("signal_spmv", g, x, n_in, "x")
+    h0 = _signal_vector("signal_spmv", g, h0, n_out, "h0")
+    out = torch.empty(n_out, dtype=torch.float32, device=g.device)
+    with nat.on_device(g.device):
+        nat.check(nat.lib().gnx_signal_spmv(g.handle, nat.ptr(vals), 1 if transposed else 0, nat.ptr(x), nat.ptr(h0), float(beta), float(alpha),
+                                            nat.ptr(out), nat.current_stream()))
+    return out
+
+
+def signal_ppr(adj: Adjacency, h0=None, a: float = 0.1, iterations: int = 10) -> torch.Tensor:
+    """``iterations`` steps x <- (1-a) A x + a h0 from x = h0 (None: the constant 1) on one scalar per node: an [n] tensor, bit for bit
+    ``iterations`` signal_spmv calls (gnx_signal_ppr).  What PPRSweep propagates: every column of its operand is the same."""
+    g, vals = _signal_adjacency("signal_ppr", adj)
+    if g.n_rows != g.n_cols:
+        raise Exception("signal_ppr: needs a square adjacency")
+    h0 = _signal_vector("signal_ppr", g, h0, g.n_rows, "h0")
+    out = torch.empty(g.n_rows, dtype=torch.float32, device=g.device)
+    work = torch.empty(g.n_rows, dtype=torch.float32, device=g.device)
+    with nat.on_device(g.device):
+        nat.check(nat.lib().gnx_signal_ppr(g.handle, nat.ptr(vals), nat.ptr(h0), float(a), int(iterations), nat.ptr(out), nat.ptr(work),
+                                           nat.current_stream()))
+    return out
+
+
+def sweep(adj: Adjacency, X: torch.Tensor, a: float = 0.1, iterations: int = 10, signal=None) -> torch.Tensor:
+    """PPRSweep.__forward__ (experimental_filter.py:12-19): X / HN with HN the ``iterations``-step PPR of a matrix of ones -- whose
+    columns are all the same, so HN is signal_ppr(adj) and the division one torch pass.  The signal has no parameters: under autograd
+    dX = g / HN.  ``signal``: HN if the caller holds it already (a constant adjacency's).
+    Where the composition measured faster it is taken: at up to SWEEP_COMPOSED_MAX_WIDTH columns on graphs of at least
+    SWEEP_COMPOSED_MIN_ROWS vertices appnp_propagate runs on the handle's degree-relabelled copy, which the width-1 loop does not have
+    (R-MAT 10M / 100M, ten iterations, composed against width-1: C = 7 15.6 / 19.3 ms, C = 8 15.1 / 18.9, C = 16 17.9 / 19.0 -- and
+    from the first width without the relabelled copy on the other way round: C = 17 22.3 / 19.0, C = 32 21.0 / 19.2, C = 48 37.4 / 19.4,
+    C = 64 38.3 / 19.6; profiles/NOTES.md, "Width-1 node signals")."""
+    if signal is None and X.shape[1] <= SWEEP_COMPOSED_MAX_WIDTH and adj.graph.n_rows >= SWEEP_COMPOSED_MIN_ROWS and adj.diag is None:
+        return X / appnp_propagate(adj, torch.ones_like(X.detach()), a, iterations)
+    HN = signal_ppr(adj, None, a, iterations) if signal is None else signal
+    return X / HN[:, None]
+
+
+SWEEP_COMPOSED_MAX_WIDTH = 16           # = the widest rows gnx_appnp_propagate runs on the relabelled copy (RELABEL_MAX_C) ...
+SWEEP_COMPOSED_MIN_ROWS = 1 << 20       # ... and the smallest graph it builds that copy for
+
+
+def signal_colsum(adj: Adjacency) -> torch.Tensor:
+    """D_j = sum_i A_ij of the adjacency's own values (tf.sparse.reduce_sum(G, axis=0), experimental_filter.py:39), in a fixed order:
+    gnx_graph_colsum with the dropout triple of a ``normalized="none"`` adjacency (or of the raw values), else A^T . 1 at width 1."""
+    g = adj.graph
+    triple = getattr(adj, "raw_dropout", None)
+    if triple is None and adj.vals is None and not adj.transposed_only and not isinstance(adj, DroppedAdjacency):
+        triple = (0.0, 0, 0)
+    if triple is None:
+        return signal_spmv(adj, torch.ones(g.n_rows, dtype=torch.float32, device=g.device), None, 1.0, 0.0, transposed=True)
+    D = torch.empty(g.n_cols, dtype=torch.float32, device=g.device)
+    with nat.on_device(g.device):
+        nat.check(nat.lib().gnx_graph_colsum(g.handle, float(triple[0]), int(triple[1]) & 0xFFFFFFFFFFFFFFFF, int(triple[2]) & 0xFFFFFFFFFFFFFFFF,
+                                             nat.ptr(D), nat.current_stream()))
+    return D
+
+
+def smoothness_work_floats(n: int) -> int:
+    """Floats of scratch gnx_signal_smoothness needs for n rows (include/gnx.h)."""
+    return n // 64 + 64
+
+
+class _Smoothness(torch.autograd.Function):
+    """lambda = sum (f - A f)^2 / sum D f^2, f = sigmoid(X . w), as ONE node: the projection, one width-1 gather with the two global
+    sums behind it; backward one gather over the transposed structure (gnx_signal_smoothness_back), dX = gz w^T as one broadcast and,
+    where w needs it, dw = X^T gz through gnx_dense_wgrad at one output column.  No value is read back: the node records into a hipGraph."""
+
+    @staticmethod
+    def forward(ctx, X, w, adj, colsum):
+        g, vals = _signal_adjacency("smoothness", adj)
+        n = g.n_rows
+        f = signal_project(X, w)
+        d = torch.empty(n, dtype=torch.float32, device=g.device)
+        sums = torch.empty(3, dtype=torch.float32, device=g.device)
+        work = torch.empty(smoothness_work_floats(n), dtype=torch.float32, device=g.device)
+        with nat.on_device(g.device):
+            nat.check(nat.lib().gnx_signal_smoothness(g.handle, nat.ptr(vals), nat.ptr(f), nat.ptr(colsum), nat.ptr(d), nat.ptr(sums),
+                                                      nat.ptr(work), nat.current_stream()))
+        ctx.adj, ctx.colsum = adj, colsum
+        ctx.save_for_backward(X, w, f, d, sums)
+        return sums[2].clone()
+
+    @staticmethod
+    def backward(ctx, upstream):
+        X, w, f, d, sums = ctx.saved_tensors
+        g, vals_t = _signal_adjacency("smoothness", ctx.adj, transposed=True)
+        upstream = upstream.detach().to(torch.float32).reshape(1).contiguous()
+        gz = torch.empty(g.n_rows, dtype=torch.float32, device=g.device)
+        with nat.on_device(g.device):
+            nat.check(nat.lib().gnx_signal_smoothness_back(g.handle, nat.ptr(vals_t), nat.ptr(f), nat.ptr(d), nat.ptr(ctx.colsum), nat.ptr(sums),
+                                                           nat.ptr(upstream), nat.ptr(gz), nat.current_stream()))
+        dX = gz[:, None] * w.detach().reshape(1, -1) if ctx.needs_input_grad[0] else None
+        dw = _dense_wgrad(X.detach(), gz[:, None]).reshape(w.shape) if ctx.needs_input_grad[1] else None
+        return dX, dw, None, None
+
+
+def smoothness(adj: Adjacency, X: torch.Tensor, w: torch.Tensor, colsum=None, fused=True) -> torch.Tensor:
+    """FastReg's Rayleigh quotient (experimental_filter.py:34-43, without its sign): the 0-dim device tensor
+    lambda = sum_i (f_i - (A f)_i)^2 / sum_i D_i f_i^2 with f = sigmoid(X . w), w [C, 1] or [C], differentiable w.r.t. X and w.
+    ``colsum``: D; by default the column sums of ``adj``'s own values (signal_colsum).  The division is plain: a graph without
+    entries gives what IEEE gives.  ``fused=True``: one autograd node over the width-1 kernels (_Smoothness).  ``fused=False``: the
+    same mathematics composed from spmm at width 1 (whose backward is gnx_spmm_tv) and torch sums -- the baseline of
+    tools/signal_bench.py, and the path of what the width-1 entries refuse: an adjacency with an added identity (``adj.diag``) takes it
+    whatever ``fused`` says, its D the column sums of the values plus the diagonal.  Square adjacency; device tensors: a graph handle
+    lives on the GPU, so neither form has a CPU path (CPU tensors raise, as they do in spmm)."""
+    g = adj.graph
+    if g.n_rows != g.n_cols:
+        raise Exception("smoothness: needs a square adjacency")
+    if X.dim() != 2 or X.shape[0] != g.n_rows or w.numel() != X.shape[1]:
+        raise Exception("smoothness: X must be [n, C] and w hold C weights")
+    nat.require_cuda(X, w, colsum)
+    _same_device(g, X, w, colsum)
+    if colsum is not None:
+        D = _signal_vector("smoothness", g, colsum, g.n_cols, "colsum")
+    elif adj.diag is not None:
+        if adj.transposed_only:
+            raise Exception("smoothness: this adjacency only holds transposed-order values")
+        D = signal_colsum(Adjacency(g, adj.vals)) + adj.diag
+    else:
+        D = signal_colsum(adj)
+    if fused and adj.diag is None:
+        return _Smoothness.apply(_as_f32_rows(X), w, adj, D)
+    f = torch.sigmoid(torch.matmul(X, w.reshape(-1, 1)))
+    diffs = f - spmm(adj, f)
+    return (diffs * diffs).sum() / (D[:, None] * f * f).sum()
+
+
+def signal_uniform(graph: DeviceGraph, n: int, bound: float, seed, stream) -> torch.Tensor:
+    """[n] draws of U(-bound, bound) from the counter RNG of the edge dropout (gnx_signal_uniform): reproducible from (seed, stream),
+    and -- the handle's dropout counter is added to the stream on the device -- fresh on every replay of a captured step."""
+    _need_symbol("signal_uniform", "gnx_signal_uniform")
+    out = torch.empty(int(n), dtype=torch.float32, device=graph.device)
+    with nat.on_device(graph.device):
+        nat.check(nat.lib().gnx_signal_uniform(graph.handle, int(n), float(bound), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFFFFFFFFFF,
+                                               nat.ptr(out), nat.current_stream()))
+    return out

@@ -75,7 +75,8 @@ const char *gnx_last_error(void);
  * task on the device (gnx_sample_negatives, gnx_edge_plan_bytes, gnx_edge_plan, gnx_edge_sorted_work_floats,
  * gnx_edge_scores_backward_sorted), likewise, and the ranking evaluation of the link task (gnx_rank_candidates_bytes,
  * gnx_rank_candidates, GNX_RANK_MAX_K, GNX_RANK_POS_PASS, GNX_RANK_MAX_SPLITS), likewise, and the spectral-preserving GCN layer in
- * one launch (gnx_step_spectral_gcn, gnx_step_spectral_gcn_dropped), likewise. */
+ * one launch (gnx_step_spectral_gcn, gnx_step_spectral_gcn_dropped), likewise, and the node signals at width 1 (gnx_signal_project,
+ * gnx_signal_spmv, gnx_signal_ppr, gnx_signal_smoothness, gnx_signal_smoothness_back, gnx_signal_uniform), likewise. */
 #define GNX_ABI_VERSION 900
 int gnx_version(void);
 
@@ -1189,6 +1190,46 @@ int gnx_rank_candidates(gnx_graph_t g, const float *d_F, int64_t ldf, int64_t n_
                         const int64_t *d_candidates, int64_t K, int64_t k, int64_t splits, int64_t *d_n_pos, int64_t *d_n_neg,
                         int64_t *d_less, int64_t *d_equal, int64_t *d_top_ids, float *d_top_scores, uint8_t *d_top_is_pos, float *d_scores,
                         void *d_workspace, int64_t bytes, void *stream);
+
+/* ---- node signals at width 1 (added within ABI 0.9 -- probe for the symbols) -------------------------------------------------
+ * One scalar per node: what PPRSweep and FastReg (gnntf/core/gnn/architectures/experimental_filter.py:7-43) compute.  The gather
+ * deals a row's ENTRIES to the lanes of a group (the SpMM kernels deal its columns, of which there is one here): every lane runs its
+ * own fmaf chain in entry order, the group's sums are added in a fixed xor tree; rows longer than the structure's long-row threshold
+ * go one wave per chunk, the chunk sums added in chunk order.  No float atomics: every result is a function of the structure and the
+ * operands alone, two calls give the same bits, a row without entries sums to +0.  All entries are stream-ordered and read no value
+ * back; they allocate only what gnx_graph_reserve(g, 1, GNX_RESERVE_TRANSPOSED) builds ahead of a capture.
+ * gnx_signal_project: d_out[i] = act(sum_c d_X[i * ldx + c] * d_w[c]), i < n; act = 1: 1 / (1 + expf(-z)) with the accurate expf
+ *   (z = +-100 gives exactly 1 / 0, never NaN), act = 0: the dot product z.  Any C >= 1, ldx >= C; 16-byte loads where every row start
+ *   allows.  Each lane adds its columns in ascending order, then a fixed xor tree.
+ * gnx_signal_spmv: d_out[i] = beta * (sum_j A[i,j] d_x[j]) + alpha * h0[i] over the matrix (transposed == 0: d_x [n_cols], d_out and
+ *   d_h0 [n_rows]) or its transpose (the other way round).  d_vals in the order of the structure WALKED (transposed: what
+ *   gnx_graph_permute_values_t / gnx_graph_normalize_t write), NULL = the raw values.  d_h0 == NULL is the constant 1, bit for bit a
+ *   vector of ones.  d_out must not be d_x.
+ * gnx_signal_ppr: K steps x <- (1-a) A x + a h0 from x = h0 (NULL: the constant 1), ping-ponging through d_work [n] so that the last
+ *   lands in d_out; bit for bit K calls of gnx_signal_spmv with beta = float(1 - a), alpha = a.  K = 0 copies h0.  Square graph; d_work
+ *   is needed for K >= 2, and for K = 1 when d_h0 is NULL.
+ * gnx_signal_smoothness: the forward of lambda = sum_i d_i^2 / sum_i D_i f_i^2, d = f - A f (experimental_filter.py:34-43 with
+ *   f = the projected signal, D = d_colsum): writes d to d_diff_out [n] and {num, den, num / den} to d_sums_out [3] -- a plain IEEE
+ *   division, so den == 0 gives what IEEE gives.  Blocks of 256 rows of the structure's row order leave their partial sums in d_work
+ *   (at least n / 64 + 64 floats), a second launch adds them in index order (64 slabs per block, in levels beyond 2^14 rows).  Square graph.
+ * gnx_signal_smoothness_back: gz_i = u * (2 / den) * ((d_i - (A^T d)_i) - lambda * D_i * f_i) * f_i * (1 - f_i): the gradient of
+ *   u * lambda with respect to the pre-sigmoid projection, one walk of the transposed structure.  d_vals_t in transposed order (NULL:
+ *   the raw values); d_sums as gnx_signal_smoothness left it; u = d_upstream[0], read on the device.
+ * gnx_signal_uniform: d_out[i] = bound * u_i, i < n, u_i = (hash_u24(seed, stream_id, i, 0, 0) - 2^23) / 2^23: uniform on a 2^-23
+ *   grid of [-1, 1), from the counter RNG of the edge dropout (the handle's dropout counter is added to stream_id): the fresh
+ *   projection vector FastReg draws per forward, reproducible from (seed, stream) and replayable inside a hipGraph.
+ * gnx_graph_last_kernel reports "signal_spmv_group8", "signal_smooth_group8", "signal_back_group8", with "+long" appended when hub
+ * rows went through the chunk launch.  Refused (GNX_ERR_INVALID, "<entry>: ..."): a NULL handle or buffer, C < 1, ldx < C, K < 0, a
+ * non-square graph where one is needed, an output that aliases an operand. */
+int gnx_signal_project(const float *d_X, int64_t ldx, int64_t n, int64_t C, const float *d_w, int act, float *d_out, void *stream);
+int gnx_signal_spmv(gnx_graph_t g, const float *d_vals, int transposed, const float *d_x, const float *d_h0, float beta, float alpha,
+                    float *d_out, void *stream);
+int gnx_signal_ppr(gnx_graph_t g, const float *d_vals, const float *d_h0, float a, int K, float *d_out, float *d_work, void *stream);
+int gnx_signal_smoothness(gnx_graph_t g, const float *d_vals, const float *d_f, const float *d_colsum, float *d_diff_out,
+                          float *d_sums_out, float *d_work, void *stream);
+int gnx_signal_smoothness_back(gnx_graph_t g, const float *d_vals_t, const float *d_f, const float *d_diff, const float *d_colsum,
+                               const float *d_sums, const float *d_upstream, float *d_gz_out, void *stream);
+int gnx_signal_uniform(gnx_graph_t g, int64_t n, float bound, uint64_t seed, uint64_t stream_id, float *d_out, void *stream);
 
 /* Halo packing for the vertex-partitioned path: out[r,:] = X[idx[r],:], idx int64 [n_idx]. */
 int gnx_gather_rows(const float *d_X, int64_t ldx, const int64_t *d_idx, int64_t n_idx, int64_t C,
