@@ -583,11 +583,16 @@ class FastReg(Layer):
     sum (f - G f)^2 / sum D f^2 of the one-column signal f = sigmoid(features . W) over the un-normalised adjacency
     (sparse.smoothness: one autograd node over the width-1 kernels).  In training mode that adjacency is dropped at the reference's
     default 0.5 and D is the column sums of those same dropped values (same seed and stream).
-    The reference calls ``create_var`` inside ``__forward__``: W is a fresh [C, 1] draw on every forward, is never trained, and the
-    model's variable list grows by one per forward.  Here W is drawn afresh per training-mode forward with create_var's default
-    initialiser, U(+-1/sqrt(shape[1])) = U(+-1), from the counter RNG of the edge dropout (one mask stream: reproducible from the seed,
-    fresh on every replay of a captured step) and is NOT registered among the model's variables -- the leak only moved the reported
-    loss through weight decay.  An eval-mode forward keeps the last draw: nothing reads it.
+    NAMED DEVIATION.  The reference calls ``create_var`` inside ``__forward__``: W is a new [C, 1] variable on every forward, is never
+    trained, and the model's variable list grows by one per forward.  A new variable holds zeros (variables.py:6) and only reset()
+    initialises it, which train() calls once, ahead of every forward: in the reference as it stands W = 0 in every forward, f = 1/2
+    everywhere and -lambda is a constant without a gradient (tests/golden/reference_step_gcniireg.npz records it;
+    tests/test_reference_golden_cpu.py holds the restatement with W = 0 to it and asserts what the draw changes).  Here W is instead
+    drawn afresh per training-mode forward with the initialiser create_var names as its default, U(+-1/sqrt(shape[1])) = U(+-1) --
+    the random projection the layer is evidently written for; with zeros it regularises nothing --, from the counter RNG of the edge
+    dropout (one mask stream, drawn AHEAD of the dropped adjacency's: reproducible from the seed, fresh on every replay of a captured
+    step), and is NOT registered among the model's variables.  An eval-mode forward keeps the last draw and draws none itself (zeros where there
+    has been no training-mode forward yet): nothing reads it, and eval forwards leave the numbering of the mask streams alone.
     On CPU tensors the forward still runs (W from torch's generator), but ``loss()`` needs the device: the adjacency is a GPU handle
     and sparse.smoothness has no CPU form."""
 
@@ -600,7 +605,12 @@ class FastReg(Layer):
     def __forward__(self, architecture: GNN, features):
         self.features = features
         self.architecture = architecture
-        if architecture.is_training() or self.W is None:
+        if not architecture.is_training():
+            # an eval-mode forward draws no mask stream, as in the reference, where no eval forward asks for anything random: ahead of
+            # the first training-mode forward W is what the reference's freshly created variable holds, zeros (variables.py:6)
+            if self.W is None:
+                self.W = torch.zeros(self.internal_shape, dtype=torch.float32, device=features.device)
+        else:
             width, bound = self.internal_shape[0], self.internal_shape[1] ** -0.5
             if isinstance(features, torch.Tensor) and features.is_cuda:
                 seed, stream = architecture._next_mask_stream()

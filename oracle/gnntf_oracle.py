@@ -4,13 +4,15 @@ TEST INFRASTRUCTURE ONLY.  Nothing under ``gnn-tf_amd/`` imports this module; on
 ``tests/``, ``__graft_entry__.smoke()`` and the ``cpu_baseline`` leg of ``bench.py`` do,
 and only as the checker.  The product path is the HIP library behind ``include/gnx.h``.
 
-PARITY UNPINNED: the reference (/root/reference, gnntf 0.0.20) ships no golden vectors,
-no known-answer tests and no fixtures for this path, and its
-arithmetic lives in an un-vendored, un-pinned TensorFlow that is absent from this image,
-so the reference itself cannot be run here.  This file restates the reference's Python
-line by line and the documented TensorFlow op semantics it relies on; it is pinned by
-closed-form known-answer tests (tests/test_oracle_kat.py) and by two independent
-re-derivations (scipy CSR, dense float64), not by reference outputs.
+The reference (gnntf 0.0.20) ships no golden vectors, no known-answer tests and no
+fixtures for this path, and its arithmetic lives in an un-vendored,
+un-pinned TensorFlow that is absent from this image.  This file restates the reference's
+Python line by line and the documented TensorFlow op semantics it relies on; it is pinned
+by closed-form known-answer tests (tests/test_oracle_kat.py), by two independent
+re-derivations (scipy CSR, dense float64), and -- to 1e-9 -- by what the reference's own
+classes compute on a stand-in for the TensorFlow names they use (oracle/tf_standin,
+tests/golden/reference_*.npz, tests/test_reference_golden_cpu.py).  What stays our reading
+is TensorFlow itself: the op semantics as the stand-in restates them, and float32 roundings.
 
 Every function cites the reference file:line (relative to /root/reference) it follows.
 All functions take/return numpy arrays; ``dtype`` selects float32 (what the reference

@@ -2,10 +2,18 @@
 
     python tests/golden/make_golden.py
 
-PARITY UNPINNED: the reference ships no vectors and cannot run here (no TensorFlow), so
-these are outputs of the restatement, not of gnntf itself.  They freeze the oracle against
-regressions and carry identical inputs/expected outputs to the GPU box.  All inputs are
-rounded to float16-representable values so they can be stored compactly and exactly.
+These three fixtures are outputs of the restatement, not of the reference itself: they freeze
+the oracle against regressions and carry identical inputs/expected outputs to the GPU box.
+All inputs are rounded to float16-representable values so they can be stored compactly and
+exactly.
+
+The restatement itself is pinned elsewhere: tests/golden/make_reference_golden.py runs the
+reference's own classes on a stand-in for the TensorFlow names they use (oracle/tf_standin)
+and writes reference_*.npz, which tests/test_reference_golden_cpu.py holds the oracle to at
+1e-9.  Pinned by the reference's own text: composition, call order, constants, axes and
+regularisation.  Still our reading: TensorFlow's documented op semantics as the stand-in
+restates them, TensorFlow's RNG streams and initialisers (no case depends on them), and
+TensorFlow's own float32 roundings.
 """
 import os
 import sys

@@ -191,11 +191,18 @@ def gcniireg_layers(num_classes, latent_dims=(64,), iterations=2, dropout=0.6, a
     return layers
 
 
-def gcniireg_reference(layers, coo, vals, shape, X, parameters, task, weight_decay, seed, fixed):
+def gcniireg_reference(layers, coo, vals, shape, X, parameters, task, weight_decay, seed, fixed, projection="uniform"):
     """model_step_ref.Reference with the FastReg layer: in a training-mode forward the layer draws one stream for its projection vector
     W (uniform_draw) and passes its input on; the objective then takes -lambda over the adjacency dropped at 0.5 under the NEXT stream
     (drawn when the loss is formed, after the whole forward), un-normalised, D its column sums.  ``.fastreg`` holds what the last
-    training forward used: w_stream, W, g_stream."""
+    training forward used: w_stream, W, g_stream.
+    ``projection``: "uniform" is this project's FastReg, a NAMED DEVIATION from the reference; "zeros" is the reference's own text:
+    its FastReg creates W inside the forward (experimental_filter.py:31), after train()'s only reset() (trainable.py:53), and a new
+    variable holds zeros (variables.py:6) -- so W = 0 in every forward, f = sigmoid(0) = 1/2 everywhere, -lambda is a constant of the
+    dropped adjacency with no gradient, and no stream is drawn for W (the dropped adjacency takes the forward's next one).
+    tests/test_reference_golden_cpu.py holds "zeros" to the reference's recorded steps at 1e-9 and asserts what "uniform" changes."""
+    if projection not in ("uniform", "zeros"):
+        raise Exception("projection is \"uniform\" or \"zeros\"")
     import torch
 
     import model_step_ref as ref
@@ -205,7 +212,7 @@ def gcniireg_reference(layers, coo, vals, shape, X, parameters, task, weight_dec
         def _layer_streams(self, layer, training):
             if layer["kind"] == "fastreg":
                 if training:
-                    self.fastreg = dict(w_stream=self._draw())
+                    self.fastreg = dict(w_stream=self._draw() if projection == "uniform" else None)
                 return None, None
             return super()._layer_streams(layer, training)
 
@@ -217,7 +224,7 @@ def gcniireg_reference(layers, coo, vals, shape, X, parameters, task, weight_dec
             feats = self.values[at]
             info = self.fastreg
             info["g_stream"] = self._draw()
-            info["W"] = uniform_draw(self.seed, info["w_stream"], feats.shape[1])
+            info["W"] = uniform_draw(self.seed, info["w_stream"], feats.shape[1]) if projection == "uniform" else np.zeros(feats.shape[1], dtype=np.float32)
             ai, av = orc.get_adjacency(self.coo, self.vals, self.shape, graph_dropout=0.5, normalized="none", training=True, seed=self.seed,
                                        stream=info["g_stream"], dtype=np.float64)
             G = self._dense(ai, av)

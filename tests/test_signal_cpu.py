@@ -199,6 +199,20 @@ def test_gcniireg_builds_the_reference_layer_list(cpu_models):
     model(model.features)
     assert tuple(out.shape) == (n, 3) and len(model.vars()) == before and not torch.equal(first, fast.W)
     assert not fast.W.requires_grad
+    # an eval-mode forward draws nothing: ahead of any training-mode forward W is the reference's freshly created variable, zeros
+    fresh = gnntf.GCNIIReg(CpuGraph(), X, 3, latent_dims=[8], iterations=2)
+    fresh.reset()
+    fresh.training_mode(False)
+    state = torch.get_rng_state()
+    fresh(fresh.features)
+    assert torch.equal(torch.get_rng_state(), state) and fresh._mask_calls == 0
+    assert tuple(fresh.layers()[2].W.shape) == (8, 1) and not fresh.layers()[2].W.any()
+    fresh.training_mode(True)
+    fresh(fresh.features)
+    kept = fresh.layers()[2].W.clone()
+    fresh.training_mode(False)
+    fresh(fresh.features)
+    assert kept.any() and torch.equal(fresh.layers()[2].W, kept)                        # an eval forward keeps the last draw
 
 
 def test_appnpreg_builds_the_reference_layer_list(cpu_models):
