@@ -39,6 +39,24 @@ class Structural(Layer):
 
 
 FEATURE_DROPOUTS = ("torch", "fused")
+STORAGE_DTYPES = (torch.float32, torch.bfloat16)
+
+# the opt-in keywords of GNN.__init__ with the values each takes, in the order __init__ checks them (a call with two bad ones names the
+# first).  The first value is today's path: what a layer reads on an architecture that does not carry the attribute (_switch)
+SWITCHES = (
+    ("dense_dropout", sparse.DENSE_DROPOUTS), ("gcn_spectral", sparse.GCN_SPECTRALS), ("ngcf_layer", sparse.NGCF_LAYERS),
+    ("ngcf_backward", sparse.NGCF_BACKWARDS), ("ngcf_wide", sparse.NGCF_WIDES), ("ngcf_wide_backward", sparse.NGCF_WIDE_BACKWARDS),
+    ("gcn_backward", sparse.GCN_BACKWARDS), ("gcn_layer", sparse.GCN_LAYERS), ("gcnii_edge_dropout", sparse.GCNII_EDGE_DROPOUTS),
+    ("gcnii_spectral", sparse.GCNII_SPECTRALS), ("feature_dropout", FEATURE_DROPOUTS), ("gcnii_backward", sparse.GCNII_BACKWARDS),
+    ("train_gather_order", sparse.GATHER_ORDERS), ("inference_dtype", STORAGE_DTYPES), ("training_dtype", STORAGE_DTYPES),
+    ("gcnii_training_dtype", STORAGE_DTYPES), ("gcnii_weight_gradient", sparse.GCNII_WEIGHT_GRADIENTS),
+)
+_TODAYS_PATH = {keyword: allowed[0] for keyword, allowed in SWITCHES}
+
+
+def _switch(architecture, keyword):
+    """What ``architecture`` says about the GNN keyword ``keyword``; today's path where it is no GNN and does not say."""
+    return getattr(architecture, keyword, _TODAYS_PATH[keyword])
 
 
 class GNN(Trainable):
@@ -260,58 +278,16 @@ class GNN(Trainable):
         Layered without a graph handle (MLP), other activations, subclasses, rates of 0 and of 1 or more, and the vertex-partitioned
         path keep today's path and bits whatever it says; ``fuse_runs = False`` keeps the layers apart, each with the counter RNG's pass
         (measurement: profiles/NOTES.md "Fused dropout around Dense")."""
-        if dense_dropout not in sparse.DENSE_DROPOUTS:
-            raise Exception("GNN: dense_dropout must be one of " + ", ".join(repr(d) for d in sparse.DENSE_DROPOUTS))
-        if gcn_spectral not in sparse.GCN_SPECTRALS:
-            raise Exception("GNN: gcn_spectral must be one of " + ", ".join(repr(f) for f in sparse.GCN_SPECTRALS))
-        if ngcf_layer not in sparse.NGCF_LAYERS:
-            raise Exception("GNN: ngcf_layer must be one of " + ", ".join(repr(f) for f in sparse.NGCF_LAYERS))
-        if ngcf_backward not in sparse.NGCF_BACKWARDS:
-            raise Exception("GNN: ngcf_backward must be one of " + ", ".join(repr(b) for b in sparse.NGCF_BACKWARDS))
-        if ngcf_wide not in sparse.NGCF_WIDES:
-            raise Exception("GNN: ngcf_wide must be one of " + ", ".join(repr(w) for w in sparse.NGCF_WIDES))
-        if ngcf_wide_backward not in sparse.NGCF_WIDE_BACKWARDS:
-            raise Exception("GNN: ngcf_wide_backward must be one of " + ", ".join(repr(w) for w in sparse.NGCF_WIDE_BACKWARDS))
-        if gcn_backward not in sparse.GCN_BACKWARDS:
-            raise Exception("GNN: gcn_backward must be one of " + ", ".join(repr(b) for b in sparse.GCN_BACKWARDS))
-        if gcn_layer not in sparse.GCN_LAYERS:
-            raise Exception("GNN: gcn_layer must be one of " + ", ".join(repr(f) for f in sparse.GCN_LAYERS))
-        if gcnii_edge_dropout not in sparse.GCNII_EDGE_DROPOUTS:
-            raise Exception("GNN: gcnii_edge_dropout must be one of " + ", ".join(repr(e) for e in sparse.GCNII_EDGE_DROPOUTS))
-        if gcnii_spectral not in sparse.GCNII_SPECTRALS:
-            raise Exception("GNN: gcnii_spectral must be one of " + ", ".join(repr(f) for f in sparse.GCNII_SPECTRALS))
-        if feature_dropout not in FEATURE_DROPOUTS:
-            raise Exception("GNN: feature_dropout must be one of " + ", ".join(repr(f) for f in FEATURE_DROPOUTS))
-        if gcnii_backward not in sparse.GCNII_BACKWARDS:
-            raise Exception("GNN: gcnii_backward must be one of " + ", ".join(repr(b) for b in sparse.GCNII_BACKWARDS))
-        if train_gather_order not in sparse.GATHER_ORDERS:
-            raise Exception("GNN: train_gather_order must be one of " + ", ".join(repr(o) for o in sparse.GATHER_ORDERS))
-        if inference_dtype not in (torch.float32, torch.bfloat16):
-            raise Exception("GNN: inference_dtype must be torch.float32 or torch.bfloat16")
-        if training_dtype not in (torch.float32, torch.bfloat16):
-            raise Exception("GNN: training_dtype must be torch.float32 or torch.bfloat16")
-        if gcnii_training_dtype not in (torch.float32, torch.bfloat16):
-            raise Exception("GNN: gcnii_training_dtype must be torch.float32 or torch.bfloat16")
-        if gcnii_weight_gradient not in sparse.GCNII_WEIGHT_GRADIENTS:
-            raise Exception("GNN: gcnii_weight_gradient must be one of " + ", ".join(repr(w) for w in sparse.GCNII_WEIGHT_GRADIENTS))
+        given = locals()
+        for keyword, allowed in SWITCHES:
+            if allowed is STORAGE_DTYPES:
+                if given[keyword] not in allowed:
+                    raise Exception(f"GNN: {keyword} must be torch.float32 or torch.bfloat16")
+            else:
+                sparse._one_of("GNN", keyword, given[keyword], allowed)
         super().__init__(features)
-        self.inference_dtype = inference_dtype
-        self.training_dtype = training_dtype
-        self.gcnii_training_dtype = gcnii_training_dtype
-        self.train_gather_order = train_gather_order
-        self.gcnii_backward = gcnii_backward
-        self.gcnii_weight_gradient = gcnii_weight_gradient
-        self.feature_dropout = feature_dropout
-        self.gcnii_spectral = gcnii_spectral
-        self.gcnii_edge_dropout = gcnii_edge_dropout
-        self.gcn_layer = gcn_layer
-        self.gcn_backward = gcn_backward
-        self.ngcf_layer = ngcf_layer
-        self.ngcf_backward = ngcf_backward
-        self.ngcf_wide = ngcf_wide
-        self.ngcf_wide_backward = ngcf_wide_backward
-        self.gcn_spectral = gcn_spectral
-        self.dense_dropout = dense_dropout
+        for keyword, _ in SWITCHES:
+            setattr(self, keyword, given[keyword])
         self._order = self._newid = None
         self.reorder_used, self.locality_share = None, None
         if isinstance(graph, sparse.DeviceGraph):
@@ -377,6 +353,10 @@ class GNN(Trainable):
             self._adjacency_cache[key] = sparse.normalize(self.graph, normalized, add_eye)
         return self._adjacency_cache[key]
 
+    def _mask_triple(self, rate):
+        """(rate, seed, stream) of a layer's counter-RNG feature mask: draws the layer's next mask stream (_next_mask_stream)."""
+        return (rate,) + tuple(self._next_mask_stream())
+
     def _enable_entry_dropout(self):
         """The entry tables of a graph with duplicate entries, once, before its first fused training propagation (fuse_entry_dropout)."""
         g = self.graph
@@ -425,9 +405,9 @@ def _propagation_run(architecture: "GNN", H0_value, a, iterations, graph_dropout
         storage = _eval_storage(architecture)
         run = lambda k: sparse.appnp_propagate(make_adj(0, False), H0_value, a, k, relu=with_relu, storage=storage)
     else:
-        storage = getattr(architecture, "training_dtype", torch.float32) if training else torch.float32
+        storage = _switch(architecture, "training_dtype") if training else torch.float32
         # (the argument is passed only where it can change the path: outside the allowance "auto" is today's call, argument for argument)
-        gather_order = getattr(architecture, "train_gather_order", "caller") if training else "caller"
+        gather_order = _switch(architecture, "train_gather_order") if training else "caller"
         ordered = dict(gather_order=gather_order) if training and sparse.may_use_train_gather(architecture.graph, gather_order) else dict()
         run = lambda k: sparse.ppr_loop(make_adj, H0_value, a, k, relu=with_relu, storage=storage, **ordered)
     return run(iterations), run, (make_adj if cheap else None)
@@ -655,7 +635,7 @@ class GCNLayer(Layer):
 
     def _fused_gcn(self, gcn, features, adjacency) -> bool:
         """Whether GNN(gcn_layer="fused") applies to this forward (no tensor is read, no mask stream is drawn)."""
-        return (getattr(gcn, "gcn_layer", "composed") == "fused" and type(self) is GCNLayer and not self.transform_first
+        return (_switch(gcn, "gcn_layer") == "fused" and type(self) is GCNLayer and not self.transform_first
                 and (self.activation is relu or self.activation is linear)
                 and isinstance(features, torch.Tensor) and features.is_cuda and features.dtype == torch.float32
                 and features.shape[1] in sparse.GCN_FUSED_WIDTHS and self.W.shape[1] <= features.shape[1]
@@ -666,11 +646,11 @@ class GCNLayer(Layer):
         if self._fused_gcn(gcn, features, adjacency):
             # GNN(gcn_layer="fused"): the aggregation and the transform in one launch; with feature_dropout="fused" the mask too
             triple = None
-            if getattr(gcn, "feature_dropout", "torch") == "fused" and gcn.is_training() and 0 < self.dropout < 1:
-                triple = (self.dropout,) + tuple(gcn._next_mask_stream())
+            if _switch(gcn, "feature_dropout") == "fused" and gcn.is_training() and 0 < self.dropout < 1:
+                triple = gcn._mask_triple(self.dropout)
             out = sparse.gcn_step(adjacency, features, self.W, self.b if isinstance(self.b, torch.Tensor) else None,
                                   relu=self.activation is relu, dropout=triple, edge_dropout="fused",
-                                  backward=getattr(gcn, "gcn_backward", "composed"))
+                                  backward=_switch(gcn, "gcn_backward"))
             return out if triple is not None else gcn.dropout(out, self.dropout)
         if self.transform_first:
             bias = self.b if isinstance(self.b, torch.Tensor) else None
@@ -694,7 +674,7 @@ class GCNSpectralPreservingLayer(GCNLayer):
 
     def _fused_spectral(self, gcn, features, adjacency) -> bool:
         """Whether GNN(gcn_spectral="fused") applies to this forward (no tensor is read, no mask stream is drawn)."""
-        return (getattr(gcn, "gcn_spectral", "composed") == "fused" and type(self) is GCNSpectralPreservingLayer and not self.transform_first
+        return (_switch(gcn, "gcn_spectral") == "fused" and type(self) is GCNSpectralPreservingLayer and not self.transform_first
                 and (self.activation is relu or self.activation is linear)
                 and isinstance(features, torch.Tensor) and features.is_cuda and features.dtype == torch.float32
                 and features.shape[1] in sparse.GCN_FUSED_WIDTHS and self.W.shape[1] <= features.shape[1]
@@ -704,10 +684,10 @@ class GCNSpectralPreservingLayer(GCNLayer):
     def __forward__(self, gcn, features):
         adjacency = gcn.get_adjacency(self.graph_dropout)
         if self._fused_spectral(gcn, features, adjacency):
-            triple = (self.dropout,) + tuple(gcn._next_mask_stream()) if gcn.is_training() and self.dropout != 0 else None
+            triple = gcn._mask_triple(self.dropout) if gcn.is_training() and self.dropout != 0 else None
             return sparse.gcn_step_spectral(adjacency, features, self.W, self.b if isinstance(self.b, torch.Tensor) else None,
                                             relu=self.activation is relu, dropout=triple, edge_dropout="fused",
-                                            backward=getattr(gcn, "gcn_backward", "composed"))
+                                            backward=_switch(gcn, "gcn_backward"))
         activated = affine(sparse.spmm(adjacency, features), self.W, self.b, self.activation)
         return 2 * gcn.dropout(activated - self.b, self.dropout)
 
@@ -770,7 +750,7 @@ class GCNIILayer(Layer):
 
     def _bf16_train_plain(self, gcn, first) -> bool:
         """Whether this layer can be one step of a training-mode bf16 run that ``first`` starts (the run's own conditions: _bf16_train_run)."""
-        fused_drop = getattr(gcn, "feature_dropout", "torch") == "fused" and 0 < self.dropout < 1
+        fused_drop = _switch(gcn, "feature_dropout") == "fused" and 0 < self.dropout < 1
         return (type(self) is GCNIILayer and (self.activation is relu or self.activation is linear)
                 and isinstance(self.a, (int, float)) and not isinstance(self.a, bool)
                 and (self.dropout == 0 or fused_drop) and self.graph_dropout == first.graph_dropout
@@ -779,7 +759,7 @@ class GCNIILayer(Layer):
     def _bf16_train_run(self, gcn, stack, at):
         """The layers of the training-mode bf16 run that starts with this layer (GNN.__init__ ``gcnii_training_dtype``), or None where
         today's path applies.  Looks at the model alone -- no tensor is read, no mask stream is drawn -- so it can be asked anywhere."""
-        if not (isinstance(gcn, GNN) and getattr(gcn, "gcnii_training_dtype", torch.float32) is torch.bfloat16 and gcn.fuse_runs
+        if not (isinstance(gcn, GNN) and _switch(gcn, "gcnii_training_dtype") is torch.bfloat16 and gcn.fuse_runs
                 and gcn.is_training() and torch.is_grad_enabled()):
             return None
         width = self.W.shape[1]
@@ -801,11 +781,11 @@ class GCNIILayer(Layer):
         adjacency = gcn.get_adjacency(self.graph_dropout)
         steps = []
         for layer in run:                                       # the mask streams in layer order: those of the f32 "fused" path
-            triple = (layer.dropout,) + tuple(gcn._next_mask_stream()) if layer.dropout != 0 else None
+            triple = gcn._mask_triple(layer.dropout) if layer.dropout != 0 else None
             steps.append((layer.H0.value, float(layer.a), layer._transform(), layer.activation is relu, triple))
         stored = []
         out = sparse.gcnii_train_run_bf16(adjacency, features, steps, stored=stored,
-                                          weight_gradient=getattr(gcn, "gcnii_weight_gradient", "stored"))
+                                          weight_gradient=_switch(gcn, "gcnii_weight_gradient"))
         for k, layer in enumerate(run[:-1]):
             layer.__dict__["_value"] = None
             layer.__dict__["_pending_value"] = lambda k=k: stored[k].float()
@@ -854,21 +834,20 @@ class GCNIILayer(Layer):
         if features.is_cuda and adjacency.diag is None:
             fused_act = self.activation is relu or self.activation is linear
             # GNN(gcnii_weight_gradient="recomputed"): plain layers alone (the argument is passed only where it can change the path)
-            wgrad = dict(weight_gradient="recomputed") if (getattr(gcn, "gcnii_weight_gradient", "stored") == "recomputed"
+            wgrad = dict(weight_gradient="recomputed") if (_switch(gcn, "gcnii_weight_gradient") == "recomputed"
                                                            and type(self) is GCNIILayer and fused_act) else dict()
             # GNN(gcnii_edge_dropout="fused"): plain training layers over a DroppedAdjacency alone (passed only where it can change the path)
-            if (getattr(gcn, "gcnii_edge_dropout", "composed") == "fused" and type(self) is GCNIILayer and fused_act and gcn.is_training()
+            if (_switch(gcn, "gcnii_edge_dropout") == "fused" and type(self) is GCNIILayer and fused_act and gcn.is_training()
                     and isinstance(adjacency, sparse.DroppedAdjacency) and features.dtype == torch.float32 and not wgrad
                     and isinstance(self.a, (int, float)) and not isinstance(self.a, bool)):
                 wgrad = dict(edge_dropout="fused")
-            if (getattr(gcn, "feature_dropout", "torch") == "fused" and type(self) is GCNIILayer and fused_act and gcn.is_training()
+            if (_switch(gcn, "feature_dropout") == "fused" and type(self) is GCNIILayer and fused_act and gcn.is_training()
                     and 0 < self.dropout < 1):                      # (a rate of 1 or more stays with gcn.dropout and what torch makes of it)
                 # GNN(feature_dropout="fused"): dropout(act(...)) leaves the layer's launch, its mask from the counter RNG
-                seed, stream = gcn._next_mask_stream()
                 return sparse.gcnii_step(adjacency, features, self.H0.value, self.a, transform, relu=self.activation is relu,
-                                         backward=getattr(gcn, "gcnii_backward", "composed"), dropout=(self.dropout, seed, stream), **wgrad)
+                                         backward=_switch(gcn, "gcnii_backward"), dropout=gcn._mask_triple(self.dropout), **wgrad)
             out = sparse.gcnii_step(adjacency, features, self.H0.value, self.a, transform, relu=self.activation is relu,
-                                    backward=getattr(gcn, "gcnii_backward", "composed"), **wgrad)
+                                    backward=_switch(gcn, "gcnii_backward"), **wgrad)
             return gcn.dropout(out if fused_act else self.activation(out), self.dropout)
         tradeoff = sparse.ppr_step(adjacency, features, self.H0.value, self.a)
         return gcn.dropout(self.activation(torch.matmul(tradeoff, transform)), self.dropout)
@@ -888,7 +867,7 @@ class GCNIISpectralPreservingLayer(GCNIILayer):
 
     def _fused_spectral(self, gcn, features, adjacency) -> bool:
         """Whether GNN(gcnii_spectral="fused") applies to this forward (no tensor is read, no mask stream is drawn)."""
-        return (getattr(gcn, "gcnii_spectral", "composed") == "fused" and type(self) is GCNIISpectralPreservingLayer
+        return (_switch(gcn, "gcnii_spectral") == "fused" and type(self) is GCNIISpectralPreservingLayer
                 and (self.activation is relu or self.activation is linear)
                 and isinstance(features, torch.Tensor) and features.is_cuda and features.dtype == torch.float32
                 and isinstance(self.a, (int, float)) and not isinstance(self.a, bool)
@@ -898,10 +877,10 @@ class GCNIISpectralPreservingLayer(GCNIILayer):
     def __forward__(self, gcn, features):
         adjacency = gcn.get_adjacency(self.graph_dropout)
         if self._fused_spectral(gcn, features, adjacency):
-            triple = (self.dropout,) + tuple(gcn._next_mask_stream()) if gcn.is_training() and self.dropout != 0 else None
+            triple = gcn._mask_triple(self.dropout) if gcn.is_training() and self.dropout != 0 else None
             return sparse.gcnii_step_spectral(adjacency, features, self.H0.value, self.a, self._transform(), self.bias,
                                               relu=self.activation is relu, dropout=triple,
-                                              backward=getattr(gcn, "gcnii_backward", "composed"))
+                                              backward=_switch(gcn, "gcnii_backward"))
         b = self.beta_transformer(self.l / (self.k + 1))
         eye = torch.eye(self.W.shape[1], device=self.W.device, dtype=self.W.dtype)
         tradeoff = sparse.ppr_step(adjacency, features, self.H0.value, self.a)
@@ -966,8 +945,8 @@ class NGCFLayer(Layer):
     def _fused_ngcf(self, gcn, features) -> bool:
         """Whether GNN(ngcf_layer="fused") applies to this forward (no tensor is read, no mask stream is drawn); at an input width of
         128 only together with GNN(ngcf_wide="fused")."""
-        widths = sparse.NGCF_FUSED_WIDTHS + (sparse.NGCF_WIDE_WIDTHS if getattr(gcn, "ngcf_wide", "composed") == "fused" else ())
-        return (getattr(gcn, "ngcf_layer", "composed") == "fused" and type(self) is NGCFLayer
+        widths = sparse.NGCF_FUSED_WIDTHS + (sparse.NGCF_WIDE_WIDTHS if _switch(gcn, "ngcf_wide") == "fused" else ())
+        return (_switch(gcn, "ngcf_layer") == "fused" and type(self) is NGCFLayer
                 and (self.activation is leaky_relu or self.activation is relu or self.activation is linear)
                 and isinstance(self.b1, torch.Tensor) == isinstance(self.b2, torch.Tensor)
                 and isinstance(features, torch.Tensor) and features.is_cuda and features.dtype == torch.float32
@@ -980,20 +959,20 @@ class NGCFLayer(Layer):
             act = "leaky" if self.activation is leaky_relu else "relu" if self.activation is relu else "none"
             b1, b2 = (self.b1, self.b2) if isinstance(self.b1, torch.Tensor) else (None, None)
             # GNN(ngcf_backward=): named only where it is not the default, so the default's calls stay today's, argument for argument
-            how = getattr(gcn, "ngcf_backward", "composed")
+            how = _switch(gcn, "ngcf_backward")
             back = dict() if how == "composed" else dict(backward=how)
             # GNN(ngcf_wide=): likewise, and only at the widths it acts on
-            wide = getattr(gcn, "ngcf_wide", "composed")
+            wide = _switch(gcn, "ngcf_wide")
             if wide != "composed" and features.shape[1] in sparse.NGCF_WIDE_WIDTHS:
                 back["wide"] = wide
             # GNN(ngcf_wide_backward=): likewise
-            wide_back = getattr(gcn, "ngcf_wide_backward", "composed")
+            wide_back = _switch(gcn, "ngcf_wide_backward")
             if wide_back != "composed" and features.shape[1] in sparse.NGCF_WIDE_WIDTHS:
                 back["wide_backward"] = wide_back
             if not gcn.is_training() or self.dropout == 0:
                 return sparse.ngcf_step(self.adjacency, features, self.W1, b1, self.W2, b2, activation=act, **back)
-            if getattr(gcn, "feature_dropout", "torch") == "fused" and 0 < self.dropout < 1:
-                triple = (self.dropout,) + tuple(gcn._next_mask_stream())
+            if _switch(gcn, "feature_dropout") == "fused" and 0 < self.dropout < 1:
+                triple = gcn._mask_triple(self.dropout)
                 return sparse.ngcf_step(self.adjacency, features, self.W1, b1, self.W2, b2, activation=act, dropout=triple, **back)
             summed = sparse.ngcf_step(self.adjacency, features, self.W1, b1, self.W2, b2, activation=act, normalize=False, **back)
             return torch.nn.functional.normalize(gcn.dropout(summed, self.dropout), dim=1, eps=1e-12)

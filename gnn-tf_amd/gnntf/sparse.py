@@ -365,6 +365,34 @@ def _same_device(g, *tensors):
             raise Exception(f"spmm: operand on {t.device}, the graph lives on {g.device}")
 
 
+def _one_of(what, keyword, value, allowed):
+    """Raises unless ``value`` is one of ``allowed``, the values the keyword ``keyword`` of ``what`` takes."""
+    if value not in allowed:
+        raise Exception(f"{what}: {keyword} must be one of " + ", ".join(repr(v) for v in allowed))
+
+
+def _need_symbol(what, entry, keyword=None):
+    """Raises where libgnx.so lacks ``entry``; ``keyword``: the opt-in of ``what`` that asked for it (it goes into the message)."""
+    if not nat.has_symbol(entry):      # (a library without the entry raises: nothing falls back)
+        asked = f"{what}:" if keyword is None else f"{what}: {keyword}=\"fused\""
+        raise Exception(f"{asked} needs {entry}, which this libgnx.so does not export: rebuild the library")
+
+
+def _bias_row(what, bias, width):
+    """``bias`` ([width] / [1, width]) as the contiguous f32 row a launch of ``what`` reads; None stays None."""
+    if bias is None:
+        return None
+    b = bias.to(torch.float32).reshape(-1).contiguous()
+    if b.numel() != width:
+        raise Exception(f"{what}: bias width mismatch")
+    return b
+
+
+def _row_stride(W):
+    """The leading dimension of the weight matrix ``W`` (torch calls a one-row matrix contiguous whatever its row stride says)."""
+    return W.stride(0) if W.shape[0] > 1 else W.shape[1]
+
+
 def _mix_operand(H0, shape, bias=False):
     """(H0 as f32 rows, ldh0) of a launch whose result has ``shape``; (None, 0) without one.  ``bias``: one row serves every output
     row (ldh0 = 0)."""
@@ -1064,9 +1092,7 @@ def _dense_launch(X, W, bias, relu):
     if X.shape[1] != W.shape[0]:
         raise Exception(f"dense: features have {X.shape[1]} columns, the weights expect {W.shape[0]}")
     out = torch.empty((X.shape[0], W.shape[1]), dtype=torch.float32, device=X.device)
-    b = None if bias is None else bias.to(torch.float32).reshape(-1).contiguous()
-    if b is not None and b.numel() != W.shape[1]:
-        raise Exception("dense: bias width mismatch")
+    b = _bias_row("dense", bias, W.shape[1])
     with nat.on_device(X.device):
         nat.check(nat.lib().gnx_dense(nat.ptr(X), X.stride(0), X.shape[0], X.shape[1], nat.ptr(W), W.stride(0), W.shape[1], nat.ptr(b),
                                       nat.ACT_RELU if relu else nat.ACT_NONE, nat.ptr(out), out.stride(0), nat.current_stream()))
@@ -1078,18 +1104,28 @@ def _relu_mask(g, out):
     return torch.ops.aten.threshold_backward(g.contiguous(), out, 0.0)
 
 
-def _dense_wgrad(X, G):
-    """dW = X^T . G on the matrix cores (gnx_dense_wgrad): row slabs, partial sums added in a fixed order."""
-    X, G = _as_f32_rows(X), _as_f32_rows(G)
+def _wgrad_slabs(n, floats):
+    """Row slabs of a weight gradient over ``n`` rows whose partial sums hold ``floats`` floats each: one per 256 rows, at most 2048,
+    the scratch capped at 1 GiB (include/gnx.h, gnx_dense_wgrad)."""
+    return max(1, min(2048, (n + 255) // 256, (1 << 28) // max(floats, 1)))
+
+
+def _dense_wgrad_launch(entry, X, G, graph=(), din=()):
+    """The scratch, dW and the call of gnx_dense_wgrad or, with the graph handle and the input mask's triple, of gnx_dense_wgrad_drop:
+    the same slabs and the same summation order.  ``X`` / ``G`` are f32 rows."""
     n, F = X.shape
     O = G.shape[1]
-    slabs = max(1, min(2048, (n + 255) // 256, (1 << 28) // max(F * O, 1)))        # scratch capped at 1 GiB
-    work = torch.empty(slabs * F * O, dtype=torch.float32, device=X.device)
+    work = torch.empty(_wgrad_slabs(n, F * O) * F * O, dtype=torch.float32, device=X.device)
     dW = torch.empty((F, O), dtype=torch.float32, device=X.device)
     with nat.on_device(X.device):
-        nat.check(nat.lib().gnx_dense_wgrad(nat.ptr(X), X.stride(0), nat.ptr(G), G.stride(0), n, F, O, nat.ptr(dW), nat.ptr(work),
-                                            work.numel(), nat.current_stream()))
+        nat.check(entry(*graph, nat.ptr(X), X.stride(0), nat.ptr(G), G.stride(0), n, F, O, *din, nat.ptr(dW), nat.ptr(work), work.numel(),
+                        nat.current_stream()))
     return dW
+
+
+def _dense_wgrad(X, G):
+    """dW = X^T . G on the matrix cores (gnx_dense_wgrad): row slabs, partial sums added in a fixed order."""
+    return _dense_wgrad_launch(nat.lib().gnx_dense_wgrad, _as_f32_rows(X), _as_f32_rows(G))
 
 
 class _DenseAct(torch.autograd.Function):
@@ -1237,9 +1273,7 @@ def _dense_drop_launch(graph: DeviceGraph, X, W, bias, relu, din, dout):
     if X.shape[1] != W.shape[0]:
         raise Exception(f"dense_step: features have {X.shape[1]} columns, the weights expect {W.shape[0]}")
     out = torch.empty((X.shape[0], W.shape[1]), dtype=torch.float32, device=X.device)
-    b = None if bias is None else bias.to(torch.float32).reshape(-1).contiguous()
-    if b is not None and b.numel() != W.shape[1]:
-        raise Exception("dense_step: bias width mismatch")
+    b = _bias_row("dense_step", bias, W.shape[1])
     with nat.on_device(X.device):
         nat.check(nat.lib().gnx_dense_drop(graph.handle, nat.ptr(X), X.stride(0), X.shape[0], X.shape[1], nat.ptr(W), W.stride(0), W.shape[1],
                                            nat.ptr(b), nat.ACT_RELU if relu else nat.ACT_NONE, *_dropout_args(din), *_dropout_args(dout),
@@ -1255,15 +1289,7 @@ def _dense_wgrad_drop(graph: DeviceGraph, X, G, din):
     _need_symbol("dense_step", "gnx_dense_wgrad_drop")
     X, G = _as_f32_rows(X), _as_f32_rows(G)
     _same_device(graph, X, G)
-    n, F = X.shape
-    O = G.shape[1]
-    slabs = max(1, min(2048, (n + 255) // 256, (1 << 28) // max(F * O, 1)))        # _dense_wgrad's scratch: the same slabs, the same bits
-    work = torch.empty(slabs * F * O, dtype=torch.float32, device=X.device)
-    dW = torch.empty((F, O), dtype=torch.float32, device=X.device)
-    with nat.on_device(X.device):
-        nat.check(nat.lib().gnx_dense_wgrad_drop(graph.handle, nat.ptr(X), X.stride(0), nat.ptr(G), G.stride(0), n, F, O, *din, nat.ptr(dW),
-                                                 nat.ptr(work), work.numel(), nat.current_stream()))
-    return dW
+    return _dense_wgrad_launch(nat.lib().gnx_dense_wgrad_drop, X, G, (graph.handle,), din)
 
 
 class _DenseStep(torch.autograd.Function):
@@ -1382,15 +1408,13 @@ GCNII_FUSED_WIDTHS = (16, 32, 64)
 
 def _edge_dropout(what, edge_dropout) -> bool:
     """Whether ``edge_dropout`` asks for the fused form; raises on anything but the two names."""
-    if edge_dropout not in GCNII_EDGE_DROPOUTS:
-        raise Exception(f"{what}: edge_dropout must be one of " + ", ".join(repr(e) for e in GCNII_EDGE_DROPOUTS))
+    _one_of(what, "edge_dropout", edge_dropout, GCNII_EDGE_DROPOUTS)
     return edge_dropout == "fused"
 
 
 def _weight_gradient(what, weight_gradient) -> bool:
     """Whether ``weight_gradient`` asks for the recomputed form; raises on anything but the two names."""
-    if weight_gradient not in GCNII_WEIGHT_GRADIENTS:
-        raise Exception(f"{what}: weight_gradient must be one of " + ", ".join(repr(w) for w in GCNII_WEIGHT_GRADIENTS))
+    _one_of(what, "weight_gradient", weight_gradient, GCNII_WEIGHT_GRADIENTS)
     return weight_gradient == "recomputed"
 
 
@@ -1409,8 +1433,7 @@ def gcnii_wgrad(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, G: 
     n = H.shape[0]
     if hub_rows is None and g.n_hub_rows > 0:
         hub_rows = torch.empty((n, C), dtype=torch.float32, device=H.device)
-    slabs = max(1, min(2048, (n + 255) // 256, (1 << 28) // (C * C)))        # _dense_wgrad's sizing
-    work = torch.empty(slabs * C * C, dtype=torch.float32, device=H.device)
+    work = torch.empty(_wgrad_slabs(n, C * C) * C * C, dtype=torch.float32, device=H.device)
     dM = torch.empty((C, C), dtype=torch.float32, device=H.device)
     entry = nat.lib().gnx_gcnii_wgrad_bf16 if bf16 else nat.lib().gnx_gcnii_wgrad
     with nat.on_device(H.device):
@@ -1544,16 +1567,13 @@ def gcnii_step(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, M: t
     and agrees to float32 rounding at 16 / 32 / 64 (matrix-core transform order).  A dropped entry is skipped, not multiplied by 0
     (the DroppedAdjacency precondition of finite features).  Constant adjacencies, calls without autograd, bf16 storage and
     ``weight_gradient="recomputed"`` keep today's path whatever it says."""
-    if backward not in GCNII_BACKWARDS:
-        raise Exception("gcnii_step: backward must be one of " + ", ".join(repr(b) for b in GCNII_BACKWARDS))
+    _one_of("gcnii_step", "backward", backward, GCNII_BACKWARDS)
     recompute = _weight_gradient("gcnii_step", weight_gradient)
     fused_edge = _edge_dropout("gcnii_step", edge_dropout) and not recompute and _fused_edge_applies(adj, H, H0, M)
     if dropout is not None:
         if _bf16(storage) or _bf16(out_storage):
             raise Exception("gcnii_step: dropout belongs to training, bf16 storage is inference only")
-        dropout = _dropout_triple(dropout, "gcnii_step")
-        if dropout is not None:
-            return _gcnii_step_dropped(adj, H, H0, a, M, relu, backward, dropout, recompute, fused_edge)
+        dropout = _dropout_triple(dropout, "gcnii_step")            # (None again for a rate of 0)
     if _bf16(storage):
         _no_grad_for_bf16("gcnii_step", H, H0, M)
         return _gcnii_launch_bf16(adj, H, H0, a, M, relu, _bf16(out_storage))
@@ -1561,11 +1581,12 @@ def gcnii_step(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, M: t
         raise Exception("gcnii_step: a bf16 result needs storage=torch.bfloat16")
     if torch.is_grad_enabled() and (H.requires_grad or H0.requires_grad or M.requires_grad):
         if fused_edge:                                              # weights made inside the fused launch itself (gnx_gcnii_step_dropped)
-            return _GCNIIStep.apply(H, H0, M, adj, float(a), bool(relu), backward, None, False, True)
+            return _GCNIIStep.apply(H, H0, M, adj, float(a), bool(relu), backward, dropout, False, True)
         if isinstance(adj, DroppedAdjacency):                       # weights made inside the SpMM: the generic composition knows how
-            return dense(ppr_step(adj, H, H0, a), M, None, relu)
-        return _GCNIIStep.apply(H, H0, M, adj, float(a), bool(relu), backward, None, recompute and H.shape[-1] in GCNII_FUSED_WIDTHS)
-    return _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=False)[0]
+            out = dense(ppr_step(adj, H, H0, a), M, None, relu)
+            return out if dropout is None else feature_dropout(adj.graph, out, *dropout)
+        return _GCNIIStep.apply(H, H0, M, adj, float(a), bool(relu), backward, dropout, recompute and H.shape[-1] in GCNII_FUSED_WIDTHS)
+    return _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=False, dropout=dropout)[0]
 
 
 def _fused_edge_applies(adj, H, H0, M) -> bool:
@@ -1573,25 +1594,9 @@ def _fused_edge_applies(adj, H, H0, M) -> bool:
     return isinstance(adj, DroppedAdjacency) and all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 for t in (H, H0, M))
 
 
-def _gcnii_step_dropped(adj, H, H0, a, M, relu, backward, dropout, recompute=False, fused_edge=False):
-    """gcnii_step with a feature dropout of rate > 0 (``dropout`` = the checked triple)."""
-    if torch.is_grad_enabled() and (H.requires_grad or H0.requires_grad or M.requires_grad):
-        if fused_edge:
-            return _GCNIIStep.apply(H, H0, M, adj, float(a), bool(relu), backward, dropout, False, True)
-        if isinstance(adj, DroppedAdjacency):
-            return feature_dropout(adj.graph, dense(ppr_step(adj, H, H0, a), M, None, relu), *dropout)
-        return _GCNIIStep.apply(H, H0, M, adj, float(a), bool(relu), backward, dropout, recompute and H.shape[-1] in GCNII_FUSED_WIDTHS)
-    return _gcnii_launch(adj, H, H0, a, M, relu, keep_mixed=False, dropout=dropout)[0]
-
-
 GCN_LAYERS = ("composed", "fused")
 GCN_BACKWARDS = ("composed", "fused")
 GCN_FUSED_WIDTHS = (16, 32, 64)       # C_in of the one-launch form of gnx_gcn_step; its C_out is any width up to C_in
-
-
-def _need_symbol(what, entry):
-    if not nat.has_symbol(entry):      # (a library without the entry raises: nothing falls back)
-        raise Exception(f"{what}: needs {entry}, which this libgnx.so does not export: rebuild the library")
 
 
 def _gcn_launch(adj: Adjacency, X, W, bias, relu, keep_agg, dropout=None, fused_edge=False, spectral=False):
@@ -1611,9 +1616,7 @@ def _gcn_launch(adj: Adjacency, X, W, bias, relu, keep_agg, dropout=None, fused_
     C_out = W.shape[1]
     if g.n_rows != g.n_cols or n != g.n_rows or W.shape[0] != C_in or C_in < 1 or C_out < 1:
         raise Exception("gcn_step: shape mismatch")
-    b = None if bias is None else bias.to(torch.float32).reshape(-1).contiguous()
-    if b is not None and b.numel() != C_out:
-        raise Exception("gcn_step: bias width mismatch")
+    b = _bias_row("gcn_step", bias, C_out)
     one_launch = C_in in GCN_FUSED_WIDTHS and C_out <= C_in and X.stride(0) % 4 == 0 and X.data_ptr() % 16 == 0
     out = torch.empty((n, C_out), dtype=torch.float32, device=X.device)
     rows = torch.empty((n, C_in), dtype=torch.float32, device=X.device) if keep_agg or not one_launch or g.n_hub_rows > 0 else None
@@ -1649,63 +1652,78 @@ class _GCNStep(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, W, bias, adj, relu, dropout, fused_edge, backward="composed"):
-        ctx.adj, ctx.relu, ctx.dropout, ctx.fused_edge, ctx.fused_backward = adj, relu, dropout, fused_edge, backward == "fused"
-        ctx.bias_shape = None if bias is None else tuple(bias.shape)
-        out, agg = _gcn_launch(adj, X, W, bias, relu, keep_agg=True, dropout=dropout, fused_edge=fused_edge)
-        if ctx.fused_backward:      # (agg is neither an input nor an output of the node: it may live on ctx, which can let it go early)
-            ctx.agg = agg
-            ctx.save_for_backward(W, out if relu or dropout is not None else None)
-            return out
-        ctx.save_for_backward(agg, W, out if relu or dropout is not None else None)
-        return out
+        return _gcn_node_forward(ctx, X, W, bias, adj, relu, dropout, fused_edge, backward, spectral=False)
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.fused_backward:
-            return _gcn_fused_backward(ctx, g) + (None, None, None, None, None)
-        agg, W, out = ctx.saved_tensors
-        g = _gated_gradient(ctx.adj.graph, g, out, ctx.relu, ctx.dropout)
-        gW = _dense_wgrad(agg, g) if ctx.needs_input_grad[1] else None
-        gb = g.sum(dim=0).reshape(ctx.bias_shape) if ctx.bias_shape is not None and ctx.needs_input_grad[2] else None
-        gX = None
-        if ctx.needs_input_grad[0]:
-            gT = _dense_launch(g, W.t().contiguous(), None, False)
-            del g                                           # (the gated gradient is done with: the transposed SpMM runs without it)
-            gX = _launch(ctx.adj, gT, None, 1.0, 0.0, nat.ACT_NONE, transposed=True)
-        return gX, gW, gb, None, None, None, None, None
+        return _gcn_node_backward(ctx, g) + (None, None, None, None, None)
 
 
-def _gcn_fused_backward(ctx, g):
-    """(dX, dW, db) of _GCNStep with ``backward="fused"``.  The gated gradient g' has the values of the composed backward's; where dX is
-    wanted it lives in rows of stride roundup4(C_out) (the gate pass writes them there; the relu mask and the ungated gradient take one
-    narrow copy when C_out is no multiple of 4), which gnx_dense_wgrad reads as an [n, C_out] view.  The column sums run over contiguous
-    rows, as the composed backward's do (torch picks its reduction by the strides).  agg = A . X [n, C_in] is released once dW is made,
-    before dX [n, C_in] is allocated."""
-    W, out = ctx.saved_tensors
-    agg, ctx.agg = ctx.agg, None
-    if agg is None:
-        raise Exception("gcn_step(backward=\"fused\"): the node let its aggregated rows go in its first backward; run the forward again "
-                        "(or use backward=\"composed\" where a graph is retained)")
+def _gcn_node_forward(ctx, X, W, bias, adj, relu, dropout, fused_edge, backward, spectral):
+    """The forward of _GCNStep and, with ``spectral``, of _GCNSpectralStep: the launch with agg = A . X kept, and what the backward
+    reads -- (agg, W, third) with third = the output where a gate needs it, the spectral layer's gate words instead."""
+    ctx.adj, ctx.relu, ctx.dropout, ctx.fused_edge, ctx.fused_backward = adj, relu, dropout, fused_edge, backward == "fused"
+    ctx.spectral, ctx.bias_shape = spectral, None if bias is None else tuple(bias.shape)
+    how = dict(spectral=True) if spectral else dict()      # (named only where it is not the default: gcn_step's call otherwise)
+    out, agg, *gate = _gcn_launch(adj, X, W, bias, relu, keep_agg=True, dropout=dropout, fused_edge=fused_edge, **how)
+    third = gate[0] if spectral else out if relu or dropout is not None else None
+    if ctx.fused_backward:      # (agg is neither an input nor an output of the node: it may live on ctx, which can let it go early)
+        ctx.agg = agg
+        ctx.save_for_backward(W, third)
+        return out
+    ctx.save_for_backward(agg, W, third)
+    return out
+
+
+def _gcn_node_backward(ctx, g):
+    """(dX, dW, db) of _GCNStep and _GCNSpectralStep: the gate, dW = agg^T G' (gnx_dense_wgrad), then dX from G' -- composed (gnx_dense,
+    then the transposed SpMM, which runs with G' already let go) or, with ``backward="fused"``, ONE launch (gcn_step_back).  Under
+    ``backward="fused"`` the node hands over the agg it kept on ``ctx`` -- once: a second backward raises -- and the rows are released
+    once dW is made, before dX [n, C_in] is allocated; where dX is wanted G' then lives in rows of stride roundup4(C_out), which
+    gnx_dense_wgrad reads as an [n, C_out] view.  The spectral gate pass writes them there and makes db itself.  _GCNStep's gate pass
+    writes them there too, while its relu mask and its ungated gradient take one narrow copy when C_out is no multiple of 4; its
+    column sums run over contiguous rows whichever backward it is (torch picks its reduction by the strides)."""
+    saved = ctx.saved_tensors
+    if ctx.fused_backward:
+        agg, ctx.agg = ctx.agg, None
+        if agg is None:
+            what = "gcn_step_spectral" if ctx.spectral else "gcn_step"
+            raise Exception(f"{what}(backward=\"fused\"): the node let its aggregated rows go in its first backward; run the forward again "
+                            "(or use backward=\"composed\" where a graph is retained)")
+        W, third = saved
+    else:
+        agg, W, third = saved
+    del saved
     want_X = ctx.needs_input_grad[0]
     want_b = ctx.bias_shape is not None and ctx.needs_input_grad[2]
-    C_out = g.shape[1]
-    padded = want_X and C_out % 4 != 0
     gb = None
-    if ctx.dropout is not None:
-        G = _feature_dropout_back(ctx.adj.graph, g, out, *ctx.dropout, relu=ctx.relu, padded=padded)
-        if want_b:
-            gb = G.contiguous().sum(dim=0)
+    if ctx.spectral:
+        G, gb = _gcnii_spectral_gate(ctx.adj.graph, g, third, ctx.relu, ctx.dropout, padded=ctx.fused_backward and want_X)
+        gb = gb if want_b else None
     else:
-        G = (_relu_mask(g, out) if ctx.relu else g).contiguous()
-        if want_b:
-            gb = G.sum(dim=0)
-        if padded:
-            narrow, G = G, _padded_rows(G.shape[0], C_out, G.device)
-            G.copy_(narrow)
-            del narrow
+        C_out = g.shape[1]
+        padded = ctx.fused_backward and want_X and C_out % 4 != 0
+        if ctx.dropout is not None:
+            G = _feature_dropout_back(ctx.adj.graph, g, third, *ctx.dropout, relu=ctx.relu, padded=padded)
+            if want_b:
+                gb = G.contiguous().sum(dim=0)
+        else:
+            G = (_relu_mask(g, third) if ctx.relu else g).contiguous()
+            if want_b:
+                gb = G.sum(dim=0)
+            if padded:
+                narrow, G = G, _padded_rows(G.shape[0], C_out, G.device)
+                G.copy_(narrow)
+                del narrow
     gW = _dense_wgrad(agg, G) if ctx.needs_input_grad[1] else None
-    del agg                                                 # (the last reference: the rows are free before dX is made)
-    gX = _gcn_back_launch(ctx.adj, G, W.t().contiguous(), ctx.fused_edge) if want_X else None
+    del agg                                                 # (under backward="fused" the last reference: the rows are free before dX is made)
+    gX = None
+    if want_X and ctx.fused_backward:
+        gX = _gcn_back_launch(ctx.adj, G, W.t().contiguous(), ctx.fused_edge)
+    elif want_X:
+        gT = _dense_launch(G, W.t().contiguous(), None, False)
+        del G                                               # (the gated gradient is done with: the transposed SpMM runs without it)
+        gX = _launch(ctx.adj, gT, None, 1.0, 0.0, nat.ACT_NONE, transposed=True)
     return gX, gW, None if gb is None else gb.reshape(ctx.bias_shape)
 
 
@@ -1731,8 +1749,7 @@ def _gcn_back_launch(adj: Adjacency, G, Wt, fused_edge=False):
         work = torch.empty((n, C_out), dtype=torch.float32, device=G.device)
     else:
         work = None
-    ldwt = Wt.stride(0) if C_out > 1 else C_in             # (torch calls a one-row matrix contiguous whatever its row stride says)
-    tail = (nat.ptr(G), G.stride(0), C_out, nat.ptr(Wt), ldwt, C_in, nat.ptr(dX), dX.stride(0), nat.ptr(work),
+    tail = (nat.ptr(G), G.stride(0), C_out, nat.ptr(Wt), _row_stride(Wt), C_in, nat.ptr(dX), dX.stride(0), nat.ptr(work),
             0 if work is None else work.numel(), nat.current_stream())
     with nat.on_device(G.device):
         if fused_edge:
@@ -1763,14 +1780,25 @@ def gcn_step_back(adj: Adjacency, G: torch.Tensor, W: torch.Tensor, edge_dropout
     return _gcn_back_launch(adj, G, W.t().contiguous(), fused_edge)
 
 
+def _dense_or_torch(X, W, bias, relu):
+    """act(X . W + bias), the transform of a composed layer: the dense kernel on device tensors, torch's ops on CPU tensors."""
+    if X.is_cuda:
+        return dense(X, W, bias, relu)
+    out = torch.matmul(X, W) + (bias if bias is not None else 0)
+    return torch.relu(out) if relu else out
+
+
+def _spectral_tail(activated, bias, dropout):
+    """2 * dropout(activated - bias), the elementwise tail of a composed spectral layer, with TORCH's dropout at the rate of ``dropout``
+    = (p, seed, stream) or None."""
+    y = activated - bias
+    p = 0.0 if dropout is None else float(dropout[0])
+    return 2 * (torch.nn.functional.dropout(y, p=p, training=True) if p != 0 else y)
+
+
 def _gcn_composed(adj, X, W, bias, relu, dropout):
     """The layer as today's ops: spmm, then the dense kernel with bias and relu (CPU tensors: torch), then the mask as a pass of its own."""
-    agg = spmm(adj, X)
-    if agg.is_cuda:
-        out = dense(agg, W, bias, relu)
-    else:
-        out = torch.matmul(agg, W) + (bias if bias is not None else 0)
-        out = torch.relu(out) if relu else out
+    out = _dense_or_torch(spmm(adj, X), W, bias, relu)
     if dropout is None or float(dropout[0]) == 0:
         return out
     if out.is_cuda:
@@ -1801,8 +1829,7 @@ def gcn_step(adj: Adjacency, X: torch.Tensor, W: torch.Tensor, bias=None, relu=T
     CPU tensors, an adjacency with a diagonal and a DroppedAdjacency without ``edge_dropout="fused"`` run ``spmm`` + ``dense``:
     today's calls and bits."""
     fused_edge = _edge_dropout("gcn_step", edge_dropout)
-    if backward not in GCN_BACKWARDS:
-        raise Exception("gcn_step: backward must be one of " + ", ".join(repr(b) for b in GCN_BACKWARDS))
+    _one_of("gcn_step", "backward", backward, GCN_BACKWARDS)
     tensors = (X, W) if bias is None else (X, W, bias)
     if (not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors) or adj.diag is not None
             or (isinstance(adj, DroppedAdjacency) and not fused_edge)):
@@ -1840,11 +1867,6 @@ def _ngcf_rows_fit(widths, C_in, C_out, X, A=None):
             and (A is None or (A.is_contiguous() and A.data_ptr() % 16 == 0)))
 
 
-def _ngcf_need_symbol(keyword, entry):
-    if not nat.has_symbol(entry):      # (a library without the entry raises: nothing falls back)
-        raise Exception(f"ngcf_step: {keyword}=\"fused\" needs {entry}, which this libgnx.so does not export: rebuild the library")
-
-
 def _ngcf_check_saved(n, C_out, activation, gate, y, rnorm):
     """What the backward reads of the forward's: the gate words, and the reciprocal norms with the output they go with."""
     if activation != "none" and (gate is None or gate.dtype != torch.int32 or tuple(gate.shape) != (n, 2 * _gate_words(C_out)) or not gate.is_contiguous()):
@@ -1874,12 +1896,7 @@ def _ngcf_launch(adj: Adjacency, X, W1, b1, W2, b2, activation, keep, dropout=No
     C_out = W1.shape[1]
     if g.n_rows != g.n_cols or n != g.n_rows or tuple(W1.shape) != (C_in, C_out) or tuple(W2.shape) != (C_in, C_out) or C_in < 1 or C_out < 1:
         raise Exception("ngcf_step: shape mismatch")
-    biases = []
-    for b in (b1, b2):
-        b = None if b is None else b.to(torch.float32).reshape(-1).contiguous()
-        if b is not None and b.numel() != C_out:
-            raise Exception("ngcf_step: bias width mismatch")
-        biases.append(b)
+    biases = [_bias_row("ngcf_step", b, C_out) for b in (b1, b2)]
     one_launch = _ngcf_rows_fit(NGCF_FUSED_WIDTHS, C_in, C_out, X)
     out = torch.empty((n, C_out), dtype=torch.float32, device=X.device)
     agg = torch.empty((n, C_in), dtype=torch.float32, device=X.device) if keep else None
@@ -1888,17 +1905,16 @@ def _ngcf_launch(adj: Adjacency, X, W1, b1, W2, b2, activation, keep, dropout=No
     rnorm = torch.empty(n, dtype=torch.float32, device=X.device) if keep and normalize else None
     rows_launch = _ngcf_wide_fusable(wide, X, C_in, C_out)
     if rows_launch:
-        _ngcf_need_symbol("wide", "gnx_step_wide_ngcf")
+        _need_symbol("ngcf_step", "gnx_step_wide_ngcf", keyword="wide")
         floats = 0 if keep else (n * C_in + 3) // 4 * 4
     else:
         floats = _ngcf_work_floats(n, C_in, C_out, g.n_hub_rows if one_launch else n, keep)
     work = torch.empty(floats, dtype=torch.float32, device=X.device) if floats else None
     p, seed, stream = _dropout_args(dropout)
-    ldw = lambda W: W.stride(0) if C_in > 1 else C_out     # (torch calls a one-row matrix contiguous whatever its row stride says)
     with nat.on_device(X.device):
         entry = nat.lib().gnx_step_wide_ngcf if rows_launch else nat.lib().gnx_ngcf_step
-        nat.check(entry(g.handle, nat.ptr(adj.vals), nat.ptr(X), X.stride(0), C_in, nat.ptr(W1), ldw(W1), nat.ptr(W2), ldw(W2),
-                        C_out, nat.ptr(biases[0]), nat.ptr(biases[1]), NGCF_ACTIVATIONS[activation], p, seed, stream,
+        nat.check(entry(g.handle, nat.ptr(adj.vals), nat.ptr(X), X.stride(0), C_in, nat.ptr(W1), _row_stride(W1), nat.ptr(W2),
+                        _row_stride(W2), C_out, nat.ptr(biases[0]), nat.ptr(biases[1]), NGCF_ACTIVATIONS[activation], p, seed, stream,
                         1 if normalize else 0, nat.ptr(out), out.stride(0), nat.ptr(agg), nat.ptr(gate), nat.ptr(rnorm),
                         nat.ptr(work), floats, nat.current_stream()))
     return out, agg, gate, rnorm
@@ -1959,13 +1975,12 @@ def _ngcf_back_launch(adj: Adjacency, g, y, rnorm, gate, activation, dropout, X,
     floats = work_floats(n, C_out) if any(want_db) else 0
     work = new(floats) if floats else None
     p, seed, stream = _dropout_args(dropout)
-    ldw = lambda W: W.stride(0) if C_in > 1 else C_out     # (torch calls a one-row matrix contiguous whatever its row stride says)
     with nat.on_device(g.device):
         nat.check(getattr(nat.lib(), entry)(
             graph.handle, nat.ptr(adj.transposed_values()) if want_dX else None, nat.ptr(g), g.stride(0), nat.ptr(y), 0 if y is None else y.stride(0),
             nat.ptr(rnorm), nat.ptr(gate) if activation != "none" else None, C_out, NGCF_ACTIVATIONS[activation], p, seed, stream, nat.ptr(X),
-            X.stride(0), nat.ptr(A), C_in, nat.ptr(W1), ldw(W1), nat.ptr(W2), ldw(W2), nat.ptr(G1), nat.ptr(G2), G1.stride(0), nat.ptr(P), nat.ptr(db1),
-            nat.ptr(db2), nat.ptr(dA), nat.ptr(R), nat.ptr(dX), C_in, nat.ptr(work), floats, nat.current_stream()))
+            X.stride(0), nat.ptr(A), C_in, nat.ptr(W1), _row_stride(W1), nat.ptr(W2), _row_stride(W2), nat.ptr(G1), nat.ptr(G2), G1.stride(0),
+            nat.ptr(P), nat.ptr(db1), nat.ptr(db2), nat.ptr(dA), nat.ptr(R), nat.ptr(dX), C_in, nat.ptr(work), floats, nat.current_stream()))
     return dict(G1=G1, G2=G2, P=P, db1=db1, db2=db2, dA=dA, R=R, dX=dX)
 
 
@@ -1982,7 +1997,7 @@ def _ngcf_wide_back_fusable(wide_backward, X, A, W1):
 def _ngcf_wide_back_launch(adj: Adjacency, g, y, rnorm, gate, activation, dropout, X, A, W1, W2, want_P=True, want_db=(True, True), want_dX=True):
     """gnx_step_back_wide_ngcf, one call: what _ngcf_back_launch returns, from the gate pass, one row-local launch and the transposed SpMM
     at C_in = 128.  A library without the entry raises: nothing falls back."""
-    _ngcf_need_symbol("wide_backward", "gnx_step_back_wide_ngcf")
+    _need_symbol("ngcf_step", "gnx_step_back_wide_ngcf", keyword="wide_backward")
     return _ngcf_back_launch(adj, g, y, rnorm, gate, activation, dropout, X, A, W1, W2, want_P=want_P, want_db=want_db, want_dX=want_dX,
                              entry="gnx_step_back_wide_ngcf", work_floats=_ngcf_wide_back_work_floats)
 
@@ -2051,11 +2066,7 @@ def _ngcf_composed(adj, X, W1, b1, W2, b2, activation, dropout, normalize):
     """The layer as today's ops: spmm, a torch multiply, two transforms (the dense kernel on the device), torch's activations and sum,
     the mask as a pass of its own (torch's dropout on CPU tensors), torch's normalize."""
     agg = spmm(adj, X)
-    if agg.is_cuda:
-        P1, P2 = dense(X * agg, W1, b1, False), dense(agg, W2, b2, False)
-    else:
-        P1 = torch.matmul(X * agg, W1) + (b1 if b1 is not None else 0)
-        P2 = torch.matmul(agg, W2) + (b2 if b2 is not None else 0)
+    P1, P2 = _dense_or_torch(X * agg, W1, b1, False), _dense_or_torch(agg, W2, b2, False)
     u = _ngcf_act(P1, activation) + _ngcf_act(P2, activation)
     if dropout is not None and float(dropout[0]) != 0:
         u = feature_dropout(adj.graph, u, *dropout) if u.is_cuda else torch.nn.functional.dropout(u, p=float(dropout[0]), training=True)
@@ -2091,14 +2102,10 @@ def ngcf_step(adj: Adjacency, X: torch.Tensor, W1: torch.Tensor, b1, W2: torch.T
     and dW2 keep their bits; dX and the bias gradients agree with the composed backward to float32 rounding.  A second backward over a
     retained graph gives the same bits.  It acts under autograd only; other widths and misaligned rows keep the composed backward.
     CPU tensors, an adjacency with a diagonal and a DroppedAdjacency run today's ops."""
-    if activation not in NGCF_ACTIVATIONS:
-        raise Exception("ngcf_step: activation must be one of " + ", ".join(repr(a) for a in NGCF_ACTIVATIONS))
-    if backward not in NGCF_BACKWARDS:
-        raise Exception("ngcf_step: backward must be one of " + ", ".join(repr(b) for b in NGCF_BACKWARDS))
-    if wide not in NGCF_WIDES:
-        raise Exception("ngcf_step: wide must be one of " + ", ".join(repr(w) for w in NGCF_WIDES))
-    if wide_backward not in NGCF_WIDE_BACKWARDS:
-        raise Exception("ngcf_step: wide_backward must be one of " + ", ".join(repr(w) for w in NGCF_WIDE_BACKWARDS))
+    _one_of("ngcf_step", "activation", activation, NGCF_ACTIVATIONS)
+    _one_of("ngcf_step", "backward", backward, NGCF_BACKWARDS)
+    _one_of("ngcf_step", "wide", wide, NGCF_WIDES)
+    _one_of("ngcf_step", "wide_backward", wide_backward, NGCF_WIDE_BACKWARDS)
     tensors = tuple(t for t in (X, W1, b1, W2, b2) if t is not None)
     if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors) or adj.diag is not None or isinstance(adj, DroppedAdjacency):
         return _ngcf_composed(adj, X, W1, b1, W2, b2, activation, dropout, bool(normalize))
@@ -2188,15 +2195,7 @@ class _GCNIISpectralStep(torch.autograd.Function):
 
 def _spectral_composed(adj, H, H0, a, M, bias, relu, dropout):
     """The layer as today's ops: ppr_step, the dense kernel with bias and relu, then torch's elementwise tail (torch's dropout)."""
-    T = ppr_step(adj, H, H0, a)
-    if T.is_cuda:
-        activated = dense(T, M, bias, relu)
-    else:
-        activated = torch.matmul(T, M) + bias
-        activated = torch.relu(activated) if relu else activated
-    y = activated - bias
-    p = 0.0 if dropout is None else float(dropout[0])
-    return 2 * (torch.nn.functional.dropout(y, p=p, training=True) if p != 0 else y)
+    return _spectral_tail(_dense_or_torch(ppr_step(adj, H, H0, a), M, bias, relu), bias, dropout)
 
 
 def gcnii_step_spectral(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, M: torch.Tensor, bias: torch.Tensor, relu=True,
@@ -2215,8 +2214,7 @@ def gcnii_step_spectral(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: fl
     The composed path -- ppr_step, the dense kernel, torch's elementwise tail with TORCH's dropout at rate p -- is kept for a
     DroppedAdjacency, an adjacency with a diagonal, CPU tensors and a rate outside [0, 1).  (``weight_gradient="recomputed"`` is not
     offered: the layer would save its input in place of T, the same 4 bytes per element.)"""
-    if backward not in GCNII_BACKWARDS:
-        raise Exception("gcnii_step_spectral: backward must be one of " + ", ".join(repr(b) for b in GCNII_BACKWARDS))
+    _one_of("gcnii_step_spectral", "backward", backward, GCNII_BACKWARDS)
     rate = 0.0 if dropout is None else float(dropout[0])
     if (isinstance(adj, DroppedAdjacency) or adj.diag is not None or not (H.is_cuda and H0.is_cuda and M.is_cuda and bias.is_cuda)
             or not 0.0 <= rate < 1.0):
@@ -2241,55 +2239,17 @@ class _GCNSpectralStep(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, W, bias, adj, relu, dropout, fused_edge, backward):
-        ctx.adj, ctx.relu, ctx.dropout, ctx.fused_edge, ctx.fused_backward = adj, relu, dropout, fused_edge, backward == "fused"
-        ctx.bias_shape = None if bias is None else tuple(bias.shape)
-        out, agg, gate = _gcn_launch(adj, X, W, bias, relu, keep_agg=True, dropout=dropout, fused_edge=fused_edge, spectral=True)
-        if ctx.fused_backward:      # (agg is neither an input nor an output of the node: it may live on ctx, which can let it go early)
-            ctx.agg = agg
-            ctx.save_for_backward(W, gate)
-            return out
-        ctx.save_for_backward(agg, W, gate)
-        return out
+        return _gcn_node_forward(ctx, X, W, bias, adj, relu, dropout, fused_edge, backward, spectral=True)
 
     @staticmethod
     def backward(ctx, g):
-        want_X, want_W = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        want_b = ctx.bias_shape is not None and ctx.needs_input_grad[2]
-        if ctx.fused_backward:
-            W, gate = ctx.saved_tensors
-            agg, ctx.agg = ctx.agg, None
-            if agg is None:
-                raise Exception("gcn_step_spectral(backward=\"fused\"): the node let its aggregated rows go in its first backward; run the "
-                                "forward again (or use backward=\"composed\" where a graph is retained)")
-        else:
-            agg, W, gate = ctx.saved_tensors
-        G, gb = _gcnii_spectral_gate(ctx.adj.graph, g, gate, ctx.relu, ctx.dropout, padded=ctx.fused_backward and want_X)
-        gb = gb.reshape(ctx.bias_shape) if want_b else None
-        gW = _dense_wgrad(agg, G) if want_W else None
-        del agg                                                 # (under backward="fused" the last reference: the rows are free before dX is made)
-        gX = None
-        if want_X and ctx.fused_backward:
-            gX = _gcn_back_launch(ctx.adj, G, W.t().contiguous(), ctx.fused_edge)
-        elif want_X:
-            gT = _dense_launch(G, W.t().contiguous(), None, False)
-            del G                                               # (the gated gradient is done with: the transposed SpMM runs without it)
-            gX = _launch(ctx.adj, gT, None, 1.0, 0.0, nat.ACT_NONE, transposed=True)
-        return gX, gW, gb, None, None, None, None, None
+        return _gcn_node_backward(ctx, g) + (None, None, None, None, None)
 
 
 def _gcn_spectral_composed(adj, X, W, bias, relu, dropout):
     """The layer as today's ops (_gcn_composed's shape): spmm, the dense kernel with bias and relu (CPU tensors: torch), then torch's
     elementwise tail with TORCH's dropout."""
-    agg = spmm(adj, X)
-    b = bias if bias is not None else 0
-    if agg.is_cuda:
-        activated = dense(agg, W, bias, relu)
-    else:
-        activated = torch.matmul(agg, W) + b
-        activated = torch.relu(activated) if relu else activated
-    y = activated - b
-    p = 0.0 if dropout is None else float(dropout[0])
-    return 2 * (torch.nn.functional.dropout(y, p=p, training=True) if p != 0 else y)
+    return _spectral_tail(_dense_or_torch(spmm(adj, X), W, bias, relu), bias if bias is not None else 0, dropout)
 
 
 def gcn_step_spectral(adj: Adjacency, X: torch.Tensor, W: torch.Tensor, bias=None, relu=True, dropout=None, edge_dropout="composed",
@@ -2313,8 +2273,7 @@ def gcn_step_spectral(adj: Adjacency, X: torch.Tensor, W: torch.Tensor, bias=Non
     CPU tensors, an adjacency with a diagonal, a DroppedAdjacency without ``edge_dropout="fused"`` and a rate outside [0, 1) run
     ``spmm`` + ``dense`` and torch's elementwise tail with TORCH's dropout: today's calls and bits."""
     fused_edge = _edge_dropout("gcn_step_spectral", edge_dropout)
-    if backward not in GCN_BACKWARDS:
-        raise Exception("gcn_step_spectral: backward must be one of " + ", ".join(repr(b) for b in GCN_BACKWARDS))
+    _one_of("gcn_step_spectral", "backward", backward, GCN_BACKWARDS)
     tensors = (X, W) if bias is None else (X, W, bias)
     rate = 0.0 if dropout is None else float(dropout[0])
     if (not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors) or adj.diag is not None
