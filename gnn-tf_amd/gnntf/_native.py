@@ -7,10 +7,12 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_uint64, c_void_p
+import re
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 900         # include/gnx.h GNX_ABI_VERSION: the header this binding was written against
+ABI_VERSION = 900         # the ABI this package's call sites are written against; include/gnx.h GNX_ABI_VERSION must equal it
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "gnx.h")
 # GNX_LIBRARY: another build of the same library (the tuning build of tools/, `make TUNING=1` -> lib/tune/libgnx.so)
 LIB_PATH = os.environ.get("GNX_LIBRARY") or os.path.join(os.path.dirname(_HERE), "lib", "libgnx.so")
 
@@ -22,181 +24,46 @@ HALO_ALL, HALO_PULL, HALO_PUSH = 0, 1, 2
 RESERVE_TRANSPOSED, RESERVE_K_LOOP, RESERVE_TRAIN_GATHER, RESERVE_GATHER_HINTS = 1, 2, 4, 8
 ORD_X, ORD_OUT = 1, 2     # `order` of the _ord training entries: X stored in the handle's gather order / the result written in it
 
-# name -> (restype, argtypes); must list every symbol include/gnx.h declares
-SIGNATURES = {
-    "gnx_last_error": (c_char_p, []),
-    "gnx_version": (c_int, []),
-    "gnx_graph_create_coo": (c_int, [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
-    "gnx_graph_create_csr": (c_int, [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
-    "gnx_graph_destroy": (c_int, [c_void_p]),
-    "gnx_graph_info": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
-    "gnx_graph_hub_rows": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64)]),
-    "gnx_graph_csr": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p)]),
-    "gnx_graph_export": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "gnx_graph_normalize": (c_int, [c_void_p, c_int, c_int, c_float, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
-    "gnx_graph_normalize_t": (c_int, [c_void_p, c_int, c_int, c_float, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
-    "gnx_graph_reserve": (c_int, [c_void_p, c_int64, c_int, c_void_p]),
-    "gnx_graph_enable_entry_dropout": (c_int, [c_void_p, c_void_p]),
-    "gnx_graph_set_row_window": (c_int, [c_void_p, c_int64, c_void_p]),
-    "gnx_graph_set_gather_hints": (c_int, [c_void_p, c_int64, c_void_p]),
-    "gnx_graph_gather_hints": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64)]),
-    "gnx_graph_set_pendant_elision": (c_int, [c_void_p, c_int, c_void_p]),
-    "gnx_graph_pendant_elision": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_void_p), POINTER(c_int)]),
-    "gnx_graph_set_dropout_counter": (c_int, [c_void_p, c_void_p]),
-    "gnx_graph_set_block": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
-    "gnx_graph_colsum": (c_int, [c_void_p, c_float, c_uint64, c_uint64, c_void_p, c_void_p]),
-    "gnx_graph_colsum_streams": (c_int, [c_void_p, c_float, c_uint64, c_uint64, c_int, c_void_p, c_void_p]),
-    "gnx_degree_scale": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p]),
-    "gnx_graph_scale_values": (c_int, [c_void_p, c_float, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "gnx_spmm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_float, c_float,
-                         c_int, c_void_p, c_int64, c_void_p]),
-    "gnx_spmm_t": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_float, c_float,
-                           c_int, c_void_p, c_int64, c_void_p]),
-    "gnx_spmm_scatter": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_float, c_float,
-                                 c_int, c_void_p, c_void_p, c_int64, c_void_p]),
-    "gnx_spmm_dropped": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64,
-                                 c_float, c_float, c_int, c_void_p, c_int64, c_void_p]),
-    "gnx_spmm_dropped_chained": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_int, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
-                                         c_int64, c_float, c_float, c_int, c_void_p, c_int64, c_void_p]),
-    "gnx_spmm_dropped_back": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_int, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
-                                      c_int64, c_float, c_float, c_void_p, c_int64, c_float, c_void_p, c_int64, c_int, c_void_p]),
-    "gnx_graph_gather_order": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p)]),
-    "gnx_spmm_dropped_chained_ord": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_int, c_void_p, c_void_p, c_int64, c_int64,
-                                             c_void_p, c_int64, c_float, c_float, c_int, c_void_p, c_int64, c_int, c_void_p]),
-    "gnx_spmm_dropped_back_ord": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_int, c_void_p, c_void_p, c_int64, c_int64,
-                                          c_void_p, c_int64, c_float, c_float, c_void_p, c_int64, c_float, c_void_p, c_int64, c_int, c_int,
-                                          c_void_p]),
-    "gnx_spmm_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_float, c_float, c_int,
-                              c_void_p, c_void_p, c_int64, c_void_p]),
-    "gnx_spmm_tv": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_float, c_float,
-                            c_int, c_void_p, c_int64, c_void_p]),
-    "gnx_graph_permute_values_t": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
-    "gnx_ppr_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_int, c_void_p, c_void_p]),
-    "gnx_appnp_propagate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int64, c_void_p, c_void_p,
-                                    c_void_p]),
-    "gnx_appnp_propagate_act": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int64, c_int, c_void_p, c_void_p,
-                                        c_void_p]),
-    "gnx_cast_bf16": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
-    "gnx_spmm_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_float, c_float,
-                              c_int, c_void_p, c_int, c_int64, c_void_p]),
-    "gnx_spmm_rows_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_float, c_float, c_int,
-                                   c_void_p, c_void_p, c_int, c_int64, c_void_p]),
-    "gnx_halo_pack_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
-    "gnx_halo_exchange_bf16": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "gnx_appnp_propagate_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int64, c_int, c_void_p, c_void_p,
-                                         c_void_p]),
-    "gnx_spmm_dropped_chained_bf16": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_int, c_void_p, c_void_p, c_int64, c_int64,
-                                              c_void_p, c_int64, c_float, c_float, c_int, c_void_p, c_int, c_int64, c_void_p]),
-    "gnx_spmm_dropped_back_bf16": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_int, c_void_p, c_void_p, c_int64, c_int64,
-                                           c_void_p, c_int64, c_float, c_float, c_void_p, c_int64, c_float, c_void_p, c_int64, c_int,
-                                           c_void_p]),
-    "gnx_halo_plan_create": (c_int, [c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
-    "gnx_halo_plan_destroy": (c_int, [c_void_p]),
-    "gnx_halo_plan_layout": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), c_void_p, c_void_p,
-                                     c_void_p]),
-    "gnx_halo_pack": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
-    "gnx_halo_exchange": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "gnx_halo_bind_rccl": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
-    "gnx_gather_rows32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
-    "gnx_gather_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
-    "gnx_gcnii_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_int64, c_int, c_void_p,
-                               c_void_p, c_void_p]),
-    "gnx_gcnii_step_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_int64, c_int, c_void_p,
-                                    c_int, c_void_p, c_void_p]),
-    "gnx_gcnii_step_back": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_float,
-                                    c_void_p, c_void_p, c_void_p]),
-    "gnx_gcnii_step_drop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_int64, c_int, c_double, c_uint64,
-                                    c_uint64, c_void_p, c_void_p, c_void_p]),
-    "gnx_feature_dropout": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_double, c_uint64, c_uint64, c_void_p, c_int64,
-                                    c_void_p]),
-    "gnx_feature_dropout_back": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_double, c_uint64, c_uint64,
-                                         c_int, c_void_p, c_int64, c_void_p]),
-    "gnx_gcnii_step_train_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_int64, c_int, c_double,
-                                          c_uint64, c_uint64, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
-    "gnx_feature_dropout_back_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_double, c_uint64, c_uint64,
-                                              c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
-    "gnx_gcnii_step_back_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
-                                         c_float, c_void_p, c_void_p, c_void_p]),
-    "gnx_gcnii_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
-                                c_void_p]),
-    "gnx_gcnii_wgrad_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
-                                     c_void_p]),
-    "gnx_gcnii_step_drop_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_int64, c_int, c_double,
-                                         c_uint64, c_uint64, c_void_p, c_int, c_void_p, c_void_p]),
-    "gnx_gcnii_step_spectral": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_int64, c_void_p, c_int, c_double,
-                                        c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "gnx_gcnii_spectral_back": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_double, c_uint64, c_uint64, c_void_p,
-                                        c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
-    "gnx_gcnii_step_dropped": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_int64,
-                                       c_int, c_double, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
-    "gnx_gcnii_step_back_dropped": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_void_p, c_float, c_int64, c_void_p, c_int64,
-                                            c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
-    "gnx_gcn_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_double, c_uint64,
-                             c_uint64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "gnx_gcn_step_dropped": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
-                                     c_void_p, c_int, c_double, c_uint64, c_uint64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "gnx_gcn_step_back": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p,
-                                  c_int64, c_void_p]),
-    "gnx_gcn_step_back_dropped": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_void_p, c_int64, c_int64, c_void_p, c_int64,
-                                          c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
-    "gnx_step_spectral_gcn": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_double,
-                                      c_uint64, c_uint64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "gnx_step_spectral_gcn_dropped": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_void_p, c_int64, c_int64, c_void_p, c_int64,
-                                              c_int64, c_void_p, c_int, c_double, c_uint64, c_uint64, c_void_p, c_int64, c_void_p, c_void_p,
-                                              c_void_p, c_void_p]),
-    "gnx_ngcf_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
-                              c_int, c_double, c_uint64, c_uint64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
-                              c_void_p]),
-    "gnx_ngcf_back_gate": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_double,
-                                   c_uint64, c_uint64, c_void_p, c_void_p, c_int64, c_void_p]),
-    "gnx_step_back_ngcf": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_double,
-                                   c_uint64, c_uint64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
-                                   c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
-                                   c_void_p]),
-    "gnx_step_back_wide_ngcf": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_double,
-                                        c_uint64, c_uint64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
-                                        c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
-                                        c_void_p]),
-    "gnx_step_wide_ngcf": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p,
-                                   c_void_p, c_int, c_double, c_uint64, c_uint64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
-                                   c_int64, c_void_p]),
-    "gnx_dense": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int64,
-                          c_void_p]),
-    "gnx_dense_wgrad": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
-    "gnx_dense_drop": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_double, c_uint64,
-                               c_uint64, c_double, c_uint64, c_uint64, c_void_p, c_int64, c_void_p]),
-    "gnx_dense_wgrad_drop": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_double, c_uint64, c_uint64,
-                                     c_void_p, c_void_p, c_int64, c_void_p]),
-    "gnx_node_ce": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "gnx_node_ce_backward": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
-                                     c_void_p]),
-    "gnx_node_argmax": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
-    "gnx_edge_scores": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "gnx_edge_scores_backward": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
-                                         c_void_p]),
-    "gnx_sample_negatives": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_uint64, c_uint64, c_void_p, c_void_p,
-                                     c_void_p]),
-    "gnx_edge_plan_bytes": (c_int64, [c_int64]),
-    "gnx_edge_plan": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "gnx_edge_sorted_work_floats": (c_int64, [c_int64, c_int64]),
-    "gnx_edge_scores_backward_sorted": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
-                                                c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "gnx_rank_candidates_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int64, c_int64]),
-    "gnx_rank_candidates": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
-                                    c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                    c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "gnx_signal_project": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
-    "gnx_signal_spmv": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p]),
-    "gnx_signal_ppr": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p]),
-    "gnx_signal_smoothness": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "gnx_signal_smoothness_back": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "gnx_signal_uniform": (c_int, [c_void_p, c_int64, c_float, c_uint64, c_uint64, c_void_p, c_void_p]),
-    "gnx_linear_combination": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
-    "gnx_stream_read": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
-    "gnx_stream_copy": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
-    "gnx_probe_block_xcd": (c_int, [c_int64, c_void_p, c_void_p]),
-    "gnx_graph_last_kernel": (c_char_p, [c_void_p]),
-}
+# C scalar type -> ctypes type; every pointer and every handle typedef crosses as void * (byref(x), a ctypes array or None at the
+# call site), `const char *` comes back as c_char_p
+SCALARS = {"int": c_int, "int64_t": c_int64, "uint64_t": c_uint64, "float": c_float, "double": c_double}
+
+
+def parse_header():
+    """{name: (restype, argtypes)} of every prototype HEADER_PATH declares.  Refuses instead of guessing: a header of another ABI
+    number, a scalar type outside SCALARS, or a gnx_ name followed by `(` that did not read as a prototype raises."""
+    if not os.path.exists(HEADER_PATH):
+        raise Exception(f"gnntf: the header {HEADER_PATH} is missing -- the binding of libgnx.so is read from it; there is no other table")
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER_PATH).read(), flags=re.S)
+    version = re.search(r"#define\s+GNX_ABI_VERSION\s+(\d+)", text)
+    if version is None or int(version.group(1)) != ABI_VERSION:
+        raise Exception(f"gnntf: {HEADER_PATH} declares ABI {version.group(1) if version else 'nothing'}, this package's call sites are "
+                        f"written against ABI {ABI_VERSION}")
+    handles = set(re.findall(r"typedef\s+struct\s+\w+\s*\*\s*(\w+)\s*;", text))
+
+    def scalar(entry, what, c_type):
+        if c_type not in SCALARS:
+            raise Exception(f"gnntf: {HEADER_PATH}: {entry}: {what} has type `{c_type}`, which the binding has no rule for")
+        return SCALARS[c_type]
+
+    def parameter(entry, arg):
+        c_type = arg.rpartition(" ")[0].removeprefix("const ")          # "int64_t ldx" -> "int64_t"
+        return c_void_p if "*" in arg or c_type in handles else scalar(entry, f"parameter `{arg}`", c_type)
+
+    signatures = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][A-Za-z_0-9 \*]*?)\b(gnx_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", text):
+        ret, args = " ".join(ret.split()), [" ".join(arg.split()) for arg in args.split(",")]
+        signatures[name] = (c_char_p if ret == "const char *" else scalar(name, "the return value", ret),
+                            [] if args == ["void"] else [parameter(name, arg) for arg in args])
+    named = set(re.findall(r"\b(gnx_[a-z_0-9]+)\s*\(", text))
+    if len(signatures) != len(named):
+        raise Exception(f"gnntf: {HEADER_PATH} names {len(named)} entries and {len(signatures)} read as prototypes; not read: "
+                        f"{sorted(named - set(signatures))}")
+    return signatures
+
+
+# name -> (restype, argtypes) of every symbol include/gnx.h declares, read from the header at import: nothing is typed here by hand
+SIGNATURES = parse_header()
 
 # entries added within ABI 0.9 that a library of the same minor version may lack: found by probing (has_symbol); their callers raise
 PROBED = ("gnx_step_wide_ngcf", "gnx_step_back_wide_ngcf", "gnx_step_spectral_gcn", "gnx_step_spectral_gcn_dropped", "gnx_dense_drop",

@@ -5,13 +5,10 @@ import re
 
 import pytest
 
+import abi_header
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "gnx.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(gnx_[a-z_0-9]+)\s*\(", text)))
+declared_symbols = abi_header.declared
 
 
 def test_header_declares_the_path():
@@ -30,11 +27,40 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_native.SIGNATURES) == declared_symbols()
 
 
+SKIPPED = []                                                         # entries of PROBED that the loaded library lacks
+
+
+@pytest.mark.parametrize("name", abi_header.declared())
+def test_every_entry_is_bound_as_the_header_declares_it(name):
+    """The loaded library's argtypes / restype and _native.SIGNATURES[name] against the header, read by tests/abi_header.py (not by
+    the package's own parser): a c_int where the header says int64_t would shift every later argument of the call."""
+    from gnntf import _native
+    want = (abi_header.restype_of(name), abi_header.ctypes_of(abi_header.prototype(name)))
+    assert _native.SIGNATURES[name] == want
+    if name in _native.PROBED and not _native.has_symbol(name):
+        SKIPPED.append(name)
+        assert len(SKIPPED) <= len(_native.PROBED)
+        pytest.skip(f"{name}: a probed entry this library lacks")
+    fn = getattr(_native.lib(), name)
+    assert (fn.restype, fn.argtypes) == want
+
+
+@pytest.mark.parametrize("old, new, message", [
+    ("int gnx_stream_copy(", "int gnx_stream_copy(size_t n_extra, ", r"gnx_stream_copy: parameter `size_t n_extra`"),   # no rule for size_t
+    ("#define GNX_ABI_VERSION 900", "#define GNX_ABI_VERSION 901", r"declares ABI 901, .* ABI 900")])               # names both numbers
+def test_parser_refuses_instead_of_guessing(old, new, message, tmp_path, monkeypatch):
+    from gnntf import _native
+    copy = tmp_path / "gnx.h"
+    copy.write_text(abi_header.text().replace(old, new, 1))
+    monkeypatch.setattr(_native, "HEADER_PATH", str(copy))
+    with pytest.raises(Exception, match=message):
+        _native.parse_header()
+
+
 def test_version_and_error_string():
     from gnntf import _native
     lib = _native.lib()
-    header = open(os.path.join(ROOT, "include", "gnx.h")).read()
-    declared = int(re.search(r"#define GNX_ABI_VERSION (\d+)", header).group(1))
+    declared = int(re.search(r"#define GNX_ABI_VERSION (\d+)", abi_header.text()).group(1))
     assert lib.gnx_version() == declared == _native.ABI_VERSION          # header, library and binding describe ONE ABI
     assert isinstance(lib.gnx_last_error(), bytes)
 

@@ -4,17 +4,15 @@ mistakes, the header declares the two entries and the binding carries their argu
 sizes under their own names without touching a device, the keyword refuses what it does not know, a model without the keyword -- or with
 it on CPU tensors -- makes torch's calls, and the layers' predicate says no to every excluded case."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+from abi_header import ctypes_of, prototype as header_prototype
 import dense_drop_ref as dref
 from test_gcn_fused_cpu import CpuGraph, OnDevice, cpu_world, tiny_graph
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 IN, OUT = (0.5, 7, 2), (0.6, 7, 3)
 PROTOTYPES = {
@@ -25,7 +23,6 @@ PROTOTYPES = {
                              "int64_t O", "double in_p", "uint64_t in_seed", "uint64_t in_stream", "float *d_dW", "float *d_work",
                              "int64_t work_floats", "void *stream"],
 }
-CTYPES = {"float": ctypes.c_float, "double": ctypes.c_double, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "int": ctypes.c_int}
 
 
 # ---- the bounds ------------------------------------------------------------------------------------------------------------------------
@@ -85,19 +82,12 @@ def test_the_backward_bounds_admit_float32_sums():
 
 
 # ---- the ABI ---------------------------------------------------------------------------------------------------------------------------
-def header_prototype(name):
-    text = open(os.path.join(ROOT, "include", "gnx.h")).read()
-    found = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-    assert found, f"include/gnx.h does not declare {name}"
-    return [" ".join(arg.split()) for arg in found.group(1).split(",")]
-
-
 @pytest.mark.parametrize("name", sorted(PROTOTYPES))
 def test_header_library_and_binding_agree(name):
     from gnntf import _native
     assert header_prototype(name) == PROTOTYPES[name]
     assert hasattr(ctypes.CDLL(_native.LIB_PATH), name) and _native.has_symbol(name) and name in _native.PROBED
-    want = [ctypes.c_void_p if "*" in arg or arg.startswith("gnx_graph_t") else CTYPES[arg.rsplit(" ", 1)[0]] for arg in PROTOTYPES[name]]
+    want = ctypes_of(PROTOTYPES[name])
     restype, argtypes = _native.SIGNATURES[name]
     assert restype is ctypes.c_int and argtypes == want
     assert not name.startswith(("gnx_gcnii_", "gnx_gcn_", "gnx_ngcf_", "gnx_feature_dropout"))

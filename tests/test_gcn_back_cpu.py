@@ -5,17 +5,16 @@ entries refuse bad arguments before they look at a device, the keywords refuse w
 association, (A^T G') W^T, and rejects a G' that lost its last column."""
 import ctypes
 import functools
-import os
 
 import numpy as np
 import pytest
 import scipy.sparse as sp
 import torch
 
+from abi_header import ctypes_of, prototype as header_prototype
 import gcn_fused_ref as gref
-from test_gcn_fused_cpu import CTYPES, CpuGraph, OnDevice, cpu_world, header_prototype, one_step, structure, tiny_graph
+from test_gcn_fused_cpu import CpuGraph, OnDevice, cpu_world, one_step, structure, tiny_graph
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 TAIL = ["const float *d_G", "int64_t ldg", "int64_t C_out", "const float *d_Wt", "int64_t ldwt", "int64_t C_in", "float *d_dX", "int64_t lddx",
         "float *d_work", "int64_t work_floats", "void *stream"]
@@ -30,7 +29,7 @@ def test_header_library_and_binding_agree(name):
     from gnntf import _native
     assert header_prototype(name) == PROTOTYPES[name]
     assert hasattr(ctypes.CDLL(_native.LIB_PATH), name)
-    want = [ctypes.c_void_p if "*" in arg or arg.startswith("gnx_graph_t") else CTYPES[arg.rsplit(" ", 1)[0]] for arg in PROTOTYPES[name]]
+    want = ctypes_of(PROTOTYPES[name])
     restype, argtypes = _native.SIGNATURES[name]
     assert restype is ctypes.c_int and argtypes == want
     assert _native.lib().gnx_version() == 900 == _native.ABI_VERSION

@@ -4,17 +4,15 @@ the keyword refuses what it does not know, the layer keeps today's ops on CPU te
 says no to every excluded case, and the bound of tests/gcn_fused_ref.py admits the float32 emulations and rejects a lost bias."""
 import ctypes
 import functools
-import os
-import re
 
 import numpy as np
 import pytest
 import scipy.sparse as sp
 import torch
 
+from abi_header import ctypes_of, prototype as header_prototype, text as header_text
 import gcn_fused_ref as gref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BOUND_CASES = [(64, 64), (64, 40), (64, 7), (16, 16)]
 
 TAIL = ["const float *d_X", "int64_t ldx", "int64_t C_in", "const float *d_W", "int64_t ldw", "int64_t C_out", "const float *d_bias", "int act",
@@ -23,23 +21,15 @@ PROTOTYPES = {
     "gnx_gcn_step": ["gnx_graph_t g", "const float *d_vals"] + TAIL,
     "gnx_gcn_step_dropped": ["gnx_graph_t g", "const float *d_D", "float edge_p", "uint64_t edge_seed", "uint64_t edge_stream"] + TAIL,
 }
-CTYPES = {"float": ctypes.c_float, "double": ctypes.c_double, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "int": ctypes.c_int}
-
-
-def header_prototype(name):
-    text = open(os.path.join(ROOT, "include", "gnx.h")).read()
-    found = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-    assert found, f"include/gnx.h does not declare {name}"
-    return [" ".join(arg.split()) for arg in found.group(1).split(",")]
 
 
 @pytest.mark.parametrize("name", sorted(PROTOTYPES))
 def test_header_library_and_binding_agree(name):
     from gnntf import _native
     assert header_prototype(name) == PROTOTYPES[name]
-    assert "gcn.py:88-89" in open(os.path.join(ROOT, "include", "gnx.h")).read()
+    assert "gcn.py:88-89" in header_text()
     assert hasattr(ctypes.CDLL(_native.LIB_PATH), name)
-    want = [ctypes.c_void_p if "*" in arg or arg.startswith("gnx_graph_t") else CTYPES[arg.rsplit(" ", 1)[0]] for arg in PROTOTYPES[name]]
+    want = ctypes_of(PROTOTYPES[name])
     restype, argtypes = _native.SIGNATURES[name]
     assert restype is ctypes.c_int and argtypes == want
     assert _native.lib().gnx_version() == 900 == _native.ABI_VERSION

@@ -2,28 +2,15 @@
 library exports it, gnntf/_native.py binds it with the declared argument types, the ABI number did not move, and the options
 gcnii_step(backward=) / GNN(gcnii_backward=) refuse values they do not know."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_header import ctypes_of, prototype as header_prototype, text as header_text
+
 NAME = "gnx_gcnii_step_back"
-
-# C type of a prototype argument -> the ctypes type the binding must use (pointers of every kind cross as void *)
-CTYPES = {"float": ctypes.c_float, "int64_t": ctypes.c_int64, "int": ctypes.c_int}
-
-
-def header_text():
-    return open(os.path.join(ROOT, "include", "gnx.h")).read()
-
-
-def header_prototype(name):
-    found = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", header_text())
-    assert found, f"include/gnx.h does not declare {name}"
-    return [" ".join(arg.split()) for arg in found.group(1).split(",")]
 
 
 def test_header_declares_the_entry():
@@ -43,8 +30,7 @@ def test_library_exports_the_entry():
 def test_native_binds_the_declared_argument_types():
     from gnntf import _native
     restype, argtypes = _native.SIGNATURES[NAME]
-    want = [ctypes.c_void_p if "*" in arg or arg.startswith("gnx_graph_t") else CTYPES[arg.rsplit(" ", 1)[0]]
-            for arg in header_prototype(NAME)]
+    want = ctypes_of(header_prototype(NAME))
     assert len(want) == 13
     assert restype is ctypes.c_int and argtypes == want
     fn = getattr(_native.lib(), NAME)

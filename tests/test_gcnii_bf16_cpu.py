@@ -2,30 +2,19 @@
 the library exports it, gnntf/_native.py binds it with the declared argument types, the ABI number did not move, and
 sparse.gcnii_step(storage=torch.bfloat16) refuses autograd."""
 import ctypes
-import os
 import re
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-# C type of a prototype argument -> the ctypes type the binding must use (pointers of every kind cross as void *)
-CTYPES = {"float": ctypes.c_float, "int64_t": ctypes.c_int64, "int": ctypes.c_int}
-
-
-def header_prototype(name):
-    text = open(os.path.join(ROOT, "include", "gnx.h")).read()
-    found = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-    assert found, f"include/gnx.h does not declare {name}"
-    return [" ".join(arg.split()) for arg in found.group(1).split(",")]
+from abi_header import ctypes_of, prototype as header_prototype, text as header_text
 
 
 def test_header_declares_the_entry():
     args = header_prototype("gnx_gcnii_step_bf16")
     assert args == ["gnx_graph_t g", "const float *d_vals", "const uint16_t *d_H", "const float *d_H0", "float a", "int64_t C",
                     "const float *d_M", "int64_t ldm", "int act", "void *d_out", "int out_bf16", "float *d_work", "void *stream"]
-    text = open(os.path.join(ROOT, "include", "gnx.h")).read()
+    text = header_text()
     assert "spmm_gcnii_mfma_bf16" in text and "spmm+dense_mfma_bf16" in text       # the reported names are documented
     assert re.search(r"#define\s+GNX_ABI_VERSION\s+900\b", text)
 
@@ -39,12 +28,7 @@ def test_library_exports_the_entry():
 def test_native_binds_the_declared_argument_types():
     from gnntf import _native
     restype, argtypes = _native.SIGNATURES["gnx_gcnii_step_bf16"]
-    want = []
-    for arg in header_prototype("gnx_gcnii_step_bf16"):
-        if "*" in arg or arg.startswith("gnx_graph_t"):
-            want.append(ctypes.c_void_p)
-        else:
-            want.append(CTYPES[arg.rsplit(" ", 1)[0]])
+    want = ctypes_of(header_prototype("gnx_gcnii_step_bf16"))
     assert restype is ctypes.c_int and argtypes == want
     fn = _native.lib().gnx_gcnii_step_bf16
     assert fn.argtypes == want and fn.restype is ctypes.c_int
@@ -52,7 +36,7 @@ def test_native_binds_the_declared_argument_types():
 
 def test_version_still_equals_the_header():
     from gnntf import _native
-    text = open(os.path.join(ROOT, "include", "gnx.h")).read()
+    text = header_text()
     number = int(re.search(r"#define\s+GNX_ABI_VERSION\s+(\d+)", text).group(1))
     assert _native.lib().gnx_version() == number == _native.ABI_VERSION
 

@@ -4,7 +4,6 @@ the header declares the three entries, the library exports them and gnntf/_nativ
 float64 emulation the GPU tests compare against is -- with its roundings switched off -- torch's float64 autograd of the dense layer
 stack, and the model's run-eligibility predicate takes every fallback GNN.__init__ lists."""
 import ctypes
-import os
 import re
 
 import numpy as np
@@ -12,9 +11,9 @@ import pytest
 import scipy.sparse as sp
 import torch
 
+from abi_header import ctypes_of, prototype as header_prototype, text as header_text
 import gcnii_bf16_train_ref as ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 PROTOTYPES = {
     "gnx_gcnii_step_train_bf16": [
@@ -29,19 +28,6 @@ PROTOTYPES = {
         "gnx_graph_t g", "const float *d_vals_t", "const uint16_t *d_Gb", "const float *d_G", "float a", "int64_t C", "const float *d_Mt",
         "int64_t ldmt", "float *d_dH", "const float *d_S_in", "float s_alpha", "float *d_S_out", "float *d_work", "void *stream"],
 }
-
-# C type of a prototype argument -> the ctypes type the binding must use (pointers of every kind cross as void *)
-CTYPES = {"float": ctypes.c_float, "double": ctypes.c_double, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "int": ctypes.c_int}
-
-
-def header_text():
-    return open(os.path.join(ROOT, "include", "gnx.h")).read()
-
-
-def header_prototype(name):
-    found = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", header_text())
-    assert found, f"include/gnx.h does not declare {name}"
-    return [" ".join(arg.split()) for arg in found.group(1).split(",")]
 
 
 # ---- the keyword ---------------------------------------------------------------------------------------------------------------------
@@ -74,8 +60,7 @@ def test_library_exports_and_native_binds_the_entry(name):
     from gnntf import _native
     assert hasattr(ctypes.CDLL(_native.LIB_PATH), name)
     restype, argtypes = _native.SIGNATURES[name]
-    want = [ctypes.c_void_p if "*" in arg or arg.startswith("gnx_graph_t") else CTYPES[arg.rsplit(" ", 1)[0]]
-            for arg in header_prototype(name)]
+    want = ctypes_of(header_prototype(name))
     assert restype is ctypes.c_int and argtypes == want
     fn = getattr(_native.lib(), name)
     assert fn.argtypes == want and fn.restype is ctypes.c_int

@@ -3,16 +3,15 @@ it goes without a GPU: the header declares the three entries, the library export
 argument types, the ABI number did not move, the options refuse what they do not know, a "fused" model on CPU tensors trains through
 torch's dropout, and the numpy mask the GPU tests compare against keeps the share of elements it should."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
 
+from abi_header import ctypes_of, prototype as header_prototype, text as header_text
 from oracle import gnntf_oracle as orc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 PROTOTYPES = {
     "gnx_gcnii_step_drop": [
@@ -26,19 +25,6 @@ PROTOTYPES = {
         "gnx_graph_t g", "const float *d_g", "int64_t ldg", "const float *d_y", "int64_t ldy", "int64_t n_rows", "int64_t C",
         "double dropout_p", "uint64_t seed", "uint64_t stream_id", "int act", "float *d_G", "int64_t ldG", "void *stream"],
 }
-
-# C type of a prototype argument -> the ctypes type the binding must use (pointers of every kind cross as void *)
-CTYPES = {"float": ctypes.c_float, "double": ctypes.c_double, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "int": ctypes.c_int}
-
-
-def header_text():
-    return open(os.path.join(ROOT, "include", "gnx.h")).read()
-
-
-def header_prototype(name):
-    found = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", header_text())
-    assert found, f"include/gnx.h does not declare {name}"
-    return [" ".join(arg.split()) for arg in found.group(1).split(",")]
 
 
 @pytest.mark.parametrize("name", sorted(PROTOTYPES))
@@ -54,8 +40,7 @@ def test_library_exports_and_native_binds_the_entry(name):
     from gnntf import _native
     assert hasattr(ctypes.CDLL(_native.LIB_PATH), name)
     restype, argtypes = _native.SIGNATURES[name]
-    want = [ctypes.c_void_p if "*" in arg or arg.startswith("gnx_graph_t") else CTYPES[arg.rsplit(" ", 1)[0]]
-            for arg in header_prototype(name)]
+    want = ctypes_of(header_prototype(name))
     assert restype is ctypes.c_int and argtypes == want
     fn = getattr(_native.lib(), name)
     assert fn.argtypes == want and fn.restype is ctypes.c_int

@@ -4,14 +4,13 @@ types, the keyword refuses what it does not know, a "fused" model on CPU tensors
 layer hands the keyword on -- and draws its mask streams in today's order and number -- exactly where GNN.__init__ says it applies (the
 launch is replaced by a recorder, so no device is needed)."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_header import ctypes_of, prototype as header_prototype, text as header_text
+
 A_MIX = 0.1
 
 PROTOTYPES = {
@@ -24,17 +23,6 @@ PROTOTYPES = {
         "int64_t C", "const float *d_Mt", "int64_t ldmt", "float *d_dH", "const float *d_S_in", "float s_alpha", "float *d_S_out",
         "float *d_work", "void *stream"],
 }
-CTYPES = {"float": ctypes.c_float, "double": ctypes.c_double, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "int": ctypes.c_int}
-
-
-def header_text():
-    return open(os.path.join(ROOT, "include", "gnx.h")).read()
-
-
-def header_prototype(name):
-    found = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", header_text())
-    assert found, f"include/gnx.h does not declare {name}"
-    return [" ".join(arg.split()) for arg in found.group(1).split(",")]
 
 
 @pytest.mark.parametrize("name", sorted(PROTOTYPES))
@@ -42,7 +30,7 @@ def test_header_library_and_binding_agree(name):
     from gnntf import _native
     assert header_prototype(name) == PROTOTYPES[name]
     assert hasattr(ctypes.CDLL(_native.LIB_PATH), name)
-    want = [ctypes.c_void_p if "*" in arg or arg.startswith("gnx_graph_t") else CTYPES[arg.rsplit(" ", 1)[0]] for arg in PROTOTYPES[name]]
+    want = ctypes_of(PROTOTYPES[name])
     restype, argtypes = _native.SIGNATURES[name]
     assert restype is ctypes.c_int and argtypes == want
     assert _native.lib().gnx_version() == 900 == _native.ABI_VERSION          # added within ABI 0.9: the number did not move

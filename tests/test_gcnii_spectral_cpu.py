@@ -5,18 +5,16 @@ and at a rate of 1 whatever the switch says, a plain GCNIILayer stack does not n
 tests/gcnii_spectral_ref.py admits the float32 emulations and leaves a small enough share of the gate undecided."""
 import ctypes
 import functools
-import os
-import re
 
 import numpy as np
 import pytest
 import scipy.sparse as sp
 import torch
 
+from abi_header import ctypes_of, prototype as header_prototype
 import gcnii_shapes_ref as ref
 import gcnii_spectral_ref as sref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 A_MIX = 0.1
 SEED, STREAM = 7, 2
 CASES = [("T", 16), ("T", 32), ("T", 64), ("S", 64), ("T", 24)]          # the shapes of tests/test_gpu_gcnii_spectral.py
@@ -31,14 +29,6 @@ PROTOTYPES = {
         "double dropout_p", "uint64_t seed", "uint64_t stream_id", "float *d_G", "int64_t ldG", "float *d_dbias", "float *d_work",
         "int64_t work_floats", "void *stream"],
 }
-CTYPES = {"float": ctypes.c_float, "double": ctypes.c_double, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "int": ctypes.c_int}
-
-
-def header_prototype(name):
-    text = open(os.path.join(ROOT, "include", "gnx.h")).read()
-    found = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-    assert found, f"include/gnx.h does not declare {name}"
-    return [" ".join(arg.split()) for arg in found.group(1).split(",")]
 
 
 @pytest.mark.parametrize("name", sorted(PROTOTYPES))
@@ -46,7 +36,7 @@ def test_header_library_and_binding_agree(name):
     from gnntf import _native
     assert header_prototype(name) == PROTOTYPES[name]
     assert hasattr(ctypes.CDLL(_native.LIB_PATH), name)
-    want = [ctypes.c_void_p if "*" in arg or arg.startswith("gnx_graph_t") else CTYPES[arg.rsplit(" ", 1)[0]] for arg in PROTOTYPES[name]]
+    want = ctypes_of(PROTOTYPES[name])
     restype, argtypes = _native.SIGNATURES[name]
     assert restype is ctypes.c_int and argtypes == want
     assert _native.lib().gnx_version() == 900 == _native.ABI_VERSION

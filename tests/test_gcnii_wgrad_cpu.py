@@ -3,14 +3,14 @@ goes without a GPU: the header declares the three entries with their argument li
 them with the declared types, the options refuse what they do not know, and a "recomputed" model on CPU tensors keeps the CPU composition
 and the bits of the "stored" one."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_header import ctypes_of, prototype as header_prototype, text as header_text
+
 
 WGRAD = ["gnx_graph_t g", "const float *d_vals", "const float *d_H", "const float *d_H0", "float a", "int64_t C", "const float *d_G",
          "float *d_dM", "float *d_hub_rows", "float *d_work", "int64_t work_floats", "void *stream"]
@@ -22,17 +22,6 @@ PROTOTYPES = {
         "int64_t ldm", "int act", "double dropout_p", "uint64_t seed", "uint64_t stream_id", "void *d_out", "int out_bf16", "float *d_work",
         "void *stream"],
 }
-CTYPES = {"float": ctypes.c_float, "double": ctypes.c_double, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "int": ctypes.c_int}
-
-
-def header_text():
-    return open(os.path.join(ROOT, "include", "gnx.h")).read()
-
-
-def header_prototype(name):
-    found = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", header_text())
-    assert found, f"include/gnx.h does not declare {name}"
-    return [" ".join(arg.split()) for arg in found.group(1).split(",")]
 
 
 @pytest.mark.parametrize("name", sorted(PROTOTYPES))
@@ -49,8 +38,7 @@ def test_library_exports_and_native_binds_the_entry(name):
     from gnntf import _native
     assert hasattr(ctypes.CDLL(_native.LIB_PATH), name)
     restype, argtypes = _native.SIGNATURES[name]
-    want = [ctypes.c_void_p if "*" in arg or arg.startswith("gnx_graph_t") else CTYPES[arg.rsplit(" ", 1)[0]]
-            for arg in header_prototype(name)]
+    want = ctypes_of(header_prototype(name))
     assert restype is ctypes.c_int and argtypes == want
     fn = getattr(_native.lib(), name)
     assert fn.argtypes == want and fn.restype is ctypes.c_int

@@ -2,15 +2,13 @@
 before anything touches a device, the package exports the new names, and the numpy reference the GPU tests compare against
 (tests/link_device_ref.py) agrees with a brute-force lookup and with float64."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_header
 import link_device_ref as ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("gnx_sample_negatives", "gnx_edge_plan_bytes", "gnx_edge_plan", "gnx_edge_sorted_work_floats", "gnx_edge_scores_backward_sorted")
 FAKE = ctypes.c_void_p(4096)         # stands for a device pointer: every call below fails a check before anything would read it
 
@@ -22,12 +20,11 @@ def lib():
 
 def test_header_declares_and_library_exports_the_entries():
     from gnntf import _native
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gnx.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(gnx_[a-z_0-9]+)\s*\(", text))
+    declared = abi_header.declared()
     handle = ctypes.CDLL(_native.LIB_PATH)
     for name in ENTRIES:
         assert name in declared and hasattr(handle, name) and name in _native.SIGNATURES
-    header = open(os.path.join(ROOT, "include", "gnx.h")).read()
+    header = abi_header.text()
     assert "graph_predictor.py:52-98" in header and "graph_predictor.py:122-146" in header
     assert handle.gnx_version() == _native.ABI_VERSION == 900            # added within 0.9: callers probe for the symbols
 

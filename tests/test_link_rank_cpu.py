@@ -3,16 +3,15 @@ before anything touches a device, the package exports the new names and refuses 
 tests compare against (tests/link_rank_ref.py) agrees with the host MeanLinkPrediction.evaluate on the tie-free construction -- as
 does the metric assembly of the device path when it is fed the reference's counts and lists."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_header
 import link_rank_ref as ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("gnx_rank_candidates_bytes", "gnx_rank_candidates")
 FAKE = ctypes.c_void_p(4096)         # stands for a device pointer: every call below fails a check before anything would read it
 NAMES = ("auc", "avprec", "prec", "rec", "f1")
@@ -25,8 +24,7 @@ def lib():
 
 def test_header_declares_and_library_exports_the_entries():
     from gnntf import _native, sparse
-    header = open(os.path.join(ROOT, "include", "gnx.h")).read()
-    declared = set(re.findall(r"\b(gnx_[a-z_0-9]+)\s*\(", re.sub(r"/\*.*?\*/", "", header, flags=re.S)))
+    header, declared = abi_header.text(), abi_header.declared()
     handle = ctypes.CDLL(_native.LIB_PATH)
     for name in ENTRIES:
         assert name in declared and hasattr(handle, name) and name in _native.SIGNATURES

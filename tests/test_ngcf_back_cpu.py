@@ -10,9 +10,10 @@ import numpy as np
 import pytest
 import torch
 
+from abi_header import ctypes_of, prototype as header_prototype
 import ngcf_back_ref as bref
 import ngcf_fused_ref as nref
-from test_gcn_fused_cpu import CTYPES, CpuGraph, OnDevice, header_prototype, tiny_graph
+from test_gcn_fused_cpu import CpuGraph, OnDevice, tiny_graph
 from test_ngcf_fused_cpu import cpu_world, one_step, structure
 
 PROTOTYPE = ["gnx_graph_t g", "const float *d_vals_t", "const float *d_g", "int64_t ldg", "const float *d_y", "int64_t ldy", "const float *d_rnorm",
@@ -26,7 +27,7 @@ def test_header_library_and_binding_agree():
     from gnntf import _native
     assert header_prototype("gnx_step_back_ngcf") == PROTOTYPE
     assert hasattr(ctypes.CDLL(_native.LIB_PATH), "gnx_step_back_ngcf")
-    want = [ctypes.c_void_p if "*" in arg or arg.startswith("gnx_graph_t") else CTYPES[arg.rsplit(" ", 1)[0]] for arg in PROTOTYPE]
+    want = ctypes_of(PROTOTYPE)
     restype, argtypes = _native.SIGNATURES["gnx_step_back_ngcf"]
     assert restype is ctypes.c_int and argtypes == want
     assert _native.lib().gnx_version() == 900 == _native.ABI_VERSION            # added within ABI 0.9: the number stays

@@ -6,16 +6,15 @@ today's calls around the gate pass, and the bounds of tests/ngcf_fused_ref.py ad
 at most 0.1 % of the gate bits undecided."""
 import ctypes
 import functools
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from abi_header import ctypes_of, prototype as header_prototype, text as header_text
 import ngcf_fused_ref as nref
-from test_gcn_fused_cpu import CTYPES, CpuGraph, OnDevice, header_prototype, tiny_graph
+from test_gcn_fused_cpu import CpuGraph, OnDevice, tiny_graph
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 PROTOTYPES = {
     "gnx_ngcf_step": ["gnx_graph_t g", "const float *d_vals", "const float *d_X", "int64_t ldx", "int64_t C_in", "const float *d_W1", "int64_t ldw1",
@@ -32,10 +31,10 @@ PROTOTYPES = {
 def test_header_library_and_binding_agree(name):
     from gnntf import _native
     assert header_prototype(name) == PROTOTYPES[name]
-    text = open(os.path.join(ROOT, "include", "gnx.h")).read()
+    text = header_text()
     assert "gcn.py:116-135" in text and "enum { GNX_ACT_LEAKY = 2 };" in text and _native.ACT_LEAKY == 2
     assert hasattr(ctypes.CDLL(_native.LIB_PATH), name)
-    want = [ctypes.c_void_p if "*" in arg or arg.startswith("gnx_graph_t") else CTYPES[arg.rsplit(" ", 1)[0]] for arg in PROTOTYPES[name]]
+    want = ctypes_of(PROTOTYPES[name])
     restype, argtypes = _native.SIGNATURES[name]
     assert restype is ctypes.c_int and argtypes == want
     assert _native.lib().gnx_version() == 900 == _native.ABI_VERSION

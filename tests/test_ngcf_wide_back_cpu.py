@@ -10,9 +10,10 @@ import numpy as np
 import pytest
 import torch
 
+from abi_header import ctypes_of, prototype as header_prototype
 import ngcf_back_ref as bref
 import ngcf_fused_ref as nref
-from test_gcn_fused_cpu import CTYPES, CpuGraph, OnDevice, header_prototype, tiny_graph
+from test_gcn_fused_cpu import CpuGraph, OnDevice, tiny_graph
 from test_ngcf_back_cpu import PROTOTYPE, TODAY, emulated, judged
 from test_ngcf_fused_cpu import cpu_world
 from test_ngcf_wide_cpu import model_calls
@@ -27,7 +28,7 @@ def test_header_library_and_binding_agree():
     assert header_prototype(NAME) == PROTOTYPE == header_prototype("gnx_step_back_ngcf")
     assert hasattr(ctypes.CDLL(_native.LIB_PATH), NAME) and _native.has_symbol(NAME)
     assert NAME in _native.SIGNATURES and NAME in _native.PROBED
-    want = [ctypes.c_void_p if "*" in arg or arg.startswith("gnx_graph_t") else CTYPES[arg.rsplit(" ", 1)[0]] for arg in PROTOTYPE]
+    want = ctypes_of(PROTOTYPE)
     assert _native.SIGNATURES[NAME] == (ctypes.c_int, want) == _native.SIGNATURES["gnx_step_back_ngcf"]
     assert _native.lib().gnx_version() == 900 == _native.ABI_VERSION            # added within ABI 0.9: the number stays
     # (tests/test_layer_entries_cpu.py pins the names that begin with the layers' prefixes: the layer's name stands behind the verb)

@@ -11,8 +11,9 @@ import numpy as np
 import pytest
 import torch
 
+from abi_header import ctypes_of, prototype as header_prototype
 import ngcf_fused_ref as nref
-from test_gcn_fused_cpu import CTYPES, CpuGraph, OnDevice, header_prototype, tiny_graph
+from test_gcn_fused_cpu import CpuGraph, OnDevice, tiny_graph
 from test_ngcf_fused_cpu import PROTOTYPES, cpu_world, structure
 
 NAME = "gnx_step_wide_ngcf"
@@ -24,7 +25,7 @@ def test_header_library_and_binding_agree():
     from gnntf import _native
     assert header_prototype(NAME) == PROTOTYPES["gnx_ngcf_step"]
     assert hasattr(ctypes.CDLL(_native.LIB_PATH), NAME) and _native.has_symbol(NAME) and NAME in _native.PROBED
-    want = [ctypes.c_void_p if "*" in arg or arg.startswith("gnx_graph_t") else CTYPES[arg.rsplit(" ", 1)[0]] for arg in PROTOTYPES["gnx_ngcf_step"]]
+    want = ctypes_of(PROTOTYPES["gnx_ngcf_step"])
     assert _native.SIGNATURES[NAME] == (ctypes.c_int, want) == _native.SIGNATURES["gnx_ngcf_step"]
     assert _native.lib().gnx_version() == 900 == _native.ABI_VERSION            # added within ABI 0.9: the number stays
 

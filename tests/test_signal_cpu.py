@@ -2,16 +2,14 @@
 gradient formula the backward kernel implements against central differences, the header's prototypes against the bindings, the argument
 checks that run before anything touches a device, and the layer lists the two models build."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+from abi_header import ctypes_of, prototype as header_prototype
 import signal_ref as ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 PROTOTYPES = {
     "gnx_signal_project": ["const float *d_X", "int64_t ldx", "int64_t n", "int64_t C", "const float *d_w", "int act", "float *d_out",
@@ -27,7 +25,6 @@ PROTOTYPES = {
     # beyond the five of the feature's plan: FastReg's per-forward draw, from the counter RNG so that a captured step replays it
     "gnx_signal_uniform": ["gnx_graph_t g", "int64_t n", "float bound", "uint64_t seed", "uint64_t stream_id", "float *d_out", "void *stream"],
 }
-CTYPES = {"float": ctypes.c_float, "double": ctypes.c_double, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "int": ctypes.c_int}
 
 
 # ---- the gradient formula ------------------------------------------------------------------------------------------------------------------
@@ -86,20 +83,13 @@ def test_uniform_draw_is_the_default_initialiser_range():
 
 
 # ---- bindings --------------------------------------------------------------------------------------------------------------------------------
-def header_prototype(name):
-    text = open(os.path.join(ROOT, "include", "gnx.h")).read()
-    found = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-    assert found, f"include/gnx.h does not declare {name}"
-    return [" ".join(arg.split()) for arg in found.group(1).split(",")]
-
-
 @pytest.mark.parametrize("name", sorted(PROTOTYPES))
 def test_header_library_and_binding_agree(name):
     from gnntf import _native
     assert header_prototype(name) == PROTOTYPES[name]
     assert hasattr(ctypes.CDLL(_native.LIB_PATH), name) and _native.has_symbol(name) and name in _native.PROBED
     restype, argtypes = _native.SIGNATURES[name]
-    want = [ctypes.c_void_p if "*" in arg or arg.startswith("gnx_graph_t") else CTYPES[arg.rsplit(" ", 1)[0]] for arg in header_prototype(name)]
+    want = ctypes_of(header_prototype(name))
     assert restype is ctypes.c_int and argtypes == want
     fn = getattr(_native.lib(), name)
     assert fn.argtypes == want and fn.restype is ctypes.c_int
