@@ -10,6 +10,8 @@ import os
 import re
 from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_uint64, c_void_p
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 ABI_VERSION = 900         # the ABI this package's call sites are written against; include/gnx.h GNX_ABI_VERSION must equal it
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "gnx.h")
@@ -30,8 +32,9 @@ SCALARS = {"int": c_int, "int64_t": c_int64, "uint64_t": c_uint64, "float": c_fl
 
 
 def parse_header():
-    """{name: (restype, argtypes)} of every prototype HEADER_PATH declares.  Refuses instead of guessing: a header of another ABI
-    number, a scalar type outside SCALARS, or a gnx_ name followed by `(` that did not read as a prototype raises."""
+    """({name: (restype, argtypes)} of every prototype HEADER_PATH declares, the names of those whose last parameter is `void *stream`).
+    Refuses instead of guessing: a header of another ABI number, a scalar type outside SCALARS, or a gnx_ name followed by `(` that did
+    not read as a prototype raises."""
     if not os.path.exists(HEADER_PATH):
         raise Exception(f"gnntf: the header {HEADER_PATH} is missing -- the binding of libgnx.so is read from it; there is no other table")
     text = re.sub(r"/\*.*?\*/", "", open(HEADER_PATH).read(), flags=re.S)
@@ -50,20 +53,23 @@ def parse_header():
         c_type = arg.rpartition(" ")[0].removeprefix("const ")          # "int64_t ldx" -> "int64_t"
         return c_void_p if "*" in arg or c_type in handles else scalar(entry, f"parameter `{arg}`", c_type)
 
-    signatures = {}
+    signatures, streamed = {}, set()
     for ret, name, args in re.findall(r"([A-Za-z_][A-Za-z_0-9 \*]*?)\b(gnx_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", text):
         ret, args = " ".join(ret.split()), [" ".join(arg.split()) for arg in args.split(",")]
         signatures[name] = (c_char_p if ret == "const char *" else scalar(name, "the return value", ret),
                             [] if args == ["void"] else [parameter(name, arg) for arg in args])
+        if args[-1] == "void *stream":
+            streamed.add(name)
     named = set(re.findall(r"\b(gnx_[a-z_0-9]+)\s*\(", text))
     if len(signatures) != len(named):
         raise Exception(f"gnntf: {HEADER_PATH} names {len(named)} entries and {len(signatures)} read as prototypes; not read: "
                         f"{sorted(named - set(signatures))}")
-    return signatures
+    return signatures, frozenset(streamed)
 
 
-# name -> (restype, argtypes) of every symbol include/gnx.h declares, read from the header at import: nothing is typed here by hand
-SIGNATURES = parse_header()
+# name -> (restype, argtypes) of every symbol include/gnx.h declares, read from the header at import: nothing is typed here by hand;
+# STREAMED: the entries that end in `void *stream` (launch() hands them torch's current stream)
+SIGNATURES, STREAMED = parse_header()
 
 # entries added within ABI 0.9 that a library of the same minor version may lack: found by probing (has_symbol); their callers raise
 PROBED = ("gnx_step_wide_ngcf", "gnx_step_back_wide_ngcf", "gnx_step_spectral_gcn", "gnx_step_spectral_gcn_dropped", "gnx_dense_drop",
@@ -115,8 +121,44 @@ def ptr(t):
 
 def current_stream():
     """The raw hipStream_t of torch's current stream on the current device (the cheap accessor: this sits on every launch)."""
-    import torch
     return c_void_p(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
+
+
+# how launch() passes an argument on, by the parameter's declared type: the expression over the argument ``{a}``.  A pointer or handle
+# parameter takes a tensor's device pointer, and None, byref(x), ctypes arrays and handles as they are
+CONVERSIONS = {c_void_p: "{a} if {a} is None or type({a}) is c_void_p else c_void_p({a}.data_ptr()) if isinstance({a}, Tensor) else {a}",
+               c_int: "int({a})", c_int64: "int({a})", c_uint64: "int({a}) & 0xFFFFFFFFFFFFFFFF", c_float: "float({a})", c_double: "float({a})"}
+
+
+def _converter(argtypes):
+    """lambda a0, a1, ...: [every argument converted by its parameter's type]: one expression per entry, made once -- launch() sits on
+    every call of launch-bound steps, and a converter called per argument measured slower than the hand-written call sites were."""
+    names = [f"a{k}" for k in range(len(argtypes))]
+    converted = ", ".join(CONVERSIONS[t].format(a=a) for t, a in zip(argtypes, names))
+    return eval(f"lambda {', '.join(names)}: [{converted}]", {"c_void_p": c_void_p, "Tensor": torch.Tensor})
+
+
+def _call(name, argtypes):
+    given = argtypes[:-1] if name in STREAMED else argtypes
+    return len(given), name in STREAMED, _converter(given)
+
+
+# name -> (the number of arguments the caller passes: all but a closing stream, whether launch() appends the stream, their converter)
+CALLS = {name: _call(name, argtypes) for name, (_, argtypes) in SIGNATURES.items()}
+
+
+def launch(device, name, *args):
+    """One call of the entry ``name`` with ``device`` current: every argument converted by its parameter's declared type (tensor ->
+    device pointer, int / float scalars, uint64_t masked to 64 bits), torch's current stream appended where the prototype ends in
+    `void *stream`, the status checked.  The function is looked up on lib() at every call: a spy put in lib's place sees all of them."""
+    count, streamed, convert = CALLS[name]
+    if len(args) != count:
+        raise Exception(f"gnntf: {name} takes {count} arguments" + (" and the stream" if streamed else "") + f", {len(args)} given")
+    with on_device(device):
+        args = convert(*args)
+        if streamed:
+            args.append(current_stream())
+        check(getattr(lib(), name)(*args))
 
 
 class on_device:
@@ -129,7 +171,6 @@ class on_device:
         self.index = device.index
 
     def __enter__(self):
-        import torch
         self.prev = torch.cuda.current_device()
         if self.index is None:
             self.index = self.prev
@@ -138,7 +179,6 @@ class on_device:
 
     def __exit__(self, *exc):
         if self.prev != self.index:
-            import torch
             torch.cuda.set_device(self.prev)
 
 

@@ -22,21 +22,17 @@ class NativeBackend:
 
     def colsum(self, graph):
         out = torch.empty(graph.n_cols, dtype=torch.float32, device=graph.device)
-        with nat.on_device(graph.device):
-            nat.check(nat.lib().gnx_graph_colsum(graph.handle, 0.0, 0, 0, nat.ptr(out), nat.current_stream()))
+        nat.launch(graph.device, "gnx_graph_colsum", graph.handle, 0.0, 0, 0, out)
         return out
 
     def degree_scale(self, deg, normalized="symmetric"):
-        with nat.on_device(deg.device):
-            nat.check(nat.lib().gnx_degree_scale(nat.ptr(deg), deg.numel(), nat.NORM[normalized], 0, nat.current_stream()))
+        nat.launch(deg.device, "gnx_degree_scale", deg, deg.numel(), nat.NORM[normalized], 0)
         return deg
 
     def scale_values(self, graph, row_scale, col_scale):
         out = torch.empty(graph.nnz, dtype=torch.float32, device=graph.device)
         row_scale = row_scale.contiguous() if row_scale is not None else None
-        with nat.on_device(graph.device):
-            nat.check(nat.lib().gnx_graph_scale_values(graph.handle, 0.0, 0, 0, nat.ptr(row_scale), nat.ptr(col_scale),
-                                                       nat.ptr(out), nat.current_stream()))
+        nat.launch(graph.device, "gnx_graph_scale_values", graph.handle, 0.0, 0, 0, row_scale, col_scale, out)
         return out
 
     def spmm_mix(self, graph, vals, X, H0, beta, alpha, out, out_rows=None, rows=None, skip_empty=False):
@@ -78,14 +74,9 @@ class NativeBackend:
             return
         if buf.dtype != send.dtype or buf.dtype not in (torch.float32, torch.bfloat16):
             raise Exception("halo_pack: the feature buffer and the send buffer must both be f32 or both bf16 (%s, %s)" % (buf.dtype, send.dtype))
-        if buf.dtype == torch.bfloat16:               # bf16 storage: pulled rows copied as they are, pushed sums rounded once
-            with nat.on_device(buf.device):
-                nat.check(nat.lib().gnx_halo_pack_bf16(plan.handle, PARTS[part], nat.ptr(buf), buf.stride(0), buf.shape[1], nat.ptr(send),
-                                                       send.stride(0), nat.current_stream()))
-            return
-        with nat.on_device(buf.device):
-            nat.check(nat.lib().gnx_halo_pack(plan.handle, PARTS[part], nat.ptr(buf), buf.stride(0), buf.shape[1], nat.ptr(send),
-                                              send.stride(0), nat.current_stream()))
+        # (bf16 storage: pulled rows copied as they are, pushed sums rounded once)
+        nat.launch(buf.device, "gnx_halo_pack_bf16" if buf.dtype == torch.bfloat16 else "gnx_halo_pack", plan.handle, PARTS[part], buf,
+                   buf.stride(0), buf.shape[1], send, send.stride(0))
 
     def cast_bf16(self, src, dst):
         """dst = bf(src) (gnx_cast_bf16): the first iterate of a bf16 propagation, straight into the local rows of its buffer."""
@@ -94,9 +85,7 @@ class NativeBackend:
     # ---- training with edge dropout on a vertex block (raw values; weights made inside the kernels) ----------
     def set_block(self, graph, row0_global, row0_buf, col_gid):
         """Dropout draws of this block are keyed by GLOBAL (row, col) from now on (gnx_graph_set_block)."""
-        with nat.on_device(graph.device):
-            nat.check(nat.lib().gnx_graph_set_block(graph.handle, int(row0_global), int(row0_buf), nat.ptr(col_gid),
-                                                    nat.current_stream()))
+        nat.launch(graph.device, "gnx_graph_set_block", graph.handle, row0_global, row0_buf, col_gid)
 
     def enable_entry_dropout(self, graph):
         """The entry tables of a block whose COO holds duplicate entries (gnx_graph_enable_entry_dropout)."""
@@ -105,10 +94,7 @@ class NativeBackend:
     def colsum_streams(self, graph, p, seed, first_stream, n_streams):
         """[n_streams, n_cols]: this block's PARTIAL column sums of the dropped raw values, one row per dropout stream."""
         out = torch.empty((n_streams, graph.n_cols), dtype=torch.float32, device=graph.device)
-        with nat.on_device(graph.device):
-            nat.check(nat.lib().gnx_graph_colsum_streams(graph.handle, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                         int(first_stream) & 0xFFFFFFFFFFFFFFFF, int(n_streams), nat.ptr(out),
-                                                         nat.current_stream()))
+        nat.launch(graph.device, "gnx_graph_colsum_streams", graph.handle, p, seed, first_stream, n_streams, out)
         return out
 
     def spmm_dropped(self, graph, D, p, seed, stream_id, transposed, X, H0, beta, alpha, out):
@@ -120,11 +106,8 @@ class NativeBackend:
     def spmm_dropped_chained(self, graph, D, p, seed, stream_id, prescaled, D_next, X, H0, beta, alpha, out):
         """The forward spmm_dropped inside a loop: X carries its column scale when ``prescaled``; the result rows carry
         ``D_next`` (the next iteration's scale of every buffer column; row r's own entry is used) unless it is None."""
-        with nat.on_device(graph.device):
-            nat.check(nat.lib().gnx_spmm_dropped_chained(graph.handle, nat.ptr(D), float(p), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                         int(stream_id) & 0xFFFFFFFFFFFFFFFF, 1 if prescaled else 0, nat.ptr(D_next),
-                                                         nat.ptr(X), X.stride(0), X.shape[1], nat.ptr(H0), H0.stride(0), float(beta),
-                                                         float(alpha), nat.ACT_NONE, nat.ptr(out), out.stride(0), nat.current_stream()))
+        nat.launch(graph.device, "gnx_spmm_dropped_chained", graph.handle, D, p, seed, stream_id, prescaled, D_next, X, X.stride(0), X.shape[1],
+                   H0, H0.stride(0), beta, alpha, nat.ACT_NONE, out, out.stride(0))
 
     def spmm_t_mix(self, graph, X, H0, beta, alpha, out):
         """out = beta * (A^T X) + alpha * H0 over the graph's own (raw) values."""

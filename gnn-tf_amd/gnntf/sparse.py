@@ -79,10 +79,9 @@ class DeviceGraph:
                 raise Exception("DeviceGraph: CSR array lengths do not match the shape")
             self.device = rowptr.device
             self._keep = (rowptr.contiguous(), colidx.contiguous(), vals.contiguous())
-            with nat.on_device(self.device):
-                nat.check(lib.gnx_graph_create_csr(shape[0], shape[1], self._keep[1].numel(), nat.ptr(self._keep[0]),
-                                                   nat.ptr(self._keep[1]), nat.ptr(self._keep[2]), nat.current_stream(),
-                                                   byref(self._h)))
+            with nat.on_device(self.device):    # (the creators take the stream mid-list: passed here, not appended)
+                nat.launch(self.device, "gnx_graph_create_csr", shape[0], shape[1], self._keep[1].numel(), *self._keep, nat.current_stream(),
+                           byref(self._h))
             self._keep = None
         else:
             device = torch.device(device if device is not None else "cuda")
@@ -93,8 +92,7 @@ class DeviceGraph:
             val = coo.values.to(device).contiguous()
             self.device = idx.device                        # with its index ("cuda" -> "cuda:0")
             with nat.on_device(device):
-                nat.check(lib.gnx_graph_create_coo(coo.dense_shape[0], coo.dense_shape[1], idx.shape[0], nat.ptr(idx),
-                                                   nat.ptr(val), nat.current_stream(), byref(self._h)))
+                nat.launch(device, "gnx_graph_create_coo", *coo.dense_shape, idx.shape[0], idx, val, nat.current_stream(), byref(self._h))
         n_rows, n_cols, nnz_e, nnz_c = c_int64(), c_int64(), c_int64(), c_int64()
         nat.check(lib.gnx_graph_info(self._h, byref(n_rows), byref(n_cols), byref(nnz_e), byref(nnz_c)))
         self.n_rows, self.n_cols = n_rows.value, n_cols.value
@@ -133,8 +131,7 @@ class DeviceGraph:
         order (gnx_graph_enable_entry_dropout).  Edge dropout then stays per stored entry (layered.py:47-50), bit for bit what the
         materialised form gives, without writing a value array per iteration.  Allocates and synchronises: call before capturing.
         Does nothing on a graph without duplicates."""
-        with nat.on_device(self.device):
-            nat.check(nat.lib().gnx_graph_enable_entry_dropout(self._h, nat.current_stream()))
+        nat.launch(self.device, "gnx_graph_enable_entry_dropout", self._h)
         self._entry_dropout = True
 
     def csr_arrays(self, with_rows=False):
@@ -143,9 +140,7 @@ class DeviceGraph:
         colidx = torch.empty(self.nnz, dtype=torch.int32, device=self.device)
         vals = torch.empty(self.nnz, dtype=torch.float32, device=self.device)
         rows = torch.empty(self.nnz, dtype=torch.int32, device=self.device) if with_rows else None
-        with nat.on_device(self.device):
-            nat.check(nat.lib().gnx_graph_export(self._h, nat.ptr(rowptr), nat.ptr(colidx), nat.ptr(vals), nat.ptr(rows),
-                                                 nat.current_stream()))
+        nat.launch(self.device, "gnx_graph_export", self._h, rowptr, colidx, vals, rows)
         return (rowptr, colidx, vals, rows) if with_rows else (rowptr, colidx, vals)
 
     def last_kernel(self) -> str:
@@ -161,24 +156,22 @@ class DeviceGraph:
         before capturing (gnx_graph_reserve)."""
         flags = ((nat.RESERVE_TRANSPOSED if transposed else 0) | (nat.RESERVE_K_LOOP if k_loop else 0)
                  | (nat.RESERVE_TRAIN_GATHER if train_gather else 0) | (nat.RESERVE_GATHER_HINTS if gather_hints else 0))
-        with nat.on_device(self.device):
-            nat.check(nat.lib().gnx_graph_reserve(self._h, int(C), flags, nat.current_stream()))
+        nat.launch(self.device, "gnx_graph_reserve", self._h, C, flags)
 
     def gather_order(self):
         """(order, rank), int32 [n] each, copies: the handle's gather order (gnx_graph_gather_order) -- ``order[i]`` = the vertex at
         position i, ``rank`` its inverse.  ``X[order.long()]`` is X stored in gather order.  Builds the order on first use
         (allocates and synchronises: not under capture)."""
         order, rank = c_void_p(), c_void_p()
+        nat.launch(self.device, "gnx_graph_gather_order", self._h, byref(order), byref(rank))
         with nat.on_device(self.device):
-            nat.check(nat.lib().gnx_graph_gather_order(self._h, byref(order), byref(rank)))
             return tuple(torch.as_tensor(_BorrowedInt32(p.value, self.n_rows), device=self.device).clone() for p in (order, rank))
 
     def set_gather_hints(self, hot_rows=-1):
         """Gather hints of the wide float32 eval launches (gnx_graph_set_gather_hints): the ``hot_rows`` rows with the most entries
         are the ones worth keeping in the L2s; every other row is gathered with a non-temporal load.  -1 = automatic (large graphs,
         the rows that fill half an L2 at the width of the call), 0 = off, n > 0 = that many hot rows.  Same bits either way."""
-        with nat.on_device(self.device):
-            nat.check(nat.lib().gnx_graph_set_gather_hints(self._h, int(hot_rows), nat.current_stream()))
+        nat.launch(self.device, "gnx_graph_set_gather_hints", self._h, hot_rows)
 
     def gather_hints(self):
         """(hinted columns int32 [nnz] or None, hot_rows): a copy of the handle's hinted column array -- the column of every entry,
@@ -201,15 +194,14 @@ class DeviceGraph:
         """Pendant elision of appnp_propagate's K loop (gnx_graph_set_pendant_elision): a row whose one entry points at a row that
         alone points back is computed by the last iteration only; its neighbour forms the iterates between itself.  -1 = automatic
         (where the automatic gather hints are on), 0 = off, 1 = on wherever the launches take gather hints.  Same bits either way."""
-        with nat.on_device(self.device):
-            nat.check(nat.lib().gnx_graph_set_pendant_elision(self._h, int(mode), nat.current_stream()))
+        nat.launch(self.device, "gnx_graph_set_pendant_elision", self._h, mode)
 
     def pendant_elision(self):
         """(elidable rows as a bool tensor [n] or None when no plan is built, whether the last K loop elided them)
         (gnx_graph_pendant_elision)."""
         count, flags, last = c_int64(), c_void_p(), c_int()
+        nat.launch(self.device, "gnx_graph_pendant_elision", self._h, byref(count), byref(flags), byref(last))
         with nat.on_device(self.device):
-            nat.check(nat.lib().gnx_graph_pendant_elision(self._h, byref(count), byref(flags), byref(last)))
             if not flags.value:
                 return None, bool(last.value)
             torch.cuda.current_stream().synchronize()
@@ -223,8 +215,7 @@ class DeviceGraph:
         """Declares that the vertex numbering of THIS graph carries locality (a community / breadth-first order): launches take the
         rows in windows of ``window_rows`` consecutive ids (degree-binned inside a window) and narrow widths stay off the
         degree-relabelled copy; 0 = the default global degree bins (gnx_graph_set_row_window).  Same sums, other launch order."""
-        with nat.on_device(self.device):
-            nat.check(nat.lib().gnx_graph_set_row_window(self._h, int(window_rows), nat.current_stream()))
+        nat.launch(self.device, "gnx_graph_set_row_window", self._h, window_rows)
         self.row_window = int(window_rows)
 
     def set_dropout_counter(self, counter):
@@ -261,8 +252,7 @@ class Adjacency:
         """Values in transposed order, permuted once and kept (a constant adjacency is reused by every backward)."""
         if self.vals_t is None:
             out = torch.empty(self.graph.nnz, dtype=torch.float32, device=self.graph.device)
-            with nat.on_device(self.graph.device):
-                nat.check(nat.lib().gnx_graph_permute_values_t(self.graph.handle, nat.ptr(self.vals), nat.ptr(out), nat.current_stream()))
+            nat.launch(self.graph.device, "gnx_graph_permute_values_t", self.graph.handle, self.vals, out)
             self.vals_t = out
         return self.vals_t
 
@@ -308,10 +298,8 @@ def dropped_degree_scales(graph: DeviceGraph, p, seed, first_stream, n_streams) 
     """D = divide_no_nan(1, sqrt(column sums of the dropped values)) (gnn.py:41) for ``n_streams`` consecutive dropout streams,
     [n_streams, n]: ONE pass over the structure for all of them (gnx_graph_colsum_streams)."""
     D = torch.empty((n_streams, graph.n_cols), dtype=torch.float32, device=graph.device)
-    with nat.on_device(graph.device):
-        nat.check(nat.lib().gnx_graph_colsum_streams(graph.handle, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                     int(first_stream) & 0xFFFFFFFFFFFFFFFF, int(n_streams), nat.ptr(D), nat.current_stream()))
-        nat.check(nat.lib().gnx_degree_scale(nat.ptr(D), D.numel(), nat.NORM["symmetric"], 0, nat.current_stream()))
+    nat.launch(graph.device, "gnx_graph_colsum_streams", graph.handle, p, seed, first_stream, n_streams, D)
+    nat.launch(graph.device, "gnx_degree_scale", D, D.numel(), nat.NORM["symmetric"], 0)
     return D
 
 
@@ -337,10 +325,8 @@ def normalize(graph: DeviceGraph, normalized="symmetric", add_eye="none", dropou
         raise Exception("Invalid add_eye option")
     vals = torch.empty(graph.nnz, dtype=torch.float32, device=graph.device)
     diag = torch.empty(graph.n_rows, dtype=torch.float32, device=graph.device) if add_eye != "none" else None
-    fn = nat.lib().gnx_graph_normalize_t if transposed_only else nat.lib().gnx_graph_normalize
-    with nat.on_device(graph.device):
-        nat.check(fn(graph.handle, nat.NORM[normalized], nat.EYE[add_eye], float(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                     int(stream_id) & 0xFFFFFFFFFFFFFFFF, nat.ptr(vals), nat.ptr(diag), nat.current_stream()))
+    nat.launch(graph.device, "gnx_graph_normalize_t" if transposed_only else "gnx_graph_normalize", graph.handle, nat.NORM[normalized],
+               nat.EYE[add_eye], dropout, seed, stream_id, vals, diag)
     adj = Adjacency(graph, None, diag, vals_t=vals) if transposed_only else Adjacency(graph, vals, diag)
     adj.transposed_only = bool(transposed_only)
     if normalized == "none" and add_eye == "none":
@@ -406,44 +392,45 @@ def _mix_operand(H0, shape, bias=False):
     return H0, H0.stride(0)
 
 
+def _spmm_buffers(X, H0, rows_in, rows_out, out, new, bf16_out=False):
+    """What _launch and _launch_bf16 check alike once ``X`` is in its stored format: (C, out, H0, ldh0) for ``rows_in`` gathered and
+    ``rows_out`` result rows.  ``out`` None: a new tensor of dtype ``new``; else f32 rows of unit column stride -- with ``bf16_out`` f32 or
+    bf16 rows whose leading dimension holds a row."""
+    if X.shape[0] != rows_in:
+        raise Exception(f"spmm: features have {X.shape[0]} rows, adjacency expects {rows_in}")
+    C = X.shape[1]
+    if out is None:
+        out = torch.empty((rows_out, C), dtype=new, device=X.device)
+    elif (tuple(out.shape) != (rows_out, C) or not (out.dtype == torch.float32 or (bf16_out and out.dtype == torch.bfloat16))
+            or out.stride(1) != 1 or (bf16_out and out.stride(0) < C) or not out.is_cuda):
+        raise Exception("spmm: bad output buffer")
+    return (C, out) + _mix_operand(H0, (rows_out, C), bias=True)
+
+
 def _launch(adj: Adjacency, X, H0, beta, alpha, act, transposed=False, out=None, out_rows=None):
     g = adj.graph
     nat.require_cuda(X, H0)
     _same_device(g, X, H0, out, out_rows, adj.diag)
     X = _as_f32_rows(X)
-    rows_in = g.n_rows if transposed else g.n_cols
-    rows_out = g.n_cols if transposed else g.n_rows
-    if X.shape[0] != rows_in:
-        raise Exception(f"spmm: features have {X.shape[0]} rows, adjacency expects {rows_in}")
-    C = X.shape[1]
-    if out is None:
-        out = torch.empty((rows_out, C), dtype=torch.float32, device=X.device)
-    elif (tuple(out.shape) != (rows_out, C) or out.dtype != torch.float32 or out.stride(1) != 1 or not out.is_cuda):
-        raise Exception("spmm: bad output buffer")
-    H0, ldh0 = _mix_operand(H0, (rows_out, C), bias=True)
+    rows_in, rows_out = (g.n_rows, g.n_cols) if transposed else (g.n_cols, g.n_rows)
+    C, out, H0, ldh0 = _spmm_buffers(X, H0, rows_in, rows_out, out, torch.float32)
     if isinstance(adj, DroppedAdjacency) and out_rows is None:       # weights produced inside the kernel
-        with nat.on_device(X.device):
-            nat.check(nat.lib().gnx_spmm_dropped(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, 1 if transposed else 0,
-                                                 nat.ptr(X), X.stride(0), C, nat.ptr(H0), ldh0, float(beta), float(alpha), int(act),
-                                                 nat.ptr(out), out.stride(0), nat.current_stream()))
+        nat.launch(X.device, "gnx_spmm_dropped", g.handle, adj.D, adj.p, adj.seed, adj.stream_id, transposed, X, X.stride(0), C, H0, ldh0,
+                   beta, alpha, act, out, out.stride(0))
         return out
     if transposed:
-        fn, values = nat.lib().gnx_spmm_tv, adj.transposed_values()
+        entry, values = "gnx_spmm_tv", adj.transposed_values()
     else:
         if adj.vals is None and adj.vals_t is not None:
             raise Exception("spmm: this adjacency only holds transposed-order values")
-        fn, values = nat.lib().gnx_spmm, adj.vals
-    with nat.on_device(X.device):
-        if out_rows is not None:                                # result row i -> out[out_rows[i]]
-            if transposed or out_rows.dtype != torch.int32 or out_rows.numel() != rows_out or not out_rows.is_cuda:
-                raise Exception("spmm: bad output row map")
-            nat.check(nat.lib().gnx_spmm_scatter(g.handle, nat.ptr(values), nat.ptr(adj.diag), nat.ptr(X), X.stride(0), C, nat.ptr(H0),
-                                                 ldh0, float(beta), float(alpha), int(act), nat.ptr(out_rows), nat.ptr(out),
-                                                 out.stride(0), nat.current_stream()))
-        else:
-            nat.check(fn(g.handle, nat.ptr(values), nat.ptr(adj.diag), nat.ptr(X), X.stride(0), C, nat.ptr(H0),
-                         ldh0, float(beta), float(alpha), int(act), nat.ptr(out), out.stride(0),
-                         nat.current_stream()))
+        entry, values = "gnx_spmm", adj.vals
+    if out_rows is not None:                                    # result row i -> out[out_rows[i]]
+        if transposed or out_rows.dtype != torch.int32 or out_rows.numel() != rows_out or not out_rows.is_cuda:
+            raise Exception("spmm: bad output row map")
+        nat.launch(X.device, "gnx_spmm_scatter", g.handle, values, adj.diag, X, X.stride(0), C, H0, ldh0, beta, alpha, act, out_rows, out,
+                   out.stride(0))
+    else:
+        nat.launch(X.device, entry, g.handle, values, adj.diag, X, X.stride(0), C, H0, ldh0, beta, alpha, act, out, out.stride(0))
     return out
 
 
@@ -466,17 +453,14 @@ def _launch_chained(adj: "DroppedAdjacency", X, H0, beta, alpha, prescaled, D_ne
     if bf16 and order is not None:
         raise Exception("chained bf16 propagation: bf16 rows have no gather-order entry")
     out = torch.empty((g.n_rows, C), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=X.device)
-    lib = nat.lib()
     if bf16:
-        fn, tail = lib.gnx_spmm_dropped_chained_bf16, (1 if out_bf16 else 0, out.stride(0))
+        entry, tail = "gnx_spmm_dropped_chained_bf16", (out_bf16, out.stride(0))
     elif order is not None:
-        fn, tail = lib.gnx_spmm_dropped_chained_ord, (out.stride(0), int(order))
+        entry, tail = "gnx_spmm_dropped_chained_ord", (out.stride(0), order)
     else:
-        fn, tail = lib.gnx_spmm_dropped_chained, (out.stride(0),)
-    with nat.on_device(X.device):
-        nat.check(fn(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, 1 if prescaled else 0, nat.ptr(D_next), nat.ptr(X), X.stride(0), C,
-                     nat.ptr(H0), H0.stride(0), float(beta), float(alpha), nat.ACT_NONE | (nat.ACT_SKIP_EMPTY if skip_empty else 0),
-                     nat.ptr(out), *tail, nat.current_stream()))
+        entry, tail = "gnx_spmm_dropped_chained", (out.stride(0),)
+    nat.launch(X.device, entry, g.handle, adj.D, adj.p, adj.seed, adj.stream_id, prescaled, D_next, X, X.stride(0), C, H0, H0.stride(0), beta,
+               alpha, nat.ACT_NONE | (nat.ACT_SKIP_EMPTY if skip_empty else 0), out, *tail)
     return out
 
 
@@ -498,13 +482,10 @@ def _launch_back(adj: "DroppedAdjacency", X, prescaled, D_next, S_in, s_alpha, s
         raise Exception("chained bf16 backward: bad operands" if bf16 else "chained backward: bad operand shapes")
     if bf16 and order is not None:
         raise Exception("chained bf16 backward: bf16 rows have no gather-order entry")
-    lib = nat.lib()
-    fn = lib.gnx_spmm_dropped_back_bf16 if bf16 else lib.gnx_spmm_dropped_back_ord if order is not None else lib.gnx_spmm_dropped_back
-    tail = () if order is None else (int(order),)
-    with nat.on_device(X.device):
-        nat.check(fn(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, 1 if prescaled else 0, nat.ptr(D_next), nat.ptr(X), C, C,
-                     nat.ptr(S_in), C, float(s_alpha), float(s_beta), nat.ptr(S_out), C, float(y_beta), nat.ptr(Y_out), C,
-                     nat.ACT_SKIP_EMPTY if skip_empty else nat.ACT_NONE, *tail, nat.current_stream()))
+    entry = "gnx_spmm_dropped_back_bf16" if bf16 else "gnx_spmm_dropped_back_ord" if order is not None else "gnx_spmm_dropped_back"
+    tail = () if order is None else (order,)
+    nat.launch(X.device, entry, g.handle, adj.D, adj.p, adj.seed, adj.stream_id, prescaled, D_next, X, C, C, S_in, C, s_alpha, s_beta, S_out, C,
+               y_beta, Y_out, C, nat.ACT_SKIP_EMPTY if skip_empty else nat.ACT_NONE, *tail)
 
 
 _launch_chained_bf16 = _launch_chained     # (the dtype of X picks the entry)
@@ -561,26 +542,43 @@ def _backward_chained_bf16(adjs, g, a):
     return _backward_chained(adjs, g, a, bf16=True)
 
 
-def launch_rows(adj: Adjacency, X, H0, beta, alpha, rows, out, act=nat.ACT_NONE):
-    """The fused step over a graph that holds a SUBSET of the output rows (the interior or the boundary rows of
-    a vertex block): result row r is written to out[rows[r]] and mixes in H0[rows[r]] (gnx_spmm_rows)."""
+def _launch_rows(bf16, adj: Adjacency, X, H0, beta, alpha, rows, out, act):
+    """gnx_spmm_rows over f32 rows ``X`` (anything else is widened) into an f32 ``out``, or with ``bf16`` gnx_spmm_rows_bf16 over bf16
+    rows into an f32 or bf16 ``out`` of a leading dimension that holds a row: the checks and the call."""
     g = adj.graph
     nat.require_cuda(X, H0, rows, out)
     _same_device(g, X, H0, rows, out)
-    X = _as_f32_rows(X)
+    if not bf16:
+        X = _as_f32_rows(X)
+    elif X.dim() != 2 or X.dtype != torch.bfloat16 or X.stride(1) != 1 or X.stride(0) < X.shape[1]:
+        raise Exception("spmm: the bf16 row launch takes a bf16 feature matrix with unit column stride")
     if X.shape[0] != g.n_cols:
         raise Exception(f"spmm: features have {X.shape[0]} rows, adjacency expects {g.n_cols}")
     C = X.shape[1]
     if rows.dtype != torch.int32 or rows.numel() != g.n_rows or not rows.is_contiguous():
         raise Exception("spmm: bad row map")
-    if out.dtype != torch.float32 or out.dim() != 2 or out.shape[1] != C or out.stride(1) != 1:
+    if (out.dtype not in ((torch.float32, torch.bfloat16) if bf16 else (torch.float32,)) or out.dim() != 2 or out.shape[1] != C
+            or out.stride(1) != 1 or (bf16 and out.stride(0) < C)):
         raise Exception("spmm: bad output buffer")
     H0, ldh0 = _mix_operand(H0, out.shape)
-    with nat.on_device(X.device):
-        nat.check(nat.lib().gnx_spmm_rows(g.handle, nat.ptr(adj.vals), nat.ptr(X), X.stride(0), C, nat.ptr(H0), ldh0, float(beta),
-                                          float(alpha), int(act), nat.ptr(rows), nat.ptr(out), out.stride(0),
-                                          nat.current_stream()))
+    layer = (g.handle, adj.vals, X, X.stride(0), C, H0, ldh0, beta, alpha, act, rows, out)
+    if bf16:
+        nat.launch(X.device, "gnx_spmm_rows_bf16", *layer, out.dtype == torch.bfloat16, out.stride(0))
+    else:
+        nat.launch(X.device, "gnx_spmm_rows", *layer, out.stride(0))
     return out
+
+
+def launch_rows(adj: Adjacency, X, H0, beta, alpha, rows, out, act=nat.ACT_NONE):
+    """The fused step over a graph that holds a SUBSET of the output rows (the interior or the boundary rows of
+    a vertex block): result row r is written to out[rows[r]] and mixes in H0[rows[r]] (gnx_spmm_rows)."""
+    return _launch_rows(False, adj, X, H0, beta, alpha, rows, out, act)
+
+
+def launch_rows_bf16(adj: Adjacency, X, H0, beta, alpha, rows, out, act=nat.ACT_NONE):
+    """launch_rows with the gathered rows X stored as bf16 (gnx_spmm_rows_bf16): result row r is written to out[rows[r]] -- f32, or
+    rounded once when ``out`` is bf16 -- and mixes in the f32 H0[rows[r]]."""
+    return _launch_rows(True, adj, X, H0, beta, alpha, rows, out, act)
 
 
 class _SpMM(torch.autograd.Function):
@@ -790,8 +788,7 @@ def linear_combination(terms) -> torch.Tensor:
     k = len(tensors)
     ptrs = (c_void_p * k)(*[t.data_ptr() for t in tensors])
     coefs = (c_float * k)(*[float(c) for _, c in terms])
-    with nat.on_device(first.device):
-        nat.check(nat.lib().gnx_linear_combination(k, ptrs, coefs, first.numel(), nat.ptr(out), nat.current_stream()))
+    nat.launch(first.device, "gnx_linear_combination", k, ptrs, coefs, first.numel(), out)
     return out
 
 
@@ -927,16 +924,21 @@ def appnp_propagate(adj: Adjacency, H0: torch.Tensor, a: float = 0.1, iterations
     H0 = _as_f32_rows(H0).contiguous()
     if g.n_rows != g.n_cols or H0.shape[0] != g.n_rows:
         raise Exception("appnp_propagate: needs a square graph matching H0")
+    return _appnp_launch(_bf16(storage) and not (H0.shape[1] < BF16_MIN_WIDTH and g.n_rows >= BF16_F32_ROWS), adj, H0, a, iterations, relu)
+
+
+def _appnp_launch(bf16, adj: Adjacency, H0, a, iterations, relu):
+    """gnx_appnp_propagate_act, or with ``bf16`` gnx_appnp_propagate_bf16 (H0: f32 contiguous [n, C]), at the line-friendly width of the
+    stored rows: the padding, the result, the ping-pong buffers (one f32 from two iterations on; two bf16 iterates) and the call."""
     C = H0.shape[1]
-    if _bf16(storage) and not (C < BF16_MIN_WIDTH and g.n_rows >= BF16_F32_ROWS):
-        return _appnp_propagate_bf16(adj, H0, a, iterations, relu)
-    H0 = _padded(H0, friendly_width(C, H0.shape[0]))
+    H0 = _padded(H0, (friendly_width_bf16 if bf16 else friendly_width)(C, H0.shape[0]))
     out = torch.empty_like(H0)
-    work = torch.empty_like(H0) if iterations > 1 else None
-    with nat.on_device(H0.device):
-        nat.check(nat.lib().gnx_appnp_propagate_act(g.handle, nat.ptr(adj.vals), nat.ptr(adj.diag), nat.ptr(H0), float(a),
-                                                    int(iterations), H0.shape[1], nat.ACT_RELU if relu else nat.ACT_NONE,
-                                                    nat.ptr(out), nat.ptr(work), nat.current_stream()))
+    if bf16:
+        work = torch.empty((2,) + tuple(H0.shape), dtype=torch.bfloat16, device=H0.device) if iterations > 0 else None
+    else:
+        work = torch.empty_like(H0) if iterations > 1 else None
+    nat.launch(H0.device, "gnx_appnp_propagate_bf16" if bf16 else "gnx_appnp_propagate_act", adj.graph.handle, adj.vals, adj.diag, H0, a,
+               iterations, H0.shape[1], nat.ACT_RELU if relu else nat.ACT_NONE, out, work)
     return _unpadded(out, C)
 
 
@@ -982,11 +984,13 @@ def to_bf16(X: torch.Tensor) -> torch.Tensor:
     """bf(X) on the device (gnx_cast_bf16: round to nearest even, NaN stays NaN), [n, C] contiguous bf16."""
     nat.require_cuda(X)
     X = _as_f32_rows(X)
-    out = torch.empty(X.shape, dtype=torch.bfloat16, device=X.device)
-    with nat.on_device(X.device):
-        nat.check(nat.lib().gnx_cast_bf16(nat.ptr(X), X.shape[0], X.shape[1], X.stride(0), nat.ptr(out), X.shape[1],
-                                          nat.current_stream()))
-    return out
+    return _cast_bf16(X, torch.empty(X.shape, dtype=torch.bfloat16, device=X.device))
+
+
+def _cast_bf16(X, dst):
+    """The call of gnx_cast_bf16: f32 rows ``X`` into the bf16 rows ``dst`` of the same shape."""
+    nat.launch(X.device, "gnx_cast_bf16", X, X.shape[0], X.shape[1], X.stride(0), dst, dst.stride(0))
+    return dst
 
 
 def _launch_bf16(adj: Adjacency, X, H0, beta, alpha, act, out_bf16=False, out=None):
@@ -994,31 +998,18 @@ def _launch_bf16(adj: Adjacency, X, H0, beta, alpha, act, out_bf16=False, out=No
     bf16 rows, any leading dimension; its dtype decides the rounding)."""
     g = adj.graph
     nat.require_cuda(X, H0)
-    _same_device(g, X, H0, adj.diag)
+    _same_device(g, X, H0, adj.diag, out)
     if X.dim() != 2:
         raise Exception("propagation expects a 2-D feature matrix")
     if X.dtype == torch.bfloat16:
         Xb = X if X.stride(1) == 1 and X.stride(0) >= X.shape[1] else X.contiguous()
     else:
         Xb = to_bf16(X)
-    if Xb.shape[0] != g.n_cols:
-        raise Exception(f"spmm: features have {Xb.shape[0]} rows, adjacency expects {g.n_cols}")
-    if adj.vals is None and adj.vals_t is not None:
+    if adj.vals is None and adj.vals_t is not None and Xb.shape[0] == g.n_cols:
         raise Exception("spmm: this adjacency only holds transposed-order values")
-    C = Xb.shape[1]
-    if out is None:
-        out = torch.empty((g.n_rows, C), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=Xb.device)
-    else:
-        _same_device(g, out)
-        if (tuple(out.shape) != (g.n_rows, C) or out.dtype not in (torch.float32, torch.bfloat16) or out.stride(1) != 1
-                or out.stride(0) < C or not out.is_cuda):
-            raise Exception("spmm: bad output buffer")
-        out_bf16 = out.dtype == torch.bfloat16
-    H0, ldh0 = _mix_operand(H0, (g.n_rows, C), bias=True)
-    with nat.on_device(Xb.device):
-        nat.check(nat.lib().gnx_spmm_bf16(g.handle, nat.ptr(adj.vals), nat.ptr(adj.diag), nat.ptr(Xb), Xb.stride(0), C, nat.ptr(H0),
-                                          ldh0, float(beta), float(alpha), int(act), nat.ptr(out), 1 if out_bf16 else 0, out.stride(0),
-                                          nat.current_stream()))
+    C, out, H0, ldh0 = _spmm_buffers(Xb, H0, g.n_cols, g.n_rows, out, torch.bfloat16 if out_bf16 else torch.float32, bf16_out=True)
+    nat.launch(Xb.device, "gnx_spmm_bf16", g.handle, adj.vals, adj.diag, Xb, Xb.stride(0), C, H0, ldh0, beta, alpha, act, out,
+               out.dtype == torch.bfloat16, out.stride(0))
     return out
 
 
@@ -1029,48 +1020,12 @@ def cast_bf16_into(X: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
     X = _as_f32_rows(X)
     if dst.dtype != torch.bfloat16 or tuple(dst.shape) != tuple(X.shape) or dst.stride(1) != 1 or dst.stride(0) < dst.shape[1] or dst.device != X.device:
         raise Exception("cast_bf16_into: bad destination")
-    if X.shape[0] and X.shape[1]:
-        with nat.on_device(X.device):
-            nat.check(nat.lib().gnx_cast_bf16(nat.ptr(X), X.shape[0], X.shape[1], X.stride(0), nat.ptr(dst), dst.stride(0),
-                                              nat.current_stream()))
-    return dst
-
-
-def launch_rows_bf16(adj: Adjacency, X, H0, beta, alpha, rows, out, act=nat.ACT_NONE):
-    """launch_rows with the gathered rows X stored as bf16 (gnx_spmm_rows_bf16): result row r is written to out[rows[r]] -- f32, or
-    rounded once when ``out`` is bf16 -- and mixes in the f32 H0[rows[r]]."""
-    g = adj.graph
-    nat.require_cuda(X, H0, rows, out)
-    _same_device(g, X, H0, rows, out)
-    if X.dim() != 2 or X.dtype != torch.bfloat16 or X.stride(1) != 1 or X.stride(0) < X.shape[1]:
-        raise Exception("spmm: the bf16 row launch takes a bf16 feature matrix with unit column stride")
-    if X.shape[0] != g.n_cols:
-        raise Exception(f"spmm: features have {X.shape[0]} rows, adjacency expects {g.n_cols}")
-    C = X.shape[1]
-    if rows.dtype != torch.int32 or rows.numel() != g.n_rows or not rows.is_contiguous():
-        raise Exception("spmm: bad row map")
-    if out.dtype not in (torch.float32, torch.bfloat16) or out.dim() != 2 or out.shape[1] != C or out.stride(1) != 1 or out.stride(0) < C:
-        raise Exception("spmm: bad output buffer")
-    H0, ldh0 = _mix_operand(H0, out.shape)
-    with nat.on_device(X.device):
-        nat.check(nat.lib().gnx_spmm_rows_bf16(g.handle, nat.ptr(adj.vals), nat.ptr(X), X.stride(0), C, nat.ptr(H0), ldh0, float(beta),
-                                               float(alpha), int(act), nat.ptr(rows), nat.ptr(out),
-                                               1 if out.dtype == torch.bfloat16 else 0, out.stride(0), nat.current_stream()))
-    return out
+    return _cast_bf16(X, dst) if X.shape[0] and X.shape[1] else dst
 
 
 def _appnp_propagate_bf16(adj: Adjacency, H0: torch.Tensor, a, iterations, relu):
-    """appnp_propagate on gnx_appnp_propagate_bf16 (H0: f32 contiguous [n, C]), at the bf16 line-friendly width."""
-    g = adj.graph
-    C = H0.shape[1]
-    H0 = _padded(H0, friendly_width_bf16(C, H0.shape[0]))
-    out = torch.empty_like(H0)
-    work = torch.empty((2,) + tuple(H0.shape), dtype=torch.bfloat16, device=H0.device) if iterations > 0 else None
-    with nat.on_device(H0.device):
-        nat.check(nat.lib().gnx_appnp_propagate_bf16(g.handle, nat.ptr(adj.vals), nat.ptr(adj.diag), nat.ptr(H0), float(a),
-                                                     int(iterations), H0.shape[1], nat.ACT_RELU if relu else nat.ACT_NONE,
-                                                     nat.ptr(out), nat.ptr(work), nat.current_stream()))
-    return _unpadded(out, C)
+    """appnp_propagate on gnx_appnp_propagate_bf16 (H0: f32 contiguous [n, C]) at every width: no f32 allowance."""
+    return _appnp_launch(True, adj, H0, a, iterations, relu)
 
 
 def gather_rows(X: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
@@ -1079,9 +1034,7 @@ def gather_rows(X: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     X = _as_f32_rows(X)
     idx = idx.to(torch.int64).contiguous()
     out = torch.empty((idx.numel(), X.shape[1]), dtype=torch.float32, device=X.device)
-    with nat.on_device(X.device):
-        nat.check(nat.lib().gnx_gather_rows(nat.ptr(X), X.stride(0), nat.ptr(idx), idx.numel(), X.shape[1], nat.ptr(out),
-                                            out.stride(0), nat.current_stream()))
+    nat.launch(X.device, "gnx_gather_rows", X, X.stride(0), idx, idx.numel(), X.shape[1], out, out.stride(0))
     return out
 
 
@@ -1093,9 +1046,8 @@ def _dense_launch(X, W, bias, relu):
         raise Exception(f"dense: features have {X.shape[1]} columns, the weights expect {W.shape[0]}")
     out = torch.empty((X.shape[0], W.shape[1]), dtype=torch.float32, device=X.device)
     b = _bias_row("dense", bias, W.shape[1])
-    with nat.on_device(X.device):
-        nat.check(nat.lib().gnx_dense(nat.ptr(X), X.stride(0), X.shape[0], X.shape[1], nat.ptr(W), W.stride(0), W.shape[1], nat.ptr(b),
-                                      nat.ACT_RELU if relu else nat.ACT_NONE, nat.ptr(out), out.stride(0), nat.current_stream()))
+    nat.launch(X.device, "gnx_dense", X, X.stride(0), X.shape[0], X.shape[1], W, W.stride(0), W.shape[1], b, nat.ACT_RELU if relu else nat.ACT_NONE,
+               out, out.stride(0))
     return out
 
 
@@ -1117,15 +1069,13 @@ def _dense_wgrad_launch(entry, X, G, graph=(), din=()):
     O = G.shape[1]
     work = torch.empty(_wgrad_slabs(n, F * O) * F * O, dtype=torch.float32, device=X.device)
     dW = torch.empty((F, O), dtype=torch.float32, device=X.device)
-    with nat.on_device(X.device):
-        nat.check(entry(*graph, nat.ptr(X), X.stride(0), nat.ptr(G), G.stride(0), n, F, O, *din, nat.ptr(dW), nat.ptr(work), work.numel(),
-                        nat.current_stream()))
+    nat.launch(X.device, entry, *graph, X, X.stride(0), G, G.stride(0), n, F, O, *din, dW, work, work.numel())
     return dW
 
 
 def _dense_wgrad(X, G):
     """dW = X^T . G on the matrix cores (gnx_dense_wgrad): row slabs, partial sums added in a fixed order."""
-    return _dense_wgrad_launch(nat.lib().gnx_dense_wgrad, _as_f32_rows(X), _as_f32_rows(G))
+    return _dense_wgrad_launch("gnx_dense_wgrad", _as_f32_rows(X), _as_f32_rows(G))
 
 
 class _DenseAct(torch.autograd.Function):
@@ -1185,9 +1135,7 @@ def _feature_dropout_launch(graph: DeviceGraph, X, p, seed, stream, rows=None, o
     n = X.shape[0] if rows is None else rows.numel()
     if X.shape[1] == 0:
         return out
-    with nat.on_device(X.device):
-        nat.check(nat.lib().gnx_feature_dropout(graph.handle, nat.ptr(X), X.stride(0), n, X.shape[1], nat.ptr(rows), float(p), seed, stream,
-                                                nat.ptr(out), out.stride(0), nat.current_stream()))
+    nat.launch(X.device, "gnx_feature_dropout", graph.handle, X, X.stride(0), n, X.shape[1], rows, p, seed, stream, out, out.stride(0))
     return out
 
 
@@ -1209,13 +1157,12 @@ def _gate_launch(graph: DeviceGraph, g, y, p, seed, stream, relu, bf16, padded=F
     if g.numel() == 0:
         return G, Gb
     y = y if relu else None
-    args = (graph.handle, nat.ptr(g), g.stride(0), nat.ptr(y), 0 if y is None else y.stride(0), g.shape[0], g.shape[1], float(p), seed, stream,
-            nat.ACT_RELU if relu else nat.ACT_NONE, nat.ptr(G), G.stride(0))
-    with nat.on_device(g.device):
-        if bf16:
-            nat.check(nat.lib().gnx_feature_dropout_back_bf16(*args, nat.ptr(Gb), Gb.stride(0), nat.current_stream()))
-        else:
-            nat.check(nat.lib().gnx_feature_dropout_back(*args, nat.current_stream()))
+    args = (graph.handle, g, g.stride(0), y, 0 if y is None else y.stride(0), g.shape[0], g.shape[1], p, seed, stream,
+            nat.ACT_RELU if relu else nat.ACT_NONE, G, G.stride(0))
+    if bf16:
+        nat.launch(g.device, "gnx_feature_dropout_back_bf16", *args, Gb, Gb.stride(0))
+    else:
+        nat.launch(g.device, "gnx_feature_dropout_back", *args)
     return G, Gb
 
 
@@ -1274,10 +1221,8 @@ def _dense_drop_launch(graph: DeviceGraph, X, W, bias, relu, din, dout):
         raise Exception(f"dense_step: features have {X.shape[1]} columns, the weights expect {W.shape[0]}")
     out = torch.empty((X.shape[0], W.shape[1]), dtype=torch.float32, device=X.device)
     b = _bias_row("dense_step", bias, W.shape[1])
-    with nat.on_device(X.device):
-        nat.check(nat.lib().gnx_dense_drop(graph.handle, nat.ptr(X), X.stride(0), X.shape[0], X.shape[1], nat.ptr(W), W.stride(0), W.shape[1],
-                                           nat.ptr(b), nat.ACT_RELU if relu else nat.ACT_NONE, *_dropout_args(din), *_dropout_args(dout),
-                                           nat.ptr(out), out.stride(0), nat.current_stream()))
+    nat.launch(X.device, "gnx_dense_drop", graph.handle, X, X.stride(0), X.shape[0], X.shape[1], W, W.stride(0), W.shape[1], b,
+               nat.ACT_RELU if relu else nat.ACT_NONE, *_dropout_args(din), *_dropout_args(dout), out, out.stride(0))
     return out
 
 
@@ -1289,7 +1234,7 @@ def _dense_wgrad_drop(graph: DeviceGraph, X, G, din):
     _need_symbol("dense_step", "gnx_dense_wgrad_drop")
     X, G = _as_f32_rows(X), _as_f32_rows(G)
     _same_device(graph, X, G)
-    return _dense_wgrad_launch(nat.lib().gnx_dense_wgrad_drop, X, G, (graph.handle,), din)
+    return _dense_wgrad_launch("gnx_dense_wgrad_drop", X, G, (graph.handle,), din)
 
 
 class _DenseStep(torch.autograd.Function):
@@ -1386,17 +1331,14 @@ def _gcnii_launch(adj: Adjacency, H, H0, a, M, relu, keep_mixed, dropout=None, f
     act = nat.ACT_RELU if relu else nat.ACT_NONE
     if fused_edge:
         _same_device(g, adj.D)
-        with nat.on_device(H.device):
-            nat.check(nat.lib().gnx_gcnii_step_dropped(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, nat.ptr(H), nat.ptr(H0), float(a), C,
-                                                       nat.ptr(M), M.stride(0), act, *_dropout_args(dropout), nat.ptr(out), nat.ptr(mixed),
-                                                       nat.current_stream()))
+        nat.launch(H.device, "gnx_gcnii_step_dropped", g.handle, adj.D, adj.p, adj.seed, adj.stream_id, H, H0, a, C, M, M.stride(0), act,
+                   *_dropout_args(dropout), out, mixed)
         return out, mixed
-    layer = (g.handle, nat.ptr(adj.vals), nat.ptr(H), nat.ptr(H0), float(a), C, nat.ptr(M), M.stride(0), act)
-    with nat.on_device(H.device):
-        if dropout is not None:
-            nat.check(nat.lib().gnx_gcnii_step_drop(*layer, *dropout, nat.ptr(out), nat.ptr(mixed), nat.current_stream()))
-        else:
-            nat.check(nat.lib().gnx_gcnii_step(*layer, nat.ptr(out), nat.ptr(mixed), nat.current_stream()))
+    layer = (g.handle, adj.vals, H, H0, a, C, M, M.stride(0), act)
+    if dropout is not None:
+        nat.launch(H.device, "gnx_gcnii_step_drop", *layer, *dropout, out, mixed)
+    else:
+        nat.launch(H.device, "gnx_gcnii_step", *layer, out, mixed)
     return out, mixed
 
 
@@ -1435,10 +1377,8 @@ def gcnii_wgrad(adj: Adjacency, H: torch.Tensor, H0: torch.Tensor, a: float, G: 
         hub_rows = torch.empty((n, C), dtype=torch.float32, device=H.device)
     work = torch.empty(_wgrad_slabs(n, C * C) * C * C, dtype=torch.float32, device=H.device)
     dM = torch.empty((C, C), dtype=torch.float32, device=H.device)
-    entry = nat.lib().gnx_gcnii_wgrad_bf16 if bf16 else nat.lib().gnx_gcnii_wgrad
-    with nat.on_device(H.device):
-        nat.check(entry(g.handle, nat.ptr(adj.vals), nat.ptr(H), nat.ptr(H0), float(a), C, nat.ptr(G), nat.ptr(dM), nat.ptr(hub_rows),
-                        nat.ptr(work), work.numel(), nat.current_stream()))
+    nat.launch(H.device, "gnx_gcnii_wgrad_bf16" if bf16 else "gnx_gcnii_wgrad", g.handle, adj.vals, H, H0, a, C, G, dM, hub_rows, work,
+               work.numel())
     return dM
 
 
@@ -1477,19 +1417,14 @@ def _gcnii_back_launch(bf16, adj, X, G, a, Mt, S_in, s_alpha, want_S, in_place, 
     work = torch.empty_like(dH) if not bf16 and C not in (16, 32, 64) else None
     if fused_edge:      # (f32 rows: gnx_gcnii_step_back_dropped makes the transposed weights itself; no value array is written)
         _same_device(g, adj.D)
-        with nat.on_device(X.device):
-            nat.check(nat.lib().gnx_gcnii_step_back_dropped(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, nat.ptr(X), float(a), C,
-                                                            nat.ptr(Mt), Mt.stride(0), nat.ptr(dH), nat.ptr(S_in), float(s_alpha), nat.ptr(S),
-                                                            nat.ptr(work), nat.current_stream()))
+        nat.launch(X.device, "gnx_gcnii_step_back_dropped", g.handle, adj.D, adj.p, adj.seed, adj.stream_id, X, a, C, Mt, Mt.stride(0), dH, S_in,
+                   s_alpha, S, work)
         return dH, S
     values = adj.transposed_values()
-    with nat.on_device(X.device):
-        if bf16:
-            nat.check(nat.lib().gnx_gcnii_step_back_bf16(g.handle, nat.ptr(values), nat.ptr(X), nat.ptr(G), float(a), C, nat.ptr(Mt), Mt.stride(0),
-                                                         nat.ptr(dH), nat.ptr(S_in), float(s_alpha), nat.ptr(S), None, nat.current_stream()))
-        else:
-            nat.check(nat.lib().gnx_gcnii_step_back(g.handle, nat.ptr(values), nat.ptr(X), float(a), C, nat.ptr(Mt), Mt.stride(0), nat.ptr(dH),
-                                                    nat.ptr(S_in), float(s_alpha), nat.ptr(S), nat.ptr(work), nat.current_stream()))
+    if bf16:
+        nat.launch(X.device, "gnx_gcnii_step_back_bf16", g.handle, values, X, G, a, C, Mt, Mt.stride(0), dH, S_in, s_alpha, S, None)
+    else:
+        nat.launch(X.device, "gnx_gcnii_step_back", g.handle, values, X, a, C, Mt, Mt.stride(0), dH, S_in, s_alpha, S, work)
     return dH, S
 
 
@@ -1622,20 +1557,18 @@ def _gcn_launch(adj: Adjacency, X, W, bias, relu, keep_agg, dropout=None, fused_
     rows = torch.empty((n, C_in), dtype=torch.float32, device=X.device) if keep_agg or not one_launch or g.n_hub_rows > 0 else None
     agg, work = (rows, None) if keep_agg else (None, rows)
     p, seed, stream = _dropout_args(dropout)
-    layer = (nat.ptr(X), X.stride(0), C_in, nat.ptr(W), W.stride(0), C_out, nat.ptr(b), nat.ACT_RELU if relu else nat.ACT_NONE, p, seed, stream,
-             nat.ptr(out), out.stride(0), nat.ptr(agg))
+    layer = (X, X.stride(0), C_in, W, W.stride(0), C_out, b, nat.ACT_RELU if relu else nat.ACT_NONE, p, seed, stream, out, out.stride(0), agg)
     if spectral:
         _need_symbol("gcn_step_spectral", "gnx_step_spectral_gcn_dropped" if fused_edge else "gnx_step_spectral_gcn")
         gate = torch.empty((n, _gate_words(C_out)), dtype=torch.int32, device=X.device) if keep_agg and relu else None
-        layer = layer + (nat.ptr(gate),)
-        plain, dropped = nat.lib().gnx_step_spectral_gcn, nat.lib().gnx_step_spectral_gcn_dropped
+        layer = layer + (gate,)
+        plain, dropped = "gnx_step_spectral_gcn", "gnx_step_spectral_gcn_dropped"
     else:
-        plain, dropped = nat.lib().gnx_gcn_step, nat.lib().gnx_gcn_step_dropped
-    with nat.on_device(X.device):
-        if fused_edge:
-            nat.check(dropped(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, *layer, nat.ptr(work), nat.current_stream()))
-        else:
-            nat.check(plain(g.handle, nat.ptr(adj.vals), *layer, nat.ptr(work), nat.current_stream()))
+        plain, dropped = "gnx_gcn_step", "gnx_gcn_step_dropped"
+    if fused_edge:
+        nat.launch(X.device, dropped, g.handle, adj.D, adj.p, adj.seed, adj.stream_id, *layer, work)
+    else:
+        nat.launch(X.device, plain, g.handle, adj.vals, *layer, work)
     return (out, agg, gate) if spectral else (out, agg)
 
 
@@ -1749,13 +1682,11 @@ def _gcn_back_launch(adj: Adjacency, G, Wt, fused_edge=False):
         work = torch.empty((n, C_out), dtype=torch.float32, device=G.device)
     else:
         work = None
-    tail = (nat.ptr(G), G.stride(0), C_out, nat.ptr(Wt), _row_stride(Wt), C_in, nat.ptr(dX), dX.stride(0), nat.ptr(work),
-            0 if work is None else work.numel(), nat.current_stream())
-    with nat.on_device(G.device):
-        if fused_edge:
-            nat.check(nat.lib().gnx_gcn_step_back_dropped(g.handle, nat.ptr(adj.D), adj.p, adj.seed, adj.stream_id, *tail))
-        else:
-            nat.check(nat.lib().gnx_gcn_step_back(g.handle, nat.ptr(adj.transposed_values()), *tail))
+    tail = (G, G.stride(0), C_out, Wt, _row_stride(Wt), C_in, dX, dX.stride(0), work, 0 if work is None else work.numel())
+    if fused_edge:
+        nat.launch(G.device, "gnx_gcn_step_back_dropped", g.handle, adj.D, adj.p, adj.seed, adj.stream_id, *tail)
+    else:
+        nat.launch(G.device, "gnx_gcn_step_back", g.handle, adj.transposed_values(), *tail)
     return dX
 
 
@@ -1911,12 +1842,9 @@ def _ngcf_launch(adj: Adjacency, X, W1, b1, W2, b2, activation, keep, dropout=No
         floats = _ngcf_work_floats(n, C_in, C_out, g.n_hub_rows if one_launch else n, keep)
     work = torch.empty(floats, dtype=torch.float32, device=X.device) if floats else None
     p, seed, stream = _dropout_args(dropout)
-    with nat.on_device(X.device):
-        entry = nat.lib().gnx_step_wide_ngcf if rows_launch else nat.lib().gnx_ngcf_step
-        nat.check(entry(g.handle, nat.ptr(adj.vals), nat.ptr(X), X.stride(0), C_in, nat.ptr(W1), _row_stride(W1), nat.ptr(W2),
-                        _row_stride(W2), C_out, nat.ptr(biases[0]), nat.ptr(biases[1]), NGCF_ACTIVATIONS[activation], p, seed, stream,
-                        1 if normalize else 0, nat.ptr(out), out.stride(0), nat.ptr(agg), nat.ptr(gate), nat.ptr(rnorm),
-                        nat.ptr(work), floats, nat.current_stream()))
+    nat.launch(X.device, "gnx_step_wide_ngcf" if rows_launch else "gnx_ngcf_step", g.handle, adj.vals, X, X.stride(0), C_in, W1, _row_stride(W1),
+               W2, _row_stride(W2), C_out, biases[0], biases[1], NGCF_ACTIVATIONS[activation], p, seed, stream, normalize, out, out.stride(0),
+               agg, gate, rnorm, work, floats)
     return out, agg, gate, rnorm
 
 
@@ -1931,10 +1859,8 @@ def _ngcf_back_gate(graph: DeviceGraph, g, y, rnorm, gate, activation, dropout=N
     y = None if rnorm is None else _as_f32_rows(y)
     G1, G2 = _padded_rows(n, C, g.device), _padded_rows(n, C, g.device)
     p, seed, stream = _dropout_args(dropout)
-    with nat.on_device(g.device):
-        nat.check(nat.lib().gnx_ngcf_back_gate(graph.handle, nat.ptr(g), g.stride(0), nat.ptr(y), 0 if y is None else y.stride(0), nat.ptr(rnorm),
-                                               nat.ptr(gate) if activation != "none" else None, n, C, NGCF_ACTIVATIONS[activation], p, seed, stream,
-                                               nat.ptr(G1), nat.ptr(G2), G1.stride(0), nat.current_stream()))
+    nat.launch(g.device, "gnx_ngcf_back_gate", graph.handle, g, g.stride(0), y, 0 if y is None else y.stride(0), rnorm,
+               gate if activation != "none" else None, n, C, NGCF_ACTIVATIONS[activation], p, seed, stream, G1, G2, G1.stride(0))
     return G1, G2
 
 
@@ -1975,12 +1901,9 @@ def _ngcf_back_launch(adj: Adjacency, g, y, rnorm, gate, activation, dropout, X,
     floats = work_floats(n, C_out) if any(want_db) else 0
     work = new(floats) if floats else None
     p, seed, stream = _dropout_args(dropout)
-    with nat.on_device(g.device):
-        nat.check(getattr(nat.lib(), entry)(
-            graph.handle, nat.ptr(adj.transposed_values()) if want_dX else None, nat.ptr(g), g.stride(0), nat.ptr(y), 0 if y is None else y.stride(0),
-            nat.ptr(rnorm), nat.ptr(gate) if activation != "none" else None, C_out, NGCF_ACTIVATIONS[activation], p, seed, stream, nat.ptr(X),
-            X.stride(0), nat.ptr(A), C_in, nat.ptr(W1), _row_stride(W1), nat.ptr(W2), _row_stride(W2), nat.ptr(G1), nat.ptr(G2), G1.stride(0),
-            nat.ptr(P), nat.ptr(db1), nat.ptr(db2), nat.ptr(dA), nat.ptr(R), nat.ptr(dX), C_in, nat.ptr(work), floats, nat.current_stream()))
+    nat.launch(g.device, entry, graph.handle, adj.transposed_values() if want_dX else None, g, g.stride(0), y, 0 if y is None else y.stride(0),
+               rnorm, gate if activation != "none" else None, C_out, NGCF_ACTIVATIONS[activation], p, seed, stream, X, X.stride(0), A, C_in,
+               W1, _row_stride(W1), W2, _row_stride(W2), G1, G2, G1.stride(0), P, db1, db2, dA, R, dX, C_in, work, floats)
     return dict(G1=G1, G2=G2, P=P, db1=db1, db2=db2, dA=dA, R=R, dX=dX)
 
 
@@ -2138,10 +2061,8 @@ def _gcnii_spectral_launch(adj: Adjacency, H, H0, a, M, bias, relu, keep, dropou
     mixed = torch.empty_like(H) if keep or C not in GCNII_FUSED_WIDTHS else None
     gate = torch.empty((H.shape[0], _gate_words(C)), dtype=torch.int32, device=H.device) if keep and relu else None
     p, seed, stream = _dropout_args(dropout)
-    with nat.on_device(H.device):
-        nat.check(nat.lib().gnx_gcnii_step_spectral(g.handle, nat.ptr(adj.vals), nat.ptr(H), nat.ptr(H0), float(a), C, nat.ptr(M), M.stride(0),
-                                                    nat.ptr(b), nat.ACT_RELU if relu else nat.ACT_NONE, p, seed, stream, nat.ptr(out),
-                                                    nat.ptr(mixed), nat.ptr(gate), nat.current_stream()))
+    nat.launch(H.device, "gnx_gcnii_step_spectral", g.handle, adj.vals, H, H0, a, C, M, M.stride(0), b, nat.ACT_RELU if relu else nat.ACT_NONE,
+               p, seed, stream, out, mixed, gate)
     return out, mixed if keep else None, gate
 
 
@@ -2162,11 +2083,8 @@ def _gcnii_spectral_gate(graph: DeviceGraph, g, gate, relu, dropout=None, padded
     slabs = max(1, min(2048, (n + 255) // 256))                      # include/gnx.h: a function of n alone
     work = torch.empty(slabs * C, dtype=torch.float32, device=g.device) if relu else None
     p, seed, stream = _dropout_args(dropout)
-    with nat.on_device(g.device):
-        nat.check(nat.lib().gnx_gcnii_spectral_back(graph.handle, nat.ptr(g), g.stride(0), nat.ptr(gate) if relu else None, n, C,
-                                                    nat.ACT_RELU if relu else nat.ACT_NONE, p, seed, stream, nat.ptr(G), G.stride(0),
-                                                    nat.ptr(dbias), nat.ptr(work), 0 if work is None else work.numel(),
-                                                    nat.current_stream()))
+    nat.launch(g.device, "gnx_gcnii_spectral_back", graph.handle, g, g.stride(0), gate if relu else None, n, C,
+               nat.ACT_RELU if relu else nat.ACT_NONE, p, seed, stream, G, G.stride(0), dbias, work, 0 if work is None else work.numel())
     return G, dbias
 
 
@@ -2312,10 +2230,8 @@ def _gcnii_launch_bf16(adj: Adjacency, H, H0, a, M, relu, out_bf16, out=None, wo
     if out.dtype != want or tuple(out.shape) != tuple(Hb.shape) or not out.is_contiguous() or work.dtype != torch.float32 \
             or tuple(work.shape) != tuple(Hb.shape) or not work.is_contiguous() or out.device != Hb.device or work.device != Hb.device:
         raise Exception("gcnii_step: bad output / work buffer")
-    with nat.on_device(Hb.device):
-        nat.check(nat.lib().gnx_gcnii_step_bf16(g.handle, nat.ptr(adj.vals), nat.ptr(Hb), nat.ptr(H0), float(a), C, nat.ptr(M),
-                                                M.stride(0), nat.ACT_RELU if relu else nat.ACT_NONE, nat.ptr(out), 1 if out_bf16 else 0,
-                                                nat.ptr(work), nat.current_stream()))
+    nat.launch(Hb.device, "gnx_gcnii_step_bf16", g.handle, adj.vals, Hb, H0, a, C, M, M.stride(0), nat.ACT_RELU if relu else nat.ACT_NONE, out,
+               out_bf16, work)
     return out
 
 
@@ -2371,13 +2287,11 @@ def gcnii_step_train_bf16(adj: Adjacency, Hb: torch.Tensor, H0: torch.Tensor, a:
     T = torch.empty(Hb.shape, dtype=torch.float32, device=Hb.device) if keep_mixed else None
     if work is None and (keep_mixed or g.n_hub_rows > 0):
         work = torch.empty(Hb.shape, dtype=torch.float32, device=Hb.device)
-    layer = (g.handle, nat.ptr(adj.vals), nat.ptr(Hb), nat.ptr(H0), float(a), C, nat.ptr(M), M.stride(0), nat.ACT_RELU if relu else nat.ACT_NONE,
-             p, seed, stream, nat.ptr(out), 1 if out_bf16 else 0)
-    with nat.on_device(Hb.device):
-        if keep_mixed:
-            nat.check(nat.lib().gnx_gcnii_step_train_bf16(*layer, nat.ptr(T), nat.ptr(work), nat.current_stream()))
-        else:
-            nat.check(nat.lib().gnx_gcnii_step_drop_bf16(*layer, nat.ptr(work), nat.current_stream()))
+    layer = (g.handle, adj.vals, Hb, H0, a, C, M, M.stride(0), nat.ACT_RELU if relu else nat.ACT_NONE, p, seed, stream, out, out_bf16)
+    if keep_mixed:
+        nat.launch(Hb.device, "gnx_gcnii_step_train_bf16", *layer, T, work)
+    else:
+        nat.launch(Hb.device, "gnx_gcnii_step_drop_bf16", *layer, work)
     return out, T
 
 
@@ -2524,9 +2438,7 @@ class _NodeCE(torch.autograd.Function):
         m = nodes.numel()
         per_node = torch.empty(m + 256, dtype=torch.float32, device=logits.device)       # + scratch of the two-level mean
         mean = torch.empty(1, dtype=torch.float32, device=logits.device)
-        with nat.on_device(logits.device):
-            nat.check(nat.lib().gnx_node_ce(nat.ptr(logits), logits.stride(0), logits.shape[0], logits.shape[1], nat.ptr(nodes),
-                                            nat.ptr(labels), m, nat.ptr(per_node), nat.ptr(mean), nat.current_stream()))
+        nat.launch(logits.device, "gnx_node_ce", logits, logits.stride(0), logits.shape[0], logits.shape[1], nodes, labels, m, per_node, mean)
         ctx.save_for_backward(logits, nodes, labels)
         return mean.reshape(())
 
@@ -2535,10 +2447,8 @@ class _NodeCE(torch.autograd.Function):
         logits, nodes, labels = ctx.saved_tensors
         grad = torch.zeros((logits.shape[0], logits.shape[1]), dtype=torch.float32, device=logits.device)
         g = g.to(torch.float32).reshape(1).contiguous()
-        with nat.on_device(logits.device):
-            nat.check(nat.lib().gnx_node_ce_backward(nat.ptr(logits), logits.stride(0), logits.shape[0], logits.shape[1], nat.ptr(nodes),
-                                                     nat.ptr(labels), nodes.numel(), nat.ptr(g), nat.ptr(grad), grad.stride(0),
-                                                     nat.current_stream()))
+        nat.launch(logits.device, "gnx_node_ce_backward", logits, logits.stride(0), logits.shape[0], logits.shape[1], nodes, labels, nodes.numel(),
+                   g, grad, grad.stride(0))
         return grad, None, None
 
 
@@ -2560,9 +2470,7 @@ def node_argmax(logits: torch.Tensor, nodes=None) -> torch.Tensor:
     idx = None if nodes is None else _as_index(nodes, logits.device, logits.shape[0], "node id")
     m = logits.shape[0] if idx is None else idx.numel()
     out = torch.empty(m, dtype=torch.int64, device=logits.device)
-    with nat.on_device(logits.device):
-        nat.check(nat.lib().gnx_node_argmax(nat.ptr(logits), logits.stride(0), logits.shape[0], logits.shape[1], nat.ptr(idx), m,
-                                            nat.ptr(out), nat.current_stream()))
+    nat.launch(logits.device, "gnx_node_argmax", logits, logits.stride(0), logits.shape[0], logits.shape[1], idx, m, out)
     return out
 
 
@@ -2629,9 +2537,7 @@ class _EdgeScores(torch.autograd.Function):
         F = _as_f32_rows(F)
         rr = None if r is None else r.to(torch.float32).reshape(-1).contiguous()
         out = torch.empty(edges.shape[0], dtype=torch.float32, device=F.device)
-        with nat.on_device(F.device):
-            nat.check(nat.lib().gnx_edge_scores(nat.ptr(F), F.stride(0), F.shape[0], F.shape[1], nat.ptr(edges), edges.shape[0], nat.ptr(rr),
-                                                nat.ptr(out), nat.current_stream()))
+        nat.launch(F.device, "gnx_edge_scores", F, F.stride(0), F.shape[0], F.shape[1], edges, edges.shape[0], rr, out)
         ctx.save_for_backward(F, edges, rr)
         ctx.r_shape = None if r is None else tuple(r.shape)
         return out
@@ -2643,9 +2549,7 @@ class _EdgeScores(torch.autograd.Function):
         gF = gr = None
         if ctx.needs_input_grad[0]:
             gF = torch.zeros((F.shape[0], F.shape[1]), dtype=torch.float32, device=F.device)
-            with nat.on_device(F.device):
-                nat.check(nat.lib().gnx_edge_scores_backward(nat.ptr(F), F.stride(0), F.shape[0], F.shape[1], nat.ptr(edges), edges.shape[0], nat.ptr(rr),
-                                                             nat.ptr(g), nat.ptr(gF), gF.stride(0), nat.current_stream()))
+            nat.launch(F.device, "gnx_edge_scores_backward", F, F.stride(0), F.shape[0], F.shape[1], edges, edges.shape[0], rr, g, gF, gF.stride(0))
         if rr is not None and ctx.needs_input_grad[2]:
             gr = (g[:, None] * F[edges[:, 0]] * F[edges[:, 1]]).sum(0).reshape(ctx.r_shape)
         return gF, None, gr
@@ -2663,15 +2567,13 @@ class EdgePlan:
         self.keys = torch.empty(2 * m, dtype=torch.int32, device=edges.device)              # uint32 in the library
         self.pos = torch.empty(2 * m, dtype=torch.int32, device=edges.device)
         self.chunks = torch.empty(2 * m + 1, dtype=torch.int32, device=edges.device)
-        with nat.on_device(edges.device):
-            if m not in EdgePlan._bytes:
-                EdgePlan._bytes[m] = int(nat.lib().gnx_edge_plan_bytes(m))
-                if EdgePlan._bytes[m] < 0:
-                    del EdgePlan._bytes[m]
-                    nat.check(-1)
-            workspace = torch.empty(max(EdgePlan._bytes[m], 16), dtype=torch.uint8, device=edges.device)
-            nat.check(nat.lib().gnx_edge_plan(nat.ptr(edges), m, self.n_rows, nat.ptr(self.keys), nat.ptr(self.pos), nat.ptr(self.chunks),
-                                              nat.ptr(workspace), workspace.numel(), nat.current_stream()))
+        if m not in EdgePlan._bytes:
+            EdgePlan._bytes[m] = int(nat.lib().gnx_edge_plan_bytes(m))
+            if EdgePlan._bytes[m] < 0:
+                del EdgePlan._bytes[m]
+                nat.check(-1)
+        workspace = torch.empty(max(EdgePlan._bytes[m], 16), dtype=torch.uint8, device=edges.device)
+        nat.launch(edges.device, "gnx_edge_plan", edges, m, self.n_rows, self.keys, self.pos, self.chunks, workspace, workspace.numel())
 
 
 def _edge_plan_of(index, edges: torch.Tensor, n_rows: int) -> EdgePlan:
@@ -2701,12 +2603,9 @@ class _EdgeScoresSorted(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             m, C, plan = edges.shape[0], F.shape[1], ctx.plan
             gF = torch.zeros((F.shape[0], C), dtype=torch.float32, device=F.device)
-            with nat.on_device(F.device):
-                floats = int(nat.lib().gnx_edge_sorted_work_floats(m, C))
-                work = torch.empty(max(floats, 4), dtype=torch.float32, device=F.device)
-                nat.check(nat.lib().gnx_edge_scores_backward_sorted(
-                    nat.ptr(F), F.stride(0), F.shape[0], C, nat.ptr(edges), m, nat.ptr(rr), nat.ptr(g), nat.ptr(gF), gF.stride(0),
-                    nat.ptr(plan.keys), nat.ptr(plan.pos), nat.ptr(plan.chunks), nat.ptr(work), work.numel(), nat.current_stream()))
+            work = torch.empty(max(int(nat.lib().gnx_edge_sorted_work_floats(m, C)), 4), dtype=torch.float32, device=F.device)
+            nat.launch(F.device, "gnx_edge_scores_backward_sorted", F, F.stride(0), F.shape[0], C, edges, m, rr, g, gF, gF.stride(0), plan.keys,
+                       plan.pos, plan.chunks, work, work.numel())
         if rr is not None and ctx.needs_input_grad[2]:
             gr = (g[:, None] * F[edges[:, 0]] * F[edges[:, 1]]).sum(0).reshape(ctx.r_shape)
         return gF, None, gr, None
@@ -2746,11 +2645,8 @@ def sample_negatives(graph: DeviceGraph, positives: torch.Tensor, samples, candi
     if fallbacks is None:
         fallbacks = torch.zeros(1, dtype=torch.int64, device=positives.device)
     _same_device(graph, positives, candidates, out, fallbacks)
-    with nat.on_device(graph.device):
-        nat.check(nat.lib().gnx_sample_negatives(graph.handle, nat.ptr(positives), m, samples, nat.ptr(candidates),
-                                                 graph.n_rows if candidates is None else candidates.numel(), int(max_tries),
-                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFFFFFFFFFF, nat.ptr(out),
-                                                 nat.ptr(fallbacks), nat.current_stream()))
+    nat.launch(graph.device, "gnx_sample_negatives", graph.handle, positives, m, samples, candidates,
+               graph.n_rows if candidates is None else candidates.numel(), max_tries, seed, stream, out, fallbacks)
     return out
 
 
@@ -2793,16 +2689,12 @@ def rank_candidates(graph: DeviceGraph, F: torch.Tensor, sources, positives, can
     top_scores = torch.empty((S, k), dtype=torch.float32, device=device)
     top_is_pos = torch.empty((S, k), dtype=torch.uint8, device=device)
     raw = torch.full((S, K), float("nan"), dtype=torch.float32, device=device) if scores else None
-    with nat.on_device(device):
-        nbytes = int(nat.lib().gnx_rank_candidates_bytes(S, ids.numel(), K, k, int(splits)))
-        if nbytes < 0:
-            nat.check(-1)
-        workspace = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-        nat.check(nat.lib().gnx_rank_candidates(
-            graph.handle, nat.ptr(F), F.stride(0), F.shape[0], F.shape[1], nat.ptr(rr), nat.ptr(sources), S, nat.ptr(ptr), nat.ptr(ids),
-            ids.numel(), nat.ptr(candidates), K, k, int(splits), nat.ptr(counts[0]), nat.ptr(counts[1]), nat.ptr(counts[2]),
-            nat.ptr(counts[3]), nat.ptr(top_ids), nat.ptr(top_scores), nat.ptr(top_is_pos), nat.ptr(raw), nat.ptr(workspace),
-            workspace.numel(), nat.current_stream()))
+    nbytes = int(nat.lib().gnx_rank_candidates_bytes(S, ids.numel(), K, k, int(splits)))
+    if nbytes < 0:
+        nat.check(-1)
+    workspace = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+    nat.launch(device, "gnx_rank_candidates", graph.handle, F, F.stride(0), F.shape[0], F.shape[1], rr, sources, S, ptr, ids, ids.numel(),
+               candidates, K, k, splits, *counts, top_ids, top_scores, top_is_pos, raw, workspace, workspace.numel())
     return RankResult(counts[0], counts[1], counts[2], counts[3], top_ids, top_scores, top_is_pos, raw)
 
 
@@ -2844,9 +2736,7 @@ def signal_project(X: torch.Tensor, w: torch.Tensor, sigmoid=True) -> torch.Tens
     if w.numel() != X.shape[1] or w.device != X.device:
         raise Exception("signal_project: w must hold one weight per column of X, on X's device")
     out = torch.empty(X.shape[0], dtype=torch.float32, device=X.device)
-    with nat.on_device(X.device):
-        nat.check(nat.lib().gnx_signal_project(nat.ptr(X), X.stride(0), X.shape[0], X.shape[1], nat.ptr(w), 1 if sigmoid else 0, nat.ptr(out),
-                                               nat.current_stream()))
+    nat.launch(X.device, "gnx_signal_project", X, X.stride(0), X.shape[0], X.shape[1], w, sigmoid, out)
     return out
 
 
@@ -2859,9 +2749,7 @@ def signal_spmv(adj: Adjacency, x: torch.Tensor, h0=None, beta=1.0, alpha=0.0, t
     x = _signal_vector("signal_spmv", g, x, n_in, "x")
     h0 = _signal_vector("signal_spmv", g, h0, n_out, "h0")
     out = torch.empty(n_out, dtype=torch.float32, device=g.device)
-    with nat.on_device(g.device):
-        nat.check(nat.lib().gnx_signal_spmv(g.handle, nat.ptr(vals), 1 if transposed else 0, nat.ptr(x), nat.ptr(h0), float(beta), float(alpha),
-                                            nat.ptr(out), nat.current_stream()))
+    nat.launch(g.device, "gnx_signal_spmv", g.handle, vals, transposed, x, h0, beta, alpha, out)
     return out
 
 
@@ -2874,9 +2762,7 @@ def signal_ppr(adj: Adjacency, h0=None, a: float = 0.1, iterations: int = 10) ->
     h0 = _signal_vector("signal_ppr", g, h0, g.n_rows, "h0")
     out = torch.empty(g.n_rows, dtype=torch.float32, device=g.device)
     work = torch.empty(g.n_rows, dtype=torch.float32, device=g.device)
-    with nat.on_device(g.device):
-        nat.check(nat.lib().gnx_signal_ppr(g.handle, nat.ptr(vals), nat.ptr(h0), float(a), int(iterations), nat.ptr(out), nat.ptr(work),
-                                           nat.current_stream()))
+    nat.launch(g.device, "gnx_signal_ppr", g.handle, vals, h0, a, iterations, out, work)
     return out
 
 
@@ -2909,9 +2795,7 @@ def signal_colsum(adj: Adjacency) -> torch.Tensor:
     if triple is None:
         return signal_spmv(adj, torch.ones(g.n_rows, dtype=torch.float32, device=g.device), None, 1.0, 0.0, transposed=True)
     D = torch.empty(g.n_cols, dtype=torch.float32, device=g.device)
-    with nat.on_device(g.device):
-        nat.check(nat.lib().gnx_graph_colsum(g.handle, float(triple[0]), int(triple[1]) & 0xFFFFFFFFFFFFFFFF, int(triple[2]) & 0xFFFFFFFFFFFFFFFF,
-                                             nat.ptr(D), nat.current_stream()))
+    nat.launch(g.device, "gnx_graph_colsum", g.handle, *triple, D)
     return D
 
 
@@ -2933,9 +2817,7 @@ class _Smoothness(torch.autograd.Function):
         d = torch.empty(n, dtype=torch.float32, device=g.device)
         sums = torch.empty(3, dtype=torch.float32, device=g.device)
         work = torch.empty(smoothness_work_floats(n), dtype=torch.float32, device=g.device)
-        with nat.on_device(g.device):
-            nat.check(nat.lib().gnx_signal_smoothness(g.handle, nat.ptr(vals), nat.ptr(f), nat.ptr(colsum), nat.ptr(d), nat.ptr(sums),
-                                                      nat.ptr(work), nat.current_stream()))
+        nat.launch(g.device, "gnx_signal_smoothness", g.handle, vals, f, colsum, d, sums, work)
         ctx.adj, ctx.colsum = adj, colsum
         ctx.save_for_backward(X, w, f, d, sums)
         return sums[2].clone()
@@ -2946,9 +2828,7 @@ class _Smoothness(torch.autograd.Function):
         g, vals_t = _signal_adjacency("smoothness", ctx.adj, transposed=True)
         upstream = upstream.detach().to(torch.float32).reshape(1).contiguous()
         gz = torch.empty(g.n_rows, dtype=torch.float32, device=g.device)
-        with nat.on_device(g.device):
-            nat.check(nat.lib().gnx_signal_smoothness_back(g.handle, nat.ptr(vals_t), nat.ptr(f), nat.ptr(d), nat.ptr(ctx.colsum), nat.ptr(sums),
-                                                           nat.ptr(upstream), nat.ptr(gz), nat.current_stream()))
+        nat.launch(g.device, "gnx_signal_smoothness_back", g.handle, vals_t, f, d, ctx.colsum, sums, upstream, gz)
         dX = gz[:, None] * w.detach().reshape(1, -1) if ctx.needs_input_grad[0] else None
         dw = _dense_wgrad(X.detach(), gz[:, None]).reshape(w.shape) if ctx.needs_input_grad[1] else None
         return dX, dw, None, None
@@ -2990,7 +2870,5 @@ def signal_uniform(graph: DeviceGraph, n: int, bound: float, seed, stream) -> to
     and -- the handle's dropout counter is added to the stream on the device -- fresh on every replay of a captured step."""
     _need_symbol("signal_uniform", "gnx_signal_uniform")
     out = torch.empty(int(n), dtype=torch.float32, device=graph.device)
-    with nat.on_device(graph.device):
-        nat.check(nat.lib().gnx_signal_uniform(graph.handle, int(n), float(bound), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFFFFFFFFFF,
-                                               nat.ptr(out), nat.current_stream()))
+    nat.launch(graph.device, "gnx_signal_uniform", graph.handle, n, bound, seed, stream, out)
     return out
